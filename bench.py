@@ -2,7 +2,12 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json): wavefront path tracing of a sparse voxel
 octree at 1920x1080, 64 spp (4 steps of 16 spp), reported as Mrays/s (primary + secondary rays).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid-res R] [--scene dragon|rtcamp|cave|tunnel]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid-res R] [--scene dragon|rtcamp|cave|tunnel] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line; `--full` adds what goes beyond the headline figure: the
+roofline pass and the CPU baseline (below) and, for N > 1, the check that every rank finds its pixels in the assembled frame (`gather_ok`).
+`--dump-outputs DIR` writes what the timed path returned after its last step as DIR/<name>.npy (the frame buffer of the path tracer;
+the arrays of the other modes), from inputs that are the same on every run with the same arguments.
 
 N > 1 without a launcher (`python bench.py --gpus N`): bench.py starts its own ranks -- `python -m torch.distributed.run --nproc-per-node N
 bench.py ...` as a child process, before this process imports torch or the library -- and relays rank 0's line.  Under an explicit
@@ -19,7 +24,7 @@ starts; K steps (+ gather for N > 1) between barrier + device synchronize on bot
 The K steps are rendered as 64-spp FRAMES (4 steps each; the metric's unit of work): clear, 4 steps, gather, device synchronise -- so
 `value` is the 64-spp figure whatever K the driver asks for (longer runs do not amortise a frame's latency floor).
 
-The JSON line also carries
+With --full the JSON line also carries (a plain run reports both as null)
   roofline     -- traversal kernel (kPtTraceStream): algorithmic bytes per launch / mean launch time, measured in an extra
                   NON-OVERLAPPED pass after the timed region (pipeline depth 1, one step per pass: HIP events on the one stream
                   every kernel runs on, so kernel times cannot overlap), against the 8 TB/s HBM peak;
@@ -40,6 +45,27 @@ sys.path.insert(0, ROOT)
 RANDOM_LINE_CEILING_GBS = 3200.0  # measured on the box: 50 G random 64-byte lines per second (tools/calib/gather_rate.hip)
 STREAM_READ_CEILING_GBS = 6100.0  # measured on the box: tools/calib/stream_read.hip, 8-32 GiB buffers (profiles/r02_stream_read.txt); SURVEY.md 8d's second denominator
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s peak (6.29 TB/s measured copy)
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy, floats and small integers as float32, wider integers as float64 (exact).  Above
+    DUMP_BUDGET_BYTES in all, the same fixed, seeded sample of rows is kept of every array, and its row indices go to DIR/sample_rows.npy."""
+    def wide(a):
+        return (a.dtype.kind in "iu" and a.dtype.itemsize > 2) or a.dtype == np.float64
+    arrays = {k: np.ascontiguousarray(v, np.float64 if wide(v) else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    headers = 1024 * (len(arrays) + 1)
+    if total + headers > DUMP_BUDGET_BYTES:
+        n = len(next(iter(arrays.values())))
+        assert all(len(a) == n for a in arrays.values()), "a sampled dump needs arrays of one length"
+        keep = int((DUMP_BUDGET_BYTES - headers) // (total / n + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def stress(args, mv):
@@ -73,6 +99,8 @@ def stress(args, mv):
     el = time.perf_counter() - tt
     desc = de.to_host().astype(np.uint64)
     hits = int((t.to_host() != mv.MAX_FLOAT).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"t": t.to_host(), "n_major": nm.to_host(), "v_index": vi.to_host(), "descents": desc})
     algo = n_rays * 40 + int(desc.sum()) * 8 + hits * 8
     # what the dependent pointer chase really moves: one brick (16 bytes of a 64-byte line) per two descents; sibling bricks share lines, so the
     # lines actually fetched are fewer -- taken from the committed counter passes (fabric read requests per ray) when they are there
@@ -144,6 +172,8 @@ def cpu_primary(args):
             r = sc.render_primary(cam, W, H, threads=th)
         out[label] = W * H * args.steps / (time.perf_counter() - t0) / 1e6
     hits = int((r["t"] != O.MAX_FLOAT).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rgba": r["rgba"], "t": r["t"], "n_major": r["nMajor"], "v_index": r["vIndex"], "descents": r["descents"]})
     print(json.dumps({
         "metric": "Mrays/sec (primary) at %dx%d, CPU IntersectorOctree path" % (W, H), "value": round(out["all"], 3), "unit": "Mrays/s", "n_gpus": 0, "steps": args.steps,
         "warmup": 1, "ms_per_step": round(W * H / out["all"] / 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "bunny.obj (tests/golden/bunny_tris.f32)",
@@ -212,6 +242,10 @@ def main():
                     help="pt = wavefront path tracer (headline); primary = the render kernel of voxRTGPU (config 2); stress = config 5; cpu-primary = config 1 (CPU only)")
     ap.add_argument("--emulate-tiles", type=int, default=0, help="diagnostic: render only tile 0 of N on one GPU (predicts per-rank time of an N-GPU run)")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the frame the CPU baseline renders (0 = auto)")
+    ap.add_argument("--full", action="store_true", help="also what goes beyond the headline figure: the non-overlapped pass the roofline comes from, "
+                    "the CPU baseline (each still switched off by --no-serial-pass / --no-cpu-baseline) and, N > 1, the gather check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step "
+                    "as DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed, seeded sample of rows beyond that)")
     args = ap.parse_args()
     if args.mode == "cpu-primary":
         return cpu_primary(args)
@@ -296,6 +330,8 @@ def main():
             svo.render_device(cam, W, H, True, rgba_dev)
         barrier_sync()
         el = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"rgba": rgba_dev.to_host()})
         print(json.dumps({"metric": "Mrays/sec (primary) at %dx%d" % (W, H), "value": round(W * H * args.steps / el / 1e6, 2), "unit": "Mrays/s", "n_gpus": 1, "steps": args.steps,
                           "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
                           "data": "synthetic", "config": {"workload": "%s stand-in %d^3 SVO, primary-ray cast with voxel colours (render kernel), %dx%d" % (args.scene, args.grid_res, W, H),
@@ -342,16 +378,24 @@ def main():
         barrier_sync()
         return time.perf_counter() - t0, pt.stats()
 
+    def frame_outputs():
+        """--dump-outputs: what a caller receives after the last timed step -- the frame buffer (accumulated RGB + sample weight per pixel;
+        N > 1: the assembled frame, on rank 0; an emulated tile share: that tile's pixels)"""
+        if not args.dump_outputs or rank != 0:
+            return None
+        return {"framebuffer": frame.cpu().numpy().reshape(-1, 4) if dist is not None else pt.read_framebuffer()}
+
     # ---- warmup, then the timed region: EXACTLY K steps (pipelined / batched as the library does by default) ----
-    elapsed, st = None, None
+    elapsed, st, outputs = None, None, None
     if not args.serial_only:
         run_steps(args.warmup, remainder_first=True)
         elapsed, st = timed(args.steps)
+        outputs = frame_outputs()
 
-    # ---- the non-overlapped pass the roofline comes from: pipeline depth 1, one step per pass, no sibling passes, HIP events around every
+    # ---- --full: the non-overlapped pass the roofline comes from: pipeline depth 1, one step per pass, no sibling passes, HIP events around every
     # kernel on the one stream everything runs on.  Kernel times cannot overlap, so sum(kernel ms) <= wall time of this pass. ----
     serial = None
-    if (not args.no_serial_pass and not args.emulate_tiles) or args.serial_only:  # (N > 1: every rank runs it on its tile share; rank 0 reports its own)
+    if (args.full and not args.no_serial_pass and not args.emulate_tiles) or args.serial_only:  # (N > 1: every rank runs it on its tile share; rank 0 reports its own)
         pt.set_pipeline_depth(1)
         pt.set_batch_steps(1)
         pt.set_split_small_passes(False)
@@ -363,6 +407,7 @@ def main():
         serial = (s_el, s_st, k_serial)
         if args.serial_only:
             elapsed, st = s_el, s_st
+            outputs = frame_outputs()
         else:  # back to the defaults for the CPU-baseline comparison below
             pt.set_pipeline_depth(3)
             pt.set_batch_steps(0)
@@ -371,16 +416,17 @@ def main():
     rays = float(st["rays"])
     gather_ok = None
     if dist is not None:
-        # outside the timed region: every rank looks its own pixels up in the assembled frame of the last gather (bit for bit)
-        from massivevoxelraytracing_amd import tiles
-        mv.synchronize()
-        full = frame.cpu().numpy().reshape(-1, 4)
-        mine = pt.read_framebuffer()
-        g = tiles.global_pixel_index(W, H, rank, world)
-        ok = g >= 0
-        flag = torch.tensor([1.0 if np.array_equal(full[g[ok]], mine[ok]) else 0.0], dtype=torch.float64, device="cuda")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        gather_ok = bool(flag[0] > 0)
+        if args.full:
+            # outside the timed region: every rank looks its own pixels up in the assembled frame of the last gather (bit for bit)
+            from massivevoxelraytracing_amd import tiles
+            mv.synchronize()
+            full = frame.cpu().numpy().reshape(-1, 4)
+            mine = pt.read_framebuffer()
+            g = tiles.global_pixel_index(W, H, rank, world)
+            ok = g >= 0
+            flag = torch.tensor([1.0 if np.array_equal(full[g[ok]], mine[ok]) else 0.0], dtype=torch.float64, device="cuda")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            gather_ok = bool(flag[0] > 0)
         t = torch.tensor([elapsed, rays], dtype=torch.float64, device="cuda")
         tmax = t.clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -420,9 +466,9 @@ def main():
             "serial_job_mrays_per_s": round(ss["rays"] / s_el / 1e6, 1),
         }
 
-    # ---- CPU baseline (rank 0, single GPU runs only): the oracle on a bounded band of the same frame ----
+    # ---- --full: CPU baseline (rank 0, single GPU runs only): the oracle on a bounded band of the same frame ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.emulate_tiles:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.emulate_tiles:
         from oracle import oracle as O  # the checker / baseline -- never part of the measured GPU path
         nodes, attrs, _ = pt.m_intersectorOctreeGPU.download()
         sc = O.Scene(nodes.view(O.NODE_DTYPE), attrs, origin, dps, args.grid_res, info.hasEmission)
@@ -488,6 +534,8 @@ def main():
             "roofline": roofline,
             "cpu_baseline": cpu,
         }
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

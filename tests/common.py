@@ -25,6 +25,35 @@ def hdr_bytes():
         return f.read()
 
 
+# Inputs of the pins against the reference's morton.hpp / MurmurHash3.cpp (tests/test_oracle_pins.py).  The reference's answers for them
+# are stored under tests/golden/ (tools/make_fixtures.py), so the pins hold wherever the reference tree is absent.
+REF_MURMUR_U32 = "ref_murmur3_x86_32.u32"
+REF_MORTON_U64 = "ref_morton_codes.u64"
+REF_MORTON_STORED = 20000  # leading points of morton_points() whose reference codes are stored
+
+
+def murmur_cases():
+    """unittest.cpp:106-132 'MurmurHash3.compatibility': 20000 cases of 0-15 random words and a random seed -> [(words uint32, seed)]"""
+    rng = np.random.default_rng(1)
+    cases = []
+    for _ in range(20000):
+        n = int(rng.integers(0, 16))
+        xs = rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
+        s = int(rng.integers(0, 2**32))
+        cases.append((xs, s))
+    return cases
+
+
+def morton_points():
+    """unittest.cpp:183-216 'morton.encodedecode': 200000 random 21-bit (x, y, z), (n, 3) uint32"""
+    rng = np.random.default_rng(2)
+    return rng.integers(0, 1 << 21, size=(200000, 3), dtype=np.uint64).astype(np.uint32)
+
+
+def ref_vector(name, dtype):
+    return np.fromfile(os.path.join(GOLDEN, name), np.dtype(dtype).newbyteorder("<"))
+
+
 def probe_camera(origin, dps, res, focus=1.0, lens_r=0.0, fovy=45.0, offset=(6, 4, 6)):
     """SURVEY.md Appendix A 'Probe camera': look-at from scene centre + (6,4,6), fovy 45 deg.
     Returns the 15 floats of CameraPinhole {o, front, up, right, tanHthetaY, lensR, focus}."""

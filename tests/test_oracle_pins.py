@@ -2,7 +2,8 @@
 
 Two kinds of pins (DESIGN.md "Oracle"):
   * the reference sources that compile as they lie (morton.hpp, smhasher MurmurHash3.cpp ->
-    oracle/_ref), exercised the way the reference's own unittest.cpp does (:106-132, :183-227);
+    oracle/_ref), exercised the way the reference's own unittest.cpp does (:106-132, :183-227); their answers to
+    those inputs are stored under tests/golden/, so the pins hold where the reference tree is absent;
   * golden numbers the survey captured from the reference source (tests/golden/survey_appendix_a.json).
 """
 import hashlib
@@ -10,7 +11,8 @@ import hashlib
 import numpy as np
 import pytest
 
-from common import bunny_tris, golden, hdr_bytes, probe_camera
+from common import (REF_MORTON_STORED, REF_MORTON_U64, REF_MURMUR_U32, bunny_tris, golden, hdr_bytes, morton_points, murmur_cases,
+                    probe_camera, ref_vector)
 from oracle import oracle as O
 
 G = golden()
@@ -26,24 +28,25 @@ def test_murmur_known_answers():
 
 
 def test_murmur_vs_reference_smhasher():
-    """unittest.cpp:106-132 'MurmurHash3.compatibility': 0-15 words, random seed."""
+    """unittest.cpp:106-132 'MurmurHash3.compatibility': 0-15 words, random seed.  Against the reference's answers stored in
+    tests/golden/ and, where oracle/_ref is built, against the reference's MurmurHash3.cpp itself."""
     ref = O.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(1)
-    for _ in range(20000):
-        n = int(rng.integers(0, 16))
-        xs = rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
-        s = int(rng.integers(0, 2**32))
-        h0 = ref.ref_murmur3_x86_32(xs.ctypes.data, n, s)
-        assert O.murmur(s, xs) == h0
+    want = ref_vector(REF_MURMUR_U32, np.uint32)
+    cases = murmur_cases()
+    assert len(want) == len(cases)
+    for (xs, s), h_stored in zip(cases, want):
+        h = O.murmur(s, xs)
+        assert h == int(h_stored)
+        if ref is not None:
+            assert h == ref.ref_murmur3_x86_32(xs.ctypes.data, len(xs), s)
 
 
 def test_morton_vs_reference_header():
-    """unittest.cpp:183-216 'morton.encodedecode': naive == PDEP == magic bits, decoders round-trip."""
-    rng = np.random.default_rng(2)
-    xyz = rng.integers(0, 1 << 21, size=(200000, 3), dtype=np.uint64).astype(np.uint32)
+    """unittest.cpp:183-216 'morton.encodedecode': naive == PDEP == magic bits, decoders round-trip.  The reference's codes of the leading
+    points are stored in tests/golden/; where oracle/_ref is built, all three reference encoders run on every point."""
+    xyz = morton_points()
     mine = O.morton_encode_batch(xyz)
+    assert np.array_equal(mine[:REF_MORTON_STORED], ref_vector(REF_MORTON_U64, np.uint64))
     ref = O.load_ref()
     if ref is not None:
         a, b, c = (np.zeros(len(xyz), np.uint64) for _ in range(3))

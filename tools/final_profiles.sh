@@ -6,8 +6,8 @@ tag=${1:-r03}; part=${2:-abcd}; root=${GRAFT_REPO_ROOT:?run through gpurun}; out
 cd /tmp && export TMPDIR=/tmp && cd $root
 SER="python3 bench.py --serial-only --no-cpu-baseline --warmup 0"
 if [[ $part == *a* ]]; then
-  python3 bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$?"
-  python3 bench.py --steps 20 --warmup 5 > $out/bench_default_steps20.json 2>/dev/null; echo "bench 20 steps rc=$?"
+  python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$?"
+  python3 bench.py --full --steps 20 --warmup 5 > $out/bench_default_steps20.json 2>/dev/null; echo "bench 20 steps rc=$?"
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_serial -- $SER > $out/stats_serial.log 2>&1; echo "serial stats rc=$?"
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_pipelined -- python3 bench.py --no-cpu-baseline --no-serial-pass > $out/stats_pipelined.log 2>&1; echo "pipelined stats rc=$?"
   for c in FETCH_SIZE WRITE_SIZE; do
@@ -22,9 +22,9 @@ if [[ $part == *b* ]]; then
   python3 bench.py --mode cpu-primary --steps 3 > $out/bench_cpu_primary_256.json 2>/dev/null; echo "cpu-primary rc=$?"
   python3 bench.py --mode primary --grid-res 1024 --no-cpu-baseline --steps 20 --warmup 3 > $out/bench_primary_1024.json 2>/dev/null; echo "primary 1024 rc=$?"
   python3 bench.py --mode primary --grid-res 8192 --no-cpu-baseline --steps 20 --warmup 3 > $out/bench_primary_8192.json 2>/dev/null; echo "primary 8192 rc=$?"
-  python3 bench.py --scene rtcamp --steps 16 --no-cpu-baseline > $out/bench_rtcamp_4096_256spp.json 2>/dev/null; echo "rtcamp rc=$?"
-  python3 bench.py --scene cave > $out/bench_cave_2048.json 2>/dev/null; echo "cave rc=$?"
-  python3 bench.py --scene tunnel > $out/bench_tunnel_4096.json 2>/dev/null; echo "tunnel rc=$?"
+  python3 bench.py --full --scene rtcamp --steps 16 --no-cpu-baseline > $out/bench_rtcamp_4096_256spp.json 2>/dev/null; echo "rtcamp rc=$?"
+  python3 bench.py --full --scene cave > $out/bench_cave_2048.json 2>/dev/null; echo "cave rc=$?"
+  python3 bench.py --full --scene tunnel > $out/bench_tunnel_4096.json 2>/dev/null; echo "tunnel rc=$?"
 fi
 if [[ $part == *c* ]]; then
   ST="python3 bench.py --mode stress --steps 3 --warmup 1"
