@@ -154,6 +154,53 @@ int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const float* roHost,
 int mvrt_render_primary( const mvrt_svo* svo, const float camera[15], int width, int height, int showVertexColor, uint8_t* rgbaDev, float* tDev, int32_t* nMajorDev,
 						 uint32_t* vIndexDev, uint32_t* descentsDev, void* stream );
 
+/* Device view of an octree: the by-value IntersectorOctreeGPU a user kernel takes (IntersectorOctreeGPU.hpp:243-275), for the
+ * per-thread traversal of include/mvrt/device.hpp (mvrt::DeviceOctree).  Fixed-width fields only; pointers are device addresses
+ * stored as uint64_t.
+ *   - The view is a SNAPSHOT of the handle: any later build, upload, cleanUp or destroy of that handle invalidates it (its
+ *     buffers are freed or replaced), exactly like a copy of the reference's struct.  Take a new view after each of them.
+ *   - emissionScale is copied from the handle; the caller may edit it in the copy it holds (getVoxelEmission( v, true ) uses it).
+ *   - Flavours MVRT_FLAVOUR_EMBEDDED and MVRT_FLAVOUR_PLAIN only; tree-flavour octrees are refused.
+ *   - levels <= MVRT_DEVICE_MAX_LEVELS (the depth of the per-thread stack). */
+#define MVRT_DEVICE_MAX_LEVELS 16
+typedef struct mvrt_device_octree
+{
+	uint32_t structBytes; /* sizeof( mvrt_device_octree ) of the library that filled it */
+	uint32_t flavour;	  /* MVRT_FLAVOUR_* */
+	uint64_t nodes;		  /* 64-byte lines {children[8], nVoxelsPSum[8] (embedded) or the 8 child masks (plain)} */
+	uint64_t kids;		  /* embedded: children[8] per node, 32 bytes per node (0 = read them from the node lines) */
+	uint64_t masks;		  /* per-node own mask, one byte per node */
+	uint64_t psumCold;	  /* plain: nVoxelsPSum[node * 8 + child] */
+	uint64_t attrs;		  /* VoxelAttirb[numberOfVoxels]: {uchar4 color, uchar4 emission} */
+	uint64_t cellBlocks;  /* reserved for the cell index of octrees built by the library (0 = none); the traversal walks nVoxelsPSum */
+	uint64_t cellEntries;
+	float lower[3];
+	float upper[3];
+	float dps;
+	float emissionScale;
+	uint32_t hasEmission;
+	uint32_t levels;
+	uint32_t numberOfNodes;
+	uint32_t numberOfVoxels;
+	uint32_t rootIndex; /* numberOfNodes - 1 */
+	uint32_t rootMask;	/* the root's own occupancy mask */
+	uint32_t treeRoot;	/* 0 (tree flavour only) */
+	uint32_t cellBits;
+} mvrt_device_octree;
+#ifdef __cplusplus
+#define MVRT_STATIC_ASSERT_( c, m ) static_assert( c, m )
+#else
+#define MVRT_STATIC_ASSERT_( c, m ) _Static_assert( c, m )
+#endif
+MVRT_STATIC_ASSERT_( sizeof( mvrt_device_octree ) == 128, "mvrt_device_octree is 128 bytes" );
+MVRT_STATIC_ASSERT_( __builtin_offsetof( mvrt_device_octree, nodes ) == 8 && __builtin_offsetof( mvrt_device_octree, cellEntries ) == 56 &&
+						 __builtin_offsetof( mvrt_device_octree, lower ) == 64 && __builtin_offsetof( mvrt_device_octree, emissionScale ) == 92 &&
+						 __builtin_offsetof( mvrt_device_octree, levels ) == 100 && __builtin_offsetof( mvrt_device_octree, cellBits ) == 124,
+					 "mvrt_device_octree field offsets" );
+#undef MVRT_STATIC_ASSERT_
+/* Fill *out with the device view of svo (no GPU call).  Fails without an octree, on a tree-flavour octree and above MVRT_DEVICE_MAX_LEVELS. */
+int mvrt_svo_device_view( const mvrt_svo* svo, mvrt_device_octree* out );
+
 /* CameraPinhole::initFromPerspective (renderCommon.hpp:21-35) */
 int mvrt_camera_from_matrices( const float view[16], const float proj[16], float focus, float lensR, float cameraOut[15] );
 

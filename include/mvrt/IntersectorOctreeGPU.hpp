@@ -85,6 +85,16 @@ struct IntersectorOctreeGPU
 	}
 	bool hasEmission() const { return m_hasEmission != 0; } // :261-264
 
+	// the by-value struct a user kernel takes (include/mvrt/device.hpp: mvrt::DeviceOctree).  emissionScale is this object's m_emissionScale, so
+	// assigning that member takes effect in kernels written on the device API.  Invalidated by the next build / upload / cleanUp (a snapshot).
+	mvrt_device_octree deviceView() const
+	{
+		mvrt_device_octree v;
+		check( mvrt_svo_device_view( m_handle, &v ), "IntersectorOctreeGPU::deviceView" );
+		v.emissionScale = m_emissionScale;
+		return v;
+	}
+
 	mvrt_svo* handle() const { return m_handle; }
 
 	// re-bind to a handle owned by someone else (PathTracer::m_intersectorOctreeGPU is a VALUE member in the reference, PathTracer.hpp:18)

@@ -30,6 +30,14 @@ class SvoInfo(C.Structure):
                 ("hasEmission", _u32), ("embeddedMask", _u32), ("gridRes", _u32), ("levels", _u32), ("totalDumpedVoxels", _u64), ("flavour", _u32), ("reserved", _u32)]
 
 
+class DeviceOctree(C.Structure):
+    """mvrt_device_octree (include/mvrt.h): the device view a user kernel takes by value (include/mvrt/device.hpp)"""
+    _fields_ = [("structBytes", _u32), ("flavour", _u32), ("nodes", _u64), ("kids", _u64), ("masks", _u64), ("psumCold", _u64), ("attrs", _u64),
+                ("cellBlocks", _u64), ("cellEntries", _u64), ("lower", _f32 * 3), ("upper", _f32 * 3), ("dps", _f32), ("emissionScale", _f32),
+                ("hasEmission", _u32), ("levels", _u32), ("numberOfNodes", _u32), ("numberOfVoxels", _u32), ("rootIndex", _u32), ("rootMask", _u32),
+                ("treeRoot", _u32), ("cellBits", _u32)]
+
+
 class PtStats(C.Structure):
     _fields_ = [("samples", _u64), ("rays", _u64), ("shadowRays", _u64), ("descents", _u64), ("shadowDescents", _u64), ("hits", _u64), ("traceLaunches", _u64),
                 ("traceKernelMs", C.c_double), ("shadeKernelMs", C.c_double), ("totalKernelMs", C.c_double)]
@@ -58,6 +66,7 @@ SIGNATURES = {
     "mvrt_svo_upload": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, _f32, _i32, _i32, _i32, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
+    "mvrt_svo_device_view": (_i32, [_vp, _vp]),
     "mvrt_svo_traversal_bytes": (_u64, [_vp]),
     "mvrt_svo_node_buffer_dev": (_vp, [_vp]),
     "mvrt_svo_attribute_buffer_dev": (_vp, [_vp]),
@@ -280,6 +289,13 @@ class IntersectorOctreeGPU:
     m_hasEmission = property(lambda s: s.info().hasEmission)
     m_nodeBuffer = property(lambda s: lib().mvrt_svo_node_buffer_dev(s._h))  # device pointers (:265-266)
     m_vAttributeBuffer = property(lambda s: lib().mvrt_svo_attribute_buffer_dev(s._h))
+
+    def device_view(self):
+        """mvrt_svo_device_view: the ctypes DeviceOctree a HIP kernel built on include/mvrt/device.hpp takes by value.
+        A snapshot: any later build / upload / cleanUp of this object invalidates it."""
+        v = DeviceOctree()
+        _check(lib().mvrt_svo_device_view(self._h, C.byref(v)))
+        return v
 
     def traversal_bytes(self):
         return lib().mvrt_svo_traversal_bytes(self._h)

@@ -93,7 +93,31 @@ def build_apps(verbose=True):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
+    build_device_apps(verbose)
     return os.path.join(root, "apps", "rtcamp_batch")
+
+
+DEVICE_APPS = {
+    # name: source -- HIP applications whose own kernels sit on the public device header (include/mvrt/device.hpp).  Built with a user's flags:
+    # hipcc defaults, no contract flag (the header keeps its arithmetic uncontracted itself)
+    "device_render": "device_render.hip",
+}
+
+
+def build_device_apps(verbose=True):
+    root = os.path.dirname(HERE)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    deps = [os.path.join(root, "apps", "scene_io.hpp"), os.path.join(root, "include", "mvrt", "device.hpp"), os.path.join(root, "include", "mvrt.h")]
+    for name, src_name in DEVICE_APPS.items():
+        out = os.path.join(root, "apps", name)
+        src = os.path.join(root, "apps", src_name)
+        if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + deps):
+            continue
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wall", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "apps"), src, "-o", out,
+               "-L", HERE, "-l:libmvrt_hip.so", "-Wl,-rpath," + HERE]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
 
 
 if __name__ == "__main__":

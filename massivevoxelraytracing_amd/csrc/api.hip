@@ -455,6 +455,40 @@ MVRT_EXPORT uint64_t mvrt_svo_traversal_bytes( const mvrt_svo* svo )
 }
 MVRT_EXPORT const void* mvrt_svo_node_buffer_dev( const mvrt_svo* svo ) { return svo ? svo->nodes : nullptr; }
 MVRT_EXPORT const void* mvrt_svo_attribute_buffer_dev( const mvrt_svo* svo ) { return svo ? svo->attrs : nullptr; }
+MVRT_EXPORT int mvrt_svo_device_view( const mvrt_svo* svo, mvrt_device_octree* out )
+{
+	REQUIRE( svo && out, "mvrt_svo_device_view: null argument" );
+	REQUIRE( svo->nodes, "mvrt_svo_device_view: no octree (build or upload first)" );
+	REQUIRE( !svo->tree, "mvrt_svo_device_view: tree-flavour octrees (MVRT_FLAVOUR_TREE) are not supported by the device API" );
+	REQUIRE( svo->info.levels <= MVRT_DEVICE_MAX_LEVELS, "mvrt_svo_device_view: %u levels, the device API supports at most %d", svo->info.levels,
+			 MVRT_DEVICE_MAX_LEVELS );
+	const SvoDev d = svo->dev();
+	mvrt_device_octree v;
+	memset( &v, 0, sizeof( v ) );
+	v.structBytes = sizeof( mvrt_device_octree );
+	v.flavour = d.embedded ? MVRT_FLAVOUR_EMBEDDED : MVRT_FLAVOUR_PLAIN;
+	v.nodes = (uint64_t)(uintptr_t)d.nodes;
+	v.kids = (uint64_t)(uintptr_t)d.kids;
+	v.masks = (uint64_t)(uintptr_t)d.masks;
+	v.psumCold = (uint64_t)(uintptr_t)d.psumCold;
+	v.attrs = (uint64_t)(uintptr_t)d.attrs;
+	v.cellBlocks = (uint64_t)(uintptr_t)d.cellBlocks;
+	v.cellEntries = d.cellBlocks ? (uint64_t)(uintptr_t)d.cellEntries : 0;
+	v.lower[0] = d.lower.x; v.lower[1] = d.lower.y; v.lower[2] = d.lower.z;
+	v.upper[0] = d.upper.x; v.upper[1] = d.upper.y; v.upper[2] = d.upper.z;
+	v.dps = d.dps;
+	v.emissionScale = d.emissionScale;
+	v.hasEmission = d.hasEmission;
+	v.levels = d.levels;
+	v.numberOfNodes = d.nNodes;
+	v.numberOfVoxels = d.nVoxels;
+	v.rootIndex = d.rootIndex;
+	v.rootMask = d.rootMask;
+	v.treeRoot = 0;
+	v.cellBits = d.cellBlocks ? d.cellBits : 0;
+	*out = v;
+	return 0;
+}
 MVRT_EXPORT int mvrt_svo_set_emission_scale( mvrt_svo* svo, float scale )
 {
 	REQUIRE( svo, "null argument" );

@@ -1,0 +1,335 @@
+"""The public device API on the MI355X: a user kernel built on include/mvrt/device.hpp (tests/hip/device_api_probe.hip, compiled here
+with hipcc and loaded through ctypes) gives what mvrt_trace_batch and the CPU oracle give, bit for bit -- t, nMajor, vIndex and
+descents -- in both stack modes, on every octree flavour the view accepts; apps/device_render reproduces mvrt_render_primary."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from common import bunny_tris, position_colors, probe_camera
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+MAXF = np.float32(3.402823466e38)
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import oracle
+    return oracle
+
+
+@pytest.fixture(scope="module")
+def mv():
+    import massivevoxelraytracing_amd as m
+    m.lib()
+    assert m.device_count() >= 1
+    return m
+
+
+def compile_probe(out_dir, flags):
+    so = os.path.join(str(out_dir), "device_api_probe%s.so" % "".join(flags).replace("=", "_"))
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror"] + flags +
+                          ["-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "hip", "device_api_probe.hip"), "-o", so], timeout=300)
+    lib = C.CDLL(so)
+    lib.probe_trace.restype = C.c_int
+    lib.probe_trace.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11 + [C.c_int]
+    lib.probe_attrs.restype = C.c_int
+    lib.probe_attrs.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
+    return lib
+
+
+@pytest.fixture(scope="module")
+def probe(mv, tmp_path_factory):
+    return compile_probe(tmp_path_factory.mktemp("probe"), [])
+
+
+def probe_trace(mv, probe, view, ro, rd, sh=None, mode=0):
+    ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
+    rd = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
+    n = len(ro)
+    if n == 0:
+        assert probe.probe_trace(C.byref(view), 0, *([None] * 11), mode) == 0
+        return {k: np.zeros(0, d) for k, d in (("t", np.float32), ("nMajor", np.int32), ("vIndex", np.uint32), ("descents", np.uint32))}
+    dev = [mv.DeviceArray.from_host(np.ascontiguousarray(a)) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
+    dsh = None if sh is None else mv.DeviceArray.from_host(np.ascontiguousarray(sh, np.uint8))
+    out = [mv.DeviceArray(n, d) for d in (np.float32, np.int32, np.uint32, np.uint32)]
+    rc = probe.probe_trace(C.byref(view), n, *[a.ptr for a in dev], None if dsh is None else dsh.ptr, *[a.ptr for a in out], mode)
+    assert rc == 0, rc
+    return dict(zip(("t", "nMajor", "vIndex", "descents"), (a.to_host() for a in out)))
+
+
+def random_rays(sc, n, seed):
+    """(tests/test_gpu_parity.py) rays from around the grid onto random points of it, with axis-parallel / zero-component directions and rays from inside"""
+    rng = np.random.default_rng(seed)
+    lo, hi = sc.bounds()
+    c = (lo + hi) / 2
+    ext = (hi - lo).max()
+    ro = (c + (rng.random((n, 3)) - 0.5) * ext * 2.5).astype(np.float32)
+    tgt = (lo + rng.random((n, 3)) * (hi - lo)).astype(np.float32)
+    rd = (tgt - ro).astype(np.float32)
+    k = n // 10
+    rd[:k, 0] = 0.0
+    rd[k:2 * k, 1] = 0.0
+    rd[2 * k:3 * k, 2] = 0.0
+    rd[3 * k:3 * k + 50] = np.array([0, 0, -1], np.float32)
+    ro[4 * k:5 * k] = (lo + rng.random((k, 3)) * (hi - lo)).astype(np.float32)
+    return ro, rd
+
+
+def tie_rays(sc, n_out=3000, n_in=1500, seed=3):
+    """(tests/test_gpu_parity.py) diagonals through lattice points of the octree from dyadic distances, and from ON the lattice planes"""
+    lo, _ = sc.bounds()
+    ext = np.float32(sc.dps * sc.grid_res)
+    levels = int(np.log2(sc.grid_res))
+    rng = np.random.default_rng(seed)
+    dirs = [(1, 1, 1), (1, 1, -1), (1, -1, 1), (-1, 1, 1), (1, 1, 0.5), (1, 0.5, 1), (0.5, 1, 1), (1, 0.5, 0.25), (2, 1, 1), (1, 2, -1), (-1, -1, -1), (1, -1, -0.5)]
+    ros, rds = [], []
+    for k in range(n_out):
+        lvl = int(rng.integers(1, levels + 1))
+        cell = ext / np.float32(2 ** lvl)
+        p = lo + cell * rng.integers(0, 2 ** lvl + 1, size=3).astype(np.float32)
+        d = np.array(dirs[k % len(dirs)], np.float32)
+        s = np.float32(2 ** int(rng.integers(0, 3)))
+        ros.append((p - d * ext * s).astype(np.float32))
+        rds.append(d if k % 3 else d * np.float32(0.5))
+    for k in range(n_in):
+        lvl = int(rng.integers(1, levels + 1))
+        cell = ext / np.float32(2 ** lvl)
+        ros.append((lo + cell * rng.integers(0, 2 ** lvl + 1, size=3).astype(np.float32)).astype(np.float32))
+        rds.append(np.array(dirs[k % len(dirs)], np.float32))
+    return np.array(ros, np.float32), np.array(rds, np.float32)
+
+
+def ray_set(sc, n, seed):
+    ro, rd = random_rays(sc, n, seed)
+    tr, td = tie_rays(sc)
+    ro, rd = np.concatenate([ro, tr]), np.concatenate([rd, td])
+    sh = (np.random.default_rng(seed + 1).random(len(ro)) < 0.3).astype(np.uint8)
+    return ro, rd, sh
+
+
+def assert_same(a, b):
+    for k in ("t", "nMajor", "vIndex", "descents"):
+        assert np.array_equal(a[k], b[k]), k
+
+
+def check_octree(mv, O, probe, svo, sc, n, seed, min_hits=1000):
+    """probe (both stack modes) == mvrt_trace_batch == oracle on every output"""
+    view = svo.device_view()
+    assert view.structBytes == C.sizeof(mv.DeviceOctree)
+    ro, rd, sh = ray_set(sc, n, seed)
+    lib = svo.intersect(ro, rd, sh, want_descents=True)
+    want = sc.trace(ro, rd, sh, threads=8, want_descents=True)
+    hit = want["t"] != MAXF
+    assert hit.sum() >= min_hits
+    assert np.array_equal(lib["t"], want["t"]) and np.array_equal(lib["descents"], want["descents"])
+    assert np.array_equal(lib["vIndex"][hit], want["vIndex"][hit]) and np.array_equal(lib["nMajor"][hit], want["nMajor"][hit])
+    for mode in (0, 1):
+        got = probe_trace(mv, probe, view, ro, rd, sh, mode)
+        assert_same(got, lib)
+    assert (lib["vIndex"][sh == 1] == 0).all()
+    return ro, rd, sh, lib
+
+
+@pytest.fixture(scope="module")
+def bunny256(O):
+    return O.build_scene_from_triangles(bunny_tris(), 256)
+
+
+def upload(mv, sc, embedded=True):
+    svo = mv.IntersectorOctreeGPU()
+    svo.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission, embeddedMask=embedded)
+    return svo
+
+
+@pytest.mark.parametrize("embedded", [True, False])
+def test_uploaded_bunny_256(mv, O, probe, bunny256, embedded):
+    # embeddedMask=False takes nodes whose child pointers are plain indices: the oracle builds those with embed=False
+    sc = bunny256 if embedded else O.build_scene_from_triangles(bunny_tris(), 256, embed=False)
+    svo = upload(mv, sc, embedded)
+    assert svo.device_view().flavour == (0 if embedded else 1)
+    check_octree(mv, O, probe, svo, sc, 200_000, 7, min_hits=10_000)
+
+
+@pytest.mark.parametrize("flags", [0, 2])
+def test_gpu_built_bunny_256(mv, O, probe, flags):
+    """octrees built by the library (these carry the cell index; the device walk sums nVoxelsPSum and must give the same integers); flags 2 = plain flavour"""
+    from massivevoxelraytracing_amd import scenes
+    tris = bunny_tris()
+    v = tris.reshape(-1, 3)
+    origin, dps = scenes.bounding_grid(v, 256)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build(v, None, None, None, origin, dps, 256, flags=flags)
+    assert svo.device_view().flavour == (1 if flags & 2 else 0)
+    sc = O.build_scene_from_triangles(tris, 256, embed=(flags & 2) == 0)
+    check_octree(mv, O, probe, svo, sc, 200_000, 17, min_hits=10_000)
+
+
+@pytest.mark.parametrize("res", [128, 1024])
+def test_tree_flavour_is_refused_by_name(mv, res):
+    """MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK builds the tree flavour (two-level bricks): the device API does not walk it yet"""
+    from massivevoxelraytracing_amd import scenes
+    v = bunny_tris().reshape(-1, 3)
+    origin, dps = scenes.bounding_grid(v, res)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build(v, None, None, None, origin, dps, res, flags=mv.IntersectorOctreeGPU.BUILD_NO_DAG | mv.IntersectorOctreeGPU.BUILD_NO_EMBEDDED_MASK)
+    assert svo.info().flavour == 2
+    with pytest.raises(mv.MvrtError, match="tree-flavour"):
+        svo.device_view()
+
+
+def test_non_canonical_psum_upload_gives_the_stored_sums(mv, O, probe, bunny256):
+    nodes = bunny256.nodes.copy()
+    for value in (0, 3):
+        nodes["psum"][:] = value
+        sc = O.Scene(nodes, bunny256.attrs, bunny256.origin, bunny256.dps, 256)
+        svo = upload(mv, sc)
+        _, _, sh, lib = check_octree(mv, O, probe, svo, sc, 30_000, 31)
+        hit = (lib["t"] != MAXF) & (sh == 0)
+        assert (lib["vIndex"][hit] == 8 * value).all()
+
+
+@pytest.mark.parametrize("res", [2, 4, 8])
+def test_tiny_grids(mv, O, probe, res):
+    sc = O.build_scene_from_triangles(bunny_tris(), res)
+    check_octree(mv, O, probe, upload(mv, sc), sc, 20_000, res, min_hits=100)
+
+
+def test_empty_batch(mv, probe, bunny256):
+    view = upload(mv, bunny256).device_view()
+    for mode in (0, 1):
+        assert len(probe_trace(mv, probe, view, np.zeros((0, 3)), np.zeros((0, 3)), mode=mode)["t"]) == 0
+
+
+def test_contract_on_build_gives_identical_output(mv, O, probe, bunny256, tmp_path):
+    on = compile_probe(tmp_path, ["-ffp-contract=on"])
+    svo = upload(mv, bunny256)
+    view = svo.device_view()
+    ro, rd, sh = ray_set(bunny256, 50_000, 41)
+    assert_same(probe_trace(mv, on, view, ro, rd, sh), probe_trace(mv, probe, view, ro, rd, sh))
+    assert_same(probe_trace(mv, on, view, ro, rd, sh), svo.intersect(ro, rd, sh, want_descents=True))
+
+
+def raw_reflectance(rgba8):
+    c = rgba8.astype(np.uint32)
+    return np.stack([(c & 0xFF).astype(np.float32) / np.float32(255), ((c >> 8) & 0xFF).astype(np.float32) / np.float32(255),
+                     ((c >> 16) & 0xFF).astype(np.float32) / np.float32(255)], 1)
+
+
+def test_voxel_colour_and_emission_of_every_voxel(mv, O, probe):
+    tris = bunny_tris()
+    cols, emis = position_colors(tris)
+    sc = O.build_scene_from_triangles(tris, 128, cols, emis)
+    svo = upload(mv, sc)
+    attrs = np.ascontiguousarray(sc.attrs).view(np.uint8).reshape(-1, 8)
+    n = len(attrs)
+    emis_u32 = attrs[:, 4:8].copy().view(np.uint32).reshape(-1)
+    assert (emis_u32 != 0).any()
+    for scale in (None, 2.25):
+        view = svo.device_view()
+        if scale is not None:
+            view.emissionScale = scale  # the caller's copy is theirs to edit
+        s = np.float32(view.emissionScale)
+        col, em, raw, he = mv.DeviceArray((n, 4), np.uint8), mv.DeviceArray((n, 3), np.float32), mv.DeviceArray((n, 3), np.float32), mv.DeviceArray(1, np.uint32)
+        assert probe.probe_attrs(C.byref(view), n, col.ptr, em.ptr, raw.ptr, he.ptr) == 0
+        assert np.array_equal(col.to_host(), attrs[:, 0:4])
+        assert np.array_equal(raw.to_host(), raw_reflectance(emis_u32))
+        assert np.array_equal(em.to_host(), (raw_reflectance(emis_u32) * s).astype(np.float32))
+        assert he.to_host()[0] == 1
+    assert np.float32(svo.device_view().emissionScale) == np.float32(7.5)
+
+
+# ---- apps/device_render ------------------------------------------------------------------------------------------------------------------------
+def write_obj(path, v, cols):
+    with open(path, "w") as f:
+        for p, c in zip(v, cols):
+            f.write("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
+        for t in range(len(v) // 3):
+            f.write("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3))
+
+
+@pytest.fixture(scope="module")
+def render_setup(mv, tmp_path_factory):
+    from massivevoxelraytracing_amd import build as b, scenes
+    b.build_apps(verbose=False)
+    exe = os.path.join(ROOT, "apps", "device_render")
+    assert os.path.exists(exe)
+    d = tmp_path_factory.mktemp("device_render")
+    tris = bunny_tris()
+    v = tris.reshape(-1, 3)
+    cols = position_colors(tris)[0].reshape(-1, 3)
+    obj = str(d / "bunny.obj")
+    write_obj(obj, v, cols)
+    origin, dps = scenes.bounding_grid(v, 256)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build(v, cols, np.zeros_like(v), None, origin, dps, 256)
+    cam = probe_camera(origin, dps, 256)
+    return exe, d, obj, svo, cam
+
+
+def run_app(exe, args):
+    r = subprocess.run(["timeout", "-k", "10", "120", exe] + args, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout
+
+
+def read_ppm(path, W, H):
+    data = open(path, "rb").read()
+    head = b"P6\n%d %d\n255\n" % (W, H)
+    assert data.startswith(head)
+    return np.frombuffer(data[len(head):], np.uint8).reshape(W * H, 3)
+
+
+@pytest.mark.parametrize("vertex_color", [False, True])
+def test_device_render_equals_render_primary(render_setup, vertex_color):
+    exe, d, obj, svo, cam = render_setup
+    W, H = 320, 180
+    out, prefix = str(d / ("img%d.ppm" % vertex_color)), str(d / ("dump%d" % vertex_color))
+    run_app(exe, [obj, out, "--size", str(W), str(H), "--res", "256", "--camera"] + ["%.9g" % c for c in cam] + ["--dump", prefix] +
+            (["--vertex-color"] if vertex_color else []))
+    want = svo.render(cam, W, H, showVertexColor=vertex_color)
+    dumped = np.array([float.fromhex(x) for x in open(prefix + ".camera.txt").read().split()], np.float32)
+    assert np.array_equal(dumped, cam)
+    assert np.array_equal(read_ppm(out, W, H), want["rgba"][:, :3])
+    assert np.array_equal(np.fromfile(prefix + ".t.f32", np.float32), want["t"])
+    nm = np.fromfile(prefix + ".nmajor.i32", np.int32)
+    hit = want["t"] != MAXF
+    assert hit.sum() > 1000
+    assert np.array_equal(nm[hit], want["nMajor"][hit]) and (nm[~hit] == -1).all()
+
+
+def test_device_render_shadow_rays_equal_trace_batch(render_setup):
+    exe, d, obj, svo, cam = render_setup
+    W, H = 320, 180
+    sun = np.array([0.3, 1.0, 0.2], np.float32)
+    prefix = str(d / "sun")
+    run_app(exe, [obj, str(d / "sun.ppm"), "--size", str(W), str(H), "--res", "256", "--camera"] + ["%.9g" % c for c in cam] + ["--dump", prefix, "--sun"] +
+            ["%.9g" % s for s in sun])
+    t = np.fromfile(prefix + ".t.f32", np.float32)
+    shadow = np.fromfile(prefix + ".shadow.u8", np.uint8)
+    hit = t != MAXF
+    # the app's primary rays (CameraPinhole::shoot through pixel centres) are mvrt_render_primary's: take t from there, rebuild the rays in f32
+    assert np.array_equal(t, svo.render(cam, W, H)["t"])
+    c = cam.astype(np.float32)
+    o, front, up, right, tan_h = c[0:3], c[3:6], c[6:9], c[9:12], c[12]
+    pix = np.arange(W * H)
+    x, y = (pix % W).astype(np.float32), (pix // W).astype(np.float32)
+    f32 = np.float32
+    xf = ((x + f32(0.5)) / f32(W)).astype(f32)
+    yf = ((y + f32(0.5)) / f32(H)).astype(f32)
+    a = (-tan_h + (tan_h - -tan_h) * xf).astype(f32)
+    b = (tan_h + (-tan_h - tan_h) * yf).astype(f32)
+    rd = ((((right[None, :] * a[:, None]) * f32(W)) / f32(H) + up[None, :] * b[:, None]) + front[None, :]).astype(f32)
+    ro = np.ascontiguousarray(np.broadcast_to(o, rd.shape))
+    assert np.array_equal(svo.intersect(ro, rd)["t"], t)  # the rays are rebuilt exactly
+    so = (ro[hit] + rd[hit] * t[hit][:, None]).astype(f32)  # the app's documented shadow origin: o = ro + rd * t per component
+    sd = np.broadcast_to(sun, so.shape).astype(f32)
+    want = svo.intersect(so, sd, np.ones(len(so), np.uint8))
+    assert np.array_equal(shadow[hit], (want["t"] != MAXF).astype(np.uint8))
+    assert (shadow[~hit] == 0).all()
+    assert 0 < shadow[hit].sum() < hit.sum()
