@@ -63,7 +63,7 @@ typedef struct mvrt_svo_info
 	uint32_t embeddedMask;	 /* 1: child pointers carry the child's mask in bits 24-31 (voxCommon.hpp:7-9) */
 	uint32_t gridRes;
 	uint32_t levels;		   /* log2(gridRes) = maximum traversal stack depth */
-	uint64_t totalDumpedVoxels; /* voxels emitted before de-duplication (build only, else 0) */
+	uint64_t totalDumpedVoxels; /* entries before de-duplication: fragments of a triangle build, n of mvrt_svo_build_voxels; 0 after an upload or an edit */
 	uint32_t flavour;			/* layout behind mvrt_svo_node_buffer_dev: MVRT_FLAVOUR_* */
 	uint32_t reserved;
 } mvrt_svo_info;
@@ -100,6 +100,27 @@ int mvrt_svo_build_ex( mvrt_svo* svo, const float* verticesHost, const float* vc
  * voxel i: h = splitmix64(seed + i); x = h & (res-1), y = (h >> 21) & (res-1), z = (h >> 42) & (res-1); c = splitmix64(h):
  * colour = (c & 0xFFFFFF) | 0x404040, emission = colour if (c >> 56) == 0 else 0. */
 int mvrt_svo_build_synthetic( mvrt_svo* svo, int gridRes, uint64_t nRandomVoxels, uint64_t seed, const float origin[3], float dps, int flags, void* stream );
+
+/* Voxel lists (new; the reference only voxelizes triangles).  Device arrays in; the calls block like mvrt_svo_build.  A failure leaves the handle exactly as it was:
+ * arguments are checked on the host before any GPU call, coordinates (and ops) on the device before anything is replaced -- the message names the LOWEST offending entry.
+ *
+ * Build from a voxel list.  xyzDev: 3 x uint32 per voxel, each in [0, gridRes).  attribsDev: VoxelAttirb per entry {uchar4 color, uchar4 emission} (8 bytes), or NULL =
+ * white, no emission (voxUtil.hpp's defaults).  Duplicate coordinates merge exactly like the reference's `unique` (integer mean of RGB per channel, alpha stored as 255,
+ * hasEmission = any emission RGB != 0).  flags: MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only.  gridRes: power of two in [2, 2^21].  1 <= n < 2^32 - 1. */
+int mvrt_svo_build_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t* attribsDev, uint64_t n, const float origin[3], float dps, int gridRes, int flags,
+						   void* stream );
+#define MVRT_VOXEL_REMOVE 0
+#define MVRT_VOXEL_SET 1
+/* Apply a batch of edits to an octree this library built (build, build_ex, build_synthetic, build_voxels, or an earlier edit; not an upload).  opsDev: one byte per entry
+ * (NULL = all SET).  SET inserts the voxel or replaces its attributes (no averaging; alpha stored as 255); REMOVE deletes it (absent voxel: no-op).  Entries naming the same
+ * voxel: the LAST one in the batch wins.  Grid, origin, dps, build flags and emission scale are kept; the flavour is whatever a fresh build of the resulting voxel set picks.
+ * A batch that only re-colours existing voxels keeps the nodes and writes the attributes in place; any insertion or removal rebuilds the levels.  Fails (handle
+ * unchanged) on a coordinate outside the grid, an unknown op byte, or an edit that would remove every voxel.  Through mvrt_pt_intersector( pt ): the steps issued
+ * before finish first and render the old scene; the frame buffer is not cleared. */
+int mvrt_svo_edit_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t* attribsDev, const uint8_t* opsDev, uint64_t n, void* stream );
+/* The current voxel set, sorted by Morton code (= vIndex order): coordinates (3 x uint32) and attributes (8 bytes) into caller device arrays of numberOfVoxels entries;
+ * either may be NULL.  Octrees built by this library only. */
+int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attribsDev, void* stream );
 
 /* Adopt an SVO built elsewhere (e.g. IntersectorOctree::buildDAGReference on the CPU, IntersectorOctree.hpp:
  * 224-231): nodes in the reference's 68-byte layout, root last.  embeddedMask = 0 selects the variant where
@@ -157,8 +178,9 @@ int mvrt_render_primary( const mvrt_svo* svo, const float camera[15], int width,
 /* Device view of an octree: the by-value IntersectorOctreeGPU a user kernel takes (IntersectorOctreeGPU.hpp:243-275), for the
  * per-thread traversal of include/mvrt/device.hpp (mvrt::DeviceOctree).  Fixed-width fields only; pointers are device addresses
  * stored as uint64_t.
- *   - The view is a SNAPSHOT of the handle: any later build, upload, cleanUp or destroy of that handle invalidates it (its
- *     buffers are freed or replaced), exactly like a copy of the reference's struct.  Take a new view after each of them.
+ *   - The view is a SNAPSHOT of the handle: any later build (mvrt_svo_build_voxels included), mvrt_svo_edit_voxels, upload, cleanUp or
+ *     destroy of that handle invalidates it (its buffers are freed, replaced or rewritten, hasEmission may change), exactly like a copy of
+ *     the reference's struct.  Take a new view after each of them.
  *   - emissionScale is copied from the handle; the caller may edit it in the copy it holds (getVoxelEmission( v, true ) uses it).
  *   - Flavours MVRT_FLAVOUR_EMBEDDED and MVRT_FLAVOUR_PLAIN only; tree-flavour octrees are refused.
  *   - levels <= MVRT_DEVICE_MAX_LEVELS (the depth of the per-thread stack). */

@@ -77,6 +77,49 @@ struct IntersectorOctreeGPU
 		refresh();
 	}
 
+	// voxel lists (mvrt_svo_build_voxels / mvrt_svo_edit_voxels / mvrt_svo_read_voxels): device arrays of xyz (3 x u32 per voxel) and VoxelAttirb (2 x u32 per voxel,
+	// nullptr = white, no emission); ops: MVRT_VOXEL_SET / MVRT_VOXEL_REMOVE per entry (nullptr = all SET), the last entry per voxel wins
+	void buildFromVoxels( const uint32_t* xyzDev, const uint32_t* attribsDev, uint64_t n, vec3 origin, float dps, int gridRes, int buildFlags, void* stream )
+	{
+		const float o[3] = { origin.x, origin.y, origin.z };
+		check( mvrt_svo_build_voxels( m_handle, xyzDev, attribsDev, n, o, dps, gridRes, buildFlags, stream ), "IntersectorOctreeGPU::buildFromVoxels" );
+		refresh();
+	}
+	void editVoxels( const uint32_t* xyzDev, const uint32_t* attribsDev, const uint8_t* opsDev, uint64_t n, void* stream )
+	{
+		check( mvrt_svo_edit_voxels( m_handle, xyzDev, attribsDev, opsDev, n, stream ), "IntersectorOctreeGPU::editVoxels" );
+		refresh();
+	}
+	void readVoxels( uint32_t* xyzDev, uint32_t* attribsDev, void* stream ) const
+	{
+		check( mvrt_svo_read_voxels( m_handle, xyzDev, attribsDev, stream ), "IntersectorOctreeGPU::readVoxels" );
+	}
+	// host-vector forms, staged through mvrt_malloc / mvrt_memcpy_*: xyz = 3 entries per voxel, attribs = 2 per voxel (empty = defaults), ops = 1 per entry (empty = all SET)
+	void buildFromVoxels( const std::vector<uint32_t>& xyz, const std::vector<uint32_t>& attribs, vec3 origin, float dps, int gridRes, int buildFlags, void* stream )
+	{
+		const uint64_t n = xyz.size() / 3;
+		Staged x( xyz.data(), xyz.size() * 4, stream ), a( attribs.empty() ? nullptr : attribs.data(), attribs.size() * 4, stream );
+		buildFromVoxels( (const uint32_t*)x.p, (const uint32_t*)a.p, n, origin, dps, gridRes, buildFlags, stream );
+	}
+	void editVoxels( const std::vector<uint32_t>& xyz, const std::vector<uint32_t>& attribs, const std::vector<uint8_t>& ops, void* stream )
+	{
+		const uint64_t n = xyz.size() / 3;
+		Staged x( xyz.data(), xyz.size() * 4, stream ), a( attribs.empty() ? nullptr : attribs.data(), attribs.size() * 4, stream ),
+			o( ops.empty() ? nullptr : ops.data(), ops.size(), stream );
+		editVoxels( (const uint32_t*)x.p, (const uint32_t*)a.p, (const uint8_t*)o.p, n, stream );
+	}
+	void readVoxels( std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs, void* stream ) const
+	{
+		mvrt_svo_info i;
+		check( mvrt_svo_get_info( m_handle, &i ), "mvrt_svo_get_info" );
+		xyz.resize( (size_t)i.numberOfVoxels * 3 );
+		attribs.resize( (size_t)i.numberOfVoxels * 2 );
+		Staged x( nullptr, xyz.size() * 4, stream ), a( nullptr, attribs.size() * 4, stream );
+		readVoxels( (uint32_t*)x.p, (uint32_t*)a.p, stream );
+		check( mvrt_memcpy_d2h( xyz.data(), x.p, xyz.size() * 4, stream ), "mvrt_memcpy_d2h" );
+		check( mvrt_memcpy_d2h( attribs.data(), a.p, attribs.size() * 4, stream ), "mvrt_memcpy_d2h" );
+	}
+
 	// batch form of the device method intersect() (:243-251): SoA device arrays
 	void intersect( uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz, const uint8_t* isShadowRay, float* t,
 					int32_t* nMajor, uint32_t* vIndex, void* stream ) const
@@ -133,6 +176,19 @@ struct IntersectorOctreeGPU
 	}
 
 private:
+	struct Staged // a device copy of host data (or uninitialised device memory when src is null and bytes != 0); no allocation for an absent array
+	{
+		void* p = nullptr;
+		Staged( const void* src, uint64_t bytes, void* stream )
+		{
+			if( !bytes ) return;
+			check( mvrt_malloc( &p, bytes ), "mvrt_malloc" );
+			if( src ) check( mvrt_memcpy_h2d( p, src, bytes, stream ), "mvrt_memcpy_h2d" );
+		}
+		~Staged() { mvrt_free( p ); }
+		Staged( const Staged& ) = delete;
+		void operator=( const Staged& ) = delete;
+	};
 	mvrt_svo* m_handle = nullptr;
 	bool m_owned = true;
 };

@@ -64,6 +64,9 @@ SIGNATURES = {
     "mvrt_svo_build_ex": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _f32, _i32, _i32]),
     "mvrt_svo_build_synthetic": (_i32, [_vp, _i32, _u64, _u64, _vp, _f32, _i32, _vp]),
     "mvrt_svo_upload": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, _f32, _i32, _i32, _i32, _vp]),
+    "mvrt_svo_build_voxels": (_i32, [_vp, _vp, _vp, _u64, _vp, _f32, _i32, _i32, _vp]),
+    "mvrt_svo_edit_voxels": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "mvrt_svo_read_voxels": (_i32, [_vp, _vp, _vp, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
     "mvrt_svo_device_view": (_i32, [_vp, _vp]),
@@ -266,6 +269,57 @@ class IntersectorOctreeGPU:
         o = np.ascontiguousarray(origin, np.float32)
         _check(lib().mvrt_svo_build_ex(self._h, _hp(v), _hp(c), _hp(e), len(v), stream, _hp(o), float(np.float32(dps)), int(gridRes), int(flags)))
 
+    VOXEL_REMOVE = 0
+    VOXEL_SET = 1
+
+    @staticmethod
+    def _voxel_arrays(xyz, attribs, ops):
+        """numpy arrays are copied to the device; DeviceArray (or raw device pointers / torch tensors with data_ptr()) are passed as they are.
+        Returns (n, keep-alive list, xyz ptr, attribs ptr, ops ptr)."""
+        keep = []
+
+        def dev(a, dtype, width):
+            if a is None:
+                return None, None
+            if isinstance(a, np.ndarray):
+                a = np.ascontiguousarray(a, dtype).reshape(-1, width) if width > 1 else np.ascontiguousarray(a, dtype).reshape(-1)
+                d = DeviceArray.from_host(a)
+                keep.append(d)
+                return d.ptr, len(a)
+            if isinstance(a, DeviceArray):
+                return a.ptr, a.nbytes // (np.dtype(dtype).itemsize * width)
+            return _dev_ptr(a), None
+
+        px, n = dev(xyz, np.uint32, 3)
+        if n is None:
+            raise ValueError("xyz must be a numpy array or a DeviceArray (the entry count is taken from it)")
+        pa, na = dev(None if attribs is None else (np.ascontiguousarray(attribs).view(np.uint8).reshape(-1, 8) if isinstance(attribs, np.ndarray) else attribs), np.uint8, 8)
+        po, no = dev(ops, np.uint8, 1)
+        for m, what in ((na, "attribs"), (no, "ops")):
+            if m is not None and m != n:
+                raise ValueError("%s has %d entries, xyz %d" % (what, m, n))
+        return n, keep, px, pa, po
+
+    def build_voxels(self, xyz, attribs=None, origin=(0.0, 0.0, 0.0), dps=None, gridRes=None, flags=0, stream=None):
+        """mvrt_svo_build_voxels: xyz (n, 3) uint32 in [0, gridRes), attribs (n, 8) uint8 VoxelAttirb {color, emission} or None (white, no emission).
+        Duplicates merge like the reference's unique (integer mean).  flags: BUILD_NO_DAG | BUILD_NO_EMBEDDED_MASK."""
+        n, keep, px, pa, _ = self._voxel_arrays(xyz, attribs, None)
+        o = np.ascontiguousarray(origin, np.float32)
+        dps = np.float32(1.0 / gridRes) if dps is None else np.float32(dps)
+        _check(lib().mvrt_svo_build_voxels(self._h, px, pa, n, _hp(o), float(dps), int(gridRes), int(flags), stream))
+
+    def edit_voxels(self, xyz, attribs=None, ops=None, stream=None):
+        """mvrt_svo_edit_voxels: ops per entry VOXEL_SET (1) / VOXEL_REMOVE (0), None = all SET; the last entry per voxel wins."""
+        n, keep, px, pa, po = self._voxel_arrays(xyz, attribs, ops)
+        _check(lib().mvrt_svo_edit_voxels(self._h, px, pa, po, n, stream))
+
+    def read_voxels(self, stream=None):
+        """mvrt_svo_read_voxels -> (xyz (n, 3) uint32, attribs (n, 8) uint8), sorted by Morton code (= vIndex order)"""
+        n = self.info().numberOfVoxels
+        xyz, at = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8)
+        _check(lib().mvrt_svo_read_voxels(self._h, xyz.ptr, at.ptr, stream))
+        return xyz.to_host(), at.to_host()
+
     def upload(self, nodes68, attribs, origin, dps, gridRes, hasEmission=0, embeddedMask=True, stream=None):
         nodes68 = np.ascontiguousarray(nodes68)
         assert nodes68.dtype.itemsize == 68 or nodes68.dtype == np.uint8
@@ -292,7 +346,7 @@ class IntersectorOctreeGPU:
 
     def device_view(self):
         """mvrt_svo_device_view: the ctypes DeviceOctree a HIP kernel built on include/mvrt/device.hpp takes by value.
-        A snapshot: any later build / upload / cleanUp of this object invalidates it."""
+        A snapshot: any later build (build_voxels included) / edit_voxels / upload / cleanUp of this object invalidates it."""
         v = DeviceOctree()
         _check(lib().mvrt_svo_device_view(self._h, C.byref(v)))
         return v

@@ -154,6 +154,7 @@ struct mvrt_svo
 	mvrt_svo_info info;
 	uint8_t rootMask = 0;
 	uint32_t leafPsumIsPopcount = 1; // (uploads: checked, see launchCheckLeafPsum)
+	int buildFlags = 0;				 // MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK of the build, kept by edits
 	mvrt_pt* owner = nullptr; // the PathTracer this is the m_intersectorOctreeGPU of (its deferred / in-flight steps read this octree)
 	mvrt_svo()
 	{
@@ -382,8 +383,9 @@ static int buildCellIndex( mvrt_svo* s, hipStream_t st )
 	return 0;
 }
 
-static int adoptBuild( mvrt_svo* svo, const SvoBuildResult& r, const float origin[3], float dps, int gridRes )
+static int adoptBuild( mvrt_svo* svo, const SvoBuildResult& r, const float origin[3], float dps, int gridRes, int flags )
 {
+	svo->buildFlags = flags & ( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK );
 	svo->nodes = r.nodes;
 	svo->masks = r.masks;
 	svo->psumCold = r.psumCold;
@@ -419,7 +421,7 @@ MVRT_EXPORT int mvrt_svo_build_ex( mvrt_svo* svo, const float* verticesHost, con
 	SvoBuildResult r;
 	memset( &r, 0, sizeof( r ) );
 	if( svoBuildFromTriangles( verticesHost, vcolorsHost, vemissionsHost, nVertices, mk3( origin[0], origin[1], origin[2] ), dps, gridRes, flags, st, &r ) ) return 1;
-	return adoptBuild( svo, r, origin, dps, gridRes );
+	return adoptBuild( svo, r, origin, dps, gridRes, flags );
 }
 MVRT_EXPORT int mvrt_svo_build( mvrt_svo* svo, const float* verticesHost, const float* vcolorsHost, const float* vemissionsHost, uint64_t nVertices, void* stream,
 								const float origin[3], float dps, int gridRes )
@@ -435,7 +437,61 @@ MVRT_EXPORT int mvrt_svo_build_synthetic( mvrt_svo* svo, int gridRes, uint64_t n
 	SvoBuildResult r;
 	memset( &r, 0, sizeof( r ) );
 	if( svoBuildSynthetic( nRandomVoxels, seed, gridRes, flags, (hipStream_t)stream, &r ) ) return 1;
-	return adoptBuild( svo, r, origin, dps, gridRes );
+	return adoptBuild( svo, r, origin, dps, gridRes, flags );
+}
+
+// Voxel lists.  Every failure leaves the handle as it was: arguments are checked on the host first, the device checks (coordinates, ops) come before anything is
+// replaced, and a structural edit builds the new list and levels next to the old octree before it releases it.
+MVRT_EXPORT int mvrt_svo_build_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t* attribsDev, uint64_t n, const float origin[3], float dps, int gridRes, int flags,
+									   void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_build_voxels: null handle" );
+	REQUIRE( xyzDev && origin, "mvrt_svo_build_voxels: null coordinates or origin" );
+	REQUIRE( n >= 1 && n < 0xFFFFFFFFull, "mvrt_svo_build_voxels: voxel count %llu is not in [1, 2^32-2]", (unsigned long long)n );
+	REQUIRE( ilog2Exact( gridRes ) > 0 && gridRes <= ( 1 << 21 ), "mvrt_svo_build_voxels: gridRes %d is not a power of two in [2, 2^21]", gridRes );
+	REQUIRE( ( flags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0,
+			 "mvrt_svo_build_voxels: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", flags );
+	hipStream_t st = (hipStream_t)stream;
+	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
+	SvoBuildResult r;
+	memset( &r, 0, sizeof( r ) );
+	if( svoBuildFromVoxels( xyzDev, attribsDev, n, gridRes, flags, st, &r ) ) return 1;
+	svo->cleanUp();
+	return adoptBuild( svo, r, origin, dps, gridRes, flags );
+}
+MVRT_EXPORT int mvrt_svo_edit_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t* attribsDev, const uint8_t* opsDev, uint64_t n, void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_edit_voxels: null handle" );
+	REQUIRE( svo->nodes, "mvrt_svo_edit_voxels: no octree (build first)" );
+	REQUIRE( svo->morton, "mvrt_svo_edit_voxels: an uploaded octree keeps no Morton codes; only octrees built by this library can be edited" );
+	REQUIRE( xyzDev, "mvrt_svo_edit_voxels: null coordinates" );
+	REQUIRE( n >= 1 && n < 0xFFFFFFFFull, "mvrt_svo_edit_voxels: entry count %llu is not in [1, 2^32-2]", (unsigned long long)n );
+	hipStream_t st = (hipStream_t)stream;
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene; an attribute-only edit writes in place
+	SvoBuildResult r;
+	memset( &r, 0, sizeof( r ) );
+	int structural = 0;
+	uint32_t he = 0;
+	if( svoEditVoxels( svo->morton, svo->attrs, svo->info.numberOfVoxels, xyzDev, attribsDev, opsDev, n, (int)svo->info.gridRes, svo->buildFlags, st, &r, &structural, &he ) )
+		return 1;
+	svo->info.totalDumpedVoxels = 0;
+	if( !structural )
+	{
+		svo->info.hasEmission = he;
+		return 0;
+	}
+	const float origin[3] = { svo->info.lower[0], svo->info.lower[1], svo->info.lower[2] };
+	const float dps = svo->info.dps;
+	const int gridRes = (int)svo->info.gridRes, flags = svo->buildFlags;
+	svo->cleanUp(); // keeps the emission scale
+	return adoptBuild( svo, r, origin, dps, gridRes, flags );
+}
+MVRT_EXPORT int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attribsDev, void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_read_voxels: null handle" );
+	REQUIRE( svo->nodes, "mvrt_svo_read_voxels: no octree (build first)" );
+	REQUIRE( svo->morton, "mvrt_svo_read_voxels: an uploaded octree keeps no Morton codes" );
+	return svoReadVoxels( svo->morton, svo->attrs, svo->info.numberOfVoxels, xyzDev, attribsDev, (hipStream_t)stream );
 }
 
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )

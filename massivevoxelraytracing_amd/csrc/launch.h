@@ -123,3 +123,10 @@ struct SvoBuildResult
 int svoBuildFromTriangles( const float* vertsHost, const float* colsHost, const float* emisHost, uint64_t nVertices, f3 origin, float dps, int gridRes, int flags,
 						   hipStream_t stream, SvoBuildResult* out );
 int svoBuildSynthetic( uint64_t nRandomVoxels, uint64_t seed, int gridRes, int flags, hipStream_t stream, SvoBuildResult* out );
+// voxel lists (device arrays): xyz = 3 x u32 per entry, attribs = VoxelAttirb (8 bytes) per entry or NULL (white, no emission)
+int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n, int gridRes, int flags, hipStream_t stream, SvoBuildResult* out );
+// a batch of edits (ops: 0 remove, 1 set; NULL = all set; last entry per voxel wins) against the sorted unique list of a build.  *structural = 1: out holds the
+// new octree (the old arrays are untouched); 0: the attributes were changed in place (node structure unchanged), *hasEmissionOut = the new flag
+int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, int flags,
+				   hipStream_t stream, SvoBuildResult* out, int* structural, uint32_t* hasEmissionOut );
+int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t stream );

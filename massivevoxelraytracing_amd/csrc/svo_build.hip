@@ -822,6 +822,301 @@ __global__ void __launch_bounds__( BB ) kSyntheticVoxels( uint64_t n, uint64_t s
 	}
 }
 
+// ---- voxel lists: build from xyz, batched edits, read-back (mvrt_svo_build_voxels / _edit_voxels / _read_voxels) ----------------------------------
+// encode + validate: xyz (3 x u32) + VoxelAttirb (NULL = white, no emission) -> (Morton, attribute with both alphas 255).  ENC_PER entries per thread: 48 bytes of
+// coordinates = three 16-byte loads (vec: the caller's arrays are 16-byte aligned).  firstBad[0] / [1]: lowest entry outside the grid / with an op byte other than
+// MVRT_VOXEL_REMOVE (0) or MVRT_VOXEL_SET (1), one atomicMin per wave.  idxOut (edits): the batch index, the value of the stable sort that follows.
+#define ENC_PER 4
+MVRT_DI void store2( uint64_t* p, uint64_t a, uint64_t b ) { *(uint4*)p = make_uint4( (uint32_t)a, (uint32_t)( a >> 32 ), (uint32_t)b, (uint32_t)( b >> 32 ) ); }
+__global__ void __launch_bounds__( BB ) kEncodeVoxels( const uint32_t* __restrict__ xyz, const uint32_t* __restrict__ attribs, const uint8_t* __restrict__ ops, uint64_t n, uint32_t gridRes,
+														int vec, uint64_t* __restrict__ keysOut, uint64_t* __restrict__ valsOut, uint32_t* __restrict__ idxOut,
+														unsigned long long* __restrict__ firstBad )
+{
+	const uint64_t nQuads = ( n + ENC_PER - 1 ) / ENC_PER;
+	const uint64_t nBlocks = ( nQuads + BB - 1 ) / BB;
+	const uint32_t lane = threadIdx.x & ( WAVE - 1 );
+	for( uint64_t vb = blockIdx.x; vb < nBlocks; vb += gridDim.x )
+	{
+		const uint64_t q = vb * BB + threadIdx.x;
+		const uint64_t i0 = q * ENC_PER;
+		const int cnt = q < nQuads ? (int)( n - i0 < ENC_PER ? n - i0 : ENC_PER ) : 0;
+		uint32_t c[ENC_PER * 3] = {}, a[ENC_PER * 2] = {};
+		if( vec && cnt == ENC_PER )
+		{
+			const uint4* p = (const uint4*)( xyz + i0 * 3 );
+			const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
+			c[0] = v0.x; c[1] = v0.y; c[2] = v0.z; c[3] = v0.w; c[4] = v1.x; c[5] = v1.y;
+			c[6] = v1.z; c[7] = v1.w; c[8] = v2.x; c[9] = v2.y; c[10] = v2.z; c[11] = v2.w;
+			if( attribs )
+			{
+				const uint4* pa = (const uint4*)( attribs + i0 * 2 );
+				const uint4 w0 = pa[0], w1 = pa[1];
+				a[0] = w0.x; a[1] = w0.y; a[2] = w0.z; a[3] = w0.w; a[4] = w1.x; a[5] = w1.y; a[6] = w1.z; a[7] = w1.w;
+			}
+		}
+		else
+		{
+#pragma unroll
+			for( int k = 0; k < ENC_PER; k++ )
+			{
+				if( k >= cnt ) continue;
+				c[3 * k] = xyz[( i0 + k ) * 3];
+				c[3 * k + 1] = xyz[( i0 + k ) * 3 + 1];
+				c[3 * k + 2] = xyz[( i0 + k ) * 3 + 2];
+				if( attribs )
+				{
+					a[2 * k] = attribs[( i0 + k ) * 2];
+					a[2 * k + 1] = attribs[( i0 + k ) * 2 + 1];
+				}
+			}
+		}
+		if( !attribs )
+		{
+#pragma unroll
+			for( int k = 0; k < ENC_PER; k++ )
+			{
+				a[2 * k] = 0xFFFFFFFFu; // white (voxUtil.hpp:49-61)
+				a[2 * k + 1] = 0u;		// no emission
+			}
+		}
+		uint64_t bad = ~0ull, badOp = ~0ull, key[ENC_PER], val[ENC_PER];
+#pragma unroll
+		for( int k = 0; k < ENC_PER; k++ )
+		{
+			const uint64_t i = i0 + k;
+			const uint32_t x = c[3 * k], y = c[3 * k + 1], z = c[3 * k + 2];
+			if( k < cnt && ( x >= gridRes || y >= gridRes || z >= gridRes ) && bad == ~0ull ) bad = i;
+			if( k < cnt && ops && ops[i] > 1u && badOp == ~0ull ) badOp = i;
+			key[k] = k < cnt ? mortonEncode( x, y, z ) : 0;
+			val[k] = (uint64_t)( a[2 * k] | 0xFF000000u ) | (uint64_t)( a[2 * k + 1] | 0xFF000000u ) << 32;
+		}
+		if( cnt == ENC_PER )
+		{
+			store2( keysOut + i0, key[0], key[1] );
+			store2( keysOut + i0 + 2, key[2], key[3] );
+			store2( valsOut + i0, val[0], val[1] );
+			store2( valsOut + i0 + 2, val[2], val[3] );
+			if( idxOut ) *(uint4*)( idxOut + i0 ) = make_uint4( (uint32_t)i0, (uint32_t)i0 + 1, (uint32_t)i0 + 2, (uint32_t)i0 + 3 );
+		}
+		else
+		{
+#pragma unroll
+			for( int k = 0; k < ENC_PER; k++ )
+			{
+				if( k >= cnt ) continue;
+				keysOut[i0 + k] = key[k];
+				valsOut[i0 + k] = val[k];
+				if( idxOut ) idxOut[i0 + k] = (uint32_t)( i0 + k );
+			}
+		}
+		// lanes hold ascending index ranges: the lowest lane with a bad entry has the wave's lowest
+		unsigned long long m = __ballot( bad != ~0ull );
+		if( m && lane == (uint32_t)__builtin_ctzll( m ) ) atomicMin( &firstBad[0], (unsigned long long)bad );
+		m = __ballot( badOp != ~0ull );
+		if( m && lane == (uint32_t)__builtin_ctzll( m ) ) atomicMin( &firstBad[1], (unsigned long long)badOp );
+	}
+}
+
+MVRT_DI uint64_t lowerBound( const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key )
+{
+	while( lo < hi )
+	{
+		const uint64_t mid = ( lo + hi ) >> 1;
+		if( a[mid] < key ) lo = mid + 1;
+		else hi = mid;
+	}
+	return lo;
+}
+MVRT_DI uint2 asAttr( uint64_t v ) { return make_uint2( (uint32_t)v, (uint32_t)( v >> 32 ) ); }
+
+enum EditKind : uint8_t
+{
+	EDIT_NOOP = 0,	  // REMOVE of an absent voxel
+	EDIT_INSERT = 1,  // SET of an absent voxel
+	EDIT_REPLACE = 2, // SET of an existing voxel
+	EDIT_REMOVE = 3	  // REMOVE of an existing voxel
+};
+// edits sorted by (Morton, batch index): the LAST entry of each key survives
+__global__ void __launch_bounds__( BB ) kEditTailCount( const uint64_t* __restrict__ keys, uint64_t n, uint32_t* __restrict__ blockCount )
+{
+	countBody( [=]( uint64_t k ) { return k + 1 == n || keys[k + 1] != keys[k]; }, n, blockCount );
+}
+// survivors -> the sorted unique edit list, each classified against the old sorted voxel list (binary search: pos = its rank among the old codes).
+// eInc = (insert, removal) as the low / high word, exclusively scanned afterwards; counts[0..2] = inserts, removals, replacements
+__global__ void __launch_bounds__( BB ) kEditClassify( const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx, uint64_t n, const uint32_t* __restrict__ blockOff,
+														const uint64_t* __restrict__ attrN, const uint8_t* __restrict__ ops, const uint64_t* __restrict__ oldMorton, uint32_t nOld,
+														uint64_t* __restrict__ eKeys, uint64_t* __restrict__ eAttr, uint32_t* __restrict__ ePos, uint8_t* __restrict__ eKind,
+														unsigned long long* __restrict__ eInc, uint32_t* __restrict__ counts )
+{
+	__shared__ uint32_t wc[BB / WAVE];
+	const uint64_t nBlocks = ( n + BB - 1 ) / BB;
+	const uint32_t lane = threadIdx.x & ( WAVE - 1 );
+	for( uint64_t vb = blockIdx.x; vb < nBlocks; vb += gridDim.x )
+	{
+		const uint64_t k = vb * BB + threadIdx.x;
+		const bool tail = k < n ? ( k + 1 == n || keys[k + 1] != keys[k] ) : false;
+		const uint32_t r = rankInBlock( tail, wc );
+		uint32_t kind = EDIT_NOOP;
+		if( tail )
+		{
+			const uint64_t key = keys[k];
+			const uint32_t j = idx[k];
+			const uint32_t op = ops ? ops[j] : 1u;
+			const uint64_t pos = lowerBound( oldMorton, 0, nOld, key );
+			const bool found = pos < nOld && oldMorton[pos] == key;
+			kind = op ? ( found ? EDIT_REPLACE : EDIT_INSERT ) : ( found ? EDIT_REMOVE : EDIT_NOOP );
+			const uint64_t e = (uint64_t)blockOff[vb] + r;
+			eKeys[e] = key;
+			eAttr[e] = attrN[j];
+			ePos[e] = (uint32_t)pos;
+			eKind[e] = (uint8_t)kind;
+			eInc[e] = ( kind == EDIT_INSERT ? 1ull : 0ull ) | ( kind == EDIT_REMOVE ? 1ull << 32 : 0ull );
+		}
+		const unsigned long long mi = __ballot( tail && kind == EDIT_INSERT ), mr = __ballot( tail && kind == EDIT_REMOVE ), mp = __ballot( tail && kind == EDIT_REPLACE );
+		if( lane == 0 )
+		{
+			if( mi ) atomicAdd( &counts[0], (uint32_t)__popcll( mi ) );
+			if( mr ) atomicAdd( &counts[1], (uint32_t)__popcll( mr ) );
+			if( mp ) atomicAdd( &counts[2], (uint32_t)__popcll( mp ) );
+		}
+	}
+}
+// structural edit, old side: one streaming pass over the old (Morton, attribute) arrays, MERGE_PER voxels per thread with 16-byte loads.  Old voxel i lands at
+// i + (inserts before it) - (removals before it), both read from the scanned edit list at e = lower_bound( edits, its code ); the edits a block of voxels can meet
+// lie between the bounds of its first and last code (the common case: none, and no lane searches).
+#define MERGE_PER 2
+__global__ void __launch_bounds__( BB ) kMergeOld( const uint64_t* __restrict__ oldMorton, const uint2* __restrict__ oldAttrs, uint32_t nOld, const uint64_t* __restrict__ eKeys,
+													const uint64_t* __restrict__ eAttr, const uint8_t* __restrict__ eKind, const unsigned long long* __restrict__ ePre, uint32_t nE,
+													uint64_t* __restrict__ newMorton, uint2* __restrict__ newAttrs, uint32_t* __restrict__ hasEmission )
+{
+	__shared__ uint32_t range[2];
+	const uint64_t per = (uint64_t)BB * MERGE_PER;
+	const uint64_t nBlocks = ( nOld + per - 1 ) / per;
+	for( uint64_t vb = blockIdx.x; vb < nBlocks; vb += gridDim.x )
+	{
+		const uint64_t b0 = vb * per, b1 = b0 + per < nOld ? b0 + per : nOld;
+		if( threadIdx.x == 0 )
+		{
+			range[0] = (uint32_t)lowerBound( eKeys, 0, nE, oldMorton[b0] );
+			range[1] = (uint32_t)lowerBound( eKeys, range[0], nE, oldMorton[b1 - 1] );
+		}
+		__syncthreads();
+		const uint64_t lo = range[0], hi = range[1];
+		__syncthreads();
+		const uint64_t i = b0 + (uint64_t)threadIdx.x * MERGE_PER;
+		bool em = false;
+		if( i < b1 )
+		{
+			uint64_t m[MERGE_PER];
+			uint2 a[MERGE_PER];
+			const int cnt = i + 1 < b1 ? 2 : 1;
+			if( cnt == 2 )
+			{
+				const uint4 mm = *(const uint4*)( oldMorton + i );
+				const uint4 aa = *(const uint4*)( oldAttrs + i );
+				m[0] = (uint64_t)mm.x | (uint64_t)mm.y << 32;
+				m[1] = (uint64_t)mm.z | (uint64_t)mm.w << 32;
+				a[0] = make_uint2( aa.x, aa.y );
+				a[1] = make_uint2( aa.z, aa.w );
+			}
+			else
+			{
+				m[0] = oldMorton[i];
+				a[0] = oldAttrs[i];
+				m[1] = 0;
+				a[1] = make_uint2( 0, 0 );
+			}
+#pragma unroll
+			for( int k = 0; k < MERGE_PER; k++ )
+			{
+				if( k >= cnt ) continue;
+				const uint64_t e = lo == hi ? lo : lowerBound( eKeys, lo, hi, m[k] );
+				const uint32_t kind = e < nE && eKeys[e] == m[k] ? eKind[e] : (uint32_t)EDIT_NOOP;
+				if( kind == EDIT_REMOVE ) continue;
+				const uint2 at = kind == EDIT_REPLACE ? asAttr( eAttr[e] ) : a[k];
+				const unsigned long long p = ePre[e];
+				const uint64_t out = i + k + (uint32_t)p - (uint32_t)( p >> 32 );
+				newMorton[out] = m[k];
+				newAttrs[out] = at;
+				em |= ( at.y & 0xFFFFFFu ) != 0u;
+			}
+		}
+		if( __ballot( em ) && ( threadIdx.x & ( WAVE - 1 ) ) == 0 ) atomicOr( hasEmission, 1u );
+	}
+}
+// structural edit, insert side: insert e lands after the old voxels below it (ePos) minus the removals and plus the inserts before it
+__global__ void __launch_bounds__( BB ) kMergeInserts( const uint64_t* __restrict__ eKeys, const uint64_t* __restrict__ eAttr, const uint8_t* __restrict__ eKind,
+														const uint32_t* __restrict__ ePos, const unsigned long long* __restrict__ ePre, uint32_t nE, uint64_t* __restrict__ newMorton,
+														uint2* __restrict__ newAttrs, uint32_t* __restrict__ hasEmission )
+{
+	for( uint64_t e = (uint64_t)blockIdx.x * BB + threadIdx.x; e < nE; e += (uint64_t)gridDim.x * BB )
+	{
+		if( eKind[e] != EDIT_INSERT ) continue;
+		const unsigned long long p = ePre[e];
+		const uint64_t out = (uint64_t)ePos[e] + (uint32_t)p - (uint32_t)( p >> 32 );
+		const uint2 at = asAttr( eAttr[e] );
+		newMorton[out] = eKeys[e];
+		newAttrs[out] = at;
+		if( at.y & 0xFFFFFFu ) atomicOr( hasEmission, 1u );
+	}
+}
+// attribute-only edit: new attributes in place (vIndex = Morton rank does not move), then hasEmission of the whole set again (it can turn either way)
+__global__ void __launch_bounds__( BB ) kScatterAttrs( const uint64_t* __restrict__ eAttr, const uint8_t* __restrict__ eKind, const uint32_t* __restrict__ ePos, uint32_t nE,
+														uint2* __restrict__ attrs )
+{
+	for( uint64_t e = (uint64_t)blockIdx.x * BB + threadIdx.x; e < nE; e += (uint64_t)gridDim.x * BB )
+		if( eKind[e] == EDIT_REPLACE ) attrs[ePos[e]] = asAttr( eAttr[e] );
+}
+__global__ void __launch_bounds__( BB ) kAnyEmission( const uint2* __restrict__ attrs, uint32_t n, uint32_t* __restrict__ hasEmission )
+{
+	const uint64_t nPairs = ( (uint64_t)n + 1 ) / 2;
+	const uint64_t nBlocks = ( nPairs + BB - 1 ) / BB;
+	for( uint64_t vb = blockIdx.x; vb < nBlocks; vb += gridDim.x )
+	{
+		const uint64_t i = ( vb * BB + threadIdx.x ) * 2;
+		bool em = false;
+		if( i + 1 < n )
+		{
+			const uint4 aa = *(const uint4*)( attrs + i );
+			em = ( ( aa.y | aa.w ) & 0xFFFFFFu ) != 0u;
+		}
+		else if( i < n )
+			em = ( attrs[i].y & 0xFFFFFFu ) != 0u;
+		if( __ballot( em ) && ( threadIdx.x & ( WAVE - 1 ) ) == 0 ) atomicOr( hasEmission, 1u );
+	}
+}
+// read-back: Morton decode -> xyz, attributes copied
+MVRT_HDI uint32_t compactBy3( uint64_t x )
+{
+	x &= 0x1249249249249249ull;
+	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
+	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
+	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
+	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
+	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
+	return (uint32_t)x;
+}
+__global__ void __launch_bounds__( BB ) kReadVoxels( const uint64_t* __restrict__ morton, const uint2* __restrict__ attrs, uint32_t n, uint32_t* __restrict__ xyz,
+													  uint32_t* __restrict__ attribs )
+{
+	for( uint64_t i = (uint64_t)blockIdx.x * BB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BB )
+	{
+		const uint64_t m = morton[i];
+		if( xyz )
+		{
+			xyz[i * 3] = compactBy3( m );
+			xyz[i * 3 + 1] = compactBy3( m >> 1 );
+			xyz[i * 3 + 2] = compactBy3( m >> 2 );
+		}
+		if( attribs )
+		{
+			const uint2 a = attrs[i];
+			attribs[i * 2] = a.x;
+			attribs[i * 2 + 1] = a.y;
+		}
+	}
+}
+
 struct MaxOp
 {
 	__host__ __device__ uint32_t operator()( uint32_t a, uint32_t b ) const { return a > b ? a : b; }
@@ -907,13 +1202,28 @@ int svoBuildSynthetic( uint64_t nRandomVoxels, uint64_t seed, int gridRes, int f
 	return buildFromFragments( keysA, valsA, nRandomVoxels, gridRes, flags, st, counter, (uint32_t*)( counter + 1 ), (uint32_t*)( counter + 2 ), out );
 }
 
+static int sortUnique( Buf& keysA, Buf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, Buf& morton, Buf& attrs,
+					   uint32_t* nVoxelsOut );
+static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
+						uint32_t* scalarOut, SvoBuildResult* out );
+
+// everything after voxelization: sort + unique of the (Morton, attribute) fragments, then the levels
 static int buildFromFragments( Buf& keysA, Buf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,
 							   uint32_t* scalarOut, SvoBuildResult* out )
 {
 	(void)counter;
 	int levels = 0;
 	while( ( 1 << levels ) < gridRes ) levels++;
-	const bool dag = !( flags & 1 );
+	Buf morton, attrs;
+	uint32_t nVoxels = 0;
+	if( sortUnique( keysA, valsA, totalDumped, levels, st, hasEmission, scalarOut, morton, attrs, &nVoxels ) ) return 1;
+	return buildLevels( morton, attrs, nVoxels, totalDumped, gridRes, flags, st, hasEmission, scalarOut, out );
+}
+
+// (keysA, valsA): totalDumped unsorted fragments (released here) -> morton / attrs: the sorted unique codes and their integer-mean attributes; *hasEmission |= any emission
+static int sortUnique( Buf& keysA, Buf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, Buf& morton, Buf& attrs,
+					   uint32_t* nVoxelsOut )
+{
 	Buf keysB, valsB;
 	if( keysB.alloc( totalDumped * 8 ) || valsB.alloc( totalDumped * 8 ) ) return 1;
 	// ---- sort (IntersectorOctreeGPU.hpp:117-124) ----
@@ -938,13 +1248,23 @@ static int buildFromFragments( Buf& keysA, Buf& valsA, unsigned long long totalD
 	uint32_t nVoxels = 0;
 	MVRT_HIP( hipMemcpyAsync( &nVoxels, scalarOut, 4, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) );
-	Buf morton, attrs;
 	if( morton.alloc( (uint64_t)nVoxels * 8 ) || attrs.alloc( (uint64_t)nVoxels * 8 ) ) return 1;
 	hipLaunchKernelGGL( kUniqueEmit, dim3( gridFor( totalDumped ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), valsB.as<uint64_t>(), (uint64_t)totalDumped,
 						blockCnt.as<uint32_t>(), morton.as<uint64_t>(), attrs.as<uint2>(), hasEmission );
 	MVRT_HIP( hipStreamSynchronize( st ) );
-	keysB.release();
-	valsB.release();
+	*nVoxelsOut = nVoxels;
+	return 0;
+}
+
+// the levels of the octree over nVoxels sorted unique codes (morton / attrs are handed to *out on success); hasEmission: the device flag of the voxel set
+static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
+						uint32_t* scalarOut, SvoBuildResult* out )
+{
+	int levels = 0;
+	while( ( 1 << levels ) < gridRes ) levels++;
+	const bool dag = !( flags & 1 );
+	Buf blockCnt;
+	if( blockCnt.alloc( ( (uint64_t)nVoxels / BB + 2 ) * 4 ) ) return 1;
 
 	// ---- upper bound on nodes: distinct parents per level (octreeTaskInit's taskCounters, voxKernel.cu:257-265) ----
 	// counted on the host from the per-level group counts as the levels are built; the node buffer grows by level.
@@ -1187,5 +1507,159 @@ static int buildFromFragments( Buf& keysA, Buf& valsA, unsigned long long totalD
 	out->hasEmission = he;
 	out->embedded = embed ? 1 : 0;
 	out->totalDumped = totalDumped;
+	return 0;
+}
+
+// ---- voxel lists ----------------------------------------------------------------------------------------------------------------------------
+// scratch of the voxel-list calls: [0] unused, [8] hasEmission, [16] scalarOut (as buildFromFragments), [32] firstBad[2], [48] edit counts[3]
+struct ListScratch
+{
+	Buf b;
+	unsigned long long* base() const { return b.as<unsigned long long>(); }
+	uint32_t* hasEmission() const { return (uint32_t*)( base() + 1 ); }
+	uint32_t* scalarOut() const { return (uint32_t*)( base() + 2 ); }
+	unsigned long long* firstBad() const { return base() + 4; }
+	uint32_t* counts() const { return (uint32_t*)( base() + 6 ); }
+	int init( hipStream_t st )
+	{
+		if( b.alloc( 64 ) ) return 1;
+		MVRT_HIP( hipMemsetAsync( b.p, 0, 64, st ) );
+		MVRT_HIP( hipMemsetAsync( firstBad(), 0xFF, 16, st ) );
+		return 0;
+	}
+};
+
+// encode + validate n entries into keys / vals (/ idx); a failure names the lowest offending entry
+static int encodeVoxels( const char* who, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, hipStream_t st, const ListScratch& sc,
+						 uint64_t* keys, uint64_t* vals, uint32_t* idx )
+{
+	const int vec = ( (uintptr_t)xyz % 16 == 0 && (uintptr_t)attribs % 16 == 0 ) ? 1 : 0;
+	hipLaunchKernelGGL( kEncodeVoxels, dim3( gridFor( ( n + ENC_PER - 1 ) / ENC_PER ) ), dim3( BB ), 0, st, xyz, attribs, ops, n, (uint32_t)gridRes, vec, keys, vals, idx,
+						sc.firstBad() );
+	unsigned long long bad[2] = { 0, 0 };
+	MVRT_HIP( hipMemcpyAsync( bad, sc.firstBad(), 16, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( bad[0] != ~0ull )
+	{
+		uint32_t c[3] = { 0, 0, 0 };
+		MVRT_HIP( hipMemcpy( c, xyz + bad[0] * 3, 12, hipMemcpyDeviceToHost ) );
+		mvrtSetError( "%s: entry %llu (%u, %u, %u) lies outside the %d^3 grid", who, bad[0], c[0], c[1], c[2], gridRes );
+		return 1;
+	}
+	if( bad[1] != ~0ull )
+	{
+		uint8_t op = 0;
+		MVRT_HIP( hipMemcpy( &op, ops + bad[1], 1, hipMemcpyDeviceToHost ) );
+		mvrtSetError( "%s: entry %llu has the unknown op %u (MVRT_VOXEL_REMOVE = 0, MVRT_VOXEL_SET = 1)", who, bad[1], (unsigned)op );
+		return 1;
+	}
+	return 0;
+}
+
+int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n, int gridRes, int flags, hipStream_t st, SvoBuildResult* out )
+{
+	ListScratch sc;
+	Buf keysA, valsA;
+	if( sc.init( st ) || keysA.alloc( n * 8 ) || valsA.alloc( n * 8 ) ) return 1;
+	if( encodeVoxels( "mvrt_svo_build_voxels", xyz, attribs, nullptr, n, gridRes, st, sc, keysA.as<uint64_t>(), valsA.as<uint64_t>(), nullptr ) ) return 1;
+	return buildFromFragments( keysA, valsA, n, gridRes, flags, st, sc.base(), sc.hasEmission(), sc.scalarOut(), out );
+}
+
+int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, int flags,
+				   hipStream_t st, SvoBuildResult* out, int* structural, uint32_t* hasEmissionOut )
+{
+	static const char* who = "mvrt_svo_edit_voxels";
+	int levels = 0;
+	while( ( 1 << levels ) < gridRes ) levels++;
+	ListScratch sc;
+	Buf keysA, attrN, idxA, keysB, idxB;
+	if( sc.init( st ) || keysA.alloc( n * 8 ) || attrN.alloc( n * 8 ) || idxA.alloc( n * 4 ) || keysB.alloc( n * 8 ) || idxB.alloc( n * 4 ) ) return 1;
+	if( encodeVoxels( who, xyz, attribs, ops, n, gridRes, st, sc, keysA.as<uint64_t>(), attrN.as<uint64_t>(), idxA.as<uint32_t>() ) ) return 1;
+	// stable sort of (Morton, batch index): within a key the batch order survives, its last entry wins
+	{
+		size_t tmpBytes = 0;
+		MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), idxA.as<uint32_t>(), idxB.as<uint32_t>(), n, 0, 3 * levels, st ) );
+		Buf tmp;
+		if( tmp.alloc( tmpBytes ) ) return 1;
+		MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( tmp.p, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), idxA.as<uint32_t>(), idxB.as<uint32_t>(), n, 0, 3 * levels, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+	}
+	keysA.release();
+	idxA.release();
+	// last entry per key -> the sorted unique edit list, classified against the old list
+	Buf blockCnt;
+	if( blockCnt.alloc( ( n / BB + 2 ) * 4 ) ) return 1;
+	hipLaunchKernelGGL( kEditTailCount, dim3( gridFor( n ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), n, blockCnt.as<uint32_t>() );
+	hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt.as<uint32_t>(), n, sc.scalarOut() );
+	uint32_t nE = 0;
+	MVRT_HIP( hipMemcpyAsync( &nE, sc.scalarOut(), 4, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	Buf eKeys, eAttr, ePos, eKind, eInc, ePre;
+	if( eKeys.alloc( (uint64_t)nE * 8 ) || eAttr.alloc( (uint64_t)nE * 8 ) || ePos.alloc( (uint64_t)nE * 4 ) || eKind.alloc( nE ) || eInc.alloc( ( (uint64_t)nE + 1 ) * 8 ) ||
+		ePre.alloc( ( (uint64_t)nE + 1 ) * 8 ) )
+		return 1;
+	MVRT_HIP( hipMemsetAsync( eInc.as<uint64_t>() + nE, 0, 8, st ) );
+	hipLaunchKernelGGL( kEditClassify, dim3( gridFor( n ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), idxB.as<uint32_t>(), n, blockCnt.as<uint32_t>(), attrN.as<uint64_t>(), ops,
+						oldMorton, nOld, eKeys.as<uint64_t>(), eAttr.as<uint64_t>(), ePos.as<uint32_t>(), eKind.as<uint8_t>(), eInc.as<unsigned long long>(), sc.counts() );
+	uint32_t counts[3] = { 0, 0, 0 };
+	MVRT_HIP( hipMemcpyAsync( counts, sc.counts(), 12, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	keysB.release();
+	idxB.release();
+	attrN.release();
+	const uint32_t nIns = counts[0], nRem = counts[1];
+	if( nIns == 0 && nRem == 0 ) // attribute-only (or nothing to do): the node structure stays, attributes change in place
+	{
+		if( nE ) hipLaunchKernelGGL( kScatterAttrs, dim3( gridFor( nE ) ), dim3( BB ), 0, st, eAttr.as<uint64_t>(), eKind.as<uint8_t>(), ePos.as<uint32_t>(), nE, oldAttrs );
+		hipLaunchKernelGGL( kAnyEmission, dim3( gridFor( ( (uint64_t)nOld + 1 ) / 2 ) ), dim3( BB ), 0, st, (const uint2*)oldAttrs, nOld, sc.hasEmission() );
+		uint32_t he = 0;
+		MVRT_HIP( hipMemcpyAsync( &he, sc.hasEmission(), 4, hipMemcpyDeviceToHost, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+		MVRT_HIP( hipGetLastError() );
+		*structural = 0;
+		*hasEmissionOut = he;
+		return 0;
+	}
+	if( (uint64_t)nOld + nIns - nRem == 0 )
+	{
+		mvrtSetError( "%s: the edit would remove every voxel of the octree", who );
+		return 1;
+	}
+	if( (uint64_t)nOld + nIns >= 0xFFFFFFFFull )
+	{
+		mvrtSetError( "%s: %llu voxels exceed the 32-bit index range of this builder", who, (unsigned long long)nOld + nIns );
+		return 1;
+	}
+	const uint32_t nNew = nOld + nIns - nRem;
+	{
+		size_t tmpBytes = 0;
+		MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( nullptr, tmpBytes, eInc.as<unsigned long long>(), ePre.as<unsigned long long>(), nE + 1, st ) );
+		Buf tmp;
+		if( tmp.alloc( tmpBytes ) ) return 1;
+		MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( tmp.p, tmpBytes, eInc.as<unsigned long long>(), ePre.as<unsigned long long>(), nE + 1, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+	}
+	Buf morton, attrs;
+	if( morton.alloc( (uint64_t)nNew * 8 ) || attrs.alloc( (uint64_t)nNew * 8 ) ) return 1;
+	hipLaunchKernelGGL( kMergeOld, dim3( gridFor( ( (uint64_t)nOld + MERGE_PER - 1 ) / MERGE_PER ) ), dim3( BB ), 0, st, oldMorton, (const uint2*)oldAttrs, nOld, eKeys.as<uint64_t>(),
+						eAttr.as<uint64_t>(), eKind.as<uint8_t>(), ePre.as<unsigned long long>(), nE, morton.as<uint64_t>(), attrs.as<uint2>(), sc.hasEmission() );
+	hipLaunchKernelGGL( kMergeInserts, dim3( gridFor( nE ) ), dim3( BB ), 0, st, eKeys.as<uint64_t>(), eAttr.as<uint64_t>(), eKind.as<uint8_t>(), ePos.as<uint32_t>(),
+						ePre.as<unsigned long long>(), nE, morton.as<uint64_t>(), attrs.as<uint2>(), sc.hasEmission() );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	eKeys.release();
+	eAttr.release();
+	ePos.release();
+	eKind.release();
+	eInc.release();
+	ePre.release();
+	*structural = 1;
+	return buildLevels( morton, attrs, nNew, 0, gridRes, flags, st, sc.hasEmission(), sc.scalarOut(), out );
+}
+
+int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t st )
+{
+	hipLaunchKernelGGL( kReadVoxels, dim3( gridFor( n ) ), dim3( BB ), 0, st, morton, attrs, n, xyz, attribs );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	MVRT_HIP( hipGetLastError() );
 	return 0;
 }

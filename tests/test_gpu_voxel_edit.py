@@ -1,0 +1,426 @@
+"""Voxel-list input, batched edits and read-back on the GPU (mvrt_svo_build_voxels / mvrt_svo_edit_voxels / mvrt_svo_read_voxels) against the oracle's
+merge_voxels + build_octree and a numpy model of the last-wins edit semantics: info, nodes (reference layout), attributes and Morton codes bit for bit."""
+import numpy as np
+import pytest
+
+from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+
+pytestmark = pytest.mark.gpu
+
+SET, REMOVE = 1, 0
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import oracle
+    return oracle
+
+
+@pytest.fixture(scope="module")
+def mv():
+    import massivevoxelraytracing_amd as m
+    m.lib()
+    return m
+
+
+def decode(m):
+    """Morton code -> (n, 3) uint32 (x = bit 0)"""
+    m = np.asarray(m, np.uint64)
+    out = np.zeros((len(m), 3), np.uint32)
+    for axis in range(3):
+        v = np.zeros(len(m), np.uint64)
+        for b in range(21):
+            v |= ((m >> np.uint64(3 * b + axis)) & np.uint64(1)) << np.uint64(b)
+        out[:, axis] = v.astype(np.uint32)
+    return out
+
+
+def normalised(attrs):
+    a = np.array(attrs, np.uint8).reshape(-1, 8)
+    a[:, 3] = 255
+    a[:, 7] = 255
+    return a
+
+
+def has_emission(attrs):
+    return int(np.any(attrs[:, 4:7] != 0))
+
+
+def oracle_octree(O, morton, grid_res, flags):
+    return O.build_octree(morton, grid_res, dag=not (flags & 1), embed=not (flags & 2))
+
+
+def assert_svo(O, svo, morton, attrs, he, grid_res, flags, dumped, nodes=None):
+    """the handle holds exactly the octree the oracle builds over (morton, attrs)"""
+    info = svo.info()
+    if nodes is None:
+        nodes = oracle_octree(O, morton, grid_res, flags)
+    assert info.totalDumpedVoxels == dumped
+    assert info.numberOfVoxels == len(morton)
+    assert info.numberOfNodes == len(nodes)
+    assert info.hasEmission == he
+    gn, ga, gm = svo.download(want_morton=True)
+    assert np.array_equal(gm, morton)
+    assert np.array_equal(ga, attrs)
+    got = gn.view(O.NODE_DTYPE)
+    for f in ("mask", "children", "psum"):
+        assert np.array_equal(got[f], nodes[f]), f
+
+
+def assert_same_handles(a, b):
+    ia, ib = a.info(), b.info()
+    for f in ("numberOfNodes", "numberOfVoxels", "hasEmission", "embeddedMask", "gridRes", "levels", "flavour", "dps"):
+        assert getattr(ia, f) == getattr(ib, f), f
+    assert list(ia.lower) == list(ib.lower) and list(ia.upper) == list(ib.upper)
+    for x, y in zip(a.download(want_morton=True), b.download(want_morton=True)):
+        assert np.array_equal(x, y)
+
+
+def random_list(rng, n, res, emissive=0.1):
+    xyz = rng.integers(0, res, size=(n, 3), dtype=np.uint32)
+    attrs = rng.integers(0, 256, size=(n, 8), dtype=np.uint8)  # garbage alpha bytes included
+    attrs[rng.random(n) >= emissive, 4:7] = 0
+    return xyz, attrs
+
+
+class Model:
+    """the voxel set as a dict Morton -> attribute row, with the last-wins batch semantics"""
+
+    def __init__(self, O, xyz, attrs):
+        m, a, _ = O.merge_voxels(O.morton_encode_batch(xyz), attrs)
+        self.d = {int(k): a[i] for i, k in enumerate(m)}
+
+    def apply(self, O, xyz, attrs, ops):
+        keys = O.morton_encode_batch(xyz)
+        attrs = normalised(attrs)
+        for i, k in enumerate(keys):
+            if ops[i] == SET:
+                self.d[int(k)] = attrs[i]
+            else:
+                self.d.pop(int(k), None)
+
+    def arrays(self):
+        ks = np.array(sorted(self.d), np.uint64)
+        at = np.array([self.d[int(k)] for k in ks], np.uint8).reshape(-1, 8)
+        return ks, at
+
+
+def edit_batch(rng, model, n, res, emissive=0.1):
+    """a mixed batch: replacements and removals of existing voxels, inserts, removals of absent cells and repeats within the batch"""
+    existing = np.array(sorted(model.d), np.uint64)
+    pick = decode(existing[rng.integers(0, len(existing), size=n // 2)])
+    fresh = rng.integers(0, res, size=(n - n // 2, 3), dtype=np.uint32)
+    xyz = np.concatenate([pick, fresh])
+    xyz = np.concatenate([xyz, xyz[rng.integers(0, len(xyz), size=n // 8)]])  # duplicates: the last one wins
+    attrs = rng.integers(0, 256, size=(len(xyz), 8), dtype=np.uint8)
+    attrs[rng.random(len(xyz)) >= emissive, 4:7] = 0
+    ops = (rng.random(len(xyz)) < 0.6).astype(np.uint8)
+    return xyz, attrs, ops
+
+
+# ---- build_voxels ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+def test_dumped_bunny_list_equals_triangle_build(mv, O, flags):
+    from massivevoxelraytracing_amd import scenes
+    tris = bunny_tris()
+    cols, emis = position_colors(tris)
+    res = 128
+    origin, dps = scenes.bounding_grid(tris.reshape(-1, 3), res)
+    m, a = O.voxelize(tris, origin, dps, res, cols, emis)
+    ref = mv.IntersectorOctreeGPU()
+    ref.build(tris.reshape(-1, 3), cols.reshape(-1, 3), emis.reshape(-1, 3), None, origin, dps, res, flags=flags)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(decode(m), a, origin=origin, dps=dps, gridRes=res, flags=flags)
+    assert svo.info().totalDumpedVoxels == len(m) == ref.info().totalDumpedVoxels
+    assert_same_handles(svo, ref)
+    assert svo.info().hasEmission == 1
+
+
+@pytest.mark.parametrize("res,n", [(2, 1), (2, 20), (4, 50), (8, 300), (256, 200000), (1024, 1000000)])
+@pytest.mark.parametrize("flags", [0, 1])
+def test_random_lists_equal_oracle(mv, O, res, n, flags):
+    rng = np.random.default_rng(res * 7919 + n + flags)
+    xyz, attrs = random_list(rng, n, res)
+    m, a, he = O.merge_voxels(O.morton_encode_batch(xyz), attrs)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(xyz, attrs, origin=(-1.0, 0.5, 2.0), dps=0.25, gridRes=res, flags=flags)
+    assert_svo(O, svo, m, a, he, res, flags, n)
+
+
+def test_full_grid_and_default_attributes(mv, O):
+    g = np.stack(np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij"), -1).reshape(-1, 3).astype(np.uint32)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(g[::-1].copy(), None, gridRes=8)
+    m = np.sort(O.morton_encode_batch(g))
+    white = np.tile(np.array([255, 255, 255, 255, 0, 0, 0, 255], np.uint8), (512, 1))
+    assert_svo(O, svo, m, white, 0, 8, 0, 512)
+    assert svo.info().numberOfNodes == 3  # a full grid is one node per level in a DAG
+
+
+def test_read_voxels_round_trip(mv, O):
+    rng = np.random.default_rng(5)
+    xyz, attrs = random_list(rng, 30000, 64)
+    a = mv.IntersectorOctreeGPU()
+    a.build_voxels(xyz, attrs, gridRes=64)
+    rx, ra = a.read_voxels()
+    m, am, _ = O.merge_voxels(O.morton_encode_batch(xyz), attrs)
+    assert np.array_equal(rx, decode(m)) and np.array_equal(ra, am)
+    b = mv.IntersectorOctreeGPU()
+    b.build_voxels(mv.DeviceArray.from_host(rx), mv.DeviceArray.from_host(ra), gridRes=64)
+    assert_same_handles(a, b)
+    assert b.info().totalDumpedVoxels == len(rx)
+
+
+# ---- edits ------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+def test_edit_sequences_equal_model(mv, O, flags):
+    res = 64
+    rng = np.random.default_rng(100 + flags)
+    xyz, attrs = random_list(rng, 20000, res)
+    model = Model(O, xyz, attrs)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(xyz, attrs, gridRes=res, flags=flags)
+    for batch, n in enumerate([1, 7, 300, 5000, 20000]):
+        exyz, ea, eops = edit_batch(rng, model, n, res)
+        if batch == 0:
+            eops[:] = SET
+        model.apply(O, exyz, ea, eops)
+        svo.edit_voxels(exyz, ea, eops)
+        m, a = model.arrays()
+        assert_svo(O, svo, m, a, has_emission(a), res, flags, 0)
+
+
+def test_edited_octree_traces_like_oracle(mv, O):
+    res = 256
+    rng = np.random.default_rng(11)
+    xyz, attrs = random_list(rng, 150000, res)
+    model = Model(O, xyz, attrs)
+    svo = mv.IntersectorOctreeGPU()
+    origin, dps = np.array([-1.0, -1.0, -1.0], np.float32), np.float32(2.0 / res)
+    svo.build_voxels(xyz, attrs, origin=origin, dps=dps, gridRes=res)
+    for n in (2000, 40000):
+        exyz, ea, eops = edit_batch(rng, model, n, res)
+        model.apply(O, exyz, ea, eops)
+        svo.edit_voxels(exyz, ea, eops)
+    m, a = model.arrays()
+    nodes = O.build_octree(m, res)
+    sc = O.Scene(nodes, a, origin, dps, res, has_emission(a))
+    nr = 200000
+    ro = (rng.random((nr, 3), np.float32) * 3.0 - 1.5).astype(np.float32)
+    tgt = (rng.random((nr, 3), np.float32) * 1.6 - 0.8).astype(np.float32)
+    rd = tgt - ro
+    rd /= np.linalg.norm(rd, axis=1, keepdims=True)
+    want = sc.trace(ro, rd, threads=8, want_descents=True)
+    got = svo.intersect(ro, rd, want_descents=True)
+    for k in ("t", "nMajor", "vIndex", "descents"):
+        assert np.array_equal(got[k], want[k]), k
+    assert int((want["t"] != O.MAX_FLOAT).sum()) > nr // 4
+    # hinted: rays that start on edited voxels, hinted with those voxels
+    inserted = O.morton_encode_batch(exyz[eops == SET])
+    inserted = inserted[np.isin(inserted, m)]
+    hv = inserted[rng.integers(0, len(inserted), size=nr)]
+    ro_h = (origin + (decode(hv).astype(np.float32) + 0.5) * dps).astype(np.float32)
+    want = sc.trace(ro_h, rd, threads=8, want_descents=True)
+    got = svo.intersect_hinted(ro_h, rd, hv)
+    for k in ("t", "nMajor", "vIndex", "descents"):
+        assert np.array_equal(got[k], want[k]), k
+
+
+def test_attribute_only_edit_keeps_nodes_and_flips_emission(mv, O):
+    res = 64
+    rng = np.random.default_rng(3)
+    xyz, attrs = random_list(rng, 20000, res, emissive=0.0)
+    model = Model(O, xyz, attrs)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(xyz, attrs, gridRes=res)
+    assert svo.info().hasEmission == 0
+    node_buffer, nodes0 = svo.m_nodeBuffer, svo.download()[0]
+    # paint emission onto existing voxels (with repeats and removals of absent cells: still attribute-only)
+    existing = np.array(sorted(model.d), np.uint64)
+    exyz = decode(existing[rng.integers(0, len(existing), size=500)])
+    ea = rng.integers(0, 256, size=(500, 8), dtype=np.uint8)
+    ops = np.ones(500, np.uint8)
+    absent = np.array([[c, c, c] for c in range(res)], np.uint32)
+    absent = absent[~np.isin(O.morton_encode_batch(absent), existing)]
+    exyz = np.concatenate([exyz, absent])
+    ea = np.concatenate([ea, np.zeros((len(absent), 8), np.uint8)])
+    ops = np.concatenate([ops, np.zeros(len(absent), np.uint8)])
+    assert np.any(ea[:500, 4:7] != 0)
+    model.apply(O, exyz, ea, ops)
+    svo.edit_voxels(exyz, ea, ops)
+    assert svo.m_nodeBuffer == node_buffer
+    assert np.array_equal(svo.download()[0], nodes0)
+    m, a = model.arrays()
+    assert_svo(O, svo, m, a, 1, res, 0, 0)
+    fresh = mv.IntersectorOctreeGPU()
+    fresh.build_voxels(decode(m), a, gridRes=res)
+    assert np.array_equal(fresh.download()[0], nodes0)
+    # clear every emissive voxel: the flag turns off again, still in place
+    em = m[np.any(a[:, 4:7] != 0, axis=1)]
+    cols = a[np.any(a[:, 4:7] != 0, axis=1)].copy()
+    cols[:, 4:7] = 0
+    svo.edit_voxels(decode(em), cols)
+    assert svo.m_nodeBuffer == node_buffer
+    assert svo.info().hasEmission == 0
+
+
+def test_edit_across_the_embedded_mask_limit(mv, O):
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_synthetic(2048, 4500000, seed=9, flags=svo.BUILD_NO_DAG)
+    i0 = svo.info()
+    assert i0.numberOfNodes < 0xFFFFFF and i0.flavour == 0
+    per_voxel = i0.numberOfNodes / i0.numberOfVoxels
+    n_add = int((0xFFFFFF - i0.numberOfNodes) / per_voxel * 1.3) + 20000
+    rng = np.random.default_rng(21)
+    exyz = rng.integers(0, 2048, size=(n_add, 3), dtype=np.uint32)
+    ea = np.tile(np.array([90, 140, 200, 0, 0, 0, 0, 0], np.uint8), (n_add, 1))
+    svo.edit_voxels(exyz, ea)
+    i1 = svo.info()
+    assert i1.numberOfNodes >= 0xFFFFFF and i1.flavour == 2  # no DAG above the limit: the tree flavour, as a fresh build picks
+    rx, ra = svo.read_voxels()
+    fresh = mv.IntersectorOctreeGPU()
+    fresh.build_voxels(rx, ra, gridRes=2048, dps=1.0 / 2048, flags=svo.BUILD_NO_DAG)
+    assert_same_handles(svo, fresh)
+    rng2 = np.random.default_rng(22)
+    ro = rng2.random((100000, 3), np.float32) * 1.4 - 0.2
+    rd = rng2.random((100000, 3), np.float32) - 0.5
+    rd /= np.linalg.norm(rd, axis=1, keepdims=True)
+    a, b = svo.intersect(ro, rd), fresh.intersect(ro, rd)
+    for k in ("t", "nMajor", "vIndex"):
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_failures_leave_the_handle_unchanged(mv, O):
+    res = 32
+    rng = np.random.default_rng(8)
+    xyz, attrs = random_list(rng, 3000, res)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(xyz, attrs, gridRes=res, flags=1)
+
+    def state():
+        i = svo.info()
+        return bytes(i), svo.download(want_morton=True)
+
+    def same(s0):
+        s1 = state()
+        assert s1[0] == s0[0]
+        for x, y in zip(s0[1], s1[1]):
+            assert np.array_equal(x, y)
+
+    s0 = state()
+    bad = xyz[:100].copy()
+    bad[37] = (3, res, 4)
+    bad[80] = (res + 5, 0, 0)
+    with pytest.raises(mv.MvrtError, match=r"entry 37 \(3, 32, 4\) lies outside the 32\^3 grid"):
+        svo.edit_voxels(bad)
+    same(s0)
+    with pytest.raises(mv.MvrtError, match="entry 37 .* lies outside the 32"):
+        svo.build_voxels(bad, gridRes=res)
+    same(s0)
+    ops = np.ones(100, np.uint8)
+    ops[64], ops[90] = 2, 255
+    with pytest.raises(mv.MvrtError, match="entry 64 has the unknown op 2"):
+        svo.edit_voxels(xyz[:100], None, ops)
+    same(s0)
+    with pytest.raises(mv.MvrtError, match="would remove every voxel"):
+        svo.edit_voxels(np.concatenate([xyz, xyz[:10]]), None, np.zeros(len(xyz) + 10, np.uint8))
+    same(s0)
+    with pytest.raises(mv.MvrtError, match="unsupported flags"):
+        svo.build_voxels(xyz, gridRes=res, flags=4)
+    same(s0)
+    # an uploaded octree keeps no Morton codes
+    up = mv.IntersectorOctreeGPU()
+    m, a, he = O.merge_voxels(O.morton_encode_batch(xyz), attrs)
+    up.upload(O.build_octree(m, res), a, (0, 0, 0), 1.0 / res, res, he)
+    u0 = up.download()
+    with pytest.raises(mv.MvrtError, match="uploaded octree"):
+        up.edit_voxels(xyz[:5])
+    with pytest.raises(mv.MvrtError, match="uploaded octree"):
+        up.read_voxels()
+    for x, y in zip(u0, up.download()):
+        assert np.array_equal(x, y)
+
+
+# ---- path tracer ordering ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("batch", [1, 2])
+def test_path_tracer_steps_before_an_edit_render_the_old_scene(mv, O, batch):
+    from massivevoxelraytracing_amd import scenes
+    tris = bunny_tris()
+    cols, emis = position_colors(tris)
+    res, w, h = 128, 64, 36
+    origin, dps = scenes.bounding_grid(tris.reshape(-1, 3), res)
+    m, a = O.voxelize(tris, origin, dps, res, cols, emis)
+    model = Model(O, decode(m), a)
+    rgba, hw, hh = O.decode_rgbe(hdr_bytes())
+    cam = probe_camera(origin, dps, res, focus=9.0, lens_r=0.05)
+    pt = mv.PathTracer()
+    pt.setup(None)
+    pt.set_batch_steps(batch)
+    pt.resizeFrameBufferIfNeeded(None, w, h)
+    pt.loadHDRIPixels(None, rgba, hw, hh, rgba, hw, hh)
+    pt.m_intersectorOctreeGPU.build_voxels(decode(m), a, origin=origin, dps=dps, gridRes=res)
+    m0, a0 = model.arrays()
+    old = O.Scene(O.build_octree(m0, res), a0, origin, dps, res, has_emission(a0))
+    pt.step(None, cam)
+    rng = np.random.default_rng(batch)
+    exyz, ea, eops = edit_batch(rng, model, 4000, res, emissive=0.3)
+    model.apply(O, exyz, ea, eops)
+    pt.m_intersectorOctreeGPU.edit_voxels(exyz, ea, eops)
+    pt.step(None, cam)
+    got = pt.read_framebuffer()[: w * h]
+    m1, a1 = model.arrays()
+    new = O.Scene(O.build_octree(m1, res), a1, origin, dps, res, has_emission(a1))
+    H = O.HDRI(rgba, hw, hh, rgba, hw, hh, 1)
+    fb, _, _ = old.render_pt(H, cam, w, h, 0, math_mode=1, threads=8)
+    fb, _, _ = new.render_pt(H, cam, w, h, 1, math_mode=1, fb=fb, threads=8)
+    assert np.array_equal(got, fb)
+
+
+# ---- at scale -------------------------------------------------------------------------------------------------------------------------------------
+def test_million_mixed_edits_on_the_dragon(mv):
+    from massivevoxelraytracing_amd import scenes
+    verts, cols, emis = scenes.dragon_standin()
+    res = 2048
+    origin, dps = scenes.bounding_grid(verts, res)
+    svo = mv.IntersectorOctreeGPU()
+    svo.build(verts, cols, emis, None, origin, dps, res)
+    _, a0, m0 = svo.download(want_morton=True)
+    rng = np.random.default_rng(2048)
+    n = 1000000
+    pick = m0[rng.integers(0, len(m0), size=n // 2)]
+    xyz = np.concatenate([svo_decode(pick), rng.integers(0, res, size=(n - n // 2, 3), dtype=np.uint32)])
+    attrs = rng.integers(0, 256, size=(n, 8), dtype=np.uint8)
+    ops = (rng.random(n) < 0.55).astype(np.uint8)
+    svo.edit_voxels(xyz, attrs, ops)
+    # numpy model of last-wins: per key the last batch entry, then set / remove against the old sorted list
+    keys = mortons(xyz)
+    rev_keys, rev_first = np.unique(keys[::-1], return_index=True)
+    last = n - 1 - rev_first
+    lop, lat = ops[last], normalised(attrs[last])
+    keep_old = ~np.isin(m0, rev_keys[lop == REMOVE])
+    old_m, old_a = m0[keep_old], a0[keep_old]
+    sets = rev_keys[lop == SET]
+    old_a = old_a.copy()
+    pos = np.searchsorted(sets, old_m)
+    hit = (pos < len(sets)) & (sets[np.minimum(pos, len(sets) - 1)] == old_m)
+    old_a[hit] = lat[lop == SET][pos[hit]]
+    new_keys = sets[~np.isin(sets, old_m)]
+    all_m = np.concatenate([old_m, new_keys])
+    all_a = np.concatenate([old_a, lat[lop == SET][~np.isin(sets, old_m)]])
+    order = np.argsort(all_m, kind="stable")
+    fresh = mv.IntersectorOctreeGPU()
+    fresh.build_voxels(svo_decode(all_m[order]), all_a[order], origin=origin, dps=dps, gridRes=res)
+    assert_same_handles(svo, fresh)
+
+
+def svo_decode(m):
+    return decode(m)
+
+
+def mortons(xyz):
+    xyz = np.asarray(xyz, np.uint64)
+    out = np.zeros(len(xyz), np.uint64)
+    for b in range(21):
+        for axis in range(3):
+            out |= ((xyz[:, axis] >> np.uint64(b)) & np.uint64(1)) << np.uint64(3 * b + axis)
+    return out

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""usage: tools/voxel_edit_bench.py [--scenes dragon,tunnel] [--reps 10] [--warmup 2] [--out FILE]
+
+Cost of getting voxels into an octree and of changing them, on the procedural stand-ins (dragon 2048^3, tunnel 4096^3):
+  rebuild      mvrt_svo_build from the triangles (voxelize + sort + unique + levels)
+  build_voxels mvrt_svo_build_voxels of the scene's unique voxel list (read back with mvrt_svo_read_voxels)
+  structural   mvrt_svo_edit_voxels batches of 1 / 10^3 / 6.4*10^4 / 10^6 entries: half removals of existing voxels, half inserts of random cells
+  attribute    batches of the same sizes that only re-colour existing voxels (the node structure stays)
+Median of --reps calls after --warmup calls; host clock around each call (every call returns after a device synchronise).  Inputs are staged on the
+device before the clock starts.  One JSON line per measurement, and a summary table on stderr."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import massivevoxelraytracing_amd as mv  # noqa: E402
+from massivevoxelraytracing_amd import scenes  # noqa: E402
+
+GRID = {"dragon": 2048, "tunnel": 4096}
+SIZES = [1, 1000, 64000, 1000000]
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        mv.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        mv.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), ts
+
+
+def decode(m):
+    out = np.zeros((len(m), 3), np.uint32)
+    for axis in range(3):
+        v = np.zeros(len(m), np.uint64)
+        for b in range(21):
+            v |= ((m >> np.uint64(3 * b + axis)) & np.uint64(1)) << np.uint64(b)
+        out[:, axis] = v.astype(np.uint32)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="dragon,tunnel")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    mv.set_device(0)
+    rows = []
+
+    def emit(**kw):
+        rows.append(kw)
+        print(json.dumps(kw), flush=True)
+
+    for name in args.scenes.split(","):
+        res = GRID[name]
+        verts, cols, emis = scenes.SCENES[name](1.0)
+        origin, dps = scenes.bounding_grid(verts, res)
+        svo = mv.IntersectorOctreeGPU()
+        ms, ts = timed(lambda: svo.build(verts, cols, emis, None, origin, dps, res), args.reps, args.warmup)
+        info = svo.info()
+        n_vox = info.numberOfVoxels
+        emit(scene=name, grid=res, op="rebuild", entries=int(info.totalDumpedVoxels), voxels=n_vox, nodes=info.numberOfNodes, ms=ms, all_ms=ts)
+        xyz, attrs = svo.read_voxels()
+        d_xyz, d_at = mv.DeviceArray.from_host(xyz), mv.DeviceArray.from_host(attrs)
+        other = mv.IntersectorOctreeGPU()
+        ms, ts = timed(lambda: other.build_voxels(d_xyz, d_at, origin=origin, dps=dps, gridRes=res), args.reps, args.warmup)
+        emit(scene=name, grid=res, op="build_voxels", entries=n_vox, voxels=other.info().numberOfVoxels, nodes=other.info().numberOfNodes, ms=ms, all_ms=ts)
+        del other
+        rng = np.random.default_rng(res)
+        for n in SIZES:
+            for kind in ("structural", "attribute"):
+                # one staged batch per call: structural = removals of existing voxels + inserts of random cells; attribute = new colours of existing voxels
+                batches = []
+                for _ in range(args.reps + args.warmup):
+                    cur = svo.info().numberOfVoxels
+                    pick = xyz[rng.integers(0, len(xyz), size=n if kind == "attribute" else max(n // 2, 1))]
+                    at = rng.integers(0, 256, size=(n, 8), dtype=np.uint8)
+                    if kind == "attribute":
+                        e_xyz, ops = pick, np.ones(n, np.uint8)
+                    else:
+                        fresh = rng.integers(0, res, size=(n - len(pick), 3), dtype=np.uint32)
+                        e_xyz = np.concatenate([pick, fresh])[:n]
+                        ops = np.concatenate([np.zeros(len(pick), np.uint8), np.ones(len(fresh), np.uint8)])[:n]
+                    batches.append((mv.DeviceArray.from_host(np.ascontiguousarray(e_xyz, np.uint32)), mv.DeviceArray.from_host(at), mv.DeviceArray.from_host(ops), cur))
+                it = iter(batches)
+
+                def call():
+                    b = next(it)
+                    svo.edit_voxels(b[0], b[1], b[2])
+
+                buf0 = svo.m_nodeBuffer
+                ms, ts = timed(call, args.reps, args.warmup)
+                kept = svo.m_nodeBuffer == buf0
+                emit(scene=name, grid=res, op="edit_" + kind, entries=n, voxels=svo.info().numberOfVoxels, nodes=svo.info().numberOfNodes, nodes_kept=bool(kept), ms=ms,
+                     all_ms=ts)
+                if kind == "structural":  # keep the read-back list in step with the octree for the next attribute batches
+                    xyz, attrs = svo.read_voxels()
+        del svo
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+    for r in rows:
+        print("%-7s %5d %-17s %9d entries %6.2f ms" % (r["scene"], r["grid"], r["op"], r["entries"], r["ms"]), file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()
