@@ -127,9 +127,24 @@ int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attri
  * the mask is fetched from the node (voxCommon.hpp:353-356; required above 0xFFFFFF nodes). */
 /* nVoxelsPSum is used as stored: vIndex = the sum of the stored values along the path (voxCommon.hpp:388-391), whatever they are -- e.g. all zero
  * for buildOctreeNaive's nodes (IntersectorOctree.hpp:195), which then give vIndex 0 like the reference.  (Internally the last level's value is
- * replaced by a popcount of the mask when the upload is found to carry exactly that there, as every octree built by bottomUpOctreeBuild does.) */
+ * replaced by a popcount of the mask when the upload is found to carry exactly that there, as every octree built by bottomUpOctreeBuild does.)
+ * The upload contract, checked on the host by mvrt_svo_check_upload before any GPU work (a rejected upload returns non-zero and leaves the handle
+ * exactly as it was; mvrt_last_error names the rule and the first offending node):
+ *   1. gridRes is a power of two in [2, 2^21].
+ *   2. Every child word of every node, reachable or not, is 0xFFFFFFFF where the mask bit is clear; where it is set, 0xFFFFFFFF (a voxel) or a node
+ *      index below numberOfNodes -- embedded: the index in bits 0-23 and that node's mask byte in bits 24-31; plain: the whole word.
+ *   3. From the root (the last node) every reachable node has one depth; voxel children occur only in nodes at depth log2(gridRes) - 1, node
+ *      children only above it.  This rejects cycles, octrees deeper or shallower than gridRes, nodes shared at two depths and voxels above the
+ *      last level (coarse voxels: not supported).
+ *   4. The largest nVoxelsPSum sum along a root-to-voxel path (64-bit) is below numberOfVoxels (so a non-empty octree needs numberOfVoxels >= 1).
+ *   5. embeddedMask: numberOfNodes < 0xFFFFFF.
+ * Accepted and traced like the reference: any numbering with the root last, unreachable nodes, any sharing at one depth, reachable inner nodes with
+ * mask 0, any nVoxelsPSum within rule 4, the empty octree (one root of mask 0, numberOfVoxels 0). */
 int mvrt_svo_upload( mvrt_svo* svo, const void* nodes68Host, uint32_t numberOfNodes, const void* attribs8Host, uint32_t numberOfVoxels, const float origin[3],
 					 float dps, int gridRes, int hasEmission, int embeddedMask, void* stream );
+/* The rules above on host arrays alone (no HIP call, no handle): 0 when mvrt_svo_upload would accept them, else non-zero with mvrt_last_error set.
+ * For applications that load octrees from files. */
+int mvrt_svo_check_upload( const void* nodes68Host, uint32_t numberOfNodes, uint32_t numberOfVoxels, int gridRes, int embeddedMask );
 int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info );
 int mvrt_svo_set_emission_scale( mvrt_svo* svo, float scale ); /* m_emissionScale (:273) */
 /* bytes of the device structure the traversal and mvrt_svo_download work from (the reference's layout would be numberOfNodes * 68):

@@ -76,6 +76,11 @@ struct IntersectorOctreeGPU
 		check( mvrt_svo_upload( m_handle, nodes68, numberOfNodes, attribs8, numberOfVoxels, o, dps, gridRes, hasEmission, embeddedMask, stream ), "mvrt_svo_upload" );
 		refresh();
 	}
+	// the upload contract (mvrt.h) on host arrays alone, no GPU call: true when upload() would accept them; else false and mvrt_last_error() says why
+	static bool checkUpload( const void* nodes68, uint32_t numberOfNodes, uint32_t numberOfVoxels, int gridRes, bool embeddedMask )
+	{
+		return mvrt_svo_check_upload( nodes68, numberOfNodes, numberOfVoxels, gridRes, embeddedMask ) == 0;
+	}
 
 	// voxel lists (mvrt_svo_build_voxels / mvrt_svo_edit_voxels / mvrt_svo_read_voxels): device arrays of xyz (3 x u32 per voxel) and VoxelAttirb (2 x u32 per voxel,
 	// nullptr = white, no emission); ops: MVRT_VOXEL_SET / MVRT_VOXEL_REMOVE per entry (nullptr = all SET), the last entry per voxel wins

@@ -64,6 +64,7 @@ SIGNATURES = {
     "mvrt_svo_build_ex": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _f32, _i32, _i32]),
     "mvrt_svo_build_synthetic": (_i32, [_vp, _i32, _u64, _u64, _vp, _f32, _i32, _vp]),
     "mvrt_svo_upload": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, _f32, _i32, _i32, _i32, _vp]),
+    "mvrt_svo_check_upload": (_i32, [_vp, _u32, _u32, _i32, _i32]),
     "mvrt_svo_build_voxels": (_i32, [_vp, _vp, _vp, _u64, _vp, _f32, _i32, _i32, _vp]),
     "mvrt_svo_edit_voxels": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "mvrt_svo_read_voxels": (_i32, [_vp, _vp, _vp, _vp]),
@@ -328,6 +329,16 @@ class IntersectorOctreeGPU:
         o = np.ascontiguousarray(origin, np.float32)
         _check(lib().mvrt_svo_upload(self._h, _hp(nodes68), n_nodes, _hp(attribs), len(attribs), _hp(o), float(np.float32(dps)), int(gridRes), int(hasEmission),
                                      int(embeddedMask), stream))
+
+    @staticmethod
+    def check_upload(nodes68, numberOfVoxels, gridRes, embeddedMask=True):
+        """mvrt_svo_check_upload: the upload contract (include/mvrt.h) on host arrays, no GPU call.  Returns None when mvrt_svo_upload would accept
+        the octree, else the error text (it names the rule and the first offending node)."""
+        nodes68 = np.ascontiguousarray(nodes68)
+        assert nodes68.dtype.itemsize == 68 or nodes68.dtype == np.uint8
+        if lib().mvrt_svo_check_upload(_hp(nodes68), nodes68.nbytes // 68, int(numberOfVoxels), int(gridRes), int(embeddedMask)) == 0:
+            return None
+        return lib().mvrt_last_error().decode("utf-8", "replace")
 
     def info(self):
         i = SvoInfo()

@@ -269,11 +269,12 @@ static int buildTopTable( mvrt_svo* s, hipStream_t st )
 	return 0;
 }
 
-static int ilog2Exact( int v )
+static int ilog2Exact( int v ) // log2 of a power of two, -1 for anything else (zero, negative, not a power of two): every int terminates
 {
+	if( v <= 0 || ( v & ( v - 1 ) ) != 0 ) return -1;
 	int l = 0;
-	while( ( 1 << l ) < v ) l++;
-	return ( 1 << l ) == v ? l : -1;
+	while( ( v >> l ) != 1 ) l++;
+	return l;
 }
 static void setBounds( mvrt_svo* s, const float origin[3], float dps, int gridRes )
 {
@@ -303,13 +304,102 @@ MVRT_EXPORT int mvrt_svo_destroy( mvrt_svo* svo )
 	return 0;
 }
 
+// The upload contract (mvrt.h): every rule on the host arrays, before any HIP call.  Rules 1 and 5 first, then rule 2 over every node in index order,
+// then one walk from the root, depth by depth in discovery order, for rules 3 and 4.  The first offending node in that order is named.
+MVRT_EXPORT int mvrt_svo_check_upload( const void* nodes68Host, uint32_t numberOfNodes, uint32_t numberOfVoxels, int gridRes, int embeddedMask )
+{
+	REQUIRE( nodes68Host && numberOfNodes > 0, "mvrt_svo_upload: empty octree" );
+	REQUIRE( gridRes >= 2 && gridRes <= ( 1 << 21 ) && ( gridRes & ( gridRes - 1 ) ) == 0, "mvrt_svo_upload: rule 1: gridRes %d is not a power of two in [2, 2^21]",
+			 gridRes );
+	const int L = ilog2Exact( gridRes );
+	REQUIRE( !embeddedMask || numberOfNodes < 0xFFFFFFu, "mvrt_svo_upload: rule 5: embedded masks need fewer than 0xFFFFFF nodes (IntersectorOctreeGPU.hpp:231), got %u",
+			 numberOfNodes );
+	const uint8_t* base = (const uint8_t*)nodes68Host;
+	auto maskOf = [base]( uint32_t n ) { return (uint32_t)base[(uint64_t)n * 68]; };
+	auto word = [base]( uint32_t n, uint32_t w ) // w: 1..8 children, 9..16 nVoxelsPSum
+	{
+		uint32_t v;
+		memcpy( &v, base + (uint64_t)n * 68 + 4 * w, 4 );
+		return v;
+	};
+	for( uint32_t n = 0; n < numberOfNodes; n++ ) // rule 2: reachable or not
+	{
+		const uint32_t mask = maskOf( n );
+		for( uint32_t c = 0; c < 8; c++ )
+		{
+			const uint32_t ch = word( n, 1 + c );
+			if( ch == MVRT_LEAF ) continue;
+			REQUIRE( ( mask >> c ) & 1u, "mvrt_svo_upload: rule 2: node %u slot %u: child word 0x%08x where the mask bit is clear (absent children must be 0xFFFFFFFF)", n, c, ch );
+			const uint32_t k = embeddedMask ? ch & 0xFFFFFFu : ch;
+			REQUIRE( k < numberOfNodes, "mvrt_svo_upload: rule 2: node %u slot %u: child word 0x%08x names node %u, not below numberOfNodes %u", n, c, ch, k, numberOfNodes );
+			REQUIRE( !embeddedMask || ( ch >> 24 ) == maskOf( k ),
+					 "mvrt_svo_upload: rule 2: node %u slot %u: embedded mask byte 0x%02x differs from the mask 0x%02x of node %u (plain indices need embeddedMask = 0)", n, c,
+					 ch >> 24, maskOf( k ), k );
+		}
+	}
+	// rules 3 and 4: per reached node its depth << 56 | the largest nVoxelsPSum sum from the root to it (< 21 * 2^32)
+	const uint64_t kSum = ( 1ull << 56 ) - 1;
+	std::vector<uint64_t> seen( numberOfNodes, ~0ull );
+	std::vector<uint32_t> cur( 1, numberOfNodes - 1 ), next;
+	seen[numberOfNodes - 1] = 0;
+	uint32_t badNode = 0, badSlot = 0;
+	uint64_t badSum = 0;
+	bool bad = false;
+	for( uint32_t d = 0; !cur.empty(); d++ )
+	{
+		next.clear();
+		for( const uint32_t n : cur )
+		{
+			const uint32_t mask = maskOf( n );
+			const uint64_t s = seen[n] & kSum;
+			for( uint32_t c = 0; c < 8; c++ )
+			{
+				if( !( ( mask >> c ) & 1u ) ) continue;
+				const uint32_t ch = word( n, 1 + c );
+				const uint64_t sum = s + word( n, 9 + c );
+				if( ch == MVRT_LEAF )
+				{
+					REQUIRE( d + 1 == (uint32_t)L,
+							 "mvrt_svo_upload: rule 3: node %u at depth %u holds a voxel in slot %u, %u level(s) above the last level: voxels above the last level "
+							 "(coarse voxels) are not supported",
+							 n, d, c, (uint32_t)L - 1 - d );
+					if( sum >= numberOfVoxels && !bad )
+					{
+						bad = true;
+						badNode = n;
+						badSlot = c;
+						badSum = sum;
+					}
+					continue;
+				}
+				const uint32_t k = embeddedMask ? ch & 0xFFFFFFu : ch;
+				REQUIRE( d + 1 < (uint32_t)L, "mvrt_svo_upload: rule 3: node %u at depth %u has node %u in slot %u: the octree is deeper than log2(gridRes) = %d levels", n, d,
+						 k, c, L );
+				if( seen[k] == ~0ull )
+				{
+					seen[k] = ( (uint64_t)( d + 1 ) << 56 ) | sum;
+					next.push_back( k );
+					continue;
+				}
+				REQUIRE( ( seen[k] >> 56 ) == d + 1,
+						 "mvrt_svo_upload: rule 3: node %u at depth %u has node %u in slot %u, which is reached at depth %u as well (a cycle or a node shared at two depths)", n, d, k,
+						 c, (uint32_t)( seen[k] >> 56 ) );
+				if( sum > ( seen[k] & kSum ) ) seen[k] = ( seen[k] & ~kSum ) | sum;
+			}
+		}
+		cur.swap( next );
+	}
+	REQUIRE( !bad, "mvrt_svo_upload: rule 4: node %u slot %u: the nVoxelsPSum sum along a path to this voxel is %llu, not below numberOfVoxels %u", badNode, badSlot,
+			 (unsigned long long)badSum, numberOfVoxels );
+	return 0;
+}
+
 MVRT_EXPORT int mvrt_svo_upload( mvrt_svo* svo, const void* nodes68Host, uint32_t numberOfNodes, const void* attribs8Host, uint32_t numberOfVoxels, const float origin[3],
 								 float dps, int gridRes, int hasEmission, int embeddedMask, void* stream )
 {
 	REQUIRE( svo && nodes68Host && numberOfNodes > 0, "mvrt_svo_upload: empty octree" );
 	REQUIRE( attribs8Host || numberOfVoxels == 0, "mvrt_svo_upload: %u voxels without attributes", numberOfVoxels );
-	REQUIRE( ilog2Exact( gridRes ) > 0, "gridRes %d is not a power of two >= 2 (IntersectorOctreeGPU.hpp:48-51)", gridRes );
-	REQUIRE( !embeddedMask || numberOfNodes < 0xFFFFFFu, "embedded masks need fewer than 0xFFFFFF nodes (IntersectorOctreeGPU.hpp:231), got %u", numberOfNodes );
+	if( mvrt_svo_check_upload( nodes68Host, numberOfNodes, numberOfVoxels, gridRes, embeddedMask ) ) return 1; // before anything is replaced
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
 	svo->cleanUp();
