@@ -7,7 +7,11 @@
 // The Alembic scene / camera animation of the reference (prlib, absent) is replaced by a Wavefront .obj mesh and an
 // orbiting look-at camera.  Everything GPU-side goes through include/mvrt/PathTracer.hpp -> libmvrt_hip.so.
 //
-//   rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png]
+//   rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov]
+//
+// --aov also writes, beside each frame, <frame>_albedo and <frame>_normal in the frame's format: the means over all samples of the first-hit
+// feature buffers (mvrt.h "First-hit feature buffers"), what a denoiser takes as guides.  Encoded on the host from read-back data, in fp32:
+// albedo byte = (int)( 255 * ( sum / samples ) + 0.5f ), normal byte = (int)( 255 * ( 0.5f * ( sum / samples ) + 0.5f ) + 0.5f ), alpha 255.
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -57,13 +61,33 @@ struct Job
 {
 	int frame;
 	uint8_t* pixels;
+	const char* suffix; // "" = the frame itself (pixels go back to the pool), else a feature image (pixels are freed)
 };
+
+// feature-buffer sums -> RGBA8; normal = false: v = sum / samples, true: v = 0.5f * ( sum / samples ) + 0.5f
+static uint8_t* encodeAov( const std::vector<float>& sum, const std::vector<float>& frame, size_t nPixels, bool normal )
+{
+	uint8_t* out = new uint8_t[nPixels * 4];
+	for( size_t p = 0; p < nPixels; p++ )
+	{
+		const float samples = frame[p * 4 + 3];
+		for( int c = 0; c < 3; c++ )
+		{
+			float v = sum[p * 4 + c] / samples;
+			if( normal ) v = 0.5f * v + 0.5f;
+			const float b = 255.0f * v;
+			out[p * 4 + c] = (uint8_t)(int)( b + 0.5f );
+		}
+		out[p * 4 + 3] = 255;
+	}
+	return out;
+}
 
 int main( int argc, char** argv )
 {
 	if( argc < 4 )
 	{
-		std::printf( "usage: rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png]\n" );
+		std::printf( "usage: rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov]\n" );
 		std::printf( "  [instance 0] rtcamp_batch ... --frame-range 0 171\n  [instance 1] rtcamp_batch ... --frame-range 171 240\n" );
 		return 0;
 	}
@@ -71,7 +95,7 @@ int main( int argc, char** argv )
 	const char* hdrPath = argv[2];
 	const std::string outDir = argv[3];
 	int totalFrames = 240, beginFrame = 0, endFrame = -1, W = 1440, H = 900, fromRes = 256, toRes = 8192, steps = 8; // RTCamp.cpp:42-45,136-137,156
-	bool png = false, dumpCameras = false;
+	bool png = false, dumpCameras = false, aov = false;
 	for( int i = 4; i < argc; i++ )
 	{
 		if( !std::strcmp( argv[i], "--dump-cameras" ) ) dumpCameras = true;
@@ -81,6 +105,7 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--res" ) && i + 2 < argc ) { fromRes = std::atoi( argv[i + 1] ); toRes = std::atoi( argv[i + 2] ); i += 2; }
 		else if( !std::strcmp( argv[i], "--steps" ) && i + 1 < argc ) steps = std::atoi( argv[++i] );
 		else if( !std::strcmp( argv[i], "--png" ) ) png = true;
+		else if( !std::strcmp( argv[i], "--aov" ) ) aov = true;
 	}
 	if( endFrame < 0 ) endFrame = totalFrames;
 
@@ -106,6 +131,7 @@ int main( int argc, char** argv )
 
 	mvrt::PathTracer pt;
 	pt.setup( stream );
+	if( aov ) pt.setAOVs( true );
 	pt.resizeFrameBufferIfNeeded( stream, W, H );
 	pt.loadHDRI( stream, hdrPath, hdrPath );
 
@@ -128,9 +154,14 @@ int main( int argc, char** argv )
 				jobs.pop_front();
 			}
 			char file[512];
-			std::snprintf( file, sizeof( file ), "%s/%03d.%s", outDir.c_str(), j.frame, png ? "png" : "ppm" );
+			std::snprintf( file, sizeof( file ), "%s/%03d%s.%s", outDir.c_str(), j.frame, j.suffix, png ? "png" : "ppm" );
 			if( png ) mvrt_io::writePngUncompressed( file, j.pixels, W, H );
 			else mvrt_io::writePpm( file, j.pixels, W, H );
+			if( j.suffix[0] )
+			{
+				delete[] j.pixels;
+				continue;
+			}
 			{
 				std::lock_guard<std::mutex> lk( mu );
 				pool.push_back( j.pixels );
@@ -181,9 +212,25 @@ int main( int argc, char** argv )
 		}
 		pt.toImageAsync( stream, buf ); // resolve + DtoH (PathTracer.hpp:118-129)
 		mvrt::check( mvrt_stream_synchronize( stream ), "sync" );
+		uint8_t *albedoImage = nullptr, *normalImage = nullptr;
+		if( aov ) // an optional output, not a hot path: read the sums back and encode them here, the writer thread does the files
+		{
+			const size_t owned = (size_t)mvrt_pt_owned_pixels( pt.handle() );
+			std::vector<float> fb( owned * 4 ), sum( owned * 4 );
+			mvrt::check( mvrt_pt_read_framebuffer( pt.handle(), stream, fb.data() ), "read_framebuffer" );
+			mvrt::check( mvrt_pt_read_aov( pt.handle(), stream, MVRT_AOV_ALBEDO, sum.data() ), "read_aov" );
+			albedoImage = encodeAov( sum, fb, (size_t)W * H, false );
+			mvrt::check( mvrt_pt_read_aov( pt.handle(), stream, MVRT_AOV_NORMAL_DEPTH, sum.data() ), "read_aov" );
+			normalImage = encodeAov( sum, fb, (size_t)W * H, true );
+		}
 		{
 			std::lock_guard<std::mutex> lk( mu );
-			jobs.push_back( Job{ frame, buf } );
+			jobs.push_back( Job{ frame, buf, "" } );
+			if( aov )
+			{
+				jobs.push_back( Job{ frame, albedoImage, "_albedo" } );
+				jobs.push_back( Job{ frame, normalImage, "_normal" } );
+			}
 		}
 		cv.notify_all();
 		std::printf( "[frame %d] res( %d -> grid %d ) voxels %llu octree %.1f MB\n", frame, resolution, gridRes, (unsigned long long)pt.getNumberOfVoxels(), pt.getOctreeBytes() / 1e6 );

@@ -306,6 +306,31 @@ int mvrt_pt_read_framebuffer( mvrt_pt* pt, void* stream, float* rgbaHost /* owne
 float* mvrt_pt_framebuffer_dev( mvrt_pt* pt );
 uint8_t* mvrt_pt_framebuffer_u8_dev( mvrt_pt* pt );
 
+/* First-hit feature buffers for denoising, compositing, picking (new; the reference has none).  Two more accumulation buffers beside the frame
+ * buffer: float4 per OWNED pixel, the frame buffer's compact layout, padding and stride, cleared with it by clear_framebuffer and reallocated with
+ * it by resize_framebuffer_if_needed / set_tile.  They describe the hit of each sample's PRIMARY ray -- the jittered thin-lens ray step() generates
+ * for it, not a pixel-centre ray, so they match the beauty image at silhouettes and with lensR > 0:
+ *   MVRT_AOV_ALBEDO        xyz = sum of the hit voxel's colour (channel / 255.0f), w = number of samples whose primary ray hit
+ *   MVRT_AOV_NORMAL_DEPTH  xyz = sum of the hit face's axis normal (+-1 on one axis), w = sum of the hit's t
+ * t is what mvrt_trace_batch returns for that ray, whose direction is not normalised: for this camera rd . front = focus, so t * focus is the
+ * distance along the view axis.  A sample whose primary ray misses adds nothing; the sample count is the frame buffer's w and is not stored again:
+ * means are sum / frameBuffer.w (over all samples) or sum / albedo.w (over the hits).  The summation order is fixed like the frame buffer's
+ * (per step the 16 samples in ascending order from +0, then steps in issue order); batching, pipelining, tiles, the HDRI scale, emission and
+ * origin hints change no bit.  mvrt_pt_assemble_tiles, mvrt_memcpy_d2d and an all-gather apply to them as to the frame buffer;
+ * mvrt_resolve_buffer is NOT meant for them (it divides by w and tone-maps).
+ * Off by default: with them off every launch, allocation and output is that of a library without them.  On: 32 bytes per pixel and merged step of
+ * path state, 32 bytes per pixel of buffers, two small kernels per pass. */
+#define MVRT_AOV_ALBEDO 0
+#define MVRT_AOV_NORMAL_DEPTH 1
+/* Waits for the steps in flight, then allocates or frees.  Fails, handle unchanged, while steps are accumulated (get_steps != 0: the buffers would
+ * not match the frame buffer's sample count) -- clear_framebuffer first.  May be called before or after resize_framebuffer_if_needed.  If the
+ * path state no longer fits, the handle has NO frame afterwards, like after any failed reallocation (mvrt_pt_set_test_free_bytes). */
+int mvrt_pt_set_aovs( mvrt_pt* pt, int enable );
+/* NULL (and mvrt_last_error) when off, without a frame or for another `which`; callers reading it on their own stream call mvrt_pt_join before */
+float* mvrt_pt_aov_dev( mvrt_pt* pt, int which );
+/* host copy; waits for the steps in flight like mvrt_pt_read_framebuffer */
+int mvrt_pt_read_aov( mvrt_pt* pt, void* stream, int which, float* rgbaHost /* ownedPixels*4 */ );
+
 /* Multi-GPU tile split (new; the reference has no multi-GPU path).  The frame is cut into the reference's own
  * 256-pixel blocks (RENDER_NUMBER_OF_THREAD, renderCommon.hpp:13) dealt round-robin: this handle renders blocks
  * b with b % tileCount == tileIndex.  Owned pixels are stored compactly in block order.  Call before

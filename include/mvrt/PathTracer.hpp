@@ -60,6 +60,8 @@ struct PathTracer
 	{
 		m_frameBufferU8.reset();
 		m_frameBufferF32.reset();
+		m_aovAlbedoF32.reset();
+		m_aovNormalDepthF32.reset();
 		m_intersectorOctreeGPU.attach( nullptr );
 		if( m_handle ) mvrt_pt_destroy( m_handle );
 		m_handle = nullptr;
@@ -73,6 +75,7 @@ struct PathTracer
 		const int64_t owned = (int64_t)mvrt_pt_owned_pixels( m_handle );
 		m_frameBufferU8.reset( new Buffer( mvrt_pt_framebuffer_u8_dev( m_handle ), owned * 4 ) );
 		m_frameBufferF32.reset( new Buffer( mvrt_pt_framebuffer_dev( m_handle ), owned * 16 ) );
+		pointAOVs();
 		m_steps = mvrt_pt_get_steps( m_handle );
 	}
 	void clearFrameBuffer( void* stream ) // :98-102
@@ -100,18 +103,46 @@ struct PathTracer
 	}
 
 	// multi-GPU extension (not in the reference): render only the 256-pixel blocks b with b % tileCount == tileIndex
-	void setTile( int tileIndex, int tileCount ) { check( mvrt_pt_set_tile( m_handle, tileIndex, tileCount ), "PathTracer::setTile" ); }
+	// (the library releases the accumulation buffers here; the views are re-pointed by the next resizeFrameBufferIfNeeded)
+	void setTile( int tileIndex, int tileCount )
+	{
+		m_frameBufferF32.reset();
+		m_aovAlbedoF32.reset();
+		m_aovNormalDepthF32.reset();
+		check( mvrt_pt_set_tile( m_handle, tileIndex, tileCount ), "PathTracer::setTile" );
+	}
+
+	// first-hit feature buffers (not in the reference; mvrt.h "First-hit feature buffers"): off by default, before or after resizeFrameBufferIfNeeded,
+	// not while steps are accumulated (clearFrameBuffer first)
+	void setAOVs( bool enable )
+	{
+		check( mvrt_pt_set_aovs( m_handle, enable ? 1 : 0 ), "PathTracer::setAOVs" );
+		pointAOVs();
+	}
 
 	mvrt_pt* handle() const { return m_handle; }
 
 	IntersectorOctreeGPU m_intersectorOctreeGPU; // reference member m_intersectorOctreeGPU (:18), a value as there; bound to the handle's octree by setup()
 	std::unique_ptr<Buffer> m_frameBufferU8;  // :23 (filled by resolve / toImageAsync); views, see Buffer above
 	std::unique_ptr<Buffer> m_frameBufferF32; // :24
+	std::unique_ptr<Buffer> m_aovAlbedoF32;		 // MVRT_AOV_ALBEDO, float4 per owned pixel; null while the feature buffers are off (setAOVs)
+	std::unique_ptr<Buffer> m_aovNormalDepthF32; // MVRT_AOV_NORMAL_DEPTH
 	int m_width = 0;
 	int m_height = 0;
 	int m_steps = 0; // :27
 
 private:
+	void pointAOVs()
+	{
+		m_aovAlbedoF32.reset();
+		m_aovNormalDepthF32.reset();
+		if( float* a = mvrt_pt_aov_dev( m_handle, MVRT_AOV_ALBEDO ) )
+		{
+			const int64_t owned = (int64_t)mvrt_pt_owned_pixels( m_handle );
+			m_aovAlbedoF32.reset( new Buffer( a, owned * 16 ) );
+			m_aovNormalDepthF32.reset( new Buffer( mvrt_pt_aov_dev( m_handle, MVRT_AOV_NORMAL_DEPTH ), owned * 16 ) );
+		}
+	}
 	mvrt_pt* m_handle = nullptr;
 };
 } // namespace mvrt

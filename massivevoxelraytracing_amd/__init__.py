@@ -109,6 +109,9 @@ SIGNATURES = {
     "mvrt_pt_read_framebuffer": (_i32, [_vp, _vp, _vp]),
     "mvrt_pt_framebuffer_dev": (_vp, [_vp]),
     "mvrt_pt_framebuffer_u8_dev": (_vp, [_vp]),
+    "mvrt_pt_set_aovs": (_i32, [_vp, _i32]),
+    "mvrt_pt_aov_dev": (_vp, [_vp, _i32]),
+    "mvrt_pt_read_aov": (_i32, [_vp, _vp, _i32, _vp]),
     "mvrt_pt_set_tile": (_i32, [_vp, _i32, _i32]),
     "mvrt_pt_owned_pixels": (_u64, [_vp]),
     "mvrt_pt_assemble_tiles": (_i32, [_vp, _i32, _u64, _i32, _i32, _vp, _vp]),
@@ -569,6 +572,23 @@ class PathTracer:
 
     def framebuffer_dev(self):
         return lib().mvrt_pt_framebuffer_dev(self._h)
+
+    AOV_ALBEDO = 0        # xyz = sum of the first hit's voxel colour, w = samples whose primary ray hit
+    AOV_NORMAL_DEPTH = 1  # xyz = sum of the first hit's axis normal, w = sum of its t
+
+    def set_aovs(self, enable):
+        """mvrt_pt_set_aovs: first-hit feature buffers beside the frame buffer (off by default); fails while steps are accumulated"""
+        _check(lib().mvrt_pt_set_aovs(self._h, 1 if enable else 0))
+
+    def read_aov(self, which, stream=None):
+        """(owned_pixels, 4) host copy of one feature buffer; means are sum / read_framebuffer()[:, 3]"""
+        out = np.zeros((self.owned_pixels(), 4), np.float32)
+        _check(lib().mvrt_pt_read_aov(self._h, stream, int(which), _hp(out)))
+        return out
+
+    def aov_dev(self, which):
+        """device pointer of one feature buffer, None when they are off (join() before reading it on a stream of your own)"""
+        return lib().mvrt_pt_aov_dev(self._h, int(which))
 
     def sample_radiance(self, n_samples=None):
         """per-sample radiance of the last pass: (n, 3) host array (debug / parity)"""

@@ -976,6 +976,9 @@ struct mvrt_pt
 	HdriDev hdri;
 	// frame buffers
 	DevBuf fbF32, fbU8; // m_frameBufferF32 / m_frameBufferU8
+	// first-hit feature buffers (mvrt_pt_set_aovs; off by default): float4 per owned pixel like fbF32, allocated and cleared with it
+	bool aovs = false;
+	DevBuf aovAlbedo, aovNormalDepth;
 	int width = 0, height = 0, steps = 0;
 	int tileIndex = 0, tileCount = 1;
 	uint64_t ownedPixels = 0, validOwnedPixels = 0;
@@ -985,6 +988,7 @@ struct mvrt_pt
 	struct Slot
 	{
 		DevBuf work, wsBuf, dbg;
+		DevBuf aovPart; // feature buffers on: the pass's partial sums, 2 x float4 per (step, pixel) (AovBuffers::partA / partN)
 		PtBuffers buf;
 		TraceWorkspace ws = { nullptr, 0, nullptr, nullptr, 0, nullptr };
 		hipStream_t stream = nullptr;
@@ -1030,6 +1034,17 @@ struct mvrt_pt
 	int launchPass( const CameraPinhole* passCams, int iteration, int nSteps, int traceGridDiv );
 	bool splitSmallPasses = true; // MVRT_SPLIT_SMALL=0 disables (A/B)
 	bool originHints = true;	  // secondary rays start below the root (mvrt_pt_set_origin_hints)
+	void releaseAovs() // (the flag stays: the next successful resize allocates them again)
+	{
+		aovAlbedo.release();
+		aovNormalDepth.release();
+		for( Slot& sl : slots ) sl.aovPart.release();
+	}
+	int allocAovFrame() // the two accumulation buffers, beside a frame buffer that exists
+	{
+		if( aovAlbedo.alloc( ownedPixels * sizeof( float4 ) ) ) return 1;
+		return aovNormalDepth.alloc( ownedPixels * sizeof( float4 ) );
+	}
 	int effectiveBatch() const // merged steps per pass, bounded so that one pass stays below ~160 M samples (~30 GB of path state)
 	{
 		uint64_t perStep = ownedPixels * MVRT_SPP_PER_STEP;
@@ -1145,6 +1160,7 @@ MVRT_EXPORT int mvrt_pt_set_tile( mvrt_pt* pt, int tileIndex, int tileCount )
 	pt->tileCount = tileCount;
 	pt->width = pt->height = 0; // force re-allocation on the next resize
 	pt->fbF32.release();
+	pt->releaseAovs();
 	return 0;
 }
 MVRT_EXPORT uint64_t mvrt_pt_owned_pixels( const mvrt_pt* pt ) { return pt ? pt->ownedPixels : 0; }
@@ -1189,6 +1205,11 @@ static int allocWorkSlot( mvrt_pt* pt, mvrt_pt::Slot& sl )
 	b.selfDev = (const PtBuffers*)take( sizeof( PtBuffers ) );
 	MVRT_HIP( hipMemset( b.liveCount, 0, 64 * 4 ) );
 	MVRT_HIP( hipMemcpy( (void*)b.selfDev, &b, sizeof( PtBuffers ), hipMemcpyHostToDevice ) );
+	if( pt->aovs ) // a block of its own: the sizes above are those of a library without feature buffers
+	{
+		if( sl.aovPart.alloc( cap / MVRT_SPP_PER_STEP * 2 * sizeof( float4 ) ) ) return 1;
+	}
+	else sl.aovPart.release();
 	return 0;
 }
 static int allocWorkInner( mvrt_pt* pt );
@@ -1206,6 +1227,7 @@ static int allocWork( mvrt_pt* pt )
 	pt->width = pt->height = 0;
 	pt->fbF32.release();
 	pt->fbU8.release();
+	pt->releaseAovs();
 	return 1;
 }
 static int allocWorkInner( mvrt_pt* pt )
@@ -1225,6 +1247,7 @@ static int allocWorkInner( mvrt_pt* pt )
 		for( mvrt_pt::Slot& sl : pt->slots ) // (what is allocated now is about to be replaced)
 		{
 			sl.work.release();
+			sl.aovPart.release();
 			memset( &sl.buf, 0, sizeof( sl.buf ) ); // no pointer into the freed block survives a failure below
 		}
 		size_t freeB = 0, totalB = 0;
@@ -1233,7 +1256,11 @@ static int allocWorkInner( mvrt_pt* pt )
 		pt->batchCap = MVRT_MAX_BATCH;
 		pt->depth = pt->depthWanted;
 		const uint64_t budget = (uint64_t)( 0.7 * (double)freeB );
-		auto need = [&]() { return (uint64_t)pt->depth * pt->ownedPixels * MVRT_SPP_PER_STEP * (uint64_t)pt->effectiveBatch() * 200ull; };
+		// (feature buffers on: + 32 B of partial sums per pixel and merged step of every pass in flight, + the two accumulation buffers)
+		auto need = [&]() {
+			const uint64_t pathState = (uint64_t)pt->depth * pt->ownedPixels * MVRT_SPP_PER_STEP * (uint64_t)pt->effectiveBatch() * 200ull;
+			return pt->aovs ? pathState + (uint64_t)pt->depth * pt->ownedPixels * (uint64_t)pt->effectiveBatch() * 32ull + pt->ownedPixels * 32ull : pathState;
+		};
 		while( need() > budget && pt->effectiveBatch() > 1 ) pt->batchCap = pt->effectiveBatch() - 1;
 		while( need() > budget && pt->depth > 1 ) pt->depth--;
 		REQUIRE( need() <= budget, "frame of %llu owned pixels needs %.1f GB of path state, %.1f GB of HBM are free (split the frame into tiles: mvrt_pt_set_tile)",
@@ -1245,6 +1272,7 @@ static int allocWorkInner( mvrt_pt* pt )
 		if( i >= pt->depth )
 		{
 			sl.work.release();
+			sl.aovPart.release();
 			sl.wsBuf.release();
 			sl.ws = TraceWorkspace{ nullptr, 0, nullptr, nullptr, 0, nullptr };
 			memset( &sl.buf, 0, sizeof( sl.buf ) );
@@ -1290,6 +1318,8 @@ MVRT_EXPORT int mvrt_pt_clear_framebuffer( mvrt_pt* pt, void* stream )
 	if( pt->steps >= 2 ) pt->lastFrameSteps = pt->steps; // the caller's frame length (passSteps); a one-step frame says nothing about the next one
 	pt->steps = 0; // PathTracer.hpp:100
 	MVRT_HIP( hipMemsetAsync( pt->fbF32.p, 0, pt->fbF32.bytes, (hipStream_t)stream ) );
+	if( pt->aovAlbedo.p ) MVRT_HIP( hipMemsetAsync( pt->aovAlbedo.p, 0, pt->aovAlbedo.bytes, (hipStream_t)stream ) );
+	if( pt->aovNormalDepth.p ) MVRT_HIP( hipMemsetAsync( pt->aovNormalDepth.p, 0, pt->aovNormalDepth.bytes, (hipStream_t)stream ) );
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream, int width, int height )
@@ -1316,6 +1346,14 @@ MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream,
 	pt->height = height;
 	if( pt->fbF32.alloc( pt->ownedPixels * sizeof( float4 ) ) ) return 1;
 	if( pt->fbU8.alloc( pt->ownedPixels * sizeof( uchar4 ) ) ) return 1;
+	if( pt->aovs && pt->allocAovFrame() ) // no frame without its feature buffers: forget it like allocWork does
+	{
+		pt->width = pt->height = 0;
+		pt->fbF32.release();
+		pt->fbU8.release();
+		pt->releaseAovs();
+		return 1;
+	}
 	if( allocWork( pt ) ) return 1;
 	return mvrt_pt_clear_framebuffer( pt, stream ); // :88
 }
@@ -1507,8 +1545,17 @@ int mvrt_pt::launchPass( const CameraPinhole* passCams, int iteration, int nStep
 		MVRT_HIP( hipStreamWaitEvent( run, pt->forkEv, 0 ) );
 		after = pt->lastAccum;
 	}
+	AovBuffers aov = { nullptr, nullptr, nullptr, nullptr };
+	if( pt->aovs )
+	{
+		REQUIRE( sl.aovPart.p && pt->aovAlbedo.p && pt->aovNormalDepth.p, "internal: feature buffers not allocated" );
+		aov.partA = sl.aovPart.as<float4>();
+		aov.partN = aov.partA + sl.buf.cap / MVRT_SPP_PER_STEP;
+		aov.albedo = pt->aovAlbedo.as<float4>();
+		aov.normalDepth = pt->aovNormalDepth.as<float4>();
+	}
 	int rc = launchPtStep( pt->intersector->dev(), sl.ws, pt->hdri, pt->pmj.as<float2>(), cams, f, sl.buf, pt->fbF32.as<float4>(), pt->numCUs,
-						   pt->profiling ? &pt->prof : nullptr, run, after );
+						   pt->profiling ? &pt->prof : nullptr, run, after, pt->aovs ? &aov : nullptr );
 	if( rc ) return rc;
 	MVRT_HIP( hipEventRecord( sl.accumDone, run ) );
 	pt->lastAccum = sl.accumDone;
@@ -1545,6 +1592,71 @@ MVRT_EXPORT int mvrt_pt_read_framebuffer( mvrt_pt* pt, void* stream, float* rgba
 	return 0;
 }
 MVRT_EXPORT float* mvrt_pt_framebuffer_dev( mvrt_pt* pt ) { return pt ? pt->fbF32.as<float>() : nullptr; }
+
+// ---- first-hit feature buffers ------------------------------------------------------------------------------
+MVRT_EXPORT int mvrt_pt_set_aovs( mvrt_pt* pt, int enable )
+{
+	REQUIRE( pt, "null argument" );
+	if( pt->drain() ) return 1;
+	const bool on = enable != 0;
+	if( on == pt->aovs ) return 0;
+	REQUIRE( pt->steps == 0, "mvrt_pt_set_aovs: %d steps are accumulated in the frame buffer, the feature buffers would not match its sample count (mvrt_pt_clear_framebuffer first)",
+			 pt->steps );
+	if( !pt->fbF32.p ) // no frame yet: the next resize allocates (or does not)
+	{
+		pt->aovs = on;
+		return 0;
+	}
+	if( on )
+	{
+		if( pt->allocAovFrame() )
+		{
+			pt->releaseAovs(); // the frame stays as it was, without feature buffers
+			return 1;
+		}
+		MVRT_HIP( hipMemset( pt->aovAlbedo.p, 0, pt->aovAlbedo.bytes ) );
+		MVRT_HIP( hipMemset( pt->aovNormalDepth.p, 0, pt->aovNormalDepth.bytes ) );
+		MVRT_HIP( hipStreamSynchronize( nullptr ) );
+	}
+	else pt->releaseAovs();
+	pt->aovs = on;
+	return allocWork( pt ); // the partial sums live beside the path state and count against the same budget; a failure leaves NO frame, like every reallocation
+}
+static DevBuf* aovBuffer( mvrt_pt* pt, int which, const char* who )
+{
+	if( !pt )
+	{
+		mvrtSetError( "%s: null argument", who );
+		return nullptr;
+	}
+	if( which != MVRT_AOV_ALBEDO && which != MVRT_AOV_NORMAL_DEPTH )
+	{
+		mvrtSetError( "%s: no feature buffer %d (MVRT_AOV_ALBEDO, MVRT_AOV_NORMAL_DEPTH)", who, which );
+		return nullptr;
+	}
+	DevBuf* b = which == MVRT_AOV_ALBEDO ? &pt->aovAlbedo : &pt->aovNormalDepth;
+	if( !pt->aovs || !b->p )
+	{
+		mvrtSetError( pt->aovs ? "%s: no frame buffer" : "%s: feature buffers are off (mvrt_pt_set_aovs)", who );
+		return nullptr;
+	}
+	return b;
+}
+MVRT_EXPORT float* mvrt_pt_aov_dev( mvrt_pt* pt, int which )
+{
+	DevBuf* b = aovBuffer( pt, which, "mvrt_pt_aov_dev" );
+	return b ? b->as<float>() : nullptr;
+}
+MVRT_EXPORT int mvrt_pt_read_aov( mvrt_pt* pt, void* stream, int which, float* rgbaHost )
+{
+	DevBuf* b = aovBuffer( pt, which, "mvrt_pt_read_aov" );
+	if( !b ) return 1;
+	REQUIRE( rgbaHost, "mvrt_pt_read_aov: null argument" );
+	if( pt->join( (hipStream_t)stream ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( rgbaHost, b->p, pt->ownedPixels * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
+	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
+	return 0;
+}
 MVRT_EXPORT uint8_t* mvrt_pt_framebuffer_u8_dev( mvrt_pt* pt ) { return pt ? pt->fbU8.as<uint8_t>() : nullptr; }
 MVRT_EXPORT const float* mvrt_pt_sample_radiance_dev( mvrt_pt* pt )
 {

@@ -887,8 +887,85 @@ __global__ void __launch_bounds__( 256 ) kPtAccumulate( PtParams P, float4* __re
 	}
 }
 
+// ---- first-hit feature buffers (mvrt_pt_set_aovs) ----------------------------------------------------
+// Runs right after the stage-0 traversal, when nothing is compacted yet: slot i == task i, so the 16 samples of (step, pixel) `ps` are entries
+// ps * 16 .. ps * 16 + 15 of every array.  FOUR lanes per (step, pixel), lane q holding samples 4q .. 4q+3: every load is 16 bytes per lane (4 bytes of
+// hitN) at consecutive addresses across the wave.  The 16 samples are added in ascending spp order starting from +0 like kPtAccumulate does: the running
+// sum is handed from lane 0 to lane 3 of the group, each adding its four samples onto it in turn.  Writes, per (step, pixel), the partial sums
+// { albedo.xyz, hits } and { normal.xyz, t } that kPtAovAccumulate adds to the buffers in step order.
+struct AovRecords
+{
+	const float* hitT;
+	const uint64_t* hitPath;
+	const uint8_t* hitN;
+	const float *rdx, *rdy, *rdz; // PathSet 0: the primary rays as kPtGenerate wrote them (stage 0 shades into set 1)
+};
+__global__ void __launch_bounds__( 256 ) kPtAovReduce( SvoDev svo, AovRecords r, uint64_t nPixelSteps, float4* __restrict__ partA, float4* __restrict__ partN )
+{
+	const uint32_t q = threadIdx.x & 3u;
+	for( uint64_t ps = ( (uint64_t)blockIdx.x * 256 + threadIdx.x ) >> 2; ps < nPixelSteps; ps += (uint64_t)gridDim.x * 64 ) // (the 4 lanes of a group share ps)
+	{
+		const uint64_t base = ps * MVRT_SPP_PER_STEP + q * 4u;
+		const float4 t4 = *(const float4*)( r.hitT + base );
+		const ulonglong2 p01 = *(const ulonglong2*)( r.hitPath + base ), p23 = *(const ulonglong2*)( r.hitPath + base + 2 );
+		const uint32_t n4 = *(const uint32_t*)( r.hitN + base );
+		const float4 dx = *(const float4*)( r.rdx + base ), dy = *(const float4*)( r.rdy + base ), dz = *(const float4*)( r.rdz + base );
+		const float t[4] = { t4.x, t4.y, t4.z, t4.w };
+		const uint64_t path[4] = { p01.x, p01.y, p23.x, p23.y };
+		const float rx[4] = { dx.x, dx.y, dx.z, dx.w }, ry[4] = { dy.x, dy.y, dy.z, dy.w }, rz[4] = { dz.x, dz.y, dz.z, dz.w };
+		// the four gathers of this lane first (independent of the running sum), then the additions in order
+		uint32_t colour[4];
+#pragma unroll
+		for( int k = 0; k < 4; k++ ) colour[k] = t[k] != MVRT_MAXF ? svo.attrs[voxelIndexFromPath( svo, path[k] )].x : 0u;
+		float acc[8] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+#pragma unroll
+		for( uint32_t turn = 0; turn < 4; turn++ )
+		{
+			if( q == turn )
+			{
+#pragma unroll
+				for( int k = 0; k < 4; k++ )
+				{
+					if( t[k] == MVRT_MAXF ) continue; // a primary ray that missed adds nothing
+					const f3 a = rawReflectance( colour[k] );
+					const f3 n = getHitN( (int)( ( n4 >> ( 8 * k ) ) & 0xFFu ), mk3( rx[k], ry[k], rz[k] ) );
+					acc[0] += a.x;
+					acc[1] += a.y;
+					acc[2] += a.z;
+					acc[3] += 1.0f;
+					acc[4] += n.x;
+					acc[5] += n.y;
+					acc[6] += n.z;
+					acc[7] += t[k];
+				}
+			}
+#pragma unroll
+			for( int j = 0; j < 8; j++ ) acc[j] = __shfl( acc[j], (int)( ( threadIdx.x & 60u ) | turn ) ); // 4-lane groups never straddle a wave
+		}
+		if( q == 0 ) partA[ps] = make_float4( acc[0], acc[1], acc[2], acc[3] );
+		if( q == 1 ) partN[ps] = make_float4( acc[4], acc[5], acc[6], acc[7] );
+	}
+}
+// the partial sums of a pass, added to the two buffers one merged step after the other (launched behind kPtAccumulate: same event chain, same order)
+__global__ void __launch_bounds__( 256 ) kPtAovAccumulate( uint64_t validOwnedPixels, int nSteps, const float4* __restrict__ partA, const float4* __restrict__ partN,
+															 float4* __restrict__ albedo, float4* __restrict__ normalDepth )
+{
+	for( uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < validOwnedPixels; p += (uint64_t)gridDim.x * 256 )
+	{
+		float4 a = albedo[p], n = normalDepth[p];
+		for( int b = 0; b < nSteps; b++ )
+		{
+			const float4 pa = partA[(uint64_t)b * validOwnedPixels + p], pn = partN[(uint64_t)b * validOwnedPixels + p];
+			a.x += pa.x; a.y += pa.y; a.z += pa.z; a.w += pa.w;
+			n.x += pn.x; n.y += pn.y; n.z += pn.z; n.w += pn.w;
+		}
+		albedo[p] = a;
+		normalDepth[p] = n;
+	}
+}
+
 int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hdri, const float2* pmj, const CameraPinhole* cams, const PtFrame& frame,
-				  const PtBuffers& buf, float4* frameBuffer, int nCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter )
+				  const PtBuffers& buf, float4* frameBuffer, int nCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov )
 {
 	PtParams P;
 	P.svo = svo;
@@ -964,6 +1041,14 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 				hipLaunchKernelGGL( kPtTraceStream<1>, dim3( g ), dim3( 64 ), 0, stream, P, ws, stage, setIdx, nKinds, shadowKind, streamChunk( nSamples * nKinds, g ), smallRpl, smallMinW );
 		}
 		PROF_END();
+		if( aov && stage == 0 ) // the first-hit records are complete and still in task order; the stage-1 traversal overwrites them, the stage-1 shade the directions
+		{
+			const AovRecords rec = { buf.hitT, buf.hitPath, buf.hitN, buf.set[0].rdx, buf.set[0].rdy, buf.set[0].rdz };
+			const uint64_t nPixelSteps = frame.validOwnedPixels * frame.nSteps;
+			PROF_BEGIN( MVRT_K_OTHER );
+			hipLaunchKernelGGL( kPtAovReduce, dim3( persistentGrid( nPixelSteps * 4, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, svo, rec, nPixelSteps, aov->partA, aov->partN );
+			PROF_END();
+		}
 		PROF_BEGIN( MVRT_K_OTHER );
 		// survivors per block were counted by the traversal's result stores; scan them (and account the rays)
 		// (a 256-thread workgroup: a 1024-thread one needs all 16 wave slots of one CU at once and waits -- up to a millisecond, measured on a tile share -- while the
@@ -1001,6 +1086,13 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 	PROF_BEGIN( MVRT_K_OTHER );
 	hipLaunchKernelGGL( kPtAccumulate, dim3( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, P, frameBuffer );
 	PROF_END();
+	if( aov )
+	{
+		PROF_BEGIN( MVRT_K_OTHER );
+		hipLaunchKernelGGL( kPtAovAccumulate, dim3( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, frame.validOwnedPixels, frame.nSteps, aov->partA,
+							aov->partN, aov->albedo, aov->normalDepth );
+		PROF_END();
+	}
 	MVRT_HIP( hipGetLastError() );
 	return 0;
 }

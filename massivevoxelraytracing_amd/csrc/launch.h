@@ -81,8 +81,17 @@ struct PtProfiler
 	virtual void begin( int kernelClass, hipStream_t s ) = 0;
 	virtual void end( hipStream_t s ) = 0;
 };
+// First-hit feature buffers (mvrt_pt_set_aovs).  Kept out of PtBuffers / PtParams on purpose: those are kernel arguments and a device-resident table of the
+// traversal and shade kernels, whose offsets must not move.  partA / partN: per (step, pixel) of ONE pass, indexed step * validOwnedPixels + localPixel like Ls*,
+// the 16-sample sums { albedo.xyz, hits } and { normal.xyz, t }; albedo / normalDepth: the accumulation buffers, float4 per owned pixel like the frame buffer.
+struct AovBuffers
+{
+	float4 *partA, *partN;
+	float4 *albedo, *normalDepth;
+};
+// aov == nullptr: exactly the launches of a library without feature buffers
 int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hdri, const float2* pmj, const CameraPinhole* cams /* frame.nSteps */, const PtFrame& frame, const PtBuffers& buf, float4* frameBuffer,
-				  int numCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter );
+				  int numCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov = nullptr );
 
 int launchResolve( const float4* fb, uint64_t n, uchar4* out, hipStream_t stream );
 int launchAssembleTiles( const float4* gathered, int tileCount, uint64_t rankStridePixels, int W, int H, float4* frame, hipStream_t stream );

@@ -1,0 +1,83 @@
+"""First-hit feature buffers, the part that needs no GPU: the recipe of tests/aov_expected.py is pinned to the oracle's own path tracer, and the
+three entry points exist in the header, the library, the Python mirror and the C++ mirror."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import aov_expected as A
+from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_rebuilt_primary_rays_hit_where_the_oracle_path_tracer_hits():
+    """the helper rebuilds each sample's primary ray from oracle primitives (murmur stream, PMJ dimensions 0 and 1, thin-lens camera); the oracle's renderPT
+    port reports per sample how many of the path's own rays hit: a path has a hit at all exactly when its primary ray hit.  Two iterations."""
+    from oracle import oracle as O
+    tris = bunny_tris()
+    cols, emis = position_colors(tris)
+    sc = O.build_scene_from_triangles(tris, 256, cols, emis)
+    rgba, hw, hh = O.decode_rgbe(hdr_bytes())
+    H = O.HDRI(rgba, hw, hh, rgba, hw, hh, math_mode=1)
+    w, h = 64, 40
+    cam = probe_camera(sc.origin, sc.dps, 256, focus=9.0, lens_r=0.05)
+    counts = []
+    for it in (0, 1):
+        path_hits = np.zeros(w * h * 16, np.uint8)
+        sc.render_pt(H, cam, w, h, it, math_mode=1, threads=8, path_hits=path_hits)
+        ro, rd = A.primary_rays(O, cam, w, h, it)
+        pa, pn, hit, normal = A.step_partials(O, sc, ro, rd)
+        assert np.array_equal(hit.reshape(-1), path_hits > 0), it
+        counts.append(int(hit.sum()))
+        # the sums are what their definition says: hits counted in albedo.w, one unit normal per hit, depth positive
+        assert np.array_equal(pa[:, 3], hit.sum(1).astype(np.float32))
+        assert np.array_equal(np.abs(normal).sum(2), hit.astype(np.float32))
+        assert (pn[:, 3][hit.any(1)] > 0).all() and (pn[:, 3][~hit.any(1)] == 0).all()
+        assert (pa[:, 0:3] <= pa[:, 3:4]).all()  # colours are <= 1 per hit
+    assert counts == [5827, 5844]  # of 40 960 samples each
+
+
+def test_feature_buffer_entry_points_exist_in_every_layer(tmp_path):
+    import massivevoxelraytracing_amd as mv
+    text = open(os.path.join(ROOT, "include", "mvrt.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for decl in (r"int\s+mvrt_pt_set_aovs\s*\(\s*mvrt_pt\s*\*\s*pt\s*,\s*int\s+enable\s*\)", r"float\s*\*\s*mvrt_pt_aov_dev\s*\(\s*mvrt_pt\s*\*\s*pt\s*,\s*int\s+which\s*\)",
+                 r"int\s+mvrt_pt_read_aov\s*\(\s*mvrt_pt\s*\*\s*pt\s*,\s*void\s*\*\s*stream\s*,\s*int\s+which\s*,\s*float\s*\*\s*rgbaHost\s*\)"):
+        assert re.search(decl, code), decl
+    assert re.search(r"#define\s+MVRT_AOV_ALBEDO\s+0\b", code) and re.search(r"#define\s+MVRT_AOV_NORMAL_DEPTH\s+1\b", code)
+    assert "mvrt_resolve_buffer is NOT meant for them" in text
+    lib = ctypes.CDLL(mv.LIB_PATH)
+    for s in ("mvrt_pt_set_aovs", "mvrt_pt_aov_dev", "mvrt_pt_read_aov"):
+        assert hasattr(lib, s), "libmvrt_hip.so does not export " + s
+        assert s in mv.SIGNATURES
+    assert (mv.PathTracer.AOV_ALBEDO, mv.PathTracer.AOV_NORMAL_DEPTH) == (0, 1)
+    for m in ("set_aovs", "read_aov", "aov_dev"):
+        assert callable(getattr(mv.PathTracer, m))
+    # argument validation happens before any GPU call
+    l = mv.lib()
+    assert l.mvrt_pt_set_aovs(None, 1) != 0
+    assert l.mvrt_pt_aov_dev(None, 0) is None and b"null" in l.mvrt_last_error()
+    assert l.mvrt_pt_read_aov(None, None, 0, None) != 0
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "aov_usage"
+    libdir = os.path.dirname(mv.LIB_PATH)
+    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "aov_usage.cpp"), "-o", str(exe),
+                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
+    assert b"MVRT_AOV_ALBEDO 0 MVRT_AOV_NORMAL_DEPTH 1" in out
+
+
+def test_image_encodings_of_the_batch_driver():
+    """the byte encodings apps/rtcamp_batch --aov applies, restated in fp32: a fully covered white pixel is 255, a normal of -1 / 0 / +1 maps to 0 / 128 / 255"""
+    samples = np.array([16, 16, 32, 16], np.float32)
+    albedo = np.array([[16, 16, 16, 16], [0, 0, 0, 0], [16, 8, 4, 20], [4, 8, 12, 16]], np.float32)
+    assert A.encode_albedo(albedo, samples).tolist() == [[255, 255, 255], [0, 0, 0], [128, 64, 32], [64, 128, 191]]
+    normal = np.array([[16, 0, -16, 0], [0, 0, 0, 0], [16, -16, 0, 0], [-8, 8, 4, 0]], np.float32)
+    assert A.encode_normal(normal, samples).tolist() == [[255, 128, 0], [128, 128, 128], [191, 64, 128], [64, 191, 159]]
