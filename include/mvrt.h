@@ -73,6 +73,12 @@ typedef struct mvrt_svo_info
 
 int mvrt_svo_create( mvrt_svo** out );
 int mvrt_svo_destroy( mvrt_svo* svo ); /* IntersectorOctreeGPU::cleanUp, :26-38 */
+/* What a failed call leaves behind.  A handle holds a whole octree, derived tables included, or NONE (numberOfNodes == 0 in mvrt_svo_get_info); never anything in
+ * between.  Every entry point that reads an octree refuses an empty handle on the host with a "no octree" error, before any GPU work.
+ *   - build, build_ex, build_synthetic, upload and mvrt_pt_update_scene release the old octree first, like the reference: once their arguments are accepted, a
+ *     failure leaves the handle EMPTY.
+ *   - build_voxels and edit_voxels build the new arrays next to the old octree and release it only then: a failure up to there (every rejected argument, coordinate
+ *     or op among them) leaves the old octree exactly as it was, a failure after it (the derived tables) leaves the handle empty. */
 
 /* IntersectorOctreeGPU::build (:40-241): voxelize triangles (six-separating), sort, de-duplicate with
  * integer-mean attributes, build the octree DAG bottom-up and embed child masks -- all on the GPU.
@@ -101,8 +107,9 @@ int mvrt_svo_build_ex( mvrt_svo* svo, const float* verticesHost, const float* vc
  * colour = (c & 0xFFFFFF) | 0x404040, emission = colour if (c >> 56) == 0 else 0. */
 int mvrt_svo_build_synthetic( mvrt_svo* svo, int gridRes, uint64_t nRandomVoxels, uint64_t seed, const float origin[3], float dps, int flags, void* stream );
 
-/* Voxel lists (new; the reference only voxelizes triangles).  Device arrays in; the calls block like mvrt_svo_build.  A failure leaves the handle exactly as it was:
- * arguments are checked on the host before any GPU call, coordinates (and ops) on the device before anything is replaced -- the message names the LOWEST offending entry.
+/* Voxel lists (new; the reference only voxelizes triangles).  Device arrays in; the calls block like mvrt_svo_build.  A rejected list leaves the handle exactly as it
+ * was: arguments are checked on the host before any GPU call, coordinates (and ops) on the device before anything is replaced -- the message names the LOWEST offending
+ * entry.  (A failed allocation: see mvrt_svo_destroy above.)
  *
  * Build from a voxel list.  xyzDev: 3 x uint32 per voxel, each in [0, gridRes).  attribsDev: VoxelAttirb per entry {uchar4 color, uchar4 emission} (8 bytes), or NULL =
  * white, no emission (voxUtil.hpp's defaults).  Duplicate coordinates merge exactly like the reference's `unique` (integer mean of RGB per channel, alpha stored as 255,
@@ -258,7 +265,7 @@ int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream, int width, 
 int mvrt_pt_clear_framebuffer( mvrt_pt* pt, void* stream );									 /* :98-102, steps = 0 */
 /* PathTracer::loadHDRI (:104-116) + HDRI::load/loadPrimary (renderCommon.hpp:214-326): decoded float4 pixels.
  * rgbaPrimaryHost may be NULL (then primary lookups use the lighting map's pixels AND size -- the reference
- * would read out of bounds, renderCommon.hpp:356-363). */
+ * would read out of bounds, renderCommon.hpp:356-363).  A failed load leaves the map loaded before, or none, fully in place. */
 int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaHost, int width, int height, const float* rgbaPrimaryHost, int widthPrimary, int heightPrimary );
 /* same from Radiance .hdr files (RGBE, flat or RLE; value = c * 2^(E-136)); filePrimary may be NULL */
 int mvrt_pt_load_hdri_file( mvrt_pt* pt, void* stream, const char* file, const char* filePrimary );
@@ -371,6 +378,11 @@ typedef struct mvrt_pt_stats
  * instead of what hipMemGetInfo reports.  After a failed (re)allocation the handle has NO frame (steps fail with an error until the next
  * successful mvrt_pt_resize_framebuffer_if_needed). */
 int mvrt_pt_set_test_free_bytes( mvrt_pt* pt, uint64_t bytes );
+/* Failure-path testing without exhausting the device.  Every device allocation the library makes for itself (not mvrt_malloc) goes through one function.
+ * fail_allocation: the nth such allocation from now on THIS thread fails with an error that names this hook, then the hook is off again; 0 turns it off.
+ * allocation_state: process-wide tallies -- buffers and bytes held right now, allocations attempted so far; any pointer may be NULL. */
+int mvrt_test_fail_allocation( int64_t nth );
+int mvrt_test_allocation_state( uint64_t* liveBuffers, uint64_t* liveBytes, uint64_t* totalAllocs );
 int mvrt_pt_set_profiling( mvrt_pt* pt, int enabled ); /* HIP events on `stream` around each kernel of step(); read by get_stats */
 int mvrt_pt_reset_stats( mvrt_pt* pt );
 int mvrt_pt_get_stats( mvrt_pt* pt, void* stream, mvrt_pt_stats* out ); /* synchronises the stream */

@@ -121,6 +121,8 @@ SIGNATURES = {
     "mvrt_pt_set_debug_capture": (_i32, [_vp, _i32]),
     "mvrt_pt_read_debug_stage": (_i32, [_vp, _i32, _vp, _u64, _vp]),
     "mvrt_pt_set_test_free_bytes": (_i32, [_vp, _u64]),
+    "mvrt_test_fail_allocation": (_i32, [C.c_int64]),
+    "mvrt_test_allocation_state": (_i32, [_vp, _vp, _vp]),
     "mvrt_pt_set_profiling": (_i32, [_vp, _i32]),
     "mvrt_pt_reset_stats": (_i32, [_vp]),
     "mvrt_pt_get_stats": (_i32, [_vp, _vp, _vp]),
@@ -176,6 +178,18 @@ def device_name():
 
 def synchronize():
     _check(lib().mvrt_device_synchronize())
+
+
+def set_test_fail_allocation(nth):
+    """failure-path tests: the nth device allocation the library makes from now on this thread fails, then the hook is off again (0 = off)"""
+    _check(lib().mvrt_test_fail_allocation(int(nth)))
+
+
+def allocation_state():
+    """(buffers held, bytes held, allocations attempted so far) of the library's own device memory, process-wide"""
+    v = [C.c_uint64(0) for _ in range(3)]
+    _check(lib().mvrt_test_allocation_state(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 class DeviceArray:

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mvrt.h"
@@ -105,102 +106,39 @@ MVRT_EXPORT int mvrt_memcpy_d2h( void* host, const void* dev, uint64_t bytes, vo
 	return 0;
 }
 
-// small RAII device buffer (role of hipUtil.hpp:48-74 Buffer)
-struct DevBuf
+// failure-path tests (mvrt.h): the hook and the tallies themselves live in DevBuf::alloc / release (devbuf.h)
+MVRT_EXPORT int mvrt_test_fail_allocation( int64_t nth )
 {
-	void* p = nullptr;
-	uint64_t bytes = 0;
-	int alloc( uint64_t b )
-	{
-		release();
-		bytes = b;
-		MVRT_HIP( hipMalloc( &p, b ? b : 1 ) );
-		return 0;
-	}
-	void release()
-	{
-		if( p ) (void)hipFree( p );
-		p = nullptr;
-		bytes = 0;
-	}
-	~DevBuf() { release(); }
-	DevBuf() {}
-	DevBuf( const DevBuf& ) = delete;
-	void operator=( const DevBuf& ) = delete;
-	template <class T> T* as() const { return (T*)p; }
-};
+	g_devBufFailIn = nth > 0 ? nth : 0;
+	return 0;
+}
+MVRT_EXPORT int mvrt_test_allocation_state( uint64_t* liveBuffers, uint64_t* liveBytes, uint64_t* totalAllocs )
+{
+	if( liveBuffers ) *liveBuffers = g_devBufState.liveBuffers;
+	if( liveBytes ) *liveBytes = g_devBufState.liveBytes;
+	if( totalAllocs ) *totalAllocs = g_devBufState.totalAllocs;
+	return 0;
+}
 
-// ---- IntersectorOctreeGPU -------------------------------------------------------------------------------
-struct mvrt_svo
+// scratch of the persistent traversal kernels with its owner: one per octree handle and one per pipeline slot of a path tracer
+struct Workspace
 {
-	Node64* nodes = nullptr;
-	uint8_t* masks = nullptr;
-	uint32_t* psumCold = nullptr; // non-embedded flavour only
-	// tree flavour (GPU-built octrees without node sharing whose masks are not embedded): `nodes` = two-level bricks, `masks` = per-node mask,
-	// treeFirst = per-node first child (reference numbering), node ranges per builder level
-	uint32_t* treeFirst = nullptr;
-	uint32_t tree = 0, treeRoot = 0, nBricks = 0;
-	uint32_t treeLevelBase[24] = { 0 }, treeLevelCount[24] = { 0 };
-	uint2* attrs = nullptr;
-	uint64_t* morton = nullptr; // only after build()
-	DevBuf kids;				// embedded flavour: children[8] per node, 32 B per node (what the traversal reads)
-	DevBuf topTable;			// per-prefix start of the nVoxelsPSum walk (SvoDev::topTable), embedded flavour
-	uint32_t topLevels = 0;
-	DevBuf cellBlocks, cellEntries; // SvoDev::cellBlocks / cellEntries, only after build()
-	uint32_t cellBits = 0;
-	mutable DevBuf wsBuf;		// traversal workspace (spill rows + cursor), sized on demand
-	mutable DevBuf pathBuf;
-	mutable TraceWorkspace ws = { nullptr, 0, nullptr, nullptr, 0, nullptr };
-	mvrt_svo_info info;
-	uint8_t rootMask = 0;
-	uint32_t leafPsumIsPopcount = 1; // (uploads: checked, see launchCheckLeafPsum)
-	int buildFlags = 0;				 // MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK of the build, kept by edits
-	mvrt_pt* owner = nullptr; // the PathTracer this is the m_intersectorOctreeGPU of (its deferred / in-flight steps read this octree)
-	mvrt_svo()
-	{
-		memset( &info, 0, sizeof( info ) );
-		info.emissionScale = 7.5f; // IntersectorOctreeGPU.hpp:273
-	}
-	void cleanUp() // :26-38
-	{
-		if( nodes ) (void)hipFree( nodes );
-		if( masks ) (void)hipFree( masks );
-		if( psumCold ) (void)hipFree( psumCold );
-		if( treeFirst ) (void)hipFree( treeFirst );
-		treeFirst = nullptr;
-		tree = treeRoot = nBricks = 0;
-		if( attrs ) (void)hipFree( attrs );
-		if( morton ) (void)hipFree( morton );
-		nodes = nullptr;
-		masks = nullptr;
-		psumCold = nullptr;
-		attrs = nullptr;
-		morton = nullptr;
-		topTable.release();
-		kids.release();
-		topLevels = 0;
-		cellBlocks.release();
-		cellEntries.release();
-		cellBits = 0;
-		float es = info.emissionScale;
-		memset( &info, 0, sizeof( info ) );
-		info.emissionScale = es;
-	}
-	int ensureWorkspace( uint64_t nPaths = 0 ) const // one per handle; users of one handle must be stream-ordered
+	DevBuf wsBuf, pathBuf; // spill rows + cursor, sized on demand; per-ray paths
+	TraceWorkspace ws = { nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr };
+	int ensure( uint32_t levels, uint64_t nPaths )
 	{
 		if( nPaths > ws.pathCap )
 		{
+			ws.paths = nullptr;
+			ws.pathCap = 0;
 			if( pathBuf.alloc( nPaths * 12 ) ) return 1; // 8-byte path + 4-byte t scratch per ray
 			ws.paths = pathBuf.as<uint64_t>();
 			ws.pathCap = nPaths;
 		}
 		const uint64_t lanes = traceWorkspaceLanes();
-		const uint64_t rows = 2 * (uint64_t)( info.levels ? info.levels : 1 ) + 2; // fast path: 1 row per level; irregular rays: 2 per slot
+		const uint64_t rows = 2 * (uint64_t)( levels ? levels : 1 ) + 2; // fast path: 1 row per level; irregular rays: 2 per slot
 		const uint64_t bytes = 256 + rows * lanes * ( sizeof( uint4 ) + 2 * sizeof( uint32_t ) );
-		if( wsBuf.bytes < bytes )
-		{
-			if( wsBuf.alloc( bytes ) ) return 1;
-		}
+		if( wsBuf.bytes < bytes && wsBuf.alloc( bytes ) ) return 1;
 		ws.cursor = (unsigned long long*)wsBuf.p;
 		ws.spill = (uint4*)( (uint8_t*)wsBuf.p + 256 );
 		ws.spillStride = lanes;
@@ -208,33 +146,69 @@ struct mvrt_svo
 		ws.spillMask2 = ws.spillMask + rows * lanes;
 		return 0;
 	}
+};
+
+// ---- IntersectorOctreeGPU -------------------------------------------------------------------------------
+// Everything that describes one resident octree.  The calls that make one fill a local Octree and move it into the handle when it is complete, derived
+// tables included: a handle holds a whole octree or an empty one (numberOfNodes == 0), which every entry point that reads an octree refuses on the host.
+struct Octree
+{
+	DevBuf nodes, masks;
+	DevBuf psumCold; // non-embedded flavour only
+	// tree flavour (GPU-built octrees without node sharing whose masks are not embedded): `nodes` = two-level bricks, `masks` = per-node mask,
+	// treeFirst = per-node first child (reference numbering), node ranges per builder level
+	DevBuf treeFirst;
+	uint32_t tree = 0, treeRoot = 0, nBricks = 0;
+	uint32_t treeLevelBase[24] = { 0 }, treeLevelCount[24] = { 0 };
+	DevBuf attrs;
+	DevBuf morton;	 // only after build()
+	DevBuf kids;	 // embedded flavour: children[8] per node, 32 B per node (what the traversal reads)
+	DevBuf topTable; // per-prefix start of the nVoxelsPSum walk (SvoDev::topTable), embedded flavour
+	uint32_t topLevels = 0;
+	DevBuf cellBlocks, cellEntries; // SvoDev::cellBlocks / cellEntries, only after build()
+	uint32_t cellBits = 0;
+	mvrt_svo_info info = {}; // (emissionScale: not here, it belongs to the handle)
+	uint8_t rootMask = 0;
+	uint32_t leafPsumIsPopcount = 1; // (uploads: checked, see launchCheckLeafPsum)
+	int buildFlags = 0;				 // MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK of the build, kept by edits
+};
+struct mvrt_svo
+{
+	Octree oct;
+	mutable Workspace work;		 // one per handle; users of one handle must be stream-ordered
+	float emissionScale = 7.5f; // IntersectorOctreeGPU.hpp:273
+	mvrt_pt* owner = nullptr;	 // the PathTracer this is the m_intersectorOctreeGPU of (its deferred / in-flight steps read this octree)
+	bool empty() const { return oct.info.numberOfNodes == 0; }
+	void cleanUp() { oct = Octree(); } // :26-38
+	int ensureWorkspace( uint64_t nPaths = 0 ) const { return work.ensure( oct.info.levels, nPaths ); }
 	SvoDev dev() const
 	{
+		const mvrt_svo_info& info = oct.info;
 		SvoDev d;
-		d.nodes = nodes;
-		d.masks = masks;
-		d.psumCold = psumCold;
-		d.attrs = attrs;
+		d.nodes = oct.nodes.as<Node64>();
+		d.masks = oct.masks.as<uint8_t>();
+		d.psumCold = oct.psumCold.as<uint32_t>();
+		d.attrs = oct.attrs.as<uint2>();
 		d.nNodes = info.numberOfNodes;
 		d.nVoxels = info.numberOfVoxels;
 		d.lower = mk3( info.lower[0], info.lower[1], info.lower[2] );
 		d.upper = mk3( info.upper[0], info.upper[1], info.upper[2] );
 		d.dps = info.dps;
-		d.emissionScale = info.emissionScale;
+		d.emissionScale = emissionScale;
 		d.hasEmission = info.hasEmission;
 		d.embedded = info.embeddedMask;
 		d.levels = info.levels;
 		d.rootIndex = info.numberOfNodes - 1; // root = last node, :250
-		d.rootMask = rootMask;
-		d.kids = kids.as<uint32_t>();
-		d.topTable = topTable.as<uint2>();
-		d.topLevels = topLevels;
-		d.cellBlocks = cellEntries.p ? cellBlocks.as<uint32_t>() : nullptr;
-		d.cellEntries = cellEntries.as<uint2>();
-		d.cellBits = cellBits;
-		d.tree = tree;
-		d.treeRoot = treeRoot;
-		d.leafPsumIsPopcount = leafPsumIsPopcount;
+		d.rootMask = oct.rootMask;
+		d.kids = oct.kids.as<uint32_t>();
+		d.topTable = oct.topTable.as<uint2>();
+		d.topLevels = oct.topLevels;
+		d.cellBlocks = oct.cellEntries.p ? oct.cellBlocks.as<uint32_t>() : nullptr;
+		d.cellEntries = oct.cellEntries.as<uint2>();
+		d.cellBits = oct.cellBits;
+		d.tree = oct.tree;
+		d.treeRoot = oct.treeRoot;
+		d.leafPsumIsPopcount = oct.leafPsumIsPopcount;
 		return d;
 	}
 };
@@ -247,46 +221,36 @@ static int ownerFlush( const mvrt_svo* s ) { return s && s->owner ? ptFlush( s->
 static int ownerDrain( const mvrt_svo* s ) { return s && s->owner ? ptDrain( s->owner ) : 0; }
 
 // after nodes are in place: the prefix table that shortens every nVoxelsPSum walk (voxelIndexFromPath).  7 levels = 16 MiB (measured: shade kernel 19.3 ms without, 17.2 ms with 6 levels, 16.6 ms with 7, 15.9 ms with 8 = 128 MiB, per 4 steps).
-static int buildTopTable( mvrt_svo* s, hipStream_t st )
+static int buildTopTable( Octree& o, hipStream_t st )
 {
-	s->topTable.release();
-	s->kids.release();
-	s->topLevels = 0;
-	if( !s->info.embeddedMask || !s->nodes || s->info.levels == 0 ) return 0;
+	const uint32_t nNodes = o.info.numberOfNodes, levels = o.info.levels;
+	if( !o.info.embeddedMask || levels == 0 ) return 0;
 	// children array (32 B per node) + behind it the prefix tables of the start below the root (traverse_stream.h): one buffer, one base register
-	if( s->kids.alloc( (uint64_t)s->info.numberOfNodes * 32 + prefixTabEntries( s->info.levels ) * 4 ) ) return 1;
-	if( launchCopyKids( s->nodes, s->info.numberOfNodes, s->kids.as<uint32_t>(), st ) ) return 1;
-	if( launchBuildPrefixRefs( s->kids.as<uint32_t>(), ( s->info.numberOfNodes - 1 ) | ( (uint32_t)s->rootMask << 24 ), hintTabLevelsOf( s->info.levels ),
-							   s->kids.as<uint32_t>() + (uint64_t)s->info.numberOfNodes * 8, st ) )
+	if( o.kids.alloc( (uint64_t)nNodes * 32 + prefixTabEntries( levels ) * 4 ) ) return 1;
+	if( launchCopyKids( o.nodes.as<Node64>(), nNodes, o.kids.as<uint32_t>(), st ) ) return 1;
+	if( launchBuildPrefixRefs( o.kids.as<uint32_t>(), ( nNodes - 1 ) | ( (uint32_t)o.rootMask << 24 ), hintTabLevelsOf( levels ), o.kids.as<uint32_t>() + (uint64_t)nNodes * 8, st ) )
 		return 1;
 	static const int envK = (int)mvrtKnob( "MVRT_TOP_LEVELS", 7 );
 	uint32_t k = (uint32_t)( envK < 0 ? 0 : ( envK > 8 ? 8 : envK ) );
-	if( k > s->info.levels ) k = s->info.levels;
+	if( k > levels ) k = levels;
 	if( k == 0 ) return 0;
-	if( s->topTable.alloc( ( 1ull << ( 3 * k ) ) * sizeof( uint2 ) ) ) return 1;
-	if( launchBuildTopTable( s->nodes, s->info.numberOfNodes - 1, k, s->topTable.as<uint2>(), st ) ) return 1;
-	s->topLevels = k;
+	if( o.topTable.alloc( ( 1ull << ( 3 * k ) ) * sizeof( uint2 ) ) ) return 1;
+	if( launchBuildTopTable( o.nodes.as<Node64>(), nNodes - 1, k, o.topTable.as<uint2>(), st ) ) return 1;
+	o.topLevels = k;
 	return 0;
 }
 
-static int ilog2Exact( int v ) // log2 of a power of two, -1 for anything else (zero, negative, not a power of two): every int terminates
-{
-	if( v <= 0 || ( v & ( v - 1 ) ) != 0 ) return -1;
-	int l = 0;
-	while( ( v >> l ) != 1 ) l++;
-	return l;
-}
-static void setBounds( mvrt_svo* s, const float origin[3], float dps, int gridRes )
+static void setBounds( mvrt_svo_info& info, const float origin[3], float dps, int gridRes )
 {
 	// IntersectorOctreeGPU.hpp:78-80: m_upper = origin + float3{dps,dps,dps} * (float)gridRes
 	for( int k = 0; k < 3; k++ )
 	{
-		s->info.lower[k] = origin[k];
-		s->info.upper[k] = origin[k] + dps * (float)gridRes;
+		info.lower[k] = origin[k];
+		info.upper[k] = origin[k] + dps * (float)gridRes;
 	}
-	s->info.dps = dps;
-	s->info.gridRes = gridRes;
-	s->info.levels = ilog2Exact( gridRes );
+	info.dps = dps;
+	info.gridRes = gridRes;
+	info.levels = levelsOf( gridRes );
 }
 
 MVRT_EXPORT int mvrt_svo_create( mvrt_svo** out )
@@ -296,11 +260,7 @@ MVRT_EXPORT int mvrt_svo_create( mvrt_svo** out )
 }
 MVRT_EXPORT int mvrt_svo_destroy( mvrt_svo* svo )
 {
-	if( svo )
-	{
-		svo->cleanUp();
-		delete svo;
-	}
+	delete svo;
 	return 0;
 }
 
@@ -311,7 +271,7 @@ MVRT_EXPORT int mvrt_svo_check_upload( const void* nodes68Host, uint32_t numberO
 	REQUIRE( nodes68Host && numberOfNodes > 0, "mvrt_svo_upload: empty octree" );
 	REQUIRE( gridRes >= 2 && gridRes <= ( 1 << 21 ) && ( gridRes & ( gridRes - 1 ) ) == 0, "mvrt_svo_upload: rule 1: gridRes %d is not a power of two in [2, 2^21]",
 			 gridRes );
-	const int L = ilog2Exact( gridRes );
+	const int L = levelsOf( gridRes );
 	REQUIRE( !embeddedMask || numberOfNodes < 0xFFFFFFu, "mvrt_svo_upload: rule 5: embedded masks need fewer than 0xFFFFFF nodes (IntersectorOctreeGPU.hpp:231), got %u",
 			 numberOfNodes );
 	const uint8_t* base = (const uint8_t*)nodes68Host;
@@ -403,113 +363,107 @@ MVRT_EXPORT int mvrt_svo_upload( mvrt_svo* svo, const void* nodes68Host, uint32_
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
 	svo->cleanUp();
+	Octree o;
 	DevBuf raw;
 	if( raw.alloc( (uint64_t)numberOfNodes * 68 ) ) return 1;
 	MVRT_HIP( hipMemcpyAsync( raw.p, nodes68Host, (uint64_t)numberOfNodes * 68, hipMemcpyHostToDevice, st ) );
-	MVRT_HIP( hipMalloc( (void**)&svo->nodes, (uint64_t)numberOfNodes * sizeof( Node64 ) ) );
-	MVRT_HIP( hipMalloc( (void**)&svo->masks, numberOfNodes ) );
-	MVRT_HIP( hipMalloc( (void**)&svo->attrs, (uint64_t)( numberOfVoxels ? numberOfVoxels : 1 ) * 8 ) );
-	if( numberOfVoxels ) MVRT_HIP( hipMemcpyAsync( svo->attrs, attribs8Host, (uint64_t)numberOfVoxels * 8, hipMemcpyHostToDevice, st ) );
-	if( !embeddedMask ) MVRT_HIP( hipMalloc( (void**)&svo->psumCold, (uint64_t)numberOfNodes * 32 ) );
-	if( launchConvertNodes( raw.as<uint8_t>(), numberOfNodes, svo->nodes, svo->masks, svo->psumCold, embeddedMask ? 0 : 1, st ) ) return 1;
-	svo->info.numberOfNodes = numberOfNodes;
-	svo->info.numberOfVoxels = numberOfVoxels;
-	svo->info.hasEmission = hasEmission ? 1 : 0;
-	svo->info.embeddedMask = embeddedMask ? 1 : 0;
-	svo->info.totalDumpedVoxels = 0;
-	setBounds( svo, origin, dps, gridRes );
-	svo->rootMask = ( (const uint8_t*)nodes68Host )[(uint64_t)( numberOfNodes - 1 ) * 68];
-	svo->leafPsumIsPopcount = 1;
+	if( o.nodes.alloc( (uint64_t)numberOfNodes * sizeof( Node64 ) ) || o.masks.alloc( numberOfNodes ) || o.attrs.alloc( (uint64_t)numberOfVoxels * 8 ) ) return 1;
+	if( numberOfVoxels ) MVRT_HIP( hipMemcpyAsync( o.attrs.p, attribs8Host, (uint64_t)numberOfVoxels * 8, hipMemcpyHostToDevice, st ) );
+	if( !embeddedMask && o.psumCold.alloc( (uint64_t)numberOfNodes * 32 ) ) return 1;
+	if( launchConvertNodes( raw.as<uint8_t>(), numberOfNodes, o.nodes.as<Node64>(), o.masks.as<uint8_t>(), o.psumCold.as<uint32_t>(), embeddedMask ? 0 : 1, st ) ) return 1;
+	o.info.numberOfNodes = numberOfNodes;
+	o.info.numberOfVoxels = numberOfVoxels;
+	o.info.hasEmission = hasEmission ? 1 : 0;
+	o.info.embeddedMask = embeddedMask ? 1 : 0;
+	setBounds( o.info, origin, dps, gridRes );
+	o.rootMask = ( (const uint8_t*)nodes68Host )[(uint64_t)( numberOfNodes - 1 ) * 68];
 	if( embeddedMask ) // an uploaded octree may carry any nVoxelsPSum (mvrt.h): the popcount shortcut of the last level only for canonical ones
 	{
 		DevBuf bad;
 		if( bad.alloc( 4 ) ) return 1;
-		if( launchCheckLeafPsum( svo->nodes, svo->masks, numberOfNodes, bad.as<uint32_t>(), st ) ) return 1;
+		if( launchCheckLeafPsum( o.nodes.as<Node64>(), o.masks.as<uint8_t>(), numberOfNodes, bad.as<uint32_t>(), st ) ) return 1;
 		uint32_t h = 0;
 		MVRT_HIP( hipMemcpyAsync( &h, bad.p, 4, hipMemcpyDeviceToHost, st ) );
 		MVRT_HIP( hipStreamSynchronize( st ) );
-		svo->leafPsumIsPopcount = h ? 0u : 1u;
+		o.leafPsumIsPopcount = h ? 0u : 1u;
 	}
-	if( buildTopTable( svo, st ) ) return 1;
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( buildTopTable( o, st ) ) return 1;
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (raw is released on return)
+	svo->oct = std::move( o );
 	return 0;
 }
 
 // SvoDev::cellBlocks / cellEntries from the sorted voxel codes of a build (not for the tree flavour, whose traversal reports voxel indices itself)
-static int buildCellIndex( mvrt_svo* s, hipStream_t st )
+static int buildCellIndex( Octree& o, hipStream_t st )
 {
-	s->cellBlocks.release();
-	s->cellEntries.release();
-	s->cellBits = 0;
 	static const int on = (int)mvrtKnob( "MVRT_CELL_INDEX", 1 );
-	const uint32_t L = s->info.levels;
-	if( !on || s->tree || !s->morton || s->info.numberOfVoxels == 0 || L == 0 || L > 14u ) return 0;
+	const uint32_t L = o.info.levels;
+	if( !on || o.tree || !o.morton.p || o.info.numberOfVoxels == 0 || L == 0 || L > 14u ) return 0;
 	static const uint32_t blockBits = (uint32_t)mvrtKnob( "MVRT_CELL_BITS", 9 );
 	const uint32_t cellBits = 3u * ( L - 1u ) < blockBits ? 3u * ( L - 1u ) : blockBits; // 8 x 8 x 8 cells per block (fewer in octrees of fewer than 4 levels)
 	const uint64_t nBlockCodes = 1ull << ( 3u * ( L - 1u ) - cellBits );
-	DevBuf cnt;
-	size_t freeB0 = 0, totalB0 = 0;
-	if( hipMemGetInfo( &freeB0, &totalB0 ) != hipSuccess || nBlockCodes * 4 > freeB0 / 4 ) return 0;
-	if( cnt.alloc( 4 ) || s->cellBlocks.alloc( nBlockCodes * 4 ) ) return 1;
+	// an accelerator, not a necessity: where a table would take more than a quarter of what is free, the octree keeps the nVoxelsPSum walk
+	DevBuf cnt, blocks, entries;
+	size_t freeB = 0, totalB = 0;
+	if( hipMemGetInfo( &freeB, &totalB ) != hipSuccess || nBlockCodes * 4 > freeB / 4 ) return 0;
+	if( cnt.alloc( 4 ) || blocks.alloc( nBlockCodes * 4 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 4, st ) );
-	MVRT_HIP( hipMemsetAsync( s->cellBlocks.p, 0xFF, nBlockCodes * 4, st ) );
-	if( launchNumberCellBlocks( s->morton, s->info.numberOfVoxels, cellBits, s->cellBlocks.as<uint32_t>(), cnt.as<uint32_t>(), st ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( blocks.p, 0xFF, nBlockCodes * 4, st ) );
+	if( launchNumberCellBlocks( o.morton.as<uint64_t>(), o.info.numberOfVoxels, cellBits, blocks.as<uint32_t>(), cnt.as<uint32_t>(), st ) ) return 1;
 	uint32_t nBlocks = 0;
 	MVRT_HIP( hipMemcpyAsync( &nBlocks, cnt.p, 4, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) );
 	const uint64_t bytes = ( (uint64_t)nBlocks << cellBits ) * sizeof( uint2 );
-	// an accelerator, not a necessity: where it would take more than a quarter of what is free (or cannot be had), the octree keeps the nVoxelsPSum walk
-	size_t freeB = 0, totalB = 0;
-	if( hipMemGetInfo( &freeB, &totalB ) != hipSuccess || bytes > freeB / 4 || s->cellEntries.alloc( bytes ) )
-	{
-		(void)hipGetLastError();
-		s->cellBlocks.release();
-		s->cellEntries.release();
-		return 0;
-	}
-	MVRT_HIP( hipMemsetAsync( s->cellEntries.p, 0, bytes, st ) );
-	if( launchFillCellIndex( s->morton, s->info.numberOfVoxels, cellBits, s->cellBlocks.as<uint32_t>(), s->cellEntries.as<uint2>(), st ) ) return 1;
-	s->cellBits = cellBits;
+	if( hipMemGetInfo( &freeB, &totalB ) != hipSuccess || bytes > freeB / 4 ) return 0;
+	if( entries.alloc( bytes ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( entries.p, 0, bytes, st ) );
+	if( launchFillCellIndex( o.morton.as<uint64_t>(), o.info.numberOfVoxels, cellBits, blocks.as<uint32_t>(), entries.as<uint2>(), st ) ) return 1;
+	o.cellBlocks = std::move( blocks );
+	o.cellEntries = std::move( entries );
+	o.cellBits = cellBits;
 	return 0;
 }
 
-static int adoptBuild( mvrt_svo* svo, const SvoBuildResult& r, const float origin[3], float dps, int gridRes, int flags )
+// The builder's arrays become the handle's octree.  What the handle still holds (build_voxels, edit_voxels: the old octree, kept while the main arrays
+// were built next to it) is released before the derived tables are made; from there on a failure leaves the handle empty.
+static int adoptBuild( mvrt_svo* svo, SvoBuildResult& r, const float origin[3], float dps, int gridRes, int flags )
 {
-	svo->buildFlags = flags & ( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK );
-	svo->nodes = r.nodes;
-	svo->masks = r.masks;
-	svo->psumCold = r.psumCold;
-	svo->tree = r.tree;
-	svo->treeRoot = r.treeRoot;
-	svo->nBricks = r.nBricks;
-	svo->treeFirst = r.treeFirst;
-	memcpy( svo->treeLevelBase, r.treeLevelBase, sizeof( svo->treeLevelBase ) );
-	memcpy( svo->treeLevelCount, r.treeLevelCount, sizeof( svo->treeLevelCount ) );
-	svo->attrs = r.attrs;
-	svo->morton = r.morton;
-	svo->info.numberOfNodes = r.nNodes;
-	svo->info.numberOfVoxels = r.nVoxels;
-	svo->info.hasEmission = r.hasEmission;
-	svo->info.embeddedMask = r.embedded; // 0 when the octree has >= 0xFFFFFF nodes (IntersectorOctreeGPU.hpp:231) or on request
-	svo->info.totalDumpedVoxels = r.totalDumped;
-	svo->leafPsumIsPopcount = 1; // (this library's builder writes the exclusive popcounts)
-	setBounds( svo, origin, dps, gridRes );
-	MVRT_HIP( hipMemcpy( &svo->rootMask, svo->masks + ( r.nNodes - 1 ), 1, hipMemcpyDeviceToHost ) );
-	if( buildTopTable( svo, nullptr ) ) return 1;
-	if( buildCellIndex( svo, nullptr ) ) return 1;
+	Octree o;
+	o.buildFlags = flags & ( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK );
+	o.nodes = std::move( r.nodes );
+	o.masks = std::move( r.masks );
+	o.psumCold = std::move( r.psumCold );
+	o.treeFirst = std::move( r.treeFirst );
+	o.attrs = std::move( r.attrs );
+	o.morton = std::move( r.morton );
+	o.tree = r.tree;
+	o.treeRoot = r.treeRoot;
+	o.nBricks = r.nBricks;
+	memcpy( o.treeLevelBase, r.treeLevelBase, sizeof( o.treeLevelBase ) );
+	memcpy( o.treeLevelCount, r.treeLevelCount, sizeof( o.treeLevelCount ) );
+	o.info.numberOfNodes = r.nNodes;
+	o.info.numberOfVoxels = r.nVoxels;
+	o.info.hasEmission = r.hasEmission;
+	o.info.embeddedMask = r.embedded; // 0 when the octree has >= 0xFFFFFF nodes (IntersectorOctreeGPU.hpp:231) or on request
+	o.info.totalDumpedVoxels = r.totalDumped;
+	setBounds( o.info, origin, dps, gridRes );
+	svo->cleanUp();
+	MVRT_HIP( hipMemcpy( &o.rootMask, o.masks.as<uint8_t>() + ( r.nNodes - 1 ), 1, hipMemcpyDeviceToHost ) );
+	if( buildTopTable( o, nullptr ) ) return 1;
+	if( buildCellIndex( o, nullptr ) ) return 1;
 	MVRT_HIP( hipDeviceSynchronize() );
+	svo->oct = std::move( o );
 	return 0;
 }
 MVRT_EXPORT int mvrt_svo_build_ex( mvrt_svo* svo, const float* verticesHost, const float* vcolorsHost, const float* vemissionsHost, uint64_t nVertices, void* stream,
 								   const float origin[3], float dps, int gridRes, int flags )
 {
 	REQUIRE( svo && verticesHost && nVertices >= 3 && nVertices % 3 == 0, "mvrt_svo_build: need 3*k vertices" );
-	REQUIRE( ilog2Exact( gridRes ) > 0, "gridRes %d is not a power of two >= 2 (IntersectorOctreeGPU.hpp:48-51)", gridRes );
+	REQUIRE( levelsOf( gridRes ) > 0, "gridRes %d is not a power of two >= 2 (IntersectorOctreeGPU.hpp:48-51)", gridRes );
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
 	svo->cleanUp(); // :53
 	SvoBuildResult r;
-	memset( &r, 0, sizeof( r ) );
 	if( svoBuildFromTriangles( verticesHost, vcolorsHost, vemissionsHost, nVertices, mk3( origin[0], origin[1], origin[2] ), dps, gridRes, flags, st, &r ) ) return 1;
 	return adoptBuild( svo, r, origin, dps, gridRes, flags );
 }
@@ -521,92 +475,89 @@ MVRT_EXPORT int mvrt_svo_build( mvrt_svo* svo, const float* verticesHost, const 
 MVRT_EXPORT int mvrt_svo_build_synthetic( mvrt_svo* svo, int gridRes, uint64_t nRandomVoxels, uint64_t seed, const float origin[3], float dps, int flags, void* stream )
 {
 	REQUIRE( svo, "null argument" );
-	REQUIRE( ilog2Exact( gridRes ) > 0 && gridRes <= ( 1 << 21 ), "gridRes %d is not a power of two in [2, 2^21]", gridRes );
+	REQUIRE( levelsOf( gridRes ) > 0 && gridRes <= ( 1 << 21 ), "gridRes %d is not a power of two in [2, 2^21]", gridRes );
 	if( ownerDrain( svo ) ) return 1;
 	svo->cleanUp();
 	SvoBuildResult r;
-	memset( &r, 0, sizeof( r ) );
 	if( svoBuildSynthetic( nRandomVoxels, seed, gridRes, flags, (hipStream_t)stream, &r ) ) return 1;
 	return adoptBuild( svo, r, origin, dps, gridRes, flags );
 }
 
-// Voxel lists.  Every failure leaves the handle as it was: arguments are checked on the host first, the device checks (coordinates, ops) come before anything is
-// replaced, and a structural edit builds the new list and levels next to the old octree before it releases it.
+// Voxel lists.  Arguments are checked on the host first, the device checks (coordinates, ops) come before anything is replaced, and the new list and levels are
+// built next to the old octree: every failure up to there leaves the handle as it was.  adoptBuild then releases the old octree; a failure after that leaves it empty.
 MVRT_EXPORT int mvrt_svo_build_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t* attribsDev, uint64_t n, const float origin[3], float dps, int gridRes, int flags,
 									   void* stream )
 {
 	REQUIRE( svo, "mvrt_svo_build_voxels: null handle" );
 	REQUIRE( xyzDev && origin, "mvrt_svo_build_voxels: null coordinates or origin" );
 	REQUIRE( n >= 1 && n < 0xFFFFFFFFull, "mvrt_svo_build_voxels: voxel count %llu is not in [1, 2^32-2]", (unsigned long long)n );
-	REQUIRE( ilog2Exact( gridRes ) > 0 && gridRes <= ( 1 << 21 ), "mvrt_svo_build_voxels: gridRes %d is not a power of two in [2, 2^21]", gridRes );
+	REQUIRE( levelsOf( gridRes ) > 0 && gridRes <= ( 1 << 21 ), "mvrt_svo_build_voxels: gridRes %d is not a power of two in [2, 2^21]", gridRes );
 	REQUIRE( ( flags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0,
 			 "mvrt_svo_build_voxels: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", flags );
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
 	SvoBuildResult r;
-	memset( &r, 0, sizeof( r ) );
 	if( svoBuildFromVoxels( xyzDev, attribsDev, n, gridRes, flags, st, &r ) ) return 1;
-	svo->cleanUp();
 	return adoptBuild( svo, r, origin, dps, gridRes, flags );
 }
 MVRT_EXPORT int mvrt_svo_edit_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t* attribsDev, const uint8_t* opsDev, uint64_t n, void* stream )
 {
 	REQUIRE( svo, "mvrt_svo_edit_voxels: null handle" );
-	REQUIRE( svo->nodes, "mvrt_svo_edit_voxels: no octree (build first)" );
-	REQUIRE( svo->morton, "mvrt_svo_edit_voxels: an uploaded octree keeps no Morton codes; only octrees built by this library can be edited" );
+	REQUIRE( !svo->empty(), "mvrt_svo_edit_voxels: no octree (build first)" );
+	REQUIRE( svo->oct.morton.p, "mvrt_svo_edit_voxels: an uploaded octree keeps no Morton codes; only octrees built by this library can be edited" );
 	REQUIRE( xyzDev, "mvrt_svo_edit_voxels: null coordinates" );
 	REQUIRE( n >= 1 && n < 0xFFFFFFFFull, "mvrt_svo_edit_voxels: entry count %llu is not in [1, 2^32-2]", (unsigned long long)n );
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene; an attribute-only edit writes in place
+	mvrt_svo_info& info = svo->oct.info;
 	SvoBuildResult r;
-	memset( &r, 0, sizeof( r ) );
 	int structural = 0;
 	uint32_t he = 0;
-	if( svoEditVoxels( svo->morton, svo->attrs, svo->info.numberOfVoxels, xyzDev, attribsDev, opsDev, n, (int)svo->info.gridRes, svo->buildFlags, st, &r, &structural, &he ) )
+	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), info.numberOfVoxels, xyzDev, attribsDev, opsDev, n, (int)info.gridRes, svo->oct.buildFlags, st, &r,
+					   &structural, &he ) )
 		return 1;
-	svo->info.totalDumpedVoxels = 0;
 	if( !structural )
 	{
-		svo->info.hasEmission = he;
+		info.totalDumpedVoxels = 0;
+		info.hasEmission = he;
 		return 0;
 	}
-	const float origin[3] = { svo->info.lower[0], svo->info.lower[1], svo->info.lower[2] };
-	const float dps = svo->info.dps;
-	const int gridRes = (int)svo->info.gridRes, flags = svo->buildFlags;
-	svo->cleanUp(); // keeps the emission scale
-	return adoptBuild( svo, r, origin, dps, gridRes, flags );
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	return adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, svo->oct.buildFlags ); // (arguments are read before the old octree goes)
 }
 MVRT_EXPORT int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attribsDev, void* stream )
 {
 	REQUIRE( svo, "mvrt_svo_read_voxels: null handle" );
-	REQUIRE( svo->nodes, "mvrt_svo_read_voxels: no octree (build first)" );
-	REQUIRE( svo->morton, "mvrt_svo_read_voxels: an uploaded octree keeps no Morton codes" );
-	return svoReadVoxels( svo->morton, svo->attrs, svo->info.numberOfVoxels, xyzDev, attribsDev, (hipStream_t)stream );
+	REQUIRE( !svo->empty(), "mvrt_svo_read_voxels: no octree (build first)" );
+	REQUIRE( svo->oct.morton.p, "mvrt_svo_read_voxels: an uploaded octree keeps no Morton codes" );
+	return svoReadVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.info.numberOfVoxels, xyzDev, attribsDev, (hipStream_t)stream );
 }
 
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );
-	*info = svo->info;
-	info->flavour = svo->tree ? MVRT_FLAVOUR_TREE : ( svo->info.embeddedMask ? MVRT_FLAVOUR_EMBEDDED : MVRT_FLAVOUR_PLAIN );
+	*info = svo->oct.info;
+	info->emissionScale = svo->emissionScale;
+	info->flavour = svo->oct.tree ? MVRT_FLAVOUR_TREE : ( info->embeddedMask ? MVRT_FLAVOUR_EMBEDDED : MVRT_FLAVOUR_PLAIN );
 	info->reserved = 0;
 	return 0;
 }
 MVRT_EXPORT uint64_t mvrt_svo_traversal_bytes( const mvrt_svo* svo )
 {
-	if( !svo || !svo->nodes ) return 0;
-	const uint64_t n = svo->info.numberOfNodes;
-	if( svo->tree ) return (uint64_t)svo->nBricks * sizeof( uint4 ) + n * 5;
-	return n * sizeof( Node64 ) + n + ( svo->psumCold ? n * 32 : 0 ) + svo->topTable.bytes + svo->kids.bytes + svo->cellBlocks.bytes + svo->cellEntries.bytes;
+	if( !svo || svo->empty() ) return 0;
+	const Octree& o = svo->oct;
+	const uint64_t n = o.info.numberOfNodes;
+	if( o.tree ) return (uint64_t)o.nBricks * sizeof( uint4 ) + n * 5;
+	return n * sizeof( Node64 ) + n + ( o.psumCold.p ? n * 32 : 0 ) + o.topTable.bytes + o.kids.bytes + o.cellBlocks.bytes + o.cellEntries.bytes;
 }
-MVRT_EXPORT const void* mvrt_svo_node_buffer_dev( const mvrt_svo* svo ) { return svo ? svo->nodes : nullptr; }
-MVRT_EXPORT const void* mvrt_svo_attribute_buffer_dev( const mvrt_svo* svo ) { return svo ? svo->attrs : nullptr; }
+MVRT_EXPORT const void* mvrt_svo_node_buffer_dev( const mvrt_svo* svo ) { return svo ? svo->oct.nodes.p : nullptr; }
+MVRT_EXPORT const void* mvrt_svo_attribute_buffer_dev( const mvrt_svo* svo ) { return svo ? svo->oct.attrs.p : nullptr; }
 MVRT_EXPORT int mvrt_svo_device_view( const mvrt_svo* svo, mvrt_device_octree* out )
 {
 	REQUIRE( svo && out, "mvrt_svo_device_view: null argument" );
-	REQUIRE( svo->nodes, "mvrt_svo_device_view: no octree (build or upload first)" );
-	REQUIRE( !svo->tree, "mvrt_svo_device_view: tree-flavour octrees (MVRT_FLAVOUR_TREE) are not supported by the device API" );
-	REQUIRE( svo->info.levels <= MVRT_DEVICE_MAX_LEVELS, "mvrt_svo_device_view: %u levels, the device API supports at most %d", svo->info.levels,
+	REQUIRE( !svo->empty(), "mvrt_svo_device_view: no octree (build or upload first)" );
+	REQUIRE( !svo->oct.tree, "mvrt_svo_device_view: tree-flavour octrees (MVRT_FLAVOUR_TREE) are not supported by the device API" );
+	REQUIRE( svo->oct.info.levels <= MVRT_DEVICE_MAX_LEVELS, "mvrt_svo_device_view: %u levels, the device API supports at most %d", svo->oct.info.levels,
 			 MVRT_DEVICE_MAX_LEVELS );
 	const SvoDev d = svo->dev();
 	mvrt_device_octree v;
@@ -639,32 +590,32 @@ MVRT_EXPORT int mvrt_svo_set_emission_scale( mvrt_svo* svo, float scale )
 {
 	REQUIRE( svo, "null argument" );
 	if( ownerFlush( svo ) ) return 1; // pending steps are launched with the scale they were issued under
-	svo->info.emissionScale = scale;
+	svo->emissionScale = scale;
 	return 0;
 }
 MVRT_EXPORT int mvrt_svo_download( const mvrt_svo* svo, void* nodes68Host, void* attribs8Host, uint64_t* mortonHost, void* stream )
 {
-	REQUIRE( svo && svo->nodes, "no octree" );
+	REQUIRE( svo && !svo->empty(), "no octree" );
+	const Octree& o = svo->oct;
+	const uint32_t nNodes = o.info.numberOfNodes, nVoxels = o.info.numberOfVoxels;
 	hipStream_t st = (hipStream_t)stream;
 	if( nodes68Host )
 	{
 		DevBuf raw;
-		if( raw.alloc( (uint64_t)svo->info.numberOfNodes * 68 ) ) return 1;
-		if( svo->tree )
+		if( raw.alloc( (uint64_t)nNodes * 68 ) ) return 1;
+		if( o.tree )
 		{
-			if( launchTreeTo68( svo->masks, svo->treeFirst, svo->treeLevelBase, svo->treeLevelCount, (int)svo->info.levels, svo->info.numberOfNodes, svo->info.numberOfVoxels,
-								raw.as<uint8_t>(), st ) )
-				return 1;
+			if( launchTreeTo68( o.masks.as<uint8_t>(), o.treeFirst.as<uint32_t>(), o.treeLevelBase, o.treeLevelCount, (int)o.info.levels, nNodes, nVoxels, raw.as<uint8_t>(), st ) ) return 1;
 		}
-		else if( launchNodesTo68( svo->nodes, svo->masks, svo->psumCold, svo->info.numberOfNodes, raw.as<uint8_t>(), svo->info.embeddedMask ? 0 : 1, st ) ) return 1;
+		else if( launchNodesTo68( o.nodes.as<Node64>(), o.masks.as<uint8_t>(), o.psumCold.as<uint32_t>(), nNodes, raw.as<uint8_t>(), o.info.embeddedMask ? 0 : 1, st ) ) return 1;
 		MVRT_HIP( hipMemcpyAsync( nodes68Host, raw.p, raw.bytes, hipMemcpyDeviceToHost, st ) );
 		MVRT_HIP( hipStreamSynchronize( st ) );
 	}
-	if( attribs8Host ) MVRT_HIP( hipMemcpyAsync( attribs8Host, svo->attrs, (uint64_t)svo->info.numberOfVoxels * 8, hipMemcpyDeviceToHost, st ) );
+	if( attribs8Host ) MVRT_HIP( hipMemcpyAsync( attribs8Host, o.attrs.p, (uint64_t)nVoxels * 8, hipMemcpyDeviceToHost, st ) );
 	if( mortonHost )
 	{
-		REQUIRE( svo->morton, "morton codes are only kept by mvrt_svo_build" );
-		MVRT_HIP( hipMemcpyAsync( mortonHost, svo->morton, (uint64_t)svo->info.numberOfVoxels * 8, hipMemcpyDeviceToHost, st ) );
+		REQUIRE( o.morton.p, "morton codes are only kept by mvrt_svo_build" );
+		MVRT_HIP( hipMemcpyAsync( mortonHost, o.morton.p, (uint64_t)nVoxels * 8, hipMemcpyDeviceToHost, st ) );
 	}
 	MVRT_HIP( hipStreamSynchronize( st ) );
 	return 0;
@@ -673,27 +624,27 @@ MVRT_EXPORT int mvrt_svo_download( const mvrt_svo* svo, void* nodes68Host, void*
 MVRT_EXPORT int mvrt_trace_batch( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
 								  const float* rdzDev, const uint8_t* isShadowDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev, uint32_t* descentsDev, void* stream )
 {
-	REQUIRE( svo && svo->nodes, "mvrt_trace_batch: no octree (build or upload first)" );
+	REQUIRE( svo && !svo->empty(), "mvrt_trace_batch: no octree (build or upload first)" );
 	REQUIRE( tDev, "mvrt_trace_batch: t output is required" );
 	if( svo->ensureWorkspace( vIndexDev ? n : 0 ) ) return 1;
-	return launchTraceBatch( svo->dev(), svo->ws, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream );
+	return launchTraceBatch( svo->dev(), svo->work.ws, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream );
 }
 
 MVRT_EXPORT int mvrt_trace_batch_hinted( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
 										 const float* rdzDev, const uint8_t* isShadowDev, const uint64_t* originVoxelMortonDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev,
 										 uint32_t* descentsDev, void* stream )
 {
-	REQUIRE( svo && svo->nodes, "mvrt_trace_batch_hinted: no octree (build or upload first)" );
+	REQUIRE( svo && !svo->empty(), "mvrt_trace_batch_hinted: no octree (build or upload first)" );
 	REQUIRE( tDev, "mvrt_trace_batch_hinted: t output is required" );
 	if( svo->ensureWorkspace( vIndexDev ? n : 0 ) ) return 1;
-	return launchTraceBatch( svo->dev(), svo->ws, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream,
+	return launchTraceBatch( svo->dev(), svo->work.ws, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream,
 							 originVoxelMortonDev );
 }
 
 MVRT_EXPORT int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const float* roHost, const float* rdHost, const uint8_t* isShadowHost, float* tHost,
 									   int32_t* nMajorHost, uint32_t* vIndexHost, uint32_t* descentsHost )
 {
-	REQUIRE( svo && svo->nodes, "mvrt_trace_batch_host: no octree" );
+	REQUIRE( svo && !svo->empty(), "mvrt_trace_batch_host: no octree" );
 	if( n == 0 ) return 0;
 	std::vector<float> soa( n * 6 );
 	for( uint64_t i = 0; i < n; i++ )
@@ -712,7 +663,7 @@ MVRT_EXPORT int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const fl
 	}
 	const float* b = in.as<float>();
 	if( svo->ensureWorkspace( n ) ) return 1;
-	if( launchTraceBatch( svo->dev(), svo->ws, n, b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, isShadowHost ? sh.as<uint8_t>() : nullptr, t.as<float>(), nm.as<int32_t>(),
+	if( launchTraceBatch( svo->dev(), svo->work.ws, n, b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, isShadowHost ? sh.as<uint8_t>() : nullptr, t.as<float>(), nm.as<int32_t>(),
 						  vi.as<uint32_t>(), de.as<uint32_t>(), 0 ) )
 		return 1;
 	MVRT_HIP( hipDeviceSynchronize() );
@@ -733,11 +684,11 @@ static CameraPinhole cameraFrom15( const float c[15] )
 MVRT_EXPORT int mvrt_render_primary( const mvrt_svo* svo, const float camera[15], int width, int height, int showVertexColor, uint8_t* rgbaDev, float* tDev,
 									 int32_t* nMajorDev, uint32_t* vIndexDev, uint32_t* descentsDev, void* stream )
 {
-	REQUIRE( svo && svo->nodes, "mvrt_render_primary: no octree" );
+	REQUIRE( svo && !svo->empty(), "mvrt_render_primary: no octree" );
 	REQUIRE( width > 0 && height > 0, "bad resolution %dx%d", width, height );
 	if( svo->ensureWorkspace( ( vIndexDev || showVertexColor ) ? (uint64_t)width * height : 0 ) ) return 1;
-	if( !tDev && ( vIndexDev || showVertexColor ) ) tDev = (float*)( svo->ws.paths + svo->ws.pathCap ); // the resolve pass needs t
-	return launchRenderPrimary( svo->dev(), svo->ws, cameraFrom15( camera ), width, height, showVertexColor, (uchar4*)rgbaDev, tDev, nMajorDev, vIndexDev, descentsDev,
+	if( !tDev && ( vIndexDev || showVertexColor ) ) tDev = (float*)( svo->work.ws.paths + svo->work.ws.pathCap ); // the resolve pass needs t
+	return launchRenderPrimary( svo->dev(), svo->work.ws, cameraFrom15( camera ), width, height, showVertexColor, (uchar4*)rgbaDev, tDev, nMajorDev, vIndexDev, descentsDev,
 								(hipStream_t)stream );
 }
 
@@ -971,9 +922,12 @@ struct mvrt_pt
 {
 	mvrt_svo* intersector = nullptr; // m_intersectorOctreeGPU
 	DevBuf pmj;						 // m_pmj
-	// m_hdri
-	DevBuf hdriPixels, hdriPrimary, hdriSat[7];
-	HdriDev hdri;
+	struct Hdri // m_hdri: what the kernels take by value and the buffers behind it.  Replaced as a whole by a successful load
+	{
+		DevBuf pixels, primary, sat[7];
+		HdriDev dev = {};
+	};
+	Hdri hdri;
 	// frame buffers
 	DevBuf fbF32, fbU8; // m_frameBufferF32 / m_frameBufferU8
 	// first-hit feature buffers (mvrt_pt_set_aovs; off by default): float4 per owned pixel like fbF32, allocated and cleared with it
@@ -987,10 +941,10 @@ struct mvrt_pt
 	// the frame-buffer additions stay in step order through an event chain.  depth 1 = everything on the caller's stream.
 	struct Slot
 	{
-		DevBuf work, wsBuf, dbg;
+		DevBuf work, dbg;
 		DevBuf aovPart; // feature buffers on: the pass's partial sums, 2 x float4 per (step, pixel) (AovBuffers::partA / partN)
 		PtBuffers buf;
-		TraceWorkspace ws = { nullptr, 0, nullptr, nullptr, 0, nullptr };
+		Workspace trace;
 		hipStream_t stream = nullptr;
 		hipEvent_t accumDone = nullptr;
 	};
@@ -1018,8 +972,7 @@ struct mvrt_pt
 	int numCUs = 0;
 	mvrt_pt()
 	{
-		memset( &hdri, 0, sizeof( hdri ) );
-		hdri.scale = 1.75f; // renderCommon.hpp:480
+		hdri.dev.scale = 1.75f; // renderCommon.hpp:480
 		for( Slot& sl : slots ) memset( &sl.buf, 0, sizeof( sl.buf ) );
 		depth = (int)mvrtKnob( "MVRT_PIPELINE_DEPTH", depth );
 		if( depth < 1 ) depth = 1;
@@ -1213,12 +1166,11 @@ static int allocWorkSlot( mvrt_pt* pt, mvrt_pt::Slot& sl )
 	return 0;
 }
 static int allocWorkInner( mvrt_pt* pt );
-// (Re)allocates the path state of every pipeline slot.  On ANY failure nothing stale is left behind: every slot's buffer table is zeroed (cap = 0, so
-// launchPass refuses to run) and the frame is forgotten (width = height = 0, frame buffer released), so that the next
-// resizeFrameBufferIfNeeded -- same size or not -- allocates again instead of returning early onto freed memory.
-static int allocWork( mvrt_pt* pt )
+// What every failed (re)allocation of a frame ends in, so that nothing stale is left behind: every slot's buffer table is zeroed (cap = 0, so launchPass
+// refuses to run) and the frame is forgotten (width = height = 0, frame buffers released), so that the next resizeFrameBufferIfNeeded -- same size or
+// not -- allocates again instead of returning early onto freed memory.  Returns 1, the status of the call that failed.
+static int forgetFrame( mvrt_pt* pt )
 {
-	if( allocWorkInner( pt ) == 0 ) return 0;
 	for( mvrt_pt::Slot& sl : pt->slots )
 	{
 		sl.work.release();
@@ -1230,6 +1182,8 @@ static int allocWork( mvrt_pt* pt )
 	pt->releaseAovs();
 	return 1;
 }
+// (Re)allocates the path state of every pipeline slot
+static int allocWork( mvrt_pt* pt ) { return allocWorkInner( pt ) == 0 ? 0 : forgetFrame( pt ); }
 static int allocWorkInner( mvrt_pt* pt )
 {
 	if( pt->drain() ) return 1;
@@ -1273,8 +1227,7 @@ static int allocWorkInner( mvrt_pt* pt )
 		{
 			sl.work.release();
 			sl.aovPart.release();
-			sl.wsBuf.release();
-			sl.ws = TraceWorkspace{ nullptr, 0, nullptr, nullptr, 0, nullptr };
+			sl.trace = Workspace();
 			memset( &sl.buf, 0, sizeof( sl.buf ) );
 			continue;
 		}
@@ -1294,23 +1247,6 @@ static int allocWorkInner( mvrt_pt* pt )
 	pt->lastAccum = nullptr;
 	return 0;
 }
-static int ensureSlotWorkspace( mvrt_pt* pt, mvrt_pt::Slot& sl )
-{
-	const uint64_t lanes = traceWorkspaceLanes();
-	const uint64_t rows = 2 * (uint64_t)( pt->intersector->info.levels ? pt->intersector->info.levels : 1 ) + 2;
-	const uint64_t bytes = 256 + rows * lanes * ( sizeof( uint4 ) + 2 * sizeof( uint32_t ) );
-	if( sl.wsBuf.bytes < bytes )
-	{
-		if( sl.wsBuf.alloc( bytes ) ) return 1;
-	}
-	sl.ws.cursor = (unsigned long long*)sl.wsBuf.p;
-	sl.ws.spill = (uint4*)( (uint8_t*)sl.wsBuf.p + 256 );
-	sl.ws.spillStride = lanes;
-	sl.ws.spillMask = (uint32_t*)( sl.ws.spill + rows * lanes );
-	sl.ws.spillMask2 = sl.ws.spillMask + rows * lanes;
-	return 0;
-}
-
 MVRT_EXPORT int mvrt_pt_clear_framebuffer( mvrt_pt* pt, void* stream )
 {
 	REQUIRE( pt && pt->fbF32.p, "no frame buffer" );
@@ -1344,16 +1280,8 @@ MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream,
 	pt->validOwnedPixels = valid;
 	pt->width = width;
 	pt->height = height;
-	if( pt->fbF32.alloc( pt->ownedPixels * sizeof( float4 ) ) ) return 1;
-	if( pt->fbU8.alloc( pt->ownedPixels * sizeof( uchar4 ) ) ) return 1;
-	if( pt->aovs && pt->allocAovFrame() ) // no frame without its feature buffers: forget it like allocWork does
-	{
-		pt->width = pt->height = 0;
-		pt->fbF32.release();
-		pt->fbU8.release();
-		pt->releaseAovs();
-		return 1;
-	}
+	// (no frame without all of its buffers)
+	if( pt->fbF32.alloc( pt->ownedPixels * sizeof( float4 ) ) || pt->fbU8.alloc( pt->ownedPixels * sizeof( uchar4 ) ) || ( pt->aovs && pt->allocAovFrame() ) ) return forgetFrame( pt );
 	if( allocWork( pt ) ) return 1;
 	return mvrt_pt_clear_framebuffer( pt, stream ); // :88
 }
@@ -1365,40 +1293,35 @@ MVRT_EXPORT int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaH
 	if( pt->drain() ) return 1;
 	hipStream_t st = (hipStream_t)stream;
 	const uint64_t n = (uint64_t)width * height;
-	if( pt->hdriPixels.alloc( n * 16 ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( pt->hdriPixels.p, rgbaHost, n * 16, hipMemcpyHostToDevice, st ) );
+	mvrt_pt::Hdri h; // built aside: a failure leaves the map that is loaded (or none) in place
+	if( h.pixels.alloc( n * 16 ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( h.pixels.p, rgbaHost, n * 16, hipMemcpyHostToDevice, st ) );
 	DevBuf satF64;
 	if( satF64.alloc( n * 8 ) ) return 1;
 	// renderCommon.hpp:243-311: uniform table, then one cosine-weighted table per axis
 	const f3 axes[6] = { mk3( 1, 0, 0 ), mk3( -1, 0, 0 ), mk3( 0, 1, 0 ), mk3( 0, -1, 0 ), mk3( 0, 0, 1 ), mk3( 0, 0, -1 ) };
 	for( int i = 0; i < 7; i++ )
 	{
-		if( pt->hdriSat[i].alloc( n * 4 ) ) return 1;
-		if( launchHdriSat( pt->hdriPixels.as<float4>(), width, height, satF64.as<double>(), pt->hdriSat[i].as<uint32_t>(), i > 0, i > 0 ? axes[i - 1] : mk3( 0, 0, 0 ), st ) )
-			return 1;
+		if( h.sat[i].alloc( n * 4 ) ) return 1;
+		if( launchHdriSat( h.pixels.as<float4>(), width, height, satF64.as<double>(), h.sat[i].as<uint32_t>(), i > 0, i > 0 ? axes[i - 1] : mk3( 0, 0, 0 ), st ) ) return 1;
 	}
-	pt->hdri.pixels = pt->hdriPixels.as<float4>();
-	pt->hdri.sat = pt->hdriSat[0].as<uint32_t>();
-	for( int i = 0; i < 6; i++ ) pt->hdri.sats[i] = pt->hdriSat[i + 1].as<uint32_t>();
-	pt->hdri.width = width;
-	pt->hdri.height = height;
+	h.dev.pixels = h.pixels.as<float4>();
+	h.dev.sat = h.sat[0].as<uint32_t>();
+	for( int i = 0; i < 6; i++ ) h.dev.sats[i] = h.sat[i + 1].as<uint32_t>();
+	h.dev.width = h.dev.widthPrimary = width; // no primary map: see mvrt.h, the reference would index with 0x0 here
+	h.dev.height = h.dev.heightPrimary = height;
 	if( rgbaPrimaryHost ) // HDRI::loadPrimary, :315-326
 	{
 		const uint64_t np = (uint64_t)widthPrimary * heightPrimary;
-		if( pt->hdriPrimary.alloc( np * 16 ) ) return 1;
-		MVRT_HIP( hipMemcpyAsync( pt->hdriPrimary.p, rgbaPrimaryHost, np * 16, hipMemcpyHostToDevice, st ) );
-		pt->hdri.pixelsPrimary = pt->hdriPrimary.as<float4>();
-		pt->hdri.widthPrimary = widthPrimary;
-		pt->hdri.heightPrimary = heightPrimary;
+		if( h.primary.alloc( np * 16 ) ) return 1;
+		MVRT_HIP( hipMemcpyAsync( h.primary.p, rgbaPrimaryHost, np * 16, hipMemcpyHostToDevice, st ) );
+		h.dev.pixelsPrimary = h.primary.as<float4>();
+		h.dev.widthPrimary = widthPrimary;
+		h.dev.heightPrimary = heightPrimary;
 	}
-	else
-	{
-		pt->hdriPrimary.release();
-		pt->hdri.pixelsPrimary = nullptr;
-		pt->hdri.widthPrimary = width; // see mvrt.h: the reference would index with 0x0 here
-		pt->hdri.heightPrimary = height;
-	}
-	MVRT_HIP( hipStreamSynchronize( st ) ); // :313
+	MVRT_HIP( hipStreamSynchronize( st ) ); // :313 (and satF64 is released on return)
+	h.dev.scale = pt->hdri.dev.scale;
+	pt->hdri = std::move( h );
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_load_hdri_file( mvrt_pt* pt, void* stream, const char* file, const char* filePrimary )
@@ -1422,15 +1345,15 @@ MVRT_EXPORT int mvrt_rgbe_read_file( const char* file, float* rgbaHost, uint64_t
 }
 MVRT_EXPORT int mvrt_pt_download_hdri_sat( mvrt_pt* pt, int which, uint32_t* satHost )
 {
-	REQUIRE( pt && which >= 0 && which < 7 && pt->hdriSat[which].p, "no such HDRI table" );
-	MVRT_HIP( hipMemcpy( satHost, pt->hdriSat[which].p, pt->hdriSat[which].bytes, hipMemcpyDeviceToHost ) );
+	REQUIRE( pt && which >= 0 && which < 7 && pt->hdri.sat[which].p, "no such HDRI table" );
+	MVRT_HIP( hipMemcpy( satHost, pt->hdri.sat[which].p, pt->hdri.sat[which].bytes, hipMemcpyDeviceToHost ) );
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_set_hdri_scale( mvrt_pt* pt, float scale )
 {
 	REQUIRE( pt, "null argument" );
 	if( pt->flush() ) return 1; // pending steps are launched with the scale they were issued under (HDRI is a by-value kernel argument)
-	pt->hdri.scale = scale;
+	pt->hdri.dev.scale = scale;
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_update_scene( mvrt_pt* pt, const float* verticesHost, const float* vcolorsHost, const float* vemissionsHost, uint64_t nVertices, void* stream,
@@ -1445,9 +1368,9 @@ MVRT_EXPORT mvrt_svo* mvrt_pt_intersector( mvrt_pt* pt ) { return pt ? pt->inter
 MVRT_EXPORT int mvrt_pt_step( mvrt_pt* pt, void* stream, const float camera[15] )
 {
 	REQUIRE( pt && pt->setupDone, "mvrt_pt_step: call mvrt_pt_setup first" );
-	REQUIRE( pt->intersector->nodes, "mvrt_pt_step: no scene (updateScene / upload first)" );
+	REQUIRE( !pt->intersector->empty(), "mvrt_pt_step: no scene (updateScene / upload first)" );
 	REQUIRE( pt->fbF32.p, "mvrt_pt_step: no frame buffer (resizeFrameBufferIfNeeded first)" );
-	REQUIRE( !( 0.0f < pt->hdri.scale ) || pt->hdri.pixels, "mvrt_pt_step: HDRI enabled (scale > 0) but none loaded" );
+	REQUIRE( !( 0.0f < pt->hdri.dev.scale ) || pt->hdri.dev.pixels, "mvrt_pt_step: HDRI enabled (scale > 0) but none loaded" );
 	PtFrame f;
 	f.width = pt->width;
 	f.height = pt->height;
@@ -1529,7 +1452,7 @@ int mvrt_pt::launchPass( const CameraPinhole* passCams, int iteration, int nStep
 	pt->lastSlot = pt->nextSlot;
 	pt->nextSlot = ( pt->nextSlot + 1 ) % pt->depth;
 	REQUIRE( sl.buf.cap >= pt->validOwnedPixels * MVRT_SPP_PER_STEP * f.nSteps, "internal: work buffers not allocated" );
-	if( ensureSlotWorkspace( pt, sl ) ) return 1;
+	if( sl.trace.ensure( pt->intersector->oct.info.levels, 0 ) ) return 1;
 	sl.buf.dbgTasks = nullptr;
 	if( pt->debugCapture )
 	{
@@ -1554,7 +1477,7 @@ int mvrt_pt::launchPass( const CameraPinhole* passCams, int iteration, int nStep
 		aov.albedo = pt->aovAlbedo.as<float4>();
 		aov.normalDepth = pt->aovNormalDepth.as<float4>();
 	}
-	int rc = launchPtStep( pt->intersector->dev(), sl.ws, pt->hdri, pt->pmj.as<float2>(), cams, f, sl.buf, pt->fbF32.as<float4>(), pt->numCUs,
+	int rc = launchPtStep( pt->intersector->dev(), sl.trace.ws, pt->hdri.dev, pt->pmj.as<float2>(), cams, f, sl.buf, pt->fbF32.as<float4>(), pt->numCUs,
 						   pt->profiling ? &pt->prof : nullptr, run, after, pt->aovs ? &aov : nullptr );
 	if( rc ) return rc;
 	MVRT_HIP( hipEventRecord( sl.accumDone, run ) );
@@ -1581,8 +1504,8 @@ MVRT_EXPORT int mvrt_pt_to_image_async( mvrt_pt* pt, void* stream, uint8_t* rgba
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_get_steps( const mvrt_pt* pt ) { return pt ? pt->steps : 0; }
-MVRT_EXPORT uint64_t mvrt_pt_get_number_of_voxels( const mvrt_pt* pt ) { return pt ? pt->intersector->info.numberOfVoxels : 0; }
-MVRT_EXPORT uint64_t mvrt_pt_get_octree_bytes( const mvrt_pt* pt ) { return pt ? (uint64_t)pt->intersector->info.numberOfNodes * 68 : 0; }
+MVRT_EXPORT uint64_t mvrt_pt_get_number_of_voxels( const mvrt_pt* pt ) { return pt ? pt->intersector->oct.info.numberOfVoxels : 0; }
+MVRT_EXPORT uint64_t mvrt_pt_get_octree_bytes( const mvrt_pt* pt ) { return pt ? (uint64_t)pt->intersector->oct.info.numberOfNodes * 68 : 0; }
 MVRT_EXPORT int mvrt_pt_read_framebuffer( mvrt_pt* pt, void* stream, float* rgbaHost )
 {
 	REQUIRE( pt && pt->fbF32.p, "no frame buffer" );

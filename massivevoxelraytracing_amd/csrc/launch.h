@@ -1,5 +1,6 @@
 // launch.h -- host-side launch wrappers implemented in the .hip translation units.
 #pragma once
+#include "devbuf.h"
 #include "mvrt_common.h"
 
 // ---- wavefront path-tracer work buffers (all device pointers, capacity `cap` paths) ---------------
@@ -113,21 +114,27 @@ int launchFillCellIndex( const uint64_t* morton, uint64_t n, uint32_t cellBits, 
 int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t* satOut, int cosWeighted, f3 axis, hipStream_t stream );
 
 // GPU SVO construction (svo_build.hip)
-struct SvoBuildResult
+struct SvoBuildResult // owns its arrays: a builder that fails hands nothing over and leaks nothing
 {
-	Node64* nodes;
-	uint8_t* masks;
-	uint32_t* psumCold; // non-embedded flavour only
-	uint2* attrs;
-	uint64_t* morton; // kept for parity checks (sorted unique codes)
-	uint32_t nNodes, nVoxels, hasEmission, embedded;
-	uint64_t totalDumped;
+	DevBuf nodes, masks;
+	DevBuf psumCold; // non-embedded flavour only
+	DevBuf attrs;
+	DevBuf morton; // kept for parity checks (sorted unique codes)
+	uint32_t nNodes = 0, nVoxels = 0, hasEmission = 0, embedded = 0;
+	uint64_t totalDumped = 0;
 	// "tree" flavour (no DAG, masks not embedded): `nodes` holds nBricks two-level bricks, `masks` the per-node masks and `treeFirst` the
 	// per-node first-child index (reference numbering); node ranges per builder level (0 = parents of voxels)
-	uint32_t tree, nBricks, treeRoot;
-	uint32_t* treeFirst;
-	uint32_t treeLevelBase[24], treeLevelCount[24];
+	uint32_t tree = 0, nBricks = 0, treeRoot = 0;
+	DevBuf treeFirst;
+	uint32_t treeLevelBase[24] = { 0 }, treeLevelCount[24] = { 0 };
 };
+static inline int levelsOf( int gridRes ) // log2 of a power of two, -1 for anything else (zero, negative, not a power of two): every int terminates
+{
+	if( gridRes <= 0 || ( gridRes & ( gridRes - 1 ) ) != 0 ) return -1;
+	int l = 0;
+	while( ( gridRes >> l ) != 1 ) l++;
+	return l;
+}
 // flags: 1 = no DAG de-duplication (every sibling group is a node), 2 = never embed masks in child pointers
 int svoBuildFromTriangles( const float* vertsHost, const float* colsHost, const float* emisHost, uint64_t nVertices, f3 origin, float dps, int gridRes, int flags,
 						   hipStream_t stream, SvoBuildResult* out );

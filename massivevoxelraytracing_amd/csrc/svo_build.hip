@@ -16,6 +16,7 @@
 // All fp32 arithmetic of the voxelizer is contraction-free and matches the oracle bit for bit.
 #include <hipcub/hipcub.hpp>
 
+#include <utility>
 #include <vector>
 
 #include "launch.h"
@@ -25,30 +26,6 @@
 
 namespace
 {
-struct Buf
-{
-	void* p = nullptr;
-	int alloc( uint64_t bytes )
-	{
-		release();
-		MVRT_HIP( hipMalloc( &p, bytes ? bytes : 1 ) );
-		return 0;
-	}
-	void release()
-	{
-		if( p ) (void)hipFree( p );
-		p = nullptr;
-	}
-	void* detach()
-	{
-		void* r = p;
-		p = nullptr;
-		return r;
-	}
-	~Buf() { release(); }
-	template <class T> T* as() const { return (T*)p; }
-};
-
 // ---------------------------------------------------------------------------------------------------
 // voxelizer (voxelization.hpp:124-337), six-separating only -- the GPU reference hard-codes it
 // (voxKernel.cu:68,109)
@@ -1128,19 +1105,29 @@ int gridFor( uint64_t n )
 	if( b < 1 ) b = 1;
 	return (int)( b > 4096 ? 4096 : b );
 }
+
+// hipcub's two calls: ask for the size of the temporary storage, allocate it, run.  Waits for the stream, since the storage is released on return
+template <class Call> int withCubTemp( hipStream_t st, Call call )
+{
+	size_t tmpBytes = 0;
+	MVRT_HIP( call( nullptr, tmpBytes ) );
+	DevBuf tmp;
+	if( tmp.alloc( tmpBytes ) ) return 1;
+	MVRT_HIP( call( tmp.p, tmpBytes ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	return 0;
+}
 } // namespace
 
-static int buildFromFragments( Buf& keysA, Buf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,
+static int buildFromFragments( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,
 							   uint32_t* scalarOut, SvoBuildResult* out );
 
 int svoBuildFromTriangles( const float* vertsHost, const float* colsHost, const float* emisHost, uint64_t nVertices, f3 origin, float dps, int gridRes, int flags, hipStream_t st,
 						   SvoBuildResult* out )
 {
 	const uint32_t nTri = (uint32_t)( nVertices / 3 );
-	int levels = 0;
-	while( ( 1 << levels ) < gridRes ) levels++;
 
-	Buf dVerts, dCols, dEmis, dCounter;
+	DevBuf dVerts, dCols, dEmis, dCounter;
 	if( dVerts.alloc( nVertices * 12 ) || dCounter.alloc( 64 ) ) return 1;
 	MVRT_HIP( hipMemcpyAsync( dVerts.p, vertsHost, nVertices * 12, hipMemcpyHostToDevice, st ) );
 	if( colsHost )
@@ -1175,7 +1162,7 @@ int svoBuildFromTriangles( const float* vertsHost, const float* colsHost, const 
 		mvrtSetError( "mvrt_svo_build: %llu voxel fragments exceed the 32-bit index range of this builder", totalDumped );
 		return 1;
 	}
-	Buf keysA, valsA;
+	DevBuf keysA, valsA;
 	if( keysA.alloc( totalDumped * 8 ) || valsA.alloc( totalDumped * 8 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( counter, 0, 8, st ) );
 	hipLaunchKernelGGL( kVoxelize<true>, dim3( triGrid ), dim3( 128 ), 0, st, dVerts.as<float>(), dCols.as<float>(), dEmis.as<float>(), nTri, counter, origin, dps, gridRes,
@@ -1194,7 +1181,7 @@ int svoBuildSynthetic( uint64_t nRandomVoxels, uint64_t seed, int gridRes, int f
 		mvrtSetError( "mvrt_svo_build_synthetic: voxel count must be in [1, 2^32-2]" );
 		return 1;
 	}
-	Buf dCounter, keysA, valsA;
+	DevBuf dCounter, keysA, valsA;
 	if( dCounter.alloc( 64 ) || keysA.alloc( nRandomVoxels * 8 ) || valsA.alloc( nRandomVoxels * 8 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( dCounter.p, 0, 64, st ) );
 	unsigned long long* counter = dCounter.as<unsigned long long>();
@@ -1202,46 +1189,40 @@ int svoBuildSynthetic( uint64_t nRandomVoxels, uint64_t seed, int gridRes, int f
 	return buildFromFragments( keysA, valsA, nRandomVoxels, gridRes, flags, st, counter, (uint32_t*)( counter + 1 ), (uint32_t*)( counter + 2 ), out );
 }
 
-static int sortUnique( Buf& keysA, Buf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, Buf& morton, Buf& attrs,
+static int sortUnique( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, DevBuf& morton, DevBuf& attrs,
 					   uint32_t* nVoxelsOut );
-static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
+static int buildLevels( DevBuf& morton, DevBuf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
 						uint32_t* scalarOut, SvoBuildResult* out );
 
 // everything after voxelization: sort + unique of the (Morton, attribute) fragments, then the levels
-static int buildFromFragments( Buf& keysA, Buf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,
+static int buildFromFragments( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,
 							   uint32_t* scalarOut, SvoBuildResult* out )
 {
 	(void)counter;
-	int levels = 0;
-	while( ( 1 << levels ) < gridRes ) levels++;
-	Buf morton, attrs;
+	const int levels = levelsOf( gridRes );
+	DevBuf morton, attrs;
 	uint32_t nVoxels = 0;
 	if( sortUnique( keysA, valsA, totalDumped, levels, st, hasEmission, scalarOut, morton, attrs, &nVoxels ) ) return 1;
 	return buildLevels( morton, attrs, nVoxels, totalDumped, gridRes, flags, st, hasEmission, scalarOut, out );
 }
 
 // (keysA, valsA): totalDumped unsorted fragments (released here) -> morton / attrs: the sorted unique codes and their integer-mean attributes; *hasEmission |= any emission
-static int sortUnique( Buf& keysA, Buf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, Buf& morton, Buf& attrs,
+static int sortUnique( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, DevBuf& morton, DevBuf& attrs,
 					   uint32_t* nVoxelsOut )
 {
-	Buf keysB, valsB;
+	DevBuf keysB, valsB;
 	if( keysB.alloc( totalDumped * 8 ) || valsB.alloc( totalDumped * 8 ) ) return 1;
 	// ---- sort (IntersectorOctreeGPU.hpp:117-124) ----
-	{
-		size_t tmpBytes = 0;
-		MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint64_t>(), valsB.as<uint64_t>(),
-													  (uint64_t)totalDumped, 0, 3 * levels, st ) );
-		Buf tmp;
-		if( tmp.alloc( tmpBytes ) ) return 1;
-		MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( tmp.p, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint64_t>(), valsB.as<uint64_t>(),
-													  (uint64_t)totalDumped, 0, 3 * levels, st ) );
-		MVRT_HIP( hipStreamSynchronize( st ) );
-	}
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+			return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint64_t>(), valsB.as<uint64_t>(), (uint64_t)totalDumped, 0,
+													   3 * levels, st );
+		} ) )
+		return 1;
 	keysA.release();
 	valsA.release();
 
 	// ---- unique with integer-mean attributes (IntersectorOctreeGPU.hpp:126-137) ----
-	Buf blockCnt;
+	DevBuf blockCnt;
 	if( blockCnt.alloc( ( totalDumped / BB + 2 ) * 4 ) ) return 1;
 	hipLaunchKernelGGL( kUniqueCount, dim3( gridFor( totalDumped ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), (uint64_t)totalDumped, blockCnt.as<uint32_t>() );
 	hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt.as<uint32_t>(), (uint64_t)totalDumped, scalarOut );
@@ -1257,31 +1238,25 @@ static int sortUnique( Buf& keysA, Buf& valsA, unsigned long long totalDumped, i
 }
 
 // the levels of the octree over nVoxels sorted unique codes (morton / attrs are handed to *out on success); hasEmission: the device flag of the voxel set
-static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
+static int buildLevels( DevBuf& morton, DevBuf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
 						uint32_t* scalarOut, SvoBuildResult* out )
 {
-	int levels = 0;
-	while( ( 1 << levels ) < gridRes ) levels++;
+	const int levels = levelsOf( gridRes );
 	const bool dag = !( flags & 1 );
-	Buf blockCnt;
+	DevBuf blockCnt;
 	if( blockCnt.alloc( ( (uint64_t)nVoxels / BB + 2 ) * 4 ) ) return 1;
 
 	// ---- upper bound on nodes: distinct parents per level (octreeTaskInit's taskCounters, voxKernel.cu:257-265) ----
 	// counted on the host from the per-level group counts as the levels are built; the node buffer grows by level.
-	Buf tasksA, tasksB;
+	DevBuf tasksA, tasksB;
 	if( tasksA.alloc( (uint64_t)nVoxels * sizeof( Task ) ) || tasksB.alloc( (uint64_t)nVoxels * sizeof( Task ) ) ) return 1;
 	hipLaunchKernelGGL( kInitTasks, dim3( gridFor( nVoxels ) ), dim3( BB ), 0, st, morton.as<uint64_t>(), nVoxels, tasksA.as<Task>() );
 
-	std::vector<Node64*> levelNodes; // per-level node arrays, concatenated at the end
-	std::vector<uint8_t*> levelMasks;
+	std::vector<DevBuf> levelNodes, levelMasks; // per-level arrays, concatenated at the end (no DAG: one of each, already final)
 	std::vector<uint32_t> levelCount;
 	bool tree = false; // no DAG + no embedded masks: compact { mask, first child } nodes + two-level bricks instead of 64-byte lines per node
-	Buf treeFirst, bricks;
+	DevBuf treeFirst, bricks;
 	uint32_t treeLevelBase[24] = { 0 }, treeLevelCount[24] = { 0 }, treeBrickBase[24] = { 0 }, nBricks = 0;
-	auto freeLevels = [&]() {
-		for( Node64* p : levelNodes ) (void)hipFree( p );
-		for( uint8_t* p : levelMasks ) (void)hipFree( p );
-	};
 
 	uint32_t nInput = nVoxels;
 	uint32_t nodeBase = 0;
@@ -1301,7 +1276,7 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 			if( level == 0 )
 			{
 				// distinct parents per level in one pass -> exact node count -> one allocation, no concatenation copy
-				Buf dCounts;
+				DevBuf dCounts;
 				if( dCounts.alloc( 32 * 8 ) ) return 1;
 				MVRT_HIP( hipMemsetAsync( dCounts.p, 0, 32 * 8, st ) );
 				hipLaunchKernelGGL( kLevelCounts, dim3( gridFor( nVoxels ) ), dim3( BB ), 0, st, morton.as<uint64_t>(), (uint64_t)nVoxels, levels, dCounts.as<unsigned long long>() );
@@ -1316,9 +1291,9 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 					return 1;
 				}
 				tree = total >= 0xFFFFFFull || ( flags & 2 );
-				uint8_t* mm = nullptr;
-				MVRT_HIP( hipMalloc( (void**)&mm, total ) );
-				levelMasks.push_back( mm );
+				levelNodes.emplace_back();
+				levelMasks.emplace_back();
+				if( levelMasks[0].alloc( total ) ) return 1;
 				levelCount.push_back( (uint32_t)total );
 				if( tree )
 				{
@@ -1334,25 +1309,19 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 					}
 					nBricks = (uint32_t)nBr;
 					if( treeFirst.alloc( total * 4 ) || bricks.alloc( ( nBr ? nBr : 1 ) * sizeof( uint4 ) ) ) return 1;
-					levelNodes.push_back( nullptr );
 				}
-				else
-				{
-					Node64* nn = nullptr;
-					MVRT_HIP( hipMalloc( (void**)&nn, total * sizeof( Node64 ) ) );
-					levelNodes.push_back( nn );
-				}
+				else if( levelNodes[0].alloc( total * sizeof( Node64 ) ) ) return 1;
 			}
 			if( tree )
 			{
-				hipLaunchKernelGGL( kMakeNodesTree, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, level == 0 ? 1 : 0, levelMasks[0],
+				hipLaunchKernelGGL( kMakeNodesTree, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, level == 0 ? 1 : 0, levelMasks[0].as<uint8_t>(),
 									treeFirst.as<uint32_t>(), nxt );
 				if( level & 1 )
-					hipLaunchKernelGGL( kMakeBricks, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, levelMasks[0], treeFirst.as<uint32_t>(), treeLevelBase[level], nGroups, level - 1 == 0 ? 1 : 0,
+					hipLaunchKernelGGL( kMakeBricks, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, levelMasks[0].as<uint8_t>(), treeFirst.as<uint32_t>(), treeLevelBase[level], nGroups, level - 1 == 0 ? 1 : 0,
 										level >= 2 ? treeLevelBase[level - 2] : 0u, level >= 2 ? treeBrickBase[level - 2] : 0u, bricks.as<uint4>() + treeBrickBase[level] );
 			}
 			else
-				hipLaunchKernelGGL( kMakeNodesDirect, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, levelNodes[0], levelMasks[0], nxt );
+				hipLaunchKernelGGL( kMakeNodesDirect, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, levelNodes[0].as<Node64>(), levelMasks[0].as<uint8_t>(), nxt );
 			MVRT_HIP( hipStreamSynchronize( st ) );
 			nodeBase += nGroups;
 			nInput = nGroups;
@@ -1361,15 +1330,12 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 			nxt = t;
 			continue;
 		}
-		Buf cands, hashes, groupIds, parents, hashesS, groupS, headPos, headScan, repOf, nodeOfGroup, blockCnt2;
+		DevBuf cands, hashes, groupIds, parents, hashesS, groupS, headPos, headScan, repOf, nodeOfGroup, blockCnt2;
 		if( cands.alloc( (uint64_t)nGroups * sizeof( Cand ) ) || hashes.alloc( (uint64_t)nGroups * 8 ) || groupIds.alloc( (uint64_t)nGroups * 4 ) ||
 			parents.alloc( (uint64_t)nGroups * 8 ) || hashesS.alloc( (uint64_t)nGroups * 8 ) || groupS.alloc( (uint64_t)nGroups * 4 ) ||
 			headPos.alloc( (uint64_t)nGroups * 4 ) || headScan.alloc( (uint64_t)nGroups * 4 ) || repOf.alloc( (uint64_t)nGroups * 4 ) ||
 			nodeOfGroup.alloc( (uint64_t)nGroups * 4 ) || blockCnt2.alloc( ( (uint64_t)nGroups / BB + 2 ) * 4 ) )
-		{
-			freeLevels();
 			return 1;
-		}
 		hipLaunchKernelGGL( kMakeCandidates, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), cands.as<Cand>(),
 							hashes.as<uint64_t>(), groupIds.as<uint32_t>(), parents.as<uint64_t>() );
 
@@ -1379,12 +1345,8 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 			MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, tmpBytes, hashes.as<uint64_t>(), hashesS.as<uint64_t>(), groupIds.as<uint32_t>(), groupS.as<uint32_t>(),
 														  nGroups, 0, 64, st ) );
 			MVRT_HIP( hipcub::DeviceScan::InclusiveScan( nullptr, tmpBytes2, headPos.as<uint32_t>(), headScan.as<uint32_t>(), MaxOp(), nGroups, st ) );
-			Buf tmp;
-			if( tmp.alloc( tmpBytes > tmpBytes2 ? tmpBytes : tmpBytes2 ) )
-			{
-				freeLevels();
-				return 1;
-			}
+			DevBuf tmp;
+			if( tmp.alloc( tmpBytes > tmpBytes2 ? tmpBytes : tmpBytes2 ) ) return 1;
 			MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( tmp.p, tmpBytes, hashes.as<uint64_t>(), hashesS.as<uint64_t>(), groupIds.as<uint32_t>(), groupS.as<uint32_t>(),
 														  nGroups, 0, 64, st ) );
 			hipLaunchKernelGGL( kMarkRuns, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, hashesS.as<uint64_t>(), groupS.as<uint32_t>(), cands.as<Cand>(), nGroups,
@@ -1399,16 +1361,13 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 		uint32_t nUnique = 0;
 		MVRT_HIP( hipMemcpyAsync( &nUnique, scalarOut, 4, hipMemcpyDeviceToHost, st ) );
 		MVRT_HIP( hipStreamSynchronize( st ) );
-		Node64* lvNodes = nullptr;
-		uint8_t* lvMasks = nullptr;
-		MVRT_HIP( hipMalloc( (void**)&lvNodes, (uint64_t)nUnique * sizeof( Node64 ) ) );
-		MVRT_HIP( hipMalloc( (void**)&lvMasks, nUnique ) );
-		levelNodes.push_back( lvNodes );
-		levelMasks.push_back( lvMasks );
+		levelNodes.emplace_back();
+		levelMasks.emplace_back();
+		if( levelNodes.back().alloc( (uint64_t)nUnique * sizeof( Node64 ) ) || levelMasks.back().alloc( nUnique ) ) return 1;
 		levelCount.push_back( nUnique );
 		// kEmitNodes writes to nodes[nodeBase + rank]: pass pointers rebased so that index nodeBase lands on lvNodes[0]
 		hipLaunchKernelGGL( kEmitNodes, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, repOf.as<uint32_t>(), cands.as<Cand>(), (uint64_t)nGroups, blockCnt2.as<uint32_t>(),
-							nodeBase, lvNodes - nodeBase, lvMasks - nodeBase, nodeOfGroup.as<uint32_t>() );
+							nodeBase, levelNodes.back().as<Node64>() - nodeBase, levelMasks.back().as<uint8_t>() - nodeBase, nodeOfGroup.as<uint32_t>() );
 		hipLaunchKernelGGL( kNextTasks, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, repOf.as<uint32_t>(), nodeOfGroup.as<uint32_t>(), cands.as<Cand>(),
 							parents.as<uint64_t>(), nGroups, nxt );
 		MVRT_HIP( hipStreamSynchronize( st ) );
@@ -1420,35 +1379,29 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 	}
 	if( nInput != 1 )
 	{
-		freeLevels();
 		mvrtSetError( "mvrt_svo_build: internal error, %u roots after %d levels", nInput, levels );
 		return 1;
 	}
 	const uint32_t nNodes = nodeBase;
-	Buf nodes, masks;
+	DevBuf nodes, masks;
 	if( !dag )
 	{
-		nodes.p = levelNodes[0]; // written in place, already final
-		masks.p = levelMasks[0];
-		levelNodes.clear();
-		levelMasks.clear();
+		nodes = std::move( levelNodes[0] ); // written in place, already final
+		masks = std::move( levelMasks[0] );
 	}
-	else if( nodes.alloc( (uint64_t)nNodes * sizeof( Node64 ) ) || masks.alloc( nNodes ) )
+	else
 	{
-		freeLevels();
-		return 1;
-	}
-	if( dag )
-	{
+		if( nodes.alloc( (uint64_t)nNodes * sizeof( Node64 ) ) || masks.alloc( nNodes ) ) return 1;
 		uint64_t off = 0;
 		for( size_t l = 0; l < levelNodes.size(); l++ )
 		{
-			MVRT_HIP( hipMemcpyAsync( nodes.as<Node64>() + off, levelNodes[l], (uint64_t)levelCount[l] * sizeof( Node64 ), hipMemcpyDeviceToDevice, st ) );
-			MVRT_HIP( hipMemcpyAsync( masks.as<uint8_t>() + off, levelMasks[l], levelCount[l], hipMemcpyDeviceToDevice, st ) );
+			MVRT_HIP( hipMemcpyAsync( nodes.as<Node64>() + off, levelNodes[l].p, (uint64_t)levelCount[l] * sizeof( Node64 ), hipMemcpyDeviceToDevice, st ) );
+			MVRT_HIP( hipMemcpyAsync( masks.as<uint8_t>() + off, levelMasks[l].p, levelCount[l], hipMemcpyDeviceToDevice, st ) );
 			off += levelCount[l];
 		}
 		MVRT_HIP( hipStreamSynchronize( st ) );
-		freeLevels();
+		levelNodes.clear();
+		levelMasks.clear();
 	}
 	if( tree ) // nothing left to convert: the traversal reads the bricks, download rebuilds the reference's nodes from { mask, first child }
 	{
@@ -1456,10 +1409,9 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 		MVRT_HIP( hipMemcpyAsync( &he, hasEmission, 4, hipMemcpyDeviceToHost, st ) );
 		MVRT_HIP( hipStreamSynchronize( st ) );
 		MVRT_HIP( hipGetLastError() );
-		out->nodes = (Node64*)bricks.detach();
-		out->masks = (uint8_t*)masks.detach();
-		out->psumCold = nullptr;
-		out->treeFirst = (uint32_t*)treeFirst.detach();
+		out->nodes = std::move( bricks );
+		out->masks = std::move( masks );
+		out->treeFirst = std::move( treeFirst );
 		out->tree = 1;
 		out->nBricks = nBricks;
 		for( int l = 0; l < 24; l++ )
@@ -1472,8 +1424,8 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 		// octree, voxel 0)
 		const int rl = levels - 1;
 		out->treeRoot = ( rl & 1 ) ? treeBrickBase[rl] : ( rl == 0 ? 0u : treeBrickBase[rl - 1] );
-		out->attrs = (uint2*)attrs.detach();
-		out->morton = (uint64_t*)morton.detach();
+		out->attrs = std::move( attrs );
+		out->morton = std::move( morton );
 		out->nNodes = nNodes;
 		out->nVoxels = nVoxels;
 		out->hasEmission = he;
@@ -1486,7 +1438,7 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 	{
 		hipLaunchKernelGGL( kEmbedMasks, dim3( divUp( (uint64_t)nNodes * 8, BB ) ), dim3( BB ), 0, st, nodes.as<Node64>(), masks.as<uint8_t>(), nNodes );
 	}
-	Buf psumCold;
+	DevBuf psumCold;
 	if( !embed ) // non-embedded flavour: nVoxelsPSum -> cold array, child masks -> the hot line (traverse_stream.h)
 	{
 		if( psumCold.alloc( (uint64_t)nNodes * 32 ) ) return 1;
@@ -1497,11 +1449,11 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 	MVRT_HIP( hipStreamSynchronize( st ) );
 	MVRT_HIP( hipGetLastError() );
 
-	out->nodes = (Node64*)nodes.detach();
-	out->masks = (uint8_t*)masks.detach();
-	out->psumCold = (uint32_t*)psumCold.detach();
-	out->attrs = (uint2*)attrs.detach();
-	out->morton = (uint64_t*)morton.detach();
+	out->nodes = std::move( nodes );
+	out->masks = std::move( masks );
+	out->psumCold = std::move( psumCold );
+	out->attrs = std::move( attrs );
+	out->morton = std::move( morton );
 	out->nNodes = nNodes;
 	out->nVoxels = nVoxels;
 	out->hasEmission = he;
@@ -1514,7 +1466,7 @@ static int buildLevels( Buf& morton, Buf& attrs, uint32_t nVoxels, unsigned long
 // scratch of the voxel-list calls: [0] unused, [8] hasEmission, [16] scalarOut (as buildFromFragments), [32] firstBad[2], [48] edit counts[3]
 struct ListScratch
 {
-	Buf b;
+	DevBuf b;
 	unsigned long long* base() const { return b.as<unsigned long long>(); }
 	uint32_t* hasEmission() const { return (uint32_t*)( base() + 1 ); }
 	uint32_t* scalarOut() const { return (uint32_t*)( base() + 2 ); }
@@ -1559,7 +1511,7 @@ static int encodeVoxels( const char* who, const uint32_t* xyz, const uint32_t* a
 int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n, int gridRes, int flags, hipStream_t st, SvoBuildResult* out )
 {
 	ListScratch sc;
-	Buf keysA, valsA;
+	DevBuf keysA, valsA;
 	if( sc.init( st ) || keysA.alloc( n * 8 ) || valsA.alloc( n * 8 ) ) return 1;
 	if( encodeVoxels( "mvrt_svo_build_voxels", xyz, attribs, nullptr, n, gridRes, st, sc, keysA.as<uint64_t>(), valsA.as<uint64_t>(), nullptr ) ) return 1;
 	return buildFromFragments( keysA, valsA, n, gridRes, flags, st, sc.base(), sc.hasEmission(), sc.scalarOut(), out );
@@ -1569,32 +1521,27 @@ int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, co
 				   hipStream_t st, SvoBuildResult* out, int* structural, uint32_t* hasEmissionOut )
 {
 	static const char* who = "mvrt_svo_edit_voxels";
-	int levels = 0;
-	while( ( 1 << levels ) < gridRes ) levels++;
+	const int levels = levelsOf( gridRes );
 	ListScratch sc;
-	Buf keysA, attrN, idxA, keysB, idxB;
+	DevBuf keysA, attrN, idxA, keysB, idxB;
 	if( sc.init( st ) || keysA.alloc( n * 8 ) || attrN.alloc( n * 8 ) || idxA.alloc( n * 4 ) || keysB.alloc( n * 8 ) || idxB.alloc( n * 4 ) ) return 1;
 	if( encodeVoxels( who, xyz, attribs, ops, n, gridRes, st, sc, keysA.as<uint64_t>(), attrN.as<uint64_t>(), idxA.as<uint32_t>() ) ) return 1;
 	// stable sort of (Morton, batch index): within a key the batch order survives, its last entry wins
-	{
-		size_t tmpBytes = 0;
-		MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), idxA.as<uint32_t>(), idxB.as<uint32_t>(), n, 0, 3 * levels, st ) );
-		Buf tmp;
-		if( tmp.alloc( tmpBytes ) ) return 1;
-		MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( tmp.p, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), idxA.as<uint32_t>(), idxB.as<uint32_t>(), n, 0, 3 * levels, st ) );
-		MVRT_HIP( hipStreamSynchronize( st ) );
-	}
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+			return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), idxA.as<uint32_t>(), idxB.as<uint32_t>(), n, 0, 3 * levels, st );
+		} ) )
+		return 1;
 	keysA.release();
 	idxA.release();
 	// last entry per key -> the sorted unique edit list, classified against the old list
-	Buf blockCnt;
+	DevBuf blockCnt;
 	if( blockCnt.alloc( ( n / BB + 2 ) * 4 ) ) return 1;
 	hipLaunchKernelGGL( kEditTailCount, dim3( gridFor( n ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), n, blockCnt.as<uint32_t>() );
 	hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt.as<uint32_t>(), n, sc.scalarOut() );
 	uint32_t nE = 0;
 	MVRT_HIP( hipMemcpyAsync( &nE, sc.scalarOut(), 4, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) );
-	Buf eKeys, eAttr, ePos, eKind, eInc, ePre;
+	DevBuf eKeys, eAttr, ePos, eKind, eInc, ePre;
 	if( eKeys.alloc( (uint64_t)nE * 8 ) || eAttr.alloc( (uint64_t)nE * 8 ) || ePos.alloc( (uint64_t)nE * 4 ) || eKind.alloc( nE ) || eInc.alloc( ( (uint64_t)nE + 1 ) * 8 ) ||
 		ePre.alloc( ( (uint64_t)nE + 1 ) * 8 ) )
 		return 1;
@@ -1631,15 +1578,11 @@ int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, co
 		return 1;
 	}
 	const uint32_t nNew = nOld + nIns - nRem;
-	{
-		size_t tmpBytes = 0;
-		MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( nullptr, tmpBytes, eInc.as<unsigned long long>(), ePre.as<unsigned long long>(), nE + 1, st ) );
-		Buf tmp;
-		if( tmp.alloc( tmpBytes ) ) return 1;
-		MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( tmp.p, tmpBytes, eInc.as<unsigned long long>(), ePre.as<unsigned long long>(), nE + 1, st ) );
-		MVRT_HIP( hipStreamSynchronize( st ) );
-	}
-	Buf morton, attrs;
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+			return hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, eInc.as<unsigned long long>(), ePre.as<unsigned long long>(), nE + 1, st );
+		} ) )
+		return 1;
+	DevBuf morton, attrs;
 	if( morton.alloc( (uint64_t)nNew * 8 ) || attrs.alloc( (uint64_t)nNew * 8 ) ) return 1;
 	hipLaunchKernelGGL( kMergeOld, dim3( gridFor( ( (uint64_t)nOld + MERGE_PER - 1 ) / MERGE_PER ) ), dim3( BB ), 0, st, oldMorton, (const uint2*)oldAttrs, nOld, eKeys.as<uint64_t>(),
 						eAttr.as<uint64_t>(), eKind.as<uint8_t>(), ePre.as<unsigned long long>(), nE, morton.as<uint64_t>(), attrs.as<uint2>(), sc.hasEmission() );
