@@ -7,11 +7,13 @@
 // The Alembic scene / camera animation of the reference (prlib, absent) is replaced by a Wavefront .obj mesh and an
 // orbiting look-at camera.  Everything GPU-side goes through include/mvrt/PathTracer.hpp -> libmvrt_hip.so.
 //
-//   rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov]
+//   rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov] [--denoise]
 //
 // --aov also writes, beside each frame, <frame>_albedo and <frame>_normal in the frame's format: the means over all samples of the first-hit
 // feature buffers (mvrt.h "First-hit feature buffers"), what a denoiser takes as guides.  Encoded on the host from read-back data, in fp32:
 // albedo byte = (int)( 255 * ( sum / samples ) + 0.5f ), normal byte = (int)( 255 * ( 0.5f * ( sum / samples ) + 0.5f ) + 0.5f ), alpha 255.
+// --denoise switches the feature buffers and the luminance moments on and also writes <frame>_denoised in the frame's format: mvrt_pt_denoise with the
+// default parameters on the accumulated frame, tone-mapped by mvrt_resolve_buffer like the frame itself (mvrt.h "Denoiser").
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -87,7 +89,9 @@ int main( int argc, char** argv )
 {
 	if( argc < 4 )
 	{
-		std::printf( "usage: rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov]\n" );
+		std::printf( "usage: rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov] [--denoise]\n"
+					 "  --aov      also write <frame>_albedo and <frame>_normal (first-hit feature buffers)\n"
+					 "  --denoise  also write <frame>_denoised (a-trous denoiser on the feature buffers and the luminance moments)\n" );
 		std::printf( "  [instance 0] rtcamp_batch ... --frame-range 0 171\n  [instance 1] rtcamp_batch ... --frame-range 171 240\n" );
 		return 0;
 	}
@@ -95,7 +99,7 @@ int main( int argc, char** argv )
 	const char* hdrPath = argv[2];
 	const std::string outDir = argv[3];
 	int totalFrames = 240, beginFrame = 0, endFrame = -1, W = 1440, H = 900, fromRes = 256, toRes = 8192, steps = 8; // RTCamp.cpp:42-45,136-137,156
-	bool png = false, dumpCameras = false, aov = false;
+	bool png = false, dumpCameras = false, aov = false, denoise = false;
 	for( int i = 4; i < argc; i++ )
 	{
 		if( !std::strcmp( argv[i], "--dump-cameras" ) ) dumpCameras = true;
@@ -106,6 +110,7 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--steps" ) && i + 1 < argc ) steps = std::atoi( argv[++i] );
 		else if( !std::strcmp( argv[i], "--png" ) ) png = true;
 		else if( !std::strcmp( argv[i], "--aov" ) ) aov = true;
+		else if( !std::strcmp( argv[i], "--denoise" ) ) denoise = true;
 	}
 	if( endFrame < 0 ) endFrame = totalFrames;
 
@@ -131,8 +136,11 @@ int main( int argc, char** argv )
 
 	mvrt::PathTracer pt;
 	pt.setup( stream );
-	if( aov ) pt.setAOVs( true );
+	if( aov || denoise ) pt.setAOVs( true );
+	if( denoise ) pt.setMoments( true );
 	pt.resizeFrameBufferIfNeeded( stream, W, H );
+	uint8_t* denoisedU8Dev = nullptr; // the tone-mapped denoised frame on the device
+	if( denoise ) mvrt::check( mvrt_malloc( (void**)&denoisedU8Dev, (uint64_t)W * H * 4 ), "mvrt_malloc" );
 	pt.loadHDRI( stream, hdrPath, hdrPath );
 
 	// worker: image writer with a 4-buffer pool (RTCamp.cpp:126-130,174-193)
@@ -223,9 +231,19 @@ int main( int argc, char** argv )
 			mvrt::check( mvrt_pt_read_aov( pt.handle(), stream, MVRT_AOV_NORMAL_DEPTH, sum.data() ), "read_aov" );
 			normalImage = encodeAov( sum, fb, (size_t)W * H, true );
 		}
+		uint8_t* denoisedImage = nullptr;
+		if( denoise )
+		{
+			pt.denoise( stream );
+			mvrt::check( mvrt_resolve_buffer( (const float*)pt.m_denoisedF32->data(), (uint64_t)W * H, denoisedU8Dev, stream ), "mvrt_resolve_buffer" );
+			denoisedImage = new uint8_t[(size_t)W * H * 4];
+			mvrt::check( mvrt_memcpy_d2h( denoisedImage, denoisedU8Dev, (uint64_t)W * H * 4, stream ), "mvrt_memcpy_d2h" );
+			mvrt::check( mvrt_stream_synchronize( stream ), "sync" );
+		}
 		{
 			std::lock_guard<std::mutex> lk( mu );
 			jobs.push_back( Job{ frame, buf, "" } );
+			if( denoise ) jobs.push_back( Job{ frame, denoisedImage, "_denoised" } );
 			if( aov )
 			{
 				jobs.push_back( Job{ frame, albedoImage, "_albedo" } );
@@ -243,6 +261,7 @@ int main( int argc, char** argv )
 	writer.join();
 	for( uint8_t* p : pool ) delete[] p;
 	pt.cleanUp();
+	if( denoisedU8Dev ) mvrt_free( denoisedU8Dev );
 	mvrt_stream_destroy( stream );
 	std::printf( "done\n" );
 	return 0;

@@ -338,6 +338,81 @@ float* mvrt_pt_aov_dev( mvrt_pt* pt, int which );
 /* host copy; waits for the steps in flight like mvrt_pt_read_framebuffer */
 int mvrt_pt_read_aov( mvrt_pt* pt, void* stream, int which, float* rgbaHost /* ownedPixels*4 */ );
 
+/* Luminance moments, the per-pixel variance a denoiser needs (new; the reference has none).  One more accumulation buffer with the frame buffer's layout,
+ * padding and stride, cleared and reallocated with it: float4 per OWNED pixel, x = sum of l, y = sum of l * l over all samples, z = w = 0 (reserved), with
+ *   l = ( 0.2126f * r + 0.7152f * g ) + 0.0722f * b
+ * of the sample's radiance, the very value the frame buffer sums.  Order, fp32 without contraction: per pixel and step s1 = sum of l and s2 = sum of l * l
+ * (the product rounded, then added) over the 16 samples in ascending order from +0; then x += s1, y += s2, steps in issue order.  Batching, pipelining,
+ * sibling passes, tiles and origin hints change no bit.  mvrt_pt_assemble_tiles, mvrt_memcpy_d2d and an all-gather apply as to the frame buffer.
+ * The sample variance of the pixel mean's luminance is max( y / n - ( x / n )^2, 0 ) / max( n - 1, 1 ) with n = frameBuffer.w.
+ * Independent of mvrt_pt_set_aovs and under the same rules: the call waits for the steps in flight, fails with the handle unchanged while get_steps != 0,
+ * may come before or after resize_framebuffer_if_needed, and leaves NO frame when the path state no longer fits.  Off by default: with it off every launch,
+ * allocation and output is that of a library without it.  On: 16 bytes per pixel, one small kernel per pass behind the frame-buffer addition. */
+int mvrt_pt_set_moments( mvrt_pt* pt, int enable ); /* new; the reference has none */
+/* new; the reference has none.  NULL (and mvrt_last_error) when off or without a frame; callers reading it on their own stream call mvrt_pt_join before */
+float* mvrt_pt_moments_dev( mvrt_pt* pt );
+/* new; the reference has none.  Host copy; waits for the steps in flight like mvrt_pt_read_framebuffer */
+int mvrt_pt_read_moments( mvrt_pt* pt, void* stream, float* rgbaHost /* ownedPixels*4 */ );
+
+/* Denoiser (new; the reference has none): an edge-avoiding a-trous wavelet filter on the demodulated mean radiance, guided by the first-hit feature
+ * buffers and by the per-pixel variance of the moments.  Inputs are FULL-FRAME buffers, pixel = y * width + x, float4 each: the frame buffer (color), the two
+ * feature buffers and the moments -- of a handle with tileCount == 1 as they are, of tile shares after mvrt_pt_assemble_tiles.  Inputs are not modified.
+ * Output: float4 per pixel, xyz = denoised mean radiance, w = 1, so that mvrt_resolve_buffer( out, width * height, u8 ) tone-maps it.
+ *
+ * THE FILTER.  All arithmetic is fp32 in exactly this order, without contraction; exp is mvrt_exp (mvrt_detmath.h); division and sqrt are IEEE;
+ * lum( x ) = ( 0.2126f * x.r + 0.7152f * x.g ) + 0.0722f * x.b; max( a, b ) = a < b ? b : a.
+ * Prepare, per pixel, with n = color.w and h = albedo.w:
+ *   n == 0: out = (0,0,0,0); the pixel is never filtered and never a tap.
+ *   c = color.xyz / n
+ *   h == 0 (sky): out = ( c, 1 ) exactly; the pixel is never filtered and never a tap.
+ *   A_k = max( ( albedo_k + ( n - h ) ) / n, albedoFloor )  per channel (misses count as albedo 1); with MVRT_DENOISE_NO_DEMODULATION A = (1,1,1)
+ *   u = c / A;  N = normalDepth.xyz / n;  Z = normalDepth.w / h;  f = h / n
+ *   m1 = moments.x / n;  m2 = moments.y / n;  var = max( m2 - m1 * m1, 0 ) / max( n - 1, 1 );  lA = lum( A );  v = var / ( lA * lA )
+ * Iteration i = 0 .. iterations - 1, stride s = 2^i, for every pixel p = (x, y) with n > 0 and h > 0, reading the { u, v } the previous iteration wrote:
+ *   lp = lum( u_p );  sv = sigmaLuminance * sqrt( v_p ) + 1e-6f;  acc = (0,0,0), accv = 0, ws = 0
+ *   taps dy = -2 .. 2 (outer loop), dx = -2 .. 2 (inner loop), q = ( x + dx * s, y + dy * s ); a tap is skipped when q lies outside the frame or n_q == 0 or h_q == 0:
+ *     d = N_p - N_q;  e = ( ( d.x * d.x + d.y * d.y ) + d.z * d.z ) / ( sigmaNormal * sigmaNormal )
+ *     dz = ( Z_p - Z_q ) / ( sigmaDepth * max( max( Z_p, Z_q ), 1e-20f ) );  e = e + dz * dz
+ *     df = ( f_p - f_q ) / sigmaCoverage;  e = e + df * df
+ *     e = e + |lp - lum( u_q )| / sv
+ *     w = ( k[dy] * k[dx] ) * mvrt_exp( -e )   with k = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f }
+ *     acc_k = acc_k + w * u_q,k;  accv = accv + ( w * w ) * v_q;  ws = ws + w
+ *   u'_p = acc / ws;  v'_p = accv / ( ws * ws )     (the centre tap is always present: ws > 0)
+ * Finish: out.xyz = u * A with the u of the last iteration, out.w = 1.  The variance is not pre-blurred. */
+#define MVRT_DENOISE_NO_DEMODULATION 1u
+typedef struct mvrt_denoise_params
+{
+	uint32_t structBytes;	/* sizeof( mvrt_denoise_params ) */
+	int32_t iterations;		/* 1..8, default 5 */
+	float sigmaNormal;		/* 0.5  */
+	float sigmaDepth;		/* 0.05 */
+	float sigmaCoverage;	/* 0.25 */
+	float sigmaLuminance;	/* 2.0  */
+	float albedoFloor;		/* 0.01 */
+	uint32_t flags;			/* MVRT_DENOISE_NO_DEMODULATION */
+	uint32_t reserved[2];	/* 0 */
+} mvrt_denoise_params;
+/* new; the reference has none.  Fills *p with the defaults above (structBytes included) */
+int mvrt_denoise_default_params( mvrt_denoise_params* p );
+/* new; the reference has none.  Bytes of scratch mvrt_denoise_buffers needs for a frame (0 and mvrt_last_error for a bad size); no GPU call */
+uint64_t mvrt_denoise_scratch_bytes( int width, int height );
+/* new; the reference has none.  The filter on full-frame device buffers, asynchronous on `stream`; params NULL = the defaults.  outDev: width * height float4; it and
+ * scratchDev must not overlap the inputs.  Every rejected argument (structBytes, iterations outside 1..8, a sigma or the floor not greater than 0, width or
+ * height not greater than 0, scratch too small, a null pointer) fails on the host before any GPU call. */
+int mvrt_denoise_buffers( const float* colorDev, const float* albedoDev, const float* normalDepthDev, const float* momentsDev, int width, int height,
+						  const mvrt_denoise_params* params, float* outDev, void* scratchDev, uint64_t scratchBytes, void* stream );
+/* new; the reference has none.  The same on a handle with tileCount == 1, feature buffers and moments on and at least one step: like resolve it launches the pending steps
+ * and makes `stream` wait for the steps in flight; otherwise asynchronous on `stream`.  The handle owns the output and the scratch (kept between calls,
+ * released by a resize and by set_tile); an allocation that fails leaves the frame, the accumulated steps and the feature buffers intact and NO denoised
+ * buffer.  The frame buffer, the feature buffers, the moments and get_steps are untouched: stepping afterwards continues the accumulation bit-identically.
+ * A handle with tileCount > 1 is refused (assemble the shares and call mvrt_denoise_buffers), as are feature buffers or moments off and a frame without steps. */
+int mvrt_pt_denoise( mvrt_pt* pt, void* stream, const mvrt_denoise_params* params /* NULL = defaults */ );
+/* new; the reference has none.  NULL before the first denoise, after a resize that reallocates, after set_tile and after a denoise whose allocation failed (a call
+ * refused for its arguments leaves the image of the last one); read it on the stream the denoise ran on */
+float* mvrt_pt_denoised_dev( mvrt_pt* pt );
+/* new; the reference has none.  Host copy on `stream` (the stream of the denoise), synchronous */
+int mvrt_pt_read_denoised( mvrt_pt* pt, void* stream, float* rgbaHost /* width*height*4 */ );
+
 /* Multi-GPU tile split (new; the reference has no multi-GPU path).  The frame is cut into the reference's own
  * 256-pixel blocks (RENDER_NUMBER_OF_THREAD, renderCommon.hpp:13) dealt round-robin: this handle renders blocks
  * b with b % tileCount == tileIndex.  Owned pixels are stored compactly in block order.  Call before

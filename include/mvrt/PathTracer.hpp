@@ -62,6 +62,8 @@ struct PathTracer
 		m_frameBufferF32.reset();
 		m_aovAlbedoF32.reset();
 		m_aovNormalDepthF32.reset();
+		m_momentsF32.reset();
+		m_denoisedF32.reset();
 		m_intersectorOctreeGPU.attach( nullptr );
 		if( m_handle ) mvrt_pt_destroy( m_handle );
 		m_handle = nullptr;
@@ -76,6 +78,8 @@ struct PathTracer
 		m_frameBufferU8.reset( new Buffer( mvrt_pt_framebuffer_u8_dev( m_handle ), owned * 4 ) );
 		m_frameBufferF32.reset( new Buffer( mvrt_pt_framebuffer_dev( m_handle ), owned * 16 ) );
 		pointAOVs();
+		pointMoments();
+		pointDenoised(); // (a resize releases the denoised image)
 		m_steps = mvrt_pt_get_steps( m_handle );
 	}
 	void clearFrameBuffer( void* stream ) // :98-102
@@ -109,6 +113,8 @@ struct PathTracer
 		m_frameBufferF32.reset();
 		m_aovAlbedoF32.reset();
 		m_aovNormalDepthF32.reset();
+		m_momentsF32.reset();
+		m_denoisedF32.reset();
 		check( mvrt_pt_set_tile( m_handle, tileIndex, tileCount ), "PathTracer::setTile" );
 	}
 
@@ -120,6 +126,25 @@ struct PathTracer
 		pointAOVs();
 	}
 
+	// luminance moments (not in the reference; mvrt.h "Luminance moments"): under the rules of setAOVs, independent of it
+	void setMoments( bool enable )
+	{
+		const int rc = mvrt_pt_set_moments( m_handle, enable ? 1 : 0 );
+		pointMoments(); // (a reallocation that fails leaves no frame: the views follow the library either way)
+		pointAOVs();
+		pointDenoised();
+		if( !mvrt_pt_framebuffer_dev( m_handle ) ) m_frameBufferF32.reset();
+		check( rc, "PathTracer::setMoments" );
+	}
+	// the a-trous denoiser (not in the reference; mvrt.h "Denoiser") on this handle's frame: needs setAOVs( true ), setMoments( true ), one tile and at least one
+	// step.  params == nullptr: the defaults.  m_denoisedF32 views the result (float4 per pixel, xyz = mean radiance, w = 1); null when the call failed
+	void denoise( void* stream, const mvrt_denoise_params* params = nullptr )
+	{
+		const int rc = mvrt_pt_denoise( m_handle, stream, params );
+		pointDenoised();
+		check( rc, "PathTracer::denoise" );
+	}
+
 	mvrt_pt* handle() const { return m_handle; }
 
 	IntersectorOctreeGPU m_intersectorOctreeGPU; // reference member m_intersectorOctreeGPU (:18), a value as there; bound to the handle's octree by setup()
@@ -127,6 +152,10 @@ struct PathTracer
 	std::unique_ptr<Buffer> m_frameBufferF32; // :24
 	std::unique_ptr<Buffer> m_aovAlbedoF32;		 // MVRT_AOV_ALBEDO, float4 per owned pixel; null while the feature buffers are off (setAOVs)
 	std::unique_ptr<Buffer> m_aovNormalDepthF32; // MVRT_AOV_NORMAL_DEPTH
+	std::unique_ptr<Buffer> m_momentsF32;		 // float4 per owned pixel { sum l, sum l * l, 0, 0 }; null while the moments are off (setMoments)
+	// float4 per pixel of the frame; null before the first denoise(), after resizeFrameBufferIfNeeded reallocated, after setTile and after a denoise() that
+	// failed -- it is re-pointed by every member that can make the library release or reallocate it, so it never names freed memory
+	std::unique_ptr<Buffer> m_denoisedF32;
 	int m_width = 0;
 	int m_height = 0;
 	int m_steps = 0; // :27
@@ -142,6 +171,16 @@ private:
 			m_aovAlbedoF32.reset( new Buffer( a, owned * 16 ) );
 			m_aovNormalDepthF32.reset( new Buffer( mvrt_pt_aov_dev( m_handle, MVRT_AOV_NORMAL_DEPTH ), owned * 16 ) );
 		}
+	}
+	void pointMoments()
+	{
+		m_momentsF32.reset();
+		if( float* m = mvrt_pt_moments_dev( m_handle ) ) m_momentsF32.reset( new Buffer( m, (int64_t)mvrt_pt_owned_pixels( m_handle ) * 16 ) );
+	}
+	void pointDenoised()
+	{
+		m_denoisedF32.reset();
+		if( float* d = mvrt_pt_denoised_dev( m_handle ) ) m_denoisedF32.reset( new Buffer( d, (int64_t)m_width * m_height * 16 ) );
 	}
 	mvrt_pt* m_handle = nullptr;
 };

@@ -43,6 +43,15 @@ class PtStats(C.Structure):
                 ("traceKernelMs", C.c_double), ("shadeKernelMs", C.c_double), ("totalKernelMs", C.c_double)]
 
 
+class DenoiseParams(C.Structure):
+    """mvrt_denoise_params (include/mvrt.h)"""
+    _fields_ = [("structBytes", _u32), ("iterations", C.c_int32), ("sigmaNormal", _f32), ("sigmaDepth", _f32), ("sigmaCoverage", _f32), ("sigmaLuminance", _f32),
+                ("albedoFloor", _f32), ("flags", _u32), ("reserved", _u32 * 2)]
+
+
+DENOISE_NO_DEMODULATION = 1
+
+
 # every symbol include/mvrt.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "mvrt_last_error": (C.c_char_p, []),
@@ -112,6 +121,15 @@ SIGNATURES = {
     "mvrt_pt_set_aovs": (_i32, [_vp, _i32]),
     "mvrt_pt_aov_dev": (_vp, [_vp, _i32]),
     "mvrt_pt_read_aov": (_i32, [_vp, _vp, _i32, _vp]),
+    "mvrt_pt_set_moments": (_i32, [_vp, _i32]),
+    "mvrt_pt_moments_dev": (_vp, [_vp]),
+    "mvrt_pt_read_moments": (_i32, [_vp, _vp, _vp]),
+    "mvrt_denoise_default_params": (_i32, [_vp]),
+    "mvrt_denoise_scratch_bytes": (_u64, [_i32, _i32]),
+    "mvrt_denoise_buffers": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "mvrt_pt_denoise": (_i32, [_vp, _vp, _vp]),
+    "mvrt_pt_denoised_dev": (_vp, [_vp]),
+    "mvrt_pt_read_denoised": (_i32, [_vp, _vp, _vp]),
     "mvrt_pt_set_tile": (_i32, [_vp, _i32, _i32]),
     "mvrt_pt_owned_pixels": (_u64, [_vp]),
     "mvrt_pt_assemble_tiles": (_i32, [_vp, _i32, _u64, _i32, _i32, _vp, _vp]),
@@ -604,6 +622,35 @@ class PathTracer:
         """device pointer of one feature buffer, None when they are off (join() before reading it on a stream of your own)"""
         return lib().mvrt_pt_aov_dev(self._h, int(which))
 
+    def set_moments(self, enable):
+        """mvrt_pt_set_moments: per-pixel sums of the samples' luminance and of its square beside the frame buffer (off by default); fails while steps are accumulated"""
+        _check(lib().mvrt_pt_set_moments(self._h, 1 if enable else 0))
+
+    def read_moments(self, stream=None):
+        """(owned_pixels, 4) host copy: x = sum of l, y = sum of l * l, z = w = 0"""
+        out = np.zeros((self.owned_pixels(), 4), np.float32)
+        _check(lib().mvrt_pt_read_moments(self._h, stream, _hp(out)))
+        return out
+
+    def moments_dev(self):
+        """device pointer of the moments, None when they are off (join() before reading it on a stream of your own)"""
+        return lib().mvrt_pt_moments_dev(self._h)
+
+    def denoise(self, stream=None, **params):
+        """mvrt_pt_denoise: filter the accumulated frame into the handle's denoised buffer (needs set_aovs, set_moments, one tile, >= 1 step).
+        params: fields of mvrt_denoise_params (iterations, sigmaNormal, sigmaDepth, sigmaCoverage, sigmaLuminance, albedoFloor, flags) over the defaults"""
+        _check(lib().mvrt_pt_denoise(self._h, stream, C.byref(denoise_params(**params)) if params else None))
+
+    def read_denoised(self, stream=None):
+        """(width * height, 4) host copy of the denoised buffer: xyz = mean radiance, w = 1"""
+        out = np.zeros((self.m_width * self.m_height, 4), np.float32)
+        _check(lib().mvrt_pt_read_denoised(self._h, stream, _hp(out)))
+        return out
+
+    def denoised_dev(self):
+        """device pointer of the denoised buffer; None before the first denoise and after a resize"""
+        return lib().mvrt_pt_denoised_dev(self._h)
+
     def sample_radiance(self, n_samples=None):
         """per-sample radiance of the last pass: (n, 3) host array (debug / parity)"""
         n = self.owned_pixels() * 16 if n_samples is None else n_samples
@@ -644,6 +691,41 @@ def memcpy_d2d(dst_dev, src_dev, nbytes, stream=None):
 
 def assemble_tiles(gathered_dev, tile_count, rank_stride_pixels, width, height, frame_dev, stream=None):
     _check(lib().mvrt_pt_assemble_tiles(_dev_ptr(gathered_dev), tile_count, rank_stride_pixels, width, height, _dev_ptr(frame_dev), stream))
+
+
+def denoise_params(**fields):
+    """mvrt_denoise_params: the library's defaults with `fields` set over them"""
+    p = DenoiseParams()
+    _check(lib().mvrt_denoise_default_params(C.byref(p)))
+    for k, v in fields.items():
+        if k not in dict(DenoiseParams._fields_) or k == "reserved":
+            raise TypeError("mvrt_denoise_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def denoise_scratch_bytes(width, height):
+    n = lib().mvrt_denoise_scratch_bytes(int(width), int(height))
+    if n == 0:
+        _check(1)
+    return n
+
+
+def denoise_buffers(color_dev, albedo_dev, normal_depth_dev, moments_dev, width, height, out_dev, scratch_dev=None, scratch_bytes=None, stream=None, **params):
+    """mvrt_denoise_buffers on full-frame device buffers (e.g. assembled tile shares).  scratch_dev None: a DeviceArray is allocated for the call and the
+    stream is synchronised before it is freed."""
+    own = None
+    if scratch_dev is None:
+        scratch_bytes = denoise_scratch_bytes(width, height)
+        own = scratch_dev = DeviceArray(scratch_bytes, np.uint8)
+    try:
+        _check(lib().mvrt_denoise_buffers(_dev_ptr(color_dev), _dev_ptr(albedo_dev), _dev_ptr(normal_depth_dev), _dev_ptr(moments_dev), int(width), int(height),
+                                          C.byref(denoise_params(**params)) if params else None, _dev_ptr(out_dev), _dev_ptr(scratch_dev), int(scratch_bytes), stream))
+        if own is not None:
+            _check(lib().mvrt_stream_synchronize(stream))
+    finally:
+        if own is not None:
+            own.free()
 
 
 def resolve_buffer(rgba_f32_dev, n_pixels, rgba_u8_dev, stream=None):

@@ -933,6 +933,11 @@ struct mvrt_pt
 	// first-hit feature buffers (mvrt_pt_set_aovs; off by default): float4 per owned pixel like fbF32, allocated and cleared with it
 	bool aovs = false;
 	DevBuf aovAlbedo, aovNormalDepth;
+	// luminance moments (mvrt_pt_set_moments; off by default, independent of the feature buffers): one more float4 per owned pixel, allocated and cleared with fbF32
+	bool moments = false;
+	DevBuf momentsBuf;
+	// mvrt_pt_denoise: its output (float4 per pixel of the frame) and its scratch, kept between calls; released together by a resize, set_tile and any failure
+	DevBuf denoised, denoiseScratch;
 	int width = 0, height = 0, steps = 0;
 	int tileIndex = 0, tileCount = 1;
 	uint64_t ownedPixels = 0, validOwnedPixels = 0;
@@ -992,6 +997,16 @@ struct mvrt_pt
 		aovAlbedo.release();
 		aovNormalDepth.release();
 		for( Slot& sl : slots ) sl.aovPart.release();
+	}
+	void releaseMoments() // with the frame, like releaseAovs (the flag stays); a denoised image belongs to the frame that is going away
+	{
+		momentsBuf.release();
+		releaseDenoised();
+	}
+	void releaseDenoised()
+	{
+		denoised.release();
+		denoiseScratch.release();
 	}
 	int allocAovFrame() // the two accumulation buffers, beside a frame buffer that exists
 	{
@@ -1114,6 +1129,7 @@ MVRT_EXPORT int mvrt_pt_set_tile( mvrt_pt* pt, int tileIndex, int tileCount )
 	pt->width = pt->height = 0; // force re-allocation on the next resize
 	pt->fbF32.release();
 	pt->releaseAovs();
+	pt->releaseMoments();
 	return 0;
 }
 MVRT_EXPORT uint64_t mvrt_pt_owned_pixels( const mvrt_pt* pt ) { return pt ? pt->ownedPixels : 0; }
@@ -1180,6 +1196,7 @@ static int forgetFrame( mvrt_pt* pt )
 	pt->fbF32.release();
 	pt->fbU8.release();
 	pt->releaseAovs();
+	pt->releaseMoments();
 	return 1;
 }
 // (Re)allocates the path state of every pipeline slot
@@ -1213,7 +1230,8 @@ static int allocWorkInner( mvrt_pt* pt )
 		// (feature buffers on: + 32 B of partial sums per pixel and merged step of every pass in flight, + the two accumulation buffers)
 		auto need = [&]() {
 			const uint64_t pathState = (uint64_t)pt->depth * pt->ownedPixels * MVRT_SPP_PER_STEP * (uint64_t)pt->effectiveBatch() * 200ull;
-			return pt->aovs ? pathState + (uint64_t)pt->depth * pt->ownedPixels * (uint64_t)pt->effectiveBatch() * 32ull + pt->ownedPixels * 32ull : pathState;
+			const uint64_t withAovs = pt->aovs ? pathState + (uint64_t)pt->depth * pt->ownedPixels * (uint64_t)pt->effectiveBatch() * 32ull + pt->ownedPixels * 32ull : pathState;
+			return pt->moments ? withAovs + pt->ownedPixels * 16ull : withAovs; // (moments on: + their accumulation buffer; they have no per-pass state)
 		};
 		while( need() > budget && pt->effectiveBatch() > 1 ) pt->batchCap = pt->effectiveBatch() - 1;
 		while( need() > budget && pt->depth > 1 ) pt->depth--;
@@ -1256,6 +1274,7 @@ MVRT_EXPORT int mvrt_pt_clear_framebuffer( mvrt_pt* pt, void* stream )
 	MVRT_HIP( hipMemsetAsync( pt->fbF32.p, 0, pt->fbF32.bytes, (hipStream_t)stream ) );
 	if( pt->aovAlbedo.p ) MVRT_HIP( hipMemsetAsync( pt->aovAlbedo.p, 0, pt->aovAlbedo.bytes, (hipStream_t)stream ) );
 	if( pt->aovNormalDepth.p ) MVRT_HIP( hipMemsetAsync( pt->aovNormalDepth.p, 0, pt->aovNormalDepth.bytes, (hipStream_t)stream ) );
+	if( pt->momentsBuf.p ) MVRT_HIP( hipMemsetAsync( pt->momentsBuf.p, 0, pt->momentsBuf.bytes, (hipStream_t)stream ) );
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream, int width, int height )
@@ -1281,7 +1300,10 @@ MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream,
 	pt->width = width;
 	pt->height = height;
 	// (no frame without all of its buffers)
-	if( pt->fbF32.alloc( pt->ownedPixels * sizeof( float4 ) ) || pt->fbU8.alloc( pt->ownedPixels * sizeof( uchar4 ) ) || ( pt->aovs && pt->allocAovFrame() ) ) return forgetFrame( pt );
+	pt->releaseDenoised(); // (a denoised image of the old size)
+	if( pt->fbF32.alloc( pt->ownedPixels * sizeof( float4 ) ) || pt->fbU8.alloc( pt->ownedPixels * sizeof( uchar4 ) ) || ( pt->aovs && pt->allocAovFrame() ) ||
+		( pt->moments && pt->momentsBuf.alloc( pt->ownedPixels * sizeof( float4 ) ) ) )
+		return forgetFrame( pt );
 	if( allocWork( pt ) ) return 1;
 	return mvrt_pt_clear_framebuffer( pt, stream ); // :88
 }
@@ -1477,8 +1499,9 @@ int mvrt_pt::launchPass( const CameraPinhole* passCams, int iteration, int nStep
 		aov.albedo = pt->aovAlbedo.as<float4>();
 		aov.normalDepth = pt->aovNormalDepth.as<float4>();
 	}
+	REQUIRE( !pt->moments || pt->momentsBuf.p, "internal: moments buffer not allocated" );
 	int rc = launchPtStep( pt->intersector->dev(), sl.trace.ws, pt->hdri.dev, pt->pmj.as<float2>(), cams, f, sl.buf, pt->fbF32.as<float4>(), pt->numCUs,
-						   pt->profiling ? &pt->prof : nullptr, run, after, pt->aovs ? &aov : nullptr );
+						   pt->profiling ? &pt->prof : nullptr, run, after, pt->aovs ? &aov : nullptr, pt->moments ? pt->momentsBuf.as<float4>() : nullptr );
 	if( rc ) return rc;
 	MVRT_HIP( hipEventRecord( sl.accumDone, run ) );
 	pt->lastAccum = sl.accumDone;
@@ -1577,6 +1600,160 @@ MVRT_EXPORT int mvrt_pt_read_aov( mvrt_pt* pt, void* stream, int which, float* r
 	REQUIRE( rgbaHost, "mvrt_pt_read_aov: null argument" );
 	if( pt->join( (hipStream_t)stream ) ) return 1;
 	MVRT_HIP( hipMemcpyAsync( rgbaHost, b->p, pt->ownedPixels * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
+	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
+	return 0;
+}
+
+// ---- luminance moments ----------------------------------------------------------------------------------------
+MVRT_EXPORT int mvrt_pt_set_moments( mvrt_pt* pt, int enable )
+{
+	REQUIRE( pt, "mvrt_pt_set_moments: null argument" );
+	if( pt->drain() ) return 1;
+	const bool on = enable != 0;
+	if( on == pt->moments ) return 0;
+	REQUIRE( pt->steps == 0, "mvrt_pt_set_moments: %d steps are accumulated in the frame buffer, the moments would not match its sample count (mvrt_pt_clear_framebuffer first)", pt->steps );
+	if( !pt->fbF32.p ) // no frame yet: the next resize allocates (or does not)
+	{
+		pt->moments = on;
+		return 0;
+	}
+	if( on )
+	{
+		if( pt->momentsBuf.alloc( pt->ownedPixels * sizeof( float4 ) ) ) return 1; // the frame stays as it was, without moments
+		hipError_t e = hipMemset( pt->momentsBuf.p, 0, pt->momentsBuf.bytes );
+		if( e == hipSuccess ) e = hipStreamSynchronize( nullptr );
+		if( e != hipSuccess )
+		{
+			pt->momentsBuf.release(); // (off means no buffer held)
+			mvrtSetError( "mvrt_pt_set_moments: clearing the moments failed: %s", hipGetErrorString( e ) );
+			return 1;
+		}
+	}
+	else pt->releaseMoments();
+	pt->moments = on;
+	return allocWork( pt ); // the buffer counts against the budget of the path state; a failure leaves NO frame, like every reallocation
+}
+static DevBuf* momentsBuffer( mvrt_pt* pt, const char* who )
+{
+	if( !pt )
+	{
+		mvrtSetError( "%s: null argument", who );
+		return nullptr;
+	}
+	if( !pt->moments || !pt->momentsBuf.p )
+	{
+		mvrtSetError( pt->moments ? "%s: no frame buffer" : "%s: the moments are off (mvrt_pt_set_moments)", who );
+		return nullptr;
+	}
+	return &pt->momentsBuf;
+}
+MVRT_EXPORT float* mvrt_pt_moments_dev( mvrt_pt* pt )
+{
+	DevBuf* b = momentsBuffer( pt, "mvrt_pt_moments_dev" );
+	return b ? b->as<float>() : nullptr;
+}
+MVRT_EXPORT int mvrt_pt_read_moments( mvrt_pt* pt, void* stream, float* rgbaHost )
+{
+	DevBuf* b = momentsBuffer( pt, "mvrt_pt_read_moments" );
+	if( !b ) return 1;
+	REQUIRE( rgbaHost, "mvrt_pt_read_moments: null argument" );
+	if( pt->join( (hipStream_t)stream ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( rgbaHost, b->p, pt->ownedPixels * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
+	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
+	return 0;
+}
+
+// ---- denoiser ---------------------------------------------------------------------------------------------------
+MVRT_EXPORT int mvrt_denoise_default_params( mvrt_denoise_params* p )
+{
+	REQUIRE( p, "mvrt_denoise_default_params: null argument" );
+	memset( p, 0, sizeof( *p ) );
+	p->structBytes = (uint32_t)sizeof( mvrt_denoise_params );
+	p->iterations = 5;
+	p->sigmaNormal = 0.5f;
+	p->sigmaDepth = 0.05f;
+	p->sigmaCoverage = 0.25f;
+	p->sigmaLuminance = 2.0f;
+	p->albedoFloor = 0.01f;
+	return 0;
+}
+// every rule on the parameters, on the host; in == NULL: the defaults
+static int denoiseParams( const mvrt_denoise_params* in, mvrt_denoise_params* out, const char* who )
+{
+	mvrt_denoise_default_params( out );
+	if( !in ) return 0;
+	REQUIRE( in->structBytes == sizeof( mvrt_denoise_params ), "%s: params->structBytes is %u, sizeof( mvrt_denoise_params ) is %u (mvrt_denoise_default_params fills it)", who, in->structBytes,
+			 (unsigned)sizeof( mvrt_denoise_params ) );
+	REQUIRE( in->iterations >= 1 && in->iterations <= 8, "%s: iterations %d outside 1..8", who, in->iterations );
+	REQUIRE( in->sigmaNormal > 0.0f, "%s: sigmaNormal %g is not greater than 0", who, (double)in->sigmaNormal );
+	REQUIRE( in->sigmaDepth > 0.0f, "%s: sigmaDepth %g is not greater than 0", who, (double)in->sigmaDepth );
+	REQUIRE( in->sigmaCoverage > 0.0f, "%s: sigmaCoverage %g is not greater than 0", who, (double)in->sigmaCoverage );
+	REQUIRE( in->sigmaLuminance > 0.0f, "%s: sigmaLuminance %g is not greater than 0", who, (double)in->sigmaLuminance );
+	REQUIRE( in->albedoFloor > 0.0f, "%s: albedoFloor %g is not greater than 0", who, (double)in->albedoFloor );
+	REQUIRE( ( in->flags & ~(uint32_t)MVRT_DENOISE_NO_DEMODULATION ) == 0, "%s: unknown flags 0x%x", who, in->flags );
+	*out = *in;
+	return 0;
+}
+static bool denoiseSizeOk( int width, int height ) { return width > 0 && height > 0 && (uint64_t)width * (uint64_t)height <= 0x7FFFFFFFull; } // (32-bit pixel indices)
+MVRT_EXPORT uint64_t mvrt_denoise_scratch_bytes( int width, int height )
+{
+	if( !denoiseSizeOk( width, height ) )
+	{
+		mvrtSetError( "mvrt_denoise_scratch_bytes: bad resolution %dx%d (width and height must be greater than 0)", width, height );
+		return 0;
+	}
+	return denoiseScratchBytes( (uint64_t)width * height );
+}
+MVRT_EXPORT int mvrt_denoise_buffers( const float* colorDev, const float* albedoDev, const float* normalDepthDev, const float* momentsDev, int width, int height,
+									  const mvrt_denoise_params* params, float* outDev, void* scratchDev, uint64_t scratchBytes, void* stream )
+{
+	REQUIRE( denoiseSizeOk( width, height ), "mvrt_denoise_buffers: bad resolution %dx%d (width and height must be greater than 0)", width, height );
+	mvrt_denoise_params P;
+	if( denoiseParams( params, &P, "mvrt_denoise_buffers" ) ) return 1;
+	REQUIRE( colorDev && albedoDev && normalDepthDev && momentsDev && outDev && scratchDev, "mvrt_denoise_buffers: null argument" );
+	const uint64_t need = denoiseScratchBytes( (uint64_t)width * height );
+	REQUIRE( scratchBytes >= need, "mvrt_denoise_buffers: scratch too small, %llu bytes given, a %dx%d frame needs %llu (mvrt_denoise_scratch_bytes)", (unsigned long long)scratchBytes, width,
+			 height, (unsigned long long)need );
+	return launchDenoise( (const float4*)colorDev, (const float4*)albedoDev, (const float4*)normalDepthDev, (const float4*)momentsDev, width, height, P.iterations, P.sigmaNormal, P.sigmaDepth,
+						  P.sigmaCoverage, P.sigmaLuminance, P.albedoFloor, P.flags, (float4*)outDev, scratchDev, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_pt_denoise( mvrt_pt* pt, void* stream, const mvrt_denoise_params* params )
+{
+	REQUIRE( pt, "mvrt_pt_denoise: null argument" );
+	mvrt_denoise_params P;
+	if( denoiseParams( params, &P, "mvrt_pt_denoise" ) ) return 1;
+	REQUIRE( pt->tileCount == 1, "mvrt_pt_denoise: this handle renders tile %d of %d; the filter needs the whole frame -- assemble the buffers (mvrt_pt_assemble_tiles) and call mvrt_denoise_buffers",
+			 pt->tileIndex, pt->tileCount );
+	REQUIRE( pt->aovs, "mvrt_pt_denoise: the feature buffers are off (mvrt_pt_set_aovs)" );
+	REQUIRE( pt->moments, "mvrt_pt_denoise: the moments are off (mvrt_pt_set_moments)" );
+	REQUIRE( pt->steps > 0, "mvrt_pt_denoise: no steps yet (the frame buffer holds no sample)" );
+	REQUIRE( pt->fbF32.p && pt->aovAlbedo.p && pt->aovNormalDepth.p && pt->momentsBuf.p, "mvrt_pt_denoise: no frame buffer" );
+	if( pt->join( (hipStream_t)stream ) ) return 1;
+	const uint64_t nPix = (uint64_t)pt->width * pt->height;
+	const uint64_t scratch = denoiseScratchBytes( nPix );
+	if( !pt->denoised.p || pt->denoised.bytes != nPix * sizeof( float4 ) || pt->denoiseScratch.bytes != scratch )
+	{
+		// nothing of the frame is touched: a failure leaves it, the steps and the feature buffers as they are, and no denoised buffer
+		if( pt->denoised.alloc( nPix * sizeof( float4 ) ) || pt->denoiseScratch.alloc( scratch ) )
+		{
+			pt->releaseDenoised();
+			return 1;
+		}
+	}
+	if( launchDenoise( pt->fbF32.as<float4>(), pt->aovAlbedo.as<float4>(), pt->aovNormalDepth.as<float4>(), pt->momentsBuf.as<float4>(), pt->width, pt->height, P.iterations, P.sigmaNormal,
+					   P.sigmaDepth, P.sigmaCoverage, P.sigmaLuminance, P.albedoFloor, P.flags, pt->denoised.as<float4>(), pt->denoiseScratch.p, (hipStream_t)stream ) )
+	{
+		pt->releaseDenoised();
+		return 1;
+	}
+	return 0;
+}
+MVRT_EXPORT float* mvrt_pt_denoised_dev( mvrt_pt* pt ) { return pt ? pt->denoised.as<float>() : nullptr; }
+MVRT_EXPORT int mvrt_pt_read_denoised( mvrt_pt* pt, void* stream, float* rgbaHost )
+{
+	REQUIRE( pt && rgbaHost, "mvrt_pt_read_denoised: null argument" );
+	REQUIRE( pt->denoised.p, "mvrt_pt_read_denoised: no denoised buffer (mvrt_pt_denoise first)" );
+	MVRT_HIP( hipMemcpyAsync( rgbaHost, pt->denoised.p, (uint64_t)pt->width * pt->height * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
 	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
 	return 0;
 }

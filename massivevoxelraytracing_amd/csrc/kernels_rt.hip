@@ -965,7 +965,7 @@ __global__ void __launch_bounds__( 256 ) kPtAovAccumulate( uint64_t validOwnedPi
 }
 
 int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hdri, const float2* pmj, const CameraPinhole* cams, const PtFrame& frame,
-				  const PtBuffers& buf, float4* frameBuffer, int nCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov )
+				  const PtBuffers& buf, float4* frameBuffer, int nCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov, float4* moments )
 {
 	PtParams P;
 	P.svo = svo;
@@ -1092,6 +1092,13 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 		hipLaunchKernelGGL( kPtAovAccumulate, dim3( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, frame.validOwnedPixels, frame.nSteps, aov->partA,
 							aov->partN, aov->albedo, aov->normalDepth );
 		PROF_END();
+	}
+	if( moments ) // luminance moments (mvrt_pt_set_moments): the Ls* planes are complete until the next pass of this slot generates
+	{
+		PROF_BEGIN( MVRT_K_OTHER );
+		const int rc = launchPtMoments( buf, frame.validOwnedPixels, frame.nSteps, moments, nCUs, stream );
+		PROF_END();
+		if( rc ) return rc;
 	}
 	MVRT_HIP( hipGetLastError() );
 	return 0;

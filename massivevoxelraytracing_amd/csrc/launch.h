@@ -90,9 +90,16 @@ struct AovBuffers
 	float4 *partA, *partN;
 	float4 *albedo, *normalDepth;
 };
-// aov == nullptr: exactly the launches of a library without feature buffers
+// aov == nullptr: exactly the launches of a library without feature buffers.  moments (mvrt_pt_set_moments; float4 per owned pixel like the frame buffer)
+// travels the same way: nullptr = off, no launch
 int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hdri, const float2* pmj, const CameraPinhole* cams /* frame.nSteps */, const PtFrame& frame, const PtBuffers& buf, float4* frameBuffer,
-				  int numCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov = nullptr );
+				  int numCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov = nullptr, float4* moments = nullptr );
+
+// kernels_denoise.hip: the luminance moments of a pass (behind kPtAccumulate, same stream) and the a-trous denoiser on full-frame buffers
+int launchPtMoments( const PtBuffers& buf, uint64_t validOwnedPixels, int nSteps, float4* moments, int numCUs, hipStream_t stream );
+uint64_t denoiseScratchBytes( uint64_t nPixels );
+int launchDenoise( const float4* color, const float4* albedo, const float4* normalDepth, const float4* moments, int W, int H, int iterations, float sigmaNormal, float sigmaDepth,
+				   float sigmaCoverage, float sigmaLuminance, float albedoFloor, uint32_t flags, float4* out, void* scratch, hipStream_t stream );
 
 int launchResolve( const float4* fb, uint64_t n, uchar4* out, hipStream_t stream );
 int launchAssembleTiles( const float4* gathered, int tileCount, uint64_t rankStridePixels, int W, int H, float4* frame, hipStream_t stream );

@@ -1,0 +1,235 @@
+"""Luminance moments and the a-trous denoiser, the part that needs no GPU: the recipe of tests/denoise_expected.py pinned to the oracle's own frame buffer, the
+quality of the filter the contract defines (on oracle renders alone), and the host-side refusals of the new entry points."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import aov_expected as A
+import denoise_expected as D
+from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+
+OFFSETS = [(6, 4, 6), (-6, -4, -6), (-2.5, 1.5, -2.0)]  # the three cameras of tests/test_gpu_aov.py
+f32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import oracle
+    return oracle
+
+
+@pytest.fixture(scope="module")
+def scene(O):
+    tris = bunny_tris()
+    cols, emis = position_colors(tris)
+    return O.build_scene_from_triangles(tris, 256, cols, emis)
+
+
+@pytest.fixture(scope="module")
+def hdri(O):
+    rgba, hw, hh = O.decode_rgbe(hdr_bytes())
+    return O.HDRI(rgba, hw, hh, rgba, hw, hh, math_mode=1)
+
+
+def test_moment_recipe_matches_the_frame_buffer_increments(O, scene, hdri):
+    """s1 of the helper is the luminance summed per sample; the oracle's frame buffer sums the same samples per channel.  lum( increment ) and s1 are two fp32
+    evaluations of one sum of non-negative terms, each of at most 19 roundings (3 products, 2 + 15 additions / 15 additions per channel, 3 products, 2 additions):
+    they agree within 40 * 2^-24 relative.  s2 >= s1^2 / 16 (Cauchy-Schwarz) within the same rounding, and both are 0 exactly where the pixel is black."""
+    w, h = 64, 40
+    cam = probe_camera(scene.origin, scene.dps, 256, focus=9.0, lens_r=0.05)
+    fb = np.zeros((w * h, 4), f32)
+    exp = D.ExpectedMoments(w, h)
+    for it in (0, 1):
+        before = fb.copy()
+        fb, sl, _ = scene.render_pt(hdri, cam, w, h, it, math_mode=1, fb=fb, want_samples=True, threads=16)
+        s1, s2 = exp.step(sl)
+        if it == 0:  # (the second increment is a difference of rounded sums: only the first is the sum itself)
+            inc = fb[:, 0:3] - before[:, 0:3]
+            li = D.lum(inc[:, 0], inc[:, 1], inc[:, 2]).astype(np.float64)
+            assert (sl >= 0).all()
+            assert (np.abs(li - s1) <= 40 * 2.0 ** -24 * np.maximum(li, s1)).all()
+            assert li.max() > 1.0
+        assert (s2.astype(np.float64) * 16 >= s1.astype(np.float64) ** 2 * (1 - 80 * 2.0 ** -24)).all()
+        assert ((s1 == 0) == (s2 == 0)).all()
+    assert not exp.moments[:, 2:4].any() and (exp.moments[:, 0] > 0).sum() > w * h // 2
+    # sequential, not pairwise: the helper's order is observable
+    s = sl.reshape(-1, 16, 3)
+    pairwise = D.lum(s[..., 0], s[..., 1], s[..., 2]).astype(f32).sum(1, dtype=f32)
+    assert (pairwise != s1).any()
+
+
+def test_filter_helper_on_hand_made_frames(O):
+    """what the contract says about special pixels, on a 6 x 5 frame: n == 0 -> (0,0,0,0); sky -> c exactly, w = 1, never a tap; a constant hit region stays constant;
+    one iteration with every edge-stopping term zero is the normalised 5 x 5 B3 kernel"""
+    W, H = 6, 5
+    n = np.full(W * H, 32, f32)
+    color = np.zeros((W * H, 4), f32)
+    color[:, 0:3] = 32 * 0.5
+    color[:, 3] = n
+    albedo = np.zeros((W * H, 4), f32)
+    albedo[:, 0:3] = 32 * 0.5
+    albedo[:, 3] = 32
+    nd = np.zeros((W * H, 4), f32)
+    nd[:, 2] = 32
+    nd[:, 3] = 32 * 3.0
+    mom = np.zeros((W * H, 4), f32)
+    mom[:, 0] = 32 * 0.5
+    mom[:, 1] = 32 * 0.3
+    sky, empty = 7, 8
+    albedo[sky] = 0
+    nd[sky] = 0
+    color[sky, 0:3] = [3.0, 5.0, 7.0]
+    color[empty] = 0
+    albedo[empty] = 0
+    out = D.denoise(O, color, albedo, nd, mom, W, H)
+    assert out[empty].tolist() == [0, 0, 0, 0]
+    assert np.array_equal(out[sky], np.array([3.0, 5.0, 7.0, 32], f32) / f32(32))
+    rest = np.ones(W * H, bool)
+    rest[[sky, empty]] = False
+    assert np.allclose(out[rest, 0:3], 0.5, rtol=1e-6) and (out[rest, 3] == 1).all()  # the bright sky pixel leaked nowhere
+    # an impulse, no demodulation, huge sigmas: the B3 weights around it
+    color[:, 0:3] = 0
+    albedo[:] = [32, 32, 32, 32]
+    nd[:] = [0, 0, 32, 32 * 3.0]
+    color[:, 3] = 32
+    c = 2 * W + 3
+    color[c, 0:3] = 32
+    mom[:, 0:2] = 0
+    out = D.denoise(O, color, albedo, nd, mom, W, H, iterations=1, sigmaLuminance=1e30, flags=D.NO_DEMODULATION)
+    # (v == 0 everywhere: the luminance term is |dl| / 1e-6 -> weight exp( -87 ) except between equal pixels; so use the neighbours' view instead)
+    k = np.array([1, 4, 6, 4, 1], np.float64) / 16
+    assert out[c, 0] == 1.0  # every neighbour differs in luminance by 1 and is rejected at v == 0
+    mom[:, 0] = 32 * 0.5
+    mom[:, 1] = 32 * 100.0  # a large variance: the luminance term vanishes
+    out = D.denoise(O, color, albedo, nd, mom, W, H, iterations=1, sigmaLuminance=1e30, flags=D.NO_DEMODULATION)
+    assert abs(out[c, 0] - k[2] * k[2]) < 1e-6 and abs(out[c - 1, 0] - k[2] * k[1]) < 1e-6
+    # at a border the taps outside the frame are skipped and the rest renormalised: pixel (4, 2) of the 6-wide frame lacks the column x = 6 (weight 1 / 16)
+    assert abs(out[c + 1, 0] - k[2] * k[1] / (1 - k[4])) < 1e-6
+
+
+def test_quality_on_oracle_frames(O, scene, hdri):
+    """bunny 256^3, 128 x 72, three cameras, inputs of 1 and 4 steps (16 and 64 spp), truth = the 48-step oracle frame, default parameters:
+    relMSE( denoised ) < relMSE( noisy ) over the whole frame and over the pixels with h > 0, in all six cases; sky pixels come out as c bit for bit.
+    relMSE = mean over the pixels of |a - b|^2 / ( |b|^2 + 1e-2 ) on rgb vectors."""
+    w, h = 128, 72
+    for off in OFFSETS:
+        cam = probe_camera(scene.origin, scene.dps, 256, focus=9.0, lens_r=0.05, offset=off)
+        fb = np.zeros((w * h, 4), f32)
+        aov = A.Expected(O, scene, w, h)
+        mom = D.ExpectedMoments(w, h)
+        inputs = {}
+        for it in range(48):
+            fb, sl, _ = scene.render_pt(hdri, cam, w, h, it, math_mode=1, fb=fb, want_samples=it < 4, threads=16)
+            if it < 4:
+                aov.step(cam)
+                mom.step(sl)
+            if it in (0, 3):
+                inputs[it + 1] = (fb.copy(), aov.albedo.copy(), aov.normal_depth.copy(), mom.moments.copy())
+        truth = (fb[:, 0:3] / fb[:, 3:4]).astype(f32)
+        for steps, (c, a, nd, m) in inputs.items():
+            out = D.denoise(O, c, a, nd, m, w, h)
+            noisy = (c[:, 0:3] / c[:, 3:4]).astype(f32)
+            hit = a[:, 3] > 0
+            assert hit.sum() > 0.05 * w * h
+            assert np.array_equal(out[~hit, 0:3], noisy[~hit]) and (out[:, 3] == 1).all()
+            for name, mask in (("whole frame", None), ("h > 0", hit)):
+                rn, rd = D.rel_mse(noisy, truth, mask), D.rel_mse(out, truth, mask)
+                print("camera %s, %d spp, %s: relMSE noisy %.5f denoised %.5f ratio %.3f" % (off, 16 * steps, name, rn, rd, rd / rn))
+                assert rd < rn, (off, steps, name, rd, rn)
+
+
+def _err(lib):
+    return lib.mvrt_last_error().decode()
+
+
+def test_host_side_refusals_without_a_gpu():
+    """every rejected argument of the new entry points fails before any GPU call, with a message that names it"""
+    import massivevoxelraytracing_amd as mv
+    lib = mv.lib()
+    P = mv.denoise_params()
+    assert (P.structBytes, P.iterations, P.flags) == (C.sizeof(mv.DenoiseParams), 5, 0) and C.sizeof(mv.DenoiseParams) == 40
+    assert [round(x, 6) for x in (P.sigmaNormal, P.sigmaDepth, P.sigmaCoverage, P.sigmaLuminance, P.albedoFloor)] == [0.5, 0.05, 0.25, 2.0, 0.01]
+    assert lib.mvrt_denoise_default_params(None) != 0 and "null" in _err(lib)
+    # scratch size: host arithmetic
+    n = mv.denoise_scratch_bytes(1920, 1080)
+    assert 1920 * 1080 * 52 <= n <= 1920 * 1080 * 52 + 4 * 256
+    for wh in ((0, 10), (10, 0), (-1, 5)):
+        assert lib.mvrt_denoise_scratch_bytes(*wh) == 0 and "width and height" in _err(lib)
+    fake = 0x1000  # never dereferenced: every call below fails before the first GPU call
+
+    def buffers(w=16, h=16, params=None, scratch_bytes=None):
+        sb = mv.denoise_scratch_bytes(16, 16) if scratch_bytes is None else scratch_bytes
+        return lib.mvrt_denoise_buffers(fake, fake, fake, fake, w, h, None if params is None else C.byref(params), fake, fake, sb, None)
+
+    for wh in ((0, 16), (16, 0), (16, -3)):
+        assert buffers(*wh) != 0 and "width and height" in _err(lib)
+    assert buffers(scratch_bytes=mv.denoise_scratch_bytes(16, 16) - 1) != 0 and "scratch too small" in _err(lib)
+    assert lib.mvrt_denoise_buffers(None, fake, fake, fake, 16, 16, None, fake, fake, 1 << 20, None) != 0 and "null" in _err(lib)
+    bad = [(dict(structBytes=36), "structBytes"), (dict(iterations=0), "iterations"), (dict(iterations=9), "iterations"), (dict(sigmaNormal=0.0), "sigmaNormal"),
+           (dict(sigmaDepth=-1.0), "sigmaDepth"), (dict(sigmaCoverage=0.0), "sigmaCoverage"), (dict(sigmaLuminance=float("nan")), "sigmaLuminance"),
+           (dict(albedoFloor=0.0), "albedoFloor"), (dict(flags=2), "flags")]
+    h = C.c_void_p(0)
+    assert lib.mvrt_pt_create(C.byref(h)) == 0
+    try:
+        for fields, word in bad:
+            p = mv.denoise_params(**fields)
+            assert buffers(params=p) != 0 and word in _err(lib), fields
+            assert lib.mvrt_pt_denoise(h, None, C.byref(p)) != 0 and word in _err(lib), fields
+        assert lib.mvrt_pt_denoise(None, None, None) != 0 and "null" in _err(lib)
+        # a handle: feature buffers off, then moments off, then no steps; a tile share is pointed to mvrt_denoise_buffers
+        assert lib.mvrt_pt_denoise(h, None, None) != 0 and "mvrt_pt_set_aovs" in _err(lib)
+        assert lib.mvrt_pt_set_aovs(h, 1) == 0
+        assert lib.mvrt_pt_denoise(h, None, None) != 0 and "mvrt_pt_set_moments" in _err(lib)
+        assert lib.mvrt_pt_moments_dev(h) is None and "mvrt_pt_set_moments" in _err(lib)
+        assert lib.mvrt_pt_set_moments(h, 1) == 0
+        assert lib.mvrt_pt_denoise(h, None, None) != 0 and "no steps" in _err(lib)
+        assert lib.mvrt_pt_moments_dev(h) is None and "no frame buffer" in _err(lib)
+        assert lib.mvrt_pt_denoised_dev(h) is None
+        out = np.zeros(4, f32)
+        assert lib.mvrt_pt_read_denoised(h, None, out.ctypes.data_as(C.c_void_p)) != 0 and "mvrt_pt_denoise first" in _err(lib)
+        assert lib.mvrt_pt_read_moments(h, None, out.ctypes.data_as(C.c_void_p)) != 0 and "no frame buffer" in _err(lib)
+        assert lib.mvrt_pt_set_tile(h, 1, 3) == 0
+        assert lib.mvrt_pt_denoise(h, None, None) != 0 and "mvrt_denoise_buffers" in _err(lib) and "tile 1 of 3" in _err(lib)
+        assert lib.mvrt_pt_set_moments(None, 1) != 0 and "null" in _err(lib)
+        assert lib.mvrt_pt_read_moments(None, None, None) != 0 and lib.mvrt_pt_moments_dev(None) is None
+    finally:
+        lib.mvrt_pt_destroy(h)
+    with pytest.raises(TypeError):
+        mv.denoise_params(sigma=1.0)
+    for m in ("set_moments", "read_moments", "moments_dev", "denoise", "read_denoised", "denoised_dev"):
+        assert callable(getattr(mv.PathTracer, m))
+    assert callable(mv.denoise_buffers) and callable(mv.denoise_scratch_bytes) and mv.DENOISE_NO_DEMODULATION == 1
+
+
+def test_entry_points_exist_in_every_layer(tmp_path):
+    """header (each new entry with its "new; the reference has none" comment), library, Python mirror, C++ mirror (tests/cpp/denoise_usage.cpp compiles with -Werror
+    and its GPU-free part runs)"""
+    import massivevoxelraytracing_amd as mv
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "mvrt.h")).read()
+    names = ["mvrt_pt_set_moments", "mvrt_pt_moments_dev", "mvrt_pt_read_moments", "mvrt_denoise_default_params", "mvrt_denoise_scratch_bytes", "mvrt_denoise_buffers",
+             "mvrt_pt_denoise", "mvrt_pt_denoised_dev", "mvrt_pt_read_denoised"]
+    lib = C.CDLL(mv.LIB_PATH)
+    for s in names:
+        m = re.search(r"^[a-z][^\n]*\b%s\s*\([^\n]*$" % s, text, re.M)  # the declaration's line
+        assert m, s
+        before = text[: m.start()].rstrip()
+        comment = before[before.rindex("/*"):] if before.endswith("*/") else ""
+        assert "new; the reference has none" in comment + m.group(0), s
+        assert hasattr(lib, s) and s in mv.SIGNATURES, s
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert re.search(r"#define\s+MVRT_DENOISE_NO_DEMODULATION\s+1u?\b", code)
+    assert "mvrt_exp( -e )" in text and "Iteration i = 0 .. iterations - 1" in text  # the filter is written out in the header
+    gxx = shutil.which("g++")
+    assert gxx, "no g++"
+    exe = tmp_path / "denoise_usage"
+    libdir = os.path.dirname(mv.LIB_PATH)
+    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "denoise_usage.cpp"), "-o", str(exe),
+                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
+    assert b"iterations 5 structBytes 40 scratch %d" % mv.denoise_scratch_bytes(64, 36) in out
