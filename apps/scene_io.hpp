@@ -189,4 +189,33 @@ inline bool writePngUncompressed( const char* path, const uint8_t* rgba, int w, 
 	std::fclose( fp );
 	return true;
 }
+
+// PLY quad mesh, the reference's Save-As-Mesh format (voxMesh.cpp:204-218: binary_little_endian 1.0, vertex float x y z, face list uchar uint vertex_indices)
+// plus a colour per face: uchar red green blue = bytes 0..2 of the VoxelAttirb (8 bytes per voxel, colour first) of the face's voxel.
+// vertices: 3 floats each; indices: 4 per face; faceVoxel: the voxel index per face; attribs8 == nullptr: white.  Little-endian hosts only.
+inline bool writePlyQuads( const char* path, const float* vertices, uint64_t nVertices, const uint32_t* indices, const uint32_t* faceVoxel, uint64_t nFaces,
+						   const uint8_t* attribs8 )
+{
+	FILE* fp = std::fopen( path, "wb" );
+	if( !fp ) return false;
+	std::fprintf( fp, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n", (unsigned long long)nVertices );
+	std::fprintf( fp, "element face %llu\nproperty list uchar uint vertex_indices\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
+				  (unsigned long long)nFaces );
+	bool ok = nVertices == 0 || std::fwrite( vertices, 12, nVertices, fp ) == nVertices;
+	std::vector<uint8_t> rec( (size_t)( nFaces < 65536 ? nFaces : 65536 ) * 20 ); // 1 + 16 + 3 bytes per face, written in chunks
+	for( uint64_t f0 = 0; f0 < nFaces && ok; f0 += 65536 )
+	{
+		const uint64_t n = nFaces - f0 < 65536 ? nFaces - f0 : 65536;
+		for( uint64_t i = 0; i < n; i++ )
+		{
+			uint8_t* r = &rec[(size_t)i * 20];
+			r[0] = 4;
+			std::memcpy( r + 1, indices + ( f0 + i ) * 4, 16 );
+			const uint8_t* c = attribs8 ? attribs8 + (uint64_t)faceVoxel[f0 + i] * 8 : nullptr;
+			for( int k = 0; k < 3; k++ ) r[17 + k] = c ? c[k] : 255;
+		}
+		ok = std::fwrite( rec.data(), 20, n, fp ) == n;
+	}
+	return std::fclose( fp ) == 0 && ok;
+}
 } // namespace mvrt_io

@@ -129,6 +129,34 @@ int mvrt_svo_edit_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t*
  * either may be NULL.  Octrees built by this library only. */
 int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attribsDev, void* stream );
 
+/* The exposed faces of the voxel set as a quad mesh: the reference voxelizer's "Save As Mesh" (voxMesh.cpp:111-219, voxelMeshWriter.hpp) on the GPU, from the
+ * sorted Morton codes and the cell index a build leaves resident.  For an octree built by this library (build, build_ex, build_synthetic, build_voxels, or any
+ * edit of one), of every flavour; an uploaded octree is refused like mvrt_svo_read_voxels ("keeps no Morton codes"), an empty handle with the "no octree" error,
+ * both before any GPU work.  The handle is never modified.  The calls block like mvrt_svo_build (the counts come back to the host).  Any output pointer may be
+ * NULL.  A capacity smaller than the count is an error: the counts are still returned and NOTHING is written to the caller's arrays; all outputs NULL is the
+ * sizing call (capacities are then ignored).  A failed allocation of scratch returns an error, leaves the octree whole and leaks nothing.
+ *   - Exposure mask: per voxel, in vIndex order (the Morton rank, as in read_voxels), one byte.  Bit b is set when the neighbouring grid cell in direction b holds
+ *     no voxel.  Directions in the reference's emission order (voxMesh.cpp:172-200): 0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X.  A neighbour outside
+ *     [0, gridRes) is empty, in all six directions (the reference tests x == 0 and relies on the missing code for x + 1 == gridRes: the same below 2^21, and no
+ *     21-bit wrap at 2^21).  Bits 6-7 are 0.  nFaces = the sum of the popcounts.
+ *   - Face list: ascending vIndex, within a voxel ascending direction.  Per face faceVoxel (the vIndex: it indexes the attribute buffer, so colours need no
+ *     output of their own), faceDir, and four corners in the reference's winding.
+ *   - Corners 0..7 of the voxel at (x, y, z) lie at the offsets 0 (0,0,0) 1 (1,0,0) 2 (1,0,1) 3 (0,0,1) 4 (0,1,0) 5 (1,1,0) 6 (1,1,1) 7 (0,1,1); the faces are
+ *     -Y = 3,2,1,0  +Y = 4,5,6,7  -Z = 0,1,5,4  +X = 1,2,6,5  +Z = 2,3,7,6  -X = 3,0,4,7.
+ *   - Positions: a corner with integer grid coordinate c in [0, gridRes] on an axis lies at lower + (float)c * dps with the lower and dps of mvrt_svo_info: one fp32
+ *     multiply and one fp32 add, each rounded, no FMA.  A DELIBERATE difference from the reference's (origin + x * dps) + dps, by an ulp in places: a corner
+ *     shared by neighbouring voxels has ONE bit pattern, so the mesh is watertight and can be welded.
+ *   - Welded mesh: a corner's key is (cz * (gridRes + 1) + cy) * (gridRes + 1) + cx (a uint64 up to gridRes 2^21); the vertices are the distinct keys of all face
+ *     corners in ascending key order, indices[f][k] = the rank of the key of face f's corner k.  Refused on the host, naming the count, when 4 * nFaces >= 2^32. */
+/* voxMesh.cpp:138-148 (the six neighbour tests).  masksDev: numberOfVoxels bytes, NULL = count only. */
+int mvrt_svo_surface_masks( const mvrt_svo* svo, uint8_t* masksDev, uint64_t* nFacesOut, void* stream );
+/* voxMesh.cpp:119-128,172-200 (one quad per exposed face, its corners not shared).  faceVoxelDev / faceDirDev: faceCapacity entries; positionsDev: 12 floats per face (4 corners x xyz). */
+int mvrt_svo_surface_quads( const mvrt_svo* svo, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut,
+							void* stream );
+/* The same faces over SHARED vertices (the reference writes eight points per voxel, voxMesh.cpp:113-129,204-218; welding is new).  indicesDev: 4 per face; verticesDev: 3 floats per vertex, vertexCapacity vertices. */
+int mvrt_svo_surface_mesh( const mvrt_svo* svo, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
+						   float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream );
+
 /* Adopt an SVO built elsewhere (e.g. IntersectorOctree::buildDAGReference on the CPU, IntersectorOctree.hpp:
  * 224-231): nodes in the reference's 68-byte layout, root last.  embeddedMask = 0 selects the variant where
  * the mask is fetched from the node (voxCommon.hpp:353-356; required above 0xFFFFFF nodes). */

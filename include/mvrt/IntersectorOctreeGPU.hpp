@@ -125,6 +125,64 @@ struct IntersectorOctreeGPU
 		check( mvrt_memcpy_d2h( attribs.data(), a.p, attribs.size() * 4, stream ), "mvrt_memcpy_d2h" );
 	}
 
+	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
+	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
+	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const
+	{
+		uint64_t nFaces = 0;
+		check( mvrt_svo_surface_masks( m_handle, masksDev, &nFaces, stream ), "IntersectorOctreeGPU::surfaceMasks" );
+		return nFaces;
+	}
+	uint64_t surfaceQuads( uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, void* stream ) const
+	{
+		uint64_t nFaces = 0;
+		check( mvrt_svo_surface_quads( m_handle, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, &nFaces, stream ), "IntersectorOctreeGPU::surfaceQuads" );
+		return nFaces;
+	}
+	void surfaceMesh( uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFaces,
+					  uint64_t* nVertices, void* stream ) const
+	{
+		check( mvrt_svo_surface_mesh( m_handle, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFaces, nVertices, stream ),
+			   "IntersectorOctreeGPU::surfaceMesh" );
+	}
+	// host-vector forms: sized here (the sizing call, then the real one), staged through mvrt_malloc / mvrt_memcpy_d2h
+	uint64_t surfaceMasks( std::vector<uint8_t>& masks, void* stream ) const
+	{
+		masks.resize( m_numberOfVoxels );
+		Staged m( nullptr, masks.size(), stream );
+		const uint64_t nFaces = surfaceMasks( (uint8_t*)m.p, stream );
+		fetch( masks, m, stream );
+		return nFaces;
+	}
+	void surfaceQuads( std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<float>& positions /* 12 per face */, void* stream ) const
+	{
+		const uint64_t n = surfaceQuads( 0, nullptr, nullptr, nullptr, stream );
+		faceVoxel.resize( n );
+		faceDir.resize( n );
+		positions.resize( n * 12 );
+		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), p( nullptr, n * 48, stream );
+		surfaceQuads( n, (uint32_t*)v.p, (uint8_t*)d.p, (float*)p.p, stream );
+		fetch( faceVoxel, v, stream );
+		fetch( faceDir, d, stream );
+		fetch( positions, p, stream );
+	}
+	void surfaceMesh( std::vector<float>& vertices /* 3 per vertex */, std::vector<uint32_t>& indices /* 4 per face */, std::vector<uint32_t>& faceVoxel,
+					  std::vector<uint8_t>& faceDir, void* stream ) const
+	{
+		uint64_t nf = 0, nv = 0;
+		surfaceMesh( 0, 0, nullptr, nullptr, nullptr, nullptr, &nf, &nv, stream );
+		vertices.resize( nv * 3 );
+		indices.resize( nf * 4 );
+		faceVoxel.resize( nf );
+		faceDir.resize( nf );
+		Staged x( nullptr, nv * 12, stream ), i( nullptr, nf * 16, stream ), v( nullptr, nf * 4, stream ), d( nullptr, nf, stream );
+		surfaceMesh( nf, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)i.p, (float*)x.p, &nf, &nv, stream );
+		fetch( vertices, x, stream );
+		fetch( indices, i, stream );
+		fetch( faceVoxel, v, stream );
+		fetch( faceDir, d, stream );
+	}
+
 	// batch form of the device method intersect() (:243-251): SoA device arrays
 	void intersect( uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz, const uint8_t* isShadowRay, float* t,
 					int32_t* nMajor, uint32_t* vIndex, void* stream ) const
@@ -194,6 +252,10 @@ private:
 		Staged( const Staged& ) = delete;
 		void operator=( const Staged& ) = delete;
 	};
+	template <class T> static void fetch( std::vector<T>& host, const Staged& dev, void* stream ) // device -> host vector of the same size (nothing for an empty one)
+	{
+		if( !host.empty() ) check( mvrt_memcpy_d2h( host.data(), dev.p, host.size() * sizeof( T ), stream ), "mvrt_memcpy_d2h" );
+	}
 	mvrt_svo* m_handle = nullptr;
 	bool m_owned = true;
 };

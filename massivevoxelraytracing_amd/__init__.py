@@ -77,6 +77,9 @@ SIGNATURES = {
     "mvrt_svo_build_voxels": (_i32, [_vp, _vp, _vp, _u64, _vp, _f32, _i32, _i32, _vp]),
     "mvrt_svo_edit_voxels": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "mvrt_svo_read_voxels": (_i32, [_vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_masks": (_i32, [_vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_quads": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_mesh": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
     "mvrt_svo_device_view": (_i32, [_vp, _vp]),
@@ -355,6 +358,46 @@ class IntersectorOctreeGPU:
         xyz, at = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8)
         _check(lib().mvrt_svo_read_voxels(self._h, xyz.ptr, at.ptr, stream))
         return xyz.to_host(), at.to_host()
+
+    def surface_masks_device(self, masks_dev=None, stream=None):
+        """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_surface_masks(self._h, _dev_ptr(masks_dev), C.byref(n), stream))
+        return n.value
+
+    def surface_masks(self, stream=None):
+        """mvrt_svo_surface_masks -> (masks (numberOfVoxels,) uint8 in vIndex order, nFaces): bit d of a mask = the neighbour in direction d is empty,
+        d = 0 -Y, 1 +Y, 2 -Z, 3 +X, 4 +Z, 5 -X"""
+        masks = DeviceArray(self.info().numberOfVoxels, np.uint8)
+        n = self.surface_masks_device(masks, stream)
+        return masks.to_host(), n
+
+    def surface_quads_device(self, face_capacity=0, faceVoxel=None, faceDir=None, positions=None, stream=None):
+        """mvrt_svo_surface_quads into caller device arrays (any may be None; all None = the sizing call); returns nFaces.  On MvrtError nothing was written."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_surface_quads(self._h, int(face_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(positions), C.byref(n), stream))
+        return n.value
+
+    def surface_quads(self, stream=None):
+        """the exposed faces as unwelded quads: {faceVoxel (n,) uint32 vIndex, faceDir (n,) uint8, positions (n, 4, 3) float32}, faces by vIndex then direction"""
+        n = self.surface_quads_device(stream=stream)
+        fv, fd, pos = DeviceArray(n, np.uint32), DeviceArray(n, np.uint8), DeviceArray((n, 4, 3), np.float32)
+        self.surface_quads_device(n, fv, fd, pos, stream)
+        return {"faceVoxel": fv.to_host(), "faceDir": fd.to_host(), "positions": pos.to_host()}
+
+    def surface_mesh_device(self, face_capacity=0, vertex_capacity=0, faceVoxel=None, faceDir=None, indices=None, vertices=None, stream=None):
+        """mvrt_svo_surface_mesh into caller device arrays (any may be None; all None = the sizing call); returns (nFaces, nVertices)"""
+        nf, nv = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_surface_mesh(self._h, int(face_capacity), int(vertex_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(indices), _dev_ptr(vertices),
+                                           C.byref(nf), C.byref(nv), stream))
+        return nf.value, nv.value
+
+    def surface_mesh(self, stream=None):
+        """the exposed faces over shared vertices: {vertices (m, 3) float32 in corner-key order, indices (n, 4) uint32, faceVoxel (n,), faceDir (n,)}"""
+        nf, nv = self.surface_mesh_device(stream=stream)
+        fv, fd, idx, vtx = DeviceArray(nf, np.uint32), DeviceArray(nf, np.uint8), DeviceArray((nf, 4), np.uint32), DeviceArray((nv, 3), np.float32)
+        self.surface_mesh_device(nf, nv, fv, fd, idx, vtx, stream)
+        return {"vertices": vtx.to_host(), "indices": idx.to_host(), "faceVoxel": fv.to_host(), "faceDir": fd.to_host()}
 
     def upload(self, nodes68, attribs, origin, dps, gridRes, hasEmission=0, embeddedMask=True, stream=None):
         nodes68 = np.ascontiguousarray(nodes68)

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("MVRT_LIB_OUT", os.path.join(HERE, "libmvrt_hip.so"))
-SOURCES = ["api.hip", "kernels_rt.hip", "kernels_setup.hip", "svo_build.hip", "kernels_denoise.hip"]
+SOURCES = ["api.hip", "kernels_rt.hip", "kernels_setup.hip", "svo_build.hip", "kernels_denoise.hip", "kernels_surface.hip"]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
     "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",
@@ -74,6 +74,8 @@ def build(force=False, verbose=True):
 APPS = {
     # name: (source, extra compile/link flags)
     "rtcamp_batch": ("rtcamp_batch.cpp", []),
+    # the reference voxelizer's Save-As-Mesh without the GUI: scene.obj -> PLY quad mesh of the exposed voxel faces
+    "voxel_mesh": ("voxel_mesh.cpp", []),
     # single-process N-GPU tile driver: HIP runtime types for RCCL's stream argument + librccl
     "tile_render": ("tile_render.cpp", ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-L/opt/rocm/lib", "-lrccl", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"]),
 }

@@ -533,6 +533,45 @@ MVRT_EXPORT int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uin
 	return svoReadVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.info.numberOfVoxels, xyzDev, attribsDev, (hipStream_t)stream );
 }
 
+// Surface extraction (kernels_surface.hip).  Only the sorted codes and, where there is one, the cell index are read: every flavour is accepted and the
+// handle is never modified.  (Builds and edits drain the steps in flight themselves; nothing here changes what a pending step reads.)
+static int surfaceSource( const mvrt_svo* svo, const char* who, SurfaceSource* s )
+{
+	REQUIRE( svo, "%s: null handle", who );
+	REQUIRE( !svo->empty(), "%s: no octree (build first)", who );
+	REQUIRE( svo->oct.morton.p, "%s: an uploaded octree keeps no Morton codes", who );
+	const Octree& o = svo->oct;
+	s->morton = o.morton.as<uint64_t>();
+	s->nVoxels = o.info.numberOfVoxels;
+	s->levels = o.info.levels;
+	s->cellBlocks = o.cellEntries.p ? o.cellBlocks.as<uint32_t>() : nullptr;
+	s->cellEntries = o.cellEntries.as<uint2>();
+	s->cellBits = o.cellBits;
+	s->lower = mk3( o.info.lower[0], o.info.lower[1], o.info.lower[2] );
+	s->dps = o.info.dps;
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_surface_masks( const mvrt_svo* svo, uint8_t* masksDev, uint64_t* nFacesOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_masks", &s ) ) return 1;
+	return surfaceMasks( s, masksDev, nFacesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_quads( const mvrt_svo* svo, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut,
+										void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_quads", &s ) ) return 1;
+	return surfaceQuads( s, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFacesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_mesh( const mvrt_svo* svo, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
+									   float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_mesh", &s ) ) return 1;
+	return surfaceMesh( s, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFacesOut, nVerticesOut, (hipStream_t)stream );
+}
+
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );

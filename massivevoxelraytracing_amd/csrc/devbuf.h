@@ -66,3 +66,15 @@ struct DevBuf // move-only
 	DevBuf& operator=( const DevBuf& ) = delete;
 	template <class T> T* as() const { return (T*)p; }
 };
+
+// hipcub's two calls: ask for the size of the temporary storage, allocate it, run.  Waits for the stream, since the storage is released on return
+template <class Call> int withCubTemp( hipStream_t st, Call call )
+{
+	size_t tmpBytes = 0;
+	MVRT_HIP( call( nullptr, tmpBytes ) );
+	DevBuf tmp;
+	if( tmp.alloc( tmpBytes ) ) return 1;
+	MVRT_HIP( call( tmp.p, tmpBytes ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	return 0;
+}

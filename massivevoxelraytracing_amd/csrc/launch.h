@@ -153,3 +153,21 @@ int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n
 int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, int flags,
 				   hipStream_t stream, SvoBuildResult* out, int* structural, uint32_t* hasEmissionOut );
 int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t stream );
+
+// surface extraction (kernels_surface.hip; mvrt_svo_surface_masks / _quads / _mesh): what it reads of a built octree.  cellBlocks == nullptr: no cell index,
+// neighbours are searched in the codes.  The calls block (the counts go back to the host), keep their scratch in DevBufs and write NOTHING to the caller's
+// arrays unless they succeed.
+struct SurfaceSource
+{
+	const uint64_t* morton; // sorted unique voxel codes
+	uint32_t nVoxels, levels;
+	const uint32_t* cellBlocks;
+	const uint2* cellEntries;
+	uint32_t cellBits;
+	f3 lower;
+	float dps;
+};
+int surfaceMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, hipStream_t stream );
+int surfaceQuads( const SurfaceSource& s, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut, hipStream_t stream );
+int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev,
+				 uint64_t* nFacesOut, uint64_t* nVerticesOut, hipStream_t stream );

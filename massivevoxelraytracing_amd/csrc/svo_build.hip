@@ -1105,18 +1105,6 @@ int gridFor( uint64_t n )
 	if( b < 1 ) b = 1;
 	return (int)( b > 4096 ? 4096 : b );
 }
-
-// hipcub's two calls: ask for the size of the temporary storage, allocate it, run.  Waits for the stream, since the storage is released on return
-template <class Call> int withCubTemp( hipStream_t st, Call call )
-{
-	size_t tmpBytes = 0;
-	MVRT_HIP( call( nullptr, tmpBytes ) );
-	DevBuf tmp;
-	if( tmp.alloc( tmpBytes ) ) return 1;
-	MVRT_HIP( call( tmp.p, tmpBytes ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
-	return 0;
-}
 } // namespace
 
 static int buildFromFragments( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""usage: tools/surface_bench.py [--scenes dragon,tunnel] [--reps 10] [--warmup 2] [--out profiles/surface_bench.json] [--no-host-method]
+
+Cost of extracting the voxel surface on the procedural stand-ins (dragon 2048^3, tunnel 4096^3):
+  masks   mvrt_svo_surface_masks into a device array (16 B read + 1 B written per voxel)
+  quads   mvrt_svo_surface_quads into device arrays (masks + scan + 53 B written per face)
+  mesh    mvrt_svo_surface_mesh into device arrays (masks + scan + corner keys + radix sort + ranks)
+Median of --reps calls after --warmup calls; host clock around each call (every call blocks until its counts are back).  Output arrays are allocated
+before the clock starts.  The achieved bytes per second of the whole masks and quads CALLS stand next to the 8 TB/s HBM peak; kernel times come from a
+kernel trace of its own (rocprofv3 --kernel-trace --stats -- python tools/surface_bench.py --reps 3 --no-host-method).
+Once, on the dragon: the only route without this feature -- mvrt_svo_read_voxels + the reference's host method (voxMesh.cpp:138-148: six searches per
+voxel in the sorted codes), here with numpy searchsorted on all cores numpy uses, masks only."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import massivevoxelraytracing_amd as mv  # noqa: E402
+from massivevoxelraytracing_amd import scenes  # noqa: E402
+
+GRID = {"dragon": 2048, "tunnel": 4096}
+HBM_PEAK = 8.0e12
+DIRS = ((1, -1), (1, +1), (2, -1), (0, +1), (2, +1), (0, -1))
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        mv.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), ts
+
+
+def morton(xyz):
+    m = np.zeros(len(xyz), np.uint64)
+    for b in range(21):
+        for axis in range(3):
+            m |= ((xyz[:, axis].astype(np.uint64) >> np.uint64(b)) & np.uint64(1)) << np.uint64(3 * b + axis)
+    return m
+
+
+def host_method(svo, res):
+    """read_voxels + six searches per voxel in the sorted codes -> (masks, seconds)"""
+    t0 = time.perf_counter()
+    xyz, _ = svo.read_voxels()
+    codes = morton(xyz)
+    out = np.zeros(len(xyz), np.uint8)
+    for d, (axis, step) in enumerate(DIRS):
+        p = xyz.astype(np.int64)
+        p[:, axis] += step
+        inside = (p[:, axis] >= 0) & (p[:, axis] < res)
+        want = morton(p[inside])
+        at = np.minimum(np.searchsorted(codes, want), len(codes) - 1)
+        present = np.zeros(len(xyz), bool)
+        present[inside] = codes[at] == want
+        out |= (~present).astype(np.uint8) << d
+    return out, time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="dragon,tunnel")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--no-host-method", action="store_true")
+    args = ap.parse_args()
+    mv.set_device(0)
+    rows = []
+
+    def emit(**kw):
+        rows.append(kw)
+        print(json.dumps(kw), flush=True)
+
+    for name in args.scenes.split(","):
+        res = GRID[name]
+        verts, cols, emis = scenes.SCENES[name](1.0)
+        origin, dps = scenes.bounding_grid(verts, res)
+        svo = mv.IntersectorOctreeGPU()
+        svo.build(verts, cols, emis, None, origin, dps, res)
+        n_vox = svo.info().numberOfVoxels
+        n_faces, n_vertices = svo.surface_mesh_device()
+        base = dict(scene=name, grid=res, voxels=n_vox, nFaces=n_faces, nVertices=n_vertices)
+        masks = mv.DeviceArray(n_vox, np.uint8)
+        ms, ts = timed(lambda: svo.surface_masks_device(masks), args.reps, args.warmup)
+        rate = n_vox * 17 / (ms * 1e-3)
+        emit(op="masks", ms=ms, all_ms=ts, bytes=n_vox * 17, bytes_per_s=rate, of_hbm_peak=rate / HBM_PEAK, **base)
+        fv, fd = mv.DeviceArray(n_faces, np.uint32), mv.DeviceArray(n_faces, np.uint8)
+        pos = mv.DeviceArray((n_faces, 12), np.float32)
+        ms, ts = timed(lambda: svo.surface_quads_device(n_faces, fv, fd, pos), args.reps, args.warmup)
+        rate = n_faces * 53 / (ms * 1e-3)
+        emit(op="quads", ms=ms, all_ms=ts, bytes=n_faces * 53, bytes_per_s=rate, of_hbm_peak=rate / HBM_PEAK, **base)
+        del pos
+        idx, vtx = mv.DeviceArray((n_faces, 4), np.uint32), mv.DeviceArray((n_vertices, 3), np.float32)
+        ms, ts = timed(lambda: svo.surface_mesh_device(n_faces, n_vertices, fv, fd, idx, vtx), args.reps, args.warmup)
+        emit(op="mesh", ms=ms, all_ms=ts, **base)
+        if name == "dragon" and not args.no_host_method:
+            got, s = host_method(svo, res)
+            emit(op="host_method_masks", ms=s * 1e3, equal_to_gpu=bool(np.array_equal(got, masks.to_host())), **base)
+        del svo
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+    for r in rows:
+        print("%-7s %5d %-18s %9d voxels %10d faces %9.2f ms" % (r["scene"], r["grid"], r["op"], r["voxels"], r["nFaces"], r["ms"]), file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()
