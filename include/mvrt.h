@@ -123,10 +123,10 @@ int mvrt_svo_build_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t
  * voxel: the LAST one in the batch wins.  Grid, origin, dps, build flags and emission scale are kept; the flavour is whatever a fresh build of the resulting voxel set picks.
  * A batch that only re-colours existing voxels keeps the nodes and writes the attributes in place; any insertion or removal rebuilds the levels.  Fails (handle
  * unchanged) on a coordinate outside the grid, an unknown op byte, or an edit that would remove every voxel.  Through mvrt_pt_intersector( pt ): the steps issued
- * before finish first and render the old scene; the frame buffer is not cleared. */
+ * before finish first and render the old scene; the frame buffer is not cleared.  An uploaded octree becomes editable after one mvrt_svo_rebuild. */
 int mvrt_svo_edit_voxels( mvrt_svo* svo, const uint32_t* xyzDev, const uint32_t* attribsDev, const uint8_t* opsDev, uint64_t n, void* stream );
 /* The current voxel set, sorted by Morton code (= vIndex order): coordinates (3 x uint32) and attributes (8 bytes) into caller device arrays of numberOfVoxels entries;
- * either may be NULL.  Octrees built by this library only. */
+ * either may be NULL.  Octrees built by this library only; for an upload call mvrt_svo_rebuild first, or list its voxels with mvrt_svo_walk_voxels. */
 int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attribsDev, void* stream );
 
 /* The exposed faces of the voxel set as a quad mesh: the reference voxelizer's "Save As Mesh" (voxMesh.cpp:111-219, voxelMeshWriter.hpp) on the GPU, from the
@@ -147,7 +147,8 @@ int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attri
  *     multiply and one fp32 add, each rounded, no FMA.  A DELIBERATE difference from the reference's (origin + x * dps) + dps, by an ulp in places: a corner
  *     shared by neighbouring voxels has ONE bit pattern, so the mesh is watertight and can be welded.
  *   - Welded mesh: a corner's key is (cz * (gridRes + 1) + cy) * (gridRes + 1) + cx (a uint64 up to gridRes 2^21); the vertices are the distinct keys of all face
- *     corners in ascending key order, indices[f][k] = the rank of the key of face f's corner k.  Refused on the host, naming the count, when 4 * nFaces >= 2^32. */
+ *     corners in ascending key order, indices[f][k] = the rank of the key of face f's corner k.  Refused on the host, naming the count, when 4 * nFaces >= 2^32.
+ * An uploaded octree gets its surface after one mvrt_svo_rebuild. */
 /* voxMesh.cpp:138-148 (the six neighbour tests).  masksDev: numberOfVoxels bytes, NULL = count only. */
 int mvrt_svo_surface_masks( const mvrt_svo* svo, uint8_t* masksDev, uint64_t* nFacesOut, void* stream );
 /* voxMesh.cpp:119-128,172-200 (one quad per exposed face, its corners not shared).  faceVoxelDev / faceDirDev: faceCapacity entries; positionsDev: 12 floats per face (4 corners x xyz). */
@@ -180,6 +181,33 @@ int mvrt_svo_upload( mvrt_svo* svo, const void* nodes68Host, uint32_t numberOfNo
 /* The rules above on host arrays alone (no HIP call, no handle): 0 when mvrt_svo_upload would accept them, else non-zero with mvrt_last_error set.
  * For applications that load octrees from files. */
 int mvrt_svo_check_upload( const void* nodes68Host, uint32_t numberOfNodes, uint32_t numberOfVoxels, int gridRes, int embeddedMask );
+
+/* Walk whatever octree the handle holds, uploaded or built, and list its voxels (new; an uploaded octree keeps no Morton codes, a walk from the root recovers
+ * them).  A path listing: one entry per root-to-voxel path, in ascending path order.  A path, three bits per level with the root's slot highest, is the voxel's
+ * Morton code; the paths of a DAG are distinct by construction, so there are no duplicates.  Per entry, into caller device arrays of `capacity` entries:
+ *   - xyzDev: 3 x uint32, decoded from the path like mvrt_svo_read_voxels does (x is bit 0 of each 3-bit group).
+ *   - vIndexDev: uint32, the stored nVoxelsPSum summed from the root to the voxel: exactly what mvrt_trace_batch reports for a hit on that voxel (upload rule 4
+ *     keeps it below numberOfVoxels).
+ *   - attribsDev: 8 bytes, the attribute buffer's entry vIndex, copied verbatim, alpha bytes included.
+ * Any output pointer may be NULL; all NULL is the sizing call (capacity is then ignored).  The call blocks like mvrt_svo_surface_quads: *nOut, a 64-bit path count,
+ * comes back to the host.  On an upload with non-canonical sums it can exceed numberOfVoxels; reachable inner nodes of mask 0 end their path and contribute
+ * nothing; the empty octree gives 0 and succeeds.  A capacity below the count is an error: the count is still returned and NOTHING is written to the caller's
+ * arrays.  Every flavour is accepted: a handle that keeps Morton codes (every octree this library built, the tree flavour among them) is answered from the codes
+ * with vIndex = the entry's number, every other one is walked; the bytes are the same either way.  A handle without an octree is refused ("no octree").  The
+ * handle is never modified; a failed allocation of scratch returns an error, leaves the octree whole and leaks nothing. */
+int mvrt_svo_walk_voxels( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* vIndexDev, uint32_t* attribsDev, uint64_t* nOut, void* stream );
+/* Make the handle's octree one this library built: walk it (above; a handle that keeps its codes: take its list as it is), bring the attributes into Morton
+ * order and build the levels again.  The result is the octree mvrt_svo_build_voxels would build from the walked list with these flags (MVRT_BUILD_NO_DAG |
+ * MVRT_BUILD_NO_EMBEDDED_MASK only): same nodes, same numbering, vIndex = Morton rank, cell index and prefix tables present -- after it mvrt_svo_read_voxels,
+ * mvrt_svo_edit_voxels and mvrt_svo_surface_* accept the handle.  Two things a voxel-list build would change are kept, so that the scene renders identically:
+ * the attribute bytes are copied verbatim (no alpha forcing), and hasEmission stays the handle's current flag (a later edit recomputes it, as documented
+ * there).  Grid, origin, dps and emission scale are kept; the build flags become `flags`; totalDumpedVoxels becomes the path count.  On a handle this library
+ * built, the call is a change of flavour (DAG to no DAG, embedded to plain or the tree flavour).
+ * Refused with the handle unchanged, before anything is replaced: a handle without an octree, an octree of 0 paths, more than 2^32 - 2 paths, unknown flags.
+ * A failed allocation before the new octree is adopted leaves the handle unchanged too (the new arrays are built next to the old octree, as by
+ * mvrt_svo_build_voxels); one after that leaves it empty (see mvrt_svo_destroy above).  Blocks like mvrt_svo_build.  Through mvrt_pt_intersector( pt ): the steps
+ * issued before finish first, as for an edit; the frame buffer is not cleared.  It invalidates every mvrt_device_octree view of the handle. */
+int mvrt_svo_rebuild( mvrt_svo* svo, int flags, void* stream );
 int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info );
 int mvrt_svo_set_emission_scale( mvrt_svo* svo, float scale ); /* m_emissionScale (:273) */
 /* bytes of the device structure the traversal and mvrt_svo_download work from (the reference's layout would be numberOfNodes * 68):
@@ -228,7 +256,7 @@ int mvrt_render_primary( const mvrt_svo* svo, const float camera[15], int width,
 /* Device view of an octree: the by-value IntersectorOctreeGPU a user kernel takes (IntersectorOctreeGPU.hpp:243-275), for the
  * per-thread traversal of include/mvrt/device.hpp (mvrt::DeviceOctree).  Fixed-width fields only; pointers are device addresses
  * stored as uint64_t.
- *   - The view is a SNAPSHOT of the handle: any later build (mvrt_svo_build_voxels included), mvrt_svo_edit_voxels, upload, cleanUp or
+ *   - The view is a SNAPSHOT of the handle: any later build (mvrt_svo_build_voxels included), mvrt_svo_edit_voxels, mvrt_svo_rebuild, upload, cleanUp or
  *     destroy of that handle invalidates it (its buffers are freed, replaced or rewritten, hasEmission may change), exactly like a copy of
  *     the reference's struct.  Take a new view after each of them.
  *   - emissionScale is copied from the handle; the caller may edit it in the copy it holds (getVoxelEmission( v, true ) uses it).

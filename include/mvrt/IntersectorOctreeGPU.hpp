@@ -125,6 +125,34 @@ struct IntersectorOctreeGPU
 		check( mvrt_memcpy_d2h( attribs.data(), a.p, attribs.size() * 4, stream ), "mvrt_memcpy_d2h" );
 	}
 
+	// the voxels of whatever octree this holds, uploaded or built, one per root-to-voxel path in ascending Morton order (mvrt_svo_walk_voxels; semantics in mvrt.h).
+	// Device-pointer form: any output may be nullptr, all nullptr = the sizing call; returns the count.  A capacity below the count aborts like any failure.
+	uint64_t walkVoxels( uint64_t capacity, uint32_t* xyzDev, uint32_t* vIndexDev, uint32_t* attribsDev, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_walk_voxels( m_handle, capacity, xyzDev, vIndexDev, attribsDev, &n, stream ), "IntersectorOctreeGPU::walkVoxels" );
+		return n;
+	}
+	// host-vector form: xyz = 3 entries per voxel, vIndex = 1, attribs = 2
+	void walkVoxels( std::vector<uint32_t>& xyz, std::vector<uint32_t>& vIndex, std::vector<uint32_t>& attribs, void* stream ) const
+	{
+		const uint64_t n = walkVoxels( 0, nullptr, nullptr, nullptr, stream );
+		xyz.resize( n * 3 );
+		vIndex.resize( n );
+		attribs.resize( n * 2 );
+		Staged x( nullptr, n * 12, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
+		if( n ) walkVoxels( n, (uint32_t*)x.p, (uint32_t*)v.p, (uint32_t*)a.p, stream );
+		fetch( xyz, x, stream );
+		fetch( vIndex, v, stream );
+		fetch( attribs, a, stream );
+	}
+	// an uploaded octree becomes one this library built (mvrt_svo_rebuild): readVoxels / editVoxels / surface* work afterwards.  Invalidates deviceView() snapshots.
+	void rebuild( int flags = 0, void* stream = nullptr )
+	{
+		check( mvrt_svo_rebuild( m_handle, flags, stream ), "IntersectorOctreeGPU::rebuild" );
+		refresh();
+	}
+
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const

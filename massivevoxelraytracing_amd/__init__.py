@@ -77,6 +77,8 @@ SIGNATURES = {
     "mvrt_svo_build_voxels": (_i32, [_vp, _vp, _vp, _u64, _vp, _f32, _i32, _i32, _vp]),
     "mvrt_svo_edit_voxels": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "mvrt_svo_read_voxels": (_i32, [_vp, _vp, _vp, _vp]),
+    "mvrt_svo_walk_voxels": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_rebuild": (_i32, [_vp, _i32, _vp]),
     "mvrt_svo_surface_masks": (_i32, [_vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_quads": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_mesh": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -358,6 +360,27 @@ class IntersectorOctreeGPU:
         xyz, at = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8)
         _check(lib().mvrt_svo_read_voxels(self._h, xyz.ptr, at.ptr, stream))
         return xyz.to_host(), at.to_host()
+
+    def walk_voxels_device(self, capacity=0, xyz=None, vIndex=None, attribs=None, stream=None):
+        """mvrt_svo_walk_voxels into caller device arrays of `capacity` entries (any may be None; all None = the sizing call); returns the path count.
+        On MvrtError nothing was written."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_walk_voxels(self._h, int(capacity), _dev_ptr(xyz), _dev_ptr(vIndex), _dev_ptr(attribs), C.byref(n), stream))
+        return n.value
+
+    def walk_voxels(self, stream=None):
+        """the voxels of whatever octree the handle holds, uploaded or built, one per root-to-voxel path in ascending path (Morton) order:
+        {xyz (n, 3) uint32, vIndex (n,) uint32 = what a trace reports for the voxel, attribs (n, 8) uint8 = the attribute of that vIndex}"""
+        n = self.walk_voxels_device(stream=stream)
+        xyz, vi, at = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
+        if n:
+            self.walk_voxels_device(n, xyz, vi, at, stream)
+        return {"xyz": xyz.to_host(), "vIndex": vi.to_host(), "attribs": at.to_host()}
+
+    def rebuild(self, flags=0, stream=None):
+        """mvrt_svo_rebuild: the octree becomes the one build_voxels would build from its walked voxels (attribute bytes and hasEmission kept), after which
+        read_voxels / edit_voxels / surface_* accept an upload.  flags: BUILD_NO_DAG | BUILD_NO_EMBEDDED_MASK.  Invalidates device_view() snapshots."""
+        _check(lib().mvrt_svo_rebuild(self._h, int(flags), stream))
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""

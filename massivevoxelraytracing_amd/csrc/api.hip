@@ -161,7 +161,7 @@ struct Octree
 	uint32_t tree = 0, treeRoot = 0, nBricks = 0;
 	uint32_t treeLevelBase[24] = { 0 }, treeLevelCount[24] = { 0 };
 	DevBuf attrs;
-	DevBuf morton;	 // only after build()
+	DevBuf morton;	 // only after build() (an upload gets them by mvrt_svo_rebuild)
 	DevBuf kids;	 // embedded flavour: children[8] per node, 32 B per node (what the traversal reads)
 	DevBuf topTable; // per-prefix start of the nVoxelsPSum walk (SvoDev::topTable), embedded flavour
 	uint32_t topLevels = 0;
@@ -531,6 +531,83 @@ MVRT_EXPORT int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uin
 	REQUIRE( !svo->empty(), "mvrt_svo_read_voxels: no octree (build first)" );
 	REQUIRE( svo->oct.morton.p, "mvrt_svo_read_voxels: an uploaded octree keeps no Morton codes" );
 	return svoReadVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.info.numberOfVoxels, xyzDev, attribsDev, (hipStream_t)stream );
+}
+
+// The voxels of whatever the handle holds (kernels_walk.hip).  A handle that keeps Morton codes is answered from them (entry i is voxel i: the tree flavour
+// has nothing else to walk); every other octree is walked from the root.  Both give the same bytes.  The caller's arrays are written by the last launch alone,
+// behind every allocation and check.
+static WalkSource walkSource( const Octree& o )
+{
+	WalkSource s;
+	s.nodes = o.nodes.as<Node64>();
+	s.masks = o.masks.as<uint8_t>();
+	s.psumCold = o.psumCold.as<uint32_t>();
+	s.nNodes = o.info.numberOfNodes;
+	s.levels = o.info.levels;
+	s.embedded = o.info.embeddedMask;
+	s.rootMask = o.rootMask;
+	return s;
+}
+MVRT_EXPORT int mvrt_svo_walk_voxels( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* vIndexDev, uint32_t* attribsDev, uint64_t* nOut, void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_walk_voxels: null handle" );
+	REQUIRE( !svo->empty(), "mvrt_svo_walk_voxels: no octree (build or upload first)" );
+	const Octree& o = svo->oct;
+	hipStream_t st = (hipStream_t)stream;
+	const bool fill = xyzDev || vIndexDev || attribsDev;
+	WalkResult w;
+	if( o.morton.p ) w.n = o.info.numberOfVoxels;
+	else if( walkPaths( walkSource( o ), fill, capacity, &w, st ) ) return 1;
+	if( nOut ) *nOut = w.n;
+	if( !fill ) return 0; // the sizing call
+	REQUIRE( capacity >= w.n, "mvrt_svo_walk_voxels: capacity %llu is smaller than the %llu voxels of the octree; nothing was written", (unsigned long long)capacity,
+			 (unsigned long long)w.n );
+	if( w.n == 0 ) return 0;
+	if( launchWalkGather( o.morton.p ? o.morton.as<uint64_t>() : w.codes.as<uint64_t>(), o.morton.p ? nullptr : w.vIndex.as<uint32_t>(), o.attrs.as<uint2>(), o.info.numberOfVoxels,
+						  w.n, xyzDev, vIndexDev, attribsDev, st ) )
+		return 1;
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	return 0;
+}
+// The handle's octree becomes the one mvrt_svo_build_voxels would build from its walked voxels.  Refusals come first, the new arrays are built next to the old
+// octree: every failure up to adoptBuild leaves the handle as it was (adoptBuild itself: see there).
+MVRT_EXPORT int mvrt_svo_rebuild( mvrt_svo* svo, int flags, void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_rebuild: null handle" );
+	REQUIRE( !svo->empty(), "mvrt_svo_rebuild: no octree (build or upload first)" );
+	REQUIRE( ( flags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0, "mvrt_svo_rebuild: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)",
+			 flags );
+	hipStream_t st = (hipStream_t)stream;
+	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
+	const Octree& o = svo->oct;
+	const mvrt_svo_info info = o.info;
+	DevBuf morton, attrs;
+	uint64_t n = 0;
+	if( o.morton.p ) // a flavour change of a built octree: its list as it is
+	{
+		n = info.numberOfVoxels;
+		if( morton.alloc( n * 8 ) || attrs.alloc( n * 8 ) ) return 1;
+		MVRT_HIP( hipMemcpyAsync( morton.p, o.morton.p, n * 8, hipMemcpyDeviceToDevice, st ) );
+		MVRT_HIP( hipMemcpyAsync( attrs.p, o.attrs.p, n * 8, hipMemcpyDeviceToDevice, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+	}
+	else
+	{
+		WalkResult w;
+		if( walkPaths( walkSource( o ), true, 0xFFFFFFFEull, &w, st ) ) return 1;
+		n = w.n;
+		REQUIRE( n >= 1, "mvrt_svo_rebuild: the octree holds no voxel" );
+		REQUIRE( n < 0xFFFFFFFFull, "mvrt_svo_rebuild: %llu voxels exceed the 32-bit index range of the builder", (unsigned long long)n );
+		if( attrs.alloc( n * 8 ) ) return 1;
+		if( launchWalkGather( w.codes.as<uint64_t>(), w.vIndex.as<uint32_t>(), o.attrs.as<uint2>(), info.numberOfVoxels, n, nullptr, nullptr, attrs.as<uint32_t>(), st ) ) return 1;
+		MVRT_HIP( hipStreamSynchronize( st ) ); // (the vIndex array is released at scope end)
+		morton = std::move( w.codes );
+	}
+	SvoBuildResult r;
+	if( svoBuildFromSorted( morton, attrs, (uint32_t)n, (int)info.gridRes, flags, st, &r ) ) return 1;
+	r.hasEmission = info.hasEmission; // the handle's flag, not recomputed: the scene renders as before
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	return adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, flags ); // (arguments are read before the old octree goes)
 }
 
 // Surface extraction (kernels_surface.hip).  Only the sorted codes and, where there is one, the cell index are read: every flavour is accepted and the

@@ -1,0 +1,222 @@
+// kernels_walk.hip -- the voxels of an octree that keeps no Morton codes (an upload), recovered by walking it (mvrt_svo_walk_voxels / mvrt_svo_rebuild, mvrt.h).
+//
+// A root-to-voxel path, three bits per level with the root's slot highest, IS the voxel's Morton code, and the nVoxelsPSum values along it add up to the
+// vIndex the traversal reports (device.hpp: voxelIndexFromPath).  The walk is breadth first, one level per pass, over a FRONTIER of paths: per entry the node
+// word (embedded flavour: index | mask << 24 as the parent stores it; plain flavour: the index), the running nVoxelsPSum sum and the path prefix, three arrays.
+//
+//   count   children of entry i = popcount of its mask: the top byte of the word (embedded) or masks[node] (plain).  Not a kernel: the input iterator of
+//   scan    a 64-bit exclusive sum (rocPRIM) over n + 1 items, the last one 0, so that offs[n] is the size of the next frontier.  It goes to the host.
+//   emit    one workgroup per 256 parents, one thread per CHILD: the children of a group are one contiguous run of the next frontier, every thread takes
+//           entries of the run, finds its parent in the group's offsets (LDS, 8 steps) and its slot as the k-th set bit of the parent's mask, and reads
+//           children[c] and nVoxelsPSum[c] from the parent's 64-byte line.  Siblings are neighbouring lanes on one line; a wave writes 64 consecutive
+//           entries of each array.  The last level writes (code, vIndex) instead of a frontier entry.
+//   gather  code -> xyz (x = bit 0 of each 3-bit group, as kReadVoxels), attribs = attrs[vIndex] verbatim.
+//
+// Paths come out in ascending order: parents are in ascending prefix order and the children of one parent in ascending slot order.  A DAG is walked per PATH,
+// shared nodes once per path that reaches them, so the count is the number of voxels, not of nodes.  Reachable nodes of mask 0 have no children: their path ends.
+// What the walk relies on is the upload contract (mvrt.h rules 2-4, checked on the host before an upload is accepted) or the builder: child words below
+// numberOfNodes, voxels in the last level only, sums below numberOfVoxels.  A word that names no node is still read as a node of mask 0, and an index past the
+// attributes as zero attributes: nothing here reads out of bounds whatever the nodes hold.
+#include <hipcub/hipcub.hpp>
+
+#include "launch.h"
+
+#define WB 256 // threads per workgroup, and parents per workgroup of the emit kernel
+
+namespace
+{
+MVRT_HDI uint32_t popcount8( uint32_t v )
+{
+	v = ( v & 0x55u ) + ( ( v >> 1 ) & 0x55u );
+	v = ( v & 0x33u ) + ( ( v >> 2 ) & 0x33u );
+	return ( v & 0x0Fu ) + ( v >> 4 );
+}
+// own mask of the node a frontier word names.  masks == nullptr: embedded flavour, the word carries it
+MVRT_HDI uint32_t wordMask( uint32_t w, const uint8_t* __restrict__ masks, uint32_t nNodes )
+{
+	if( masks ) return w < nNodes ? (uint32_t)masks[w] : 0u;
+	return ( w & 0xFFFFFFu ) < nNodes ? w >> 24 : 0u;
+}
+struct ChildCount // scan input: children of frontier entry i; item n is the 0 behind the last entry
+{
+	const uint32_t* word;
+	const uint8_t* masks;
+	uint32_t nNodes;
+	uint64_t n;
+	__host__ __device__ uint64_t operator()( uint64_t i ) const { return i < n ? popcount8( wordMask( word[i], masks, nNodes ) ) : 0ull; }
+};
+
+// One workgroup per WB parents.  offs: nParents + 1 exclusive offsets.  The group's children are the run [offs[first], offs[end]) of the output; thread t takes
+// entries t, t + WB, ... of the run (at most 8 * WB).  LAST: the children are voxels -> cPrefix = the Morton code, cSum = the vIndex, cWord is not written.
+template <bool EMB, bool LAST>
+__global__ void __launch_bounds__( WB ) kWalkEmit( const Node64* __restrict__ nodes, const uint8_t* __restrict__ masks, const uint32_t* __restrict__ psumCold, uint32_t nNodes,
+												   const uint32_t* __restrict__ pWord, const uint32_t* __restrict__ pSum, const uint64_t* __restrict__ pPrefix,
+												   const uint64_t* __restrict__ offs, uint64_t nParents, uint32_t* __restrict__ cWord, uint32_t* __restrict__ cSum,
+												   uint64_t* __restrict__ cPrefix )
+{
+	__shared__ uint32_t sOff[WB + 1];
+	__shared__ uint32_t sWord[WB];
+	__shared__ uint32_t sSum[WB];
+	__shared__ uint64_t sPrefix[WB];
+	__shared__ uint8_t sMask[WB];
+	const uint64_t first = (uint64_t)blockIdx.x * WB;
+	const uint64_t p = first + threadIdx.x;
+	const bool in = p < nParents;
+	const uint64_t base = offs[first];
+	sOff[threadIdx.x] = (uint32_t)( offs[in ? p : nParents] - base ); // <= 8 * WB
+	if( threadIdx.x == 0 ) sOff[WB] = (uint32_t)( offs[first + WB < nParents ? first + WB : nParents] - base );
+	const uint32_t w = in ? pWord[p] : 0u;
+	sWord[threadIdx.x] = w;
+	sMask[threadIdx.x] = in ? (uint8_t)wordMask( w, EMB ? nullptr : masks, nNodes ) : (uint8_t)0;
+	sSum[threadIdx.x] = in ? pSum[p] : 0u;
+	sPrefix[threadIdx.x] = in ? pPrefix[p] : 0ull;
+	__syncthreads();
+	const uint32_t total = sOff[WB];
+	for( uint32_t j = threadIdx.x; j < total; j += WB )
+	{
+		// the last parent of the group whose offset is <= j: parents without children repeat the offset of the next one and are passed over
+		uint32_t lo = 0, hi = WB;
+		while( hi - lo > 1 )
+		{
+			const uint32_t mid = ( lo + hi ) >> 1;
+			if( sOff[mid] <= j ) lo = mid;
+			else hi = mid;
+		}
+		uint32_t m = sMask[lo];
+		for( uint32_t r = j - sOff[lo]; r > 0; r-- ) m &= m - 1u; // the ( j - offset )-th set bit
+		const uint32_t c = (uint32_t)__ffs( (int)m ) - 1u;
+		const uint32_t node = EMB ? sWord[lo] & 0xFFFFFFu : sWord[lo]; // (a parent with children has a mask, so it is below nNodes: wordMask)
+		const Node64& line = nodes[node];
+		const uint32_t ps = EMB ? line.psum[c] : psumCold[(uint64_t)node * 8u + c];
+		const uint64_t out = base + j;
+		if( !LAST ) cWord[out] = line.children[c];
+		cSum[out] = sSum[lo] + ps;
+		cPrefix[out] = ( sPrefix[lo] << 3 ) | c;
+	}
+}
+
+MVRT_DI uint32_t compact3( uint64_t x )
+{
+	x &= 0x1249249249249249ull;
+	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
+	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
+	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
+	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
+	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
+	return (uint32_t)x;
+}
+// vIndex == nullptr: the codes are the sorted list of a build and entry i is voxel i.  Any output may be null.
+__global__ void __launch_bounds__( WB ) kWalkGather( const uint64_t* __restrict__ codes, const uint32_t* __restrict__ vIndex, const uint2* __restrict__ attrs, uint32_t nVoxels,
+													 uint64_t n, uint32_t* __restrict__ xyz, uint32_t* __restrict__ vIndexOut, uint32_t* __restrict__ attribs )
+{
+	for( uint64_t i = (uint64_t)blockIdx.x * WB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * WB )
+	{
+		const uint32_t v = vIndex ? vIndex[i] : (uint32_t)i;
+		if( xyz )
+		{
+			const uint64_t m = codes[i];
+			xyz[i * 3] = compact3( m );
+			xyz[i * 3 + 1] = compact3( m >> 1 );
+			xyz[i * 3 + 2] = compact3( m >> 2 );
+		}
+		if( vIndexOut ) vIndexOut[i] = v;
+		if( attribs )
+		{
+			const uint2 a = v < nVoxels ? attrs[v] : make_uint2( 0u, 0u );
+			attribs[i * 2] = a.x;
+			attribs[i * 2 + 1] = a.y;
+		}
+	}
+}
+
+struct Frontier
+{
+	DevBuf word, sum, prefix;
+	int alloc( uint64_t n ) { return word.alloc( n * 4 ) || sum.alloc( n * 4 ) || prefix.alloc( n * 8 ); }
+};
+
+template <bool EMB, bool LAST>
+void launchEmit( const WalkSource& s, const Frontier& par, const uint64_t* offs, uint64_t nParents, uint32_t* cWord, uint32_t* cSum, uint64_t* cPrefix, hipStream_t st )
+{
+	hipLaunchKernelGGL( ( kWalkEmit<EMB, LAST> ), dim3( divUp( nParents, WB ) ), dim3( WB ), 0, st, s.nodes, s.masks, s.psumCold, s.nNodes, par.word.as<uint32_t>(),
+						par.sum.as<uint32_t>(), par.prefix.as<uint64_t>(), offs, nParents, cWord, cSum, cPrefix );
+}
+} // namespace
+
+int launchWalkGather( const uint64_t* codes, const uint32_t* vIndex, const uint2* attrs, uint32_t nVoxels, uint64_t n, uint32_t* xyz, uint32_t* vIndexOut, uint32_t* attribs,
+					  hipStream_t st )
+{
+	if( n == 0 ) return 0;
+	const uint64_t blocks = ( n + WB - 1 ) / WB;
+	hipLaunchKernelGGL( kWalkGather, dim3( (uint32_t)( blocks > 65536 ? 65536 : blocks ) ), dim3( WB ), 0, st, codes, vIndex, attrs, nVoxels, n, xyz, vIndexOut, attribs );
+	MVRT_HIP( hipGetLastError() );
+	return 0;
+}
+
+// One host synchronisation that waits per level (the size of the next frontier), one more behind the last emit.  Every buffer is a DevBuf of this call: a failed
+// allocation returns an error and leaks nothing.  The buffers alternate between two sets, so what a level allocates over was last read two levels earlier, by
+// launches the previous level's synchronisation has already seen finish.
+int walkPaths( const WalkSource& s, bool fill, uint64_t fillLimit, WalkResult* out, hipStream_t st )
+{
+	out->n = 0;
+	out->filled = 0;
+	if( s.levels == 0 || s.nNodes == 0 ) return 0;
+	Frontier fr[2];
+	DevBuf offs[2];
+	struct SyncOnExit // declared behind the buffers, so it runs before they go: an error return never frees what a launch in flight still reads
+	{
+		hipStream_t st;
+		~SyncOnExit() { (void)hipStreamSynchronize( st ); }
+	} syncOnExit{ st };
+	if( fr[0].alloc( 1 ) ) return 1;
+	const uint32_t rootWord = ( s.nNodes - 1u ) | ( s.embedded ? s.rootMask << 24 : 0u );
+	MVRT_HIP( hipMemcpyAsync( fr[0].word.p, &rootWord, 4, hipMemcpyHostToDevice, st ) ); // (rootWord outlives the first synchronisation below)
+	MVRT_HIP( hipMemsetAsync( fr[0].sum.p, 0, 4, st ) );
+	MVRT_HIP( hipMemsetAsync( fr[0].prefix.p, 0, 8, st ) );
+	uint64_t n = 1;
+	for( uint32_t d = 0; d < s.levels; d++ )
+	{
+		const Frontier& par = fr[d & 1u];
+		Frontier& kid = fr[( d + 1u ) & 1u];
+		DevBuf& off = offs[d & 1u];
+		const bool last = d + 1u == s.levels;
+		if( off.alloc( ( n + 1 ) * 8 ) ) return 1;
+		unsigned long long total = 0;
+		{
+			hipcub::CountingInputIterator<uint64_t> counting( 0ull );
+			hipcub::TransformInputIterator<uint64_t, ChildCount, hipcub::CountingInputIterator<uint64_t>> in(
+				counting, ChildCount{ par.word.as<uint32_t>(), s.embedded ? nullptr : s.masks, s.nNodes, n } );
+			size_t tmpBytes = 0;
+			MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( nullptr, tmpBytes, in, off.as<uint64_t>(), n + 1, st ) );
+			DevBuf tmp;
+			if( tmp.alloc( tmpBytes ) ) return 1;
+			MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( tmp.p, tmpBytes, in, off.as<uint64_t>(), n + 1, st ) );
+			MVRT_HIP( hipMemcpyAsync( &total, off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st ) );
+			MVRT_HIP( hipStreamSynchronize( st ) ); // (tmp is released at scope end)
+		}
+		if( last ) out->n = total;
+		if( total == 0 ) return 0; // every path ended in a node of mask 0 (the empty octree: the root)
+		if( last && ( !fill || total > fillLimit ) ) return 0;
+		if( ( n + WB - 1 ) / WB > 0x7FFFFFFFull )
+		{
+			mvrtSetError( "octree walk: a frontier of %llu paths is beyond one launch", (unsigned long long)n );
+			return 1;
+		}
+		if( last )
+		{
+			if( out->codes.alloc( total * 8 ) || out->vIndex.alloc( total * 4 ) ) return 1;
+			if( s.embedded ) launchEmit<true, true>( s, par, off.as<uint64_t>(), n, nullptr, out->vIndex.as<uint32_t>(), out->codes.as<uint64_t>(), st );
+			else launchEmit<false, true>( s, par, off.as<uint64_t>(), n, nullptr, out->vIndex.as<uint32_t>(), out->codes.as<uint64_t>(), st );
+			MVRT_HIP( hipGetLastError() );
+			MVRT_HIP( hipStreamSynchronize( st ) ); // (the frontier and the offsets are released on return)
+			out->filled = 1;
+			return 0;
+		}
+		if( kid.alloc( total ) ) return 1;
+		if( s.embedded ) launchEmit<true, false>( s, par, off.as<uint64_t>(), n, kid.word.as<uint32_t>(), kid.sum.as<uint32_t>(), kid.prefix.as<uint64_t>(), st );
+		else launchEmit<false, false>( s, par, off.as<uint64_t>(), n, kid.word.as<uint32_t>(), kid.sum.as<uint32_t>(), kid.prefix.as<uint64_t>(), st );
+		MVRT_HIP( hipGetLastError() );
+		n = total;
+	}
+	return 0;
+}

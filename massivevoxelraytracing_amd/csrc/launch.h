@@ -153,6 +153,9 @@ int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n
 int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, int flags,
 				   hipStream_t stream, SvoBuildResult* out, int* structural, uint32_t* hasEmissionOut );
 int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t stream );
+// the levels over n sorted unique codes and their attributes (both handed to *out on success), as svoBuildFromVoxels builds them behind its sort: the attribute
+// bytes are kept verbatim and out->hasEmission is 0 -- the caller knows the flag of the set it hands in (mvrt_svo_rebuild)
+int svoBuildFromSorted( DevBuf& morton, DevBuf& attrs, uint32_t n, int gridRes, int flags, hipStream_t stream, SvoBuildResult* out );
 
 // surface extraction (kernels_surface.hip; mvrt_svo_surface_masks / _quads / _mesh): what it reads of a built octree.  cellBlocks == nullptr: no cell index,
 // neighbours are searched in the codes.  The calls block (the counts go back to the host), keep their scratch in DevBufs and write NOTHING to the caller's
@@ -171,3 +174,24 @@ int surfaceMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut
 int surfaceQuads( const SurfaceSource& s, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut, hipStream_t stream );
 int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev,
 				 uint64_t* nFacesOut, uint64_t* nVerticesOut, hipStream_t stream );
+
+// octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
+// flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.
+struct WalkSource
+{
+	const Node64* nodes;
+	const uint8_t* masks;	  // per-node own mask (read in the plain flavour)
+	const uint32_t* psumCold; // plain flavour: nVoxelsPSum[node * 8 + child]
+	uint32_t nNodes, levels, embedded, rootMask;
+};
+struct WalkResult
+{
+	DevBuf codes, vIndex; // per path, ascending: the Morton code (uint64) and the nVoxelsPSum sum (uint32)
+	uint64_t n = 0;		  // paths, whether or not the arrays were filled
+	int filled = 0;
+};
+// counts the root-to-voxel paths; fill && n <= fillLimit: also lists them (n == 0: nothing to list, filled stays 0)
+int walkPaths( const WalkSource& s, bool fill, uint64_t fillLimit, WalkResult* out, hipStream_t stream );
+// per entry i < n: xyz = the decoded code, vIndexOut = v, attribs = attrs[v] with v = vIndex[i] (vIndex == nullptr: v = i); any output may be null.  Not synchronised.
+int launchWalkGather( const uint64_t* codes, const uint32_t* vIndex, const uint2* attrs, uint32_t nVoxels, uint64_t n, uint32_t* xyz, uint32_t* vIndexOut, uint32_t* attribs,
+					  hipStream_t stream );

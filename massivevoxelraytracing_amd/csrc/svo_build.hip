@@ -1505,6 +1505,13 @@ int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n
 	return buildFromFragments( keysA, valsA, n, gridRes, flags, st, sc.base(), sc.hasEmission(), sc.scalarOut(), out );
 }
 
+int svoBuildFromSorted( DevBuf& morton, DevBuf& attrs, uint32_t n, int gridRes, int flags, hipStream_t st, SvoBuildResult* out )
+{
+	ListScratch sc;
+	if( sc.init( st ) ) return 1;
+	return buildLevels( morton, attrs, n, n, gridRes, flags, st, sc.hasEmission(), sc.scalarOut(), out );
+}
+
 int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, int flags,
 				   hipStream_t st, SvoBuildResult* out, int* structural, uint32_t* hasEmissionOut )
 {

@@ -1,0 +1,109 @@
+"""The model of the octree walk (tests/walk_expected.py) against things already trusted, without a GPU: the builder's Morton codes and ranks, the
+upload-shape generators (tests/upload_shapes.py) whose effect on paths and sums is known, and the oracle's traversal, whose hit vIndex is the sum the
+walk must report.  Also compiles the C++ mirror's usage program (run on a GPU by tests/test_gpu_walk.py)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import deep_scenes as D
+import upload_shapes as U
+import walk_expected as W
+from test_gpu_upload_shapes import oracle_scene, shapes, voxel_set
+
+import massivevoxelraytracing_amd as mv
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MAXF = np.float32(3.402823466e38)
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import oracle
+    return oracle
+
+
+@pytest.fixture(scope="module")
+def random7():
+    return voxel_set("random7", 7, 20_000, 2_000, 7)
+
+
+@pytest.mark.parametrize("levels", [1, 2, 3, 4])
+def test_builder_octrees_of_few_levels(O, levels):
+    rng = np.random.default_rng(levels)
+    for dag in (True, False):
+        for emb in (True, False):
+            for _ in range(5):
+                nodes, n, res, _ = U.small_octree(O, rng, levels, dag, emb)
+                paths, vi, xyz = W.walk(nodes, res, emb)
+                assert np.array_equal(paths, U.voxel_paths(nodes, res, emb)) and len(paths) == n
+                assert np.array_equal(vi, np.arange(n))  # the builder's sums: vIndex = Morton rank
+                assert np.array_equal(D.morton(xyz), paths)
+
+
+@pytest.mark.parametrize("emb", [True, False])
+def test_generated_shapes_of_random7(O, random7, emb):
+    base = random7
+    n = len(base.morton)
+    s = shapes(O, base, emb, 17)
+    for name in ("builder", "permute", "unreachable", "unshare"):
+        paths, vi, xyz = W.walk(s[name][0], base.res, emb)
+        assert np.array_equal(paths, base.morton), name
+        assert np.array_equal(vi, np.arange(n)), name
+        assert np.array_equal(xyz, D.decode(base.morton)), name
+    paths, vi, _ = W.walk(s["psum_zero"][0], base.res, emb)
+    assert np.array_equal(paths, base.morton) and not vi.any()
+    for name in ("empty_inner", "all", "psum_random", "psum_one_off"):  # dead branches add nothing; other sums move no path
+        assert np.array_equal(W.walk(s[name][0], base.res, emb)[0], base.morton), name
+    vi = W.walk(s["psum_one_off"][0], base.res, emb)[1]
+    off = vi.astype(np.int64) - np.arange(n)  # one slot of one node is a sum lower by one: every path through that (shared) node, no other
+    assert (off == -1).sum() >= 1 and ((off == 0) | (off == -1)).all()
+    assert W.walk(shapes(O, None, emb, 0)["empty"][0], 4, emb)[0].size == 0
+
+
+def rays_at_voxels(base, paths, n, seed):
+    """rays from 3 to 10 voxels away towards the centre of n sampled voxels"""
+    rng = np.random.default_rng(seed)
+    centre = D.decode(paths[rng.integers(0, len(paths), n)]).astype(np.float64) + 0.5
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    start = centre + u * (3.0 + 7.0 * rng.random((n, 1)))
+    ro = (base.origin.astype(np.float64) + start * float(base.dps)).astype(np.float32)
+    rd = ((centre - start) * float(base.dps)).astype(np.float32)
+    return ro, rd
+
+
+@pytest.mark.parametrize("emb", [True, False])
+@pytest.mark.parametrize("shape", ["builder", "psum_random", "all"])
+def test_vindex_is_what_the_oracle_reports_for_a_hit(O, random7, shape, emb):
+    """200 rays aimed at sampled voxels.  (Not started inside them: the reference's traversal does not report the voxel a ray starts in.)  The voxel a ray
+    hits is found from the hit point, a thousandth of a voxel further along the ray; the oracle's vIndex for it is the walk's sum along that voxel's path."""
+    base = random7
+    nodes = shapes(O, base, emb, 23)[shape][0]
+    paths, vi, _ = W.walk(nodes, base.res, emb)
+    ro, rd = rays_at_voxels(base, paths, 200, 5)
+    hit = oracle_scene(O, base, nodes, emb).trace(ro, rd, None, threads=4)
+    assert (hit["t"] != MAXF).all()
+    d = rd.astype(np.float64)
+    p = ro.astype(np.float64) + d * hit["t"].astype(np.float64)[:, None] + d / np.linalg.norm(d, axis=1, keepdims=True) * 1e-3 * float(base.dps)
+    code = D.morton(np.floor((p - base.origin.astype(np.float64)) / float(base.dps)).astype(np.int64))
+    i = np.searchsorted(paths, code)
+    assert np.array_equal(paths[i], code)  # every hit point lies in a voxel of the set
+    assert np.array_equal(hit["vIndex"], vi[i])
+    assert len(np.unique(hit["vIndex"])) > 100  # many different voxels, and with psum_random sums that are no ranks
+    assert shape != "psum_random" or (vi[i] != i).sum() > 100
+
+
+def test_cpp_mirror_walk_methods_compile_and_link(tmp_path):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "walk_usage"
+    libdir = os.path.dirname(mv.LIB_PATH)
+    cmd = [gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "walk_usage.cpp"), "-o", str(exe),
+           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"]
+    subprocess.check_call(cmd)
+    out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
+    assert b"usage" in out
