@@ -157,6 +157,35 @@ int mvrt_svo_surface_quads( const mvrt_svo* svo, uint64_t faceCapacity, uint32_t
 /* The same faces over SHARED vertices (the reference writes eight points per voxel, voxMesh.cpp:113-129,204-218; welding is new).  indicesDev: 4 per face; verticesDev: 3 floats per vertex, vertexCapacity vertices. */
 int mvrt_svo_surface_mesh( const mvrt_svo* svo, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
 						   float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream );
+/* The same surface with coplanar faces merged into rectangles (new; the reference has no counterpart).  The rules of the three calls above hold word for word:
+ * the accepted handles and the two refusals before any GPU work (unknown flag bits are refused there too), a handle that is never modified, a blocking call, any
+ * output NULL, all NULL = the sizing call, a capacity below the count = counts returned and NOTHING written, scratch that leaks nothing.  gridRes up to 2^21.
+ *   - Faces: exactly those of mvrt_svo_surface_masks, directions d = 0..5 as there.  A face with normal axis a lies in plane p = the voxel's coordinate on a and has
+ *     the in-plane coordinates (u, v) = the voxel's coordinates on the two other axes, the lower-numbered axis being u: x -> (y, z), y -> (x, z), z -> (x, y).
+ *   - Two faces are mergeable when they have the same d and p and their voxels' attribute entries are equal in all 8 bytes (colour, emission, both alpha bytes);
+ *     with MVRT_SURFACE_MERGE_ANY_ATTRIBUTE the attributes are not looked at.
+ *   - Step 1, rows: within one (d, p, v) a run is a maximal sequence of faces at consecutive u, each mergeable with its predecessor: (d, p, v, u0, du).
+ *   - Step 2, stacks: among the runs with the same (d, p, u0, du) and the same attribute (any attribute with the flag) a rectangle is a maximal sequence at
+ *     consecutive v: (d, p, u0, v0, du, dv).
+ *     Both steps take the maximal chains of a relation between neighbours, so the result is unique and independent of any processing order.  It is deliberately
+ *     NOT a greedy merge: an L-shaped region gives two rectangles, a staircase one per row.
+ *   - Order: ascending (d, p, u0, v0); the anchor face at (u0, v0) belongs to exactly one rectangle, so the order is total.
+ *   - Per rectangle: rectVoxel = the vIndex of the anchor face's voxel (it indexes the attribute buffer like faceVoxel), rectDir = d, rectSize = 2 x uint32
+ *     (du, dv), positions = 12 floats, the four corners.  Corner k has the integer grid coordinate: the anchor voxel's coordinate plus the corner offset of face d's
+ *     corner k (the tables above), the offset scaled by du on the u axis, by dv on the v axis and by 1 on the normal axis; its position is lower + (float)c * dps
+ *     as above -- for a 1 x 1 rectangle the bits and the winding of mvrt_svo_surface_quads.
+ *   - With MVRT_SURFACE_MERGE_WELD the corners are welded exactly as in mvrt_svo_surface_mesh: the same key, vertices = the distinct keys ascending,
+ *     indices[r][k] = the rank of the key of rectangle r's corner k.  A welded MERGED mesh has T-junctions: the edge of a rectangle can pass through a corner of
+ *     its neighbour without having a vertex there.  Refused on the host, naming the count, when 4 * nRects >= 2^32.  Without the flag non-NULL indicesDev or
+ *     verticesDev is refused on the host and *nVerticesOut is 0.
+ *   - For every input the sum of du * dv equals the nFaces of mvrt_svo_surface_masks, and the rectangles cover exactly the faces of mvrt_svo_surface_quads, none twice.
+ * rectVoxelDev / rectDirDev: rectCapacity entries; rectSizeDev: 2 per rectangle; positionsDev: 12 floats per rectangle; indicesDev: 4 per rectangle; verticesDev: 3
+ * floats per vertex, vertexCapacity vertices. */
+#define MVRT_SURFACE_MERGE_ANY_ATTRIBUTE 1u
+#define MVRT_SURFACE_MERGE_WELD 2u
+int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev,
+							 uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut,
+							 uint64_t* nVerticesOut, void* stream );
 
 /* Adopt an SVO built elsewhere (e.g. IntersectorOctree::buildDAGReference on the CPU, IntersectorOctree.hpp:
  * 224-231): nodes in the reference's 68-byte layout, root last.  embeddedMask = 0 selects the variant where

@@ -211,6 +211,40 @@ struct IntersectorOctreeGPU
 		fetch( faceDir, d, stream );
 	}
 
+	// the same surface with coplanar faces merged into rectangles (mvrt_svo_surface_merged; the rule is in mvrt.h).  flags: MVRT_SURFACE_MERGE_ANY_ATTRIBUTE |
+	// MVRT_SURFACE_MERGE_WELD; indicesDev / verticesDev need the weld flag.  Device-pointer form: any output may be nullptr, all nullptr = the sizing call.
+	void surfaceMerged( uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev, float* positionsDev,
+						uint32_t* indicesDev, float* verticesDev, uint64_t* nFaces, uint64_t* nRects, uint64_t* nVertices, void* stream ) const
+	{
+		check( mvrt_svo_surface_merged( m_handle, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev, nFaces, nRects,
+										nVertices, stream ),
+			   "IntersectorOctreeGPU::surfaceMerged" );
+	}
+	// host-vector form.  With the weld flag: shared vertices and 4 indices per rectangle, like surfaceMesh.  Without it: `vertices` holds the 4 corners of every
+	// rectangle (12 floats each) and `indices` stays empty.  Returns nFaces, the number of voxel faces the rectangles cover.
+	uint64_t surfaceMerged( uint32_t flags, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& rectVoxel, std::vector<uint8_t>& rectDir,
+							std::vector<uint32_t>& rectSize /* 2 per rectangle */, void* stream ) const
+	{
+		const bool weld = ( flags & MVRT_SURFACE_MERGE_WELD ) != 0;
+		uint64_t nf = 0, nr = 0, nv = 0;
+		surfaceMerged( flags, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nf, &nr, &nv, stream );
+		const uint64_t points = weld ? nv : nr * 4;
+		vertices.resize( points * 3 );
+		indices.resize( weld ? nr * 4 : 0 );
+		rectVoxel.resize( nr );
+		rectDir.resize( nr );
+		rectSize.resize( nr * 2 );
+		Staged x( nullptr, points * 12, stream ), i( nullptr, indices.size() * 4, stream ), v( nullptr, nr * 4, stream ), d( nullptr, nr, stream ), s( nullptr, nr * 8, stream );
+		surfaceMerged( flags, nr, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)s.p, weld ? nullptr : (float*)x.p, weld ? (uint32_t*)i.p : nullptr, weld ? (float*)x.p : nullptr, &nf,
+					   &nr, &nv, stream );
+		fetch( vertices, x, stream );
+		fetch( indices, i, stream );
+		fetch( rectVoxel, v, stream );
+		fetch( rectDir, d, stream );
+		fetch( rectSize, s, stream );
+		return nf;
+	}
+
 	// batch form of the device method intersect() (:243-251): SoA device arrays
 	void intersect( uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz, const uint8_t* isShadowRay, float* t,
 					int32_t* nMajor, uint32_t* vIndex, void* stream ) const

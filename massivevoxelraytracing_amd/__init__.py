@@ -50,6 +50,8 @@ class DenoiseParams(C.Structure):
 
 
 DENOISE_NO_DEMODULATION = 1
+SURFACE_MERGE_ANY_ATTRIBUTE = 1  # mvrt_svo_surface_merged flags (include/mvrt.h)
+SURFACE_MERGE_WELD = 2
 
 
 # every symbol include/mvrt.h declares: name -> (restype, argtypes)
@@ -82,6 +84,7 @@ SIGNATURES = {
     "mvrt_svo_surface_masks": (_i32, [_vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_quads": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_mesh": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_merged": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
     "mvrt_svo_device_view": (_i32, [_vp, _vp]),
@@ -294,6 +297,8 @@ class IntersectorOctreeGPU:
     BUILD_NO_DAG = 1
     BUILD_NO_EMBEDDED_MASK = 2
     BUILD_CONSERVATIVE = 4
+    SURFACE_MERGE_ANY_ATTRIBUTE = SURFACE_MERGE_ANY_ATTRIBUTE
+    SURFACE_MERGE_WELD = SURFACE_MERGE_WELD
 
     def build_synthetic(self, gridRes, n_random_voxels, seed, origin=(0.0, 0.0, 0.0), dps=None, flags=0, stream=None):
         """seeded random-voxel octree built on the GPU (HBM-bound stress, mvrt_svo_build_synthetic)"""
@@ -421,6 +426,28 @@ class IntersectorOctreeGPU:
         fv, fd, idx, vtx = DeviceArray(nf, np.uint32), DeviceArray(nf, np.uint8), DeviceArray((nf, 4), np.uint32), DeviceArray((nv, 3), np.float32)
         self.surface_mesh_device(nf, nv, fv, fd, idx, vtx, stream)
         return {"vertices": vtx.to_host(), "indices": idx.to_host(), "faceVoxel": fv.to_host(), "faceDir": fd.to_host()}
+
+    def surface_merged_device(self, flags=0, rect_capacity=0, vertex_capacity=0, rectVoxel=None, rectDir=None, rectSize=None, positions=None, indices=None, vertices=None,
+                              stream=None):
+        """mvrt_svo_surface_merged into caller device arrays (any may be None; all None = the sizing call); returns (nFaces, nRects, nVertices).
+        flags: SURFACE_MERGE_ANY_ATTRIBUTE | SURFACE_MERGE_WELD; indices / vertices need the weld flag.  On MvrtError nothing was written."""
+        nf, nr, nv = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_surface_merged(self._h, int(flags), int(rect_capacity), int(vertex_capacity), _dev_ptr(rectVoxel), _dev_ptr(rectDir), _dev_ptr(rectSize),
+                                             _dev_ptr(positions), _dev_ptr(indices), _dev_ptr(vertices), C.byref(nf), C.byref(nr), C.byref(nv), stream))
+        return nf.value, nr.value, nv.value
+
+    def surface_merged(self, flags=0, stream=None):
+        """the exposed faces merged into rectangles, ascending (direction, plane, u0, v0): {nFaces, rectVoxel (n,) uint32 the anchor's vIndex, rectDir (n,) uint8,
+        rectSize (n, 2) uint32 (du, dv), positions (n, 4, 3) float32}; with SURFACE_MERGE_WELD also {vertices (m, 3) float32, indices (n, 4) uint32}"""
+        nf, nr, nv = self.surface_merged_device(flags, stream=stream)
+        weld = bool(flags & self.SURFACE_MERGE_WELD)
+        rv, rd, rs, pos = DeviceArray(nr, np.uint32), DeviceArray(nr, np.uint8), DeviceArray((nr, 2), np.uint32), DeviceArray((nr, 4, 3), np.float32)
+        idx, vtx = (DeviceArray((nr, 4), np.uint32), DeviceArray((nv, 3), np.float32)) if weld else (None, None)
+        self.surface_merged_device(flags, nr, nv, rv, rd, rs, pos, idx, vtx, stream)
+        out = {"nFaces": nf, "rectVoxel": rv.to_host(), "rectDir": rd.to_host(), "rectSize": rs.to_host(), "positions": pos.to_host()}
+        if weld:
+            out.update(vertices=vtx.to_host(), indices=idx.to_host())
+        return out
 
     def upload(self, nodes68, attribs, origin, dps, gridRes, hasEmission=0, embeddedMask=True, stream=None):
         nodes68 = np.ascontiguousarray(nodes68)

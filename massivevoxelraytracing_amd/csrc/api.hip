@@ -626,6 +626,7 @@ static int surfaceSource( const mvrt_svo* svo, const char* who, SurfaceSource* s
 	s->cellBits = o.cellBits;
 	s->lower = mk3( o.info.lower[0], o.info.lower[1], o.info.lower[2] );
 	s->dps = o.info.dps;
+	s->attrs = o.attrs.as<uint2>();
 	return 0;
 }
 MVRT_EXPORT int mvrt_svo_surface_masks( const mvrt_svo* svo, uint8_t* masksDev, uint64_t* nFacesOut, void* stream )
@@ -647,6 +648,18 @@ MVRT_EXPORT int mvrt_svo_surface_mesh( const mvrt_svo* svo, uint64_t faceCapacit
 	SurfaceSource s;
 	if( surfaceSource( svo, "mvrt_svo_surface_mesh", &s ) ) return 1;
 	return surfaceMesh( s, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFacesOut, nVerticesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev,
+										 uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut,
+										 uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	if( nVerticesOut ) *nVerticesOut = 0;
+	REQUIRE( ( flags & ~(uint32_t)( MVRT_SURFACE_MERGE_ANY_ATTRIBUTE | MVRT_SURFACE_MERGE_WELD ) ) == 0, "mvrt_svo_surface_merged: unknown flags 0x%x", flags );
+	if( surfaceSource( svo, "mvrt_svo_surface_merged", &s ) ) return 1;
+	REQUIRE( ( flags & MVRT_SURFACE_MERGE_WELD ) || ( !indicesDev && !verticesDev ), "mvrt_svo_surface_merged: indicesDev / verticesDev need MVRT_SURFACE_MERGE_WELD" );
+	return surfaceMerged( s, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev, nFacesOut, nRectsOut, nVerticesOut,
+						  (hipStream_t)stream );
 }
 
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )

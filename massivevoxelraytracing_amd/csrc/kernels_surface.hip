@@ -278,6 +278,29 @@ int scanOffsets( const SurfaceSource& s, const DevBuf& masks, DevBuf& offs, hipS
 	hipcub::TransformInputIterator<uint64_t, PopcountOf, const uint8_t*> in( masks.as<uint8_t>(), PopcountOf() );
 	return withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, in, offs.as<uint64_t>(), items, st ); } );
 }
+// the weld behind the corner keys: radix sort of (key, corner number) into keysB / valsB (keysA / valsA are released), head flags, inclusive scan = rank + 1
+// into rank1, and the number of distinct keys on the host when this returns
+int sortAndRankCorners( const SurfaceSource& s, DevBuf& keysA, DevBuf& valsA, uint32_t nCorners, DevBuf& keysB, DevBuf& valsB, DevBuf& rank1, uint32_t* nVertices, hipStream_t st )
+{
+	if( keysB.alloc( (uint64_t)nCorners * 8 ) || valsB.alloc( (uint64_t)nCorners * 4 ) ) return 1;
+	int endBit = 3 * ( (int)s.levels + 1 ); // a key is below ( gridRes + 1 )^3 <= 2^( 3 * ( levels + 1 ) )
+	if( endBit > 64 ) endBit = 64;
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+			return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint32_t>(), valsB.as<uint32_t>(), (uint64_t)nCorners, 0,
+													   endBit, st );
+		} ) )
+		return 1;
+	keysA.release();
+	valsA.release();
+	if( rank1.alloc( (uint64_t)nCorners * 4 ) ) return 1;
+	hipcub::CountingInputIterator<uint32_t> counting( 0u );
+	hipcub::TransformInputIterator<uint32_t, HeadOf, hipcub::CountingInputIterator<uint32_t>> heads( counting, HeadOf{ keysB.as<uint64_t>() } );
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, heads, rank1.as<uint32_t>(), (uint64_t)nCorners, st ); } ) )
+		return 1;
+	MVRT_HIP( hipMemcpyAsync( nVertices, rank1.as<uint32_t>() + ( nCorners - 1 ), 4, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	return 0;
+}
 } // namespace
 
 int surfaceMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, hipStream_t st )
@@ -328,24 +351,9 @@ int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexC
 	{
 		if( scanOffsets( s, masks, offs, st ) ) return 1;
 		DevBuf keysA, valsA;
-		if( keysA.alloc( (uint64_t)nCorners * 8 ) || valsA.alloc( (uint64_t)nCorners * 4 ) || keysB.alloc( (uint64_t)nCorners * 8 ) || valsB.alloc( (uint64_t)nCorners * 4 ) ) return 1;
+		if( keysA.alloc( (uint64_t)nCorners * 8 ) || valsA.alloc( (uint64_t)nCorners * 4 ) ) return 1;
 		if( launchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), nullptr, nullptr, nullptr, keysA.as<uint64_t>(), valsA.as<uint32_t>(), st ) ) return 1;
-		int endBit = 3 * ( (int)s.levels + 1 ); // a key is below ( gridRes + 1 )^3 <= 2^( 3 * ( levels + 1 ) )
-		if( endBit > 64 ) endBit = 64;
-		if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
-				return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint32_t>(), valsB.as<uint32_t>(), (uint64_t)nCorners, 0,
-														   endBit, st );
-			} ) )
-			return 1;
-		keysA.release();
-		valsA.release();
-		if( rank1.alloc( (uint64_t)nCorners * 4 ) ) return 1;
-		hipcub::CountingInputIterator<uint32_t> counting( 0u );
-		hipcub::TransformInputIterator<uint32_t, HeadOf, hipcub::CountingInputIterator<uint32_t>> heads( counting, HeadOf{ keysB.as<uint64_t>() } );
-		if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, heads, rank1.as<uint32_t>(), (uint64_t)nCorners, st ); } ) )
-			return 1;
-		MVRT_HIP( hipMemcpyAsync( &nVertices, rank1.as<uint32_t>() + ( nCorners - 1 ), 4, hipMemcpyDeviceToHost, st ) );
-		MVRT_HIP( hipStreamSynchronize( st ) );
+		if( sortAndRankCorners( s, keysA, valsA, nCorners, keysB, valsB, rank1, &nVertices, st ) ) return 1;
 	}
 	if( nVerticesOut ) *nVerticesOut = nVertices;
 	if( !faceVoxelDev && !faceDirDev && !indicesDev && !verticesDev ) return 0; // the sizing call
@@ -363,6 +371,347 @@ int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexC
 	}
 	if( nCorners == 0 ) return 0;
 	if( ( faceVoxelDev || faceDirDev ) && launchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), faceVoxelDev, faceDirDev, nullptr, nullptr, nullptr, st ) ) return 1;
+	if( indicesDev || verticesDev )
+	{
+		hipLaunchKernelGGL( kSurfaceWeld, dim3( divUp( nCorners, SB ) ), dim3( SB ), 0, st, keysB.as<uint64_t>(), valsB.as<uint32_t>(), rank1.as<uint32_t>(), nCorners, s.lower, s.dps,
+							1u << s.levels, indicesDev, verticesDev );
+		MVRT_HIP( hipGetLastError() );
+	}
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	return 0;
+}
+
+// ---- merged rectangles (mvrt_svo_surface_merged; the rule is in mvrt.h, the passes in DESIGN.md 5.11) ----------------------------------------------------
+// One direction at a time.  A face of direction d is the key p << 2L | v << L | u (L = levels bits per field: p the voxel's coordinate on the normal axis,
+// (u, v) its coordinates on the two other axes, the lower-numbered axis u) with the value vIndex.  Sorted, the faces of a row (p, v) lie together by u:
+// head flags end a run where u is not one higher IN THE SAME ROW or the attributes differ.  The runs, keyed p << 2L | u0 << L | v, are sorted again: runs that
+// start at the same u0 lie together by v, and head flags end a stack where v is not one higher IN THE SAME COLUMN, du differs or the attributes differ.
+// The heads of the second pass, in its order, are the rectangles of the direction in (p, u0, v0) order.
+namespace
+{
+struct MergeRect // one rectangle of a direction, kept until every direction is counted
+{
+	uint32_t voxel, du, dv; // the anchor face's vIndex and the extent in faces
+};
+
+struct BitOf // scan input: 1 where voxel i has a face in direction d
+{
+	uint32_t d;
+	__host__ __device__ uint32_t operator()( uint8_t m ) const { return ( (uint32_t)m >> d ) & 1u; }
+};
+struct FlagOf // scan input: a head flag
+{
+	__host__ __device__ uint32_t operator()( uint8_t f ) const { return f; }
+};
+
+// in-plane axes of normal axis a: x -> (y, z), y -> (x, z), z -> (x, y)
+MVRT_DI uint32_t axisU( uint32_t a ) { return a == 0u ? 1u : 0u; }
+MVRT_DI uint32_t axisV( uint32_t a ) { return a == 2u ? 1u : 2u; }
+MVRT_DI bool sameAttribute( const uint2* __restrict__ attrs, uint32_t v0, uint32_t v1 ) // all 8 bytes, one 8-byte load each
+{
+	const uint2 a = attrs[v0], b = attrs[v1];
+	return a.x == b.x && a.y == b.y;
+}
+
+// offs: n + 1 exclusive offsets of bit d.  The voxels with the bit write their record at their offset: the set lanes of a wave write consecutive records.
+__global__ void __launch_bounds__( SB ) kMergeFaceKeys( const uint64_t* __restrict__ morton, const uint8_t* __restrict__ masks, const uint32_t* __restrict__ offs, uint32_t n, uint32_t d,
+															uint32_t levels, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	if( i >= n || !( ( masks[i] >> d ) & 1u ) ) return;
+	const uint64_t c = morton[i];
+	const uint32_t xyz[3] = { compact3( c ), compact3( c >> 1 ), compact3( c >> 2 ) };
+	const uint32_t a = dirAxis( d );
+	const uint32_t o = offs[i];
+	keys[o] = ( (uint64_t)xyz[a] << ( 2u * levels ) ) | ( (uint64_t)xyz[axisV( a )] << levels ) | xyz[axisU( a )];
+	vals[o] = (uint32_t)i;
+}
+
+// step 1 on the sorted faces: flags[i] = 0 where face i continues the run of face i - 1.  "Same row, u one higher" is key == previous + 1 AND u != 0: the
+// last face of a row and the first of the next differ by 1 too when the u field is full, which at `levels` bits per field it is at every gridRes.
+__global__ void __launch_bounds__( SB ) kMergeRunHeads( const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint2* __restrict__ attrs, uint32_t n, uint32_t levels,
+															uint32_t anyAttribute, uint8_t* __restrict__ flags )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	if( i >= n ) return;
+	bool head = true;
+	if( i > 0 )
+	{
+		const uint64_t k = keys[i];
+		if( k == keys[i - 1] + 1ull && ( k & ( ( 1ull << levels ) - 1ull ) ) != 0ull ) head = !anyAttribute && !sameAttribute( attrs, vals[i], vals[i - 1] );
+	}
+	flags[i] = head ? 1 : 0;
+}
+
+// rank1 = inclusive scan of the flags: starts[r] = the r-th flagged entry, starts[count] = n
+__global__ void __launch_bounds__( SB ) kMergeStarts( const uint8_t* __restrict__ flags, const uint32_t* __restrict__ rank1, uint32_t n, uint32_t* __restrict__ starts )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	if( i >= n ) return;
+	if( flags[i] ) starts[rank1[i] - 1u] = (uint32_t)i;
+	if( i == n - 1u ) starts[rank1[i]] = n;
+}
+
+// run r = the faces [runStart[r], runStart[r + 1]) -> key p << 2L | u0 << L | v, value r
+__global__ void __launch_bounds__( SB ) kMergeRunKeys( const uint64_t* __restrict__ faceKeys, const uint32_t* __restrict__ runStart, uint32_t nRuns, uint32_t levels,
+														   uint64_t* __restrict__ keys, uint32_t* __restrict__ vals )
+{
+	const uint64_t r = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	if( r >= nRuns ) return;
+	const uint64_t k = faceKeys[runStart[r]];
+	const uint64_t field = ( 1ull << levels ) - 1ull;
+	keys[r] = ( k & ~( ( field << levels ) | field ) ) | ( ( k & field ) << levels ) | ( ( k >> levels ) & field );
+	vals[r] = (uint32_t)r;
+}
+
+// step 2 on the sorted runs: flags[j] = 0 where run j stacks on run j - 1: same column and v one higher (the same trap as above), same du, same attribute
+__global__ void __launch_bounds__( SB ) kMergeStackHeads( const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ runStart,
+															  const uint32_t* __restrict__ faceVoxel, const uint2* __restrict__ attrs, uint32_t nRuns, uint32_t levels, uint32_t anyAttribute,
+															  uint8_t* __restrict__ flags )
+{
+	const uint64_t j = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	if( j >= nRuns ) return;
+	bool head = true;
+	if( j > 0 )
+	{
+		const uint64_t k = keys[j];
+		if( k == keys[j - 1] + 1ull && ( k & ( ( 1ull << levels ) - 1ull ) ) != 0ull )
+		{
+			const uint32_t r = vals[j], q = vals[j - 1];
+			const uint32_t i = runStart[r], h = runStart[q];
+			head = runStart[r + 1] - i != runStart[q + 1] - h || ( !anyAttribute && !sameAttribute( attrs, faceVoxel[i], faceVoxel[h] ) );
+		}
+	}
+	flags[j] = head ? 1 : 0;
+}
+
+// rectangle t of the direction = the sorted runs [rectStart[t], rectStart[t + 1])
+__global__ void __launch_bounds__( SB ) kMergeRects( const uint32_t* __restrict__ rectStart, uint32_t nRects, const uint32_t* __restrict__ runOf, const uint32_t* __restrict__ runStart,
+														 const uint32_t* __restrict__ faceVoxel, MergeRect* __restrict__ rects )
+{
+	const uint64_t t = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	if( t >= nRects ) return;
+	const uint32_t j = rectStart[t];
+	const uint32_t r = runOf[j];
+	const uint32_t i = runStart[r];
+	MergeRect o;
+	o.voxel = faceVoxel[i];
+	o.du = runStart[r + 1] - i;
+	o.dv = rectStart[t + 1] - j;
+	rects[t] = o;
+}
+
+// the rectangles of direction d at the running offset `base` of every output; any output may be null.  keys / vals: the weld's corner keys and rect * 4 + k.
+template <bool V4>
+__global__ void __launch_bounds__( SB ) kMergeEmit( const MergeRect* __restrict__ rects, uint32_t nRects, uint64_t base, uint32_t d, const uint64_t* __restrict__ morton, f3 lower, float dps,
+														uint32_t gridRes, uint32_t* __restrict__ rectVoxel, uint8_t* __restrict__ rectDir, uint32_t* __restrict__ rectSize,
+														float* __restrict__ positions, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals )
+{
+	const uint64_t t = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	if( t >= nRects ) return;
+	const MergeRect r = rects[t];
+	const uint64_t f = base + t;
+	if( rectVoxel ) rectVoxel[f] = r.voxel;
+	if( rectDir ) rectDir[f] = (uint8_t)d;
+	if( rectSize )
+	{
+		rectSize[f * 2] = r.du;
+		rectSize[f * 2 + 1] = r.dv;
+	}
+	if( !positions && !keys ) return;
+	const uint64_t c = morton[r.voxel];
+	const uint32_t x = compact3( c ), y = compact3( c >> 1 ), z = compact3( c >> 2 );
+	const uint32_t a = dirAxis( d );
+	uint32_t scale[3] = { 1u, 1u, 1u }; // a corner offset counts du on the u axis, dv on the v axis, 1 on the normal axis
+	scale[axisU( a )] = r.du;
+	scale[axisV( a )] = r.dv;
+	float p[12];
+#pragma unroll
+	for( uint32_t k = 0; k < 4; k++ )
+	{
+		const uint32_t cn = faceCorner( d, k );
+		const uint32_t cx = x + cornerX( cn ) * scale[0], cy = y + cornerY( cn ) * scale[1], cz = z + cornerZ( cn ) * scale[2];
+		p[k * 3] = lower.x + (float)cx * dps;
+		p[k * 3 + 1] = lower.y + (float)cy * dps;
+		p[k * 3 + 2] = lower.z + (float)cz * dps;
+		if( keys )
+		{
+			const uint64_t R1 = (uint64_t)gridRes + 1ull;
+			keys[f * 4 + k] = ( (uint64_t)cz * R1 + cy ) * R1 + cx;
+			vals[f * 4 + k] = (uint32_t)( f * 4 + k );
+		}
+	}
+	if( positions )
+	{
+		if( V4 )
+		{
+			float4* o = reinterpret_cast<float4*>( positions + f * 12 );
+			o[0] = make_float4( p[0], p[1], p[2], p[3] );
+			o[1] = make_float4( p[4], p[5], p[6], p[7] );
+			o[2] = make_float4( p[8], p[9], p[10], p[11] );
+		}
+		else
+		{
+#pragma unroll
+			for( int k = 0; k < 12; k++ ) positions[f * 12 + k] = p[k];
+		}
+	}
+}
+
+#define MERGE_LAUNCH( kernel, items, ... )                                                                     \
+	do                                                                                                          \
+	{                                                                                                           \
+		hipLaunchKernelGGL( kernel, dim3( divUp( items, SB ) ), dim3( SB ), 0, st, __VA_ARGS__ );               \
+		MVRT_HIP( hipGetLastError() );                                                                          \
+	} while( 0 )
+
+// n head flags -> starts (count + 1 entries, the last one n) and the count on the host
+int startsOfHeads( const DevBuf& flags, uint32_t n, DevBuf& starts, uint32_t* count, hipStream_t st )
+{
+	DevBuf rank1;
+	if( rank1.alloc( (uint64_t)n * 4 ) ) return 1;
+	hipcub::TransformInputIterator<uint32_t, FlagOf, const uint8_t*> in( flags.as<uint8_t>(), FlagOf() );
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, in, rank1.as<uint32_t>(), (uint64_t)n, st ); } ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( count, rank1.as<uint32_t>() + ( n - 1 ), 4, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( starts.alloc( ( (uint64_t)*count + 1 ) * 4 ) ) return 1;
+	MERGE_LAUNCH( kMergeStarts, n, flags.as<uint8_t>(), rank1.as<uint32_t>(), n, starts.as<uint32_t>() );
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (rank1 is released on return)
+	return 0;
+}
+int sortMergeKeys( DevBuf& keysA, DevBuf& valsA, uint32_t n, uint32_t levels, DevBuf& keysB, DevBuf& valsB, hipStream_t st ) // A is released
+{
+	if( keysB.alloc( (uint64_t)n * 8 ) || valsB.alloc( (uint64_t)n * 4 ) ) return 1;
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+			return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint32_t>(), valsB.as<uint32_t>(), (uint64_t)n, 0,
+													   3 * (int)levels, st );
+		} ) )
+		return 1;
+	keysA.release();
+	valsA.release();
+	return 0;
+}
+
+// the rectangles of direction d into `rects` (nRects of them; 0 leaves it empty)
+int mergeDirection( const SurfaceSource& s, const uint8_t* masks /* n + 1, the last 0 */, uint32_t d, uint32_t anyAttribute, DevBuf& rects, uint32_t* nRects, hipStream_t st )
+{
+	*nRects = 0;
+	const uint32_t n = s.nVoxels, L = s.levels;
+	DevBuf faceKeys, faceVoxel; // the faces of this direction, sorted by (p, v, u)
+	uint32_t nFaces = 0;
+	{
+		DevBuf offs, keysA, valsA;
+		const uint64_t items = (uint64_t)n + 1;
+		if( offs.alloc( items * 4 ) ) return 1;
+		hipcub::TransformInputIterator<uint32_t, BitOf, const uint8_t*> in( masks, BitOf{ d } );
+		if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, in, offs.as<uint32_t>(), items, st ); } ) ) return 1;
+		MVRT_HIP( hipMemcpyAsync( &nFaces, offs.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+		if( nFaces == 0 ) return 0;
+		if( keysA.alloc( (uint64_t)nFaces * 8 ) || valsA.alloc( (uint64_t)nFaces * 4 ) ) return 1;
+		MERGE_LAUNCH( kMergeFaceKeys, n, s.morton, masks, offs.as<uint32_t>(), n, d, L, keysA.as<uint64_t>(), valsA.as<uint32_t>() );
+		if( sortMergeKeys( keysA, valsA, nFaces, L, faceKeys, faceVoxel, st ) ) return 1; // (waits: offs goes at scope end)
+	}
+	DevBuf flags, runStart;
+	uint32_t nRuns = 0;
+	if( flags.alloc( nFaces ) ) return 1;
+	MERGE_LAUNCH( kMergeRunHeads, nFaces, faceKeys.as<uint64_t>(), faceVoxel.as<uint32_t>(), s.attrs, nFaces, L, anyAttribute, flags.as<uint8_t>() );
+	if( startsOfHeads( flags, nFaces, runStart, &nRuns, st ) ) return 1;
+
+	DevBuf runKeys, runOf; // the runs sorted by (p, u0, v): key and run number
+	{
+		DevBuf keysA, valsA;
+		if( keysA.alloc( (uint64_t)nRuns * 8 ) || valsA.alloc( (uint64_t)nRuns * 4 ) ) return 1;
+		MERGE_LAUNCH( kMergeRunKeys, nRuns, faceKeys.as<uint64_t>(), runStart.as<uint32_t>(), nRuns, L, keysA.as<uint64_t>(), valsA.as<uint32_t>() );
+		if( sortMergeKeys( keysA, valsA, nRuns, L, runKeys, runOf, st ) ) return 1;
+	}
+	faceKeys.release();
+	DevBuf rectStart;
+	uint32_t count = 0;
+	if( flags.alloc( nRuns ) ) return 1;
+	MERGE_LAUNCH( kMergeStackHeads, nRuns, runKeys.as<uint64_t>(), runOf.as<uint32_t>(), runStart.as<uint32_t>(), faceVoxel.as<uint32_t>(), s.attrs, nRuns, L, anyAttribute,
+				  flags.as<uint8_t>() );
+	if( startsOfHeads( flags, nRuns, rectStart, &count, st ) ) return 1;
+	if( rects.alloc( (uint64_t)count * sizeof( MergeRect ) ) ) return 1;
+	MERGE_LAUNCH( kMergeRects, count, rectStart.as<uint32_t>(), count, runOf.as<uint32_t>(), runStart.as<uint32_t>(), faceVoxel.as<uint32_t>(), rects.as<MergeRect>() );
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	*nRects = count;
+	return 0;
+}
+int launchMergeEmit( const SurfaceSource& s, const DevBuf* rects, const uint32_t* counts, uint32_t* rectVoxel, uint8_t* rectDir, uint32_t* rectSize, float* positions, uint64_t* keys,
+					 uint32_t* vals, hipStream_t st )
+{
+	uint64_t base = 0;
+	for( uint32_t d = 0; d < 6; base += counts[d], d++ )
+	{
+		if( counts[d] == 0 ) continue;
+		if( ( (uintptr_t)positions & 15u ) == 0 )
+			MERGE_LAUNCH( kMergeEmit<true>, counts[d], rects[d].as<MergeRect>(), counts[d], base, d, s.morton, s.lower, s.dps, 1u << s.levels, rectVoxel, rectDir, rectSize, positions, keys,
+						  vals );
+		else
+			MERGE_LAUNCH( kMergeEmit<false>, counts[d], rects[d].as<MergeRect>(), counts[d], base, d, s.morton, s.lower, s.dps, 1u << s.levels, rectVoxel, rectDir, rectSize, positions, keys,
+						  vals );
+	}
+	return 0;
+}
+} // namespace
+
+int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev,
+				   float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut, hipStream_t st )
+{
+	const bool weld = ( flags & 2u ) != 0; // MVRT_SURFACE_MERGE_WELD
+	DevBuf rects[6];
+	uint32_t counts[6];
+	uint64_t nFaces = 0, nRects = 0;
+	{
+		DevBuf masks;
+		if( scratchMasksAndCount( s, masks, &nFaces, st ) ) return 1;
+		if( nFacesOut ) *nFacesOut = nFaces;
+		if( nRectsOut ) *nRectsOut = 0;
+		if( nVerticesOut ) *nVerticesOut = 0;
+		for( uint32_t d = 0; d < 6; d++ )
+		{
+			if( mergeDirection( s, masks.as<uint8_t>(), d, flags & 1u /* MVRT_SURFACE_MERGE_ANY_ATTRIBUTE */, rects[d], &counts[d], st ) ) return 1;
+			nRects += counts[d];
+		}
+	}
+	if( nRectsOut ) *nRectsOut = nRects;
+	uint32_t nCorners = 0, nVertices = 0;
+	DevBuf keysB, valsB, rank1;
+	if( weld )
+	{
+		if( 4ull * nRects >= ( 1ull << 32 ) )
+		{
+			mvrtSetError( "mvrt_svo_surface_merged: the %llu rectangles of the surface have 2^32 corners or more, beyond the 32-bit indices of a welded mesh (call without "
+						  "MVRT_SURFACE_MERGE_WELD)",
+						  (unsigned long long)nRects );
+			return 1;
+		}
+		nCorners = (uint32_t)( 4ull * nRects );
+		if( nCorners )
+		{
+			DevBuf keysA, valsA;
+			if( keysA.alloc( (uint64_t)nCorners * 8 ) || valsA.alloc( (uint64_t)nCorners * 4 ) ) return 1;
+			if( launchMergeEmit( s, rects, counts, nullptr, nullptr, nullptr, nullptr, keysA.as<uint64_t>(), valsA.as<uint32_t>(), st ) ) return 1;
+			if( sortAndRankCorners( s, keysA, valsA, nCorners, keysB, valsB, rank1, &nVertices, st ) ) return 1;
+		}
+		if( nVerticesOut ) *nVerticesOut = nVertices;
+	}
+	if( !rectVoxelDev && !rectDirDev && !rectSizeDev && !positionsDev && !indicesDev && !verticesDev ) return 0; // the sizing call
+	if( ( rectVoxelDev || rectDirDev || rectSizeDev || positionsDev || indicesDev ) && rectCapacity < nRects )
+	{
+		mvrtSetError( "mvrt_svo_surface_merged: rectCapacity %llu is smaller than the %llu rectangles of the surface; nothing was written", (unsigned long long)rectCapacity,
+					  (unsigned long long)nRects );
+		return 1;
+	}
+	if( verticesDev && vertexCapacity < nVertices )
+	{
+		mvrtSetError( "mvrt_svo_surface_merged: vertexCapacity %llu is smaller than the %u vertices of the surface; nothing was written", (unsigned long long)vertexCapacity, nVertices );
+		return 1;
+	}
+	if( nRects == 0 ) return 0;
+	if( ( rectVoxelDev || rectDirDev || rectSizeDev || positionsDev ) && launchMergeEmit( s, rects, counts, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, nullptr, nullptr, st ) )
+		return 1;
 	if( indicesDev || verticesDev )
 	{
 		hipLaunchKernelGGL( kSurfaceWeld, dim3( divUp( nCorners, SB ) ), dim3( SB ), 0, st, keysB.as<uint64_t>(), valsB.as<uint32_t>(), rank1.as<uint32_t>(), nCorners, s.lower, s.dps,

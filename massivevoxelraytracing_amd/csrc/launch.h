@@ -169,11 +169,15 @@ struct SurfaceSource
 	uint32_t cellBits;
 	f3 lower;
 	float dps;
+	const uint2* attrs; // VoxelAttirb per voxel, read by surfaceMerged only
 };
 int surfaceMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, hipStream_t stream );
 int surfaceQuads( const SurfaceSource& s, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut, hipStream_t stream );
 int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev,
 				 uint64_t* nFacesOut, uint64_t* nVerticesOut, hipStream_t stream );
+// flags: MVRT_SURFACE_MERGE_* (mvrt.h), checked by the caller, as is that indicesDev / verticesDev come with the weld flag only
+int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev,
+				   float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut, hipStream_t stream );
 
 // octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
 // flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.

@@ -5,6 +5,8 @@ Cost of extracting the voxel surface on the procedural stand-ins (dragon 2048^3,
   masks   mvrt_svo_surface_masks into a device array (16 B read + 1 B written per voxel)
   quads   mvrt_svo_surface_quads into device arrays (masks + scan + 53 B written per face)
   mesh    mvrt_svo_surface_mesh into device arrays (masks + scan + corner keys + radix sort + ranks)
+  merged  mvrt_svo_surface_merged into device arrays, once per flag combination (per direction: keys + radix sort + heads, twice; with the weld flag the
+          corner sort as in mesh): nRects, nRects / nFaces and the time
 Median of --reps calls after --warmup calls; host clock around each call (every call blocks until its counts are back).  Output arrays are allocated
 before the clock starts.  The achieved bytes per second of the whole masks and quads CALLS stand next to the 8 TB/s HBM peak; kernel times come from a
 kernel trace of its own (rocprofv3 --kernel-trace --stats -- python tools/surface_bench.py --reps 3 --no-host-method).
@@ -103,6 +105,17 @@ def main():
         idx, vtx = mv.DeviceArray((n_faces, 4), np.uint32), mv.DeviceArray((n_vertices, 3), np.float32)
         ms, ts = timed(lambda: svo.surface_mesh_device(n_faces, n_vertices, fv, fd, idx, vtx), args.reps, args.warmup)
         emit(op="mesh", ms=ms, all_ms=ts, **base)
+        del idx, vtx, fv, fd
+        for flags in (0, mv.SURFACE_MERGE_ANY_ATTRIBUTE, mv.SURFACE_MERGE_WELD, mv.SURFACE_MERGE_ANY_ATTRIBUTE | mv.SURFACE_MERGE_WELD):
+            weld = bool(flags & mv.SURFACE_MERGE_WELD)
+            _, n_rects, n_welded = svo.surface_merged_device(flags)
+            rv, rd, rs = mv.DeviceArray(n_rects, np.uint32), mv.DeviceArray(n_rects, np.uint8), mv.DeviceArray((n_rects, 2), np.uint32)
+            pos = None if weld else mv.DeviceArray((n_rects, 12), np.float32)
+            idx, vtx = (mv.DeviceArray((n_rects, 4), np.uint32), mv.DeviceArray((n_welded, 3), np.float32)) if weld else (None, None)
+            ms, ts = timed(lambda: svo.surface_merged_device(flags, n_rects, n_welded, rv, rd, rs, pos, idx, vtx), args.reps, args.warmup)
+            emit(op="merged", flags=flags, any_attribute=bool(flags & mv.SURFACE_MERGE_ANY_ATTRIBUTE), weld=weld, nRects=n_rects, nMergedVertices=n_welded,
+                 rects_per_face=n_rects / max(n_faces, 1), ms=ms, all_ms=ts, **base)
+            del rv, rd, rs, pos, idx, vtx
         if name == "dragon" and not args.no_host_method:
             got, s = host_method(svo, res)
             emit(op="host_method_masks", ms=s * 1e3, equal_to_gpu=bool(np.array_equal(got, masks.to_host())), **base)
@@ -111,7 +124,8 @@ def main():
         with open(args.out, "w") as f:
             json.dump(rows, f, indent=1)
     for r in rows:
-        print("%-7s %5d %-18s %9d voxels %10d faces %9.2f ms" % (r["scene"], r["grid"], r["op"], r["voxels"], r["nFaces"], r["ms"]), file=sys.stderr)
+        op = r["op"] + ("" if "flags" not in r else " flags %d: %d rects, %.4f per face" % (r["flags"], r["nRects"], r["rects_per_face"]))
+        print("%-7s %5d %-18s %9d voxels %10d faces %9.2f ms" % (r["scene"], r["grid"], op, r["voxels"], r["nFaces"], r["ms"]), file=sys.stderr)
 
 
 if __name__ == "__main__":
