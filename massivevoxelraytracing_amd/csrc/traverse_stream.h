@@ -245,6 +245,14 @@ MVRT_DI unsigned long long signMask( uint32_t v )
 	asm( "v_cmp_gt_i32 %0, 0, %1" : "=s"( m ) : "v"( v ) );
 	return m;
 }
+// number of set bits of a lane mask, in a scalar register (s_bcnt1_i32_b64): __popcll on a mask makes the compiler count on the vector unit and compare
+// there.  Scalar ALU only; it clobbers SCC like every scalar bit count
+MVRT_DI uint32_t activeLanes( lmask m )
+{
+	uint32_t n;
+	asm( "s_bcnt1_i32_b64 %0, %1" : "=s"( n ) : "s"( m ) : "scc" );
+	return n;
+}
 typedef float v2f __attribute__( ( ext_vector_type( 2 ) ) );
 typedef uint32_t u4v __attribute__( ( ext_vector_type( 4 ) ) );
 typedef __attribute__( ( address_space( 3 ) ) ) u4v LdsU4; // (u4v: clang vector, assignable across address spaces)
@@ -464,6 +472,10 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 	// wave-uniform cursor state
 	uint32_t chunkNext = 0, chunkEnd = 0;
 	bool exhausted = false;
+	// the step loop runs while MORE than `thr` lanes traverse: 64 - REFILL_MIN while the stream has rays (then a refill pays), 0 once it is exhausted (nothing
+	// to refill with: the wave drains).  Changed in ONE place, together with `exhausted` -- a non-zero threshold on an exhausted stream would send a wave with a
+	// few live lanes round the outer loop forever
+	uint32_t thr = 64u - MVRT_REFILL_MIN_OF( FL );
 
 	// per-lane state.  st: 0 idle, 1 traversing, finished and holding a result that is not stored yet: 2 = miss, 3 = hit (the lane's slab state is
 	// untouched since the step that found the leaf: t and nMajor are re-derived from it at flush time instead of being selected into two more
@@ -535,6 +547,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 						if( base >= total )
 						{
 							exhausted = true;
+							thr = 0u;
 							// a wave that only drains its last rays is on the launch's critical path: let it win issue arbitration against the waves of
 							// a sibling pass that shares the SIMD (1/8 tile share: -1 % dragon, -3 % rtcamp; nothing on a full frame)
 							__builtin_amdgcn_s_setprio( 3 );
@@ -736,7 +749,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 		// mask of every lane lives bit-sliced in three SGPR pairs (+ a "first visit" mask) while the loop runs.
 		lmask cmX = __ballot( ( childMask & 1u ) != 0u ), cmY = __ballot( ( childMask & 2u ) != 0u ), cmZ = __ballot( ( childMask & 4u ) != 0u );
 		lmask mFirst = __ballot( ( childMask & 8u ) != 0u );
-		lmask actM = __ballot( st == 1u ), hitM = 0ull, missM = 0ull;
+		lmask actM = __ballot( st == 1u ), hitM = 0ull;
 		for( ;; )
 		{
 			const lmask act = actM;
@@ -759,9 +772,10 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
 			const float tyM = tMyz.x, tzM = tMyz.y;
 			// octant the node is entered in (:342-348), or the candidate a popped node resumes with
-			const lmask X = ( mFirst & __ballot( txM < S ) ) | ( ~mFirst & cmX );
-			const lmask Y = ( mFirst & __ballot( tyM < S ) ) | ( ~mFirst & cmY );
-			const lmask Z = ( mFirst & __ballot( tzM < S ) ) | ( ~mFirst & cmZ );
+			// (cmX / cmY / cmZ carry bits only for lanes whose mFirst bit is clear: kept so by the loop tail)
+			const lmask X = ( mFirst & __ballot( txM < S ) ) | cmX;
+			const lmask Y = ( mFirst & __ballot( tyM < S ) ) | cmY;
+			const lmask Z = ( mFirst & __ballot( tzM < S ) ) | cmZ;
 			// first exit event = lexicographic minimum of (t1, axis); flips = mid-plane events of unset axes that come before it, i.e.
 			// before EVERY exit event (an axis' own exit never precedes its mid-plane: tM <= t1).  (tM_a, a) < (t1_b, b) is "tM_a <= t1_b" for
 			// a < b and "tM_a < t1_b" for a > b
@@ -902,18 +916,21 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			// (a hit only changes the lane's state: t and nMajor are re-derived by finishedHit() from the slab state the lane keeps)
 			// bit-sliced child mask of the lanes that popped = the sign bits of the restored exit times; a descent starts a first visit
 			// (`popped` is zero for the lanes that did not pop)
-			cmX = ( cmX & ~mPopOk ) | signMask( popped.y );
-			cmY = ( cmY & ~mPopOk ) | signMask( popped.z );
-			cmZ = ( cmZ & ~mPopOk ) | signMask( popped.w );
-			mFirst = ( mFirst & ~mPopOk ) | mGo;
-			// which lanes are still traversing / hold a hit / hold a miss is kept in lane masks (scalar unit) while the loop runs
-			const lmask mMiss = mPop & ~mPopOk;
+			// (a lane that descended starts a first visit: its resume bits are cleared with those of the lanes that popped, which keeps the invariant the top
+			// of the loop relies on)
+			const lmask keep = ~( mPopOk | mGo );
+			cmX = ( cmX & keep ) | signMask( popped.y );
+			cmY = ( cmY & keep ) | signMask( popped.z );
+			cmZ = ( cmZ & keep ) | signMask( popped.w );
+			mFirst = ( mFirst & keep ) | mGo;
+			// which lanes are still traversing / hold a hit is kept in lane masks (scalar unit) while the loop runs.  An active lane hits, descends or pops; it
+			// stays active iff it descended or popped an entry (a pop from an empty stack is a miss: derived after the loop)
 			hitM |= mHit;
-			missM |= mMiss;
-			actM &= ~( mHit | mMiss );
-			const int nAct = __builtin_popcount( (uint32_t)actM ) + __builtin_popcount( (uint32_t)( actM >> 32 ) ); // (two 32-bit counts: a 64-bit one is compared on the VALU)
-			if( nAct == 0 || ( nAct <= 64 - MVRT_REFILL_MIN_OF( FL ) && !exhausted ) ) break;
+			actM = mGo | mPopOk;
+			if( activeLanes( actM ) <= thr ) break; // one scalar bit count, one compare, one branch
 		}
+		// the lanes that were traversing when the loop was entered and neither still are nor hit have missed; lanes that were idle or parked keep their state
+		const lmask missM = __ballot( st == 1u ) & ~actM & ~hitM; // (st is not written while the loop runs: no mask of the entry state has to live across it)
 		st = LANE( hitM ) ? 3u : ( LANE( missM ) ? 2u : st );
 		childMask = LANE( mFirst ) ? 8u : ( ( LANE( cmX ) ? 1u : 0u ) | ( LANE( cmY ) ? 2u : 0u ) | ( LANE( cmZ ) ? 4u : 0u ) );
 	}
