@@ -151,23 +151,18 @@ struct Workspace
 // ---- IntersectorOctreeGPU -------------------------------------------------------------------------------
 // Everything that describes one resident octree.  The calls that make one fill a local Octree and move it into the handle when it is complete, derived
 // tables included: a handle holds a whole octree or an empty one (numberOfNodes == 0), which every entry point that reads an octree refuses on the host.
-struct Octree
+// The main arrays, the counts and the tree description are the builder's record (launch.h), taken over whole from a build and filled in by an upload; what
+// is derived from them lives here.
+struct Octree : SvoBuildResult
 {
-	DevBuf nodes, masks;
-	DevBuf psumCold; // non-embedded flavour only
-	// tree flavour (GPU-built octrees without node sharing whose masks are not embedded): `nodes` = two-level bricks, `masks` = per-node mask,
-	// treeFirst = per-node first child (reference numbering), node ranges per builder level
-	DevBuf treeFirst;
-	uint32_t tree = 0, treeRoot = 0, nBricks = 0;
-	uint32_t treeLevelBase[24] = { 0 }, treeLevelCount[24] = { 0 };
-	DevBuf attrs;
-	DevBuf morton;	 // only after build() (an upload gets them by mvrt_svo_rebuild)
+	Octree() {}
+	explicit Octree( SvoBuildResult&& built ) : SvoBuildResult( std::move( built ) ) {}
 	DevBuf kids;	 // embedded flavour: children[8] per node, 32 B per node (what the traversal reads)
 	DevBuf topTable; // per-prefix start of the nVoxelsPSum walk (SvoDev::topTable), embedded flavour
 	uint32_t topLevels = 0;
 	DevBuf cellBlocks, cellEntries; // SvoDev::cellBlocks / cellEntries, only after build()
 	uint32_t cellBits = 0;
-	mvrt_svo_info info = {}; // (emissionScale: not here, it belongs to the handle)
+	mvrt_svo_info info = {}; // bounds, dps, gridRes, levels: the counts are the record's and emissionScale the handle's (mvrt_svo_get_info)
 	uint8_t rootMask = 0;
 	uint32_t leafPsumIsPopcount = 1; // (uploads: checked, see launchCheckLeafPsum)
 	int buildFlags = 0;				 // MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK of the build, kept by edits
@@ -178,7 +173,7 @@ struct mvrt_svo
 	mutable Workspace work;		 // one per handle; users of one handle must be stream-ordered
 	float emissionScale = 7.5f; // IntersectorOctreeGPU.hpp:273
 	mvrt_pt* owner = nullptr;	 // the PathTracer this is the m_intersectorOctreeGPU of (its deferred / in-flight steps read this octree)
-	bool empty() const { return oct.info.numberOfNodes == 0; }
+	bool empty() const { return oct.nNodes == 0; }
 	void cleanUp() { oct = Octree(); } // :26-38
 	int ensureWorkspace( uint64_t nPaths = 0 ) const { return work.ensure( oct.info.levels, nPaths ); }
 	SvoDev dev() const
@@ -189,16 +184,16 @@ struct mvrt_svo
 		d.masks = oct.masks.as<uint8_t>();
 		d.psumCold = oct.psumCold.as<uint32_t>();
 		d.attrs = oct.attrs.as<uint2>();
-		d.nNodes = info.numberOfNodes;
-		d.nVoxels = info.numberOfVoxels;
+		d.nNodes = oct.nNodes;
+		d.nVoxels = oct.nVoxels;
 		d.lower = mk3( info.lower[0], info.lower[1], info.lower[2] );
 		d.upper = mk3( info.upper[0], info.upper[1], info.upper[2] );
 		d.dps = info.dps;
 		d.emissionScale = emissionScale;
-		d.hasEmission = info.hasEmission;
-		d.embedded = info.embeddedMask;
+		d.hasEmission = oct.hasEmission;
+		d.embedded = oct.embedded;
 		d.levels = info.levels;
-		d.rootIndex = info.numberOfNodes - 1; // root = last node, :250
+		d.rootIndex = oct.nNodes - 1; // root = last node, :250
 		d.rootMask = oct.rootMask;
 		d.kids = oct.kids.as<uint32_t>();
 		d.topTable = oct.topTable.as<uint2>();
@@ -223,8 +218,8 @@ static int ownerDrain( const mvrt_svo* s ) { return s && s->owner ? ptDrain( s->
 // after nodes are in place: the prefix table that shortens every nVoxelsPSum walk (voxelIndexFromPath).  7 levels = 16 MiB (measured: shade kernel 19.3 ms without, 17.2 ms with 6 levels, 16.6 ms with 7, 15.9 ms with 8 = 128 MiB, per 4 steps).
 static int buildTopTable( Octree& o, hipStream_t st )
 {
-	const uint32_t nNodes = o.info.numberOfNodes, levels = o.info.levels;
-	if( !o.info.embeddedMask || levels == 0 ) return 0;
+	const uint32_t nNodes = o.nNodes, levels = o.info.levels;
+	if( !o.embedded || levels == 0 ) return 0;
 	// children array (32 B per node) + behind it the prefix tables of the start below the root (traverse_stream.h): one buffer, one base register
 	if( o.kids.alloc( (uint64_t)nNodes * 32 + prefixTabEntries( levels ) * 4 ) ) return 1;
 	if( launchCopyKids( o.nodes.as<Node64>(), nNodes, o.kids.as<uint32_t>(), st ) ) return 1;
@@ -371,10 +366,10 @@ MVRT_EXPORT int mvrt_svo_upload( mvrt_svo* svo, const void* nodes68Host, uint32_
 	if( numberOfVoxels ) MVRT_HIP( hipMemcpyAsync( o.attrs.p, attribs8Host, (uint64_t)numberOfVoxels * 8, hipMemcpyHostToDevice, st ) );
 	if( !embeddedMask && o.psumCold.alloc( (uint64_t)numberOfNodes * 32 ) ) return 1;
 	if( launchConvertNodes( raw.as<uint8_t>(), numberOfNodes, o.nodes.as<Node64>(), o.masks.as<uint8_t>(), o.psumCold.as<uint32_t>(), embeddedMask ? 0 : 1, st ) ) return 1;
-	o.info.numberOfNodes = numberOfNodes;
-	o.info.numberOfVoxels = numberOfVoxels;
-	o.info.hasEmission = hasEmission ? 1 : 0;
-	o.info.embeddedMask = embeddedMask ? 1 : 0;
+	o.nNodes = numberOfNodes;
+	o.nVoxels = numberOfVoxels;
+	o.hasEmission = hasEmission ? 1 : 0;
+	o.embedded = embeddedMask ? 1 : 0;
 	setBounds( o.info, origin, dps, gridRes );
 	o.rootMask = ( (const uint8_t*)nodes68Host )[(uint64_t)( numberOfNodes - 1 ) * 68];
 	if( embeddedMask ) // an uploaded octree may carry any nVoxelsPSum (mvrt.h): the popcount shortcut of the last level only for canonical ones
@@ -398,7 +393,7 @@ static int buildCellIndex( Octree& o, hipStream_t st )
 {
 	static const int on = (int)mvrtKnob( "MVRT_CELL_INDEX", 1 );
 	const uint32_t L = o.info.levels;
-	if( !on || o.tree || !o.morton.p || o.info.numberOfVoxels == 0 || L == 0 || L > 14u ) return 0;
+	if( !on || o.tree || !o.morton.p || o.nVoxels == 0 || L == 0 || L > 14u ) return 0;
 	static const uint32_t blockBits = (uint32_t)mvrtKnob( "MVRT_CELL_BITS", 9 );
 	const uint32_t cellBits = 3u * ( L - 1u ) < blockBits ? 3u * ( L - 1u ) : blockBits; // 8 x 8 x 8 cells per block (fewer in octrees of fewer than 4 levels)
 	const uint64_t nBlockCodes = 1ull << ( 3u * ( L - 1u ) - cellBits );
@@ -409,7 +404,7 @@ static int buildCellIndex( Octree& o, hipStream_t st )
 	if( cnt.alloc( 4 ) || blocks.alloc( nBlockCodes * 4 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 4, st ) );
 	MVRT_HIP( hipMemsetAsync( blocks.p, 0xFF, nBlockCodes * 4, st ) );
-	if( launchNumberCellBlocks( o.morton.as<uint64_t>(), o.info.numberOfVoxels, cellBits, blocks.as<uint32_t>(), cnt.as<uint32_t>(), st ) ) return 1;
+	if( launchNumberCellBlocks( o.morton.as<uint64_t>(), o.nVoxels, cellBits, blocks.as<uint32_t>(), cnt.as<uint32_t>(), st ) ) return 1;
 	uint32_t nBlocks = 0;
 	MVRT_HIP( hipMemcpyAsync( &nBlocks, cnt.p, 4, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) );
@@ -417,7 +412,7 @@ static int buildCellIndex( Octree& o, hipStream_t st )
 	if( hipMemGetInfo( &freeB, &totalB ) != hipSuccess || bytes > freeB / 4 ) return 0;
 	if( entries.alloc( bytes ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( entries.p, 0, bytes, st ) );
-	if( launchFillCellIndex( o.morton.as<uint64_t>(), o.info.numberOfVoxels, cellBits, blocks.as<uint32_t>(), entries.as<uint2>(), st ) ) return 1;
+	if( launchFillCellIndex( o.morton.as<uint64_t>(), o.nVoxels, cellBits, blocks.as<uint32_t>(), entries.as<uint2>(), st ) ) return 1;
 	o.cellBlocks = std::move( blocks );
 	o.cellEntries = std::move( entries );
 	o.cellBits = cellBits;
@@ -428,27 +423,11 @@ static int buildCellIndex( Octree& o, hipStream_t st )
 // were built next to it) is released before the derived tables are made; from there on a failure leaves the handle empty.
 static int adoptBuild( mvrt_svo* svo, SvoBuildResult& r, const float origin[3], float dps, int gridRes, int flags )
 {
-	Octree o;
+	Octree o( std::move( r ) );
 	o.buildFlags = flags & ( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK );
-	o.nodes = std::move( r.nodes );
-	o.masks = std::move( r.masks );
-	o.psumCold = std::move( r.psumCold );
-	o.treeFirst = std::move( r.treeFirst );
-	o.attrs = std::move( r.attrs );
-	o.morton = std::move( r.morton );
-	o.tree = r.tree;
-	o.treeRoot = r.treeRoot;
-	o.nBricks = r.nBricks;
-	memcpy( o.treeLevelBase, r.treeLevelBase, sizeof( o.treeLevelBase ) );
-	memcpy( o.treeLevelCount, r.treeLevelCount, sizeof( o.treeLevelCount ) );
-	o.info.numberOfNodes = r.nNodes;
-	o.info.numberOfVoxels = r.nVoxels;
-	o.info.hasEmission = r.hasEmission;
-	o.info.embeddedMask = r.embedded; // 0 when the octree has >= 0xFFFFFF nodes (IntersectorOctreeGPU.hpp:231) or on request
-	o.info.totalDumpedVoxels = r.totalDumped;
 	setBounds( o.info, origin, dps, gridRes );
 	svo->cleanUp();
-	MVRT_HIP( hipMemcpy( &o.rootMask, o.masks.as<uint8_t>() + ( r.nNodes - 1 ), 1, hipMemcpyDeviceToHost ) );
+	MVRT_HIP( hipMemcpy( &o.rootMask, o.masks.as<uint8_t>() + ( o.nNodes - 1 ), 1, hipMemcpyDeviceToHost ) );
 	if( buildTopTable( o, nullptr ) ) return 1;
 	if( buildCellIndex( o, nullptr ) ) return 1;
 	MVRT_HIP( hipDeviceSynchronize() );
@@ -509,17 +488,17 @@ MVRT_EXPORT int mvrt_svo_edit_voxels( mvrt_svo* svo, const uint32_t* xyzDev, con
 	REQUIRE( n >= 1 && n < 0xFFFFFFFFull, "mvrt_svo_edit_voxels: entry count %llu is not in [1, 2^32-2]", (unsigned long long)n );
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene; an attribute-only edit writes in place
-	mvrt_svo_info& info = svo->oct.info;
+	const mvrt_svo_info& info = svo->oct.info;
 	SvoBuildResult r;
 	int structural = 0;
 	uint32_t he = 0;
-	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), info.numberOfVoxels, xyzDev, attribsDev, opsDev, n, (int)info.gridRes, svo->oct.buildFlags, st, &r,
+	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyzDev, attribsDev, opsDev, n, (int)info.gridRes, svo->oct.buildFlags, st, &r,
 					   &structural, &he ) )
 		return 1;
 	if( !structural )
 	{
-		info.totalDumpedVoxels = 0;
-		info.hasEmission = he;
+		svo->oct.totalDumped = 0;
+		svo->oct.hasEmission = he;
 		return 0;
 	}
 	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
@@ -530,7 +509,7 @@ MVRT_EXPORT int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uin
 	REQUIRE( svo, "mvrt_svo_read_voxels: null handle" );
 	REQUIRE( !svo->empty(), "mvrt_svo_read_voxels: no octree (build first)" );
 	REQUIRE( svo->oct.morton.p, "mvrt_svo_read_voxels: an uploaded octree keeps no Morton codes" );
-	return svoReadVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.info.numberOfVoxels, xyzDev, attribsDev, (hipStream_t)stream );
+	return svoReadVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyzDev, attribsDev, (hipStream_t)stream );
 }
 
 // The voxels of whatever the handle holds (kernels_walk.hip).  A handle that keeps Morton codes is answered from them (entry i is voxel i: the tree flavour
@@ -542,9 +521,9 @@ static WalkSource walkSource( const Octree& o )
 	s.nodes = o.nodes.as<Node64>();
 	s.masks = o.masks.as<uint8_t>();
 	s.psumCold = o.psumCold.as<uint32_t>();
-	s.nNodes = o.info.numberOfNodes;
+	s.nNodes = o.nNodes;
 	s.levels = o.info.levels;
-	s.embedded = o.info.embeddedMask;
+	s.embedded = o.embedded;
 	s.rootMask = o.rootMask;
 	return s;
 }
@@ -556,14 +535,14 @@ MVRT_EXPORT int mvrt_svo_walk_voxels( const mvrt_svo* svo, uint64_t capacity, ui
 	hipStream_t st = (hipStream_t)stream;
 	const bool fill = xyzDev || vIndexDev || attribsDev;
 	WalkResult w;
-	if( o.morton.p ) w.n = o.info.numberOfVoxels;
+	if( o.morton.p ) w.n = o.nVoxels;
 	else if( walkPaths( walkSource( o ), fill, capacity, &w, st ) ) return 1;
 	if( nOut ) *nOut = w.n;
 	if( !fill ) return 0; // the sizing call
 	REQUIRE( capacity >= w.n, "mvrt_svo_walk_voxels: capacity %llu is smaller than the %llu voxels of the octree; nothing was written", (unsigned long long)capacity,
 			 (unsigned long long)w.n );
 	if( w.n == 0 ) return 0;
-	if( launchWalkGather( o.morton.p ? o.morton.as<uint64_t>() : w.codes.as<uint64_t>(), o.morton.p ? nullptr : w.vIndex.as<uint32_t>(), o.attrs.as<uint2>(), o.info.numberOfVoxels,
+	if( launchWalkGather( o.morton.p ? o.morton.as<uint64_t>() : w.codes.as<uint64_t>(), o.morton.p ? nullptr : w.vIndex.as<uint32_t>(), o.attrs.as<uint2>(), o.nVoxels,
 						  w.n, xyzDev, vIndexDev, attribsDev, st ) )
 		return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
@@ -585,7 +564,7 @@ MVRT_EXPORT int mvrt_svo_rebuild( mvrt_svo* svo, int flags, void* stream )
 	uint64_t n = 0;
 	if( o.morton.p ) // a flavour change of a built octree: its list as it is
 	{
-		n = info.numberOfVoxels;
+		n = o.nVoxels;
 		if( morton.alloc( n * 8 ) || attrs.alloc( n * 8 ) ) return 1;
 		MVRT_HIP( hipMemcpyAsync( morton.p, o.morton.p, n * 8, hipMemcpyDeviceToDevice, st ) );
 		MVRT_HIP( hipMemcpyAsync( attrs.p, o.attrs.p, n * 8, hipMemcpyDeviceToDevice, st ) );
@@ -599,13 +578,13 @@ MVRT_EXPORT int mvrt_svo_rebuild( mvrt_svo* svo, int flags, void* stream )
 		REQUIRE( n >= 1, "mvrt_svo_rebuild: the octree holds no voxel" );
 		REQUIRE( n < 0xFFFFFFFFull, "mvrt_svo_rebuild: %llu voxels exceed the 32-bit index range of the builder", (unsigned long long)n );
 		if( attrs.alloc( n * 8 ) ) return 1;
-		if( launchWalkGather( w.codes.as<uint64_t>(), w.vIndex.as<uint32_t>(), o.attrs.as<uint2>(), info.numberOfVoxels, n, nullptr, nullptr, attrs.as<uint32_t>(), st ) ) return 1;
+		if( launchWalkGather( w.codes.as<uint64_t>(), w.vIndex.as<uint32_t>(), o.attrs.as<uint2>(), o.nVoxels, n, nullptr, nullptr, attrs.as<uint32_t>(), st ) ) return 1;
 		MVRT_HIP( hipStreamSynchronize( st ) ); // (the vIndex array is released at scope end)
 		morton = std::move( w.codes );
 	}
 	SvoBuildResult r;
 	if( svoBuildFromSorted( morton, attrs, (uint32_t)n, (int)info.gridRes, flags, st, &r ) ) return 1;
-	r.hasEmission = info.hasEmission; // the handle's flag, not recomputed: the scene renders as before
+	r.hasEmission = o.hasEmission; // the handle's flag, not recomputed: the scene renders as before
 	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
 	return adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, flags ); // (arguments are read before the old octree goes)
 }
@@ -619,7 +598,7 @@ static int surfaceSource( const mvrt_svo* svo, const char* who, SurfaceSource* s
 	REQUIRE( svo->oct.morton.p, "%s: an uploaded octree keeps no Morton codes", who );
 	const Octree& o = svo->oct;
 	s->morton = o.morton.as<uint64_t>();
-	s->nVoxels = o.info.numberOfVoxels;
+	s->nVoxels = o.nVoxels;
 	s->levels = o.info.levels;
 	s->cellBlocks = o.cellEntries.p ? o.cellBlocks.as<uint32_t>() : nullptr;
 	s->cellEntries = o.cellEntries.as<uint2>();
@@ -665,9 +644,15 @@ MVRT_EXPORT int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, ui
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );
-	*info = svo->oct.info;
+	const Octree& o = svo->oct;
+	*info = o.info;
+	info->numberOfNodes = o.nNodes;
+	info->numberOfVoxels = o.nVoxels;
+	info->hasEmission = o.hasEmission;
+	info->embeddedMask = o.embedded;
+	info->totalDumpedVoxels = o.totalDumped;
 	info->emissionScale = svo->emissionScale;
-	info->flavour = svo->oct.tree ? MVRT_FLAVOUR_TREE : ( info->embeddedMask ? MVRT_FLAVOUR_EMBEDDED : MVRT_FLAVOUR_PLAIN );
+	info->flavour = o.tree ? MVRT_FLAVOUR_TREE : ( info->embeddedMask ? MVRT_FLAVOUR_EMBEDDED : MVRT_FLAVOUR_PLAIN );
 	info->reserved = 0;
 	return 0;
 }
@@ -675,7 +660,7 @@ MVRT_EXPORT uint64_t mvrt_svo_traversal_bytes( const mvrt_svo* svo )
 {
 	if( !svo || svo->empty() ) return 0;
 	const Octree& o = svo->oct;
-	const uint64_t n = o.info.numberOfNodes;
+	const uint64_t n = o.nNodes;
 	if( o.tree ) return (uint64_t)o.nBricks * sizeof( uint4 ) + n * 5;
 	return n * sizeof( Node64 ) + n + ( o.psumCold.p ? n * 32 : 0 ) + o.topTable.bytes + o.kids.bytes + o.cellBlocks.bytes + o.cellEntries.bytes;
 }
@@ -726,7 +711,7 @@ MVRT_EXPORT int mvrt_svo_download( const mvrt_svo* svo, void* nodes68Host, void*
 {
 	REQUIRE( svo && !svo->empty(), "no octree" );
 	const Octree& o = svo->oct;
-	const uint32_t nNodes = o.info.numberOfNodes, nVoxels = o.info.numberOfVoxels;
+	const uint32_t nNodes = o.nNodes, nVoxels = o.nVoxels;
 	hipStream_t st = (hipStream_t)stream;
 	if( nodes68Host )
 	{
@@ -736,7 +721,7 @@ MVRT_EXPORT int mvrt_svo_download( const mvrt_svo* svo, void* nodes68Host, void*
 		{
 			if( launchTreeTo68( o.masks.as<uint8_t>(), o.treeFirst.as<uint32_t>(), o.treeLevelBase, o.treeLevelCount, (int)o.info.levels, nNodes, nVoxels, raw.as<uint8_t>(), st ) ) return 1;
 		}
-		else if( launchNodesTo68( o.nodes.as<Node64>(), o.masks.as<uint8_t>(), o.psumCold.as<uint32_t>(), nNodes, raw.as<uint8_t>(), o.info.embeddedMask ? 0 : 1, st ) ) return 1;
+		else if( launchNodesTo68( o.nodes.as<Node64>(), o.masks.as<uint8_t>(), o.psumCold.as<uint32_t>(), nNodes, raw.as<uint8_t>(), o.embedded ? 0 : 1, st ) ) return 1;
 		MVRT_HIP( hipMemcpyAsync( nodes68Host, raw.p, raw.bytes, hipMemcpyDeviceToHost, st ) );
 		MVRT_HIP( hipStreamSynchronize( st ) );
 	}
@@ -1656,8 +1641,8 @@ MVRT_EXPORT int mvrt_pt_to_image_async( mvrt_pt* pt, void* stream, uint8_t* rgba
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_get_steps( const mvrt_pt* pt ) { return pt ? pt->steps : 0; }
-MVRT_EXPORT uint64_t mvrt_pt_get_number_of_voxels( const mvrt_pt* pt ) { return pt ? pt->intersector->oct.info.numberOfVoxels : 0; }
-MVRT_EXPORT uint64_t mvrt_pt_get_octree_bytes( const mvrt_pt* pt ) { return pt ? (uint64_t)pt->intersector->oct.info.numberOfNodes * 68 : 0; }
+MVRT_EXPORT uint64_t mvrt_pt_get_number_of_voxels( const mvrt_pt* pt ) { return pt ? pt->intersector->oct.nVoxels : 0; }
+MVRT_EXPORT uint64_t mvrt_pt_get_octree_bytes( const mvrt_pt* pt ) { return pt ? (uint64_t)pt->intersector->oct.nNodes * 68 : 0; }
 MVRT_EXPORT int mvrt_pt_read_framebuffer( mvrt_pt* pt, void* stream, float* rgbaHost )
 {
 	REQUIRE( pt && pt->fbF32.p, "no frame buffer" );

@@ -121,13 +121,15 @@ int launchFillCellIndex( const uint64_t* morton, uint64_t n, uint32_t cellBits, 
 int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t* satOut, int cosWeighted, f3 axis, hipStream_t stream );
 
 // GPU SVO construction (svo_build.hip)
-struct SvoBuildResult // owns its arrays: a builder that fails hands nothing over and leaks nothing
+// What a build produces, and what an octree handle keeps of it (api.hip, Octree).  It owns its arrays: a builder that fails hands nothing over and leaks nothing
+struct SvoBuildResult
 {
 	DevBuf nodes, masks;
 	DevBuf psumCold; // non-embedded flavour only
 	DevBuf attrs;
-	DevBuf morton; // kept for parity checks (sorted unique codes)
-	uint32_t nNodes = 0, nVoxels = 0, hasEmission = 0, embedded = 0;
+	DevBuf morton; // sorted unique codes (an upload has none until mvrt_svo_rebuild)
+	uint32_t nNodes = 0, nVoxels = 0, hasEmission = 0;
+	uint32_t embedded = 0; // 0 when the octree has >= 0xFFFFFF nodes (IntersectorOctreeGPU.hpp:231) or on request
 	uint64_t totalDumped = 0;
 	// "tree" flavour (no DAG, masks not embedded): `nodes` holds nBricks two-level bricks, `masks` the per-node masks and `treeFirst` the
 	// per-node first-child index (reference numbering); node ranges per builder level (0 = parents of voxels)

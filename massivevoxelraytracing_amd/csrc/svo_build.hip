@@ -1105,98 +1105,46 @@ int gridFor( uint64_t n )
 	if( b < 1 ) b = 1;
 	return (int)( b > 4096 ? 4096 : b );
 }
-} // namespace
 
-static int buildFromFragments( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,
-							   uint32_t* scalarOut, SvoBuildResult* out );
-
-int svoBuildFromTriangles( const float* vertsHost, const float* colsHost, const float* emisHost, uint64_t nVertices, f3 origin, float dps, int gridRes, int flags, hipStream_t st,
-						   SvoBuildResult* out )
+// ---- host side ------------------------------------------------------------------------------------------------------------------------------
+// The builder's device scalars, one zeroed 64-byte block: [0] fragment counter of the voxelizer, [8] hasEmission of the voxel set, [16] scalarOut (the total
+// of scanCounts), [32] firstBad[2] and [48] edit counts[3] of the voxel-list calls
+struct BuildScratch
 {
-	const uint32_t nTri = (uint32_t)( nVertices / 3 );
-
-	DevBuf dVerts, dCols, dEmis, dCounter;
-	if( dVerts.alloc( nVertices * 12 ) || dCounter.alloc( 64 ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( dVerts.p, vertsHost, nVertices * 12, hipMemcpyHostToDevice, st ) );
-	if( colsHost )
+	DevBuf b;
+	unsigned long long* fragments() const { return b.as<unsigned long long>(); }
+	uint32_t* hasEmission() const { return (uint32_t*)( fragments() + 1 ); }
+	uint32_t* scalarOut() const { return (uint32_t*)( fragments() + 2 ); }
+	unsigned long long* firstBad() const { return fragments() + 4; }
+	uint32_t* counts() const { return (uint32_t*)( fragments() + 6 ); }
+	int init( hipStream_t st )
 	{
-		if( dCols.alloc( nVertices * 12 ) ) return 1;
-		MVRT_HIP( hipMemcpyAsync( dCols.p, colsHost, nVertices * 12, hipMemcpyHostToDevice, st ) );
+		if( b.alloc( 64 ) ) return 1;
+		MVRT_HIP( hipMemsetAsync( b.p, 0, 64, st ) );
+		return 0;
 	}
-	if( emisHost )
+	int initForLists( hipStream_t st ) // firstBad = none
 	{
-		if( dEmis.alloc( nVertices * 12 ) ) return 1;
-		MVRT_HIP( hipMemcpyAsync( dEmis.p, emisHost, nVertices * 12, hipMemcpyHostToDevice, st ) );
+		if( init( st ) ) return 1;
+		MVRT_HIP( hipMemsetAsync( firstBad(), 0xFF, 16, st ) );
+		return 0;
 	}
-	unsigned long long* counter = dCounter.as<unsigned long long>();
-	uint32_t* hasEmission = (uint32_t*)( counter + 1 );
-	uint32_t* scalarOut = (uint32_t*)( counter + 2 );
-	MVRT_HIP( hipMemsetAsync( dCounter.p, 0, 64, st ) );
+};
 
-	// ---- voxelize: count, allocate, emit (IntersectorOctreeGPU.hpp:81-116) ----
-	const uint32_t triGrid = divUp( nTri, 128 );
-	hipLaunchKernelGGL( kVoxelize<false>, dim3( triGrid ), dim3( 128 ), 0, st, dVerts.as<float>(), (const float*)nullptr, (const float*)nullptr, nTri, counter, origin, dps,
-						gridRes, (uint64_t*)nullptr, (uint64_t*)nullptr, ( flags & 4 ) ? 1 : 0 );
-	unsigned long long totalDumped = 0;
-	MVRT_HIP( hipMemcpyAsync( &totalDumped, counter, 8, hipMemcpyDeviceToHost, st ) );
+// second half of every stable compaction: the per-block counts a k...Count kernel left for nItems items become block offsets, their total goes to the host.
+// Waits for the stream.
+int scanCounts( const DevBuf& blockCnt, uint64_t nItems, const BuildScratch& sc, hipStream_t st, uint32_t* total )
+{
+	hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt.as<uint32_t>(), nItems, sc.scalarOut() );
+	*total = 0;
+	MVRT_HIP( hipMemcpyAsync( total, sc.scalarOut(), 4, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) );
-	if( totalDumped == 0 )
-	{
-		mvrtSetError( "mvrt_svo_build: the triangles touch no voxel of the grid" );
-		return 1;
-	}
-	if( totalDumped >= 0xFFFFFFFFull )
-	{
-		mvrtSetError( "mvrt_svo_build: %llu voxel fragments exceed the 32-bit index range of this builder", totalDumped );
-		return 1;
-	}
-	DevBuf keysA, valsA;
-	if( keysA.alloc( totalDumped * 8 ) || valsA.alloc( totalDumped * 8 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( counter, 0, 8, st ) );
-	hipLaunchKernelGGL( kVoxelize<true>, dim3( triGrid ), dim3( 128 ), 0, st, dVerts.as<float>(), dCols.as<float>(), dEmis.as<float>(), nTri, counter, origin, dps, gridRes,
-						keysA.as<uint64_t>(), valsA.as<uint64_t>(), ( flags & 4 ) ? 1 : 0 );
-
-	dVerts.release();
-	dCols.release();
-	dEmis.release();
-	return buildFromFragments( keysA, valsA, totalDumped, gridRes, flags, st, counter, hasEmission, scalarOut, out );
-}
-
-int svoBuildSynthetic( uint64_t nRandomVoxels, uint64_t seed, int gridRes, int flags, hipStream_t st, SvoBuildResult* out )
-{
-	if( nRandomVoxels == 0 || nRandomVoxels >= 0xFFFFFFFFull )
-	{
-		mvrtSetError( "mvrt_svo_build_synthetic: voxel count must be in [1, 2^32-2]" );
-		return 1;
-	}
-	DevBuf dCounter, keysA, valsA;
-	if( dCounter.alloc( 64 ) || keysA.alloc( nRandomVoxels * 8 ) || valsA.alloc( nRandomVoxels * 8 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( dCounter.p, 0, 64, st ) );
-	unsigned long long* counter = dCounter.as<unsigned long long>();
-	hipLaunchKernelGGL( kSyntheticVoxels, dim3( gridFor( nRandomVoxels ) ), dim3( BB ), 0, st, nRandomVoxels, seed, (uint32_t)gridRes, keysA.as<uint64_t>(), valsA.as<uint64_t>() );
-	return buildFromFragments( keysA, valsA, nRandomVoxels, gridRes, flags, st, counter, (uint32_t*)( counter + 1 ), (uint32_t*)( counter + 2 ), out );
-}
-
-static int sortUnique( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, DevBuf& morton, DevBuf& attrs,
-					   uint32_t* nVoxelsOut );
-static int buildLevels( DevBuf& morton, DevBuf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
-						uint32_t* scalarOut, SvoBuildResult* out );
-
-// everything after voxelization: sort + unique of the (Morton, attribute) fragments, then the levels
-static int buildFromFragments( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, unsigned long long* counter, uint32_t* hasEmission,
-							   uint32_t* scalarOut, SvoBuildResult* out )
-{
-	(void)counter;
-	const int levels = levelsOf( gridRes );
-	DevBuf morton, attrs;
-	uint32_t nVoxels = 0;
-	if( sortUnique( keysA, valsA, totalDumped, levels, st, hasEmission, scalarOut, morton, attrs, &nVoxels ) ) return 1;
-	return buildLevels( morton, attrs, nVoxels, totalDumped, gridRes, flags, st, hasEmission, scalarOut, out );
+	return 0;
 }
 
 // (keysA, valsA): totalDumped unsorted fragments (released here) -> morton / attrs: the sorted unique codes and their integer-mean attributes; *hasEmission |= any emission
-static int sortUnique( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, uint32_t* hasEmission, uint32_t* scalarOut, DevBuf& morton, DevBuf& attrs,
-					   uint32_t* nVoxelsOut )
+int sortUnique( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int levels, hipStream_t st, const BuildScratch& sc, DevBuf& morton, DevBuf& attrs,
+				uint32_t* nVoxelsOut )
 {
 	DevBuf keysB, valsB;
 	if( keysB.alloc( totalDumped * 8 ) || valsB.alloc( totalDumped * 8 ) ) return 1;
@@ -1213,264 +1161,306 @@ static int sortUnique( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDum
 	DevBuf blockCnt;
 	if( blockCnt.alloc( ( totalDumped / BB + 2 ) * 4 ) ) return 1;
 	hipLaunchKernelGGL( kUniqueCount, dim3( gridFor( totalDumped ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), (uint64_t)totalDumped, blockCnt.as<uint32_t>() );
-	hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt.as<uint32_t>(), (uint64_t)totalDumped, scalarOut );
 	uint32_t nVoxels = 0;
-	MVRT_HIP( hipMemcpyAsync( &nVoxels, scalarOut, 4, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( scanCounts( blockCnt, totalDumped, sc, st, &nVoxels ) ) return 1;
 	if( morton.alloc( (uint64_t)nVoxels * 8 ) || attrs.alloc( (uint64_t)nVoxels * 8 ) ) return 1;
 	hipLaunchKernelGGL( kUniqueEmit, dim3( gridFor( totalDumped ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), valsB.as<uint64_t>(), (uint64_t)totalDumped,
-						blockCnt.as<uint32_t>(), morton.as<uint64_t>(), attrs.as<uint2>(), hasEmission );
+						blockCnt.as<uint32_t>(), morton.as<uint64_t>(), attrs.as<uint2>(), sc.hasEmission() );
 	MVRT_HIP( hipStreamSynchronize( st ) );
 	*nVoxelsOut = nVoxels;
 	return 0;
 }
 
-// the levels of the octree over nVoxels sorted unique codes (morton / attrs are handed to *out on success); hasEmission: the device flag of the voxel set
-static int buildLevels( DevBuf& morton, DevBuf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const uint32_t* hasEmission,
-						uint32_t* scalarOut, SvoBuildResult* out )
+// The levels of one build, bottom-up.  A level turns the nInput tasks of `cur` (one per voxel, then one per node of the level below, in Morton order) into one
+// task per sibling group in `nxt`, and the groups into nodes: a DAG level de-duplicates them, a direct or tree level (no DAG) writes every group to its final slot.
+struct LevelBuild
 {
-	const int levels = levelsOf( gridRes );
-	const bool dag = !( flags & 1 );
-	DevBuf blockCnt;
-	if( blockCnt.alloc( ( (uint64_t)nVoxels / BB + 2 ) * 4 ) ) return 1;
+	hipStream_t st;
+	const BuildScratch& sc;
+	int levels, flags;
+	SvoBuildResult b; // filled as the levels go and handed over whole at the end: a failure on the way hands nothing over
+	DevBuf blockCnt, tasksA, tasksB;
+	Task *cur = nullptr, *nxt = nullptr;
+	uint32_t nInput = 0, nGroups = 0, nodeBase = 0;
+	std::vector<DevBuf> levelNodes, levelMasks; // DAG: the nodes of each level (levelMasks[l].bytes of them), concatenated at the end
+	uint32_t treeBrickBase[24] = { 0 };			// tree: first brick of each (odd) builder level
 
-	// ---- upper bound on nodes: distinct parents per level (octreeTaskInit's taskCounters, voxKernel.cu:257-265) ----
-	// counted on the host from the per-level group counts as the levels are built; the node buffer grows by level.
-	DevBuf tasksA, tasksB;
-	if( tasksA.alloc( (uint64_t)nVoxels * sizeof( Task ) ) || tasksB.alloc( (uint64_t)nVoxels * sizeof( Task ) ) ) return 1;
-	hipLaunchKernelGGL( kInitTasks, dim3( gridFor( nVoxels ) ), dim3( BB ), 0, st, morton.as<uint64_t>(), nVoxels, tasksA.as<Task>() );
-
-	std::vector<DevBuf> levelNodes, levelMasks; // per-level arrays, concatenated at the end (no DAG: one of each, already final)
-	std::vector<uint32_t> levelCount;
-	bool tree = false; // no DAG + no embedded masks: compact { mask, first child } nodes + two-level bricks instead of 64-byte lines per node
-	DevBuf treeFirst, bricks;
-	uint32_t treeLevelBase[24] = { 0 }, treeLevelCount[24] = { 0 }, treeBrickBase[24] = { 0 }, nBricks = 0;
-
-	uint32_t nInput = nVoxels;
-	uint32_t nodeBase = 0;
-	Task* cur = tasksA.as<Task>();
-	Task* nxt = tasksB.as<Task>();
-	for( int level = 0; level < levels; level++ )
+	int start( const DevBuf& morton, uint32_t nVoxels )
 	{
-		// sibling groups
+		if( blockCnt.alloc( ( (uint64_t)nVoxels / BB + 2 ) * 4 ) ) return 1;
+		if( tasksA.alloc( (uint64_t)nVoxels * sizeof( Task ) ) || tasksB.alloc( (uint64_t)nVoxels * sizeof( Task ) ) ) return 1;
+		hipLaunchKernelGGL( kInitTasks, dim3( gridFor( nVoxels ) ), dim3( BB ), 0, st, morton.as<uint64_t>(), nVoxels, tasksA.as<Task>() );
+		cur = tasksA.as<Task>();
+		nxt = tasksB.as<Task>();
+		nInput = nVoxels;
+		return 0;
+	}
+	// sibling groups of `cur`: nGroups, and in blockCnt the offsets every level kernel ranks its group heads with
+	int countGroups()
+	{
 		hipLaunchKernelGGL( kGroupCount, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>() );
-		hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt.as<uint32_t>(), (uint64_t)nInput, scalarOut );
-		uint32_t nGroups = 0;
-		MVRT_HIP( hipMemcpyAsync( &nGroups, scalarOut, 4, hipMemcpyDeviceToHost, st ) );
-		MVRT_HIP( hipStreamSynchronize( st ) );
+		return scanCounts( blockCnt, nInput, sc, st, &nGroups );
+	}
 
-		if( !dag ) // every group is a node: write it straight into the (pre-sized) final arrays
-		{
-			if( level == 0 )
-			{
-				// distinct parents per level in one pass -> exact node count -> one allocation, no concatenation copy
-				DevBuf dCounts;
-				if( dCounts.alloc( 32 * 8 ) ) return 1;
-				MVRT_HIP( hipMemsetAsync( dCounts.p, 0, 32 * 8, st ) );
-				hipLaunchKernelGGL( kLevelCounts, dim3( gridFor( nVoxels ) ), dim3( BB ), 0, st, morton.as<uint64_t>(), (uint64_t)nVoxels, levels, dCounts.as<unsigned long long>() );
-				unsigned long long hc[32];
-				MVRT_HIP( hipMemcpyAsync( hc, dCounts.p, sizeof( hc ), hipMemcpyDeviceToHost, st ) );
-				MVRT_HIP( hipStreamSynchronize( st ) );
-				unsigned long long total = 0;
-				for( int l = 0; l < levels; l++ ) total += hc[l];
-				if( total >= 0xFFFFFFFEull )
-				{
-					mvrtSetError( "mvrt_svo_build: %llu nodes exceed 32-bit node indices", total );
-					return 1;
-				}
-				tree = total >= 0xFFFFFFull || ( flags & 2 );
-				levelNodes.emplace_back();
-				levelMasks.emplace_back();
-				if( levelMasks[0].alloc( total ) ) return 1;
-				levelCount.push_back( (uint32_t)total );
-				if( tree )
-				{
-					// node ranges per builder level (0 = parents of voxels ... levels - 1 = root) and brick ranges of the odd levels
-					unsigned long long nb = 0, nBr = 0;
-					for( int l = 0; l < levels; l++ )
-					{
-						treeLevelBase[l] = (uint32_t)nb;
-						treeLevelCount[l] = (uint32_t)hc[l];
-						treeBrickBase[l] = (uint32_t)nBr;
-						nb += hc[l];
-						if( l & 1 ) nBr += hc[l];
-					}
-					nBricks = (uint32_t)nBr;
-					if( treeFirst.alloc( total * 4 ) || bricks.alloc( ( nBr ? nBr : 1 ) * sizeof( uint4 ) ) ) return 1;
-				}
-				else if( levelNodes[0].alloc( total * sizeof( Node64 ) ) ) return 1;
-			}
-			if( tree )
-			{
-				hipLaunchKernelGGL( kMakeNodesTree, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, level == 0 ? 1 : 0, levelMasks[0].as<uint8_t>(),
-									treeFirst.as<uint32_t>(), nxt );
-				if( level & 1 )
-					hipLaunchKernelGGL( kMakeBricks, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, levelMasks[0].as<uint8_t>(), treeFirst.as<uint32_t>(), treeLevelBase[level], nGroups, level - 1 == 0 ? 1 : 0,
-										level >= 2 ? treeLevelBase[level - 2] : 0u, level >= 2 ? treeBrickBase[level - 2] : 0u, bricks.as<uint4>() + treeBrickBase[level] );
-			}
-			else
-				hipLaunchKernelGGL( kMakeNodesDirect, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, levelNodes[0].as<Node64>(), levelMasks[0].as<uint8_t>(), nxt );
-			MVRT_HIP( hipStreamSynchronize( st ) );
-			nodeBase += nGroups;
-			nInput = nGroups;
-			Task* t = cur;
-			cur = nxt;
-			nxt = t;
-			continue;
-		}
+	// ---- DAG: a candidate node per group; equal-content candidates collapse onto their first group; the first occurrences become this level's nodes, numbered
+	// in group order (the creation order of the CPU reference).  *nUnique of them.  The scratch of the level is released on return.
+	int dagLevel( uint32_t* nUnique )
+	{
+		const uint64_t n = nGroups;
 		DevBuf cands, hashes, groupIds, parents, hashesS, groupS, headPos, headScan, repOf, nodeOfGroup, blockCnt2;
-		if( cands.alloc( (uint64_t)nGroups * sizeof( Cand ) ) || hashes.alloc( (uint64_t)nGroups * 8 ) || groupIds.alloc( (uint64_t)nGroups * 4 ) ||
-			parents.alloc( (uint64_t)nGroups * 8 ) || hashesS.alloc( (uint64_t)nGroups * 8 ) || groupS.alloc( (uint64_t)nGroups * 4 ) ||
-			headPos.alloc( (uint64_t)nGroups * 4 ) || headScan.alloc( (uint64_t)nGroups * 4 ) || repOf.alloc( (uint64_t)nGroups * 4 ) ||
-			nodeOfGroup.alloc( (uint64_t)nGroups * 4 ) || blockCnt2.alloc( ( (uint64_t)nGroups / BB + 2 ) * 4 ) )
+		if( cands.alloc( n * sizeof( Cand ) ) || hashes.alloc( n * 8 ) || groupIds.alloc( n * 4 ) || parents.alloc( n * 8 ) || hashesS.alloc( n * 8 ) || groupS.alloc( n * 4 ) ||
+			headPos.alloc( n * 4 ) || headScan.alloc( n * 4 ) || repOf.alloc( n * 4 ) || nodeOfGroup.alloc( n * 4 ) || blockCnt2.alloc( ( n / BB + 2 ) * 4 ) )
 			return 1;
-		hipLaunchKernelGGL( kMakeCandidates, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), cands.as<Cand>(),
-							hashes.as<uint64_t>(), groupIds.as<uint32_t>(), parents.as<uint64_t>() );
-
-		// DAG de-duplication by sorted content hash
+		const dim3 grid( gridFor( nGroups ) ), block( BB );
+		hipLaunchKernelGGL( kMakeCandidates, dim3( gridFor( nInput ) ), block, 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), cands.as<Cand>(), hashes.as<uint64_t>(),
+							groupIds.as<uint32_t>(), parents.as<uint64_t>() );
+		// de-duplication by sorted content hash: repOf[group] = the first group with its content.  Not two withCubTemp calls: each would allocate and wait for the
+		// stream; here the sort and the scan share one temporary of the larger size and the five steps are enqueued back to back, with one wait at the end
 		{
-			size_t tmpBytes = 0, tmpBytes2 = 0;
-			MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, tmpBytes, hashes.as<uint64_t>(), hashesS.as<uint64_t>(), groupIds.as<uint32_t>(), groupS.as<uint32_t>(),
-														  nGroups, 0, 64, st ) );
-			MVRT_HIP( hipcub::DeviceScan::InclusiveScan( nullptr, tmpBytes2, headPos.as<uint32_t>(), headScan.as<uint32_t>(), MaxOp(), nGroups, st ) );
+			const auto sort = [&]( void* tmp, size_t& bytes ) {
+				return hipcub::DeviceRadixSort::SortPairs( tmp, bytes, hashes.as<uint64_t>(), hashesS.as<uint64_t>(), groupIds.as<uint32_t>(), groupS.as<uint32_t>(), nGroups, 0, 64, st );
+			};
+			const auto scan = [&]( void* tmp, size_t& bytes ) {
+				return hipcub::DeviceScan::InclusiveScan( tmp, bytes, headPos.as<uint32_t>(), headScan.as<uint32_t>(), MaxOp(), nGroups, st );
+			};
+			size_t sortBytes = 0, scanBytes = 0;
+			MVRT_HIP( sort( nullptr, sortBytes ) );
+			MVRT_HIP( scan( nullptr, scanBytes ) );
 			DevBuf tmp;
-			if( tmp.alloc( tmpBytes > tmpBytes2 ? tmpBytes : tmpBytes2 ) ) return 1;
-			MVRT_HIP( hipcub::DeviceRadixSort::SortPairs( tmp.p, tmpBytes, hashes.as<uint64_t>(), hashesS.as<uint64_t>(), groupIds.as<uint32_t>(), groupS.as<uint32_t>(),
-														  nGroups, 0, 64, st ) );
-			hipLaunchKernelGGL( kMarkRuns, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, hashesS.as<uint64_t>(), groupS.as<uint32_t>(), cands.as<Cand>(), nGroups,
-								headPos.as<uint32_t>() );
-			MVRT_HIP( hipcub::DeviceScan::InclusiveScan( tmp.p, tmpBytes2, headPos.as<uint32_t>(), headScan.as<uint32_t>(), MaxOp(), nGroups, st ) );
-			hipLaunchKernelGGL( kScatterReps, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, groupS.as<uint32_t>(), headScan.as<uint32_t>(), nGroups, repOf.as<uint32_t>() );
+			if( tmp.alloc( sortBytes > scanBytes ? sortBytes : scanBytes ) ) return 1;
+			MVRT_HIP( sort( tmp.p, sortBytes ) );
+			hipLaunchKernelGGL( kMarkRuns, grid, block, 0, st, hashesS.as<uint64_t>(), groupS.as<uint32_t>(), cands.as<Cand>(), nGroups, headPos.as<uint32_t>() );
+			MVRT_HIP( scan( tmp.p, scanBytes ) );
+			hipLaunchKernelGGL( kScatterReps, grid, block, 0, st, groupS.as<uint32_t>(), headScan.as<uint32_t>(), nGroups, repOf.as<uint32_t>() );
 			MVRT_HIP( hipStreamSynchronize( st ) ); // tmp is released at scope end
 		}
 		// number the first occurrences in group order and write their nodes
-		hipLaunchKernelGGL( kFirstCount, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, repOf.as<uint32_t>(), (uint64_t)nGroups, blockCnt2.as<uint32_t>() );
-		hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt2.as<uint32_t>(), (uint64_t)nGroups, scalarOut );
-		uint32_t nUnique = 0;
-		MVRT_HIP( hipMemcpyAsync( &nUnique, scalarOut, 4, hipMemcpyDeviceToHost, st ) );
-		MVRT_HIP( hipStreamSynchronize( st ) );
+		hipLaunchKernelGGL( kFirstCount, grid, block, 0, st, repOf.as<uint32_t>(), n, blockCnt2.as<uint32_t>() );
+		if( scanCounts( blockCnt2, n, sc, st, nUnique ) ) return 1;
 		levelNodes.emplace_back();
 		levelMasks.emplace_back();
-		if( levelNodes.back().alloc( (uint64_t)nUnique * sizeof( Node64 ) ) || levelMasks.back().alloc( nUnique ) ) return 1;
-		levelCount.push_back( nUnique );
-		// kEmitNodes writes to nodes[nodeBase + rank]: pass pointers rebased so that index nodeBase lands on lvNodes[0]
-		hipLaunchKernelGGL( kEmitNodes, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, repOf.as<uint32_t>(), cands.as<Cand>(), (uint64_t)nGroups, blockCnt2.as<uint32_t>(),
-							nodeBase, levelNodes.back().as<Node64>() - nodeBase, levelMasks.back().as<uint8_t>() - nodeBase, nodeOfGroup.as<uint32_t>() );
-		hipLaunchKernelGGL( kNextTasks, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, repOf.as<uint32_t>(), nodeOfGroup.as<uint32_t>(), cands.as<Cand>(),
-							parents.as<uint64_t>(), nGroups, nxt );
+		if( levelNodes.back().alloc( (uint64_t)*nUnique * sizeof( Node64 ) ) || levelMasks.back().alloc( *nUnique ) ) return 1;
+		// kEmitNodes writes to nodes[nodeBase + rank]: pass pointers rebased so that index nodeBase lands on the level's first node
+		hipLaunchKernelGGL( kEmitNodes, grid, block, 0, st, repOf.as<uint32_t>(), cands.as<Cand>(), n, blockCnt2.as<uint32_t>(), nodeBase, levelNodes.back().as<Node64>() - nodeBase,
+							levelMasks.back().as<uint8_t>() - nodeBase, nodeOfGroup.as<uint32_t>() );
+		hipLaunchKernelGGL( kNextTasks, grid, block, 0, st, repOf.as<uint32_t>(), nodeOfGroup.as<uint32_t>(), cands.as<Cand>(), parents.as<uint64_t>(), nGroups, nxt );
 		MVRT_HIP( hipStreamSynchronize( st ) );
-		nodeBase += nUnique;
-		nInput = nGroups;
-		Task* t = cur;
-		cur = nxt;
-		nxt = t;
+		return 0;
 	}
-	if( nInput != 1 )
+	// the per-level arrays -> b.nodes / b.masks
+	int concatLevels()
 	{
-		mvrtSetError( "mvrt_svo_build: internal error, %u roots after %d levels", nInput, levels );
-		return 1;
-	}
-	const uint32_t nNodes = nodeBase;
-	DevBuf nodes, masks;
-	if( !dag )
-	{
-		nodes = std::move( levelNodes[0] ); // written in place, already final
-		masks = std::move( levelMasks[0] );
-	}
-	else
-	{
-		if( nodes.alloc( (uint64_t)nNodes * sizeof( Node64 ) ) || masks.alloc( nNodes ) ) return 1;
+		if( b.nodes.alloc( (uint64_t)nodeBase * sizeof( Node64 ) ) || b.masks.alloc( nodeBase ) ) return 1;
 		uint64_t off = 0;
 		for( size_t l = 0; l < levelNodes.size(); l++ )
 		{
-			MVRT_HIP( hipMemcpyAsync( nodes.as<Node64>() + off, levelNodes[l].p, (uint64_t)levelCount[l] * sizeof( Node64 ), hipMemcpyDeviceToDevice, st ) );
-			MVRT_HIP( hipMemcpyAsync( masks.as<uint8_t>() + off, levelMasks[l].p, levelCount[l], hipMemcpyDeviceToDevice, st ) );
-			off += levelCount[l];
+			const uint64_t count = levelMasks[l].bytes;
+			MVRT_HIP( hipMemcpyAsync( b.nodes.as<Node64>() + off, levelNodes[l].p, count * sizeof( Node64 ), hipMemcpyDeviceToDevice, st ) );
+			MVRT_HIP( hipMemcpyAsync( b.masks.as<uint8_t>() + off, levelMasks[l].p, count, hipMemcpyDeviceToDevice, st ) );
+			off += count;
 		}
 		MVRT_HIP( hipStreamSynchronize( st ) );
 		levelNodes.clear();
 		levelMasks.clear();
+		return 0;
 	}
-	if( tree ) // nothing left to convert: the traversal reads the bricks, download rebuilds the reference's nodes from { mask, first child }
+
+	// ---- no DAG: every group is a node.  Before the first level: distinct parents per level in one pass (octreeTaskInit's taskCounters, voxKernel.cu:257-265) ->
+	// exact node count -> the final arrays in one allocation each, and which of the two flavours fills them
+	int sizeNoDag( const DevBuf& morton, uint32_t nVoxels )
 	{
-		uint32_t he = 0;
-		MVRT_HIP( hipMemcpyAsync( &he, hasEmission, 4, hipMemcpyDeviceToHost, st ) );
+		DevBuf dCounts;
+		if( dCounts.alloc( 32 * 8 ) ) return 1;
+		MVRT_HIP( hipMemsetAsync( dCounts.p, 0, 32 * 8, st ) );
+		hipLaunchKernelGGL( kLevelCounts, dim3( gridFor( nVoxels ) ), dim3( BB ), 0, st, morton.as<uint64_t>(), (uint64_t)nVoxels, levels, dCounts.as<unsigned long long>() );
+		unsigned long long hc[32];
+		MVRT_HIP( hipMemcpyAsync( hc, dCounts.p, sizeof( hc ), hipMemcpyDeviceToHost, st ) );
 		MVRT_HIP( hipStreamSynchronize( st ) );
-		MVRT_HIP( hipGetLastError() );
-		out->nodes = std::move( bricks );
-		out->masks = std::move( masks );
-		out->treeFirst = std::move( treeFirst );
-		out->tree = 1;
-		out->nBricks = nBricks;
-		for( int l = 0; l < 24; l++ )
+		unsigned long long total = 0;
+		for( int l = 0; l < levels; l++ ) total += hc[l];
+		if( total >= 0xFFFFFFFEull )
 		{
-			out->treeLevelBase[l] = treeLevelBase[l];
-			out->treeLevelCount[l] = treeLevelCount[l];
+			mvrtSetError( "mvrt_svo_build: %llu nodes exceed 32-bit node indices", total );
+			return 1;
 		}
+		// no embedded masks (too many nodes, or switched off): compact { mask, first child } nodes + two-level bricks instead of 64-byte lines per node
+		b.tree = total >= 0xFFFFFFull || ( flags & 2 );
+		if( b.masks.alloc( total ) ) return 1;
+		if( !b.tree ) return b.nodes.alloc( total * sizeof( Node64 ) );
+		// node ranges per builder level (0 = parents of voxels ... levels - 1 = root) and brick ranges of the odd levels
+		unsigned long long nb = 0, nBr = 0;
+		for( int l = 0; l < levels; l++ )
+		{
+			b.treeLevelBase[l] = (uint32_t)nb;
+			b.treeLevelCount[l] = (uint32_t)hc[l];
+			treeBrickBase[l] = (uint32_t)nBr;
+			nb += hc[l];
+			if( l & 1 ) nBr += hc[l];
+		}
+		b.nBricks = (uint32_t)nBr;
 		// where the traversal starts: the root is the single node of builder level levels - 1.  Odd level: it is a brick root -> its brick.
 		// Even level: it is an "in-brick child" whose children (level levels - 2) are brick roots -> the first of them (or, for a one-level
 		// octree, voxel 0)
 		const int rl = levels - 1;
-		out->treeRoot = ( rl & 1 ) ? treeBrickBase[rl] : ( rl == 0 ? 0u : treeBrickBase[rl - 1] );
-		out->attrs = std::move( attrs );
-		out->morton = std::move( morton );
-		out->nNodes = nNodes;
-		out->nVoxels = nVoxels;
-		out->hasEmission = he;
-		out->embedded = 0;
-		out->totalDumped = totalDumped;
+		b.treeRoot = ( rl & 1 ) ? treeBrickBase[rl] : ( rl == 0 ? 0u : treeBrickBase[rl - 1] );
+		return b.treeFirst.alloc( total * 4 ) || b.nodes.alloc( ( nBr ? nBr : 1 ) * sizeof( uint4 ) );
+	}
+	int directLevel()
+	{
+		hipLaunchKernelGGL( kMakeNodesDirect, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, b.nodes.as<Node64>(),
+							b.masks.as<uint8_t>(), nxt );
+		MVRT_HIP( hipStreamSynchronize( st ) );
 		return 0;
 	}
-	const bool embed = nNodes < 0xFFFFFFu && !( flags & 2 );
-	if( embed )
+	int treeLevel( int level ) // its nodes, and for an odd level their bricks (b.nodes)
 	{
-		hipLaunchKernelGGL( kEmbedMasks, dim3( divUp( (uint64_t)nNodes * 8, BB ) ), dim3( BB ), 0, st, nodes.as<Node64>(), masks.as<uint8_t>(), nNodes );
-	}
-	DevBuf psumCold;
-	if( !embed ) // non-embedded flavour: nVoxelsPSum -> cold array, child masks -> the hot line (traverse_stream.h)
-	{
-		if( psumCold.alloc( (uint64_t)nNodes * 32 ) ) return 1;
-		if( launchSplitPsum( nodes.as<Node64>(), masks.as<uint8_t>(), psumCold.as<uint32_t>(), nNodes, st ) ) return 1;
-	}
-	uint32_t he = 0;
-	MVRT_HIP( hipMemcpyAsync( &he, hasEmission, 4, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
-	MVRT_HIP( hipGetLastError() );
-
-	out->nodes = std::move( nodes );
-	out->masks = std::move( masks );
-	out->psumCold = std::move( psumCold );
-	out->attrs = std::move( attrs );
-	out->morton = std::move( morton );
-	out->nNodes = nNodes;
-	out->nVoxels = nVoxels;
-	out->hasEmission = he;
-	out->embedded = embed ? 1 : 0;
-	out->totalDumped = totalDumped;
-	return 0;
-}
-
-// ---- voxel lists ----------------------------------------------------------------------------------------------------------------------------
-// scratch of the voxel-list calls: [0] unused, [8] hasEmission, [16] scalarOut (as buildFromFragments), [32] firstBad[2], [48] edit counts[3]
-struct ListScratch
-{
-	DevBuf b;
-	unsigned long long* base() const { return b.as<unsigned long long>(); }
-	uint32_t* hasEmission() const { return (uint32_t*)( base() + 1 ); }
-	uint32_t* scalarOut() const { return (uint32_t*)( base() + 2 ); }
-	unsigned long long* firstBad() const { return base() + 4; }
-	uint32_t* counts() const { return (uint32_t*)( base() + 6 ); }
-	int init( hipStream_t st )
-	{
-		if( b.alloc( 64 ) ) return 1;
-		MVRT_HIP( hipMemsetAsync( b.p, 0, 64, st ) );
-		MVRT_HIP( hipMemsetAsync( firstBad(), 0xFF, 16, st ) );
+		hipLaunchKernelGGL( kMakeNodesTree, dim3( gridFor( nInput ) ), dim3( BB ), 0, st, cur, (uint64_t)nInput, blockCnt.as<uint32_t>(), nodeBase, level == 0 ? 1 : 0,
+							b.masks.as<uint8_t>(), b.treeFirst.as<uint32_t>(), nxt );
+		if( level & 1 )
+			hipLaunchKernelGGL( kMakeBricks, dim3( gridFor( nGroups ) ), dim3( BB ), 0, st, b.masks.as<uint8_t>(), b.treeFirst.as<uint32_t>(), b.treeLevelBase[level], nGroups,
+								level - 1 == 0 ? 1 : 0, level >= 2 ? b.treeLevelBase[level - 2] : 0u, level >= 2 ? treeBrickBase[level - 2] : 0u,
+								b.nodes.as<uint4>() + treeBrickBase[level] );
+		MVRT_HIP( hipStreamSynchronize( st ) );
 		return 0;
+	}
+
+	// ---- 64-byte nodes, DAG or direct: child masks into the child pointers (embedded flavour), or nVoxelsPSum -> cold array and child masks -> the hot line
+	// (plain flavour, traverse_stream.h).  The tree flavour has nothing left to convert: the traversal reads the bricks, download rebuilds the reference's nodes
+	int finishNodes()
+	{
+		const uint32_t nNodes = nodeBase;
+		b.embedded = nNodes < 0xFFFFFFu && !( flags & 2 ) ? 1 : 0;
+		if( b.embedded )
+		{
+			hipLaunchKernelGGL( kEmbedMasks, dim3( divUp( (uint64_t)nNodes * 8, BB ) ), dim3( BB ), 0, st, b.nodes.as<Node64>(), b.masks.as<uint8_t>(), nNodes );
+			return 0;
+		}
+		if( b.psumCold.alloc( (uint64_t)nNodes * 32 ) ) return 1;
+		return launchSplitPsum( b.nodes.as<Node64>(), b.masks.as<uint8_t>(), b.psumCold.as<uint32_t>(), nNodes, st );
 	}
 };
 
+// the levels of the octree over nVoxels sorted unique codes (morton / attrs are handed to *out on success); sc.hasEmission(): the device flag of the voxel set
+int buildLevels( DevBuf& morton, DevBuf& attrs, uint32_t nVoxels, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const BuildScratch& sc,
+				 SvoBuildResult* out )
+{
+	const bool dag = !( flags & 1 );
+	LevelBuild lb{ st, sc, levelsOf( gridRes ), flags };
+	if( lb.start( morton, nVoxels ) ) return 1;
+	for( int level = 0; level < lb.levels; level++ )
+	{
+		if( lb.countGroups() ) return 1;
+		uint32_t nNew = lb.nGroups; // nodes of this level
+		if( dag )
+		{
+			if( lb.dagLevel( &nNew ) ) return 1;
+		}
+		else
+		{
+			if( level == 0 && lb.sizeNoDag( morton, nVoxels ) ) return 1;
+			if( lb.b.tree ? lb.treeLevel( level ) : lb.directLevel() ) return 1;
+		}
+		lb.nodeBase += nNew;
+		lb.nInput = lb.nGroups;
+		std::swap( lb.cur, lb.nxt );
+	}
+	if( lb.nInput != 1 )
+	{
+		mvrtSetError( "mvrt_svo_build: internal error, %u roots after %d levels", lb.nInput, lb.levels );
+		return 1;
+	}
+	if( dag && lb.concatLevels() ) return 1;
+	if( !lb.b.tree && lb.finishNodes() ) return 1;
+	SvoBuildResult& b = lb.b;
+	MVRT_HIP( hipMemcpyAsync( &b.hasEmission, sc.hasEmission(), 4, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	MVRT_HIP( hipGetLastError() );
+	b.attrs = std::move( attrs );
+	b.morton = std::move( morton );
+	b.nNodes = lb.nodeBase;
+	b.nVoxels = nVoxels;
+	b.totalDumped = totalDumped;
+	*out = std::move( b );
+	return 0;
+}
+
+// everything after voxelization: sort + unique of the (Morton, attribute) fragments, then the levels
+int buildFromFragments( DevBuf& keysA, DevBuf& valsA, unsigned long long totalDumped, int gridRes, int flags, hipStream_t st, const BuildScratch& sc, SvoBuildResult* out )
+{
+	DevBuf morton, attrs;
+	uint32_t nVoxels = 0;
+	if( sortUnique( keysA, valsA, totalDumped, levelsOf( gridRes ), st, sc, morton, attrs, &nVoxels ) ) return 1;
+	return buildLevels( morton, attrs, nVoxels, totalDumped, gridRes, flags, st, sc, out );
+}
+
+} // namespace
+
+int svoBuildFromTriangles( const float* vertsHost, const float* colsHost, const float* emisHost, uint64_t nVertices, f3 origin, float dps, int gridRes, int flags, hipStream_t st,
+						   SvoBuildResult* out )
+{
+	const uint32_t nTri = (uint32_t)( nVertices / 3 );
+
+	DevBuf dVerts, dCols, dEmis;
+	BuildScratch sc;
+	if( dVerts.alloc( nVertices * 12 ) || sc.init( st ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( dVerts.p, vertsHost, nVertices * 12, hipMemcpyHostToDevice, st ) );
+	if( colsHost )
+	{
+		if( dCols.alloc( nVertices * 12 ) ) return 1;
+		MVRT_HIP( hipMemcpyAsync( dCols.p, colsHost, nVertices * 12, hipMemcpyHostToDevice, st ) );
+	}
+	if( emisHost )
+	{
+		if( dEmis.alloc( nVertices * 12 ) ) return 1;
+		MVRT_HIP( hipMemcpyAsync( dEmis.p, emisHost, nVertices * 12, hipMemcpyHostToDevice, st ) );
+	}
+
+	// ---- voxelize: count, allocate, emit (IntersectorOctreeGPU.hpp:81-116) ----
+	const uint32_t triGrid = divUp( nTri, 128 );
+	hipLaunchKernelGGL( kVoxelize<false>, dim3( triGrid ), dim3( 128 ), 0, st, dVerts.as<float>(), (const float*)nullptr, (const float*)nullptr, nTri, sc.fragments(), origin, dps,
+						gridRes, (uint64_t*)nullptr, (uint64_t*)nullptr, ( flags & 4 ) ? 1 : 0 );
+	unsigned long long totalDumped = 0;
+	MVRT_HIP( hipMemcpyAsync( &totalDumped, sc.fragments(), 8, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( totalDumped == 0 )
+	{
+		mvrtSetError( "mvrt_svo_build: the triangles touch no voxel of the grid" );
+		return 1;
+	}
+	if( totalDumped >= 0xFFFFFFFFull )
+	{
+		mvrtSetError( "mvrt_svo_build: %llu voxel fragments exceed the 32-bit index range of this builder", totalDumped );
+		return 1;
+	}
+	DevBuf keysA, valsA;
+	if( keysA.alloc( totalDumped * 8 ) || valsA.alloc( totalDumped * 8 ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( sc.fragments(), 0, 8, st ) );
+	hipLaunchKernelGGL( kVoxelize<true>, dim3( triGrid ), dim3( 128 ), 0, st, dVerts.as<float>(), dCols.as<float>(), dEmis.as<float>(), nTri, sc.fragments(), origin, dps, gridRes,
+						keysA.as<uint64_t>(), valsA.as<uint64_t>(), ( flags & 4 ) ? 1 : 0 );
+
+	dVerts.release();
+	dCols.release();
+	dEmis.release();
+	return buildFromFragments( keysA, valsA, totalDumped, gridRes, flags, st, sc, out );
+}
+
+int svoBuildSynthetic( uint64_t nRandomVoxels, uint64_t seed, int gridRes, int flags, hipStream_t st, SvoBuildResult* out )
+{
+	if( nRandomVoxels == 0 || nRandomVoxels >= 0xFFFFFFFFull )
+	{
+		mvrtSetError( "mvrt_svo_build_synthetic: voxel count must be in [1, 2^32-2]" );
+		return 1;
+	}
+	BuildScratch sc;
+	DevBuf keysA, valsA;
+	if( sc.init( st ) || keysA.alloc( nRandomVoxels * 8 ) || valsA.alloc( nRandomVoxels * 8 ) ) return 1;
+	hipLaunchKernelGGL( kSyntheticVoxels, dim3( gridFor( nRandomVoxels ) ), dim3( BB ), 0, st, nRandomVoxels, seed, (uint32_t)gridRes, keysA.as<uint64_t>(), valsA.as<uint64_t>() );
+	return buildFromFragments( keysA, valsA, nRandomVoxels, gridRes, flags, st, sc, out );
+}
+
+// ---- voxel lists ----------------------------------------------------------------------------------------------------------------------------
 // encode + validate n entries into keys / vals (/ idx); a failure names the lowest offending entry
-static int encodeVoxels( const char* who, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, hipStream_t st, const ListScratch& sc,
+static int encodeVoxels( const char* who, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, hipStream_t st, const BuildScratch& sc,
 						 uint64_t* keys, uint64_t* vals, uint32_t* idx )
 {
 	const int vec = ( (uintptr_t)xyz % 16 == 0 && (uintptr_t)attribs % 16 == 0 ) ? 1 : 0;
@@ -1498,18 +1488,18 @@ static int encodeVoxels( const char* who, const uint32_t* xyz, const uint32_t* a
 
 int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n, int gridRes, int flags, hipStream_t st, SvoBuildResult* out )
 {
-	ListScratch sc;
+	BuildScratch sc;
 	DevBuf keysA, valsA;
-	if( sc.init( st ) || keysA.alloc( n * 8 ) || valsA.alloc( n * 8 ) ) return 1;
+	if( sc.initForLists( st ) || keysA.alloc( n * 8 ) || valsA.alloc( n * 8 ) ) return 1;
 	if( encodeVoxels( "mvrt_svo_build_voxels", xyz, attribs, nullptr, n, gridRes, st, sc, keysA.as<uint64_t>(), valsA.as<uint64_t>(), nullptr ) ) return 1;
-	return buildFromFragments( keysA, valsA, n, gridRes, flags, st, sc.base(), sc.hasEmission(), sc.scalarOut(), out );
+	return buildFromFragments( keysA, valsA, n, gridRes, flags, st, sc, out );
 }
 
 int svoBuildFromSorted( DevBuf& morton, DevBuf& attrs, uint32_t n, int gridRes, int flags, hipStream_t st, SvoBuildResult* out )
 {
-	ListScratch sc;
-	if( sc.init( st ) ) return 1;
-	return buildLevels( morton, attrs, n, n, gridRes, flags, st, sc.hasEmission(), sc.scalarOut(), out );
+	BuildScratch sc;
+	if( sc.initForLists( st ) ) return 1;
+	return buildLevels( morton, attrs, n, n, gridRes, flags, st, sc, out );
 }
 
 int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, int flags,
@@ -1517,9 +1507,9 @@ int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, co
 {
 	static const char* who = "mvrt_svo_edit_voxels";
 	const int levels = levelsOf( gridRes );
-	ListScratch sc;
+	BuildScratch sc;
 	DevBuf keysA, attrN, idxA, keysB, idxB;
-	if( sc.init( st ) || keysA.alloc( n * 8 ) || attrN.alloc( n * 8 ) || idxA.alloc( n * 4 ) || keysB.alloc( n * 8 ) || idxB.alloc( n * 4 ) ) return 1;
+	if( sc.initForLists( st ) || keysA.alloc( n * 8 ) || attrN.alloc( n * 8 ) || idxA.alloc( n * 4 ) || keysB.alloc( n * 8 ) || idxB.alloc( n * 4 ) ) return 1;
 	if( encodeVoxels( who, xyz, attribs, ops, n, gridRes, st, sc, keysA.as<uint64_t>(), attrN.as<uint64_t>(), idxA.as<uint32_t>() ) ) return 1;
 	// stable sort of (Morton, batch index): within a key the batch order survives, its last entry wins
 	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
@@ -1532,10 +1522,8 @@ int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, co
 	DevBuf blockCnt;
 	if( blockCnt.alloc( ( n / BB + 2 ) * 4 ) ) return 1;
 	hipLaunchKernelGGL( kEditTailCount, dim3( gridFor( n ) ), dim3( BB ), 0, st, keysB.as<uint64_t>(), n, blockCnt.as<uint32_t>() );
-	hipLaunchKernelGGL( kScanCounts, dim3( 1 ), dim3( 1024 ), 0, st, blockCnt.as<uint32_t>(), n, sc.scalarOut() );
 	uint32_t nE = 0;
-	MVRT_HIP( hipMemcpyAsync( &nE, sc.scalarOut(), 4, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( scanCounts( blockCnt, n, sc, st, &nE ) ) return 1;
 	DevBuf eKeys, eAttr, ePos, eKind, eInc, ePre;
 	if( eKeys.alloc( (uint64_t)nE * 8 ) || eAttr.alloc( (uint64_t)nE * 8 ) || ePos.alloc( (uint64_t)nE * 4 ) || eKind.alloc( nE ) || eInc.alloc( ( (uint64_t)nE + 1 ) * 8 ) ||
 		ePre.alloc( ( (uint64_t)nE + 1 ) * 8 ) )
@@ -1591,7 +1579,7 @@ int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, co
 	eInc.release();
 	ePre.release();
 	*structural = 1;
-	return buildLevels( morton, attrs, nNew, 0, gridRes, flags, st, sc.hasEmission(), sc.scalarOut(), out );
+	return buildLevels( morton, attrs, nNew, 0, gridRes, flags, st, sc, out );
 }
 
 int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t st )

@@ -147,6 +147,27 @@ def test_random_lists_equal_oracle(mv, O, res, n, flags):
     assert_svo(O, svo, m, a, he, res, flags, n)
 
 
+@pytest.fixture(scope="module")
+def cells128():
+    """the cells of a 128^3 grid in a seeded random order: any prefix is a list of distinct voxels"""
+    return np.random.default_rng(128).permutation(128 ** 3).astype(np.uint64)
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 262144, 262145])
+@pytest.mark.parametrize("flags", [0, 3])
+def test_distinct_lists_at_scan_boundaries(mv, O, cells128, n, flags):
+    """n distinct voxels: the fragment count, the voxel count and the task count of the first level are all n, so every count -> scan -> read-back of the
+    build runs at n items.  256 items fill one block of the count kernels (255 / 257: one short, one over into a second block); 262144 items are 1024
+    blocks, the last size at which the scan kernel sums one block count per thread, 262145 the first at which it sums two."""
+    xyz = decode(cells128[:n])
+    attrs = random_list(np.random.default_rng(n + flags), n, 128)[1]
+    m, a, he = O.merge_voxels(O.morton_encode_batch(xyz), attrs)
+    assert len(m) == n
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(xyz, attrs, origin=(-1.0, 0.5, 2.0), dps=0.25, gridRes=128, flags=flags)
+    assert_svo(O, svo, m, a, he, 128, flags, n)
+
+
 def test_full_grid_and_default_attributes(mv, O):
     g = np.stack(np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij"), -1).reshape(-1, 3).astype(np.uint32)
     svo = mv.IntersectorOctreeGPU()
