@@ -194,7 +194,7 @@ inline bool writePngUncompressed( const char* path, const uint8_t* rgba, int w, 
 // plus a colour per face: uchar red green blue = bytes 0..2 of the VoxelAttirb (8 bytes per voxel, colour first) of the face's voxel.
 // vertices: 3 floats each; indices: 4 per face; faceVoxel: the voxel index per face; attribs8 == nullptr: white.  Little-endian hosts only.
 inline bool writePlyQuads( const char* path, const float* vertices, uint64_t nVertices, const uint32_t* indices, const uint32_t* faceVoxel, uint64_t nFaces,
-						   const uint8_t* attribs8 )
+						   const uint8_t* attribs8, const uint8_t* faceRgb = nullptr /* 3 bytes per face: used instead of the voxel's colour */ )
 {
 	FILE* fp = std::fopen( path, "wb" );
 	if( !fp ) return false;
@@ -211,7 +211,7 @@ inline bool writePlyQuads( const char* path, const float* vertices, uint64_t nVe
 			uint8_t* r = &rec[(size_t)i * 20];
 			r[0] = 4;
 			std::memcpy( r + 1, indices + ( f0 + i ) * 4, 16 );
-			const uint8_t* c = attribs8 ? attribs8 + (uint64_t)faceVoxel[f0 + i] * 8 : nullptr;
+			const uint8_t* c = faceRgb ? faceRgb + ( f0 + i ) * 3 : ( attribs8 ? attribs8 + (uint64_t)faceVoxel[f0 + i] * 8 : nullptr );
 			for( int k = 0; k < 3; k++ ) r[17 + k] = c ? c[k] : 255;
 		}
 		ok = std::fwrite( rec.data(), 20, n, fp ) == n;

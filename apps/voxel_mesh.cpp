@@ -1,11 +1,14 @@
 // voxel_mesh -- the reference voxelizer's "Save As Mesh" (voxMesh.cpp:111-219) without the GUI: voxelize a Wavefront .obj on the GPU and write the exposed
 // faces of the voxel set as a PLY quad mesh, one colour per face from its voxel.
 //
-//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative]
+//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
 // whatever their attributes, each rectangle in the colour of its anchor voxel.  Both combine with --no-weld; a welded merged mesh has T-junctions (mvrt.h).
+// --ao: bake per-face ambient occlusion into the colours (mvrt_svo_surface_ao): of `samples` rays (a power of two up to 256, default 64; the number, if any,
+// directly follows --ao) `open` leave the face unoccluded within --ao-radius voxels (default 8), and every colour byte c becomes (c * open + samples / 2) / samples.
+// With and without --no-weld; not with --merge / --merge-any: the bake is per face and a rectangle has no single value.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <cstdio>
 #include <cstdlib>
@@ -17,7 +20,9 @@
 
 int main( int argc, char** argv )
 {
-	bool weld = true, conservative = false, merge = false, mergeAny = false;
+	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false;
+	int aoSamples = 64;
+	float aoRadiusVoxels = 8.0f;
 	std::vector<const char*> pos;
 	for( int i = 1; i < argc; i++ )
 	{
@@ -25,15 +30,33 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--merge" ) ) merge = true;
 		else if( !std::strcmp( argv[i], "--merge-any" ) ) merge = mergeAny = true;
 		else if( !std::strcmp( argv[i], "--conservative" ) ) conservative = true;
+		else if( !std::strcmp( argv[i], "--ao" ) )
+		{
+			ao = true;
+			if( i + 1 < argc && argv[i + 1][0] && std::strspn( argv[i + 1], "0123456789" ) == std::strlen( argv[i + 1] ) ) aoSamples = std::atoi( argv[++i] );
+		}
+		else if( !std::strcmp( argv[i], "--ao-radius" ) && i + 1 < argc ) aoRadiusVoxels = (float)std::atof( argv[++i] );
 		else pos.push_back( argv[i] );
 	}
 	if( pos.size() != 3 )
 	{
-		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative]\n"
+		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--ao [samples] [--ao-radius voxels]]\n"
+					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
+					 "               --ao-radius voxels (default 8); not with --merge / --merge-any\n"
 					 "  --no-weld    four vertices of its own per face instead of shared ones\n"
 					 "  --merge      merge coplanar faces of equal colour and emission into rectangles\n"
 					 "  --merge-any  merge whatever the attributes; a rectangle takes the colour of its anchor voxel\n" );
 		return pos.empty() ? 0 : 2;
+	}
+	if( ao && merge )
+	{
+		std::fprintf( stderr, "voxel_mesh: --ao cannot be combined with --merge / --merge-any: the occlusion is baked per face and a rectangle has no single value\n" );
+		return 2;
+	}
+	if( ao && ( aoSamples < 1 || aoSamples > 256 || ( aoSamples & ( aoSamples - 1 ) ) != 0 || !( aoRadiusVoxels > 0.0f ) ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: --ao needs a power of two in [1, 256] and --ao-radius a value above 0\n" );
+		return 2;
 	}
 	const int gridRes = std::atoi( pos[1] );
 	std::vector<mvrt_io::V3> vertices, vcolors, vemissions;
@@ -75,8 +98,26 @@ int main( int argc, char** argv )
 		indices.resize( faceVoxel.size() * 4 );
 		for( size_t i = 0; i < indices.size(); i++ ) indices[i] = (uint32_t)i;
 	}
+	std::vector<uint8_t> faceRgb; // --ao: the voxel's colour scaled by the open fraction of its face
+	if( ao )
+	{
+		std::vector<uint32_t> aoVoxel;
+		std::vector<uint8_t> aoDir;
+		std::vector<uint16_t> open;
+		svo.surfaceAo( aoSamples, aoRadiusVoxels * dps, aoVoxel, aoDir, open, stream );
+		if( aoVoxel != faceVoxel || aoDir != faceDir )
+		{
+			std::fprintf( stderr, "voxel_mesh: the face list of the bake differs from the mesh's\n" );
+			return 1;
+		}
+		const uint8_t* a8 = reinterpret_cast<const uint8_t*>( attribs.data() );
+		faceRgb.resize( open.size() * 3 );
+		for( size_t f = 0; f < open.size(); f++ )
+			for( int k = 0; k < 3; k++ )
+				faceRgb[f * 3 + k] = (uint8_t)( ( (uint32_t)a8[(size_t)faceVoxel[f] * 8 + k] * open[f] + (uint32_t)aoSamples / 2 ) / (uint32_t)aoSamples );
+	}
 	if( !mvrt_io::writePlyQuads( pos[2], points.data(), points.size() / 3, indices.data(), faceVoxel.data(), faceVoxel.size(),
-								 reinterpret_cast<const uint8_t*>( attribs.data() ) ) )
+								 reinterpret_cast<const uint8_t*>( attribs.data() ), ao ? faceRgb.data() : nullptr ) )
 	{
 		std::fprintf( stderr, "voxel_mesh: cannot write %s\n", pos[2] );
 		return 1;

@@ -272,6 +272,37 @@ int mvrt_trace_batch( const mvrt_svo* svo, uint64_t n, const float* roxDev, cons
 int mvrt_trace_batch_hinted( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
 							 const float* rdzDev, const uint8_t* isShadowDev, const uint64_t* originVoxelMortonDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev,
 							 uint32_t* descentsDev, void* stream );
+/* The same rays with a DISTANCE LIMIT per ray (new; every ray of the reference runs to infinity).  tMaxDev: n floats, required.  Ray i reports what mvrt_trace_batch
+ * reports for it when that hit has t <= tMax[i] -- t is the traversal's own t, in units of rd -- and a miss (MVRT_MAX_FLOAT, -1, 0) otherwise, bit for bit for every
+ * ray, the ones with zero direction components included.  A NaN tMax, 0 or a negative one therefore always gives a miss; MVRT_MAX_FLOAT and +inf give the unlimited
+ * result.  The walk ends early once everything still to come is entered beyond the limit (by a margin that covers the rounding of the entry times);
+ * descentsDev (optional) = the child fetches the limited ray made: at most those of the unlimited ray, equal to them on a reported hit.
+ * Arguments, outputs and asynchrony as for mvrt_trace_batch (nMajorDev, vIndexDev, descentsDev may be NULL).  Embedded and plain flavours, uploaded or built, up to
+ * MVRT_DEVICE_MAX_LEVELS levels (the octrees mvrt_svo_device_view accepts: the kernel is the per-thread walk of include/mvrt/device.hpp); the tree flavour is
+ * refused by name.  n = 0 succeeds without a launch.  A NULL tMaxDev, tDev or ray array is refused on the host before the handle is looked at. */
+int mvrt_trace_batch_range( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
+							const float* rdzDev, const uint8_t* isShadowDev, const float* tMaxDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev,
+							uint32_t* descentsDev, void* stream );
+/* Per-face ambient occlusion of the voxel surface (new; the reference has none).  For every face f of a list (faceVoxel, faceDir) as mvrt_svo_surface_quads /
+ * _mesh return it -- any list of (vIndex, direction) pairs is legal -- openDev[f] = how many of `samples` shadow rays leave the face's centre without being
+ * occluded within `radius`, under the contract of mvrt_trace_batch_range.
+ *   - samples = K, a power of two in [1, 256].  Sample k of direction d has the direction sampleLambertian( a_k, b_k, N_d ) of the path tracer
+ *     (renderCommon.hpp:134-151) in the deterministic math of mvrt_detmath.h, at the Hammersley point a_k = (k + 0.5) / K, b_k = the base-2 radical inverse of k
+ *     (both exact in fp32); N_d = the unit normal of direction d in the order of mvrt_svo_surface_masks (0 -Y, 1 +Y, 2 -Z, 3 +X, 4 +Z, 5 -X), its zeros +0.0.
+ *     mvrt_ao_directions returns that table, dirsHost[(d * K + k) * 3 + axis]: host only, no GPU call.  The bake uses exactly these bits.
+ *   - Origin = the face centre.  With the voxel at integer (x, y, z), decoded from its Morton code: c2 = 2 * coord + 1 on the two in-plane axes, 2 * coord (-) or
+ *     2 * coord + 2 (+) on the normal axis; ro[a] = lower[a] + (float)c2 * (0.5f * dps), each operation rounded, no FMA.  No offset along the normal: a hit
+ *     needs 0 < t, which keeps a ray from hitting the voxel it leaves.
+ *   - radius > 0 in the units of dps (the directions have unit length up to rounding); MVRT_MAX_FLOAT or +inf = unlimited (sky visibility).  NaN and values <= 0 are
+ *     refused on the host, as are other sample counts and NULL arrays (with nFaces > 0), all before the handle is looked at.
+ *   - Handles as for mvrt_svo_surface_quads (an upload is refused: "keeps no Morton codes"; an empty handle: "no octree"), except the tree flavour, which is
+ *     refused by name, and octrees above MVRT_DEVICE_MAX_LEVELS levels.  The handle is never modified.
+ *   - Every faceVoxel must be below numberOfVoxels and every faceDir below 6: checked on the device BEFORE anything is written.  Otherwise the call fails, names
+ *     the lowest offending entry and leaves openDev untouched.
+ *   - The call blocks like mvrt_svo_surface_quads.  Its scratch (the direction table) is one allocation: if that fails the call returns an error and leaks nothing. */
+int mvrt_ao_directions( int samples, float* dirsHost /* 6 * samples * 3 */ );
+int mvrt_svo_surface_ao( const mvrt_svo* svo, uint64_t nFaces, const uint32_t* faceVoxelDev, const uint8_t* faceDirDev, int samples, float radius, uint16_t* openDev /* nFaces */,
+						 void* stream );
 /* convenience: packed host arrays (n*3 floats), synchronous */
 int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const float* roHost, const float* rdHost, const uint8_t* isShadowHost, float* tHost, int32_t* nMajorHost,
 						   uint32_t* vIndexHost, uint32_t* descentsHost );

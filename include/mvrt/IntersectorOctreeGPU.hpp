@@ -251,6 +251,38 @@ struct IntersectorOctreeGPU
 	{
 		check( mvrt_trace_batch( m_handle, n, rox, roy, roz, rdx, rdy, rdz, isShadowRay, t, nMajor, vIndex, nullptr, stream ), "IntersectorOctreeGPU::intersect" );
 	}
+	// the same rays with a distance limit per ray (mvrt_trace_batch_range): the hit of intersect() where its t <= tMax[i], else a miss; descents may be nullptr
+	void intersectRange( uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz, const uint8_t* isShadowRay,
+						 const float* tMax, float* t, int32_t* nMajor, uint32_t* vIndex, uint32_t* descents, void* stream ) const
+	{
+		check( mvrt_trace_batch_range( m_handle, n, rox, roy, roz, rdx, rdy, rdz, isShadowRay, tMax, t, nMajor, vIndex, descents, stream ), "IntersectorOctreeGPU::intersectRange" );
+	}
+	// per-face ambient occlusion (mvrt_svo_surface_ao): open[f] of `samples` rays leave face f unoccluded within `radius`.  Device-pointer form
+	void surfaceAo( uint64_t nFaces, const uint32_t* faceVoxelDev, const uint8_t* faceDirDev, int samples, float radius, uint16_t* openDev, void* stream ) const
+	{
+		check( mvrt_svo_surface_ao( m_handle, nFaces, faceVoxelDev, faceDirDev, samples, radius, openDev, stream ), "IntersectorOctreeGPU::surfaceAo" );
+	}
+	// host-vector form: the faces of surfaceQuads with their occlusion
+	void surfaceAo( int samples, float radius, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<uint16_t>& open, void* stream ) const
+	{
+		const uint64_t n = surfaceQuads( 0, nullptr, nullptr, nullptr, stream );
+		faceVoxel.resize( n );
+		faceDir.resize( n );
+		open.resize( n );
+		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), o( nullptr, n * 2, stream );
+		surfaceQuads( n, (uint32_t*)v.p, (uint8_t*)d.p, nullptr, stream );
+		surfaceAo( n, (const uint32_t*)v.p, (const uint8_t*)d.p, samples, radius, (uint16_t*)o.p, stream );
+		fetch( faceVoxel, v, stream );
+		fetch( faceDir, d, stream );
+		fetch( open, o, stream );
+	}
+	// the table of occlusion ray directions (mvrt_ao_directions): 6 * samples * 3 floats, host only
+	static std::vector<float> aoDirections( int samples )
+	{
+		std::vector<float> dirs( samples > 0 ? (size_t)6 * samples * 3 : 0 );
+		check( mvrt_ao_directions( samples, dirs.data() ), "IntersectorOctreeGPU::aoDirections" );
+		return dirs;
+	}
 	bool hasEmission() const { return m_hasEmission != 0; } // :261-264
 
 	// the by-value struct a user kernel takes (include/mvrt/device.hpp: mvrt::DeviceOctree).  emissionScale is this object's m_emissionScale, so

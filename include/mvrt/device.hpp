@@ -8,6 +8,9 @@
 //     intersect( ro, rd, &t, &nMajor, &vIndex, isShadowRay )            stack kept by the thread (scratch memory)
 //     intersect( stack, ro, rd, &t, &nMajor, &vIndex, isShadowRay )     caller's stack: levels entries of 16 bytes, LDS or global
 //     intersectEx( ..., &descents )                                     + child fetches per ray (voxCommon.hpp:381)
+//     intersectRange( [stack,] ro, rd, tMax, &t, &nMajor, &vIndex, isShadowRay )   the same ray, limited to t <= tMax (see below)
+//     intersectRangeEx( ..., &descents )
+//     occluded( [stack,] ro, rd, tMax )                                 shadow ray with the limit: true when something is hit within tMax
 //     getVoxelColor( vIndex ), getVoxelEmission( vIndex, withScale ), hasEmission()
 //
 // Results equal mvrt_trace_batch's bit for bit (t, nMajor, vIndex, descents; MVRT_MAX_FLOAT / -1 / 0 on a miss, vIndex 0 for
@@ -16,6 +19,12 @@
 // 16-byte stack entries in level-indexed slots (traverse_stream.h): the pending levels are a 32-bit mask (pop = highest set
 // bit), the candidate a popped node resumes with rides in a 3-bits-per-level register, the hit voxel's path in another.  vIndex
 // is the sum of the stored nVoxelsPSum along that path, read after the hit.
+//
+// Distance limit: a ray with limit tMax reports what the unlimited ray reports when that ray hits with t <= tMax (t in units of rd), and a miss
+// otherwise -- bit for bit, for every ray, so a NaN tMax or one that is not above 0 always misses and MVRT_MAX_FLOAT / +inf change nothing.  The walk
+// stops early once the candidate child's entry time exceeds tMax by a margin that covers the fp32 rounding of the entry times along the walk
+// (DESIGN.md 5.12 derives it); rays whose slab deltas are not all finite are never cut, only filtered.  descents of a limited ray = the child
+// fetches it made: at most the unlimited ray's, equal to them on an accepted hit.
 //
 // Floating point: bit-exactness needs every product and sum rounded on its own.  Every function here that does fp32 arithmetic
 // opens with `#pragma clang fp contract(off)`, which clang honours under hipcc's default and under -ffp-contract=on.
@@ -163,6 +172,53 @@ struct DeviceOctree
 	// stack: view.levels entries (slot = tree level of the saved node)
 	__device__ void intersectEx( StackEntry* stack, float3 ro, float3 rd, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay, uint32_t* descentsOut ) const
 	{
+		walk<false>( stack, ro, rd, 0.0f, t, nMajor, vIndex, isShadowRay, descentsOut );
+	}
+
+	// the same ray limited to t <= tMax
+	__device__ void intersectRange( float3 ro, float3 rd, float tMax, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay ) const
+	{
+		StackEntry stack[MVRT_DEVICE_MAX_LEVELS];
+		uint32_t descents;
+		walk<true>( stack, ro, rd, tMax, t, nMajor, vIndex, isShadowRay, &descents );
+	}
+	__device__ void intersectRange( StackEntry* stack, float3 ro, float3 rd, float tMax, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay ) const
+	{
+		uint32_t descents;
+		walk<true>( stack, ro, rd, tMax, t, nMajor, vIndex, isShadowRay, &descents );
+	}
+	__device__ void intersectRangeEx( float3 ro, float3 rd, float tMax, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay, uint32_t* descents ) const
+	{
+		StackEntry stack[MVRT_DEVICE_MAX_LEVELS];
+		walk<true>( stack, ro, rd, tMax, t, nMajor, vIndex, isShadowRay, descents );
+	}
+	__device__ void intersectRangeEx( StackEntry* stack, float3 ro, float3 rd, float tMax, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay,
+									  uint32_t* descents ) const
+	{
+		walk<true>( stack, ro, rd, tMax, t, nMajor, vIndex, isShadowRay, descents );
+	}
+	// a shadow ray with the limit: is anything hit with t <= tMax
+	__device__ bool occluded( float3 ro, float3 rd, float tMax ) const
+	{
+		float t;
+		int nMajor;
+		uint32_t vIndex;
+		intersectRange( ro, rd, tMax, &t, &nMajor, &vIndex, true );
+		return t != detail::kMaxFloat;
+	}
+	__device__ bool occluded( StackEntry* stack, float3 ro, float3 rd, float tMax ) const
+	{
+		float t;
+		int nMajor;
+		uint32_t vIndex;
+		intersectRange( stack, ro, rd, tMax, &t, &nMajor, &vIndex, true );
+		return t != detail::kMaxFloat;
+	}
+
+	// the walk of every method above.  RANGE = false is the unlimited ray: tMax is not read and no compare is added to the loop
+	template <bool RANGE>
+	__device__ void walk( StackEntry* stack, float3 ro, float3 rd, float tMax, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay, uint32_t* descentsOut ) const
+	{
 		MVRT_DEVICE_FP_STRICT
 		using namespace detail;
 		const bool embedded = view.flavour == MVRT_FLAVOUR_EMBEDDED;
@@ -172,6 +228,7 @@ struct DeviceOctree
 		*nMajor = -1;
 		*vIndex = 0;
 		*descentsOut = 0;
+		if( RANGE && !( 0.0f < tMax ) ) return; // a hit has 0 < t: nothing lies within such a limit (NaN included)
 		// ray setup, voxCommon.hpp:240-278
 		float ix = 1.0f / rd.x, iy = 1.0f / rd.y, iz = 1.0f / rd.z;
 		uint32_t vMask = 0;
@@ -200,6 +257,22 @@ struct DeviceOctree
 		float tx1 = ( hix - ro.x ) * ix, ty1 = ( hiy - ro.y ) * iy, tz1 = ( hiz - ro.z ) * iz;
 		if( min3( tx1, ty1, tz1 ) < max3( t0x, t0y, t0z ) ) return; // misses the root box
 		const float dtx = tx1 - t0x, dty = ty1 - t0y, dtz = tz1 - t0z; // :312
+		// RANGE: the walk ends at the first candidate child entered later than `cut` = tMax + margin.  The entry times are recomputed per level, so a
+		// voxel's t can lie below the entry time of a node visited before it: the margin, 16 (levels + 2)^2 roundings of the largest slab time, bounds
+		// that.  Rays with a slab delta that is not finite (no front-to-back order) or with slab times whose sums could overflow are
+		// never cut: +inf
+		float cut = __uint_as_float( 0x7F800000u );
+		if( RANGE )
+		{
+			const bool regular = ( __float_as_uint( dtx ) & 0x7F800000u ) != 0x7F800000u && ( __float_as_uint( dty ) & 0x7F800000u ) != 0x7F800000u &&
+								 ( __float_as_uint( dtz ) & 0x7F800000u ) != 0x7F800000u;
+			if( regular )
+			{
+				const float T = smax( smax( max3( sabs( t0x ), sabs( t0y ), sabs( t0z ) ), max3( sabs( tx1 ), sabs( ty1 ), sabs( tz1 ) ) ), 7.8886090522e-31f /* 2^-100 */ );
+				const float k = (float)( 16u * ( view.levels + 2u ) * ( view.levels + 2u ) ) * 5.9604644775e-8f /* 2^-24 */;
+				if( T <= 1.2676506002e+30f /* 2^100 */ ) cut = tMax + T * k;
+			}
+		}
 
 		const detail::Line64* const lines = (const detail::Line64*)(uintptr_t)view.nodes;
 		const uint32_t* const kids = (const uint32_t*)(uintptr_t)view.kids;
@@ -221,9 +294,10 @@ struct DeviceOctree
 			{
 				if( 0.0f < S )
 				{
+					*descentsOut = descents;
+					if( RANGE && !( S <= tMax ) ) return; // the unlimited ray's hit lies beyond the limit: a miss
 					*t = S;
 					*nMajor = ( S == tx0 ) ? 1 : ( ( S == ty0 ) ? 2 : 0 );
-					*descentsOut = descents;
 					if( !isShadowRay ) *vIndex = voxelIndexFromPath( path );
 					return;
 				}
@@ -244,6 +318,11 @@ struct DeviceOctree
 				const uint32_t childIndex = childMask ^ vMask;
 				const uint32_t nextMask = childMask | mv;
 				const bool exists = embedded ? ( ( node >> ( 24u + childIndex ) ) & 1u ) != 0u : ( ( nodeMask >> childIndex ) & 1u ) != 0u;
+				if( RANGE )
+				{
+					const float x0 = ( childMask & 1u ) ? txM : tx0, y0 = ( childMask & 2u ) ? tyM : ty0, z0 = ( childMask & 4u ) ? tzM : tz0;
+					if( cut < max3( x0, y0, z0 ) ) break; // this child and every node still to come are entered beyond the limit
+				}
 				if( exists && !( u < 0.0f ) )
 				{
 					if( hasNext ) // push (:377-380)

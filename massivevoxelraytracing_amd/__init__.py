@@ -96,6 +96,9 @@ SIGNATURES = {
     "mvrt_trace_batch": (_i32, [_vp, _u64] + [_vp] * 11 + [_vp]),
     "mvrt_trace_batch_hinted": (_i32, [_vp, _u64] + [_vp] * 12 + [_vp]),
     "mvrt_trace_batch_host": (_i32, [_vp, _u64] + [_vp] * 7),
+    "mvrt_trace_batch_range": (_i32, [_vp, _u64] + [_vp] * 12 + [_vp]),
+    "mvrt_ao_directions": (_i32, [_i32, _vp]),
+    "mvrt_svo_surface_ao": (_i32, [_vp, _u64, _vp, _vp, _i32, _f32, _vp, _vp]),
     "mvrt_render_primary": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_camera_from_matrices": (_i32, [_vp, _vp, _f32, _f32, _vp]),
     "mvrt_compact_indices": (_i32, [_vp, _u64, _vp, _vp, _vp]),
@@ -264,6 +267,15 @@ def _dev_ptr(x):
     if hasattr(x, "data_ptr"):
         return x.data_ptr()
     return int(x)
+
+
+def ao_directions(samples):
+    """mvrt_ao_directions: the (6, samples, 3) float32 table of occlusion ray directions, direction d in the order of surface_masks, sample k at the Hammersley
+    point ((k + 0.5) / samples, radical inverse of k).  Host only, no GPU call."""
+    samples = int(samples)
+    out = np.zeros((6, max(samples, 0), 3), np.float32)
+    _check(lib().mvrt_ao_directions(samples, _hp(out)))
+    return out
 
 
 def camera_from_matrices(view, proj, focus=1.0, lens_r=0.0):
@@ -526,6 +538,41 @@ class IntersectorOctreeGPU:
 
     def intersect_device(self, n, rox, roy, roz, rdx, rdy, rdz, isShadow, t, nMajor, vIndex, descents=None, stream=None):
         _check(lib().mvrt_trace_batch(self._h, n, *[_dev_ptr(a) for a in (rox, roy, roz, rdx, rdy, rdz, isShadow, t, nMajor, vIndex, descents)], stream))
+
+    def intersect_range(self, ro, rd, tMax, isShadowRay=None, want_descents=False):
+        """mvrt_trace_batch_range on packed host arrays (n,3) and one limit per ray (a scalar = the same for all): the hit of intersect() where its t <= tMax, else a miss"""
+        ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
+        rd = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
+        n = len(ro)
+        lim = np.ascontiguousarray(np.broadcast_to(np.asarray(tMax, np.float32), (n,)))
+        dev = [DeviceArray.from_host(np.ascontiguousarray(a)) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
+        sh = None if isShadowRay is None else DeviceArray.from_host(np.ascontiguousarray(isShadowRay, np.uint8))
+        t, nm, vi, de = DeviceArray(n, np.float32), DeviceArray(n, np.int32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32)
+        dlim = DeviceArray.from_host(lim)
+        self.intersect_range_device(n, *dev, sh, dlim, t, nm, vi, de)
+        synchronize()
+        out = {"t": t.to_host(), "nMajor": nm.to_host(), "vIndex": vi.to_host()}
+        if want_descents:
+            out["descents"] = de.to_host()
+        return out
+
+    def intersect_range_device(self, n, rox, roy, roz, rdx, rdy, rdz, isShadow, tMax, t, nMajor=None, vIndex=None, descents=None, stream=None):
+        _check(lib().mvrt_trace_batch_range(self._h, n, *[_dev_ptr(a) for a in (rox, roy, roz, rdx, rdy, rdz, isShadow, tMax, t, nMajor, vIndex, descents)], stream))
+
+    def surface_ao_device(self, nFaces, faceVoxel, faceDir, samples, radius, open, stream=None):
+        """mvrt_svo_surface_ao into a caller device array of nFaces uint16: per face the number of `samples` occlusion rays that are open within `radius`.
+        On MvrtError nothing was written."""
+        _check(lib().mvrt_svo_surface_ao(self._h, int(nFaces), _dev_ptr(faceVoxel), _dev_ptr(faceDir), int(samples), float(np.float32(radius)), _dev_ptr(open), stream))
+
+    def surface_ao(self, samples=64, radius=None, stream=None):
+        """the exposed faces with their baked occlusion: {faceVoxel (n,) uint32, faceDir (n,) uint8, open (n,) uint16 in [0, samples]}; radius defaults to 8 * dps"""
+        if radius is None:
+            radius = np.float32(8) * np.float32(self.info().dps)
+        n = self.surface_quads_device(stream=stream)
+        fv, fd, op = DeviceArray(n, np.uint32), DeviceArray(n, np.uint8), DeviceArray(n, np.uint16)
+        self.surface_quads_device(n, fv, fd, None, stream)
+        self.surface_ao_device(n, fv, fd, samples, radius, op, stream)
+        return {"faceVoxel": fv.to_host(), "faceDir": fd.to_host(), "open": op.to_host()}
 
     def intersect_hinted(self, ro, rd, origin_voxel_morton, isShadowRay=None):
         """mvrt_trace_batch_hinted on packed host arrays: per ray the Morton code of an EXISTING voxel (or 2^64-1 = no hint) to start below the root from"""

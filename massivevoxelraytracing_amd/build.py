@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("MVRT_LIB_OUT", os.path.join(HERE, "libmvrt_hip.so"))
-SOURCES = ["api.hip", "kernels_rt.hip", "kernels_setup.hip", "svo_build.hip", "kernels_denoise.hip", "kernels_surface.hip", "kernels_walk.hip"]
+SOURCES = ["api.hip", "kernels_rt.hip", "kernels_setup.hip", "svo_build.hip", "kernels_denoise.hip", "kernels_surface.hip", "kernels_walk.hip", "kernels_range.hip"]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
     "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",
@@ -32,6 +32,7 @@ def source_digest():
     h.update("\0".join(FLAGS).encode())
     deps = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".hpp")))
     deps += [os.path.join(HERE, "..", "include", f) for f in ("mvrt.h", "mvrt_detmath.h")]
+    deps.append(os.path.join(HERE, "..", "include", "mvrt", "device.hpp"))  # kernels_range.hip is built on the public per-lane walk
     for d in deps:
         h.update(os.path.basename(d).encode() + b"\0")
         with open(d, "rb") as f:

@@ -755,6 +755,45 @@ MVRT_EXPORT int mvrt_trace_batch_hinted( const mvrt_svo* svo, uint64_t n, const 
 							 originVoxelMortonDev );
 }
 
+// Distance-limited rays and the occlusion bake (kernels_range.hip): the per-lane walk of include/mvrt/device.hpp, so the flavours of mvrt_svo_device_view.
+// Arguments are checked first, on the host, then the handle.
+static int rangeView( const mvrt_svo* svo, const char* who, mvrt_device_octree* view )
+{
+	REQUIRE( !svo->oct.tree, "%s: tree-flavour octrees (MVRT_FLAVOUR_TREE) are not supported", who );
+	return mvrt_svo_device_view( svo, view );
+}
+MVRT_EXPORT int mvrt_trace_batch_range( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
+										const float* rdzDev, const uint8_t* isShadowDev, const float* tMaxDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev,
+										uint32_t* descentsDev, void* stream )
+{
+	REQUIRE( tMaxDev, "mvrt_trace_batch_range: tMaxDev is required (one limit per ray)" );
+	REQUIRE( tDev, "mvrt_trace_batch_range: t output is required" );
+	REQUIRE( n == 0 || ( roxDev && royDev && rozDev && rdxDev && rdyDev && rdzDev ), "mvrt_trace_batch_range: null ray array" );
+	REQUIRE( svo && !svo->empty(), "mvrt_trace_batch_range: no octree (build or upload first)" );
+	mvrt_device_octree view;
+	if( rangeView( svo, "mvrt_trace_batch_range", &view ) ) return 1;
+	return launchTraceRange( view, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tMaxDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_ao_directions( int samples, float* dirsHost )
+{
+	REQUIRE( aoSamplesOk( samples ), "mvrt_ao_directions: samples = %d is not a power of two in [1, 256]", samples );
+	REQUIRE( dirsHost, "mvrt_ao_directions: null output" );
+	aoDirections( samples, dirsHost );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_surface_ao( const mvrt_svo* svo, uint64_t nFaces, const uint32_t* faceVoxelDev, const uint8_t* faceDirDev, int samples, float radius,
+									 uint16_t* openDev, void* stream )
+{
+	REQUIRE( aoSamplesOk( samples ), "mvrt_svo_surface_ao: samples = %d is not a power of two in [1, 256]", samples );
+	REQUIRE( radius > 0.0f, "mvrt_svo_surface_ao: radius %g is not greater than 0 (MVRT_MAX_FLOAT or +inf = unlimited)", (double)radius );
+	REQUIRE( nFaces == 0 || ( faceVoxelDev && faceDirDev && openDev ), "mvrt_svo_surface_ao: null faceVoxelDev, faceDirDev or openDev" );
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_ao", &s ) ) return 1;
+	mvrt_device_octree view;
+	if( rangeView( svo, "mvrt_svo_surface_ao", &view ) ) return 1;
+	return surfaceAo( view, s.morton, nFaces, faceVoxelDev, faceDirDev, samples, radius, openDev, (hipStream_t)stream );
+}
+
 MVRT_EXPORT int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const float* roHost, const float* rdHost, const uint8_t* isShadowHost, float* tHost,
 									   int32_t* nMajorHost, uint32_t* vIndexHost, uint32_t* descentsHost )
 {

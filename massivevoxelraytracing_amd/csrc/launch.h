@@ -201,3 +201,14 @@ int walkPaths( const WalkSource& s, bool fill, uint64_t fillLimit, WalkResult* o
 // per entry i < n: xyz = the decoded code, vIndexOut = v, attribs = attrs[v] with v = vIndex[i] (vIndex == nullptr: v = i); any output may be null.  Not synchronised.
 int launchWalkGather( const uint64_t* codes, const uint32_t* vIndex, const uint2* attrs, uint32_t nVoxels, uint64_t n, uint32_t* xyz, uint32_t* vIndexOut, uint32_t* attribs,
 					  hipStream_t stream );
+
+// distance-limited rays and the ambient occlusion bake (kernels_range.hip; mvrt_trace_batch_range / mvrt_ao_directions / mvrt_svo_surface_ao): the per-lane walk of
+// include/mvrt/device.hpp on the view mvrt_svo_device_view fills.  launchTraceRange is asynchronous; surfaceAo validates the entries on the device, blocks, keeps
+// its scratch in one DevBuf and writes NOTHING to `open` unless every entry is in range.
+struct mvrt_device_octree;
+int launchTraceRange( const mvrt_device_octree& view, uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz,
+					  const uint8_t* isShadow, const float* tMax, float* t, int32_t* nMajor, uint32_t* vIndex, uint32_t* descents, hipStream_t stream );
+bool aoSamplesOk( int samples );				// a power of two in [1, 256]
+void aoDirections( int samples, float* dirs ); // host only: 6 * samples * 3 floats
+int surfaceAo( const mvrt_device_octree& view, const uint64_t* morton, uint64_t nFaces, const uint32_t* faceVoxel, const uint8_t* faceDir, int samples, float radius,
+			   uint16_t* open, hipStream_t stream );
