@@ -532,7 +532,11 @@ int mvrt_pt_read_denoised( mvrt_pt* pt, void* stream, float* rgbaHost /* width*h
 /* Multi-GPU tile split (new; the reference has no multi-GPU path).  The frame is cut into the reference's own
  * 256-pixel blocks (RENDER_NUMBER_OF_THREAD, renderCommon.hpp:13) dealt round-robin: this handle renders blocks
  * b with b % tileCount == tileIndex.  Owned pixels are stored compactly in block order.  Call before
- * resize_framebuffer.  Samples depend only on (global pixel index, spp), so any split reproduces the 1-GPU image. */
+ * resize_framebuffer.  Samples depend only on (global pixel index, spp), so any split reproduces the 1-GPU image.
+ * The call leaves the handle WITHOUT a frame, in the state a failed reallocation leaves: everything sized for the old tiling is
+ * released at once (both frame buffers, feature buffers, moments, denoised image, path state), the entry points that read a
+ * frame report "no frame buffer", mvrt_pt_framebuffer_u8_dev and mvrt_pt_sample_radiance_dev return NULL and
+ * mvrt_pt_owned_pixels 0, until the next resize_framebuffer.  The options (set_aovs, set_moments, ...) are kept. */
 int mvrt_pt_set_tile( mvrt_pt* pt, int tileIndex, int tileCount );
 uint64_t mvrt_pt_owned_pixels( const mvrt_pt* pt ); /* padded to whole 256-pixel blocks */
 /* scatter gathered per-rank buffers (rank-major, each rankStridePixels float4) back to a width*height frame */

@@ -107,9 +107,10 @@ struct PathTracer
 	}
 
 	// multi-GPU extension (not in the reference): render only the 256-pixel blocks b with b % tileCount == tileIndex
-	// (the library releases the accumulation buffers here; the views are re-pointed by the next resizeFrameBufferIfNeeded)
+	// (the library releases everything of the frame here, the u8 buffer included: no view survives, the next resizeFrameBufferIfNeeded points them again)
 	void setTile( int tileIndex, int tileCount )
 	{
+		m_frameBufferU8.reset();
 		m_frameBufferF32.reset();
 		m_aovAlbedoF32.reset();
 		m_aovNormalDepthF32.reset();

@@ -1,20 +1,13 @@
-// api.hip -- the C-ABI of libmvrt_hip.so (include/mvrt.h): host objects that own device memory and
-// launch the kernels.  Mirrors the reference's host structs IntersectorOctreeGPU
-// (IntersectorOctreeGPU.hpp:21-275) and PathTracer (PathTracer.hpp:14-170) behind opaque handles.
+// api.hip -- the C-ABI of libmvrt_hip.so (include/mvrt.h), first half: the runtime pass-throughs, the octree handle (the reference's host struct
+// IntersectorOctreeGPU, IntersectorOctreeGPU.hpp:21-275, behind an opaque handle), the batch traces and the camera.  The path tracer is api_pt.hip.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
-#include <string>
-#include <utility>
 #include <vector>
 
-#include "../../include/mvrt.h"
-#include "launch.h"
+#include "api_handles.h"
 #include "traverse_stream.h" // (hint geometry: hintTabLevelsOf, prefixTabEntries)
-
-#define MVRT_EXPORT extern "C" __attribute__( ( visibility( "default" ) ) )
 
 static thread_local char g_err[1024] = "";
 void mvrtSetError( const char* fmt, ... )
@@ -25,16 +18,6 @@ void mvrtSetError( const char* fmt, ... )
 	va_end( ap );
 }
 MVRT_EXPORT const char* mvrt_last_error( void ) { return g_err; }
-
-#define REQUIRE( cond, ... )          \
-	do                                \
-	{                                 \
-		if( !( cond ) )               \
-		{                             \
-			mvrtSetError( __VA_ARGS__ ); \
-			return 1;                 \
-		}                             \
-	} while( 0 )
 
 // ---- runtime ------------------------------------------------------------------------------------------
 MVRT_EXPORT int mvrt_device_count( int* count )
@@ -120,98 +103,7 @@ MVRT_EXPORT int mvrt_test_allocation_state( uint64_t* liveBuffers, uint64_t* liv
 	return 0;
 }
 
-// scratch of the persistent traversal kernels with its owner: one per octree handle and one per pipeline slot of a path tracer
-struct Workspace
-{
-	DevBuf wsBuf, pathBuf; // spill rows + cursor, sized on demand; per-ray paths
-	TraceWorkspace ws = { nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr };
-	int ensure( uint32_t levels, uint64_t nPaths )
-	{
-		if( nPaths > ws.pathCap )
-		{
-			ws.paths = nullptr;
-			ws.pathCap = 0;
-			if( pathBuf.alloc( nPaths * 12 ) ) return 1; // 8-byte path + 4-byte t scratch per ray
-			ws.paths = pathBuf.as<uint64_t>();
-			ws.pathCap = nPaths;
-		}
-		const uint64_t lanes = traceWorkspaceLanes();
-		const uint64_t rows = 2 * (uint64_t)( levels ? levels : 1 ) + 2; // fast path: 1 row per level; irregular rays: 2 per slot
-		const uint64_t bytes = 256 + rows * lanes * ( sizeof( uint4 ) + 2 * sizeof( uint32_t ) );
-		if( wsBuf.bytes < bytes && wsBuf.alloc( bytes ) ) return 1;
-		ws.cursor = (unsigned long long*)wsBuf.p;
-		ws.spill = (uint4*)( (uint8_t*)wsBuf.p + 256 );
-		ws.spillStride = lanes;
-		ws.spillMask = (uint32_t*)( ws.spill + rows * lanes );
-		ws.spillMask2 = ws.spillMask + rows * lanes;
-		return 0;
-	}
-};
-
-// ---- IntersectorOctreeGPU -------------------------------------------------------------------------------
-// Everything that describes one resident octree.  The calls that make one fill a local Octree and move it into the handle when it is complete, derived
-// tables included: a handle holds a whole octree or an empty one (numberOfNodes == 0), which every entry point that reads an octree refuses on the host.
-// The main arrays, the counts and the tree description are the builder's record (launch.h), taken over whole from a build and filled in by an upload; what
-// is derived from them lives here.
-struct Octree : SvoBuildResult
-{
-	Octree() {}
-	explicit Octree( SvoBuildResult&& built ) : SvoBuildResult( std::move( built ) ) {}
-	DevBuf kids;	 // embedded flavour: children[8] per node, 32 B per node (what the traversal reads)
-	DevBuf topTable; // per-prefix start of the nVoxelsPSum walk (SvoDev::topTable), embedded flavour
-	uint32_t topLevels = 0;
-	DevBuf cellBlocks, cellEntries; // SvoDev::cellBlocks / cellEntries, only after build()
-	uint32_t cellBits = 0;
-	mvrt_svo_info info = {}; // bounds, dps, gridRes, levels: the counts are the record's and emissionScale the handle's (mvrt_svo_get_info)
-	uint8_t rootMask = 0;
-	uint32_t leafPsumIsPopcount = 1; // (uploads: checked, see launchCheckLeafPsum)
-	int buildFlags = 0;				 // MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK of the build, kept by edits
-};
-struct mvrt_svo
-{
-	Octree oct;
-	mutable Workspace work;		 // one per handle; users of one handle must be stream-ordered
-	float emissionScale = 7.5f; // IntersectorOctreeGPU.hpp:273
-	mvrt_pt* owner = nullptr;	 // the PathTracer this is the m_intersectorOctreeGPU of (its deferred / in-flight steps read this octree)
-	bool empty() const { return oct.nNodes == 0; }
-	void cleanUp() { oct = Octree(); } // :26-38
-	int ensureWorkspace( uint64_t nPaths = 0 ) const { return work.ensure( oct.info.levels, nPaths ); }
-	SvoDev dev() const
-	{
-		const mvrt_svo_info& info = oct.info;
-		SvoDev d;
-		d.nodes = oct.nodes.as<Node64>();
-		d.masks = oct.masks.as<uint8_t>();
-		d.psumCold = oct.psumCold.as<uint32_t>();
-		d.attrs = oct.attrs.as<uint2>();
-		d.nNodes = oct.nNodes;
-		d.nVoxels = oct.nVoxels;
-		d.lower = mk3( info.lower[0], info.lower[1], info.lower[2] );
-		d.upper = mk3( info.upper[0], info.upper[1], info.upper[2] );
-		d.dps = info.dps;
-		d.emissionScale = emissionScale;
-		d.hasEmission = oct.hasEmission;
-		d.embedded = oct.embedded;
-		d.levels = info.levels;
-		d.rootIndex = oct.nNodes - 1; // root = last node, :250
-		d.rootMask = oct.rootMask;
-		d.kids = oct.kids.as<uint32_t>();
-		d.topTable = oct.topTable.as<uint2>();
-		d.topLevels = oct.topLevels;
-		d.cellBlocks = oct.cellEntries.p ? oct.cellBlocks.as<uint32_t>() : nullptr;
-		d.cellEntries = oct.cellEntries.as<uint2>();
-		d.cellBits = oct.cellBits;
-		d.tree = oct.tree;
-		d.treeRoot = oct.treeRoot;
-		d.leafPsumIsPopcount = oct.leafPsumIsPopcount;
-		return d;
-	}
-};
-
-// The reference's step() passes m_intersectorOctreeGPU and m_hdri to the kernel BY VALUE at call time (PathTracer.hpp:150-169).  step() is
-// deferred here, so every change of state a pending or in-flight step reads is preceded by launching (flush) or finishing (drain) those steps.
-static int ptFlush( mvrt_pt* pt );
-static int ptDrain( mvrt_pt* pt );
+// ---- IntersectorOctreeGPU (the handle itself: api_handles.h, as is why its owner is flushed or drained first) --------------------------------
 static int ownerFlush( const mvrt_svo* s ) { return s && s->owner ? ptFlush( s->owner ) : 0; }
 static int ownerDrain( const mvrt_svo* s ) { return s && s->owner ? ptDrain( s->owner ) : 0; }
 
@@ -735,24 +627,27 @@ MVRT_EXPORT int mvrt_svo_download( const mvrt_svo* svo, void* nodes68Host, void*
 	return 0;
 }
 
+static int traceBatch( const char* who, const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
+					   const float* rdzDev, const uint8_t* isShadowDev, const uint64_t* originVoxelMortonDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev, uint32_t* descentsDev,
+					   void* stream )
+{
+	REQUIRE( svo && !svo->empty(), "%s: no octree (build or upload first)", who );
+	REQUIRE( tDev, "%s: t output is required", who );
+	if( svo->ensureWorkspace( vIndexDev ? n : 0 ) ) return 1;
+	return launchTraceBatch( svo->dev(), svo->work.ws, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream,
+							 originVoxelMortonDev );
+}
 MVRT_EXPORT int mvrt_trace_batch( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
 								  const float* rdzDev, const uint8_t* isShadowDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev, uint32_t* descentsDev, void* stream )
 {
-	REQUIRE( svo && !svo->empty(), "mvrt_trace_batch: no octree (build or upload first)" );
-	REQUIRE( tDev, "mvrt_trace_batch: t output is required" );
-	if( svo->ensureWorkspace( vIndexDev ? n : 0 ) ) return 1;
-	return launchTraceBatch( svo->dev(), svo->work.ws, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream );
+	return traceBatch( "mvrt_trace_batch", svo, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, nullptr, tDev, nMajorDev, vIndexDev, descentsDev, stream );
 }
-
 MVRT_EXPORT int mvrt_trace_batch_hinted( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
 										 const float* rdzDev, const uint8_t* isShadowDev, const uint64_t* originVoxelMortonDev, float* tDev, int32_t* nMajorDev, uint32_t* vIndexDev,
 										 uint32_t* descentsDev, void* stream )
 {
-	REQUIRE( svo && !svo->empty(), "mvrt_trace_batch_hinted: no octree (build or upload first)" );
-	REQUIRE( tDev, "mvrt_trace_batch_hinted: t output is required" );
-	if( svo->ensureWorkspace( vIndexDev ? n : 0 ) ) return 1;
-	return launchTraceBatch( svo->dev(), svo->work.ws, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, tDev, nMajorDev, vIndexDev, descentsDev, (hipStream_t)stream,
-							 originVoxelMortonDev );
+	return traceBatch( "mvrt_trace_batch_hinted", svo, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, isShadowDev, originVoxelMortonDev, tDev, nMajorDev, vIndexDev, descentsDev,
+					   stream );
 }
 
 // Distance-limited rays and the occlusion bake (kernels_range.hip): the per-lane walk of include/mvrt/device.hpp, so the flavours of mvrt_svo_device_view.
@@ -827,13 +722,6 @@ MVRT_EXPORT int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const fl
 	return 0;
 }
 
-static CameraPinhole cameraFrom15( const float c[15] )
-{
-	CameraPinhole cam;
-	memcpy( &cam, c, sizeof( cam ) );
-	return cam;
-}
-
 MVRT_EXPORT int mvrt_render_primary( const mvrt_svo* svo, const float camera[15], int width, int height, int showVertexColor, uint8_t* rgbaDev, float* tDev,
 									 int32_t* nMajorDev, uint32_t* vIndexDev, uint32_t* descentsDev, void* stream )
 {
@@ -876,1186 +764,5 @@ MVRT_EXPORT int mvrt_compact_indices( const uint8_t* keepDev, uint64_t n, uint32
 	if( scratch.alloc( ( n / 256 + 8 ) * 4 ) ) return 1; // (+ padding: the scan reads whole 16-byte quads)
 	if( launchCompactIndices( keepDev, n, dstIndexDev, keptDev, scratch.as<uint32_t>(), (hipStream_t)stream ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) ); // scratch is freed on return
-	return 0;
-}
-
-// ---- PMJ02 table (host), pmjSampler.hpp:14-58,114-144 -----------------------------------------------------
-namespace
-{
-struct PCG32 // renderCommon.hpp:86-110
-{
-	uint64_t state, inc;
-	void setup( uint64_t seed, uint64_t stream )
-	{
-		state = 0;
-		inc = stream * 2 + 1;
-		nextU32();
-		state += seed;
-		nextU32();
-	}
-	uint32_t nextU32()
-	{
-		uint64_t old = state;
-		state = old * 6364136223846793005ULL + inc;
-		uint32_t xs = (uint32_t)( ( ( old >> 18u ) ^ old ) >> 27u );
-		uint32_t rot = (uint32_t)( old >> 59u );
-		return ( xs >> rot ) | ( xs << ( ( -rot ) & 31 ) );
-	}
-};
-inline float uniformf( uint32_t x ) { return mvrt_u2f( ( x >> 9 ) | 0x3f800000u ) - 1.0f; } // :112-117
-
-// Helmer's stochastic generation of a pmj02 sequence; xi0 is drawn before xi1 (see DESIGN.md "PMJ order")
-void pmj02Sequence( int numSamples, float* samples, PCG32& rng )
-{
-	static const uint32_t xors[2][32] = {
-		{ 0x0, 0x0, 0x2, 0x6, 0x6, 0xe, 0x36, 0x4e, 0x16, 0x2e, 0x276, 0x6ce, 0x716, 0xc2e, 0x3076, 0x40ce, 0x116, 0x22e, 0x20676, 0x60ece, 0x61716,
-		  0xe2c2e, 0x367076, 0x4ec0ce, 0x170116, 0x2c022e, 0x2700676, 0x6c00ece, 0x7001716, 0xc002c2e, 0x30007076, 0x4000c0ce },
-		{ 0x0, 0x1, 0x3, 0x3, 0x7, 0x1b, 0x27, 0xb, 0x17, 0x13b, 0x367, 0x38b, 0x617, 0x183b, 0x2067, 0x8b, 0x117, 0x1033b, 0x30767, 0x30b8b,
-		  0x71617, 0x1b383b, 0x276067, 0xb808b, 0x160117, 0x138033b, 0x3600767, 0x3800b8b, 0x6001617, 0x1800383b, 0x20006067, 0x808b } };
-	samples[0] = uniformf( rng.nextU32() );
-	samples[1] = uniformf( rng.nextU32() );
-	for( int logN = 0; ( 1 << logN ) < numSamples; logN++ )
-	{
-		const int prevLen = 1 << logN;
-		const int nStrata = prevLen * 2;
-		const float iStrata = 1.0f / nStrata;
-		for( int i = 0; i < prevLen && ( prevLen + i ) < numSamples; i++ )
-		{
-			const int xStratum = ( (int)( samples[( i ^ xors[0][logN] ) * 2] * nStrata ) ) ^ 1;
-			const int yStratum = ( (int)( samples[( i ^ xors[1][logN] ) * 2 + 1] * nStrata ) ) ^ 1;
-			const float xi0 = uniformf( rng.nextU32() );
-			const float xi1 = uniformf( rng.nextU32() );
-			samples[( prevLen + i ) * 2] = ( xi0 + xStratum ) * iStrata;
-			samples[( prevLen + i ) * 2 + 1] = ( xi1 + yStratum ) * iStrata;
-		}
-	}
-}
-
-// Radiance RGBE reader: header lines, blank line, "-Y h +X w", then flat or new-RLE scanlines.
-int loadRgbe( const char* path, std::vector<float>& rgba, int* w, int* h )
-{
-	FILE* fp = fopen( path, "rb" );
-	REQUIRE( fp, "cannot open %s", path );
-	std::vector<uint8_t> d;
-	uint8_t tmp[65536];
-	size_t got;
-	while( ( got = fread( tmp, 1, sizeof( tmp ), fp ) ) > 0 ) d.insert( d.end(), tmp, tmp + got );
-	fclose( fp );
-	size_t pos = 0;
-	bool blank = false;
-	*w = *h = 0;
-	while( pos < d.size() )
-	{
-		size_t e = pos;
-		while( e < d.size() && d[e] != '\n' ) e++;
-		std::string line( (const char*)d.data() + pos, e - pos );
-		pos = e + 1;
-		if( !blank )
-		{
-			if( line.empty() ) blank = true;
-			continue;
-		}
-		REQUIRE( sscanf( line.c_str(), "-Y %d +X %d", h, w ) == 2, "%s: unsupported resolution line '%s'", path, line.c_str() );
-		break;
-	}
-	REQUIRE( *w > 0 && *h > 0, "%s: not a Radiance .hdr file", path );
-	const int W = *w, H = *h;
-	rgba.resize( (size_t)W * H * 4 );
-	std::vector<uint8_t> scan( (size_t)W * 4 );
-	for( int y = 0; y < H; y++ )
-	{
-		if( pos + 4 <= d.size() && W >= 8 && W < 32768 && d[pos] == 2 && d[pos + 1] == 2 && ( d[pos + 2] & 0x80 ) == 0 && ( ( d[pos + 2] << 8 ) | d[pos + 3] ) == W )
-		{
-			pos += 4;
-			for( int c = 0; c < 4; c++ )
-			{
-				int x = 0;
-				while( x < W )
-				{
-					REQUIRE( pos < d.size(), "%s: truncated RLE data", path );
-					int count = d[pos++];
-					if( count > 128 )
-					{
-						count -= 128;
-						REQUIRE( pos < d.size() && x + count <= W, "%s: bad RLE run", path );
-						uint8_t v = d[pos++];
-						for( int k = 0; k < count; k++ ) scan[( x++ ) * 4 + c] = v;
-					}
-					else
-					{
-						REQUIRE( pos + count <= d.size() && x + count <= W, "%s: bad RLE literal", path );
-						for( int k = 0; k < count; k++ ) scan[( x++ ) * 4 + c] = d[pos++];
-					}
-				}
-			}
-		}
-		else
-		{
-			REQUIRE( pos + (size_t)W * 4 <= d.size(), "%s: truncated pixel data", path );
-			memcpy( scan.data(), d.data() + pos, (size_t)W * 4 );
-			pos += (size_t)W * 4;
-		}
-		for( int x = 0; x < W; x++ )
-		{
-			const uint8_t* p = &scan[(size_t)x * 4];
-			float* o = &rgba[( (size_t)y * W + x ) * 4];
-			if( p[3] )
-			{
-				float f = mvrt_u2f( (uint32_t)( (int)p[3] - 136 + 127 ) << 23 ); // 2^(E-136), E >= 10 keeps it normal
-				if( (int)p[3] - 136 + 127 <= 0 ) f = 0.0f;
-				o[0] = p[0] * f;
-				o[1] = p[1] * f;
-				o[2] = p[2] * f;
-			}
-			else
-			{
-				o[0] = o[1] = o[2] = 0.0f;
-			}
-			o[3] = 1.0f;
-		}
-	}
-	return 0;
-}
-} // namespace
-
-// ---- PathTracer ---------------------------------------------------------------------------------------------
-struct EventProfiler : PtProfiler
-{
-	struct Rec
-	{
-		hipEvent_t a, b;
-		int cls;
-	};
-	std::vector<Rec> recs;
-	std::vector<hipEvent_t> pool;
-	double ms[3] = { 0, 0, 0 };
-	uint64_t traceLaunches = 0;
-	hipEvent_t get()
-	{
-		if( !pool.empty() )
-		{
-			hipEvent_t e = pool.back();
-			pool.pop_back();
-			return e;
-		}
-		hipEvent_t e;
-		(void)hipEventCreate( &e );
-		return e;
-	}
-	void begin( int cls, hipStream_t s ) override
-	{
-		Rec r;
-		r.a = get();
-		r.b = get();
-		r.cls = cls;
-		(void)hipEventRecord( r.a, s );
-		recs.push_back( r );
-	}
-	void end( hipStream_t s ) override { (void)hipEventRecord( recs.back().b, s ); }
-	void collect() // caller has synchronised the stream
-	{
-		for( Rec& r : recs )
-		{
-			float t = 0.0f;
-			if( hipEventElapsedTime( &t, r.a, r.b ) == hipSuccess ) ms[r.cls] += t;
-			if( r.cls == MVRT_K_TRACE ) traceLaunches++;
-			pool.push_back( r.a );
-			pool.push_back( r.b );
-		}
-		recs.clear();
-	}
-	~EventProfiler()
-	{
-		collect();
-		for( hipEvent_t e : pool ) (void)hipEventDestroy( e );
-	}
-};
-
-struct mvrt_pt
-{
-	mvrt_svo* intersector = nullptr; // m_intersectorOctreeGPU
-	DevBuf pmj;						 // m_pmj
-	struct Hdri // m_hdri: what the kernels take by value and the buffers behind it.  Replaced as a whole by a successful load
-	{
-		DevBuf pixels, primary, sat[7];
-		HdriDev dev = {};
-	};
-	Hdri hdri;
-	// frame buffers
-	DevBuf fbF32, fbU8; // m_frameBufferF32 / m_frameBufferU8
-	// first-hit feature buffers (mvrt_pt_set_aovs; off by default): float4 per owned pixel like fbF32, allocated and cleared with it
-	bool aovs = false;
-	DevBuf aovAlbedo, aovNormalDepth;
-	// luminance moments (mvrt_pt_set_moments; off by default, independent of the feature buffers): one more float4 per owned pixel, allocated and cleared with fbF32
-	bool moments = false;
-	DevBuf momentsBuf;
-	// mvrt_pt_denoise: its output (float4 per pixel of the frame) and its scratch, kept between calls; released together by a resize, set_tile and any failure
-	DevBuf denoised, denoiseScratch;
-	int width = 0, height = 0, steps = 0;
-	int tileIndex = 0, tileCount = 1;
-	uint64_t ownedPixels = 0, validOwnedPixels = 0;
-	// wavefront work buffers: one set per in-flight step.  Consecutive step() calls are pipelined on internal
-	// streams (depth slots) so that the thin late bounces of one step overlap the dense early bounces of the next;
-	// the frame-buffer additions stay in step order through an event chain.  depth 1 = everything on the caller's stream.
-	struct Slot
-	{
-		DevBuf work, dbg;
-		DevBuf aovPart; // feature buffers on: the pass's partial sums, 2 x float4 per (step, pixel) (AovBuffers::partA / partN)
-		PtBuffers buf;
-		Workspace trace;
-		hipStream_t stream = nullptr;
-		hipEvent_t accumDone = nullptr;
-	};
-	Slot slots[4];
-	// deferred execution: up to `batch` consecutive step() calls are merged into ONE wavefront pass (bigger launches,
-	// same per-sample results, frame-buffer additions still in step order).  Flushed by any consumer of the frame.
-	std::vector<CameraPinhole> pendingCams;
-	int pendingIteration = 0;
-	hipStream_t pendingStream = nullptr;
-	int batchCap = MVRT_MAX_BATCH; // footprint bound (allocWork)
-	int batch = 0; // 0 = automatic: merge steps until a pass holds ~2 full-HD steps worth of samples (see effectiveBatch)
-	int depth = 3;
-	int depthWanted = 3; // what the caller asked for; `depth` may be lower when the path state would not fit (allocWork)
-	int nextSlot = 0, lastSlot = 0;
-	DevBuf statsBuf;
-	hipEvent_t forkEv = nullptr;
-	hipEvent_t lastAccum = nullptr;
-	bool pendingJoin = false;
-	PtBuffers& buf = slots[0].buf; // slot 0 doubles as "the" buffer set for capacity / stats bookkeeping
-	bool setupDone = false;
-	bool profiling = false;
-	uint64_t testFreeBytes = 0; // != 0: allocWork budgets against this instead of hipMemGetInfo (tests of the failure path)
-	bool debugCapture = false; // keep the survivor list of every shade stage of the last pass (mvrt_pt_set_debug_capture)
-	EventProfiler prof;
-	int numCUs = 0;
-	mvrt_pt()
-	{
-		hdri.dev.scale = 1.75f; // renderCommon.hpp:480
-		for( Slot& sl : slots ) memset( &sl.buf, 0, sizeof( sl.buf ) );
-		depth = (int)mvrtKnob( "MVRT_PIPELINE_DEPTH", depth );
-		if( depth < 1 ) depth = 1;
-		if( depth > 4 ) depth = 4;
-		depthWanted = depth;
-		splitSmallPasses = mvrtKnob( "MVRT_SPLIT_SMALL", 1 ) != 0;
-		batch = (int)mvrtKnob( "MVRT_BATCH_STEPS", 0 );
-		if( batch < 0 ) batch = 0;
-		if( batch > MVRT_MAX_BATCH ) batch = MVRT_MAX_BATCH;
-	}
-	int flush( bool moreStepsFollow = false ); // launch the pending steps (defined below)
-	int launchPass( const CameraPinhole* passCams, int iteration, int nSteps, int traceGridDiv );
-	bool splitSmallPasses = true; // MVRT_SPLIT_SMALL=0 disables (A/B)
-	bool originHints = true;	  // secondary rays start below the root (mvrt_pt_set_origin_hints)
-	void releaseAovs() // (the flag stays: the next successful resize allocates them again)
-	{
-		aovAlbedo.release();
-		aovNormalDepth.release();
-		for( Slot& sl : slots ) sl.aovPart.release();
-	}
-	void releaseMoments() // with the frame, like releaseAovs (the flag stays); a denoised image belongs to the frame that is going away
-	{
-		momentsBuf.release();
-		releaseDenoised();
-	}
-	void releaseDenoised()
-	{
-		denoised.release();
-		denoiseScratch.release();
-	}
-	int allocAovFrame() // the two accumulation buffers, beside a frame buffer that exists
-	{
-		if( aovAlbedo.alloc( ownedPixels * sizeof( float4 ) ) ) return 1;
-		return aovNormalDepth.alloc( ownedPixels * sizeof( float4 ) );
-	}
-	int effectiveBatch() const // merged steps per pass, bounded so that one pass stays below ~160 M samples (~30 GB of path state)
-	{
-		uint64_t perStep = ownedPixels * MVRT_SPP_PER_STEP;
-		if( perStep == 0 ) return 1;
-		int b = batch;
-		if( b == 0 ) // automatic: big enough to amortise launch tails, small enough that several passes can pipeline
-		{
-			b = (int)( ( 66000000ull + perStep / 2 ) / perStep );
-			if( b < 1 ) b = 1;
-			if( b > MVRT_MAX_BATCH ) b = MVRT_MAX_BATCH;
-		}
-		while( b > 1 && perStep * b > 160000000ull ) b--;
-		if( b > batchCap ) b = batchCap; // lowered by allocWork when the path state would not fit the free HBM
-		return b;
-	}
-	// steps merged into the next pass: effectiveBatch(), but at most HALF of the caller's frame -- the number of steps it accumulated before its last
-	// clearFrameBuffer -- when no batch size was set: a frame that fits ONE pass has nothing to overlap that pass's launch tails and shade kernels with, two passes
-	// hide each other's (measured on a 1/2 tile share of a 64-spp frame, where the automatic batch is the whole frame: 9.23 -> 8.49 ms per step; full frame and
-	// 1/4, 1/8 shares unchanged).  Capacity is sized by effectiveBatch(), which this never exceeds.
-	int lastFrameSteps = 0;
-	int passSteps() const
-	{
-		int b = effectiveBatch();
-		if( batch == 0 && lastFrameSteps >= 2 && b > ( lastFrameSteps + 1 ) / 2 ) b = ( lastFrameSteps + 1 ) / 2;
-		return b;
-	}
-	// make `user` stream wait for every step that was issued on the internal streams
-	int join( hipStream_t user )
-	{
-		if( flush() ) return 1;
-		if( pendingJoin && lastAccum ) MVRT_HIP( hipStreamWaitEvent( user, lastAccum, 0 ) );
-		pendingJoin = false;
-		return 0;
-	}
-	int drain() // host-side: everything the internal streams hold has finished
-	{
-		if( flush() ) return 1;
-		// depth 1 runs on the caller's stream, which the caller may have destroyed since: wait for the event recorded behind the pass
-		if( lastAccum ) MVRT_HIP( hipEventSynchronize( lastAccum ) );
-		for( Slot& sl : slots )
-			if( sl.stream ) MVRT_HIP( hipStreamSynchronize( sl.stream ) );
-		pendingJoin = false;
-		pendingStream = nullptr;
-		return 0;
-	}
-	~mvrt_pt()
-	{
-		for( Slot& sl : slots )
-		{
-			if( sl.stream )
-			{
-				(void)hipStreamSynchronize( sl.stream );
-				(void)hipStreamDestroy( sl.stream );
-			}
-			if( sl.accumDone ) (void)hipEventDestroy( sl.accumDone );
-		}
-		if( forkEv ) (void)hipEventDestroy( forkEv );
-	}
-};
-
-static int ptFlush( mvrt_pt* pt ) { return pt->flush(); }
-static int ptDrain( mvrt_pt* pt ) { return pt->drain(); }
-
-MVRT_EXPORT int mvrt_pt_create( mvrt_pt** out )
-{
-	mvrt_pt* pt = new mvrt_pt();
-	pt->intersector = new mvrt_svo();
-	pt->intersector->owner = pt;
-	*out = pt;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_destroy( mvrt_pt* pt )
-{
-	if( pt )
-	{
-		mvrt_svo_destroy( pt->intersector );
-		delete pt;
-	}
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_setup( mvrt_pt* pt, void* stream )
-{
-	REQUIRE( pt, "null argument" );
-	// PMJSampler::setup, pmjSampler.hpp:114-144
-	std::vector<float> samples( (size_t)2 * MVRT_PMJ_LENGTH * MVRT_PMJ_NSEQ );
-	PCG32 rng;
-	rng.setup( 0, 2525 );
-	for( int i = 0; i < MVRT_PMJ_NSEQ; i++ ) pmj02Sequence( MVRT_PMJ_LENGTH, samples.data() + (size_t)2 * MVRT_PMJ_LENGTH * i, rng );
-	if( pt->pmj.alloc( samples.size() * 4 ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( pt->pmj.p, samples.data(), samples.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream ) );
-	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
-	int dev = 0;
-	MVRT_HIP( hipGetDevice( &dev ) );
-	hipDeviceProp_t p;
-	MVRT_HIP( hipGetDeviceProperties( &p, dev ) );
-	pt->numCUs = p.multiProcessorCount;
-	pt->setupDone = true;
-	return 0;
-}
-
-MVRT_EXPORT int mvrt_pt_download_pmj( mvrt_pt* pt, float* tableHost )
-{
-	REQUIRE( pt && pt->pmj.p && tableHost, "mvrt_pt_download_pmj: call mvrt_pt_setup first" );
-	MVRT_HIP( hipMemcpy( tableHost, pt->pmj.p, pt->pmj.bytes, hipMemcpyDeviceToHost ) );
-	return 0;
-}
-
-MVRT_EXPORT int mvrt_pt_set_tile( mvrt_pt* pt, int tileIndex, int tileCount )
-{
-	REQUIRE( pt && tileCount >= 1 && tileIndex >= 0 && tileIndex < tileCount, "bad tile %d of %d", tileIndex, tileCount );
-	if( pt->drain() ) return 1;
-	pt->tileIndex = tileIndex;
-	pt->tileCount = tileCount;
-	pt->width = pt->height = 0; // force re-allocation on the next resize
-	pt->fbF32.release();
-	pt->releaseAovs();
-	pt->releaseMoments();
-	return 0;
-}
-MVRT_EXPORT uint64_t mvrt_pt_owned_pixels( const mvrt_pt* pt ) { return pt ? pt->ownedPixels : 0; }
-
-static int allocWorkSlot( mvrt_pt* pt, mvrt_pt::Slot& sl )
-{
-	const uint64_t cap = pt->ownedPixels * MVRT_SPP_PER_STEP * pt->effectiveBatch();
-	const uint64_t nBlocks = cap / 256 + 8; // (+ padding: the scan reads whole 16-byte quads)
-	// 2 path sets x 17 arrays + 6 direction arrays + hitT + 3 sample-radiance arrays + 2 x 8-byte path arrays,
-	// 4 bytes per word; 3 byte arrays; every array is padded to 256 B so the float4 reads of Ls* stay aligned
-	const uint64_t words = cap * ( 34 + 6 + 1 + 3 + 4 );
-	const uint64_t bytes = words * 4 + cap * 3 + nBlocks * 4 + 64 * 4 + 32 * 8 + 1024 + 64 * 256;
-	if( sl.work.alloc( bytes ) ) return 1;
-	uint8_t* base = (uint8_t*)sl.work.p;
-	uint64_t off = 0;
-	auto take = [&]( uint64_t b ) {
-		void* r = base + off;
-		off += ( b + 255 ) & ~(uint64_t)255;
-		return r;
-	};
-	PtBuffers& b = sl.buf;
-	for( int s = 0; s < 2; s++ )
-	{
-		PathSet& ps = b.set[s];
-		ps.task = (uint32_t*)take( cap * 4 );
-		ps.org = (uint32_t*)take( cap * 4 );
-		float** f[] = { &ps.rox, &ps.roy, &ps.roz, &ps.rdx, &ps.rdy, &ps.rdz, &ps.Tx, &ps.Ty, &ps.Tz, &ps.Lx, &ps.Ly, &ps.Lz, &ps.nx, &ps.ny, &ps.nz };
-		for( float** q : f ) *q = (float*)take( cap * 4 );
-	}
-	float** d[] = { &b.sx, &b.sy, &b.sz, &b.ex, &b.ey, &b.ez, &b.hitT, &b.Lsx, &b.Lsy, &b.Lsz };
-	for( float** q : d ) *q = (float*)take( cap * 4 );
-	b.hitPath = (uint64_t*)take( cap * 8 );
-	b.hitEPath = (uint64_t*)take( cap * 8 );
-	b.hitN = (uint8_t*)take( cap );
-	b.hitS = (uint8_t*)take( cap );
-	b.hitE = (uint8_t*)take( cap );
-	b.blockCount = (uint32_t*)take( nBlocks * 4 );
-	b.liveCount = (uint32_t*)take( 64 * 4 );
-	b.cursors = (unsigned long long*)take( 16 * 8 );
-	b.stats = pt->statsBuf.as<unsigned long long>(); // shared by all slots (atomic tallies)
-	b.cap = cap;
-	b.selfDev = (const PtBuffers*)take( sizeof( PtBuffers ) );
-	MVRT_HIP( hipMemset( b.liveCount, 0, 64 * 4 ) );
-	MVRT_HIP( hipMemcpy( (void*)b.selfDev, &b, sizeof( PtBuffers ), hipMemcpyHostToDevice ) );
-	if( pt->aovs ) // a block of its own: the sizes above are those of a library without feature buffers
-	{
-		if( sl.aovPart.alloc( cap / MVRT_SPP_PER_STEP * 2 * sizeof( float4 ) ) ) return 1;
-	}
-	else sl.aovPart.release();
-	return 0;
-}
-static int allocWorkInner( mvrt_pt* pt );
-// What every failed (re)allocation of a frame ends in, so that nothing stale is left behind: every slot's buffer table is zeroed (cap = 0, so launchPass
-// refuses to run) and the frame is forgotten (width = height = 0, frame buffers released), so that the next resizeFrameBufferIfNeeded -- same size or
-// not -- allocates again instead of returning early onto freed memory.  Returns 1, the status of the call that failed.
-static int forgetFrame( mvrt_pt* pt )
-{
-	for( mvrt_pt::Slot& sl : pt->slots )
-	{
-		sl.work.release();
-		memset( &sl.buf, 0, sizeof( sl.buf ) );
-	}
-	pt->width = pt->height = 0;
-	pt->fbF32.release();
-	pt->fbU8.release();
-	pt->releaseAovs();
-	pt->releaseMoments();
-	return 1;
-}
-// (Re)allocates the path state of every pipeline slot
-static int allocWork( mvrt_pt* pt ) { return allocWorkInner( pt ) == 0 ? 0 : forgetFrame( pt ); }
-static int allocWorkInner( mvrt_pt* pt )
-{
-	if( pt->drain() ) return 1;
-	if( !pt->statsBuf.p )
-	{
-		if( pt->statsBuf.alloc( 64 * 8 ) ) return 1;
-		MVRT_HIP( hipMemset( pt->statsBuf.p, 0, 64 * 8 ) );
-	}
-	if( !pt->forkEv ) MVRT_HIP( hipEventCreateWithFlags( &pt->forkEv, hipEventDisableTiming ) );
-	// Footprint: every in-flight pass owns ~190 bytes of path state per sample (two ping-pong path sets, ray directions, hit records, per-sample
-	// radiance) -- depth x batch x ownedPixels x 16 x 190 B, e.g. 3 x 2 x 6.3 GB at 1920x1080 (the reference: a fixed 1.24 GB stack slab).  It
-	// must fit beside the octree: when it would take more than 70 % of the HBM that is free right now, merge fewer steps per pass first, then
-	// keep fewer passes in flight.  Results do not depend on either.
-	{
-		for( mvrt_pt::Slot& sl : pt->slots ) // (what is allocated now is about to be replaced)
-		{
-			sl.work.release();
-			sl.aovPart.release();
-			memset( &sl.buf, 0, sizeof( sl.buf ) ); // no pointer into the freed block survives a failure below
-		}
-		size_t freeB = 0, totalB = 0;
-		MVRT_HIP( hipMemGetInfo( &freeB, &totalB ) );
-		if( pt->testFreeBytes ) freeB = (size_t)pt->testFreeBytes; // mvrt_pt_set_test_free_bytes: pretend this much HBM is free (failure-path tests)
-		pt->batchCap = MVRT_MAX_BATCH;
-		pt->depth = pt->depthWanted;
-		const uint64_t budget = (uint64_t)( 0.7 * (double)freeB );
-		// (feature buffers on: + 32 B of partial sums per pixel and merged step of every pass in flight, + the two accumulation buffers)
-		auto need = [&]() {
-			const uint64_t pathState = (uint64_t)pt->depth * pt->ownedPixels * MVRT_SPP_PER_STEP * (uint64_t)pt->effectiveBatch() * 200ull;
-			const uint64_t withAovs = pt->aovs ? pathState + (uint64_t)pt->depth * pt->ownedPixels * (uint64_t)pt->effectiveBatch() * 32ull + pt->ownedPixels * 32ull : pathState;
-			return pt->moments ? withAovs + pt->ownedPixels * 16ull : withAovs; // (moments on: + their accumulation buffer; they have no per-pass state)
-		};
-		while( need() > budget && pt->effectiveBatch() > 1 ) pt->batchCap = pt->effectiveBatch() - 1;
-		while( need() > budget && pt->depth > 1 ) pt->depth--;
-		REQUIRE( need() <= budget, "frame of %llu owned pixels needs %.1f GB of path state, %.1f GB of HBM are free (split the frame into tiles: mvrt_pt_set_tile)",
-				 (unsigned long long)pt->ownedPixels, need() / 1e9, freeB / 1e9 );
-	}
-	for( int i = 0; i < 4; i++ )
-	{
-		mvrt_pt::Slot& sl = pt->slots[i];
-		if( i >= pt->depth )
-		{
-			sl.work.release();
-			sl.aovPart.release();
-			sl.trace = Workspace();
-			memset( &sl.buf, 0, sizeof( sl.buf ) );
-			continue;
-		}
-		if( allocWorkSlot( pt, sl ) ) return 1;
-		if( pt->depth > 1 && !sl.stream )
-		{
-			// (experiment knob: slot streams of different priorities live in different hardware-queue pools and are dispatched in priority order)
-			const int mode = (int)mvrtKnob( "MVRT_SLOT_PRIO", 0 );
-			int lo = 0, hi = 0;
-			MVRT_HIP( hipDeviceGetStreamPriorityRange( &lo, &hi ) );
-			const int prio = mode == 0 ? 0 : ( mode == 1 ? ( i == 0 ? hi : ( i == 2 ? lo : 0 ) ) : ( i % 2 == 0 ? hi : lo ) );
-			MVRT_HIP( hipStreamCreateWithPriority( &sl.stream, hipStreamNonBlocking, prio ) );
-		}
-		if( !sl.accumDone ) MVRT_HIP( hipEventCreateWithFlags( &sl.accumDone, hipEventDisableTiming ) );
-	}
-	pt->nextSlot = pt->lastSlot = 0;
-	pt->lastAccum = nullptr;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_clear_framebuffer( mvrt_pt* pt, void* stream )
-{
-	REQUIRE( pt && pt->fbF32.p, "no frame buffer" );
-	if( pt->join( (hipStream_t)stream ) ) return 1;
-	if( pt->steps >= 2 ) pt->lastFrameSteps = pt->steps; // the caller's frame length (passSteps); a one-step frame says nothing about the next one
-	pt->steps = 0; // PathTracer.hpp:100
-	MVRT_HIP( hipMemsetAsync( pt->fbF32.p, 0, pt->fbF32.bytes, (hipStream_t)stream ) );
-	if( pt->aovAlbedo.p ) MVRT_HIP( hipMemsetAsync( pt->aovAlbedo.p, 0, pt->aovAlbedo.bytes, (hipStream_t)stream ) );
-	if( pt->aovNormalDepth.p ) MVRT_HIP( hipMemsetAsync( pt->aovNormalDepth.p, 0, pt->aovNormalDepth.bytes, (hipStream_t)stream ) );
-	if( pt->momentsBuf.p ) MVRT_HIP( hipMemsetAsync( pt->momentsBuf.p, 0, pt->momentsBuf.bytes, (hipStream_t)stream ) );
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream, int width, int height )
-{
-	REQUIRE( pt && width > 0 && height > 0, "bad resolution %dx%d", width, height );
-	if( pt->fbF32.p && pt->width == width && pt->height == height ) return 0;
-	if( pt->drain() ) return 1;
-	const uint64_t nPix = (uint64_t)width * height;
-	const uint64_t nBlocks = ( nPix + MVRT_TILE_PIXELS - 1 ) / MVRT_TILE_PIXELS;
-	// blocks b with b % tileCount == tileIndex
-	const uint64_t myBlocks = nBlocks > (uint64_t)pt->tileIndex ? ( nBlocks - pt->tileIndex + pt->tileCount - 1 ) / pt->tileCount : 0;
-	// every rank pads to the same count so an all-gather of equal chunks works
-	const uint64_t maxBlocks = ( nBlocks + pt->tileCount - 1 ) / pt->tileCount;
-	pt->ownedPixels = maxBlocks * MVRT_TILE_PIXELS;
-	uint64_t valid = myBlocks * MVRT_TILE_PIXELS;
-	if( myBlocks > 0 )
-	{
-		const uint64_t lastGlobalBlock = ( myBlocks - 1 ) * pt->tileCount + pt->tileIndex;
-		const uint64_t endPix = ( lastGlobalBlock + 1 ) * MVRT_TILE_PIXELS;
-		if( endPix > nPix ) valid -= endPix - nPix;
-	}
-	pt->validOwnedPixels = valid;
-	pt->width = width;
-	pt->height = height;
-	// (no frame without all of its buffers)
-	pt->releaseDenoised(); // (a denoised image of the old size)
-	if( pt->fbF32.alloc( pt->ownedPixels * sizeof( float4 ) ) || pt->fbU8.alloc( pt->ownedPixels * sizeof( uchar4 ) ) || ( pt->aovs && pt->allocAovFrame() ) ||
-		( pt->moments && pt->momentsBuf.alloc( pt->ownedPixels * sizeof( float4 ) ) ) )
-		return forgetFrame( pt );
-	if( allocWork( pt ) ) return 1;
-	return mvrt_pt_clear_framebuffer( pt, stream ); // :88
-}
-
-MVRT_EXPORT int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaHost, int width, int height, const float* rgbaPrimaryHost, int widthPrimary,
-								   int heightPrimary )
-{
-	REQUIRE( pt && rgbaHost && width > 0 && height > 0, "mvrt_pt_load_hdri: bad image" );
-	if( pt->drain() ) return 1;
-	hipStream_t st = (hipStream_t)stream;
-	const uint64_t n = (uint64_t)width * height;
-	mvrt_pt::Hdri h; // built aside: a failure leaves the map that is loaded (or none) in place
-	if( h.pixels.alloc( n * 16 ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( h.pixels.p, rgbaHost, n * 16, hipMemcpyHostToDevice, st ) );
-	DevBuf satF64;
-	if( satF64.alloc( n * 8 ) ) return 1;
-	// renderCommon.hpp:243-311: uniform table, then one cosine-weighted table per axis
-	const f3 axes[6] = { mk3( 1, 0, 0 ), mk3( -1, 0, 0 ), mk3( 0, 1, 0 ), mk3( 0, -1, 0 ), mk3( 0, 0, 1 ), mk3( 0, 0, -1 ) };
-	for( int i = 0; i < 7; i++ )
-	{
-		if( h.sat[i].alloc( n * 4 ) ) return 1;
-		if( launchHdriSat( h.pixels.as<float4>(), width, height, satF64.as<double>(), h.sat[i].as<uint32_t>(), i > 0, i > 0 ? axes[i - 1] : mk3( 0, 0, 0 ), st ) ) return 1;
-	}
-	h.dev.pixels = h.pixels.as<float4>();
-	h.dev.sat = h.sat[0].as<uint32_t>();
-	for( int i = 0; i < 6; i++ ) h.dev.sats[i] = h.sat[i + 1].as<uint32_t>();
-	h.dev.width = h.dev.widthPrimary = width; // no primary map: see mvrt.h, the reference would index with 0x0 here
-	h.dev.height = h.dev.heightPrimary = height;
-	if( rgbaPrimaryHost ) // HDRI::loadPrimary, :315-326
-	{
-		const uint64_t np = (uint64_t)widthPrimary * heightPrimary;
-		if( h.primary.alloc( np * 16 ) ) return 1;
-		MVRT_HIP( hipMemcpyAsync( h.primary.p, rgbaPrimaryHost, np * 16, hipMemcpyHostToDevice, st ) );
-		h.dev.pixelsPrimary = h.primary.as<float4>();
-		h.dev.widthPrimary = widthPrimary;
-		h.dev.heightPrimary = heightPrimary;
-	}
-	MVRT_HIP( hipStreamSynchronize( st ) ); // :313 (and satF64 is released on return)
-	h.dev.scale = pt->hdri.dev.scale;
-	pt->hdri = std::move( h );
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_load_hdri_file( mvrt_pt* pt, void* stream, const char* file, const char* filePrimary )
-{
-	std::vector<float> a, b;
-	int w = 0, h = 0, wp = 0, hp = 0;
-	if( loadRgbe( file, a, &w, &h ) ) return 1;
-	if( filePrimary && loadRgbe( filePrimary, b, &wp, &hp ) ) return 1;
-	return mvrt_pt_load_hdri( pt, stream, a.data(), w, h, filePrimary ? b.data() : nullptr, wp, hp );
-}
-// host-only: the decoder behind mvrt_pt_load_hdri_file (pr::Image2DRGBA32::loadFromHDR's role, PathTracer.hpp:106-113)
-MVRT_EXPORT int mvrt_rgbe_read_file( const char* file, float* rgbaHost, uint64_t capacityPixels, int* width, int* height )
-{
-	REQUIRE( file && width && height, "null argument" );
-	std::vector<float> a;
-	if( loadRgbe( file, a, width, height ) ) return 1;
-	if( !rgbaHost ) return 0;
-	REQUIRE( (uint64_t)*width * *height <= capacityPixels, "%s: %dx%d pixels do not fit %llu", file, *width, *height, (unsigned long long)capacityPixels );
-	memcpy( rgbaHost, a.data(), a.size() * sizeof( float ) );
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_download_hdri_sat( mvrt_pt* pt, int which, uint32_t* satHost )
-{
-	REQUIRE( pt && which >= 0 && which < 7 && pt->hdri.sat[which].p, "no such HDRI table" );
-	MVRT_HIP( hipMemcpy( satHost, pt->hdri.sat[which].p, pt->hdri.sat[which].bytes, hipMemcpyDeviceToHost ) );
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_set_hdri_scale( mvrt_pt* pt, float scale )
-{
-	REQUIRE( pt, "null argument" );
-	if( pt->flush() ) return 1; // pending steps are launched with the scale they were issued under (HDRI is a by-value kernel argument)
-	pt->hdri.dev.scale = scale;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_update_scene( mvrt_pt* pt, const float* verticesHost, const float* vcolorsHost, const float* vemissionsHost, uint64_t nVertices, void* stream,
-									  const float origin[3], float dps, int gridRes )
-{
-	REQUIRE( pt, "null argument" );
-	if( pt->drain() ) return 1;
-	return mvrt_svo_build( pt->intersector, verticesHost, vcolorsHost, vemissionsHost, nVertices, stream, origin, dps, gridRes );
-}
-MVRT_EXPORT mvrt_svo* mvrt_pt_intersector( mvrt_pt* pt ) { return pt ? pt->intersector : nullptr; }
-
-MVRT_EXPORT int mvrt_pt_step( mvrt_pt* pt, void* stream, const float camera[15] )
-{
-	REQUIRE( pt && pt->setupDone, "mvrt_pt_step: call mvrt_pt_setup first" );
-	REQUIRE( !pt->intersector->empty(), "mvrt_pt_step: no scene (updateScene / upload first)" );
-	REQUIRE( pt->fbF32.p, "mvrt_pt_step: no frame buffer (resizeFrameBufferIfNeeded first)" );
-	REQUIRE( !( 0.0f < pt->hdri.dev.scale ) || pt->hdri.dev.pixels, "mvrt_pt_step: HDRI enabled (scale > 0) but none loaded" );
-	PtFrame f;
-	f.width = pt->width;
-	f.height = pt->height;
-	f.tileIndex = pt->tileIndex;
-	f.tileCount = pt->tileCount;
-	f.ownedPixels = pt->ownedPixels;
-	f.validOwnedPixels = pt->validOwnedPixels;
-	(void)f;
-	// deferred: remember the camera; the pass is launched when `batch` steps are pending or a consumer joins
-	if( pt->pendingCams.empty() )
-	{
-		pt->pendingIteration = pt->steps;
-		pt->pendingStream = (hipStream_t)stream;
-	}
-	else if( pt->pendingStream != (hipStream_t)stream )
-	{
-		if( pt->flush() ) return 1;
-		pt->pendingIteration = pt->steps;
-		pt->pendingStream = (hipStream_t)stream;
-	}
-	pt->steps++; // PathTracer.hpp:159
-	pt->pendingCams.push_back( cameraFrom15( camera ) );
-	if( (int)pt->pendingCams.size() >= pt->passSteps() ) return pt->flush( true ); // a full batch: the caller is still stepping
-	return 0;
-}
-int mvrt_pt::flush( bool moreStepsFollow )
-{
-	if( pendingCams.empty() ) return 0;
-	const int n = (int)pendingCams.size();
-	// A SMALL pass (a tile share of a multi-GPU frame, a small frame) is dominated by the latency floors of its nine traversal
-	// launches and by its un-overlapped shade kernels.  Two sibling passes on two streams, each traversal launch restricted to half
-	// of the wave slots, overlap one pass's tails and shading with the other's traversal.  Same per-sample results; the frame-buffer
-	// additions stay in step order through the event chain.
-	const uint64_t samples = ownedPixels * MVRT_SPP_PER_STEP * (uint64_t)n;
-	static const uint64_t splitMax = (uint64_t)mvrtKnob( "MVRT_SPLIT_SMALL_MAX", 40000000ll );
-	// ... but only when this pass would otherwise run ALONE: if the caller keeps stepping, or an earlier pass is still in flight, the
-	// passes already overlap each other and halving their grids only slows them (measured: 2.68 -> 2.99 ms per step at 16 steps)
-	const bool alone = !moreStepsFollow && ( !lastAccum || !pendingJoin || hipEventQuery( lastAccum ) == hipSuccess );
-	const bool split = splitSmallPasses && alone && depth >= 2 && n >= 2 && samples <= splitMax;
-	std::vector<CameraPinhole> cams( pendingCams );
-	const int first = pendingIteration;
-	pendingCams.clear();
-	if( !split ) return launchPass( cams.data(), first, n, 1 );
-	// `ways` sibling passes (at most one per work-buffer slot and per step), each restricted to 1/ways of the wave slots
-	static const int envWays = (int)mvrtKnob( "MVRT_SPLIT_WAYS", 2 );
-	int ways = envWays < 2 ? 2 : envWays;
-	if( ways > depth ) ways = depth;
-	if( ways > n ) ways = n;
-	int done = 0;
-	for( int k = 0; k < ways; k++ )
-	{
-		const int cnt = ( n - done ) / ( ways - k );
-		// (r02: each sibling's traversal launches took 1 / ways of the wave slots; r03 re-measured with the cheaper-to-drain kernel: full grids are 1-2 %
-		//  better on a 1/8 share -- dragon 2.744 -> 2.698, rtcamp 2.421 -> 2.393 ms per step -- the dispatcher hands the slots of retiring waves to the sibling)
-		static const int siblingDiv = (int)mvrtKnob( "MVRT_SIBLING_GRID_DIV", 1 );
-		if( launchPass( cams.data() + done, first + done, cnt, siblingDiv > 0 ? siblingDiv : ways ) ) return 1;
-		done += cnt;
-	}
-	return 0;
-}
-int mvrt_pt::launchPass( const CameraPinhole* passCams, int iteration, int nSteps, int traceGridDiv )
-{
-	mvrt_pt* pt = this;
-	PtFrame f;
-	f.width = width;
-	f.height = height;
-	f.tileIndex = tileIndex;
-	f.tileCount = tileCount;
-	f.ownedPixels = ownedPixels;
-	f.validOwnedPixels = validOwnedPixels;
-	f.iteration = iteration;
-	f.nSteps = nSteps;
-	f.traceGridDiv = traceGridDiv;
-	f.useHints = originHints ? 1 : 0;
-	CameraPinhole cams[MVRT_MAX_BATCH];
-	for( int b = 0; b < f.nSteps; b++ ) cams[b] = passCams[b];
-	hipStream_t user = pendingStream;
-	mvrt_pt::Slot& sl = pt->slots[pt->nextSlot];
-	pt->lastSlot = pt->nextSlot;
-	pt->nextSlot = ( pt->nextSlot + 1 ) % pt->depth;
-	REQUIRE( sl.buf.cap >= pt->validOwnedPixels * MVRT_SPP_PER_STEP * f.nSteps, "internal: work buffers not allocated" );
-	if( sl.trace.ensure( pt->intersector->oct.info.levels, 0 ) ) return 1;
-	sl.buf.dbgTasks = nullptr;
-	if( pt->debugCapture )
-	{
-		if( sl.dbg.bytes < sl.buf.cap * 4 * MVRT_MAX_DEPTH && sl.dbg.alloc( sl.buf.cap * 4 * MVRT_MAX_DEPTH ) ) return 1;
-		sl.buf.dbgTasks = sl.dbg.as<uint32_t>();
-	}
-	hipStream_t run = user;
-	hipEvent_t after = nullptr;
-	if( pt->depth > 1 )
-	{
-		run = sl.stream;
-		MVRT_HIP( hipEventRecord( pt->forkEv, user ) ); // everything the caller queued so far (clear, upload, ...) comes first
-		MVRT_HIP( hipStreamWaitEvent( run, pt->forkEv, 0 ) );
-		after = pt->lastAccum;
-	}
-	AovBuffers aov = { nullptr, nullptr, nullptr, nullptr };
-	if( pt->aovs )
-	{
-		REQUIRE( sl.aovPart.p && pt->aovAlbedo.p && pt->aovNormalDepth.p, "internal: feature buffers not allocated" );
-		aov.partA = sl.aovPart.as<float4>();
-		aov.partN = aov.partA + sl.buf.cap / MVRT_SPP_PER_STEP;
-		aov.albedo = pt->aovAlbedo.as<float4>();
-		aov.normalDepth = pt->aovNormalDepth.as<float4>();
-	}
-	REQUIRE( !pt->moments || pt->momentsBuf.p, "internal: moments buffer not allocated" );
-	int rc = launchPtStep( pt->intersector->dev(), sl.trace.ws, pt->hdri.dev, pt->pmj.as<float2>(), cams, f, sl.buf, pt->fbF32.as<float4>(), pt->numCUs,
-						   pt->profiling ? &pt->prof : nullptr, run, after, pt->aovs ? &aov : nullptr, pt->moments ? pt->momentsBuf.as<float4>() : nullptr );
-	if( rc ) return rc;
-	MVRT_HIP( hipEventRecord( sl.accumDone, run ) );
-	pt->lastAccum = sl.accumDone;
-	if( pt->depth > 1 ) pt->pendingJoin = true;
-	return 0; // profiling events are collected lazily by mvrt_pt_get_stats (no sync inside step)
-}
-MVRT_EXPORT int mvrt_pt_step_matrices( mvrt_pt* pt, void* stream, const float view[16], const float proj[16], float focus, float lensR )
-{
-	float cam[15];
-	mvrt_camera_from_matrices( view, proj, focus, lensR, cam );
-	return mvrt_pt_step( pt, stream, cam );
-}
-MVRT_EXPORT int mvrt_pt_resolve( mvrt_pt* pt, void* stream )
-{
-	REQUIRE( pt && pt->fbF32.p, "no frame buffer" );
-	if( pt->join( (hipStream_t)stream ) ) return 1;
-	return launchResolve( pt->fbF32.as<float4>(), pt->validOwnedPixels, pt->fbU8.as<uchar4>(), (hipStream_t)stream );
-}
-MVRT_EXPORT int mvrt_pt_to_image_async( mvrt_pt* pt, void* stream, uint8_t* rgbaHost )
-{
-	if( mvrt_pt_resolve( pt, stream ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( rgbaHost, pt->fbU8.p, pt->validOwnedPixels * 4, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_get_steps( const mvrt_pt* pt ) { return pt ? pt->steps : 0; }
-MVRT_EXPORT uint64_t mvrt_pt_get_number_of_voxels( const mvrt_pt* pt ) { return pt ? pt->intersector->oct.nVoxels : 0; }
-MVRT_EXPORT uint64_t mvrt_pt_get_octree_bytes( const mvrt_pt* pt ) { return pt ? (uint64_t)pt->intersector->oct.nNodes * 68 : 0; }
-MVRT_EXPORT int mvrt_pt_read_framebuffer( mvrt_pt* pt, void* stream, float* rgbaHost )
-{
-	REQUIRE( pt && pt->fbF32.p, "no frame buffer" );
-	if( pt->join( (hipStream_t)stream ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( rgbaHost, pt->fbF32.p, pt->ownedPixels * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
-	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
-	return 0;
-}
-MVRT_EXPORT float* mvrt_pt_framebuffer_dev( mvrt_pt* pt ) { return pt ? pt->fbF32.as<float>() : nullptr; }
-
-// ---- first-hit feature buffers ------------------------------------------------------------------------------
-MVRT_EXPORT int mvrt_pt_set_aovs( mvrt_pt* pt, int enable )
-{
-	REQUIRE( pt, "null argument" );
-	if( pt->drain() ) return 1;
-	const bool on = enable != 0;
-	if( on == pt->aovs ) return 0;
-	REQUIRE( pt->steps == 0, "mvrt_pt_set_aovs: %d steps are accumulated in the frame buffer, the feature buffers would not match its sample count (mvrt_pt_clear_framebuffer first)",
-			 pt->steps );
-	if( !pt->fbF32.p ) // no frame yet: the next resize allocates (or does not)
-	{
-		pt->aovs = on;
-		return 0;
-	}
-	if( on )
-	{
-		if( pt->allocAovFrame() )
-		{
-			pt->releaseAovs(); // the frame stays as it was, without feature buffers
-			return 1;
-		}
-		MVRT_HIP( hipMemset( pt->aovAlbedo.p, 0, pt->aovAlbedo.bytes ) );
-		MVRT_HIP( hipMemset( pt->aovNormalDepth.p, 0, pt->aovNormalDepth.bytes ) );
-		MVRT_HIP( hipStreamSynchronize( nullptr ) );
-	}
-	else pt->releaseAovs();
-	pt->aovs = on;
-	return allocWork( pt ); // the partial sums live beside the path state and count against the same budget; a failure leaves NO frame, like every reallocation
-}
-static DevBuf* aovBuffer( mvrt_pt* pt, int which, const char* who )
-{
-	if( !pt )
-	{
-		mvrtSetError( "%s: null argument", who );
-		return nullptr;
-	}
-	if( which != MVRT_AOV_ALBEDO && which != MVRT_AOV_NORMAL_DEPTH )
-	{
-		mvrtSetError( "%s: no feature buffer %d (MVRT_AOV_ALBEDO, MVRT_AOV_NORMAL_DEPTH)", who, which );
-		return nullptr;
-	}
-	DevBuf* b = which == MVRT_AOV_ALBEDO ? &pt->aovAlbedo : &pt->aovNormalDepth;
-	if( !pt->aovs || !b->p )
-	{
-		mvrtSetError( pt->aovs ? "%s: no frame buffer" : "%s: feature buffers are off (mvrt_pt_set_aovs)", who );
-		return nullptr;
-	}
-	return b;
-}
-MVRT_EXPORT float* mvrt_pt_aov_dev( mvrt_pt* pt, int which )
-{
-	DevBuf* b = aovBuffer( pt, which, "mvrt_pt_aov_dev" );
-	return b ? b->as<float>() : nullptr;
-}
-MVRT_EXPORT int mvrt_pt_read_aov( mvrt_pt* pt, void* stream, int which, float* rgbaHost )
-{
-	DevBuf* b = aovBuffer( pt, which, "mvrt_pt_read_aov" );
-	if( !b ) return 1;
-	REQUIRE( rgbaHost, "mvrt_pt_read_aov: null argument" );
-	if( pt->join( (hipStream_t)stream ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( rgbaHost, b->p, pt->ownedPixels * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
-	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
-	return 0;
-}
-
-// ---- luminance moments ----------------------------------------------------------------------------------------
-MVRT_EXPORT int mvrt_pt_set_moments( mvrt_pt* pt, int enable )
-{
-	REQUIRE( pt, "mvrt_pt_set_moments: null argument" );
-	if( pt->drain() ) return 1;
-	const bool on = enable != 0;
-	if( on == pt->moments ) return 0;
-	REQUIRE( pt->steps == 0, "mvrt_pt_set_moments: %d steps are accumulated in the frame buffer, the moments would not match its sample count (mvrt_pt_clear_framebuffer first)", pt->steps );
-	if( !pt->fbF32.p ) // no frame yet: the next resize allocates (or does not)
-	{
-		pt->moments = on;
-		return 0;
-	}
-	if( on )
-	{
-		if( pt->momentsBuf.alloc( pt->ownedPixels * sizeof( float4 ) ) ) return 1; // the frame stays as it was, without moments
-		hipError_t e = hipMemset( pt->momentsBuf.p, 0, pt->momentsBuf.bytes );
-		if( e == hipSuccess ) e = hipStreamSynchronize( nullptr );
-		if( e != hipSuccess )
-		{
-			pt->momentsBuf.release(); // (off means no buffer held)
-			mvrtSetError( "mvrt_pt_set_moments: clearing the moments failed: %s", hipGetErrorString( e ) );
-			return 1;
-		}
-	}
-	else pt->releaseMoments();
-	pt->moments = on;
-	return allocWork( pt ); // the buffer counts against the budget of the path state; a failure leaves NO frame, like every reallocation
-}
-static DevBuf* momentsBuffer( mvrt_pt* pt, const char* who )
-{
-	if( !pt )
-	{
-		mvrtSetError( "%s: null argument", who );
-		return nullptr;
-	}
-	if( !pt->moments || !pt->momentsBuf.p )
-	{
-		mvrtSetError( pt->moments ? "%s: no frame buffer" : "%s: the moments are off (mvrt_pt_set_moments)", who );
-		return nullptr;
-	}
-	return &pt->momentsBuf;
-}
-MVRT_EXPORT float* mvrt_pt_moments_dev( mvrt_pt* pt )
-{
-	DevBuf* b = momentsBuffer( pt, "mvrt_pt_moments_dev" );
-	return b ? b->as<float>() : nullptr;
-}
-MVRT_EXPORT int mvrt_pt_read_moments( mvrt_pt* pt, void* stream, float* rgbaHost )
-{
-	DevBuf* b = momentsBuffer( pt, "mvrt_pt_read_moments" );
-	if( !b ) return 1;
-	REQUIRE( rgbaHost, "mvrt_pt_read_moments: null argument" );
-	if( pt->join( (hipStream_t)stream ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( rgbaHost, b->p, pt->ownedPixels * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
-	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
-	return 0;
-}
-
-// ---- denoiser ---------------------------------------------------------------------------------------------------
-MVRT_EXPORT int mvrt_denoise_default_params( mvrt_denoise_params* p )
-{
-	REQUIRE( p, "mvrt_denoise_default_params: null argument" );
-	memset( p, 0, sizeof( *p ) );
-	p->structBytes = (uint32_t)sizeof( mvrt_denoise_params );
-	p->iterations = 5;
-	p->sigmaNormal = 0.5f;
-	p->sigmaDepth = 0.05f;
-	p->sigmaCoverage = 0.25f;
-	p->sigmaLuminance = 2.0f;
-	p->albedoFloor = 0.01f;
-	return 0;
-}
-// every rule on the parameters, on the host; in == NULL: the defaults
-static int denoiseParams( const mvrt_denoise_params* in, mvrt_denoise_params* out, const char* who )
-{
-	mvrt_denoise_default_params( out );
-	if( !in ) return 0;
-	REQUIRE( in->structBytes == sizeof( mvrt_denoise_params ), "%s: params->structBytes is %u, sizeof( mvrt_denoise_params ) is %u (mvrt_denoise_default_params fills it)", who, in->structBytes,
-			 (unsigned)sizeof( mvrt_denoise_params ) );
-	REQUIRE( in->iterations >= 1 && in->iterations <= 8, "%s: iterations %d outside 1..8", who, in->iterations );
-	REQUIRE( in->sigmaNormal > 0.0f, "%s: sigmaNormal %g is not greater than 0", who, (double)in->sigmaNormal );
-	REQUIRE( in->sigmaDepth > 0.0f, "%s: sigmaDepth %g is not greater than 0", who, (double)in->sigmaDepth );
-	REQUIRE( in->sigmaCoverage > 0.0f, "%s: sigmaCoverage %g is not greater than 0", who, (double)in->sigmaCoverage );
-	REQUIRE( in->sigmaLuminance > 0.0f, "%s: sigmaLuminance %g is not greater than 0", who, (double)in->sigmaLuminance );
-	REQUIRE( in->albedoFloor > 0.0f, "%s: albedoFloor %g is not greater than 0", who, (double)in->albedoFloor );
-	REQUIRE( ( in->flags & ~(uint32_t)MVRT_DENOISE_NO_DEMODULATION ) == 0, "%s: unknown flags 0x%x", who, in->flags );
-	*out = *in;
-	return 0;
-}
-static bool denoiseSizeOk( int width, int height ) { return width > 0 && height > 0 && (uint64_t)width * (uint64_t)height <= 0x7FFFFFFFull; } // (32-bit pixel indices)
-MVRT_EXPORT uint64_t mvrt_denoise_scratch_bytes( int width, int height )
-{
-	if( !denoiseSizeOk( width, height ) )
-	{
-		mvrtSetError( "mvrt_denoise_scratch_bytes: bad resolution %dx%d (width and height must be greater than 0)", width, height );
-		return 0;
-	}
-	return denoiseScratchBytes( (uint64_t)width * height );
-}
-MVRT_EXPORT int mvrt_denoise_buffers( const float* colorDev, const float* albedoDev, const float* normalDepthDev, const float* momentsDev, int width, int height,
-									  const mvrt_denoise_params* params, float* outDev, void* scratchDev, uint64_t scratchBytes, void* stream )
-{
-	REQUIRE( denoiseSizeOk( width, height ), "mvrt_denoise_buffers: bad resolution %dx%d (width and height must be greater than 0)", width, height );
-	mvrt_denoise_params P;
-	if( denoiseParams( params, &P, "mvrt_denoise_buffers" ) ) return 1;
-	REQUIRE( colorDev && albedoDev && normalDepthDev && momentsDev && outDev && scratchDev, "mvrt_denoise_buffers: null argument" );
-	const uint64_t need = denoiseScratchBytes( (uint64_t)width * height );
-	REQUIRE( scratchBytes >= need, "mvrt_denoise_buffers: scratch too small, %llu bytes given, a %dx%d frame needs %llu (mvrt_denoise_scratch_bytes)", (unsigned long long)scratchBytes, width,
-			 height, (unsigned long long)need );
-	return launchDenoise( (const float4*)colorDev, (const float4*)albedoDev, (const float4*)normalDepthDev, (const float4*)momentsDev, width, height, P.iterations, P.sigmaNormal, P.sigmaDepth,
-						  P.sigmaCoverage, P.sigmaLuminance, P.albedoFloor, P.flags, (float4*)outDev, scratchDev, (hipStream_t)stream );
-}
-MVRT_EXPORT int mvrt_pt_denoise( mvrt_pt* pt, void* stream, const mvrt_denoise_params* params )
-{
-	REQUIRE( pt, "mvrt_pt_denoise: null argument" );
-	mvrt_denoise_params P;
-	if( denoiseParams( params, &P, "mvrt_pt_denoise" ) ) return 1;
-	REQUIRE( pt->tileCount == 1, "mvrt_pt_denoise: this handle renders tile %d of %d; the filter needs the whole frame -- assemble the buffers (mvrt_pt_assemble_tiles) and call mvrt_denoise_buffers",
-			 pt->tileIndex, pt->tileCount );
-	REQUIRE( pt->aovs, "mvrt_pt_denoise: the feature buffers are off (mvrt_pt_set_aovs)" );
-	REQUIRE( pt->moments, "mvrt_pt_denoise: the moments are off (mvrt_pt_set_moments)" );
-	REQUIRE( pt->steps > 0, "mvrt_pt_denoise: no steps yet (the frame buffer holds no sample)" );
-	REQUIRE( pt->fbF32.p && pt->aovAlbedo.p && pt->aovNormalDepth.p && pt->momentsBuf.p, "mvrt_pt_denoise: no frame buffer" );
-	if( pt->join( (hipStream_t)stream ) ) return 1;
-	const uint64_t nPix = (uint64_t)pt->width * pt->height;
-	const uint64_t scratch = denoiseScratchBytes( nPix );
-	if( !pt->denoised.p || pt->denoised.bytes != nPix * sizeof( float4 ) || pt->denoiseScratch.bytes != scratch )
-	{
-		// nothing of the frame is touched: a failure leaves it, the steps and the feature buffers as they are, and no denoised buffer
-		if( pt->denoised.alloc( nPix * sizeof( float4 ) ) || pt->denoiseScratch.alloc( scratch ) )
-		{
-			pt->releaseDenoised();
-			return 1;
-		}
-	}
-	if( launchDenoise( pt->fbF32.as<float4>(), pt->aovAlbedo.as<float4>(), pt->aovNormalDepth.as<float4>(), pt->momentsBuf.as<float4>(), pt->width, pt->height, P.iterations, P.sigmaNormal,
-					   P.sigmaDepth, P.sigmaCoverage, P.sigmaLuminance, P.albedoFloor, P.flags, pt->denoised.as<float4>(), pt->denoiseScratch.p, (hipStream_t)stream ) )
-	{
-		pt->releaseDenoised();
-		return 1;
-	}
-	return 0;
-}
-MVRT_EXPORT float* mvrt_pt_denoised_dev( mvrt_pt* pt ) { return pt ? pt->denoised.as<float>() : nullptr; }
-MVRT_EXPORT int mvrt_pt_read_denoised( mvrt_pt* pt, void* stream, float* rgbaHost )
-{
-	REQUIRE( pt && rgbaHost, "mvrt_pt_read_denoised: null argument" );
-	REQUIRE( pt->denoised.p, "mvrt_pt_read_denoised: no denoised buffer (mvrt_pt_denoise first)" );
-	MVRT_HIP( hipMemcpyAsync( rgbaHost, pt->denoised.p, (uint64_t)pt->width * pt->height * 16, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
-	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
-	return 0;
-}
-MVRT_EXPORT uint8_t* mvrt_pt_framebuffer_u8_dev( mvrt_pt* pt ) { return pt ? pt->fbU8.as<uint8_t>() : nullptr; }
-MVRT_EXPORT const float* mvrt_pt_sample_radiance_dev( mvrt_pt* pt )
-{
-	if( !pt ) return nullptr;
-	(void)pt->drain();
-	return pt->slots[pt->lastSlot].buf.Lsx;
-}
-MVRT_EXPORT int mvrt_pt_read_sample_radiance( mvrt_pt* pt, float* xyzHost, uint64_t nSamples )
-{
-	REQUIRE( pt && xyzHost, "null argument" );
-	if( pt->drain() ) return 1;
-	const PtBuffers& b = pt->slots[pt->lastSlot].buf;
-	REQUIRE( b.Lsx && nSamples <= b.cap, "no such samples" );
-	MVRT_HIP( hipMemcpy( xyzHost, b.Lsx, nSamples * 4, hipMemcpyDeviceToHost ) );
-	MVRT_HIP( hipMemcpy( xyzHost + nSamples, b.Lsy, nSamples * 4, hipMemcpyDeviceToHost ) );
-	MVRT_HIP( hipMemcpy( xyzHost + 2 * nSamples, b.Lsz, nSamples * 4, hipMemcpyDeviceToHost ) );
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_join( mvrt_pt* pt, void* stream )
-{
-	REQUIRE( pt, "null argument" );
-	return pt->join( (hipStream_t)stream );
-}
-MVRT_EXPORT int mvrt_pt_set_batch_steps( mvrt_pt* pt, int maxSteps )
-{
-	REQUIRE( pt && maxSteps >= 0 && maxSteps <= MVRT_MAX_BATCH, "batch must be 0 (automatic) or 1..%d", MVRT_MAX_BATCH );
-	if( pt->drain() ) return 1;
-	pt->batch = maxSteps;
-	if( pt->fbF32.p ) return allocWork( pt );
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_set_split_small_passes( mvrt_pt* pt, int enable )
-{
-	REQUIRE( pt, "null argument" );
-	if( pt->drain() ) return 1;
-	pt->splitSmallPasses = enable != 0;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_set_origin_hints( mvrt_pt* pt, int enable )
-{
-	REQUIRE( pt, "null argument" );
-	if( pt->flush() ) return 1;
-	pt->originHints = enable != 0;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_set_pipeline_depth( mvrt_pt* pt, int depth )
-{
-	REQUIRE( pt && depth >= 1 && depth <= 4, "pipeline depth must be 1..4" );
-	if( pt->drain() ) return 1;
-	pt->depth = pt->depthWanted = depth;
-	if( pt->fbF32.p ) return allocWork( pt );
-	return 0;
-}
-
-MVRT_EXPORT int mvrt_pt_assemble_tiles( const float* gatheredDev, int tileCount, uint64_t rankStridePixels, int width, int height, float* frameDev, void* stream )
-{
-	REQUIRE( gatheredDev && frameDev && tileCount >= 1, "bad arguments" );
-	return launchAssembleTiles( (const float4*)gatheredDev, tileCount, rankStridePixels, width, height, (float4*)frameDev, (hipStream_t)stream );
-}
-MVRT_EXPORT int mvrt_resolve_buffer( const float* rgbaF32Dev, uint64_t nPixels, uint8_t* rgbaU8Dev, void* stream )
-{
-	return launchResolve( (const float4*)rgbaF32Dev, nPixels, (uchar4*)rgbaU8Dev, (hipStream_t)stream );
-}
-
-MVRT_EXPORT int mvrt_pt_set_debug_capture( mvrt_pt* pt, int enabled )
-{
-	REQUIRE( pt, "null argument" );
-	if( pt->drain() ) return 1;
-	pt->debugCapture = enabled != 0;
-	if( !enabled )
-		for( mvrt_pt::Slot& sl : pt->slots ) sl.dbg.release();
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_read_debug_stage( mvrt_pt* pt, int stage, uint32_t* tasksHost, uint64_t capacity, uint32_t* survivorsOut )
-{
-	REQUIRE( pt && stage >= 0 && stage < MVRT_MAX_DEPTH && survivorsOut, "bad arguments" );
-	if( pt->drain() ) return 1;
-	const mvrt_pt::Slot& sl = pt->slots[pt->lastSlot];
-	REQUIRE( sl.buf.dbgTasks, "debug capture was not enabled for the last pass" );
-	MVRT_HIP( hipMemcpy( survivorsOut, sl.buf.liveCount + stage + 1, 4, hipMemcpyDeviceToHost ) );
-	REQUIRE( *survivorsOut <= capacity && *survivorsOut <= sl.buf.cap, "tasksHost holds %llu entries, stage %d kept %u", (unsigned long long)capacity, stage, *survivorsOut );
-	if( tasksHost && *survivorsOut ) MVRT_HIP( hipMemcpy( tasksHost, sl.buf.dbgTasks + (uint64_t)stage * sl.buf.cap, (uint64_t)*survivorsOut * 4, hipMemcpyDeviceToHost ) );
-	return 0;
-}
-
-MVRT_EXPORT int mvrt_pt_set_test_free_bytes( mvrt_pt* pt, uint64_t bytes )
-{
-	REQUIRE( pt, "null argument" );
-	pt->testFreeBytes = bytes;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_set_profiling( mvrt_pt* pt, int enabled )
-{
-	REQUIRE( pt, "null argument" );
-	pt->profiling = enabled != 0;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_reset_stats( mvrt_pt* pt )
-{
-	REQUIRE( pt, "null argument" );
-	if( pt->drain() ) return 1;
-	if( pt->buf.stats ) MVRT_HIP( hipMemset( pt->buf.stats, 0, 64 * 8 ) );
-	pt->prof.collect();
-	pt->prof.ms[0] = pt->prof.ms[1] = pt->prof.ms[2] = 0.0;
-	pt->prof.traceLaunches = 0;
-	return 0;
-}
-MVRT_EXPORT int mvrt_pt_get_stats( mvrt_pt* pt, void* stream, mvrt_pt_stats* out )
-{
-	REQUIRE( pt && out, "null argument" );
-	memset( out, 0, sizeof( *out ) );
-	if( pt->drain() ) return 1;
-	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
-	if( pt->buf.stats )
-	{
-		unsigned long long s[6];
-		MVRT_HIP( hipMemcpy( s, pt->buf.stats, sizeof( s ), hipMemcpyDeviceToHost ) );
-		out->rays = s[0];
-		out->shadowRays = s[1];
-		out->descents = s[2];
-		out->shadowDescents = s[3];
-		out->hits = s[4];
-		out->samples = s[5];
-#ifdef MVRT_UTIL_STATS
-		if( getenv( "MVRT_PRINT_UTIL" ) ) // (a diagnostic build's tallies: tools/build_variant.sh util -DMVRT_UTIL_STATS)
-		{
-			unsigned long long u[4];
-			MVRT_HIP( hipMemcpy( u, pt->buf.stats + 8, sizeof( u ), hipMemcpyDeviceToHost ) );
-			// u[0], u[1]: refill events and the lanes active right after them; u[2], u[3]: wave-iterations of the node-visit loop and
-			// the lanes active in them
-			fprintf( stderr, "[util] wave-iterations %llu, active-lane-iterations %llu (%.1f%% of lane slots); refill events %llu; rays %llu -> %.2f lane-iterations per ray\n", u[2], u[3],
-					 100.0 * u[3] / ( 64.0 * ( u[2] ? u[2] : 1 ) ), u[0], (unsigned long long)s[0], (double)u[3] / (double)( s[0] ? s[0] : 1 ) );
-			unsigned long long c[2];
-			MVRT_HIP( hipMemcpy( c, pt->buf.stats + 12, sizeof( c ), hipMemcpyDeviceToHost ) );
-			fprintf( stderr, "[util] traversal waves: %.1f%% of their shader clocks in refill sections (result flush, ray loads, setup, hint replay)\n", 100.0 * (double)c[0] / (double)( c[1] ? c[1] : 1 ) );
-			unsigned long long w[48];
-			MVRT_HIP( hipMemcpy( w, pt->buf.stats + 16, sizeof( w ), hipMemcpyDeviceToHost ) );
-			for( int k = 0; k <= MVRT_MAX_DEPTH; k++ )
-				fprintf( stderr, "[util] stage %d: longest wave %llu iterations, waves %llu, longest ray %llu iterations\n", k, w[k], w[16 + k], w[32 + k] );
-		}
-#endif
-	}
-	pt->prof.collect();
-	out->traceLaunches = pt->prof.traceLaunches;
-	out->traceKernelMs = pt->prof.ms[MVRT_K_TRACE];
-	out->shadeKernelMs = pt->prof.ms[MVRT_K_SHADE];
-	out->totalKernelMs = pt->prof.ms[0] + pt->prof.ms[1] + pt->prof.ms[2];
 	return 0;
 }

@@ -1,6 +1,7 @@
 // kernels_denoise.hip -- the luminance-moments buffer (mvrt_pt_set_moments) and the variance-guided a-trous denoiser (mvrt_denoise_buffers,
 // mvrt_pt_denoise).  New; the reference has neither.  The filter is a CONTRACT (include/mvrt.h "Denoiser"): every operation below is fp32 in
 // the order stated there, compiled without contraction, exp is mvrt_exp, division and sqrt are IEEE -- the test helper restates that text, not this file.
+#include "../../include/mvrt.h"
 #include "launch.h"
 
 // lum( x ) = ( 0.2126 r + 0.7152 g ) + 0.0722 b: the one luminance of the moments, of the albedo normalisation and of the edge-stopping term
@@ -188,26 +189,26 @@ __global__ void __launch_bounds__( 256 ) kDenoiseAtrous( const float4* __restric
 static uint64_t dnAlign( uint64_t b ) { return ( b + 255 ) & ~(uint64_t)255; }
 uint64_t denoiseScratchBytes( uint64_t nPixels ) { return 3 * dnAlign( nPixels * 16 ) + dnAlign( nPixels * 4 ); }
 
-// arguments are checked by the callers (api.hip); scratch holds denoiseScratchBytes( W * H )
-int launchDenoise( const float4* color, const float4* albedo, const float4* normalDepth, const float4* moments, int W, int H, int iterations, float sigmaNormal, float sigmaDepth,
-				   float sigmaCoverage, float sigmaLuminance, float albedoFloor, uint32_t flags, float4* out, void* scratch, hipStream_t stream )
+// arguments are checked by the callers (api_pt.hip); scratch holds denoiseScratchBytes( W * H )
+int launchDenoise( const float4* color, const float4* albedo, const float4* normalDepth, const float4* moments, int W, int H, const mvrt_denoise_params& p, float4* out, void* scratch,
+				   hipStream_t stream )
 {
 	const uint64_t n = (uint64_t)W * H;
 	uint8_t* base = (uint8_t*)scratch;
 	float4* uv[2] = { (float4*)base, (float4*)( base + dnAlign( n * 16 ) ) };
 	float4* geo = (float4*)( base + 2 * dnAlign( n * 16 ) );
 	float* cov = (float*)( base + 3 * dnAlign( n * 16 ) );
-	hipLaunchKernelGGL( kDenoisePrepare, dim3( divUp( n, 256 ) ), dim3( 256 ), 0, stream, color, albedo, normalDepth, moments, (uint32_t)n, albedoFloor, flags, uv[0], geo, cov, out );
-	const DnSigmas sg = { sigmaNormal * sigmaNormal, sigmaDepth, sigmaCoverage, sigmaLuminance };
+	hipLaunchKernelGGL( kDenoisePrepare, dim3( divUp( n, 256 ) ), dim3( 256 ), 0, stream, color, albedo, normalDepth, moments, (uint32_t)n, p.albedoFloor, p.flags, uv[0], geo, cov, out );
+	const DnSigmas sg = { p.sigmaNormal * p.sigmaNormal, p.sigmaDepth, p.sigmaCoverage, p.sigmaLuminance };
 	const dim3 grid( divUp( W, DN_TILE_X ), divUp( H, DN_TILE_Y ) );
-	for( int i = 0; i < iterations; i++ )
+	for( int i = 0; i < p.iterations; i++ )
 	{
 		const float4* in = uv[i & 1];
 		float4* next = uv[( i & 1 ) ^ 1];
-		if( i + 1 < iterations )
-			hipLaunchKernelGGL( kDenoiseAtrous<false>, grid, dim3( 256 ), 0, stream, in, geo, cov, W, H, 1 << i, sg, next, color, albedo, albedoFloor, flags, out );
+		if( i + 1 < p.iterations )
+			hipLaunchKernelGGL( kDenoiseAtrous<false>, grid, dim3( 256 ), 0, stream, in, geo, cov, W, H, 1 << i, sg, next, color, albedo, p.albedoFloor, p.flags, out );
 		else
-			hipLaunchKernelGGL( kDenoiseAtrous<true>, grid, dim3( 256 ), 0, stream, in, geo, cov, W, H, 1 << i, sg, next, color, albedo, albedoFloor, flags, out );
+			hipLaunchKernelGGL( kDenoiseAtrous<true>, grid, dim3( 256 ), 0, stream, in, geo, cov, W, H, 1 << i, sg, next, color, albedo, p.albedoFloor, p.flags, out );
 	}
 	MVRT_HIP( hipGetLastError() );
 	return 0;

@@ -98,8 +98,9 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 // kernels_denoise.hip: the luminance moments of a pass (behind kPtAccumulate, same stream) and the a-trous denoiser on full-frame buffers
 int launchPtMoments( const PtBuffers& buf, uint64_t validOwnedPixels, int nSteps, float4* moments, int numCUs, hipStream_t stream );
 uint64_t denoiseScratchBytes( uint64_t nPixels );
-int launchDenoise( const float4* color, const float4* albedo, const float4* normalDepth, const float4* moments, int W, int H, int iterations, float sigmaNormal, float sigmaDepth,
-				   float sigmaCoverage, float sigmaLuminance, float albedoFloor, uint32_t flags, float4* out, void* scratch, hipStream_t stream );
+struct mvrt_denoise_params; // (mvrt.h)
+int launchDenoise( const float4* color, const float4* albedo, const float4* normalDepth, const float4* moments, int W, int H, const mvrt_denoise_params& params, float4* out, void* scratch,
+				   hipStream_t stream );
 
 int launchResolve( const float4* fb, uint64_t n, uchar4* out, hipStream_t stream );
 int launchAssembleTiles( const float4* gathered, int tileCount, uint64_t rankStridePixels, int W, int H, float4* frame, hipStream_t stream );
@@ -121,7 +122,7 @@ int launchFillCellIndex( const uint64_t* morton, uint64_t n, uint32_t cellBits, 
 int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t* satOut, int cosWeighted, f3 axis, hipStream_t stream );
 
 // GPU SVO construction (svo_build.hip)
-// What a build produces, and what an octree handle keeps of it (api.hip, Octree).  It owns its arrays: a builder that fails hands nothing over and leaks nothing
+// What a build produces, and what an octree handle keeps of it (api_handles.h, Octree).  It owns its arrays: a builder that fails hands nothing over and leaks nothing
 struct SvoBuildResult
 {
 	DevBuf nodes, masks;

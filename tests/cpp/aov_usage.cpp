@@ -49,7 +49,7 @@ int main( int argc, char** argv )
 	pt.setAOVs( false );
 	std::printf( "off %d %d dev %d\n", (int)( pt.m_aovAlbedoF32 == nullptr ), (int)( pt.m_aovNormalDepthF32 == nullptr ), (int)( mvrt_pt_aov_dev( pt.handle(), MVRT_AOV_ALBEDO ) == nullptr ) );
 	pt.setAOVs( true );
-	pt.setTile( 0, 2 ); // the library releases the buffers: no stale view survives
+	pt.setTile( 0, 2 ); // the library releases everything of the frame, the u8 buffer included: no stale view survives
 	std::printf( "tile %d %d %d\n", (int)( pt.m_aovAlbedoF32 == nullptr ), (int)( pt.m_aovNormalDepthF32 == nullptr ), (int)( pt.m_frameBufferF32 == nullptr ) );
 	pt.cleanUp();
 	return 0;

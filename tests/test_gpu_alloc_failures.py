@@ -365,18 +365,33 @@ def test_hdri_load_over_a_map(mv, O, bunny):
         assert np.array_equal(frame(pt, cam), want_other)
 
 
-@pytest.mark.parametrize("aovs", [False, True])
-def test_resize_framebuffer(mv, O, bunny, aovs):
+@pytest.fixture(scope="module")
+def bunny_frame(O, bunny):
+    """the probe camera and the oracle's first step of the bunny at W x H without an HDRI map (path_tracer's scale 0)"""
     rgba, hw, hh = O.decode_rgbe(hdr_bytes())
     hd = O.HDRI(rgba, hw, hh, rgba, hw, hh, math_mode=1)
     hd.set_scale(0.0)
     cam = probe_camera(bunny.origin, bunny.dps, RES, focus=9.0, lens_r=0.05)
     want, _, _ = bunny.render_pt(hd, cam, W, H, 0, math_mode=1, threads=8)
+    return cam, want
+
+
+def assert_no_frame(mv, pt, cam):
+    for call in (lambda: pt.step(None, cam), pt.resolve, pt.read_framebuffer, pt.clearFrameBuffer):
+        with pytest.raises(mv.MvrtError, match="no frame buffer"):
+            call()
+
+
+@pytest.mark.parametrize("moments", [False, True])
+@pytest.mark.parametrize("aovs", [False, True])
+def test_resize_framebuffer(mv, bunny, bunny_frame, aovs, moments):
+    cam, want = bunny_frame
 
     def fresh():
         pt = path_tracer(mv)
         pt.m_intersectorOctreeGPU.upload(bunny.nodes, bunny.attrs, bunny.origin, bunny.dps, RES, bunny.has_emission)
         pt.set_aovs(aovs)
+        pt.set_moments(moments)
         return pt
 
     ref = fresh()
@@ -387,16 +402,85 @@ def test_resize_framebuffer(mv, O, bunny, aovs):
     n = count_allocations(mv, lambda: ref.resizeFrameBufferIfNeeded(None, W, H))  # (a frame of another size over the first one)
     assert np.array_equal(frame(ref, cam), want)
     want_aovs = [ref.read_aov(i) for i in (0, 1)] if aovs else []
+    want_moments = ref.read_moments() if moments else None
     pt = fresh()
     pt.resizeFrameBufferIfNeeded(None, 48, 27)
     for k in range(1, n + 1):
         pt.resizeFrameBufferIfNeeded(None, 48, 27)
         assert fail_nth(mv, k, lambda: pt.resizeFrameBufferIfNeeded(None, W, H)) == -held, k
-        for call in (lambda: pt.step(None, cam), pt.resolve, pt.read_framebuffer, pt.clearFrameBuffer):  # no frame
-            with pytest.raises(mv.MvrtError, match="no frame buffer"):
-                call()
+        assert_no_frame(mv, pt, cam)
         if aovs:
             assert not pt.aov_dev(0) and not pt.aov_dev(1)
+        if moments:
+            assert not pt.moments_dev()
         pt.resizeFrameBufferIfNeeded(None, W, H)
         assert np.array_equal(frame(pt, cam), want)
         assert all(np.array_equal(pt.read_aov(i), w) for i, w in zip((0, 1), want_aovs))
+        if moments:
+            assert np.array_equal(pt.read_moments(), want_moments)
+
+
+# The calls that reallocate the path state under a live frame.  own: how many of the call's first allocations are the option's own accumulation buffers, beside
+# a frame that is not touched yet; buffers: what the option adds to read, once it is on
+REALLOCATING_CALLS = {
+    "set_aovs": (lambda pt: pt.set_aovs(True), 2, lambda pt: [pt.read_aov(0), pt.read_aov(1)]),
+    "set_moments": (lambda pt: pt.set_moments(True), 1, lambda pt: [pt.read_moments()]),
+    "set_batch_steps": (lambda pt: pt.set_batch_steps(2), 0, lambda pt: []),
+    "set_pipeline_depth": (lambda pt: pt.set_pipeline_depth(2), 0, lambda pt: []),
+}
+
+
+def assert_option_off(mv, pt, name):
+    if name == "set_aovs":
+        assert not pt.aov_dev(0) and not pt.aov_dev(1)
+        with pytest.raises(mv.MvrtError, match="feature buffers are off"):
+            pt.read_aov(0)
+    if name == "set_moments":
+        assert not pt.moments_dev()
+        with pytest.raises(mv.MvrtError, match="moments are off"):
+            pt.read_moments()
+
+
+@pytest.mark.parametrize("name", list(REALLOCATING_CALLS))
+def test_reallocation_under_a_live_frame(mv, bunny, bunny_frame, name):
+    """Every allocation of the call fails in turn on a cleared frame.  What is left is (a) the frame as it was, the option off -- only while the option's own
+    accumulation buffers are being allocated -- or (b) no frame at all, from which a resize recovers."""
+    call, own, buffers = REALLOCATING_CALLS[name]
+    cam, want = bunny_frame
+
+    def fresh():
+        pt = path_tracer(mv)
+        pt.m_intersectorOctreeGPU.upload(bunny.nodes, bunny.attrs, bunny.origin, bunny.dps, RES, bunny.has_emission)
+        base = live(mv)
+        pt.resizeFrameBufferIfNeeded(None, W, H)
+        held = live(mv) - base - 1  # buffers of the frame (- 1: the counters of a path tracer, kept)
+        pt.clearFrameBuffer(None)
+        assert pt.getSteps() == 0
+        return pt, held
+
+    twin, held = fresh()
+    assert held >= 5
+    n = count_allocations(mv, lambda: call(twin))
+    assert n > own
+    assert np.array_equal(frame(twin, cam), want)
+    want_buffers = buffers(twin)
+    ends = []
+    for k in range(1, n + 1):
+        pt, _ = fresh()
+        delta = fail_nth(mv, k, lambda: call(pt))
+        if delta == 0:  # (a)
+            ends.append("a")
+            assert k <= own, k
+            assert_option_off(mv, pt, name)
+            assert np.array_equal(frame(pt, cam), want)
+            continue
+        ends.append("b")
+        assert delta == -held, k
+        assert_no_frame(mv, pt, cam)
+        pt.resizeFrameBufferIfNeeded(None, W, H)
+        assert np.array_equal(frame(pt, cam), want)
+        pt.clearFrameBuffer(None)
+        call(pt)  # ... and with the option on
+        assert np.array_equal(frame(pt, cam), want)
+        assert all(np.array_equal(x, y) for x, y in zip(buffers(pt), want_buffers))
+    print(name, "-- allocations failed in turn:", n, "-- ends:", "".join(ends), "-- buffers of the frame:", held)

@@ -4,7 +4,7 @@
 name=$1; shift
 d=build/ab/$name; mkdir -p $d
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fvisibility=hidden -fno-gpu-rdc -Wno-unused-result -DMVRT_EXPERIMENT $@"
-S="api kernels_rt kernels_setup svo_build kernels_denoise kernels_surface kernels_walk"
+S=$(python3 -c "import sys; sys.path.insert(0, 'massivevoxelraytracing_amd'); import build; print(' '.join(s[:-4] for s in build.SOURCES))") # the library's own list
 for s in $S; do
   if [ $s = kernels_rt ] || [ ! -f $d/$s.o ]; then /opt/rocm/bin/hipcc $F -c massivevoxelraytracing_amd/csrc/$s.hip -o $d/$s.o & fi
 done
