@@ -50,6 +50,11 @@ MVRT_DI void proj2i( int x, int y, int z, int axis, int* a, int* b )
 MVRT_DI int projRemI( int x, int y, int z, int axis ) { return axis == 0 ? z : ( axis == 1 ? x : y ); }
 MVRT_DI f3 cross3( f3 a, f3 b ) { return mk3( a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x ); }
 
+// float -> int of the voxelizer as the reference's HOST build performs it (x86 cvttss2si: NaN and everything outside [-2^31, 2^31) give INT_MIN).  The
+// hardware conversion gives 0 for NaN and saturates instead, which made a triangle with a zero normal (two equal vertices: kx, ky NaN) emit the voxels
+// of z index 0 of its bounding box where the reference and the oracle emit none (tests/test_gpu_reference_pins.py).
+MVRT_DI int f2iHost( float f ) { return ( f >= -2147483648.0f && f < 2147483648.0f ) ? (int)f : (int)0x80000000u; }
+
 struct VT
 {
 	int major;
@@ -71,8 +76,8 @@ struct VT
 		}
 		f3 bl = mk3( smin( smin( v0.x, v1.x ), v2.x ), smin( smin( v0.y, v1.y ), v2.y ), smin( smin( v0.z, v1.z ), v2.z ) );
 		f3 bu = mk3( smax( smax( v0.x, v1.x ), v2.x ), smax( smax( v0.y, v1.y ), v2.y ), smax( smax( v0.z, v1.z ), v2.z ) );
-		int lx = (int)floorf( ( bl.x - origin.x ) / dps ), ly = (int)floorf( ( bl.y - origin.y ) / dps ), lz = (int)floorf( ( bl.z - origin.z ) / dps );
-		int ux = (int)floorf( ( bu.x - origin.x ) / dps ), uy = (int)floorf( ( bu.y - origin.y ) / dps ), uz = (int)floorf( ( bu.z - origin.z ) / dps );
+		int lx = f2iHost( floorf( ( bl.x - origin.x ) / dps ) ), ly = f2iHost( floorf( ( bl.y - origin.y ) / dps ) ), lz = f2iHost( floorf( ( bl.z - origin.z ) / dps ) );
+		int ux = f2iHost( floorf( ( bu.x - origin.x ) / dps ) ), uy = f2iHost( floorf( ( bu.y - origin.y ) / dps ) ), uz = f2iHost( floorf( ( bu.z - origin.z ) / dps ) );
 		lx = lx < 0 ? 0 : lx;
 		ly = ly < 0 ? 0 : ly;
 		lz = lz < 0 ? 0 : lz;
@@ -144,8 +149,8 @@ struct VT
 		}
 		float minIndexF = smax( ( miny - oy ) / dps, -2147483648.0f );
 		float maxIndexF = smin( ( maxy - oy ) / dps, 2147483520.0f );
-		int lowerY = (int)ceilf( minIndexF );
-		int upperY = (int)floorf( maxIndexF );
+		int lowerY = f2iHost( ceilf( minIndexF ) );
+		int upperY = f2iHost( floorf( maxIndexF ) );
 		lowerY = lowerY < loy ? loy : lowerY;
 		upperY = upperY > hiy ? hiy : upperY;
 		return i2{ lowerY, upperY };
@@ -158,16 +163,16 @@ struct VT
 		if( conservative ) // :296-301
 		{
 			float tmax = var + cMax, tmin = var + cMin;
-			zmin = (int)floorf( ( tmin - oz ) / dps );
-			zmax = (int)floorf( ( tmax - oz ) / dps );
+			zmin = f2iHost( floorf( ( tmin - oz ) / dps ) );
+			zmax = f2iHost( floorf( ( tmax - oz ) / dps ) );
 		}
 		else
 		{
 			float tsix = var + cSix;
 			float indexf = ( tsix - oz ) / dps;
 			float zf = floorf( indexf );
-			int z = (int)zf;
-			zmin = indexf == zf ? z - 1 : z;
+			int z = f2iHost( zf );
+			zmin = indexf == zf ? (int)( (uint32_t)z - 1u ) : z; // (z = INT_MIN wraps like the host build, the range is empty either way)
 			zmax = z;
 		}
 		zmin = zmin < loz ? loz : zmin;

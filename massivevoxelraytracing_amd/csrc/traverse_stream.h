@@ -604,9 +604,13 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 							st = 2u;
 						}
 						else if( ( ( mvrt_f2u( tx1 - t0x ) & 0x7F800000u ) == 0x7F800000u ) || ( ( mvrt_f2u( ty1 - t0y ) & 0x7F800000u ) == 0x7F800000u ) ||
-								 ( ( mvrt_f2u( tz1 - t0z ) & 0x7F800000u ) == 0x7F800000u ) )
+								 ( ( mvrt_f2u( tz1 - t0z ) & 0x7F800000u ) == 0x7F800000u ) ||
+								 !( smax( max3f( sabs( tx1 ), sabs( ty1 ), sabs( tz1 ) ), max3f( sabs( t0x ), sabs( t0y ), sabs( t0z ) ) ) < 1.7014118346046923e38f ) )
 						{
-							// irregular ray (inf / NaN slab delta): exact reference emulation, see traceIrregular
+							// irregular ray (inf / NaN slab delta): exact reference emulation, see traceIrregular.  Also a ray with a slab time of 2^127 or more (every
+							// direction component zero or denormal: 1 / rd clamped to MAX_FLOAT / extent): its deltas are finite, but the reference's mid-plane
+							// 0.5f * ( t0 + t1 ) overflows to +inf, the walk then goes down the first children and reports a HIT at t = +inf (voxCommon.hpp:338-340,
+							// 324-331), which the fast loop ends as a miss (tests/test_gpu_reference_pins.py::test_trace_batch)
 							float resT = MVRT_MAXF;
 							int resN = -1;
 							traceIrregular<FL>( s, tx1, ty1, tz1, t0x, t0y, t0z, vMask, mySpill, spillStride, &resT, &resN, &path, &descents );

@@ -674,6 +674,13 @@ ORC_API int64_t orc_voxelize( const float* tris, const float* cols, const float*
 	return n;
 }
 
+// Voxels per triangle of the same loop (what the reference's counting pass voxKernel.cu:68-88 adds to its counter, triangle by triangle).
+ORC_API void orc_voxelize_counts( const float* tris, int64_t nTri, const float* origin3, float dps, int gridRes, int sixSeparating, uint32_t* countsOut )
+{
+	for( int64_t t = 0; t < nTri; t++ )
+		countsOut[t] = (uint32_t)orc_voxelize( tris + t * 9, nullptr, nullptr, 1, origin3, dps, gridRes, sixSeparating, nullptr, nullptr, 0 );
+}
+
 // mergeVoxels (voxRT.cpp:14-51) == `unique` kernel (voxKernel.cu:170-243): sort by morton, one
 // entry per distinct code, colour/emission = INTEGER mean over duplicates, alpha 255.
 // In place; returns the unique count and *hasEmission (voxKernel.cu:225-228).
@@ -1135,6 +1142,13 @@ static inline float3 getHitN( int major, float3 rd )
 	case 2: return { 0.0f, 0.0f < rd.y ? -1.0f : 1.0f, 0.0f };
 	}
 	return { 0.0f, 0.0f, 0.0f };
+}
+ORC_API void orc_get_hit_n( int major, const float* rd3, float* out3 )
+{
+	float3 n = getHitN( major, float3{ rd3[0], rd3[1], rd3[2] } );
+	out3[0] = n.x;
+	out3[1] = n.y;
+	out3[2] = n.z;
 }
 
 // ------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 It wraps oracle/libmvrt_oracle.so (the C++ restatement, oracle/mvrt_oracle.cpp) and, when
-present, oracle/_ref/libmvrt_ref.so (the two reference sources that compile as they lie).
+present, the two libraries of oracle/_ref/ that are compiled from the reference sources as they lie (libmvrt_ref.so: morton + Murmur;
+libmvrt_ref_walk.so: voxelizer context, octree builders, traversal and the small helpers of voxCommon.hpp).
 """
 import ctypes as C
 import os
@@ -13,6 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libmvrt_oracle.so")
 _REF = os.path.join(_HERE, "_ref", "libmvrt_ref.so")
+_REF_WALK = os.path.join(_HERE, "_ref", "libmvrt_ref_walk.so")
 
 MAX_FLOAT = np.float32(3.402823466e38)
 PMJ_FLOATS = 2 * 4096 * 128
@@ -87,6 +89,8 @@ _resolve = _sig("orc_resolve", None, [_vp, _i64, _i32, _vp])
 _compact = _sig("orc_compact_indices", _i64, [_vp, _i64, _vp, _vp])
 _detmath = _sig("orc_detmath_eval", None, [_i32, _vp, _vp, _i64, _vp])
 _sizes = _sig("orc_struct_sizes", _i32, [_vp])
+_voxelize_counts = _sig("orc_voxelize_counts", None, [_vp, _i64, _vp, _f32, _i32, _i32, _vp])
+_get_hit_n = _sig("orc_get_hit_n", None, [_i32, _vp, _vp])
 
 NODE_DTYPE = np.dtype([("mask", "u1"), ("_pad", "u1", 3), ("children", "<u4", 8), ("psum", "<u4", 8)])
 assert NODE_DTYPE.itemsize == 68
@@ -177,6 +181,22 @@ def voxelize(tris, origin, dps, grid_res, cols=None, emis=None, six_separating=T
     attrs = np.zeros((n, 8), np.uint8)
     _voxelize(_p(tris), _p(cols), _p(emis), len(tris), _p(origin), dps, grid_res, int(six_separating), _p(morton), _p(attrs), n)
     return morton, attrs
+
+
+def voxelize_counts(tris, origin, dps, grid_res, six_separating=True):
+    """Voxels per triangle of voxelize(): uint32[n]."""
+    tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+    origin = np.ascontiguousarray(origin, np.float32)
+    out = np.zeros(len(tris), np.uint32)
+    _voxelize_counts(_p(tris), len(tris), _p(origin), dps, grid_res, int(six_separating), _p(out))
+    return out
+
+
+def get_hit_n(major, rd):
+    rd = np.ascontiguousarray(rd, np.float32)
+    out = np.zeros(3, np.float32)
+    _get_hit_n(int(major), _p(rd), _p(out))
+    return out
 
 
 def merge_voxels(morton, attrs):
@@ -391,8 +411,89 @@ def struct_sizes():
     return dict(zip(["OctreeNode", "StackElement", "OctreeTask", "VoxelAttirb", "CameraPinhole"], (int(v) for v in out[:n])))
 
 
-# ---- oracle/_ref: the reference's own morton.hpp + smhasher MurmurHash3, compiled as they lie ---
+# ---- oracle/_ref: reference sources compiled as they lie (oracle/Makefile, target `ref`) ----------
+class RefWalk:
+    """oracle/_ref/libmvrt_ref_walk.so (oracle/ref_shim_walk.cpp): the reference's VTContext, buildOctreeDAGReference / buildOctreeNaive /
+    embedMask, octreeTraverse_EfficientParametric and the small helpers of voxCommon.hpp, behind batch entry points."""
+
+    def __init__(self, path):
+        w = C.CDLL(path)
+        self._voxelize = self._bind(w, "refw_voxelize", _i64, [_vp, _i64, _i32, _vp, _f32, _i32, _vp, _vp, _i64])
+        self._build = self._bind(w, "refw_build_octree", _i64, [_vp, _i64, _i32, _i32, _i32, _vp, _i64])
+        self._trace = self._bind(w, "refw_trace_batch", None, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp])
+        self._hit_n = self._bind(w, "refw_get_hit_n", None, [_i32, _vp, _vp])
+        self._bsearch = self._bind(w, "refw_bsearch_i32", _i32, [_vp, _i32, _i32])
+        self._sort_bits = self._bind(w, "refw_sort_bits_morton", _i32, [_u32])
+        self._hc = [self._bind(w, "refw_hash_combine%d" % k, _u32, [_u32] * k) for k in (2, 3, 4)]
+        self._sizes = self._bind(w, "refw_struct_sizes", _i32, [_vp])
+
+    @staticmethod
+    def _bind(w, name, res, args):
+        f = getattr(w, name)  # AttributeError on a missing symbol: a failure, never a skip
+        f.restype = res
+        f.argtypes = args
+        return f
+
+    def voxelize(self, tris, origin, dps, grid_res, six_separating=True):
+        """-> (morton u64[total] in the reference's order, duplicates kept; counts u32[n] per triangle)"""
+        tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+        origin = np.ascontiguousarray(origin, np.float32)
+        counts = np.zeros(len(tris), np.uint32)
+        n = self._voxelize(_p(tris), len(tris), int(six_separating), _p(origin), dps, grid_res, _p(counts), None, 0)
+        morton = np.zeros(n, np.uint64)
+        self._voxelize(_p(tris), len(tris), int(six_separating), _p(origin), dps, grid_res, _p(counts), _p(morton), n)
+        return morton, counts
+
+    def build_octree(self, morton, grid_res, dag=True, embed=True):
+        """68-byte nodes.  dag=False is buildOctreeNaive, which leaves psum unwritten: only mask and children mean anything then."""
+        morton = np.ascontiguousarray(morton, np.uint64)
+        n = self._build(_p(morton), len(morton), grid_res, int(dag), int(embed), None, 0)
+        nodes = np.zeros(n, NODE_DTYPE)
+        self._build(_p(morton), len(morton), grid_res, int(dag), int(embed), _p(nodes), n)
+        return nodes
+
+    def trace(self, nodes, lower, upper, ro, rd, is_shadow=None):
+        """Embedded nodes only (ENABLE_EMBEDED_MASK is hard-wired, voxCommon.hpp:9).  Root = last node.  Misses keep t = MAX_FLOAT,
+        nMajor = -1, vIndex = 0."""
+        nodes = np.ascontiguousarray(nodes)
+        assert nodes.dtype.itemsize == 68 and 0 < len(nodes) < 0xFFFFFF
+        lower = np.ascontiguousarray(lower, np.float32)
+        upper = np.ascontiguousarray(upper, np.float32)
+        ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
+        rd = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
+        n = len(ro)
+        assert len(rd) == n and lower.size == 3 and upper.size == 3
+        sh = None if is_shadow is None else np.ascontiguousarray(is_shadow, np.uint8)
+        assert sh is None or len(sh) == n
+        t, nm, vi = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        self._trace(_p(nodes), len(nodes), _p(lower), _p(upper), n, _p(ro), _p(rd), _p(sh), _p(t), _p(nm), _p(vi))
+        return {"t": t, "nMajor": nm, "vIndex": vi}
+
+    def get_hit_n(self, major, rd):
+        rd = np.ascontiguousarray(rd, np.float32)
+        out = np.zeros(3, np.float32)
+        self._hit_n(int(major), _p(rd), _p(out))
+        return out
+
+    def bsearch(self, xs, x):
+        xs = np.ascontiguousarray(xs, np.int32)
+        return int(self._bsearch(_p(xs), len(xs), x))
+
+    def sort_bits_morton(self, grid_res):
+        return int(self._sort_bits(grid_res))
+
+    def hash_combine(self, *words):
+        return int(self._hc[len(words) - 2](*words))
+
+    def struct_sizes(self):
+        out = np.zeros(8, np.int32)
+        n = self._sizes(_p(out))
+        return dict(zip(["OctreeNode", "StackElement", "OctreeTask", "VoxelAttirb"], (int(v) for v in out[:n])))
+
+
 def load_ref():
+    """None where oracle/_ref holds no libmvrt_ref.so.  The returned library carries `.walk`: a RefWalk, or None where libmvrt_ref_walk.so
+    is absent."""
     if not os.path.exists(_REF):
         return None
     r = C.CDLL(_REF)
@@ -401,4 +502,5 @@ def load_ref():
     r.ref_murmur3_x86_32.argtypes = [_vp, _i32, _u32]
     for nm in ("ref_morton_decode_naive", "ref_morton_decode_pext", "ref_morton_decode_magicbits"):
         getattr(r, nm).argtypes = [_u64, _vp]
+    r.walk = RefWalk(_REF_WALK) if os.path.exists(_REF_WALK) else None
     return r

@@ -1,6 +1,7 @@
 /*
- * ref_shim.cpp -- C entry points over the two pieces of the REFERENCE that compile unmodified in
- * this image: morton.hpp (morton.hpp:5-113) and libs/smhasher/MurmurHash3.cpp.  This file contains
+ * ref_shim.cpp -- C entry points over the two pieces of the REFERENCE that compile unmodified with
+ * g++ and no stand-in header: morton.hpp (morton.hpp:5-113) and libs/smhasher/MurmurHash3.cpp (the
+ * voxelizer, the builders and the traversal are in ref_shim_walk.cpp).  This file contains
  * no reference code; it includes the reference headers from $(REF) at build time (oracle/Makefile,
  * target `ref`) and the resulting library lives only in oracle/_ref/ (git-ignored).
  * TEST INFRASTRUCTURE: used by tests/test_oracle_pins.py to pin the oracle's integer helpers the
