@@ -1,7 +1,7 @@
 // voxel_mesh -- the reference voxelizer's "Save As Mesh" (voxMesh.cpp:111-219) without the GUI: voxelize a Wavefront .obj on the GPU and write the exposed
 // faces of the voxel set as a PLY quad mesh, one colour per face from its voxel.
 //
-//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--ao [samples] [--ao-radius voxels]]
+//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill] [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -9,6 +9,8 @@
 // --ao: bake per-face ambient occlusion into the colours (mvrt_svo_surface_ao): of `samples` rays (a power of two up to 256, default 64; the number, if any,
 // directly follows --ao) `open` leave the face unoccluded within --ao-radius voxels (default 8), and every colour byte c becomes (c * open + samples / 2) / samples.
 // With and without --no-weld; not with --merge / --merge-any: the bake is per face and a rectangle has no single value.
+// --fill: the empty cells enclosed by the voxel shell become white voxels before the surface is extracted (mvrt_svo_fill_enclosed), so the inner side of the
+// shell, which no outside ray can see, is not written; a line reports the voxels before and after and the cell and region counts.  With every other flag.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +22,7 @@
 
 int main( int argc, char** argv )
 {
-	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false;
+	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false, fill = false;
 	int aoSamples = 64;
 	float aoRadiusVoxels = 8.0f;
 	std::vector<const char*> pos;
@@ -30,6 +32,7 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--merge" ) ) merge = true;
 		else if( !std::strcmp( argv[i], "--merge-any" ) ) merge = mergeAny = true;
 		else if( !std::strcmp( argv[i], "--conservative" ) ) conservative = true;
+		else if( !std::strcmp( argv[i], "--fill" ) ) fill = true;
 		else if( !std::strcmp( argv[i], "--ao" ) )
 		{
 			ao = true;
@@ -40,7 +43,8 @@ int main( int argc, char** argv )
 	}
 	if( pos.size() != 3 )
 	{
-		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--ao [samples] [--ao-radius voxels]]\n"
+		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill] [--ao [samples] [--ao-radius voxels]]\n"
+					 "  --fill       fill the empty cells the voxel shell encloses (white voxels) before the surface is extracted\n"
 					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
 					 "               --ao-radius voxels (default 8); not with --merge / --merge-any\n"
 					 "  --no-weld    four vertices of its own per face instead of shared ones\n"
@@ -72,6 +76,15 @@ int main( int argc, char** argv )
 	void* stream = nullptr;
 	mvrt::IntersectorOctreeGPU svo;
 	svo.build( vertices, vcolors, vemissions, nullptr, stream, origin, dps, gridRes, conservative ? MVRT_BUILD_CONSERVATIVE : 0 );
+	if( fill )
+	{
+		const uint32_t before = svo.m_numberOfVoxels;
+		uint64_t nRegions = 0;
+		const uint64_t nCells = svo.enclosedCells( 0, nullptr, nullptr, &nRegions, stream );
+		const uint64_t nFilled = svo.fillEnclosed( nullptr, stream );
+		std::printf( "fill: voxels %u -> %u, enclosed cells %llu in %llu regions, filled %llu\n", before, svo.m_numberOfVoxels, (unsigned long long)nCells,
+					 (unsigned long long)nRegions, (unsigned long long)nFilled );
+	}
 	std::vector<uint32_t> xyz, attribs;
 	svo.readVoxels( xyz, attribs, stream );
 

@@ -187,6 +187,35 @@ int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, uint64_t rectC
 							 uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut,
 							 uint64_t* nVerticesOut, void* stream );
 
+/* The enclosed empty cells of the voxel set, and the fill that makes a shell solid (new; the reference has none).  The work grows with the number of voxels, not
+ * with the gridRes^3 cells of the grid.  Definitions:
+ *   - Grid: [0, R)^3 with R = gridRes.  An empty cell is a grid cell without a voxel.
+ *   - Neighbours: two empty cells are neighbours when they share a FACE (6-connectivity).  Diagonal contact does not connect.
+ *   - Exterior: an empty cell is exterior when its connected component contains a cell with a coordinate equal to 0 or R - 1 -- the rule of
+ *     mvrt_svo_surface_masks: outside the grid is empty.
+ *   - Enclosed: every other empty cell.  Its component is a region.
+ *   - Listing order: the enclosed cells in ascending Morton code (the order of mvrt_svo_read_voxels, x in bit 0 of each group); regions are numbered 0, 1, ... in
+ *     order of first appearance in that list, so region[0] == 0 and a new id is always the previous maximum + 1.
+ *   - The result is a property of the voxel set alone: unique and independent of any processing order.
+ * mvrt_svo_enclosed_cells follows the rules of mvrt_svo_surface_quads word for word: every octree this library built or edited is accepted, in every flavour, the
+ * tree flavour included (only the codes are read); an upload is refused ("keeps no Morton codes": it works after one mvrt_svo_rebuild), an empty handle too ("no
+ * octree"), both before any GPU work.  The handle is never modified.  The call blocks (the counts come back to the host).  xyzDev: 3 x uint32 per cell, regionDev:
+ * one uint32 per cell, `capacity` cells each; any output may be NULL, all arrays NULL is the sizing call (capacity is then ignored).  A capacity below the count is
+ * an error: the counts are still returned and NOTHING is written.  A listing of 2^32 cells or more is refused on the host, the message names the count and the
+ * counts are still returned.  Zero enclosed cells is a success with both counts 0.  gridRes up to 2^21.  A failed allocation of scratch returns an error, leaves
+ * the octree whole and leaks nothing. */
+int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev /* 3 per cell */, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut,
+							 void* stream );
+/* Fill the enclosed cells: the handle's octree becomes exactly what mvrt_svo_edit_voxels leaves when given the cells of mvrt_svo_enclosed_cells, each with
+ * fillAttribHost (8 bytes, VoxelAttirb {color, emission}; NULL = white, no emission) and MVRT_VOXEL_SET -- nodes and numbering, attributes with alpha stored as
+ * 255, the recomputed hasEmission, the flavour a fresh build picks, the resident derived tables, the kept build flags, origin, dps and emission scale.  Existing
+ * voxels keep their attributes.  The cells never travel to the host.  Failures and ordering are the edit's: the new arrays are built next to the old octree, a
+ * failure before they are adopted leaves the handle unchanged, one after that leaves it empty (see mvrt_svo_destroy above); through mvrt_pt_intersector( pt ) the
+ * steps issued before finish first and the frame buffer is not cleared; every mvrt_device_octree view of the handle is invalidated.  With zero enclosed cells the
+ * call succeeds with *nFilledOut = 0 and leaves the handle untouched (no rebuild, views stay valid).  Refused with the handle unchanged: an upload, an empty
+ * handle, and numberOfVoxels + nCells >= 2^32 - 1 (the message names the count).  nFilledOut may be NULL. */
+int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8] /* VoxelAttirb, NULL = white, no emission */, uint64_t* nFilledOut, void* stream );
+
 /* Adopt an SVO built elsewhere (e.g. IntersectorOctree::buildDAGReference on the CPU, IntersectorOctree.hpp:
  * 224-231): nodes in the reference's 68-byte layout, root last.  embeddedMask = 0 selects the variant where
  * the mask is fetched from the node (voxCommon.hpp:353-356; required above 0xFFFFFF nodes). */

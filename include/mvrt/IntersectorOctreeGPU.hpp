@@ -153,6 +153,37 @@ struct IntersectorOctreeGPU
 		refresh();
 	}
 
+	// the empty cells that no path of face-neighbouring empty cells joins to the grid border, and the fill that turns them into voxels (mvrt_svo_enclosed_cells /
+	// mvrt_svo_fill_enclosed; semantics in mvrt.h).  Device-pointer form: either output may be nullptr, both nullptr = the sizing call; returns the cell count.
+	uint64_t enclosedCells( uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nRegions, void* stream ) const
+	{
+		uint64_t nCells = 0;
+		check( mvrt_svo_enclosed_cells( m_handle, capacity, xyzDev, regionDev, &nCells, nRegions, stream ), "IntersectorOctreeGPU::enclosedCells" );
+		return nCells;
+	}
+	// host-vector form: xyz = 3 entries per cell in ascending Morton order, region = 1 per cell, numbered by first appearance; returns the number of regions
+	uint64_t enclosedCells( std::vector<uint32_t>& xyz, std::vector<uint32_t>& region, void* stream ) const
+	{
+		uint64_t nRegions = 0;
+		const uint64_t n = enclosedCells( 0, nullptr, nullptr, &nRegions, stream );
+		xyz.resize( n * 3 );
+		region.resize( n );
+		Staged x( nullptr, n * 12, stream ), r( nullptr, n * 4, stream );
+		if( n ) enclosedCells( n, (uint32_t*)x.p, (uint32_t*)r.p, nullptr, stream );
+		fetch( xyz, x, stream );
+		fetch( region, r, stream );
+		return nRegions;
+	}
+	// every enclosed cell becomes a voxel with fillAttrib (8 bytes VoxelAttirb, nullptr = white, no emission), as editVoxels would set it; returns the number of
+	// cells filled.  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
+	uint64_t fillEnclosed( const uint8_t* fillAttrib = nullptr, void* stream = nullptr )
+	{
+		uint64_t nFilled = 0;
+		check( mvrt_svo_fill_enclosed( m_handle, fillAttrib, &nFilled, stream ), "IntersectorOctreeGPU::fillEnclosed" );
+		refresh();
+		return nFilled;
+	}
+
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const

@@ -85,6 +85,8 @@ SIGNATURES = {
     "mvrt_svo_surface_quads": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_mesh": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_merged": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_enclosed_cells": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_fill_enclosed": (_i32, [_vp, _vp, _vp, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
     "mvrt_svo_device_view": (_i32, [_vp, _vp]),
@@ -398,6 +400,30 @@ class IntersectorOctreeGPU:
         """mvrt_svo_rebuild: the octree becomes the one build_voxels would build from its walked voxels (attribute bytes and hasEmission kept), after which
         read_voxels / edit_voxels / surface_* accept an upload.  flags: BUILD_NO_DAG | BUILD_NO_EMBEDDED_MASK.  Invalidates device_view() snapshots."""
         _check(lib().mvrt_svo_rebuild(self._h, int(flags), stream))
+
+    def enclosed_cells_device(self, capacity=0, xyz=None, region=None, stream=None):
+        """mvrt_svo_enclosed_cells into caller device arrays of `capacity` cells (either may be None; both None = the sizing call); returns (nCells, nRegions).
+        On MvrtError nothing was written."""
+        nc, nr = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_enclosed_cells(self._h, int(capacity), _dev_ptr(xyz), _dev_ptr(region), C.byref(nc), C.byref(nr), stream))
+        return nc.value, nr.value
+
+    def enclosed_cells(self, stream=None):
+        """the empty cells no 6-connected path of empty cells joins to the grid border: {xyz (n, 3) uint32 in ascending Morton order, region (n,) uint32 numbered
+        by first appearance in that order, nRegions}"""
+        n, nr = self.enclosed_cells_device(stream=stream)
+        xyz, region = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32)
+        if n:
+            self.enclosed_cells_device(n, xyz, region, stream)
+        return {"xyz": xyz.to_host(), "region": region.to_host(), "nRegions": nr}
+
+    def fill_enclosed(self, attrib=None, stream=None):
+        """mvrt_svo_fill_enclosed: every enclosed cell becomes a voxel with `attrib` (8 bytes VoxelAttirb {color, emission}; None = white, no emission), exactly
+        as edit_voxels would set them; returns the number of cells filled (0: the handle was not touched).  Invalidates device_view() snapshots otherwise."""
+        a = None if attrib is None else np.ascontiguousarray(attrib).view(np.uint8).reshape(8)
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_fill_enclosed(self._h, _hp(a), C.byref(n), stream))
+        return n.value
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""

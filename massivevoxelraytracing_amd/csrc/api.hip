@@ -533,6 +533,49 @@ MVRT_EXPORT int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, ui
 						  (hipStream_t)stream );
 }
 
+// Enclosed empty cells and the fill (kernels_fill.hip).  The listing reads the sorted codes alone, like the surface calls.  The fill hands the cells, which stay on
+// the device, to the edit's own path: what it leaves is what mvrt_svo_edit_voxels leaves, by construction.
+MVRT_EXPORT int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_enclosed_cells", &s ) ) return 1;
+	return enclosedCells( s, capacity, xyzDev, regionDev, nCellsOut, nRegionsOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8], uint64_t* nFilledOut, void* stream )
+{
+	if( nFilledOut ) *nFilledOut = 0;
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_fill_enclosed", &s ) ) return 1;
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf xyz, attribs;
+	uint64_t nCells = 0;
+	if( enclosedCellsUnordered( s, xyz, &nCells, st ) ) return 1;
+	if( nCells == 0 ) return 0; // nothing to fill: the handle is not touched
+	REQUIRE( (uint64_t)svo->oct.nVoxels + nCells < 0xFFFFFFFFull, "mvrt_svo_fill_enclosed: %llu voxels and %llu enclosed cells exceed the 32-bit index range of the builder",
+			 (unsigned long long)svo->oct.nVoxels, (unsigned long long)nCells );
+	if( fillAttribHost )
+	{
+		uint2 a;
+		memcpy( &a, fillAttribHost, 8 );
+		if( attribs.alloc( nCells * 8 ) || launchFillAttribs( a, nCells, attribs.as<uint2>(), st ) ) return 1;
+	}
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
+	const mvrt_svo_info& info = svo->oct.info;
+	SvoBuildResult r;
+	int structural = 0;
+	uint32_t he = 0;
+	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nCells, (int)info.gridRes,
+					   svo->oct.buildFlags, st, &r, &structural, &he ) )
+		return 1;
+	REQUIRE( structural, "mvrt_svo_fill_enclosed: internal error: the enclosed cells hold voxels" ); // (every cell is an insert)
+	xyz.release();
+	attribs.release();
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	if( adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, svo->oct.buildFlags ) ) return 1; // (arguments are read before the old octree goes)
+	if( nFilledOut ) *nFilledOut = nCells;
+	return 0;
+}
+
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );

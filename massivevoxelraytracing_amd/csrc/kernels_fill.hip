@@ -1,0 +1,379 @@
+// kernels_fill.hip -- the enclosed empty cells of the voxel set (mvrt_svo_enclosed_cells / mvrt_svo_fill_enclosed, mvrt.h).  The work grows with
+// the number of voxels, never with the number of cells of the grid.
+//
+//   rows    the voxels sorted by the linear key ( z * R + y ) * R + x (one radix sort of the codes): a row is one (y, z), its voxels lie together by x.
+//   gaps    gap i = the empty run between sorted voxels i and i + 1 where they share a row and their x differ by more than 1.  The run before the first voxel of
+//           a row, the run behind its last one and every row without voxels hold a border cell: exterior by themselves.  Only a gap can be enclosed.
+//   unions  node 0 = EXTERIOR, node i + 1 = gap i.  One thread per gap looks at its four neighbour rows (y +- 1, z), (y, z +- 1): a row outside the grid joins the
+//           gap to EXTERIOR; in a row inside it a binary search finds the first voxel at or behind the gap's x0 and a walk up to x1 unites the gap with every
+//           gap it overlaps and with EXTERIOR for every overlapped stretch that is an end run or a voxel-free row.  The larger root is always hooked under the
+//           smaller one: the root of a set is its lowest id whatever the schedule, and EXTERIOR is the root of everything exterior.
+//   emit    flatten, length of every gap whose root is not EXTERIOR, 64-bit exclusive scan, one workgroup per 256 gaps writes its cells (a contiguous run of
+//           the output), radix sort of (Morton code, root), roots ranked by the position of their first cell.
+//
+// Nothing here waits on another thread.  find() walks strictly downwards in id (a parent is never larger than its child), unite() retries only after a failed
+// compare-and-swap, and then from a strictly smaller id; the neighbour walk advances its voxel index every turn.
+#include <hipcub/hipcub.hpp>
+
+#include "launch.h"
+
+#define WAVE 64
+#define FB 256 // threads per workgroup, and gaps per workgroup of the emit kernel
+
+namespace
+{
+MVRT_DI uint32_t compact3( uint64_t x )
+{
+	x &= 0x1249249249249249ull;
+	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
+	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
+	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
+	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
+	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
+	return (uint32_t)x;
+}
+
+__global__ void __launch_bounds__( FB ) kFillLinearKeys( const uint64_t* __restrict__ morton, uint32_t n, uint32_t L, uint64_t* __restrict__ keys )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	if( i >= n ) return;
+	const uint64_t c = morton[i];
+	keys[i] = ( (uint64_t)compact3( c >> 2 ) << ( 2u * L ) ) | ( (uint64_t)compact3( c >> 1 ) << L ) | compact3( c );
+}
+
+// lin: the sorted linear keys.  Gap i exists when voxels i and i + 1 share a row and are not adjacent; its cells are x in [ x(i) + 1, x(i + 1) - 1 ]
+MVRT_HDI uint64_t gapLength( const uint64_t* __restrict__ lin, uint32_t n, uint32_t L, uint64_t i )
+{
+	if( i + 1 >= n ) return 0;
+	const uint64_t a = lin[i], b = lin[i + 1];
+	return ( a >> L ) == ( b >> L ) ? b - a - 1ull : 0ull;
+}
+
+// ---- union-find over node ids: parent[v] <= v always, a root has parent[v] == v, only roots are ever hooked and only under smaller ids ------------------------
+MVRT_DI uint32_t ufLoad( uint32_t* p ) { return __hip_atomic_load( p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ); }
+MVRT_DI void ufStore( uint32_t* p, uint32_t v ) { __hip_atomic_store( p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ); }
+// v strictly decreases.  Path halving on the way: a node that is no root (it never becomes one again) is pointed at its grandparent, an ancestor with a lower id
+MVRT_DI uint32_t ufFind( uint32_t* parent, uint32_t v )
+{
+	for( ;; )
+	{
+		const uint32_t p = ufLoad( parent + v );
+		if( p >= v ) return v; // ( p == v: a root )
+		const uint32_t gp = ufLoad( parent + p );
+		if( gp < p ) ufStore( parent + v, gp );
+		v = p;
+	}
+}
+MVRT_DI void ufUnite( uint32_t* parent, uint32_t a, uint32_t b )
+{
+	for( ;; )
+	{
+		a = ufFind( parent, a );
+		b = ufFind( parent, b );
+		if( a == b ) return;
+		if( a < b )
+		{
+			const uint32_t t = a;
+			a = b;
+			b = t;
+		}
+		// a > b: hook a under b if a is still a root.  Otherwise somebody hooked it meanwhile, under an id below a: the next find( a ) ends lower, so a + b
+		// strictly decreases from one turn to the next
+		if( atomicCAS( parent + a, a, b ) == a ) return;
+	}
+}
+
+__global__ void __launch_bounds__( FB ) kFillInitParents( uint32_t* __restrict__ parent, uint64_t nNodes )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	if( i < nNodes ) parent[i] = (uint32_t)i;
+}
+
+MVRT_DI uint64_t lowerBound( const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key )
+{
+	while( lo < hi )
+	{
+		const uint64_t mid = ( lo + hi ) >> 1;
+		if( a[mid] < key ) lo = mid + 1;
+		else hi = mid;
+	}
+	return lo;
+}
+
+// gap g = [x0, x1] of some row against the row `row` (= z << L | y, inside the grid)
+MVRT_DI void uniteWithRow( const uint64_t* __restrict__ lin, uint32_t n, uint32_t L, uint32_t* parent, uint32_t g, uint64_t row, uint64_t x0, uint64_t x1 )
+{
+	const uint64_t xMask = ( 1ull << L ) - 1ull;
+	uint64_t j = lowerBound( lin, 0, n, ( row << L ) | x0 ); // the first voxel of the list at or behind (row, x0)
+	uint64_t cur = x0;										 // the first cell of [x0, x1] not yet looked at
+	bool leftVoxel = j > 0 && ( lin[j - 1] >> L ) == row;	 // is there a voxel of this row left of cur?
+	for( ;; j++ )											 // j < n grows every turn
+	{
+		const bool inRow = j < n && ( lin[j] >> L ) == row;
+		const uint64_t xj = inRow ? ( lin[j] & xMask ) : ~0ull;
+		const uint64_t end = inRow && xj <= x1 ? xj : x1 + 1; // the empty stretch [cur, end) lies within [x0, x1]
+		if( end > cur ) ufUnite( parent, g, leftVoxel && inRow ? (uint32_t)j : 0u ); // between voxels j - 1 and j of one row: gap j - 1 = node j; else an end run or a voxel-free row
+		if( !inRow || xj >= x1 ) return;
+		cur = xj + 1;
+		leftVoxel = true;
+	}
+}
+
+__global__ void __launch_bounds__( FB ) kFillUnite( const uint64_t* __restrict__ lin, uint32_t n, uint32_t L, uint32_t* parent )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	const uint64_t len = gapLength( lin, n, L, i );
+	if( len == 0 ) return;
+	const uint64_t R = 1ull << L, xMask = R - 1ull;
+	const uint64_t a = lin[i];
+	const uint64_t row = a >> L, y = row & xMask, z = row >> L;
+	const uint64_t x0 = ( a & xMask ) + 1ull, x1 = x0 + len - 1ull;
+	const uint32_t g = (uint32_t)i + 1u;
+	if( y == 0 || y == R - 1 || z == 0 || z == R - 1 ) ufUnite( parent, g, 0u ); // a neighbour row outside the grid (and the gap's own cells are border cells)
+	if( y > 0 ) uniteWithRow( lin, n, L, parent, g, row - 1ull, x0, x1 );
+	if( y < R - 1 ) uniteWithRow( lin, n, L, parent, g, row + 1ull, x0, x1 );
+	if( z > 0 ) uniteWithRow( lin, n, L, parent, g, row - R, x0, x1 );
+	if( z < R - 1 ) uniteWithRow( lin, n, L, parent, g, row + R, x0, x1 );
+}
+
+// the same walk without the stores, for the flatten: there parent[v] is written once, by v's own thread, with the root
+MVRT_DI uint32_t ufRoot( uint32_t* parent, uint32_t v )
+{
+	for( ;; )
+	{
+		const uint32_t p = ufLoad( parent + v );
+		if( p >= v ) return v;
+		v = p;
+	}
+}
+// parent[v] = the root of v (node v = gap v - 1; the unions are complete: this is a kernel of its own), and the number of enclosed regions = gaps that are
+// their own root.  No path halving here: a halving store of a grandparent read earlier could land behind the store of the root and leave a node that is no
+// root in a flattened entry.  A thread that walks through an entry another thread has flattened already reads the root there, else an ancestor as before
+__global__ void __launch_bounds__( FB ) kFillFlatten( const uint64_t* __restrict__ lin, uint32_t n, uint32_t L, uint32_t* parent, unsigned long long* __restrict__ nRegions )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	uint32_t isRoot = 0;
+	if( i < n && gapLength( lin, n, L, i ) )
+	{
+		const uint32_t g = (uint32_t)i + 1u;
+		const uint32_t r = ufRoot( parent, g );
+		if( r != g ) ufStore( parent + g, r );
+		isRoot = r == g ? 1u : 0u;
+	}
+	const unsigned long long m = __ballot( isRoot );
+	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && m ) atomicAdd( nRegions, (unsigned long long)__popcll( m ) );
+}
+
+struct EnclosedLength // scan input: the cells of gap i where its root is not EXTERIOR (item n - 1 and beyond: 0)
+{
+	const uint64_t* lin;
+	const uint32_t* root;
+	uint32_t n, L;
+	__host__ __device__ uint64_t operator()( uint32_t i ) const
+	{
+		const uint64_t len = gapLength( lin, n, L, i );
+		return len && root[i + 1u] != 0u ? len : 0ull;
+	}
+};
+
+// One workgroup per FB gaps.  offs: n + 1 exclusive offsets (offs[n] = nCells).  The group's cells are the run [offs[first], offs[end]) of the output; thread t
+// takes cells t, t + FB, ... of the run and finds their gap in the group's offsets (LDS), so a wave writes 64 consecutive records.
+// codes / roots: the (Morton code, root) pairs of the listing; xyz: the coordinates as they come (the fill, which sorts them itself).  Either may be null.
+__global__ void __launch_bounds__( FB ) kFillEmit( const uint64_t* __restrict__ lin, const uint32_t* __restrict__ root, const uint64_t* __restrict__ offs, uint32_t n, uint32_t L,
+												   uint64_t* __restrict__ codes, uint32_t* __restrict__ roots, uint32_t* __restrict__ xyz )
+{
+	__shared__ uint32_t sOff[FB + 1];
+	__shared__ uint64_t sLin[FB];
+	__shared__ uint32_t sRoot[FB];
+	const uint64_t first = (uint64_t)blockIdx.x * FB;
+	const uint64_t v = first + threadIdx.x;
+	const uint64_t base = offs[first];
+	sOff[threadIdx.x] = (uint32_t)( offs[v < n ? v : n] - base ); // <= FB * 2^21
+	if( threadIdx.x == 0 ) sOff[FB] = (uint32_t)( offs[first + FB < n ? first + FB : n] - base );
+	sLin[threadIdx.x] = v < n ? lin[v] : 0ull;
+	sRoot[threadIdx.x] = v < n ? root[v + 1] : 0u;
+	__syncthreads();
+	const uint32_t total = sOff[FB];
+	const uint64_t xMask = ( 1ull << L ) - 1ull;
+	for( uint32_t j = threadIdx.x; j < total; j += FB )
+	{
+		// the last gap of the group whose offset is <= j: gaps without cells repeat the offset of the next one and are passed over
+		uint32_t lo = 0, hi = FB;
+		while( hi - lo > 1 )
+		{
+			const uint32_t mid = ( lo + hi ) >> 1;
+			if( sOff[mid] <= j ) lo = mid;
+			else hi = mid;
+		}
+		const uint64_t a = sLin[lo];
+		const uint32_t x = (uint32_t)( a & xMask ) + 1u + ( j - sOff[lo] ), y = (uint32_t)( ( a >> L ) & xMask ), z = (uint32_t)( a >> ( 2u * L ) );
+		const uint64_t c = base + j;
+		if( codes )
+		{
+			codes[c] = mortonEncode( x, y, z );
+			roots[c] = sRoot[lo];
+		}
+		if( xyz )
+		{
+			xyz[c * 3] = x;
+			xyz[c * 3 + 1] = y;
+			xyz[c * 3 + 2] = z;
+		}
+	}
+}
+
+// the cells sorted by Morton code: firstCell[root] = the lowest position of a cell of that root (preset to ~0).  Only the first cell of a run of equal roots asks
+__global__ void __launch_bounds__( FB ) kFillFirstCells( const uint32_t* __restrict__ roots, uint32_t nCells, uint32_t* __restrict__ firstCell )
+{
+	const uint64_t c = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	if( c >= nCells ) return;
+	const uint32_t r = roots[c];
+	if( c == 0 || roots[c - 1] != r ) atomicMin( firstCell + r, (uint32_t)c );
+}
+struct RegionHead // scan input: 1 where cell c is the first one of its region
+{
+	const uint32_t* roots;
+	const uint32_t* firstCell;
+	__host__ __device__ uint32_t operator()( uint32_t c ) const { return firstCell[roots[c]] == c ? 1u : 0u; }
+};
+// rank1: the inclusive scan of the heads.  region = rank of the root's first cell; xyz = the decoded code
+__global__ void __launch_bounds__( FB ) kFillList( const uint64_t* __restrict__ codes, const uint32_t* __restrict__ roots, const uint32_t* __restrict__ firstCell,
+												   const uint32_t* __restrict__ rank1, uint32_t nCells, uint32_t* __restrict__ xyz, uint32_t* __restrict__ region )
+{
+	const uint64_t c = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	if( c >= nCells ) return;
+	if( region ) region[c] = rank1[firstCell[roots[c]]] - 1u;
+	if( xyz )
+	{
+		const uint64_t m = codes[c];
+		xyz[c * 3] = compact3( m );
+		xyz[c * 3 + 1] = compact3( m >> 1 );
+		xyz[c * 3 + 2] = compact3( m >> 2 );
+	}
+}
+
+__global__ void __launch_bounds__( FB ) kFillAttribs( uint2 attrib, uint64_t n, uint2* __restrict__ out )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	if( i < n ) out[i] = attrib;
+}
+
+// what the classification leaves for the emit: the sorted linear keys, the flattened roots (node i + 1 = gap i) and the n + 1 cell offsets
+struct Classified
+{
+	DevBuf lin, root, offs;
+	uint64_t nCells = 0, nRegions = 0;
+};
+int classify( const SurfaceSource& s, Classified* out, hipStream_t st )
+{
+	const uint32_t n = s.nVoxels, L = s.levels;
+	const dim3 grid( divUp( n, FB ) ), block( FB );
+	DevBuf cnt;
+	if( cnt.alloc( 8 ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 8, st ) );
+	{
+		DevBuf keys;
+		if( keys.alloc( (uint64_t)n * 8 ) || out->lin.alloc( (uint64_t)n * 8 ) ) return 1;
+		hipLaunchKernelGGL( kFillLinearKeys, grid, block, 0, st, s.morton, n, L, keys.as<uint64_t>() );
+		MVRT_HIP( hipGetLastError() );
+		if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+				return hipcub::DeviceRadixSort::SortKeys( tmp, tmpBytes, keys.as<uint64_t>(), out->lin.as<uint64_t>(), (uint64_t)n, 0, (int)( 3u * L ), st );
+			} ) )
+			return 1;
+	}
+	const uint64_t nNodes = (uint64_t)n + 1;
+	if( out->root.alloc( nNodes * 4 ) ) return 1;
+	hipLaunchKernelGGL( kFillInitParents, dim3( divUp( nNodes, FB ) ), block, 0, st, out->root.as<uint32_t>(), nNodes );
+	hipLaunchKernelGGL( kFillUnite, grid, block, 0, st, out->lin.as<uint64_t>(), n, L, out->root.as<uint32_t>() );
+	hipLaunchKernelGGL( kFillFlatten, grid, block, 0, st, out->lin.as<uint64_t>(), n, L, out->root.as<uint32_t>(), cnt.as<unsigned long long>() );
+	MVRT_HIP( hipGetLastError() );
+	if( out->offs.alloc( nNodes * 8 ) ) return 1;
+	hipcub::CountingInputIterator<uint32_t> counting( 0u );
+	hipcub::TransformInputIterator<uint64_t, EnclosedLength, hipcub::CountingInputIterator<uint32_t>> lengths( counting,
+																												EnclosedLength{ out->lin.as<uint64_t>(), out->root.as<uint32_t>(), n, L } );
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, lengths, out->offs.as<uint64_t>(), nNodes, st ); } ) ) return 1;
+	unsigned long long h[2] = { 0, 0 };
+	MVRT_HIP( hipMemcpyAsync( &h[0], out->offs.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipMemcpyAsync( &h[1], cnt.p, 8, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	out->nCells = h[0];
+	out->nRegions = h[1];
+	return 0;
+}
+int launchEmit( const SurfaceSource& s, const Classified& c, uint64_t* codes, uint32_t* roots, uint32_t* xyz, hipStream_t st )
+{
+	hipLaunchKernelGGL( kFillEmit, dim3( divUp( s.nVoxels, FB ) ), dim3( FB ), 0, st, c.lin.as<uint64_t>(), c.root.as<uint32_t>(), c.offs.as<uint64_t>(), s.nVoxels, s.levels, codes,
+						roots, xyz );
+	MVRT_HIP( hipGetLastError() );
+	return 0;
+}
+} // namespace
+
+int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, hipStream_t st )
+{
+	Classified c;
+	if( classify( s, &c, st ) ) return 1;
+	if( nCellsOut ) *nCellsOut = c.nCells;
+	if( nRegionsOut ) *nRegionsOut = c.nRegions;
+	if( !xyzDev && !regionDev ) return 0; // the sizing call
+	if( c.nCells >= ( 1ull << 32 ) )
+	{
+		mvrtSetError( "mvrt_svo_enclosed_cells: the %llu enclosed cells are 2^32 or more, beyond what one listing holds; nothing was written", (unsigned long long)c.nCells );
+		return 1;
+	}
+	if( capacity < c.nCells )
+	{
+		mvrtSetError( "mvrt_svo_enclosed_cells: capacity %llu is smaller than the %llu enclosed cells; nothing was written", (unsigned long long)capacity,
+					  (unsigned long long)c.nCells );
+		return 1;
+	}
+	if( c.nCells == 0 ) return 0;
+	const uint32_t nCells = (uint32_t)c.nCells;
+	DevBuf codes, roots, firstCell, rank1;
+	{
+		DevBuf codesA, rootsA;
+		if( codesA.alloc( c.nCells * 8 ) || rootsA.alloc( c.nCells * 4 ) || codes.alloc( c.nCells * 8 ) || roots.alloc( c.nCells * 4 ) ) return 1;
+		if( launchEmit( s, c, codesA.as<uint64_t>(), rootsA.as<uint32_t>(), nullptr, st ) ) return 1;
+		if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+				return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, codesA.as<uint64_t>(), codes.as<uint64_t>(), rootsA.as<uint32_t>(), roots.as<uint32_t>(), c.nCells, 0,
+														   (int)( 3u * s.levels ), st );
+			} ) )
+			return 1;
+	}
+	c.lin.release();
+	c.offs.release();
+	c.root.release();
+	const uint64_t nNodes = (uint64_t)s.nVoxels + 1;
+	if( firstCell.alloc( nNodes * 4 ) || rank1.alloc( c.nCells * 4 ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( firstCell.p, 0xFF, nNodes * 4, st ) );
+	const dim3 grid( divUp( nCells, FB ) ), block( FB );
+	hipLaunchKernelGGL( kFillFirstCells, grid, block, 0, st, roots.as<uint32_t>(), nCells, firstCell.as<uint32_t>() );
+	MVRT_HIP( hipGetLastError() );
+	hipcub::CountingInputIterator<uint32_t> counting( 0u );
+	hipcub::TransformInputIterator<uint32_t, RegionHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, RegionHead{ roots.as<uint32_t>(), firstCell.as<uint32_t>() } );
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, heads, rank1.as<uint32_t>(), c.nCells, st ); } ) ) return 1;
+	// (the caller's arrays are written by this launch alone, behind every allocation and check)
+	hipLaunchKernelGGL( kFillList, grid, block, 0, st, codes.as<uint64_t>(), roots.as<uint32_t>(), firstCell.as<uint32_t>(), rank1.as<uint32_t>(), nCells, xyzDev, regionDev );
+	MVRT_HIP( hipGetLastError() );
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	return 0;
+}
+
+int enclosedCellsUnordered( const SurfaceSource& s, DevBuf& xyz, uint64_t* nCells, hipStream_t st )
+{
+	Classified c;
+	if( classify( s, &c, st ) ) return 1;
+	*nCells = c.nCells;
+	if( c.nCells == 0 || c.nCells >= ( 1ull << 32 ) ) return 0; // (nothing to list / the caller refuses the count)
+	if( xyz.alloc( c.nCells * 12 ) ) return 1;
+	if( launchEmit( s, c, nullptr, nullptr, xyz.as<uint32_t>(), st ) ) return 1;
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	return 0;
+}
+
+int launchFillAttribs( uint2 attrib, uint64_t n, uint2* out, hipStream_t st )
+{
+	hipLaunchKernelGGL( kFillAttribs, dim3( divUp( n, FB ) ), dim3( FB ), 0, st, attrib, n, out );
+	MVRT_HIP( hipGetLastError() );
+	return 0;
+}

@@ -182,6 +182,13 @@ int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexC
 int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev,
 				   float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut, hipStream_t stream );
 
+// enclosed empty cells (kernels_fill.hip; mvrt_svo_enclosed_cells / mvrt_svo_fill_enclosed): only morton, nVoxels and levels of the source are read.  The calls
+// block, keep their scratch in DevBufs and write NOTHING to the caller's arrays unless they succeed.
+int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, hipStream_t stream );
+// the same cells in no particular order into xyz (allocated here, 3 x u32 per cell; left empty when there are none or 2^32 or more: the caller looks at *nCells)
+int enclosedCellsUnordered( const SurfaceSource& s, DevBuf& xyz, uint64_t* nCells, hipStream_t stream );
+int launchFillAttribs( uint2 attrib, uint64_t n, uint2* out, hipStream_t stream ); // n copies of one VoxelAttirb.  Not synchronised.
+
 // octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
 // flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.
 struct WalkSource
