@@ -8,37 +8,26 @@
 //           gap to EXTERIOR; in a row inside it a binary search finds the first voxel at or behind the gap's x0 and a walk up to x1 unites the gap with every
 //           gap it overlaps and with EXTERIOR for every overlapped stretch that is an end run or a voxel-free row.  The larger root is always hooked under the
 //           smaller one: the root of a set is its lowest id whatever the schedule, and EXTERIOR is the root of everything exterior.
-//   emit    flatten, length of every gap whose root is not EXTERIOR, 64-bit exclusive scan, one workgroup per 256 gaps writes its cells (a contiguous run of
-//           the output), radix sort of (Morton code, root), roots ranked by the position of their first cell.
+//   emit    flatten, length of every gap whose root is not EXTERIOR, 64-bit exclusive scan, then the run expansion of voxel_passes.h: one workgroup per 256 gaps
+//           writes its cells, one thread per cell; radix sort of (Morton code, root), roots ranked by the position of their first cell (sortPairsInto, rankHeads).
 //
 // Nothing here waits on another thread.  find() walks strictly downwards in id (a parent is never larger than its child), unite() retries only after a failed
 // compare-and-swap, and then from a strictly smaller id; the neighbour walk advances its voxel index every turn.
-#include <hipcub/hipcub.hpp>
-
 #include "launch.h"
+#include "voxel_passes.h"
 
 #define WAVE 64
 #define FB 256 // threads per workgroup, and gaps per workgroup of the emit kernel
 
 namespace
 {
-MVRT_DI uint32_t compact3( uint64_t x )
-{
-	x &= 0x1249249249249249ull;
-	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
-	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
-	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
-	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
-	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
-	return (uint32_t)x;
-}
-
 __global__ void __launch_bounds__( FB ) kFillLinearKeys( const uint64_t* __restrict__ morton, uint32_t n, uint32_t L, uint64_t* __restrict__ keys )
 {
 	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
 	if( i >= n ) return;
-	const uint64_t c = morton[i];
-	keys[i] = ( (uint64_t)compact3( c >> 2 ) << ( 2u * L ) ) | ( (uint64_t)compact3( c >> 1 ) << L ) | compact3( c );
+	uint32_t x, y, z;
+	mortonDecode( morton[i], x, y, z );
+	keys[i] = ( (uint64_t)z << ( 2u * L ) ) | ( (uint64_t)y << L ) | x;
 }
 
 // lin: the sorted linear keys.  Gap i exists when voxels i and i + 1 share a row and are not adjacent; its cells are x in [ x(i) + 1, x(i + 1) - 1 ]
@@ -87,17 +76,6 @@ __global__ void __launch_bounds__( FB ) kFillInitParents( uint32_t* __restrict__
 {
 	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
 	if( i < nNodes ) parent[i] = (uint32_t)i;
-}
-
-MVRT_DI uint64_t lowerBound( const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key )
-{
-	while( lo < hi )
-	{
-		const uint64_t mid = ( lo + hi ) >> 1;
-		if( a[mid] < key ) lo = mid + 1;
-		else hi = mid;
-	}
-	return lo;
 }
 
 // gap g = [x0, x1] of some row against the row `row` (= z << L | y, inside the grid)
@@ -176,8 +154,7 @@ struct EnclosedLength // scan input: the cells of gap i where its root is not EX
 	}
 };
 
-// One workgroup per FB gaps.  offs: n + 1 exclusive offsets (offs[n] = nCells).  The group's cells are the run [offs[first], offs[end]) of the output; thread t
-// takes cells t, t + FB, ... of the run and finds their gap in the group's offsets (LDS), so a wave writes 64 consecutive records.
+// One workgroup per FB gaps, the run expansion of voxel_passes.h: offs = n + 1 exclusive offsets (offs[n] = nCells), the records are cells, a gap's cells its x in order.
 // codes / roots: the (Morton code, root) pairs of the listing; xyz: the coordinates as they come (the fill, which sorts them itself).  Either may be null.
 __global__ void __launch_bounds__( FB ) kFillEmit( const uint64_t* __restrict__ lin, const uint32_t* __restrict__ root, const uint64_t* __restrict__ offs, uint32_t n, uint32_t L,
 												   uint64_t* __restrict__ codes, uint32_t* __restrict__ roots, uint32_t* __restrict__ xyz )
@@ -185,11 +162,8 @@ __global__ void __launch_bounds__( FB ) kFillEmit( const uint64_t* __restrict__ 
 	__shared__ uint32_t sOff[FB + 1];
 	__shared__ uint64_t sLin[FB];
 	__shared__ uint32_t sRoot[FB];
-	const uint64_t first = (uint64_t)blockIdx.x * FB;
-	const uint64_t v = first + threadIdx.x;
-	const uint64_t base = offs[first];
-	sOff[threadIdx.x] = (uint32_t)( offs[v < n ? v : n] - base ); // <= FB * 2^21
-	if( threadIdx.x == 0 ) sOff[FB] = (uint32_t)( offs[first + FB < n ? first + FB : n] - base );
+	const uint64_t v = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	const uint64_t base = stageRunOffsets<FB>( offs, n, sOff ); // (relative offsets <= FB * 2^21)
 	sLin[threadIdx.x] = v < n ? lin[v] : 0ull;
 	sRoot[threadIdx.x] = v < n ? root[v + 1] : 0u;
 	__syncthreads();
@@ -197,14 +171,7 @@ __global__ void __launch_bounds__( FB ) kFillEmit( const uint64_t* __restrict__ 
 	const uint64_t xMask = ( 1ull << L ) - 1ull;
 	for( uint32_t j = threadIdx.x; j < total; j += FB )
 	{
-		// the last gap of the group whose offset is <= j: gaps without cells repeat the offset of the next one and are passed over
-		uint32_t lo = 0, hi = FB;
-		while( hi - lo > 1 )
-		{
-			const uint32_t mid = ( lo + hi ) >> 1;
-			if( sOff[mid] <= j ) lo = mid;
-			else hi = mid;
-		}
+		const uint32_t lo = findRun( sOff, FB, j );
 		const uint64_t a = sLin[lo];
 		const uint32_t x = (uint32_t)( a & xMask ) + 1u + ( j - sOff[lo] ), y = (uint32_t)( ( a >> L ) & xMask ), z = (uint32_t)( a >> ( 2u * L ) );
 		const uint64_t c = base + j;
@@ -243,13 +210,7 @@ __global__ void __launch_bounds__( FB ) kFillList( const uint64_t* __restrict__ 
 	const uint64_t c = (uint64_t)blockIdx.x * FB + threadIdx.x;
 	if( c >= nCells ) return;
 	if( region ) region[c] = rank1[firstCell[roots[c]]] - 1u;
-	if( xyz )
-	{
-		const uint64_t m = codes[c];
-		xyz[c * 3] = compact3( m );
-		xyz[c * 3 + 1] = compact3( m >> 1 );
-		xyz[c * 3 + 2] = compact3( m >> 2 );
-	}
+	if( xyz ) mortonDecode( codes[c], xyz[c * 3], xyz[c * 3 + 1], xyz[c * 3 + 2] );
 }
 
 __global__ void __launch_bounds__( FB ) kFillAttribs( uint2 attrib, uint64_t n, uint2* __restrict__ out )
@@ -287,18 +248,11 @@ int classify( const SurfaceSource& s, Classified* out, hipStream_t st )
 	hipLaunchKernelGGL( kFillUnite, grid, block, 0, st, out->lin.as<uint64_t>(), n, L, out->root.as<uint32_t>() );
 	hipLaunchKernelGGL( kFillFlatten, grid, block, 0, st, out->lin.as<uint64_t>(), n, L, out->root.as<uint32_t>(), cnt.as<unsigned long long>() );
 	MVRT_HIP( hipGetLastError() );
-	if( out->offs.alloc( nNodes * 8 ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( &out->nRegions, cnt.p, 8, hipMemcpyDeviceToHost, st ) ); // (behind kFillFlatten; the scan below waits)
 	hipcub::CountingInputIterator<uint32_t> counting( 0u );
 	hipcub::TransformInputIterator<uint64_t, EnclosedLength, hipcub::CountingInputIterator<uint32_t>> lengths( counting,
 																												EnclosedLength{ out->lin.as<uint64_t>(), out->root.as<uint32_t>(), n, L } );
-	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, lengths, out->offs.as<uint64_t>(), nNodes, st ); } ) ) return 1;
-	unsigned long long h[2] = { 0, 0 };
-	MVRT_HIP( hipMemcpyAsync( &h[0], out->offs.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipMemcpyAsync( &h[1], cnt.p, 8, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
-	out->nCells = h[0];
-	out->nRegions = h[1];
-	return 0;
+	return exclusiveOffsets<uint64_t>( lengths, nNodes, out->offs, &out->nCells, st );
 }
 int launchEmit( const SurfaceSource& s, const Classified& c, uint64_t* codes, uint32_t* roots, uint32_t* xyz, hipStream_t st )
 {
@@ -329,29 +283,22 @@ int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, 
 	}
 	if( c.nCells == 0 ) return 0;
 	const uint32_t nCells = (uint32_t)c.nCells;
-	DevBuf codes, roots, firstCell, rank1;
-	{
-		DevBuf codesA, rootsA;
-		if( codesA.alloc( c.nCells * 8 ) || rootsA.alloc( c.nCells * 4 ) || codes.alloc( c.nCells * 8 ) || roots.alloc( c.nCells * 4 ) ) return 1;
-		if( launchEmit( s, c, codesA.as<uint64_t>(), rootsA.as<uint32_t>(), nullptr, st ) ) return 1;
-		if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
-				return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, codesA.as<uint64_t>(), codes.as<uint64_t>(), rootsA.as<uint32_t>(), roots.as<uint32_t>(), c.nCells, 0,
-														   (int)( 3u * s.levels ), st );
-			} ) )
-			return 1;
-	}
+	DevBuf codesA, rootsA, codes, roots, firstCell, rank1;
+	if( codesA.alloc( c.nCells * 8 ) || rootsA.alloc( c.nCells * 4 ) ) return 1;
+	if( launchEmit( s, c, codesA.as<uint64_t>(), rootsA.as<uint32_t>(), nullptr, st ) ) return 1;
+	if( sortPairsInto( codesA, rootsA, c.nCells, (int)( 3u * s.levels ), codes, roots, st ) ) return 1;
 	c.lin.release();
 	c.offs.release();
 	c.root.release();
 	const uint64_t nNodes = (uint64_t)s.nVoxels + 1;
-	if( firstCell.alloc( nNodes * 4 ) || rank1.alloc( c.nCells * 4 ) ) return 1;
+	if( firstCell.alloc( nNodes * 4 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( firstCell.p, 0xFF, nNodes * 4, st ) );
 	const dim3 grid( divUp( nCells, FB ) ), block( FB );
 	hipLaunchKernelGGL( kFillFirstCells, grid, block, 0, st, roots.as<uint32_t>(), nCells, firstCell.as<uint32_t>() );
 	MVRT_HIP( hipGetLastError() );
 	hipcub::CountingInputIterator<uint32_t> counting( 0u );
 	hipcub::TransformInputIterator<uint32_t, RegionHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, RegionHead{ roots.as<uint32_t>(), firstCell.as<uint32_t>() } );
-	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, heads, rank1.as<uint32_t>(), c.nCells, st ); } ) ) return 1;
+	if( rankHeads( heads, c.nCells, rank1, nullptr, st ) ) return 1;
 	// (the caller's arrays are written by this launch alone, behind every allocation and check)
 	hipLaunchKernelGGL( kFillList, grid, block, 0, st, codes.as<uint64_t>(), roots.as<uint32_t>(), firstCell.as<uint32_t>(), rank1.as<uint32_t>(), nCells, xyzDev, regionDev );
 	MVRT_HIP( hipGetLastError() );

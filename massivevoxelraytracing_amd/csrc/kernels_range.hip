@@ -108,16 +108,6 @@ __global__ void __launch_bounds__( 256 ) kAoValidate( uint64_t nFaces, const uin
 	if( faceVoxel[i] >= nVoxels || faceDir[i] >= 6 ) atomicMin( lowestBad, (unsigned long long)i );
 }
 
-MVRT_DI uint32_t aoCompactBy3( uint64_t x )
-{
-	x &= 0x1249249249249249ull;
-	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
-	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
-	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
-	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
-	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
-	return (uint32_t)x;
-}
 // One wave per block.  K < 64: the wave bakes 64 / K consecutive faces, lane = face * K + sample; K >= 64: one face, K / 64 rounds of 64 samples.  The
 // entries were validated (kAoValidate) before this kernel is launched.
 __global__ void __launch_bounds__( RANGE_WAVE ) kSurfaceAo( mvrt_device_octree view, const uint64_t* __restrict__ morton, uint64_t nFaces, const uint32_t* __restrict__ faceVoxel,
@@ -139,7 +129,7 @@ __global__ void __launch_bounds__( RANGE_WAVE ) kSurfaceAo( mvrt_device_octree v
 	{
 		d = faceDir[face];
 		const uint64_t code = morton[faceVoxel[face]];
-		uint32_t c2[3] = { 2u * aoCompactBy3( code ) + 1u, 2u * aoCompactBy3( code >> 1 ) + 1u, 2u * aoCompactBy3( code >> 2 ) + 1u };
+		uint32_t c2[3] = { 2u * compactBy3( code ) + 1u, 2u * compactBy3( code >> 1 ) + 1u, 2u * compactBy3( code >> 2 ) + 1u };
 		// the face centre in half voxels: the in-plane axes at the voxel's middle, the normal axis on the face
 		const uint32_t axis = ( d < 2u ) ? 1u : ( ( d == 2u || d == 4u ) ? 2u : 0u );
 		const bool positive = d == 1u || d == 3u || d == 4u;

@@ -3,35 +3,23 @@
 //
 //   masks   one byte per voxel, bit d = the neighbour in direction d is empty.  Read from the sorted Morton codes of the build; a neighbour is looked up in the
 //           cell index (SvoDev::cellBlocks / cellEntries) where the octree has one, else by binary search in the codes.  Both give the same bytes.
-//   faces   exclusive scan of the popcounts (64-bit offsets, rocPRIM), then one workgroup per 256 voxels emits that group's faces: the faces of a group are
-//           one contiguous run of the output, every thread takes faces of the run and finds their voxel in the group's offsets (LDS), so a wave writes
-//           64 consecutive records.
-//   weld    corner keys, radix sort of (key, face * 4 + k), head flags, inclusive scan = rank + 1, scatter of the ranks and decode of the heads.
+//   faces   exclusive scan of the popcounts (64-bit offsets), then the run expansion of voxel_passes.h: one workgroup per 256 voxels emits that group's faces,
+//           one thread per face, so a wave writes 64 consecutive records.
+//   weld    corner keys, then the Weld record: radix sort of (key, face * 4 + k), head flags, inclusive scan = rank + 1; scatter of the ranks and decode of the heads.
+//
+// The codec, the searches and the host steps (exclusiveOffsets, sortPairsInto, rankHeads) are those of mvrt_common.h and voxel_passes.h; the four
+// corners of a quad are emitQuadCorners here, for the unit faces and for the merged rectangles.
 //
 // Directions, corners and windings are the reference's (voxMesh.cpp:172-200); positions are lower + (float)c * dps, one multiply and one add, each rounded
 // (this file is compiled without contraction like every other).
-#include <hipcub/hipcub.hpp>
-
 #include "launch.h"
+#include "voxel_passes.h"
 
 #define WAVE 64
 #define SB 256 // threads per workgroup, and voxels per workgroup of the emit kernel
 
 namespace
 {
-constexpr uint64_t kDimMask = 0x1249249249249249ull; // the bits of x in a Morton code; y = << 1, z = << 2
-
-MVRT_DI uint32_t compact3( uint64_t x )
-{
-	x &= kDimMask;
-	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
-	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
-	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
-	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
-	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
-	return (uint32_t)x;
-}
-
 // direction d (voxMesh.cpp:172-200): 0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X
 MVRT_DI uint32_t dirAxis( uint32_t d ) { return ( 0x020211u >> ( 4u * d ) ) & 3u; } // x = 0, y = 1, z = 2
 MVRT_DI uint32_t dirPositive( uint32_t d ) { return ( 0x1Au >> d ) & 1u; }			 // +Y, +X, +Z
@@ -45,14 +33,8 @@ MVRT_DI uint32_t cellMaskOf( const SurfaceSource& s, uint64_t cell )
 }
 MVRT_DI bool codePresent( const uint64_t* __restrict__ morton, uint32_t n, uint64_t code ) // binary search in the sorted unique codes
 {
-	uint32_t lo = 0, hi = n;
-	while( lo < hi )
-	{
-		const uint32_t mid = lo + ( ( hi - lo ) >> 1 );
-		if( morton[mid] < code ) lo = mid + 1;
-		else hi = mid;
-	}
-	return lo < n && morton[lo] == code;
+	const uint64_t i = lowerBound( morton, 0, n, code );
+	return i < n && morton[i] == code;
 }
 template <bool CELLS> MVRT_DI uint32_t exposureMask( const SurfaceSource& s, uint64_t c )
 {
@@ -64,7 +46,7 @@ template <bool CELLS> MVRT_DI uint32_t exposureMask( const SurfaceSource& s, uin
 	for( uint32_t d = 0; d < 6; d++ )
 	{
 		const uint32_t a = dirAxis( d ), pos = dirPositive( d );
-		const uint64_t M = kDimMask << a;
+		const uint64_t M = splitBy3( 0x1FFFFFu ) << a; // the bits of axis a in a Morton code
 		bool present;
 		if( CELLS && ( ( inCell >> a ) & 1u ) != pos ) // the neighbour shares this voxel's cell
 			present = ( own >> ( inCell ^ ( 1u << a ) ) ) & 1u;
@@ -112,13 +94,7 @@ template <bool CELLS> __global__ void __launch_bounds__( SB ) kSurfaceMasks( Sur
 
 struct PopcountOf // scan input: faces of voxel i
 {
-	__host__ __device__ uint64_t operator()( uint8_t m ) const
-	{
-		uint32_t v = m;
-		v = ( v & 0x55u ) + ( ( v >> 1 ) & 0x55u );
-		v = ( v & 0x33u ) + ( ( v >> 2 ) & 0x33u );
-		return ( v & 0x0Fu ) + ( v >> 4 );
-	}
+	__host__ __device__ uint64_t operator()( uint8_t m ) const { return popcount8( m ); }
 };
 
 // corner number -> offset (the reference's numbering): 0 (0,0,0) 1 (1,0,0) 2 (1,0,1) 3 (0,0,1) 4 (0,1,0) 5 (1,1,0) 6 (1,1,1) 7 (0,1,1)
@@ -133,8 +109,47 @@ MVRT_DI uint32_t faceCorner( uint32_t d, uint32_t k )
 	return (uint32_t)( ( d < 3u ? lo >> ( 12u * d ) : hi >> ( 12u * ( d - 3u ) ) ) >> ( 3u * k ) ) & 7u;
 }
 
-// One workgroup per SB voxels.  offs: n + 1 exclusive offsets (offs[n] = nFaces).  The group's faces are the run [offs[first], offs[end]) of every output;
-// thread t takes faces t, t + SB, ... of the run.  Any output may be null.  keys / vals: the weld's corner keys and face * 4 + k.
+// The four corners of quad f: direction d at voxel (x, y, z), a corner offset counting sx / sy / sz voxels on its axis (1, 1, 1: a unit face).  positions (12 floats
+// per quad) and keys / vals (the weld's corner keys and f * 4 + k) may each be null.
+template <bool V4>
+MVRT_DI void emitQuadCorners( uint32_t x, uint32_t y, uint32_t z, uint32_t d, uint32_t sx, uint32_t sy, uint32_t sz, f3 lower, float dps, uint32_t gridRes, uint64_t f,
+							  float* __restrict__ positions, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals )
+{
+	float p[12];
+#pragma unroll
+	for( uint32_t k = 0; k < 4; k++ )
+	{
+		const uint32_t cn = faceCorner( d, k );
+		const uint32_t cx = x + cornerX( cn ) * sx, cy = y + cornerY( cn ) * sy, cz = z + cornerZ( cn ) * sz;
+		p[k * 3] = lower.x + (float)cx * dps;
+		p[k * 3 + 1] = lower.y + (float)cy * dps;
+		p[k * 3 + 2] = lower.z + (float)cz * dps;
+		if( keys )
+		{
+			const uint64_t R1 = (uint64_t)gridRes + 1ull;
+			keys[f * 4 + k] = ( (uint64_t)cz * R1 + cy ) * R1 + cx;
+			vals[f * 4 + k] = (uint32_t)( f * 4 + k );
+		}
+	}
+	if( positions )
+	{
+		if( V4 )
+		{
+			float4* o = reinterpret_cast<float4*>( positions + f * 12 );
+			o[0] = make_float4( p[0], p[1], p[2], p[3] );
+			o[1] = make_float4( p[4], p[5], p[6], p[7] );
+			o[2] = make_float4( p[8], p[9], p[10], p[11] );
+		}
+		else
+		{
+#pragma unroll
+			for( int k = 0; k < 12; k++ ) positions[f * 12 + k] = p[k];
+		}
+	}
+}
+
+// One workgroup per SB voxels, the run expansion of voxel_passes.h: offs = n + 1 exclusive offsets (offs[n] = nFaces), the records are faces, a voxel's faces the set
+// bits of its mask.  Any output may be null.  keys / vals: the weld's corner keys and face * 4 + k.
 template <bool V4>
 __global__ void __launch_bounds__( SB ) kSurfaceEmit( const uint64_t* __restrict__ morton, const uint8_t* __restrict__ masks, const uint64_t* __restrict__ offs, uint32_t n, f3 lower,
 													  float dps, uint32_t gridRes, uint32_t* __restrict__ faceVoxel, uint8_t* __restrict__ faceDir, float* __restrict__ positions,
@@ -145,63 +160,22 @@ __global__ void __launch_bounds__( SB ) kSurfaceEmit( const uint64_t* __restrict
 	__shared__ uint64_t sCode[SB];
 	const uint64_t first = (uint64_t)blockIdx.x * SB;
 	const uint64_t v = first + threadIdx.x;
-	const uint64_t base = offs[first];
-	sOff[threadIdx.x] = (uint32_t)( offs[v < n ? v : n] - base ); // <= 6 * SB
-	if( threadIdx.x == 0 ) sOff[SB] = (uint32_t)( offs[first + SB < n ? first + SB : n] - base );
+	const uint64_t base = stageRunOffsets<SB>( offs, n, sOff ); // (relative offsets <= 6 * SB)
 	sMask[threadIdx.x] = v < n ? masks[v] : (uint8_t)0;
 	sCode[threadIdx.x] = v < n ? morton[v] : 0ull;
 	__syncthreads();
 	const uint32_t total = sOff[SB];
 	for( uint32_t j = threadIdx.x; j < total; j += SB )
 	{
-		// the last voxel of the group whose offset is <= j: voxels without faces repeat the offset of the next one and are passed over
-		uint32_t lo = 0, hi = SB;
-		while( hi - lo > 1 )
-		{
-			const uint32_t mid = ( lo + hi ) >> 1;
-			if( sOff[mid] <= j ) lo = mid;
-			else hi = mid;
-		}
-		uint32_t m = sMask[lo];
-		for( uint32_t r = j - sOff[lo]; r > 0; r-- ) m &= m - 1u; // the ( j - offset )-th set bit
-		const uint32_t d = (uint32_t)__ffs( (int)m ) - 1u;
+		const uint32_t lo = findRun( sOff, SB, j );
+		const uint32_t d = nthSetBit( sMask[lo], j - sOff[lo] );
 		const uint64_t f = base + j;
 		if( faceVoxel ) faceVoxel[f] = (uint32_t)( first + lo );
 		if( faceDir ) faceDir[f] = (uint8_t)d;
 		if( !positions && !keys ) continue;
-		const uint64_t c = sCode[lo];
-		const uint32_t x = compact3( c ), y = compact3( c >> 1 ), z = compact3( c >> 2 );
-		float p[12];
-#pragma unroll
-		for( uint32_t k = 0; k < 4; k++ )
-		{
-			const uint32_t cn = faceCorner( d, k );
-			const uint32_t cx = x + cornerX( cn ), cy = y + cornerY( cn ), cz = z + cornerZ( cn );
-			p[k * 3] = lower.x + (float)cx * dps;
-			p[k * 3 + 1] = lower.y + (float)cy * dps;
-			p[k * 3 + 2] = lower.z + (float)cz * dps;
-			if( keys )
-			{
-				const uint64_t R1 = (uint64_t)gridRes + 1ull;
-				keys[f * 4 + k] = ( (uint64_t)cz * R1 + cy ) * R1 + cx;
-				vals[f * 4 + k] = (uint32_t)( f * 4 + k );
-			}
-		}
-		if( positions )
-		{
-			if( V4 )
-			{
-				float4* o = reinterpret_cast<float4*>( positions + f * 12 );
-				o[0] = make_float4( p[0], p[1], p[2], p[3] );
-				o[1] = make_float4( p[4], p[5], p[6], p[7] );
-				o[2] = make_float4( p[8], p[9], p[10], p[11] );
-			}
-			else
-			{
-#pragma unroll
-				for( int k = 0; k < 12; k++ ) positions[f * 12 + k] = p[k];
-			}
-		}
+		uint32_t x, y, z;
+		mortonDecode( sCode[lo], x, y, z );
+		emitQuadCorners<V4>( x, y, z, d, 1u, 1u, 1u, lower, dps, gridRes, f, positions, keys, vals );
 	}
 }
 
@@ -273,32 +247,36 @@ int scratchMasksAndCount( const SurfaceSource& s, DevBuf& masks, uint64_t* nFace
 }
 int scanOffsets( const SurfaceSource& s, const DevBuf& masks, DevBuf& offs, hipStream_t st )
 {
-	const uint64_t items = (uint64_t)s.nVoxels + 1;
-	if( offs.alloc( items * 8 ) ) return 1;
 	hipcub::TransformInputIterator<uint64_t, PopcountOf, const uint8_t*> in( masks.as<uint8_t>(), PopcountOf() );
-	return withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, in, offs.as<uint64_t>(), items, st ); } );
+	return exclusiveOffsets<uint64_t>( in, (uint64_t)s.nVoxels + 1, offs, nullptr, st );
 }
-// the weld behind the corner keys: radix sort of (key, corner number) into keysB / valsB (keysA / valsA are released), head flags, inclusive scan = rank + 1
-// into rank1, and the number of distinct keys on the host when this returns
-int sortAndRankCorners( const SurfaceSource& s, DevBuf& keysA, DevBuf& valsA, uint32_t nCorners, DevBuf& keysB, DevBuf& valsB, DevBuf& rank1, uint32_t* nVertices, hipStream_t st )
+
+// The weld of a list of quads (unit faces or merged rectangles): the corners sorted by key with their numbers (quad * 4 + k), rank + 1 of every sorted corner among
+// the distinct keys, and the two counts.  Left empty where there is no corner.
+struct Weld
 {
-	if( keysB.alloc( (uint64_t)nCorners * 8 ) || valsB.alloc( (uint64_t)nCorners * 4 ) ) return 1;
+	DevBuf keys, vals, rank1;
+	uint32_t nCorners = 0, nVertices = 0;
+};
+// from the keys and numbers of nCorners >= 1 corners (keysA / valsA are released): radix sort, head flags, inclusive scan.  The counts are on the host when this returns
+int buildWeld( const SurfaceSource& s, DevBuf& keysA, DevBuf& valsA, uint32_t nCorners, Weld* w, hipStream_t st )
+{
 	int endBit = 3 * ( (int)s.levels + 1 ); // a key is below ( gridRes + 1 )^3 <= 2^( 3 * ( levels + 1 ) )
 	if( endBit > 64 ) endBit = 64;
-	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
-			return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint32_t>(), valsB.as<uint32_t>(), (uint64_t)nCorners, 0,
-													   endBit, st );
-		} ) )
-		return 1;
-	keysA.release();
-	valsA.release();
-	if( rank1.alloc( (uint64_t)nCorners * 4 ) ) return 1;
+	if( sortPairsInto( keysA, valsA, nCorners, endBit, w->keys, w->vals, st ) ) return 1;
 	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, HeadOf, hipcub::CountingInputIterator<uint32_t>> heads( counting, HeadOf{ keysB.as<uint64_t>() } );
-	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, heads, rank1.as<uint32_t>(), (uint64_t)nCorners, st ); } ) )
-		return 1;
-	MVRT_HIP( hipMemcpyAsync( nVertices, rank1.as<uint32_t>() + ( nCorners - 1 ), 4, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	hipcub::TransformInputIterator<uint32_t, HeadOf, hipcub::CountingInputIterator<uint32_t>> heads( counting, HeadOf{ w->keys.as<uint64_t>() } );
+	if( rankHeads( heads, nCorners, w->rank1, &w->nVertices, st ) ) return 1;
+	w->nCorners = nCorners;
+	return 0;
+}
+// indices[quad * 4 + k] and the vertices of a weld with corners; either may be null.  Not synchronised.
+int writeWeld( const SurfaceSource& s, const Weld& w, uint32_t* indicesDev, float* verticesDev, hipStream_t st )
+{
+	if( !indicesDev && !verticesDev ) return 0;
+	hipLaunchKernelGGL( kSurfaceWeld, dim3( divUp( w.nCorners, SB ) ), dim3( SB ), 0, st, w.keys.as<uint64_t>(), w.vals.as<uint32_t>(), w.rank1.as<uint32_t>(), w.nCorners, s.lower,
+						s.dps, 1u << s.levels, indicesDev, verticesDev );
+	MVRT_HIP( hipGetLastError() );
 	return 0;
 }
 } // namespace
@@ -345,16 +323,16 @@ int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexC
 		return 1;
 	}
 	const uint32_t nCorners = (uint32_t)( 4ull * nFaces );
-	uint32_t nVertices = 0;
-	DevBuf keysB, valsB, rank1;
+	Weld weld;
 	if( nCorners )
 	{
 		if( scanOffsets( s, masks, offs, st ) ) return 1;
 		DevBuf keysA, valsA;
 		if( keysA.alloc( (uint64_t)nCorners * 8 ) || valsA.alloc( (uint64_t)nCorners * 4 ) ) return 1;
 		if( launchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), nullptr, nullptr, nullptr, keysA.as<uint64_t>(), valsA.as<uint32_t>(), st ) ) return 1;
-		if( sortAndRankCorners( s, keysA, valsA, nCorners, keysB, valsB, rank1, &nVertices, st ) ) return 1;
+		if( buildWeld( s, keysA, valsA, nCorners, &weld, st ) ) return 1;
 	}
+	const uint32_t nVertices = weld.nVertices;
 	if( nVerticesOut ) *nVerticesOut = nVertices;
 	if( !faceVoxelDev && !faceDirDev && !indicesDev && !verticesDev ) return 0; // the sizing call
 	// (the capacities are looked at behind the sort: a refused call still returns BOTH counts, and the vertex count is the sort's result)
@@ -371,12 +349,7 @@ int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexC
 	}
 	if( nCorners == 0 ) return 0;
 	if( ( faceVoxelDev || faceDirDev ) && launchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), faceVoxelDev, faceDirDev, nullptr, nullptr, nullptr, st ) ) return 1;
-	if( indicesDev || verticesDev )
-	{
-		hipLaunchKernelGGL( kSurfaceWeld, dim3( divUp( nCorners, SB ) ), dim3( SB ), 0, st, keysB.as<uint64_t>(), valsB.as<uint32_t>(), rank1.as<uint32_t>(), nCorners, s.lower, s.dps,
-							1u << s.levels, indicesDev, verticesDev );
-		MVRT_HIP( hipGetLastError() );
-	}
+	if( writeWeld( s, weld, indicesDev, verticesDev, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }
@@ -420,7 +393,7 @@ __global__ void __launch_bounds__( SB ) kMergeFaceKeys( const uint64_t* __restri
 	const uint64_t i = (uint64_t)blockIdx.x * SB + threadIdx.x;
 	if( i >= n || !( ( masks[i] >> d ) & 1u ) ) return;
 	const uint64_t c = morton[i];
-	const uint32_t xyz[3] = { compact3( c ), compact3( c >> 1 ), compact3( c >> 2 ) };
+	const uint32_t xyz[3] = { compactBy3( c ), compactBy3( c >> 1 ), compactBy3( c >> 2 ) };
 	const uint32_t a = dirAxis( d );
 	const uint32_t o = offs[i];
 	keys[o] = ( (uint64_t)xyz[a] << ( 2u * levels ) ) | ( (uint64_t)xyz[axisV( a )] << levels ) | xyz[axisU( a )];
@@ -519,43 +492,13 @@ __global__ void __launch_bounds__( SB ) kMergeEmit( const MergeRect* __restrict_
 		rectSize[f * 2 + 1] = r.dv;
 	}
 	if( !positions && !keys ) return;
-	const uint64_t c = morton[r.voxel];
-	const uint32_t x = compact3( c ), y = compact3( c >> 1 ), z = compact3( c >> 2 );
+	uint32_t x, y, z;
+	mortonDecode( morton[r.voxel], x, y, z );
 	const uint32_t a = dirAxis( d );
 	uint32_t scale[3] = { 1u, 1u, 1u }; // a corner offset counts du on the u axis, dv on the v axis, 1 on the normal axis
 	scale[axisU( a )] = r.du;
 	scale[axisV( a )] = r.dv;
-	float p[12];
-#pragma unroll
-	for( uint32_t k = 0; k < 4; k++ )
-	{
-		const uint32_t cn = faceCorner( d, k );
-		const uint32_t cx = x + cornerX( cn ) * scale[0], cy = y + cornerY( cn ) * scale[1], cz = z + cornerZ( cn ) * scale[2];
-		p[k * 3] = lower.x + (float)cx * dps;
-		p[k * 3 + 1] = lower.y + (float)cy * dps;
-		p[k * 3 + 2] = lower.z + (float)cz * dps;
-		if( keys )
-		{
-			const uint64_t R1 = (uint64_t)gridRes + 1ull;
-			keys[f * 4 + k] = ( (uint64_t)cz * R1 + cy ) * R1 + cx;
-			vals[f * 4 + k] = (uint32_t)( f * 4 + k );
-		}
-	}
-	if( positions )
-	{
-		if( V4 )
-		{
-			float4* o = reinterpret_cast<float4*>( positions + f * 12 );
-			o[0] = make_float4( p[0], p[1], p[2], p[3] );
-			o[1] = make_float4( p[4], p[5], p[6], p[7] );
-			o[2] = make_float4( p[8], p[9], p[10], p[11] );
-		}
-		else
-		{
-#pragma unroll
-			for( int k = 0; k < 12; k++ ) positions[f * 12 + k] = p[k];
-		}
-	}
+	emitQuadCorners<V4>( x, y, z, d, scale[0], scale[1], scale[2], lower, dps, gridRes, f, positions, keys, vals );
 }
 
 #define MERGE_LAUNCH( kernel, items, ... )                                                                     \
@@ -569,26 +512,11 @@ __global__ void __launch_bounds__( SB ) kMergeEmit( const MergeRect* __restrict_
 int startsOfHeads( const DevBuf& flags, uint32_t n, DevBuf& starts, uint32_t* count, hipStream_t st )
 {
 	DevBuf rank1;
-	if( rank1.alloc( (uint64_t)n * 4 ) ) return 1;
 	hipcub::TransformInputIterator<uint32_t, FlagOf, const uint8_t*> in( flags.as<uint8_t>(), FlagOf() );
-	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, in, rank1.as<uint32_t>(), (uint64_t)n, st ); } ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( count, rank1.as<uint32_t>() + ( n - 1 ), 4, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( rankHeads( in, n, rank1, count, st ) ) return 1;
 	if( starts.alloc( ( (uint64_t)*count + 1 ) * 4 ) ) return 1;
 	MERGE_LAUNCH( kMergeStarts, n, flags.as<uint8_t>(), rank1.as<uint32_t>(), n, starts.as<uint32_t>() );
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (rank1 is released on return)
-	return 0;
-}
-int sortMergeKeys( DevBuf& keysA, DevBuf& valsA, uint32_t n, uint32_t levels, DevBuf& keysB, DevBuf& valsB, hipStream_t st ) // A is released
-{
-	if( keysB.alloc( (uint64_t)n * 8 ) || valsB.alloc( (uint64_t)n * 4 ) ) return 1;
-	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
-			return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint32_t>(), valsB.as<uint32_t>(), (uint64_t)n, 0,
-													   3 * (int)levels, st );
-		} ) )
-		return 1;
-	keysA.release();
-	valsA.release();
 	return 0;
 }
 
@@ -601,16 +529,12 @@ int mergeDirection( const SurfaceSource& s, const uint8_t* masks /* n + 1, the l
 	uint32_t nFaces = 0;
 	{
 		DevBuf offs, keysA, valsA;
-		const uint64_t items = (uint64_t)n + 1;
-		if( offs.alloc( items * 4 ) ) return 1;
 		hipcub::TransformInputIterator<uint32_t, BitOf, const uint8_t*> in( masks, BitOf{ d } );
-		if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) { return hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, in, offs.as<uint32_t>(), items, st ); } ) ) return 1;
-		MVRT_HIP( hipMemcpyAsync( &nFaces, offs.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st ) );
-		MVRT_HIP( hipStreamSynchronize( st ) );
+		if( exclusiveOffsets<uint32_t>( in, (uint64_t)n + 1, offs, &nFaces, st ) ) return 1;
 		if( nFaces == 0 ) return 0;
 		if( keysA.alloc( (uint64_t)nFaces * 8 ) || valsA.alloc( (uint64_t)nFaces * 4 ) ) return 1;
 		MERGE_LAUNCH( kMergeFaceKeys, n, s.morton, masks, offs.as<uint32_t>(), n, d, L, keysA.as<uint64_t>(), valsA.as<uint32_t>() );
-		if( sortMergeKeys( keysA, valsA, nFaces, L, faceKeys, faceVoxel, st ) ) return 1; // (waits: offs goes at scope end)
+		if( sortPairsInto( keysA, valsA, nFaces, 3 * (int)L, faceKeys, faceVoxel, st ) ) return 1; // (waits: offs goes at scope end)
 	}
 	DevBuf flags, runStart;
 	uint32_t nRuns = 0;
@@ -623,7 +547,7 @@ int mergeDirection( const SurfaceSource& s, const uint8_t* masks /* n + 1, the l
 		DevBuf keysA, valsA;
 		if( keysA.alloc( (uint64_t)nRuns * 8 ) || valsA.alloc( (uint64_t)nRuns * 4 ) ) return 1;
 		MERGE_LAUNCH( kMergeRunKeys, nRuns, faceKeys.as<uint64_t>(), runStart.as<uint32_t>(), nRuns, L, keysA.as<uint64_t>(), valsA.as<uint32_t>() );
-		if( sortMergeKeys( keysA, valsA, nRuns, L, runKeys, runOf, st ) ) return 1;
+		if( sortPairsInto( keysA, valsA, nRuns, 3 * (int)L, runKeys, runOf, st ) ) return 1;
 	}
 	faceKeys.release();
 	DevBuf rectStart;
@@ -659,7 +583,7 @@ int launchMergeEmit( const SurfaceSource& s, const DevBuf* rects, const uint32_t
 int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev,
 				   float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut, hipStream_t st )
 {
-	const bool weld = ( flags & 2u ) != 0; // MVRT_SURFACE_MERGE_WELD
+	const bool welded = ( flags & 2u ) != 0; // MVRT_SURFACE_MERGE_WELD
 	DevBuf rects[6];
 	uint32_t counts[6];
 	uint64_t nFaces = 0, nRects = 0;
@@ -676,9 +600,8 @@ int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity
 		}
 	}
 	if( nRectsOut ) *nRectsOut = nRects;
-	uint32_t nCorners = 0, nVertices = 0;
-	DevBuf keysB, valsB, rank1;
-	if( weld )
+	Weld weld;
+	if( welded )
 	{
 		if( 4ull * nRects >= ( 1ull << 32 ) )
 		{
@@ -687,16 +610,17 @@ int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity
 						  (unsigned long long)nRects );
 			return 1;
 		}
-		nCorners = (uint32_t)( 4ull * nRects );
+		const uint32_t nCorners = (uint32_t)( 4ull * nRects );
 		if( nCorners )
 		{
 			DevBuf keysA, valsA;
 			if( keysA.alloc( (uint64_t)nCorners * 8 ) || valsA.alloc( (uint64_t)nCorners * 4 ) ) return 1;
 			if( launchMergeEmit( s, rects, counts, nullptr, nullptr, nullptr, nullptr, keysA.as<uint64_t>(), valsA.as<uint32_t>(), st ) ) return 1;
-			if( sortAndRankCorners( s, keysA, valsA, nCorners, keysB, valsB, rank1, &nVertices, st ) ) return 1;
+			if( buildWeld( s, keysA, valsA, nCorners, &weld, st ) ) return 1;
 		}
-		if( nVerticesOut ) *nVerticesOut = nVertices;
+		if( nVerticesOut ) *nVerticesOut = weld.nVertices;
 	}
+	const uint32_t nVertices = weld.nVertices;
 	if( !rectVoxelDev && !rectDirDev && !rectSizeDev && !positionsDev && !indicesDev && !verticesDev ) return 0; // the sizing call
 	if( ( rectVoxelDev || rectDirDev || rectSizeDev || positionsDev || indicesDev ) && rectCapacity < nRects )
 	{
@@ -712,12 +636,7 @@ int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity
 	if( nRects == 0 ) return 0;
 	if( ( rectVoxelDev || rectDirDev || rectSizeDev || positionsDev ) && launchMergeEmit( s, rects, counts, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, nullptr, nullptr, st ) )
 		return 1;
-	if( indicesDev || verticesDev )
-	{
-		hipLaunchKernelGGL( kSurfaceWeld, dim3( divUp( nCorners, SB ) ), dim3( SB ), 0, st, keysB.as<uint64_t>(), valsB.as<uint32_t>(), rank1.as<uint32_t>(), nCorners, s.lower, s.dps,
-							1u << s.levels, indicesDev, verticesDev );
-		MVRT_HIP( hipGetLastError() );
-	}
+	if( writeWeld( s, weld, indicesDev, verticesDev, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }

@@ -5,32 +5,25 @@
 // word (embedded flavour: index | mask << 24 as the parent stores it; plain flavour: the index), the running nVoxelsPSum sum and the path prefix, three arrays.
 //
 //   count   children of entry i = popcount of its mask: the top byte of the word (embedded) or masks[node] (plain).  Not a kernel: the input iterator of
-//   scan    a 64-bit exclusive sum (rocPRIM) over n + 1 items, the last one 0, so that offs[n] is the size of the next frontier.  It goes to the host.
-//   emit    one workgroup per 256 parents, one thread per CHILD: the children of a group are one contiguous run of the next frontier, every thread takes
-//           entries of the run, finds its parent in the group's offsets (LDS, 8 steps) and its slot as the k-th set bit of the parent's mask, and reads
-//           children[c] and nVoxelsPSum[c] from the parent's 64-byte line.  Siblings are neighbouring lanes on one line; a wave writes 64 consecutive
-//           entries of each array.  The last level writes (code, vIndex) instead of a frontier entry.
-//   gather  code -> xyz (x = bit 0 of each 3-bit group, as kReadVoxels), attribs = attrs[vIndex] verbatim.
+//   scan    a 64-bit exclusive sum (exclusiveOffsets, voxel_passes.h) over n + 1 items, the last one 0, so that offs[n] is the size of the next frontier.  It
+//           goes to the host.
+//   emit    the run expansion of voxel_passes.h: one workgroup per 256 parents, one thread per CHILD, its slot the k-th set bit of the parent's
+//           mask; it reads children[c] and nVoxelsPSum[c] from the parent's 64-byte line.  Siblings are neighbouring lanes on one line; a wave writes 64
+//           consecutive entries of each array.  The last level writes (code, vIndex) instead of a frontier entry.
+//   gather  code -> xyz (x = bit 0 of each 3-bit group), attribs = attrs[vIndex] verbatim.  Also the read-back of a build's own list (mvrt_svo_read_voxels).
 //
 // Paths come out in ascending order: parents are in ascending prefix order and the children of one parent in ascending slot order.  A DAG is walked per PATH,
 // shared nodes once per path that reaches them, so the count is the number of voxels, not of nodes.  Reachable nodes of mask 0 have no children: their path ends.
 // What the walk relies on is the upload contract (mvrt.h rules 2-4, checked on the host before an upload is accepted) or the builder: child words below
 // numberOfNodes, voxels in the last level only, sums below numberOfVoxels.  A word that names no node is still read as a node of mask 0, and an index past the
 // attributes as zero attributes: nothing here reads out of bounds whatever the nodes hold.
-#include <hipcub/hipcub.hpp>
-
 #include "launch.h"
+#include "voxel_passes.h"
 
 #define WB 256 // threads per workgroup, and parents per workgroup of the emit kernel
 
 namespace
 {
-MVRT_HDI uint32_t popcount8( uint32_t v )
-{
-	v = ( v & 0x55u ) + ( ( v >> 1 ) & 0x55u );
-	v = ( v & 0x33u ) + ( ( v >> 2 ) & 0x33u );
-	return ( v & 0x0Fu ) + ( v >> 4 );
-}
 // own mask of the node a frontier word names.  masks == nullptr: embedded flavour, the word carries it
 MVRT_HDI uint32_t wordMask( uint32_t w, const uint8_t* __restrict__ masks, uint32_t nNodes )
 {
@@ -46,8 +39,8 @@ struct ChildCount // scan input: children of frontier entry i; item n is the 0 b
 	__host__ __device__ uint64_t operator()( uint64_t i ) const { return i < n ? popcount8( wordMask( word[i], masks, nNodes ) ) : 0ull; }
 };
 
-// One workgroup per WB parents.  offs: nParents + 1 exclusive offsets.  The group's children are the run [offs[first], offs[end]) of the output; thread t takes
-// entries t, t + WB, ... of the run (at most 8 * WB).  LAST: the children are voxels -> cPrefix = the Morton code, cSum = the vIndex, cWord is not written.
+// One workgroup per WB parents, the run expansion of voxel_passes.h: offs = nParents + 1 exclusive offsets, the records are children (at most 8 * WB a group), a
+// parent's children the set bits of its mask.  LAST: the children are voxels -> cPrefix = the Morton code, cSum = the vIndex, cWord is not written.
 template <bool EMB, bool LAST>
 __global__ void __launch_bounds__( WB ) kWalkEmit( const Node64* __restrict__ nodes, const uint8_t* __restrict__ masks, const uint32_t* __restrict__ psumCold, uint32_t nNodes,
 												   const uint32_t* __restrict__ pWord, const uint32_t* __restrict__ pSum, const uint64_t* __restrict__ pPrefix,
@@ -59,12 +52,9 @@ __global__ void __launch_bounds__( WB ) kWalkEmit( const Node64* __restrict__ no
 	__shared__ uint32_t sSum[WB];
 	__shared__ uint64_t sPrefix[WB];
 	__shared__ uint8_t sMask[WB];
-	const uint64_t first = (uint64_t)blockIdx.x * WB;
-	const uint64_t p = first + threadIdx.x;
+	const uint64_t p = (uint64_t)blockIdx.x * WB + threadIdx.x;
 	const bool in = p < nParents;
-	const uint64_t base = offs[first];
-	sOff[threadIdx.x] = (uint32_t)( offs[in ? p : nParents] - base ); // <= 8 * WB
-	if( threadIdx.x == 0 ) sOff[WB] = (uint32_t)( offs[first + WB < nParents ? first + WB : nParents] - base );
+	const uint64_t base = stageRunOffsets<WB>( offs, nParents, sOff );
 	const uint32_t w = in ? pWord[p] : 0u;
 	sWord[threadIdx.x] = w;
 	sMask[threadIdx.x] = in ? (uint8_t)wordMask( w, EMB ? nullptr : masks, nNodes ) : (uint8_t)0;
@@ -74,17 +64,8 @@ __global__ void __launch_bounds__( WB ) kWalkEmit( const Node64* __restrict__ no
 	const uint32_t total = sOff[WB];
 	for( uint32_t j = threadIdx.x; j < total; j += WB )
 	{
-		// the last parent of the group whose offset is <= j: parents without children repeat the offset of the next one and are passed over
-		uint32_t lo = 0, hi = WB;
-		while( hi - lo > 1 )
-		{
-			const uint32_t mid = ( lo + hi ) >> 1;
-			if( sOff[mid] <= j ) lo = mid;
-			else hi = mid;
-		}
-		uint32_t m = sMask[lo];
-		for( uint32_t r = j - sOff[lo]; r > 0; r-- ) m &= m - 1u; // the ( j - offset )-th set bit
-		const uint32_t c = (uint32_t)__ffs( (int)m ) - 1u;
+		const uint32_t lo = findRun( sOff, WB, j );
+		const uint32_t c = nthSetBit( sMask[lo], j - sOff[lo] );
 		const uint32_t node = EMB ? sWord[lo] & 0xFFFFFFu : sWord[lo]; // (a parent with children has a mask, so it is below nNodes: wordMask)
 		const Node64& line = nodes[node];
 		const uint32_t ps = EMB ? line.psum[c] : psumCold[(uint64_t)node * 8u + c];
@@ -95,30 +76,15 @@ __global__ void __launch_bounds__( WB ) kWalkEmit( const Node64* __restrict__ no
 	}
 }
 
-MVRT_DI uint32_t compact3( uint64_t x )
-{
-	x &= 0x1249249249249249ull;
-	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
-	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
-	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
-	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
-	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
-	return (uint32_t)x;
-}
-// vIndex == nullptr: the codes are the sorted list of a build and entry i is voxel i.  Any output may be null.
+// The read-back of voxels, walked (launchWalkGather) or kept by a build (svoReadVoxels).  vIndex == nullptr: the codes are the sorted list of a build and entry i
+// is voxel i.  Any output may be null.
 __global__ void __launch_bounds__( WB ) kWalkGather( const uint64_t* __restrict__ codes, const uint32_t* __restrict__ vIndex, const uint2* __restrict__ attrs, uint32_t nVoxels,
 													 uint64_t n, uint32_t* __restrict__ xyz, uint32_t* __restrict__ vIndexOut, uint32_t* __restrict__ attribs )
 {
 	for( uint64_t i = (uint64_t)blockIdx.x * WB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * WB )
 	{
 		const uint32_t v = vIndex ? vIndex[i] : (uint32_t)i;
-		if( xyz )
-		{
-			const uint64_t m = codes[i];
-			xyz[i * 3] = compact3( m );
-			xyz[i * 3 + 1] = compact3( m >> 1 );
-			xyz[i * 3 + 2] = compact3( m >> 2 );
-		}
+		if( xyz ) mortonDecode( codes[i], xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2] );
 		if( vIndexOut ) vIndexOut[i] = v;
 		if( attribs )
 		{
@@ -152,6 +118,15 @@ int launchWalkGather( const uint64_t* codes, const uint32_t* vIndex, const uint2
 	MVRT_HIP( hipGetLastError() );
 	return 0;
 }
+// mvrt_svo_read_voxels: the sorted list of a build, entry i = voxel i, on the builder's grid of 1 to 4096 groups.  Waits for the stream.
+int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t st )
+{
+	const uint64_t blocks = ( (uint64_t)n + WB - 1 ) / WB;
+	hipLaunchKernelGGL( kWalkGather, dim3( (uint32_t)( blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks ) ), dim3( WB ), 0, st, morton, nullptr, attrs, n, n, xyz, nullptr, attribs );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	MVRT_HIP( hipGetLastError() );
+	return 0;
+}
 
 // One host synchronisation that waits per level (the size of the next frontier), one more behind the last emit.  Every buffer is a DevBuf of this call: a failed
 // allocation returns an error and leaks nothing.  The buffers alternate between two sets, so what a level allocates over was last read two levels earlier, by
@@ -180,20 +155,11 @@ int walkPaths( const WalkSource& s, bool fill, uint64_t fillLimit, WalkResult* o
 		Frontier& kid = fr[( d + 1u ) & 1u];
 		DevBuf& off = offs[d & 1u];
 		const bool last = d + 1u == s.levels;
-		if( off.alloc( ( n + 1 ) * 8 ) ) return 1;
-		unsigned long long total = 0;
-		{
-			hipcub::CountingInputIterator<uint64_t> counting( 0ull );
-			hipcub::TransformInputIterator<uint64_t, ChildCount, hipcub::CountingInputIterator<uint64_t>> in(
-				counting, ChildCount{ par.word.as<uint32_t>(), s.embedded ? nullptr : s.masks, s.nNodes, n } );
-			size_t tmpBytes = 0;
-			MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( nullptr, tmpBytes, in, off.as<uint64_t>(), n + 1, st ) );
-			DevBuf tmp;
-			if( tmp.alloc( tmpBytes ) ) return 1;
-			MVRT_HIP( hipcub::DeviceScan::ExclusiveSum( tmp.p, tmpBytes, in, off.as<uint64_t>(), n + 1, st ) );
-			MVRT_HIP( hipMemcpyAsync( &total, off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st ) );
-			MVRT_HIP( hipStreamSynchronize( st ) ); // (tmp is released at scope end)
-		}
+		uint64_t total = 0;
+		hipcub::CountingInputIterator<uint64_t> counting( 0ull );
+		hipcub::TransformInputIterator<uint64_t, ChildCount, hipcub::CountingInputIterator<uint64_t>> in(
+			counting, ChildCount{ par.word.as<uint32_t>(), s.embedded ? nullptr : s.masks, s.nNodes, n } );
+		if( exclusiveOffsets<uint64_t>( in, n + 1, off, &total, st ) ) return 1;
 		if( last ) out->n = total;
 		if( total == 0 ) return 0; // every path ended in a node of mask 0 (the empty octree: the root)
 		if( last && ( !fill || total > fillLimit ) ) return 0;

@@ -155,7 +155,6 @@ int svoBuildFromVoxels( const uint32_t* xyz, const uint32_t* attribs, uint64_t n
 // new octree (the old arrays are untouched); 0: the attributes were changed in place (node structure unchanged), *hasEmissionOut = the new flag
 int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, int gridRes, int flags,
 				   hipStream_t stream, SvoBuildResult* out, int* structural, uint32_t* hasEmissionOut );
-int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t stream );
 // the levels over n sorted unique codes and their attributes (both handed to *out on success), as svoBuildFromVoxels builds them behind its sort: the attribute
 // bytes are kept verbatim and out->hasEmission is 0 -- the caller knows the flag of the set it hands in (mvrt_svo_rebuild)
 int svoBuildFromSorted( DevBuf& morton, DevBuf& attrs, uint32_t n, int gridRes, int flags, hipStream_t stream, SvoBuildResult* out );
@@ -209,6 +208,8 @@ int walkPaths( const WalkSource& s, bool fill, uint64_t fillLimit, WalkResult* o
 // per entry i < n: xyz = the decoded code, vIndexOut = v, attribs = attrs[v] with v = vIndex[i] (vIndex == nullptr: v = i); any output may be null.  Not synchronised.
 int launchWalkGather( const uint64_t* codes, const uint32_t* vIndex, const uint2* attrs, uint32_t nVoxels, uint64_t n, uint32_t* xyz, uint32_t* vIndexOut, uint32_t* attribs,
 					  hipStream_t stream );
+// mvrt_svo_read_voxels: the same kernel on the sorted list of a build (entry i = voxel i).  Waits for the stream.
+int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t stream );
 
 // distance-limited rays and the ambient occlusion bake (kernels_range.hip; mvrt_trace_batch_range / mvrt_ao_directions / mvrt_svo_surface_ao): the per-lane walk of
 // include/mvrt/device.hpp on the view mvrt_svo_device_view fills.  launchTraceRange is asynchronous; surfaceAo validates the entries on the device, blocks, keeps

@@ -71,6 +71,41 @@ MVRT_HDI uint64_t splitBy3( uint32_t a )
 	return x;
 }
 MVRT_HDI uint64_t mortonEncode( uint32_t x, uint32_t y, uint32_t z ) { return splitBy3( x ) | splitBy3( y ) << 1 | splitBy3( z ) << 2; }
+MVRT_HDI uint32_t compactBy3( uint64_t x ) // every third bit from bit 0 on, packed: the inverse of splitBy3
+{
+	x &= 0x1249249249249249ull;
+	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
+	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
+	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
+	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
+	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
+	return (uint32_t)x;
+}
+MVRT_HDI void mortonDecode( uint64_t code, uint32_t& x, uint32_t& y, uint32_t& z )
+{
+	x = compactBy3( code );
+	y = compactBy3( code >> 1 );
+	z = compactBy3( code >> 2 );
+}
+
+// ---- searches and counts of the passes over sorted voxel codes ---------------------------------------
+// the first index in [lo, hi) of the ascending array a whose entry is not below key; hi where there is none
+MVRT_HDI uint64_t lowerBound( const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key )
+{
+	while( lo < hi )
+	{
+		const uint64_t mid = ( lo + hi ) >> 1;
+		if( a[mid] < key ) lo = mid + 1;
+		else hi = mid;
+	}
+	return lo;
+}
+MVRT_HDI uint32_t popcount8( uint32_t v ) // of the low byte; the bits above it are 0
+{
+	v = ( v & 0x55u ) + ( ( v >> 1 ) & 0x55u );
+	v = ( v & 0x33u ) + ( ( v >> 2 ) & 0x33u );
+	return ( v & 0x0Fu ) + ( v >> 4 );
+}
 
 // ---- Owen-scrambled PMJ02 lookup (pmjSampler.hpp:62-102,158-173) -----------------------------------
 #define MVRT_PMJ_LENGTH 4096

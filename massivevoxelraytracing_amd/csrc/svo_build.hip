@@ -804,7 +804,7 @@ __global__ void __launch_bounds__( BB ) kSyntheticVoxels( uint64_t n, uint64_t s
 	}
 }
 
-// ---- voxel lists: build from xyz, batched edits, read-back (mvrt_svo_build_voxels / _edit_voxels / _read_voxels) ----------------------------------
+// ---- voxel lists: build from xyz, batched edits (mvrt_svo_build_voxels / _edit_voxels; the read-back of _read_voxels is kWalkGather, kernels_walk.hip) ----------------
 // encode + validate: xyz (3 x u32) + VoxelAttirb (NULL = white, no emission) -> (Morton, attribute with both alphas 255).  ENC_PER entries per thread: 48 bytes of
 // coordinates = three 16-byte loads (vec: the caller's arrays are 16-byte aligned).  firstBad[0] / [1]: lowest entry outside the grid / with an op byte other than
 // MVRT_VOXEL_REMOVE (0) or MVRT_VOXEL_SET (1), one atomicMin per wave.  idxOut (edits): the batch index, the value of the stable sort that follows.
@@ -899,16 +899,6 @@ __global__ void __launch_bounds__( BB ) kEncodeVoxels( const uint32_t* __restric
 	}
 }
 
-MVRT_DI uint64_t lowerBound( const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t key )
-{
-	while( lo < hi )
-	{
-		const uint64_t mid = ( lo + hi ) >> 1;
-		if( a[mid] < key ) lo = mid + 1;
-		else hi = mid;
-	}
-	return lo;
-}
 MVRT_DI uint2 asAttr( uint64_t v ) { return make_uint2( (uint32_t)v, (uint32_t)( v >> 32 ) ); }
 
 enum EditKind : uint8_t
@@ -1067,38 +1057,6 @@ __global__ void __launch_bounds__( BB ) kAnyEmission( const uint2* __restrict__ 
 		if( __ballot( em ) && ( threadIdx.x & ( WAVE - 1 ) ) == 0 ) atomicOr( hasEmission, 1u );
 	}
 }
-// read-back: Morton decode -> xyz, attributes copied
-MVRT_HDI uint32_t compactBy3( uint64_t x )
-{
-	x &= 0x1249249249249249ull;
-	x = ( x ^ ( x >> 2 ) ) & 0x10c30c30c30c30c3ull;
-	x = ( x ^ ( x >> 4 ) ) & 0x100f00f00f00f00full;
-	x = ( x ^ ( x >> 8 ) ) & 0x1f0000ff0000ffull;
-	x = ( x ^ ( x >> 16 ) ) & 0x1f00000000ffffull;
-	x = ( x ^ ( x >> 32 ) ) & 0x1fffffull;
-	return (uint32_t)x;
-}
-__global__ void __launch_bounds__( BB ) kReadVoxels( const uint64_t* __restrict__ morton, const uint2* __restrict__ attrs, uint32_t n, uint32_t* __restrict__ xyz,
-													  uint32_t* __restrict__ attribs )
-{
-	for( uint64_t i = (uint64_t)blockIdx.x * BB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BB )
-	{
-		const uint64_t m = morton[i];
-		if( xyz )
-		{
-			xyz[i * 3] = compactBy3( m );
-			xyz[i * 3 + 1] = compactBy3( m >> 1 );
-			xyz[i * 3 + 2] = compactBy3( m >> 2 );
-		}
-		if( attribs )
-		{
-			const uint2 a = attrs[i];
-			attribs[i * 2] = a.x;
-			attribs[i * 2 + 1] = a.y;
-		}
-	}
-}
-
 struct MaxOp
 {
 	__host__ __device__ uint32_t operator()( uint32_t a, uint32_t b ) const { return a > b ? a : b; }
@@ -1585,12 +1543,4 @@ int svoEditVoxels( const uint64_t* oldMorton, uint2* oldAttrs, uint32_t nOld, co
 	ePre.release();
 	*structural = 1;
 	return buildLevels( morton, attrs, nNew, 0, gridRes, flags, st, sc, out );
-}
-
-int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t* xyz, uint32_t* attribs, hipStream_t st )
-{
-	hipLaunchKernelGGL( kReadVoxels, dim3( gridFor( n ) ), dim3( BB ), 0, st, morton, attrs, n, xyz, attribs );
-	MVRT_HIP( hipStreamSynchronize( st ) );
-	MVRT_HIP( hipGetLastError() );
-	return 0;
 }

@@ -1,0 +1,80 @@
+// voxel_passes.h -- the steps that the passes over a sorted voxel set share (kernels_surface.hip, kernels_fill.hip, kernels_walk.hip).
+//
+//   run expansion   item i of a list yields len[i] >= 0 records; offs = the n + 1 exclusive offsets of the lengths (offs[n] = the number of records).  One workgroup
+//                   per B items: its records are the contiguous run [offs[first], offs[end]) of every output.  stageRunOffsets puts the group's B + 1 offsets,
+//                   relative to offs[first], into LDS; thread t then takes records t, t + B, ... of the run, findRun gives the item of a record and
+//                   j - sOff[item] its number within the item, so a wave writes 64 consecutive records.  Where an item's records are the set bits of a mask,
+//                   nthSetBit picks the bit.
+//   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
+//                   entries -> rank + 1 of every entry and the number of runs).  Each allocates its output itself, runs hipcub through withCubTemp and has waited
+//                   for the stream when it returns.
+#pragma once
+#include <hipcub/hipcub.hpp>
+
+#include "devbuf.h"
+
+// ---- run expansion ----------------------------------------------------------------------------------------------------------------------------------------
+// Called by all B threads of the group, before the __syncthreads() that also covers what the kernel stages for itself.  sOff[t] = offs[first + t] - offs[first]
+// for t = 0 .. B; the last group reads offs[n] for every item past the end, so its tail repeats the total.  Returns offs[first], the group's place in the output.
+template <uint32_t B> MVRT_DI uint64_t stageRunOffsets( const uint64_t* __restrict__ offs, uint64_t n, uint32_t* sOff )
+{
+	const uint64_t first = (uint64_t)blockIdx.x * B;
+	const uint64_t v = first + threadIdx.x;
+	const uint64_t base = offs[first];
+	sOff[threadIdx.x] = (uint32_t)( offs[v < n ? v : n] - base );
+	if( threadIdx.x == 0 ) sOff[B] = (uint32_t)( offs[first + B < n ? first + B : n] - base );
+	return base;
+}
+// the last i < count with sOff[i] <= j, for sOff ascending from sOff[0] = 0: an item of length 0 repeats the offset of the next one and is passed over
+MVRT_HDI uint32_t findRun( const uint32_t* sOff, uint32_t count, uint32_t j )
+{
+	uint32_t lo = 0, hi = count;
+	while( hi - lo > 1 )
+	{
+		const uint32_t mid = ( lo + hi ) >> 1;
+		if( sOff[mid] <= j ) lo = mid;
+		else hi = mid;
+	}
+	return lo;
+}
+// the position of the r-th set bit of mask, r counted from 0 at the lowest (~0 where the mask has r bits or fewer)
+MVRT_HDI uint32_t nthSetBit( uint32_t mask, uint32_t r )
+{
+	for( ; r > 0; r-- ) mask &= mask - 1u;
+	return mask == 0u ? ~0u : (uint32_t)__builtin_ctz( mask );
+}
+
+// ---- host steps -------------------------------------------------------------------------------------------------------------------------------------------
+// offs (allocated here) = the exclusive sums of `items` values of `in`, as T.  lastOnHost: where offs[items - 1] goes, valid when this returns (null = not wanted)
+template <class T, class In> int exclusiveOffsets( In in, uint64_t items, DevBuf& offs, T* lastOnHost, hipStream_t st )
+{
+	if( offs.alloc( items * sizeof( T ) ) ) return 1;
+	return withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+		const hipError_t e = hipcub::DeviceScan::ExclusiveSum( tmp, tmpBytes, in, offs.as<T>(), items, st );
+		if( e != hipSuccess || !tmp || !lastOnHost ) return e;
+		return hipMemcpyAsync( lastOnHost, offs.as<T>() + ( items - 1 ), sizeof( T ), hipMemcpyDeviceToHost, st ); // (withCubTemp waits)
+	} );
+}
+// n (key, value) pairs sorted by bits [0, endBit) of the key from A into B (allocated here); A is released
+inline int sortPairsInto( DevBuf& keysA, DevBuf& valsA, uint64_t n, int endBit, DevBuf& keysB, DevBuf& valsB, hipStream_t st )
+{
+	if( keysB.alloc( n * 8 ) || valsB.alloc( n * 4 ) ) return 1;
+	if( withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+			return hipcub::DeviceRadixSort::SortPairs( tmp, tmpBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), valsA.as<uint32_t>(), valsB.as<uint32_t>(), n, 0, endBit, st );
+		} ) )
+		return 1;
+	keysA.release();
+	valsA.release();
+	return 0;
+}
+// rank1 (allocated here) = the inclusive sums of n >= 1 head flags: rank1[i] - 1 is the number of the run entry i lies in.  count: where the number of heads
+// goes, valid when this returns (null = not wanted)
+template <class In> int rankHeads( In heads, uint64_t n, DevBuf& rank1, uint32_t* count, hipStream_t st )
+{
+	if( rank1.alloc( n * 4 ) ) return 1;
+	return withCubTemp( st, [&]( void* tmp, size_t& tmpBytes ) {
+		const hipError_t e = hipcub::DeviceScan::InclusiveSum( tmp, tmpBytes, heads, rank1.as<uint32_t>(), n, st );
+		if( e != hipSuccess || !tmp || !count ) return e;
+		return hipMemcpyAsync( count, rank1.as<uint32_t>() + ( n - 1 ), 4, hipMemcpyDeviceToHost, st ); // (withCubTemp waits)
+	} );
+}

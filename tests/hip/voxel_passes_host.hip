@@ -1,0 +1,203 @@
+// voxel_passes_host.hip -- the host-callable helpers of csrc/mvrt_common.h (Morton codec, lowerBound, popcount8) and csrc/voxel_passes.h (findRun, nthSetBit)
+// against brute force.  A program of its own: it makes no HIP call and needs no GPU.  Exit status 0 = every check held; each failure prints one line.
+#include <stdio.h>
+
+#include <vector>
+
+#include "../../massivevoxelraytracing_amd/csrc/voxel_passes.h"
+
+static int g_failures = 0;
+#define CHECK( cond, ... )                     \
+	do                                         \
+	{                                          \
+		if( !( cond ) )                        \
+		{                                      \
+			if( g_failures++ < 20 )            \
+			{                                  \
+				printf( "FAILED %s: ", #cond ); \
+				printf( __VA_ARGS__ );         \
+				printf( "\n" );                \
+			}                                  \
+		}                                      \
+	} while( 0 )
+
+static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
+static uint64_t rnd() // xorshift64
+{
+	g_rng ^= g_rng << 13;
+	g_rng ^= g_rng >> 7;
+	g_rng ^= g_rng << 17;
+	return g_rng;
+}
+
+// ---- codec ------------------------------------------------------------------------------------------------------------------------------------------------
+static uint64_t splitSlow( uint32_t a )
+{
+	uint64_t r = 0;
+	for( int b = 0; b < 21; b++ ) r |= (uint64_t)( ( a >> b ) & 1u ) << ( 3 * b );
+	return r;
+}
+static void roundTrip( uint32_t a )
+{
+	CHECK( splitBy3( a ) == splitSlow( a ), "a = 0x%x", a );
+	CHECK( compactBy3( splitBy3( a ) ) == a, "a = 0x%x", a );
+}
+static void decodeIs( uint64_t code, uint32_t ex, uint32_t ey, uint32_t ez )
+{
+	uint32_t x = ~0u, y = ~0u, z = ~0u;
+	mortonDecode( code, x, y, z );
+	CHECK( x == ex && y == ey && z == ez, "code 0x%llx -> (0x%x, 0x%x, 0x%x), expected (0x%x, 0x%x, 0x%x)", (unsigned long long)code, x, y, z, ex, ey, ez );
+}
+static void testCodec()
+{
+	const uint32_t full = 0x1FFFFFu;
+	roundTrip( 0u );
+	roundTrip( 1u );
+	for( int b = 0; b < 21; b++ ) roundTrip( 1u << b );
+	roundTrip( full );
+	for( int i = 0; i < 4096; i++ ) roundTrip( (uint32_t)rnd() & full );
+	// every field full: the all-ones 63-bit code
+	CHECK( mortonEncode( full, full, full ) == 0x7FFFFFFFFFFFFFFFull, "encode of three full fields" );
+	decodeIs( 0x7FFFFFFFFFFFFFFFull, full, full, full );
+	// one field full, the others 0: nothing of a neighbour's bits comes through
+	decodeIs( mortonEncode( full, 0u, 0u ), full, 0u, 0u );
+	decodeIs( mortonEncode( 0u, full, 0u ), 0u, full, 0u );
+	decodeIs( mortonEncode( 0u, 0u, full ), 0u, 0u, full );
+	// and one field 0, the others full
+	decodeIs( mortonEncode( 0u, full, full ), 0u, full, full );
+	decodeIs( mortonEncode( full, 0u, full ), full, 0u, full );
+	decodeIs( mortonEncode( full, full, 0u ), full, full, 0u );
+	for( int i = 0; i < 4096; i++ )
+	{
+		const uint32_t x = (uint32_t)rnd() & full, y = (uint32_t)rnd() & full, z = (uint32_t)rnd() & full;
+		decodeIs( mortonEncode( x, y, z ), x, y, z );
+	}
+}
+
+// ---- findRun ----------------------------------------------------------------------------------------------------------------------------------------------
+#define RB 256 // items per group, as in the emit kernels
+// off[0 .. RB] from the lengths of `items` <= RB items; the entries past the last item repeat the total, as stageRunOffsets leaves them in the last group
+static std::vector<uint32_t> offsetsOf( const std::vector<uint32_t>& len )
+{
+	std::vector<uint32_t> off( RB + 1 );
+	uint32_t sum = 0;
+	for( uint32_t i = 0; i <= RB; i++ )
+	{
+		off[i] = sum;
+		if( i < len.size() ) sum += len[i];
+	}
+	return off;
+}
+static void checkRun( const char* name, const std::vector<uint32_t>& off, uint32_t j )
+{
+	uint32_t want = 0;
+	for( uint32_t i = 0; i < RB; i++ )
+		if( off[i] <= j ) want = i; // linear scan: the last one
+	const uint32_t got = findRun( off.data(), RB, j );
+	CHECK( got == want, "%s: j = %u -> item %u, linear scan says %u", name, j, got, want );
+	CHECK( got < RB && off[got] <= j && j < off[got + 1], "%s: j = %u is not a record of item %u", name, j, got );
+}
+static void checkAllRuns( const char* name, const std::vector<uint32_t>& len )
+{
+	const std::vector<uint32_t> off = offsetsOf( len );
+	for( uint32_t j = 0; j < off[RB]; j++ ) checkRun( name, off, j );
+}
+static void testFindRun()
+{
+	for( uint32_t at : { 0u, 128u, 255u } ) // every length 0 but one: first, middle, last
+	{
+		std::vector<uint32_t> len( RB, 0u );
+		len[at] = 5u;
+		checkAllRuns( "one item with records", len );
+	}
+	{
+		std::vector<uint32_t> len( RB, 0u ); // lengths 0 at both ends, 0 .. 6 in between
+		for( uint32_t i = 10; i < RB - 10; i++ ) len[i] = (uint32_t)( rnd() % 7u );
+		len[10] = 3u;
+		len[RB - 11] = 1u;
+		checkAllRuns( "zeros at both ends", len );
+	}
+	{
+		std::vector<uint32_t> len( RB, 6u ); // 1536 records: longer than the group has threads
+		CHECK( offsetsOf( len )[RB] == 1536u, "total of 256 x 6" );
+		checkAllRuns( "all 6", len );
+	}
+	for( uint32_t at : { 0u, 100u, 255u } ) // one item of 2^21 - 2 records (the longest gap of a row) among zeros
+	{
+		std::vector<uint32_t> len( RB, 0u );
+		len[at] = ( 1u << 21 ) - 2u;
+		const std::vector<uint32_t> off = offsetsOf( len );
+		const uint32_t total = off[RB];
+		for( uint32_t j = 0; j < 300u; j++ ) checkRun( "one long item, low end", off, j );
+		for( uint32_t j = total - 300u; j < total; j++ ) checkRun( "one long item, high end", off, j );
+		for( int i = 0; i < 2000; i++ ) checkRun( "one long item, random", off, (uint32_t)( rnd() % total ) );
+	}
+	for( uint32_t items : { 1u, 77u, 255u } ) // the last group: fewer than 256 items, the tail repeats the total
+	{
+		std::vector<uint32_t> len( items );
+		for( uint32_t i = 0; i < items; i++ ) len[i] = (uint32_t)( rnd() % 9u );
+		len[items - 1] = 2u;
+		const std::vector<uint32_t> off = offsetsOf( len );
+		CHECK( off[items] == off[RB] && off[RB] > 0u, "the tail repeats the total" );
+		checkAllRuns( "short last group", len );
+	}
+	{
+		std::vector<uint32_t> len( 77u, 0u ); // the same with the last items empty: the tail of zeros and the repeated total meet
+		len[3] = 4u;
+		len[40] = 8u;
+		checkAllRuns( "short last group ending in zeros", len );
+	}
+}
+
+// ---- nthSetBit, popcount8 ---------------------------------------------------------------------------------------------------------------------------------
+static void testBits()
+{
+	for( uint32_t mask = 0; mask < 256u; mask++ )
+	{
+		uint32_t r = 0;
+		for( uint32_t b = 0; b < 8u; b++ )
+			if( ( mask >> b ) & 1u )
+			{
+				CHECK( nthSetBit( mask, r ) == b, "mask 0x%02x, r = %u -> %u, expected %u", mask, r, nthSetBit( mask, r ), b );
+				r++;
+			}
+		CHECK( popcount8( mask ) == r, "mask 0x%02x: popcount8 %u, expected %u", mask, popcount8( mask ), r );
+	}
+}
+
+// ---- lowerBound -------------------------------------------------------------------------------------------------------------------------------------------
+static void checkBound( const std::vector<uint64_t>& a, uint64_t lo, uint64_t hi, uint64_t key )
+{
+	uint64_t want = lo;
+	while( want < hi && a[want] < key ) want++;
+	const uint64_t got = lowerBound( a.data(), lo, hi, key );
+	CHECK( got == want, "lowerBound in [%llu, %llu) of %llu entries, key %llu -> %llu, expected %llu", (unsigned long long)lo, (unsigned long long)hi,
+		   (unsigned long long)a.size(), (unsigned long long)key, (unsigned long long)got, (unsigned long long)want );
+}
+static void testLowerBound()
+{
+	const std::vector<uint64_t> none( 1, 7ull ); // (a valid pointer; the range is empty)
+	for( uint64_t key : { 0ull, 7ull, ~0ull } ) checkBound( none, 0, 0, key );
+	for( uint64_t key : { 0ull, 6ull, 7ull, 8ull, ~0ull } ) checkBound( none, 0, 1, key ); // one element: below, equal, above
+	std::vector<uint64_t> a;
+	for( uint64_t i = 0; i < 37; i++ ) a.push_back( 10ull + 3ull * i + ( i > 20 ? 1ull << 40 : 0ull ) ); // ascending, unique, beyond 32 bits at the top
+	for( uint64_t v : a )
+		for( uint64_t key : { v - 1, v, v + 1 } ) // between, equal, between
+		{
+			checkBound( a, 0, a.size(), key );
+			checkBound( a, 5, 30, key ); // a sub-range, as the edit merge searches
+			checkBound( a, 12, 12, key );
+		}
+	for( uint64_t key : { (uint64_t)0, (uint64_t)9, a.back() + 1, ~(uint64_t)0 } ) checkBound( a, 0, a.size(), key ); // below all, above all
+}
+
+int main()
+{
+	testCodec();
+	testFindRun();
+	testBits();
+	testLowerBound();
+	if( g_failures ) printf( "%d checks failed\n", g_failures );
+	else printf( "voxel passes host checks ok\n" );
+	return g_failures ? 1 : 0;
+}

@@ -1,7 +1,7 @@
 """Enclosed empty cells and the fill on the GPU (mvrt_svo_enclosed_cells / mvrt_svo_fill_enclosed) against the numpy model of tests/fill_expected.py: xyz,
 region, nCells and nRegions bit for bit, on the smallest inputs that can break each mechanism -- grids without a gap, a one-cell cage, diagonal contact, a shell
 on the grid border, one long gap (the neighbour walk), several hundred chained gaps (the depth of the union-find and its propagation across launch blocks),
-nesting and numbering, random fills across every 256-item seam, the 21-bit edge, every flavour, edits, a rebuilt upload, the bunny -- and the contract of the two
+nesting and numbering, random fills across every 256-item seam, lists of 255 to 612 voxels with cells on both sides of a seam and a group without any, the 21-bit edge, every flavour, edits, a rebuilt upload, the bunny -- and the contract of the two
 calls.  The listing limit (nCells >= 2^32) and the fill limit (numberOfVoxels + nCells >= 2^32 - 1) are host comparisons (csrc/kernels_fill.hip, csrc/api.hip)
 covered by reading: reaching them takes 2^32 cells."""
 import ctypes as C
@@ -173,6 +173,70 @@ def test_random_fills_have_many_small_regions():
     """(the model alone) the random sets above are worth their time: dozens of regions at 32^3"""
     rng = np.random.default_rng(1000 * 32 + 10 * 7 + 0)
     assert F.enclosed(np.argwhere(rng.random((32, 32, 32)) < 0.7), 32)["nRegions"] >= 24
+
+
+# ---- the seams of the emit kernel's groups -----------------------------------------------------------------------------------------------------------------------
+def emitted_per_gap(xyz, res, want):
+    """per voxel i of the list sorted by (z, y, x) -- the order the emit kernel's groups of 256 are cut from -- the enclosed cells of the gap between voxels i
+    and i + 1 (0: no gap, or an exterior one), from the model's cells"""
+    p = np.asarray(xyz, np.int64)
+    lin = np.sort((p[:, 2] * res + p[:, 1]) * res + p[:, 0])
+    length = np.where(lin[1:] // res == lin[:-1] // res, lin[1:] - lin[:-1] - 1, 0)
+    w = want["xyz"].astype(np.int64)
+    inside = np.isin(lin[:-1] + 1, (w[:, 2] * res + w[:, 1]) * res + w[:, 0])  # (a gap is enclosed or exterior as a whole: its first cell decides)
+    out = np.append(np.where(inside, length, 0), 0)
+    assert out.sum() == len(w)
+    return out
+
+
+def filler(count, z, res=32):
+    """`count` voxels of layer z without an enclosed gap: full rows along x, then a partial row whose last voxel stands at the far border (one exterior gap)"""
+    i = np.arange(count)
+    p = np.stack([i % res, i // res, np.full(count, z)], 1)
+    if 1 < count % res < res - 1:
+        p[-1, 0] = res - 1
+    return p
+
+
+def seam_scene(n):
+    """n voxels at gridRes 32, in (z, y, x) order: a cage, a layer of filler, [two cages that share a voxel, a layer of filler,] a cage"""
+    cage = np.array(CAGE)
+    if n == 513:  # the two gaps of the double cage are items 255 and 256: the last of the first group and the first of the second
+        double = np.unique(np.concatenate([cage + (0, 0, 6), cage + (2, 0, 6)]), axis=0)
+        assert len(double) == 11
+        middle = [filler(245, 4), double, filler(n - 6 - 245 - 11 - 6, 10)]
+    else:
+        middle = [filler(n - 12, 4)]
+    xyz = np.concatenate([cage] + middle + [cage + (5, 5, 12)])
+    assert len(xyz) == n == len(np.unique(xyz, axis=0))
+    return xyz
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 513, 612])
+def test_voxel_counts_at_the_group_seams(mv, n):
+    xyz = seam_scene(n)
+    svo, want = check(mv, xyz, 32)
+    cells = emitted_per_gap(xyz, 32, want)
+    groups = [int(cells[g:g + 256].sum()) for g in range(0, n, 256)]
+    print(n, "cells per group", groups)
+    assert cells[2] == 1 and cells[n - 4] == 1  # the first cage's gap and the last one's, four items before the end
+    if n == 513:
+        assert cells[255] == 1 and cells[256] == 1 and groups == [2, 2, 0]
+    elif n == 612:  # a whole group without a cell between two that have one
+        assert groups == [1, 0, 1]
+    else:
+        assert groups == [2] + [0] * (len(groups) - 1)
+    assert svo.fill_enclosed() == len(want["xyz"])  # the emit's other output: the cells as they come
+    assert np.array_equal(svo.read_voxels()[0], F.filled_set(xyz, 32))
+
+
+def test_a_gap_longer_than_a_group(mv):
+    """the tube's one gap has more cells than a group has threads and than a group has items: every thread takes a second cell of the same item"""
+    t = tube()
+    svo, want = check(mv, t, 512)
+    cells = emitted_per_gap(t, 512, want)
+    assert cells.max() == 298 > 256 and (cells > 0).sum() == 1
+    assert svo.fill_enclosed() == 298 and np.array_equal(svo.read_voxels()[0], F.filled_set(t, 512))
 
 
 # ---- the 21-bit edge -------------------------------------------------------------------------------------------------------------------------------------------------

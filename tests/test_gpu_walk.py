@@ -1,7 +1,8 @@
 """mvrt_svo_walk_voxels and mvrt_svo_rebuild on the GPU against the numpy model of tests/walk_expected.py, the oracle's builder and the library's own
 read-back, integers and bytes bit for bit.  The scenes are the smallest that reach each way the walk can go wrong: a root whose children are voxels (no
 frontier level), one-voxel chains, the empty octree, several thousand parents with uneven child counts (offsets across the 256-parent groups), a 63-bit
-prefix at 21 levels; every legal upload shape of tests/upload_shapes.py, both flavours."""
+prefix at 21 levels; every legal upload shape of tests/upload_shapes.py, both flavours; hand-made trees whose last frontier is 255, 256 and 257 parents, and
+one with a whole group of 256 childless parents between two groups with children."""
 import os
 import shutil
 import subprocess
@@ -255,6 +256,78 @@ def test_rebuild_of_a_built_handle_changes_the_flavour(mv, O, scenes, first, the
     assert_svo(O, svo, base.morton, attrs, base.he, base.res, then, len(base.morton), nodes=oracle_octree(O, base.morton, base.res, then))
     assert svo.info().flavour == {0: 0, 1: 0, 2: 1, 3: 2}[then]
     assert_walk(svo.walk_voxels(), D.decode(base.morton), np.arange(len(base.morton)), attrs)
+
+
+# ---- 7. the seams of the emit kernel's groups -----------------------------------------------------------------------------------------------------------
+def tree_of(O, leaf_masks, levels, emb):
+    """The octree (a tree: no sharing, children numbered before their parent, root last, the builder's nVoxelsPSum) whose parents of voxels are the keys of
+    leaf_masks -- paths of levels - 1 octal digits -- with the given masks of voxels.  Mask 0 is a reachable empty node, legal in an upload."""
+    prefixes = {(levels - 1 - up, k >> (3 * up)) for k in leaf_masks for up in range(levels)}  # (depth, path so far)
+    rows = []
+
+    def make(prefix, depth):  # -> (index, own mask, voxels below)
+        kids, psum, mask, count = [U.LEAF] * 8, [0] * 8, 0, 0
+        for c in range(8):
+            psum[c] = count
+            if depth == levels - 1:
+                if leaf_masks[prefix] >> c & 1:
+                    mask, count = mask | 1 << c, count + 1
+            elif (depth + 1, prefix * 8 + c) in prefixes:
+                i, m, n = make(prefix * 8 + c, depth + 1)
+                kids[c], mask, count = (i | m << 24) if emb else i, mask | 1 << c, count + n
+        rows.append((mask, kids, psum))
+        return len(rows) - 1, mask, count
+
+    n_voxels = make(0, 0)[2]
+    nodes = np.zeros(len(rows), O.NODE_DTYPE)
+    nodes["mask"], nodes["children"], nodes["psum"] = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
+    return nodes, n_voxels
+
+
+def seam_masks(name):
+    """-> (levels, {path: mask}) with the parents of voxels in path order cut into the emit kernel's groups of 256 where it can go wrong"""
+    rng = np.random.default_rng(len(name))
+    if name == "empty_group":  # 770 parents: the whole second group (256 .. 511) has mask 0, between two groups with children
+        keys = np.sort(rng.choice(8 ** 4, 770, replace=False))
+        masks = rng.integers(1, 256, 770)
+        masks[rng.random(770) < 0.2] = 0
+        masks[250:515] = 0
+        masks[[0, 249, 515, 769]] = [0x81, 0xFF, 0x01, 0x80]
+        return 5, dict(zip(keys.tolist(), masks.tolist()))
+    n = int(name)  # 255, 256, 257 parents: one group short of full, full, and one parent in a second group
+    keys = np.sort(rng.choice(8 ** 3, n, replace=False))
+    masks = rng.integers(1, 256, n)
+    masks[rng.random(n) < 0.2] = 0
+    masks[[0, 254]] = [0x80, 0xFF]  # children in the first and the last full lane of the first group
+    masks[n - 1] = 0x01 if n != 256 else 0  # the last parent: one child, or none (the group's run ends before its last item)
+    return 4, dict(zip(keys.tolist(), masks.tolist()))
+
+
+@pytest.mark.parametrize("emb", [True, False])
+@pytest.mark.parametrize("name", ["255", "256", "257", "empty_group"])
+def test_frontiers_at_the_group_seams(mv, O, name, emb):
+    levels, leaf_masks = seam_masks(name)
+    res = 1 << levels
+    nodes, nv = tree_of(O, leaf_masks, levels, emb)
+    U.set_masks_zero_padding(nodes)
+    assert mv.IntersectorOctreeGPU.check_upload(nodes, nv, res, emb) is None
+    # what the scene is for, from the nodes themselves: the frontier of the last level in path order, and its runs of mask 0
+    frontier = nodes["mask"][U.depths(nodes, emb) == levels - 1]  # (a tree numbered in path order: index order is path order)
+    assert len(frontier) == len(leaf_masks) and np.array_equal(frontier, [leaf_masks[k] for k in sorted(leaf_masks)])
+    if name == "empty_group":
+        assert len(frontier) > 512 and not frontier[256:512].any() and frontier[:256].any() and frontier[512:].any()
+        zero_run = max(len(r) for r in "".join("0" if m == 0 else "1" for m in frontier).split("1"))
+        assert zero_run >= 256
+    else:
+        assert len(frontier) == int(name)
+    rng = np.random.default_rng(5)
+    attrs = rng.integers(0, 256, (nv, 8), dtype=np.uint8)
+    paths, vi, xyz = W.walk(nodes, res, emb)
+    assert len(paths) == nv == int(sum(bin(m).count("1") for m in leaf_masks.values())) and np.array_equal(vi, np.arange(nv))
+    svo = mv.IntersectorOctreeGPU()
+    svo.upload(nodes, attrs, (0.0, 0.0, 0.0), np.float32(1.0 / res), res, int(attrs[:, 4:7].any()), embeddedMask=emb)
+    assert svo.walk_voxels_device() == nv
+    assert_walk(svo.walk_voxels(), xyz, vi, attrs[vi])
 
 
 # ---- upper layers -----------------------------------------------------------------------------------------------------------------------------------------
