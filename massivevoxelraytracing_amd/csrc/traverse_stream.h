@@ -33,9 +33,10 @@
 //        hence at strictly increasing levels, so "which entries are pending" is a 32-bit mask in a
 //        register; pop = highest set bit.  Neither sp nor the level is stored.
 //      - scale = 2^-level is rebuilt from the level.
-//      - the child a node is left through (3 bits) rides in the sign bits of tx1/ty1/tz1: a saved node was entered with
-//        min(x1,y1,z1) >= 0, so its exit times are never negative (a -0.0 would come back as +0.0,
-//        which no comparison or output can distinguish).
+//      - the child a node is left through (3 bits) is not stored: it is in the path of child indices (below), in the three bits
+//        above the node's own prefix, and the pop reads it there.  (Tree flavour, which keeps no path: it rides in the sign bits of
+//        tx1/ty1/tz1 -- a saved node was entered with min(x1,y1,z1) >= 0, so its exit times are never negative; a -0.0 would come
+//        back as +0.0, which no comparison or output can distinguish.)
 //      - nVoxelSkipped is not saved at all: the path of child indices (3 bits per level, one 64-bit
 //        register = the hit voxel's morton code) is kept instead; the traversal reports that path and
 //        the CONSUMER of the hit sums nVoxelsPSum along it (voxelIndexFromPath) in a dense kernel where
@@ -484,7 +485,11 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 	bool isShadow = false;
 	uint32_t ray = 0;
 	float dtx = 0, dty = 0, dtz = 0, tx1 = 0, ty1 = 0, tz1 = 0;
-	uint32_t vMask = 0, vMaskHi = 24u, node = 0, nodeMask = 0, level = 0, childMask = 8u, pending = 0, inLds = 0, descents = 0;
+	uint32_t vMask = 0, vMaskHi = 24u, node = 0, nodeMask = 0, level = 0, pending = 0, inLds = 0, descents = 0;
+	// where the visit of the current node resumes.  Flavours that keep the path: nres = ~resume, where resume is -1 on a first visit (nres = 0) and, on the revisit of
+	// a popped node, the mirrored-space candidate index through which the node was left (see the step).  Tree flavour: childMask, the candidate a revisit restarts
+	// from (8 = first visit)
+	uint32_t nres = 0u, childMask = 8u;
 	uint32_t bLo = 0, bHi = 0; // tree flavour: child masks of the brick whose root is being visited
 	uint64_t path = 0;
 	// result of a finished lane (st >= 2), from its parked state
@@ -628,6 +633,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 							if( TREE && ( s.levelsM1 & 1u ) ) treeEnterBrick( nodes, s.rootIndex, &node, &nodeMask, &bLo, &bHi ); // the root is a brick root
 							level = 0;
 							childMask = 8u;
+							nres = 0u;
 							pending = 0;
 							inLds = 0;
 							st = 1u;
@@ -672,14 +678,14 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 										if( on )
 										{
 											const bool later = ( (int)!bx & (int)( txM <= minF( ty1, tz1 ) ) ) | ( (int)!by & (int)( tMyz.x < tx1 ) & (int)( tMyz.x <= tz1 ) ) | ( (int)!bz & (int)( tMyz.y < minF( tx1, ty1 ) ) );
-											if( later ) // stack the ancestor (:377-380); its exit times carry the octant it is left through, like any entry
+											if( later ) // stack the ancestor (:377-380); the octant it is left through is the hint's child at this level, which `path` holds as for any entry
 											{
 												// (the node reference -- word 0 -- is filled in after the walk, when the table gathers have landed: their
 												// latency hides behind this arithmetic instead of stalling the wave at the first level)
 												LdsU32* const w = (LdsU32*)( myRing + L * 64 );
-												w[1] = mvrt_f2u( tx1 ) | ( bx ? 0x80000000u : 0u ); // (T >= 0: the sign bits are free)
-												w[2] = mvrt_f2u( ty1 ) | ( by ? 0x80000000u : 0u );
-												w[3] = mvrt_f2u( tz1 ) | ( bz ? 0x80000000u : 0u );
+												w[1] = mvrt_f2u( tx1 );
+												w[2] = mvrt_f2u( ty1 );
+												w[3] = mvrt_f2u( tz1 );
 												pending |= 1u << L;
 											}
 											tx1 = bx ? tx1 : txM; // :382-386
@@ -749,10 +755,28 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 		// (the reference's min + "x first, then y" tie rule) until the first exit event; every earlier mid-plane event of a not yet
 		// passed axis is a flip -- so the up to four candidates, their existence in the node's mask and the "behind the origin" test
 		// are evaluated side by side, the first valid one is entered, and the node is pushed only if a later VALID candidate exists.
-		// All of it is 1-bit logic: the compares produce 64-bit lane masks and the combinatorics run on the scalar unit.  The child
-		// mask of every lane lives bit-sliced in three SGPR pairs (+ a "first visit" mask) while the loop runs.
-		lmask cmX = __ballot( ( childMask & 1u ) != 0u ), cmY = __ballot( ( childMask & 2u ) != 0u ), cmZ = __ballot( ( childMask & 4u ) != 0u );
-		lmask mFirst = __ballot( ( childMask & 8u ) != 0u );
+		// All of it is 1-bit logic: the compares produce 64-bit lane masks and the combinatorics run on the scalar unit.
+		//
+		// REVISIT of a popped node (flavours that keep the path).  The exit times of a popped node come back bit for bit and its level with them, so the revisit
+		// recomputes the first visit's X, Y, Z, flips and candidate chain i0, i1, i2, i3 exactly.  The chain is nested -- each candidate adds the bit of one flipped
+		// axis -- hence strictly increasing as a number wherever the next candidate exists geometrically (n1 / n2 / n3).  If the node was left through candidate j
+		// (`resume` = i_j), the candidates already dealt with are exactly those with i_k <= resume, and candidate k stays eligible iff i_k > resume: a first visit
+		// (resume = -1) filters nothing.  Where candidates coincide (no flip: i1 == i0; two flips: i2 == i3) the later one has n_k clear and is never valid, so a
+		// tie cannot admit the child already taken a second time.
+		// Behind-the-origin prefix (b0..b2): candidate j was entered, so it was not behind (b_j clear; for j == 3 nothing follows).  The candidates behind the
+		// origin are a prefix of the chain, so b_k is clear for every k > j as well: on the eligible candidates the test is vacuous, which is what a revisit that
+		// restarts from candidate j sees (its remaining flips are the events after a non-negative one: none is negative).  Eligible and valid are thus the same
+		// candidates, in the same order, as for the restart: the same child is entered, and the push -- "two or more valid candidates" -- fires under the same
+		// condition.  A replayed ancestor of the hint was left through the origin's octant, i_j with j = the number of negative flips, so b_j is clear there too.
+		// The resume point needs no storage: the child a stacked node was left through is in `path`, in the three bits above the node's own prefix.
+		// Tree flavour (no path): the restart, with the candidate in the sign bits of the stacked exit times and bit-sliced in three SGPR pairs (+ a "first visit"
+		// mask) while the loop runs.
+		lmask cmX = 0ull, cmY = 0ull, cmZ = 0ull, mFirst = 0ull;
+		if( TREE )
+		{
+			cmX = __ballot( ( childMask & 1u ) != 0u ), cmY = __ballot( ( childMask & 2u ) != 0u ), cmZ = __ballot( ( childMask & 4u ) != 0u );
+			mFirst = __ballot( ( childMask & 8u ) != 0u );
+		}
 		lmask actM = __ballot( st == 1u ), hitM = 0ull;
 		for( ;; )
 		{
@@ -775,11 +799,11 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
 			const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
 			const float tyM = tMyz.x, tzM = tMyz.y;
-			// octant the node is entered in (:342-348), or the candidate a popped node resumes with
+			// octant the node is entered in (:342-348); tree flavour: or the candidate a popped node resumes with
 			// (cmX / cmY / cmZ carry bits only for lanes whose mFirst bit is clear: kept so by the loop tail)
-			const lmask X = ( mFirst & __ballot( txM < S ) ) | cmX;
-			const lmask Y = ( mFirst & __ballot( tyM < S ) ) | cmY;
-			const lmask Z = ( mFirst & __ballot( tzM < S ) ) | cmZ;
+			const lmask X = TREE ? ( mFirst & __ballot( txM < S ) ) | cmX : __ballot( txM < S );
+			const lmask Y = TREE ? ( mFirst & __ballot( tyM < S ) ) | cmY : __ballot( tyM < S );
+			const lmask Z = TREE ? ( mFirst & __ballot( tzM < S ) ) | cmZ : __ballot( tzM < S );
 			// first exit event = lexicographic minimum of (t1, axis); flips = mid-plane events of unset axes that come before it, i.e.
 			// before EVERY exit event (an axis' own exit never precedes its mid-plane: tM <= t1).  (tM_a, a) < (t1_b, b) is "tM_a <= t1_b" for
 			// a < b and "tM_a < t1_b" for a > b
@@ -803,7 +827,12 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			const uint32_t i3 = i0 | MVRT_SELKK( fX, 1, 0 ) | MVRT_SELKK( fY, 2, 0 ) | MVRT_SELKK( fZ, 4, 0 );
 			const uint32_t i1 = i0 | MVRT_SELK( aX, 1, MVRT_SELK( aY, 2, MVRT_SELKK( aZ, 4, 0 ) ) );
 			const uint32_t i2 = i3 ^ MVRT_SELK( zX, 1, MVRT_SELK( zY, 2, MVRT_SELKK( zZ, 4, 0 ) ) );
-#define MVRT_EXISTS( i ) __ballot( EMBED ? bitMask( node, ( i ) ^ vMaskHi ) != 0u : ( ( nodeMask >> ( ( ( i ) ^ vMaskHi ) & 7u ) ) & 1u ) != 0u )
+			// e_k: candidate k exists in the node's mask -- and, with the path at hand, is eligible (i_k > resume) in the same compare: m = 0 / -1 from the mask bit,
+			// m ^ i_k is ~i_k (negative) for a child that exists and i_k (>= 0) for one that does not; against nres = ~resume (0 on a first visit, negative on a
+			// revisit) "m ^ i_k < nres" is ~i_k < ~resume, i.e. i_k > resume, for the former and never true for the latter
+#define MVRT_EXISTS( i )                                                                                                                                                      \
+	( TREE ? __ballot( ( ( nodeMask >> ( ( ( i ) ^ vMaskHi ) & 7u ) ) & 1u ) != 0u )                                                                                          \
+		   : __ballot( (int)( ( EMBED ? bitMask( node, ( i ) ^ vMaskHi ) : bitMask( nodeMask, ( i ) ^ vMask ) ) ^ ( i ) ) < (int)nres ) )
 			const lmask e0 = MVRT_EXISTS( i0 ), e1 = MVRT_EXISTS( i1 ), e2 = MVRT_EXISTS( i2 ), e3 = MVRT_EXISTS( i3 );
 #undef MVRT_EXISTS
 			// a candidate is behind the origin when the event that ends it is negative (:373).  Events are visited in time order, so the
@@ -813,11 +842,12 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			const lmask b0 = kx | ky | kz, b1 = ( kx & ky ) | ( ( kx | ky ) & kz ), b2 = kx & ky & kz;
 			const lmask mLeaf = act & __ballot( node == MVRT_LEAF ); // :322
 			const lmask inner = act & ~mLeaf & ~__ballot( T < 0.0f );
-			// candidate 0 of a popped node is the child it was left through: already done
-			const lmask v0 = mFirst & e0 & ~b0, v1 = n1 & e1 & ~b1, v2 = n2 & e2 & ~b2, v3 = n3 & e3;
-			const lmask mGo = inner & ( v0 | v1 | v2 | v3 );
-			const lmask l3 = v3, l2 = v2 | l3, l1 = v1 | l2; // a valid candidate at or after 3 / 2 / 1
-			const lmask mPush = inner & ( ( v0 & l1 ) | ( ~v0 & ( ( v1 & l2 ) | ( ~v1 & v2 & l3 ) ) ) ); // only if a later VALID candidate exists (the reference: any later candidate; measured +8.6 %)
+			// tree flavour: candidate 0 of a popped node is the child it was left through: already done
+			const lmask v0 = ( TREE ? mFirst & e0 : e0 ) & ~b0, v1 = n1 & e1 & ~b1, v2 = n2 & e2 & ~b2, v3 = n3 & e3;
+			// push only if a later VALID candidate exists (the reference: any later candidate; measured +8.6 %), i.e. if at least two of the four are valid
+			const lmask vA = v0 | v1, vB = v0 & v1, vC = v2 | v3, vD = v2 & v3;
+			const lmask mGo = inner & ( vA | vC );
+			const lmask mPush = inner & ( vB | vD | ( vA & vC ) );
 			const lmask mHit = mLeaf & __ballot( 0.0f < S ); // :324
 			const lmask mPop = act & ~mHit & ~mGo;
 			// the entered candidate = the first valid one
@@ -825,7 +855,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			const uint32_t childBit = ci ^ vMaskHi; // :369 (+24)
 			const uint32_t childIndex = childBit & 7u;
 
-			uint4 popped = make_uint4( 0u, 0u, 0u, 0u );
+			uint4 popped = make_uint4( 0u, 0u, 0u, 0u ); // (tree flavour: zero on the lanes that do not pop, for the sign tests of the loop tail; otherwise never read there)
 			uint32_t poppedMask = 0;
 			const lmask mPopOk = mPop & __ballot( pending != 0u ); // (lane masks are only ever computed at the top level: a value assigned
 																  // under a divergent branch stops being wave-uniform for the compiler)
@@ -848,6 +878,10 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 						popped = *(const uint4*)( (const char*)spill + ( ( L << spillShift ) + spillOff ) );
 						if( !EMBED ) poppedMask = *(const uint32_t*)( (const char*)spillMask + ( ( L << spillMaskShift ) + spillMaskOff ) );
 						if( TREE ) poppedMask2 = *(const uint32_t*)( (const char*)spillMask2 + ( ( L << spillMaskShift ) + spillMaskOff ) );
+						// the restored exit times are the loaded words themselves: "use" them HERE, so that the wait for this rare load sits in this block.  Left to the
+						// first real use -- the slab arithmetic at the top of the next iteration -- that wait would also cover the child-pointer load of the lanes that
+						// descend, whose latency is meant to hide behind that arithmetic
+						if( !TREE ) asm volatile( "" : "+v"( popped.y ), "+v"( popped.z ), "+v"( popped.w ) );
 					}
 					if( TREE && ( ( s.levelsM1 - L ) & 1u ) ) // back at a brick root: its child masks come off the stack, its own mask is their non-zero bytes
 					{
@@ -857,14 +891,22 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 					}
 					pending &= ~bit;
 					inLds &= ~bit;
-					if( !TREE ) path >>= 3u * ( level - L );
+					if( !TREE )
+					{
+						// the path down to the child of level L the node was left through, that child's index (mirrored: the candidate) as the resume point, then the
+						// path of the node itself
+						path >>= 3u * ( level - L ) - 3u;
+						nres = ~( ( (uint32_t)path ^ vMask ) & 7u );
+						path >>= 3u;
+					}
 					level = L;
 					node = popped.x;
 
 					if( !EMBED ) nodeMask = poppedMask;
-					tx1 = mvrt_u2f( popped.y & 0x7FFFFFFFu );
-					ty1 = mvrt_u2f( popped.z & 0x7FFFFFFFu );
-					tz1 = mvrt_u2f( popped.w & 0x7FFFFFFFu );
+					// (tree flavour: the sign bits carry the candidate the node was left through)
+					tx1 = mvrt_u2f( TREE ? popped.y & 0x7FFFFFFFu : popped.y );
+					ty1 = mvrt_u2f( TREE ? popped.z & 0x7FFFFFFFu : popped.z );
+					tz1 = mvrt_u2f( TREE ? popped.w & 0x7FFFFFFFu : popped.w );
 				}
 			}
 			if( LANE( mGo ) )
@@ -883,10 +925,19 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 					}
 					u4v e;
 					e.x = node;
-					// the sign bits of a saved node's exit times are free (entered with min >= 0): they carry the child the node is left through
-					e.y = lshlOr( ci, 31u, mvrt_f2u( tx1 ) );
-					e.z = bfi( 0x7FFFFFFFu, mvrt_f2u( ty1 ), ci << 30 );
-					e.w = bfi( 0x7FFFFFFFu, mvrt_f2u( tz1 ), ci << 29 );
+					if( TREE )
+					{
+						// the sign bits of a saved node's exit times are free (entered with min >= 0): they carry the child the node is left through
+						e.y = lshlOr( ci, 31u, mvrt_f2u( tx1 ) );
+						e.z = bfi( 0x7FFFFFFFu, mvrt_f2u( ty1 ), ci << 30 );
+						e.w = bfi( 0x7FFFFFFFu, mvrt_f2u( tz1 ), ci << 29 );
+					}
+					else // the child the node is left through goes into `path` below
+					{
+						e.y = mvrt_f2u( tx1 );
+						e.z = mvrt_f2u( ty1 );
+						e.w = mvrt_f2u( tz1 );
+					}
 					myRing[slot * 64] = e;
 					if( !EMBED ) myRingMask[slot * 64] = ( TREE && ( ( s.levelsM1 - level ) & 1u ) ) ? bLo : nodeMask;
 					if( TREE ) myRingMask2[slot * 64] = bHi;
@@ -914,19 +965,23 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 				ty1 = mvrt_u2f( bfi( bitMask( ci, 1 ), mvrt_f2u( ty1 ), mvrt_f2u( tyM ) ) );
 				tz1 = mvrt_u2f( bfi( bitMask( ci, 2 ), mvrt_f2u( tz1 ), mvrt_f2u( tzM ) ) );
 				level++;
+				nres = 0u; // a first visit
 			}
 			// hit (:324-334) or miss: the lane holds its result until the next refill.  Selects, not a branch: some lane finishes in
 			// almost every iteration of a 64-lane wave anyway
 			// (a hit only changes the lane's state: t and nMajor are re-derived by finishedHit() from the slab state the lane keeps)
-			// bit-sliced child mask of the lanes that popped = the sign bits of the restored exit times; a descent starts a first visit
-			// (`popped` is zero for the lanes that did not pop)
-			// (a lane that descended starts a first visit: its resume bits are cleared with those of the lanes that popped, which keeps the invariant the top
-			// of the loop relies on)
-			const lmask keep = ~( mPopOk | mGo );
-			cmX = ( cmX & keep ) | signMask( popped.y );
-			cmY = ( cmY & keep ) | signMask( popped.z );
-			cmZ = ( cmZ & keep ) | signMask( popped.w );
-			mFirst = ( mFirst & keep ) | mGo;
+			if( TREE )
+			{
+				// bit-sliced child mask of the lanes that popped = the sign bits of the restored exit times; a descent starts a first visit
+				// (`popped` is zero for the lanes that did not pop)
+				// (a lane that descended starts a first visit: its resume bits are cleared with those of the lanes that popped, which keeps the invariant the top
+				// of the loop relies on)
+				const lmask keep = ~( mPopOk | mGo );
+				cmX = ( cmX & keep ) | signMask( popped.y );
+				cmY = ( cmY & keep ) | signMask( popped.z );
+				cmZ = ( cmZ & keep ) | signMask( popped.w );
+				mFirst = ( mFirst & keep ) | mGo;
+			}
 			// which lanes are still traversing / hold a hit is kept in lane masks (scalar unit) while the loop runs.  An active lane hits, descends or pops; it
 			// stays active iff it descended or popped an entry (a pop from an empty stack is a miss: derived after the loop)
 			hitM |= mHit;
@@ -936,6 +991,6 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 		// the lanes that were traversing when the loop was entered and neither still are nor hit have missed; lanes that were idle or parked keep their state
 		const lmask missM = __ballot( st == 1u ) & ~actM & ~hitM; // (st is not written while the loop runs: no mask of the entry state has to live across it)
 		st = LANE( hitM ) ? 3u : ( LANE( missM ) ? 2u : st );
-		childMask = LANE( mFirst ) ? 8u : ( ( LANE( cmX ) ? 1u : 0u ) | ( LANE( cmY ) ? 2u : 0u ) | ( LANE( cmZ ) ? 4u : 0u ) );
+		if( TREE ) childMask = LANE( mFirst ) ? 8u : ( ( LANE( cmX ) ? 1u : 0u ) | ( LANE( cmY ) ? 2u : 0u ) | ( LANE( cmZ ) ? 4u : 0u ) );
 	}
 }
