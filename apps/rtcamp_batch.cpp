@@ -8,12 +8,17 @@
 // orbiting look-at camera.  Everything GPU-side goes through include/mvrt/PathTracer.hpp -> libmvrt_hip.so.
 //
 //   rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov] [--denoise]
+//                [--adaptive threshold] [--adaptive-every K]
 //
 // --aov also writes, beside each frame, <frame>_albedo and <frame>_normal in the frame's format: the means over all samples of the first-hit
 // feature buffers (mvrt.h "First-hit feature buffers"), what a denoiser takes as guides.  Encoded on the host from read-back data, in fp32:
 // albedo byte = (int)( 255 * ( sum / samples ) + 0.5f ), normal byte = (int)( 255 * ( 0.5f * ( sum / samples ) + 0.5f ) + 0.5f ), alpha 255.
 // --denoise switches the feature buffers and the luminance moments on and also writes <frame>_denoised in the frame's format: mvrt_pt_denoise with the
 // default parameters on the accumulated frame, tone-mapped by mvrt_resolve_buffer like the frame itself (mvrt.h "Denoiser").
+// --adaptive switches the luminance moments on and keeps sampling only where the frame has not converged (mvrt.h "Adaptive sampling"): the first
+// minSamples / 16 = 2 steps sample every pixel; then, every K steps (--adaptive-every, default 2), mvrt_pt_error_mask with the threshold marks the pixels whose
+// standard error still exceeds threshold * max( mean luminance, 0.01 ) and mvrt_pt_set_sample_mask restricts the steps to them.  A frame stops early when no
+// pixel is marked.  Per frame it prints the steps taken and the samples spent against steps * pixels * 16.  Composes with --denoise (per-pixel sample counts).
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -90,8 +95,10 @@ int main( int argc, char** argv )
 	if( argc < 4 )
 	{
 		std::printf( "usage: rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov] [--denoise]\n"
+					 "                    [--adaptive threshold] [--adaptive-every K]\n"
 					 "  --aov      also write <frame>_albedo and <frame>_normal (first-hit feature buffers)\n"
-					 "  --denoise  also write <frame>_denoised (a-trous denoiser on the feature buffers and the luminance moments)\n" );
+					 "  --denoise  also write <frame>_denoised (a-trous denoiser on the feature buffers and the luminance moments)\n"
+					 "  --adaptive after 32 samples per pixel, sample only the pixels whose standard error exceeds threshold * mean luminance; re-marked every K steps (default 2)\n" );
 		std::printf( "  [instance 0] rtcamp_batch ... --frame-range 0 171\n  [instance 1] rtcamp_batch ... --frame-range 171 240\n" );
 		return 0;
 	}
@@ -100,6 +107,9 @@ int main( int argc, char** argv )
 	const std::string outDir = argv[3];
 	int totalFrames = 240, beginFrame = 0, endFrame = -1, W = 1440, H = 900, fromRes = 256, toRes = 8192, steps = 8; // RTCamp.cpp:42-45,136-137,156
 	bool png = false, dumpCameras = false, aov = false, denoise = false;
+	float adaptive = 0.0f; // > 0: the threshold of --adaptive
+	int adaptiveEvery = 2;
+	const int adaptiveMinSamples = 32;
 	for( int i = 4; i < argc; i++ )
 	{
 		if( !std::strcmp( argv[i], "--dump-cameras" ) ) dumpCameras = true;
@@ -111,8 +121,11 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--png" ) ) png = true;
 		else if( !std::strcmp( argv[i], "--aov" ) ) aov = true;
 		else if( !std::strcmp( argv[i], "--denoise" ) ) denoise = true;
+		else if( !std::strcmp( argv[i], "--adaptive" ) && i + 1 < argc ) adaptive = (float)std::atof( argv[++i] );
+		else if( !std::strcmp( argv[i], "--adaptive-every" ) && i + 1 < argc ) adaptiveEvery = std::atoi( argv[++i] );
 	}
 	if( endFrame < 0 ) endFrame = totalFrames;
+	if( adaptiveEvery < 1 ) adaptiveEvery = 1;
 
 	std::vector<mvrt_io::V3> vertices, vcolors, vemissions;
 	if( !mvrt_io::readObj( objPath, &vertices, &vcolors, &vemissions ) )
@@ -137,8 +150,10 @@ int main( int argc, char** argv )
 	mvrt::PathTracer pt;
 	pt.setup( stream );
 	if( aov || denoise ) pt.setAOVs( true );
-	if( denoise ) pt.setMoments( true );
+	if( denoise || adaptive > 0.0f ) pt.setMoments( true );
 	pt.resizeFrameBufferIfNeeded( stream, W, H );
+	uint8_t* maskDev = nullptr; // --adaptive: the error mask, one byte per owned pixel
+	if( adaptive > 0.0f ) mvrt::check( mvrt_malloc( (void**)&maskDev, mvrt_pt_owned_pixels( pt.handle() ) ), "mvrt_malloc" );
 	uint8_t* denoisedU8Dev = nullptr; // the tone-mapped denoised frame on the device
 	if( denoise ) mvrt::check( mvrt_malloc( (void**)&denoisedU8Dev, (uint64_t)W * H * 4 ), "mvrt_malloc" );
 	pt.loadHDRI( stream, hdrPath, hdrPath );
@@ -209,7 +224,20 @@ int main( int argc, char** argv )
 		}
 
 		pt.clearFrameBuffer( stream );
-		for( int iteration = 0; iteration < steps; iteration++ ) pt.step( stream, view, proj, focus, lensR );
+		int taken = 0;
+		uint64_t spent = 0; // samples
+		for( int iteration = 0; iteration < steps; iteration++ )
+		{
+			const int sinceFull = iteration - adaptiveMinSamples / 16; // the first minSamples / 16 steps sample every pixel
+			if( adaptive > 0.0f && sinceFull >= 0 && sinceFull % adaptiveEvery == 0 )
+			{
+				pt.errorMask( stream, adaptive, maskDev, 0.01f, adaptiveMinSamples );
+				if( pt.setSampleMask( stream, maskDev ) == 0 ) break; // converged everywhere
+			}
+			pt.step( stream, view, proj, focus, lensR );
+			taken++;
+			spent += pt.activePixels() * 16;
+		}
 
 		uint8_t* buf = nullptr;
 		{
@@ -252,6 +280,8 @@ int main( int argc, char** argv )
 		}
 		cv.notify_all();
 		std::printf( "[frame %d] res( %d -> grid %d ) voxels %llu octree %.1f MB\n", frame, resolution, gridRes, (unsigned long long)pt.getNumberOfVoxels(), pt.getOctreeBytes() / 1e6 );
+		if( adaptive > 0.0f )
+			std::printf( "[frame %d] adaptive: %d of %d steps, %llu of %llu samples\n", frame, taken, steps, (unsigned long long)spent, (unsigned long long)steps * (uint64_t)W * H * 16 );
 	}
 	{
 		std::lock_guard<std::mutex> lk( mu );
@@ -262,6 +292,7 @@ int main( int argc, char** argv )
 	for( uint8_t* p : pool ) delete[] p;
 	pt.cleanUp();
 	if( denoisedU8Dev ) mvrt_free( denoisedU8Dev );
+	if( maskDev ) mvrt_free( maskDev );
 	mvrt_stream_destroy( stream );
 	std::printf( "done\n" );
 	return 0;

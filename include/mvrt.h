@@ -558,6 +558,38 @@ float* mvrt_pt_denoised_dev( mvrt_pt* pt );
 /* new; the reference has none.  Host copy on `stream` (the stream of the denoise), synchronous */
 int mvrt_pt_read_denoised( mvrt_pt* pt, void* stream, float* rgbaHost /* width*height*4 */ );
 
+/* Adaptive sampling (new; the reference has none): a per-pixel SAMPLE MASK restricts the steps to a subset of the owned pixels, and an ERROR MASK computed from
+ * the moments says which pixels have not converged.  A sample's radiance depends only on (global pixel, iteration, spp), so for an ACTIVE pixel a step under a
+ * mask makes exactly the additions an unmasked step makes -- to the frame buffer (w += 16 included), to both feature buffers and to the moments, same values,
+ * same order -- and for an INACTIVE pixel no bit of any buffer changes.  get_steps and the iteration advance as before: a pixel that sits out iteration k never
+ * gets iteration k's samples.  Batching, pipelining, sibling passes, tiles, origin hints and the HDRI scale change no bit, and a mask with every valid pixel
+ * active equals no mask.  Off by default: with no mask set every launch, allocation and output is that of a library without it.
+ *
+ * mvrt_pt_set_sample_mask: maskDev holds one byte per owned pixel in the handle's local pixel order (the order of mvrt_pt_framebuffer_dev), nonzero = active;
+ * only the first validOwnedPixels bytes are read, padding is never active.  The mask is a snapshot: the call launches the pending steps (they run under the
+ * mask they were issued under), lists the active pixels in ascending order, blocks until their number is on the host (*nActiveOut) and the array may be
+ * reused.  With no active pixel the call succeeds and the steps that follow advance the counter and launch nothing.  Under a mask everything indexed by task uses
+ * the compact numbering: sample = ( ( step * nActive + slot ) * 16 + spp ), slot = the pixel's rank among the active ones -- mvrt_pt_read_sample_radiance,
+ * mvrt_pt_sample_radiance_dev, mvrt_pt_read_debug_stage -- and mvrt_pt_stats.samples counts the active samples only.
+ * The mask goes off with maskDev == NULL, with mvrt_pt_clear_framebuffer (a new frame needs every pixel), with a resize that reallocates, with mvrt_pt_set_tile
+ * and with anything that leaves the handle without a frame; mvrt_pt_update_scene and edits through mvrt_pt_intersector keep it.
+ * Refused on the host with the handle unchanged: a null pt, no frame ("no frame buffer").  Every non-NULL call builds its list (one uint32 per owned pixel,
+ * kept with the frame) and its scratch aside: when an allocation fails, the call returns an error, the mask that was in force stays in force and nothing leaks. */
+int mvrt_pt_set_sample_mask( mvrt_pt* pt, void* stream, const uint8_t* maskDev /* ownedPixels bytes; NULL = off */, uint64_t* nActiveOut /* may be NULL */ ); /* new; the reference has none */
+/* new; the reference has none.  The pixels a step samples: validOwnedPixels when no mask is set; 0 without a frame */
+uint64_t mvrt_pt_active_pixels( const mvrt_pt* pt );
+/* new; the reference has none.  Like resolve it launches the pending steps and makes `stream` wait for the steps in flight; writes one byte (0 or 1) per owned
+ * pixel to maskDev (padding 0), blocks and returns the number of ones.  It does NOT set the mask: the caller may combine or grow it first.  Needs a frame and the
+ * moments (mvrt_pt_set_moments).  All arithmetic is fp32 in exactly this order, without contraction, division and sqrt IEEE, max( a, b ) = a < b ? b : a.
+ * Per pixel, n = frameBuffer.w:
+ *   n < (float)minSamples: 1 (n == 0 among them)
+ *   otherwise maxSamples > 0 and n >= (float)maxSamples: 0
+ *   otherwise m1 = moments.x / n;  m2 = moments.y / n;  var = max( m2 - m1 * m1, 0 ) / max( n - 1, 1 ) (the denoiser's var);  se = sqrt( var );
+ *             1 if and only if se > threshold * max( m1, lumFloor )
+ * Refused on the host: threshold or lumFloor not greater than 0 (NaN included), minSamples < 1, maxSamples < 0, a null pt or maskDev, moments off, no frame. */
+int mvrt_pt_error_mask( mvrt_pt* pt, void* stream, float threshold, float lumFloor, int minSamples, int maxSamples /* 0 = none */, uint8_t* maskDev /* ownedPixels bytes */,
+						uint64_t* nActiveOut /* may be NULL */ );
+
 /* Multi-GPU tile split (new; the reference has no multi-GPU path).  The frame is cut into the reference's own
  * 256-pixel blocks (RENDER_NUMBER_OF_THREAD, renderCommon.hpp:13) dealt round-robin: this handle renders blocks
  * b with b % tileCount == tileIndex.  Owned pixels are stored compactly in block order.  Call before

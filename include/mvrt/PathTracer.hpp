@@ -146,6 +146,24 @@ struct PathTracer
 		check( rc, "PathTracer::denoise" );
 	}
 
+	// adaptive sampling (not in the reference; mvrt.h "Adaptive sampling").  setSampleMask: one byte per owned pixel on the device, nonzero = the steps that follow
+	// sample the pixel; nullptr = every pixel again.  Returns the number of active pixels.  clearFrameBuffer, a reallocating resize and setTile drop the mask
+	uint64_t setSampleMask( void* stream, const uint8_t* maskDev )
+	{
+		uint64_t n = 0;
+		check( mvrt_pt_set_sample_mask( m_handle, stream, maskDev, &n ), "PathTracer::setSampleMask" );
+		return n;
+	}
+	uint64_t activePixels() const { return mvrt_pt_active_pixels( m_handle ); }
+	// writes 1 to maskDev (one byte per owned pixel) where the standard error of the pixel's mean luminance exceeds threshold * max( mean, lumFloor ), or the pixel
+	// has fewer than minSamples samples; 0 from maxSamples samples on (0 = no limit).  Needs setMoments( true ).  Returns the number of ones; sets no mask
+	uint64_t errorMask( void* stream, float threshold, uint8_t* maskDev, float lumFloor = 0.01f, int minSamples = 32, int maxSamples = 0 )
+	{
+		uint64_t n = 0;
+		check( mvrt_pt_error_mask( m_handle, stream, threshold, lumFloor, minSamples, maxSamples, maskDev, &n ), "PathTracer::errorMask" );
+		return n;
+	}
+
 	mvrt_pt* handle() const { return m_handle; }
 
 	IntersectorOctreeGPU m_intersectorOctreeGPU; // reference member m_intersectorOctreeGPU (:18), a value as there; bound to the handle's octree by setup()

@@ -143,6 +143,9 @@ SIGNATURES = {
     "mvrt_pt_denoise": (_i32, [_vp, _vp, _vp]),
     "mvrt_pt_denoised_dev": (_vp, [_vp]),
     "mvrt_pt_read_denoised": (_i32, [_vp, _vp, _vp]),
+    "mvrt_pt_set_sample_mask": (_i32, [_vp, _vp, _vp, _vp]),
+    "mvrt_pt_active_pixels": (_u64, [_vp]),
+    "mvrt_pt_error_mask": (_i32, [_vp, _vp, _f32, _f32, _i32, _i32, _vp, _vp]),
     "mvrt_pt_set_tile": (_i32, [_vp, _i32, _i32]),
     "mvrt_pt_owned_pixels": (_u64, [_vp]),
     "mvrt_pt_assemble_tiles": (_i32, [_vp, _i32, _u64, _i32, _i32, _vp, _vp]),
@@ -816,6 +819,42 @@ class PathTracer:
     def denoised_dev(self):
         """device pointer of the denoised buffer; None before the first denoise and after a resize"""
         return lib().mvrt_pt_denoised_dev(self._h)
+
+    def set_sample_mask(self, mask, stream=None):
+        """mvrt_pt_set_sample_mask: the steps that follow sample only the owned pixels whose byte is nonzero; None = every pixel again.  `mask`: a numpy array
+        (one entry per owned pixel, or per valid owned pixel: the padding is filled with 0) or a device array of owned_pixels() bytes.  Returns the number of
+        active pixels.  clearFrameBuffer, a reallocating resize and set_tile drop the mask"""
+        n = C.c_uint64(0)
+        if mask is None:
+            _check(lib().mvrt_pt_set_sample_mask(self._h, stream, None, C.byref(n)))
+            return n.value
+        dev = mask
+        if isinstance(mask, np.ndarray):
+            host = np.zeros(self.owned_pixels(), np.uint8)
+            flat = np.asarray(mask).reshape(-1) != 0
+            if len(flat) > len(host):
+                raise MvrtError("set_sample_mask: %d mask entries for %d owned pixels" % (len(flat), len(host)))
+            host[: len(flat)] = flat
+            dev = DeviceArray.from_host(host)
+        _check(lib().mvrt_pt_set_sample_mask(self._h, stream, _dev_ptr(dev), C.byref(n)))  # (blocks: the temporary copy may go)
+        return n.value
+
+    def active_pixels(self):
+        """the pixels a step samples: the valid owned pixels when no mask is set, 0 without a frame"""
+        return lib().mvrt_pt_active_pixels(self._h)
+
+    def error_mask(self, threshold, lum_floor=0.01, min_samples=32, max_samples=0, out_dev=None, stream=None):
+        """mvrt_pt_error_mask: 1 where the standard error of the pixel's mean luminance exceeds threshold * max( mean, lum_floor ) or the pixel has fewer than
+        min_samples samples, 0 from max_samples on (0 = no limit); needs set_moments.  Returns (mask, count): mask = out_dev when given (a device array of
+        owned_pixels() bytes, nothing is copied back), else an (owned_pixels,) uint8 host array.  Sets no mask: pass the result to set_sample_mask"""
+        n = C.c_uint64(0)
+        dev = out_dev
+        if dev is None and self.owned_pixels():
+            dev = DeviceArray(self.owned_pixels(), np.uint8)
+        # (without a frame there is nothing to size an array by: the library refuses the call on the host before it looks at the pointer)
+        ptr = _dev_ptr(dev) if dev is not None else C.c_void_p(1)
+        _check(lib().mvrt_pt_error_mask(self._h, stream, float(threshold), float(lum_floor), int(min_samples), int(max_samples), ptr, C.byref(n)))
+        return (out_dev if out_dev is not None else dev.to_host()), n.value
 
     def sample_radiance(self, n_samples=None):
         """per-sample radiance of the last pass: (n, 3) host array (debug / parity)"""

@@ -222,6 +222,20 @@ struct mvrt_pt
 		DevBuf albedo, normalDepth;		 // first-hit feature buffers (mvrt_pt_set_aovs): float4 per owned pixel like f32, allocated and cleared with it
 		DevBuf moments;					 // luminance moments (mvrt_pt_set_moments), independent of the feature buffers: one more float4 per owned pixel
 		DevBuf denoised, denoiseScratch; // mvrt_pt_denoise: its output (float4 per pixel of the frame) and its scratch, kept between calls
+		// Sample mask (mvrt_pt_set_sample_mask).  masked: the steps issued from now on sample the nActive pixels of activeList (their local indices, ascending; one
+		// uint32 per owned pixel).  The list may outlive `masked`: passes in flight still read it, so it goes with the frame or when the next list replaces it
+		DevBuf activeList;
+		uint64_t nActive = 0;
+		bool masked = false;
+		DevBuf errorCount; // mvrt_pt_error_mask: its counter
+		const uint32_t* passList() const { return masked ? activeList.as<uint32_t>() : nullptr; }
+		uint64_t activePixels() const { return masked ? nActive : validOwnedPixels; }
+		void dropMask() // the caller has drained
+		{
+			activeList.release();
+			nActive = 0;
+			masked = false;
+		}
 		uint64_t accumBytes() const { return ownedPixels * sizeof( float4 ); }
 		void release() { *this = Frame(); }
 		void releaseDenoised() // alone: by a resize (an image of the old size) and by a denoise that failed
@@ -338,6 +352,17 @@ struct mvrt_pt
 	int passSteps() const
 	{
 		int b = effectiveBatch();
+		// under a sample mask the automatic size counts the active samples of a step, so that a thin mask does not make passes that are all launch tail;
+		// bounded by what the slots were allocated for (effectiveBatch() steps of the whole frame).  Never smaller than without the mask: nActive <= ownedPixels
+		if( batch == 0 && frame.masked && frame.nActive > 0 )
+		{
+			const uint64_t perStep = frame.nActive * MVRT_SPP_PER_STEP;
+			uint64_t m = ( 66000000ull + perStep / 2 ) / perStep;
+			const uint64_t fits = frame.ownedPixels * (uint64_t)b / frame.nActive;
+			if( m > fits ) m = fits;
+			if( m > MVRT_MAX_BATCH ) m = MVRT_MAX_BATCH;
+			if( (int)m > b ) b = (int)m;
+		}
 		if( batch == 0 && lastFrameSteps >= 2 && b > ( lastFrameSteps + 1 ) / 2 ) b = ( lastFrameSteps + 1 ) / 2;
 		return b;
 	}
@@ -358,7 +383,7 @@ struct mvrt_pt
 		f.tileIndex = tileIndex;
 		f.tileCount = tileCount;
 		f.ownedPixels = frame.ownedPixels;
-		f.validOwnedPixels = frame.validOwnedPixels;
+		f.validOwnedPixels = frame.activePixels(); // (under a sample mask the pass numbers its tasks over the active list)
 		f.iteration = iteration;
 		f.nSteps = nSteps;
 		f.traceGridDiv = traceGridDiv;
@@ -557,6 +582,7 @@ MVRT_EXPORT int mvrt_pt_clear_framebuffer( mvrt_pt* pt, void* stream )
 	if( pt->join( (hipStream_t)stream ) ) return 1;
 	if( pt->steps >= 2 ) pt->lastFrameSteps = pt->steps; // the caller's frame length (passSteps); a one-step frame says nothing about the next one
 	pt->steps = 0; // PathTracer.hpp:100
+	pt->frame.masked = false; // a new frame needs every pixel (the steps in flight still read the list: it is kept)
 	return pt->frame.clear( (hipStream_t)stream );
 }
 MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream, int width, int height )
@@ -583,6 +609,7 @@ MVRT_EXPORT int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream,
 	fr.width = width;
 	fr.height = height;
 	fr.releaseDenoised(); // (a denoised image of the old size)
+	fr.dropMask();		  // (a mask of the old size)
 	if( fr.alloc( pt->aovs, pt->moments ) ) return pt->forgetFrame(); // (no frame without all of its buffers)
 	if( pt->allocWork() ) return 1;
 	return mvrt_pt_clear_framebuffer( pt, stream ); // :88
@@ -681,6 +708,7 @@ MVRT_EXPORT int mvrt_pt_step( mvrt_pt* pt, void* stream, const float camera[15] 
 		pt->pendingStream = (hipStream_t)stream;
 	}
 	pt->steps++; // PathTracer.hpp:159
+	if( pt->frame.masked && pt->frame.nActive == 0 ) return 0; // no pixel is active: the iteration is spent, nothing is launched
 	pt->pendingCams.push_back( cameraFrom15( camera ) );
 	if( (int)pt->pendingCams.size() >= pt->passSteps() ) return pt->flush( true ); // a full batch: the caller is still stepping
 	return 0;
@@ -693,7 +721,7 @@ int mvrt_pt::flush( bool moreStepsFollow )
 	// launches and by its un-overlapped shade kernels.  Two sibling passes on two streams, each traversal launch restricted to half
 	// of the wave slots, overlap one pass's tails and shading with the other's traversal.  Same per-sample results; the frame-buffer
 	// additions stay in step order through the event chain.
-	const uint64_t samples = frame.ownedPixels * MVRT_SPP_PER_STEP * (uint64_t)n;
+	const uint64_t samples = ( frame.masked ? frame.nActive : frame.ownedPixels ) * MVRT_SPP_PER_STEP * (uint64_t)n;
 	static const uint64_t splitMax = (uint64_t)mvrtKnob( "MVRT_SPLIT_SMALL_MAX", 40000000ll );
 	// ... but only when this pass would otherwise run ALONE: if the caller keeps stepping, or an earlier pass is still in flight, the
 	// passes already overlap each other and halving their grids only slows them (measured: 2.68 -> 2.99 ms per step at 16 steps)
@@ -726,7 +754,7 @@ int mvrt_pt::launchPass( const CameraPinhole* cams, int iteration, int nSteps, i
 	Slot& sl = slots[nextSlot];
 	lastSlot = nextSlot;
 	nextSlot = ( nextSlot + 1 ) % depth;
-	REQUIRE( sl.buf.cap >= frame.validOwnedPixels * MVRT_SPP_PER_STEP * nSteps, "internal: work buffers not allocated" );
+	REQUIRE( sl.buf.cap >= frame.activePixels() * MVRT_SPP_PER_STEP * nSteps, "internal: work buffers not allocated" );
 	if( sl.trace.ensure( intersector->oct.info.levels, 0 ) ) return 1;
 	sl.buf.dbgTasks = nullptr;
 	if( debugCapture )
@@ -754,7 +782,7 @@ int mvrt_pt::launchPass( const CameraPinhole* cams, int iteration, int nSteps, i
 	}
 	REQUIRE( !moments || frame.moments.p, "internal: moments buffer not allocated" );
 	int rc = launchPtStep( intersector->dev(), sl.trace.ws, hdri.dev, pmj.as<float2>(), cams, passFrame( iteration, nSteps, traceGridDiv ), sl.buf, frame.f32.as<float4>(), numCUs,
-						   profiling ? &prof : nullptr, run, after, aovs ? &aov : nullptr, moments ? frame.moments.as<float4>() : nullptr );
+						   profiling ? &prof : nullptr, run, after, aovs ? &aov : nullptr, moments ? frame.moments.as<float4>() : nullptr, frame.passList() );
 	if( rc ) return rc;
 	MVRT_HIP( hipEventRecord( sl.accumDone, run ) );
 	lastAccum = sl.accumDone;
@@ -965,6 +993,68 @@ MVRT_EXPORT int mvrt_pt_denoise( mvrt_pt* pt, void* stream, const mvrt_denoise_p
 	}
 	return 0;
 }
+// ---- adaptive sampling: the sample mask and the error mask ----------------------------------------------------------------------------------------
+MVRT_EXPORT int mvrt_pt_set_sample_mask( mvrt_pt* pt, void* stream, const uint8_t* maskDev, uint64_t* nActiveOut )
+{
+	REQUIRE( pt, "mvrt_pt_set_sample_mask: null argument" );
+	mvrt_pt::Frame& fr = pt->frame;
+	REQUIRE( fr.f32.p, "mvrt_pt_set_sample_mask: no frame buffer" );
+	if( pt->flush() ) return 1; // the pending steps run under the mask they were issued under
+	if( !maskDev )
+	{
+		fr.masked = false;
+		if( nActiveOut ) *nActiveOut = fr.validOwnedPixels;
+		return 0;
+	}
+	// built aside: a failure leaves the mask that is in force (or none) in force, and the steps in flight go on reading the list they were launched with
+	const uint64_t n = fr.validOwnedPixels;
+	DevBuf list, scratch;
+	const uint64_t rankBytes = ( n * 4 + 255 ) & ~(uint64_t)255, blockBytes = ( ( n / 256 + 8 ) * 4 + 255 ) & ~(uint64_t)255; // (+ padding: the scan reads whole 16-byte quads)
+	if( list.alloc( fr.ownedPixels * 4 ) || scratch.alloc( rankBytes + blockBytes + 4 ) ) return 1;
+	uint32_t* kept = (uint32_t*)( scratch.as<uint8_t>() + rankBytes + blockBytes );
+	uint32_t count = 0;
+	if( n ) // (a rank of a tile split may own nothing)
+	{
+		if( launchActiveList( maskDev, n, list.as<uint32_t>(), kept, scratch.as<uint32_t>(), (uint32_t*)( scratch.as<uint8_t>() + rankBytes ), (hipStream_t)stream ) ) return 1;
+		MVRT_HIP( hipMemcpyAsync( &count, kept, 4, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
+		MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) ); // launch sizes need the count, and the caller's array is free again
+	}
+	if( pt->drain() ) return 1; // the list in force is replaced: nothing reads it any more
+	if( count == n ) // every valid pixel is active, which IS no mask: the steps take the unmasked kernels, without the lookups through a list that says slot == pixel
+	{
+		fr.dropMask();
+		if( nActiveOut ) *nActiveOut = count;
+		return 0;
+	}
+	fr.activeList = std::move( list );
+	fr.nActive = count;
+	fr.masked = true;
+	if( nActiveOut ) *nActiveOut = count;
+	return 0;
+}
+MVRT_EXPORT uint64_t mvrt_pt_active_pixels( const mvrt_pt* pt ) { return pt && pt->frame.f32.p ? pt->frame.activePixels() : 0; }
+MVRT_EXPORT int mvrt_pt_error_mask( mvrt_pt* pt, void* stream, float threshold, float lumFloor, int minSamples, int maxSamples, uint8_t* maskDev, uint64_t* nActiveOut )
+{
+	REQUIRE( pt && maskDev, "mvrt_pt_error_mask: null argument" );
+	REQUIRE( threshold > 0.0f, "mvrt_pt_error_mask: threshold %g is not greater than 0", (double)threshold );
+	REQUIRE( lumFloor > 0.0f, "mvrt_pt_error_mask: lumFloor %g is not greater than 0", (double)lumFloor );
+	REQUIRE( minSamples >= 1, "mvrt_pt_error_mask: minSamples %d is less than 1", minSamples );
+	REQUIRE( maxSamples >= 0, "mvrt_pt_error_mask: maxSamples %d is negative (0 = no limit)", maxSamples );
+	REQUIRE( pt->moments, "mvrt_pt_error_mask: the moments are off (mvrt_pt_set_moments)" );
+	mvrt_pt::Frame& fr = pt->frame;
+	REQUIRE( fr.f32.p && fr.moments.p, "mvrt_pt_error_mask: no frame buffer" );
+	if( pt->join( (hipStream_t)stream ) ) return 1;
+	if( !fr.errorCount.p && fr.errorCount.alloc( 4 ) ) return 1;
+	if( launchErrorMask( fr.f32.as<float4>(), fr.moments.as<float4>(), fr.validOwnedPixels, fr.ownedPixels, threshold, lumFloor, minSamples, maxSamples, maskDev,
+						 fr.errorCount.as<uint32_t>(), (hipStream_t)stream ) )
+		return 1;
+	uint32_t count = 0;
+	MVRT_HIP( hipMemcpyAsync( &count, fr.errorCount.p, 4, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
+	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
+	if( nActiveOut ) *nActiveOut = count;
+	return 0;
+}
+
 MVRT_EXPORT float* mvrt_pt_denoised_dev( mvrt_pt* pt ) { return pt ? pt->frame.denoised.as<float>() : nullptr; }
 MVRT_EXPORT int mvrt_pt_read_denoised( mvrt_pt* pt, void* stream, float* rgbaHost )
 {

@@ -10,12 +10,18 @@ static MVRT_DI float lum3( float r, float g, float b ) { return ( 0.2126f * r + 
 // ---- moments: moments[p].x += sum of l, .y += sum of l * l over the 16 samples of each merged step ---------------------------------------------------
 // Reads the Ls* planes exactly as kPtAccumulate does (four 16-byte loads per plane, pixel and step) and adds in its order: per step the 16 samples ascending
 // from +0, the product l * l rounded before it is added, then the two partial sums onto the buffer, steps in issue order.  z and w are never written.
+static MVRT_DI uint64_t activePixel( uint64_t slot ) { return slot; }
+static MVRT_DI uint64_t activePixel( uint64_t slot, const uint32_t* active ) { return active[slot]; }
+// Under a sample mask: n = the active pixels, p = a slot of the active list, and the pixel's record is reached through the list as in kPtAccumulate.
+// ACTIVE: empty, or the list (one `const uint32_t*`); the unmasked instantiation compiles to the instructions the kernel had without the mask.
+template <class... ACTIVE>
 __global__ void __launch_bounds__( 256 ) kPtMoments( const float* __restrict__ Lsx, const float* __restrict__ Lsy, const float* __restrict__ Lsz, uint64_t n, int nSteps,
-													   float4* __restrict__ moments )
+													   float4* __restrict__ moments, ACTIVE... active )
 {
 	for( uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256 )
 	{
-		float4 v = moments[p];
+		const uint64_t px = sizeof...( ACTIVE ) ? (uint64_t)activePixel( p, active... ) : p;
+		float4 v = moments[px];
 		for( int b = 0; b < nSteps; b++ )
 		{
 			const uint64_t base = ( (uint64_t)b * n + p ) * MVRT_SPP_PER_STEP;
@@ -36,15 +42,52 @@ __global__ void __launch_bounds__( 256 ) kPtMoments( const float* __restrict__ L
 			v.x += s1;
 			v.y += s2;
 		}
-		moments[p] = v;
+		moments[px] = v;
 	}
 }
-int launchPtMoments( const PtBuffers& buf, uint64_t validOwnedPixels, int nSteps, float4* moments, int nCUs, hipStream_t stream )
+int launchPtMoments( const PtBuffers& buf, uint64_t validOwnedPixels, int nSteps, float4* moments, int nCUs, hipStream_t stream, const uint32_t* active )
 {
 	if( validOwnedPixels == 0 ) return 0;
 	uint32_t grid = divUp( validOwnedPixels, 256 );
 	if( nCUs > 0 && grid > (uint32_t)nCUs * 8u ) grid = (uint32_t)nCUs * 8u;
-	hipLaunchKernelGGL( kPtMoments, dim3( grid ), dim3( 256 ), 0, stream, buf.Lsx, buf.Lsy, buf.Lsz, validOwnedPixels, nSteps, moments );
+	if( active ) hipLaunchKernelGGL( kPtMoments<const uint32_t*>, dim3( grid ), dim3( 256 ), 0, stream, buf.Lsx, buf.Lsy, buf.Lsz, validOwnedPixels, nSteps, moments, active );
+	else hipLaunchKernelGGL( kPtMoments<>, dim3( grid ), dim3( 256 ), 0, stream, buf.Lsx, buf.Lsy, buf.Lsz, validOwnedPixels, nSteps, moments );
+	MVRT_HIP( hipGetLastError() );
+	return 0;
+}
+
+// ---- error mask (mvrt_pt_error_mask): which pixels have not converged ---------------------------------------------------------------------------------
+// A CONTRACT like the filter (include/mvrt.h "Adaptive sampling"): se = sqrt( var ) with the denoiser's var, active iff se > threshold * max( m1, lumFloor ),
+// fp32 in that order.  One lane per owned pixel, one byte each (padding 0); the ones are counted per wave with one atomic.
+__global__ void __launch_bounds__( 256 ) kErrorMask( const float4* __restrict__ fb, const float4* __restrict__ moments, uint64_t nValid, uint64_t nOwned, float threshold, float lumFloor,
+													   float minSamples, float maxSamples, uint8_t* __restrict__ mask, uint32_t* __restrict__ count )
+{
+	const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	bool on = false;
+	if( p < nValid )
+	{
+		const float n = fb[p].w;
+		if( n < minSamples ) on = true; // (n == 0 among them)
+		else if( maxSamples > 0.0f && n >= maxSamples ) on = false;
+		else
+		{
+			const float4 m4 = moments[p];
+			const float m1 = m4.x / n, m2 = m4.y / n;
+			const float var = smax( m2 - m1 * m1, 0.0f ) / smax( n - 1.0f, 1.0f );
+			const float se = sqrtf( var );
+			on = se > threshold * smax( m1, lumFloor );
+		}
+	}
+	if( p < nOwned ) mask[p] = on ? 1 : 0;
+	const unsigned long long b = __ballot( on );
+	if( ( threadIdx.x & 63u ) == 0 && b ) atomicAdd( count, (uint32_t)__popcll( b ) );
+}
+int launchErrorMask( const float4* frameBuffer, const float4* moments, uint64_t validOwnedPixels, uint64_t ownedPixels, float threshold, float lumFloor, int minSamples,
+					 int maxSamples, uint8_t* mask, uint32_t* countDev, hipStream_t stream )
+{
+	MVRT_HIP( hipMemsetAsync( countDev, 0, 4, stream ) );
+	hipLaunchKernelGGL( kErrorMask, dim3( divUp( ownedPixels, 256 ) ), dim3( 256 ), 0, stream, frameBuffer, moments, validOwnedPixels, ownedPixels, threshold, lumFloor, (float)minSamples,
+						(float)maxSamples, mask, countDev );
 	MVRT_HIP( hipGetLastError() );
 	return 0;
 }

@@ -435,8 +435,16 @@ MVRT_DI void decodeTask( const PtFrame& f, uint32_t task, uint32_t* step, uint32
 // number of PMJ dimensions consumed before the shading of depth k (voxKernel.cu:662-666,699-700,724,741)
 MVRT_DI int dimBase( int k, int hdriEnabled, int extraSamples ) { return 2 + k * ( ( hdriEnabled ? 2 : 0 ) + 1 ) + ( k > 0 ? extraSamples : 0 ); }
 
+// Sample mask (mvrt_pt_set_sample_mask): a pass restricted to the active pixels numbers its tasks over the ACTIVE LIST -- PtFrame::validOwnedPixels is the
+// number of active pixels and decodeTask's pixel is a slot of the list -- and the kernels that turn a task into a pixel look the owned pixel up here.  They
+// are instantiated twice; the unmasked instantiation keeps the kernel's arguments and compiles to the instructions it had without the mask.
+// The kernels take the list as a trailing parameter PACK (`ACTIVE... active`): empty for the unmasked instantiation, one `const uint32_t*` for the masked one.
+MVRT_DI uint32_t slotPixel( uint32_t slot ) { return slot; }
+MVRT_DI uint32_t slotPixel( uint32_t slot, const uint32_t* active ) { return active[slot]; }
+
 // ---- generate: camera samples -> primary rays (voxKernel.cu:635-667) -------------------------------
-__global__ void __launch_bounds__( 256 ) kPtGenerate( PtParams P )
+template <class... ACTIVE>
+__global__ void __launch_bounds__( 256 ) kPtGenerate( PtParams P, ACTIVE... active )
 {
 	const uint64_t n = P.frame.validOwnedPixels * MVRT_SPP_PER_STEP * P.frame.nSteps;
 	const PathSet& o = P.buf.set[0];
@@ -444,7 +452,7 @@ __global__ void __launch_bounds__( 256 ) kPtGenerate( PtParams P )
 	{
 		uint32_t step, localPixel, localSpp;
 		decodeTask( P.frame, (uint32_t)task, &step, &localPixel, &localSpp );
-		uint32_t pixelIdx = globalPixel( P.frame, localPixel );
+		uint32_t pixelIdx = globalPixel( P.frame, slotPixel( localPixel, active... ) );
 		int x = pixelIdx % P.frame.width;
 		int y = pixelIdx / P.frame.width;
 		uint32_t spp = ( P.frame.iteration + step ) * MVRT_SPP_PER_STEP + localSpp; // voxKernel.cu:642
@@ -717,8 +725,8 @@ MVRT_DI f3 voxelEmission( const SvoDev& s, uint32_t vIndex, bool withScale ) // 
 #ifndef MVRT_SHADE_WAVES
 #define MVRT_SHADE_WAVES 5 // waves per SIMD the shade kernel is register-budgeted for
 #endif
-template <int WAVES> // register budget: waves per SIMD the kernel is compiled for
-__global__ void __launch_bounds__( CBLOCK, WAVES ) kPtShade( PtParams P, int stage, int inSet )
+template <int WAVES, class... ACTIVE> // WAVES = register budget: waves per SIMD the kernel is compiled for
+__global__ void __launch_bounds__( CBLOCK, WAVES ) kPtShade( PtParams P, int stage, int inSet, ACTIVE... active )
 {
 	__shared__ uint32_t waveCnt[CBLOCK / WAVE];
 	const uint64_t n = P.buf.liveCount[stage];
@@ -805,7 +813,7 @@ __global__ void __launch_bounds__( CBLOCK, WAVES ) kPtShade( PtParams P, int sta
 			uint32_t step, localPixel, localSpp;
 			decodeTask( P.frame, task, &step, &localPixel, &localSpp );
 			const uint32_t spp = ( P.frame.iteration + step ) * MVRT_SPP_PER_STEP + localSpp;
-			const uint32_t stream = hashCombine2( 0u, globalPixel( P.frame, localPixel ) );
+			const uint32_t stream = hashCombine2( 0u, globalPixel( P.frame, slotPixel( localPixel, active... ) ) );
 			int dim = dimBase( stage, P.hdriEnabled, P.extraSamples );
 			const f3 R = rawReflectance( attr.x ); // :693
 			const f3 hitN = getHitN( nMajor, rd );				  // :694
@@ -857,12 +865,16 @@ __global__ void __launch_bounds__( CBLOCK, WAVES ) kPtShade( PtParams P, int sta
 
 // ---- accumulate: frameBuffer[p].xyz += sum of the 16 samples in ascending spp order, .w += 16 -------
 // (voxKernel.cu:763-774; the reference's LDS atomicAdd order is nondeterministic, ascending is ours)
-__global__ void __launch_bounds__( 256 ) kPtAccumulate( PtParams P, float4* __restrict__ fb )
+// Masked: one thread per slot of the active list.  The reads of Ls* are those of the unmasked kernel (slot order, coalesced); the 16-byte read-modify-write of
+// the pixel is scattered through the list, which ascends, so neighbouring lanes still touch neighbouring or identical cache lines.
+template <class... ACTIVE>
+__global__ void __launch_bounds__( 256 ) kPtAccumulate( PtParams P, float4* __restrict__ fb, ACTIVE... active )
 {
 	const uint64_t n = P.frame.validOwnedPixels;
 	for( uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256 )
 	{
-		float4 v = fb[p];
+		const uint64_t px = sizeof...( ACTIVE ) ? (uint64_t)slotPixel( (uint32_t)p, active... ) : p;
+		float4 v = fb[px];
 		for( int b = 0; b < P.frame.nSteps; b++ ) // merged steps are added one after the other, exactly as separate launches would
 		{
 			const uint64_t base = ( (uint64_t)b * n + p ) * MVRT_SPP_PER_STEP;
@@ -883,7 +895,7 @@ __global__ void __launch_bounds__( 256 ) kPtAccumulate( PtParams P, float4* __re
 			v.z += az;
 			v.w += (float)MVRT_SPP_PER_STEP;
 		}
-		fb[p] = v;
+		fb[px] = v;
 	}
 }
 
@@ -947,25 +959,35 @@ __global__ void __launch_bounds__( 256 ) kPtAovReduce( SvoDev svo, AovRecords r,
 	}
 }
 // the partial sums of a pass, added to the two buffers one merged step after the other (launched behind kPtAccumulate: same event chain, same order)
+// (masked: validOwnedPixels = the active pixels, the partial sums are indexed by slot and the two buffers through the list, as in kPtAccumulate)
+template <class... ACTIVE>
 __global__ void __launch_bounds__( 256 ) kPtAovAccumulate( uint64_t validOwnedPixels, int nSteps, const float4* __restrict__ partA, const float4* __restrict__ partN,
-															 float4* __restrict__ albedo, float4* __restrict__ normalDepth )
+															 float4* __restrict__ albedo, float4* __restrict__ normalDepth, ACTIVE... active )
 {
 	for( uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < validOwnedPixels; p += (uint64_t)gridDim.x * 256 )
 	{
-		float4 a = albedo[p], n = normalDepth[p];
+		const uint64_t px = sizeof...( ACTIVE ) ? (uint64_t)slotPixel( (uint32_t)p, active... ) : p;
+		float4 a = albedo[px], n = normalDepth[px];
 		for( int b = 0; b < nSteps; b++ )
 		{
 			const float4 pa = partA[(uint64_t)b * validOwnedPixels + p], pn = partN[(uint64_t)b * validOwnedPixels + p];
 			a.x += pa.x; a.y += pa.y; a.z += pa.z; a.w += pa.w;
 			n.x += pn.x; n.y += pn.y; n.z += pn.z; n.w += pn.w;
 		}
-		albedo[p] = a;
-		normalDepth[p] = n;
+		albedo[px] = a;
+		normalDepth[px] = n;
 	}
 }
 
+// The masked instantiations are launched from functions defined BEHIND launchPtStep: a kernel template is emitted where it is first used, so every kernel of the
+// unmasked path keeps the place in the code object that it has without the mask, and the masked ones follow them
+static void launchMaskedGenerate( int grid, hipStream_t stream, const PtParams& P, const uint32_t* active );
+static void launchMaskedShade( bool dense8, int grid, hipStream_t stream, const PtParams& P, int stage, int setIdx, const uint32_t* active );
+static void launchMaskedAccumulate( int grid, hipStream_t stream, const PtParams& P, float4* frameBuffer, const AovBuffers* aov, const uint32_t* active );
+
 int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hdri, const float2* pmj, const CameraPinhole* cams, const PtFrame& frame,
-				  const PtBuffers& buf, float4* frameBuffer, int nCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov, float4* moments )
+				  const PtBuffers& buf, float4* frameBuffer, int nCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov, float4* moments,
+				  const uint32_t* active )
 {
 	PtParams P;
 	P.svo = svo;
@@ -1001,7 +1023,8 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 #define PROF_END() if( prof ) prof->end( stream )
 
 	PROF_BEGIN( MVRT_K_OTHER );
-	hipLaunchKernelGGL( kPtGenerate, dim3( persistentGrid( nSamples, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, P );
+	if( active ) launchMaskedGenerate( persistentGrid( nSamples, 256, nCUs, 8 ), stream, P, active );
+	else hipLaunchKernelGGL( kPtGenerate<>, dim3( persistentGrid( nSamples, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, P );
 	PROF_END();
 
 	for( int stage = 0; stage <= MVRT_MAX_DEPTH; stage++ )
@@ -1072,7 +1095,9 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 			// that had to wait for a slot ran as a second, thin round -- most of what the 8-wave build seemed to gain.  5-wave build with 8 / 6 / 5 workgroups per CU:
 			// dragon 16.6 / 14.1 / 14.0 ms of shade time per 4 serial steps, cave 133.7 / 132.3 / 129.2
 			static const int bpc8 = (int)mvrtKnob( "MVRT_SHADE_BPC8", 8 ), bpc5 = (int)mvrtKnob( "MVRT_SHADE_BPC5", 5 );
-			if( ( dense >> stage ) & 1 )
+			const bool dense8 = ( ( dense >> stage ) & 1 ) != 0;
+			if( active ) launchMaskedShade( dense8, persistentGrid( nSamples, CBLOCK, nCUs, dense8 ? bpc8 : bpc5 ), stream, P, stage, setIdx, active );
+			else if( dense8 )
 				hipLaunchKernelGGL( kPtShade<8>, dim3( persistentGrid( nSamples, CBLOCK, nCUs, bpc8 ) ), dim3( CBLOCK ), 0, stream, P, stage, setIdx );
 			else
 				hipLaunchKernelGGL( kPtShade<MVRT_SHADE_WAVES>, dim3( persistentGrid( nSamples, CBLOCK, nCUs, bpc5 ) ), dim3( CBLOCK ), 0, stream, P, stage, setIdx );
@@ -1084,22 +1109,43 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 	// frame-buffer additions must happen in step order (fixed fp32 summation order): wait for the previous step's
 	if( accumulateAfter ) MVRT_HIP( hipStreamWaitEvent( stream, accumulateAfter, 0 ) );
 	PROF_BEGIN( MVRT_K_OTHER );
-	hipLaunchKernelGGL( kPtAccumulate, dim3( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, P, frameBuffer );
+	if( active ) launchMaskedAccumulate( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ), stream, P, frameBuffer, nullptr, active );
+	else hipLaunchKernelGGL( kPtAccumulate<>, dim3( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, P, frameBuffer );
 	PROF_END();
 	if( aov )
 	{
 		PROF_BEGIN( MVRT_K_OTHER );
-		hipLaunchKernelGGL( kPtAovAccumulate, dim3( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, frame.validOwnedPixels, frame.nSteps, aov->partA,
-							aov->partN, aov->albedo, aov->normalDepth );
+		if( active ) launchMaskedAccumulate( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ), stream, P, nullptr, aov, active );
+		else
+			hipLaunchKernelGGL( kPtAovAccumulate<>, dim3( persistentGrid( frame.validOwnedPixels, 256, nCUs, 8 ) ), dim3( 256 ), 0, stream, frame.validOwnedPixels, frame.nSteps, aov->partA,
+								aov->partN, aov->albedo, aov->normalDepth );
 		PROF_END();
 	}
 	if( moments ) // luminance moments (mvrt_pt_set_moments): the Ls* planes are complete until the next pass of this slot generates
 	{
 		PROF_BEGIN( MVRT_K_OTHER );
-		const int rc = launchPtMoments( buf, frame.validOwnedPixels, frame.nSteps, moments, nCUs, stream );
+		const int rc = launchPtMoments( buf, frame.validOwnedPixels, frame.nSteps, moments, nCUs, stream, active );
 		PROF_END();
 		if( rc ) return rc;
 	}
 	MVRT_HIP( hipGetLastError() );
 	return 0;
+}
+
+static void launchMaskedGenerate( int grid, hipStream_t stream, const PtParams& P, const uint32_t* active )
+{
+	hipLaunchKernelGGL( kPtGenerate<const uint32_t*>, dim3( grid ), dim3( 256 ), 0, stream, P, active );
+}
+static void launchMaskedShade( bool dense8, int grid, hipStream_t stream, const PtParams& P, int stage, int setIdx, const uint32_t* active )
+{
+	if( dense8 ) hipLaunchKernelGGL( ( kPtShade<8, const uint32_t*> ), dim3( grid ), dim3( CBLOCK ), 0, stream, P, stage, setIdx, active );
+	else hipLaunchKernelGGL( ( kPtShade<MVRT_SHADE_WAVES, const uint32_t*> ), dim3( grid ), dim3( CBLOCK ), 0, stream, P, stage, setIdx, active );
+}
+// frameBuffer: the frame-buffer addition; aov: that of the two feature buffers
+static void launchMaskedAccumulate( int grid, hipStream_t stream, const PtParams& P, float4* frameBuffer, const AovBuffers* aov, const uint32_t* active )
+{
+	if( frameBuffer ) hipLaunchKernelGGL( kPtAccumulate<const uint32_t*>, dim3( grid ), dim3( 256 ), 0, stream, P, frameBuffer, active );
+	if( aov )
+		hipLaunchKernelGGL( kPtAovAccumulate<const uint32_t*>, dim3( grid ), dim3( 256 ), 0, stream, P.frame.validOwnedPixels, P.frame.nSteps, aov->partA, aov->partN, aov->albedo,
+							aov->normalDepth, active );
 }

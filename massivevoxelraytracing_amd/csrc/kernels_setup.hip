@@ -395,3 +395,20 @@ int launchAssembleTiles( const float4* gathered, int tileCount, uint64_t rankStr
 	MVRT_HIP( hipGetLastError() );
 	return 0;
 }
+
+// ---- the active list of a sample mask (mvrt_pt_set_sample_mask) ---------------------------------------------------------------------------------------
+// the inverse of the ranks kRankFlags wrote: list[rank of i] = i for every kept i, which lists the kept items in ascending order
+__global__ void __launch_bounds__( 256 ) kListRanked( const uint32_t* __restrict__ rank, uint64_t n, uint32_t* __restrict__ list )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if( i >= n ) return;
+	const uint32_t r = rank[i];
+	if( r != 0xFFFFFFFFu ) list[r] = (uint32_t)i; // r < the number kept <= n: inside the list of n entries
+}
+int launchActiveList( const uint8_t* mask, uint64_t n, uint32_t* list, uint32_t* kept, uint32_t* rankScratch, uint32_t* blockScratch, hipStream_t stream )
+{
+	if( launchCompactIndices( mask, n, rankScratch, kept, blockScratch, stream ) ) return 1;
+	hipLaunchKernelGGL( kListRanked, dim3( divUp( n, 256 ) ), dim3( 256 ), 0, stream, rankScratch, n, list );
+	MVRT_HIP( hipGetLastError() );
+	return 0;
+}

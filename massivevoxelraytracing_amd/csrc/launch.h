@@ -75,6 +75,8 @@ int launchTraceBatch( const SvoDev& svo, const TraceWorkspace& ws, uint64_t n, c
 int launchRenderPrimary( const SvoDev& svo, const TraceWorkspace& ws, const CameraPinhole& cam, int W, int H, int showVertexColor, uchar4* rgba, float* t, int32_t* nMajor, uint32_t* vIndex,
 						 uint32_t* descents, hipStream_t stream );
 int launchCompactIndices( const uint8_t* keep, uint64_t n, uint32_t* dstIndex, uint32_t* kept, uint32_t* blockScratch, hipStream_t stream );
+// the indices i < n with mask[i] != 0, ascending, into list (n entries) and their number into *kept: launchCompactIndices (rankScratch: n entries) and its inverse
+int launchActiveList( const uint8_t* mask, uint64_t n, uint32_t* list, uint32_t* kept, uint32_t* rankScratch, uint32_t* blockScratch, hipStream_t stream );
 
 // one PathTracer::step().  `mark(class)` is called before/after each kernel when profiling is on.
 struct PtProfiler
@@ -90,13 +92,21 @@ struct AovBuffers
 	float4 *partA, *partN;
 	float4 *albedo, *normalDepth;
 };
+// active (mvrt_pt_set_sample_mask): the owned pixels this pass samples, ascending, frame.validOwnedPixels of them -- the pass numbers its tasks, Ls* and
+// partA / partN over the slots of this list; nullptr = every valid owned pixel, exactly the launches of a library without the mask.  It comes after everything
+// else and stays out of PtBuffers / PtParams for the reason given above.
 // aov == nullptr: exactly the launches of a library without feature buffers.  moments (mvrt_pt_set_moments; float4 per owned pixel like the frame buffer)
 // travels the same way: nullptr = off, no launch
 int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hdri, const float2* pmj, const CameraPinhole* cams /* frame.nSteps */, const PtFrame& frame, const PtBuffers& buf, float4* frameBuffer,
-				  int numCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov = nullptr, float4* moments = nullptr );
+				  int numCUs, PtProfiler* prof, hipStream_t stream, hipEvent_t accumulateAfter, const AovBuffers* aov = nullptr, float4* moments = nullptr,
+				  const uint32_t* active = nullptr );
 
 // kernels_denoise.hip: the luminance moments of a pass (behind kPtAccumulate, same stream) and the a-trous denoiser on full-frame buffers
-int launchPtMoments( const PtBuffers& buf, uint64_t validOwnedPixels, int nSteps, float4* moments, int numCUs, hipStream_t stream );
+int launchPtMoments( const PtBuffers& buf, uint64_t validOwnedPixels, int nSteps, float4* moments, int numCUs, hipStream_t stream, const uint32_t* active = nullptr );
+// mask[p] (one byte per owned pixel, padding 0) = 1 where the standard error of the mean luminance exceeds threshold * max( mean, lumFloor ) (mvrt.h,
+// mvrt_pt_error_mask); the ones are counted into *countDev (zeroed here).  Not synchronised.
+int launchErrorMask( const float4* frameBuffer, const float4* moments, uint64_t validOwnedPixels, uint64_t ownedPixels, float threshold, float lumFloor, int minSamples,
+					 int maxSamples, uint8_t* mask, uint32_t* countDev, hipStream_t stream );
 uint64_t denoiseScratchBytes( uint64_t nPixels );
 struct mvrt_denoise_params; // (mvrt.h)
 int launchDenoise( const float4* color, const float4* albedo, const float4* normalDepth, const float4* moments, int W, int H, const mvrt_denoise_params& params, float4* out, void* scratch,
