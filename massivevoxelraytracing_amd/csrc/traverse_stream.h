@@ -231,6 +231,8 @@ MVRT_DI uint32_t selU( lmask m, uint32_t a, uint32_t b ) // lane bit set ? a : b
 }
 #define MVRT_SELKK( m, K1, K0 ) ( { uint32_t r_; asm( "v_cndmask_b32 %0, " #K0 ", " #K1 ", %1" : "=v"( r_ ) : "s"( m ) ); r_; } )	   // bit ? K1 : K0
 #define MVRT_SELK( m, K1, b ) ( { uint32_t r_; asm( "v_cndmask_b32 %0, %1, " #K1 ", %2" : "=v"( r_ ) : "v"( b ), "s"( m ) ); r_; } ) // bit ? K1 : b
+// x + x + this lane's bit of m: shifts a lane mask into a lane integer, one add-with-carry per bit and no OR (the carry out goes to a scalar pair nobody reads)
+#define MVRT_SHIFT_IN( x, m ) ( { uint32_t r_; lmask c_; asm( "v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"( r_ ), "=s"( c_ ) : "v"( x ), "s"( m ) ); r_; } )
 // IEEE minimum of two NaN-free values as ONE v_min_f32 (fminf() makes the compiler quiet possible signalling NaNs first: a v_max x, x per operand)
 MVRT_DI float minF( float a, float b )
 {
@@ -253,6 +255,24 @@ MVRT_DI uint32_t activeLanes( lmask m )
 	uint32_t n;
 	asm( "s_bcnt1_i32_b64 %0, %1" : "=s"( n ) : "s"( m ) : "scc" );
 	return n;
+}
+// the exit times of child ci of a node (:382-386): per axis, upper half (bit set) -> keep the exit time, else the mid-plane.  v_bfe_i32 (0 / -1 from the bit, the bit
+// number an inline constant) + v_bfi_b32 per axis, all in ONE asm statement: after every asm statement whose result the next vector instruction may read the compiler
+// spends a wait state (a transcendental result would need one; these have no such hazard), so three statements cost up to three
+MVRT_DI void halveBox( uint32_t ci, float* tx1, float* ty1, float* tz1, float txM, float tyM, float tzM )
+{
+	uint32_t m;
+	asm( "v_bfe_i32 %3, %4, 0, 1\n\tv_bfi_b32 %0, %3, %0, %5\n\tv_bfe_i32 %3, %4, 1, 1\n\tv_bfi_b32 %1, %3, %1, %6\n\tv_bfe_i32 %3, %4, 2, 1\n\tv_bfi_b32 %2, %3, %2, %7"
+		 : "+v"( *tx1 ), "+v"( *ty1 ), "+v"( *tz1 ), "=&v"( m )
+		 : "v"( ci ), "v"( txM ), "v"( tyM ), "v"( tzM ) );
+}
+// byte offset of a child pointer of the embedded flavour, ( ( ref & 0xFFFFFF ) << 5 ) | at: mask first (v_bfe_u32 + v_lshl_or_b32, inline constants only).  The
+// compiler shifts first and masks with 0x1fffffe0, a literal that v_and_or_b32 cannot encode: one s_mov_b32 per descent to re-materialise it
+MVRT_DI uint32_t childOffset( uint32_t ref, uint32_t at )
+{
+	uint32_t r;
+	asm( "v_bfe_u32 %0, %1, 0, 24\n\tv_lshl_or_b32 %0, %0, 5, %2" : "=&v"( r ) : "v"( ref ), "v"( at ) );
+	return r;
 }
 typedef float v2f __attribute__( ( ext_vector_type( 2 ) ) );
 typedef uint32_t u4v __attribute__( ( ext_vector_type( 4 ) ) );
@@ -640,11 +660,12 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 							if( EMBED && hint != MVRT_NO_HINT && !( min3f( tx1, ty1, tz1 ) < 0.0f ) ) // (a box behind the origin: the root visit settles it)
 							{
 								// Start below the root: replay the walk down the hint's path (see the top of this file).  In a first visit with
-								// T = min( t1 ) >= 0 the candidates behind the origin are those ended by a NEGATIVE mid-plane event (kx, ky, kz of the
-								// step below; the "before the first exit" condition of a flip holds for every negative tM once T >= 0), and they are
-								// a prefix of the candidate order; so the first candidate that is not behind has bit a = ( tM_a < S ) | ( tM_a < 0 )
-								// = tM_a < max( S, 0 ).  If that octant is the hint's child it exists, the step would enter it (its exit is >= 0 by the
-								// same inequalities: T stays >= 0 level after level), and a later candidate exists iff an axis whose bit is clear flips
+								// T = min( t1 ) >= 0 the candidates behind the origin are those ended by a NEGATIVE mid-plane event (the "before the
+								// first exit" condition of a flip holds for every negative tM once T >= 0), and they are a prefix of the reference's
+								// candidate order; so the first candidate that is not behind has bit a = ( tM_a < S ) | ( tM_a < 0 ) = tM_a < max( S, 0 )
+								// -- the very octant the step below starts its candidate chain with (X, Y, Z there), computed here with the same
+								// operations.  If that octant is the hint's child it exists, the step would enter it (its exit is >= 0 by the same
+								// inequalities: T stays >= 0 level after level), and a later candidate exists iff an axis whose bit is clear flips
 								// before the first exit event (fX, fY, fZ of the step).
 								// Straight-line code: the level counter is a compile-time constant (the loop is unrolled, at most MVRT_HINT_MAX = 7
 								// levels = ring slots: a refilled lane's ring is empty, so nothing is ever evicted here), the node references of the
@@ -753,8 +774,9 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 		// to no further descent.  Here ONE step settles a whole visit: the order in which the ray leaves the octants of a node is a
 		// pure function of the three mid-plane times and the three exit times -- walk the events (time, axis) in lexicographic order
 		// (the reference's min + "x first, then y" tie rule) until the first exit event; every earlier mid-plane event of a not yet
-		// passed axis is a flip -- so the up to four candidates, their existence in the node's mask and the "behind the origin" test
-		// are evaluated side by side, the first valid one is entered, and the node is pushed only if a later VALID candidate exists.
+		// passed axis is a flip -- so the up to four candidates and their existence in the node's mask are evaluated side by side (the candidates
+		// behind the origin are masked out in the tree flavour and never built in the others), the first valid one is entered, and the node is
+		// pushed only if a later VALID candidate exists.
 		// All of it is 1-bit logic: the compares produce 64-bit lane masks and the combinatorics run on the scalar unit.
 		//
 		// REVISIT of a popped node (flavours that keep the path).  The exit times of a popped node come back bit for bit and its level with them, so the revisit
@@ -763,11 +785,11 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 		// (`resume` = i_j), the candidates already dealt with are exactly those with i_k <= resume, and candidate k stays eligible iff i_k > resume: a first visit
 		// (resume = -1) filters nothing.  Where candidates coincide (no flip: i1 == i0; two flips: i2 == i3) the later one has n_k clear and is never valid, so a
 		// tie cannot admit the child already taken a second time.
-		// Behind-the-origin prefix (b0..b2): candidate j was entered, so it was not behind (b_j clear; for j == 3 nothing follows).  The candidates behind the
-		// origin are a prefix of the chain, so b_k is clear for every k > j as well: on the eligible candidates the test is vacuous, which is what a revisit that
-		// restarts from candidate j sees (its remaining flips are the events after a non-negative one: none is negative).  Eligible and valid are thus the same
-		// candidates, in the same order, as for the restart: the same child is entered, and the push -- "two or more valid candidates" -- fires under the same
-		// condition.  A replayed ancestor of the hint was left through the origin's octant, i_j with j = the number of negative flips, so b_j is clear there too.
+		// Behind the origin: these flavours' chain starts at the first candidate that is not behind the origin (see "BEHIND THE ORIGIN" in the step), on a first visit
+		// and on a revisit alike, so the candidate j a node was left through is one of the chain and the filter keeps what follows it.  Eligible and valid are the
+		// same candidates, in the same order, as for a revisit that restarts from candidate j (its remaining flips are the events after a non-negative one: none
+		// is negative): the same child is entered, and the push -- "two or more valid candidates" -- fires under the same condition.  A replayed ancestor of the
+		// hint was left through the origin's octant, which is this chain's i0.
 		// The resume point needs no storage: the child a stacked node was left through is in `path`, in the three bits above the node's own prefix.
 		// Tree flavour (no path): the restart, with the candidate in the sign bits of the stacked exit times and bit-sliced in three SGPR pairs (+ a "first visit"
 		// mask) while the loop runs.
@@ -799,16 +821,28 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
 			const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
 			const float tyM = tMyz.x, tzM = tMyz.y;
-			// octant the node is entered in (:342-348); tree flavour: or the candidate a popped node resumes with
-			// (cmX / cmY / cmZ carry bits only for lanes whose mFirst bit is clear: kept so by the loop tail)
-			const lmask X = TREE ? ( mFirst & __ballot( txM < S ) ) | cmX : __ballot( txM < S );
-			const lmask Y = TREE ? ( mFirst & __ballot( tyM < S ) ) | cmY : __ballot( tyM < S );
-			const lmask Z = TREE ? ( mFirst & __ballot( tzM < S ) ) | cmZ : __ballot( tzM < S );
+			// octant the candidate chain starts in.  Tree flavour: the octant the node is entered in (:342-348), or the candidate a popped node resumes with
+			// (cmX / cmY / cmZ carry bits only for lanes whose mFirst bit is clear: kept so by the loop tail).  Flavours that keep the path: the first candidate
+			// that is NOT BEHIND THE ORIGIN, bit a = tM_a < max( S, 0 ) -- see "behind the origin" below
+			const float S0 = TREE ? S : fmaxf( S, 0.0f );
+			const lmask X = TREE ? ( mFirst & __ballot( txM < S ) ) | cmX : __ballot( txM < S0 );
+			const lmask Y = TREE ? ( mFirst & __ballot( tyM < S ) ) | cmY : __ballot( tyM < S0 );
+			const lmask Z = TREE ? ( mFirst & __ballot( tzM < S ) ) | cmZ : __ballot( tzM < S0 );
 			// first exit event = lexicographic minimum of (t1, axis); flips = mid-plane events of unset axes that come before it, i.e.
 			// before EVERY exit event (an axis' own exit never precedes its mid-plane: tM <= t1).  (tM_a, a) < (t1_b, b) is "tM_a <= t1_b" for
 			// a < b and "tM_a < t1_b" for a > b
-			const float mXY = minF( tx1, ty1 ), mYZ = minF( ty1, tz1 );
-			const float T = minF( mXY, tz1 );
+			// (one asm statement for the three: after every asm statement whose result the next vector instruction reads the compiler spends a wait state, since a
+			// transcendental result would need one; v_min_f32 has no such hazard)
+			// (tree flavour: it waits for HBM, not for issue slots, and measured 0.3 % slower on the 8192^3 stress octree with the merged statements and the add-with-carry
+			// assembly below: it keeps the separate statements and the selects)
+			float mXY, mYZ, T;
+			if( TREE )
+			{
+				mXY = minF( tx1, ty1 ), mYZ = minF( ty1, tz1 );
+				T = minF( mXY, tz1 );
+			}
+			else
+				asm( "v_min_f32 %0, %3, %4\n\tv_min_f32 %1, %4, %5\n\tv_min_f32 %2, %0, %5" : "=&v"( mXY ), "=&v"( mYZ ), "=&v"( T ) : "v"( tx1 ), "v"( ty1 ), "v"( tz1 ) );
 			const lmask fX = ~X & __ballot( txM <= mYZ );
 			const lmask fY = ~Y & __ballot( tyM < tx1 ) & __ballot( tyM <= tz1 );
 			const lmask fZ = ~Z & __ballot( tzM < mXY );
@@ -823,8 +857,9 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			// child indices of the four candidates (mirrored space), nested: each adds the axis of one flip.  With two flips the third
 			// candidate is already the last (i2 == i3); with three, it is the last minus the last flip
 			// (asm selects = one v_cndmask on an SGPR mask; written as nested ?: the compiler turns these chains into branches)
-			const uint32_t i0 = MVRT_SELKK( X, 1, 0 ) | MVRT_SELKK( Y, 2, 0 ) | MVRT_SELKK( Z, 4, 0 );
-			const uint32_t i3 = i0 | MVRT_SELKK( fX, 1, 0 ) | MVRT_SELKK( fY, 2, 0 ) | MVRT_SELKK( fZ, 4, 0 );
+			// (flavours that keep the path: the three bits through add-with-carry, x + x + bit, one instruction per bit and no OR)
+			const uint32_t i0 = TREE ? MVRT_SELKK( X, 1, 0 ) | MVRT_SELKK( Y, 2, 0 ) | MVRT_SELKK( Z, 4, 0 ) : MVRT_SHIFT_IN( MVRT_SHIFT_IN( MVRT_SELKK( Z, 1, 0 ), Y ), X );
+			const uint32_t i3 = i0 | ( TREE ? MVRT_SELKK( fX, 1, 0 ) | MVRT_SELKK( fY, 2, 0 ) | MVRT_SELKK( fZ, 4, 0 ) : MVRT_SHIFT_IN( MVRT_SHIFT_IN( MVRT_SELKK( fZ, 1, 0 ), fY ), fX ) );
 			const uint32_t i1 = i0 | MVRT_SELK( aX, 1, MVRT_SELK( aY, 2, MVRT_SELKK( aZ, 4, 0 ) ) );
 			const uint32_t i2 = i3 ^ MVRT_SELK( zX, 1, MVRT_SELK( zY, 2, MVRT_SELKK( zZ, 4, 0 ) ) );
 			// e_k: candidate k exists in the node's mask -- and, with the path at hand, is eligible (i_k > resume) in the same compare: m = 0 / -1 from the mask bit,
@@ -835,20 +870,33 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 		   : __ballot( (int)( ( EMBED ? bitMask( node, ( i ) ^ vMaskHi ) : bitMask( nodeMask, ( i ) ^ vMask ) ) ^ ( i ) ) < (int)nres ) )
 			const lmask e0 = MVRT_EXISTS( i0 ), e1 = MVRT_EXISTS( i1 ), e2 = MVRT_EXISTS( i2 ), e3 = MVRT_EXISTS( i3 );
 #undef MVRT_EXISTS
-			// a candidate is behind the origin when the event that ends it is negative (:373).  Events are visited in time order, so the
-			// candidates behind the origin are a prefix: candidate k is behind iff more than k flips are negative, all of them iff the
-			// exit is
-			const lmask kx = fX & __ballot( txM < 0.0f ), ky = fY & __ballot( tyM < 0.0f ), kz = fZ & __ballot( tzM < 0.0f );
-			const lmask b0 = kx | ky | kz, b1 = ( kx & ky ) | ( ( kx | ky ) & kz ), b2 = kx & ky & kz;
+			// BEHIND THE ORIGIN.  A candidate is behind the origin when the event that ends it is negative (:373).  Events are visited in time order, so the
+			// candidates behind the origin are a prefix of the reference's chain: candidate k is behind iff more than k flips are negative, all of them iff the
+			// exit is (T < 0: `inner` below).
+			// Tree flavour: that prefix is masked out (b0..b2).
+			// Flavours that keep the path never build it: their chain STARTS at the first candidate that is not behind.  That candidate is the entry octant plus the
+			// axes of the negative flips (the flips are ordered by time, so the negative ones are the first), bit a = ( tM_a < S ) | ( tM_a < 0 and a flips ).  With
+			// T >= 0 "a flips" may be dropped: an axis outside the entry octant whose mid-plane is negative and does NOT come before the first exit would make that
+			// exit negative.  So bit a = tM_a < max( S, 0 ) = X, Y, Z above (one v_max, no compare against zero, no prefix logic); the flips of the remaining axes
+			// are the non-negative flips of the reference's chain in their order, i3 is the same last candidate, and i0..i3 are exactly the reference's candidates
+			// nNeg..3 (nNeg = number of negative flips) followed by repeats of the last, which have n_k clear.  Valid candidates, their order and their number are
+			// what the masked chain gave; with T < 0 nothing is entered whatever the chain says.  The resume point of a revisit is a candidate that was entered,
+			// hence one of this chain, and the filter i_k > resume reads it as before.  (tM = -0.0 is not negative for either compare.)
+			lmask b0 = 0ull, b1 = 0ull, b2 = 0ull;
+			if( TREE )
+			{
+				const lmask kx = fX & __ballot( txM < 0.0f ), ky = fY & __ballot( tyM < 0.0f ), kz = fZ & __ballot( tzM < 0.0f );
+				b0 = kx | ky | kz, b1 = ( kx & ky ) | ( ( kx | ky ) & kz ), b2 = kx & ky & kz;
+			}
 			const lmask mLeaf = act & __ballot( node == MVRT_LEAF ); // :322
 			const lmask inner = act & ~mLeaf & ~__ballot( T < 0.0f );
 			// tree flavour: candidate 0 of a popped node is the child it was left through: already done
-			const lmask v0 = ( TREE ? mFirst & e0 : e0 ) & ~b0, v1 = n1 & e1 & ~b1, v2 = n2 & e2 & ~b2, v3 = n3 & e3;
+			const lmask v0 = TREE ? mFirst & e0 & ~b0 : e0, v1 = n1 & e1 & ~b1, v2 = n2 & e2 & ~b2, v3 = n3 & e3;
 			// push only if a later VALID candidate exists (the reference: any later candidate; measured +8.6 %), i.e. if at least two of the four are valid
 			const lmask vA = v0 | v1, vB = v0 & v1, vC = v2 | v3, vD = v2 & v3;
 			const lmask mGo = inner & ( vA | vC );
 			const lmask mPush = inner & ( vB | vD | ( vA & vC ) );
-			const lmask mHit = mLeaf & __ballot( 0.0f < S ); // :324
+			const lmask mHit = mLeaf & __ballot( 0.0f < S0 ); // :324 (0 < S iff 0 < max( S, 0 ))
 			const lmask mPop = act & ~mHit & ~mGo;
 			// the entered candidate = the first valid one
 			const uint32_t ci = selU( v0, i0, selU( v1, i1, selU( v2, i2, i3 ) ) );
@@ -867,7 +915,11 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 					const uint32_t L = 31u - __builtin_clz( pending );
 					const uint32_t bit = 1u << L;
 					u4v ev;
-					asm volatile( "ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"( ev ) : "v"( ringAddr + ( ( L & ( MVRT_RING - 1 ) ) << 10 ) ) : "memory" );
+					// (the slot number masked FIRST, then v_lshl_add_u32: inline constants only, in an asm statement of their own.  Written as ( L & 7 ) << 10 the compiler shifts first and needs the mask
+					// 0x1c00 in a scalar register, re-materialised in every iteration.  Embedded flavour only: the others index their mask rings with the same slot number)
+					uint32_t slotAddr = ringAddr + ( ( L & ( MVRT_RING - 1 ) ) << 10 );
+					if( EMBED ) asm( "v_and_b32 %0, %3, %1\n\tv_lshl_add_u32 %0, %0, 10, %2" : "=&v"( slotAddr ) : "v"( L ), "v"( ringAddr ), "n"( MVRT_RING - 1 ) );
+					asm volatile( "ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"( ev ) : "v"( slotAddr ) : "memory" );
 					popped = make_uint4( ev.x, ev.y, ev.z, ev.w );
 					uint32_t poppedMask2 = 0;
 					if( !EMBED ) poppedMask = myRingMask[( L & ( MVRT_RING - 1 ) ) * 64];
@@ -895,7 +947,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 					{
 						// the path down to the child of level L the node was left through, that child's index (mirrored: the candidate) as the resume point, then the
 						// path of the node itself
-						path >>= 3u * ( level - L ) - 3u;
+						path >>= __umul24( level - L, 3u ) - 3u; // (24-bit multiply-add, one full-rate instruction: as 3u * x - 3u it feeds a 64-bit shift and becomes v_mad_u64_u32)
 						nres = ~( ( (uint32_t)path ^ vMask ) & 7u );
 						path >>= 3u;
 					}
@@ -947,7 +999,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 				if( EMBED )
 				{
 					// :381 -- 32-bit byte offset from the uniform node base (global_load with an SGPR base, no 64-bit VALU adds)
-					node = *(const uint32_t*)( (const char*)kids + ( ( ( node & 0xFFFFFFu ) << 5 ) | ( childIndex << 2 ) ) );
+					node = *(const uint32_t*)( (const char*)kids + childOffset( node, childIndex << 2 ) );
 				}
 				else if( TREE )
 				{
@@ -961,9 +1013,14 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 				}
 				descents++;
 				if( !TREE ) path = ( path << 3 ) | childIndex;
-				tx1 = mvrt_u2f( bfi( bitMask( ci, 0 ), mvrt_f2u( tx1 ), mvrt_f2u( txM ) ) ); // :382-386: upper half -> keep the exit time, else the mid-plane
-				ty1 = mvrt_u2f( bfi( bitMask( ci, 1 ), mvrt_f2u( ty1 ), mvrt_f2u( tyM ) ) );
-				tz1 = mvrt_u2f( bfi( bitMask( ci, 2 ), mvrt_f2u( tz1 ), mvrt_f2u( tzM ) ) );
+				if( TREE )
+				{
+					tx1 = mvrt_u2f( bfi( bitMask( ci, 0 ), mvrt_f2u( tx1 ), mvrt_f2u( txM ) ) ); // :382-386: upper half -> keep the exit time, else the mid-plane
+					ty1 = mvrt_u2f( bfi( bitMask( ci, 1 ), mvrt_f2u( ty1 ), mvrt_f2u( tyM ) ) );
+					tz1 = mvrt_u2f( bfi( bitMask( ci, 2 ), mvrt_f2u( tz1 ), mvrt_f2u( tzM ) ) );
+				}
+				else
+					halveBox( ci, &tx1, &ty1, &tz1, txM, tyM, tzM ); // :382-386
 				level++;
 				nres = 0u; // a first visit
 			}

@@ -1,0 +1,208 @@
+"""Candidates behind the ray origin in the node visit (csrc/traverse_stream.h).  The flavours that keep the voxel path no longer build the
+candidates that lie behind the origin and mask them out: their candidate chain starts at the first child that is not behind, octant bit
+a = tM_a < max(S, 0), and the revisit filter (i_k > resume) reads that shorter chain.  The tree flavour keeps its masks.  The shapes at which
+the two can part, each against the CPU oracle element for element (t, nMajor, vIndex, descents; frame buffer and counters for the path
+tracer), for build flags 0, 2 and 3:
+  * origins inside the grid with every mirror mask (negative mid-plane times from the root down, first visits and revisits),
+  * origins ON mid-planes (mid-plane times of exactly zero at several levels: "tM < 0" and a sign-bit reading would part here),
+  * origins inside an occupied voxel and in the cell layer right behind a wall, pointing away (whole chains behind the origin),
+  * the path tracer with its camera inside a closed scene (secondary rays replay hints from origins inside nodes)."""
+import numpy as np
+import pytest
+
+import deep_scenes as D
+from common import hdr_bytes
+from test_gpu_parity import assert_hits_equal
+from test_gpu_resume_point import voxel_scene
+
+pytestmark = pytest.mark.gpu
+
+MAXF = np.float32(3.402823466e38)
+FLAGS = [0, 2, 3]  # embedded masks / plain indices / tree (bricks): flavours 0, 1, 2
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import oracle
+    return oracle
+
+
+@pytest.fixture(scope="module")
+def mv():
+    import massivevoxelraytracing_amd as m
+    m.lib()
+    return m
+
+
+def build(mv, s, flags):
+    svo = mv.IntersectorOctreeGPU()
+    svo.build_voxels(s.xyz, s.attrs, origin=s.origin, dps=s.dps, gridRes=s.res, flags=flags)
+    assert svo.info().flavour == (2 if flags == 3 else int(flags == 2))
+    return svo
+
+
+def signs(k):
+    """(n, 3) of +-1 from the three low bits of k: bit a set = negative along axis a"""
+    return np.stack([np.where(k & 1, -1.0, 1.0), np.where(k & 2, -1.0, 1.0), np.where(k & 4, -1.0, 1.0)], -1).astype(np.float32)
+
+
+# ---- origins inside the grid, every mirror mask ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def inside64():
+    rng = np.random.default_rng(6412)
+    s = voxel_scene(rng.integers(0, 64, size=(5300, 3)), 64)  # ~2 % of 64^3
+    n = 8192
+    ro = (0.001 + 0.998 * rng.random((n, 3))).astype(np.float32)  # strictly inside the unit cube
+    mag = (0.05 + rng.random((n, 3))).astype(np.float32)
+    k = np.arange(n) % 8  # the eight sign combinations in equal shares
+    sh = (np.arange(n) % 5 == 0).astype(np.uint8)
+    return s, ro, (mag * signs(k)).astype(np.float32), sh, k
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_origins_inside_every_mirror_mask(mv, O, inside64, flags):
+    s, ro, rd, sh, k = inside64
+    assert ((ro > 0) & (ro < 1)).all() and (np.bincount(k, minlength=8) == len(k) // 8).all()
+    # from the inputs alone: mirrored by its direction signs (an axis with a negative direction is reflected about the grid's centre), a ray that starts in the
+    # upper half of the root along an axis has passed that axis' mid-plane: a negative mid-plane time at the root visit, so a candidate behind the origin
+    mirrored = np.where(rd < 0, np.float32(1.0) - ro, ro)
+    upper = (mirrored > 0.5).any(1)
+    print("rays that start in an upper half of the root after mirroring: %.3f" % upper.mean())
+    assert upper.mean() >= 0.8
+    sc = D.oracle_scene(O, s, flags)
+    want = sc.trace(ro, rd, sh, threads=8, want_descents=True)
+    # pops from the oracle's descent counts, as tests/test_gpu_resume_point.py::test_all_mirror_masks: a descent that is not on the path to the hit voxel is undone by
+    # a pop, one pop undoes at most `levels` of them, so a hit after W wasted descents has popped twice if W > levels; a miss ends with a pop from the empty stack,
+    # which resumes nothing: twice if W > 2 * levels
+    levels = 6
+    hit = want["t"] != MAXF
+    wasted = want["descents"].astype(np.int64) - np.where(hit, levels, 0)
+    popped_twice = np.where(hit, wasted > levels, wasted > 2 * levels)
+    print("rays that pop at least twice: %.3f, hits %.3f, mean descents %.1f" % (popped_twice.mean(), hit.mean(), want["descents"].mean()))
+    assert popped_twice.mean() >= 1.0 / 3.0
+    for m in range(8):  # every mirror mask on its own
+        assert popped_twice[k == m].sum() > 200, m
+    assert_hits_equal(want, build(mv, s, flags).intersect(ro, rd, sh, want_descents=True))
+
+
+# ---- origins on mid-planes ------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def midplane32():
+    res = 32
+    g = np.stack(np.meshgrid(np.arange(res), np.arange(res), np.arange(res), indexing="ij"), -1).reshape(-1, 3)
+    s = voxel_scene(g[g.sum(1) % 2 == 0], res)  # the checkerboard of tests/test_gpu_resume_point.py::checker32
+    dirs = []
+    for ax in range(3):  # axis-parallel, both signs
+        for sg in (1.0, -1.0):
+            d = np.zeros(3)
+            d[ax] = sg
+            dirs.append(d)
+    for a, b in ((0, 1), (0, 2), (1, 2)):  # face diagonals, every sign
+        for sa in (1.0, -1.0):
+            for sb in (1.0, -1.0):
+                d = np.zeros(3)
+                d[a], d[b] = sa, sb
+                dirs.append(d)
+    k8 = np.arange(8)
+    dirs += list(signs(k8).astype(np.float64))  # space diagonals, every sign
+    # (the directions above with a zero component take the exact-emulation path for irregular rays; the space diagonals and these dyadic slopes, every sign, are the
+    # ones whose zero mid-plane times meet the node-visit step)
+    for base in ((1.0, 1.0, 0.5), (1.0, 0.5, 0.25), (2.0, 1.0, 1.0), (0.5, 1.0, 2.0)):
+        dirs += list(signs(k8).astype(np.float64) * np.array(base))
+    dirs = np.array(dirs, np.float32)
+    assert len(dirs) == 6 + 12 + 8 + 32
+    rng = np.random.default_rng(3212)
+    n = 5800
+    d = dirs[np.arange(n) % len(dirs)]
+    # origins ON multiples of half a cell, strictly inside the grid: lattice points, cell centres, face and edge midpoints.  Every such coordinate is the mid-plane
+    # of the nodes of some level (and a node boundary below it): mid-plane times of exactly zero, at several levels at once where the coordinates are round
+    ro = (rng.integers(1, 2 * res, size=(n, 3)) / np.float32(2 * res)).astype(np.float32)
+    ro[: n // 4] = (rng.integers(1, 8, size=(n // 4, 3)) / np.float32(8)).astype(np.float32)  # a quarter on the mid-planes of the top three levels
+    sh = (np.arange(n) % 4 == 0).astype(np.uint8)
+    return s, ro, d.copy(), sh
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_origins_on_mid_planes(mv, O, midplane32, flags):
+    s, ro, rd, sh = midplane32
+    assert ((ro > 0) & (ro < 1)).all() and (np.modf(ro * 64)[0] == 0).all()
+    sc = D.oracle_scene(O, s, flags)
+    want = sc.trace(ro, rd, sh, threads=8, want_descents=True)
+    hit = want["t"] != MAXF
+    regular = (rd != 0).all(1)
+    print("hits %.3f (rays without a zero component: %.3f), mean descents %.1f" % (hit.mean(), hit[regular].mean(), want["descents"].mean()))
+    assert hit[regular].mean() > 0.2 and (want["descents"][regular] > 5).mean() > 0.2  # walks that go down, and past dead ends
+    assert_hits_equal(want, build(mv, s, flags).intersect(ro, rd, sh, want_descents=True))
+
+
+# ---- inside an occupied voxel, and one voxel behind a wall ------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def block64():
+    res, lo, hi = 64, 28, 36  # a solid 8^3 block across the root's mid-planes: eight 4^3 corners, one per octant of the root
+    g = np.stack(np.meshgrid(np.arange(lo, hi), np.arange(lo, hi), np.arange(lo, hi), indexing="ij"), -1).reshape(-1, 3)
+    s = voxel_scene(g, res)
+    rng = np.random.default_rng(6436)
+    n_in = 4096
+    ro = [(lo + 8.0 * rng.random((n_in, 3))) / res]  # inside the block = inside an occupied voxel
+    rd = [(0.05 + rng.random((n_in, 3))) * signs(np.arange(n_in) % 8)]
+    away = [np.zeros(n_in, bool)]
+    n_face = 512
+    for ax in range(3):  # the cell layer directly outside each of the six faces, pointing away from the block
+        for side in (0, 1):
+            p = lo + 8.0 * rng.random((n_face, 3))
+            p[:, ax] = (hi + rng.random(n_face)) if side else (lo - 1.0 + rng.random(n_face))
+            d = (0.05 + rng.random((n_face, 3))) * signs(np.arange(n_face) % 8)
+            d[:, ax] = np.abs(d[:, ax]) * (1.0 if side else -1.0)
+            ro.append(p / res)
+            rd.append(d)
+            away.append(np.ones(n_face, bool))
+    ro, rd, away = np.concatenate(ro).astype(np.float32), np.concatenate(rd).astype(np.float32), np.concatenate(away)
+    sh = (np.arange(len(ro)) % 5 == 0).astype(np.uint8)
+    return s, ro, rd, sh, away
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_inside_a_voxel_and_behind_a_wall(mv, O, block64, flags):
+    s, ro, rd, sh, away = block64
+    sc = D.oracle_scene(O, s, flags)
+    want = sc.trace(ro, rd, sh, threads=8, want_descents=True)
+    hit = want["t"] != MAXF
+    print("hits: from inside the block %.3f, from behind a wall %.3f; mean descents %.1f / %.1f" % (hit[~away].mean(), hit[away].mean(), want["descents"][~away].mean(), want["descents"][away].mean()))
+    # one voxel behind the wall and pointing away: everything the walk could enter next to the origin is behind it, nothing is hit -- and the walk did go down (it
+    # starts in nodes that hold the block) and came back up
+    assert not hit[away].any() and (want["descents"][away] >= 1).mean() > 0.9
+    # from inside the block the voxel the origin lies in is no hit (S <= 0), the next one on the way out is (0 < S): all but the rays that leave through the
+    # block's surface at once
+    assert hit[~away].mean() > 0.8 and (want["t"][hit] > 0).all()
+    assert_hits_equal(want, build(mv, s, flags).intersect(ro, rd, sh, want_descents=True))
+
+
+# ---- path tracer, camera inside a closed scene ----------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def cave_frame(O):
+    from massivevoxelraytracing_amd import scenes
+    res, w, h = 128, 48, 27
+    v, c, e = scenes.SCENES["cave"](1.0)
+    origin, dps = scenes.bounding_grid(v, res)
+    sc = O.build_scene_from_triangles(v.reshape(-1, 9), res, c.reshape(-1, 9), e.reshape(-1, 9), origin=origin, dps=dps)
+    rgba, hw, hh = O.decode_rgbe(hdr_bytes())
+    cam = scenes.cave_camera(sc.origin, sc.origin + np.float32(res) * sc.dps)
+    fb, _, cnt = sc.render_pt(O.HDRI(rgba, hw, hh, rgba, hw, hh, math_mode=1), cam, w, h, 0, math_mode=1, threads=8)
+    return sc, (rgba, hw, hh), cam, w, h, fb, cnt
+
+
+@pytest.mark.parametrize("hints", [True, False])
+def test_path_tracer_camera_inside_closed_scene(mv, cave_frame, hints):
+    sc, (rgba, hw, hh), cam, w, h, fb, cnt = cave_frame
+    assert cnt["rays"] >= 8 * cnt["samples"]  # a closed room: nearly every bounce hits, so the secondary rays start on voxels, inside nodes, level after level
+    pt = mv.PathTracer()
+    pt.setup(None)
+    pt.resizeFrameBufferIfNeeded(None, w, h)
+    pt.loadHDRIPixels(None, rgba, hw, hh, rgba, hw, hh)
+    pt.set_origin_hints(hints)
+    pt.m_intersectorOctreeGPU.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission)
+    pt.step(None, cam)
+    assert np.array_equal(pt.read_framebuffer()[: w * h], fb)
+    st = pt.stats()
+    for key in ("rays", "descents", "shadowDescents", "hits"):
+        assert st[key] == cnt[key], key

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Scan the gfx950 ISA of kernels_rt.hip for a hazard the compiler cannot pad because the reader sits in inline asm:
 on gfx940+ a VALU instruction that writes an SGPR (v_cmp into an SGPR pair / vcc, v_readfirstlane ...) must be followed by 2 wait
-states before a VALU instruction reads that SGPR (here: the asm v_cndmask_b32 selects, recognisable by their missing _e32/_e64
-suffix).  Exit code 1 if a suspicious pair is found.   usage: tools/check_asm_hazards.py [file.s]  (compiles the ISA if no file)"""
+states before a VALU instruction reads that SGPR (here: the asm v_cndmask_b32 selects and the asm v_addc_co_u32 that shift a lane mask
+into a lane integer through the carry in, recognisable by their missing _e32/_e64 suffix).  Exit code 1 if a suspicious pair is found.   usage: tools/check_asm_hazards.py [file.s]  (compiles the ISA if no file)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1:
@@ -46,11 +46,11 @@ def valu_sgpr_writes(p):
 
 bad = n = 0
 for k, l in enumerate(ins):
-    m = re.match(r"v_cndmask_b32 (\S+), (\S+), (\S+), (s\[\d+:\d+\]|vcc)$", l)
+    m = re.match(r"v_cndmask_b32 (\S+), (\S+), (\S+), (s\[\d+:\d+\]|vcc)$", l) or re.match(r"v_addc_co_u32 (\S+), (\S+), (\S+), (\S+), (s\[\d+:\d+\]|vcc)$", l)
     if not m:
         continue
     n += 1
-    mask = sgprs(m.group(4))
+    mask = sgprs(m.groups()[-1])  # the select mask / the carry in
     for back in (1, 2):
         p = ins[k - back]
         if p.startswith("v_") and valu_sgpr_writes(p) & mask:  # any overlap with the mask pair
@@ -58,5 +58,5 @@ for k, l in enumerate(ins):
             print("HAZARD?", p, " ->", l)
 # (the scan is linear: a select that is the target of a branch is checked against the instructions that precede it in the text, not against the
 # branch's source block -- every asm select of traverse_stream.h sits in straight-line code behind SALU-produced masks)
-print("asm v_cndmask selects: %d, suspicious producer within 2 instructions: %d" % (n, bad))
+print("asm v_cndmask selects and v_addc shifts: %d, suspicious producer within 2 instructions: %d" % (n, bad))
 sys.exit(1 if bad else 0)
