@@ -1,7 +1,7 @@
 // voxel_mesh -- the reference voxelizer's "Save As Mesh" (voxMesh.cpp:111-219) without the GUI: voxelize a Wavefront .obj on the GPU and write the exposed
 // faces of the voxel set as a PLY quad mesh, one colour per face from its voxel.
 //
-//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill] [--ao [samples] [--ao-radius voxels]]
+//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill | --exterior] [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -11,6 +11,9 @@
 // With and without --no-weld; not with --merge / --merge-any: the bake is per face and a rectangle has no single value.
 // --fill: the empty cells enclosed by the voxel shell become white voxels before the surface is extracted (mvrt_svo_fill_enclosed), so the inner side of the
 // shell, which no outside ray can see, is not written; a line reports the voxels before and after and the cell and region counts.  With every other flag.
+// --exterior: the same faces as --fill writes, without touching the octree: the faces that look into an enclosed cell are dropped from the masks
+// (mvrt_svo_surface_exterior_masks) and the mesh is extracted from those (mvrt_svo_surface_*_masked); a line reports the faces before and after.  With every
+// other flag except --fill: one or the other.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <cstdio>
 #include <cstdlib>
@@ -22,7 +25,7 @@
 
 int main( int argc, char** argv )
 {
-	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false, fill = false;
+	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false, fill = false, exterior = false;
 	int aoSamples = 64;
 	float aoRadiusVoxels = 8.0f;
 	std::vector<const char*> pos;
@@ -33,6 +36,7 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--merge-any" ) ) merge = mergeAny = true;
 		else if( !std::strcmp( argv[i], "--conservative" ) ) conservative = true;
 		else if( !std::strcmp( argv[i], "--fill" ) ) fill = true;
+		else if( !std::strcmp( argv[i], "--exterior" ) ) exterior = true;
 		else if( !std::strcmp( argv[i], "--ao" ) )
 		{
 			ao = true;
@@ -43,14 +47,20 @@ int main( int argc, char** argv )
 	}
 	if( pos.size() != 3 )
 	{
-		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill] [--ao [samples] [--ao-radius voxels]]\n"
+		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill | --exterior] [--ao [samples] [--ao-radius voxels]]\n"
 					 "  --fill       fill the empty cells the voxel shell encloses (white voxels) before the surface is extracted\n"
+					 "  --exterior   drop the faces that look into an enclosed cell instead; the octree stays as built.  Not with --fill\n"
 					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
 					 "               --ao-radius voxels (default 8); not with --merge / --merge-any\n"
 					 "  --no-weld    four vertices of its own per face instead of shared ones\n"
 					 "  --merge      merge coplanar faces of equal colour and emission into rectangles\n"
 					 "  --merge-any  merge whatever the attributes; a rectangle takes the colour of its anchor voxel\n" );
 		return pos.empty() ? 0 : 2;
+	}
+	if( fill && exterior )
+	{
+		std::fprintf( stderr, "voxel_mesh: --exterior cannot be combined with --fill: one or the other (both write the same faces)\n" );
+		return 2;
 	}
 	if( ao && merge )
 	{
@@ -92,13 +102,28 @@ int main( int argc, char** argv )
 	std::vector<uint32_t> indices, faceVoxel;
 	std::vector<uint8_t> faceDir;
 	uint64_t nFaces = 0;
+	std::vector<uint8_t> masks; // --exterior: the face set of every call below
+	if( exterior )
+	{
+		uint64_t nHidden = 0;
+		const uint64_t nExterior = svo.surfaceExteriorMasks( masks, &nHidden, stream );
+		std::printf( "exterior: faces %llu -> %llu, %llu look into an enclosed cell\n", (unsigned long long)( nExterior + nHidden ), (unsigned long long)nExterior,
+					 (unsigned long long)nHidden );
+	}
+	const uint32_t mergeFlags = ( mergeAny ? MVRT_SURFACE_MERGE_ANY_ATTRIBUTE : 0u ) | ( weld ? MVRT_SURFACE_MERGE_WELD : 0u );
 	if( merge )
 	{
 		std::vector<uint32_t> rectSize;
-		nFaces = svo.surfaceMerged( ( mergeAny ? MVRT_SURFACE_MERGE_ANY_ATTRIBUTE : 0u ) | ( weld ? MVRT_SURFACE_MERGE_WELD : 0u ), points, indices, faceVoxel, faceDir, rectSize, stream );
+		nFaces = exterior ? svo.surfaceMergedMasked( masks, mergeFlags, points, indices, faceVoxel, faceDir, rectSize, stream )
+						  : svo.surfaceMerged( mergeFlags, points, indices, faceVoxel, faceDir, rectSize, stream );
 	}
 	else if( weld )
-		svo.surfaceMesh( points, indices, faceVoxel, faceDir, stream );
+	{
+		if( exterior ) svo.surfaceMeshMasked( masks, points, indices, faceVoxel, faceDir, stream );
+		else svo.surfaceMesh( points, indices, faceVoxel, faceDir, stream );
+	}
+	else if( exterior )
+		svo.surfaceQuadsMasked( masks, faceVoxel, faceDir, points, stream );
 	else
 		svo.surfaceQuads( faceVoxel, faceDir, points, stream );
 	if( !weld ) // four corners of its own per face or rectangle
@@ -117,7 +142,8 @@ int main( int argc, char** argv )
 		std::vector<uint32_t> aoVoxel;
 		std::vector<uint8_t> aoDir;
 		std::vector<uint16_t> open;
-		svo.surfaceAo( aoSamples, aoRadiusVoxels * dps, aoVoxel, aoDir, open, stream );
+		if( exterior ) svo.surfaceAoMasked( masks, aoSamples, aoRadiusVoxels * dps, aoVoxel, aoDir, open, stream );
+		else svo.surfaceAo( aoSamples, aoRadiusVoxels * dps, aoVoxel, aoDir, open, stream );
 		if( aoVoxel != faceVoxel || aoDir != faceDir )
 		{
 			std::fprintf( stderr, "voxel_mesh: the face list of the bake differs from the mesh's\n" );

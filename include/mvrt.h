@@ -216,6 +216,43 @@ int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* x
  * handle, and numberOfVoxels + nCells >= 2^32 - 1 (the message names the count).  nFilledOut may be NULL. */
 int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8] /* VoxelAttirb, NULL = white, no emission */, uint64_t* nFilledOut, void* stream );
 
+/* Exterior-only surface extraction without touching the octree, and the three extraction calls on face masks the caller supplies (new; the reference has
+ * none).  Definitions:
+ *   - Exterior mask of a voxel: one byte, directions d = 0..5 as in mvrt_svo_surface_masks (0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X).  Bit d is set when the
+ *     neighbour cell in direction d is outside the grid, or is empty and NOT an enclosed cell in the sense of mvrt_svo_enclosed_cells above (6-connectivity;
+ *     exterior = the component holds a cell with a coordinate equal to 0 or gridRes - 1).  Bits 6-7 are 0.
+ *   - (E1) It is the mask of mvrt_svo_surface_masks with the bits that look into an enclosed cell cleared.
+ *   - (E2) It is the mask of mvrt_svo_surface_masks the same voxel has after mvrt_svo_fill_enclosed; a filled cell itself has no exposed face.
+ *   - A shell nested inside another shell's cavity has no exterior face at all.  In a closed scene -- a room, a tunnel: everything inside the outer walls is
+ *     enclosed -- only the outside of the block has exterior faces, exactly as the fill would make such a scene solid.
+ *   - The result is a property of the voxel set alone: unique and independent of any processing order.
+ * mvrt_svo_surface_exterior_masks follows the rules of mvrt_svo_surface_quads word for word: every octree this library built or edited is accepted, in every
+ * flavour; an upload is refused ("keeps no Morton codes": it works after one mvrt_svo_rebuild), an empty handle too ("no octree"), both before any GPU work.  The
+ * handle is never modified: no voxel is inserted, every vIndex stays.  The call blocks.  masksDev: numberOfVoxels bytes in vIndex order, NULL = counts only.
+ * *nFacesOut = the sum of the popcounts of the exterior masks, *nHiddenOut = the faces of mvrt_svo_surface_masks minus those; either may be NULL.  Counts are
+ * 64-bit.  gridRes up to 2^21.  A failed allocation of scratch returns an error, leaves the octree whole, leaks nothing and has written nothing to masksDev. */
+int mvrt_svo_surface_exterior_masks( const mvrt_svo* svo, uint8_t* masksDev /* numberOfVoxels bytes in vIndex order, NULL = counts only */, uint64_t* nFacesOut,
+									 uint64_t* nHiddenOut /* plain faces - exterior faces */, void* stream );
+/* mvrt_svo_surface_quads / _mesh / _merged on a face set the caller supplies.  Each behaves exactly like its namesake -- handles, refusals, blocking, NULL
+ * outputs, the sizing call, capacities, counts, order, corners, positions, the weld and the merge rule -- except that the faces are the set bits 0..5 of
+ * masksDev: numberOfVoxels bytes in vIndex order, e.g. those of mvrt_svo_surface_exterior_masks, of mvrt_svo_surface_masks (the namesake's output, byte for
+ * byte), or any selection of the caller's: one direction only, a clip region.
+ *   - The masks are taken as given: a set bit whose neighbour cell is in fact occupied still yields its face.  Bits 6 and 7 are ignored.  masksDev is only read.
+ *   - masksDev == NULL is refused on the host ("null masksDev"), like a null handle, before any GPU work.
+ *   - All outputs NULL is the sizing call: *nFacesOut = the number of set bits 0..5 of the given masks.  All-zero masks are a success with 0 faces, nothing written.
+ *   - mvrt_svo_surface_merged_masked takes the two flags of mvrt_svo_surface_merged; unknown bits are refused as there, and indicesDev / verticesDev need
+ *     MVRT_SURFACE_MERGE_WELD as there.  The rectangles depend only on the given faces and their voxels' attributes.
+ *   - Masks belong to the voxel set they were made for.  After mvrt_svo_edit_voxels, mvrt_svo_fill_enclosed or mvrt_svo_rebuild the vIndex order may have
+ *     changed: stale masks are not detected, they are the caller's business.
+ * mvrt_svo_surface_ao needs no counterpart: it takes a face list already, so the faces of a _masked call go straight in. */
+int mvrt_svo_surface_quads_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev,
+								   uint64_t* nFacesOut, void* stream );
+int mvrt_svo_surface_mesh_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev,
+								  uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream );
+int mvrt_svo_surface_merged_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev,
+									uint8_t* rectDirDev, uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut,
+									uint64_t* nRectsOut, uint64_t* nVerticesOut, void* stream );
+
 /* Adopt an SVO built elsewhere (e.g. IntersectorOctree::buildDAGReference on the CPU, IntersectorOctree.hpp:
  * 224-231): nodes in the reference's 68-byte layout, root last.  embeddedMask = 0 selects the variant where
  * the mask is fetched from the node (voxCommon.hpp:353-356; required above 0xFFFFFF nodes). */

@@ -276,6 +276,116 @@ struct IntersectorOctreeGPU
 		return nf;
 	}
 
+	// exterior-only masks and the three extraction calls on face masks the caller supplies (mvrt_svo_surface_exterior_masks / mvrt_svo_surface_*_masked; semantics in
+	// mvrt.h): the masks of surfaceMasks without the bits that look into an enclosed cell, the octree untouched; and surfaceQuads / surfaceMesh / surfaceMerged
+	// whose faces are the set bits 0..5 of numberOfVoxels mask bytes, taken as given.  Device-pointer forms; masksDev of surfaceExteriorMasks may be nullptr
+	// (counts only); returns the exterior faces, *nHidden = the faces of surfaceMasks minus those
+	uint64_t surfaceExteriorMasks( uint8_t* masksDev, uint64_t* nHidden, void* stream ) const
+	{
+		uint64_t nFaces = 0;
+		check( mvrt_svo_surface_exterior_masks( m_handle, masksDev, &nFaces, nHidden, stream ), "IntersectorOctreeGPU::surfaceExteriorMasks" );
+		return nFaces;
+	}
+	uint64_t surfaceQuadsMasked( const uint8_t* masksDev, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, void* stream ) const
+	{
+		uint64_t nFaces = 0;
+		check( mvrt_svo_surface_quads_masked( m_handle, masksDev, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, &nFaces, stream ), "IntersectorOctreeGPU::surfaceQuadsMasked" );
+		return nFaces;
+	}
+	void surfaceMeshMasked( const uint8_t* masksDev, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
+							float* verticesDev, uint64_t* nFaces, uint64_t* nVertices, void* stream ) const
+	{
+		check( mvrt_svo_surface_mesh_masked( m_handle, masksDev, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFaces, nVertices, stream ),
+			   "IntersectorOctreeGPU::surfaceMeshMasked" );
+	}
+	void surfaceMergedMasked( const uint8_t* masksDev, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev,
+							  uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFaces, uint64_t* nRects, uint64_t* nVertices,
+							  void* stream ) const
+	{
+		check( mvrt_svo_surface_merged_masked( m_handle, masksDev, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev,
+											   nFaces, nRects, nVertices, stream ),
+			   "IntersectorOctreeGPU::surfaceMergedMasked" );
+	}
+	// host-vector forms, like their namesakes; `masks` holds numberOfVoxels bytes
+	uint64_t surfaceExteriorMasks( std::vector<uint8_t>& masks, uint64_t* nHidden, void* stream ) const
+	{
+		masks.resize( m_numberOfVoxels );
+		Staged m( nullptr, masks.size(), stream );
+		const uint64_t nFaces = surfaceExteriorMasks( (uint8_t*)m.p, nHidden, stream );
+		fetch( masks, m, stream );
+		return nFaces;
+	}
+	void surfaceQuadsMasked( const std::vector<uint8_t>& masks, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<float>& positions /* 12 per face */,
+							 void* stream ) const
+	{
+		Staged m( masks.data(), masks.size(), stream );
+		const uint64_t n = surfaceQuadsMasked( (const uint8_t*)m.p, 0, nullptr, nullptr, nullptr, stream );
+		faceVoxel.resize( n );
+		faceDir.resize( n );
+		positions.resize( n * 12 );
+		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), p( nullptr, n * 48, stream );
+		surfaceQuadsMasked( (const uint8_t*)m.p, n, (uint32_t*)v.p, (uint8_t*)d.p, (float*)p.p, stream );
+		fetch( faceVoxel, v, stream );
+		fetch( faceDir, d, stream );
+		fetch( positions, p, stream );
+	}
+	void surfaceMeshMasked( const std::vector<uint8_t>& masks, std::vector<float>& vertices /* 3 per vertex */, std::vector<uint32_t>& indices /* 4 per face */,
+							std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, void* stream ) const
+	{
+		Staged m( masks.data(), masks.size(), stream );
+		uint64_t nf = 0, nv = 0;
+		surfaceMeshMasked( (const uint8_t*)m.p, 0, 0, nullptr, nullptr, nullptr, nullptr, &nf, &nv, stream );
+		vertices.resize( nv * 3 );
+		indices.resize( nf * 4 );
+		faceVoxel.resize( nf );
+		faceDir.resize( nf );
+		Staged x( nullptr, nv * 12, stream ), i( nullptr, nf * 16, stream ), v( nullptr, nf * 4, stream ), d( nullptr, nf, stream );
+		surfaceMeshMasked( (const uint8_t*)m.p, nf, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)i.p, (float*)x.p, &nf, &nv, stream );
+		fetch( vertices, x, stream );
+		fetch( indices, i, stream );
+		fetch( faceVoxel, v, stream );
+		fetch( faceDir, d, stream );
+	}
+	uint64_t surfaceMergedMasked( const std::vector<uint8_t>& masks, uint32_t flags, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& rectVoxel,
+								  std::vector<uint8_t>& rectDir, std::vector<uint32_t>& rectSize /* 2 per rectangle */, void* stream ) const
+	{
+		Staged m( masks.data(), masks.size(), stream );
+		const bool weld = ( flags & MVRT_SURFACE_MERGE_WELD ) != 0;
+		uint64_t nf = 0, nr = 0, nv = 0;
+		surfaceMergedMasked( (const uint8_t*)m.p, flags, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nf, &nr, &nv, stream );
+		const uint64_t points = weld ? nv : nr * 4;
+		vertices.resize( points * 3 );
+		indices.resize( weld ? nr * 4 : 0 );
+		rectVoxel.resize( nr );
+		rectDir.resize( nr );
+		rectSize.resize( nr * 2 );
+		Staged x( nullptr, points * 12, stream ), i( nullptr, indices.size() * 4, stream ), v( nullptr, nr * 4, stream ), d( nullptr, nr, stream ), s( nullptr, nr * 8, stream );
+		surfaceMergedMasked( (const uint8_t*)m.p, flags, nr, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)s.p, weld ? nullptr : (float*)x.p, weld ? (uint32_t*)i.p : nullptr,
+							 weld ? (float*)x.p : nullptr, &nf, &nr, &nv, stream );
+		fetch( vertices, x, stream );
+		fetch( indices, i, stream );
+		fetch( rectVoxel, v, stream );
+		fetch( rectDir, d, stream );
+		fetch( rectSize, s, stream );
+		return nf;
+	}
+	// the faces of surfaceQuadsMasked with their occlusion (surfaceAo below takes any face list)
+	void surfaceAoMasked( const std::vector<uint8_t>& masks, int samples, float radius, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<uint16_t>& open,
+						  void* stream ) const
+	{
+		Staged m( masks.data(), masks.size(), stream );
+		const uint64_t n = surfaceQuadsMasked( (const uint8_t*)m.p, 0, nullptr, nullptr, nullptr, stream );
+		faceVoxel.resize( n );
+		faceDir.resize( n );
+		open.resize( n );
+		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), o( nullptr, n * 2, stream );
+		surfaceQuadsMasked( (const uint8_t*)m.p, n, (uint32_t*)v.p, (uint8_t*)d.p, nullptr, stream );
+		surfaceAo( n, (const uint32_t*)v.p, (const uint8_t*)d.p, samples, radius, (uint16_t*)o.p, stream );
+		fetch( faceVoxel, v, stream );
+		fetch( faceDir, d, stream );
+		fetch( open, o, stream );
+	}
+
 	// batch form of the device method intersect() (:243-251): SoA device arrays
 	void intersect( uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz, const uint8_t* isShadowRay, float* t,
 					int32_t* nMajor, uint32_t* vIndex, void* stream ) const

@@ -85,6 +85,10 @@ SIGNATURES = {
     "mvrt_svo_surface_quads": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_mesh": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_merged": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_exterior_masks": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_quads_masked": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_mesh_masked": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_surface_merged_masked": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_enclosed_cells": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_fill_enclosed": (_i32, [_vp, _vp, _vp, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
@@ -441,50 +445,92 @@ class IntersectorOctreeGPU:
         n = self.surface_masks_device(masks, stream)
         return masks.to_host(), n
 
-    def surface_quads_device(self, face_capacity=0, faceVoxel=None, faceDir=None, positions=None, stream=None):
-        """mvrt_svo_surface_quads into caller device arrays (any may be None; all None = the sizing call); returns nFaces.  On MvrtError nothing was written."""
+    def surface_exterior_masks_device(self, masks_dev=None, stream=None):
+        """mvrt_svo_surface_exterior_masks into a caller's device array of numberOfVoxels bytes (None = counts only); returns (nFaces, nHidden): the exterior
+        faces and the faces of surface_masks that look into an enclosed cell.  The octree is not modified."""
+        nf, nh = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_surface_exterior_masks(self._h, _dev_ptr(masks_dev), C.byref(nf), C.byref(nh), stream))
+        return nf.value, nh.value
+
+    def surface_exterior_masks(self, stream=None):
+        """mvrt_svo_surface_exterior_masks -> (masks (numberOfVoxels,) uint8 in vIndex order, nFaces, nHidden): the masks of surface_masks without the bits that
+        look into an enclosed cell -- the masks the same voxels have after fill_enclosed"""
+        masks = DeviceArray(self.info().numberOfVoxels, np.uint8)
+        nf, nh = self.surface_exterior_masks_device(masks, stream)
+        return masks.to_host(), nf, nh
+
+    @staticmethod
+    def _given_masks(masks):
+        """masks= of the surface calls: a numpy uint8 array goes to the device, a device array is passed on"""
+        return DeviceArray.from_host(np.ascontiguousarray(masks, np.uint8)) if isinstance(masks, np.ndarray) else masks
+
+    def surface_quads_device(self, face_capacity=0, faceVoxel=None, faceDir=None, positions=None, stream=None, *, masks=None):
+        """mvrt_svo_surface_quads into caller device arrays (any may be None; all None = the sizing call); returns nFaces.  On MvrtError nothing was written.
+        masks (numberOfVoxels uint8, numpy or device): mvrt_svo_surface_quads_masked, the faces are the set bits 0..5 of the masks as given."""
         n = C.c_uint64(0)
-        _check(lib().mvrt_svo_surface_quads(self._h, int(face_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(positions), C.byref(n), stream))
+        if masks is None:
+            _check(lib().mvrt_svo_surface_quads(self._h, int(face_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(positions), C.byref(n), stream))
+        else:
+            m = self._given_masks(masks)
+            _check(lib().mvrt_svo_surface_quads_masked(self._h, _dev_ptr(m), int(face_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(positions), C.byref(n), stream))
         return n.value
 
-    def surface_quads(self, stream=None):
-        """the exposed faces as unwelded quads: {faceVoxel (n,) uint32 vIndex, faceDir (n,) uint8, positions (n, 4, 3) float32}, faces by vIndex then direction"""
-        n = self.surface_quads_device(stream=stream)
+    def surface_quads(self, stream=None, *, masks=None):
+        """the exposed faces as unwelded quads: {faceVoxel (n,) uint32 vIndex, faceDir (n,) uint8, positions (n, 4, 3) float32}, faces by vIndex then direction;
+        masks: the faces of the given masks instead (surface_quads_device)"""
+        masks = None if masks is None else self._given_masks(masks)
+        n = self.surface_quads_device(stream=stream, masks=masks)
         fv, fd, pos = DeviceArray(n, np.uint32), DeviceArray(n, np.uint8), DeviceArray((n, 4, 3), np.float32)
-        self.surface_quads_device(n, fv, fd, pos, stream)
+        self.surface_quads_device(n, fv, fd, pos, stream, masks=masks)
         return {"faceVoxel": fv.to_host(), "faceDir": fd.to_host(), "positions": pos.to_host()}
 
-    def surface_mesh_device(self, face_capacity=0, vertex_capacity=0, faceVoxel=None, faceDir=None, indices=None, vertices=None, stream=None):
-        """mvrt_svo_surface_mesh into caller device arrays (any may be None; all None = the sizing call); returns (nFaces, nVertices)"""
+    def surface_mesh_device(self, face_capacity=0, vertex_capacity=0, faceVoxel=None, faceDir=None, indices=None, vertices=None, stream=None, *, masks=None):
+        """mvrt_svo_surface_mesh into caller device arrays (any may be None; all None = the sizing call); returns (nFaces, nVertices).
+        masks: mvrt_svo_surface_mesh_masked (surface_quads_device)"""
         nf, nv = C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_surface_mesh(self._h, int(face_capacity), int(vertex_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(indices), _dev_ptr(vertices),
-                                           C.byref(nf), C.byref(nv), stream))
+        if masks is None:
+            _check(lib().mvrt_svo_surface_mesh(self._h, int(face_capacity), int(vertex_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(indices), _dev_ptr(vertices),
+                                               C.byref(nf), C.byref(nv), stream))
+        else:
+            m = self._given_masks(masks)
+            _check(lib().mvrt_svo_surface_mesh_masked(self._h, _dev_ptr(m), int(face_capacity), int(vertex_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(indices),
+                                                      _dev_ptr(vertices), C.byref(nf), C.byref(nv), stream))
         return nf.value, nv.value
 
-    def surface_mesh(self, stream=None):
-        """the exposed faces over shared vertices: {vertices (m, 3) float32 in corner-key order, indices (n, 4) uint32, faceVoxel (n,), faceDir (n,)}"""
-        nf, nv = self.surface_mesh_device(stream=stream)
+    def surface_mesh(self, stream=None, *, masks=None):
+        """the exposed faces over shared vertices: {vertices (m, 3) float32 in corner-key order, indices (n, 4) uint32, faceVoxel (n,), faceDir (n,)};
+        masks: the faces of the given masks instead (surface_quads_device)"""
+        masks = None if masks is None else self._given_masks(masks)
+        nf, nv = self.surface_mesh_device(stream=stream, masks=masks)
         fv, fd, idx, vtx = DeviceArray(nf, np.uint32), DeviceArray(nf, np.uint8), DeviceArray((nf, 4), np.uint32), DeviceArray((nv, 3), np.float32)
-        self.surface_mesh_device(nf, nv, fv, fd, idx, vtx, stream)
+        self.surface_mesh_device(nf, nv, fv, fd, idx, vtx, stream, masks=masks)
         return {"vertices": vtx.to_host(), "indices": idx.to_host(), "faceVoxel": fv.to_host(), "faceDir": fd.to_host()}
 
     def surface_merged_device(self, flags=0, rect_capacity=0, vertex_capacity=0, rectVoxel=None, rectDir=None, rectSize=None, positions=None, indices=None, vertices=None,
-                              stream=None):
+                              stream=None, *, masks=None):
         """mvrt_svo_surface_merged into caller device arrays (any may be None; all None = the sizing call); returns (nFaces, nRects, nVertices).
-        flags: SURFACE_MERGE_ANY_ATTRIBUTE | SURFACE_MERGE_WELD; indices / vertices need the weld flag.  On MvrtError nothing was written."""
+        flags: SURFACE_MERGE_ANY_ATTRIBUTE | SURFACE_MERGE_WELD; indices / vertices need the weld flag.  On MvrtError nothing was written.
+        masks: mvrt_svo_surface_merged_masked (surface_quads_device)"""
         nf, nr, nv = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_surface_merged(self._h, int(flags), int(rect_capacity), int(vertex_capacity), _dev_ptr(rectVoxel), _dev_ptr(rectDir), _dev_ptr(rectSize),
-                                             _dev_ptr(positions), _dev_ptr(indices), _dev_ptr(vertices), C.byref(nf), C.byref(nr), C.byref(nv), stream))
+        out = [_dev_ptr(a) for a in (rectVoxel, rectDir, rectSize, positions, indices, vertices)]
+        if masks is None:
+            _check(lib().mvrt_svo_surface_merged(self._h, int(flags), int(rect_capacity), int(vertex_capacity), *out, C.byref(nf), C.byref(nr), C.byref(nv), stream))
+        else:
+            m = self._given_masks(masks)
+            _check(lib().mvrt_svo_surface_merged_masked(self._h, _dev_ptr(m), int(flags), int(rect_capacity), int(vertex_capacity), *out, C.byref(nf), C.byref(nr), C.byref(nv),
+                                                        stream))
         return nf.value, nr.value, nv.value
 
-    def surface_merged(self, flags=0, stream=None):
+    def surface_merged(self, flags=0, stream=None, *, masks=None):
         """the exposed faces merged into rectangles, ascending (direction, plane, u0, v0): {nFaces, rectVoxel (n,) uint32 the anchor's vIndex, rectDir (n,) uint8,
-        rectSize (n, 2) uint32 (du, dv), positions (n, 4, 3) float32}; with SURFACE_MERGE_WELD also {vertices (m, 3) float32, indices (n, 4) uint32}"""
-        nf, nr, nv = self.surface_merged_device(flags, stream=stream)
+        rectSize (n, 2) uint32 (du, dv), positions (n, 4, 3) float32}; with SURFACE_MERGE_WELD also {vertices (m, 3) float32, indices (n, 4) uint32};
+        masks: the faces of the given masks instead (surface_quads_device)"""
+        masks = None if masks is None else self._given_masks(masks)
+        nf, nr, nv = self.surface_merged_device(flags, stream=stream, masks=masks)
         weld = bool(flags & self.SURFACE_MERGE_WELD)
         rv, rd, rs, pos = DeviceArray(nr, np.uint32), DeviceArray(nr, np.uint8), DeviceArray((nr, 2), np.uint32), DeviceArray((nr, 4, 3), np.float32)
         idx, vtx = (DeviceArray((nr, 4), np.uint32), DeviceArray((nv, 3), np.float32)) if weld else (None, None)
-        self.surface_merged_device(flags, nr, nv, rv, rd, rs, pos, idx, vtx, stream)
+        self.surface_merged_device(flags, nr, nv, rv, rd, rs, pos, idx, vtx, stream, masks=masks)
         out = {"nFaces": nf, "rectVoxel": rv.to_host(), "rectDir": rd.to_host(), "rectSize": rs.to_host(), "positions": pos.to_host()}
         if weld:
             out.update(vertices=vtx.to_host(), indices=idx.to_host())
@@ -593,13 +639,15 @@ class IntersectorOctreeGPU:
         On MvrtError nothing was written."""
         _check(lib().mvrt_svo_surface_ao(self._h, int(nFaces), _dev_ptr(faceVoxel), _dev_ptr(faceDir), int(samples), float(np.float32(radius)), _dev_ptr(open), stream))
 
-    def surface_ao(self, samples=64, radius=None, stream=None):
-        """the exposed faces with their baked occlusion: {faceVoxel (n,) uint32, faceDir (n,) uint8, open (n,) uint16 in [0, samples]}; radius defaults to 8 * dps"""
+    def surface_ao(self, samples=64, radius=None, stream=None, *, masks=None):
+        """the exposed faces with their baked occlusion: {faceVoxel (n,) uint32, faceDir (n,) uint8, open (n,) uint16 in [0, samples]}; radius defaults to 8 * dps;
+        masks: the faces of the given masks instead (surface_quads_device)"""
         if radius is None:
             radius = np.float32(8) * np.float32(self.info().dps)
-        n = self.surface_quads_device(stream=stream)
+        masks = None if masks is None else self._given_masks(masks)
+        n = self.surface_quads_device(stream=stream, masks=masks)
         fv, fd, op = DeviceArray(n, np.uint32), DeviceArray(n, np.uint8), DeviceArray(n, np.uint16)
-        self.surface_quads_device(n, fv, fd, None, stream)
+        self.surface_quads_device(n, fv, fd, None, stream, masks=masks)
         self.surface_ao_device(n, fv, fd, samples, radius, op, stream)
         return {"faceVoxel": fv.to_host(), "faceDir": fd.to_host(), "open": op.to_host()}
 

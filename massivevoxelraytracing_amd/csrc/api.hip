@@ -511,14 +511,14 @@ MVRT_EXPORT int mvrt_svo_surface_quads( const mvrt_svo* svo, uint64_t faceCapaci
 {
 	SurfaceSource s;
 	if( surfaceSource( svo, "mvrt_svo_surface_quads", &s ) ) return 1;
-	return surfaceQuads( s, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFacesOut, (hipStream_t)stream );
+	return surfaceQuads( s, nullptr, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFacesOut, (hipStream_t)stream );
 }
 MVRT_EXPORT int mvrt_svo_surface_mesh( const mvrt_svo* svo, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
 									   float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream )
 {
 	SurfaceSource s;
 	if( surfaceSource( svo, "mvrt_svo_surface_mesh", &s ) ) return 1;
-	return surfaceMesh( s, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFacesOut, nVerticesOut, (hipStream_t)stream );
+	return surfaceMesh( s, nullptr, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFacesOut, nVerticesOut, (hipStream_t)stream );
 }
 MVRT_EXPORT int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev,
 										 uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut,
@@ -529,8 +529,49 @@ MVRT_EXPORT int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, ui
 	REQUIRE( ( flags & ~(uint32_t)( MVRT_SURFACE_MERGE_ANY_ATTRIBUTE | MVRT_SURFACE_MERGE_WELD ) ) == 0, "mvrt_svo_surface_merged: unknown flags 0x%x", flags );
 	if( surfaceSource( svo, "mvrt_svo_surface_merged", &s ) ) return 1;
 	REQUIRE( ( flags & MVRT_SURFACE_MERGE_WELD ) || ( !indicesDev && !verticesDev ), "mvrt_svo_surface_merged: indicesDev / verticesDev need MVRT_SURFACE_MERGE_WELD" );
-	return surfaceMerged( s, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev, nFacesOut, nRectsOut, nVerticesOut,
+	return surfaceMerged( s, nullptr, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev, nFacesOut, nRectsOut, nVerticesOut,
 						  (hipStream_t)stream );
+}
+
+// The same three calls on a caller's face masks, and the exterior masks as one producer of them (kernels_fill.hip).  A null handle and null masks are refused
+// first, then what the namesake refuses.
+MVRT_EXPORT int mvrt_svo_surface_exterior_masks( const mvrt_svo* svo, uint8_t* masksDev, uint64_t* nFacesOut, uint64_t* nHiddenOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_exterior_masks", &s ) ) return 1;
+	return surfaceExteriorMasks( s, masksDev, nFacesOut, nHiddenOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_quads_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev,
+												 uint64_t* nFacesOut, void* stream )
+{
+	SurfaceSource s;
+	REQUIRE( svo, "mvrt_svo_surface_quads_masked: null handle" );
+	REQUIRE( masksDev, "mvrt_svo_surface_quads_masked: null masksDev" );
+	if( surfaceSource( svo, "mvrt_svo_surface_quads_masked", &s ) ) return 1;
+	return surfaceQuads( s, masksDev, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFacesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_mesh_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev,
+												uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	REQUIRE( svo, "mvrt_svo_surface_mesh_masked: null handle" );
+	REQUIRE( masksDev, "mvrt_svo_surface_mesh_masked: null masksDev" );
+	if( surfaceSource( svo, "mvrt_svo_surface_mesh_masked", &s ) ) return 1;
+	return surfaceMesh( s, masksDev, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFacesOut, nVerticesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_merged_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev,
+												  uint8_t* rectDirDev, uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut,
+												  uint64_t* nRectsOut, uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	if( nVerticesOut ) *nVerticesOut = 0;
+	REQUIRE( ( flags & ~(uint32_t)( MVRT_SURFACE_MERGE_ANY_ATTRIBUTE | MVRT_SURFACE_MERGE_WELD ) ) == 0, "mvrt_svo_surface_merged_masked: unknown flags 0x%x", flags );
+	REQUIRE( svo, "mvrt_svo_surface_merged_masked: null handle" );
+	REQUIRE( masksDev, "mvrt_svo_surface_merged_masked: null masksDev" );
+	if( surfaceSource( svo, "mvrt_svo_surface_merged_masked", &s ) ) return 1;
+	REQUIRE( ( flags & MVRT_SURFACE_MERGE_WELD ) || ( !indicesDev && !verticesDev ), "mvrt_svo_surface_merged_masked: indicesDev / verticesDev need MVRT_SURFACE_MERGE_WELD" );
+	return surfaceMerged( s, masksDev, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev, nFacesOut, nRectsOut,
+						  nVerticesOut, (hipStream_t)stream );
 }
 
 // Enclosed empty cells and the fill (kernels_fill.hip).  The listing reads the sorted codes alone, like the surface calls.  The fill hands the cells, which stay on

@@ -1,4 +1,4 @@
-// kernels_fill.hip -- the enclosed empty cells of the voxel set (mvrt_svo_enclosed_cells / mvrt_svo_fill_enclosed, mvrt.h).  The work grows with
+// kernels_fill.hip -- the enclosed empty cells of the voxel set (mvrt_svo_enclosed_cells / mvrt_svo_fill_enclosed / mvrt_svo_surface_exterior_masks, mvrt.h).  The work grows with
 // the number of voxels, never with the number of cells of the grid.
 //
 //   rows    the voxels sorted by the linear key ( z * R + y ) * R + x (one radix sort of the codes): a row is one (y, z), its voxels lie together by x.
@@ -10,6 +10,9 @@
 //           smaller one: the root of a set is its lowest id whatever the schedule, and EXTERIOR is the root of everything exterior.
 //   emit    flatten, length of every gap whose root is not EXTERIOR, 64-bit exclusive scan, then the run expansion of voxel_passes.h: one workgroup per 256 gaps
 //           writes its cells, one thread per cell; radix sort of (Morton code, root), roots ranked by the position of their first cell (sortPairsInto, rankHeads).
+//
+//   exterior  the front half alone -- rows, unions, flatten -- serves mvrt_svo_surface_exterior_masks: the plain exposure masks of
+//           kernels_surface.hip, then one pass that clears every bit whose neighbour cell lies in a gap with a root other than EXTERIOR.
 //
 // Nothing here waits on another thread.  find() walks strictly downwards in id (a parent is never larger than its child), unite() retries only after a failed
 // compare-and-swap, and then from a strictly smaller id; the neighbour walk advances its voxel index every turn.
@@ -30,13 +33,7 @@ __global__ void __launch_bounds__( FB ) kFillLinearKeys( const uint64_t* __restr
 	keys[i] = ( (uint64_t)z << ( 2u * L ) ) | ( (uint64_t)y << L ) | x;
 }
 
-// lin: the sorted linear keys.  Gap i exists when voxels i and i + 1 share a row and are not adjacent; its cells are x in [ x(i) + 1, x(i + 1) - 1 ]
-MVRT_HDI uint64_t gapLength( const uint64_t* __restrict__ lin, uint32_t n, uint32_t L, uint64_t i )
-{
-	if( i + 1 >= n ) return 0;
-	const uint64_t a = lin[i], b = lin[i + 1];
-	return ( a >> L ) == ( b >> L ) ? b - a - 1ull : 0ull;
-}
+// (gapLength and gapNodeOfCell: voxel_passes.h)
 
 // ---- union-find over node ids: parent[v] <= v always, a root has parent[v] == v, only roots are ever hooked and only under smaller ids ------------------------
 MVRT_DI uint32_t ufLoad( uint32_t* p ) { return __hip_atomic_load( p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ); }
@@ -142,6 +139,45 @@ __global__ void __launch_bounds__( FB ) kFillFlatten( const uint64_t* __restrict
 	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && m ) atomicAdd( nRegions, (unsigned long long)__popcll( m ) );
 }
 
+// ---- exterior masks (mvrt_svo_surface_exterior_masks) --------------------------------------------------------------------------------------------
+// masks: the plain exposure masks in vIndex order, changed in place: a set bit whose neighbour cell lies inside the grid and in a gap whose root is not EXTERIOR
+// is cleared.  One thread per voxel, the owner of its byte.  The +-X neighbours share the voxel's row: one search of its own key gives its rank p in lin, they
+// are the gaps p and p - 1 where those exist; the other four directions take one search each (gapNodeOfCell).  A neighbour that is no gap cell maps to node 0,
+// whose root is 0.  The cleared bits are counted by a wave reduction and one atomic per wave.
+__global__ void __launch_bounds__( FB ) kFillExteriorMasks( const uint64_t* __restrict__ morton, const uint64_t* __restrict__ lin, const uint32_t* __restrict__ root, uint32_t n, uint32_t L,
+															uint8_t* __restrict__ masks, unsigned long long* __restrict__ nHidden )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * FB + threadIdx.x;
+	uint32_t cleared = 0;
+	const uint32_t m = i < n ? masks[i] : 0u;
+	if( m )
+	{
+		uint32_t x, y, z;
+		mortonDecode( morton[i], x, y, z );
+		const uint32_t last = ( 1u << L ) - 1u; // R - 1
+		const uint64_t row = ( (uint64_t)z << L ) | y, key = ( row << L ) | x;
+		uint32_t node[6] = { 0u, 0u, 0u, 0u, 0u, 0u }; // per direction; 0 = outside the grid, no face, or no gap
+		if( ( m & 0x28u ) != 0u ) // +X or -X
+		{
+			const uint64_t p = lowerBound( lin, 0, n, key ); // ( lin[p] == key )
+			if( ( m & 0x08u ) && x < last && p + 1 < n && ( lin[p + 1] >> L ) == row ) node[3] = (uint32_t)p + 1u; // gap p
+			if( ( m & 0x20u ) && x > 0u && p > 0 && p < n && ( lin[p - 1] >> L ) == row ) node[5] = (uint32_t)p;	   // gap p - 1
+		}
+		if( ( m & 0x01u ) && y > 0u ) node[0] = gapNodeOfCell( lin, n, L, key - ( 1ull << L ) );
+		if( ( m & 0x02u ) && y < last ) node[1] = gapNodeOfCell( lin, n, L, key + ( 1ull << L ) );
+		if( ( m & 0x04u ) && z > 0u ) node[2] = gapNodeOfCell( lin, n, L, key - ( 1ull << ( 2u * L ) ) );
+		if( ( m & 0x10u ) && z < last ) node[4] = gapNodeOfCell( lin, n, L, key + ( 1ull << ( 2u * L ) ) );
+		uint32_t out = m;
+#pragma unroll
+		for( uint32_t d = 0; d < 6; d++ )
+			if( node[d] != 0u && root[node[d]] != 0u ) out &= ~( 1u << d );
+		cleared = __popc( m ^ out );
+		if( cleared ) masks[i] = (uint8_t)out;
+	}
+	for( int o = WAVE / 2; o > 0; o >>= 1 ) cleared += __shfl_down( cleared, o, WAVE );
+	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && cleared ) atomicAdd( nHidden, (unsigned long long)cleared );
+}
+
 struct EnclosedLength // scan input: the cells of gap i where its root is not EXTERIOR (item n - 1 and beyond: 0)
 {
 	const uint64_t* lin;
@@ -219,19 +255,19 @@ __global__ void __launch_bounds__( FB ) kFillAttribs( uint2 attrib, uint64_t n, 
 	if( i < n ) out[i] = attrib;
 }
 
-// what the classification leaves for the emit: the sorted linear keys, the flattened roots (node i + 1 = gap i) and the n + 1 cell offsets
+// what the classification leaves: the sorted linear keys, the flattened roots (node i + 1 = gap i; root 0 = EXTERIOR) and, for the emit, the n + 1 cell offsets
 struct Classified
 {
-	DevBuf lin, root, offs;
+	DevBuf count, lin, root, offs;
 	uint64_t nCells = 0, nRegions = 0;
 };
-int classify( const SurfaceSource& s, Classified* out, hipStream_t st )
+// keys, sort, parents, unions, flatten: lin and root.  nRegions is on its way to the host: valid once the stream has been waited for
+int classifyGaps( const SurfaceSource& s, Classified* out, hipStream_t st )
 {
 	const uint32_t n = s.nVoxels, L = s.levels;
 	const dim3 grid( divUp( n, FB ) ), block( FB );
-	DevBuf cnt;
-	if( cnt.alloc( 8 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 8, st ) );
+	if( out->count.alloc( 8 ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( out->count.p, 0, 8, st ) );
 	{
 		DevBuf keys;
 		if( keys.alloc( (uint64_t)n * 8 ) || out->lin.alloc( (uint64_t)n * 8 ) ) return 1;
@@ -246,13 +282,19 @@ int classify( const SurfaceSource& s, Classified* out, hipStream_t st )
 	if( out->root.alloc( nNodes * 4 ) ) return 1;
 	hipLaunchKernelGGL( kFillInitParents, dim3( divUp( nNodes, FB ) ), block, 0, st, out->root.as<uint32_t>(), nNodes );
 	hipLaunchKernelGGL( kFillUnite, grid, block, 0, st, out->lin.as<uint64_t>(), n, L, out->root.as<uint32_t>() );
-	hipLaunchKernelGGL( kFillFlatten, grid, block, 0, st, out->lin.as<uint64_t>(), n, L, out->root.as<uint32_t>(), cnt.as<unsigned long long>() );
+	hipLaunchKernelGGL( kFillFlatten, grid, block, 0, st, out->lin.as<uint64_t>(), n, L, out->root.as<uint32_t>(), out->count.as<unsigned long long>() );
 	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipMemcpyAsync( &out->nRegions, cnt.p, 8, hipMemcpyDeviceToHost, st ) ); // (behind kFillFlatten; the scan below waits)
+	MVRT_HIP( hipMemcpyAsync( &out->nRegions, out->count.p, 8, hipMemcpyDeviceToHost, st ) ); // (behind kFillFlatten)
+	return 0;
+}
+// the same and the cell offsets of the enclosed gaps; the scan waits for the stream
+int classify( const SurfaceSource& s, Classified* out, hipStream_t st )
+{
+	if( classifyGaps( s, out, st ) ) return 1;
 	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint64_t, EnclosedLength, hipcub::CountingInputIterator<uint32_t>> lengths( counting,
-																												EnclosedLength{ out->lin.as<uint64_t>(), out->root.as<uint32_t>(), n, L } );
-	return exclusiveOffsets<uint64_t>( lengths, nNodes, out->offs, &out->nCells, st );
+	hipcub::TransformInputIterator<uint64_t, EnclosedLength, hipcub::CountingInputIterator<uint32_t>> lengths(
+		counting, EnclosedLength{ out->lin.as<uint64_t>(), out->root.as<uint32_t>(), s.nVoxels, s.levels } );
+	return exclusiveOffsets<uint64_t>( lengths, (uint64_t)s.nVoxels + 1, out->offs, &out->nCells, st );
 }
 int launchEmit( const SurfaceSource& s, const Classified& c, uint64_t* codes, uint32_t* roots, uint32_t* xyz, hipStream_t st )
 {
@@ -315,6 +357,37 @@ int enclosedCellsUnordered( const SurfaceSource& s, DevBuf& xyz, uint64_t* nCell
 	if( xyz.alloc( c.nCells * 12 ) ) return 1;
 	if( launchEmit( s, c, nullptr, nullptr, xyz.as<uint32_t>(), st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	return 0;
+}
+
+int surfaceExteriorMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, uint64_t* nHiddenOut, hipStream_t st )
+{
+	Classified c;
+	if( classifyGaps( s, &c, st ) ) return 1;
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (nRegions)
+	DevBuf cnt, own;
+	if( cnt.alloc( 16 ) ) return 1;
+	uint8_t* masks = masksDev;
+	if( !masks && c.nRegions ) // counts only: the second kernel still reads the plain masks
+	{
+		if( own.alloc( s.nVoxels ) ) return 1;
+		masks = own.as<uint8_t>();
+	}
+	// (the caller's array is written from here on, behind every allocation)
+	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 16, st ) );
+	unsigned long long* counts = cnt.as<unsigned long long>(); // [0] plain faces [1] hidden faces
+	if( launchSurfaceMasks( s, masks, counts, st ) ) return 1;
+	if( c.nRegions ) // without an enclosed region the exterior masks are the plain masks
+	{
+		hipLaunchKernelGGL( kFillExteriorMasks, dim3( divUp( s.nVoxels, FB ) ), dim3( FB ), 0, st, s.morton, c.lin.as<uint64_t>(), c.root.as<uint32_t>(), s.nVoxels, s.levels, masks,
+							counts + 1 );
+		MVRT_HIP( hipGetLastError() );
+	}
+	unsigned long long h[2] = { 0, 0 };
+	MVRT_HIP( hipMemcpyAsync( h, cnt.p, 16, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	if( nFacesOut ) *nFacesOut = h[0] - h[1];
+	if( nHiddenOut ) *nHiddenOut = h[1];
 	return 0;
 }
 

@@ -3,6 +3,8 @@
 //
 //   masks   one byte per voxel, bit d = the neighbour in direction d is empty.  Read from the sorted Morton codes of the build; a neighbour is looked up in the
 //           cell index (SvoDev::cellBlocks / cellEntries) where the octree has one, else by binary search in the codes.  Both give the same bytes.
+//           The _masked calls take a caller's bytes instead (kSurfaceGivenMasks copies them, without bits 6-7, and counts); everything behind the masks reads
+//           the masks alone, never occupancy.
 //   faces   exclusive scan of the popcounts (64-bit offsets), then the run expansion of voxel_passes.h: one workgroup per 256 voxels emits that group's faces,
 //           one thread per face, so a wave writes 64 consecutive records.
 //   weld    corner keys, then the Weld record: radix sort of (key, face * 4 + k), head flags, inclusive scan = rank + 1; scatter of the ranks and decode of the heads.
@@ -87,6 +89,21 @@ template <bool CELLS> __global__ void __launch_bounds__( SB ) kSurfaceMasks( Sur
 			masks[i] = (uint8_t)m0;
 			if( two ) masks[i + 1] = (uint8_t)m1;
 		}
+	}
+	for( int o = WAVE / 2; o > 0; o >>= 1 ) cnt += __shfl_down( cnt, o, WAVE );
+	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && cnt ) atomicAdd( nFaces, (unsigned long long)cnt );
+}
+
+// the caller's masks of the _masked calls into the scratch: bits 6 and 7 dropped, the set bits counted the same way
+__global__ void __launch_bounds__( SB ) kSurfaceGivenMasks( const uint8_t* __restrict__ given, uint32_t n, uint8_t* __restrict__ masks, unsigned long long* __restrict__ nFaces )
+{
+	const uint64_t i = (uint64_t)blockIdx.x * SB + threadIdx.x;
+	uint32_t cnt = 0;
+	if( i < n )
+	{
+		const uint32_t m = given[i] & 0x3Fu;
+		masks[i] = (uint8_t)m;
+		cnt = __popc( m );
 	}
 	for( int o = WAVE / 2; o > 0; o >>= 1 ) cnt += __shfl_down( cnt, o, WAVE );
 	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && cnt ) atomicAdd( nFaces, (unsigned long long)cnt );
@@ -204,14 +221,6 @@ __global__ void __launch_bounds__( SB ) kSurfaceWeld( const uint64_t* __restrict
 	}
 }
 
-int launchMasks( const SurfaceSource& s, uint8_t* masks, unsigned long long* nFacesDev, hipStream_t st )
-{
-	const dim3 grid( divUp( s.nVoxels, 2 * SB ) );
-	if( s.cellBlocks ) hipLaunchKernelGGL( kSurfaceMasks<true>, grid, dim3( SB ), 0, st, s, masks, nFacesDev );
-	else hipLaunchKernelGGL( kSurfaceMasks<false>, grid, dim3( SB ), 0, st, s, masks, nFacesDev );
-	MVRT_HIP( hipGetLastError() );
-	return 0;
-}
 int launchEmit( const SurfaceSource& s, const uint8_t* masks, const uint64_t* offs, uint32_t* faceVoxel, uint8_t* faceDir, float* positions, uint64_t* keys, uint32_t* vals,
 				hipStream_t st )
 {
@@ -225,13 +234,18 @@ int launchEmit( const SurfaceSource& s, const uint8_t* masks, const uint64_t* of
 	return 0;
 }
 
-// the masks kernel into `masks` (null = count only) and the sum of the popcounts, on the host when this returns
-int masksAndCount( const SurfaceSource& s, uint8_t* masks, uint64_t* nFaces, hipStream_t st )
+// the masks kernel into `masks` (null = count only), or a caller's `given` masks copied there, and the sum of the popcounts, on the host when this returns
+int masksAndCount( const SurfaceSource& s, const uint8_t* given, uint8_t* masks, uint64_t* nFaces, hipStream_t st )
 {
 	DevBuf cnt;
 	if( cnt.alloc( 8 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 8, st ) );
-	if( launchMasks( s, masks, cnt.as<unsigned long long>(), st ) ) return 1;
+	if( given )
+	{
+		hipLaunchKernelGGL( kSurfaceGivenMasks, dim3( divUp( s.nVoxels, SB ) ), dim3( SB ), 0, st, given, s.nVoxels, masks, cnt.as<unsigned long long>() );
+		MVRT_HIP( hipGetLastError() );
+	}
+	else if( launchSurfaceMasks( s, masks, cnt.as<unsigned long long>(), st ) ) return 1;
 	unsigned long long h = 0;
 	MVRT_HIP( hipMemcpyAsync( &h, cnt.p, 8, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) );
@@ -239,11 +253,11 @@ int masksAndCount( const SurfaceSource& s, uint8_t* masks, uint64_t* nFaces, hip
 	return 0;
 }
 // the same into scratch of n + 1 bytes, the last one 0 so that the scan below yields offs[n]
-int scratchMasksAndCount( const SurfaceSource& s, DevBuf& masks, uint64_t* nFaces, hipStream_t st )
+int scratchMasksAndCount( const SurfaceSource& s, const uint8_t* given, DevBuf& masks, uint64_t* nFaces, hipStream_t st )
 {
 	if( masks.alloc( (uint64_t)s.nVoxels + 1 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( masks.as<uint8_t>() + s.nVoxels, 0, 1, st ) );
-	return masksAndCount( s, masks.as<uint8_t>(), nFaces, st );
+	return masksAndCount( s, given, masks.as<uint8_t>(), nFaces, st );
 }
 int scanOffsets( const SurfaceSource& s, const DevBuf& masks, DevBuf& offs, hipStream_t st )
 {
@@ -281,24 +295,34 @@ int writeWeld( const SurfaceSource& s, const Weld& w, uint32_t* indicesDev, floa
 }
 } // namespace
 
+int launchSurfaceMasks( const SurfaceSource& s, uint8_t* masks, unsigned long long* nFacesDev, hipStream_t st )
+{
+	const dim3 grid( divUp( s.nVoxels, 2 * SB ) );
+	if( s.cellBlocks ) hipLaunchKernelGGL( kSurfaceMasks<true>, grid, dim3( SB ), 0, st, s, masks, nFacesDev );
+	else hipLaunchKernelGGL( kSurfaceMasks<false>, grid, dim3( SB ), 0, st, s, masks, nFacesDev );
+	MVRT_HIP( hipGetLastError() );
+	return 0;
+}
+
 int surfaceMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, hipStream_t st )
 {
 	uint64_t nFaces = 0;
-	if( masksAndCount( s, masksDev, &nFaces, st ) ) return 1;
+	if( masksAndCount( s, nullptr, masksDev, &nFaces, st ) ) return 1;
 	if( nFacesOut ) *nFacesOut = nFaces;
 	return 0;
 }
 
-int surfaceQuads( const SurfaceSource& s, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut, hipStream_t st )
+int surfaceQuads( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut, hipStream_t st )
 {
+	const char* who = givenMasks ? "mvrt_svo_surface_quads_masked" : "mvrt_svo_surface_quads";
 	DevBuf masks, offs;
 	uint64_t nFaces = 0;
-	if( scratchMasksAndCount( s, masks, &nFaces, st ) ) return 1;
+	if( scratchMasksAndCount( s, givenMasks, masks, &nFaces, st ) ) return 1;
 	if( nFacesOut ) *nFacesOut = nFaces;
 	if( !faceVoxelDev && !faceDirDev && !positionsDev ) return 0; // the sizing call
 	if( faceCapacity < nFaces )
 	{
-		mvrtSetError( "mvrt_svo_surface_quads: faceCapacity %llu is smaller than the %llu faces of the surface; nothing was written", (unsigned long long)faceCapacity,
+		mvrtSetError( "%s: faceCapacity %llu is smaller than the %llu faces of the surface; nothing was written", who, (unsigned long long)faceCapacity,
 					  (unsigned long long)nFaces );
 		return 1;
 	}
@@ -308,17 +332,18 @@ int surfaceQuads( const SurfaceSource& s, uint64_t faceCapacity, uint32_t* faceV
 	return 0;
 }
 
-int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev,
+int surfaceMesh( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev,
 				 uint64_t* nFacesOut, uint64_t* nVerticesOut, hipStream_t st )
 {
+	const char* who = givenMasks ? "mvrt_svo_surface_mesh_masked" : "mvrt_svo_surface_mesh";
 	DevBuf masks, offs;
 	uint64_t nFaces = 0;
-	if( scratchMasksAndCount( s, masks, &nFaces, st ) ) return 1;
+	if( scratchMasksAndCount( s, givenMasks, masks, &nFaces, st ) ) return 1;
 	if( nFacesOut ) *nFacesOut = nFaces;
 	if( nVerticesOut ) *nVerticesOut = 0;
 	if( 4ull * nFaces >= ( 1ull << 32 ) )
 	{
-		mvrtSetError( "mvrt_svo_surface_mesh: the %llu faces of the surface have 2^32 corners or more, beyond the 32-bit indices of a welded mesh (use mvrt_svo_surface_quads)",
+		mvrtSetError( "%s: the %llu faces of the surface have 2^32 corners or more, beyond the 32-bit indices of a welded mesh (use mvrt_svo_surface_quads)", who,
 					  (unsigned long long)nFaces );
 		return 1;
 	}
@@ -338,13 +363,13 @@ int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexC
 	// (the capacities are looked at behind the sort: a refused call still returns BOTH counts, and the vertex count is the sort's result)
 	if( ( faceVoxelDev || faceDirDev || indicesDev ) && faceCapacity < nFaces )
 	{
-		mvrtSetError( "mvrt_svo_surface_mesh: faceCapacity %llu is smaller than the %llu faces of the surface; nothing was written", (unsigned long long)faceCapacity,
+		mvrtSetError( "%s: faceCapacity %llu is smaller than the %llu faces of the surface; nothing was written", who, (unsigned long long)faceCapacity,
 					  (unsigned long long)nFaces );
 		return 1;
 	}
 	if( verticesDev && vertexCapacity < nVertices )
 	{
-		mvrtSetError( "mvrt_svo_surface_mesh: vertexCapacity %llu is smaller than the %u vertices of the surface; nothing was written", (unsigned long long)vertexCapacity, nVertices );
+		mvrtSetError( "%s: vertexCapacity %llu is smaller than the %u vertices of the surface; nothing was written", who, (unsigned long long)vertexCapacity, nVertices );
 		return 1;
 	}
 	if( nCorners == 0 ) return 0;
@@ -580,16 +605,17 @@ int launchMergeEmit( const SurfaceSource& s, const DevBuf* rects, const uint32_t
 }
 } // namespace
 
-int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev,
+int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev,
 				   float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut, hipStream_t st )
 {
+	const char* who = givenMasks ? "mvrt_svo_surface_merged_masked" : "mvrt_svo_surface_merged";
 	const bool welded = ( flags & 2u ) != 0; // MVRT_SURFACE_MERGE_WELD
 	DevBuf rects[6];
 	uint32_t counts[6];
 	uint64_t nFaces = 0, nRects = 0;
 	{
 		DevBuf masks;
-		if( scratchMasksAndCount( s, masks, &nFaces, st ) ) return 1;
+		if( scratchMasksAndCount( s, givenMasks, masks, &nFaces, st ) ) return 1;
 		if( nFacesOut ) *nFacesOut = nFaces;
 		if( nRectsOut ) *nRectsOut = 0;
 		if( nVerticesOut ) *nVerticesOut = 0;
@@ -605,8 +631,8 @@ int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity
 	{
 		if( 4ull * nRects >= ( 1ull << 32 ) )
 		{
-			mvrtSetError( "mvrt_svo_surface_merged: the %llu rectangles of the surface have 2^32 corners or more, beyond the 32-bit indices of a welded mesh (call without "
-						  "MVRT_SURFACE_MERGE_WELD)",
+			mvrtSetError( "%s: the %llu rectangles of the surface have 2^32 corners or more, beyond the 32-bit indices of a welded mesh (call without "
+						  "MVRT_SURFACE_MERGE_WELD)", who,
 						  (unsigned long long)nRects );
 			return 1;
 		}
@@ -624,13 +650,13 @@ int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity
 	if( !rectVoxelDev && !rectDirDev && !rectSizeDev && !positionsDev && !indicesDev && !verticesDev ) return 0; // the sizing call
 	if( ( rectVoxelDev || rectDirDev || rectSizeDev || positionsDev || indicesDev ) && rectCapacity < nRects )
 	{
-		mvrtSetError( "mvrt_svo_surface_merged: rectCapacity %llu is smaller than the %llu rectangles of the surface; nothing was written", (unsigned long long)rectCapacity,
+		mvrtSetError( "%s: rectCapacity %llu is smaller than the %llu rectangles of the surface; nothing was written", who, (unsigned long long)rectCapacity,
 					  (unsigned long long)nRects );
 		return 1;
 	}
 	if( verticesDev && vertexCapacity < nVertices )
 	{
-		mvrtSetError( "mvrt_svo_surface_merged: vertexCapacity %llu is smaller than the %u vertices of the surface; nothing was written", (unsigned long long)vertexCapacity, nVertices );
+		mvrtSetError( "%s: vertexCapacity %llu is smaller than the %u vertices of the surface; nothing was written", who, (unsigned long long)vertexCapacity, nVertices );
 		return 1;
 	}
 	if( nRects == 0 ) return 0;

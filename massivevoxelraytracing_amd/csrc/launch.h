@@ -184,18 +184,26 @@ struct SurfaceSource
 	const uint2* attrs; // VoxelAttirb per voxel, read by surfaceMerged only
 };
 int surfaceMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, hipStream_t stream );
-int surfaceQuads( const SurfaceSource& s, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut, hipStream_t stream );
-int surfaceMesh( const SurfaceSource& s, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev,
-				 uint64_t* nFacesOut, uint64_t* nVerticesOut, hipStream_t stream );
+// the masks kernel alone (masks == nullptr: count only); the sum of the popcounts is added to *nFacesDev.  Not synchronised.
+int launchSurfaceMasks( const SurfaceSource& s, uint8_t* masks, unsigned long long* nFacesDev, hipStream_t stream );
+// givenMasks (the _masked calls; nullptr = the exposure masks): nVoxels bytes whose set bits 0..5 are the faces, taken as given; the error messages name the _masked call
+int surfaceQuads( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut,
+				  hipStream_t stream );
+int surfaceMesh( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
+				 float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, hipStream_t stream );
 // flags: MVRT_SURFACE_MERGE_* (mvrt.h), checked by the caller, as is that indicesDev / verticesDev come with the weld flag only
-int surfaceMerged( const SurfaceSource& s, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev, uint32_t* rectSizeDev,
-				   float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut, hipStream_t stream );
+int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev,
+				   uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut,
+				   hipStream_t stream );
 
 // enclosed empty cells (kernels_fill.hip; mvrt_svo_enclosed_cells / mvrt_svo_fill_enclosed): only morton, nVoxels and levels of the source are read.  The calls
 // block, keep their scratch in DevBufs and write NOTHING to the caller's arrays unless they succeed.
 int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, hipStream_t stream );
 // the same cells in no particular order into xyz (allocated here, 3 x u32 per cell; left empty when there are none or 2^32 or more: the caller looks at *nCells)
 int enclosedCellsUnordered( const SurfaceSource& s, DevBuf& xyz, uint64_t* nCells, hipStream_t stream );
+// exterior masks (mvrt_svo_surface_exterior_masks): the exposure masks with the bits that look into an enclosed cell cleared, from the front half of the
+// classification above (linear keys, unions, flatten) and the masks kernel of kernels_surface.hip.  masksDev == nullptr: counts only
+int surfaceExteriorMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, uint64_t* nHiddenOut, hipStream_t stream );
 int launchFillAttribs( uint2 attrib, uint64_t n, uint2* out, hipStream_t stream ); // n copies of one VoxelAttirb.  Not synchronised.
 
 // octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree

@@ -5,6 +5,8 @@
 //                   relative to offs[first], into LDS; thread t then takes records t, t + B, ... of the run, findRun gives the item of a record and
 //                   j - sOff[item] its number within the item, so a wave writes 64 consecutive records.  Where an item's records are the set bits of a mask,
 //                   nthSetBit picks the bit.
+//   rows and gaps   gapLength / gapNodeOfCell on the sorted linear keys of kernels_fill.hip: the empty run between two voxels of a row, and the run an empty cell
+//                   lies in.  Host-callable, so that a host program checks them against brute force (tests/hip/exterior_host.hip).
 //   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
 //                   entries -> rank + 1 of every entry and the number of runs).  Each allocates its output itself, runs hipcub through withCubTemp and has waited
 //                   for the stream when it returns.
@@ -42,6 +44,26 @@ MVRT_HDI uint32_t nthSetBit( uint32_t mask, uint32_t r )
 {
 	for( ; r > 0; r-- ) mask &= mask - 1u;
 	return mask == 0u ? ~0u : (uint32_t)__builtin_ctz( mask );
+}
+
+// ---- rows and gaps (kernels_fill.hip) -----------------------------------------------------------------------------------------------------------------------
+// lin: the n sorted linear keys ( z << 2L | y << L | x ) of the voxels.  Gap i exists when voxels i and i + 1 share a row and are not adjacent; its cells are
+// x in [ x(i) + 1, x(i + 1) - 1 ]
+MVRT_HDI uint64_t gapLength( const uint64_t* __restrict__ lin, uint32_t n, uint32_t L, uint64_t i )
+{
+	if( i + 1 >= n ) return 0;
+	const uint64_t a = lin[i], b = lin[i + 1];
+	return ( a >> L ) == ( b >> L ) ? b - a - 1ull : 0ull;
+}
+// The union-find node of the empty in-grid cell with the linear key `key` (not in lin): node j = gap j - 1 when the voxels j - 1 and j of the list stand left and
+// right of the cell in its row; 0 = EXTERIOR when the cell lies in the run before the first voxel of its row, in the run behind the last one or in a row
+// without voxels, which hold a border cell and are exterior by themselves.  One bounded search; reads lin[j - 1] and lin[j] only for 0 < j < n.
+MVRT_HDI uint32_t gapNodeOfCell( const uint64_t* __restrict__ lin, uint32_t n, uint32_t L, uint64_t key )
+{
+	const uint64_t j = lowerBound( lin, 0, n, key );
+	if( j == 0 || j >= n ) return 0u;
+	const uint64_t row = key >> L;
+	return ( lin[j - 1] >> L ) == row && ( lin[j] >> L ) == row ? (uint32_t)j : 0u;
 }
 
 // ---- host steps -------------------------------------------------------------------------------------------------------------------------------------------
