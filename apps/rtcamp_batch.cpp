@@ -95,7 +95,8 @@ int main( int argc, char** argv )
 	if( argc < 4 )
 	{
 		std::printf( "usage: rtcamp_batch scene.obj env.hdr outdir [--frame-range a b] [--frames N] [--size W H] [--res from to] [--steps K] [--png] [--aov] [--denoise]\n"
-					 "                    [--adaptive threshold] [--adaptive-every K]\n"
+					 "                    [--adaptive threshold] [--adaptive-every K] [--lod K]\n"
+					 "  --lod K    coarsen the tracer's octree in place by K levels after every scene build (mvrt_svo_coarsen): a preview at gridRes >> K\n"
 					 "  --aov      also write <frame>_albedo and <frame>_normal (first-hit feature buffers)\n"
 					 "  --denoise  also write <frame>_denoised (a-trous denoiser on the feature buffers and the luminance moments)\n"
 					 "  --adaptive after 32 samples per pixel, sample only the pixels whose standard error exceeds threshold * mean luminance; re-marked every K steps (default 2)\n" );
@@ -109,6 +110,7 @@ int main( int argc, char** argv )
 	bool png = false, dumpCameras = false, aov = false, denoise = false;
 	float adaptive = 0.0f; // > 0: the threshold of --adaptive
 	int adaptiveEvery = 2;
+	int lod = 0; // > 0: the levels of --lod
 	const int adaptiveMinSamples = 32;
 	for( int i = 4; i < argc; i++ )
 	{
@@ -123,6 +125,7 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--denoise" ) ) denoise = true;
 		else if( !std::strcmp( argv[i], "--adaptive" ) && i + 1 < argc ) adaptive = (float)std::atof( argv[++i] );
 		else if( !std::strcmp( argv[i], "--adaptive-every" ) && i + 1 < argc ) adaptiveEvery = std::atoi( argv[++i] );
+		else if( !std::strcmp( argv[i], "--lod" ) && i + 1 < argc ) lod = std::atoi( argv[++i] );
 	}
 	if( endFrame < 0 ) endFrame = totalFrames;
 	if( adaptiveEvery < 1 ) adaptiveEvery = 1;
@@ -203,6 +206,12 @@ int main( int argc, char** argv )
 		const int resolution = (int)std::ceil( boxWide / dps );
 		const int gridRes = (int)next_power_of_two( (uint32_t)resolution );
 		pt.updateScene( vertices, vcolors, vemissions, stream, lo, dps, gridRes );
+		if( lod > 0 )
+		{
+			const uint32_t fine = pt.m_intersectorOctreeGPU.m_numberOfVoxels;
+			pt.m_intersectorOctreeGPU.coarsen( lod, 1, 0, nullptr, stream );
+			std::printf( "lod: voxels %u -> %u, gridRes %d -> %d\n", fine, pt.m_intersectorOctreeGPU.m_numberOfVoxels, gridRes, gridRes >> lod );
+		}
 
 		const float ang = 6.2831853f * tt;
 		const float eye[3] = { centre[0] + 1.6f * boxWide * std::cos( ang ), centre[1] + 0.5f * boxWide, centre[2] + 1.6f * boxWide * std::sin( ang ) };

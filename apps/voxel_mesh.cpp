@@ -1,7 +1,8 @@
 // voxel_mesh -- the reference voxelizer's "Save As Mesh" (voxMesh.cpp:111-219) without the GUI: voxelize a Wavefront .obj on the GPU and write the exposed
 // faces of the voxel set as a PLY quad mesh, one colour per face from its voxel.
 //
-//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill | --exterior] [--ao [samples] [--ao-radius voxels]]
+//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]
+//              [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -14,6 +15,8 @@
 // --exterior: the same faces as --fill writes, without touching the octree: the faces that look into an enclosed cell are dropped from the masks
 // (mvrt_svo_surface_exterior_masks) and the mesh is extracted from those (mvrt_svo_surface_*_masked); a line reports the faces before and after.  With every
 // other flag except --fill: one or the other.
+// --lod K: the octree is coarsened in place by K levels (mvrt_svo_coarsen: gridRes >> K, a cell is a voxel when it holds at least --lod-min-count fine voxels,
+// default 1) before anything else is done with it; a line reports voxels and gridRes before and after.  With every other flag.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +31,8 @@ int main( int argc, char** argv )
 	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false, fill = false, exterior = false;
 	int aoSamples = 64;
 	float aoRadiusVoxels = 8.0f;
+	int lod = 0;
+	unsigned long long lodMinCount = 1;
 	std::vector<const char*> pos;
 	for( int i = 1; i < argc; i++ )
 	{
@@ -43,11 +48,15 @@ int main( int argc, char** argv )
 			if( i + 1 < argc && argv[i + 1][0] && std::strspn( argv[i + 1], "0123456789" ) == std::strlen( argv[i + 1] ) ) aoSamples = std::atoi( argv[++i] );
 		}
 		else if( !std::strcmp( argv[i], "--ao-radius" ) && i + 1 < argc ) aoRadiusVoxels = (float)std::atof( argv[++i] );
+		else if( !std::strcmp( argv[i], "--lod" ) && i + 1 < argc ) lod = std::atoi( argv[++i] );
+		else if( !std::strcmp( argv[i], "--lod-min-count" ) && i + 1 < argc ) lodMinCount = std::strtoull( argv[++i], nullptr, 10 );
 		else pos.push_back( argv[i] );
 	}
 	if( pos.size() != 3 )
 	{
-		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--fill | --exterior] [--ao [samples] [--ao-radius voxels]]\n"
+		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]\n"
+					 "                  [--ao [samples] [--ao-radius voxels]]\n"
+					 "  --lod K      coarsen the octree by K levels first (gridRes >> K); --lod-min-count C keeps a coarse cell only when it holds C fine voxels\n"
 					 "  --fill       fill the empty cells the voxel shell encloses (white voxels) before the surface is extracted\n"
 					 "  --exterior   drop the faces that look into an enclosed cell instead; the octree stays as built.  Not with --fill\n"
 					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
@@ -86,6 +95,13 @@ int main( int argc, char** argv )
 	void* stream = nullptr;
 	mvrt::IntersectorOctreeGPU svo;
 	svo.build( vertices, vcolors, vemissions, nullptr, stream, origin, dps, gridRes, conservative ? MVRT_BUILD_CONSERVATIVE : 0 );
+	if( lod > 0 ) // before anything else is done with the octree
+	{
+		const uint32_t before = svo.m_numberOfVoxels;
+		svo.coarsen( lod, lodMinCount, 0, nullptr, stream );
+		dps = svo.m_dps; // (the --ao radius is given in voxels of the mesh that is written)
+		std::printf( "lod: voxels %u -> %u, gridRes %d -> %d\n", before, svo.m_numberOfVoxels, gridRes, gridRes >> lod );
+	}
 	if( fill )
 	{
 		const uint32_t before = svo.m_numberOfVoxels;

@@ -216,6 +216,40 @@ int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* x
  * handle, and numberOfVoxels + nCells >= 2^32 - 1 (the message names the count).  nFilledOut may be NULL. */
 int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8] /* VoxelAttirb, NULL = white, no emission */, uint64_t* nFilledOut, void* stream );
 
+/* A coarser level of detail of the voxel set, made from the voxels themselves (new; the reference voxelizes the triangles again at every resolution, and a set
+ * built from a voxel list, an edit, a fill or an upload has no triangles).  Definitions, with R = gridRes of the source, L = log2 R, k = levelsDown in
+ * [1, L - 1], so that the coarse grid has R' = R >> k >= 2:
+ *   - The coarse cell of a voxel (x, y, z) is (x >> k, y >> k, z >> k); its Morton code is the voxel's code >> 3k.
+ *   - count(c): the number of source voxels in cell c, 1 .. 8^k.
+ *   - Cell c is KEPT when count(c) >= minCount, a uint64 in [1, 8^k].  minCount = 1 keeps every occupied cell: a conservative superset of the fine set.  A larger
+ *     value drops thin features: a single stray fine voxel no longer becomes a whole coarse voxel.
+ *   - Attribute of a kept cell, per channel R, G, B of colour and of emission: floor( sum of the channel / count ) with an EXACT integer sum (64-bit: a cell may
+ *     hold 2^32 - 2 voxels, 255 times that needs 40 bits).  Both alpha bytes are stored as 255; the alpha bytes of the source are not read.  This is the
+ *     reference's unique rule (voxKernel.cu:201-210): with minCount = 1 the result is what mvrt_svo_build_voxels makes of the shifted list wherever that call's
+ *     32-bit sums do not overflow (a cell of more than 2^31 / 255 voxels).
+ *   - Order: ascending coarse Morton code, the vIndex order of the coarse octree.
+ *   - The result is a property of the voxel set alone: integer sums make it independent of any processing order.
+ * mvrt_svo_coarse_voxels, the listing, follows the rules of mvrt_svo_enclosed_cells word for word: every octree this library built or edited is accepted, in every
+ * flavour, the tree flavour included (only the codes and the attributes are read); an upload is refused ("keeps no Morton codes": it works after one
+ * mvrt_svo_rebuild), an empty handle too ("no octree"); levelsDown outside [1, L - 1] is refused (the message names the range), minCount outside [1, 8^k] too; all
+ * refusals happen on the host before any GPU work.  The handle is never modified.  The call blocks.  Per kept cell, into caller device arrays of `capacity`
+ * cells: xyzDev 3 x uint32 coarse coordinates, attribsDev 8 bytes, countDev one uint32 = count(c).  Any output may be NULL; all NULL is the sizing call (capacity is
+ * then ignored).  A capacity below the count is an error: the count is still returned and NOTHING is written.  Zero kept cells is a success with *nOut = 0.  A failed
+ * allocation of scratch returns an error, leaves the octree whole and leaks nothing.  gridRes up to 2^21: the shift reaches 60 bits. */
+int mvrt_svo_coarse_voxels( const mvrt_svo* svo, int levelsDown, uint64_t minCount, uint64_t capacity, uint32_t* xyzDev /* 3 per cell, coarse coordinates */,
+							uint32_t* attribsDev /* 8 bytes per cell */, uint32_t* countDev /* fine voxels per cell */, uint64_t* nOut, void* stream );
+/* dst becomes exactly the octree mvrt_svo_build_voxels would build from that listing at gridRes >> levelsDown with buildFlags (MVRT_BUILD_NO_DAG |
+ * MVRT_BUILD_NO_EMBEDDED_MASK only; any other bit is refused): same nodes, numbering, flavour choice, cell index and prefix tables, vIndex = Morton rank.  The list
+ * never travels to the host and is neither encoded nor sorted again.  lower = the source's; dps' = dps * 2^k, one fp32 multiply by an exact power of two (a
+ * non-finite product is refused); gridRes = R'; upper = lower + dps' * R' is therefore bit-identical to the source's.  hasEmission is recomputed from the kept
+ * cells, totalDumpedVoxels = the source's numberOfVoxels, the emission scale is the destination handle's own and is not touched.  dst == src is allowed: the
+ * in-place LOD.  Otherwise src is never modified.  Refusals are the listing's, on the host; zero kept cells is refused with dst unchanged ("would leave no
+ * voxel").  Failures are the voxel-list build's: the new arrays are built next to whatever dst holds, every failure before they are adopted leaves dst exactly as
+ * it was, one after that leaves dst empty (see mvrt_svo_destroy above); src != dst stays whole throughout.  Through mvrt_pt_intersector( pt ) as dst: the steps
+ * issued before finish first and render the old scene, the frame buffer is not cleared; every mvrt_device_octree view of dst is invalidated.  Blocks like
+ * mvrt_svo_build. */
+int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levelsDown, uint64_t minCount, int buildFlags, void* stream );
+
 /* Exterior-only surface extraction without touching the octree, and the three extraction calls on face masks the caller supplies (new; the reference has
  * none).  Definitions:
  *   - Exterior mask of a voxel: one byte, directions d = 0..5 as in mvrt_svo_surface_masks (0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X).  Bit d is set when the

@@ -184,6 +184,37 @@ struct IntersectorOctreeGPU
 		return nFilled;
 	}
 
+	// a coarser level of detail from the voxels themselves (mvrt_svo_coarse_voxels / mvrt_svo_coarsen; semantics in mvrt.h): the cells (x >> k, y >> k, z >> k),
+	// k = levelsDown, that hold at least minCount voxels, each with the integer mean attribute.  Device-pointer form: any output may be nullptr, all nullptr = the
+	// sizing call; returns the number of kept cells.
+	uint64_t coarseVoxels( int levelsDown, uint64_t minCount, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_coarse_voxels( m_handle, levelsDown, minCount, capacity, xyzDev, attribsDev, countDev, &n, stream ), "IntersectorOctreeGPU::coarseVoxels" );
+		return n;
+	}
+	// host-vector form: xyz = 3 entries per cell in ascending Morton order, attribs = 2, count = 1 (the fine voxels of the cell)
+	void coarseVoxels( int levelsDown, uint64_t minCount, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs, std::vector<uint32_t>& count, void* stream ) const
+	{
+		const uint64_t n = coarseVoxels( levelsDown, minCount, 0, nullptr, nullptr, nullptr, stream );
+		xyz.resize( n * 3 );
+		attribs.resize( n * 2 );
+		count.resize( n );
+		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), c( nullptr, n * 4, stream );
+		if( n ) coarseVoxels( levelsDown, minCount, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint32_t*)c.p, stream );
+		fetch( xyz, x, stream );
+		fetch( attribs, a, stream );
+		fetch( count, c, stream );
+	}
+	// dst (nullptr = this object: the in-place LOD) becomes the octree buildFromVoxels would build from that list at gridRes >> levelsDown with buildFlags, inside
+	// the same bounds.  Invalidates deviceView() snapshots of dst.
+	void coarsen( int levelsDown, uint64_t minCount = 1, int buildFlags = 0, IntersectorOctreeGPU* dst = nullptr, void* stream = nullptr )
+	{
+		IntersectorOctreeGPU* d = dst ? dst : this;
+		check( mvrt_svo_coarsen( m_handle, d->m_handle, levelsDown, minCount, buildFlags, stream ), "IntersectorOctreeGPU::coarsen" );
+		d->refresh();
+	}
+
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const

@@ -91,6 +91,8 @@ SIGNATURES = {
     "mvrt_svo_surface_merged_masked": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_enclosed_cells": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_fill_enclosed": (_i32, [_vp, _vp, _vp, _vp]),
+    "mvrt_svo_coarse_voxels": (_i32, [_vp, _i32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_coarsen": (_i32, [_vp, _vp, _i32, _u64, _i32, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
     "mvrt_svo_device_view": (_i32, [_vp, _vp]),
@@ -431,6 +433,30 @@ class IntersectorOctreeGPU:
         n = C.c_uint64(0)
         _check(lib().mvrt_svo_fill_enclosed(self._h, _hp(a), C.byref(n), stream))
         return n.value
+
+    def coarse_voxels_device(self, levels_down, min_count=1, capacity=0, xyz=None, attribs=None, count=None, stream=None):
+        """mvrt_svo_coarse_voxels into caller device arrays of `capacity` cells (any may be None; all None = the sizing call); returns the number of kept cells.
+        On MvrtError nothing was written."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_coarse_voxels(self._h, int(levels_down), int(min_count), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(count), C.byref(n), stream))
+        return n.value
+
+    def coarse_voxels(self, levels_down, min_count=1, stream=None):
+        """the voxel set `levels_down` levels coarser: the cells (x >> k, y >> k, z >> k) that hold at least min_count voxels, in ascending Morton order:
+        {xyz (n, 3) uint32 coarse coordinates, attribs (n, 8) uint8 = the integer mean per channel with alpha 255, count (n,) uint32 fine voxels per cell}"""
+        n = self.coarse_voxels_device(levels_down, min_count, stream=stream)
+        xyz, at, cnt = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint32)
+        if n:
+            self.coarse_voxels_device(levels_down, min_count, n, xyz, at, cnt, stream)
+        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "count": cnt.to_host()}
+
+    def coarsen(self, levels_down, min_count=1, flags=0, dst=None, stream=None):
+        """mvrt_svo_coarsen: dst (None = this object, the in-place LOD) becomes the octree build_voxels would build from coarse_voxels() at gridRes >> levels_down
+        with `flags` (BUILD_NO_DAG | BUILD_NO_EMBEDDED_MASK), same lower and upper bounds, dps * 2^levels_down.  Returns dst.  Invalidates device_view()
+        snapshots of dst."""
+        dst = self if dst is None else dst
+        _check(lib().mvrt_svo_coarsen(self._h, dst._h, int(levels_down), int(min_count), int(flags), stream))
+        return dst
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""

@@ -617,6 +617,52 @@ MVRT_EXPORT int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribH
 	return 0;
 }
 
+// A coarser level of detail (kernels_coarsen.hip).  Every refusal is made here, on the host: first what the arguments alone decide, then the handle.  The listing
+// reads the sorted codes and the attributes alone; the build hands the list, which stays on the device, to the levels of the voxel-list build.
+static int coarsenSource( const mvrt_svo* svo, const char* who, int levelsDown, uint64_t minCount )
+{
+	REQUIRE( levelsDown >= 1 && levelsDown <= 20, "%s: levelsDown %d is outside [1, log2( gridRes ) - 1] (20 at most, for gridRes 2^21)", who, levelsDown );
+	REQUIRE( minCount >= 1 && minCount <= coarseCellCapacity( levelsDown ), "%s: minCount %llu is outside [1, 8^levelsDown = %llu]", who, (unsigned long long)minCount,
+			 (unsigned long long)coarseCellCapacity( levelsDown ) );
+	REQUIRE( !svo->empty(), "%s: no octree (build first)", who );
+	REQUIRE( svo->oct.morton.p, "%s: an uploaded octree keeps no Morton codes", who );
+	const int L = (int)svo->oct.info.levels;
+	REQUIRE( levelsDown <= L - 1, "%s: levelsDown %d is outside [1, %d] = [1, log2( gridRes ) - 1] for gridRes %u", who, levelsDown, L - 1, svo->oct.info.gridRes );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_coarse_voxels( const mvrt_svo* svo, int levelsDown, uint64_t minCount, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev,
+										uint64_t* nOut, void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_coarse_voxels: null handle" );
+	if( coarsenSource( svo, "mvrt_svo_coarse_voxels", levelsDown, minCount ) ) return 1;
+	const Octree& o = svo->oct;
+	return coarseVoxels( o.morton.as<uint64_t>(), o.attrs.as<uint2>(), o.nVoxels, levelsDown, minCount, capacity, xyzDev, attribsDev, countDev, nOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levelsDown, uint64_t minCount, int buildFlags, void* stream )
+{
+	REQUIRE( src && dst, "mvrt_svo_coarsen: null handle" );
+	REQUIRE( ( buildFlags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0,
+			 "mvrt_svo_coarsen: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", buildFlags );
+	if( coarsenSource( src, "mvrt_svo_coarsen", levelsDown, minCount ) ) return 1;
+	const mvrt_svo_info info = src->oct.info; // (a copy: dst may be src)
+	const float dps = info.dps * (float)( 1u << levelsDown ); // exact: a power of two
+	REQUIRE( dps - dps == 0.0f, "mvrt_svo_coarsen: dps %g times 2^%d is not finite", (double)info.dps, levelsDown );
+	const int gridRes = (int)( info.gridRes >> levelsDown );
+	const uint32_t nFine = src->oct.nVoxels;
+	hipStream_t st = (hipStream_t)stream;
+	if( ownerDrain( dst ) ) return 1; // steps already issued render the old scene
+	DevBuf morton, attrs;
+	uint32_t nKept = 0, he = 0;
+	if( coarseList( src->oct.morton.as<uint64_t>(), src->oct.attrs.as<uint2>(), nFine, levelsDown, minCount, morton, attrs, &nKept, &he, st ) ) return 1;
+	REQUIRE( nKept >= 1, "mvrt_svo_coarsen: minCount %llu would leave no voxel (no coarse cell holds that many of the %u voxels)", (unsigned long long)minCount, nFine );
+	SvoBuildResult r;
+	if( svoBuildFromSorted( morton, attrs, nKept, gridRes, buildFlags, st, &r ) ) return 1;
+	r.hasEmission = he;
+	r.totalDumped = nFine;
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	return adoptBuild( dst, r, origin, dps, gridRes, buildFlags ); // (the source is read before the old octree of dst goes)
+}
+
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );

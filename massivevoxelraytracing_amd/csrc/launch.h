@@ -206,6 +206,16 @@ int enclosedCellsUnordered( const SurfaceSource& s, DevBuf& xyz, uint64_t* nCell
 int surfaceExteriorMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, uint64_t* nHiddenOut, hipStream_t stream );
 int launchFillAttribs( uint2 attrib, uint64_t n, uint2* out, hipStream_t stream ); // n copies of one VoxelAttirb.  Not synchronised.
 
+// coarse cells (kernels_coarsen.hip; mvrt_svo_coarse_voxels / mvrt_svo_coarsen): the n >= 1 sorted codes and Morton-ordered attributes of a build, levelsDown in
+// [1, levels - 1] and minCount in [1, coarseCellCapacity( levelsDown )], all checked by the caller.  The calls block, keep their scratch in DevBufs and write
+// NOTHING to the caller's arrays unless they succeed.
+uint64_t coarseCellCapacity( int levelsDown ); // 8^levelsDown, the fine voxels one coarse cell can hold (levelsDown <= 20)
+int coarseVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev,
+				  uint32_t* countDev, uint64_t* nOut, hipStream_t stream );
+// the same list as sorted codes and attributes for svoBuildFromSorted (both allocated here; left empty when no cell is kept: the caller looks at *nKept)
+int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
+				hipStream_t stream );
+
 // octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
 // flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.
 struct WalkSource

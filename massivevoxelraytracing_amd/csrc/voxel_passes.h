@@ -7,6 +7,8 @@
 //                   nthSetBit picks the bit.
 //   rows and gaps   gapLength / gapNodeOfCell on the sorted linear keys of kernels_fill.hip: the empty run between two voxels of a row, and the run an empty cell
 //                   lies in.  Host-callable, so that a host program checks them against brute force (tests/hip/exterior_host.hip).
+//   coarse cells    coarseHead on the shifted codes and the per-cell finish of kernels_coarsen.hip: coarseKeep, coarseAttrib (the integer means of 64-bit sums) and
+//                   coarseMaxCount.  Host-callable as well (tests/hip/coarsen_host.hip).
 //   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
 //                   entries -> rank + 1 of every entry and the number of runs).  Each allocates its output itself, runs hipcub through withCubTemp and has waited
 //                   for the stream when it returns.
@@ -64,6 +66,28 @@ MVRT_HDI uint32_t gapNodeOfCell( const uint64_t* __restrict__ lin, uint32_t n, u
 	if( j == 0 || j >= n ) return 0u;
 	const uint64_t row = key >> L;
 	return ( lin[j - 1] >> L ) == row && ( lin[j] >> L ) == row ? (uint32_t)j : 0u;
+}
+
+// ---- coarse cells (kernels_coarsen.hip) -----------------------------------------------------------------------------------------------------------------------
+// codes: the n sorted voxel codes, shift = 3 * levelsDown <= 60.  The coarse cell of a voxel is code >> shift, still ascending: a cell is one run of entries, and
+// entry i starts one when it is the first of the list or its cell differs from its predecessor's.  Host-callable like the gap helpers (tests/hip/coarsen_host.hip).
+MVRT_HDI bool coarseHead( const uint64_t* __restrict__ codes, uint64_t i, uint32_t shift ) { return i == 0 || ( codes[i] >> shift ) != ( codes[i - 1] >> shift ); }
+// the fine voxels a coarse cell can hold, 8^levelsDown: the largest legal minCount (levelsDown <= 20: up to 2^60)
+MVRT_HDI uint64_t coarseMaxCount( uint32_t levelsDown ) { return 1ull << ( 3u * levelsDown ); }
+MVRT_HDI bool coarseKeep( uint64_t count, uint64_t minCount ) { return count >= minCount; }
+// floor( sum / count ) for count >= 1 and sum <= 255 * count; the 32-bit division where both fit (nearly every cell), the quotient is the same
+MVRT_HDI uint32_t coarseMean( uint64_t sum, uint64_t count )
+{
+	return ( ( sum | count ) >> 32 ) == 0 ? (uint32_t)sum / (uint32_t)count : (uint32_t)( sum / count );
+}
+// the attribute of a cell from the exact sums of R, G, B of colour (sums[0..2]) and of emission (sums[3..5]) over its count voxels: the reference's unique rule
+// (voxKernel.cu:201-210) with sums that cannot overflow; both alpha bytes are 255
+MVRT_HDI uint2 coarseAttrib( const uint64_t sums[6], uint64_t count )
+{
+	uint2 a;
+	a.x = coarseMean( sums[0], count ) | coarseMean( sums[1], count ) << 8 | coarseMean( sums[2], count ) << 16 | 255u << 24;
+	a.y = coarseMean( sums[3], count ) | coarseMean( sums[4], count ) << 8 | coarseMean( sums[5], count ) << 16 | 255u << 24;
+	return a;
 }
 
 // ---- host steps -------------------------------------------------------------------------------------------------------------------------------------------
