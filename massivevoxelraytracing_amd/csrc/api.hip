@@ -891,7 +891,7 @@ MVRT_EXPORT int mvrt_compact_indices( const uint8_t* keepDev, uint64_t n, uint32
 		return 0;
 	}
 	DevBuf scratch;
-	if( scratch.alloc( ( n / 256 + 8 ) * 4 ) ) return 1; // (+ padding: the scan reads whole 16-byte quads)
+	if( scratch.alloc( ( scanCountEntries( n ) + scanTileEntries( n ) ) * 4 ) ) return 1; // block counts, then the tile sums of the scan (launch.h)
 	if( launchCompactIndices( keepDev, n, dstIndexDev, keptDev, scratch.as<uint32_t>(), (hipStream_t)stream ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( (hipStream_t)stream ) ); // scratch is freed on return
 	return 0;

@@ -511,12 +511,13 @@ static uint64_t carveWork( uintptr_t base, uint64_t cap, uint64_t nBlocks, PtBuf
 	b.liveCount = (uint32_t*)take( 64 * 4 );
 	b.cursors = (unsigned long long*)take( 16 * 8 );
 	b.selfDev = (const PtBuffers*)take( sizeof( PtBuffers ) );
+	b.tileBase = (uint32_t*)take( scanTileEntries( cap ) * 4 );
 	return off;
 }
 int mvrt_pt::allocWorkSlot( Slot& sl )
 {
 	const uint64_t cap = frame.ownedPixels * MVRT_SPP_PER_STEP * effectiveBatch();
-	const uint64_t nBlocks = cap / 256 + 8; // (+ padding: the scan reads whole 16-byte quads)
+	const uint64_t nBlocks = scanCountEntries( cap ); // (padded: the scan reads whole 16-byte quads)
 	PtBuffers measured;
 	const uint64_t bytes = carveWork( 0, cap, nBlocks, measured );
 	if( sl.work.alloc( bytes ) ) return 1;
@@ -1009,7 +1010,7 @@ MVRT_EXPORT int mvrt_pt_set_sample_mask( mvrt_pt* pt, void* stream, const uint8_
 	// built aside: a failure leaves the mask that is in force (or none) in force, and the steps in flight go on reading the list they were launched with
 	const uint64_t n = fr.validOwnedPixels;
 	DevBuf list, scratch;
-	const uint64_t rankBytes = ( n * 4 + 255 ) & ~(uint64_t)255, blockBytes = ( ( n / 256 + 8 ) * 4 + 255 ) & ~(uint64_t)255; // (+ padding: the scan reads whole 16-byte quads)
+	const uint64_t rankBytes = ( n * 4 + 255 ) & ~(uint64_t)255, blockBytes = ( ( scanCountEntries( n ) + scanTileEntries( n ) ) * 4 + 255 ) & ~(uint64_t)255; // (counts, then tile sums)
 	if( list.alloc( fr.ownedPixels * 4 ) || scratch.alloc( rankBytes + blockBytes + 4 ) ) return 1;
 	uint32_t* kept = (uint32_t*)( scratch.as<uint8_t>() + rankBytes + blockBytes );
 	uint32_t count = 0;

@@ -318,65 +318,84 @@ MVRT_DI uint32_t blockRank( bool keep, uint32_t* waveCnt /* LDS, 4 entries */ )
 	return off + inWave;
 }
 
-// exclusive scan of blockCount[0..nBlocks) in place by ONE workgroup of 1024 threads; total -> *totalOut.
-// nBlocks is read from device memory when nDev != null (n = *nDev items).  Tiles of 4096 counts: every thread owns four consecutive counts
-// (one 16-byte load and store, coalesced), scans them, the workgroup scans the 1024 thread sums (wave shuffles + 16 wave totals in LDS) and a
-// running total carries over to the next tile.  The count arrays are padded to a multiple of 4 entries (allocWorkSlot, mvrt_compact_indices).
-template <int THREADS>
-__global__ void __launch_bounds__( THREADS ) kScanBlockCounts( uint32_t* __restrict__ blockCount, uint64_t nItemsHost, const uint32_t* __restrict__ nItemsDev,
-															 uint32_t* __restrict__ totalOut, unsigned long long* __restrict__ rayStats = nullptr, int nKinds = 0, int shadowKind = 0 )
+// The survivor scan: two launches of one-wave workgroups that declare NO LDS and never wait for one another (a launch boundary is the only ordering).
+//   kScanTiles: wave t scans tile t -- MVRT_SCAN_TILE (T = 256) consecutive block counts -- in place and writes the tile's sum to tileBase[t];
+//   kScanTop:   one wave scans the tile sums in place, 256 (C: 64 lanes x 4) per iteration with a running carry, and writes the grand total.
+// The offset of block vb is then blockCount[vb] + tileBase[vb / T] (scanOffset).  Every lane owns four consecutive entries: one 16-byte load and store, coalesced;
+// both arrays are padded to whole quads (scanCountEntries / scanTileEntries, launch.h).  The item count is read from device memory when nItemsDev != null:
+// the grid is sized for the host's upper bound and tiles past the end exit.
+// Why one-wave workgroups without LDS: the persistent traversal waves of the sibling pass hold all 160 KiB of a CU's LDS and all but 112 VGPRs of every SIMD
+// until their launch tail; a single wave that asks for no LDS is the unit that still finds a slot there.
+#define SCAN_TOP_TILES 256 // C: tile sums one kScanTop iteration takes
+// exclusive scan, in place and plus `carry`, of the up to 256 entries a[base .. min( base + 256, n )) by one wave; returns their sum to every lane
+MVRT_DI uint32_t waveScan256( uint32_t* __restrict__ a, uint32_t base, uint32_t n, uint32_t lane, uint32_t carry )
 {
-	__shared__ uint32_t waveTot[THREADS / WAVE];
-	__shared__ uint32_t carryLds;
-	uint64_t nItems = nItemsDev ? (uint64_t)*nItemsDev : nItemsHost;
+	const uint32_t i0 = base + lane * 4;
+	uint4 c = make_uint4( 0u, 0u, 0u, 0u );
+	if( i0 < n ) c = *(const uint4*)( a + i0 ); // entries past n inside the last quad are padding: masked below
+	if( i0 + 1 >= n ) c.y = 0u;
+	if( i0 + 2 >= n ) c.z = 0u;
+	if( i0 + 3 >= n ) c.w = 0u;
+	const uint32_t mine = c.x + c.y + c.z + c.w;
+	uint32_t incl = mine; // inclusive scan of the lane sums
+	for( int o = 1; o < WAVE; o <<= 1 )
+	{
+		const uint32_t v = __shfl_up( incl, o, WAVE );
+		if( (int)lane >= o ) incl += v;
+	}
+	const uint32_t e0 = carry + incl - mine;
+	if( i0 + 3 < n ) *(uint4*)( a + i0 ) = make_uint4( e0, e0 + c.x, e0 + c.x + c.y, e0 + c.x + c.y + c.z );
+	else if( i0 < n ) // the last, partial quad: nothing is written past n
+	{
+		a[i0] = e0;
+		if( i0 + 1 < n ) a[i0 + 1] = e0 + c.x;
+		if( i0 + 2 < n ) a[i0 + 2] = e0 + c.x + c.y;
+	}
+	return __shfl( incl, WAVE - 1, WAVE );
+}
+__global__ void __launch_bounds__( WAVE ) kScanTiles( uint32_t* __restrict__ blockCount, uint64_t nItemsHost, const uint32_t* __restrict__ nItemsDev, uint32_t* __restrict__ tileBase )
+{
+	const uint64_t nItems = nItemsDev ? (uint64_t)*nItemsDev : nItemsHost;
+	const uint32_t nBlocks = (uint32_t)( ( nItems + CBLOCK - 1 ) / CBLOCK );
+	const uint32_t nTiles = ( nBlocks + MVRT_SCAN_TILE - 1 ) / MVRT_SCAN_TILE;
+	for( uint32_t tile = blockIdx.x; tile < nTiles; tile += gridDim.x )
+	{
+		const uint32_t sum = waveScan256( blockCount, tile * MVRT_SCAN_TILE, nBlocks, threadIdx.x, 0u );
+		if( threadIdx.x == 0 ) tileBase[tile] = sum;
+	}
+}
+__global__ void __launch_bounds__( WAVE ) kScanTop( uint32_t* __restrict__ tileBase, uint64_t nItemsHost, const uint32_t* __restrict__ nItemsDev, uint32_t* __restrict__ totalOut,
+													unsigned long long* __restrict__ rayStats, int nKinds, int shadowKind )
+{
+	const uint64_t nItems = nItemsDev ? (uint64_t)*nItemsDev : nItemsHost;
 	if( rayStats && threadIdx.x == 0 ) // ray accounting of the stage that was just traced (intersect() calls)
 	{
 		atomicAdd( &rayStats[0], (unsigned long long)nItems * nKinds );
 		if( shadowKind ) atomicAdd( &rayStats[1], (unsigned long long)nItems );
 	}
 	const uint32_t nBlocks = (uint32_t)( ( nItems + CBLOCK - 1 ) / CBLOCK );
-	const uint32_t lane = threadIdx.x & ( WAVE - 1 ), wave = threadIdx.x / WAVE;
+	const uint32_t nTiles = ( nBlocks + MVRT_SCAN_TILE - 1 ) / MVRT_SCAN_TILE;
 	uint32_t carry = 0;
-	for( uint32_t base = 0; base < nBlocks; base += THREADS * 4 )
-	{
-		const uint32_t i0 = base + threadIdx.x * 4;
-		uint4 c = make_uint4( 0u, 0u, 0u, 0u );
-		if( i0 < nBlocks ) c = *(const uint4*)( blockCount + i0 ); // entries past nBlocks inside the last quad are padding: masked below
-		if( i0 + 1 >= nBlocks ) c.y = 0u;
-		if( i0 + 2 >= nBlocks ) c.z = 0u;
-		if( i0 + 3 >= nBlocks ) c.w = 0u;
-		const uint32_t mine = c.x + c.y + c.z + c.w;
-		uint32_t incl = mine; // inclusive scan of the thread sums inside the wave
-		for( int o = 1; o < WAVE; o <<= 1 )
-		{
-			const uint32_t v = __shfl_up( incl, o, WAVE );
-			if( (int)lane >= o ) incl += v;
-		}
-		if( lane == WAVE - 1 ) waveTot[wave] = incl;
-		__syncthreads();
-		uint32_t before = carry;
-		for( uint32_t w = 0; w < wave; w++ ) before += waveTot[w];
-		if( threadIdx.x == THREADS - 1 ) carryLds = before + incl;
-		const uint32_t e0 = before + incl - mine;
-		if( i0 + 3 < nBlocks ) *(uint4*)( blockCount + i0 ) = make_uint4( e0, e0 + c.x, e0 + c.x + c.y, e0 + c.x + c.y + c.z );
-		else if( i0 < nBlocks ) // the last, partial quad: nothing is written past nBlocks
-		{
-			blockCount[i0] = e0;
-			if( i0 + 1 < nBlocks ) blockCount[i0 + 1] = e0 + c.x;
-			if( i0 + 2 < nBlocks ) blockCount[i0 + 2] = e0 + c.x + c.y;
-		}
-		__syncthreads();
-		carry = carryLds;
-		__syncthreads();
-	}
+	for( uint32_t base = 0; base < nTiles; base += SCAN_TOP_TILES ) carry += waveScan256( tileBase, base, nTiles, threadIdx.x, carry );
 	if( threadIdx.x == 0 && totalOut ) *totalOut = carry;
+}
+// first stable slot of block vb after the two launches
+MVRT_DI uint32_t scanOffset( const uint32_t* __restrict__ blockCount, const uint32_t* __restrict__ tileBase, uint64_t vb ) { return blockCount[vb] + tileBase[vb / MVRT_SCAN_TILE]; }
+// nItems: the host's count or, with nItemsDev, its upper bound
+static void launchScan( uint32_t* blockCount, uint32_t* tileBase, uint64_t nItems, const uint32_t* nItemsDev, uint32_t* totalOut, unsigned long long* rayStats, int nKinds, int shadowKind,
+						hipStream_t stream )
+{
+	const uint64_t nBlocks = ( nItems + CBLOCK - 1 ) / CBLOCK, nTiles = ( nBlocks + MVRT_SCAN_TILE - 1 ) / MVRT_SCAN_TILE;
+	hipLaunchKernelGGL( kScanTiles, dim3( (uint32_t)( nTiles ? nTiles : 1 ) ), dim3( WAVE ), 0, stream, blockCount, nItemsDev ? (uint64_t)0 : nItems, nItemsDev, tileBase );
+	hipLaunchKernelGGL( kScanTop, dim3( 1 ), dim3( WAVE ), 0, stream, tileBase, nItemsDev ? (uint64_t)0 : nItems, nItemsDev, totalOut, rayStats, nKinds, shadowKind );
 }
 
 __global__ void __launch_bounds__( CBLOCK ) kCountFlags( const uint8_t* __restrict__ keep, uint64_t n, uint32_t* __restrict__ blockCount )
 {
 	blockCountBody( [=]( uint64_t i ) { return keep[i] != 0; }, n, blockCount );
 }
-__global__ void __launch_bounds__( CBLOCK ) kRankFlags( const uint8_t* __restrict__ keep, uint64_t n, const uint32_t* __restrict__ blockOffset, uint32_t* __restrict__ dstIndex )
+__global__ void __launch_bounds__( CBLOCK ) kRankFlags( const uint8_t* __restrict__ keep, uint64_t n, const uint32_t* __restrict__ blockOffset, const uint32_t* __restrict__ tileBase,
+													   uint32_t* __restrict__ dstIndex )
 {
 	__shared__ uint32_t waveCnt[CBLOCK / WAVE];
 	const uint64_t nBlocks = ( n + CBLOCK - 1 ) / CBLOCK;
@@ -385,16 +404,18 @@ __global__ void __launch_bounds__( CBLOCK ) kRankFlags( const uint8_t* __restric
 		uint64_t i = vb * CBLOCK + threadIdx.x;
 		bool k = i < n ? keep[i] != 0 : false;
 		uint32_t r = blockRank( k, waveCnt );
-		if( i < n ) dstIndex[i] = k ? blockOffset[vb] + r : 0xFFFFFFFFu;
+		if( i < n ) dstIndex[i] = k ? scanOffset( blockOffset, tileBase, vb ) + r : 0xFFFFFFFFu;
 	}
 }
 
+// blockScratch: scanCountEntries( n ) + scanTileEntries( n ) entries, 16-byte aligned
 int launchCompactIndices( const uint8_t* keep, uint64_t n, uint32_t* dstIndex, uint32_t* kept, uint32_t* blockScratch, hipStream_t stream )
 {
 	int grid = persistentGrid( n, CBLOCK, numCUs(), 8 );
+	uint32_t* tileBase = blockScratch + scanCountEntries( n );
 	hipLaunchKernelGGL( kCountFlags, dim3( grid ), dim3( CBLOCK ), 0, stream, keep, n, blockScratch );
-	hipLaunchKernelGGL( kScanBlockCounts<1024>, dim3( 1 ), dim3( 1024 ), 0, stream, blockScratch, n, (const uint32_t*)nullptr, kept, (unsigned long long*)nullptr, 0, 0 );
-	hipLaunchKernelGGL( kRankFlags, dim3( grid ), dim3( CBLOCK ), 0, stream, keep, n, blockScratch, dstIndex );
+	launchScan( blockScratch, tileBase, n, nullptr, kept, nullptr, 0, 0, stream );
+	hipLaunchKernelGGL( kRankFlags, dim3( grid ), dim3( CBLOCK ), 0, stream, keep, n, blockScratch, tileBase, dstIndex );
 	MVRT_HIP( hipGetLastError() );
 	return 0;
 }
@@ -725,10 +746,13 @@ MVRT_DI f3 voxelEmission( const SvoDev& s, uint32_t vIndex, bool withScale ) // 
 #ifndef MVRT_SHADE_WAVES
 #define MVRT_SHADE_WAVES 5 // waves per SIMD the shade kernel is register-budgeted for
 #endif
+// One-wave workgroups, no LDS, no barrier: a wave owns one 256-path block (CBLOCK and blockCount keep their meaning) and walks it as four 64-lane sub-blocks.
+// The stable slot of a survivor is the block's scanned offset + the survivors of the earlier sub-blocks (a running scalar count) + its ballot rank.  One-wave
+// workgroups find room beside the persistent traversal waves of the sibling pass, which hold all of a CU's LDS and most of its registers until their launch tail:
+// the pipelined frame gains 1.0-1.5 % although the kernel alone is 12-18 % slower than the 256-thread form it replaces (profiles/r13_coresident_shade.txt).
 template <int WAVES, class... ACTIVE> // WAVES = register budget: waves per SIMD the kernel is compiled for
-__global__ void __launch_bounds__( CBLOCK, WAVES ) kPtShade( PtParams P, int stage, int inSet, ACTIVE... active )
+__global__ void __launch_bounds__( WAVE, WAVES ) kPtShade( PtParams P, int stage, int inSet, ACTIVE... active )
 {
-	__shared__ uint32_t waveCnt[CBLOCK / WAVE];
 	const uint64_t n = P.buf.liveCount[stage];
 	const PathSet& in = P.buf.set[inSet];
 	const PathSet& out = P.buf.set[inSet ^ 1];
@@ -736,129 +760,139 @@ __global__ void __launch_bounds__( CBLOCK, WAVES ) kPtShade( PtParams P, int sta
 	const uint64_t nBlocks = ( n + CBLOCK - 1 ) / CBLOCK;
 	for( uint64_t vb = blockIdx.x; vb < nBlocks; vb += gridDim.x )
 	{
-		const uint64_t i = vb * CBLOCK + threadIdx.x;
-		const bool valid = i < n;
-		bool alive = false;
-		uint32_t task = 0, vIndex = 0;
-		uint2 attr = make_uint2( 0u, 0u );
-		uint64_t hitPath = 0;
-		int nMajor = 0;
-		float t = MVRT_MAXF;
-		f3 ro, rd, T, L;
-		if( valid )
+		uint32_t blockOffset = 0; // (nothing survives stage 8: no slots, and the counts stay as they are)
+		if( !lastStage )
 		{
-			task = in.task[i];
-			ro = mk3( in.rox[i], in.roy[i], in.roz[i] );
-			rd = mk3( in.rdx[i], in.rdy[i], in.rdz[i] );
-			t = P.buf.hitT[i];
-			nMajor = P.buf.hitN[i];
-			const bool hit = t != MVRT_MAXF;
-			// the persistent traversal reports the hit voxel's path; its index is summed here, all lanes together
-			hitPath = hit ? P.buf.hitPath[i] : 0ull;
-			vIndex = hit ? voxelIndexFromPath( P.svo, hitPath ) : 0u;
-			if( hit ) attr = P.svo.attrs[vIndex]; // colour and emission of the hit voxel: one 8-byte gather serves both uses below
-			if( stage == 0 )
+			blockOffset = scanOffset( P.buf.blockCount, P.buf.tileBase, vb );
+			if( threadIdx.x == 0 ) P.buf.blockCount[vb] = 0u; // the next stage's traversal counts its survivors into it again
+		}
+#pragma unroll 1
+		for( uint64_t i = vb * CBLOCK + threadIdx.x; i < vb * CBLOCK + CBLOCK; i += WAVE ) // the four sub-blocks in turn (not unrolled: the body is ~2000 instructions)
+		{
+			if( i - threadIdx.x >= n ) break; // a sub-block past the end: uniform
+			const bool valid = i < n;
+			bool alive = false;
+			uint32_t task = 0, vIndex = 0;
+			uint2 attr = make_uint2( 0u, 0u );
+			uint64_t hitPath = 0;
+			int nMajor = 0;
+			float t = MVRT_MAXF;
+			f3 ro, rd, T, L;
+			if( valid )
 			{
-				T = mk3( 1.0f, 1.0f, 1.0f );
-				L = mk3( 0.0f, 0.0f, 0.0f );
-				if( !hit ) // voxKernel.cu:678-684
+				task = in.task[i];
+				ro = mk3( in.rox[i], in.roy[i], in.roz[i] );
+				rd = mk3( in.rdx[i], in.rdy[i], in.rdz[i] );
+				t = P.buf.hitT[i];
+				nMajor = P.buf.hitN[i];
+				const bool hit = t != MVRT_MAXF;
+				// the persistent traversal reports the hit voxel's path; its index is summed here, all lanes together
+				hitPath = hit ? P.buf.hitPath[i] : 0ull;
+				vIndex = hit ? voxelIndexFromPath( P.svo, hitPath ) : 0u;
+				if( hit ) attr = P.svo.attrs[vIndex]; // colour and emission of the hit voxel: one 8-byte gather serves both uses below
+				if( stage == 0 )
 				{
-					L = L + T * hdriSampleNearest( P.hdri, rd, true );
-				}
-				else // :685-689
-				{
-					L = L + T * rawReflectance( attr.y ); // (IntersectorOctreeGPU.hpp:256-259 without the scale)
-				}
-			}
-			else
-			{
-				T = mk3( in.Tx[i], in.Ty[i], in.Tz[i] );
-				L = mk3( in.Lx[i], in.Ly[i], in.Lz[i] );
-				if( P.hdriEnabled && P.buf.hitS[i] == 0 ) // :712-715, contribution computed when the ray was generated
-				{
-					L = L + mk3( in.nx[i], in.ny[i], in.nz[i] );
-				}
-				if( stage == 1 && P.extraSamples ) // :722-738
-				{
-					if( P.buf.hitE[i] )
+					T = mk3( 1.0f, 1.0f, 1.0f );
+					L = mk3( 0.0f, 0.0f, 0.0f );
+					if( !hit ) // voxKernel.cu:678-684
 					{
-						const uint32_t ev = voxelIndexFromPath( P.svo, P.buf.hitEPath[i] );
-						f3 Le = voxelEmission( P.svo, ev, true );
-						L = L + T * Le / (float)( 1 + P.extraSamples );
+						L = L + T * hdriSampleNearest( P.hdri, rd, true );
+					}
+					else // :685-689
+					{
+						L = L + T * rawReflectance( attr.y ); // (IntersectorOctreeGPU.hpp:256-259 without the scale)
 					}
 				}
-				if( hit ) // :750-759
+				else
 				{
-					f3 Le = rawReflectance( attr.y ) * P.svo.emissionScale; // IntersectorOctreeGPU.hpp:256-259
-					L = L + T * Le * ( stage == 1 ? 1.0f / (float)( 1 + P.extraSamples ) : 1.0f );
+					T = mk3( in.Tx[i], in.Ty[i], in.Tz[i] );
+					L = mk3( in.Lx[i], in.Ly[i], in.Lz[i] );
+					if( P.hdriEnabled && P.buf.hitS[i] == 0 ) // :712-715, contribution computed when the ray was generated
+					{
+						L = L + mk3( in.nx[i], in.ny[i], in.nz[i] );
+					}
+					if( stage == 1 && P.extraSamples ) // :722-738
+					{
+						if( P.buf.hitE[i] )
+						{
+							const uint32_t ev = voxelIndexFromPath( P.svo, P.buf.hitEPath[i] );
+							f3 Le = voxelEmission( P.svo, ev, true );
+							L = L + T * Le / (float)( 1 + P.extraSamples );
+						}
+					}
+					if( hit ) // :750-759
+					{
+						f3 Le = rawReflectance( attr.y ) * P.svo.emissionScale; // IntersectorOctreeGPU.hpp:256-259
+						L = L + T * Le * ( stage == 1 ? 1.0f / (float)( 1 + P.extraSamples ) : 1.0f );
+					}
+				}
+				alive = hit && !lastStage;
+				if( !alive )
+				{
+					P.buf.Lsx[task] = L.x;
+					P.buf.Lsy[task] = L.y;
+					P.buf.Lsz[task] = L.z;
 				}
 			}
-			alive = hit && !lastStage;
-			if( !alive )
+			if( lastStage ) continue; // nothing survives stage 8; uniform across the grid
+			const unsigned long long aliveLanes = __ballot( alive );
+			const uint32_t rank = __popcll( aliveLanes & ( ( 1ull << threadIdx.x ) - 1ull ) );
+			const uint32_t slotBase = blockOffset; // first slot of this sub-block's survivors
+			blockOffset += __popcll( aliveLanes );
+			if( alive )
 			{
-				P.buf.Lsx[task] = L.x;
-				P.buf.Lsy[task] = L.y;
-				P.buf.Lsz[task] = L.z;
+				const uint64_t j = (uint64_t)slotBase + rank;
+				// depth = stage of the reference loop
+				uint32_t step, localPixel, localSpp;
+				decodeTask( P.frame, task, &step, &localPixel, &localSpp );
+				const uint32_t spp = ( P.frame.iteration + step ) * MVRT_SPP_PER_STEP + localSpp;
+				const uint32_t stream = hashCombine2( 0u, globalPixel( P.frame, slotPixel( localPixel, active... ) ) );
+				int dim = dimBase( stage, P.hdriEnabled, P.extraSamples );
+				const f3 R = rawReflectance( attr.x ); // :693
+				const f3 hitN = getHitN( nMajor, rd );				  // :694
+				const f3 hitP = ro + rd * t;						  // :695
+				f3 nee = mk3( 0.0f, 0.0f, 0.0f );
+				if( P.hdriEnabled ) // :697-716
+				{
+					f2 u01 = pmjSample2d( P.pmj, spp, dim++, stream );
+					f2 u23 = pmjSample2d( P.pmj, spp, dim++, stream );
+					f3 sdir, emissive;
+					float p;
+					hdriImportanceSample( P.hdri, &sdir, &emissive, &p, hitN, u01.x, u01.y, u23.x, u23.y );
+					nee = T * ( R / MVRT_PI ) * smax( dot3( hitN, sdir ), 0.0f ) * emissive / p;
+					P.buf.sx[j] = sdir.x;
+					P.buf.sy[j] = sdir.y;
+					P.buf.sz[j] = sdir.z;
+				}
+				T = T * R;								// :718
+				if( stage == 0 && P.extraSamples ) // :721-726
+				{
+					f2 u = pmjSample2d( P.pmj, spp, dim++, stream );
+					f3 edir = sampleLambertian( u.x, u.y, hitN );
+					P.buf.ex[j] = edir.x;
+					P.buf.ey[j] = edir.y;
+					P.buf.ez[j] = edir.z;
+				}
+				f2 u = pmjSample2d( P.pmj, spp, dim++, stream ); // :741-745
+				f3 bdir = sampleLambertian( u.x, u.y, hitN );
+				out.task[j] = task;
+				if( P.svo.embedded ) out.org[j] = hintFromVoxelPath( hitPath, P.svo.levels ); // the rays of the next stage start on this voxel
+				out.rox[j] = hitP.x;
+				out.roy[j] = hitP.y;
+				out.roz[j] = hitP.z;
+				out.rdx[j] = bdir.x;
+				out.rdy[j] = bdir.y;
+				out.rdz[j] = bdir.z;
+				out.Tx[j] = T.x;
+				out.Ty[j] = T.y;
+				out.Tz[j] = T.z;
+				out.Lx[j] = L.x;
+				out.Ly[j] = L.y;
+				out.Lz[j] = L.z;
+				out.nx[j] = nee.x;
+				out.ny[j] = nee.y;
+				out.nz[j] = nee.z;
 			}
-		}
-		if( lastStage ) continue; // nothing survives stage 8; uniform across the grid
-		const uint32_t rank = blockRank( alive, waveCnt );
-		const uint32_t blockOffset = P.buf.blockCount[vb];
-		__syncthreads();
-		if( threadIdx.x == 0 ) P.buf.blockCount[vb] = 0u; // the next stage's traversal counts its survivors into it again
-		if( alive )
-		{
-			const uint64_t j = (uint64_t)blockOffset + rank;
-			// depth = stage of the reference loop
-			uint32_t step, localPixel, localSpp;
-			decodeTask( P.frame, task, &step, &localPixel, &localSpp );
-			const uint32_t spp = ( P.frame.iteration + step ) * MVRT_SPP_PER_STEP + localSpp;
-			const uint32_t stream = hashCombine2( 0u, globalPixel( P.frame, slotPixel( localPixel, active... ) ) );
-			int dim = dimBase( stage, P.hdriEnabled, P.extraSamples );
-			const f3 R = rawReflectance( attr.x ); // :693
-			const f3 hitN = getHitN( nMajor, rd );				  // :694
-			const f3 hitP = ro + rd * t;						  // :695
-			f3 nee = mk3( 0.0f, 0.0f, 0.0f );
-			if( P.hdriEnabled ) // :697-716
-			{
-				f2 u01 = pmjSample2d( P.pmj, spp, dim++, stream );
-				f2 u23 = pmjSample2d( P.pmj, spp, dim++, stream );
-				f3 sdir, emissive;
-				float p;
-				hdriImportanceSample( P.hdri, &sdir, &emissive, &p, hitN, u01.x, u01.y, u23.x, u23.y );
-				nee = T * ( R / MVRT_PI ) * smax( dot3( hitN, sdir ), 0.0f ) * emissive / p;
-				P.buf.sx[j] = sdir.x;
-				P.buf.sy[j] = sdir.y;
-				P.buf.sz[j] = sdir.z;
-			}
-			T = T * R;								// :718
-			if( stage == 0 && P.extraSamples ) // :721-726
-			{
-				f2 u = pmjSample2d( P.pmj, spp, dim++, stream );
-				f3 edir = sampleLambertian( u.x, u.y, hitN );
-				P.buf.ex[j] = edir.x;
-				P.buf.ey[j] = edir.y;
-				P.buf.ez[j] = edir.z;
-			}
-			f2 u = pmjSample2d( P.pmj, spp, dim++, stream ); // :741-745
-			f3 bdir = sampleLambertian( u.x, u.y, hitN );
-			out.task[j] = task;
-			if( P.svo.embedded ) out.org[j] = hintFromVoxelPath( hitPath, P.svo.levels ); // the rays of the next stage start on this voxel
-			out.rox[j] = hitP.x;
-			out.roy[j] = hitP.y;
-			out.roz[j] = hitP.z;
-			out.rdx[j] = bdir.x;
-			out.rdy[j] = bdir.y;
-			out.rdz[j] = bdir.z;
-			out.Tx[j] = T.x;
-			out.Ty[j] = T.y;
-			out.Tz[j] = T.z;
-			out.Lx[j] = L.x;
-			out.Ly[j] = L.y;
-			out.Lz[j] = L.z;
-			out.nx[j] = nee.x;
-			out.ny[j] = nee.y;
-			out.nz[j] = nee.z;
 		}
 	}
 }
@@ -1073,16 +1107,10 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 			PROF_END();
 		}
 		PROF_BEGIN( MVRT_K_OTHER );
-		// survivors per block were counted by the traversal's result stores; scan them (and account the rays)
-		// (a 256-thread workgroup: a 1024-thread one needs all 16 wave slots of one CU at once and waits -- up to a millisecond, measured on a tile share -- while the
-		// traversal waves of a sibling pass hold them)
-		static const int scanThreads = (int)mvrtKnob( "MVRT_SCAN_THREADS", 256 );
-		if( scanThreads == 1024 )
-			hipLaunchKernelGGL( kScanBlockCounts<1024>, dim3( 1 ), dim3( 1024 ), 0, stream, buf.blockCount, (uint64_t)0, (const uint32_t*)( buf.liveCount + stage ),
-								stage < MVRT_MAX_DEPTH ? buf.liveCount + stage + 1 : (uint32_t*)nullptr, buf.stats, nKinds, shadowKind );
-		else
-			hipLaunchKernelGGL( kScanBlockCounts<256>, dim3( 1 ), dim3( 256 ), 0, stream, buf.blockCount, (uint64_t)0, (const uint32_t*)( buf.liveCount + stage ),
-								stage < MVRT_MAX_DEPTH ? buf.liveCount + stage + 1 : (uint32_t*)nullptr, buf.stats, nKinds, shadowKind );
+		// survivors per block were counted by the traversal's result stores; scan them (and account the rays).  One-wave workgroups without LDS: they find a
+		// wave slot on a CU whose LDS the traversal waves of a sibling pass hold
+		launchScan( buf.blockCount, buf.tileBase, nSamples, (const uint32_t*)( buf.liveCount + stage ), stage < MVRT_MAX_DEPTH ? buf.liveCount + stage + 1 : (uint32_t*)nullptr, buf.stats,
+					nKinds, shadowKind, stream );
 		PROF_END();
 		PROF_BEGIN( MVRT_K_SHADE );
 		{
@@ -1094,13 +1122,15 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 			// The grid-stride grids hold exactly the workgroups that are RESIDENT at once (8 / 5 per CU): r02 launched 8 per CU for the 5-wave build too, and the three
 			// that had to wait for a slot ran as a second, thin round -- most of what the 8-wave build seemed to gain.  5-wave build with 8 / 6 / 5 workgroups per CU:
 			// dragon 16.6 / 14.1 / 14.0 ms of shade time per 4 serial steps, cave 133.7 / 132.3 / 129.2
+			// (since the kernel holds no LDS its workgroups are single waves, each owning one 256-path block: the same 32 / 20 resident waves per CU as 32 / 20 workgroups)
 			static const int bpc8 = (int)mvrtKnob( "MVRT_SHADE_BPC8", 8 ), bpc5 = (int)mvrtKnob( "MVRT_SHADE_BPC5", 5 );
 			const bool dense8 = ( ( dense >> stage ) & 1 ) != 0;
-			if( active ) launchMaskedShade( dense8, persistentGrid( nSamples, CBLOCK, nCUs, dense8 ? bpc8 : bpc5 ), stream, P, stage, setIdx, active );
+			const int wpc = ( dense8 ? bpc8 : bpc5 ) * ( CBLOCK / WAVE ); // waves per CU
+			if( active ) launchMaskedShade( dense8, persistentGrid( nSamples, CBLOCK, nCUs, wpc ), stream, P, stage, setIdx, active );
 			else if( dense8 )
-				hipLaunchKernelGGL( kPtShade<8>, dim3( persistentGrid( nSamples, CBLOCK, nCUs, bpc8 ) ), dim3( CBLOCK ), 0, stream, P, stage, setIdx );
+				hipLaunchKernelGGL( kPtShade<8>, dim3( persistentGrid( nSamples, CBLOCK, nCUs, wpc ) ), dim3( WAVE ), 0, stream, P, stage, setIdx );
 			else
-				hipLaunchKernelGGL( kPtShade<MVRT_SHADE_WAVES>, dim3( persistentGrid( nSamples, CBLOCK, nCUs, bpc5 ) ), dim3( CBLOCK ), 0, stream, P, stage, setIdx );
+				hipLaunchKernelGGL( kPtShade<MVRT_SHADE_WAVES>, dim3( persistentGrid( nSamples, CBLOCK, nCUs, wpc ) ), dim3( WAVE ), 0, stream, P, stage, setIdx );
 		}
 		PROF_END();
 		if( buf.dbgTasks && stage < MVRT_MAX_DEPTH ) // debug capture: the compacted survivor list this stage wrote (parity of the compaction indices)
@@ -1138,8 +1168,8 @@ static void launchMaskedGenerate( int grid, hipStream_t stream, const PtParams& 
 }
 static void launchMaskedShade( bool dense8, int grid, hipStream_t stream, const PtParams& P, int stage, int setIdx, const uint32_t* active )
 {
-	if( dense8 ) hipLaunchKernelGGL( ( kPtShade<8, const uint32_t*> ), dim3( grid ), dim3( CBLOCK ), 0, stream, P, stage, setIdx, active );
-	else hipLaunchKernelGGL( ( kPtShade<MVRT_SHADE_WAVES, const uint32_t*> ), dim3( grid ), dim3( CBLOCK ), 0, stream, P, stage, setIdx, active );
+	if( dense8 ) hipLaunchKernelGGL( ( kPtShade<8, const uint32_t*> ), dim3( grid ), dim3( WAVE ), 0, stream, P, stage, setIdx, active );
+	else hipLaunchKernelGGL( ( kPtShade<MVRT_SHADE_WAVES, const uint32_t*> ), dim3( grid ), dim3( WAVE ), 0, stream, P, stage, setIdx, active );
 }
 // frameBuffer: the frame-buffer addition; aov: that of the two feature buffers
 static void launchMaskedAccumulate( int grid, hipStream_t stream, const PtParams& P, float4* frameBuffer, const AovBuffers* aov, const uint32_t* active )

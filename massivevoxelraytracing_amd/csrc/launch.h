@@ -27,14 +27,21 @@ struct PtBuffers
 	uint64_t* hitPath;	// kind 0: voxel path (persistent traversal; vIndex is derived by the shade kernel)
 	uint64_t* hitEPath; // kind 2: voxel path
 	float *Lsx, *Lsy, *Lsz; // final radiance per sample, indexed by task (read by accumulate)
-	uint32_t* blockCount; // survivors per 256-path virtual block; exclusive-scanned in place
+	uint32_t* blockCount; // survivors per 256-path virtual block; exclusive-scanned in place inside its tile of MVRT_SCAN_TILE blocks (tileBase holds the rest)
 	uint32_t* liveCount;  // [stage] number of live paths entering stage k (0..9)
 	unsigned long long* cursors; // [16] per-stage ray cursors of the persistent traversal waves (zeroed by generate)
 	unsigned long long* stats; // [0] rays [1] shadowRays [2] descents [3] shadowDescents [4] hits [5] samples
 	uint64_t cap;
 	uint32_t* dbgTasks; // debug capture (host-side use only): [MVRT_MAX_DEPTH][cap] task ids of the survivors each shade stage wrote, in slot order
 	const PtBuffers* selfDev; // device-resident copy of this table (read with scalar loads where needed, see PtIO)
+	uint32_t* tileBase; // survivors in the scan tiles before each tile (exclusive scan of the tile sums); behind everything else: no older member moves
 };
+// The survivor scan (kernels_rt.hip): T = MVRT_SCAN_TILE block counts per tile.  A count array for n items holds scanCountEntries( n ) entries and its tile sums
+// scanTileEntries( n ): both are padded because the scan loads whole 16-byte quads, and the first is a multiple of 4 so that tile sums carved right behind the
+// counts stay 16-byte aligned.
+#define MVRT_SCAN_TILE 256
+static inline uint64_t scanCountEntries( uint64_t n ) { return ( n / 256 + 8 ) & ~(uint64_t)3; }
+static inline uint64_t scanTileEntries( uint64_t n ) { return ( n / 256 + 1 ) / MVRT_SCAN_TILE + 8; }
 
 struct PtFrame
 {

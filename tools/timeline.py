@@ -3,7 +3,7 @@
 import csv, glob, sys, os
 d = sys.argv[1]; last = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-rows = [r for r in csv.DictReader(open(f)) if r["Kernel_Name"].replace("void ", "").startswith(("kPt", "kScanBlock"))]
+rows = [r for r in csv.DictReader(open(f)) if r["Kernel_Name"].replace("void ", "").startswith(("kPt", "kScan"))]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 t0 = int(rows[0]["Start_Timestamp"])
 if last: rows = rows[-last:]
