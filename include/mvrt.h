@@ -481,7 +481,15 @@ int mvrt_pt_resize_framebuffer_if_needed( mvrt_pt* pt, void* stream, int width, 
 int mvrt_pt_clear_framebuffer( mvrt_pt* pt, void* stream );									 /* :98-102, steps = 0 */
 /* PathTracer::loadHDRI (:104-116) + HDRI::load/loadPrimary (renderCommon.hpp:214-326): decoded float4 pixels.
  * rgbaPrimaryHost may be NULL (then primary lookups use the lighting map's pixels AND size -- the reference
- * would read out of bounds, renderCommon.hpp:356-363).  A failed load leaves the map loaded before, or none, fully in place. */
+ * would read out of bounds, renderCommon.hpp:356-363).  A failed load leaves the map loaded before, or none, fully in place.
+ * Refused before any pointer is read or anything is allocated: a non-NULL primary with widthPrimary <= 0 or heightPrimary <= 0, and a lighting or
+ * primary map of 2^31 pixels or more (pixels are indexed with 32-bit integers).
+ * Zero tables (a second deviation): an importance table whose f64 total is not > 0 -- an all-black map, the -y table of a sky over a black ground,
+ * the tables of a 1x1 / 2x1 / 1x2 map whose axis no pixel centre faces -- is stored as all zeros; the reference normalises by the total and converts
+ * NaN to u32, which is undefined (voxKernel.cu:600-608).  Such a table selects nothing: where the hit normal picks it, next-event estimation
+ * returns L = 0 with pdf = 1 along the normal, so the contribution is exactly 0, the shadow ray is still traced (along the normal), the four sample
+ * dimensions are still consumed and the rest of the path is unchanged.  The reference would divide by zero in its row search and index about 2^32
+ * elements outside the table (renderCommon.hpp:367-435).  Maps without such a table are unaffected, bit for bit. */
 int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaHost, int width, int height, const float* rgbaPrimaryHost, int widthPrimary, int heightPrimary );
 /* same from Radiance .hdr files (RGBE, flat or RLE; value = c * 2^(E-136)); filePrimary may be NULL */
 int mvrt_pt_load_hdri_file( mvrt_pt* pt, void* stream, const char* file, const char* filePrimary );

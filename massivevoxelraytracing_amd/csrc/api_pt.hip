@@ -620,6 +620,10 @@ MVRT_EXPORT int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaH
 								   int heightPrimary )
 {
 	REQUIRE( pt && rgbaHost && width > 0 && height > 0, "mvrt_pt_load_hdri: bad image" );
+	// refused before a pointer is read or a byte allocated: the table kernels and the lookups index pixels with 32-bit integers
+	REQUIRE( !rgbaPrimaryHost || ( widthPrimary > 0 && heightPrimary > 0 ), "mvrt_pt_load_hdri: bad primary image size %dx%d", widthPrimary, heightPrimary );
+	REQUIRE( (uint64_t)width * height < ( 1ull << 31 ), "mvrt_pt_load_hdri: %dx%d is 2^31 pixels or more", width, height );
+	REQUIRE( !rgbaPrimaryHost || (uint64_t)widthPrimary * heightPrimary < ( 1ull << 31 ), "mvrt_pt_load_hdri: primary %dx%d is 2^31 pixels or more", widthPrimary, heightPrimary );
 	if( pt->drain() ) return 1;
 	hipStream_t st = (hipStream_t)stream;
 	const uint64_t n = (uint64_t)width * height;
@@ -627,13 +631,14 @@ MVRT_EXPORT int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaH
 	if( h.pixels.alloc( n * 16 ) ) return 1;
 	MVRT_HIP( hipMemcpyAsync( h.pixels.p, rgbaHost, n * 16, hipMemcpyHostToDevice, st ) );
 	DevBuf satF64;
-	if( satF64.alloc( n * 8 ) ) return 1;
+	if( satF64.alloc( ( n + 7 ) * 8 ) ) return 1; // the running table, then the seven totals
 	// renderCommon.hpp:243-311: uniform table, then one cosine-weighted table per axis
 	const f3 axes[6] = { mk3( 1, 0, 0 ), mk3( -1, 0, 0 ), mk3( 0, 1, 0 ), mk3( 0, -1, 0 ), mk3( 0, 0, 1 ), mk3( 0, 0, -1 ) };
 	for( int i = 0; i < 7; i++ )
 	{
 		if( h.sat[i].alloc( n * 4 ) ) return 1;
-		if( launchHdriSat( h.pixels.as<float4>(), width, height, satF64.as<double>(), h.sat[i].as<uint32_t>(), i > 0, i > 0 ? axes[i - 1] : mk3( 0, 0, 0 ), st ) ) return 1;
+		if( launchHdriSat( h.pixels.as<float4>(), width, height, satF64.as<double>(), h.sat[i].as<uint32_t>(), i > 0, i > 0 ? axes[i - 1] : mk3( 0, 0, 0 ), satF64.as<double>() + n + i, st ) )
+			return 1;
 	}
 	h.dev.pixels = h.pixels.as<float4>();
 	h.dev.sat = h.sat[0].as<uint32_t>();
@@ -650,6 +655,10 @@ MVRT_EXPORT int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaH
 		h.dev.heightPrimary = heightPrimary;
 	}
 	MVRT_HIP( hipStreamSynchronize( st ) ); // :313 (and satF64 is released on return)
+	double totals[7];
+	MVRT_HIP( hipMemcpy( totals, satF64.as<double>() + n, sizeof( totals ), hipMemcpyDeviceToHost ) );
+	for( int i = 0; i < 7; i++ ) // a table without a total > 0 is all zeros and selects nothing (mvrt.h): the shade kernel tests this bit, not memory
+		if( !( totals[i] > 0.0 ) ) h.dev.zeroTables |= 1u << i;
 	h.dev.scale = pt->hdri.dev.scale;
 	pt->hdri = std::move( h );
 	return 0;

@@ -672,13 +672,23 @@ MVRT_DI uint32_t satCount( const HdriDev& h, const uint32_t* s, uint32_t x, uint
 MVRT_DI void hdriImportanceSample( const HdriDev& h, f3* dir, f3* L, float* pdf, f3 N, float u0, float u1, float u2, float u3 )
 {
 	const uint32_t* s = h.sat;
+	uint32_t zero = h.zeroTables; // bit 0: the selected table is all zeros
 	const float k = 0.8f;
-	if( k < N.x ) s = h.sats[0];
-	else if( N.x < -k ) s = h.sats[1];
-	else if( k < N.y ) s = h.sats[2];
-	else if( N.y < -k ) s = h.sats[3];
-	else if( k < N.z ) s = h.sats[4];
-	else if( N.z < -k ) s = h.sats[5];
+	if( k < N.x ) s = h.sats[0], zero >>= 1;
+	else if( N.x < -k ) s = h.sats[1], zero >>= 2;
+	else if( k < N.y ) s = h.sats[2], zero >>= 3;
+	else if( N.y < -k ) s = h.sats[3], zero >>= 4;
+	else if( k < N.z ) s = h.sats[4], zero >>= 5;
+	else if( N.z < -k ) s = h.sats[5], zero >>= 6;
+	// Deviation from renderCommon.hpp:367-435: a table without a total > 0 selects nothing.  The reference would divide by vol == 0 and index about
+	// 2^32 elements away.  L = 0, pdf = 1, dir = N: the NEE term is exactly 0, the shadow ray is still emitted (along N) and nothing is read.
+	if( zero & 1u )
+	{
+		*dir = N;
+		*L = mk3( 0.0f, 0.0f, 0.0f );
+		*pdf = 1.0f;
+		return;
+	}
 
 	int i = 0, j = h.width; // upper_bound_f, renderCommon.hpp:182-202
 	while( i < j )

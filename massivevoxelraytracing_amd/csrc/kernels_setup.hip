@@ -333,19 +333,22 @@ __global__ void __launch_bounds__( SAT_BLOCK ) kSatScan( int w, int h, double* _
 		__syncthreads();
 	}
 }
-// buildSAT2u32, voxKernel.cu:600-608
-__global__ void kSatToU32( uint32_t* __restrict__ satU32, const double* __restrict__ satF64, int n )
+// buildSAT2u32, voxKernel.cu:600-608.  Deviation: a table whose total is not > 0 (a black map, a black hemisphere under a cosine weight, a map too
+// small to have a pixel centre on the axis' side) is stored as zeros -- the reference divides by it and converts NaN to u32, which is undefined.
+// totalOut receives the total, for the host's zero-table mask.
+__global__ void kSatToU32( uint32_t* __restrict__ satU32, const double* __restrict__ satF64, int n, double* __restrict__ totalOut )
 {
 	int i = blockIdx.x * blockDim.x + threadIdx.x;
 	double sum = satF64[n - 1];
-	if( i < n ) satU32[i] = (uint32_t)( satF64[i] / ( sum ) * (double)0xFFFFFFFFu );
+	if( i == 0 ) *totalOut = sum;
+	if( i < n ) satU32[i] = sum > 0.0 ? (uint32_t)( satF64[i] / ( sum ) * (double)0xFFFFFFFFu ) : 0u;
 }
-int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t* satOut, int cosWeighted, f3 axis, hipStream_t stream )
+int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t* satOut, int cosWeighted, f3 axis, double* totalOut, hipStream_t stream )
 {
 	hipLaunchKernelGGL( kHdriImportance, dim3( divUp( w, 8 ), divUp( h, 8 ) ), dim3( 8, 8 ), 0, stream, pixels, w, h, satF64, cosWeighted, axis );
 	hipLaunchKernelGGL( kSatScan, dim3( h ), dim3( SAT_BLOCK ), 0, stream, w, h, satF64, 1 );
 	hipLaunchKernelGGL( kSatScan, dim3( w ), dim3( SAT_BLOCK ), 0, stream, w, h, satF64, 0 );
-	hipLaunchKernelGGL( kSatToU32, dim3( divUp( (uint64_t)w * h, 64 ) ), dim3( 64 ), 0, stream, satOut, satF64, w * h );
+	hipLaunchKernelGGL( kSatToU32, dim3( divUp( (uint64_t)w * h, 64 ) ), dim3( 64 ), 0, stream, satOut, satF64, w * h, totalOut );
 	MVRT_HIP( hipGetLastError() );
 	return 0;
 }

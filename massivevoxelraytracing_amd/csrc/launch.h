@@ -136,7 +136,7 @@ int launchBuildPrefixRefs( const uint32_t* kids, uint32_t rootRef, uint32_t tabL
 // cell index of a build (SvoDev::cellBlocks / cellEntries) from its sorted voxel codes: number the occupied blocks (blocks[] preset to ~0, counter to 0), then fill the entries (zeroed)
 int launchNumberCellBlocks( const uint64_t* morton, uint64_t n, uint32_t cellBits, uint32_t* blocks, uint32_t* counterDev, hipStream_t stream );
 int launchFillCellIndex( const uint64_t* morton, uint64_t n, uint32_t cellBits, const uint32_t* blocks, uint2* entries, hipStream_t stream );
-int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t* satOut, int cosWeighted, f3 axis, hipStream_t stream );
+int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t* satOut, int cosWeighted, f3 axis, double* totalOut, hipStream_t stream );
 
 // GPU SVO construction (svo_build.hip)
 // What a build produces, and what an octree handle keeps of it (api_handles.h, Octree).  It owns its arrays: a builder that fails hands nothing over and leaks nothing

@@ -245,6 +245,7 @@ struct HdriDev
 	const uint32_t* sats[6]; // +x,-x,+y,-y,+z,-z
 	int width, height, widthPrimary, heightPrimary;
 	float scale;
+	uint32_t zeroTables; // bit i: table i (0 = uniform, 1..6 = sats[i-1]) has no total > 0 and is all zeros -- it selects nothing (mvrt.h, mvrt_pt_load_hdri)
 };
 
 // error plumbing -------------------------------------------------------------------------------------

@@ -1365,7 +1365,8 @@ struct HDRI
 		int n = m_width * m_height;
 		out.resize( n );
 		double sum = s[n - 1];
-		for( int i = 0; i < n; i++ ) out[i] = (uint32_t)( s[i] / ( sum ) * (double)0xFFFFFFFFu );
+		// Deviation from voxKernel.cu:600-608: a table whose total is not > 0 is stored as zeros (the reference converts NaN to u32: undefined)
+		for( int i = 0; i < n; i++ ) out[i] = sum > 0.0 ? (uint32_t)( s[i] / ( sum ) * (double)0xFFFFFFFFu ) : 0u;
 	}
 	// HDRI::load, renderCommon.hpp:214-314
 	void load( const float* rgba, int width, int height )
@@ -1436,6 +1437,15 @@ struct HDRI
 			else if( N.y < -k ) s = sats[3].data();
 			else if( k < N.z ) s = sats[4].data();
 			else if( N.z < -k ) s = sats[5].data();
+		}
+		// Deviation from renderCommon.hpp:367-435: a table without a total > 0 (all zeros, buildSAT) selects nothing -- L = 0, pdf = 1 and
+		// direction = N, so the NEE term is exactly 0 and nothing is indexed.  The reference divides by vol == 0 below and ends with Y = (uint32_t)-1.
+		if( s[(size_t)m_width * m_height - 1] == 0 )
+		{
+			*direction = N;
+			*L = float3{ 0.0f, 0.0f, 0.0f };
+			*srPDF = 1.0f;
+			return;
 		}
 		uint32_t X = upper_bound_f( [this, s]( int i ) { return (float)getPrefixSumExclusiveH( s, i ) / (float)0xFFFFFFFFu; }, m_width, u0 ) - 1;
 		uint32_t vol = getPrefixSumExclusiveH( s, X + 1 ) - getPrefixSumExclusiveH( s, X );
