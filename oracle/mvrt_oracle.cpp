@@ -1864,3 +1864,141 @@ ORC_API int orc_struct_sizes( int* out ) // SURVEY Appendix A struct sizes
 	out[4] = (int)sizeof( CameraPinhole );
 	return 5;
 }
+
+// ------------------------------------------------------------------------------------
+// Batch entry points of the renderer's sampling code, one per entry point of oracle/ref_shim_render.cpp (the compiled reference): same
+// arguments, so tests/test_reference_pins_cpu.py calls both sides alike.  mathMode as everywhere: 0 = libm, 1 = mvrt_detmath.h.
+// ------------------------------------------------------------------------------------
+static inline float3 degammaReflectance( const Math& M, uchar4 c ) // renderCommon.hpp:153-159 (not used by the path tracer, which shades with rawReflectance)
+{
+	return { M.pow_( (float)c.x / 255.0f, 2.2f ), M.pow_( (float)c.y / 255.0f, 2.2f ), M.pow_( (float)c.z / 255.0f, 2.2f ) };
+}
+static inline uint32_t gcd( uint32_t a, uint32_t b ) { return b == 0 ? a : gcd( b, a % b ); } // :484-489
+struct LCGShuffler // :493-514
+{
+	uint32_t a = 1, c = 0, n = 0;
+	uint32_t operator()( uint32_t i ) const { return ( static_cast<uint64_t>( i ) * a + c ) % n; }
+	bool tryInit( uint32_t r0, uint32_t r1, uint32_t numberOfElement )
+	{
+		a = r0;
+		c = r1;
+		n = numberOfElement;
+		return gcd( a, n ) == 1;
+	}
+};
+static inline float3 ld3( const float* p ) { return float3{ p[0], p[1], p[2] }; }
+static inline void st3( float* p, float3 v ) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+
+// px: n * 4 ints (x, y, W, H); fl: n * 4 floats (xo, yo, u0, u1)
+ORC_API void orc_camera_shoot_batch( const float* cam15, int64_t n, const int32_t* px, const float* fl, int thinLens, float* ro, float* rd )
+{
+	CameraPinhole c;
+	memcpy( &c, cam15, sizeof( c ) );
+	for( int64_t i = 0; i < n; i++ )
+	{
+		const int32_t* p = px + i * 4;
+		const float* f = fl + i * 4;
+		float3 o, d;
+		if( thinLens ) c.shootThinLens( &o, &d, p[0], p[1], f[0], f[1], p[2], p[3], f[2], f[3] );
+		else c.shoot( &o, &d, p[0], p[1], f[0], f[1], p[2], p[3] );
+		st3( ro + i * 3, o );
+		st3( rd + i * 3, d );
+	}
+}
+ORC_API void orc_uniformf_batch( int64_t n, const uint32_t* x, float* out )
+{
+	for( int64_t i = 0; i < n; i++ ) out[i] = uniformf( x[i] );
+}
+ORC_API void orc_orthonormal_basis( int64_t n, const float* z, float* xaxis, float* yaxis )
+{
+	for( int64_t i = 0; i < n; i++ )
+	{
+		float3 x, y;
+		GetOrthonormalBasis( ld3( z + i * 3 ), &x, &y );
+		st3( xaxis + i * 3, x );
+		st3( yaxis + i * 3, y );
+	}
+}
+ORC_API void orc_sample_lambertian_batch( int mathMode, int64_t n, const float* ab, const float* Ng, float* out )
+{
+	Math M = { mathMode };
+	for( int64_t i = 0; i < n; i++ ) st3( out + i * 3, sampleLambertian( M, ab[i * 2], ab[i * 2 + 1], ld3( Ng + i * 3 ) ) );
+}
+ORC_API void orc_get_spherical( int mathMode, int64_t n, const float* dir, float* out2 )
+{
+	Math M = { mathMode };
+	for( int64_t i = 0; i < n; i++ )
+	{
+		float2 s = getSpherical( M, ld3( dir + i * 3 ) );
+		out2[i * 2] = s.x;
+		out2[i * 2 + 1] = s.y;
+	}
+}
+ORC_API void orc_reflectance( int mathMode, int64_t n, const uint8_t* rgba, float* degamma, float* raw )
+{
+	Math M = { mathMode };
+	for( int64_t i = 0; i < n; i++ )
+	{
+		uchar4 c = { rgba[i * 4], rgba[i * 4 + 1], rgba[i * 4 + 2], rgba[i * 4 + 3] };
+		st3( degamma + i * 3, degammaReflectance( M, c ) );
+		st3( raw + i * 3, rawReflectance( c ) );
+	}
+}
+ORC_API void orc_luminance( int64_t n, const float* rgb, float* out )
+{
+	for( int64_t i = 0; i < n; i++ ) out[i] = luminance( ld3( rgb + i * 3 ) );
+}
+ORC_API void orc_upper_bound( const float* values, int nValues, int64_t n, const float* b, int32_t* out )
+{
+	for( int64_t i = 0; i < n; i++ ) out[i] = upper_bound_f( [values]( int k ) { return values[k]; }, nValues, b[i] );
+}
+ORC_API int orc_lcg_shuffler( uint32_t r0, uint32_t r1, uint32_t numberOfElement, int64_t n, const uint32_t* idx, uint32_t* out )
+{
+	LCGShuffler s;
+	bool ok = s.tryInit( r0, r1, numberOfElement );
+	for( int64_t i = 0; i < n; i++ ) out[i] = s( idx[i] );
+	return ok ? 1 : 0;
+}
+ORC_API void orc_pmj_sample2d_batch( const float* table, int64_t n, const uint32_t* sampleIdx, const uint32_t* dimension, const uint32_t* stream, float* out2 )
+{
+	for( int64_t i = 0; i < n; i++ )
+	{
+		float2 v = pmj_sample2d( table, sampleIdx[i], dimension[i], stream[i] );
+		out2[i * 2] = v.x;
+		out2[i * 2 + 1] = v.y;
+	}
+}
+ORC_API void orc_nested_uniform_scramble_batch( int64_t n, const uint32_t* x, const uint32_t* seed, uint32_t* out )
+{
+	for( int64_t i = 0; i < n; i++ ) out[i] = nested_uniform_scramble( x[i], seed[i] );
+}
+ORC_API void orc_scramble_f32_batch( int64_t n, const float* x, const uint32_t* seed, float* out )
+{
+	for( int64_t i = 0; i < n; i++ ) out[i] = scramble_f32( x[i], seed[i] );
+}
+// the math mode is the HDRI's (orc_hdri_create): its tables were built in it
+ORC_API void orc_hdri_importance_sample_batch( void* h, int64_t n, const float* N, int axisAligned, const float* u, float* direction, float* L, float* srPDF )
+{
+	const HDRI* H = (const HDRI*)h;
+	for( int64_t i = 0; i < n; i++ )
+	{
+		float3 d, l;
+		H->importanceSample( &d, &l, srPDF + i, ld3( N + i * 3 ), axisAligned != 0, u[i * 4], u[i * 4 + 1], u[i * 4 + 2], u[i * 4 + 3] );
+		st3( direction + i * 3, d );
+		st3( L + i * 3, l );
+	}
+}
+// which: 0 = uniform, 1..6 = +x,-x,+y,-y,+z,-z.  Points outside the ranges the readers may index give 0.
+ORC_API void orc_hdri_table_queries( void* h, int which, int64_t n, const uint32_t* xy, uint32_t* prefixH, uint32_t* prefixV, uint32_t* count )
+{
+	const HDRI* H = (const HDRI*)h;
+	const uint32_t* s = ( which == 0 ? H->sat : H->sats[which - 1] ).data();
+	const uint32_t w = (uint32_t)H->m_width, hh = (uint32_t)H->m_height;
+	for( int64_t i = 0; i < n; i++ )
+	{
+		uint32_t x = xy[i * 2], y = xy[i * 2 + 1];
+		prefixH[i] = x <= w ? H->getPrefixSumExclusiveH( s, x ) : 0;
+		prefixV[i] = ( x < w && y <= hh ) ? H->getPrefixSumExclusiveV( s, x, y ) : 0;
+		count[i] = ( x < w && y < hh ) ? H->getCount( s, x, y ) : 0;
+	}
+}

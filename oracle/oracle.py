@@ -2,8 +2,9 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 It wraps oracle/libmvrt_oracle.so (the C++ restatement, oracle/mvrt_oracle.cpp) and, when
-present, the two libraries of oracle/_ref/ that are compiled from the reference sources as they lie (libmvrt_ref.so: morton + Murmur;
-libmvrt_ref_walk.so: voxelizer context, octree builders, traversal and the small helpers of voxCommon.hpp).
+present, the three libraries of oracle/_ref/ that are compiled from the reference sources as they lie (libmvrt_ref.so: morton + Murmur;
+libmvrt_ref_walk.so: voxelizer context, octree builders, traversal and the small helpers of voxCommon.hpp; libmvrt_ref_render.so: the host
+branch of renderCommon.hpp and pmjSampler.hpp -- camera, PCG32, Lambert sampling, PMJ table and sample2d, HDRI::importanceSample).
 """
 import ctypes as C
 import os
@@ -15,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libmvrt_oracle.so")
 _REF = os.path.join(_HERE, "_ref", "libmvrt_ref.so")
 _REF_WALK = os.path.join(_HERE, "_ref", "libmvrt_ref_walk.so")
+_REF_RENDER = os.path.join(_HERE, "_ref", "libmvrt_ref_render.so")
 
 MAX_FLOAT = np.float32(3.402823466e38)
 PMJ_FLOATS = 2 * 4096 * 128
@@ -91,6 +93,20 @@ _detmath = _sig("orc_detmath_eval", None, [_i32, _vp, _vp, _i64, _vp])
 _sizes = _sig("orc_struct_sizes", _i32, [_vp])
 _voxelize_counts = _sig("orc_voxelize_counts", None, [_vp, _i64, _vp, _f32, _i32, _i32, _vp])
 _get_hit_n = _sig("orc_get_hit_n", None, [_i32, _vp, _vp])
+_cam_shoot_b = _sig("orc_camera_shoot_batch", None, [_vp, _i64, _vp, _vp, _i32, _vp, _vp])
+_uniformf_b = _sig("orc_uniformf_batch", None, [_i64, _vp, _vp])
+_basis = _sig("orc_orthonormal_basis", None, [_i64, _vp, _vp, _vp])
+_lambert_b = _sig("orc_sample_lambertian_batch", None, [_i32, _i64, _vp, _vp, _vp])
+_spherical = _sig("orc_get_spherical", None, [_i32, _i64, _vp, _vp])
+_reflectance = _sig("orc_reflectance", None, [_i32, _i64, _vp, _vp, _vp])
+_luminance = _sig("orc_luminance", None, [_i64, _vp, _vp])
+_upper_bound = _sig("orc_upper_bound", None, [_vp, _i32, _i64, _vp, _vp])
+_lcg = _sig("orc_lcg_shuffler", _i32, [_u32, _u32, _u32, _i64, _vp, _vp])
+_s2d_b = _sig("orc_pmj_sample2d_batch", None, [_vp, _i64, _vp, _vp, _vp, _vp])
+_nus_b = _sig("orc_nested_uniform_scramble_batch", None, [_i64, _vp, _vp, _vp])
+_scr_b = _sig("orc_scramble_f32_batch", None, [_i64, _vp, _vp, _vp])
+_hdri_is_b = _sig("orc_hdri_importance_sample_batch", None, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp])
+_hdri_q = _sig("orc_hdri_table_queries", None, [_vp, _i32, _i64, _vp, _vp, _vp, _vp])
 
 NODE_DTYPE = np.dtype([("mask", "u1"), ("_pad", "u1", 3), ("children", "<u4", 8), ("psum", "<u4", 8)])
 assert NODE_DTYPE.itemsize == 68
@@ -374,6 +390,22 @@ class HDRI:
         _hdri_is(self._h, _p(n), int(axis_aligned), _p(u), _p(d), _p(L), C.byref(pdf))
         return d, L, np.float32(pdf.value)
 
+    def importance_sample_batch(self, n, u, axis_aligned=True):
+        """n: (k, 3), u: (k, 4) -> direction (k, 3), L (k, 3), srPDF (k,)"""
+        n = np.ascontiguousarray(n, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 4)
+        assert len(n) == len(u)
+        d, L, pdf = np.zeros((len(n), 3), np.float32), np.zeros((len(n), 3), np.float32), np.zeros(len(n), np.float32)
+        _hdri_is_b(self._h, len(n), _p(n), int(axis_aligned), _p(u), _p(d), _p(L), _p(pdf))
+        return d, L, pdf
+
+    def table_queries(self, which, xy):
+        """getPrefixSumExclusiveH( x ), getPrefixSumExclusiveV( x, y ), getCount( x, y ) of table `which` at xy (k, 2) uint32"""
+        xy = np.ascontiguousarray(xy, np.uint32).reshape(-1, 2)
+        out = [np.zeros(len(xy), np.uint32) for _ in range(3)]
+        _hdri_q(self._h, which, len(xy), _p(xy), _p(out[0]), _p(out[1]), _p(out[2]))
+        return out
+
     def sample_nearest(self, d, is_primary):
         d = np.ascontiguousarray(d, np.float32)
         out = np.zeros(3, np.float32)
@@ -491,9 +523,193 @@ class RefWalk:
         return dict(zip(["OctreeNode", "StackElement", "OctreeTask", "VoxelAttirb"], (int(v) for v in out[:n])))
 
 
+def _c(a, dtype, cols=None):
+    a = np.ascontiguousarray(a, dtype)
+    return a if cols is None else a.reshape(-1, cols)
+
+
+class RenderOracle:
+    """The oracle's renderer sampling code behind the batch interface that RefRender gives the compiled reference: every method takes and
+    returns the same arrays (HDRI apart: the oracle builds its own tables, see O.HDRI).  math_mode 0: libm, 1: mvrt_detmath.h."""
+
+    def __init__(self, math_mode=0):
+        self.math_mode = int(math_mode)
+
+    def camera_shoot(self, cam, px, fl, thin_lens):
+        """cam: 15 floats; px (n, 4) int32 x, y, W, H; fl (n, 4) float32 xo, yo, u0, u1 -> ro, rd (n, 3)"""
+        cam, px, fl = _c(cam, np.float32), _c(px, np.int32, 4), _c(fl, np.float32, 4)
+        assert cam.size == 15 and len(px) == len(fl)
+        ro, rd = np.zeros((len(px), 3), np.float32), np.zeros((len(px), 3), np.float32)
+        self._camera_shoot(_p(cam), len(px), _p(px), _p(fl), int(thin_lens), _p(ro), _p(rd))
+        return ro, rd
+
+    def _camera_shoot(self, *a):
+        _cam_shoot_b(*a)
+
+    def pcg32(self, seed, stream, n):
+        return pcg32(seed, stream, n)
+
+    def uniformf(self, x):
+        x = _c(x, np.uint32)
+        out = np.zeros(len(x), np.float32)
+        self._call("uniformf", len(x), _p(x), _p(out))
+        return out
+
+    def orthonormal_basis(self, z):
+        z = _c(z, np.float32, 3)
+        xa, ya = np.zeros_like(z), np.zeros_like(z)
+        self._call("basis", len(z), _p(z), _p(xa), _p(ya))
+        return xa, ya
+
+    def sample_lambertian(self, ab, n):
+        ab, n = _c(ab, np.float32, 2), _c(n, np.float32, 3)
+        assert len(ab) == len(n)
+        out = np.zeros_like(n)
+        self._call("lambert", len(n), _p(ab), _p(n), _p(out), math=True)
+        return out
+
+    def get_spherical(self, d):
+        d = _c(d, np.float32, 3)
+        out = np.zeros((len(d), 2), np.float32)
+        self._call("spherical", len(d), _p(d), _p(out), math=True)
+        return out
+
+    def reflectance(self, rgba):
+        """-> degammaReflectance, rawReflectance (n, 3) of (n, 4) bytes"""
+        rgba = _c(rgba, np.uint8, 4)
+        dg, raw = np.zeros((len(rgba), 3), np.float32), np.zeros((len(rgba), 3), np.float32)
+        self._call("reflectance", len(rgba), _p(rgba), _p(dg), _p(raw), math=True)
+        return dg, raw
+
+    def luminance(self, rgb):
+        rgb = _c(rgb, np.float32, 3)
+        out = np.zeros(len(rgb), np.float32)
+        self._call("luminance", len(rgb), _p(rgb), _p(out))
+        return out
+
+    def upper_bound(self, values, b):
+        """upper_bound_f over f( i ) = values[i] for every b"""
+        values, b = _c(values, np.float32), _c(b, np.float32)
+        out = np.zeros(len(b), np.int32)
+        self._call("upper_bound", _p(values), len(values), len(b), _p(b), _p(out))
+        return out
+
+    def lcg_shuffler(self, r0, r1, n_elements, idx):
+        """-> (tryInit's answer, the shuffled indices)"""
+        idx = _c(idx, np.uint32)
+        out = np.zeros(len(idx), np.uint32)
+        ok = self._call("lcg", r0, r1, n_elements, len(idx), _p(idx), _p(out))
+        return bool(ok), out
+
+    def pmj_table(self):
+        return pmj_table()
+
+    def sample2d(self, table, sample_idx, dim, stream):
+        table = _c(table, np.float32)
+        assert table.size == PMJ_FLOATS
+        si, di, st = (_c(a, np.uint32) for a in (sample_idx, dim, stream))
+        assert len(si) == len(di) == len(st)
+        out = np.zeros((len(si), 2), np.float32)
+        self._call("sample2d", _p(table), len(si), _p(si), _p(di), _p(st), _p(out))
+        return out
+
+    def nested_uniform_scramble(self, x, seed):
+        x, seed = _c(x, np.uint32), _c(seed, np.uint32)
+        assert len(x) == len(seed)
+        out = np.zeros(len(x), np.uint32)
+        self._call("nus", len(x), _p(x), _p(seed), _p(out))
+        return out
+
+    def scramble_f32(self, x, seed):
+        x, seed = _c(x, np.float32), _c(seed, np.uint32)
+        assert len(x) == len(seed)
+        out = np.zeros(len(x), np.float32)
+        self._call("scramble", len(x), _p(x), _p(seed), _p(out))
+        return out
+
+    _FUNCS = {"uniformf": _uniformf_b, "basis": _basis, "lambert": _lambert_b, "spherical": _spherical, "reflectance": _reflectance, "luminance": _luminance,
+              "upper_bound": _upper_bound, "lcg": _lcg, "sample2d": _s2d_b, "nus": _nus_b, "scramble": _scr_b}
+
+    def _call(self, name, *args, math=False):
+        return self._FUNCS[name](*(((self.math_mode,) if math else ()) + args))
+
+
+class RefRender(RenderOracle):
+    """oracle/_ref/libmvrt_ref_render.so (oracle/ref_shim_render.cpp): the host branch of the reference's renderCommon.hpp and pmjSampler.hpp
+    behind batch entry points.  Its transcendentals are the C library's (math mode 0 of the oracle)."""
+
+    def __init__(self, path):
+        w = C.CDLL(path)
+        b = RefWalk._bind
+        self.math_mode = 0
+        self._shoot = b(w, "refr_camera_shoot", None, [_vp, _i64, _vp, _vp, _i32, _vp, _vp])
+        self._pcg = b(w, "refr_pcg32", None, [_u64, _u64, _i64, _vp])
+        self._table = b(w, "refr_pmj_table", None, [_vp])
+        self._is = b(w, "refr_hdri_importance_sample", None, [_vp, _i32, _i32, _vp, _f32, _i64, _vp, _i32, _vp, _vp, _vp, _vp])
+        self._q = b(w, "refr_hdri_table_queries", None, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp])
+        self._sizes = b(w, "refr_struct_sizes", _i32, [_vp])
+        self._f = {"uniformf": b(w, "refr_uniformf", None, [_i64, _vp, _vp]),
+                   "basis": b(w, "refr_orthonormal_basis", None, [_i64, _vp, _vp, _vp]),
+                   "lambert": b(w, "refr_sample_lambertian", None, [_i64, _vp, _vp, _vp]),
+                   "spherical": b(w, "refr_get_spherical", None, [_i64, _vp, _vp]),
+                   "reflectance": b(w, "refr_reflectance", None, [_i64, _vp, _vp, _vp]),
+                   "luminance": b(w, "refr_luminance", None, [_i64, _vp, _vp]),
+                   "upper_bound": b(w, "refr_upper_bound", None, [_vp, _i32, _i64, _vp, _vp]),
+                   "lcg": b(w, "refr_lcg_shuffler", _i32, [_u32, _u32, _u32, _i64, _vp, _vp]),
+                   "sample2d": b(w, "refr_pmj_sample2d", None, [_vp, _i64, _vp, _vp, _vp, _vp]),
+                   "nus": b(w, "refr_nested_uniform_scramble", None, [_i64, _vp, _vp, _vp]),
+                   "scramble": b(w, "refr_scramble_f32", None, [_i64, _vp, _vp, _vp])}
+        self._pmj = None
+
+    def _call(self, name, *args, math=False):
+        return self._f[name](*args)
+
+    def _camera_shoot(self, *a):
+        self._shoot(*a)
+
+    def pcg32(self, seed, stream, n):
+        out = np.zeros(n, np.uint32)
+        self._pcg(seed, stream, n, _p(out))
+        return out
+
+    def pmj_table(self):
+        """PMJSampler::setup( false, ... )'s table"""
+        if self._pmj is None:
+            t = np.zeros(PMJ_FLOATS, np.float32)
+            self._table(_p(t))
+            self._pmj = t
+        return self._pmj
+
+    def struct_sizes(self):
+        out = np.zeros(8, np.int32)
+        n = self._sizes(_p(out))
+        return dict(zip(["CameraPinhole", "PCG32", "PMJ_LENGTH", "PMJ_N_SEQUENCE"], (int(v) for v in out[:n])))
+
+    def hdri_importance_sample(self, rgba, w, h, tables7, scale, n, u, axis_aligned=True):
+        """HDRI::importanceSample over the caller's pixels (w * h, 4) and seven tables (uniform, +x, -x, +y, -y, +z, -z; w * h uint32 each).  The table
+        that a normal selects must have a total (its last entry non-zero): without one the reference indexes out of range."""
+        rgba = _c(rgba, np.float32, 4)
+        tabs = [_c(t, np.uint32) for t in tables7]
+        assert len(rgba) == w * h and len(tabs) == 7 and all(t.size == w * h for t in tabs)
+        n, u = _c(n, np.float32, 3), _c(u, np.float32, 4)
+        assert len(n) == len(u)
+        ptrs = (C.c_void_p * 7)(*[t.ctypes.data for t in tabs])
+        d, L, pdf = np.zeros((len(n), 3), np.float32), np.zeros((len(n), 3), np.float32), np.zeros(len(n), np.float32)
+        self._is(_p(rgba), w, h, ptrs, scale, len(n), _p(n), int(axis_aligned), _p(u), _p(d), _p(L), _p(pdf))
+        return d, L, pdf
+
+    def hdri_table_queries(self, table, w, h, xy):
+        table = _c(table, np.uint32)
+        assert table.size == w * h
+        xy = _c(xy, np.uint32, 2)
+        out = [np.zeros(len(xy), np.uint32) for _ in range(3)]
+        self._q(_p(table), w, h, len(xy), _p(xy), _p(out[0]), _p(out[1]), _p(out[2]))
+        return out
+
+
 def load_ref():
     """None where oracle/_ref holds no libmvrt_ref.so.  The returned library carries `.walk`: a RefWalk, or None where libmvrt_ref_walk.so
-    is absent."""
+    is absent, and `.render`: a RefRender, or None where libmvrt_ref_render.so is absent."""
     if not os.path.exists(_REF):
         return None
     r = C.CDLL(_REF)
@@ -503,4 +719,5 @@ def load_ref():
     for nm in ("ref_morton_decode_naive", "ref_morton_decode_pext", "ref_morton_decode_magicbits"):
         getattr(r, nm).argtypes = [_u64, _vp]
     r.walk = RefWalk(_REF_WALK) if os.path.exists(_REF_WALK) else None
+    r.render = RefRender(_REF_RENDER) if os.path.exists(_REF_RENDER) else None
     return r

@@ -1,5 +1,6 @@
 """Inputs, fixtures and the comparison rule of the pins against the COMPILED reference (oracle/_ref/libmvrt_ref_walk.so, built by `make -C oracle ref`
-from voxCommon.hpp, voxelization.hpp, morton.hpp and IntersectorOctree.hpp as they lie): tests/test_reference_pins_cpu.py (oracle == reference) and
+from voxCommon.hpp, voxelization.hpp, morton.hpp and IntersectorOctree.hpp as they lie, and libmvrt_ref_render.so, from the host branch of
+renderCommon.hpp and pmjSampler.hpp): tests/test_reference_pins_cpu.py (oracle == reference) and
 tests/test_gpu_reference_pins.py (kernels == reference).
 
 Where oracle/_ref is absent, the reference's answers are still known: a SHA-256 of each answer is stored in tests/golden/reference_pin_digests.json
@@ -376,3 +377,225 @@ def rays_of(O, name):
     if name not in _ray_sets:
         _ray_sets[name] = ray_set(ray_scene(O, name))
     return _ray_sets[name]
+
+
+# ---- the renderer's sampling code: oracle/_ref/libmvrt_ref_render.so ------------------------------------------------------------------------------
+BELOW1 = np.nextafter(f32(1), f32(0))  # the largest float below 1
+
+
+def load_render(O, tree_decides):
+    """the RefRender of oracle/_ref, or None; the rules of load_walk"""
+    ref = O.load_ref()
+    if tree_decides and os.path.isdir(REFERENCE_TREE):
+        assert ref is not None and ref.render is not None, "the reference tree is present but oracle/_ref is not built: run __graft_entry__.build() (make -C oracle ref)"
+    if ref is None:
+        return None
+    assert ref.render is not None, "oracle/_ref holds libmvrt_ref.so but not libmvrt_ref_render.so: rebuild it (make -C oracle ref)"
+    return ref.render
+
+
+def needs_libm(render, what):
+    """answers that pass through sinf / cosf / atan2f / powf depend on the host's C library: no digest is stored for them, and without the compiled
+    reference they skip by name"""
+    if render is None:
+        import pytest
+        pytest.skip(what + ": depends on the host's libm, compared only where oracle/_ref/libmvrt_ref_render.so is present")
+
+
+def cameras():
+    """{name: 15 floats}.  probe: an orthonormal look-at with a lens.  skew: a rotated basis that is neither orthogonal nor of unit length, with odd
+    values everywhere -- no product in shoot / shootThinLens is exact, so every association of the reference's expressions shows in the last bit."""
+    from common import probe_camera
+    rng = np.random.default_rng(71)
+    skew = np.zeros(15, f32)
+    skew[0:3] = (-3.7, 2.9, 11.3)
+    skew[3:12] = (rng.normal(size=9) * [1, 1, 1, 0.7, 0.7, 0.7, 1.3, 1.3, 1.3]).astype(f32)
+    skew[12], skew[13], skew[14] = f32(0.41421357), f32(0.037), f32(7.3)
+    return {"probe": probe_camera(np.zeros(3, f32), f32(1 / 64), 64, focus=9.0, lens_r=0.05), "skew": skew}
+
+
+CAMERA_SIZES = [(97, 61), (64, 40), (1, 1), (7, 5), (1920, 1080), (61, 97)]
+
+
+def camera_rays(n_random=400, seed=72):
+    """(px (n, 4) int32 x, y, W, H; fl (n, 4) float32 xo, yo, u0, u1): per image size, the four corner pixels with every combination of pixel offset and
+    lens sample in {0, the float below 1}, then random pixels with random offsets, a quarter of them with one offset / lens sample at an end"""
+    rng = np.random.default_rng(seed)
+    px, fl = [], []
+    ends = np.array([[a, b, c, d] for a in (0, BELOW1) for b in (0, BELOW1) for c in (0, BELOW1) for d in (0, BELOW1)], f32)
+    for W, H in CAMERA_SIZES:
+        for x in sorted({0, W - 1}):
+            for y in sorted({0, H - 1}):
+                px.append(np.tile(np.array([x, y, W, H], np.int32), (16, 1)))
+                fl.append(ends)
+        p = np.stack([rng.integers(0, W, n_random), rng.integers(0, H, n_random), np.full(n_random, W), np.full(n_random, H)], 1).astype(np.int32)
+        f = rng.random((n_random, 4), dtype=f32)
+        k = n_random // 4
+        f[np.arange(k), rng.integers(0, 4, k)] = np.where(rng.random(k) < 0.5, f32(0), BELOW1)
+        px.append(p)
+        fl.append(f)
+    return np.concatenate(px), np.concatenate(fl)
+
+
+def unit_normals(n, seed):
+    v = np.random.default_rng(seed).normal(size=(n, 3))
+    return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(f32)
+
+
+DENORMAL = f32(1e-45)
+SPECIAL_NORMALS = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1], [0, 0, -0.0], [1, 0, -0.0], [1, 0, DENORMAL], [0, 1, -DENORMAL],
+                            [0.6, 0.8, DENORMAL], [0.6, -0.8, -0.0], [0.6, 0, -0.8], [0, -0.6, 0.8]], f32)
+
+
+def lambert_inputs(n_random=20_000, seed=73):
+    """(ab (n, 2), normals (n, 3)): the special normals (both signs of every axis, z = -1 exactly, z = -0 and z a denormal of either sign) with a in
+    {0, 1, random} and b in {0, the float below 1, random}; then random unit normals with random a, b"""
+    rng = np.random.default_rng(seed)
+    ab = np.array([[a, b] for a in (0, 1, 0.37, BELOW1) for b in (0, BELOW1, 0.25, 0.5, 0.61)], f32)
+    n = np.repeat(SPECIAL_NORMALS, len(ab), 0)
+    ab = np.tile(ab, (len(SPECIAL_NORMALS), 1))
+    return np.concatenate([ab, rng.random((n_random, 2), dtype=f32)]), np.concatenate([n, unit_normals(n_random, seed + 1)])
+
+
+PT_DIMENSIONS = 28  # kPtGenerate uses dimensions 0 (pixel jitter) and 1 (lens); the shade kernel 2 .. 27: per bounce two for the light sample, one for the
+#                     bounce, at the first bounce one more for the extra direct sample (oracle/mvrt_oracle.cpp ptSample): 2 + 1 + 8 * 3 = 27 drawn at most
+
+
+def sample2d_inputs():
+    """(sampleIdx, dimension, stream) uint32 (n,): sample indices 0 .. 4095 and beyond the table's length, every dimension the path tracer draws and
+    dimensions beyond the 128 sequences, streams 0, 2^32 - 1 and two in between -- the full product"""
+    idx = np.concatenate([np.arange(4096), [4096, 4097, 8191, 65536, 2**31, 2**32 - 1]]).astype(np.uint32)
+    dim = np.concatenate([np.arange(PT_DIMENSIONS + 4), [127, 128, 129, 2**32 - 1]]).astype(np.uint32)
+    stream = np.array([0, 2**32 - 1, 0x9E3779B9, 1], np.uint32)
+    g = np.meshgrid(idx, dim, stream, indexing="ij")
+    return tuple(np.ascontiguousarray(a.reshape(-1)) for a in g)
+
+
+def hdri_map(name):
+    """(rgba, w, h) of the maps of tests/hdri_maps.py that the importance-sampling pins use"""
+    import hdri_maps as M
+    if name.startswith("noise"):
+        w, h = (int(v) for v in name[5:].split("x"))
+        return M.noise(w, h, seed=w * 1000 + h), w, h
+    return {"sun": lambda: (M.sun(520, 260), 520, 260), "black_ground": lambda: (M.black_ground(64, 32), 64, 32),
+            "denormal_floor": lambda: (M.denormal_floor(64, 32), 64, 32), "all_black": lambda: (M.all_black(8, 4), 8, 4)}[name]()
+
+
+HDRI_MAPS = ["noise1x1", "noise2x1", "noise1x2", "noise7x5", "noise64x32", "noise520x260", "sun", "black_ground", "denormal_floor"]
+K08 = f32(0.8)
+# normals on both sides of importanceSample's 0.8 threshold on every axis, exactly 0.8 included (k < N.x is false there: the next test decides), then
+# normals that select the uniform table
+HDRI_NORMALS = np.array([[s * v if a == 0 else 0, s * v if a == 1 else 0, s * v if a == 2 else 0] for a in range(3) for s in (1, -1)
+                         for v in (f32(1), np.nextafter(K08, f32(1)), K08, np.nextafter(K08, f32(0)))] + [[0.8, 0.9, 0], [-0.8, -0.8, -0.9], [0.5, 0.5, 0.70710678]], f32)
+
+
+def table_of_normal(n):
+    """which of the seven tables (0 uniform, 1 .. 6 = +x, -x, +y, -y, +z, -z) importanceSample( axisAligned ) takes for the normals n (k, 3): the chain of
+    renderCommon.hpp:371-398, restated on integers for the tests' bookkeeping only (which cases have a total); the compared values never pass through it"""
+    n = np.asarray(n, f32)
+    out = np.zeros(len(n), np.int32)
+    for which, (axis, positive) in reversed(list(enumerate([(0, True), (0, False), (1, True), (1, False), (2, True), (2, False)], 1))):
+        sel = (K08 < n[:, axis]) if positive else (n[:, axis] < -K08)
+        out[sel] = which
+    return out
+
+
+def hdri_inputs(tables7, w, h, n_random=1500, seed=74):
+    """(N (k, 3), u (k, 4)): for each normal of HDRI_NORMALS -- u0 / u1 at 0, at the float below 1 and ON entries of the table that the normal selects
+    (prefix / 0xFFFFFFFF rounded to float, where `value <= b` decides between two texels), u2 / u3 at 0 and below 1, then random u"""
+    rng = np.random.default_rng(seed)
+    which = table_of_normal(HDRI_NORMALS)
+    Ns, us = [], []
+    for N, t in zip(HDRI_NORMALS, which):
+        tab = np.asarray(tables7[t], np.uint32).reshape(h, w)
+        ends = [[a, b, c, d] for a in (0, BELOW1) for b in (0, BELOW1) for c in (0, BELOW1) for d in (0, BELOW1)]
+        row = tab[h - 1].astype(np.float64)
+        on_h = (row[rng.integers(0, w, 12)] .astype(f32) / f32(0xFFFFFFFF)).astype(f32)
+        on_h = on_h[on_h < 1]
+        on = [[v, rng.random(), rng.random(), rng.random()] for v in on_h] + [[np.nextafter(v, f32(0)), rng.random(), rng.random(), rng.random()] for v in on_h]
+        # u1 on an entry of the chosen column: V( X, y ) / vol as the reference forms it, for a few columns; u0 = the column's own start selects it
+        for x in rng.integers(0, w, 6):
+            lo = 0 if x == 0 else int(tab[h - 1, x - 1])
+            vol = (int(tab[h - 1, x]) - lo) & 0xFFFFFFFF
+            if vol == 0:
+                continue
+            u0 = f32(f32(lo) / f32(0xFFFFFFFF))
+            y = int(rng.integers(0, h))
+            v = (int(tab[y, x]) - (0 if x == 0 else int(tab[y, x - 1]))) & 0xFFFFFFFF
+            u1 = f32(f32(v) / f32(vol))
+            if u0 < 1 and u1 < 1:
+                on += [[u0, u1, rng.random(), rng.random()], [u0, np.nextafter(u1, f32(0)), rng.random(), rng.random()]]
+        u = np.concatenate([np.array(ends, f32), np.array(on, f32).reshape(-1, 4), rng.random((n_random // len(HDRI_NORMALS), 4), dtype=f32)])
+        Ns.append(np.tile(N, (len(u), 1)))
+        us.append(u)
+    return np.concatenate(Ns), np.concatenate(us)
+
+
+# ---- frames composed from the compiled reference alone (tests/test_gpu_reference_pins.py) ---------------------------------------------------------
+class ReferenceProvider:
+    """the provider of tests/aov_expected.py over the compiled reference: PMJSampler::sample2d on PMJSampler::setup's own table and
+    CameraPinhole::shootThinLens from the render library, octreeTraverse_EfficientParametric from the walk library"""
+
+    def __init__(self, render, walk):
+        self.render, self.walk = render, walk
+
+    def sample2d(self, sample_idx, dim, stream):
+        return self.render.sample2d(self.render.pmj_table(), sample_idx, dim, stream)
+
+    def shoot_thin_lens(self, cam, px, fl):
+        return self.render.camera_shoot(cam, px, fl, True)
+
+    def trace(self, sc, ro, rd):
+        lower, upper = sc.bounds()
+        return self.walk.trace(sc.nodes, lower, upper, ro, rd)
+
+
+_frame_scene = None
+
+
+def frame_scene(O):
+    """bunny at 64^3 with colours (the octree itself is pinned to the reference's builder by test_builder)"""
+    global _frame_scene
+    if _frame_scene is None:
+        from common import position_colors
+        tris = bunny_tris()
+        cols, emis = position_colors(tris)
+        _frame_scene = O.build_scene_from_triangles(tris, 64, cols, emis)
+    return _frame_scene
+
+
+def frame_cameras(sc):
+    """{name: 15 floats}, lensR 0.05: `outside` looks at the grid from far off (the probe camera), `inside` stands in the grid's upper corner region, within the
+    bounds, and looks across the model -- its rays start inside the root node"""
+    from common import probe_camera
+    ext = float(sc.dps) * sc.grid_res
+    return {"outside": probe_camera(sc.origin, sc.dps, sc.grid_res, focus=9.0, lens_r=0.05),
+            "inside": probe_camera(sc.origin, sc.dps, sc.grid_res, focus=0.5 * ext, lens_r=0.05, offset=(0.42 * ext, 0.38 * ext, 0.45 * ext))}
+
+
+PRIMARY_SIZES = [(97, 61), (64, 40)]
+
+
+def reference_primary(pair, sc, cam, W, H):
+    """the `render` kernel's rays composed from the reference: CameraPinhole::shoot through every pixel centre (voxKernel.cu:437-483 passes 0.5f, 0.5f), then
+    octreeTraverse_EfficientParametric -> [t, nMajor, vIndex]; a miss keeps MAX_FLOAT, -1, 0"""
+    render, walk = pair
+    p = np.arange(W * H)
+    px = np.stack([p % W, p // W, np.full(W * H, W), np.full(W * H, H)], 1).astype(np.int32)
+    fl = np.tile(np.array([0.5, 0.5, 0, 0], f32), (W * H, 1))
+    ro, rd = render.camera_shoot(cam, px, fl, False)
+    lower, upper = sc.bounds()
+    return list(walk.trace(sc.nodes, lower, upper, ro, rd).values())
+
+
+FIRST_HIT_SIZE = (64, 40)
+
+
+def reference_first_hit(pair, O, sc, cam):
+    """[normal/depth buffer (W * H, 4)] of one 16-spp step at 64x40 with the sampler, the thin-lens camera and the traversal of the compiled reference.
+    The buffer is no output of the reference (it has no such buffer): xyz is the sum of the first hits' axis normals and w the sum of their t, 16 sequential
+    float32 additions per pixel in ascending sample order from +0 (include/mvrt.h) -- that derivation is restated once, in tests/aov_expected.py."""
+    import aov_expected as A
+    exp = A.Expected(O, sc, *FIRST_HIT_SIZE, provider=ReferenceProvider(*pair))
+    exp.step(cam)
+    return [exp.normal_depth]

@@ -40,6 +40,8 @@ def compile_probe(out_dir, flags):
     lib.probe_trace.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11 + [C.c_int]
     lib.probe_attrs.restype = C.c_int
     lib.probe_attrs.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
+    lib.probe_camera.restype = C.c_int
+    lib.probe_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     return lib
 
 

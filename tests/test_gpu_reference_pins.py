@@ -4,12 +4,17 @@ triangles -- and the traversal on the ray set of tests/test_reference_pins_cpu.p
 of the reference written together with the kernels; these do not go through it.  Where oracle/_ref is absent the kernels must reproduce the stored
 SHA-256 of the reference's answer (tests/reference_pins.py::check).  All comparisons are exact.
 
+The renderer's sampling code is compared with oracle/_ref/libmvrt_ref_render.so (the host branch of renderCommon.hpp / pmjSampler.hpp) wherever no
+transcendental is involved: the PMJ table on the device, the device header's camera, the primary cast and the first-hit buffers of one path-tracing step,
+whose rays are the work of kPtGenerate (PMJ dimensions 0 and 1, their scrambles, the thin lens).
+
 Colours and emission are compared with the oracle, as everywhere: the reference's barycentric code (closestBarycentricCoordinateOnTriangle) sits in
 voxKernel.cu, which no host compiler here builds."""
 import numpy as np
 import pytest
 
 import reference_pins as R
+from common import hdr_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -100,3 +105,86 @@ def test_trace_batch(mv, O, walk, scene):
     got = svo.intersect(ro, rd, sh)
     R.check("trace/" + scene, [got["t"], got["nMajor"], got["vIndex"]], walk,
             lambda w: [x for x in w.trace(rs.nodes, rs.lower, rs.upper, ro, rd, sh).values()])
+
+
+# ---- the renderer's sampling code against oracle/_ref/libmvrt_ref_render.so, not through the oracle ------------------------------------------------
+@pytest.fixture(scope="module")
+def render(O):
+    return R.load_render(O, tree_decides=False)
+
+
+@pytest.fixture(scope="module")
+def pair(render, walk):
+    """(render library, walk library), or None where oracle/_ref is absent: then the stored digests of the same compositions stand in"""
+    return None if render is None or walk is None else (render, walk)
+
+
+def test_pmj_table_on_the_device(mv, render):
+    """the table as read back from the device equals the table of the reference's PMJSampler::setup( false, ... ), float by float"""
+    pt = mv.PathTracer()
+    pt.setup(None)
+    R.check("render/pmj_table", [pt.pmj_table()], render, lambda r: [r.pmj_table()])
+
+
+def test_device_camera(mv, render, tmp_path_factory):
+    """mvrt::CameraPinhole::shoot / shootThinLens of include/mvrt/device.hpp, run on the device by tests/hip/device_api_probe.hip: corner pixels, offsets and
+    lens samples at 0 and at the float below 1, odd and non-square sizes, an orthonormal and a skewed basis -- 2736 rays per camera and entry point"""
+    from test_gpu_device_api import compile_probe
+    probe = compile_probe(tmp_path_factory.mktemp("camera_probe"), [])
+    px, fl = R.camera_rays()
+    dpx, dfl = mv.DeviceArray.from_host(px), mv.DeviceArray.from_host(fl)
+    for name, cam in R.cameras().items():
+        for thin in (0, 1):
+            ro, rd = mv.DeviceArray((len(px), 3), np.float32), mv.DeviceArray((len(px), 3), np.float32)
+            assert probe.probe_camera(cam.ctypes.data, len(px), dpx.ptr, dfl.ptr, thin, ro.ptr, rd.ptr) == 0
+            R.check("render/camera/%s/%d" % (name, thin), [ro.to_host(), rd.to_host()], render, lambda r: list(r.camera_shoot(cam, px, fl, bool(thin))))
+
+
+@pytest.fixture(scope="module")
+def frame(mv, O):
+    sc = R.frame_scene(O)
+    svo = mv.IntersectorOctreeGPU()
+    svo.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission)
+    info = svo.info()
+    lower, upper = sc.bounds()
+    assert np.array_equal(np.array(info.lower[:], np.float32), lower) and np.array_equal(np.array(info.upper[:], np.float32), upper)
+    return sc, svo
+
+
+@pytest.mark.parametrize("size", R.PRIMARY_SIZES, ids=["%dx%d" % s for s in R.PRIMARY_SIZES])
+@pytest.mark.parametrize("cam", ["outside", "inside"])
+def test_primary_cast(mv, O, pair, frame, cam, size):
+    """render( ..., want_hits=True ) of the bunny at 64^3 against the reference composed here: shoot from the render library through every pixel centre, then
+    octreeTraverse_EfficientParametric from the walk library.  t by its bits, nMajor and vIndex on every pixel, misses included."""
+    sc, svo = frame
+    W, H = size
+    c = R.frame_cameras(sc)[cam]
+    got = svo.render(c, W, H, want_hits=True)
+    hit = got["t"] != R.MAXF
+    assert 0.1 < hit.mean() and (cam == "inside" or hit.mean() < 0.9) and len(np.unique(got["nMajor"][hit])) == 3
+    R.check("render/primary/%s/%dx%d" % (cam, W, H), [got["t"], got["nMajor"], got["vIndex"]], pair, lambda p: R.reference_primary(p, sc, c, W, H))
+
+
+@pytest.mark.parametrize("cam", ["outside", "inside"])
+def test_first_hit_buffers(mv, O, pair, frame, cam):
+    """the normal / depth buffer of one 16-spp step at 64x40, lensR 0.05, against rays built from the compiled reference alone: sample2d (dimensions 0 and 1,
+    stream = Murmur of the pixel, spp 0 .. 15) and shootThinLens from the render library, then the walk library's traversal.  This checks kPtGenerate's
+    dimensions, scrambles and thin lens against the reference directly.  Depth is a derived quantity: the buffer stores no single t but the sum of the 16
+    samples' first-hit t (and of their axis normals), added in ascending sample order in float32 -- tests/aov_expected.py restates that sum, once, for
+    the oracle's and the reference's rays alike; with the rays equal to the reference's, the sums are equal by their bits."""
+    sc, _ = frame
+    W, H = R.FIRST_HIT_SIZE
+    c = R.frame_cameras(sc)[cam]
+    assert c[13] == np.float32(0.05)
+    rgba, hw, hh = O.decode_rgbe(hdr_bytes())
+    pt = mv.PathTracer()
+    pt.setup(None)
+    pt.set_aovs(True)
+    pt.resizeFrameBufferIfNeeded(None, W, H)
+    pt.loadHDRIPixels(None, rgba, hw, hh, rgba, hw, hh)
+    pt.m_intersectorOctreeGPU.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission)
+    pt.step(None, c)
+    nd = pt.read_aov(pt.AOV_NORMAL_DEPTH)[: W * H]
+    hits = pt.read_aov(pt.AOV_ALBEDO)[: W * H, 3]
+    assert ((hits > 0) & (hits < 16)).sum() >= 30 and (hits == 16).sum() >= 100  # partly covered pixels: the order and the set of the samples matter
+    R.check("render/first_hit/" + cam, [nd], pair, lambda p: R.reference_first_hit(p, O, sc, c))

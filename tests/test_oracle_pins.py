@@ -241,7 +241,8 @@ def test_bunny2048_primary_hits_and_stack_depth():
 def test_render_pt_colour_independent_statistics():
     """The only reference-derived numbers that touch the per-sample path function (voxKernel.cu:648-760): the survey's emulated renderPT on the
     bunny at 256^3 (emissive scene, monks_forest_s.hdr for both maps, probe camera, lens radius 0.05, 256x144, iteration 0, libm) counted 1.51 rays
-    per sample, 5.7 descents per non-shadow ray and 13.4 per shadow ray.  The survey's colours, emissive set and focus distance are not recorded,
+    per sample, 5.7 descents per non-shadow ray and 13.4 per shadow ray.  The survey records its rules (position-derived colours, emissive voxels where
+    the y index exceeds 0.9 * res: SURVEY.md Appendix A) but applies them per voxel, and records no focus distance; this scene applies its own per vertex,
     so this is a WEAK pin: ray and descent counts do not depend on colours, and only slightly on which voxels emit and where the lens focuses --
     the oracle gives 1.54 / 5.84 / 13.39 with this repo's own choice of the three."""
     from common import position_colors
