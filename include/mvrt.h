@@ -374,8 +374,10 @@ int mvrt_trace_batch_hinted( const mvrt_svo* svo, uint64_t n, const float* roxDe
 							 uint32_t* descentsDev, void* stream );
 /* The same rays with a DISTANCE LIMIT per ray (new; every ray of the reference runs to infinity).  tMaxDev: n floats, required.  Ray i reports what mvrt_trace_batch
  * reports for it when that hit has t <= tMax[i] -- t is the traversal's own t, in units of rd -- and a miss (MVRT_MAX_FLOAT, -1, 0) otherwise, bit for bit for every
- * ray, the ones with zero direction components included.  A NaN tMax, 0 or a negative one therefore always gives a miss; MVRT_MAX_FLOAT and +inf give the unlimited
- * result.  The walk ends early once everything still to come is entered beyond the limit (by a margin that covers the rounding of the entry times);
+ * ray, the ones with zero direction components included.  A NaN tMax, 0 or a negative one therefore always gives a miss; +inf gives the unlimited result, and so
+ * does MVRT_MAX_FLOAT for every hit with a finite t.  The one difference: a ray without a direction (every component zero or denormal) can report a hit at
+ * t = +inf, as in the reference; inf <= MVRT_MAX_FLOAT is false, so that ray is a miss under MVRT_MAX_FLOAT and a hit under +inf.
+ * The walk ends early once everything still to come is entered beyond the limit (by a margin that covers the rounding of the entry times);
  * descentsDev (optional) = the child fetches the limited ray made: at most those of the unlimited ray, equal to them on a reported hit.
  * Arguments, outputs and asynchrony as for mvrt_trace_batch (nMajorDev, vIndexDev, descentsDev may be NULL).  Embedded and plain flavours, uploaded or built, up to
  * MVRT_DEVICE_MAX_LEVELS levels (the octrees mvrt_svo_device_view accepts: the kernel is the per-thread walk of include/mvrt/device.hpp); the tree flavour is
@@ -393,7 +395,8 @@ int mvrt_trace_batch_range( const mvrt_svo* svo, uint64_t n, const float* roxDev
  *   - Origin = the face centre.  With the voxel at integer (x, y, z), decoded from its Morton code: c2 = 2 * coord + 1 on the two in-plane axes, 2 * coord (-) or
  *     2 * coord + 2 (+) on the normal axis; ro[a] = lower[a] + (float)c2 * (0.5f * dps), each operation rounded, no FMA.  No offset along the normal: a hit
  *     needs 0 < t, which keeps a ray from hitting the voxel it leaves.
- *   - radius > 0 in the units of dps (the directions have unit length up to rounding); MVRT_MAX_FLOAT or +inf = unlimited (sky visibility).  NaN and values <= 0 are
+ *   - radius > 0 in the units of dps (the directions have unit length up to rounding); +inf = unlimited (sky visibility), and MVRT_MAX_FLOAT the same for the bake's
+ *     own rays, whose directions have unit length: a t of +inf needs a ray without a direction (mvrt_trace_batch_range above).  NaN and values <= 0 are
  *     refused on the host, as are other sample counts and NULL arrays (with nFaces > 0), all before the handle is looked at.
  *   - Handles as for mvrt_svo_surface_quads (an upload is refused: "keeps no Morton codes"; an empty handle: "no octree"), except the tree flavour, which is
  *     refused by name, and octrees above MVRT_DEVICE_MAX_LEVELS levels.  The handle is never modified.

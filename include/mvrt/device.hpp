@@ -21,7 +21,9 @@
 // is the sum of the stored nVoxelsPSum along that path, read after the hit.
 //
 // Distance limit: a ray with limit tMax reports what the unlimited ray reports when that ray hits with t <= tMax (t in units of rd), and a miss
-// otherwise -- bit for bit, for every ray, so a NaN tMax or one that is not above 0 always misses and MVRT_MAX_FLOAT / +inf change nothing.  The walk
+// otherwise -- bit for bit, for every ray, so a NaN tMax or one that is not above 0 always misses, +inf changes nothing, and MVRT_MAX_FLOAT changes nothing
+// but this: a ray without a direction (every component zero or denormal) can "hit" at t = +inf as in the reference, and inf <= MVRT_MAX_FLOAT is
+// false, so under MVRT_MAX_FLOAT that ray misses and under +inf it hits (occluded() likewise).  The walk
 // stops early once the candidate child's entry time exceeds tMax by a margin that covers the fp32 rounding of the entry times along the walk
 // (DESIGN.md 5.12 derives it); rays whose slab deltas are not all finite are never cut, only filtered.  descents of a limited ray = the child
 // fetches it made: at most the unlimited ray's, equal to them on an accepted hit.

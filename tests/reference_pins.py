@@ -379,6 +379,41 @@ def rays_of(O, name):
     return _ray_sets[name]
 
 
+FAR_K = 24  # origins extent * 2^k away, k = 0 .. 23: at k = 23 one float32 rounding of an origin coordinate or of a slab time spans the whole grid
+FAR_SCENES = ("bunny64", "deep16", "deep21")  # the far-ray pins against the compiled reference: 16 levels is the device view's limit, 21 the library's
+N_FAR_PIN = 60_000
+
+
+def far_rays(rs, n, seed):
+    """(ro, rd, isShadow, k) of a RayScene: n rays at a random point of a random voxel from an origin extent * 2^k away, k uniform in 0 .. 23.  A third of
+    the directions are flattened by 1e-3 on one axis (grazing rays).  The direction is taken from the origin as float32 holds it and scaled by
+    2^-20 .. 2^20, so t covers 2^-20 .. 2^43 extents.  Not part of ray_set: the digests of the trace/ keys do not contain these rays.  Every third ray
+    is a shadow ray."""
+    rng = np.random.default_rng(seed)
+    lo, ext = rs.lower.astype(np.float64), float((rs.upper - rs.lower).max())
+    cells = D.decode(rs.morton[rng.integers(0, len(rs.morton), n)]).astype(np.float64)
+    tgt = lo + float(rs.dps) * (cells + rng.random((n, 3)))
+    u = rng.normal(size=(n, 3))
+    flat = np.flatnonzero(np.arange(n) % 3 == 1)
+    u[flat, rng.integers(0, 3, len(flat))] *= 1e-3
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    k = rng.integers(0, FAR_K, n)
+    ro = (tgt - u * (ext * 2.0 ** k)[:, None]).astype(f32)
+    d = tgt - ro.astype(np.float64)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    rd = (d * (2.0 ** rng.integers(-20, 21, n))[:, None]).astype(f32)
+    return ro, rd, (np.arange(n) % 3 == 0).astype(np.uint8), k.astype(np.int32)
+
+
+_far_sets = {}
+
+
+def far_rays_of(O, name, n, seed=29):
+    if (name, n, seed) not in _far_sets:
+        _far_sets[(name, n, seed)] = far_rays(ray_scene(O, name), n, seed)
+    return _far_sets[(name, n, seed)]
+
+
 # ---- the renderer's sampling code: oracle/_ref/libmvrt_ref_render.so ------------------------------------------------------------------------------
 BELOW1 = np.nextafter(f32(1), f32(0))  # the largest float below 1
 

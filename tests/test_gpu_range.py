@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from common import bunny_tris
+from lane_walk_expected import CASES, expected, limits  # shared with tests/test_lane_walk_cpu.py and tests/test_gpu_lane_walk_edges.py
 from test_gpu_device_api import ray_set, upload
 
 pytestmark = pytest.mark.gpu
@@ -16,7 +17,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAXF = np.float32(3.402823466e38)
-CASES = ("t", "below", "above", "quarter", "four", "maxf", "inf", "zero", "minus", "nan")
 OUTPUTS = ("t", "nMajor", "vIndex", "descents")
 
 
@@ -57,26 +57,6 @@ def probe_range(mv, probe, view, ro, rd, sh, tmax, mode):
     rc = probe.probe_range(C.byref(view), n, *[a.ptr for a in dev], dsh.ptr, dlim.ptr, *[a.ptr for a in out], mode)
     assert rc == 0, rc
     return dict(zip(OUTPUTS + ("occluded",), (a.to_host() for a in out)))
-
-
-def limits(sc, t_unlimited):
-    """the per-ray limit: case i % 10 of CASES around the oracle's unlimited t of that ray (the scene's extent for a miss)"""
-    f32 = np.float32
-    ext = f32(f32(sc.dps) * f32(sc.grid_res))
-    base = np.where(t_unlimited != MAXF, t_unlimited, ext).astype(f32)
-    case = np.arange(len(base)) % len(CASES)
-    with np.errstate(over="ignore"):
-        choices = [base, np.nextafter(base, f32(0)), np.nextafter(base, f32(np.inf)), (f32(0.25) * base).astype(f32), (f32(4) * base).astype(f32),
-                   np.full_like(base, MAXF), np.full_like(base, np.inf), np.zeros_like(base), np.full_like(base, -1), np.full_like(base, np.nan)]
-    return np.choose(case, choices).astype(f32), case
-
-
-def expected(want, sh, tmax):
-    """the filtered oracle: its hit where t <= tMax in fp32 (false for a NaN limit), else the miss triple"""
-    with np.errstate(invalid="ignore"):
-        keep = (want["t"] != MAXF) & (want["t"] <= tmax)
-    return {"t": np.where(keep, want["t"], MAXF).astype(np.float32), "nMajor": np.where(keep, want["nMajor"], -1).astype(np.int32),
-            "vIndex": np.where(keep & (sh == 0), want["vIndex"], 0).astype(np.uint32)}, keep
 
 
 class Reference:

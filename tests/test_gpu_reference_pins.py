@@ -92,10 +92,11 @@ def test_all_classes_between_bunny_triangles(mv, O, walk, case):
     build_and_compare(mv, O, walk, *case)
 
 
-@pytest.mark.parametrize("scene", ["bunny64", "deep21"])
+@pytest.mark.parametrize("scene", R.FAR_SCENES)
 def test_trace_batch(mv, O, walk, scene):
     """one mvrt_trace_batch of the CPU pin's whole ray set -- ties, origins on voxel corners / edges / faces, secondary-style origins, direction
-    components of +-0, denormals, +-inf and NaN, a third shadow rays -- against the reference's traversal: t by its bits, nMajor and vIndex on all rays"""
+    components of +-0, denormals, +-inf and NaN, a third shadow rays -- against the reference's traversal: t by its bits, nMajor and vIndex on all rays.
+    A second call traces the CPU pin's far-origin rays (origins up to 2^23 extents away; the fast loop of traceStream had seen 4 extents at most)."""
     rs = R.ray_scene(O, scene)
     ro, rd, sh = R.rays_of(O, scene)
     svo = mv.IntersectorOctreeGPU()
@@ -105,6 +106,11 @@ def test_trace_batch(mv, O, walk, scene):
     got = svo.intersect(ro, rd, sh)
     R.check("trace/" + scene, [got["t"], got["nMajor"], got["vIndex"]], walk,
             lambda w: [x for x in w.trace(rs.nodes, rs.lower, rs.upper, ro, rd, sh).values()])
+    fro, frd, fsh, _ = R.far_rays_of(O, scene, R.N_FAR_PIN)
+    far = svo.intersect(fro, frd, fsh)
+    assert ((far["t"] != R.MAXF) & (far["t"] > 2.0 ** 20 * rs.dps * rs.sc.grid_res)).sum() > 1000
+    R.check("trace_far/" + scene, [far["t"], far["nMajor"], far["vIndex"]], walk,
+            lambda w: [x for x in w.trace(rs.nodes, rs.lower, rs.upper, fro, frd, fsh).values()])
 
 
 # ---- the renderer's sampling code against oracle/_ref/libmvrt_ref_render.so, not through the oracle ------------------------------------------------

@@ -117,6 +117,25 @@ def test_traversal(walk, scene):
             lambda w: [x for x in w.trace(rs.nodes, rs.lower, rs.upper, ro, rd, sh).values()])
 
 
+@pytest.mark.parametrize("scene", R.FAR_SCENES)
+def test_traversal_far_origins(walk, scene):
+    """60 000 rays at voxels from origins extent * 2^k away, k = 0 .. 23 (R.far_rays): one float32 rounding of a slab time spans up to the whole grid, t reaches
+    2^43 extents.  t by its bits, nMajor and vIndex on all of them, a third shadow rays."""
+    rs = R.ray_scene(O, scene)
+    ro, rd, sh, k = R.far_rays_of(O, scene, R.N_FAR_PIN)
+    ext = float((rs.upper - rs.lower).max())
+    dist = np.linalg.norm(ro.astype(np.float64) - (rs.lower.astype(np.float64) + rs.upper) / 2, axis=1) / ext
+    # the origin is 2^k extents from its target, the target at most sqrt( 3 ) / 2 extents from the centre
+    assert len(ro) == R.N_FAR_PIN and set(k.tolist()) == set(range(R.FAR_K)) and (np.abs(dist - 2.0 ** k) <= 0.87 + 2.0 ** k * 1e-6).all()
+    got = rs.sc.trace(ro, rd, sh, threads=8)
+    hit = got["t"] != R.MAXF
+    per_k = np.bincount(k[hit], minlength=R.FAR_K)
+    assert (per_k[:6] >= 1000).all() and (per_k > 0).all() and (~hit).sum() >= 1000, per_k  # most near rays hit; hits at every distance; misses
+    assert got["t"][hit].max() > 2.0 ** 30 * got["t"][hit].min()
+    R.check("trace_far/" + scene, [got["t"], got["nMajor"], got["vIndex"]], walk,
+            lambda w: [x for x in w.trace(rs.nodes, rs.lower, rs.upper, ro, rd, sh).values()])
+
+
 def test_deep_scenes_fit_the_reference_stack():
     """IntersectorOctree::intersect walks with StackElement stack[32] (IntersectorOctree.hpp:250): 14 to 21 levels fit"""
     assert max(D.DEPTHS) <= 32 and list(R.RAY_SCENES[-len(D.DEPTHS):]) == ["deep%d" % L for L in D.DEPTHS]
