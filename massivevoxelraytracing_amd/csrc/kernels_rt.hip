@@ -5,6 +5,8 @@
 // :610-777 (renderPT), voxCommon.hpp:231-423 (traversal), StreamCompaction.hpp:87-184 (stable compaction).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "launch.h"
 #include "traverse_stream.h"
 
@@ -34,10 +36,7 @@ struct BatchIO
 	int32_t* nMajorOut;
 	uint64_t* pathOut; // scratch: resolved to vIndex by kResolveVIndex
 	uint32_t* descentsOut;
-#ifdef MVRT_UTIL_STATS
-	unsigned long long utilIters = 0, utilActive = 0, utilTailIters = 0, utilTailActive = 0, utilRefillClocks = 0, utilTotalClocks = 0;
-	uint32_t utilMaxRayIters = 0;
-#endif
+	MVRT_UTIL_COUNTERS
 	const uint64_t* originPath; // optional: per ray, the full path of an existing voxel (start-below-the-root hint), ~0 = none
 	uint32_t levels;
 	MVRT_DI bool load( uint32_t i, f3* ro, f3* rd, uint32_t* hint ) const
@@ -88,9 +87,7 @@ __global__ void __launch_bounds__( 256 ) kResolveVIndex( SvoDev svo, uint64_t n,
 template <int FL>
 __global__ void __launch_bounds__( 64, MVRT_WAVES_OF( FL ) ) kTraceBatchStream( SvoDev svo, uint64_t n, BatchIO io, TraceWorkspace ws, uint32_t chunk )
 {
-	__shared__ uint4 ring[MVRT_RING_OF( FL ) * 64];
-	__shared__ uint32_t ringMask[FL == 0 ? 1 : ( FL == 2 ? 2 : 1 ) * MVRT_RING_OF( FL ) * 64]; // (tree flavour: two mask words per stacked node)
-	traceStream<FL>( makeTraceCore( svo ), io, n, ws.cursor, chunk, ring, ws.spill, ws.spillStride, (uint64_t)blockIdx.x * 64 + threadIdx.x, ringMask, ws.spillMask, ws.spillMask2 );
+	traceStream<FL>( makeTraceCore( svo ), io, n, ws.cursor, chunk, ws );
 }
 
 struct PrimaryIO
@@ -103,10 +100,7 @@ struct PrimaryIO
 	int32_t* nMajorOut;
 	uint64_t* pathOut;
 	uint32_t* descentsOut;
-#ifdef MVRT_UTIL_STATS
-	unsigned long long utilIters = 0, utilActive = 0, utilTailIters = 0, utilTailActive = 0, utilRefillClocks = 0, utilTotalClocks = 0;
-	uint32_t utilMaxRayIters = 0;
-#endif
+	MVRT_UTIL_COUNTERS
 	f3 rdKeep; // direction of the ray this lane is tracing (for the normal colour)
 	MVRT_DI bool load( uint32_t pixelIdx, f3* ro, f3* rd, uint32_t* )
 	{
@@ -138,10 +132,7 @@ struct PrimaryIO
 template <int FL>
 __global__ void __launch_bounds__( 64, MVRT_WAVES_OF( FL ) ) kRenderPrimaryStream( PrimaryIO io, TraceWorkspace ws, uint32_t chunk )
 {
-	__shared__ uint4 ring[MVRT_RING_OF( FL ) * 64];
-	__shared__ uint32_t ringMask[FL == 0 ? 1 : ( FL == 2 ? 2 : 1 ) * MVRT_RING_OF( FL ) * 64]; // (tree flavour: two mask words per stacked node)
-	traceStream<FL>( makeTraceCore( io.svo ), io, (uint64_t)io.W * io.H, ws.cursor, chunk, ring, ws.spill, ws.spillStride, (uint64_t)blockIdx.x * 64 + threadIdx.x, ringMask,
-						ws.spillMask, ws.spillMask2 );
+	traceStream<FL>( makeTraceCore( io.svo ), io, (uint64_t)io.W * io.H, ws.cursor, chunk, ws );
 }
 
 static uint32_t streamChunk( uint64_t total, uint64_t waves )
@@ -210,6 +201,15 @@ static int numCUs()
 	return g_numCUs;
 }
 
+// the traversal flavour of an octree (traverse_stream.h) as a compile-time constant: calls f( std::integral_constant<int, FL>() )
+template <class F>
+static void withFlavour( const SvoDev& svo, F&& f )
+{
+	if( svo.embedded ) f( std::integral_constant<int, 0>() );
+	else if( svo.tree ) f( std::integral_constant<int, 2>() );
+	else f( std::integral_constant<int, 1>() );
+}
+
 int launchTraceBatch( const SvoDev& svo, const TraceWorkspace& ws, uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy,
 					  const float* rdz, const uint8_t* isShadow, float* t, int32_t* nMajor, uint32_t* vIndex, uint32_t* descents, hipStream_t stream, const uint64_t* originPath )
 {
@@ -227,9 +227,7 @@ int launchTraceBatch( const SvoDev& svo, const TraceWorkspace& ws, uint64_t n, c
 		io.levels = svo.levels;
 		int grid = streamGridKnown( n, numCUs() );
 		MVRT_HIP( hipMemsetAsync( ws.cursor, 0, 8, stream ) );
-		if( svo.embedded ) hipLaunchKernelGGL( kTraceBatchStream<0>, dim3( grid ), dim3( 64 ), 0, stream, svo, n, io, ws, streamChunk( n, grid ) );
-		else if( svo.tree ) hipLaunchKernelGGL( kTraceBatchStream<2>, dim3( grid ), dim3( 64 ), 0, stream, svo, n, io, ws, streamChunk( n, grid ) );
-		else hipLaunchKernelGGL( kTraceBatchStream<1>, dim3( grid ), dim3( 64 ), 0, stream, svo, n, io, ws, streamChunk( n, grid ) );
+		withFlavour( svo, [&]( auto fl ) { hipLaunchKernelGGL( kTraceBatchStream<decltype( fl )::value>, dim3( grid ), dim3( 64 ), 0, stream, svo, n, io, ws, streamChunk( n, grid ) ); } );
 		if( vIndex )
 			hipLaunchKernelGGL( kResolveVIndex, dim3( persistentGrid( n, 256, numCUs(), 8 ) ), dim3( 256 ), 0, stream, svo, n, t, paths, isShadow, vIndex, (uchar4*)nullptr );
 		MVRT_HIP( hipGetLastError() );
@@ -269,9 +267,7 @@ int launchRenderPrimary( const SvoDev& svo, const TraceWorkspace& ws, const Came
 		io.rdKeep = mk3( 0, 0, 0 );
 		int grid = streamGridKnown( n, numCUs() );
 		MVRT_HIP( hipMemsetAsync( ws.cursor, 0, 8, stream ) );
-		if( svo.embedded ) hipLaunchKernelGGL( kRenderPrimaryStream<0>, dim3( grid ), dim3( 64 ), 0, stream, io, ws, streamChunk( n, grid ) );
-		else if( svo.tree ) hipLaunchKernelGGL( kRenderPrimaryStream<2>, dim3( grid ), dim3( 64 ), 0, stream, io, ws, streamChunk( n, grid ) );
-		else hipLaunchKernelGGL( kRenderPrimaryStream<1>, dim3( grid ), dim3( 64 ), 0, stream, io, ws, streamChunk( n, grid ) );
+		withFlavour( svo, [&]( auto fl ) { hipLaunchKernelGGL( kRenderPrimaryStream<decltype( fl )::value>, dim3( grid ), dim3( 64 ), 0, stream, io, ws, streamChunk( n, grid ) ); } );
 		if( needPaths )
 			hipLaunchKernelGGL( kResolveVIndex, dim3( persistentGrid( n, 256, numCUs(), 8 ) ), dim3( 256 ), 0, stream, svo, n, t, ws.paths, (const uint8_t*)nullptr, vIndex,
 								showVertexColor ? rgba : (uchar4*)nullptr );
@@ -520,10 +516,7 @@ struct PtIO
 	uint32_t n;
 	int shadowKind;
 	int useHint; // stage > 0 on an embedded-mask octree: PathSet::org holds the start-below-the-root hint of every path
-#ifdef MVRT_UTIL_STATS
-	unsigned long long utilIters = 0, utilActive = 0, utilTailIters = 0, utilTailActive = 0, utilRefillClocks = 0, utilTotalClocks = 0;
-	uint32_t utilMaxRayIters = 0;
-#endif
+	MVRT_UTIL_COUNTERS
 	uint32_t dNormal, dShadow, nHits; // per-lane tallies (a lane sees far fewer than 2^32 descents per launch)
 	MVRT_DI int kindOf( uint32_t r, uint32_t* i ) const
 	{
@@ -575,8 +568,6 @@ template <int FL>
 __global__ void __launch_bounds__( 64, MVRT_WAVES_OF( FL ) ) kPtTraceStream( PtParams P, TraceWorkspace ws, int stage, int setIdx, int nKinds, int shadowKind, uint32_t chunk,
 																			uint32_t raysPerLane, uint32_t minWaves )
 {
-	__shared__ uint4 ring[MVRT_RING_OF( FL ) * 64];
-	__shared__ uint32_t ringMask[FL == 0 ? 1 : ( FL == 2 ? 2 : 1 ) * MVRT_RING_OF( FL ) * 64]; // (tree flavour: two mask words per stacked node)
 	PtIO io;
 	io.table = P.buf.selfDev;
 	io.setIdx = setIdx;
@@ -601,8 +592,7 @@ __global__ void __launch_bounds__( 64, MVRT_WAVES_OF( FL ) ) kPtTraceStream( PtP
 	c = ( c + 63 ) / 64 * 64;
 	if( c < 64 ) c = 64;
 	if( c > chunk ) c = chunk;
-	traceStream<FL>( makeTraceCore( P.svo ), io, total, P.buf.cursors + stage, (uint32_t)c, ring, ws.spill, ws.spillStride, (uint64_t)blockIdx.x * 64 + threadIdx.x, ringMask,
-						ws.spillMask, ws.spillMask2 );
+	traceStream<FL>( makeTraceCore( P.svo ), io, total, P.buf.cursors + stage, (uint32_t)c, ws );
 	unsigned long long dN = waveSum( (unsigned long long)io.dNormal ), dS = waveSum( (unsigned long long)io.dShadow ), nH = waveSum( (unsigned long long)io.nHits );
 #ifdef MVRT_UTIL_STATS
 	if( threadIdx.x == 0 )
@@ -1023,6 +1013,55 @@ __global__ void __launch_bounds__( 256 ) kPtAovAccumulate( uint64_t validOwnedPi
 	}
 }
 
+// Grid of a path-tracer stage's traversal launch of `rays` rays (an upper bound: live counts stay on the device), and the small-launch limits the kernel applies
+// to it (kPtTraceStream: raysPerLane, minWaves).  traceGridDiv = the frame's tile divisor.
+struct PtTraceGrid
+{
+	int grid;
+	uint32_t smallRpl, smallMinW;
+};
+static PtTraceGrid ptTraceGrid( uint64_t rays, int nCUs, int stage, int traceGridDiv )
+{
+	// a pass that shares the GPU with a sibling pass on another stream takes only 1/div of the wave slots, so that the two
+	// really run side by side (a full persistent grid would hold every slot until its own tail)
+	static const int envDiv = (int)mvrtKnob( "MVRT_TRACE_GRID_DIV", 0 );
+	// ... for its BIG launches only (the first bounces; live counts are on the device, so the stage stands in for them): a small
+	// launch finishes sooner the more lanes it may use, and is gone before it can be in the sibling's way
+	static const int divMaxStage = (int)mvrtKnob( "MVRT_TRACE_DIV_MAX_STAGE", 99 );
+	// small launches keep only total / (64 * 16) waves alive, at least 2048 (two per SIMD): measured with the 8-slot ring on a 1/8 tile
+	// share -6.5 % (dragon, rtcamp stand-in), full frame -1 %, closed scene unchanged (gpurun_out/sweep_small2.log)
+	static const uint32_t envRpl = (uint32_t)mvrtKnob( "MVRT_SMALL_RPL", 16 );
+	static const uint32_t envMinW = (uint32_t)mvrtKnob( "MVRT_SMALL_MINW", 2048 );
+	// experiment knob: waves per CU of a full-grid traversal launch (32 = every slot the register budget allows and then some)
+	static const int wpc = (int)mvrtKnob( "MVRT_TRACE_WAVES_PER_CU", 0 );
+	int g = streamGrid( rays, nCUs );
+	const int div = stage > divMaxStage ? 1 : ( envDiv > 0 ? envDiv : traceGridDiv );
+	if( div > 1 && g > nCUs * STREAM_WAVES_PER_CU / div ) g = nCUs * STREAM_WAVES_PER_CU / div;
+	if( wpc > 0 && g > nCUs * wpc / ( div > 1 ? div : 1 ) ) g = nCUs * wpc / ( div > 1 ? div : 1 );
+	return { g, envRpl, envMinW };
+}
+
+// Which build of the shade kernel a stage runs.
+// Two builds of the kernel: stages 0 and 1 -- where most paths END (69 % of the primaries of an open scene miss) and the work per path is loads and a few adds --
+// run the 8-waves-per-SIMD build (64 VGPRs, 44 bytes of scratch that the dying paths never touch); the deeper stages, whose paths mostly survive and run
+// the ~2000-instruction shading, the 5-wave build.  r03, serial-mode shade time per 4 steps, stages {} / {0} / {0,1} / {1..8} / all on the 8-wave build:
+// dragon 16.6 / 15.8 / 14.9 / 15.6 / 14.6 ms, closed cave 133.7 / 132.5 / 133.3 / 137.6 / 136.8 (tools/sweep_shade.sh)
+static bool shadeDense8( int stage )
+{
+	static const int dense = (int)mvrtKnob( "MVRT_SHADE8_STAGES", 3 );
+	return ( ( dense >> stage ) & 1 ) != 0;
+}
+// ... and the waves per CU of its grid.
+// The grid-stride grids hold exactly the workgroups that are RESIDENT at once (8 / 5 per CU): r02 launched 8 per CU for the 5-wave build too, and the three
+// that had to wait for a slot ran as a second, thin round -- most of what the 8-wave build seemed to gain.  5-wave build with 8 / 6 / 5 workgroups per CU:
+// dragon 16.6 / 14.1 / 14.0 ms of shade time per 4 serial steps, cave 133.7 / 132.3 / 129.2
+// (since the kernel holds no LDS its workgroups are single waves, each owning one 256-path block: the same 32 / 20 resident waves per CU as 32 / 20 workgroups)
+static int shadeWavesPerCU( bool dense8 )
+{
+	static const int bpc8 = (int)mvrtKnob( "MVRT_SHADE_BPC8", 8 ), bpc5 = (int)mvrtKnob( "MVRT_SHADE_BPC5", 5 );
+	return ( dense8 ? bpc8 : bpc5 ) * ( CBLOCK / WAVE );
+}
+
 // The masked instantiations are launched from functions defined BEHIND launchPtStep: a kernel template is emitted where it is first used, so every kernel of the
 // unmasked path keeps the place in the code object that it has without the mask, and the masked ones follow them
 static void launchMaskedGenerate( int grid, hipStream_t stream, const PtParams& P, const uint32_t* active );
@@ -1079,33 +1118,11 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 		const int nKinds = 1 + shadowKind + extraKind;
 		PROF_BEGIN( MVRT_K_TRACE );
 		{
-			int g = streamGrid( nSamples * nKinds, nCUs );
-			uint32_t smallRpl = 0, smallMinW = 0;
-			{
-				// a pass that shares the GPU with a sibling pass on another stream takes only 1/div of the wave slots, so that the two
-				// really run side by side (a full persistent grid would hold every slot until its own tail)
-				static const int envDiv = (int)mvrtKnob( "MVRT_TRACE_GRID_DIV", 0 );
-				// ... for its BIG launches only (the first bounces; live counts are on the device, so the stage stands in for them): a small
-				// launch finishes sooner the more lanes it may use, and is gone before it can be in the sibling's way
-				static const int divMaxStage = (int)mvrtKnob( "MVRT_TRACE_DIV_MAX_STAGE", 99 );
-				const int div = stage > divMaxStage ? 1 : ( envDiv > 0 ? envDiv : frame.traceGridDiv );
-				if( div > 1 && g > nCUs * STREAM_WAVES_PER_CU / div ) g = nCUs * STREAM_WAVES_PER_CU / div;
-				// small launches keep only total / (64 * 16) waves alive, at least 2048 (two per SIMD): measured with the 8-slot ring on a 1/8 tile
-				// share -6.5 % (dragon, rtcamp stand-in), full frame -1 %, closed scene unchanged (gpurun_out/sweep_small2.log)
-				static const uint32_t envRpl = (uint32_t)mvrtKnob( "MVRT_SMALL_RPL", 16 );
-				static const uint32_t envMinW = (uint32_t)mvrtKnob( "MVRT_SMALL_MINW", 2048 );
-				smallRpl = envRpl;
-				smallMinW = envMinW;
-				// experiment knob: waves per CU of a full-grid traversal launch (32 = every slot the register budget allows and then some)
-				static const int wpc = (int)mvrtKnob( "MVRT_TRACE_WAVES_PER_CU", 0 );
-				if( wpc > 0 && g > nCUs * wpc / ( div > 1 ? div : 1 ) ) g = nCUs * wpc / ( div > 1 ? div : 1 );
-			}
-			if( svo.embedded )
-				hipLaunchKernelGGL( kPtTraceStream<0>, dim3( g ), dim3( 64 ), 0, stream, P, ws, stage, setIdx, nKinds, shadowKind, streamChunk( nSamples * nKinds, g ), smallRpl, smallMinW );
-			else if( svo.tree )
-				hipLaunchKernelGGL( kPtTraceStream<2>, dim3( g ), dim3( 64 ), 0, stream, P, ws, stage, setIdx, nKinds, shadowKind, streamChunk( nSamples * nKinds, g ), smallRpl, smallMinW );
-			else
-				hipLaunchKernelGGL( kPtTraceStream<1>, dim3( g ), dim3( 64 ), 0, stream, P, ws, stage, setIdx, nKinds, shadowKind, streamChunk( nSamples * nKinds, g ), smallRpl, smallMinW );
+			const PtTraceGrid tg = ptTraceGrid( nSamples * nKinds, nCUs, stage, frame.traceGridDiv );
+			withFlavour( svo, [&]( auto fl ) {
+				hipLaunchKernelGGL( kPtTraceStream<decltype( fl )::value>, dim3( tg.grid ), dim3( 64 ), 0, stream, P, ws, stage, setIdx, nKinds, shadowKind, streamChunk( nSamples * nKinds, tg.grid ),
+									tg.smallRpl, tg.smallMinW );
+			} );
 		}
 		PROF_END();
 		if( aov && stage == 0 ) // the first-hit records are complete and still in task order; the stage-1 traversal overwrites them, the stage-1 shade the directions
@@ -1124,18 +1141,8 @@ int launchPtStep( const SvoDev& svo, const TraceWorkspace& ws, const HdriDev& hd
 		PROF_END();
 		PROF_BEGIN( MVRT_K_SHADE );
 		{
-			// Two builds of the kernel: stages 0 and 1 -- where most paths END (69 % of the primaries of an open scene miss) and the work per path is loads and a few adds --
-			// run the 8-waves-per-SIMD build (64 VGPRs, 44 bytes of scratch that the dying paths never touch); the deeper stages, whose paths mostly survive and run
-			// the ~2000-instruction shading, the 5-wave build.  r03, serial-mode shade time per 4 steps, stages {} / {0} / {0,1} / {1..8} / all on the 8-wave build:
-			// dragon 16.6 / 15.8 / 14.9 / 15.6 / 14.6 ms, closed cave 133.7 / 132.5 / 133.3 / 137.6 / 136.8 (tools/sweep_shade.sh)
-			static const int dense = (int)mvrtKnob( "MVRT_SHADE8_STAGES", 3 );
-			// The grid-stride grids hold exactly the workgroups that are RESIDENT at once (8 / 5 per CU): r02 launched 8 per CU for the 5-wave build too, and the three
-			// that had to wait for a slot ran as a second, thin round -- most of what the 8-wave build seemed to gain.  5-wave build with 8 / 6 / 5 workgroups per CU:
-			// dragon 16.6 / 14.1 / 14.0 ms of shade time per 4 serial steps, cave 133.7 / 132.3 / 129.2
-			// (since the kernel holds no LDS its workgroups are single waves, each owning one 256-path block: the same 32 / 20 resident waves per CU as 32 / 20 workgroups)
-			static const int bpc8 = (int)mvrtKnob( "MVRT_SHADE_BPC8", 8 ), bpc5 = (int)mvrtKnob( "MVRT_SHADE_BPC5", 5 );
-			const bool dense8 = ( ( dense >> stage ) & 1 ) != 0;
-			const int wpc = ( dense8 ? bpc8 : bpc5 ) * ( CBLOCK / WAVE ); // waves per CU
+			const bool dense8 = shadeDense8( stage );
+			const int wpc = shadeWavesPerCU( dense8 );
 			if( active ) launchMaskedShade( dense8, persistentGrid( nSamples, CBLOCK, nCUs, wpc ), stream, P, stage, setIdx, active );
 			else if( dense8 )
 				hipLaunchKernelGGL( kPtShade<8>, dim3( persistentGrid( nSamples, CBLOCK, nCUs, wpc ) ), dim3( WAVE ), 0, stream, P, stage, setIdx );

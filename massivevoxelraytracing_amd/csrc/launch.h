@@ -56,18 +56,6 @@ struct PtFrame
 };
 #define MVRT_MAX_BATCH 8
 
-// scratch of the persistent traversal kernels (traverse_stream.h): HBM spill rows [level][lane] + a ray cursor.
-// One workspace serves one in-flight launch: calls that share it must be ordered on one stream.
-struct TraceWorkspace
-{
-	uint4* spill;
-	uint64_t spillStride; // lanes = CUs * 32 waves * 64
-	unsigned long long* cursor;
-	uint64_t* paths; // per-ray voxel paths of batch / primary-cast launches, resolved to vIndex by a dense pass
-	uint64_t pathCap;
-	uint32_t* spillMask; // non-embedded flavour: node masks of evicted stack entries, [level][lane]
-	uint32_t* spillMask2; // tree flavour: the second mask word of evicted entries
-};
 uint64_t traceWorkspaceLanes();
 
 enum MvrtKernelClass

@@ -456,6 +456,394 @@ MVRT_DI void traceIrregular( const TraceCore& s, float tx1, float ty1, float tz1
 	*descentsOut = descents;
 }
 
+// ---- ray setup, voxCommon.hpp:240-312: the six slab times of the root box in the mirrored space; returns the mirror mask ----
+MVRT_DI uint32_t setupRay( const TraceCore& s, f3 ro, f3 rd, float* t0x, float* t0y, float* t0z, float* tx1, float* ty1, float* tz1 )
+{
+	float ix = 1.0f / rd.x, iy = 1.0f / rd.y, iz = 1.0f / rd.z;
+	uint32_t vMask = 0;
+	if( ix < 0.0f )
+	{
+		vMask |= 1u;
+		ix = -ix;
+		ro.x = s.lox + s.hix - ro.x;
+	}
+	if( iy < 0.0f )
+	{
+		vMask |= 2u;
+		iy = -iy;
+		ro.y = s.loy + s.hiy - ro.y;
+	}
+	if( iz < 0.0f )
+	{
+		vMask |= 4u;
+		iz = -iz;
+		ro.z = s.loz + s.hiz - ro.z;
+	}
+	ix = smin( ix, MVRT_MAXF / smax( smax( sabs( s.lox - ro.x ), sabs( s.hix - ro.x ) ), 1.0f ) );
+	iy = smin( iy, MVRT_MAXF / smax( smax( sabs( s.loy - ro.y ), sabs( s.hiy - ro.y ) ), 1.0f ) );
+	iz = smin( iz, MVRT_MAXF / smax( smax( sabs( s.loz - ro.z ), sabs( s.hiz - ro.z ) ), 1.0f ) );
+	*t0x = ( s.lox - ro.x ) * ix, *t0y = ( s.loy - ro.y ) * iy, *t0z = ( s.loz - ro.z ) * iz;
+	*tx1 = ( s.hix - ro.x ) * ix;
+	*ty1 = ( s.hiy - ro.y ) * iy;
+	*tz1 = ( s.hiz - ro.z ) * iz;
+	return vMask;
+}
+
+// ---- cursor: grab the next `chunk` rays of the stream with one atomic; returns the stream position the chunk starts at, wave-uniform ----
+MVRT_DI unsigned long long grabChunk( unsigned long long* cursor, uint32_t chunk, uint32_t lane )
+{
+	unsigned long long base = 0;
+	if( lane == 0 ) base = atomicAdd( cursor, (unsigned long long)chunk );
+	// readfirstlane, not a shuffle: the cursor state (and with it `exhausted` and the exit test of the step loop) is then
+	// wave-uniform FOR THE COMPILER -- scalar registers, scalar branches, and the lane masks of the step loop stay in SGPRs
+	// across its exit instead of being copied to VGPRs in every iteration
+	return (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane( (uint32_t)base ) | ( (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane( (uint32_t)( base >> 32 ) ) << 32 );
+}
+
+MVRT_DI bool missesRootBox( float tx1, float ty1, float tz1, float t0x, float t0y, float t0z ) { return min3f( tx1, ty1, tz1 ) < max3f( t0x, t0y, t0z ); } // :275-278
+
+// NODE-VISIT step.  The reference examines the candidate children of a node one at a time (voxCommon.hpp:362-412); measured on
+// a path-traced bunny that is 30.3 candidate tests per ray for 20.6 node visits and 14.7 descents, and 2.0 of the 5.5 pops lead
+// to no further descent.  Here ONE step settles a whole visit: the order in which the ray leaves the octants of a node is a
+// pure function of the three mid-plane times and the three exit times -- walk the events (time, axis) in lexicographic order
+// (the reference's min + "x first, then y" tie rule) until the first exit event; every earlier mid-plane event of a not yet
+// passed axis is a flip -- so the up to four candidates and their existence in the node's mask are evaluated side by side (the candidates
+// behind the origin are masked out in the tree flavour and never built in the others), the first valid one is entered, and the node is
+// pushed only if a later VALID candidate exists.
+// All of it is 1-bit logic: the compares produce 64-bit lane masks and the combinatorics run on the scalar unit.
+//
+// REVISIT of a popped node (flavours that keep the path).  The exit times of a popped node come back bit for bit and its level with them, so the revisit
+// recomputes the first visit's X, Y, Z, flips and candidate chain i0, i1, i2, i3 exactly.  The chain is nested -- each candidate adds the bit of one flipped
+// axis -- hence strictly increasing as a number wherever the next candidate exists geometrically (n1 / n2 / n3).  If the node was left through candidate j
+// (`resume` = i_j), the candidates already dealt with are exactly those with i_k <= resume, and candidate k stays eligible iff i_k > resume: a first visit
+// (resume = -1) filters nothing.  Where candidates coincide (no flip: i1 == i0; two flips: i2 == i3) the later one has n_k clear and is never valid, so a
+// tie cannot admit the child already taken a second time.
+// Behind the origin: these flavours' chain starts at the first candidate that is not behind the origin (see "BEHIND THE ORIGIN" in the step), on a first visit
+// and on a revisit alike, so the candidate j a node was left through is one of the chain and the filter keeps what follows it.  Eligible and valid are the
+// same candidates, in the same order, as for a revisit that restarts from candidate j (its remaining flips are the events after a non-negative one: none
+// is negative): the same child is entered, and the push -- "two or more valid candidates" -- fires under the same condition.  A replayed ancestor of the
+// hint was left through the origin's octant, which is this chain's i0.
+// The resume point needs no storage: the child a stacked node was left through is in `path`, in the three bits above the node's own prefix.
+// Tree flavour (no path): the restart, with the candidate in the sign bits of the stacked exit times and bit-sliced in three SGPR pairs (+ a "first visit"
+// mask) while the loop runs.
+struct VisitStep // what the candidate chain of one step decides: the lanes that hit, descend, push first, pop; the candidate entered; the mid-plane times of the descent
+{
+	lmask mHit, mGo, mPush, mPop;
+	uint32_t ci;
+	float txM, tyM, tzM;
+};
+// Returns lane masks: call it at the top level of control flow (a value assigned under a divergent branch stops being wave-uniform for the compiler)
+template <int FL>
+MVRT_DI VisitStep visitCandidates( uint32_t level, float tx1, float ty1, float tz1, float dtx, float dty, float dtz, uint32_t node, uint32_t nodeMask, uint32_t vMask, uint32_t vMaskHi, uint32_t nres,
+								   lmask act, lmask cmX, lmask cmY, lmask cmZ, lmask mFirst )
+{
+	constexpr bool EMBED = FL == 0, TREE = FL == 2;
+	const float scale = mvrt_u2f( ( 127u - level ) << 23 );
+	const v2f t1yz = { ty1, tz1 };
+	const v2f dtyz = { dty, dtz };
+	const float tx0 = tx1 - dtx * scale; // :317-320
+	const v2f t0yz = t1yz - dtyz * scale;
+	const float ty0 = t0yz.x, tz0 = t0yz.y;
+	const float S = fmaxf( fmaxf( tx0, ty0 ), tz0 );
+	const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
+	const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
+	const float tyM = tMyz.x, tzM = tMyz.y;
+	// octant the candidate chain starts in.  Tree flavour: the octant the node is entered in (:342-348), or the candidate a popped node resumes with
+	// (cmX / cmY / cmZ carry bits only for lanes whose mFirst bit is clear: kept so by the loop tail).  Flavours that keep the path: the first candidate
+	// that is NOT BEHIND THE ORIGIN, bit a = tM_a < max( S, 0 ) -- see "behind the origin" below
+	const float S0 = TREE ? S : fmaxf( S, 0.0f );
+	const lmask X = TREE ? ( mFirst & __ballot( txM < S ) ) | cmX : __ballot( txM < S0 );
+	const lmask Y = TREE ? ( mFirst & __ballot( tyM < S ) ) | cmY : __ballot( tyM < S0 );
+	const lmask Z = TREE ? ( mFirst & __ballot( tzM < S ) ) | cmZ : __ballot( tzM < S0 );
+	// first exit event = lexicographic minimum of (t1, axis); flips = mid-plane events of unset axes that come before it, i.e.
+	// before EVERY exit event (an axis' own exit never precedes its mid-plane: tM <= t1).  (tM_a, a) < (t1_b, b) is "tM_a <= t1_b" for
+	// a < b and "tM_a < t1_b" for a > b
+	// (one asm statement for the three: after every asm statement whose result the next vector instruction reads the compiler spends a wait state, since a
+	// transcendental result would need one; v_min_f32 has no such hazard)
+	// (tree flavour: it waits for HBM, not for issue slots, and measured 0.3 % slower on the 8192^3 stress octree with the merged statements and the add-with-carry
+	// assembly below: it keeps the separate statements and the selects)
+	float mXY, mYZ, T;
+	if( TREE )
+	{
+		mXY = minF( tx1, ty1 ), mYZ = minF( ty1, tz1 );
+		T = minF( mXY, tz1 );
+	}
+	else
+		asm( "v_min_f32 %0, %3, %4\n\tv_min_f32 %1, %4, %5\n\tv_min_f32 %2, %0, %5" : "=&v"( mXY ), "=&v"( mYZ ), "=&v"( T ) : "v"( tx1 ), "v"( ty1 ), "v"( tz1 ) );
+	const lmask fX = ~X & __ballot( txM <= mYZ );
+	const lmask fY = ~Y & __ballot( tyM < tx1 ) & __ballot( tyM <= tz1 );
+	const lmask fZ = ~Z & __ballot( tzM < mXY );
+	// order of the flips among themselves: (tM, axis) lexicographic
+	const lmask xy = __ballot( txM <= tyM ), xz = __ballot( txM <= tzM ), yz = __ballot( tyM <= tzM );
+	const lmask n1 = fX | fY | fZ, n2 = ( fX & fY ) | ( fZ & ( fX | fY ) ), n3 = fX & fY & fZ; // a 2nd / 3rd / 4th candidate exists geometrically
+	// the axis of the FIRST flip, and -- only when all three axes flip -- of the LAST one
+	const lmask aX = fX & ~( fY & ~xy ) & ~( fZ & ~xz );
+	const lmask aY = fY & ~( fX & xy ) & ~( fZ & ~yz );
+	const lmask aZ = fZ & ~( fX & xz ) & ~( fY & yz );
+	const lmask zX = n3 & ~( xy | xz ), zY = n3 & xy & ~yz, zZ = n3 & xz & yz;
+	// child indices of the four candidates (mirrored space), nested: each adds the axis of one flip.  With two flips the third
+	// candidate is already the last (i2 == i3); with three, it is the last minus the last flip
+	// (asm selects = one v_cndmask on an SGPR mask; written as nested ?: the compiler turns these chains into branches)
+	// (flavours that keep the path: the three bits through add-with-carry, x + x + bit, one instruction per bit and no OR)
+	const uint32_t i0 = TREE ? MVRT_SELKK( X, 1, 0 ) | MVRT_SELKK( Y, 2, 0 ) | MVRT_SELKK( Z, 4, 0 ) : MVRT_SHIFT_IN( MVRT_SHIFT_IN( MVRT_SELKK( Z, 1, 0 ), Y ), X );
+	const uint32_t i3 = i0 | ( TREE ? MVRT_SELKK( fX, 1, 0 ) | MVRT_SELKK( fY, 2, 0 ) | MVRT_SELKK( fZ, 4, 0 ) : MVRT_SHIFT_IN( MVRT_SHIFT_IN( MVRT_SELKK( fZ, 1, 0 ), fY ), fX ) );
+	const uint32_t i1 = i0 | MVRT_SELK( aX, 1, MVRT_SELK( aY, 2, MVRT_SELKK( aZ, 4, 0 ) ) );
+	const uint32_t i2 = i3 ^ MVRT_SELK( zX, 1, MVRT_SELK( zY, 2, MVRT_SELKK( zZ, 4, 0 ) ) );
+	// e_k: candidate k exists in the node's mask -- and, with the path at hand, is eligible (i_k > resume) in the same compare: m = 0 / -1 from the mask bit,
+	// m ^ i_k is ~i_k (negative) for a child that exists and i_k (>= 0) for one that does not; against nres = ~resume (0 on a first visit, negative on a
+	// revisit) "m ^ i_k < nres" is ~i_k < ~resume, i.e. i_k > resume, for the former and never true for the latter
+#define MVRT_EXISTS( i )                                                                                                                                                      \
+	( TREE ? __ballot( ( ( nodeMask >> ( ( ( i ) ^ vMaskHi ) & 7u ) ) & 1u ) != 0u )                                                                                          \
+		   : __ballot( (int)( ( EMBED ? bitMask( node, ( i ) ^ vMaskHi ) : bitMask( nodeMask, ( i ) ^ vMask ) ) ^ ( i ) ) < (int)nres ) )
+	const lmask e0 = MVRT_EXISTS( i0 ), e1 = MVRT_EXISTS( i1 ), e2 = MVRT_EXISTS( i2 ), e3 = MVRT_EXISTS( i3 );
+#undef MVRT_EXISTS
+	// BEHIND THE ORIGIN.  A candidate is behind the origin when the event that ends it is negative (:373).  Events are visited in time order, so the
+	// candidates behind the origin are a prefix of the reference's chain: candidate k is behind iff more than k flips are negative, all of them iff the
+	// exit is (T < 0: `inner` below).
+	// Tree flavour: that prefix is masked out (b0..b2).
+	// Flavours that keep the path never build it: their chain STARTS at the first candidate that is not behind.  That candidate is the entry octant plus the
+	// axes of the negative flips (the flips are ordered by time, so the negative ones are the first), bit a = ( tM_a < S ) | ( tM_a < 0 and a flips ).  With
+	// T >= 0 "a flips" may be dropped: an axis outside the entry octant whose mid-plane is negative and does NOT come before the first exit would make that
+	// exit negative.  So bit a = tM_a < max( S, 0 ) = X, Y, Z above (one v_max, no compare against zero, no prefix logic); the flips of the remaining axes
+	// are the non-negative flips of the reference's chain in their order, i3 is the same last candidate, and i0..i3 are exactly the reference's candidates
+	// nNeg..3 (nNeg = number of negative flips) followed by repeats of the last, which have n_k clear.  Valid candidates, their order and their number are
+	// what the masked chain gave; with T < 0 nothing is entered whatever the chain says.  The resume point of a revisit is a candidate that was entered,
+	// hence one of this chain, and the filter i_k > resume reads it as before.  (tM = -0.0 is not negative for either compare.)
+	lmask b0 = 0ull, b1 = 0ull, b2 = 0ull;
+	if( TREE )
+	{
+		const lmask kx = fX & __ballot( txM < 0.0f ), ky = fY & __ballot( tyM < 0.0f ), kz = fZ & __ballot( tzM < 0.0f );
+		b0 = kx | ky | kz, b1 = ( kx & ky ) | ( ( kx | ky ) & kz ), b2 = kx & ky & kz;
+	}
+	const lmask mLeaf = act & __ballot( node == MVRT_LEAF ); // :322
+	const lmask inner = act & ~mLeaf & ~__ballot( T < 0.0f );
+	// tree flavour: candidate 0 of a popped node is the child it was left through: already done
+	const lmask v0 = TREE ? mFirst & e0 & ~b0 : e0, v1 = n1 & e1 & ~b1, v2 = n2 & e2 & ~b2, v3 = n3 & e3;
+	// push only if a later VALID candidate exists (the reference: any later candidate; measured +8.6 %), i.e. if at least two of the four are valid
+	const lmask vA = v0 | v1, vB = v0 & v1, vC = v2 | v3, vD = v2 & v3;
+	const lmask mGo = inner & ( vA | vC );
+	const lmask mPush = inner & ( vB | vD | ( vA & vC ) );
+	const lmask mHit = mLeaf & __ballot( 0.0f < S0 ); // :324 (0 < S iff 0 < max( S, 0 ))
+	const lmask mPop = act & ~mHit & ~mGo;
+	// the entered candidate = the first valid one
+	const uint32_t ci = selU( v0, i0, selU( v1, i1, selU( v2, i2, i3 ) ) );
+	VisitStep v;
+	v.mHit = mHit, v.mGo = mGo, v.mPush = mPush, v.mPop = mPop;
+	v.ci = ci;
+	v.txM = txM, v.tyM = tyM, v.tzM = tzM;
+	return v;
+}
+
+// ---- hint replay (embedded flavour) ----
+// Start below the root: replay the walk down the hint's path (see the top of this file).  In a first visit with
+// T = min( t1 ) >= 0 the candidates behind the origin are those ended by a NEGATIVE mid-plane event (the "before the
+// first exit" condition of a flip holds for every negative tM once T >= 0), and they are a prefix of the reference's
+// candidate order; so the first candidate that is not behind has bit a = ( tM_a < S ) | ( tM_a < 0 ) = tM_a < max( S, 0 )
+// -- the very octant the step below starts its candidate chain with (X, Y, Z there), computed here with the same
+// operations.  If that octant is the hint's child it exists, the step would enter it (its exit is >= 0 by the same
+// inequalities: T stays >= 0 level after level), and a later candidate exists iff an axis whose bit is clear flips
+// before the first exit event (fX, fY, fZ of the step).
+// Straight-line code: the level counter is a compile-time constant (the loop is unrolled, at most MVRT_HINT_MAX = 7
+// levels = ring slots: a refilled lane's ring is empty, so nothing is ever evicted here), the node references of the
+// hint's ancestors are ONE batch of independent table gathers issued up front (no pointer chase), lanes that have left
+// the hint's path just stop changing their state.
+struct HintStart // where the fast loop starts: exit times, node, the stacked ancestors, the levels skipped and the path down to there
+{
+	float tx1, ty1, tz1;
+	uint32_t node, pending, levels;
+	uint64_t path;
+};
+MVRT_DI HintStart replayHint( const TraceCore& s, LdsU4* myRing, uint32_t hint, uint32_t node, uint32_t vMask, float dtx, float dty, float dtz, float tx1, float ty1, float tz1 )
+{
+	uint32_t pending = 0;
+	const uint32_t P = hintLevelsOf( s.levelsM1 + 1u );
+	const char* const tab = (const char*)s.kids + ( ( s.rootIndex + 1u ) << 5 ); // the prefix tables lie behind the children array (32 B per node; root = last node)
+	uint32_t anc[MVRT_HINT_MAX + 1];
+#pragma unroll
+	for( uint32_t L = 1; L <= MVRT_HINT_MAX; L++ )
+		anc[L] = L <= P ? *(const uint32_t*)( tab + ( ( prefixTabOffset( L ) + ( hint >> ( 3u * ( P - L ) ) ) ) << 2 ) ) : 0u;
+	uint32_t k = 0u;
+	bool on = true;
+	anc[0] = node;
+#pragma unroll
+	for( uint32_t L = 0; L < MVRT_HINT_MAX; L++ )
+	{
+		if( L < P && on ) // (L < P is wave-uniform; lanes that have left the hint's path drop out of the rest of the nest)
+		{
+			const float scale = mvrt_u2f( ( 127u - L ) << 23 );
+			const v2f t1yz = { ty1, tz1 };
+			const v2f dtyz = { dty, dtz };
+			const float tx0 = tx1 - dtx * scale; // :317-320, the step's own operations
+			const v2f t0yz = t1yz - dtyz * scale;
+			const float S0 = fmaxf( fmaxf( fmaxf( tx0, t0yz.x ), t0yz.y ), 0.0f );
+			const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
+			const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
+			const bool bx = txM < S0, by = tMyz.x < S0, bz = tMyz.y < S0;
+			const uint32_t b = ( bx ? 1u : 0u ) | ( by ? 2u : 0u ) | ( bz ? 4u : 0u );
+			on = ( b ^ vMask ) == ( ( hint >> ( 3u * ( P - 1u - L ) ) ) & 7u ); // the origin's octant is the hint's child: it exists, the step enters it
+			if( on )
+			{
+				const bool later = ( (int)!bx & (int)( txM <= minF( ty1, tz1 ) ) ) | ( (int)!by & (int)( tMyz.x < tx1 ) & (int)( tMyz.x <= tz1 ) ) | ( (int)!bz & (int)( tMyz.y < minF( tx1, ty1 ) ) );
+				if( later ) // stack the ancestor (:377-380); the octant it is left through is the hint's child at this level, which `path` holds as for any entry
+				{
+					// (the node reference -- word 0 -- is filled in after the walk, when the table gathers have landed: their
+					// latency hides behind this arithmetic instead of stalling the wave at the first level)
+					LdsU32* const w = (LdsU32*)( myRing + L * 64 );
+					w[1] = mvrt_f2u( tx1 );
+					w[2] = mvrt_f2u( ty1 );
+					w[3] = mvrt_f2u( tz1 );
+					pending |= 1u << L;
+				}
+				tx1 = bx ? tx1 : txM; // :382-386
+				ty1 = by ? ty1 : tMyz.x;
+				tz1 = bz ? tz1 : tMyz.y;
+				k = L + 1u;
+			}
+		}
+	}
+#pragma unroll
+	for( uint32_t L = 0; L < MVRT_HINT_MAX; L++ )
+	{
+		if( L < P )
+		{
+			if( pending & ( 1u << L ) ) *(LdsU32*)( myRing + L * 64 ) = anc[L];
+			node = k == L + 1u ? anc[L + 1] : node;
+		}
+	}
+	HintStart hs;
+	hs.tx1 = tx1, hs.ty1 = ty1, hs.tz1 = tz1;
+	hs.node = node;
+	hs.pending = pending;
+	hs.levels = k;
+	hs.path = k ? (uint64_t)( hint >> ( 3u * ( P - k ) ) ) : 0ull;
+	return hs;
+}
+
+// the tallies of a diagnostic -DMVRT_UTIL_STATS build, as members of an IO struct (nothing otherwise)
+#ifdef MVRT_UTIL_STATS
+#define MVRT_UTIL_COUNTERS                                                                                                                   \
+	unsigned long long utilIters = 0, utilActive = 0, utilTailIters = 0, utilTailActive = 0, utilRefillClocks = 0, utilTotalClocks = 0; \
+	uint32_t utilMaxRayIters = 0;
+#else
+#define MVRT_UTIL_COUNTERS
+#endif
+
+// ---- stack view: this lane's view of the LDS ring, the mask rings and the HBM spill rows (constant while the lane lives; the mutable `pending` / `inLds` stay with the lane) ----
+template <int FL>
+struct LaneStack
+{
+	static constexpr bool EMBED = FL == 0, TREE = FL == 2;
+	static constexpr uint32_t RING = MVRT_RING_OF( FL );
+	static constexpr uint32_t RING_CLASH = RING == 4 ? 0x11111111u : ( RING == 8 ? 0x01010101u : 0x00010001u ); // the levels that share ring slot 0
+	LdsU4* myRing;
+	uint32_t ringAddr; // LDS byte address of this lane's slot 0
+	uint4* mySpill;	   // level L at mySpill[L * spillStride]  (irregular rays only)
+	LdsU32* myRingMask;
+	LdsU32* myRingMask2;
+	uint4* spill;
+	uint32_t *spillMask, *spillMask2;
+	uint32_t spillShift, spillOff, spillMaskShift, spillMaskOff;
+	MVRT_DI LaneStack( uint4* ldsRing, uint32_t* ldsMask, uint4* spill_, uint32_t* spillMask_, uint32_t* spillMask2_, uint64_t spillStride, uint64_t spillLane )
+	{
+		const uint32_t lane = threadIdx.x;
+		spill = spill_, spillMask = spillMask_, spillMask2 = spillMask2_;
+		// LDS ring: explicit LDS address space (so the optimiser cannot fold a ring read and a spill read into one flat
+		// load); slot k of this lane at byte offset k * 1024 + lane * 16
+		myRing = (LdsU4*)ldsRing + lane;
+		ringAddr = (uint32_t)(uintptr_t)myRing; // LDS byte address of this lane's slot 0
+		mySpill = spill + spillLane; // level L at mySpill[L * spillStride]  (irregular rays only)
+		myRingMask = EMBED ? nullptr : (LdsU32*)ldsMask + lane;
+		// tree flavour: a stacked brick root keeps its 8 child masks in the two mask words (its own mask = their non-zero bytes); an in-brick node its mask in the first
+		myRingMask2 = TREE ? (LdsU32*)ldsMask + RING * 64 + lane : nullptr;
+		// spill rows: spillStride is a power of two (traceWorkspaceLanes), rows * stride * 16 B < 4 GiB: row L of this lane
+		// is base + ((L << spillShift) + lane offset) with 32-bit arithmetic and a scalar base
+		spillShift = 4u + (uint32_t)__builtin_ctzll( spillStride );
+		spillOff = (uint32_t)spillLane * 16u;
+		spillMaskShift = spillShift - 2u, spillMaskOff = (uint32_t)spillLane * 4u;
+	}
+	// the slot still holds a shallower pending entry: evict it to HBM
+	MVRT_DI void evict( uint32_t slot, uint32_t clash ) const
+	{
+		const uint32_t lc = __builtin_ctz( clash );
+		*(u4v*)( (char*)spill + ( ( lc << spillShift ) + spillOff ) ) = myRing[slot * 64];
+		if( !EMBED ) *(uint32_t*)( (char*)spillMask + ( ( lc << spillMaskShift ) + spillMaskOff ) ) = myRingMask[slot * 64];
+		if( TREE ) *(uint32_t*)( (char*)spillMask2 + ( ( lc << spillMaskShift ) + spillMaskOff ) ) = myRingMask2[slot * 64];
+	}
+	// push (:377-380) the node the lane leaves through candidate ci; returns the lane's new inLds mask
+	MVRT_DI uint32_t push( const TraceCore& s, uint32_t level, uint32_t node, uint32_t nodeMask, uint32_t bLo, uint32_t bHi, float tx1, float ty1, float tz1, uint32_t ci, uint32_t inLds ) const
+	{
+		const uint32_t slot = level & ( RING - 1 );
+		const uint32_t clash = inLds & ( RING_CLASH << slot );
+		if( clash ) // the slot still holds a shallower pending entry: evict it to HBM
+		{
+			evict( slot, clash );
+			inLds &= ~clash;
+		}
+		u4v e;
+		e.x = node;
+		if( TREE )
+		{
+			// the sign bits of a saved node's exit times are free (entered with min >= 0): they carry the child the node is left through
+			e.y = lshlOr( ci, 31u, mvrt_f2u( tx1 ) );
+			e.z = bfi( 0x7FFFFFFFu, mvrt_f2u( ty1 ), ci << 30 );
+			e.w = bfi( 0x7FFFFFFFu, mvrt_f2u( tz1 ), ci << 29 );
+		}
+		else // the child the node is left through goes into `path` below
+		{
+			e.y = mvrt_f2u( tx1 );
+			e.z = mvrt_f2u( ty1 );
+			e.w = mvrt_f2u( tz1 );
+		}
+		myRing[slot * 64] = e;
+		if( !EMBED ) myRingMask[slot * 64] = ( TREE && ( ( s.levelsM1 - level ) & 1u ) ) ? bLo : nodeMask;
+		if( TREE ) myRingMask2[slot * 64] = bHi;
+		return inLds | ( 1u << level );
+	}
+};
+
+// ---- descent into candidate ci (child childIndex) of the lane's node: the child's reference per flavour (:381), the path, the halved box (:382-386) ----
+struct Descent
+{
+	uint32_t node, nodeMask, bLo, bHi;
+	uint64_t path;
+	float tx1, ty1, tz1;
+};
+template <int FL>
+MVRT_DI Descent descend( const TraceCore& s, uint32_t level, uint32_t ci, uint32_t childIndex, uint32_t node, uint32_t nodeMask, uint32_t bLo, uint32_t bHi, uint64_t path, float tx1, float ty1, float tz1,
+						 float txM, float tyM, float tzM )
+{
+	constexpr bool EMBED = FL == 0, TREE = FL == 2;
+	if( EMBED )
+	{
+		// :381 -- 32-bit byte offset from the uniform node base (global_load with an SGPR base, no 64-bit VALU adds)
+		node = *(const uint32_t*)( (const char*)s.kids + childOffset( node, childIndex << 2 ) );
+	}
+	else if( TREE )
+	{
+		treeDescend( s.nodes, s.levelsM1, level, childIndex, &node, &nodeMask, &bLo, &bHi, &path );
+	}
+	else
+	{
+		const Node64* nd = s.nodes + node; // up to 2^32 nodes: 64-bit addressing
+		nodeMask = ( nd->psum[childIndex >> 2] >> ( 8u * ( childIndex & 3u ) ) ) & 0xFFu; // the child's mask: same line as
+		node = nd->children[childIndex];												 // its pointer
+	}
+	if( !TREE ) path = ( path << 3 ) | childIndex;
+	if( TREE )
+	{
+		tx1 = mvrt_u2f( bfi( bitMask( ci, 0 ), mvrt_f2u( tx1 ), mvrt_f2u( txM ) ) ); // :382-386: upper half -> keep the exit time, else the mid-plane
+		ty1 = mvrt_u2f( bfi( bitMask( ci, 1 ), mvrt_f2u( ty1 ), mvrt_f2u( tyM ) ) );
+		tz1 = mvrt_u2f( bfi( bitMask( ci, 2 ), mvrt_f2u( tz1 ), mvrt_f2u( tzM ) ) );
+	}
+	else
+		halveBox( ci, &tx1, &ty1, &tz1, txM, tyM, tzM ); // :382-386
+	Descent d;
+	d.node = node, d.nodeMask = nodeMask, d.bLo = bLo, d.bHi = bHi;
+	d.path = path;
+	d.tx1 = tx1, d.ty1 = ty1, d.tz1 = tz1;
+	return d;
+}
+
 // IO concept (ray indices are 32-bit: a launch never exceeds 2^32 rays):
 //   bool load( uint32_t ray, f3* ro, f3* rd, uint32_t* hint )   -> returns isShadowRay; *hint = MVRT_NO_HINT or hintFromVoxelPath( an existing voxel )
 //   void store( uint32_t ray, const StreamHit& h, bool isShadowRay )
@@ -465,30 +853,21 @@ MVRT_DI void traceIrregular( const TraceCore& s, float tx1, float ty1, float tz1
 // every active lane: straight-line bit arithmetic (v_bfi / v_bfe selects instead of compare-select chains)
 // followed by three shallow branches: descend (with push), pop, hit.
 template <int FL, class IO>
-MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned long long* __restrict__ cursor, uint32_t chunk, uint4* __restrict__ ldsRing /* [MVRT_RING_OF( FL )][64] */,
-						  uint4* __restrict__ spill /* [levels][spillStride] */, uint64_t spillStride, uint64_t spillLane, uint32_t* __restrict__ ldsMask = nullptr /* [MVRT_RING][64], !EMBED */,
-						  uint32_t* __restrict__ spillMask = nullptr /* [levels][spillStride], !EMBED */, uint32_t* __restrict__ spillMask2 = nullptr /* second word, TREE */ )
+MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned long long* __restrict__ cursor, uint32_t chunk, const TraceWorkspace& ws )
 {
 	constexpr bool EMBED = FL == 0, TREE = FL == 2;
 	constexpr uint32_t MVRT_RING = MVRT_RING_OF( FL );
-	constexpr uint32_t MVRT_RING_CLASH = MVRT_RING == 4 ? 0x11111111u : ( MVRT_RING == 8 ? 0x01010101u : 0x00010001u ); // the levels that share ring slot 0
+	// THE place that declares a flavour's rings (one wave per workgroup): [MVRT_RING][64] stack entries, and the mask words of the flavours without embedded masks (two per entry for the tree flavour)
+	__shared__ uint4 ldsRing[MVRT_RING * 64];
+	__shared__ uint32_t ldsMask[EMBED ? 1 : ( TREE ? 2 : 1 ) * MVRT_RING * 64];
+	uint4* const spill = ws.spill;				 // [levels][spillStride]
+	uint32_t* const spillMask = ws.spillMask;	 // [levels][spillStride], !EMBED
+	uint32_t* const spillMask2 = ws.spillMask2; // second word, TREE
+	const uint64_t spillStride = ws.spillStride, spillLane = (uint64_t)blockIdx.x * 64 + threadIdx.x;
 	const uint32_t lane = threadIdx.x;
 	const uint32_t total = (uint32_t)total64;
 	const Node64* __restrict__ nodes = s.nodes;
-	const uint32_t* __restrict__ kids = s.kids;
-	// LDS ring: explicit LDS address space (so the optimiser cannot fold a ring read and a spill read into one flat
-	// load); slot k of this lane at byte offset k * 1024 + lane * 16
-	LdsU4* const myRing = (LdsU4*)ldsRing + lane;
-	const uint32_t ringAddr = (uint32_t)(uintptr_t)myRing; // LDS byte address of this lane's slot 0
-	uint4* const mySpill = spill + spillLane; // level L at mySpill[L * spillStride]  (irregular rays only)
-	LdsU32* const myRingMask = EMBED ? nullptr : (LdsU32*)ldsMask + lane;
-	// tree flavour: a stacked brick root keeps its 8 child masks in the two mask words (its own mask = their non-zero bytes); an in-brick node its mask in the first
-	LdsU32* const myRingMask2 = TREE ? (LdsU32*)ldsMask + MVRT_RING * 64 + lane : nullptr;
-	// spill rows: spillStride is a power of two (traceWorkspaceLanes), rows * stride * 16 B < 4 GiB: row L of this lane
-	// is base + ((L << spillShift) + lane offset) with 32-bit arithmetic and a scalar base
-	const uint32_t spillShift = 4u + (uint32_t)__builtin_ctzll( spillStride );
-	const uint32_t spillOff = (uint32_t)spillLane * 16u;
-	const uint32_t spillMaskShift = spillShift - 2u, spillMaskOff = (uint32_t)spillLane * 4u;
+	const LaneStack<FL> stk( ldsRing, ldsMask, spill, spillMask, spillMask2, spillStride, spillLane );
 
 	// wave-uniform cursor state
 	uint32_t chunkNext = 0, chunkEnd = 0;
@@ -562,13 +941,8 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 				{
 					if( chunkNext == chunkEnd )
 					{
-						unsigned long long base = 0;
 						const uint32_t c = chunk;
-						if( lane == 0 ) base = atomicAdd( cursor, (unsigned long long)c );
-						// readfirstlane, not a shuffle: the cursor state (and with it `exhausted` and the exit test of the step loop) is then
-						// wave-uniform FOR THE COMPILER -- scalar registers, scalar branches, and the lane masks of the step loop stay in SGPRs
-						// across its exit instead of being copied to VGPRs in every iteration
-						base = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane( (uint32_t)base ) | ( (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane( (uint32_t)( base >> 32 ) ) << 32 );
+						const unsigned long long base = grabChunk( cursor, c, lane );
 						if( base >= total )
 						{
 							exhausted = true;
@@ -586,37 +960,12 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 					if( st == 0u && myRank >= given && myRank < given + take )
 					{
 						ray = chunkNext + ( myRank - given );
-						// ---- ray setup, voxCommon.hpp:240-312 ----
+						// ---- a new ray for this lane: load, set up (setupRay), classify, start ----
 						f3 ro, rd;
 						uint32_t hint = MVRT_NO_HINT;
 						isShadow = io.load( ray, &ro, &rd, &hint );
-						float ix = 1.0f / rd.x, iy = 1.0f / rd.y, iz = 1.0f / rd.z;
-						vMask = 0;
-						if( ix < 0.0f )
-						{
-							vMask |= 1u;
-							ix = -ix;
-							ro.x = s.lox + s.hix - ro.x;
-						}
-						if( iy < 0.0f )
-						{
-							vMask |= 2u;
-							iy = -iy;
-							ro.y = s.loy + s.hiy - ro.y;
-						}
-						if( iz < 0.0f )
-						{
-							vMask |= 4u;
-							iz = -iz;
-							ro.z = s.loz + s.hiz - ro.z;
-						}
-						ix = smin( ix, MVRT_MAXF / smax( smax( sabs( s.lox - ro.x ), sabs( s.hix - ro.x ) ), 1.0f ) );
-						iy = smin( iy, MVRT_MAXF / smax( smax( sabs( s.loy - ro.y ), sabs( s.hiy - ro.y ) ), 1.0f ) );
-						iz = smin( iz, MVRT_MAXF / smax( smax( sabs( s.loz - ro.z ), sabs( s.hiz - ro.z ) ), 1.0f ) );
-						const float t0x = ( s.lox - ro.x ) * ix, t0y = ( s.loy - ro.y ) * iy, t0z = ( s.loz - ro.z ) * iz;
-						tx1 = ( s.hix - ro.x ) * ix;
-						ty1 = ( s.hiy - ro.y ) * iy;
-						tz1 = ( s.hiz - ro.z ) * iz;
+						float t0x, t0y, t0z;
+						vMask = setupRay( s, ro, rd, &t0x, &t0y, &t0z, &tx1, &ty1, &tz1 );
 						descents = 0;
 						path = 0;
 #ifdef MVRT_UTIL_STATS
@@ -624,7 +973,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 						utilVis = 0;
 #endif
 						vMaskHi = vMask | 24u;
-						if( min3f( tx1, ty1, tz1 ) < max3f( t0x, t0y, t0z ) ) // :275-278 misses the root box
+						if( missesRootBox( tx1, ty1, tz1, t0x, t0y, t0z ) )
 						{
 							st = 2u;
 						}
@@ -638,7 +987,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 							// 324-331), which the fast loop ends as a miss (tests/test_gpu_reference_pins.py::test_trace_batch)
 							float resT = MVRT_MAXF;
 							int resN = -1;
-							traceIrregular<FL>( s, tx1, ty1, tz1, t0x, t0y, t0z, vMask, mySpill, spillStride, &resT, &resN, &path, &descents );
+							traceIrregular<FL>( s, tx1, ty1, tz1, t0x, t0y, t0z, vMask, stk.mySpill, spillStride, &resT, &resN, &path, &descents );
 							tx1 = resT; // parked where finishedHit() looks for an st == 4 result
 							level = (uint32_t)resN;
 							st = 4u;
@@ -659,76 +1008,16 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 							st = 1u;
 							if( EMBED && hint != MVRT_NO_HINT && !( min3f( tx1, ty1, tz1 ) < 0.0f ) ) // (a box behind the origin: the root visit settles it)
 							{
-								// Start below the root: replay the walk down the hint's path (see the top of this file).  In a first visit with
-								// T = min( t1 ) >= 0 the candidates behind the origin are those ended by a NEGATIVE mid-plane event (the "before the
-								// first exit" condition of a flip holds for every negative tM once T >= 0), and they are a prefix of the reference's
-								// candidate order; so the first candidate that is not behind has bit a = ( tM_a < S ) | ( tM_a < 0 ) = tM_a < max( S, 0 )
-								// -- the very octant the step below starts its candidate chain with (X, Y, Z there), computed here with the same
-								// operations.  If that octant is the hint's child it exists, the step would enter it (its exit is >= 0 by the same
-								// inequalities: T stays >= 0 level after level), and a later candidate exists iff an axis whose bit is clear flips
-								// before the first exit event (fX, fY, fZ of the step).
-								// Straight-line code: the level counter is a compile-time constant (the loop is unrolled, at most MVRT_HINT_MAX = 7
-								// levels = ring slots: a refilled lane's ring is empty, so nothing is ever evicted here), the node references of the
-								// hint's ancestors are ONE batch of independent table gathers issued up front (no pointer chase), lanes that have left
-								// the hint's path just stop changing their state.
-								const uint32_t P = hintLevelsOf( s.levelsM1 + 1u );
-								const char* const tab = (const char*)kids + ( ( s.rootIndex + 1u ) << 5 ); // the prefix tables lie behind the children array (32 B per node; root = last node)
-								uint32_t anc[MVRT_HINT_MAX + 1];
-#pragma unroll
-								for( uint32_t L = 1; L <= MVRT_HINT_MAX; L++ )
-									anc[L] = L <= P ? *(const uint32_t*)( tab + ( ( prefixTabOffset( L ) + ( hint >> ( 3u * ( P - L ) ) ) ) << 2 ) ) : 0u;
-								uint32_t k = 0u;
-								bool on = true;
-								anc[0] = node;
-#pragma unroll
-								for( uint32_t L = 0; L < MVRT_HINT_MAX; L++ )
-								{
-									if( L < P && on ) // (L < P is wave-uniform; lanes that have left the hint's path drop out of the rest of the nest)
-									{
-										const float scale = mvrt_u2f( ( 127u - L ) << 23 );
-										const v2f t1yz = { ty1, tz1 };
-										const v2f dtyz = { dty, dtz };
-										const float tx0 = tx1 - dtx * scale; // :317-320, the step's own operations
-										const v2f t0yz = t1yz - dtyz * scale;
-										const float S0 = fmaxf( fmaxf( fmaxf( tx0, t0yz.x ), t0yz.y ), 0.0f );
-										const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
-										const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
-										const bool bx = txM < S0, by = tMyz.x < S0, bz = tMyz.y < S0;
-										const uint32_t b = ( bx ? 1u : 0u ) | ( by ? 2u : 0u ) | ( bz ? 4u : 0u );
-										on = ( b ^ vMask ) == ( ( hint >> ( 3u * ( P - 1u - L ) ) ) & 7u ); // the origin's octant is the hint's child: it exists, the step enters it
-										if( on )
-										{
-											const bool later = ( (int)!bx & (int)( txM <= minF( ty1, tz1 ) ) ) | ( (int)!by & (int)( tMyz.x < tx1 ) & (int)( tMyz.x <= tz1 ) ) | ( (int)!bz & (int)( tMyz.y < minF( tx1, ty1 ) ) );
-											if( later ) // stack the ancestor (:377-380); the octant it is left through is the hint's child at this level, which `path` holds as for any entry
-											{
-												// (the node reference -- word 0 -- is filled in after the walk, when the table gathers have landed: their
-												// latency hides behind this arithmetic instead of stalling the wave at the first level)
-												LdsU32* const w = (LdsU32*)( myRing + L * 64 );
-												w[1] = mvrt_f2u( tx1 );
-												w[2] = mvrt_f2u( ty1 );
-												w[3] = mvrt_f2u( tz1 );
-												pending |= 1u << L;
-											}
-											tx1 = bx ? tx1 : txM; // :382-386
-											ty1 = by ? ty1 : tMyz.x;
-											tz1 = bz ? tz1 : tMyz.y;
-											k = L + 1u;
-										}
-									}
-								}
-#pragma unroll
-								for( uint32_t L = 0; L < MVRT_HINT_MAX; L++ )
-								{
-									if( L < P )
-									{
-										if( pending & ( 1u << L ) ) *(LdsU32*)( myRing + L * 64 ) = anc[L];
-										node = k == L + 1u ? anc[L + 1] : node;
-									}
-								}
+								const HintStart hs = replayHint( s, stk.myRing, hint, node, vMask, dtx, dty, dtz, tx1, ty1, tz1 );
+								tx1 = hs.tx1;
+								ty1 = hs.ty1;
+								tz1 = hs.tz1;
+								node = hs.node;
+								pending = hs.pending;
 								inLds = pending;
-								level = k;
-								path = k ? (uint64_t)( hint >> ( 3u * ( P - k ) ) ) : 0ull;
-								descents = k; // the reference fetched one child pointer per level (:381)
+								level = hs.levels;
+								path = hs.path;
+								descents = hs.levels; // the reference fetched one child pointer per level (:381)
 							}
 						}
 					}
@@ -769,30 +1058,7 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 		}
 #endif
 		// ---------------- (2) traversal steps until enough lanes are idle again ----------------
-		// NODE-VISIT step.  The reference examines the candidate children of a node one at a time (voxCommon.hpp:362-412); measured on
-		// a path-traced bunny that is 30.3 candidate tests per ray for 20.6 node visits and 14.7 descents, and 2.0 of the 5.5 pops lead
-		// to no further descent.  Here ONE step settles a whole visit: the order in which the ray leaves the octants of a node is a
-		// pure function of the three mid-plane times and the three exit times -- walk the events (time, axis) in lexicographic order
-		// (the reference's min + "x first, then y" tie rule) until the first exit event; every earlier mid-plane event of a not yet
-		// passed axis is a flip -- so the up to four candidates and their existence in the node's mask are evaluated side by side (the candidates
-		// behind the origin are masked out in the tree flavour and never built in the others), the first valid one is entered, and the node is
-		// pushed only if a later VALID candidate exists.
-		// All of it is 1-bit logic: the compares produce 64-bit lane masks and the combinatorics run on the scalar unit.
-		//
-		// REVISIT of a popped node (flavours that keep the path).  The exit times of a popped node come back bit for bit and its level with them, so the revisit
-		// recomputes the first visit's X, Y, Z, flips and candidate chain i0, i1, i2, i3 exactly.  The chain is nested -- each candidate adds the bit of one flipped
-		// axis -- hence strictly increasing as a number wherever the next candidate exists geometrically (n1 / n2 / n3).  If the node was left through candidate j
-		// (`resume` = i_j), the candidates already dealt with are exactly those with i_k <= resume, and candidate k stays eligible iff i_k > resume: a first visit
-		// (resume = -1) filters nothing.  Where candidates coincide (no flip: i1 == i0; two flips: i2 == i3) the later one has n_k clear and is never valid, so a
-		// tie cannot admit the child already taken a second time.
-		// Behind the origin: these flavours' chain starts at the first candidate that is not behind the origin (see "BEHIND THE ORIGIN" in the step), on a first visit
-		// and on a revisit alike, so the candidate j a node was left through is one of the chain and the filter keeps what follows it.  Eligible and valid are the
-		// same candidates, in the same order, as for a revisit that restarts from candidate j (its remaining flips are the events after a non-negative one: none
-		// is negative): the same child is entered, and the push -- "two or more valid candidates" -- fires under the same condition.  A replayed ancestor of the
-		// hint was left through the origin's octant, which is this chain's i0.
-		// The resume point needs no storage: the child a stacked node was left through is in `path`, in the three bits above the node's own prefix.
-		// Tree flavour (no path): the restart, with the candidate in the sign bits of the stacked exit times and bit-sliced in three SGPR pairs (+ a "first visit"
-		// mask) while the loop runs.
+		// (the NODE-VISIT step and the REVISIT of a popped node: see visitCandidates)
 		lmask cmX = 0ull, cmY = 0ull, cmZ = 0ull, mFirst = 0ull;
 		if( TREE )
 		{
@@ -811,95 +1077,10 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 				io.utilTailActive += (unsigned long long)__popcll( act );
 			}
 #endif
-			const float scale = mvrt_u2f( ( 127u - level ) << 23 );
-			const v2f t1yz = { ty1, tz1 };
-			const v2f dtyz = { dty, dtz };
-			const float tx0 = tx1 - dtx * scale; // :317-320
-			const v2f t0yz = t1yz - dtyz * scale;
-			const float ty0 = t0yz.x, tz0 = t0yz.y;
-			const float S = fmaxf( fmaxf( tx0, ty0 ), tz0 );
-			const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
-			const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
-			const float tyM = tMyz.x, tzM = tMyz.y;
-			// octant the candidate chain starts in.  Tree flavour: the octant the node is entered in (:342-348), or the candidate a popped node resumes with
-			// (cmX / cmY / cmZ carry bits only for lanes whose mFirst bit is clear: kept so by the loop tail).  Flavours that keep the path: the first candidate
-			// that is NOT BEHIND THE ORIGIN, bit a = tM_a < max( S, 0 ) -- see "behind the origin" below
-			const float S0 = TREE ? S : fmaxf( S, 0.0f );
-			const lmask X = TREE ? ( mFirst & __ballot( txM < S ) ) | cmX : __ballot( txM < S0 );
-			const lmask Y = TREE ? ( mFirst & __ballot( tyM < S ) ) | cmY : __ballot( tyM < S0 );
-			const lmask Z = TREE ? ( mFirst & __ballot( tzM < S ) ) | cmZ : __ballot( tzM < S0 );
-			// first exit event = lexicographic minimum of (t1, axis); flips = mid-plane events of unset axes that come before it, i.e.
-			// before EVERY exit event (an axis' own exit never precedes its mid-plane: tM <= t1).  (tM_a, a) < (t1_b, b) is "tM_a <= t1_b" for
-			// a < b and "tM_a < t1_b" for a > b
-			// (one asm statement for the three: after every asm statement whose result the next vector instruction reads the compiler spends a wait state, since a
-			// transcendental result would need one; v_min_f32 has no such hazard)
-			// (tree flavour: it waits for HBM, not for issue slots, and measured 0.3 % slower on the 8192^3 stress octree with the merged statements and the add-with-carry
-			// assembly below: it keeps the separate statements and the selects)
-			float mXY, mYZ, T;
-			if( TREE )
-			{
-				mXY = minF( tx1, ty1 ), mYZ = minF( ty1, tz1 );
-				T = minF( mXY, tz1 );
-			}
-			else
-				asm( "v_min_f32 %0, %3, %4\n\tv_min_f32 %1, %4, %5\n\tv_min_f32 %2, %0, %5" : "=&v"( mXY ), "=&v"( mYZ ), "=&v"( T ) : "v"( tx1 ), "v"( ty1 ), "v"( tz1 ) );
-			const lmask fX = ~X & __ballot( txM <= mYZ );
-			const lmask fY = ~Y & __ballot( tyM < tx1 ) & __ballot( tyM <= tz1 );
-			const lmask fZ = ~Z & __ballot( tzM < mXY );
-			// order of the flips among themselves: (tM, axis) lexicographic
-			const lmask xy = __ballot( txM <= tyM ), xz = __ballot( txM <= tzM ), yz = __ballot( tyM <= tzM );
-			const lmask n1 = fX | fY | fZ, n2 = ( fX & fY ) | ( fZ & ( fX | fY ) ), n3 = fX & fY & fZ; // a 2nd / 3rd / 4th candidate exists geometrically
-			// the axis of the FIRST flip, and -- only when all three axes flip -- of the LAST one
-			const lmask aX = fX & ~( fY & ~xy ) & ~( fZ & ~xz );
-			const lmask aY = fY & ~( fX & xy ) & ~( fZ & ~yz );
-			const lmask aZ = fZ & ~( fX & xz ) & ~( fY & yz );
-			const lmask zX = n3 & ~( xy | xz ), zY = n3 & xy & ~yz, zZ = n3 & xz & yz;
-			// child indices of the four candidates (mirrored space), nested: each adds the axis of one flip.  With two flips the third
-			// candidate is already the last (i2 == i3); with three, it is the last minus the last flip
-			// (asm selects = one v_cndmask on an SGPR mask; written as nested ?: the compiler turns these chains into branches)
-			// (flavours that keep the path: the three bits through add-with-carry, x + x + bit, one instruction per bit and no OR)
-			const uint32_t i0 = TREE ? MVRT_SELKK( X, 1, 0 ) | MVRT_SELKK( Y, 2, 0 ) | MVRT_SELKK( Z, 4, 0 ) : MVRT_SHIFT_IN( MVRT_SHIFT_IN( MVRT_SELKK( Z, 1, 0 ), Y ), X );
-			const uint32_t i3 = i0 | ( TREE ? MVRT_SELKK( fX, 1, 0 ) | MVRT_SELKK( fY, 2, 0 ) | MVRT_SELKK( fZ, 4, 0 ) : MVRT_SHIFT_IN( MVRT_SHIFT_IN( MVRT_SELKK( fZ, 1, 0 ), fY ), fX ) );
-			const uint32_t i1 = i0 | MVRT_SELK( aX, 1, MVRT_SELK( aY, 2, MVRT_SELKK( aZ, 4, 0 ) ) );
-			const uint32_t i2 = i3 ^ MVRT_SELK( zX, 1, MVRT_SELK( zY, 2, MVRT_SELKK( zZ, 4, 0 ) ) );
-			// e_k: candidate k exists in the node's mask -- and, with the path at hand, is eligible (i_k > resume) in the same compare: m = 0 / -1 from the mask bit,
-			// m ^ i_k is ~i_k (negative) for a child that exists and i_k (>= 0) for one that does not; against nres = ~resume (0 on a first visit, negative on a
-			// revisit) "m ^ i_k < nres" is ~i_k < ~resume, i.e. i_k > resume, for the former and never true for the latter
-#define MVRT_EXISTS( i )                                                                                                                                                      \
-	( TREE ? __ballot( ( ( nodeMask >> ( ( ( i ) ^ vMaskHi ) & 7u ) ) & 1u ) != 0u )                                                                                          \
-		   : __ballot( (int)( ( EMBED ? bitMask( node, ( i ) ^ vMaskHi ) : bitMask( nodeMask, ( i ) ^ vMask ) ) ^ ( i ) ) < (int)nres ) )
-			const lmask e0 = MVRT_EXISTS( i0 ), e1 = MVRT_EXISTS( i1 ), e2 = MVRT_EXISTS( i2 ), e3 = MVRT_EXISTS( i3 );
-#undef MVRT_EXISTS
-			// BEHIND THE ORIGIN.  A candidate is behind the origin when the event that ends it is negative (:373).  Events are visited in time order, so the
-			// candidates behind the origin are a prefix of the reference's chain: candidate k is behind iff more than k flips are negative, all of them iff the
-			// exit is (T < 0: `inner` below).
-			// Tree flavour: that prefix is masked out (b0..b2).
-			// Flavours that keep the path never build it: their chain STARTS at the first candidate that is not behind.  That candidate is the entry octant plus the
-			// axes of the negative flips (the flips are ordered by time, so the negative ones are the first), bit a = ( tM_a < S ) | ( tM_a < 0 and a flips ).  With
-			// T >= 0 "a flips" may be dropped: an axis outside the entry octant whose mid-plane is negative and does NOT come before the first exit would make that
-			// exit negative.  So bit a = tM_a < max( S, 0 ) = X, Y, Z above (one v_max, no compare against zero, no prefix logic); the flips of the remaining axes
-			// are the non-negative flips of the reference's chain in their order, i3 is the same last candidate, and i0..i3 are exactly the reference's candidates
-			// nNeg..3 (nNeg = number of negative flips) followed by repeats of the last, which have n_k clear.  Valid candidates, their order and their number are
-			// what the masked chain gave; with T < 0 nothing is entered whatever the chain says.  The resume point of a revisit is a candidate that was entered,
-			// hence one of this chain, and the filter i_k > resume reads it as before.  (tM = -0.0 is not negative for either compare.)
-			lmask b0 = 0ull, b1 = 0ull, b2 = 0ull;
-			if( TREE )
-			{
-				const lmask kx = fX & __ballot( txM < 0.0f ), ky = fY & __ballot( tyM < 0.0f ), kz = fZ & __ballot( tzM < 0.0f );
-				b0 = kx | ky | kz, b1 = ( kx & ky ) | ( ( kx | ky ) & kz ), b2 = kx & ky & kz;
-			}
-			const lmask mLeaf = act & __ballot( node == MVRT_LEAF ); // :322
-			const lmask inner = act & ~mLeaf & ~__ballot( T < 0.0f );
-			// tree flavour: candidate 0 of a popped node is the child it was left through: already done
-			const lmask v0 = TREE ? mFirst & e0 & ~b0 : e0, v1 = n1 & e1 & ~b1, v2 = n2 & e2 & ~b2, v3 = n3 & e3;
-			// push only if a later VALID candidate exists (the reference: any later candidate; measured +8.6 %), i.e. if at least two of the four are valid
-			const lmask vA = v0 | v1, vB = v0 & v1, vC = v2 | v3, vD = v2 & v3;
-			const lmask mGo = inner & ( vA | vC );
-			const lmask mPush = inner & ( vB | vD | ( vA & vC ) );
-			const lmask mHit = mLeaf & __ballot( 0.0f < S0 ); // :324 (0 < S iff 0 < max( S, 0 ))
-			const lmask mPop = act & ~mHit & ~mGo;
-			// the entered candidate = the first valid one
-			const uint32_t ci = selU( v0, i0, selU( v1, i1, selU( v2, i2, i3 ) ) );
+			const VisitStep v = visitCandidates<FL>( level, tx1, ty1, tz1, dtx, dty, dtz, node, nodeMask, vMask, vMaskHi, nres, act, cmX, cmY, cmZ, mFirst );
+			const lmask mHit = v.mHit, mGo = v.mGo, mPush = v.mPush, mPop = v.mPop;
+			const uint32_t ci = v.ci;
+			const float txM = v.txM, tyM = v.tyM, tzM = v.tzM;
 			const uint32_t childBit = ci ^ vMaskHi; // :369 (+24)
 			const uint32_t childIndex = childBit & 7u;
 
@@ -917,19 +1098,19 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 					u4v ev;
 					// (the slot number masked FIRST, then v_lshl_add_u32: inline constants only, in an asm statement of their own.  Written as ( L & 7 ) << 10 the compiler shifts first and needs the mask
 					// 0x1c00 in a scalar register, re-materialised in every iteration.  Embedded flavour only: the others index their mask rings with the same slot number)
-					uint32_t slotAddr = ringAddr + ( ( L & ( MVRT_RING - 1 ) ) << 10 );
-					if( EMBED ) asm( "v_and_b32 %0, %3, %1\n\tv_lshl_add_u32 %0, %0, 10, %2" : "=&v"( slotAddr ) : "v"( L ), "v"( ringAddr ), "n"( MVRT_RING - 1 ) );
+					uint32_t slotAddr = stk.ringAddr + ( ( L & ( MVRT_RING - 1 ) ) << 10 );
+					if( EMBED ) asm( "v_and_b32 %0, %3, %1\n\tv_lshl_add_u32 %0, %0, 10, %2" : "=&v"( slotAddr ) : "v"( L ), "v"( stk.ringAddr ), "n"( MVRT_RING - 1 ) );
 					asm volatile( "ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"( ev ) : "v"( slotAddr ) : "memory" );
 					popped = make_uint4( ev.x, ev.y, ev.z, ev.w );
 					uint32_t poppedMask2 = 0;
-					if( !EMBED ) poppedMask = myRingMask[( L & ( MVRT_RING - 1 ) ) * 64];
-					if( TREE ) poppedMask2 = myRingMask2[( L & ( MVRT_RING - 1 ) ) * 64];
+					if( !EMBED ) poppedMask = stk.myRingMask[( L & ( MVRT_RING - 1 ) ) * 64];
+					if( TREE ) poppedMask2 = stk.myRingMask2[( L & ( MVRT_RING - 1 ) ) * 64];
 					if( !( inLds & bit ) ) // rare; the empty asm keeps this a real branch (otherwise: address select + one flat load)
 					{
 						asm volatile( "" ::: "memory" );
-						popped = *(const uint4*)( (const char*)spill + ( ( L << spillShift ) + spillOff ) );
-						if( !EMBED ) poppedMask = *(const uint32_t*)( (const char*)spillMask + ( ( L << spillMaskShift ) + spillMaskOff ) );
-						if( TREE ) poppedMask2 = *(const uint32_t*)( (const char*)spillMask2 + ( ( L << spillMaskShift ) + spillMaskOff ) );
+						popped = *(const uint4*)( (const char*)spill + ( ( L << stk.spillShift ) + stk.spillOff ) );
+						if( !EMBED ) poppedMask = *(const uint32_t*)( (const char*)spillMask + ( ( L << stk.spillMaskShift ) + stk.spillMaskOff ) );
+						if( TREE ) poppedMask2 = *(const uint32_t*)( (const char*)spillMask2 + ( ( L << stk.spillMaskShift ) + stk.spillMaskOff ) );
 						// the restored exit times are the loaded words themselves: "use" them HERE, so that the wait for this rare load sits in this block.  Left to the
 						// first real use -- the slab arithmetic at the top of the next iteration -- that wait would also cover the child-pointer load of the lanes that
 						// descend, whose latency is meant to hide behind that arithmetic
@@ -965,62 +1146,19 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 			{
 				if( LANE( mPush ) ) // push (:377-380)
 				{
-					const uint32_t slot = level & ( MVRT_RING - 1 );
-					const uint32_t clash = inLds & ( MVRT_RING_CLASH << slot );
-					if( clash ) // the slot still holds a shallower pending entry: evict it to HBM
-					{
-						const uint32_t lc = __builtin_ctz( clash );
-						*(u4v*)( (char*)spill + ( ( lc << spillShift ) + spillOff ) ) = myRing[slot * 64];
-						if( !EMBED ) *(uint32_t*)( (char*)spillMask + ( ( lc << spillMaskShift ) + spillMaskOff ) ) = myRingMask[slot * 64];
-						if( TREE ) *(uint32_t*)( (char*)spillMask2 + ( ( lc << spillMaskShift ) + spillMaskOff ) ) = myRingMask2[slot * 64];
-						inLds &= ~clash;
-					}
-					u4v e;
-					e.x = node;
-					if( TREE )
-					{
-						// the sign bits of a saved node's exit times are free (entered with min >= 0): they carry the child the node is left through
-						e.y = lshlOr( ci, 31u, mvrt_f2u( tx1 ) );
-						e.z = bfi( 0x7FFFFFFFu, mvrt_f2u( ty1 ), ci << 30 );
-						e.w = bfi( 0x7FFFFFFFu, mvrt_f2u( tz1 ), ci << 29 );
-					}
-					else // the child the node is left through goes into `path` below
-					{
-						e.y = mvrt_f2u( tx1 );
-						e.z = mvrt_f2u( ty1 );
-						e.w = mvrt_f2u( tz1 );
-					}
-					myRing[slot * 64] = e;
-					if( !EMBED ) myRingMask[slot * 64] = ( TREE && ( ( s.levelsM1 - level ) & 1u ) ) ? bLo : nodeMask;
-					if( TREE ) myRingMask2[slot * 64] = bHi;
+					inLds = stk.push( s, level, node, nodeMask, bLo, bHi, tx1, ty1, tz1, ci, inLds );
 					pending |= 1u << level;
-					inLds |= 1u << level;
 				}
-				if( EMBED )
-				{
-					// :381 -- 32-bit byte offset from the uniform node base (global_load with an SGPR base, no 64-bit VALU adds)
-					node = *(const uint32_t*)( (const char*)kids + childOffset( node, childIndex << 2 ) );
-				}
-				else if( TREE )
-				{
-					treeDescend( nodes, s.levelsM1, level, childIndex, &node, &nodeMask, &bLo, &bHi, &path );
-				}
-				else
-				{
-					const Node64* nd = nodes + node; // up to 2^32 nodes: 64-bit addressing
-					nodeMask = ( nd->psum[childIndex >> 2] >> ( 8u * ( childIndex & 3u ) ) ) & 0xFFu; // the child's mask: same line as
-					node = nd->children[childIndex];												 // its pointer
-				}
+				const Descent d = descend<FL>( s, level, ci, childIndex, node, nodeMask, bLo, bHi, path, tx1, ty1, tz1, txM, tyM, tzM );
+				node = d.node;
+				nodeMask = d.nodeMask;
+				bLo = d.bLo;
+				bHi = d.bHi;
+				path = d.path;
+				tx1 = d.tx1;
+				ty1 = d.ty1;
+				tz1 = d.tz1;
 				descents++;
-				if( !TREE ) path = ( path << 3 ) | childIndex;
-				if( TREE )
-				{
-					tx1 = mvrt_u2f( bfi( bitMask( ci, 0 ), mvrt_f2u( tx1 ), mvrt_f2u( txM ) ) ); // :382-386: upper half -> keep the exit time, else the mid-plane
-					ty1 = mvrt_u2f( bfi( bitMask( ci, 1 ), mvrt_f2u( ty1 ), mvrt_f2u( tyM ) ) );
-					tz1 = mvrt_u2f( bfi( bitMask( ci, 2 ), mvrt_f2u( tz1 ), mvrt_f2u( tzM ) ) );
-				}
-				else
-					halveBox( ci, &tx1, &ty1, &tz1, txM, tyM, tzM ); // :382-386
 				level++;
 				nres = 0u; // a first visit
 			}
