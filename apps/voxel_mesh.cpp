@@ -2,7 +2,7 @@
 // faces of the voxel set as a PLY quad mesh, one colour per face from its voxel.
 //
 //   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]
-//              [--ao [samples] [--ao-radius voxels]]
+//              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -17,6 +17,9 @@
 // other flag except --fill: one or the other.
 // --lod K: the octree is coarsened in place by K levels (mvrt_svo_coarsen: gridRes >> K, a cell is a voxel when it holds at least --lod-min-count fine voxels,
 // default 1) before anything else is done with it; a line reports voxels and gridRes before and after.  With every other flag.
+// --dilate K, --erode K, --close K, --open K (one of them): K steps of the operator on the voxel set (mvrt_svo_dilate / _erode / _close / _open) with --element
+// faces (the 6 face neighbours) or cube (the 26 of the 3x3x3 block, the default), after --lod and before --fill / --exterior; a line reports the voxels before
+// and after.  --close 1 --fill repairs a shell with one-voxel holes, which the fill alone finds empty of enclosed cells.  With every other flag.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +36,9 @@ int main( int argc, char** argv )
 	float aoRadiusVoxels = 8.0f;
 	int lod = 0;
 	unsigned long long lodMinCount = 1;
+	const char* morphOp = nullptr; // "dilate", "erode", "close" or "open"
+	int morphSteps = 0, morphOps = 0, element = MVRT_MORPH_CUBE;
+	bool elementOk = true;
 	std::vector<const char*> pos;
 	for( int i = 1; i < argc; i++ )
 	{
@@ -50,13 +56,28 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--ao-radius" ) && i + 1 < argc ) aoRadiusVoxels = (float)std::atof( argv[++i] );
 		else if( !std::strcmp( argv[i], "--lod" ) && i + 1 < argc ) lod = std::atoi( argv[++i] );
 		else if( !std::strcmp( argv[i], "--lod-min-count" ) && i + 1 < argc ) lodMinCount = std::strtoull( argv[++i], nullptr, 10 );
+		else if( ( !std::strcmp( argv[i], "--dilate" ) || !std::strcmp( argv[i], "--erode" ) || !std::strcmp( argv[i], "--close" ) || !std::strcmp( argv[i], "--open" ) ) && i + 1 < argc )
+		{
+			morphOp = argv[i] + 2;
+			morphSteps = std::atoi( argv[++i] );
+			morphOps++;
+		}
+		else if( !std::strcmp( argv[i], "--element" ) && i + 1 < argc )
+		{
+			i++;
+			if( !std::strcmp( argv[i], "faces" ) ) element = MVRT_MORPH_FACES;
+			else if( !std::strcmp( argv[i], "cube" ) ) element = MVRT_MORPH_CUBE;
+			else elementOk = false;
+		}
 		else pos.push_back( argv[i] );
 	}
 	if( pos.size() != 3 )
 	{
 		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]\n"
-					 "                  [--ao [samples] [--ao-radius voxels]]\n"
+					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--ao [samples] [--ao-radius voxels]]\n"
 					 "  --lod K      coarsen the octree by K levels first (gridRes >> K); --lod-min-count C keeps a coarse cell only when it holds C fine voxels\n"
+					 "  --dilate K   grow the voxel set by K layers; --erode K peels K layers; --close K = dilate K, erode K (plugs holes); --open K = erode K,\n"
+					 "               dilate K (removes specks).  One of them, after --lod and before --fill / --exterior; --element faces|cube (default cube)\n"
 					 "  --fill       fill the empty cells the voxel shell encloses (white voxels) before the surface is extracted\n"
 					 "  --exterior   drop the faces that look into an enclosed cell instead; the octree stays as built.  Not with --fill\n"
 					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
@@ -69,6 +90,11 @@ int main( int argc, char** argv )
 	if( fill && exterior )
 	{
 		std::fprintf( stderr, "voxel_mesh: --exterior cannot be combined with --fill: one or the other (both write the same faces)\n" );
+		return 2;
+	}
+	if( morphOps > 1 || !elementOk || ( morphOps == 1 && ( morphSteps < 1 || morphSteps > 64 ) ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: one of --dilate / --erode / --close / --open with K in [1, 64], and --element faces or cube\n" );
 		return 2;
 	}
 	if( ao && merge )
@@ -101,6 +127,17 @@ int main( int argc, char** argv )
 		svo.coarsen( lod, lodMinCount, 0, nullptr, stream );
 		dps = svo.m_dps; // (the --ao radius is given in voxels of the mesh that is written)
 		std::printf( "lod: voxels %u -> %u, gridRes %d -> %d\n", before, svo.m_numberOfVoxels, gridRes, gridRes >> lod );
+	}
+	if( morphOp ) // after --lod, before --fill / --exterior
+	{
+		const uint32_t before = svo.m_numberOfVoxels;
+		uint64_t changed = 0;
+		if( !std::strcmp( morphOp, "dilate" ) ) changed = svo.dilate( element, morphSteps, stream );
+		else if( !std::strcmp( morphOp, "erode" ) ) changed = svo.erode( element, morphSteps, stream );
+		else if( !std::strcmp( morphOp, "close" ) ) changed = svo.close( element, morphSteps, stream );
+		else changed = svo.open( element, morphSteps, stream );
+		std::printf( "%s: voxels %u -> %u, element %s, steps %d, %s %llu\n", morphOp, before, svo.m_numberOfVoxels, element == MVRT_MORPH_FACES ? "faces" : "cube", morphSteps,
+					 !std::strcmp( morphOp, "dilate" ) || !std::strcmp( morphOp, "close" ) ? "added" : "removed", (unsigned long long)changed );
 	}
 	if( fill )
 	{

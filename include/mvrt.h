@@ -250,6 +250,53 @@ int mvrt_svo_coarse_voxels( const mvrt_svo* svo, int levelsDown, uint64_t minCou
  * mvrt_svo_build. */
 int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levelsDown, uint64_t minCount, int buildFlags, void* stream );
 
+/* Dilation, erosion, closing and opening of the voxel set (new; the reference has none).  Definitions, on the grid [0, R)^3 with R = gridRes and A = the voxel
+ * set of the handle:
+ *   - Structuring element e: MVRT_MORPH_FACES = the 6 face neighbours, MVRT_MORPH_CUBE = the 26 neighbours of the 3x3x3 block.  N_e(c) = the e-neighbours of
+ *     cell c that lie INSIDE the grid.
+ *   - One dilation step: D(A) = A + { c in the grid, c not in A, N_e(c) meets A }.  It is clipped to the grid: a neighbour coordinate of -1 or R does not exist,
+ *     and at R = 2^21 nothing wraps in the 21 bits per axis of a code.  A new cell c takes, per channel R, G, B of colour and of emission,
+ *     floor( sum over the voxels of N_e(c) in A / their number ), the number being 1..6 or 1..26; both alpha bytes are stored as 255, the alpha bytes of the source
+ *     are not read.  This is the reference's unique rule (voxKernel.cu:201-210) and that of mvrt_svo_coarse_voxels; integer sums make it independent of any
+ *     processing order.  Voxels of A keep all 8 attribute bytes verbatim.
+ *   - One erosion step: E(A) = { v in A : N_e(v) lies in A }.  Cells outside the grid count as OCCUPIED here -- on purpose the opposite of
+ *     mvrt_svo_surface_masks, where outside is empty: a build puts the extreme voxels of every model on the grid border, and with outside = empty every closing
+ *     would eat exactly those.  With this rule D and E are adjoint on the subsets of the grid: E(A) = grid \ D(grid \ A), a closing contains A, an opening lies in
+ *     A, and both are idempotent, for every A, e and number of steps.  Surviving voxels keep all 8 bytes verbatim.
+ *   - k steps = the single step applied k times; the attributes of step i come from the set after step i - 1, so colour spreads outward layer by layer.
+ *     steps in [1, 64].
+ *   - Closing: k dilation steps, then k erosion steps.  Cells of A keep their bytes, an added cell carries the attribute its dilation step gave it.
+ *   - Opening: the SET D^k(E^k(A)), a subset of A; every voxel of it keeps its ORIGINAL 8 bytes.  An opening is a pure removal, the same as mvrt_svo_edit_voxels
+ *     with MVRT_VOXEL_REMOVE on A \ opening; the means of its dilation half are not used.
+ *   - Every result is a property of the voxel set alone.
+ * The listings give one step and follow the rules of mvrt_svo_enclosed_cells word for word: every octree this library built or edited is accepted, in every
+ * flavour, the tree flavour included (only the codes and the attributes are read); an upload is refused ("keeps no Morton codes": it works after one
+ * mvrt_svo_rebuild), an empty handle too ("no octree"), an unknown element too; all refusals happen on the host before any GPU work.  The handle is never
+ * modified.  The calls block.  Arrays hold `capacity` entries; any output may be NULL, all NULL is the sizing call (capacity is then ignored).  A capacity below the
+ * count is an error: the count is still returned and NOTHING is written.  Zero entries is a success.  A failed allocation of scratch returns an error, leaves the
+ * octree whole and leaks nothing.  One step whose (voxel, empty neighbour) pairs number 2^32 - 1 or more is refused.
+ * mvrt_svo_dilation_cells: the cells D(A) \ A in ascending Morton code: xyzDev 3 x uint32, attribsDev 8 bytes, countDev one uint32 = the occupied neighbours the
+ * mean was taken over.  mvrt_svo_erosion_voxels: the voxels A \ E(A), the ones a step removes, as ascending vIndex. */
+#define MVRT_MORPH_FACES 0
+#define MVRT_MORPH_CUBE 1
+int mvrt_svo_dilation_cells( const mvrt_svo* svo, int element, uint64_t capacity, uint32_t* xyzDev /* 3 per cell */, uint32_t* attribsDev /* 8 bytes per cell */,
+							 uint32_t* countDev /* occupied neighbours, 1..26 */, uint64_t* nOut, void* stream );
+int mvrt_svo_erosion_voxels( const mvrt_svo* svo, int element, uint64_t capacity, uint32_t* vIndexDev, uint64_t* nOut, void* stream );
+/* In place: the handle's octree becomes exactly what mvrt_svo_edit_voxels leaves when given the net added cells with their attributes (MVRT_VOXEL_SET) and the net
+ * removed voxels (MVRT_VOXEL_REMOVE) -- nodes and numbering, alpha 255 on new cells, the recomputed hasEmission, the flavour a fresh build picks, the derived
+ * tables, the kept build flags, origin, dps and emission scale.  The steps run on sorted lists of codes and attributes; the levels are built ONCE per call, whatever
+ * `steps` is.  Failures and ordering are the edit's: the new arrays are built next to the old octree, a failure before they are adopted leaves the handle
+ * unchanged, one after that leaves it empty (see mvrt_svo_destroy above); through mvrt_pt_intersector( pt ) the steps issued before finish first and the frame
+ * buffer is not cleared; every mvrt_device_octree view of the handle is invalidated.  A call that changes nothing (a dilation or an erosion of a full grid, a
+ * closing that adds nothing) succeeds with 0 and leaves the handle untouched, its views valid.  Refused with the handle unchanged: an upload, an empty handle, an
+ * unknown element, steps outside [1, 64], a voxel count that would reach 2^32 - 1 at any step (the message names the step and the count), and an erosion or
+ * opening that would leave no voxel.  The count pointer may be NULL: the cells added by a dilation, the voxels removed by an erosion, the NET cells a closing adds
+ * and the NET voxels an opening removes. */
+int mvrt_svo_dilate( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream );
+int mvrt_svo_erode( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream );
+int mvrt_svo_close( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream );
+int mvrt_svo_open( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream );
+
 /* Exterior-only surface extraction without touching the octree, and the three extraction calls on face masks the caller supplies (new; the reference has
  * none).  Definitions:
  *   - Exterior mask of a voxel: one byte, directions d = 0..5 as in mvrt_svo_surface_masks (0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X).  Bit d is set when the

@@ -215,6 +215,74 @@ struct IntersectorOctreeGPU
 		d->refresh();
 	}
 
+	// dilation, erosion, closing and opening of the voxel set (mvrt_svo_dilation_cells / _erosion_voxels / _dilate / _erode / _close / _open; semantics in mvrt.h),
+	// element = MVRT_MORPH_FACES or MVRT_MORPH_CUBE.  Device-pointer forms of the one-step listings: any output may be nullptr, all nullptr = the sizing call; they
+	// return the count.
+	uint64_t dilationCells( int element, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_dilation_cells( m_handle, element, capacity, xyzDev, attribsDev, countDev, &n, stream ), "IntersectorOctreeGPU::dilationCells" );
+		return n;
+	}
+	// host-vector form: xyz = 3 entries per cell in ascending Morton order, attribs = 2, count = 1 (the occupied neighbours of the cell)
+	void dilationCells( int element, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs, std::vector<uint32_t>& count, void* stream ) const
+	{
+		const uint64_t n = dilationCells( element, 0, nullptr, nullptr, nullptr, stream );
+		xyz.resize( n * 3 );
+		attribs.resize( n * 2 );
+		count.resize( n );
+		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), c( nullptr, n * 4, stream );
+		if( n ) dilationCells( element, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint32_t*)c.p, stream );
+		fetch( xyz, x, stream );
+		fetch( attribs, a, stream );
+		fetch( count, c, stream );
+	}
+	uint64_t erosionVoxels( int element, uint64_t capacity, uint32_t* vIndexDev, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_erosion_voxels( m_handle, element, capacity, vIndexDev, &n, stream ), "IntersectorOctreeGPU::erosionVoxels" );
+		return n;
+	}
+	// host-vector form: the vIndex, ascending, of the voxels one erosion step removes
+	void erosionVoxels( int element, std::vector<uint32_t>& vIndex, void* stream ) const
+	{
+		const uint64_t n = erosionVoxels( element, 0, nullptr, stream );
+		vIndex.resize( n );
+		Staged v( nullptr, n * 4, stream );
+		if( n ) erosionVoxels( element, n, (uint32_t*)v.p, stream );
+		fetch( vIndex, v, stream );
+	}
+	// in place, the levels built once per call.  They return the cells added (dilate), the voxels removed (erode), the net cells added (close) and the net voxels
+	// removed (open).  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
+	uint64_t dilate( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_dilate( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::dilate" );
+		refresh();
+		return n;
+	}
+	uint64_t erode( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_erode( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::erode" );
+		refresh();
+		return n;
+	}
+	uint64_t close( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_close( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::close" );
+		refresh();
+		return n;
+	}
+	uint64_t open( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_open( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::open" );
+		refresh();
+		return n;
+	}
+
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const

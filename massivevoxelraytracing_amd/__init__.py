@@ -52,6 +52,8 @@ class DenoiseParams(C.Structure):
 DENOISE_NO_DEMODULATION = 1
 SURFACE_MERGE_ANY_ATTRIBUTE = 1  # mvrt_svo_surface_merged flags (include/mvrt.h)
 SURFACE_MERGE_WELD = 2
+MORPH_FACES = 0  # structuring elements of dilate / erode / close / open (include/mvrt.h)
+MORPH_CUBE = 1
 
 
 # every symbol include/mvrt.h declares: name -> (restype, argtypes)
@@ -93,6 +95,12 @@ SIGNATURES = {
     "mvrt_svo_fill_enclosed": (_i32, [_vp, _vp, _vp, _vp]),
     "mvrt_svo_coarse_voxels": (_i32, [_vp, _i32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_coarsen": (_i32, [_vp, _vp, _i32, _u64, _i32, _vp]),
+    "mvrt_svo_dilation_cells": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_erosion_voxels": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp]),
+    "mvrt_svo_dilate": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "mvrt_svo_erode": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "mvrt_svo_close": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "mvrt_svo_open": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
     "mvrt_svo_device_view": (_i32, [_vp, _vp]),
@@ -457,6 +465,60 @@ class IntersectorOctreeGPU:
         dst = self if dst is None else dst
         _check(lib().mvrt_svo_coarsen(self._h, dst._h, int(levels_down), int(min_count), int(flags), stream))
         return dst
+
+    def dilation_cells_device(self, element=MORPH_CUBE, capacity=0, xyz=None, attribs=None, count=None, stream=None):
+        """mvrt_svo_dilation_cells into caller device arrays of `capacity` cells (any may be None; all None = the sizing call); returns the number of cells.
+        On MvrtError nothing was written."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_dilation_cells(self._h, int(element), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(count), C.byref(n), stream))
+        return n.value
+
+    def dilation_cells(self, element=MORPH_CUBE, stream=None):
+        """the cells one dilation step with `element` (MORPH_FACES / MORPH_CUBE) adds, in ascending Morton order: {xyz (n, 3) uint32, attribs (n, 8) uint8 = the
+        integer mean per channel over the occupied in-grid neighbours with alpha 255, count (n,) uint32 = their number}"""
+        n = self.dilation_cells_device(element, stream=stream)
+        xyz, at, cnt = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint32)
+        if n:
+            self.dilation_cells_device(element, n, xyz, at, cnt, stream)
+        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "count": cnt.to_host()}
+
+    def erosion_voxels_device(self, element=MORPH_CUBE, capacity=0, vIndex=None, stream=None):
+        """mvrt_svo_erosion_voxels into a caller device array of `capacity` entries (None = the sizing call); returns the number of voxels a step removes."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_erosion_voxels(self._h, int(element), int(capacity), _dev_ptr(vIndex), C.byref(n), stream))
+        return n.value
+
+    def erosion_voxels(self, element=MORPH_CUBE, stream=None):
+        """the vIndex, ascending, of the voxels one erosion step removes: those with an empty e-neighbour inside the grid (outside counts as occupied)"""
+        n = self.erosion_voxels_device(element, stream=stream)
+        vi = DeviceArray(n, np.uint32)
+        if n:
+            self.erosion_voxels_device(element, n, vi, stream)
+        return vi.to_host()
+
+    def _morph(self, fn, element, steps, stream):
+        n = C.c_uint64(0)
+        _check(fn(self._h, int(element), int(steps), C.byref(n), stream))
+        return n.value
+
+    def dilate(self, element=MORPH_CUBE, steps=1, stream=None):
+        """mvrt_svo_dilate: `steps` dilation steps in place, the levels built once; returns the cells added (0: the handle was not touched).  Invalidates
+        device_view() snapshots otherwise, like edit_voxels."""
+        return self._morph(lib().mvrt_svo_dilate, element, steps, stream)
+
+    def erode(self, element=MORPH_CUBE, steps=1, stream=None):
+        """mvrt_svo_erode: `steps` erosion steps in place (outside the grid counts as occupied); returns the voxels removed.  Refused when none would be left."""
+        return self._morph(lib().mvrt_svo_erode, element, steps, stream)
+
+    def close(self, element=MORPH_CUBE, steps=1, stream=None):
+        """mvrt_svo_close: `steps` dilation steps, then `steps` erosion steps, in place; returns the net cells added.  close(MORPH_CUBE, 1) before fill_enclosed
+        repairs a shell with one-voxel holes."""
+        return self._morph(lib().mvrt_svo_close, element, steps, stream)
+
+    def open(self, element=MORPH_CUBE, steps=1, stream=None):
+        """mvrt_svo_open: `steps` erosion steps, then `steps` dilation steps, in place; a pure removal (the voxels left keep their bytes); returns the net voxels
+        removed.  Refused when none would be left."""
+        return self._morph(lib().mvrt_svo_open, element, steps, stream)
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""

@@ -663,6 +663,67 @@ MVRT_EXPORT int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levels
 	return adoptBuild( dst, r, origin, dps, gridRes, buildFlags ); // (the source is read before the old octree of dst goes)
 }
 
+// Dilation, erosion, closing and opening (kernels_morph.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listings read the
+// sorted codes and the attributes alone; the in-place calls run their steps on sorted lists next to the old octree and build the levels once, from the last list.
+static int morphSource( const mvrt_svo* svo, const char* who, int element, SurfaceSource* s )
+{
+	if( surfaceSource( svo, who, s ) ) return 1;
+	REQUIRE( element == MVRT_MORPH_FACES || element == MVRT_MORPH_CUBE, "%s: unknown element %d (MVRT_MORPH_FACES = 0, MVRT_MORPH_CUBE = 1)", who, element );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_dilation_cells( const mvrt_svo* svo, int element, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, uint64_t* nOut,
+										 void* stream )
+{
+	SurfaceSource s;
+	if( morphSource( svo, "mvrt_svo_dilation_cells", element, &s ) ) return 1;
+	return morphDilationCells( s, element, capacity, xyzDev, attribsDev, countDev, nOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_erosion_voxels( const mvrt_svo* svo, int element, uint64_t capacity, uint32_t* vIndexDev, uint64_t* nOut, void* stream )
+{
+	SurfaceSource s;
+	if( morphSource( svo, "mvrt_svo_erosion_voxels", element, &s ) ) return 1;
+	return morphErosionVoxels( s, element, capacity, vIndexDev, nOut, (hipStream_t)stream );
+}
+static int morphInPlace( mvrt_svo* svo, const char* who, int op, int element, int steps, uint64_t* nChangedOut, void* stream )
+{
+	if( nChangedOut ) *nChangedOut = 0;
+	SurfaceSource s;
+	if( morphSource( svo, who, element, &s ) ) return 1;
+	REQUIRE( steps >= 1 && steps <= 64, "%s: steps %d is outside [1, 64]", who, steps );
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf morton, attrs;
+	uint32_t n = 0, he = 0;
+	if( morphList( who, s, element, op, steps, morton, attrs, &n, &he, st ) ) return 1;
+	const uint32_t nOld = svo->oct.nVoxels;
+	if( n == nOld ) return 0; // nothing changes: the handle is not touched
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
+	const mvrt_svo_info& info = svo->oct.info;
+	SvoBuildResult r;
+	if( svoBuildFromSorted( morton, attrs, n, (int)info.gridRes, svo->oct.buildFlags, st, &r ) ) return 1;
+	r.hasEmission = he;
+	r.totalDumped = 0; // (as an edit leaves it)
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	if( adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, svo->oct.buildFlags ) ) return 1; // (arguments are read before the old octree goes)
+	if( nChangedOut ) *nChangedOut = n > nOld ? n - nOld : nOld - n;
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_dilate( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_dilate", MVRT_MORPH_OP_DILATE, element, steps, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_erode( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_erode", MVRT_MORPH_OP_ERODE, element, steps, nRemovedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_close( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_close", MVRT_MORPH_OP_CLOSE, element, steps, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_open( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_open", MVRT_MORPH_OP_OPEN, element, steps, nRemovedOut, stream );
+}
+
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );

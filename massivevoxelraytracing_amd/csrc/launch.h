@@ -211,6 +211,22 @@ int coarseVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, int le
 int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
 				hipStream_t stream );
 
+// dilation, erosion, closing and opening (kernels_morph.hip; mvrt_svo_dilation_cells / _erosion_voxels / _dilate / _erode / _close / _open): morton, attrs, nVoxels
+// and levels of the source are read, element is MVRT_MORPH_FACES or MVRT_MORPH_CUBE, checked by the caller.  The calls block, keep their scratch in DevBufs and
+// write NOTHING to the caller's arrays unless they succeed.
+int morphDilationCells( const SurfaceSource& s, int element, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, uint64_t* nOut, hipStream_t stream );
+int morphErosionVoxels( const SurfaceSource& s, int element, uint64_t capacity, uint32_t* vIndexDev, uint64_t* nOut, hipStream_t stream );
+enum
+{
+	MVRT_MORPH_OP_DILATE = 0,
+	MVRT_MORPH_OP_ERODE = 1,
+	MVRT_MORPH_OP_CLOSE = 2,
+	MVRT_MORPH_OP_OPEN = 3
+};
+// `steps` >= 1 steps of the operator on sorted lists, for svoBuildFromSorted: *nOut = the voxels of the result; codes / attribs (allocated here) are left empty
+// when *nOut == nVoxels, which means that the set did not change.  A step that would reach 2^32 - 1 voxels or leave none is refused; `who` names the call
+int morphList( const char* who, const SurfaceSource& s, int element, int op, int steps, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission, hipStream_t stream );
+
 // octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
 // flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.
 struct WalkSource

@@ -90,6 +90,58 @@ MVRT_HDI uint2 coarseAttrib( const uint64_t sums[6], uint64_t count )
 	return a;
 }
 
+// ---- structuring elements (kernels_morph.hip) ---------------------------------------------------------------------------------------------------------------
+// element 0 = the 6 face neighbours, 1 = the 26 neighbours of the 3x3x3 block (MVRT_MORPH_FACES / MVRT_MORPH_CUBE, mvrt.h).  Neighbour j of a cell, j in
+// [0, morphNeighbours( element )): faces in the order -x, +x, -y, +y, -z, +z; the block in the order of t = ( dz + 1 ) * 9 + ( dy + 1 ) * 3 + ( dx + 1 ) with the
+// centre t = 13 left out.  Host-callable like the gap and coarse helpers (tests/hip/morph_host.hip).
+MVRT_HDI bool morphElementOk( int element ) { return element == 0 || element == 1; }
+MVRT_HDI uint32_t morphNeighbours( int element ) { return element == 0 ? 6u : 26u; }
+MVRT_HDI void morphOffset( int element, uint32_t j, int& dx, int& dy, int& dz )
+{
+	if( element == 0 )
+	{
+		const int s = ( j & 1u ) ? 1 : -1;
+		dx = j < 2u ? s : 0;
+		dy = j >= 2u && j < 4u ? s : 0;
+		dz = j >= 4u ? s : 0;
+		return;
+	}
+	const uint32_t t = j < 13u ? j : j + 1u;
+	dx = (int)( t % 3u ) - 1;
+	dy = (int)( ( t / 3u ) % 3u ) - 1;
+	dz = (int)( t / 9u ) - 1;
+}
+// neighbour j of the cell (x, y, z) of a grid of R = 2^levels <= 2^21 cells per axis: false when it lies outside the grid (a coordinate of -1 wraps to 2^32 - 1,
+// one of R is R: neither is below R, so nothing is ever folded back into the 21 bits per axis of a code), else true and *code = its Morton code
+MVRT_HDI bool morphNeighbour( uint32_t x, uint32_t y, uint32_t z, uint32_t levels, int element, uint32_t j, uint64_t* code )
+{
+	int dx, dy, dz;
+	morphOffset( element, j, dx, dy, dz );
+	const uint32_t R = 1u << levels, nx = x + (uint32_t)dx, ny = y + (uint32_t)dy, nz = z + (uint32_t)dz;
+	if( nx >= R || ny >= R || nz >= R ) return false;
+	*code = mortonEncode( nx, ny, nz );
+	return true;
+}
+MVRT_HDI bool codePresentIn( const uint64_t* __restrict__ codes, uint64_t n, uint64_t code )
+{
+	const uint64_t i = lowerBound( codes, 0, n, code );
+	return i < n && codes[i] == code;
+}
+// bit j = neighbour j of voxel (x, y, z) lies inside the grid and is not among the n sorted codes: the cells a dilation step adds next to this voxel, and the
+// reason an erosion step removes it (any bit set; outside the grid counts as occupied)
+MVRT_HDI uint32_t morphEmptyMask( const uint64_t* __restrict__ codes, uint64_t n, uint32_t levels, int element, uint64_t code )
+{
+	uint32_t x, y, z, mask = 0u;
+	mortonDecode( code, x, y, z );
+	const uint32_t nb = morphNeighbours( element );
+	for( uint32_t j = 0; j < nb; j++ )
+	{
+		uint64_t c;
+		if( morphNeighbour( x, y, z, levels, element, j, &c ) && !codePresentIn( codes, n, c ) ) mask |= 1u << j;
+	}
+	return mask;
+}
+
 // ---- host steps -------------------------------------------------------------------------------------------------------------------------------------------
 // offs (allocated here) = the exclusive sums of `items` values of `in`, as T.  lastOnHost: where offs[items - 1] goes, valid when this returns (null = not wanted)
 template <class T, class In> int exclusiveOffsets( In in, uint64_t items, DevBuf& offs, T* lastOnHost, hipStream_t st )

@@ -1,0 +1,52 @@
+"""The morphology interface without a GPU: the header, the Python table and the C++ mirror declare the six calls, and tests/cpp/morph_usage.cpp compiles and
+links against the library (it is run on a GPU by tests/test_gpu_morph_app.py)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import massivevoxelraytracing_amd as mv
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALLS = ("mvrt_svo_dilation_cells", "mvrt_svo_erosion_voxels", "mvrt_svo_dilate", "mvrt_svo_erode", "mvrt_svo_close", "mvrt_svo_open")
+
+
+def compile_usage(tmp_path):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "morph_usage"
+    libdir = os.path.dirname(mv.LIB_PATH)
+    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "morph_usage.cpp"), "-o", str(exe),
+                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    return exe, libdir
+
+
+def test_header_python_and_mirror_declare_the_interface():
+    src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
+    for name in CALLS:
+        assert name + "(" in src and name in mv.SIGNATURES
+    assert "#define MVRT_MORPH_FACES 0" in src and "#define MVRT_MORPH_CUBE 1" in src and (mv.MORPH_FACES, mv.MORPH_CUBE) == (0, 1)
+    for name in ("dilation_cells_device", "dilation_cells", "erosion_voxels_device", "erosion_voxels", "dilate", "erode", "close", "open"):
+        assert callable(getattr(mv.IntersectorOctreeGPU, name))
+    hpp = open(os.path.join(ROOT, "include", "mvrt", "IntersectorOctreeGPU.hpp")).read()
+    for name in ("dilationCells(", "erosionVoxels(", "dilate(", "erode(", "close(", "open("):
+        assert name in hpp
+
+
+def test_refusals_that_need_no_gpu():
+    """a null handle and an empty one are refused on the host, before any GPU work"""
+    lib = mv.lib()
+    assert lib.mvrt_svo_dilate(None, 0, 1, None, None) != 0 and b"null handle" in lib.mvrt_last_error()
+    assert lib.mvrt_svo_erosion_voxels(None, 0, 0, None, None, None) != 0 and b"null handle" in lib.mvrt_last_error()
+    svo = mv.IntersectorOctreeGPU()
+    for call in (svo.dilation_cells_device, svo.erosion_voxels_device, svo.dilate, svo.erode, svo.close, svo.open):
+        with pytest.raises(mv.MvrtError, match="no octree"):
+            call()
+
+
+def test_cpp_mirror_morph_methods_compile_and_link(tmp_path):
+    exe, libdir = compile_usage(tmp_path)
+    out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
+    assert b"usage" in out
