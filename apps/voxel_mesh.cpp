@@ -2,7 +2,8 @@
 // faces of the voxel set as a PLY quad mesh, one colour per face from its voxel.
 //
 //   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]
-//              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--ao [samples] [--ao-radius voxels]]
+//              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]
+//              [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -20,7 +21,13 @@
 // --dilate K, --erode K, --close K, --open K (one of them): K steps of the operator on the voxel set (mvrt_svo_dilate / _erode / _close / _open) with --element
 // faces (the 6 face neighbours) or cube (the 26 of the 3x3x3 block, the default), after --lod and before --fill / --exterior; a line reports the voxels before
 // and after.  --close 1 --fill repairs a shell with one-voxel holes, which the fill alone finds empty of enclosed cells.  With every other flag.
+// --components: a line reports the number of connected components under --element and the five largest sizes (mvrt_svo_components); nothing changes.
+// --keep-largest K, --min-component N (either or both): only the components of at least N voxels and, of those, the K largest stay (mvrt_svo_keep_components
+// with --element: cube = 26-connected, the default; faces = 6-connected); a line reports voxels and components before and after.  All three come after --dilate
+// / --erode / --close / --open and before --fill / --exterior, --components first: it counts what the other two select from.  --close 1 --keep-largest 1 --fill
+// repairs a shell, drops the debris around it and fills it.  With every other flag.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,7 +45,9 @@ int main( int argc, char** argv )
 	unsigned long long lodMinCount = 1;
 	const char* morphOp = nullptr; // "dilate", "erode", "close" or "open"
 	int morphSteps = 0, morphOps = 0, element = MVRT_MORPH_CUBE;
-	bool elementOk = true;
+	bool elementOk = true, components = false;
+	long long keepLargest = 0, minComponent = 1; // 0 = no --keep-largest
+	bool keep = false, keepOk = true;
 	std::vector<const char*> pos;
 	for( int i = 1; i < argc; i++ )
 	{
@@ -62,6 +71,19 @@ int main( int argc, char** argv )
 			morphSteps = std::atoi( argv[++i] );
 			morphOps++;
 		}
+		else if( !std::strcmp( argv[i], "--components" ) ) components = true;
+		else if( !std::strcmp( argv[i], "--keep-largest" ) && i + 1 < argc )
+		{
+			keepLargest = std::atoll( argv[++i] );
+			keep = true;
+			keepOk = keepOk && keepLargest >= 1 && keepLargest <= 0xFFFFFFFFll;
+		}
+		else if( !std::strcmp( argv[i], "--min-component" ) && i + 1 < argc )
+		{
+			minComponent = std::atoll( argv[++i] );
+			keep = true;
+			keepOk = keepOk && minComponent >= 1;
+		}
 		else if( !std::strcmp( argv[i], "--element" ) && i + 1 < argc )
 		{
 			i++;
@@ -74,10 +96,14 @@ int main( int argc, char** argv )
 	if( pos.size() != 3 )
 	{
 		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]\n"
-					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--ao [samples] [--ao-radius voxels]]\n"
+					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]\n"
+					 "                  [--ao [samples] [--ao-radius voxels]]\n"
 					 "  --lod K      coarsen the octree by K levels first (gridRes >> K); --lod-min-count C keeps a coarse cell only when it holds C fine voxels\n"
 					 "  --dilate K   grow the voxel set by K layers; --erode K peels K layers; --close K = dilate K, erode K (plugs holes); --open K = erode K,\n"
 					 "               dilate K (removes specks).  One of them, after --lod and before --fill / --exterior; --element faces|cube (default cube)\n"
+					 "  --components report the number of connected components (26-connected with --element cube, 6-connected with faces) and the five largest\n"
+					 "  --keep-largest K, --min-component N  keep only the components of at least N voxels and, of those, the K largest; after the\n"
+					 "               operators above and before --fill / --exterior\n"
 					 "  --fill       fill the empty cells the voxel shell encloses (white voxels) before the surface is extracted\n"
 					 "  --exterior   drop the faces that look into an enclosed cell instead; the octree stays as built.  Not with --fill\n"
 					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
@@ -95,6 +121,11 @@ int main( int argc, char** argv )
 	if( morphOps > 1 || !elementOk || ( morphOps == 1 && ( morphSteps < 1 || morphSteps > 64 ) ) )
 	{
 		std::fprintf( stderr, "voxel_mesh: one of --dilate / --erode / --close / --open with K in [1, 64], and --element faces or cube\n" );
+		return 2;
+	}
+	if( !keepOk )
+	{
+		std::fprintf( stderr, "voxel_mesh: --keep-largest needs K in [1, 2^32 - 1] and --min-component N >= 1\n" );
 		return 2;
 	}
 	if( ao && merge )
@@ -138,6 +169,24 @@ int main( int argc, char** argv )
 		else changed = svo.open( element, morphSteps, stream );
 		std::printf( "%s: voxels %u -> %u, element %s, steps %d, %s %llu\n", morphOp, before, svo.m_numberOfVoxels, element == MVRT_MORPH_FACES ? "faces" : "cube", morphSteps,
 					 !std::strcmp( morphOp, "dilate" ) || !std::strcmp( morphOp, "close" ) ? "added" : "removed", (unsigned long long)changed );
+	}
+	if( components ) // what --keep-largest / --min-component select from
+	{
+		std::vector<uint32_t> label, size, first, box;
+		svo.components( element, label, size, first, box, stream );
+		std::sort( size.begin(), size.end(), []( uint32_t a, uint32_t b ) { return a > b; } );
+		std::printf( "components: %zu, element %s, largest", size.size(), element == MVRT_MORPH_FACES ? "faces" : "cube" );
+		for( size_t i = 0; i < size.size() && i < 5; i++ ) std::printf( " %u", size[i] );
+		std::printf( "\n" );
+	}
+	if( keep ) // after the operators, before --fill / --exterior
+	{
+		const uint32_t before = svo.m_numberOfVoxels;
+		const uint64_t nBefore = svo.components( element, nullptr, 0, nullptr, nullptr, nullptr, nullptr, stream );
+		uint64_t nKept = 0;
+		const uint64_t removed = svo.keepComponents( element, (uint64_t)minComponent, (uint32_t)keepLargest, &nKept, stream );
+		std::printf( "keep: voxels %u -> %u, components %llu -> %llu, element %s, removed %llu\n", before, svo.m_numberOfVoxels, (unsigned long long)nBefore,
+					 (unsigned long long)nKept, element == MVRT_MORPH_FACES ? "faces" : "cube", (unsigned long long)removed );
 	}
 	if( fill )
 	{

@@ -297,6 +297,36 @@ int mvrt_svo_erode( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut
 int mvrt_svo_close( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream );
 int mvrt_svo_open( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream );
 
+/* Connected components of the voxel set (new; the reference has none).  Definitions, on the grid [0, R)^3 with R = gridRes and A = the voxel set of the handle:
+ *   - Connectivity e: MVRT_MORPH_FACES (6) or MVRT_MORPH_CUBE (26), the structuring elements above.
+ *   - Two voxels are adjacent when one is an e-neighbour of the other INSIDE the grid: nothing wraps at coordinate 0, at R - 1, or in the 21 bits per axis of a code
+ *     at R = 2^21.  A component is a class of the transitive closure of adjacency.
+ *   - Labels: the components are numbered 0, 1, ... in order of first appearance in vIndex order (ascending Morton code): label[0] == 0, and a new label is always
+ *     the previous maximum + 1 -- the numbering rule of mvrt_svo_enclosed_cells.
+ *   - Per component: size = its voxels (uint32); first = its lowest vIndex (uint32); box = 6 x uint32: min x, y, z, then max x, y, z, inclusive.
+ *   - Everything is a property of the voxel set alone: integers only, independent of any schedule.
+ * mvrt_svo_components, the listing, follows the rules of mvrt_svo_enclosed_cells / mvrt_svo_dilation_cells word for word: every octree this library built or
+ * edited is accepted, in every flavour, the tree flavour included (only the codes are read); an upload is refused ("keeps no Morton codes": it works after one
+ * mvrt_svo_rebuild), an empty handle too ("no octree"), an unknown element too; all refusals happen on the host before any GPU work.  The handle is never
+ * modified.  The call blocks.  labelDev holds numberOfVoxels entries in vIndex order; sizeDev, firstDev and boxDev hold componentCapacity components.  Any output
+ * may be NULL; all four arrays NULL is the sizing call (componentCapacity is then ignored, as it is when labelDev is the only array).  A componentCapacity below the
+ * count with a per-component array given is an error: the counts are still returned and NOTHING is written, labelDev included.  *nComponentsOut = the number of
+ * components, *largestOut = the size of the largest.  A failed allocation of scratch returns an error, leaves the octree whole, leaks nothing and has written
+ * nothing. */
+int mvrt_svo_components( const mvrt_svo* svo, int element, uint32_t* labelDev /* numberOfVoxels, vIndex order */, uint64_t componentCapacity, uint32_t* sizeDev,
+						 uint32_t* firstDev, uint32_t* boxDev /* 6 per component */, uint64_t* nComponentsOut, uint64_t* largestOut, void* stream );
+/* In place: component c is kept when size(c) >= minVoxels and ( keepLargest == 0 or rank(c) < keepLargest ), rank ordering the components by (size descending,
+ * label ascending): a tie in size goes to the component that appears first.  minVoxels >= 1; minVoxels == 1 && keepLargest == 0 keeps everything.  The handle
+ * becomes exactly what mvrt_svo_edit_voxels leaves when given the voxels of the dropped components with MVRT_VOXEL_REMOVE -- nodes and numbering, the surviving
+ * attributes (all 8 bytes verbatim), the recomputed hasEmission, the flavour a fresh build picks, the derived tables, the kept build flags, origin, dps and
+ * emission scale, totalDumpedVoxels 0.  The list is compacted on the device and the levels are built once.  Failures and ordering are the edit's: the new arrays
+ * are built next to the old octree, a failure before they are adopted leaves the handle unchanged, one after that leaves it empty (see mvrt_svo_destroy above);
+ * through mvrt_pt_intersector( pt ) the steps issued before finish first and the frame buffer is not cleared; every mvrt_device_octree view of the handle is
+ * invalidated.  A call that drops nothing succeeds, reports 0 removed and leaves the handle untouched, its views valid.  Refused with the handle unchanged: an
+ * upload, an empty handle, an unknown element, minVoxels == 0, and a selection that would leave no voxel ("would leave no voxel").  *nRemovedOut = the voxels
+ * removed, *nKeptOut = the components kept; either may be NULL. */
+int mvrt_svo_keep_components( mvrt_svo* svo, int element, uint64_t minVoxels, uint32_t keepLargest, uint64_t* nRemovedOut, uint64_t* nKeptOut, void* stream );
+
 /* Exterior-only surface extraction without touching the octree, and the three extraction calls on face masks the caller supplies (new; the reference has
  * none).  Definitions:
  *   - Exterior mask of a voxel: one byte, directions d = 0..5 as in mvrt_svo_surface_masks (0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X).  Bit d is set when the

@@ -283,6 +283,42 @@ struct IntersectorOctreeGPU
 		return n;
 	}
 
+	// connected components of the voxel set (mvrt_svo_components / mvrt_svo_keep_components; semantics in mvrt.h), element = MVRT_MORPH_FACES (6-connected) or
+	// MVRT_MORPH_CUBE (26-connected).  Device-pointer form: labelDev holds numberOfVoxels entries, the others componentCapacity components (boxDev 6 each); any
+	// output may be nullptr, all nullptr = the sizing call.  Returns the number of components; *largest (may be nullptr) = the size of the largest.
+	uint64_t components( int element, uint32_t* labelDev, uint64_t componentCapacity, uint32_t* sizeDev, uint32_t* firstDev, uint32_t* boxDev, uint64_t* largest, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_components( m_handle, element, labelDev, componentCapacity, sizeDev, firstDev, boxDev, &n, largest, stream ), "IntersectorOctreeGPU::components" );
+		return n;
+	}
+	// host-vector form: label = one entry per voxel in vIndex order, numbered by first appearance; per component size = 1 entry, first = 1 (its lowest vIndex),
+	// box = 6 (min x, y, z, max x, y, z)
+	void components( int element, std::vector<uint32_t>& label, std::vector<uint32_t>& size, std::vector<uint32_t>& first, std::vector<uint32_t>& box, void* stream ) const
+	{
+		const uint64_t n = components( element, nullptr, 0, nullptr, nullptr, nullptr, nullptr, stream );
+		label.resize( m_numberOfVoxels );
+		size.resize( n );
+		first.resize( n );
+		box.resize( n * 6 );
+		Staged l( nullptr, (uint64_t)m_numberOfVoxels * 4, stream ), s( nullptr, n * 4, stream ), f( nullptr, n * 4, stream ), b( nullptr, n * 24, stream );
+		components( element, (uint32_t*)l.p, n, (uint32_t*)s.p, (uint32_t*)f.p, (uint32_t*)b.p, nullptr, stream );
+		fetch( label, l, stream );
+		fetch( size, s, stream );
+		fetch( first, f, stream );
+		fetch( box, b, stream );
+	}
+	// in place: keeps the components of at least minVoxels voxels and, where keepLargest != 0, only the keepLargest largest of them (a tie goes to the component
+	// that appears first).  Returns the voxels removed; *keptComponents (may be nullptr) = the components kept.  0: the octree was not touched; otherwise
+	// deviceView() snapshots are invalidated.
+	uint64_t keepComponents( int element = MVRT_MORPH_CUBE, uint64_t minVoxels = 1, uint32_t keepLargest = 0, uint64_t* keptComponents = nullptr, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_keep_components( m_handle, element, minVoxels, keepLargest, &n, keptComponents, stream ), "IntersectorOctreeGPU::keepComponents" );
+		refresh();
+		return n;
+	}
+
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const

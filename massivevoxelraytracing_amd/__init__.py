@@ -97,6 +97,8 @@ SIGNATURES = {
     "mvrt_svo_coarsen": (_i32, [_vp, _vp, _i32, _u64, _i32, _vp]),
     "mvrt_svo_dilation_cells": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_erosion_voxels": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp]),
+    "mvrt_svo_components": (_i32, [_vp, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_keep_components": (_i32, [_vp, _i32, _u64, C.c_uint32, _vp, _vp, _vp]),
     "mvrt_svo_dilate": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_erode": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_close": (_i32, [_vp, _i32, _i32, _vp, _vp]),
@@ -519,6 +521,29 @@ class IntersectorOctreeGPU:
         """mvrt_svo_open: `steps` erosion steps, then `steps` dilation steps, in place; a pure removal (the voxels left keep their bytes); returns the net voxels
         removed.  Refused when none would be left."""
         return self._morph(lib().mvrt_svo_open, element, steps, stream)
+
+    def components_device(self, element=MORPH_CUBE, label=None, capacity=0, size=None, first=None, box=None, stream=None):
+        """mvrt_svo_components into caller device arrays: label of numberOfVoxels uint32, size / first of `capacity` uint32, box of capacity x 6 uint32 (any may be
+        None; all None = the sizing call); returns (nComponents, largest).  On MvrtError nothing was written."""
+        n, big = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_components(self._h, int(element), _dev_ptr(label), int(capacity), _dev_ptr(size), _dev_ptr(first), _dev_ptr(box), C.byref(n), C.byref(big), stream))
+        return n.value, big.value
+
+    def components(self, element=MORPH_CUBE, stream=None):
+        """the connected components under `element` (MORPH_FACES = 6-connected, MORPH_CUBE = 26-connected), numbered in order of first appearance in vIndex
+        order: {label (numberOfVoxels,) uint32, size (n,) uint32, first (n,) uint32 = the lowest vIndex, box (n, 6) uint32 = min x, y, z, max x, y, z}"""
+        n, _ = self.components_device(element, stream=stream)
+        label, size, first, box = DeviceArray(self.info().numberOfVoxels, np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 6), np.uint32)
+        self.components_device(element, label, n, size, first, box, stream)
+        return {"label": label.to_host(), "size": size.to_host(), "first": first.to_host(), "box": box.to_host()}
+
+    def keep_components(self, element=MORPH_CUBE, min_voxels=1, keep_largest=0, stream=None):
+        """mvrt_svo_keep_components: keeps, in place, the components of at least `min_voxels` voxels and, where keep_largest != 0, only the keep_largest largest
+        of them (a tie goes to the component that appears first); exactly edit_voxels with VOXEL_REMOVE on the rest.  Returns (voxels removed, components
+        kept); 0 removed: the handle was not touched.  Refused when no voxel would be left."""
+        removed, kept = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_keep_components(self._h, int(element), int(min_voxels), int(keep_largest), C.byref(removed), C.byref(kept), stream))
+        return removed.value, kept.value
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""

@@ -724,6 +724,48 @@ MVRT_EXPORT int mvrt_svo_open( mvrt_svo* svo, int element, int steps, uint64_t* 
 	return morphInPlace( svo, "mvrt_svo_open", MVRT_MORPH_OP_OPEN, element, steps, nRemovedOut, stream );
 }
 
+// Connected components (kernels_components.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listing reads the sorted codes
+// alone; the in-place call compacts the kept voxels next to the old octree and builds the levels once, as the opening does.  The handle and the element are
+// checked by morphSource: the connectivity is a structuring element.
+MVRT_EXPORT int mvrt_svo_components( const mvrt_svo* svo, int element, uint32_t* labelDev, uint64_t componentCapacity, uint32_t* sizeDev, uint32_t* firstDev, uint32_t* boxDev,
+									 uint64_t* nComponentsOut, uint64_t* largestOut, void* stream )
+{
+	SurfaceSource s;
+	if( morphSource( svo, "mvrt_svo_components", element, &s ) ) return 1;
+	return componentsList( s, element, labelDev, componentCapacity, sizeDev, firstDev, boxDev, nComponentsOut, largestOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_keep_components( mvrt_svo* svo, int element, uint64_t minVoxels, uint32_t keepLargest, uint64_t* nRemovedOut, uint64_t* nKeptOut, void* stream )
+{
+	const char* who = "mvrt_svo_keep_components";
+	if( nRemovedOut ) *nRemovedOut = 0;
+	if( nKeptOut ) *nKeptOut = 0;
+	SurfaceSource s;
+	if( morphSource( svo, who, element, &s ) ) return 1;
+	REQUIRE( minVoxels >= 1, "%s: minVoxels 0 (1 keeps every component)", who );
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf morton, attrs;
+	uint32_t n = 0, he = 0, nComponents = 0, nKept = 0;
+	if( componentsKeepList( s, element, minVoxels, keepLargest, morton, attrs, &n, &he, &nComponents, &nKept, st ) ) return 1;
+	REQUIRE( nKept >= 1, "%s: minVoxels %llu would leave no voxel (the largest of the %u components is smaller)", who, (unsigned long long)minVoxels, nComponents );
+	const uint32_t nOld = svo->oct.nVoxels;
+	if( n == nOld ) // nothing goes: the handle is not touched
+	{
+		if( nKeptOut ) *nKeptOut = nKept;
+		return 0;
+	}
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
+	const mvrt_svo_info& info = svo->oct.info;
+	SvoBuildResult r;
+	if( svoBuildFromSorted( morton, attrs, n, (int)info.gridRes, svo->oct.buildFlags, st, &r ) ) return 1;
+	r.hasEmission = he;
+	r.totalDumped = 0; // (as an edit leaves it)
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	if( adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, svo->oct.buildFlags ) ) return 1; // (arguments are read before the old octree goes)
+	if( nRemovedOut ) *nRemovedOut = nOld - n;
+	if( nKeptOut ) *nKeptOut = nKept;
+	return 0;
+}
+
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );

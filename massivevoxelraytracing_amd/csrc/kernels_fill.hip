@@ -35,39 +35,7 @@ __global__ void __launch_bounds__( FB ) kFillLinearKeys( const uint64_t* __restr
 
 // (gapLength and gapNodeOfCell: voxel_passes.h)
 
-// ---- union-find over node ids: parent[v] <= v always, a root has parent[v] == v, only roots are ever hooked and only under smaller ids ------------------------
-MVRT_DI uint32_t ufLoad( uint32_t* p ) { return __hip_atomic_load( p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ); }
-MVRT_DI void ufStore( uint32_t* p, uint32_t v ) { __hip_atomic_store( p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ); }
-// v strictly decreases.  Path halving on the way: a node that is no root (it never becomes one again) is pointed at its grandparent, an ancestor with a lower id
-MVRT_DI uint32_t ufFind( uint32_t* parent, uint32_t v )
-{
-	for( ;; )
-	{
-		const uint32_t p = ufLoad( parent + v );
-		if( p >= v ) return v; // ( p == v: a root )
-		const uint32_t gp = ufLoad( parent + p );
-		if( gp < p ) ufStore( parent + v, gp );
-		v = p;
-	}
-}
-MVRT_DI void ufUnite( uint32_t* parent, uint32_t a, uint32_t b )
-{
-	for( ;; )
-	{
-		a = ufFind( parent, a );
-		b = ufFind( parent, b );
-		if( a == b ) return;
-		if( a < b )
-		{
-			const uint32_t t = a;
-			a = b;
-			b = t;
-		}
-		// a > b: hook a under b if a is still a root.  Otherwise somebody hooked it meanwhile, under an id below a: the next find( a ) ends lower, so a + b
-		// strictly decreases from one turn to the next
-		if( atomicCAS( parent + a, a, b ) == a ) return;
-	}
-}
+// (ufLoad, ufStore, ufFind, ufUnite and ufRoot, the union-find over node ids: voxel_passes.h)
 
 __global__ void __launch_bounds__( FB ) kFillInitParents( uint32_t* __restrict__ parent, uint64_t nNodes )
 {
@@ -111,16 +79,6 @@ __global__ void __launch_bounds__( FB ) kFillUnite( const uint64_t* __restrict__
 	if( z < R - 1 ) uniteWithRow( lin, n, L, parent, g, row + R, x0, x1 );
 }
 
-// the same walk without the stores, for the flatten: there parent[v] is written once, by v's own thread, with the root
-MVRT_DI uint32_t ufRoot( uint32_t* parent, uint32_t v )
-{
-	for( ;; )
-	{
-		const uint32_t p = ufLoad( parent + v );
-		if( p >= v ) return v;
-		v = p;
-	}
-}
 // parent[v] = the root of v (node v = gap v - 1; the unions are complete: this is a kernel of its own), and the number of enclosed regions = gaps that are
 // their own root.  No path halving here: a halving store of a grandparent read earlier could land behind the store of the root and leave a node that is no
 // root in a flattened entry.  A thread that walks through an entry another thread has flattened already reads the root there, else an ancestor as before

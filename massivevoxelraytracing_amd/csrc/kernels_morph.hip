@@ -245,26 +245,46 @@ int dilateStep( const char* who, int step, VoxelList& l, uint32_t levels, int el
 	*changed = 1;
 	return 0;
 }
+// the entries of a list whose mask is 0, in order: *nKept of them, into codes / attrs (allocated here; left empty when *nKept is 0 or n: the caller looks at it).
+// Has waited for the stream
+int compactUnmasked( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attrs, uint32_t* nKept, hipStream_t st )
+{
+	DevBuf offs;
+	hipcub::CountingInputIterator<uint32_t> counting( 0u );
+	hipcub::TransformInputIterator<uint32_t, MaskFlag, hipcub::CountingInputIterator<uint32_t>> kept( counting, MaskFlag{ mask, n, 0u } );
+	if( exclusiveOffsets<uint32_t>( kept, (uint64_t)n + 1, offs, nKept, st ) ) return 1;
+	if( *nKept == n || *nKept == 0 ) return 0;
+	if( codes.alloc( (uint64_t)*nKept * 8 ) || attrs.alloc( (uint64_t)*nKept * 8 ) ) return 1;
+	hipLaunchKernelGGL( kMorphCompact, dim3( divUp( n, MB ) ), dim3( MB ), 0, st, srcCodes, srcAttrs, mask, offs.as<uint32_t>(), n, 0u, codes.as<uint64_t>(), attrs.as<uint2>(), nullptr );
+	MVRT_HIP( hipGetLastError() );
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (offs is released on return)
+	return 0;
+}
+// *hasEmission = 1 where one of the n attributes has an emission byte set.  Has waited for the stream
+int anyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t st )
+{
+	DevBuf flag;
+	if( flag.alloc( 4 ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( flag.p, 0, 4, st ) );
+	hipLaunchKernelGGL( kMorphAnyEmission, dim3( divUp( n, MB ) ), dim3( MB ), 0, st, attrs, n, flag.as<uint32_t>() );
+	MVRT_HIP( hipGetLastError() );
+	MVRT_HIP( hipMemcpyAsync( hasEmission, flag.p, 4, hipMemcpyDeviceToHost, st ) );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	return 0;
+}
 int erodeStep( const char* who, int step, VoxelList& l, uint32_t levels, int element, int* changed, hipStream_t st )
 {
 	*changed = 0;
-	DevBuf mask, offs, codes, attrs;
+	DevBuf mask, codes, attrs;
 	if( launchMasks( l.codes, l.n, levels, element, mask, st ) ) return 1;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, MaskFlag, hipcub::CountingInputIterator<uint32_t>> kept( counting, MaskFlag{ mask.as<uint32_t>(), l.n, 0u } );
 	uint32_t nKept = 0;
-	if( exclusiveOffsets<uint32_t>( kept, (uint64_t)l.n + 1, offs, &nKept, st ) ) return 1;
+	if( compactUnmasked( l.codes, l.attrs, mask.as<uint32_t>(), l.n, codes, attrs, &nKept, st ) ) return 1;
 	if( nKept == l.n ) return 0;
 	if( nKept == 0 )
 	{
 		mvrtSetError( "%s: erosion step %d would leave no voxel (it removes all %u)", who, step, l.n );
 		return 1;
 	}
-	if( codes.alloc( (uint64_t)nKept * 8 ) || attrs.alloc( (uint64_t)nKept * 8 ) ) return 1;
-	hipLaunchKernelGGL( kMorphCompact, dim3( divUp( l.n, MB ) ), dim3( MB ), 0, st, l.codes, l.attrs, mask.as<uint32_t>(), offs.as<uint32_t>(), l.n, 0u, codes.as<uint64_t>(),
-						attrs.as<uint2>(), nullptr );
-	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipStreamSynchronize( st ) ); // (the inputs are released below)
 	l.take( codes, attrs, nKept );
 	*changed = 1;
 	return 0;
@@ -336,9 +356,6 @@ int morphList( const char* who, const SurfaceSource& s, int element, int op, int
 	*hasEmission = 0;
 	// dilation grows, erosion shrinks, a closing holds the set and an opening lies in it: the same count is the same set, with the same bytes
 	if( l.n == s.nVoxels ) return 0;
-	DevBuf flag;
-	if( flag.alloc( 4 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( flag.p, 0, 4, st ) );
 	if( op == MVRT_MORPH_OP_OPEN ) // a pure removal: the original bytes, not the means of the dilation half
 	{
 		DevBuf original;
@@ -349,11 +366,17 @@ int morphList( const char* who, const SurfaceSource& s, int element, int op, int
 		l.ownAttrs = std::move( original );
 		l.attrs = l.ownAttrs.as<uint2>();
 	}
-	hipLaunchKernelGGL( kMorphAnyEmission, dim3( divUp( l.n, MB ) ), dim3( MB ), 0, st, l.attrs, l.n, flag.as<uint32_t>() );
-	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipMemcpyAsync( hasEmission, flag.p, 4, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( anyEmission( l.attrs, l.n, hasEmission, st ) ) return 1;
 	codes = std::move( l.ownCodes );
 	attribs = std::move( l.ownAttrs );
 	return 0;
+}
+
+int morphCompactKept( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
+					  hipStream_t st )
+{
+	*hasEmission = 0;
+	if( compactUnmasked( srcCodes, srcAttrs, mask, n, codes, attribs, nKept, st ) ) return 1;
+	if( *nKept == n || *nKept == 0 ) return 0;
+	return anyEmission( attribs.as<uint2>(), *nKept, hasEmission, st );
 }

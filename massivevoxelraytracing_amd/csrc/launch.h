@@ -226,6 +226,20 @@ enum
 // `steps` >= 1 steps of the operator on sorted lists, for svoBuildFromSorted: *nOut = the voxels of the result; codes / attribs (allocated here) are left empty
 // when *nOut == nVoxels, which means that the set did not change.  A step that would reach 2^32 - 1 voxels or leave none is refused; `who` names the call
 int morphList( const char* who, const SurfaceSource& s, int element, int op, int steps, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission, hipStream_t stream );
+// the erosion's scan and scatter on a caller's mask: the entries of the n sorted codes and attributes whose mask is 0, in order, into codes / attribs (allocated
+// here; left empty when *nKept is 0 or n) and the emission flag over them.  Blocks
+int morphCompactKept( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
+					  hipStream_t stream );
+
+// connected components (kernels_components.hip; mvrt_svo_components / mvrt_svo_keep_components): morton, attrs, nVoxels and levels of the source are read, element
+// is MVRT_MORPH_FACES or MVRT_MORPH_CUBE, checked by the caller.  The calls block, keep their scratch in DevBufs and write NOTHING to the caller's arrays
+// unless they succeed.
+int componentsList( const SurfaceSource& s, int element, uint32_t* labelDev, uint64_t capacity, uint32_t* sizeDev, uint32_t* firstDev, uint32_t* boxDev, uint64_t* nComponentsOut,
+					uint64_t* largestOut, hipStream_t stream );
+// the voxels of the kept components (minVoxels >= 1, checked by the caller) as sorted codes and attributes for svoBuildFromSorted: *nOut = their number; codes /
+// attribs (allocated here) are left empty when *nOut == nVoxels (every component is kept) or 0 (none is: the caller refuses)
+int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels, uint32_t keepLargest, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission,
+						uint32_t* nComponents, uint32_t* nKeptComponents, hipStream_t stream );
 
 // octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
 // flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.

@@ -9,6 +9,10 @@
 //                   lies in.  Host-callable, so that a host program checks them against brute force (tests/hip/exterior_host.hip).
 //   coarse cells    coarseHead on the shifted codes and the per-cell finish of kernels_coarsen.hip: coarseKeep, coarseAttrib (the integer means of 64-bit sums) and
 //                   coarseMaxCount.  Host-callable as well (tests/hip/coarsen_host.hip).
+//   elements        the neighbour tables of the two structuring elements, the presence search on the sorted codes (kernels_morph.hip) and, for the connected
+//                   components (kernels_components.hip), the half of an element that sees every adjacent pair once and the search that returns the index.
+//   union-find      ufLoad / ufStore / ufFind / ufUnite / ufRoot: the lock-free union-find over node ids that kernels_fill.hip runs on the gaps and
+//                   kernels_components.hip on the voxels.  Device only.
 //   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
 //                   entries -> rank + 1 of every entry and the number of runs).  Each allocates its output itself, runs hipcub through withCubTemp and has waited
 //                   for the stream when it returns.
@@ -127,6 +131,16 @@ MVRT_HDI bool codePresentIn( const uint64_t* __restrict__ codes, uint64_t n, uin
 	const uint64_t i = lowerBound( codes, 0, n, code );
 	return i < n && codes[i] == code;
 }
+// the index of `code` among the n sorted unique codes, n where it is not one of them: codePresentIn that says where
+MVRT_HDI uint64_t codeIndexIn( const uint64_t* __restrict__ codes, uint64_t n, uint64_t code )
+{
+	const uint64_t i = lowerBound( codes, 0, n, code );
+	return i < n && codes[i] == code ? i : n;
+}
+// The half of an element (kernels_components.hip): neighbour j belongs to it when its offset (dz, dy, dx) is lexicographically below (0, 0, 0) -- the faces -x, -y,
+// -z (even j), the first 13 of the block (t < 13).  The other half holds the negated offsets, so of an adjacent pair {a, b} exactly one of a -> b and b -> a
+// lies in the half: a pass over the halves of all voxels sees every unordered pair once.  3 of 6, 13 of 26 (tests/hip/components_host.hip)
+MVRT_HDI bool componentHalf( int element, uint32_t j ) { return element == 0 ? ( j & 1u ) == 0u && j < 6u : j < 13u; }
 // bit j = neighbour j of voxel (x, y, z) lies inside the grid and is not among the n sorted codes: the cells a dilation step adds next to this voxel, and the
 // reason an erosion step removes it (any bit set; outside the grid counts as occupied)
 MVRT_HDI uint32_t morphEmptyMask( const uint64_t* __restrict__ codes, uint64_t n, uint32_t levels, int element, uint64_t code )
@@ -140,6 +154,53 @@ MVRT_HDI uint32_t morphEmptyMask( const uint64_t* __restrict__ codes, uint64_t n
 		if( morphNeighbour( x, y, z, levels, element, j, &c ) && !codePresentIn( codes, n, c ) ) mask |= 1u << j;
 	}
 	return mask;
+}
+
+// ---- union-find over node ids (kernels_fill.hip, kernels_components.hip) --------------------------------------------------------------------------------------
+// parent[v] <= v always, a root has parent[v] == v, only roots are ever hooked and only under smaller ids: the root of a set is its lowest id whatever the
+// schedule.  Nothing here waits on another thread: find() walks strictly downwards in id (a parent is never larger than its child), unite() retries only after a
+// failed compare-and-swap, and then from a strictly smaller id.  Device only.
+MVRT_DI uint32_t ufLoad( uint32_t* p ) { return __hip_atomic_load( p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ); }
+MVRT_DI void ufStore( uint32_t* p, uint32_t v ) { __hip_atomic_store( p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ); }
+// v strictly decreases.  Path halving on the way: a node that is no root (it never becomes one again) is pointed at its grandparent, an ancestor with a lower id
+MVRT_DI uint32_t ufFind( uint32_t* parent, uint32_t v )
+{
+	for( ;; )
+	{
+		const uint32_t p = ufLoad( parent + v );
+		if( p >= v ) return v; // ( p == v: a root )
+		const uint32_t gp = ufLoad( parent + p );
+		if( gp < p ) ufStore( parent + v, gp );
+		v = p;
+	}
+}
+MVRT_DI void ufUnite( uint32_t* parent, uint32_t a, uint32_t b )
+{
+	for( ;; )
+	{
+		a = ufFind( parent, a );
+		b = ufFind( parent, b );
+		if( a == b ) return;
+		if( a < b )
+		{
+			const uint32_t t = a;
+			a = b;
+			b = t;
+		}
+		// a > b: hook a under b if a is still a root.  Otherwise somebody hooked it meanwhile, under an id below a: the next find( a ) ends lower, so a + b
+		// strictly decreases from one turn to the next
+		if( atomicCAS( parent + a, a, b ) == a ) return;
+	}
+}
+// the same walk without the stores, for a flatten: there parent[v] is written once, by v's own thread, with the root
+MVRT_DI uint32_t ufRoot( uint32_t* parent, uint32_t v )
+{
+	for( ;; )
+	{
+		const uint32_t p = ufLoad( parent + v );
+		if( p >= v ) return v;
+		v = p;
+	}
 }
 
 // ---- host steps -------------------------------------------------------------------------------------------------------------------------------------------
