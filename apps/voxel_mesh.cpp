@@ -3,7 +3,7 @@
 //
 //   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]
 //              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]
-//              [--ao [samples] [--ao-radius voxels]]
+//              [--union | --intersect | --subtract | --xor other.obj [--offset x y z] [--attrib-b]] [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -26,6 +26,10 @@
 // with --element: cube = 26-connected, the default; faces = 6-connected); a line reports voxels and components before and after.  All three come after --dilate
 // / --erode / --close / --open and before --fill / --exterior, --components first: it counts what the other two select from.  --close 1 --keep-largest 1 --fill
 // repairs a shell, drops the debris around it and fills it.  With every other flag.
+// --union other.obj, --intersect other.obj, --subtract other.obj, --xor other.obj (one of them): the voxel set of a second model is combined with that of the
+// scene (mvrt_svo_combine) before --lod and everything behind it.  Both models are voxelised on one lattice, the grid placement below applied to their joint
+// bounding box; --offset x y z moves the second set by whole cells first (what leaves the grid is clipped), --attrib-b gives the cells both models share the
+// colour of the second.  A line reports the voxels before and after, the second model's voxels, the overlap and the clipped voxels.  With every other flag.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <algorithm>
 #include <cstdio>
@@ -48,6 +52,9 @@ int main( int argc, char** argv )
 	bool elementOk = true, components = false;
 	long long keepLargest = 0, minComponent = 1; // 0 = no --keep-largest
 	bool keep = false, keepOk = true;
+	const char *combineName = nullptr, *otherObj = nullptr; // "union", "intersect", "subtract" or "xor"
+	int combineOps = 0, combineOp = 0, offset[3] = { 0, 0, 0 };
+	bool attribB = false;
 	std::vector<const char*> pos;
 	for( int i = 1; i < argc; i++ )
 	{
@@ -71,6 +78,22 @@ int main( int argc, char** argv )
 			morphSteps = std::atoi( argv[++i] );
 			morphOps++;
 		}
+		else if( ( !std::strcmp( argv[i], "--union" ) || !std::strcmp( argv[i], "--intersect" ) || !std::strcmp( argv[i], "--subtract" ) || !std::strcmp( argv[i], "--xor" ) ) &&
+				 i + 1 < argc )
+		{
+			combineName = argv[i] + 2;
+			combineOp = !std::strcmp( combineName, "union" )	   ? mvrt::IntersectorOctreeGPU::COMBINE_UNION
+						: !std::strcmp( combineName, "intersect" ) ? mvrt::IntersectorOctreeGPU::COMBINE_INTERSECTION
+						: !std::strcmp( combineName, "subtract" )  ? mvrt::IntersectorOctreeGPU::COMBINE_DIFFERENCE
+																   : mvrt::IntersectorOctreeGPU::COMBINE_XOR;
+			otherObj = argv[++i];
+			combineOps++;
+		}
+		else if( !std::strcmp( argv[i], "--offset" ) && i + 3 < argc )
+		{
+			for( int k = 0; k < 3; k++ ) offset[k] = std::atoi( argv[++i] );
+		}
+		else if( !std::strcmp( argv[i], "--attrib-b" ) ) attribB = true;
 		else if( !std::strcmp( argv[i], "--components" ) ) components = true;
 		else if( !std::strcmp( argv[i], "--keep-largest" ) && i + 1 < argc )
 		{
@@ -97,7 +120,9 @@ int main( int argc, char** argv )
 	{
 		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]\n"
 					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]\n"
-					 "                  [--ao [samples] [--ao-radius voxels]]\n"
+					 "                  [--union | --intersect | --subtract | --xor other.obj [--offset x y z] [--attrib-b]] [--ao [samples] [--ao-radius voxels]]\n"
+					 "  --union O, --intersect O, --subtract O, --xor O  combine the voxel set with that of a second model O.obj first, both voxelised on one grid\n"
+					 "               over their joint bounding box; --offset x y z moves the second set by whole cells, --attrib-b colours shared cells from it\n"
 					 "  --lod K      coarsen the octree by K levels first (gridRes >> K); --lod-min-count C keeps a coarse cell only when it holds C fine voxels\n"
 					 "  --dilate K   grow the voxel set by K layers; --erode K peels K layers; --close K = dilate K, erode K (plugs holes); --open K = erode K,\n"
 					 "               dilate K (removes specks).  One of them, after --lod and before --fill / --exterior; --element faces|cube (default cube)\n"
@@ -112,6 +137,11 @@ int main( int argc, char** argv )
 					 "  --merge      merge coplanar faces of equal colour and emission into rectangles\n"
 					 "  --merge-any  merge whatever the attributes; a rectangle takes the colour of its anchor voxel\n" );
 		return pos.empty() ? 0 : 2;
+	}
+	if( combineOps > 1 )
+	{
+		std::fprintf( stderr, "voxel_mesh: only one of --union / --intersect / --subtract / --xor\n" );
+		return 2;
 	}
 	if( fill && exterior )
 	{
@@ -145,13 +175,33 @@ int main( int argc, char** argv )
 		std::fprintf( stderr, "voxel_mesh: cannot read triangles from %s\n", pos[0] );
 		return 1;
 	}
+	std::vector<mvrt_io::V3> otherVertices, otherColors, otherEmissions;
+	if( otherObj && !mvrt_io::readObj( otherObj, &otherVertices, &otherColors, &otherEmissions ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: cannot read triangles from %s\n", otherObj );
+		return 1;
+	}
 	mvrt_io::V3 origin;
 	float dps;
-	mvrt_io::boundingGrid( vertices, gridRes, &origin, &dps );
+	std::vector<mvrt_io::V3> joint = vertices; // one lattice for both models
+	joint.insert( joint.end(), otherVertices.begin(), otherVertices.end() );
+	mvrt_io::boundingGrid( joint, gridRes, &origin, &dps );
 
 	void* stream = nullptr;
 	mvrt::IntersectorOctreeGPU svo;
 	svo.build( vertices, vcolors, vemissions, nullptr, stream, origin, dps, gridRes, conservative ? MVRT_BUILD_CONSERVATIVE : 0 );
+	if( otherObj ) // before anything else is done with the octree
+	{
+		mvrt::IntersectorOctreeGPU other;
+		other.build( otherVertices, otherColors, otherEmissions, nullptr, stream, origin, dps, gridRes, conservative ? MVRT_BUILD_CONSERVATIVE : 0 );
+		const uint32_t before = svo.m_numberOfVoxels, flags = attribB ? mvrt::IntersectorOctreeGPU::COMBINE_ATTRIB_B : 0u;
+		uint64_t overlap = 0, clipped = 0, removed = 0;
+		svo.combineVoxels( other, combineOp, offset, flags, 0, nullptr, nullptr, nullptr, &overlap, &clipped, stream );
+		const uint64_t added = svo.combine( other, combineOp, offset, flags, &removed, nullptr, stream );
+		std::printf( "%s: voxels %u -> %u, other %u, offset %d %d %d, overlap %llu, clipped %llu, added %llu, removed %llu\n", combineName, before, svo.m_numberOfVoxels,
+					 other.m_numberOfVoxels, offset[0], offset[1], offset[2], (unsigned long long)overlap, (unsigned long long)clipped, (unsigned long long)added,
+					 (unsigned long long)removed );
+	}
 	if( lod > 0 ) // before anything else is done with the octree
 	{
 		const uint32_t before = svo.m_numberOfVoxels;

@@ -327,6 +327,47 @@ int mvrt_svo_components( const mvrt_svo* svo, int element, uint32_t* labelDev /*
  * removed, *nKeptOut = the components kept; either may be NULL. */
 int mvrt_svo_keep_components( mvrt_svo* svo, int element, uint64_t minVoxels, uint32_t keepLargest, uint64_t* nRemovedOut, uint64_t* nKeptOut, void* stream );
 
+/* Boolean operations between two voxel sets, the second moved by an integer cell offset (new; the reference has none).  Definitions:
+ *   - Sets: on the grid [0, R)^3 with R = gridRes of handle a, A = the voxel set of a and B = the voxel set of b, taken cell for cell: b's lower and dps are not
+ *     read, and b's gridRes need not equal a's.
+ *   - Offset o: three int32, each in [-2^21, 2^21]; NULL = zero.  B' = { v + o : v in B, v + o in [0, R)^3 }.  The sum is taken in an integer type that cannot
+ *     wrap: a translated coordinate of -1 or R does not exist, R = 2^21 included, and nothing is folded back into the 21 bits per axis of a code.
+ *     nClipped = |B| - |B'|.  Translation is injective, so B' has no duplicates.
+ *   - op: MVRT_COMBINE_UNION = A + B', MVRT_COMBINE_INTERSECTION = A n B', MVRT_COMBINE_DIFFERENCE = A \ B', MVRT_COMBINE_XOR = ( A \ B' ) + ( B' \ A ).
+ *   - Attributes: a result voxel that is in A keeps a's 8 bytes verbatim.  A voxel of B' alone takes b's colour RGB and emission RGB with both alpha bytes stored
+ *     as 255, the rule of MVRT_VOXEL_SET.  flags bit 0, MVRT_COMBINE_ATTRIB_B: the voxels of A n B' that survive (under UNION and INTERSECTION only) take b's
+ *     attribute by that rule instead; it has no effect under DIFFERENCE and XOR.  Any other flags bit is refused.
+ *   - Order: ascending Morton code in a's grid.  Everything is integers, a property of the two sets and the offset alone.
+ * mvrt_svo_combine_voxels, the listing, follows the rules of mvrt_svo_dilation_cells word for word: every octree this library built or edited is accepted for
+ * either handle, in every flavour, the tree flavour included (only the codes and the attributes are read); an upload is refused ("keeps no Morton codes": it
+ * works after one mvrt_svo_rebuild), an empty handle too ("no octree"), an unknown op or flags bit too, and an offset component outside the range; all refusals
+ * happen on the host before any GPU work.  Neither handle is modified.  The call blocks.  Arrays hold `capacity` entries: xyzDev 3 x uint32, attribsDev 8 bytes,
+ * sourceDev one byte = 1 (in A only), 2 (in B' only) or 3 (in both).  Any output may be NULL, all three arrays NULL is the sizing call (capacity is then
+ * ignored).  A capacity below the count is an error: the counts are still returned and NOTHING is written.  An empty result is a success with *nOut = 0.
+ * *nOverlapOut = |A n B'| whatever the op, *nClippedOut = nClipped.  A failed allocation of scratch returns an error, leaves both octrees whole, leaks nothing
+ * and has written nothing. */
+#define MVRT_COMBINE_UNION 0
+#define MVRT_COMBINE_INTERSECTION 1
+#define MVRT_COMBINE_DIFFERENCE 2
+#define MVRT_COMBINE_XOR 3
+#define MVRT_COMBINE_ATTRIB_B 1u
+int mvrt_svo_combine_voxels( const mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t capacity, uint32_t* xyzDev /* 3 per voxel */,
+							 uint32_t* attribsDev /* 8 bytes per voxel */, uint8_t* sourceDev /* 1 = a only, 2 = b only, 3 = both */, uint64_t* nOut,
+							 uint64_t* nOverlapOut /* |A n B'| */, uint64_t* nClippedOut, void* stream );
+/* In place: a becomes exactly what mvrt_svo_edit_voxels leaves when given B' \ A with b's attributes as MVRT_VOXEL_SET (UNION and XOR), the overlap with b's
+ * attributes as MVRT_VOXEL_SET (under MVRT_COMBINE_ATTRIB_B) and the voxels the operation drops as MVRT_VOXEL_REMOVE -- nodes and numbering, the recomputed
+ * hasEmission, the flavour a fresh build picks, the derived tables, the kept build flags, origin, dps and emission scale, totalDumpedVoxels 0.  The lists never
+ * travel to the host and the levels are built once.  Failures and ordering are the edit's: the new arrays are built next to the old octree, a failure before
+ * they are adopted leaves a unchanged, one after that leaves it empty (see mvrt_svo_destroy above); b stays whole throughout.  Through mvrt_pt_intersector( pt )
+ * as a the steps issued before finish first and the frame buffer is not cleared; every mvrt_device_octree view of a is invalidated.  a == b is allowed (b's list is
+ * read before anything is replaced): with a non-zero offset the union is a directional smear.  A call that adds nothing, removes nothing and recolours nothing
+ * succeeds, reports 0 / 0 and leaves the handle untouched, its views valid.  A call that only recolours under the flag behaves like the attribute-only edit: the
+ * nodes are kept, the attributes are written in place and hasEmission is recomputed.  Refused with a unchanged: everything the listing refuses, a result of
+ * 2^32 - 1 voxels or more (the message names the count) and an empty result ("would leave no voxel").  *nAddedOut = |B' \ A| where the op takes it, *nRemovedOut
+ * = the voxels of A the op drops, *nClippedOut = nClipped; each may be NULL. */
+int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t* nAddedOut, uint64_t* nRemovedOut, uint64_t* nClippedOut,
+					  void* stream );
+
 /* Exterior-only surface extraction without touching the octree, and the three extraction calls on face masks the caller supplies (new; the reference has
  * none).  Definitions:
  *   - Exterior mask of a voxel: one byte, directions d = 0..5 as in mvrt_svo_surface_masks (0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X).  Bit d is set when the

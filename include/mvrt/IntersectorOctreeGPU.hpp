@@ -319,6 +319,51 @@ struct IntersectorOctreeGPU
 		return n;
 	}
 
+	// boolean operations with a second voxel set moved by an integer cell offset (mvrt_svo_combine_voxels / mvrt_svo_combine; semantics in mvrt.h): op = COMBINE_*,
+	// offset = 3 ints or nullptr (zero), flags = 0 or COMBINE_ATTRIB_B.  Device-pointer form of the listing: any output may be nullptr, all nullptr = the sizing
+	// call.  Returns the number of voxels; *overlap and *clipped (either may be nullptr) = the voxels in both sets and the voxels of b moved out of the grid.
+	enum
+	{
+		COMBINE_UNION = MVRT_COMBINE_UNION,
+		COMBINE_INTERSECTION = MVRT_COMBINE_INTERSECTION,
+		COMBINE_DIFFERENCE = MVRT_COMBINE_DIFFERENCE,
+		COMBINE_XOR = MVRT_COMBINE_XOR,
+		COMBINE_ATTRIB_B = MVRT_COMBINE_ATTRIB_B
+	};
+	uint64_t combineVoxels( const IntersectorOctreeGPU& b, int op, const int32_t* offset, uint32_t flags, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev,
+							uint8_t* sourceDev, uint64_t* overlap, uint64_t* clipped, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_combine_voxels( m_handle, b.m_handle, op, offset, flags, capacity, xyzDev, attribsDev, sourceDev, &n, overlap, clipped, stream ),
+			   "IntersectorOctreeGPU::combineVoxels" );
+		return n;
+	}
+	// host-vector form: xyz = 3 entries per voxel in ascending Morton order, attribs = 2, source = 1 byte (1 = this set only, 2 = b only, 3 = both)
+	void combineVoxels( const IntersectorOctreeGPU& b, int op, const int32_t* offset, uint32_t flags, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs,
+						std::vector<uint8_t>& source, uint64_t* overlap, uint64_t* clipped, void* stream ) const
+	{
+		const uint64_t n = combineVoxels( b, op, offset, flags, 0, nullptr, nullptr, nullptr, overlap, clipped, stream );
+		xyz.resize( n * 3 );
+		attribs.resize( n * 2 );
+		source.resize( n );
+		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), s( nullptr, n, stream );
+		if( n ) combineVoxels( b, op, offset, flags, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint8_t*)s.p, nullptr, nullptr, stream );
+		fetch( xyz, x, stream );
+		fetch( attribs, a, stream );
+		fetch( source, s, stream );
+	}
+	// in place: this octree becomes the result, exactly as the edit with the added voxels as MVRT_VOXEL_SET and the dropped ones as MVRT_VOXEL_REMOVE leaves it; b
+	// may be this object.  Returns the voxels added; *removed and *clipped may be nullptr.  A call that changes nothing does not touch the octree; otherwise
+	// deviceView() snapshots are invalidated.
+	uint64_t combine( const IntersectorOctreeGPU& b, int op, const int32_t* offset = nullptr, uint32_t flags = 0, uint64_t* removed = nullptr, uint64_t* clipped = nullptr,
+					  void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_combine( m_handle, b.m_handle, op, offset, flags, &n, removed, clipped, stream ), "IntersectorOctreeGPU::combine" );
+		refresh();
+		return n;
+	}
+
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const

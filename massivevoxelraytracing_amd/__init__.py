@@ -54,6 +54,8 @@ SURFACE_MERGE_ANY_ATTRIBUTE = 1  # mvrt_svo_surface_merged flags (include/mvrt.h
 SURFACE_MERGE_WELD = 2
 MORPH_FACES = 0  # structuring elements of dilate / erode / close / open (include/mvrt.h)
 MORPH_CUBE = 1
+COMBINE_UNION, COMBINE_INTERSECTION, COMBINE_DIFFERENCE, COMBINE_XOR = 0, 1, 2, 3  # mvrt_svo_combine_voxels / mvrt_svo_combine ops (include/mvrt.h)
+COMBINE_ATTRIB_B = 1  # flags: the surviving overlap takes b's attributes
 
 
 # every symbol include/mvrt.h declares: name -> (restype, argtypes)
@@ -99,6 +101,8 @@ SIGNATURES = {
     "mvrt_svo_erosion_voxels": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp]),
     "mvrt_svo_components": (_i32, [_vp, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_keep_components": (_i32, [_vp, _i32, _u64, C.c_uint32, _vp, _vp, _vp]),
+    "mvrt_svo_combine_voxels": (_i32, [_vp, _vp, _i32, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_combine": (_i32, [_vp, _vp, _i32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "mvrt_svo_dilate": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_erode": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_close": (_i32, [_vp, _i32, _i32, _vp, _vp]),
@@ -544,6 +548,37 @@ class IntersectorOctreeGPU:
         removed, kept = C.c_uint64(0), C.c_uint64(0)
         _check(lib().mvrt_svo_keep_components(self._h, int(element), int(min_voxels), int(keep_largest), C.byref(removed), C.byref(kept), stream))
         return removed.value, kept.value
+
+    @staticmethod
+    def _offset(offset):
+        return None if offset is None else np.ascontiguousarray(offset, np.int32).reshape(3)
+
+    def combine_voxels_device(self, b, op, offset=None, flags=0, capacity=0, xyz=None, attribs=None, source=None, stream=None):
+        """mvrt_svo_combine_voxels into caller device arrays of `capacity` voxels (any may be None; all None = the sizing call); returns (n, overlap, clipped).
+        On MvrtError nothing was written."""
+        n, ov, cl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_combine_voxels(self._h, b._h, int(op), _hp(self._offset(offset)), int(flags), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(source),
+                                             C.byref(n), C.byref(ov), C.byref(cl), stream))
+        return n.value, ov.value, cl.value
+
+    def combine_voxels(self, b, op, offset=None, flags=0, stream=None):
+        """this set `op` (COMBINE_UNION / _INTERSECTION / _DIFFERENCE / _XOR) the set of `b` moved by `offset` (3 ints, None = 0) and clipped to this grid, in
+        ascending Morton order: {xyz (n, 3) uint32, attribs (n, 8) uint8, source (n,) uint8 = 1 this only, 2 b only, 3 both, overlap = the voxels in both,
+        clipped = the voxels of b the offset moves out of the grid}.  A voxel of this set keeps its bytes (COMBINE_ATTRIB_B: the overlap takes b's), one of b
+        alone takes b's colour and emission with alpha 255.  Neither octree is modified."""
+        n, ov, cl = self.combine_voxels_device(b, op, offset, flags, stream=stream)
+        xyz, at, src = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint8)
+        if n:
+            self.combine_voxels_device(b, op, offset, flags, n, xyz, at, src, stream)
+        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "source": src.to_host(), "overlap": ov, "clipped": cl}
+
+    def combine(self, b, op, offset=None, flags=0, stream=None):
+        """mvrt_svo_combine: this octree becomes combine_voxels(b, op, offset, flags), exactly as edit_voxels with the added voxels (and, under COMBINE_ATTRIB_B,
+        the overlap) as VOXEL_SET and the dropped ones as VOXEL_REMOVE would leave it; b may be this object.  Returns (added, removed, clipped); a call that
+        changes nothing leaves the handle untouched.  Refused when no voxel would be left.  Invalidates device_view() snapshots otherwise."""
+        ad, rm, cl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_combine(self._h, b._h, int(op), _hp(self._offset(offset)), int(flags), C.byref(ad), C.byref(rm), C.byref(cl), stream))
+        return ad.value, rm.value, cl.value
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""

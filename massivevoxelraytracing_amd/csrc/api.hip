@@ -766,6 +766,72 @@ MVRT_EXPORT int mvrt_svo_keep_components( mvrt_svo* svo, int element, uint64_t m
 	return 0;
 }
 
+// Two voxel sets (kernels_combine.hip).  Every refusal the arguments and the handles decide is made here, on the host.  The listing reads the sorted codes and the
+// attributes of both handles; the in-place call emits the result next to the old octree and builds the levels once, as the opening does.
+static_assert( MVRT_COMBINE_UNION == MVRT_COMBINE_OP_UNION && MVRT_COMBINE_INTERSECTION == MVRT_COMBINE_OP_INTERSECTION && MVRT_COMBINE_DIFFERENCE == MVRT_COMBINE_OP_DIFFERENCE &&
+				   MVRT_COMBINE_XOR == MVRT_COMBINE_OP_XOR && (int)MVRT_COMBINE_ATTRIB_B == MVRT_COMBINE_FLAG_ATTRIB_B,
+			   "mvrt.h and launch.h number the operators alike" );
+static int combineSources( const mvrt_svo* a, const mvrt_svo* b, const char* who, int op, const int32_t offset[3], uint32_t flags, SurfaceSource* sa, SurfaceSource* sb, int32_t o[3] )
+{
+	if( surfaceSource( a, who, sa ) ) return 1;
+	REQUIRE( b, "%s: null handle b", who );
+	REQUIRE( !b->empty(), "%s: b holds no octree (build first)", who );
+	REQUIRE( b->oct.morton.p, "%s: b is an uploaded octree, which keeps no Morton codes", who );
+	if( surfaceSource( b, who, sb ) ) return 1;
+	REQUIRE( op >= MVRT_COMBINE_UNION && op <= MVRT_COMBINE_XOR, "%s: unknown op %d (MVRT_COMBINE_UNION = 0, _INTERSECTION = 1, _DIFFERENCE = 2, _XOR = 3)", who, op );
+	REQUIRE( ( flags & ~(uint32_t)MVRT_COMBINE_ATTRIB_B ) == 0, "%s: unknown flags 0x%x (MVRT_COMBINE_ATTRIB_B only)", who, flags );
+	for( int k = 0; k < 3; k++ )
+	{
+		o[k] = offset ? offset[k] : 0;
+		REQUIRE( o[k] >= -( 1 << 21 ) && o[k] <= ( 1 << 21 ), "%s: offset[%d] = %d is outside [-2^21, 2^21]", who, k, o[k] );
+	}
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_combine_voxels( const mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t capacity, uint32_t* xyzDev,
+										 uint32_t* attribsDev, uint8_t* sourceDev, uint64_t* nOut, uint64_t* nOverlapOut, uint64_t* nClippedOut, void* stream )
+{
+	SurfaceSource sa, sb;
+	int32_t o[3];
+	if( combineSources( a, b, "mvrt_svo_combine_voxels", op, offset, flags, &sa, &sb, o ) ) return 1;
+	return combineVoxels( sa, sb, op, o, flags, capacity, xyzDev, attribsDev, sourceDev, nOut, nOverlapOut, nClippedOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t* nAddedOut, uint64_t* nRemovedOut,
+								  uint64_t* nClippedOut, void* stream )
+{
+	const char* who = "mvrt_svo_combine";
+	if( nAddedOut ) *nAddedOut = 0;
+	if( nRemovedOut ) *nRemovedOut = 0;
+	if( nClippedOut ) *nClippedOut = 0;
+	SurfaceSource sa, sb;
+	int32_t o[3];
+	if( combineSources( a, b, who, op, offset, flags, &sa, &sb, o ) ) return 1;
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf morton, attrs;
+	CombineCounts c;
+	if( combineList( who, sa, sb, op, o, flags, morton, attrs, &c, st ) ) return 1;
+	if( nClippedOut ) *nClippedOut = c.nClipped;
+	if( c.nAdded == 0 && c.nRemoved == 0 && !c.recolours ) return 0; // nothing changes: the handle is not touched
+	if( ownerDrain( a ) ) return 1; // steps already issued render the old scene; a recolouring writes in place
+	if( c.nAdded == 0 && c.nRemoved == 0 ) // the attribute-only edit: the node structure stays
+	{
+		MVRT_HIP( hipMemcpyAsync( a->oct.attrs.p, attrs.p, c.n * 8, hipMemcpyDeviceToDevice, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+		a->oct.totalDumped = 0;
+		a->oct.hasEmission = c.hasEmission;
+		return 0;
+	}
+	const mvrt_svo_info& info = a->oct.info;
+	SvoBuildResult r;
+	if( svoBuildFromSorted( morton, attrs, (uint32_t)c.n, (int)info.gridRes, a->oct.buildFlags, st, &r ) ) return 1;
+	r.hasEmission = c.hasEmission;
+	r.totalDumped = 0; // (as an edit leaves it)
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	if( adoptBuild( a, r, origin, info.dps, (int)info.gridRes, a->oct.buildFlags ) ) return 1; // (arguments are read before the old octree goes; b == a was read above)
+	if( nAddedOut ) *nAddedOut = c.nAdded;
+	if( nRemovedOut ) *nRemovedOut = c.nRemoved;
+	return 0;
+}
+
 MVRT_EXPORT int mvrt_svo_get_info( const mvrt_svo* svo, mvrt_svo_info* info )
 {
 	REQUIRE( svo && info, "null argument" );

@@ -241,7 +241,31 @@ int componentsList( const SurfaceSource& s, int element, uint32_t* labelDev, uin
 int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels, uint32_t keepLargest, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission,
 						uint32_t* nComponents, uint32_t* nKeptComponents, hipStream_t stream );
 
-// octree walk (kernels_walk.hip; mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
+// two voxel sets (kernels_combine.hip; mvrt_svo_combine_voxels / mvrt_svo_combine): morton, attrs, nVoxels and levels of a, morton, attrs and nVoxels of b (its
+// levels only decide whether its codes can stand as they are), op and flags as in mvrt.h and o[3] in [-2^21, 2^21], all checked by the caller.  The calls block,
+// keep their scratch in DevBufs and write NOTHING to the caller's arrays unless they succeed.
+enum
+{
+	MVRT_COMBINE_OP_UNION = 0,
+	MVRT_COMBINE_OP_INTERSECTION = 1,
+	MVRT_COMBINE_OP_DIFFERENCE = 2,
+	MVRT_COMBINE_OP_XOR = 3,
+	MVRT_COMBINE_FLAG_ATTRIB_B = 1
+};
+int combineVoxels( const SurfaceSource& a, const SurfaceSource& b, int op, const int32_t o[3], uint32_t flags, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev,
+				   uint8_t* sourceDev, uint64_t* nOut, uint64_t* nOverlapOut, uint64_t* nClippedOut, hipStream_t stream );
+struct CombineCounts
+{
+	uint64_t n = 0, nOverlap = 0, nClipped = 0; // the result, A n B', the entries of b the offset moves out of the grid
+	uint32_t nAdded = 0, nRemoved = 0;			// B' \ A where the operator takes it, the voxels of A it drops
+	uint32_t recolours = 0, hasEmission = 0;	// the overlap survives and takes b's attributes; the emission flag over the result
+};
+// the result as sorted codes and attributes for svoBuildFromSorted (allocated here).  nAdded == nRemoved == 0: with recolours only `attribs` is filled (the codes
+// are a's), without it nothing is (nothing changes).  A result of no voxel or of 2^32 - 1 or more is refused; `who` names the call
+int combineList( const char* who, const SurfaceSource& a, const SurfaceSource& b, int op, const int32_t o[3], uint32_t flags, DevBuf& codes, DevBuf& attribs, CombineCounts* counts,
+				 hipStream_t stream );
+
+// octree walk (kernels_walk.hip;mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
 // flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.
 struct WalkSource
 {

@@ -11,6 +11,8 @@
 //                   coarseMaxCount.  Host-callable as well (tests/hip/coarsen_host.hip).
 //   elements        the neighbour tables of the two structuring elements, the presence search on the sorted codes (kernels_morph.hip) and, for the connected
 //                   components (kernels_components.hip), the half of an element that sees every adjacent pair once and the search that returns the index.
+//   two sets        combineTranslate (a code moved by an integer offset and clipped to a grid) of kernels_combine.hip, and combineWindow / codeIndexInRange: the
+//                   partner search of a group of ascending codes, bounded once per group.  Host-callable (tests/hip/combine_host.hip).
 //   union-find      ufLoad / ufStore / ufFind / ufUnite / ufRoot: the lock-free union-find over node ids that kernels_fill.hip runs on the gaps and
 //                   kernels_components.hip on the voxels.  Device only.
 //   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
@@ -154,6 +156,35 @@ MVRT_HDI uint32_t morphEmptyMask( const uint64_t* __restrict__ codes, uint64_t n
 		if( morphNeighbour( x, y, z, levels, element, j, &c ) && !codePresentIn( codes, n, c ) ) mask |= 1u << j;
 	}
 	return mask;
+}
+
+// ---- two sets (kernels_combine.hip) -------------------------------------------------------------------------------------------------------------------------
+// The cell `code` names, moved by the offset o (each component in [-2^21, 2^21]) inside a grid of R = 2^levels <= 2^21 cells per axis: false when it leaves the
+// grid, else true and *codeOut = its code there.  The sums are taken in 64 bits, where 2^21 - 1 + 2^21 and 0 - 2^21 are ordinary numbers: a coordinate of -1 or R is
+// outside, nothing is folded back into the 21 bits per axis of a code.  The source grid may be larger or smaller than R.  Host-callable (tests/hip/combine_host.hip)
+MVRT_HDI bool combineTranslate( uint64_t code, const int32_t o[3], uint32_t levels, uint64_t* codeOut )
+{
+	uint32_t x, y, z;
+	mortonDecode( code, x, y, z );
+	const int64_t R = (int64_t)1 << levels, nx = (int64_t)x + o[0], ny = (int64_t)y + o[1], nz = (int64_t)z + o[2];
+	if( nx < 0 || nx >= R || ny < 0 || ny >= R || nz < 0 || nz >= R ) return false;
+	*codeOut = mortonEncode( (uint32_t)nx, (uint32_t)ny, (uint32_t)nz );
+	return true;
+}
+// (kCombineClassify searches the whole list per lane: with one thread finding the window for its workgroup the kernel was measured a third slower, DESIGN.md 5.20.  The
+// two helpers below are that bounded search, host-callable and checked against codeIndexIn by tests/hip/combine_host.hip.)
+// The window of the n sorted unique codes that a group of ascending codes first <= ... <= last needs: every entry below *lo is below `first`, every entry from *hi
+// on is not below `last`, so for each code c of the group lowerBound( codes, *lo, *hi, c ) == lowerBound( codes, 0, n, c ).  0 <= *lo <= *hi <= n; n == 0 gives 0, 0
+MVRT_HDI void combineWindow( const uint64_t* __restrict__ codes, uint64_t n, uint64_t first, uint64_t last, uint64_t* lo, uint64_t* hi )
+{
+	*lo = lowerBound( codes, 0, n, first );
+	*hi = lowerBound( codes, *lo, n, last );
+}
+// codeIndexIn for a code of the group, searched in its window alone: the index of `code` among the n codes, n where it is not one of them
+MVRT_HDI uint64_t codeIndexInRange( const uint64_t* __restrict__ codes, uint64_t n, uint64_t lo, uint64_t hi, uint64_t code )
+{
+	const uint64_t i = lowerBound( codes, lo, hi, code );
+	return i < n && codes[i] == code ? i : n;
 }
 
 // ---- union-find over node ids (kernels_fill.hip, kernels_components.hip) --------------------------------------------------------------------------------------
