@@ -3,6 +3,7 @@
 //
 //   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]
 //              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]
+//              [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]
 //              [--union | --intersect | --subtract | --xor other.obj [--offset x y z] [--attrib-b]] [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
@@ -21,6 +22,10 @@
 // --dilate K, --erode K, --close K, --open K (one of them): K steps of the operator on the voxel set (mvrt_svo_dilate / _erode / _close / _open) with --element
 // faces (the 6 face neighbours) or cube (the 26 of the 3x3x3 block, the default), after --lod and before --fill / --exterior; a line reports the voxels before
 // and after.  --close 1 --fill repairs a shell with one-voxel holes, which the fill alone finds empty of enclosed cells.  With every other flag.
+// --round-dilate RHO, --round-erode RHO, --round-close RHO, --round-open RHO (one of them, and none of the four above): the operator with the ball of squared
+// radius RHO in [1, 1024] as one operation (mvrt_svo_dilate_ball / _erode_ball / _close_ball / _open_ball): a round offset, where K steps give an octahedron or
+// a cube.  At the same place, after --lod and before --keep-largest / --fill / --exterior; a line reports the voxels before and after.  --round-close 16 --fill
+// bridges gaps of up to 8 cells in every direction alike.  With every other flag.
 // --components: a line reports the number of connected components under --element and the five largest sizes (mvrt_svo_components); nothing changes.
 // --keep-largest K, --min-component N (either or both): only the components of at least N voxels and, of those, the K largest stay (mvrt_svo_keep_components
 // with --element: cube = 26-connected, the default; faces = 6-connected); a line reports voxels and components before and after.  All three come after --dilate
@@ -49,6 +54,9 @@ int main( int argc, char** argv )
 	unsigned long long lodMinCount = 1;
 	const char* morphOp = nullptr; // "dilate", "erode", "close" or "open"
 	int morphSteps = 0, morphOps = 0, element = MVRT_MORPH_CUBE;
+	const char* roundOp = nullptr; // "dilate", "erode", "close" or "open"
+	long long roundRadius2 = 0;
+	int roundOps = 0;
 	bool elementOk = true, components = false;
 	long long keepLargest = 0, minComponent = 1; // 0 = no --keep-largest
 	bool keep = false, keepOk = true;
@@ -77,6 +85,14 @@ int main( int argc, char** argv )
 			morphOp = argv[i] + 2;
 			morphSteps = std::atoi( argv[++i] );
 			morphOps++;
+		}
+		else if( ( !std::strcmp( argv[i], "--round-dilate" ) || !std::strcmp( argv[i], "--round-erode" ) || !std::strcmp( argv[i], "--round-close" ) ||
+				   !std::strcmp( argv[i], "--round-open" ) ) &&
+				 i + 1 < argc )
+		{
+			roundOp = argv[i] + 8;
+			roundRadius2 = std::atoll( argv[++i] );
+			roundOps++;
 		}
 		else if( ( !std::strcmp( argv[i], "--union" ) || !std::strcmp( argv[i], "--intersect" ) || !std::strcmp( argv[i], "--subtract" ) || !std::strcmp( argv[i], "--xor" ) ) &&
 				 i + 1 < argc )
@@ -120,12 +136,15 @@ int main( int argc, char** argv )
 	{
 		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]\n"
 					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]\n"
+					 "                  [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]\n"
 					 "                  [--union | --intersect | --subtract | --xor other.obj [--offset x y z] [--attrib-b]] [--ao [samples] [--ao-radius voxels]]\n"
 					 "  --union O, --intersect O, --subtract O, --xor O  combine the voxel set with that of a second model O.obj first, both voxelised on one grid\n"
 					 "               over their joint bounding box; --offset x y z moves the second set by whole cells, --attrib-b colours shared cells from it\n"
 					 "  --lod K      coarsen the octree by K levels first (gridRes >> K); --lod-min-count C keeps a coarse cell only when it holds C fine voxels\n"
 					 "  --dilate K   grow the voxel set by K layers; --erode K peels K layers; --close K = dilate K, erode K (plugs holes); --open K = erode K,\n"
 					 "               dilate K (removes specks).  One of them, after --lod and before --fill / --exterior; --element faces|cube (default cube)\n"
+					 "  --round-dilate RHO, --round-erode RHO, --round-close RHO, --round-open RHO  the same operators with the ball of squared radius RHO in\n"
+					 "               [1, 1024] as one operation: a round offset.  One of them, at the same place, and none of the four above\n"
 					 "  --components report the number of connected components (26-connected with --element cube, 6-connected with faces) and the five largest\n"
 					 "  --keep-largest K, --min-component N  keep only the components of at least N voxels and, of those, the K largest; after the\n"
 					 "               operators above and before --fill / --exterior\n"
@@ -151,6 +170,12 @@ int main( int argc, char** argv )
 	if( morphOps > 1 || !elementOk || ( morphOps == 1 && ( morphSteps < 1 || morphSteps > 64 ) ) )
 	{
 		std::fprintf( stderr, "voxel_mesh: one of --dilate / --erode / --close / --open with K in [1, 64], and --element faces or cube\n" );
+		return 2;
+	}
+	if( roundOps > 1 || ( roundOps == 1 && ( morphOps != 0 || roundRadius2 < 1 || roundRadius2 > 1024 ) ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: one of --round-dilate / --round-erode / --round-close / --round-open with RHO in [1, 1024], and not together with --dilate / "
+							  "--erode / --close / --open\n" );
 		return 2;
 	}
 	if( !keepOk )
@@ -219,6 +244,17 @@ int main( int argc, char** argv )
 		else changed = svo.open( element, morphSteps, stream );
 		std::printf( "%s: voxels %u -> %u, element %s, steps %d, %s %llu\n", morphOp, before, svo.m_numberOfVoxels, element == MVRT_MORPH_FACES ? "faces" : "cube", morphSteps,
 					 !std::strcmp( morphOp, "dilate" ) || !std::strcmp( morphOp, "close" ) ? "added" : "removed", (unsigned long long)changed );
+	}
+	if( roundOp ) // at the same place
+	{
+		const uint32_t before = svo.m_numberOfVoxels, rho = (uint32_t)roundRadius2;
+		uint64_t changed = 0;
+		if( !std::strcmp( roundOp, "dilate" ) ) changed = svo.dilateBall( rho, stream );
+		else if( !std::strcmp( roundOp, "erode" ) ) changed = svo.erodeBall( rho, stream );
+		else if( !std::strcmp( roundOp, "close" ) ) changed = svo.closeBall( rho, stream );
+		else changed = svo.openBall( rho, stream );
+		std::printf( "round-%s: voxels %u -> %u, radius2 %u, %s %llu\n", roundOp, before, svo.m_numberOfVoxels, rho,
+					 !std::strcmp( roundOp, "dilate" ) || !std::strcmp( roundOp, "close" ) ? "added" : "removed", (unsigned long long)changed );
 	}
 	if( components ) // what --keep-largest / --min-component select from
 	{

@@ -297,6 +297,47 @@ int mvrt_svo_erode( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut
 int mvrt_svo_close( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream );
 int mvrt_svo_open( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream );
 
+/* Round offsets: the exact distance band and dilation, erosion, closing and opening with a ball (new; the reference has none).  Definitions, on the grid [0, R)^3
+ * with R = gridRes and A = the voxel set of the handle; radius2 = rho is a uint32 in [1, 1024], so the reach k = floor( sqrt( rho ) ) is at most 32:
+ *   - Ball: B(rho) = { o in Z^3 : ox^2 + oy^2 + oz^2 <= rho }.  rho = 1 is the FACES element plus the centre, rho = 3 the CUBE element plus the centre, rho = 2 the
+ *     18-neighbourhood.
+ *   - Outer distance: for an in-grid cell c not in A, d2(c) = min over v in A of |c - v|^2, the exact integer squared distance; near(c) = the lowest vIndex among
+ *     the voxels that attain the minimum.
+ *   - Ball dilation: D_rho(A) = A + { c in the grid, c not in A, d2(c) <= rho }.  It is clipped to the grid: nothing wraps at coordinate 0, at R - 1, or in the 21
+ *     bits per axis of a code at R = 2^21.  A new cell takes colour RGB and emission RGB of voxel near(c), with both alpha bytes stored as 255 (the rule of
+ *     MVRT_VOXEL_SET).  This is not a mean: a round offset keeps colours crisp, and the tie rule makes it unique.  Voxels of A keep all 8 bytes verbatim.
+ *   - Depth: for v in A, e2(v) = min over IN-GRID cells c not in A of |v - c|^2.  Cells outside the grid count as occupied, the rule of mvrt_svo_erode, for the
+ *     reason given there.  If the grid is full, e2 is infinite.
+ *   - Ball erosion: E_rho(A) = { v in A : e2(v) > rho }.  With this rule E_rho(A) = grid \ D_rho(grid \ A), the closing C_rho = E_rho(D_rho(A)) contains A, the
+ *     opening O_rho = D_rho(E_rho(A)) lies in A, and both are idempotent, for every A and rho.
+ *   - Closing: cells of A keep their bytes, an added cell carries the attribute the dilation gave it.
+ *   - Opening: a pure removal: every surviving voxel keeps its ORIGINAL 8 bytes.
+ *   - A ball of rho is one operation, not k repeated steps.  As sets, D_1 / E_1 equal one FACES step of mvrt_svo_dilate / _erode and D_3 / E_3 one CUBE step; the
+ *     attributes of new cells differ: the nearest voxel here, the mean there.
+ *   - Order: ascending Morton code.  Everything is integers, a property of the voxel set alone and independent of any schedule.
+ * The listings follow the rules of mvrt_svo_dilation_cells / mvrt_svo_erosion_voxels word for word: every octree this library built or edited is accepted, in every
+ * flavour; an upload is refused ("keeps no Morton codes"), an empty handle too ("no octree"), and a radius2 outside [1, 1024] (the message names the range); all
+ * refusals happen on the host before any GPU work.  The handle is never modified.  The calls block.  Any output may be NULL, all arrays NULL is the sizing call
+ * (capacity is then ignored).  A capacity below the count is an error: the count is still returned and NOTHING is written.  Zero entries is a success.  A failed
+ * allocation of scratch returns an error, leaks nothing and has written nothing.  A pass whose records number 2^32 - 1 or more is refused; the message names the
+ * pass and the count.
+ * mvrt_svo_distance_cells: the cells of D_rho(A) \ A in ascending Morton code: xyzDev 3 x uint32, dist2Dev = d2, nearestDev = near as a vIndex, attribsDev the 8
+ * bytes the cell would get.  mvrt_svo_depth_voxels: the voxels with e2 <= rho, that is A \ E_rho(A), as ascending vIndex with e2 in depth2Dev; with rho = 1024 it
+ * doubles as a wall-thickness probe. */
+int mvrt_svo_distance_cells( const mvrt_svo* svo, uint32_t radius2, uint64_t capacity, uint32_t* xyzDev /* 3 per cell */, uint32_t* dist2Dev,
+							 uint32_t* nearestDev /* vIndex */, uint32_t* attribsDev /* 8 bytes per cell */, uint64_t* nOut, void* stream );
+int mvrt_svo_depth_voxels( const mvrt_svo* svo, uint32_t radius2, uint64_t capacity, uint32_t* vIndexDev, uint32_t* depth2Dev, uint64_t* nOut, void* stream );
+/* In place, following mvrt_svo_dilate .. _open word for word: the handle's octree becomes exactly what mvrt_svo_edit_voxels leaves when given the net added cells
+ * with their attributes (MVRT_VOXEL_SET) and the net removed voxels (MVRT_VOXEL_REMOVE); the halves run on sorted lists and the levels are built ONCE per call.
+ * Failures and ordering are the edit's.  A call that changes nothing succeeds with 0 and leaves the handle untouched, its views valid.  Refused with the handle
+ * unchanged: an upload, an empty handle, a radius2 outside [1, 1024], a voxel count that would reach 2^32 - 1, and an erosion or opening that would leave no
+ * voxel.  The count pointer may be NULL: the cells added by a dilation, the voxels removed by an erosion, the NET cells a closing adds and the NET voxels an
+ * opening removes. */
+int mvrt_svo_dilate_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nAddedOut, void* stream );
+int mvrt_svo_erode_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nRemovedOut, void* stream );
+int mvrt_svo_close_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nAddedOut, void* stream );
+int mvrt_svo_open_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nRemovedOut, void* stream );
+
 /* Connected components of the voxel set (new; the reference has none).  Definitions, on the grid [0, R)^3 with R = gridRes and A = the voxel set of the handle:
  *   - Connectivity e: MVRT_MORPH_FACES (6) or MVRT_MORPH_CUBE (26), the structuring elements above.
  *   - Two voxels are adjacent when one is an e-neighbour of the other INSIDE the grid: nothing wraps at coordinate 0, at R - 1, or in the 21 bits per axis of a code
@@ -839,6 +880,12 @@ int mvrt_pt_set_test_free_bytes( mvrt_pt* pt, uint64_t bytes );
  * allocation_state: process-wide tallies -- buffers and bytes held right now, allocations attempted so far; any pointer may be NULL. */
 int mvrt_test_fail_allocation( int64_t nth );
 int mvrt_test_allocation_state( uint64_t* liveBuffers, uint64_t* liveBytes, uint64_t* totalAllocs );
+/* Measuring: *peakOut (may be NULL) = the most bytes the library held at one time, process-wide, since the last reset; reset != 0 starts a new period at what it
+ * holds now.  Around one blocking call, peak minus the bytes held before it is the call's scratch plus what it leaves. */
+int mvrt_test_peak_bytes( uint64_t* peakOut, int reset );
+/* Measuring (tools/ball_bench.py): what the last distance band this thread ran did: out[0..2] = the records of the passes along x, y and z, out[3] = its seeds,
+ * out[4] = its cells.  A closing or an opening runs two bands; this is the second. */
+int mvrt_test_ball_stats( uint64_t out[5] );
 int mvrt_pt_set_profiling( mvrt_pt* pt, int enabled ); /* HIP events on `stream` around each kernel of step(); read by get_stats */
 int mvrt_pt_reset_stats( mvrt_pt* pt );
 int mvrt_pt_get_stats( mvrt_pt* pt, void* stream, mvrt_pt_stats* out ); /* synchronises the stream */

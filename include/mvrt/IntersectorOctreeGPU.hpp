@@ -283,6 +283,78 @@ struct IntersectorOctreeGPU
 		return n;
 	}
 
+	// round offsets (mvrt_svo_distance_cells / _depth_voxels / _dilate_ball / _erode_ball / _close_ball / _open_ball; semantics in mvrt.h), radius2 = the squared
+	// radius of the ball, 1..1024.  Device-pointer forms of the listings: any output may be nullptr, all nullptr = the sizing call; they return the count.
+	uint64_t distanceCells( uint32_t radius2, uint64_t capacity, uint32_t* xyzDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_distance_cells( m_handle, radius2, capacity, xyzDev, dist2Dev, nearestDev, attribsDev, &n, stream ), "IntersectorOctreeGPU::distanceCells" );
+		return n;
+	}
+	// host-vector form: xyz = 3 entries per cell in ascending Morton order, dist2 = 1 (the exact squared distance to the set), nearest = 1 (the vIndex of the
+	// nearest voxel, the lowest on a tie), attribs = 2 (that voxel's colour and emission, alpha 255)
+	void distanceCells( uint32_t radius2, std::vector<uint32_t>& xyz, std::vector<uint32_t>& dist2, std::vector<uint32_t>& nearest, std::vector<uint32_t>& attribs, void* stream ) const
+	{
+		const uint64_t n = distanceCells( radius2, 0, nullptr, nullptr, nullptr, nullptr, stream );
+		xyz.resize( n * 3 );
+		dist2.resize( n );
+		nearest.resize( n );
+		attribs.resize( n * 2 );
+		Staged x( nullptr, n * 12, stream ), d( nullptr, n * 4, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
+		if( n ) distanceCells( radius2, n, (uint32_t*)x.p, (uint32_t*)d.p, (uint32_t*)v.p, (uint32_t*)a.p, stream );
+		fetch( xyz, x, stream );
+		fetch( dist2, d, stream );
+		fetch( nearest, v, stream );
+		fetch( attribs, a, stream );
+	}
+	uint64_t depthVoxels( uint32_t radius2, uint64_t capacity, uint32_t* vIndexDev, uint32_t* depth2Dev, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_depth_voxels( m_handle, radius2, capacity, vIndexDev, depth2Dev, &n, stream ), "IntersectorOctreeGPU::depthVoxels" );
+		return n;
+	}
+	// host-vector form: the vIndex, ascending, of the voxels whose squared depth is at most radius2, and that depth
+	void depthVoxels( uint32_t radius2, std::vector<uint32_t>& vIndex, std::vector<uint32_t>& depth2, void* stream ) const
+	{
+		const uint64_t n = depthVoxels( radius2, 0, nullptr, nullptr, stream );
+		vIndex.resize( n );
+		depth2.resize( n );
+		Staged v( nullptr, n * 4, stream ), d( nullptr, n * 4, stream );
+		if( n ) depthVoxels( radius2, n, (uint32_t*)v.p, (uint32_t*)d.p, stream );
+		fetch( vIndex, v, stream );
+		fetch( depth2, d, stream );
+	}
+	// in place, one ball per call, the levels built once.  They return the cells added (dilateBall), the voxels removed (erodeBall), the net cells added (closeBall)
+	// and the net voxels removed (openBall).  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
+	uint64_t dilateBall( uint32_t radius2, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_dilate_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::dilateBall" );
+		refresh();
+		return n;
+	}
+	uint64_t erodeBall( uint32_t radius2, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_erode_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::erodeBall" );
+		refresh();
+		return n;
+	}
+	uint64_t closeBall( uint32_t radius2, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_close_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::closeBall" );
+		refresh();
+		return n;
+	}
+	uint64_t openBall( uint32_t radius2, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_open_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::openBall" );
+		refresh();
+		return n;
+	}
+
 	// connected components of the voxel set (mvrt_svo_components / mvrt_svo_keep_components; semantics in mvrt.h), element = MVRT_MORPH_FACES (6-connected) or
 	// MVRT_MORPH_CUBE (26-connected).  Device-pointer form: labelDev holds numberOfVoxels entries, the others componentCapacity components (boxDev 6 each); any
 	// output may be nullptr, all nullptr = the sizing call.  Returns the number of components; *largest (may be nullptr) = the size of the largest.

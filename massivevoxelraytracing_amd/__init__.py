@@ -107,6 +107,12 @@ SIGNATURES = {
     "mvrt_svo_erode": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_close": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_open": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "mvrt_svo_distance_cells": (_i32, [_vp, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_depth_voxels": (_i32, [_vp, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_dilate_ball": (_i32, [_vp, _u32, _vp, _vp]),
+    "mvrt_svo_erode_ball": (_i32, [_vp, _u32, _vp, _vp]),
+    "mvrt_svo_close_ball": (_i32, [_vp, _u32, _vp, _vp]),
+    "mvrt_svo_open_ball": (_i32, [_vp, _u32, _vp, _vp]),
     "mvrt_svo_get_info": (_i32, [_vp, _vp]),
     "mvrt_svo_set_emission_scale": (_i32, [_vp, _f32]),
     "mvrt_svo_device_view": (_i32, [_vp, _vp]),
@@ -177,6 +183,8 @@ SIGNATURES = {
     "mvrt_pt_set_test_free_bytes": (_i32, [_vp, _u64]),
     "mvrt_test_fail_allocation": (_i32, [C.c_int64]),
     "mvrt_test_allocation_state": (_i32, [_vp, _vp, _vp]),
+    "mvrt_test_ball_stats": (_i32, [_vp]),
+    "mvrt_test_peak_bytes": (_i32, [_vp, _i32]),
     "mvrt_pt_set_profiling": (_i32, [_vp, _i32]),
     "mvrt_pt_reset_stats": (_i32, [_vp]),
     "mvrt_pt_get_stats": (_i32, [_vp, _vp, _vp]),
@@ -237,6 +245,20 @@ def synchronize():
 def set_test_fail_allocation(nth):
     """failure-path tests: the nth device allocation the library makes from now on this thread fails, then the hook is off again (0 = off)"""
     _check(lib().mvrt_test_fail_allocation(int(nth)))
+
+
+def peak_bytes(reset=False):
+    """measuring: the most bytes of device memory the library held at one time since the last reset (mvrt_test_peak_bytes)"""
+    v = C.c_uint64(0)
+    _check(lib().mvrt_test_peak_bytes(C.byref(v), int(bool(reset))))
+    return v.value
+
+
+def ball_stats():
+    """measuring: what the last distance band this thread ran did: {records: per pass along x, y, z, seeds, cells} (mvrt_test_ball_stats)"""
+    v = (C.c_uint64 * 5)()
+    _check(lib().mvrt_test_ball_stats(v))
+    return {"records": [int(v[0]), int(v[1]), int(v[2])], "seeds": int(v[3]), "cells": int(v[4])}
 
 
 def allocation_state():
@@ -525,6 +547,62 @@ class IntersectorOctreeGPU:
         """mvrt_svo_open: `steps` erosion steps, then `steps` dilation steps, in place; a pure removal (the voxels left keep their bytes); returns the net voxels
         removed.  Refused when none would be left."""
         return self._morph(lib().mvrt_svo_open, element, steps, stream)
+
+    def distance_cells_device(self, radius2=1, capacity=0, xyz=None, dist2=None, nearest=None, attribs=None, stream=None):
+        """mvrt_svo_distance_cells into caller device arrays of `capacity` cells (any may be None; all None = the sizing call); returns the number of cells.
+        On MvrtError nothing was written."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_distance_cells(self._h, int(radius2), int(capacity), _dev_ptr(xyz), _dev_ptr(dist2), _dev_ptr(nearest), _dev_ptr(attribs), C.byref(n), stream))
+        return n.value
+
+    def distance_cells(self, radius2=1, stream=None):
+        """the empty in-grid cells within squared distance `radius2` (1..1024) of the set, in ascending Morton order: {xyz (n, 3) uint32, dist2 (n,) uint32 = the
+        exact squared distance to the set, nearest (n,) uint32 = the lowest vIndex among the voxels at that distance, attribs (n, 8) uint8 = that voxel's colour and
+        emission with alpha 255}"""
+        n = self.distance_cells_device(radius2, stream=stream)
+        xyz, d2, near, at = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
+        if n:
+            self.distance_cells_device(radius2, n, xyz, d2, near, at, stream)
+        return {"xyz": xyz.to_host(), "dist2": d2.to_host(), "nearest": near.to_host(), "attribs": at.to_host()}
+
+    def depth_voxels_device(self, radius2=1, capacity=0, vIndex=None, depth2=None, stream=None):
+        """mvrt_svo_depth_voxels into caller device arrays of `capacity` entries (any may be None; both None = the sizing call); returns the number of voxels."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_depth_voxels(self._h, int(radius2), int(capacity), _dev_ptr(vIndex), _dev_ptr(depth2), C.byref(n), stream))
+        return n.value
+
+    def depth_voxels(self, radius2=1, stream=None):
+        """the voxels whose squared distance to the nearest empty in-grid cell is at most `radius2` (outside the grid counts as occupied), the ones erode_ball
+        removes: {vIndex (n,) uint32 ascending, depth2 (n,) uint32}"""
+        n = self.depth_voxels_device(radius2, stream=stream)
+        vi, d2 = DeviceArray(n, np.uint32), DeviceArray(n, np.uint32)
+        if n:
+            self.depth_voxels_device(radius2, n, vi, d2, stream)
+        return {"vIndex": vi.to_host(), "depth2": d2.to_host()}
+
+    def _ball(self, fn, radius2, stream):
+        n = C.c_uint64(0)
+        _check(fn(self._h, int(radius2), C.byref(n), stream))
+        return n.value
+
+    def dilate_ball(self, radius2=1, stream=None):
+        """mvrt_svo_dilate_ball: the set grown by the ball of squared radius `radius2` in place, one operation, the levels built once; a new cell takes the
+        attribute of its nearest voxel.  Returns the cells added (0: the handle was not touched).  Invalidates device_view() snapshots otherwise."""
+        return self._ball(lib().mvrt_svo_dilate_ball, radius2, stream)
+
+    def erode_ball(self, radius2=1, stream=None):
+        """mvrt_svo_erode_ball: the voxels deeper than `radius2` stay (outside the grid counts as occupied); returns the voxels removed.  Refused when none would
+        be left."""
+        return self._ball(lib().mvrt_svo_erode_ball, radius2, stream)
+
+    def close_ball(self, radius2=1, stream=None):
+        """mvrt_svo_close_ball: dilate_ball, then erode_ball, in one call; returns the net cells added."""
+        return self._ball(lib().mvrt_svo_close_ball, radius2, stream)
+
+    def open_ball(self, radius2=1, stream=None):
+        """mvrt_svo_open_ball: erode_ball, then dilate_ball, in one call; a pure removal (the voxels left keep their bytes); returns the net voxels removed.
+        Refused when none would be left."""
+        return self._ball(lib().mvrt_svo_open_ball, radius2, stream)
 
     def components_device(self, element=MORPH_CUBE, label=None, capacity=0, size=None, first=None, box=None, stream=None):
         """mvrt_svo_components into caller device arrays: label of numberOfVoxels uint32, size / first of `capacity` uint32, box of capacity x 6 uint32 (any may be

@@ -684,6 +684,22 @@ MVRT_EXPORT int mvrt_svo_erosion_voxels( const mvrt_svo* svo, int element, uint6
 	if( morphSource( svo, "mvrt_svo_erosion_voxels", element, &s ) ) return 1;
 	return morphErosionVoxels( s, element, capacity, vIndexDev, nOut, (hipStream_t)stream );
 }
+// the end of an in-place call: the handle takes the n sorted codes and attributes a list operator left (both empty when n is the old count: nothing changed)
+static int morphAdopt( mvrt_svo* svo, DevBuf& morton, DevBuf& attrs, uint32_t n, uint32_t hasEmission, uint64_t* nChangedOut, hipStream_t st )
+{
+	const uint32_t nOld = svo->oct.nVoxels;
+	if( n == nOld ) return 0; // nothing changes: the handle is not touched
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
+	const mvrt_svo_info& info = svo->oct.info;
+	SvoBuildResult r;
+	if( svoBuildFromSorted( morton, attrs, n, (int)info.gridRes, svo->oct.buildFlags, st, &r ) ) return 1;
+	r.hasEmission = hasEmission;
+	r.totalDumped = 0; // (as an edit leaves it)
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	if( adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, svo->oct.buildFlags ) ) return 1; // (arguments are read before the old octree goes)
+	if( nChangedOut ) *nChangedOut = n > nOld ? n - nOld : nOld - n;
+	return 0;
+}
 static int morphInPlace( mvrt_svo* svo, const char* who, int op, int element, int steps, uint64_t* nChangedOut, void* stream )
 {
 	if( nChangedOut ) *nChangedOut = 0;
@@ -694,18 +710,7 @@ static int morphInPlace( mvrt_svo* svo, const char* who, int op, int element, in
 	DevBuf morton, attrs;
 	uint32_t n = 0, he = 0;
 	if( morphList( who, s, element, op, steps, morton, attrs, &n, &he, st ) ) return 1;
-	const uint32_t nOld = svo->oct.nVoxels;
-	if( n == nOld ) return 0; // nothing changes: the handle is not touched
-	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
-	const mvrt_svo_info& info = svo->oct.info;
-	SvoBuildResult r;
-	if( svoBuildFromSorted( morton, attrs, n, (int)info.gridRes, svo->oct.buildFlags, st, &r ) ) return 1;
-	r.hasEmission = he;
-	r.totalDumped = 0; // (as an edit leaves it)
-	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
-	if( adoptBuild( svo, r, origin, info.dps, (int)info.gridRes, svo->oct.buildFlags ) ) return 1; // (arguments are read before the old octree goes)
-	if( nChangedOut ) *nChangedOut = n > nOld ? n - nOld : nOld - n;
-	return 0;
+	return morphAdopt( svo, morton, attrs, n, he, nChangedOut, st );
 }
 MVRT_EXPORT int mvrt_svo_dilate( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream )
 {
@@ -722,6 +727,70 @@ MVRT_EXPORT int mvrt_svo_close( mvrt_svo* svo, int element, int steps, uint64_t*
 MVRT_EXPORT int mvrt_svo_open( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream )
 {
 	return morphInPlace( svo, "mvrt_svo_open", MVRT_MORPH_OP_OPEN, element, steps, nRemovedOut, stream );
+}
+
+// Round offsets (kernels_ball.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listings read the sorted codes and the
+// attributes alone; the in-place calls run their halves on sorted lists next to the old octree and build the levels once, as the morphology above does.
+static int ballSource( const mvrt_svo* svo, const char* who, uint32_t radius2, SurfaceSource* s )
+{
+	if( surfaceSource( svo, who, s ) ) return 1;
+	REQUIRE( radius2 >= 1u && radius2 <= 1024u, "%s: radius2 %u is outside [1, 1024]", who, radius2 );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_distance_cells( const mvrt_svo* svo, uint32_t radius2, uint64_t capacity, uint32_t* xyzDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev,
+										 uint64_t* nOut, void* stream )
+{
+	SurfaceSource s;
+	if( ballSource( svo, "mvrt_svo_distance_cells", radius2, &s ) ) return 1;
+	return ballDistanceCells( s, radius2, capacity, xyzDev, dist2Dev, nearestDev, attribsDev, nOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_depth_voxels( const mvrt_svo* svo, uint32_t radius2, uint64_t capacity, uint32_t* vIndexDev, uint32_t* depth2Dev, uint64_t* nOut, void* stream )
+{
+	SurfaceSource s;
+	if( ballSource( svo, "mvrt_svo_depth_voxels", radius2, &s ) ) return 1;
+	return ballDepthVoxels( s, radius2, capacity, vIndexDev, depth2Dev, nOut, (hipStream_t)stream );
+}
+static int ballInPlace( mvrt_svo* svo, const char* who, int op, uint32_t radius2, uint64_t* nChangedOut, void* stream )
+{
+	if( nChangedOut ) *nChangedOut = 0;
+	SurfaceSource s;
+	if( ballSource( svo, who, radius2, &s ) ) return 1;
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf morton, attrs;
+	uint32_t n = 0, he = 0;
+	if( ballList( who, s, radius2, op, morton, attrs, &n, &he, st ) ) return 1;
+	return morphAdopt( svo, morton, attrs, n, he, nChangedOut, st );
+}
+MVRT_EXPORT int mvrt_svo_dilate_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nAddedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_dilate_ball", MVRT_MORPH_OP_DILATE, radius2, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_erode_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nRemovedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_erode_ball", MVRT_MORPH_OP_ERODE, radius2, nRemovedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_close_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nAddedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_close_ball", MVRT_MORPH_OP_CLOSE, radius2, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_open_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nRemovedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_open_ball", MVRT_MORPH_OP_OPEN, radius2, nRemovedOut, stream );
+}
+MVRT_EXPORT int mvrt_test_peak_bytes( uint64_t* peakOut, int reset )
+{
+	if( peakOut ) *peakOut = g_devBufState.peakBytes;
+	if( reset ) g_devBufState.peakBytes = g_devBufState.liveBytes.load();
+	return 0;
+}
+MVRT_EXPORT int mvrt_test_ball_stats( uint64_t out[5] )
+{
+	const BallStats b = ballLastStats();
+	REQUIRE( out, "mvrt_test_ball_stats: null out" );
+	for( int k = 0; k < 3; k++ ) out[k] = b.records[k];
+	out[3] = b.seeds;
+	out[4] = b.cells;
+	return 0;
 }
 
 // Connected components (kernels_components.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listing reads the sorted codes

@@ -9,6 +9,7 @@
 struct DevBufState // process-wide
 {
 	std::atomic<uint64_t> liveBuffers{ 0 }, liveBytes{ 0 }, totalAllocs{ 0 };
+	std::atomic<uint64_t> peakBytes{ 0 }; // the largest liveBytes since mvrt_test_peak_bytes last reset it
 };
 inline DevBufState g_devBufState;
 inline thread_local int64_t g_devBufFailIn = 0; // n > 0: the n-th alloc from now on this thread fails, then the hook is off again
@@ -29,7 +30,8 @@ struct DevBuf // move-only
 		MVRT_HIP( hipMalloc( &p, b ? b : 1 ) );
 		bytes = b;
 		g_devBufState.liveBuffers++;
-		g_devBufState.liveBytes += b;
+		const uint64_t live = ( g_devBufState.liveBytes += b );
+		for( uint64_t peak = g_devBufState.peakBytes; live > peak && !g_devBufState.peakBytes.compare_exchange_weak( peak, live ); ) {}
 		return 0;
 	}
 	void release()

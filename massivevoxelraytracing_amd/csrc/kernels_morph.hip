@@ -236,11 +236,7 @@ int dilateStep( const char* who, int step, VoxelList& l, uint32_t levels, int el
 	MVRT_HIP( hipStreamSynchronize( st ) );
 	const uint32_t nNew = r.nCells, nAll = l.n + nNew;
 	r = Records();
-	if( codes.alloc( (uint64_t)nAll * 8 ) || attrs.alloc( (uint64_t)nAll * 8 ) ) return 1;
-	hipLaunchKernelGGL( kMorphMerge, dim3( divUp( nAll, MB ) ), dim3( MB ), 0, st, l.codes, l.attrs, l.n, newCodes.as<uint64_t>(), newAttrs.as<uint2>(), nNew, codes.as<uint64_t>(),
-						attrs.as<uint2>() );
-	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipStreamSynchronize( st ) ); // (the inputs are released below)
+	if( morphMergeLists( l.codes, l.attrs, l.n, newCodes.as<uint64_t>(), newAttrs.as<uint2>(), nNew, codes, attrs, st ) ) return 1; // (the inputs are released below)
 	l.take( codes, attrs, nAll );
 	*changed = 1;
 	return 0;
@@ -309,6 +305,17 @@ int morphDilationCells( const SurfaceSource& s, int element, uint64_t capacity, 
 	return 0;
 }
 
+int morphStepCodes( const char* who, const uint64_t* codes, const uint2* attrs, uint32_t n, uint32_t levels, int element, DevBuf& cellCodes, uint32_t* nCells, hipStream_t st )
+{
+	Records r;
+	if( dilationRecords( who, codes, n, levels, element, &r, st ) ) return 1;
+	*nCells = r.nCells;
+	if( r.nCells == 0 ) return 0;
+	if( cellCodes.alloc( (uint64_t)r.nCells * 8 ) || launchCells( r, attrs, cellCodes.as<uint64_t>(), nullptr, nullptr, nullptr, st ) ) return 1;
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the records are released on return)
+	return 0;
+}
+
 int morphErosionVoxels( const SurfaceSource& s, int element, uint64_t capacity, uint32_t* vIndexDev, uint64_t* nOut, hipStream_t st )
 {
 	DevBuf mask, offs;
@@ -359,10 +366,7 @@ int morphList( const char* who, const SurfaceSource& s, int element, int op, int
 	if( op == MVRT_MORPH_OP_OPEN ) // a pure removal: the original bytes, not the means of the dilation half
 	{
 		DevBuf original;
-		if( original.alloc( (uint64_t)l.n * 8 ) ) return 1;
-		hipLaunchKernelGGL( kMorphGatherAttrs, dim3( divUp( l.n, MB ) ), dim3( MB ), 0, st, l.codes, l.n, s.morton, s.attrs, s.nVoxels, original.as<uint2>() );
-		MVRT_HIP( hipGetLastError() );
-		MVRT_HIP( hipStreamSynchronize( st ) );
+		if( morphGatherAttrs( l.codes, l.n, s.morton, s.attrs, s.nVoxels, original, st ) ) return 1;
 		l.ownAttrs = std::move( original );
 		l.attrs = l.ownAttrs.as<uint2>();
 	}
@@ -371,6 +375,25 @@ int morphList( const char* who, const SurfaceSource& s, int element, int op, int
 	attribs = std::move( l.ownAttrs );
 	return 0;
 }
+
+int morphMergeLists( const uint64_t* aCodes, const uint2* aAttrs, uint32_t nA, const uint64_t* bCodes, const uint2* bAttrs, uint32_t nB, DevBuf& codes, DevBuf& attribs, hipStream_t st )
+{
+	const uint32_t nAll = nA + nB;
+	if( codes.alloc( (uint64_t)nAll * 8 ) || attribs.alloc( (uint64_t)nAll * 8 ) ) return 1;
+	hipLaunchKernelGGL( kMorphMerge, dim3( divUp( nAll, MB ) ), dim3( MB ), 0, st, aCodes, aAttrs, nA, bCodes, bAttrs, nB, codes.as<uint64_t>(), attribs.as<uint2>() );
+	MVRT_HIP( hipGetLastError() );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	return 0;
+}
+int morphGatherAttrs( const uint64_t* codes, uint32_t n, const uint64_t* srcCodes, const uint2* srcAttrs, uint32_t nSrc, DevBuf& attribs, hipStream_t st )
+{
+	if( attribs.alloc( (uint64_t)n * 8 ) ) return 1;
+	hipLaunchKernelGGL( kMorphGatherAttrs, dim3( divUp( n, MB ) ), dim3( MB ), 0, st, codes, n, srcCodes, srcAttrs, nSrc, attribs.as<uint2>() );
+	MVRT_HIP( hipGetLastError() );
+	MVRT_HIP( hipStreamSynchronize( st ) );
+	return 0;
+}
+int morphAnyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t st ) { return anyEmission( attrs, n, hasEmission, st ); }
 
 int morphCompactKept( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
 					  hipStream_t st )

@@ -216,6 +216,8 @@ int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int leve
 // write NOTHING to the caller's arrays unless they succeed.
 int morphDilationCells( const SurfaceSource& s, int element, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, uint64_t* nOut, hipStream_t stream );
 int morphErosionVoxels( const SurfaceSource& s, int element, uint64_t capacity, uint32_t* vIndexDev, uint64_t* nOut, hipStream_t stream );
+// the cells one dilation step adds to the n sorted codes, as ascending codes into cellCodes (allocated here; left empty when *nCells is 0: a full grid).  Blocks
+int morphStepCodes( const char* who, const uint64_t* codes, const uint2* attrs, uint32_t n, uint32_t levels, int element, DevBuf& cellCodes, uint32_t* nCells, hipStream_t stream );
 enum
 {
 	MVRT_MORPH_OP_DILATE = 0,
@@ -230,6 +232,28 @@ int morphList( const char* who, const SurfaceSource& s, int element, int op, int
 // here; left empty when *nKept is 0 or n) and the emission flag over them.  Blocks
 int morphCompactKept( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
 					  hipStream_t stream );
+
+// the other list steps of kernels_morph.hip that kernels_ball.hip runs as well; each allocates its outputs here and blocks.  Two sorted lists without a common
+// code merged into one; the attributes that the n codes, a subset of srcCodes, have there; *hasEmission = 1 where one of the n attributes has an emission byte set
+int morphMergeLists( const uint64_t* aCodes, const uint2* aAttrs, uint32_t nA, const uint64_t* bCodes, const uint2* bAttrs, uint32_t nB, DevBuf& codes, DevBuf& attribs, hipStream_t stream );
+int morphGatherAttrs( const uint64_t* codes, uint32_t n, const uint64_t* srcCodes, const uint2* srcAttrs, uint32_t nSrc, DevBuf& attribs, hipStream_t stream );
+int morphAnyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t stream );
+
+// round offsets (kernels_ball.hip; mvrt_svo_distance_cells / _depth_voxels / _dilate_ball / _erode_ball / _close_ball / _open_ball): morton, attrs, nVoxels and levels
+// of the source are read, radius2 is in [1, 1024], checked by the caller.  The calls block, keep their scratch in DevBufs and write NOTHING to the caller's arrays
+// unless they succeed.
+struct BallStats // what the last band of a call did (tools/ball_bench.py through mvrt_test_ball_stats)
+{
+	uint64_t records[3] = { 0, 0, 0 }; // per pass x, y, z
+	uint64_t seeds = 0, cells = 0;
+};
+int ballDistanceCells( const SurfaceSource& s, uint32_t radius2, uint64_t capacity, uint32_t* xyzDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, uint64_t* nOut,
+					   hipStream_t stream );
+int ballDepthVoxels( const SurfaceSource& s, uint32_t radius2, uint64_t capacity, uint32_t* vIndexDev, uint32_t* depth2Dev, uint64_t* nOut, hipStream_t stream );
+// the operator (MVRT_MORPH_OP_*) with the ball of radius2 on sorted lists, for svoBuildFromSorted: *nOut = the voxels of the result; codes / attribs (allocated
+// here) are left empty when *nOut == nVoxels, which means that the set did not change.  A result of 2^32 - 1 voxels or more or of none is refused; `who` names the call
+int ballList( const char* who, const SurfaceSource& s, uint32_t radius2, int op, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission, hipStream_t stream );
+BallStats ballLastStats(); // of this thread
 
 // connected components (kernels_components.hip; mvrt_svo_components / mvrt_svo_keep_components): morton, attrs, nVoxels and levels of the source are read, element
 // is MVRT_MORPH_FACES or MVRT_MORPH_CUBE, checked by the caller.  The calls block, keep their scratch in DevBufs and write NOTHING to the caller's arrays

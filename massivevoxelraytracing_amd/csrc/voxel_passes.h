@@ -11,6 +11,8 @@
 //                   coarseMaxCount.  Host-callable as well (tests/hip/coarsen_host.hip).
 //   elements        the neighbour tables of the two structuring elements, the presence search on the sorted codes (kernels_morph.hip) and, for the connected
 //                   components (kernels_components.hip), the half of an element that sees every adjacent pair once and the search that returns the index.
+//   round offsets   ballReach, ballShiftRange, ballShifted and the packed key ( d2 << 32 | payload ) of kernels_ball.hip: the shifts an entry of a distance pass sends
+//                   records to, clipped to the grid and to the radius.  Host-callable (tests/hip/ball_host.hip).
 //   two sets        combineTranslate (a code moved by an integer offset and clipped to a grid) of kernels_combine.hip, and combineWindow / codeIndexInRange: the
 //                   partner search of a group of ascending codes, bounded once per group.  Host-callable (tests/hip/combine_host.hip).
 //   union-find      ufLoad / ufStore / ufFind / ufUnite / ufRoot: the lock-free union-find over node ids that kernels_fill.hip runs on the gaps and
@@ -157,6 +159,44 @@ MVRT_HDI uint32_t morphEmptyMask( const uint64_t* __restrict__ codes, uint64_t n
 	}
 	return mask;
 }
+
+// ---- round offsets (kernels_ball.hip) -----------------------------------------------------------------------------------------------------------------------
+// The exact squared distance is a sum over the axes, so the band of cells within rho of a seed list is made by three passes, one per axis: an
+// entry ( code, d2 << 32 | payload ) yields the in-grid cells at shift s on the axis of the pass with d2 + s * s <= rho.  Host-callable like the morph helpers
+// (tests/hip/ball_host.hip).
+// floor( sqrt( rho ) ) for rho < 4096 without floating point: the reach of a ball, 32 at most for a legal radius
+MVRT_HDI uint32_t ballReach( uint32_t rho )
+{
+	uint32_t k = 0u;
+	for( uint32_t bit = 32u; bit != 0u; bit >>= 1 )
+		if( ( k + bit ) * ( k + bit ) <= rho ) k += bit;
+	return k;
+}
+MVRT_HDI uint64_t ballKey( uint32_t d2, uint32_t payload ) { return (uint64_t)d2 << 32 | payload; }
+MVRT_HDI uint32_t ballKeyDist2( uint64_t key ) { return (uint32_t)( key >> 32 ); }
+MVRT_HDI uint32_t ballKeyPayload( uint64_t key ) { return (uint32_t)key; }
+MVRT_HDI uint32_t ballAxisCoord( uint64_t code, uint32_t axis ) { return compactBy3( code >> axis ); }
+// The shifts an entry at coordinate `coord` of the pass's axis, with squared distance d2 <= rho so far, sends records to: *first, *first + 1, ..., *first + count - 1
+// with count the return value, at least 1 (the shift 0).  m = ballReach( rho - d2 ) bounds |s|; below, the shift stops at coordinate 0, above at R - 1: a
+// coordinate of -1 or R does not exist, R = 2^21 included, so nothing is ever folded back into the 21 bits per axis of a code.
+MVRT_HDI uint32_t ballShiftRange( uint32_t coord, uint32_t levels, uint32_t d2, uint32_t rho, int32_t* first )
+{
+	const uint32_t m = ballReach( rho - d2 ), above = ( 1u << levels ) - 1u - coord;
+	const uint32_t down = m < coord ? m : coord, up = m < above ? m : above;
+	*first = -(int32_t)down;
+	return down + up + 1u;
+}
+// the cell `code` names moved by s cells along the axis (0 = x, 1 = y, 2 = z) of a grid of R = 2^levels <= 2^21 cells per axis: false when it leaves the grid,
+// else true and *codeOut = its code.  The sum is taken in 64 bits like combineTranslate's
+MVRT_HDI bool ballShifted( uint64_t code, uint32_t levels, uint32_t axis, int32_t s, uint64_t* codeOut )
+{
+	const int64_t c = (int64_t)ballAxisCoord( code, axis ) + s;
+	if( c < 0 || c >= (int64_t)1 << levels ) return false;
+	*codeOut = ( code & ~( 0x1249249249249249ull << axis ) ) | splitBy3( (uint32_t)c ) << axis;
+	return true;
+}
+// the key of the record at shift s: the distance field grows by s * s, the payload stays.  Adding the same constant to both keeps the order of two keys
+MVRT_HDI uint64_t ballShiftKey( uint64_t key, int32_t s ) { return key + ( (uint64_t)( (uint32_t)( s * s ) ) << 32 ); }
 
 // ---- two sets (kernels_combine.hip) -------------------------------------------------------------------------------------------------------------------------
 // The cell `code` names, moved by the offset o (each component in [-2^21, 2^21]) inside a grid of R = 2^levels <= 2^21 cells per axis: false when it leaves the
