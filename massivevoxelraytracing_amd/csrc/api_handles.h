@@ -1,5 +1,5 @@
-// api_handles.h -- what the two halves of the C-ABI share: api.hip (runtime, octree handles, batch traces) and api_pt.hip (the path tracer) meet in
-// the octree handle alone.  Host code only.
+// api_handles.h -- what the parts of the C-ABI share: api.hip (runtime, octree handles, batch traces), api_voxels.hip (the voxel-set operators) and
+// api_pt.hip (the path tracer, which meets the others in the octree handle alone).  Host code only.
 #pragma once
 #include <string.h>
 
@@ -119,3 +119,12 @@ static inline CameraPinhole cameraFrom15( const float c[15] ) // the 15 floats o
 // deferred here, so every change of state a pending or in-flight step reads is preceded by launching (flush) or finishing (drain) those steps.
 int ptFlush( mvrt_pt* pt ); // (api_pt.hip)
 int ptDrain( mvrt_pt* pt );
+
+// What api.hip and api_voxels.hip share.  ownerDrain finishes the steps of the path tracer that owns the handle; adoptBuild, adoptOnOwnGrid and adoptSorted are
+// the only ways a handle takes a new octree (api.hip, where each says what a failure leaves); surfaceSource refuses a handle without sorted codes, in the name
+// of the call `who`, and fills what the passes read (api_voxels.hip)
+int ownerDrain( const mvrt_svo* svo );
+int adoptBuild( mvrt_svo* svo, SvoBuildResult& r, const float origin[3], float dps, int gridRes, int flags );
+int adoptOnOwnGrid( mvrt_svo* svo, SvoBuildResult& r, int flags );
+int adoptSorted( mvrt_svo* svo, SortedVoxels& v, hipStream_t stream );
+int surfaceSource( const mvrt_svo* svo, const char* who, SurfaceSource* s );

@@ -1,0 +1,391 @@
+// api_voxels.hip -- the C-ABI of libmvrt_hip.so (include/mvrt.h), the voxel-set operators on a built octree: surface extraction, enclosed cells and the fill,
+// coarsening, morphology with the step elements and with the ball, connected components and the two-set operators.  Every refusal the arguments and the handles
+// decide is made here, on the host; the listings never touch the handle, the in-place calls end in adoptSorted (api.hip).
+#include "api_handles.h"
+
+// Surface extraction (kernels_surface.hip).  Only the sorted codes and, where there is one, the cell index are read: every flavour is accepted and the
+// handle is never modified.  (Builds and edits drain the steps in flight themselves; nothing here changes what a pending step reads.)
+int surfaceSource( const mvrt_svo* svo, const char* who, SurfaceSource* s )
+{
+	REQUIRE( svo, "%s: null handle", who );
+	REQUIRE( !svo->empty(), "%s: no octree (build first)", who );
+	REQUIRE( svo->oct.morton.p, "%s: an uploaded octree keeps no Morton codes", who );
+	const Octree& o = svo->oct;
+	s->morton = o.morton.as<uint64_t>();
+	s->nVoxels = o.nVoxels;
+	s->levels = o.info.levels;
+	s->cellBlocks = o.cellEntries.p ? o.cellBlocks.as<uint32_t>() : nullptr;
+	s->cellEntries = o.cellEntries.as<uint2>();
+	s->cellBits = o.cellBits;
+	s->lower = mk3( o.info.lower[0], o.info.lower[1], o.info.lower[2] );
+	s->dps = o.info.dps;
+	s->attrs = o.attrs.as<uint2>();
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_surface_masks( const mvrt_svo* svo, uint8_t* masksDev, uint64_t* nFacesOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_masks", &s ) ) return 1;
+	return surfaceMasks( s, masksDev, nFacesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_quads( const mvrt_svo* svo, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, uint64_t* nFacesOut,
+										void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_quads", &s ) ) return 1;
+	return surfaceQuads( s, nullptr, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFacesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_mesh( const mvrt_svo* svo, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
+									   float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_mesh", &s ) ) return 1;
+	return surfaceMesh( s, nullptr, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFacesOut, nVerticesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_merged( const mvrt_svo* svo, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev,
+										 uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut,
+										 uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	if( nVerticesOut ) *nVerticesOut = 0;
+	REQUIRE( ( flags & ~(uint32_t)( MVRT_SURFACE_MERGE_ANY_ATTRIBUTE | MVRT_SURFACE_MERGE_WELD ) ) == 0, "mvrt_svo_surface_merged: unknown flags 0x%x", flags );
+	if( surfaceSource( svo, "mvrt_svo_surface_merged", &s ) ) return 1;
+	REQUIRE( ( flags & MVRT_SURFACE_MERGE_WELD ) || ( !indicesDev && !verticesDev ), "mvrt_svo_surface_merged: indicesDev / verticesDev need MVRT_SURFACE_MERGE_WELD" );
+	return surfaceMerged( s, nullptr, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev, nFacesOut, nRectsOut, nVerticesOut,
+						  (hipStream_t)stream );
+}
+
+// The same three calls on a caller's face masks, and the exterior masks as one producer of them (kernels_fill.hip).  A null handle and null masks are refused
+// first, then what the namesake refuses.
+MVRT_EXPORT int mvrt_svo_surface_exterior_masks( const mvrt_svo* svo, uint8_t* masksDev, uint64_t* nFacesOut, uint64_t* nHiddenOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_surface_exterior_masks", &s ) ) return 1;
+	return surfaceExteriorMasks( s, masksDev, nFacesOut, nHiddenOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_quads_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev,
+												 uint64_t* nFacesOut, void* stream )
+{
+	SurfaceSource s;
+	REQUIRE( svo, "mvrt_svo_surface_quads_masked: null handle" );
+	REQUIRE( masksDev, "mvrt_svo_surface_quads_masked: null masksDev" );
+	if( surfaceSource( svo, "mvrt_svo_surface_quads_masked", &s ) ) return 1;
+	return surfaceQuads( s, masksDev, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFacesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_mesh_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev,
+												uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	REQUIRE( svo, "mvrt_svo_surface_mesh_masked: null handle" );
+	REQUIRE( masksDev, "mvrt_svo_surface_mesh_masked: null masksDev" );
+	if( surfaceSource( svo, "mvrt_svo_surface_mesh_masked", &s ) ) return 1;
+	return surfaceMesh( s, masksDev, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, nFacesOut, nVerticesOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_surface_merged_masked( const mvrt_svo* svo, const uint8_t* masksDev, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev,
+												  uint8_t* rectDirDev, uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut,
+												  uint64_t* nRectsOut, uint64_t* nVerticesOut, void* stream )
+{
+	SurfaceSource s;
+	if( nVerticesOut ) *nVerticesOut = 0;
+	REQUIRE( ( flags & ~(uint32_t)( MVRT_SURFACE_MERGE_ANY_ATTRIBUTE | MVRT_SURFACE_MERGE_WELD ) ) == 0, "mvrt_svo_surface_merged_masked: unknown flags 0x%x", flags );
+	REQUIRE( svo, "mvrt_svo_surface_merged_masked: null handle" );
+	REQUIRE( masksDev, "mvrt_svo_surface_merged_masked: null masksDev" );
+	if( surfaceSource( svo, "mvrt_svo_surface_merged_masked", &s ) ) return 1;
+	REQUIRE( ( flags & MVRT_SURFACE_MERGE_WELD ) || ( !indicesDev && !verticesDev ), "mvrt_svo_surface_merged_masked: indicesDev / verticesDev need MVRT_SURFACE_MERGE_WELD" );
+	return surfaceMerged( s, masksDev, flags, rectCapacity, vertexCapacity, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, indicesDev, verticesDev, nFacesOut, nRectsOut,
+						  nVerticesOut, (hipStream_t)stream );
+}
+
+// Enclosed empty cells and the fill (kernels_fill.hip).  The listing reads the sorted codes alone, like the surface calls.  The fill hands the cells, which stay on
+// the device, to the edit's own path: what it leaves is what mvrt_svo_edit_voxels leaves, by construction.
+MVRT_EXPORT int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_enclosed_cells", &s ) ) return 1;
+	return enclosedCells( s, capacity, xyzDev, regionDev, nCellsOut, nRegionsOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8], uint64_t* nFilledOut, void* stream )
+{
+	if( nFilledOut ) *nFilledOut = 0;
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_fill_enclosed", &s ) ) return 1;
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf xyz, attribs;
+	uint64_t nCells = 0;
+	if( enclosedCellsUnordered( s, xyz, &nCells, st ) ) return 1;
+	if( nCells == 0 ) return 0; // nothing to fill: the handle is not touched
+	REQUIRE( (uint64_t)svo->oct.nVoxels + nCells < 0xFFFFFFFFull, "mvrt_svo_fill_enclosed: %llu voxels and %llu enclosed cells exceed the 32-bit index range of the builder",
+			 (unsigned long long)svo->oct.nVoxels, (unsigned long long)nCells );
+	if( fillAttribHost )
+	{
+		uint2 a;
+		memcpy( &a, fillAttribHost, 8 );
+		if( attribs.alloc( nCells * 8 ) || launchFillAttribs( a, nCells, attribs.as<uint2>(), st ) ) return 1;
+	}
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
+	const mvrt_svo_info& info = svo->oct.info;
+	SvoBuildResult r;
+	int structural = 0;
+	uint32_t he = 0;
+	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nCells, (int)info.gridRes,
+					   svo->oct.buildFlags, st, &r, &structural, &he ) )
+		return 1;
+	REQUIRE( structural, "mvrt_svo_fill_enclosed: internal error: the enclosed cells hold voxels" ); // (every cell is an insert)
+	xyz.release();
+	attribs.release();
+	if( adoptOnOwnGrid( svo, r, svo->oct.buildFlags ) ) return 1;
+	if( nFilledOut ) *nFilledOut = nCells;
+	return 0;
+}
+
+// A coarser level of detail (kernels_coarsen.hip).  Every refusal is made here, on the host: first what the arguments alone decide, then the handle.  The listing
+// reads the sorted codes and the attributes alone; the build hands the list, which stays on the device, to the levels of the voxel-list build.
+static int coarsenSource( const mvrt_svo* svo, const char* who, int levelsDown, uint64_t minCount )
+{
+	REQUIRE( levelsDown >= 1 && levelsDown <= 20, "%s: levelsDown %d is outside [1, log2( gridRes ) - 1] (20 at most, for gridRes 2^21)", who, levelsDown );
+	REQUIRE( minCount >= 1 && minCount <= coarseCellCapacity( levelsDown ), "%s: minCount %llu is outside [1, 8^levelsDown = %llu]", who, (unsigned long long)minCount,
+			 (unsigned long long)coarseCellCapacity( levelsDown ) );
+	REQUIRE( !svo->empty(), "%s: no octree (build first)", who );
+	REQUIRE( svo->oct.morton.p, "%s: an uploaded octree keeps no Morton codes", who );
+	const int L = (int)svo->oct.info.levels;
+	REQUIRE( levelsDown <= L - 1, "%s: levelsDown %d is outside [1, %d] = [1, log2( gridRes ) - 1] for gridRes %u", who, levelsDown, L - 1, svo->oct.info.gridRes );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_coarse_voxels( const mvrt_svo* svo, int levelsDown, uint64_t minCount, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev,
+										uint64_t* nOut, void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_coarse_voxels: null handle" );
+	if( coarsenSource( svo, "mvrt_svo_coarse_voxels", levelsDown, minCount ) ) return 1;
+	const Octree& o = svo->oct;
+	return coarseVoxels( o.morton.as<uint64_t>(), o.attrs.as<uint2>(), o.nVoxels, levelsDown, minCount, capacity, xyzDev, attribsDev, countDev, nOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levelsDown, uint64_t minCount, int buildFlags, void* stream )
+{
+	REQUIRE( src && dst, "mvrt_svo_coarsen: null handle" );
+	REQUIRE( ( buildFlags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0,
+			 "mvrt_svo_coarsen: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", buildFlags );
+	if( coarsenSource( src, "mvrt_svo_coarsen", levelsDown, minCount ) ) return 1;
+	const mvrt_svo_info info = src->oct.info; // (a copy: dst may be src)
+	const float dps = info.dps * (float)( 1u << levelsDown ); // exact: a power of two
+	REQUIRE( dps - dps == 0.0f, "mvrt_svo_coarsen: dps %g times 2^%d is not finite", (double)info.dps, levelsDown );
+	const int gridRes = (int)( info.gridRes >> levelsDown );
+	const uint32_t nFine = src->oct.nVoxels;
+	hipStream_t st = (hipStream_t)stream;
+	if( ownerDrain( dst ) ) return 1; // steps already issued render the old scene
+	SortedVoxels v;
+	if( coarseList( src->oct.morton.as<uint64_t>(), src->oct.attrs.as<uint2>(), nFine, levelsDown, minCount, v, st ) ) return 1;
+	REQUIRE( v.n >= 1, "mvrt_svo_coarsen: minCount %llu would leave no voxel (no coarse cell holds that many of the %u voxels)", (unsigned long long)minCount, nFine );
+	SvoBuildResult r;
+	if( svoBuildFromSorted( v.codes, v.attrs, v.n, gridRes, buildFlags, st, &r ) ) return 1;
+	r.hasEmission = v.hasEmission;
+	r.totalDumped = nFine;
+	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
+	return adoptBuild( dst, r, origin, dps, gridRes, buildFlags ); // (the source is read before the old octree of dst goes)
+}
+
+// Dilation, erosion, closing and opening (kernels_morph.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listings read the
+// sorted codes and the attributes alone; the in-place calls run their steps on sorted lists next to the old octree and build the levels once, from the last list.
+static int morphSource( const mvrt_svo* svo, const char* who, int element, SurfaceSource* s )
+{
+	if( surfaceSource( svo, who, s ) ) return 1;
+	REQUIRE( element == MVRT_MORPH_FACES || element == MVRT_MORPH_CUBE, "%s: unknown element %d (MVRT_MORPH_FACES = 0, MVRT_MORPH_CUBE = 1)", who, element );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_dilation_cells( const mvrt_svo* svo, int element, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, uint64_t* nOut,
+										 void* stream )
+{
+	SurfaceSource s;
+	if( morphSource( svo, "mvrt_svo_dilation_cells", element, &s ) ) return 1;
+	return morphDilationCells( s, element, capacity, xyzDev, attribsDev, countDev, nOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_erosion_voxels( const mvrt_svo* svo, int element, uint64_t capacity, uint32_t* vIndexDev, uint64_t* nOut, void* stream )
+{
+	SurfaceSource s;
+	if( morphSource( svo, "mvrt_svo_erosion_voxels", element, &s ) ) return 1;
+	return morphErosionVoxels( s, element, capacity, vIndexDev, nOut, (hipStream_t)stream );
+}
+// the out-count of the morphological in-place calls: the voxels added or removed (0, as preset, when nothing changed)
+static void countChange( uint32_t nOld, uint32_t n, uint64_t* nChangedOut )
+{
+	if( nChangedOut ) *nChangedOut = n > nOld ? n - nOld : nOld - n;
+}
+static int morphInPlace( mvrt_svo* svo, const char* who, int op, int element, int steps, uint64_t* nChangedOut, void* stream )
+{
+	if( nChangedOut ) *nChangedOut = 0;
+	SurfaceSource s;
+	if( morphSource( svo, who, element, &s ) ) return 1;
+	REQUIRE( steps >= 1 && steps <= 64, "%s: steps %d is outside [1, 64]", who, steps );
+	hipStream_t st = (hipStream_t)stream;
+	SortedVoxels v;
+	if( morphList( who, s, element, op, steps, v, st ) || adoptSorted( svo, v, st ) ) return 1;
+	countChange( s.nVoxels, v.n, nChangedOut );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_dilate( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_dilate", MVRT_MORPH_OP_DILATE, element, steps, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_erode( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_erode", MVRT_MORPH_OP_ERODE, element, steps, nRemovedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_close( mvrt_svo* svo, int element, int steps, uint64_t* nAddedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_close", MVRT_MORPH_OP_CLOSE, element, steps, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_open( mvrt_svo* svo, int element, int steps, uint64_t* nRemovedOut, void* stream )
+{
+	return morphInPlace( svo, "mvrt_svo_open", MVRT_MORPH_OP_OPEN, element, steps, nRemovedOut, stream );
+}
+
+// Round offsets (kernels_ball.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listings read the sorted codes and the
+// attributes alone; the in-place calls run their halves on sorted lists next to the old octree and build the levels once, as the morphology above does.
+static int ballSource( const mvrt_svo* svo, const char* who, uint32_t radius2, SurfaceSource* s )
+{
+	if( surfaceSource( svo, who, s ) ) return 1;
+	REQUIRE( radius2 >= 1u && radius2 <= 1024u, "%s: radius2 %u is outside [1, 1024]", who, radius2 );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_distance_cells( const mvrt_svo* svo, uint32_t radius2, uint64_t capacity, uint32_t* xyzDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev,
+										 uint64_t* nOut, void* stream )
+{
+	SurfaceSource s;
+	if( ballSource( svo, "mvrt_svo_distance_cells", radius2, &s ) ) return 1;
+	return ballDistanceCells( s, radius2, capacity, xyzDev, dist2Dev, nearestDev, attribsDev, nOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_depth_voxels( const mvrt_svo* svo, uint32_t radius2, uint64_t capacity, uint32_t* vIndexDev, uint32_t* depth2Dev, uint64_t* nOut, void* stream )
+{
+	SurfaceSource s;
+	if( ballSource( svo, "mvrt_svo_depth_voxels", radius2, &s ) ) return 1;
+	return ballDepthVoxels( s, radius2, capacity, vIndexDev, depth2Dev, nOut, (hipStream_t)stream );
+}
+static int ballInPlace( mvrt_svo* svo, const char* who, int op, uint32_t radius2, uint64_t* nChangedOut, void* stream )
+{
+	if( nChangedOut ) *nChangedOut = 0;
+	SurfaceSource s;
+	if( ballSource( svo, who, radius2, &s ) ) return 1;
+	hipStream_t st = (hipStream_t)stream;
+	SortedVoxels v;
+	if( ballList( who, s, radius2, op, v, st ) || adoptSorted( svo, v, st ) ) return 1;
+	countChange( s.nVoxels, v.n, nChangedOut );
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_dilate_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nAddedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_dilate_ball", MVRT_MORPH_OP_DILATE, radius2, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_erode_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nRemovedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_erode_ball", MVRT_MORPH_OP_ERODE, radius2, nRemovedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_close_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nAddedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_close_ball", MVRT_MORPH_OP_CLOSE, radius2, nAddedOut, stream );
+}
+MVRT_EXPORT int mvrt_svo_open_ball( mvrt_svo* svo, uint32_t radius2, uint64_t* nRemovedOut, void* stream )
+{
+	return ballInPlace( svo, "mvrt_svo_open_ball", MVRT_MORPH_OP_OPEN, radius2, nRemovedOut, stream );
+}
+MVRT_EXPORT int mvrt_test_peak_bytes( uint64_t* peakOut, int reset )
+{
+	if( peakOut ) *peakOut = g_devBufState.peakBytes;
+	if( reset ) g_devBufState.peakBytes = g_devBufState.liveBytes.load();
+	return 0;
+}
+MVRT_EXPORT int mvrt_test_ball_stats( uint64_t out[5] )
+{
+	const BallStats b = ballLastStats();
+	REQUIRE( out, "mvrt_test_ball_stats: null out" );
+	for( int k = 0; k < 3; k++ ) out[k] = b.records[k];
+	out[3] = b.seeds;
+	out[4] = b.cells;
+	return 0;
+}
+
+// Connected components (kernels_components.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listing reads the sorted codes
+// alone; the in-place call compacts the kept voxels next to the old octree and builds the levels once, as the opening does.  The handle and the element are
+// checked by morphSource: the connectivity is a structuring element.
+MVRT_EXPORT int mvrt_svo_components( const mvrt_svo* svo, int element, uint32_t* labelDev, uint64_t componentCapacity, uint32_t* sizeDev, uint32_t* firstDev, uint32_t* boxDev,
+									 uint64_t* nComponentsOut, uint64_t* largestOut, void* stream )
+{
+	SurfaceSource s;
+	if( morphSource( svo, "mvrt_svo_components", element, &s ) ) return 1;
+	return componentsList( s, element, labelDev, componentCapacity, sizeDev, firstDev, boxDev, nComponentsOut, largestOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_keep_components( mvrt_svo* svo, int element, uint64_t minVoxels, uint32_t keepLargest, uint64_t* nRemovedOut, uint64_t* nKeptOut, void* stream )
+{
+	const char* who = "mvrt_svo_keep_components";
+	if( nRemovedOut ) *nRemovedOut = 0;
+	if( nKeptOut ) *nKeptOut = 0;
+	SurfaceSource s;
+	if( morphSource( svo, who, element, &s ) ) return 1;
+	REQUIRE( minVoxels >= 1, "%s: minVoxels 0 (1 keeps every component)", who );
+	hipStream_t st = (hipStream_t)stream;
+	SortedVoxels v;
+	uint32_t nComponents = 0, nKept = 0;
+	if( componentsKeepList( s, element, minVoxels, keepLargest, v, &nComponents, &nKept, st ) ) return 1;
+	REQUIRE( nKept >= 1, "%s: minVoxels %llu would leave no voxel (the largest of the %u components is smaller)", who, (unsigned long long)minVoxels, nComponents );
+	if( adoptSorted( svo, v, st ) ) return 1; // (every component kept: the list is unchanged and the handle is not touched)
+	if( nRemovedOut ) *nRemovedOut = s.nVoxels - v.n;
+	if( nKeptOut ) *nKeptOut = nKept;
+	return 0;
+}
+
+// Two voxel sets (kernels_combine.hip).  Every refusal the arguments and the handles decide is made here, on the host.  The listing reads the sorted codes and the
+// attributes of both handles; the in-place call emits the result next to the old octree and builds the levels once, as the opening does.
+static_assert( MVRT_COMBINE_UNION == MVRT_COMBINE_OP_UNION && MVRT_COMBINE_INTERSECTION == MVRT_COMBINE_OP_INTERSECTION && MVRT_COMBINE_DIFFERENCE == MVRT_COMBINE_OP_DIFFERENCE &&
+				   MVRT_COMBINE_XOR == MVRT_COMBINE_OP_XOR && (int)MVRT_COMBINE_ATTRIB_B == MVRT_COMBINE_FLAG_ATTRIB_B,
+			   "mvrt.h and launch.h number the operators alike" );
+static int combineSources( const mvrt_svo* a, const mvrt_svo* b, const char* who, int op, const int32_t offset[3], uint32_t flags, SurfaceSource* sa, SurfaceSource* sb, int32_t o[3] )
+{
+	if( surfaceSource( a, who, sa ) ) return 1;
+	REQUIRE( b, "%s: null handle b", who );
+	REQUIRE( !b->empty(), "%s: b holds no octree (build first)", who );
+	REQUIRE( b->oct.morton.p, "%s: b is an uploaded octree, which keeps no Morton codes", who );
+	if( surfaceSource( b, who, sb ) ) return 1;
+	REQUIRE( op >= MVRT_COMBINE_UNION && op <= MVRT_COMBINE_XOR, "%s: unknown op %d (MVRT_COMBINE_UNION = 0, _INTERSECTION = 1, _DIFFERENCE = 2, _XOR = 3)", who, op );
+	REQUIRE( ( flags & ~(uint32_t)MVRT_COMBINE_ATTRIB_B ) == 0, "%s: unknown flags 0x%x (MVRT_COMBINE_ATTRIB_B only)", who, flags );
+	for( int k = 0; k < 3; k++ )
+	{
+		o[k] = offset ? offset[k] : 0;
+		REQUIRE( o[k] >= -( 1 << 21 ) && o[k] <= ( 1 << 21 ), "%s: offset[%d] = %d is outside [-2^21, 2^21]", who, k, o[k] );
+	}
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_combine_voxels( const mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t capacity, uint32_t* xyzDev,
+										 uint32_t* attribsDev, uint8_t* sourceDev, uint64_t* nOut, uint64_t* nOverlapOut, uint64_t* nClippedOut, void* stream )
+{
+	SurfaceSource sa, sb;
+	int32_t o[3];
+	if( combineSources( a, b, "mvrt_svo_combine_voxels", op, offset, flags, &sa, &sb, o ) ) return 1;
+	return combineVoxels( sa, sb, op, o, flags, capacity, xyzDev, attribsDev, sourceDev, nOut, nOverlapOut, nClippedOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t* nAddedOut, uint64_t* nRemovedOut,
+								  uint64_t* nClippedOut, void* stream )
+{
+	const char* who = "mvrt_svo_combine";
+	if( nAddedOut ) *nAddedOut = 0;
+	if( nRemovedOut ) *nRemovedOut = 0;
+	if( nClippedOut ) *nClippedOut = 0;
+	SurfaceSource sa, sb;
+	int32_t o[3];
+	if( combineSources( a, b, who, op, offset, flags, &sa, &sb, o ) ) return 1;
+	hipStream_t st = (hipStream_t)stream;
+	CombineCounts c;
+	if( combineList( who, sa, sb, op, o, flags, &c, st ) ) return 1;
+	if( nClippedOut ) *nClippedOut = c.nClipped;
+	if( c.nAdded == 0 && c.nRemoved == 0 ) // the node structure stays
+	{
+		if( !c.recolours ) return 0; // nothing changes: the handle is not touched
+		if( ownerDrain( a ) ) return 1; // steps already issued render the old scene; a recolouring writes in place
+		MVRT_HIP( hipMemcpyAsync( a->oct.attrs.p, c.list.attrs.p, (uint64_t)c.list.n * 8, hipMemcpyDeviceToDevice, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+		a->oct.totalDumped = 0;
+		a->oct.hasEmission = c.list.hasEmission;
+		return 0;
+	}
+	if( adoptSorted( a, c.list, st ) ) return 1; // (b == a was read above)
+	if( nAddedOut ) *nAddedOut = c.nAdded;
+	if( nRemovedOut ) *nRemovedOut = c.nRemoved;
+	return 0;
+}

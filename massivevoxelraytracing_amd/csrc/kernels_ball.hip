@@ -11,7 +11,7 @@
 //   dilate   seeds = the voxels with an empty in-grid face neighbour (the nearest voxel of an empty cell is one of them), payload = vIndex.  The band minus the
 //            cells of the set (one search each), scanned and scattered: code, d2, nearest voxel and its attribute with both alpha bytes 255.
 //   erode    seeds = the cells of one FACES dilation step (the nearest empty cell of a voxel is one of them; morphStepCodes, kernels_morph.hip), no payload.  Every
-//            voxel looks itself up in the band: found = its depth is <= rho.  The erosion's scan and scatter follow (morphCompactKept).
+//            voxel looks itself up in the band: found = its depth is <= rho.  The erosion's scan and scatter follow (compactUnmasked, kernels_list.hip).
 // No floating point, no atomics.
 #include "launch.h"
 #include "voxel_passes.h"
@@ -271,22 +271,6 @@ int depthBand( const char* who, const uint64_t* codes, const uint2* attrs, uint3
 	return exclusiveOffsets<uint32_t>( shallow, (uint64_t)n + 1, offs, nShallow, st ); // (has waited: the band is released on return)
 }
 
-// the list a call works on: the handle's arrays first (not owned), then the arrays the last half made
-struct VoxelList
-{
-	const uint64_t* codes;
-	const uint2* attrs;
-	uint32_t n;
-	DevBuf ownCodes, ownAttrs;
-	void take( DevBuf& c, DevBuf& a, uint32_t count )
-	{
-		ownCodes = std::move( c );
-		ownAttrs = std::move( a );
-		codes = ownCodes.as<uint64_t>();
-		attrs = ownAttrs.as<uint2>();
-		n = count;
-	}
-};
 int dilateHalf( const char* who, VoxelList& l, uint32_t levels, uint32_t rho, hipStream_t st )
 {
 	DevBuf newCodes, newAttrs, codes, attrs;
@@ -305,14 +289,15 @@ int dilateHalf( const char* who, VoxelList& l, uint32_t levels, uint32_t rho, hi
 		if( launchNewCells( c, l.attrs, newCodes.as<uint64_t>(), nullptr, nullptr, nullptr, newAttrs.as<uint32_t>(), st ) ) return 1;
 		MVRT_HIP( hipStreamSynchronize( st ) ); // (the band is released here)
 	}
-	if( morphMergeLists( l.codes, l.attrs, l.n, newCodes.as<uint64_t>(), newAttrs.as<uint2>(), nNew, codes, attrs, st ) ) return 1;
+	if( mergeLists( l.codes, l.attrs, l.n, newCodes.as<uint64_t>(), newAttrs.as<uint2>(), nNew, codes, attrs, st ) ) return 1;
 	l.take( codes, attrs, l.n + nNew );
 	return 0;
 }
 int erodeHalf( const char* who, VoxelList& l, uint32_t levels, uint32_t rho, hipStream_t st )
 {
-	DevBuf depth, offs, codes, attrs;
-	uint32_t nShallow = 0, nKept = 0, he = 0;
+	DevBuf depth, offs;
+	SortedVoxels kept;
+	uint32_t nShallow = 0;
 	if( depthBand( who, l.codes, l.attrs, l.n, levels, rho, depth, offs, &nShallow, st ) ) return 1;
 	if( nShallow == 0 ) return 0;
 	if( nShallow == l.n )
@@ -321,8 +306,8 @@ int erodeHalf( const char* who, VoxelList& l, uint32_t levels, uint32_t rho, hip
 		return 1;
 	}
 	offs.release();
-	if( morphCompactKept( l.codes, l.attrs, depth.as<uint32_t>(), l.n, codes, attrs, &nKept, &he, st ) ) return 1;
-	l.take( codes, attrs, nKept );
+	if( compactUnmasked( l.codes, l.attrs, depth.as<uint32_t>(), l.n, true, kept, st ) ) return 1;
+	l.take( kept.codes, kept.attrs, kept.n );
 	return 0;
 }
 } // namespace
@@ -335,13 +320,8 @@ int ballDistanceCells( const SurfaceSource& s, uint32_t radius2, uint64_t capaci
 	NewCells c;
 	if( dilationBand( "mvrt_svo_distance_cells", s.morton, s.nVoxels, s.levels, radius2, &c, st ) ) return 1;
 	if( nOut ) *nOut = c.nNew;
-	if( !xyzDev && !dist2Dev && !nearestDev && !attribsDev ) return 0; // the sizing call
-	if( capacity < c.nNew )
-	{
-		mvrtSetError( "mvrt_svo_distance_cells: capacity %llu is smaller than the %u cells; nothing was written", (unsigned long long)capacity, c.nNew );
-		return 1;
-	}
-	if( c.nNew == 0 ) return 0;
+	const int tail = listingTail( "mvrt_svo_distance_cells", "capacity", "cells", !xyzDev && !dist2Dev && !nearestDev && !attribsDev, capacity, c.nNew );
+	if( tail != LISTING_WRITE ) return tail;
 	// (the caller's arrays are written by this launch alone, behind every allocation and check)
 	if( launchNewCells( c, s.attrs, nullptr, xyzDev, dist2Dev, nearestDev, attribsDev, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
@@ -354,13 +334,8 @@ int ballDepthVoxels( const SurfaceSource& s, uint32_t radius2, uint64_t capacity
 	uint32_t nShallow = 0;
 	if( depthBand( "mvrt_svo_depth_voxels", s.morton, s.attrs, s.nVoxels, s.levels, radius2, depth, offs, &nShallow, st ) ) return 1;
 	if( nOut ) *nOut = nShallow;
-	if( !vIndexDev && !depth2Dev ) return 0; // the sizing call
-	if( capacity < nShallow )
-	{
-		mvrtSetError( "mvrt_svo_depth_voxels: capacity %llu is smaller than the %u voxels; nothing was written", (unsigned long long)capacity, nShallow );
-		return 1;
-	}
-	if( nShallow == 0 ) return 0;
+	const int tail = listingTail( "mvrt_svo_depth_voxels", "capacity", "voxels", !vIndexDev && !depth2Dev, capacity, nShallow );
+	if( tail != LISTING_WRITE ) return tail;
 	// (the caller's arrays are written by this launch alone, behind every allocation and check)
 	hipLaunchKernelGGL( kBallDepthList, dim3( divUp( s.nVoxels, BB ) ), dim3( BB ), 0, st, depth.as<uint32_t>(), offs.as<uint32_t>(), s.nVoxels, vIndexDev, depth2Dev );
 	MVRT_HIP( hipGetLastError() );
@@ -368,35 +343,10 @@ int ballDepthVoxels( const SurfaceSource& s, uint32_t radius2, uint64_t capacity
 	return 0;
 }
 
-int ballList( const char* who, const SurfaceSource& s, uint32_t radius2, int op, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission, hipStream_t st )
+int ballList( const char* who, const SurfaceSource& s, uint32_t radius2, int op, SortedVoxels& out, hipStream_t st )
 {
-	VoxelList l;
-	l.codes = s.morton;
-	l.attrs = s.attrs;
-	l.n = s.nVoxels;
-	*nOut = s.nVoxels;
-	*hasEmission = 0;
-	// the halves of a call: one dilation, one erosion or both, in the order of the operator; a first half that changes nothing leaves nothing to the second
-	const bool dilateFirst = op == MVRT_MORPH_OP_DILATE || op == MVRT_MORPH_OP_CLOSE;
-	const int halves = op == MVRT_MORPH_OP_CLOSE || op == MVRT_MORPH_OP_OPEN ? 2 : 1;
-	for( int h = 0; h < halves; h++ )
-	{
-		const bool dilate = ( h == 0 ) == dilateFirst;
-		if( dilate ? dilateHalf( who, l, s.levels, radius2, st ) : erodeHalf( who, l, s.levels, radius2, st ) ) return 1;
-		if( l.n == s.nVoxels && h == 0 ) return 0;
-	}
-	*nOut = l.n;
-	// dilation grows, erosion shrinks, a closing holds the set and an opening lies in it: the same count is the same set, with the same bytes
-	if( l.n == s.nVoxels ) return 0;
-	if( op == MVRT_MORPH_OP_OPEN ) // a pure removal: the original bytes, not the nearest voxel's of the dilation half
-	{
-		DevBuf original;
-		if( morphGatherAttrs( l.codes, l.n, s.morton, s.attrs, s.nVoxels, original, st ) ) return 1;
-		l.ownAttrs = std::move( original );
-		l.attrs = l.ownAttrs.as<uint2>();
-	}
-	if( morphAnyEmission( l.attrs, l.n, hasEmission, st ) ) return 1;
-	codes = std::move( l.ownCodes );
-	attribs = std::move( l.ownAttrs );
-	return 0;
+	// one dilation, one erosion or both; a first half that changes nothing leaves nothing to the second
+	const uint32_t levels = s.levels;
+	return runListOperator(
+		op, s, true, [=]( VoxelList& l ) { return dilateHalf( who, l, levels, radius2, st ); }, [=]( VoxelList& l ) { return erodeHalf( who, l, levels, radius2, st ); }, out, st );
 }

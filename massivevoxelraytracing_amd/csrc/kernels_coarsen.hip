@@ -270,32 +270,26 @@ int coarseVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, int le
 	Reduced r;
 	if( reduceCells( morton, attrs, n, (uint32_t)levelsDown, minCount, !fill, &r, st ) ) return 1;
 	if( nOut ) *nOut = r.nKept;
-	if( !fill ) return 0; // the sizing call
-	if( capacity < r.nKept )
-	{
-		mvrtSetError( "mvrt_svo_coarse_voxels: capacity %llu is smaller than the %u coarse voxels; nothing was written", (unsigned long long)capacity, r.nKept );
-		return 1;
-	}
-	if( r.nKept == 0 ) return 0;
+	const int tail = listingTail( "mvrt_svo_coarse_voxels", "capacity", "coarse voxels", !fill, capacity, r.nKept );
+	if( tail != LISTING_WRITE ) return tail;
 	// (the caller's arrays are written by this launch alone, behind every allocation and check)
 	if( launchEmit( r, minCount, nullptr, attribsDev, countDev, xyzDev, nullptr, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }
 
-int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
-				hipStream_t st )
+int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, SortedVoxels& out, hipStream_t st )
 {
 	Reduced r;
 	if( reduceCells( morton, attrs, n, (uint32_t)levelsDown, minCount, false, &r, st ) ) return 1;
-	*nKept = r.nKept;
-	*hasEmission = 0;
+	out.n = r.nKept;
+	out.hasEmission = 0;
 	if( r.nKept == 0 ) return 0;
 	DevBuf flag;
-	if( codes.alloc( (uint64_t)r.nKept * 8 ) || attribs.alloc( (uint64_t)r.nKept * 8 ) || flag.alloc( 4 ) ) return 1;
+	if( out.codes.alloc( (uint64_t)r.nKept * 8 ) || out.attrs.alloc( (uint64_t)r.nKept * 8 ) || flag.alloc( 4 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( flag.p, 0, 4, st ) );
-	if( launchEmit( r, minCount, codes.as<uint64_t>(), attribs.as<uint32_t>(), nullptr, nullptr, flag.as<uint32_t>(), st ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( hasEmission, flag.p, 4, hipMemcpyDeviceToHost, st ) );
+	if( launchEmit( r, minCount, out.codes.as<uint64_t>(), out.attrs.as<uint32_t>(), nullptr, nullptr, flag.as<uint32_t>(), st ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( &out.hasEmission, flag.p, 4, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }

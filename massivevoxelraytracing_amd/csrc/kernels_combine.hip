@@ -7,7 +7,7 @@
 //   classify   one thread per entry of A and one per entry of B': its lower bound in the other list (the partner position, one search of the whole list), whether
 //              the code stands there (the overlap) and whether the entry survives the operator.  A voxel of the overlap survives as the entry of A, never as that of B'.
 //   emit       exclusive scans of the survive flags of both lists; a survivor goes to its own offset plus the offset of the other list at its partner position
-//              (the rule of kMorphMerge with holes).  One scatter writes code or coordinates, attribute and source byte, and ORs the emission flag once per wave.
+//              (the rule of kListMerge with holes).  One scatter writes code or coordinates, attribute and source byte, and ORs the emission flag once per wave.
 // No floating point, no atomics but that OR.
 #include "launch.h"
 #include "voxel_passes.h"
@@ -248,30 +248,25 @@ int combineVoxels( const SurfaceSource& a, const SurfaceSource& b, int op, const
 	if( nOut ) *nOut = p.n;
 	if( nOverlapOut ) *nOverlapOut = p.nOverlap;
 	if( nClippedOut ) *nClippedOut = p.nClipped;
-	if( !xyzDev && !attribsDev && !sourceDev ) return 0; // the sizing call
-	if( capacity < p.n )
-	{
-		mvrtSetError( "mvrt_svo_combine_voxels: capacity %llu is smaller than the %llu voxels; nothing was written", (unsigned long long)capacity, (unsigned long long)p.n );
-		return 1;
-	}
-	if( p.n == 0 ) return 0;
+	const int tail = listingTail( "mvrt_svo_combine_voxels", "capacity", "voxels", !xyzDev && !attribsDev && !sourceDev, capacity, p.n );
+	if( tail != LISTING_WRITE ) return tail;
 	// (the caller's arrays are written by this launch alone, behind every allocation and check)
 	if( launchEmit( p, flags & MVRT_COMBINE_FLAG_ATTRIB_B, nullptr, attribsDev, xyzDev, sourceDev, nullptr, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }
 
-int combineList( const char* who, const SurfaceSource& a, const SurfaceSource& b, int op, const int32_t o[3], uint32_t flags, DevBuf& codes, DevBuf& attribs, CombineCounts* c,
-				 hipStream_t st )
+int combineList( const char* who, const SurfaceSource& a, const SurfaceSource& b, int op, const int32_t o[3], uint32_t flags, CombineCounts* c, hipStream_t st )
 {
 	Plan p;
 	if( makePlan( a, b, op, o, &p, st ) ) return 1;
-	c->n = p.n;
+	SortedVoxels& out = c->list;
+	out.n = a.nVoxels;
+	out.hasEmission = 0;
 	c->nAdded = p.cb.nLives;
 	c->nRemoved = a.nVoxels - p.ca.nLives;
 	c->nOverlap = p.nOverlap;
 	c->nClipped = p.nClipped;
-	c->hasEmission = 0;
 	const bool keepsOverlap = op == MVRT_COMBINE_OP_UNION || op == MVRT_COMBINE_OP_INTERSECTION;
 	c->recolours = ( flags & MVRT_COMBINE_FLAG_ATTRIB_B ) && keepsOverlap && p.nOverlap > 0 ? 1u : 0u;
 	if( c->nAdded == 0 && c->nRemoved == 0 && !c->recolours ) return 0; // nothing changes
@@ -285,12 +280,13 @@ int combineList( const char* who, const SurfaceSource& a, const SurfaceSource& b
 		mvrtSetError( "%s: the result would hold %llu voxels, beyond the 32-bit index range of the builder", who, (unsigned long long)p.n );
 		return 1;
 	}
+	out.n = (uint32_t)p.n;
 	DevBuf flag;
 	const bool structural = c->nAdded != 0 || c->nRemoved != 0; // else the codes are a's own: the attributes alone
-	if( ( structural && codes.alloc( p.n * 8 ) ) || attribs.alloc( p.n * 8 ) || flag.alloc( 4 ) ) return 1;
+	if( ( structural && out.codes.alloc( p.n * 8 ) ) || out.attrs.alloc( p.n * 8 ) || flag.alloc( 4 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( flag.p, 0, 4, st ) );
-	if( launchEmit( p, c->recolours, structural ? codes.as<uint64_t>() : nullptr, attribs.as<uint32_t>(), nullptr, nullptr, flag.as<uint32_t>(), st ) ) return 1;
-	MVRT_HIP( hipMemcpyAsync( &c->hasEmission, flag.p, 4, hipMemcpyDeviceToHost, st ) );
+	if( launchEmit( p, c->recolours, structural ? out.codes.as<uint64_t>() : nullptr, out.attrs.as<uint32_t>(), nullptr, nullptr, flag.as<uint32_t>(), st ) ) return 1;
+	MVRT_HIP( hipMemcpyAsync( &out.hasEmission, flag.p, 4, hipMemcpyDeviceToHost, st ) );
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }

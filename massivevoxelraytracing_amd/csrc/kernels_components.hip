@@ -14,7 +14,7 @@
 //            moves.  Every turn retires at least that first lane.  Nearly all voxels of a real scene belong to one component: per-voxel atomics would
 //            serialise on one address.
 //   select   (in place) the keys ( ~size ) << 32 | label radix-sorted: position = rank by (size descending, label ascending).  One keep flag per component,
-//            gathered per voxel as a drop mask, then the erosion's scan and scatter (morphCompactKept, kernels_morph.hip).
+//            gathered per voxel as a drop mask, then the erosion's scan and scatter (compactUnmasked, kernels_list.hip).
 // No LDS beyond hipcub's, no floating point.
 #include "launch.h"
 #include "voxel_passes.h"
@@ -215,7 +215,7 @@ int componentsList( const SurfaceSource& s, int element, uint32_t* labelDev, uin
 	if( !labelDev && !sizeDev && !firstDev && !boxDev ) return 0; // the sizing call
 	if( !fits && ( sizeDev || firstDev || boxDev ) )
 	{
-		mvrtSetError( "mvrt_svo_components: componentCapacity %llu is smaller than the %u components; nothing was written", (unsigned long long)capacity, nc );
+		listingRefusal( "mvrt_svo_components", "componentCapacity", "components", capacity, nc );
 		return 1;
 	}
 	// (the caller's arrays are written from here on, behind every allocation and check)
@@ -230,15 +230,15 @@ int componentsList( const SurfaceSource& s, int element, uint32_t* labelDev, uin
 	return 0;
 }
 
-int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels, uint32_t keepLargest, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission,
-						uint32_t* nComponents, uint32_t* nKeptComponents, hipStream_t st )
+int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels, uint32_t keepLargest, SortedVoxels& out, uint32_t* nComponents, uint32_t* nKeptComponents,
+						hipStream_t st )
 {
 	Labelled l;
 	if( labelComponents( s, element, &l, st ) ) return 1;
 	const uint32_t nc = l.nComponents;
 	*nComponents = nc;
-	*nOut = s.nVoxels;
-	*hasEmission = 0;
+	out.n = s.nVoxels;
+	out.hasEmission = 0;
 	DevBuf drop;
 	{
 		DevBuf size, keys, sorted, keep, count;
@@ -259,7 +259,7 @@ int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels,
 		if( *nKeptComponents == nc ) return 0; // nothing goes
 		if( *nKeptComponents == 0 )
 		{
-			*nOut = 0;
+			out.n = 0;
 			return 0; // (the caller refuses)
 		}
 		if( drop.alloc( (uint64_t)s.nVoxels * 4 ) ) return 1;
@@ -269,5 +269,5 @@ int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels,
 		MVRT_HIP( hipStreamSynchronize( st ) ); // (keep is released at scope end)
 	}
 	l = Labelled();
-	return morphCompactKept( s.morton, s.attrs, drop.as<uint32_t>(), s.nVoxels, codes, attribs, nOut, hasEmission, st );
+	return compactUnmasked( s.morton, s.attrs, drop.as<uint32_t>(), s.nVoxels, true, out, st );
 }

@@ -275,13 +275,8 @@ int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, 
 		mvrtSetError( "mvrt_svo_enclosed_cells: the %llu enclosed cells are 2^32 or more, beyond what one listing holds; nothing was written", (unsigned long long)c.nCells );
 		return 1;
 	}
-	if( capacity < c.nCells )
-	{
-		mvrtSetError( "mvrt_svo_enclosed_cells: capacity %llu is smaller than the %llu enclosed cells; nothing was written", (unsigned long long)capacity,
-					  (unsigned long long)c.nCells );
-		return 1;
-	}
-	if( c.nCells == 0 ) return 0;
+	const int tail = listingTail( "mvrt_svo_enclosed_cells", "capacity", "enclosed cells", false, capacity, c.nCells );
+	if( tail != LISTING_WRITE ) return tail;
 	const uint32_t nCells = (uint32_t)c.nCells;
 	DevBuf codesA, rootsA, codes, roots, firstCell, rank1;
 	if( codesA.alloc( c.nCells * 8 ) || rootsA.alloc( c.nCells * 4 ) ) return 1;

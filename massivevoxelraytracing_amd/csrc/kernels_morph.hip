@@ -8,12 +8,11 @@
 //            channels of its sources and emits code, coarseAttrib( sums, count ) and count at the run's rank -- integer sums, so the order inside a run does not
 //            matter.  The new cells and the old list, both sorted and disjoint, are merged by ranks: an entry goes to its own index plus lowerBound in the other
 //            list.  The next step gets a sorted unique list; nothing is sorted but the records.
-//   erode    an exclusive scan of the keep flags and one scatter.
-// No floating point, no atomics but the one-per-wave OR of the emission flag.
+//   erode    an exclusive scan of the keep flags and one scatter (compactUnmasked).
+// The merge, the compaction and the operator's frame (halves, unchanged test, emission scan) are the list steps of kernels_list.hip.  No floating point, no atomics.
 #include "launch.h"
 #include "voxel_passes.h"
 
-#define WAVE 64
 #define MB 256 // threads per workgroup = items per workgroup of the run expansion
 
 namespace
@@ -28,12 +27,6 @@ struct MaskLength // scan input: the records of voxel i (item n: 0)
 	const uint32_t* mask;
 	uint32_t n;
 	__host__ __device__ uint64_t operator()( uint32_t i ) const { return i < n ? (uint64_t)__builtin_popcount( mask[i] ) : 0ull; }
-};
-struct MaskFlag // scan input: 1 where voxel i has ( removed = 1 ) or has not ( removed = 0 ) an empty in-grid neighbour (item n: 0)
-{
-	const uint32_t* mask;
-	uint32_t n, removed;
-	__host__ __device__ uint32_t operator()( uint32_t i ) const { return i < n && ( mask[i] != 0u ) == ( removed != 0u ) ? 1u : 0u; }
 };
 struct RecordHead // scan input: 1 where sorted record i starts a new cell
 {
@@ -101,60 +94,6 @@ __global__ void __launch_bounds__( MB ) kMorphCells( const uint64_t* __restrict_
 	if( xyzOut ) mortonDecode( key, xyzOut[d * 3], xyzOut[d * 3 + 1], xyzOut[d * 3 + 2] );
 }
 
-// two sorted lists without a common code -> one: an entry's place is its own index plus the number of entries of the other list below it
-__global__ void __launch_bounds__( MB ) kMorphMerge( const uint64_t* __restrict__ aCodes, const uint2* __restrict__ aAttrs, uint32_t nA, const uint64_t* __restrict__ bCodes,
-													  const uint2* __restrict__ bAttrs, uint32_t nB, uint64_t* __restrict__ codes, uint2* __restrict__ attrs )
-{
-	const uint64_t i = (uint64_t)blockIdx.x * MB + threadIdx.x;
-	if( i >= (uint64_t)nA + nB ) return;
-	uint64_t c, d;
-	uint2 a;
-	if( i < nA )
-	{
-		c = aCodes[i];
-		a = aAttrs[i];
-		d = i + lowerBound( bCodes, 0, nB, c );
-	}
-	else
-	{
-		const uint64_t j = i - nA;
-		c = bCodes[j];
-		a = bAttrs[j];
-		d = j + lowerBound( aCodes, 0, nA, c );
-	}
-	codes[d] = c;
-	attrs[d] = a;
-}
-
-// offs: the exclusive sums of MaskFlag.  The flagged voxels, in order: their code and attribute (a step) or their index (the listing); any output may be null
-__global__ void __launch_bounds__( MB ) kMorphCompact( const uint64_t* __restrict__ codes, const uint2* __restrict__ attrs, const uint32_t* __restrict__ mask,
-														const uint32_t* __restrict__ offs, uint32_t n, uint32_t removed, uint64_t* __restrict__ codesOut,
-														uint2* __restrict__ attrsOut, uint32_t* __restrict__ vIndexOut )
-{
-	const uint64_t i = (uint64_t)blockIdx.x * MB + threadIdx.x;
-	if( i >= n || ( mask[i] != 0u ) != ( removed != 0u ) ) return;
-	const uint32_t d = offs[i];
-	if( codesOut ) codesOut[d] = codes[i];
-	if( attrsOut ) attrsOut[d] = attrs[i];
-	if( vIndexOut ) vIndexOut[d] = (uint32_t)i;
-}
-
-// codes: a subset of srcCodes.  attrsOut[i] = the attribute the code has there
-__global__ void __launch_bounds__( MB ) kMorphGatherAttrs( const uint64_t* __restrict__ codes, uint32_t n, const uint64_t* __restrict__ srcCodes,
-															const uint2* __restrict__ srcAttrs, uint32_t nSrc, uint2* __restrict__ attrsOut )
-{
-	const uint64_t i = (uint64_t)blockIdx.x * MB + threadIdx.x;
-	if( i >= n ) return;
-	const uint64_t j = lowerBound( srcCodes, 0, nSrc, codes[i] );
-	attrsOut[i] = srcAttrs[j < nSrc ? j : nSrc - 1u];
-}
-__global__ void __launch_bounds__( MB ) kMorphAnyEmission( const uint2* __restrict__ attrs, uint32_t n, uint32_t* __restrict__ hasEmission )
-{
-	const uint64_t i = (uint64_t)blockIdx.x * MB + threadIdx.x;
-	const uint32_t em = i < n ? attrs[i].y & 0xFFFFFFu : 0u;
-	if( __ballot( em ) && ( threadIdx.x & ( WAVE - 1 ) ) == 0 ) atomicOr( hasEmission, 1u );
-}
-
 int launchMasks( const uint64_t* codes, uint32_t n, uint32_t levels, int element, DevBuf& mask, hipStream_t st )
 {
 	if( mask.alloc( (uint64_t)n * 4 ) ) return 1;
@@ -202,22 +141,6 @@ int launchCells( const Records& r, const uint2* attrs, uint64_t* codes, uint32_t
 	return 0;
 }
 
-// the list a sequence of steps works on: the handle's arrays first (not owned), then the arrays the last step made
-struct VoxelList
-{
-	const uint64_t* codes;
-	const uint2* attrs;
-	uint32_t n;
-	DevBuf ownCodes, ownAttrs;
-	void take( DevBuf& c, DevBuf& a, uint32_t count )
-	{
-		ownCodes = std::move( c );
-		ownAttrs = std::move( a );
-		codes = ownCodes.as<uint64_t>();
-		attrs = ownAttrs.as<uint2>();
-		n = count;
-	}
-};
 // *changed = 0: the step adds (removes) nothing, and so would every further one
 int dilateStep( const char* who, int step, VoxelList& l, uint32_t levels, int element, int* changed, hipStream_t st )
 {
@@ -236,52 +159,25 @@ int dilateStep( const char* who, int step, VoxelList& l, uint32_t levels, int el
 	MVRT_HIP( hipStreamSynchronize( st ) );
 	const uint32_t nNew = r.nCells, nAll = l.n + nNew;
 	r = Records();
-	if( morphMergeLists( l.codes, l.attrs, l.n, newCodes.as<uint64_t>(), newAttrs.as<uint2>(), nNew, codes, attrs, st ) ) return 1; // (the inputs are released below)
+	if( mergeLists( l.codes, l.attrs, l.n, newCodes.as<uint64_t>(), newAttrs.as<uint2>(), nNew, codes, attrs, st ) ) return 1; // (the inputs are released below)
 	l.take( codes, attrs, nAll );
 	*changed = 1;
-	return 0;
-}
-// the entries of a list whose mask is 0, in order: *nKept of them, into codes / attrs (allocated here; left empty when *nKept is 0 or n: the caller looks at it).
-// Has waited for the stream
-int compactUnmasked( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attrs, uint32_t* nKept, hipStream_t st )
-{
-	DevBuf offs;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, MaskFlag, hipcub::CountingInputIterator<uint32_t>> kept( counting, MaskFlag{ mask, n, 0u } );
-	if( exclusiveOffsets<uint32_t>( kept, (uint64_t)n + 1, offs, nKept, st ) ) return 1;
-	if( *nKept == n || *nKept == 0 ) return 0;
-	if( codes.alloc( (uint64_t)*nKept * 8 ) || attrs.alloc( (uint64_t)*nKept * 8 ) ) return 1;
-	hipLaunchKernelGGL( kMorphCompact, dim3( divUp( n, MB ) ), dim3( MB ), 0, st, srcCodes, srcAttrs, mask, offs.as<uint32_t>(), n, 0u, codes.as<uint64_t>(), attrs.as<uint2>(), nullptr );
-	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipStreamSynchronize( st ) ); // (offs is released on return)
-	return 0;
-}
-// *hasEmission = 1 where one of the n attributes has an emission byte set.  Has waited for the stream
-int anyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t st )
-{
-	DevBuf flag;
-	if( flag.alloc( 4 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( flag.p, 0, 4, st ) );
-	hipLaunchKernelGGL( kMorphAnyEmission, dim3( divUp( n, MB ) ), dim3( MB ), 0, st, attrs, n, flag.as<uint32_t>() );
-	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipMemcpyAsync( hasEmission, flag.p, 4, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
 	return 0;
 }
 int erodeStep( const char* who, int step, VoxelList& l, uint32_t levels, int element, int* changed, hipStream_t st )
 {
 	*changed = 0;
-	DevBuf mask, codes, attrs;
+	DevBuf mask;
+	SortedVoxels kept;
 	if( launchMasks( l.codes, l.n, levels, element, mask, st ) ) return 1;
-	uint32_t nKept = 0;
-	if( compactUnmasked( l.codes, l.attrs, mask.as<uint32_t>(), l.n, codes, attrs, &nKept, st ) ) return 1;
-	if( nKept == l.n ) return 0;
-	if( nKept == 0 )
+	if( compactUnmasked( l.codes, l.attrs, mask.as<uint32_t>(), l.n, false, kept, st ) ) return 1;
+	if( kept.n == l.n ) return 0;
+	if( kept.n == 0 )
 	{
 		mvrtSetError( "%s: erosion step %d would leave no voxel (it removes all %u)", who, step, l.n );
 		return 1;
 	}
-	l.take( codes, attrs, nKept );
+	l.take( kept.codes, kept.attrs, kept.n );
 	*changed = 1;
 	return 0;
 }
@@ -292,13 +188,8 @@ int morphDilationCells( const SurfaceSource& s, int element, uint64_t capacity, 
 	Records r;
 	if( dilationRecords( "mvrt_svo_dilation_cells", s.morton, s.nVoxels, s.levels, element, &r, st ) ) return 1;
 	if( nOut ) *nOut = r.nCells;
-	if( !xyzDev && !attribsDev && !countDev ) return 0; // the sizing call
-	if( capacity < r.nCells )
-	{
-		mvrtSetError( "mvrt_svo_dilation_cells: capacity %llu is smaller than the %u cells; nothing was written", (unsigned long long)capacity, r.nCells );
-		return 1;
-	}
-	if( r.nCells == 0 ) return 0;
+	const int tail = listingTail( "mvrt_svo_dilation_cells", "capacity", "cells", !xyzDev && !attribsDev && !countDev, capacity, r.nCells );
+	if( tail != LISTING_WRITE ) return tail;
 	// (the caller's arrays are written by this launch alone, behind every allocation and check)
 	if( launchCells( r, s.attrs, nullptr, attribsDev, countDev, xyzDev, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
@@ -320,86 +211,31 @@ int morphErosionVoxels( const SurfaceSource& s, int element, uint64_t capacity, 
 {
 	DevBuf mask, offs;
 	if( launchMasks( s.morton, s.nVoxels, s.levels, element, mask, st ) ) return 1;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, MaskFlag, hipcub::CountingInputIterator<uint32_t>> removed( counting, MaskFlag{ mask.as<uint32_t>(), s.nVoxels, 1u } );
 	uint32_t nRemoved = 0;
-	if( exclusiveOffsets<uint32_t>( removed, (uint64_t)s.nVoxels + 1, offs, &nRemoved, st ) ) return 1;
+	if( maskOffsets( mask.as<uint32_t>(), s.nVoxels, 1u, offs, &nRemoved, st ) ) return 1;
 	if( nOut ) *nOut = nRemoved;
-	if( !vIndexDev ) return 0; // the sizing call
-	if( capacity < nRemoved )
-	{
-		mvrtSetError( "mvrt_svo_erosion_voxels: capacity %llu is smaller than the %u voxels; nothing was written", (unsigned long long)capacity, nRemoved );
-		return 1;
-	}
-	if( nRemoved == 0 ) return 0;
+	const int tail = listingTail( "mvrt_svo_erosion_voxels", "capacity", "voxels", !vIndexDev, capacity, nRemoved );
+	if( tail != LISTING_WRITE ) return tail;
 	// (the caller's array is written by this launch alone, behind every allocation and check)
-	hipLaunchKernelGGL( kMorphCompact, dim3( divUp( s.nVoxels, MB ) ), dim3( MB ), 0, st, s.morton, s.attrs, mask.as<uint32_t>(), offs.as<uint32_t>(), s.nVoxels, 1u, nullptr, nullptr,
-						vIndexDev );
-	MVRT_HIP( hipGetLastError() );
+	if( launchCompactMasked( s.morton, s.attrs, mask.as<uint32_t>(), offs.as<uint32_t>(), s.nVoxels, 1u, nullptr, nullptr, vIndexDev, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }
 
-int morphList( const char* who, const SurfaceSource& s, int element, int op, int steps, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission, hipStream_t st )
+int morphList( const char* who, const SurfaceSource& s, int element, int op, int steps, SortedVoxels& out, hipStream_t st )
 {
-	VoxelList l;
-	l.codes = s.morton;
-	l.attrs = s.attrs;
-	l.n = s.nVoxels;
-	// the halves of a call: dilation steps, erosion steps or both, in the order of the operator
-	const bool dilateFirst = op == MVRT_MORPH_OP_DILATE || op == MVRT_MORPH_OP_CLOSE;
-	const int halves = op == MVRT_MORPH_OP_CLOSE || op == MVRT_MORPH_OP_OPEN ? 2 : 1;
-	for( int h = 0; h < halves; h++ )
-	{
-		const bool dilate = ( h == 0 ) == dilateFirst;
-		for( int k = 1; k <= steps; k++ )
-		{
-			int changed = 0;
-			if( dilate ? dilateStep( who, k, l, s.levels, element, &changed, st ) : erodeStep( who, k, l, s.levels, element, &changed, st ) ) return 1;
-			if( !changed ) break;
-		}
-	}
-	*nOut = l.n;
-	*hasEmission = 0;
-	// dilation grows, erosion shrinks, a closing holds the set and an opening lies in it: the same count is the same set, with the same bytes
-	if( l.n == s.nVoxels ) return 0;
-	if( op == MVRT_MORPH_OP_OPEN ) // a pure removal: the original bytes, not the means of the dilation half
-	{
-		DevBuf original;
-		if( morphGatherAttrs( l.codes, l.n, s.morton, s.attrs, s.nVoxels, original, st ) ) return 1;
-		l.ownAttrs = std::move( original );
-		l.attrs = l.ownAttrs.as<uint2>();
-	}
-	if( anyEmission( l.attrs, l.n, hasEmission, st ) ) return 1;
-	codes = std::move( l.ownCodes );
-	attribs = std::move( l.ownAttrs );
-	return 0;
-}
-
-int morphMergeLists( const uint64_t* aCodes, const uint2* aAttrs, uint32_t nA, const uint64_t* bCodes, const uint2* bAttrs, uint32_t nB, DevBuf& codes, DevBuf& attribs, hipStream_t st )
-{
-	const uint32_t nAll = nA + nB;
-	if( codes.alloc( (uint64_t)nAll * 8 ) || attribs.alloc( (uint64_t)nAll * 8 ) ) return 1;
-	hipLaunchKernelGGL( kMorphMerge, dim3( divUp( nAll, MB ) ), dim3( MB ), 0, st, aCodes, aAttrs, nA, bCodes, bAttrs, nB, codes.as<uint64_t>(), attribs.as<uint2>() );
-	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipStreamSynchronize( st ) );
-	return 0;
-}
-int morphGatherAttrs( const uint64_t* codes, uint32_t n, const uint64_t* srcCodes, const uint2* srcAttrs, uint32_t nSrc, DevBuf& attribs, hipStream_t st )
-{
-	if( attribs.alloc( (uint64_t)n * 8 ) ) return 1;
-	hipLaunchKernelGGL( kMorphGatherAttrs, dim3( divUp( n, MB ) ), dim3( MB ), 0, st, codes, n, srcCodes, srcAttrs, nSrc, attribs.as<uint2>() );
-	MVRT_HIP( hipGetLastError() );
-	MVRT_HIP( hipStreamSynchronize( st ) );
-	return 0;
-}
-int morphAnyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t st ) { return anyEmission( attrs, n, hasEmission, st ); }
-
-int morphCompactKept( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
-					  hipStream_t st )
-{
-	*hasEmission = 0;
-	if( compactUnmasked( srcCodes, srcAttrs, mask, n, codes, attribs, nKept, st ) ) return 1;
-	if( *nKept == n || *nKept == 0 ) return 0;
-	return anyEmission( attribs.as<uint2>(), *nKept, hasEmission, st );
+	// a half: up to `steps` steps, ended by the first that changes nothing (so would every further one).  An idle first half still leaves the second its turn
+	const uint32_t levels = s.levels;
+	auto half = [=]( decltype( &dilateStep ) step ) {
+		return [=]( VoxelList& l ) {
+			for( int k = 1; k <= steps; k++ )
+			{
+				int changed = 0;
+				if( step( who, k, l, levels, element, &changed, st ) ) return 1;
+				if( !changed ) break;
+			}
+			return 0;
+		};
+	};
+	return runListOperator( op, s, false, half( dilateStep ), half( erodeStep ), out, st );
 }

@@ -322,8 +322,7 @@ int surfaceQuads( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fa
 	if( !faceVoxelDev && !faceDirDev && !positionsDev ) return 0; // the sizing call
 	if( faceCapacity < nFaces )
 	{
-		mvrtSetError( "%s: faceCapacity %llu is smaller than the %llu faces of the surface; nothing was written", who, (unsigned long long)faceCapacity,
-					  (unsigned long long)nFaces );
+		listingRefusal( who, "faceCapacity", "faces of the surface", faceCapacity, nFaces );
 		return 1;
 	}
 	if( scanOffsets( s, masks, offs, st ) ) return 1;
@@ -363,13 +362,12 @@ int surfaceMesh( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fac
 	// (the capacities are looked at behind the sort: a refused call still returns BOTH counts, and the vertex count is the sort's result)
 	if( ( faceVoxelDev || faceDirDev || indicesDev ) && faceCapacity < nFaces )
 	{
-		mvrtSetError( "%s: faceCapacity %llu is smaller than the %llu faces of the surface; nothing was written", who, (unsigned long long)faceCapacity,
-					  (unsigned long long)nFaces );
+		listingRefusal( who, "faceCapacity", "faces of the surface", faceCapacity, nFaces );
 		return 1;
 	}
 	if( verticesDev && vertexCapacity < nVertices )
 	{
-		mvrtSetError( "%s: vertexCapacity %llu is smaller than the %u vertices of the surface; nothing was written", who, (unsigned long long)vertexCapacity, nVertices );
+		listingRefusal( who, "vertexCapacity", "vertices of the surface", vertexCapacity, nVertices );
 		return 1;
 	}
 	if( nCorners == 0 ) return 0;
@@ -650,13 +648,12 @@ int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t f
 	if( !rectVoxelDev && !rectDirDev && !rectSizeDev && !positionsDev && !indicesDev && !verticesDev ) return 0; // the sizing call
 	if( ( rectVoxelDev || rectDirDev || rectSizeDev || positionsDev || indicesDev ) && rectCapacity < nRects )
 	{
-		mvrtSetError( "%s: rectCapacity %llu is smaller than the %llu rectangles of the surface; nothing was written", who, (unsigned long long)rectCapacity,
-					  (unsigned long long)nRects );
+		listingRefusal( who, "rectCapacity", "rectangles of the surface", rectCapacity, nRects );
 		return 1;
 	}
 	if( verticesDev && vertexCapacity < nVertices )
 	{
-		mvrtSetError( "%s: vertexCapacity %llu is smaller than the %u vertices of the surface; nothing was written", who, (unsigned long long)vertexCapacity, nVertices );
+		listingRefusal( who, "vertexCapacity", "vertices of the surface", vertexCapacity, nVertices );
 		return 1;
 	}
 	if( nRects == 0 ) return 0;

@@ -1,5 +1,8 @@
 // launch.h -- host-side launch wrappers implemented in the .hip translation units.
 #pragma once
+#include <functional>
+#include <utility>
+
 #include "devbuf.h"
 #include "mvrt_common.h"
 
@@ -201,15 +204,76 @@ int enclosedCellsUnordered( const SurfaceSource& s, DevBuf& xyz, uint64_t* nCell
 int surfaceExteriorMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, uint64_t* nHiddenOut, hipStream_t stream );
 int launchFillAttribs( uint2 attrib, uint64_t n, uint2* out, hipStream_t stream ); // n copies of one VoxelAttirb.  Not synchronised.
 
+// ---- sorted voxel lists (kernels_list.hip) -------------------------------------------------------------------------------------------------------------
+// What every voxel-set operator hands to svoBuildFromSorted: n sorted unique codes with their attributes and the emission flag over them, allocated by the
+// operator.  The one convention of "nothing changed": the arrays are left empty and n is the voxel count of the set the operator started from.
+struct SortedVoxels
+{
+	DevBuf codes, attrs;
+	uint32_t n = 0, hasEmission = 0;
+	bool unchanged( uint32_t nVoxels ) const { return !codes.p && !attrs.p && n == nVoxels; }
+};
+// the list a sequence of steps works on: borrowed arrays first (the handle's, not owned), then the arrays the last step made
+struct VoxelList
+{
+	const uint64_t* codes;
+	const uint2* attrs;
+	uint32_t n;
+	DevBuf ownCodes, ownAttrs;
+	VoxelList( const uint64_t* c, const uint2* a, uint32_t count ) : codes( c ), attrs( a ), n( count ) {}
+	void take( DevBuf& c, DevBuf& a, uint32_t count )
+	{
+		ownCodes = std::move( c );
+		ownAttrs = std::move( a );
+		codes = ownCodes.as<uint64_t>();
+		attrs = ownAttrs.as<uint2>();
+		n = count;
+	}
+};
+// The list steps; each allocates its outputs itself and has waited for the stream when it returns.  Two sorted lists without a common code merged into one; the
+// attributes that the n codes, a subset of srcCodes, have there; *hasEmission = 1 where one of the n attributes has an emission byte set
+int mergeLists( const uint64_t* aCodes, const uint2* aAttrs, uint32_t nA, const uint64_t* bCodes, const uint2* bAttrs, uint32_t nB, DevBuf& codes, DevBuf& attribs, hipStream_t stream );
+int gatherAttrs( const uint64_t* codes, uint32_t n, const uint64_t* srcCodes, const uint2* srcAttrs, uint32_t nSrc, DevBuf& attribs, hipStream_t stream );
+int anyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t stream );
+// offs = the n + 1 exclusive sums of the flags ( mask[i] != 0 ) == ( removed != 0 ), *count = their number; then the flagged entries in order: code and attribute
+// (a step) or index (a listing), any output may be null.  The launch is not synchronised
+int maskOffsets( const uint32_t* mask, uint32_t n, uint32_t removed, DevBuf& offs, uint32_t* count, hipStream_t stream );
+int launchCompactMasked( const uint64_t* codes, const uint2* attrs, const uint32_t* mask, const uint32_t* offs, uint32_t n, uint32_t removed, uint64_t* codesOut, uint2* attrsOut,
+						 uint32_t* vIndexOut, hipStream_t stream );
+// the erosion's scan and scatter on a caller's mask: the entries of the n sorted codes and attributes whose mask is 0, in order (out.n of them; the arrays are
+// left empty when that is 0 or n), and with scanEmission the emission flag over them
+int compactUnmasked( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, bool scanEmission, SortedVoxels& out, hipStream_t stream );
+// One dilate / erode / close / open on the list of s: the halves in the order of the operator, the unchanged test by the count, the opening's re-gather of the
+// original attribute bytes, the emission scan and the move into `out`.  A half returns non-zero on failure and leaves the list alone when it changes nothing.
+// idleFirstHalfEnds: a first half that changes nothing ends the call (the second is not run)
+enum
+{
+	MVRT_MORPH_OP_DILATE = 0,
+	MVRT_MORPH_OP_ERODE = 1,
+	MVRT_MORPH_OP_CLOSE = 2,
+	MVRT_MORPH_OP_OPEN = 3
+};
+typedef std::function<int( VoxelList& )> ListHalf;
+int runListOperator( int op, const SurfaceSource& s, bool idleFirstHalfEnds, const ListHalf& dilate, const ListHalf& erode, SortedVoxels& out, hipStream_t stream );
+// The tail of a listing call, behind its counts: the sizing call is done, a capacity below n is refused ("<who>: <capacityName> <capacity> is smaller than the
+// <n> <things>; nothing was written", listingRefusal), an empty listing is done, else the caller writes its arrays
+enum
+{
+	LISTING_DONE = 0,
+	LISTING_REFUSED = 1,
+	LISTING_WRITE = 2
+};
+int listingTail( const char* who, const char* capacityName, const char* things, bool sizing, uint64_t capacity, uint64_t n );
+void listingRefusal( const char* who, const char* capacityName, const char* things, uint64_t capacity, uint64_t n );
+
 // coarse cells (kernels_coarsen.hip; mvrt_svo_coarse_voxels / mvrt_svo_coarsen): the n >= 1 sorted codes and Morton-ordered attributes of a build, levelsDown in
 // [1, levels - 1] and minCount in [1, coarseCellCapacity( levelsDown )], all checked by the caller.  The calls block, keep their scratch in DevBufs and write
 // NOTHING to the caller's arrays unless they succeed.
 uint64_t coarseCellCapacity( int levelsDown ); // 8^levelsDown, the fine voxels one coarse cell can hold (levelsDown <= 20)
 int coarseVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev,
 				  uint32_t* countDev, uint64_t* nOut, hipStream_t stream );
-// the same list as sorted codes and attributes for svoBuildFromSorted (both allocated here; left empty when no cell is kept: the caller looks at *nKept)
-int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
-				hipStream_t stream );
+// the same list as sorted codes and attributes for svoBuildFromSorted (left empty when no cell is kept: the caller looks at out.n)
+int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, SortedVoxels& out, hipStream_t stream );
 
 // dilation, erosion, closing and opening (kernels_morph.hip; mvrt_svo_dilation_cells / _erosion_voxels / _dilate / _erode / _close / _open): morton, attrs, nVoxels
 // and levels of the source are read, element is MVRT_MORPH_FACES or MVRT_MORPH_CUBE, checked by the caller.  The calls block, keep their scratch in DevBufs and
@@ -218,26 +282,8 @@ int morphDilationCells( const SurfaceSource& s, int element, uint64_t capacity, 
 int morphErosionVoxels( const SurfaceSource& s, int element, uint64_t capacity, uint32_t* vIndexDev, uint64_t* nOut, hipStream_t stream );
 // the cells one dilation step adds to the n sorted codes, as ascending codes into cellCodes (allocated here; left empty when *nCells is 0: a full grid).  Blocks
 int morphStepCodes( const char* who, const uint64_t* codes, const uint2* attrs, uint32_t n, uint32_t levels, int element, DevBuf& cellCodes, uint32_t* nCells, hipStream_t stream );
-enum
-{
-	MVRT_MORPH_OP_DILATE = 0,
-	MVRT_MORPH_OP_ERODE = 1,
-	MVRT_MORPH_OP_CLOSE = 2,
-	MVRT_MORPH_OP_OPEN = 3
-};
-// `steps` >= 1 steps of the operator on sorted lists, for svoBuildFromSorted: *nOut = the voxels of the result; codes / attribs (allocated here) are left empty
-// when *nOut == nVoxels, which means that the set did not change.  A step that would reach 2^32 - 1 voxels or leave none is refused; `who` names the call
-int morphList( const char* who, const SurfaceSource& s, int element, int op, int steps, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission, hipStream_t stream );
-// the erosion's scan and scatter on a caller's mask: the entries of the n sorted codes and attributes whose mask is 0, in order, into codes / attribs (allocated
-// here; left empty when *nKept is 0 or n) and the emission flag over them.  Blocks
-int morphCompactKept( const uint64_t* srcCodes, const uint2* srcAttrs, const uint32_t* mask, uint32_t n, DevBuf& codes, DevBuf& attribs, uint32_t* nKept, uint32_t* hasEmission,
-					  hipStream_t stream );
-
-// the other list steps of kernels_morph.hip that kernels_ball.hip runs as well; each allocates its outputs here and blocks.  Two sorted lists without a common
-// code merged into one; the attributes that the n codes, a subset of srcCodes, have there; *hasEmission = 1 where one of the n attributes has an emission byte set
-int morphMergeLists( const uint64_t* aCodes, const uint2* aAttrs, uint32_t nA, const uint64_t* bCodes, const uint2* bAttrs, uint32_t nB, DevBuf& codes, DevBuf& attribs, hipStream_t stream );
-int morphGatherAttrs( const uint64_t* codes, uint32_t n, const uint64_t* srcCodes, const uint2* srcAttrs, uint32_t nSrc, DevBuf& attribs, hipStream_t stream );
-int morphAnyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t stream );
+// `steps` >= 1 steps of the operator (MVRT_MORPH_OP_*) on sorted lists.  A step that would reach 2^32 - 1 voxels or leave none is refused; `who` names the call
+int morphList( const char* who, const SurfaceSource& s, int element, int op, int steps, SortedVoxels& out, hipStream_t stream );
 
 // round offsets (kernels_ball.hip; mvrt_svo_distance_cells / _depth_voxels / _dilate_ball / _erode_ball / _close_ball / _open_ball): morton, attrs, nVoxels and levels
 // of the source are read, radius2 is in [1, 1024], checked by the caller.  The calls block, keep their scratch in DevBufs and write NOTHING to the caller's arrays
@@ -250,9 +296,8 @@ struct BallStats // what the last band of a call did (tools/ball_bench.py throug
 int ballDistanceCells( const SurfaceSource& s, uint32_t radius2, uint64_t capacity, uint32_t* xyzDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, uint64_t* nOut,
 					   hipStream_t stream );
 int ballDepthVoxels( const SurfaceSource& s, uint32_t radius2, uint64_t capacity, uint32_t* vIndexDev, uint32_t* depth2Dev, uint64_t* nOut, hipStream_t stream );
-// the operator (MVRT_MORPH_OP_*) with the ball of radius2 on sorted lists, for svoBuildFromSorted: *nOut = the voxels of the result; codes / attribs (allocated
-// here) are left empty when *nOut == nVoxels, which means that the set did not change.  A result of 2^32 - 1 voxels or more or of none is refused; `who` names the call
-int ballList( const char* who, const SurfaceSource& s, uint32_t radius2, int op, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission, hipStream_t stream );
+// the operator (MVRT_MORPH_OP_*) with the ball of radius2 on sorted lists.  A result of 2^32 - 1 voxels or more or of none is refused; `who` names the call
+int ballList( const char* who, const SurfaceSource& s, uint32_t radius2, int op, SortedVoxels& out, hipStream_t stream );
 BallStats ballLastStats(); // of this thread
 
 // connected components (kernels_components.hip; mvrt_svo_components / mvrt_svo_keep_components): morton, attrs, nVoxels and levels of the source are read, element
@@ -260,10 +305,10 @@ BallStats ballLastStats(); // of this thread
 // unless they succeed.
 int componentsList( const SurfaceSource& s, int element, uint32_t* labelDev, uint64_t capacity, uint32_t* sizeDev, uint32_t* firstDev, uint32_t* boxDev, uint64_t* nComponentsOut,
 					uint64_t* largestOut, hipStream_t stream );
-// the voxels of the kept components (minVoxels >= 1, checked by the caller) as sorted codes and attributes for svoBuildFromSorted: *nOut = their number; codes /
-// attribs (allocated here) are left empty when *nOut == nVoxels (every component is kept) or 0 (none is: the caller refuses)
-int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels, uint32_t keepLargest, DevBuf& codes, DevBuf& attribs, uint32_t* nOut, uint32_t* hasEmission,
-						uint32_t* nComponents, uint32_t* nKeptComponents, hipStream_t stream );
+// the voxels of the kept components (minVoxels >= 1, checked by the caller) as a sorted list: unchanged when every component is kept, out.n == 0 when none is
+// (the caller refuses)
+int componentsKeepList( const SurfaceSource& s, int element, uint64_t minVoxels, uint32_t keepLargest, SortedVoxels& out, uint32_t* nComponents, uint32_t* nKeptComponents,
+						hipStream_t stream );
 
 // two voxel sets (kernels_combine.hip; mvrt_svo_combine_voxels / mvrt_svo_combine): morton, attrs, nVoxels and levels of a, morton, attrs and nVoxels of b (its
 // levels only decide whether its codes can stand as they are), op and flags as in mvrt.h and o[3] in [-2^21, 2^21], all checked by the caller.  The calls block,
@@ -280,14 +325,13 @@ int combineVoxels( const SurfaceSource& a, const SurfaceSource& b, int op, const
 				   uint8_t* sourceDev, uint64_t* nOut, uint64_t* nOverlapOut, uint64_t* nClippedOut, hipStream_t stream );
 struct CombineCounts
 {
-	uint64_t n = 0, nOverlap = 0, nClipped = 0; // the result, A n B', the entries of b the offset moves out of the grid
-	uint32_t nAdded = 0, nRemoved = 0;			// B' \ A where the operator takes it, the voxels of A it drops
-	uint32_t recolours = 0, hasEmission = 0;	// the overlap survives and takes b's attributes; the emission flag over the result
+	SortedVoxels list;						 // the result.  nAdded == nRemoved == 0: with recolours only list.attrs is filled (the codes are a's), without it nothing is
+	uint64_t nOverlap = 0, nClipped = 0;	 // A n B', the entries of b the offset moves out of the grid
+	uint32_t nAdded = 0, nRemoved = 0;		 // B' \ A where the operator takes it, the voxels of A it drops
+	uint32_t recolours = 0;					 // the overlap survives and takes b's attributes
 };
-// the result as sorted codes and attributes for svoBuildFromSorted (allocated here).  nAdded == nRemoved == 0: with recolours only `attribs` is filled (the codes
-// are a's), without it nothing is (nothing changes).  A result of no voxel or of 2^32 - 1 or more is refused; `who` names the call
-int combineList( const char* who, const SurfaceSource& a, const SurfaceSource& b, int op, const int32_t o[3], uint32_t flags, DevBuf& codes, DevBuf& attribs, CombineCounts* counts,
-				 hipStream_t stream );
+// A result of no voxel or of 2^32 - 1 or more is refused; `who` names the call
+int combineList( const char* who, const SurfaceSource& a, const SurfaceSource& b, int op, const int32_t o[3], uint32_t flags, CombineCounts* counts, hipStream_t stream );
 
 // octree walk (kernels_walk.hip;mvrt_svo_walk_voxels / mvrt_svo_rebuild): what it reads of an embedded or plain octree, built or uploaded (never the tree
 // flavour, which always keeps its codes).  The calls block, keep their scratch in DevBufs and never write to the octree.

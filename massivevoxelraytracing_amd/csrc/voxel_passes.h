@@ -20,6 +20,8 @@
 //   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
 //                   entries -> rank + 1 of every entry and the number of runs).  Each allocates its output itself, runs hipcub through withCubTemp and has waited
 //                   for the stream when it returns.
+//   list steps      not here: the steps on whole sorted voxel lists that the operators share (merge, gather of attributes, emission scan, compaction by a mask, the
+//                   driver of a dilate / erode / close / open, the tail of a listing) are declared in launch.h under "sorted voxel lists" and live in kernels_list.hip.
 #pragma once
 #include <hipcub/hipcub.hpp>
 
