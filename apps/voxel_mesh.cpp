@@ -4,7 +4,8 @@
 //   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]
 //              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]
 //              [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]
-//              [--union | --intersect | --subtract | --xor other.obj [--offset x y z] [--attrib-b]] [--ao [samples] [--ao-radius voxels]]
+//              [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]
+//              [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -35,8 +36,13 @@
 // scene (mvrt_svo_combine) before --lod and everything behind it.  Both models are voxelised on one lattice, the grid placement below applied to their joint
 // bounding box; --offset x y z moves the second set by whole cells first (what leaves the grid is clipped), --attrib-b gives the cells both models share the
 // colour of the second.  A line reports the voxels before and after, the second model's voxels, the overlap and the clipped voxels.  With every other flag.
+// --rotate-b ax ay az deg, --scale-b s (either or both, only with one of the four above): the second set is turned by deg degrees about the axis (ax, ay, az) and
+// scaled by s > 0, both about the centre of the grid, before it is combined: resampled into a scratch octree on the same lattice (mvrt_svo_resample with the
+// transform mvrt_cell_transform_from_world makes of the world matrix), no triangle is voxelised again.  A line reports the second set's voxels before and after;
+// --offset still applies, to the resampled set.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,7 +68,8 @@ int main( int argc, char** argv )
 	bool keep = false, keepOk = true;
 	const char *combineName = nullptr, *otherObj = nullptr; // "union", "intersect", "subtract" or "xor"
 	int combineOps = 0, combineOp = 0, offset[3] = { 0, 0, 0 };
-	bool attribB = false;
+	bool attribB = false, resampleB = false, resampleOk = true;
+	double rotateB[4] = { 0.0, 0.0, 1.0, 0.0 }, scaleB = 1.0; // axis and degrees
 	std::vector<const char*> pos;
 	for( int i = 1; i < argc; i++ )
 	{
@@ -110,6 +117,18 @@ int main( int argc, char** argv )
 			for( int k = 0; k < 3; k++ ) offset[k] = std::atoi( argv[++i] );
 		}
 		else if( !std::strcmp( argv[i], "--attrib-b" ) ) attribB = true;
+		else if( !std::strcmp( argv[i], "--rotate-b" ) && i + 4 < argc )
+		{
+			for( int k = 0; k < 4; k++ ) rotateB[k] = std::atof( argv[++i] );
+			resampleB = true;
+			resampleOk = resampleOk && rotateB[0] * rotateB[0] + rotateB[1] * rotateB[1] + rotateB[2] * rotateB[2] > 0.0;
+		}
+		else if( !std::strcmp( argv[i], "--scale-b" ) && i + 1 < argc )
+		{
+			scaleB = std::atof( argv[++i] );
+			resampleB = true;
+			resampleOk = resampleOk && scaleB > 0.0 && scaleB - scaleB == 0.0;
+		}
 		else if( !std::strcmp( argv[i], "--components" ) ) components = true;
 		else if( !std::strcmp( argv[i], "--keep-largest" ) && i + 1 < argc )
 		{
@@ -137,9 +156,12 @@ int main( int argc, char** argv )
 		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]\n"
 					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]\n"
 					 "                  [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]\n"
-					 "                  [--union | --intersect | --subtract | --xor other.obj [--offset x y z] [--attrib-b]] [--ao [samples] [--ao-radius voxels]]\n"
+					 "                  [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]\n"
+					 "                  [--ao [samples] [--ao-radius voxels]]\n"
 					 "  --union O, --intersect O, --subtract O, --xor O  combine the voxel set with that of a second model O.obj first, both voxelised on one grid\n"
 					 "               over their joint bounding box; --offset x y z moves the second set by whole cells, --attrib-b colours shared cells from it\n"
+					 "  --rotate-b ax ay az deg, --scale-b s  turn the second voxel set by deg degrees about the axis and scale it by s > 0, about the grid centre,\n"
+					 "               before it is combined (resampled on the GPU; only with one of the four options above)\n"
 					 "  --lod K      coarsen the octree by K levels first (gridRes >> K); --lod-min-count C keeps a coarse cell only when it holds C fine voxels\n"
 					 "  --dilate K   grow the voxel set by K layers; --erode K peels K layers; --close K = dilate K, erode K (plugs holes); --open K = erode K,\n"
 					 "               dilate K (removes specks).  One of them, after --lod and before --fill / --exterior; --element faces|cube (default cube)\n"
@@ -160,6 +182,11 @@ int main( int argc, char** argv )
 	if( combineOps > 1 )
 	{
 		std::fprintf( stderr, "voxel_mesh: only one of --union / --intersect / --subtract / --xor\n" );
+		return 2;
+	}
+	if( resampleB && ( combineOps != 1 || !resampleOk ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: --rotate-b ax ay az deg (an axis that is not zero) and --scale-b s (s > 0) need one of --union / --intersect / --subtract / --xor\n" );
 		return 2;
 	}
 	if( fill && exterior )
@@ -219,12 +246,33 @@ int main( int argc, char** argv )
 	{
 		mvrt::IntersectorOctreeGPU other;
 		other.build( otherVertices, otherColors, otherEmissions, nullptr, stream, origin, dps, gridRes, conservative ? MVRT_BUILD_CONSERVATIVE : 0 );
+		mvrt::IntersectorOctreeGPU turned, *second = &other; // what is combined
+		if( resampleB ) // the second set turned and scaled about the grid centre, on the same lattice
+		{
+			const double n = std::sqrt( rotateB[0] * rotateB[0] + rotateB[1] * rotateB[1] + rotateB[2] * rotateB[2] ), a[3] = { rotateB[0] / n, rotateB[1] / n, rotateB[2] / n };
+			const double rad = rotateB[3] * 3.14159265358979323846 / 180.0, c = std::cos( rad ), sn = std::sin( rad ), t = 1.0 - c;
+			const double R[9] = { c + t * a[0] * a[0],		  t * a[0] * a[1] - sn * a[2], t * a[0] * a[2] + sn * a[1], t * a[0] * a[1] + sn * a[2], c + t * a[1] * a[1],
+								  t * a[1] * a[2] - sn * a[0], t * a[0] * a[2] - sn * a[1], t * a[1] * a[2] + sn * a[0], c + t * a[2] * a[2] };
+			const double half = 0.5 * (double)dps * (double)gridRes, centre[3] = { (double)origin.x + half, (double)origin.y + half, (double)origin.z + half };
+			double world[12]; // p' = s R ( p - centre ) + centre
+			for( int i = 0; i < 3; i++ )
+			{
+				for( int j = 0; j < 3; j++ ) world[4 * i + j] = scaleB * R[3 * i + j];
+				world[4 * i + 3] = centre[i] - ( world[4 * i] * centre[0] + world[4 * i + 1] * centre[1] + world[4 * i + 2] * centre[2] );
+			}
+			const mvrt::vec3 lower = { origin.x, origin.y, origin.z };
+			const mvrt_cell_transform xf = mvrt::IntersectorOctreeGPU::cellTransformFromWorld( world, lower, dps, lower, dps );
+			other.resample( xf, lower, dps, gridRes, 0, &turned, stream );
+			std::printf( "resample-b: voxels %u -> %u, axis %g %g %g, degrees %g, scale %g\n", other.m_numberOfVoxels, turned.m_numberOfVoxels, rotateB[0], rotateB[1], rotateB[2],
+						 rotateB[3], scaleB );
+			second = &turned;
+		}
 		const uint32_t before = svo.m_numberOfVoxels, flags = attribB ? mvrt::IntersectorOctreeGPU::COMBINE_ATTRIB_B : 0u;
 		uint64_t overlap = 0, clipped = 0, removed = 0;
-		svo.combineVoxels( other, combineOp, offset, flags, 0, nullptr, nullptr, nullptr, &overlap, &clipped, stream );
-		const uint64_t added = svo.combine( other, combineOp, offset, flags, &removed, nullptr, stream );
+		svo.combineVoxels( *second, combineOp, offset, flags, 0, nullptr, nullptr, nullptr, &overlap, &clipped, stream );
+		const uint64_t added = svo.combine( *second, combineOp, offset, flags, &removed, nullptr, stream );
 		std::printf( "%s: voxels %u -> %u, other %u, offset %d %d %d, overlap %llu, clipped %llu, added %llu, removed %llu\n", combineName, before, svo.m_numberOfVoxels,
-					 other.m_numberOfVoxels, offset[0], offset[1], offset[2], (unsigned long long)overlap, (unsigned long long)clipped, (unsigned long long)added,
+					 second->m_numberOfVoxels, offset[0], offset[1], offset[2], (unsigned long long)overlap, (unsigned long long)clipped, (unsigned long long)added,
 					 (unsigned long long)removed );
 	}
 	if( lod > 0 ) // before anything else is done with the octree

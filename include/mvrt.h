@@ -409,6 +409,57 @@ int mvrt_svo_combine_voxels( const mvrt_svo* a, const mvrt_svo* b, int op, const
 int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t* nAddedOut, uint64_t* nRemovedOut, uint64_t* nClippedOut,
 					  void* stream );
 
+/* The voxel set of one octree resampled onto another grid under an affine map (new; the reference has none).  With mvrt_svo_combine behind it this is the rotated
+ * or scaled stamp; mvrt_cell_transform_from_world below is the world-space alignment of two lattices.  Definitions, with S = the voxel set of src on [0, Rs)^3,
+ * Rd = the destination gridRes, a power of two in [2, 2^21] as for mvrt_svo_build_voxels, and F = MVRT_TRANSFORM_FRAC_BITS = 24:
+ *   - The rule.  For a destination cell c = (c0, c1, c2) in [0, Rd)^3:
+ *       P_i = m[3i+0]*(2*c0+1) + m[3i+1]*(2*c1+1) + m[3i+2]*(2*c2+1) + t[i], taken in int64;
+ *       s_i = floor( P_i / 2^(F+1) ), the floor towards minus infinity.
+ *     Cell c belongs to the result when s lies in [0, Rs)^3 and is a voxel of S.  It then takes that voxel's colour RGB and emission RGB with both alpha bytes 255,
+ *     the rule of MVRT_VOXEL_SET, and source(c) is that voxel's vIndex.
+ *   - In words: m is the INVERSE map in Q24, destination cell space to source cell space, and t is its translation in Q25; the sample point is the centre of the
+ *     destination cell.  The rule is nearest-neighbour resampling by inverse mapping: no holes under rotation, and no duplicates.
+ *   - Limits: |m[k]| <= 2^30, so entries reach 64, and |t[i]| <= 2^52.  With 2*c+1 < 2^22 every |P_i| stays below 2^55: nothing can wrap.  The bounds are checked on
+ *     the host; structBytes must be sizeof( mvrt_cell_transform ) and reserved must be 0.
+ *   - Singular maps are legal: m need not be invertible, because only the inverse direction is ever evaluated.  An all-zero m sends every destination cell to the
+ *     cell that t names.
+ *   - Order: ascending Morton code in the destination grid.  Everything is integers: the result is a property of the set and the transform alone.
+ *   - Two facts that pin the conventions.  A signed permutation about the grid centre with Rd == Rs gives a bijection, c_j -> c_j or Rs - 1 - c_j per axis, exact in
+ *     Q24 (mirror of axis j: m = -2^24 on it, t = Rs * 2^25).  A = I/2 gives s = c >> 1, so each voxel becomes a 2x2x2 block; A = 2I gives s = 2c + 1: this is
+ *     sub-sampling, NOT the count rule of mvrt_svo_coarsen.
+ * mvrt_svo_resample_voxels, the listing, follows the rules of mvrt_svo_combine_voxels word for word: every octree this library built or edited is accepted, in every
+ * flavour, the tree flavour included (only the codes and the attributes are read); an upload is refused ("keeps no Morton codes": it works after one
+ * mvrt_svo_rebuild), an empty handle too ("no octree"); a bad transform or a bad gridRes is refused on the host, before any GPU work and
+ * before the state of the handle is looked at (a null handle comes first of all).  src is never modified.  The
+ * call blocks.  Arrays hold `capacity` entries: xyzDev 3 x uint32, attribsDev 8 bytes, sourceDev one uint32 = source(c).  Any output may be NULL, all three NULL is
+ * the sizing call (capacity is then ignored).  A capacity below the count is an error: the count is still returned and NOTHING is written.  An empty result is a
+ * success with *nOut = 0.  The destination grid is refined top-down, a frontier of nodes per level: a result, or an intermediate frontier, of 2^32 - 1 entries or
+ * more is refused (the message names the count).  A failed allocation of scratch returns an error, leaks nothing and has written nothing. */
+#define MVRT_TRANSFORM_FRAC_BITS 24
+typedef struct mvrt_cell_transform
+{
+	uint32_t structBytes, reserved;
+	int64_t m[9]; /* row-major, Q24 */
+	int64_t t[3]; /* Q25 */
+} mvrt_cell_transform;
+int mvrt_svo_resample_voxels( const mvrt_svo* src, const mvrt_cell_transform* xf, int dstGridRes, uint64_t capacity, uint32_t* xyzDev /* 3 per voxel */,
+							  uint32_t* attribsDev /* 8 bytes per voxel */, uint32_t* sourceDev /* vIndex in src */, uint64_t* nOut, void* stream );
+/* Into a handle, by the rules of mvrt_svo_coarsen: dst becomes exactly the octree mvrt_svo_build_voxels would build from that listing with dstOriginHost, dstDps,
+ * dstGridRes and buildFlags (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only; any other bit is refused): same nodes, numbering, flavour choice, cell index and
+ * prefix tables, vIndex = Morton rank.  The list never travels to the host and is neither encoded nor sorted again.  hasEmission is recomputed from the result,
+ * totalDumpedVoxels = the source's numberOfVoxels, the emission scale is the destination handle's own and is not touched.  dst == src is allowed: the list is
+ * complete before anything is replaced.  Otherwise src is never modified.  Refusals are the listing's, on the host; an empty result is refused with dst unchanged
+ * ("would leave no voxel").  Failures and ordering are the voxel-list build's: the new arrays are built next to whatever dst holds, every failure before they are
+ * adopted leaves dst exactly as it was, one after that leaves dst empty (see mvrt_svo_destroy above); src != dst stays whole throughout.  Through
+ * mvrt_pt_intersector( pt ) as dst: the steps issued before finish first and render the old scene, the frame buffer is not cleared; every mvrt_device_octree view
+ * of dst is invalidated.  *nOut (may be NULL) = the voxels of the result.  Blocks like mvrt_svo_build. */
+int mvrt_svo_resample( const mvrt_svo* src, mvrt_svo* dst, const mvrt_cell_transform* xf, const float dstOriginHost[3], float dstDps, int dstGridRes, int buildFlags,
+					   uint64_t* nOut, void* stream );
+/* Host only, no GPU call: the transform that aligns two lattices in world space.  world is 3x4 row-major, p_dst = W * p_src + w.  With Winv computed in double:
+ * A = Winv * ( dstDps / srcDps ), b = ( Winv * ( dstLower - w ) - srcLower ) / srcDps, m[k] = llrint( A[k] * 2^24 ) and t[i] = llrint( b[i] * 2^25 ).  Refused: a
+ * non-finite input, det W == 0 or a non-finite inverse ("singular"), a dps that is not finite and positive, and any entry outside the limits above. */
+int mvrt_cell_transform_from_world( const double world[12], const float srcLower[3], float srcDps, const float dstLower[3], float dstDps, mvrt_cell_transform* out );
+
 /* Exterior-only surface extraction without touching the octree, and the three extraction calls on face masks the caller supplies (new; the reference has
  * none).  Definitions:
  *   - Exterior mask of a voxel: one byte, directions d = 0..5 as in mvrt_svo_surface_masks (0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X).  Bit d is set when the
@@ -886,6 +937,9 @@ int mvrt_test_peak_bytes( uint64_t* peakOut, int reset );
 /* Measuring (tools/ball_bench.py): what the last distance band this thread ran did: out[0..2] = the records of the passes along x, y and z, out[3] = its seeds,
  * out[4] = its cells.  A closing or an opening runs two bands; this is the second. */
 int mvrt_test_ball_stats( uint64_t out[5] );
+/* Measuring (tools/resample_bench.py): what the last resampling this thread ran did: out[0] = L, the levels of the destination grid, out[l] for l = 1 .. L = the
+ * nodes of level l its frontier kept (out[L] = the result cells; 0 from the level on at which nothing was left), the rest 0. */
+int mvrt_test_resample_stats( uint64_t out[24] );
 int mvrt_pt_set_profiling( mvrt_pt* pt, int enabled ); /* HIP events on `stream` around each kernel of step(); read by get_stats */
 int mvrt_pt_reset_stats( mvrt_pt* pt );
 int mvrt_pt_get_stats( mvrt_pt* pt, void* stream, mvrt_pt_stats* out ); /* synchronises the stream */

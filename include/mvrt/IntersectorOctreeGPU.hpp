@@ -436,6 +436,47 @@ struct IntersectorOctreeGPU
 		return n;
 	}
 
+	// the voxel set resampled onto a grid of dstGridRes cells per axis under an affine map (mvrt_svo_resample_voxels / mvrt_svo_resample; semantics in mvrt.h): xf is
+	// the INVERSE map, destination cells to source cells, in fixed point; cellTransformFromWorld makes it from a world matrix and two lattices.  Device-pointer form
+	// of the listing: any output may be nullptr, all nullptr = the sizing call.  Returns the number of voxels.
+	static mvrt_cell_transform cellTransformFromWorld( const double world[12], vec3 srcLower, float srcDps, vec3 dstLower, float dstDps )
+	{
+		mvrt_cell_transform xf;
+		const float sl[3] = { srcLower.x, srcLower.y, srcLower.z }, dl[3] = { dstLower.x, dstLower.y, dstLower.z };
+		check( mvrt_cell_transform_from_world( world, sl, srcDps, dl, dstDps, &xf ), "IntersectorOctreeGPU::cellTransformFromWorld" );
+		return xf;
+	}
+	uint64_t resampleVoxels( const mvrt_cell_transform& xf, int dstGridRes, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* sourceDev, void* stream ) const
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_resample_voxels( m_handle, &xf, dstGridRes, capacity, xyzDev, attribsDev, sourceDev, &n, stream ), "IntersectorOctreeGPU::resampleVoxels" );
+		return n;
+	}
+	// host-vector form: xyz = 3 entries per voxel in ascending Morton order of the destination grid, attribs = 2, source = 1 (the vIndex the voxel comes from)
+	void resampleVoxels( const mvrt_cell_transform& xf, int dstGridRes, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs, std::vector<uint32_t>& source, void* stream ) const
+	{
+		const uint64_t n = resampleVoxels( xf, dstGridRes, 0, nullptr, nullptr, nullptr, stream );
+		xyz.resize( n * 3 );
+		attribs.resize( n * 2 );
+		source.resize( n );
+		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), s( nullptr, n * 4, stream );
+		if( n ) resampleVoxels( xf, dstGridRes, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint32_t*)s.p, stream );
+		fetch( xyz, x, stream );
+		fetch( attribs, a, stream );
+		fetch( source, s, stream );
+	}
+	// dst (nullptr = this object) becomes the octree buildFromVoxels would build from that list with dstOrigin, dstDps, dstGridRes and buildFlags.  Returns the voxels
+	// of the result; an empty result aborts like any failure.  Invalidates deviceView() snapshots of dst.
+	uint64_t resample( const mvrt_cell_transform& xf, vec3 dstOrigin, float dstDps, int dstGridRes, int buildFlags = 0, IntersectorOctreeGPU* dst = nullptr, void* stream = nullptr )
+	{
+		IntersectorOctreeGPU* d = dst ? dst : this;
+		const float o[3] = { dstOrigin.x, dstOrigin.y, dstOrigin.z };
+		uint64_t n = 0;
+		check( mvrt_svo_resample( m_handle, d->m_handle, &xf, o, dstDps, dstGridRes, buildFlags, &n, stream ), "IntersectorOctreeGPU::resample" );
+		d->refresh();
+		return n;
+	}
+
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const

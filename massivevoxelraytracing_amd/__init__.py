@@ -49,6 +49,31 @@ class DenoiseParams(C.Structure):
                 ("albedoFloor", _f32), ("flags", _u32), ("reserved", _u32 * 2)]
 
 
+class CellTransform(C.Structure):
+    """mvrt_cell_transform (include/mvrt.h): the inverse map, destination cell space to source cell space, m row-major in Q24 and t in Q25.
+    CellTransform.make(m, t) takes 9 and 3 Python ints as they are; from_cells(A, b) rounds a real 3x3 matrix and translation in cell units."""
+    _fields_ = [("structBytes", _u32), ("reserved", _u32), ("m", C.c_int64 * 9), ("t", C.c_int64 * 3)]
+
+    @classmethod
+    def make(cls, m, t):
+        x = cls()
+        x.structBytes, x.reserved = C.sizeof(cls), 0
+        x.m[:] = [int(v) for v in np.asarray(m, object).reshape(9)]
+        x.t[:] = [int(v) for v in np.asarray(t, object).reshape(3)]
+        return x
+
+    @classmethod
+    def from_cells(cls, A, b=(0.0, 0.0, 0.0)):
+        """s = A c + b in cell coordinates (c the destination point, s the source point): m = rint(A * 2^24), t = rint(b * 2^25)"""
+        A, b = np.asarray(A, np.float64).reshape(9), np.asarray(b, np.float64).reshape(3)
+        return cls.make([int(v) for v in np.rint(A * 2.0 ** TRANSFORM_FRAC_BITS)], [int(v) for v in np.rint(b * 2.0 ** (TRANSFORM_FRAC_BITS + 1))])
+
+    def arrays(self):
+        """(m (9,) int64, t (3,) int64)"""
+        return np.array(self.m[:], np.int64), np.array(self.t[:], np.int64)
+
+
+TRANSFORM_FRAC_BITS = 24  # MVRT_TRANSFORM_FRAC_BITS
 DENOISE_NO_DEMODULATION = 1
 SURFACE_MERGE_ANY_ATTRIBUTE = 1  # mvrt_svo_surface_merged flags (include/mvrt.h)
 SURFACE_MERGE_WELD = 2
@@ -103,6 +128,9 @@ SIGNATURES = {
     "mvrt_svo_keep_components": (_i32, [_vp, _i32, _u64, C.c_uint32, _vp, _vp, _vp]),
     "mvrt_svo_combine_voxels": (_i32, [_vp, _vp, _i32, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_combine": (_i32, [_vp, _vp, _i32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_resample_voxels": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_resample": (_i32, [_vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp]),
+    "mvrt_cell_transform_from_world": (_i32, [_vp, _vp, _f32, _vp, _f32, _vp]),
     "mvrt_svo_dilate": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_erode": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_close": (_i32, [_vp, _i32, _i32, _vp, _vp]),
@@ -184,6 +212,7 @@ SIGNATURES = {
     "mvrt_test_fail_allocation": (_i32, [C.c_int64]),
     "mvrt_test_allocation_state": (_i32, [_vp, _vp, _vp]),
     "mvrt_test_ball_stats": (_i32, [_vp]),
+    "mvrt_test_resample_stats": (_i32, [_vp]),
     "mvrt_test_peak_bytes": (_i32, [_vp, _i32]),
     "mvrt_pt_set_profiling": (_i32, [_vp, _i32]),
     "mvrt_pt_reset_stats": (_i32, [_vp]),
@@ -259,6 +288,24 @@ def ball_stats():
     v = (C.c_uint64 * 5)()
     _check(lib().mvrt_test_ball_stats(v))
     return {"records": [int(v[0]), int(v[1]), int(v[2])], "seeds": int(v[3]), "cells": int(v[4])}
+
+
+def resample_stats():
+    """measuring: what the last resampling this thread ran did: {levels of the destination grid, frontier: the nodes kept per level 1 .. levels, the last entry
+    being the result cells} (mvrt_test_resample_stats)"""
+    v = (C.c_uint64 * 24)()
+    _check(lib().mvrt_test_resample_stats(v))
+    return {"levels": int(v[0]), "frontier": [int(v[l]) for l in range(1, int(v[0]) + 1)]}
+
+
+def cell_transform_from_world(world, src_lower, src_dps, dst_lower, dst_dps):
+    """mvrt_cell_transform_from_world: the CellTransform that aligns two lattices in world space.  world: 3x4 row-major (or 12 numbers), p_dst = W p_src + w;
+    the lattices by their lower corner (3 float32) and dps.  Host only, no GPU call."""
+    w = np.ascontiguousarray(world, np.float64).reshape(12)
+    sl, dl = np.ascontiguousarray(src_lower, np.float32).reshape(3), np.ascontiguousarray(dst_lower, np.float32).reshape(3)
+    out = CellTransform()
+    _check(lib().mvrt_cell_transform_from_world(_hp(w), _hp(sl), float(np.float32(src_dps)), _hp(dl), float(np.float32(dst_dps)), C.byref(out)))
+    return out
 
 
 def allocation_state():
@@ -657,6 +704,37 @@ class IntersectorOctreeGPU:
         ad, rm, cl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().mvrt_svo_combine(self._h, b._h, int(op), _hp(self._offset(offset)), int(flags), C.byref(ad), C.byref(rm), C.byref(cl), stream))
         return ad.value, rm.value, cl.value
+
+    def resample_voxels_device(self, xf, gridRes=None, capacity=0, xyz=None, attribs=None, source=None, stream=None):
+        """mvrt_svo_resample_voxels into caller device arrays of `capacity` voxels (any may be None; all None = the sizing call); returns the count.  gridRes: the
+        destination grid (None = this octree's).  On MvrtError nothing was written."""
+        n = C.c_uint64(0)
+        res = int((self.info().gridRes or 2) if gridRes is None else gridRes)  # (an empty handle has no grid: the call itself refuses it, "no octree")
+        _check(lib().mvrt_svo_resample_voxels(self._h, C.byref(xf), res, int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(source), C.byref(n), stream))
+        return n.value
+
+    def resample_voxels(self, xf, gridRes=None, stream=None):
+        """this set resampled onto a grid of gridRes cells per axis (None = its own) under the CellTransform xf, the INVERSE map from destination cells to source
+        cells: the destination cells whose centre maps into a voxel, in ascending Morton order: {xyz (n, 3) uint32, attribs (n, 8) uint8 = that voxel's colour and
+        emission with alpha 255, source (n,) uint32 = its vIndex}.  The octree is not modified."""
+        n = self.resample_voxels_device(xf, gridRes, stream=stream)
+        xyz, at, src = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint32)
+        if n:
+            self.resample_voxels_device(xf, gridRes, n, xyz, at, src, stream)
+        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "source": src.to_host()}
+
+    def resample(self, xf, dst=None, origin=None, dps=None, gridRes=None, flags=0, stream=None):
+        """mvrt_svo_resample: dst (None = this object) becomes the octree build_voxels would build from resample_voxels(xf, gridRes) with origin, dps, gridRes (None
+        = this octree's own lattice) and `flags` (BUILD_NO_DAG | BUILD_NO_EMBEDDED_MASK).  Returns dst.  Refused when no voxel would be left.  Invalidates
+        device_view() snapshots of dst."""
+        dst = self if dst is None else dst
+        i = self.info() if origin is None or dps is None or gridRes is None else None
+        o = np.ascontiguousarray(i.lower[:] if origin is None else origin, np.float32).reshape(3)
+        dps = np.float32(i.dps if dps is None else dps)
+        res = int((i.gridRes or 2) if gridRes is None else gridRes)
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_resample(self._h, dst._h, C.byref(xf), _hp(o), float(dps), res, int(flags), C.byref(n), stream))
+        return dst
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""

@@ -1,5 +1,5 @@
 // api_voxels.hip -- the C-ABI of libmvrt_hip.so (include/mvrt.h), the voxel-set operators on a built octree: surface extraction, enclosed cells and the fill,
-// coarsening, morphology with the step elements and with the ball, connected components and the two-set operators.  Every refusal the arguments and the handles
+// coarsening, morphology with the step elements and with the ball, connected components, the two-set operators and the affine resampling.  Every refusal the arguments and the handles
 // decide is made here, on the host; the listings never touch the handle, the in-place calls end in adoptSorted (api.hip).
 #include "api_handles.h"
 
@@ -387,5 +387,100 @@ MVRT_EXPORT int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const 
 	if( adoptSorted( a, c.list, st ) ) return 1; // (b == a was read above)
 	if( nAddedOut ) *nAddedOut = c.nAdded;
 	if( nRemovedOut ) *nRemovedOut = c.nRemoved;
+	return 0;
+}
+
+// Affine resampling (kernels_resample.hip).  Every refusal the arguments and the handles decide is made here, on the host: first what the arguments alone decide
+// (a null handle, the transform, the grid), then the handle, as the coarsening does.  The listing reads the sorted codes and the attributes alone; the build hands the list, which stays on the device, to the
+// levels of the voxel-list build, as the coarsening does.
+static_assert( MVRT_TRANSFORM_FRAC_BITS == 24 && sizeof( mvrt_cell_transform ) == 8 + 12 * 8, "mvrt.h and kernels_resample.hip agree on the fixed point and the record" );
+static int resampleSource( const mvrt_svo* src, const char* who, const mvrt_cell_transform* xf, int dstGridRes, SurfaceSource* s )
+{
+	REQUIRE( src, "%s: null handle", who );
+	REQUIRE( xf, "%s: null transform", who );
+	REQUIRE( xf->structBytes == sizeof( mvrt_cell_transform ), "%s: structBytes %u is not sizeof( mvrt_cell_transform ) = %u", who, xf->structBytes,
+			 (unsigned)sizeof( mvrt_cell_transform ) );
+	REQUIRE( xf->reserved == 0u, "%s: the reserved field of the transform is %u, not 0", who, xf->reserved );
+	REQUIRE( resampleTransformValid( xf->m, xf->t ), "%s: an entry of the transform is out of range (|m[k]| <= 2^30, |t[i]| <= 2^52)", who );
+	REQUIRE( levelsOf( dstGridRes ) > 0 && dstGridRes <= ( 1 << 21 ), "%s: dstGridRes %d is not a power of two in [2, 2^21]", who, dstGridRes );
+	return surfaceSource( src, who, s );
+}
+MVRT_EXPORT int mvrt_svo_resample_voxels( const mvrt_svo* src, const mvrt_cell_transform* xf, int dstGridRes, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev,
+										  uint32_t* sourceDev, uint64_t* nOut, void* stream )
+{
+	SurfaceSource s;
+	if( resampleSource( src, "mvrt_svo_resample_voxels", xf, dstGridRes, &s ) ) return 1;
+	return resampleVoxels( s, xf->m, xf->t, (uint32_t)levelsOf( dstGridRes ), capacity, xyzDev, attribsDev, sourceDev, nOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_resample( const mvrt_svo* src, mvrt_svo* dst, const mvrt_cell_transform* xf, const float dstOriginHost[3], float dstDps, int dstGridRes, int buildFlags,
+								   uint64_t* nOut, void* stream )
+{
+	const char* who = "mvrt_svo_resample";
+	if( nOut ) *nOut = 0;
+	REQUIRE( src && dst, "%s: null handle", who );
+	REQUIRE( ( buildFlags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0, "%s: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", who,
+			 buildFlags );
+	SurfaceSource s;
+	if( resampleSource( src, who, xf, dstGridRes, &s ) ) return 1;
+	REQUIRE( dstOriginHost, "%s: null origin", who );
+	const float origin[3] = { dstOriginHost[0], dstOriginHost[1], dstOriginHost[2] }; // (a copy: the caller may pass the info of dst)
+	const uint32_t nSrc = s.nVoxels;
+	hipStream_t st = (hipStream_t)stream;
+	if( ownerDrain( dst ) ) return 1; // steps already issued render the old scene
+	SortedVoxels v;
+	if( resampleList( who, s, xf->m, xf->t, (uint32_t)levelsOf( dstGridRes ), v, st ) ) return 1;
+	REQUIRE( v.n >= 1, "%s: the transform would leave no voxel (no destination cell centre maps into one of the %u voxels)", who, nSrc );
+	SvoBuildResult r;
+	if( svoBuildFromSorted( v.codes, v.attrs, v.n, dstGridRes, buildFlags, st, &r ) ) return 1;
+	r.hasEmission = v.hasEmission;
+	r.totalDumped = nSrc;
+	if( nOut ) *nOut = v.n;
+	return adoptBuild( dst, r, origin, dstDps, dstGridRes, buildFlags ); // (the source is read before the old octree of dst goes)
+}
+// host only, no GPU call: the transform of two lattices in world space
+MVRT_EXPORT int mvrt_cell_transform_from_world( const double world[12], const float srcLower[3], float srcDps, const float dstLower[3], float dstDps, mvrt_cell_transform* out )
+{
+	const char* who = "mvrt_cell_transform_from_world";
+	REQUIRE( world && srcLower && dstLower && out, "%s: null argument", who );
+	for( int k = 0; k < 12; k++ ) REQUIRE( world[k] - world[k] == 0.0, "%s: world[%d] is not finite", who, k );
+	for( int k = 0; k < 3; k++ ) REQUIRE( srcLower[k] - srcLower[k] == 0.0f && dstLower[k] - dstLower[k] == 0.0f, "%s: a lower bound is not finite", who );
+	REQUIRE( srcDps > 0.0f && srcDps - srcDps == 0.0f && dstDps > 0.0f && dstDps - dstDps == 0.0f, "%s: dps %g / %g is not finite and positive", who, (double)srcDps,
+			 (double)dstDps );
+	const double* w = world; // row i: w[4 i .. 4 i + 2] = W, w[4 i + 3] = the translation
+	const double c00 = w[5] * w[10] - w[6] * w[9], c01 = w[6] * w[8] - w[4] * w[10], c02 = w[4] * w[9] - w[5] * w[8];
+	const double det = w[0] * c00 + w[1] * c01 + w[2] * c02;
+	REQUIRE( det != 0.0 && det - det == 0.0, "%s: the world matrix is singular (det = %g)", who, det );
+	const double inv[9] = { c00 / det, ( w[2] * w[9] - w[1] * w[10] ) / det, ( w[1] * w[6] - w[2] * w[5] ) / det,
+							c01 / det, ( w[0] * w[10] - w[2] * w[8] ) / det, ( w[2] * w[4] - w[0] * w[6] ) / det,
+							c02 / det, ( w[1] * w[8] - w[0] * w[9] ) / det, ( w[0] * w[5] - w[1] * w[4] ) / det };
+	for( int k = 0; k < 9; k++ ) REQUIRE( inv[k] - inv[k] == 0.0, "%s: the world matrix is singular (its inverse is not finite)", who );
+	const double ratio = (double)dstDps / (double)srcDps, mOne = 16777216.0 /* 2^24 */, mMax = 1073741824.0 /* 2^30 */, tMax = 4503599627370496.0 /* 2^52 */;
+	mvrt_cell_transform x;
+	x.structBytes = (uint32_t)sizeof( x );
+	x.reserved = 0;
+	const double d[3] = { (double)dstLower[0] - w[3], (double)dstLower[1] - w[7], (double)dstLower[2] - w[11] };
+	for( int i = 0; i < 3; i++ )
+	{
+		for( int j = 0; j < 3; j++ )
+		{
+			const double a = inv[3 * i + j] * ratio * mOne;
+			REQUIRE( a >= -mMax && a <= mMax, "%s: m[%d] = %g * 2^24 is out of range (|m[k]| <= 2^30)", who, 3 * i + j, inv[3 * i + j] * ratio );
+			x.m[3 * i + j] = llrint( a );
+		}
+		const double b = ( ( inv[3 * i] * d[0] + inv[3 * i + 1] * d[1] + inv[3 * i + 2] * d[2] ) - (double)srcLower[i] ) / (double)srcDps;
+		const double tb = b * ( 2.0 * mOne );
+		REQUIRE( tb >= -tMax && tb <= tMax, "%s: t[%d] = %g * 2^25 is out of range (|t[i]| <= 2^52)", who, i, b );
+		x.t[i] = llrint( tb );
+	}
+	*out = x;
+	return 0;
+}
+MVRT_EXPORT int mvrt_test_resample_stats( uint64_t out[24] )
+{
+	const ResampleStats r = resampleLastStats();
+	REQUIRE( out, "mvrt_test_resample_stats: null out" );
+	out[0] = r.levels;
+	for( int l = 1; l < 22; l++ ) out[l] = r.frontier[l];
+	out[22] = out[23] = 0;
 	return 0;
 }

@@ -266,6 +266,22 @@ enum
 int listingTail( const char* who, const char* capacityName, const char* things, bool sizing, uint64_t capacity, uint64_t n );
 void listingRefusal( const char* who, const char* capacityName, const char* things, uint64_t capacity, uint64_t n );
 
+// affine resampling (kernels_resample.hip; mvrt_svo_resample_voxels / mvrt_svo_resample): morton, attrs, nVoxels and levels of the source are read; m[9] and t[3] are
+// the inverse map of mvrt_cell_transform, within its limits (resampleTransformValid), and dstLevels = log2 of the destination gridRes in [1, 21], all checked by the
+// caller.  The calls block, keep their scratch in DevBufs and write NOTHING to the caller's arrays unless they succeed.  A frontier or a result of 2^32 - 1 entries
+// or more is refused; `who` names the call
+struct ResampleStats // what the last refinement of this thread did (tools/resample_bench.py through mvrt_test_resample_stats)
+{
+	uint32_t levels = 0;	 // of the destination grid
+	uint64_t frontier[22] = {}; // frontier[l], l = 1 .. levels: the surviving nodes of level l; frontier[levels] = the result cells
+};
+bool resampleTransformValid( const int64_t m[9], const int64_t t[3] );
+int resampleVoxels( const SurfaceSource& s, const int64_t m[9], const int64_t t[3], uint32_t dstLevels, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* sourceDev,
+					uint64_t* nOut, hipStream_t stream );
+// the same list as sorted codes and attributes for svoBuildFromSorted (left empty when the result is: the caller looks at out.n)
+int resampleList( const char* who, const SurfaceSource& s, const int64_t m[9], const int64_t t[3], uint32_t dstLevels, SortedVoxels& out, hipStream_t stream );
+ResampleStats resampleLastStats(); // of this thread
+
 // coarse cells (kernels_coarsen.hip; mvrt_svo_coarse_voxels / mvrt_svo_coarsen): the n >= 1 sorted codes and Morton-ordered attributes of a build, levelsDown in
 // [1, levels - 1] and minCount in [1, coarseCellCapacity( levelsDown )], all checked by the caller.  The calls block, keep their scratch in DevBufs and write
 // NOTHING to the caller's arrays unless they succeed.

@@ -15,6 +15,8 @@
 //                   records to, clipped to the grid and to the radius.  Host-callable (tests/hip/ball_host.hip).
 //   two sets        combineTranslate (a code moved by an integer offset and clipped to a grid) of kernels_combine.hip, and combineWindow / codeIndexInRange: the
 //                   partner search of a group of ascending codes, bounded once per group.  Host-callable (tests/hip/combine_host.hip).
+//   resampling      resamplePoint (the point rule of mvrt_cell_transform), resampleBox / resampleBoxShift / resampleBoxHoldsVoxel (the conservative test of a node
+//                   of the destination grid) and resampleTransformOk of kernels_resample.hip.  Host-callable (tests/hip/resample_host.hip).
 //   union-find      ufLoad / ufStore / ufFind / ufUnite / ufRoot: the lock-free union-find over node ids that kernels_fill.hip runs on the gaps and
 //                   kernels_components.hip on the voxels.  Device only.
 //   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
@@ -227,6 +229,90 @@ MVRT_HDI uint64_t codeIndexInRange( const uint64_t* __restrict__ codes, uint64_t
 {
 	const uint64_t i = lowerBound( codes, lo, hi, code );
 	return i < n && codes[i] == code ? i : n;
+}
+
+// ---- affine resampling (kernels_resample.hip) ---------------------------------------------------------------------------------------------------------------
+// The inverse map of mvrt_cell_transform (mvrt.h): m in Q24 with |m[k]| <= 2^30, t in Q25 with |t[i]| <= 2^52.  A sample coordinate 2 * c + 1 is below 2^22, so a
+// product is below 2^52 in magnitude and a sum of three plus t below 2^55: nothing here can wrap.  Host-callable (tests/hip/resample_host.hip, which runs under
+// UBSan's signed-overflow check and compares with __int128).
+#define RESAMPLE_FRAC_BITS 24
+struct ResampleXf
+{
+	int64_t m[9], t[3];
+};
+MVRT_HDI bool resampleTransformOk( const int64_t m[9], const int64_t t[3] )
+{
+	const int64_t mMax = (int64_t)1 << 30, tMax = (int64_t)1 << 52;
+	for( int k = 0; k < 9; k++ )
+		if( m[k] < -mMax || m[k] > mMax ) return false;
+	for( int i = 0; i < 3; i++ )
+		if( t[i] < -tMax || t[i] > tMax ) return false;
+	return true;
+}
+// floor( p / 2^(F + 1) ) towards minus infinity, written without a shift of a negative number
+MVRT_HDI int64_t resampleFloor( int64_t p )
+{
+	const int64_t one = (int64_t)1 << ( RESAMPLE_FRAC_BITS + 1 );
+	return p >= 0 ? p / one : -( ( -p + one - 1 ) / one );
+}
+// The point rule: the source cell s the centre of the destination cell c = (c0, c1, c2), each below 2^21, maps into.  True when s lies in [0, 2^srcLevels)^3;
+// s is written either way, a coordinate outside the grid as it is (it fits: |s| < 2^30)
+MVRT_HDI bool resamplePoint( const ResampleXf& xf, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t srcLevels, int64_t s[3] )
+{
+	const int64_t q0 = 2 * (int64_t)c0 + 1, q1 = 2 * (int64_t)c1 + 1, q2 = 2 * (int64_t)c2 + 1, Rs = (int64_t)1 << srcLevels;
+	bool inside = true;
+	for( int i = 0; i < 3; i++ )
+	{
+		s[i] = resampleFloor( xf.m[3 * i] * q0 + xf.m[3 * i + 1] * q1 + xf.m[3 * i + 2] * q2 + xf.t[i] );
+		inside = inside && s[i] >= 0 && s[i] < Rs;
+	}
+	return inside;
+}
+// The node of 2^k cells per axis whose lowest cell is c (k <= 21, c a multiple of 2^k, c + 2^k <= 2^21): the exact bounding box of the source cells of all its
+// sample points, clipped to [0, 2^srcLevels)^3.  Per axis the extremes of a sum of three terms linear in one coordinate each are the sums of the terms' extremes,
+// taken at the first and the last sample coordinate; floor is monotone.  False when the box misses the source grid on some axis; else lo <= hi, inclusive
+MVRT_HDI bool resampleBox( const ResampleXf& xf, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t k, uint32_t srcLevels, uint32_t lo[3], uint32_t hi[3] )
+{
+	const int64_t span = ( (int64_t)1 << k ) - 1, Rs = (int64_t)1 << srcLevels;
+	const int64_t qLo[3] = { 2 * (int64_t)c0 + 1, 2 * (int64_t)c1 + 1, 2 * (int64_t)c2 + 1 };
+	for( int i = 0; i < 3; i++ )
+	{
+		int64_t pMin = xf.t[i], pMax = xf.t[i];
+		for( int j = 0; j < 3; j++ )
+		{
+			const int64_t a = xf.m[3 * i + j] * qLo[j], b = xf.m[3 * i + j] * ( qLo[j] + 2 * span );
+			pMin += a < b ? a : b;
+			pMax += a < b ? b : a;
+		}
+		const int64_t sMin = resampleFloor( pMin ), sMax = resampleFloor( pMax );
+		if( sMax < 0 || sMin >= Rs ) return false;
+		lo[i] = (uint32_t)( sMin < 0 ? 0 : sMin );
+		hi[i] = (uint32_t)( sMax >= Rs ? Rs - 1 : sMax );
+	}
+	return true;
+}
+// the smallest h at which the box [lo, hi] spans at most 2 cells of 2^h per axis: at most 8 coarse cells cover it (h <= the levels of the grid the box lies in)
+MVRT_HDI uint32_t resampleBoxShift( const uint32_t lo[3], const uint32_t hi[3] )
+{
+	uint32_t h = 0;
+	while( ( hi[0] >> h ) - ( lo[0] >> h ) > 1u || ( hi[1] >> h ) - ( lo[1] >> h ) > 1u || ( hi[2] >> h ) - ( lo[2] >> h ) > 1u ) h++;
+	return h;
+}
+// whether one of the n sorted codes lies in one of the coarse cells that cover the box: per coarse cell one search, a voxel is there when the first code not below
+// the cell's first is below the next cell's first ( ( code + 1 ) << 3h <= 2^63 ).  Conservative: the cover may be larger than the box, never smaller
+MVRT_HDI bool resampleBoxHoldsVoxel( const uint64_t* __restrict__ codes, uint64_t n, const uint32_t lo[3], const uint32_t hi[3] )
+{
+	const uint32_t h = resampleBoxShift( lo, hi ), shift = 3u * h;
+	const uint32_t x0 = lo[0] >> h, y0 = lo[1] >> h, z0 = lo[2] >> h, nx = ( hi[0] >> h ) - x0, ny = ( hi[1] >> h ) - y0, nz = ( hi[2] >> h ) - z0;
+	for( uint32_t dz = 0; dz <= nz; dz++ )
+		for( uint32_t dy = 0; dy <= ny; dy++ )
+			for( uint32_t dx = 0; dx <= nx; dx++ )
+			{
+				const uint64_t code = mortonEncode( x0 + dx, y0 + dy, z0 + dz );
+				const uint64_t i = lowerBound( codes, 0, n, code << shift );
+				if( i < n && codes[i] < ( code + 1ull ) << shift ) return true;
+			}
+	return false;
 }
 
 // ---- union-find over node ids (kernels_fill.hip, kernels_components.hip) --------------------------------------------------------------------------------------

@@ -1,0 +1,135 @@
+"""The resampling interface: the header, the Python table and the C++ mirror declare the calls, and tests/cpp/resample_usage.cpp, which pins their C signatures and
+the layout of mvrt_cell_transform, compiles and links against the library -- without a GPU, where it also checks the refusals the host makes before any GPU work.
+On a GPU the program is run, and every line it prints is compared with what the Python wrapper and the model of tests/resample_expected.py give for the same set."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import massivevoxelraytracing_amd as mv
+import resample_expected as E
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALLS = ("mvrt_svo_resample_voxels", "mvrt_svo_resample", "mvrt_cell_transform_from_world", "mvrt_test_resample_stats")
+
+
+def compile_usage(tmp_path):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "resample_usage"
+    libdir = os.path.dirname(mv.LIB_PATH)
+    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "resample_usage.cpp"), "-o", str(exe),
+                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    return exe, libdir
+
+
+def test_header_python_and_mirror_declare_the_interface():
+    src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
+    for name in CALLS:
+        assert name + "(" in src and name in mv.SIGNATURES
+    assert [len(mv.SIGNATURES[n][1]) for n in CALLS] == [9, 9, 6, 1]
+    assert "#define MVRT_TRANSFORM_FRAC_BITS 24\n" in src and mv.TRANSFORM_FRAC_BITS == E.F == 24
+    assert "typedef struct mvrt_cell_transform" in src and "uint32_t structBytes, reserved;" in src and "int64_t m[9];" in src and "int64_t t[3];" in src
+    assert C.sizeof(mv.CellTransform) == 104 and mv.CellTransform.m.offset == 8 and mv.CellTransform.t.offset == 80
+    for fact in ("A signed permutation about the grid centre with Rd == Rs gives a bijection", "A = I/2 gives s = c >> 1", "A = 2I gives s = 2c + 1", "NOT the count rule"):
+        assert fact in src  # the facts that pin the conventions are stated in the header
+    for name in ("resample_voxels_device", "resample_voxels", "resample"):
+        assert callable(getattr(mv.IntersectorOctreeGPU, name))
+    assert callable(mv.cell_transform_from_world) and callable(mv.resample_stats)
+    hpp = open(os.path.join(ROOT, "include", "mvrt", "IntersectorOctreeGPU.hpp")).read()
+    for name in ("uint64_t resampleVoxels(", "void resampleVoxels(", "uint64_t resample(", "static mvrt_cell_transform cellTransformFromWorld("):
+        assert name in hpp
+
+
+def test_refusals_that_need_no_gpu():
+    """a null handle, an empty handle, a bad record, an entry out of range and a gridRes that is no power of two are refused on the host, before any GPU work: first
+    what the arguments alone decide, then the handle"""
+    lib = mv.lib()
+    svo, other = mv.IntersectorOctreeGPU(), mv.IntersectorOctreeGPU()
+    xf = mv.CellTransform.make(*E.identity())
+    assert lib.mvrt_svo_resample_voxels(None, C.byref(xf), 16, 0, None, None, None, None, None) != 0 and b"null handle" in lib.mvrt_last_error()
+    assert lib.mvrt_svo_resample(None, svo._h, C.byref(xf), None, 1.0, 16, 0, None, None) != 0 and b"null handle" in lib.mvrt_last_error()
+    assert lib.mvrt_svo_resample(svo._h, None, C.byref(xf), None, 1.0, 16, 0, None, None) != 0 and b"null handle" in lib.mvrt_last_error()
+    assert lib.mvrt_svo_resample_voxels(svo._h, None, 16, 0, None, None, None, None, None) != 0 and b"null transform" in lib.mvrt_last_error()
+
+    def record(**fields):
+        x = mv.CellTransform.make(*E.identity())
+        for k, v in fields.items():
+            setattr(x, k, v)
+        return x
+
+    def entry(k, v, t=False):
+        x = mv.CellTransform.make(*E.identity())
+        (x.t if t else x.m)[k] = v
+        return x
+
+    cases = [(xf, 16, "no octree"), (record(structBytes=96), 16, "structBytes"), (record(structBytes=0), 16, "structBytes"), (record(reserved=1), 16, "reserved"),
+             (entry(4, (1 << 30) + 1), 16, "out of range"), (entry(0, -(1 << 30) - 1), 16, "out of range"), (entry(2, (1 << 52) + 1, True), 16, "out of range"),
+             (entry(1, -(1 << 63), True), 16, "out of range"), (xf, 3, "power of two"), (xf, 0, "power of two"), (xf, -4, "power of two"), (xf, 1 << 22, "power of two"),
+             (entry(4, 1 << 30), 16, "no octree"), (entry(2, -(1 << 52), True), 2, "no octree"), (xf, 1 << 21, "no octree")]  # (the limits themselves are legal)
+    allocs = mv.allocation_state()[2]
+    for x, r, text in cases:
+        for call in (lambda: svo.resample_voxels_device(x, r), lambda: svo.resample_voxels(x, r), lambda: svo.resample(x, gridRes=r, origin=(0, 0, 0), dps=1.0),
+                     lambda: svo.resample(x, other, gridRes=r, origin=(0, 0, 0), dps=1.0)):
+            with pytest.raises(mv.MvrtError, match=text):
+                call()
+    with pytest.raises(mv.MvrtError, match="unsupported flags"):
+        svo.resample(xf, gridRes=16, origin=(0, 0, 0), dps=1.0, flags=4)
+    assert mv.allocation_state()[2] == allocs  # no device allocation was attempted
+
+
+def test_the_python_record_carries_what_the_c_side_reads():
+    m, t = E.identity()
+    x = mv.CellTransform.make(m, t)
+    assert x.structBytes == 104 and x.reserved == 0 and np.array_equal(x.arrays()[0], m) and np.array_equal(x.arrays()[1], t)
+    big = mv.CellTransform.make([1 << 30] * 9, [-(1 << 52)] * 3)
+    assert big.m[8] == 1 << 30 and big.t[0] == -(1 << 52)
+    assert np.array_equal(mv.CellTransform.from_cells(np.eye(3) * 0.5, (1.5, 0, -2)).arrays()[1], [3 << 24, 0, -(4 << 24)])
+
+
+def test_cpp_mirror_resample_methods_compile_link_and_refuse(tmp_path):
+    exe, libdir = compile_usage(tmp_path)
+    r = subprocess.run([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")), capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0 and "usage" in r.stdout and "(0 host checks failed)" in r.stdout
+
+
+def checksum(r):
+    """the sum tests/cpp/resample_usage.cpp prints, modulo 2^64"""
+    words = np.ascontiguousarray(r["attribs"]).view("<u4").reshape(-1, 2)
+    s = 0
+    for i, (v, w, src) in enumerate(zip(r["xyz"].tolist(), words.tolist(), r["source"].tolist())):
+        s += (i + 1) * (v[0] + 17 * v[1] + 289 * v[2] + 4913 * src) + w[0] + 3 * w[1]
+    return s % (1 << 64)
+
+
+@pytest.mark.gpu
+def test_cpp_mirror_agrees_with_the_python_wrapper(tmp_path):
+    exe, _ = compile_usage(tmp_path)
+    out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
+    print(out)
+    ell = np.array([(x, y, z) for z in range(2, 5) for y in range(1, 12) for x in range(1, 14) if y < 4 or x < 3], np.uint32)
+    colour = np.zeros((len(ell), 2), "<u4")
+    colour[:, 0] = ell[:, 0] + 0x100 * ell[:, 1] + 0x10000 * ell[:, 2]
+    colour[ell[:, 0] == 1, 1] = 0x700
+    at = colour.view(np.uint8).reshape(-1, 8)
+    src, dst = mv.IntersectorOctreeGPU(), mv.IntersectorOctreeGPU()
+    src.build_voxels(ell, at, dps=1.0 / 16, gridRes=16)
+    turn = [0, -1, 0, 1, 1, 0, 0, 0, 0, 0, 1, 0]
+    xf = mv.cell_transform_from_world(turn, (0, 0, 0), 1.0 / 16, (0, 0, 0), 1.0 / 16)
+    got, want = src.resample_voxels(xf), E.dense(ell, at, 16, *xf.arrays(), 16)
+    assert all(np.array_equal(got[k], want[k]) for k in ("xyz", "attribs", "source")) and len(got["xyz"]) == len(ell)
+    # p_dst = (1 - y, x): the cell (x, y) goes to (15 - y, x)
+    assert set(map(tuple, got["xyz"].tolist())) == set((15 - int(y), int(x), int(z)) for x, y, z in ell)
+    assert "turn n %d sized %d of %d checksum %d\n" % (len(got["xyz"]), src.resample_voxels_device(xf), len(ell), checksum(got)) in out
+    fine = mv.cell_transform_from_world(turn, (0, 0, 0), 1.0 / 16, (0, 0, 0), 1.0 / 32)
+    src.resample(fine, dst, dps=1.0 / 32, gridRes=32)
+    i = dst.info()
+    assert "fine n %d voxels %d emission %d dps %.9g source voxels %d\n" % (8 * len(ell), i.numberOfVoxels, i.hasEmission, i.dps, len(ell)) in out
+    assert (i.numberOfVoxels, i.hasEmission, i.totalDumpedVoxels) == (8 * len(ell), 1, len(ell))
+    src.resample(xf)
+    assert "self n %d voxels %d\n" % (len(ell), src.info().numberOfVoxels) in out and np.array_equal(src.read_voxels()[0], want["xyz"])
