@@ -1,7 +1,8 @@
 // voxel_mesh -- the reference voxelizer's "Save As Mesh" (voxMesh.cpp:111-219) without the GUI: voxelize a Wavefront .obj on the GPU and write the exposed
 // faces of the voxel set as a PLY quad mesh, one colour per face from its voxel.
 //
-//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]
+//   voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --fill-nearest | --exterior]
+//              [--solid]
 //              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]
 //              [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]
 //              [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]
@@ -18,6 +19,11 @@
 // --exterior: the same faces as --fill writes, without touching the octree: the faces that look into an enclosed cell are dropped from the masks
 // (mvrt_svo_surface_exterior_masks) and the mesh is extracted from those (mvrt_svo_surface_*_masked); a line reports the faces before and after.  With every
 // other flag except --fill: one or the other.
+// --fill-nearest: as --fill, but every filled cell takes the colour and emission of its nearest voxel (mvrt_svo_fill_enclosed_nearest): the lowest vIndex among
+// the voxels at the exact smallest distance, whatever that distance.  At the place of --fill; the line also reports the deepest squared distance.  Not with
+// --fill or --exterior.
+// --solid: the same fill, applied to the scene's model straight after it is voxelised and BEFORE --union / --intersect / --subtract / --xor, so that the faces a
+// second model cuts into it carry the colours of the shell: --solid --subtract other.obj.  With every other flag that --fill combines with.
 // --lod K: the octree is coarsened in place by K levels (mvrt_svo_coarsen: gridRes >> K, a cell is a voxel when it holds at least --lod-min-count fine voxels,
 // default 1) before anything else is done with it; a line reports voxels and gridRes before and after.  With every other flag.
 // --dilate K, --erode K, --close K, --open K (one of them): K steps of the operator on the voxel set (mvrt_svo_dilate / _erode / _close / _open) with --element
@@ -53,7 +59,7 @@
 
 int main( int argc, char** argv )
 {
-	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false, fill = false, exterior = false;
+	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false, fill = false, exterior = false, fillNearest = false, solid = false;
 	int aoSamples = 64;
 	float aoRadiusVoxels = 8.0f;
 	int lod = 0;
@@ -79,6 +85,8 @@ int main( int argc, char** argv )
 		else if( !std::strcmp( argv[i], "--conservative" ) ) conservative = true;
 		else if( !std::strcmp( argv[i], "--fill" ) ) fill = true;
 		else if( !std::strcmp( argv[i], "--exterior" ) ) exterior = true;
+		else if( !std::strcmp( argv[i], "--fill-nearest" ) ) fillNearest = true;
+		else if( !std::strcmp( argv[i], "--solid" ) ) solid = true;
 		else if( !std::strcmp( argv[i], "--ao" ) )
 		{
 			ao = true;
@@ -153,7 +161,8 @@ int main( int argc, char** argv )
 	}
 	if( pos.size() != 3 )
 	{
-		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]] [--fill | --exterior]\n"
+		std::printf( "usage: voxel_mesh scene.obj gridRes out.ply [--no-weld] [--merge | --merge-any] [--conservative] [--lod K [--lod-min-count C]]\n"
+					 "                  [--fill | --fill-nearest | --exterior] [--solid]\n"
 					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]\n"
 					 "                  [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]\n"
 					 "                  [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]\n"
@@ -171,6 +180,9 @@ int main( int argc, char** argv )
 					 "  --keep-largest K, --min-component N  keep only the components of at least N voxels and, of those, the K largest; after the\n"
 					 "               operators above and before --fill / --exterior\n"
 					 "  --fill       fill the empty cells the voxel shell encloses (white voxels) before the surface is extracted\n"
+					 "  --fill-nearest  the same fill, every cell in the colour of its nearest voxel, at the place of --fill.  Not with --fill or --exterior\n"
+					 "  --solid      that fill on the scene's model straight after it is voxelised, before --union / --intersect / --subtract / --xor: the faces\n"
+					 "               the second model cuts carry the colours of the shell\n"
 					 "  --exterior   drop the faces that look into an enclosed cell instead; the octree stays as built.  Not with --fill\n"
 					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
 					 "               --ao-radius voxels (default 8); not with --merge / --merge-any\n"
@@ -192,6 +204,11 @@ int main( int argc, char** argv )
 	if( fill && exterior )
 	{
 		std::fprintf( stderr, "voxel_mesh: --exterior cannot be combined with --fill: one or the other (both write the same faces)\n" );
+		return 2;
+	}
+	if( fillNearest && ( fill || exterior ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: --fill-nearest cannot be combined with --fill or --exterior: one of the three\n" );
 		return 2;
 	}
 	if( morphOps > 1 || !elementOk || ( morphOps == 1 && ( morphSteps < 1 || morphSteps > 64 ) ) )
@@ -242,6 +259,17 @@ int main( int argc, char** argv )
 	void* stream = nullptr;
 	mvrt::IntersectorOctreeGPU svo;
 	svo.build( vertices, vcolors, vemissions, nullptr, stream, origin, dps, gridRes, conservative ? MVRT_BUILD_CONSERVATIVE : 0 );
+	// --fill-nearest / --solid: every enclosed cell takes the colour of its nearest voxel; `label` starts the line
+	auto fillWithNearest = [&]( const char* label ) {
+		const uint32_t before = svo.m_numberOfVoxels;
+		uint64_t nRegions = 0, stats[8] = {};
+		const uint64_t nCells = svo.enclosedNearest( 0, nullptr, nullptr, nullptr, nullptr, nullptr, &nRegions, stream );
+		const uint64_t nFilled = svo.fillEnclosedNearest( stream );
+		mvrt::check( mvrt_test_enclosed_nearest_stats( stats ), "mvrt_test_enclosed_nearest_stats" ); // (of the fill: the deepest squared distance)
+		std::printf( "%s: voxels %u -> %u, enclosed cells %llu in %llu regions, deepest d2 %llu, filled %llu\n", label, before, svo.m_numberOfVoxels, (unsigned long long)nCells,
+					 (unsigned long long)nRegions, (unsigned long long)stats[7], (unsigned long long)nFilled );
+	};
+	if( solid ) fillWithNearest( "solid" ); // before the second model is combined
 	if( otherObj ) // before anything else is done with the octree
 	{
 		mvrt::IntersectorOctreeGPU other;
@@ -331,6 +359,7 @@ int main( int argc, char** argv )
 		std::printf( "fill: voxels %u -> %u, enclosed cells %llu in %llu regions, filled %llu\n", before, svo.m_numberOfVoxels, (unsigned long long)nCells,
 					 (unsigned long long)nRegions, (unsigned long long)nFilled );
 	}
+	if( fillNearest ) fillWithNearest( "fill-nearest" );
 	std::vector<uint32_t> xyz, attribs;
 	svo.readVoxels( xyz, attribs, stream );
 

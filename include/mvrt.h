@@ -215,6 +215,32 @@ int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* x
  * call succeeds with *nFilledOut = 0 and leaves the handle untouched (no rebuild, views stay valid).  Refused with the handle unchanged: an upload, an empty
  * handle, and numberOfVoxels + nCells >= 2^32 - 1 (the message names the count).  nFilledOut may be NULL. */
 int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8] /* VoxelAttirb, NULL = white, no emission */, uint64_t* nFilledOut, void* stream );
+/* The enclosed cells with their nearest voxel, and the fill that takes its colours from it (new; the reference has none).  With A = the voxel set and c an
+ * enclosed cell:
+ *   - d2(c) = min over v in A of |c - v|^2 and near(c) = the lowest vIndex among the voxels that attain the minimum, as defined for mvrt_svo_distance_cells below.
+ *     The minimum is over ALL of A: there is no radius.
+ *   - dist2 < 2^20 always: no voxel lies in the open ball of radius sqrt( d2 ) around c, and every cell of that ball is an enclosed cell of c's region.  A
+ *     listing holds fewer than 2^32 cells, so ( 4 / 3 ) pi d2^( 3 / 2 ) < 2^32.
+ * mvrt_svo_enclosed_nearest: cells, order, xyzDev and regionDev are exactly what mvrt_svo_enclosed_cells writes (ascending Morton code), so the arrays of the two
+ * calls align.  dist2Dev = d2(c), nearestDev = near(c) as a vIndex, attribsDev = colour RGB and emission RGB of voxel near(c) with both alpha bytes 255 (8 bytes
+ * per cell; the rule of MVRT_VOXEL_SET and of the ball dilation).  Together they are the exact interior distance field of a closed shape: the depth of every
+ * inside cell, and the largest inscribed ball of a cavity.  The call follows the rules of mvrt_svo_enclosed_cells word for word: every octree this library built or
+ * edited is accepted, in every flavour (only the codes and the attributes are read); an upload is refused ("keeps no Morton codes"), an empty handle too ("no
+ * octree"), both before any GPU work.  The handle is never modified.  The call blocks.  `capacity` cells per array; any output may be NULL, all five arrays NULL is
+ * the sizing call (capacity is then ignored), which costs what the sizing call of mvrt_svo_enclosed_cells costs: the distances are not computed.  A capacity
+ * below the count is an error: the counts are still returned and NOTHING is written.  A listing of 2^32 cells or more is refused on the host, the message names the
+ * count and the counts are still returned.  Zero enclosed cells is a success with both counts 0.  A failed allocation of scratch returns an error, leaves the
+ * octree whole, leaks nothing and has written nothing. */
+int mvrt_svo_enclosed_nearest( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev /* 3 per cell */, uint32_t* regionDev, uint32_t* dist2Dev,
+							   uint32_t* nearestDev /* vIndex */, uint32_t* attribsDev /* 8 bytes per cell */, uint64_t* nCellsOut, uint64_t* nRegionsOut, void* stream );
+/* Fill the enclosed cells with the colours of the shell: the handle's octree becomes exactly what mvrt_svo_edit_voxels leaves when given the cells of
+ * mvrt_svo_enclosed_nearest with the attributes it lists and MVRT_VOXEL_SET.  near(c) is taken on the set BEFORE the fill.  A shell with emission makes emissive
+ * inside cells: hasEmission is recomputed over all voxels, and a cell behind an emissive voxel carries that voxel's emission bytes.  Everything else follows
+ * mvrt_svo_fill_enclosed word for word: the cells never travel to the host; failures and ordering are the edit's (a failure before the new arrays are adopted
+ * leaves the handle unchanged, one after that leaves it empty; steps issued before finish first; every mvrt_device_octree view is invalidated); with zero enclosed
+ * cells the call succeeds with *nFilledOut = 0 and leaves the handle untouched (no rebuild, views stay valid).  Refused with the handle unchanged: an upload, an
+ * empty handle, and numberOfVoxels + nCells >= 2^32 - 1 (the message names the count).  nFilledOut may be NULL.  mvrt_svo_fill_enclosed itself is unchanged. */
+int mvrt_svo_fill_enclosed_nearest( mvrt_svo* svo, uint64_t* nFilledOut, void* stream );
 
 /* A coarser level of detail of the voxel set, made from the voxels themselves (new; the reference voxelizes the triangles again at every resolution, and a set
  * built from a voxel list, an edit, a fill or an upload has no triangles).  Definitions, with R = gridRes of the source, L = log2 R, k = levelsDown in
@@ -940,6 +966,10 @@ int mvrt_test_ball_stats( uint64_t out[5] );
 /* Measuring (tools/resample_bench.py): what the last resampling this thread ran did: out[0] = L, the levels of the destination grid, out[l] for l = 1 .. L = the
  * nodes of level l its frontier kept (out[L] = the result cells; 0 from the level on at which nothing was left), the rest 0. */
 int mvrt_test_resample_stats( uint64_t out[24] );
+/* Measuring (tools/enclosed_nearest_bench.py): what the last mvrt_svo_enclosed_nearest or mvrt_svo_fill_enclosed_nearest of this thread did: out[0] = its enclosed
+ * cells, out[1..3] = the gaps of the passes along x, y and z, out[4..6] = the longest gap per axis in cells, out[7] = the deepest d2.  A call that ran no pass
+ * (the sizing call, a refusal, zero cells) leaves all but out[0] at 0. */
+int mvrt_test_enclosed_nearest_stats( uint64_t out[8] );
 int mvrt_pt_set_profiling( mvrt_pt* pt, int enabled ); /* HIP events on `stream` around each kernel of step(); read by get_stats */
 int mvrt_pt_reset_stats( mvrt_pt* pt );
 int mvrt_pt_get_stats( mvrt_pt* pt, void* stream, mvrt_pt_stats* out ); /* synchronises the stream */

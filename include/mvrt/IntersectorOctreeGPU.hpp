@@ -183,6 +183,45 @@ struct IntersectorOctreeGPU
 		refresh();
 		return nFilled;
 	}
+	// the same cells with their nearest voxel, without a radius (mvrt_svo_enclosed_nearest / mvrt_svo_fill_enclosed_nearest; semantics in mvrt.h).  Device-pointer
+	// form: any output may be nullptr, all nullptr = the sizing call, which computes no distance; returns the cell count.
+	uint64_t enclosedNearest( uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, uint64_t* nRegions,
+							  void* stream ) const
+	{
+		uint64_t nCells = 0;
+		check( mvrt_svo_enclosed_nearest( m_handle, capacity, xyzDev, regionDev, dist2Dev, nearestDev, attribsDev, &nCells, nRegions, stream ), "IntersectorOctreeGPU::enclosedNearest" );
+		return nCells;
+	}
+	// host-vector form: xyz and region as enclosedCells gives them, dist2 = 1 entry per cell (the exact squared distance to the set, below 2^20), nearest = 1 (the
+	// vIndex of the nearest voxel, the lowest on a tie), attribs = 2 (that voxel's colour and emission, alpha 255); returns the number of regions
+	uint64_t enclosedNearest( std::vector<uint32_t>& xyz, std::vector<uint32_t>& region, std::vector<uint32_t>& dist2, std::vector<uint32_t>& nearest, std::vector<uint32_t>& attribs,
+							  void* stream ) const
+	{
+		uint64_t nRegions = 0;
+		const uint64_t n = enclosedNearest( 0, nullptr, nullptr, nullptr, nullptr, nullptr, &nRegions, stream );
+		xyz.resize( n * 3 );
+		region.resize( n );
+		dist2.resize( n );
+		nearest.resize( n );
+		attribs.resize( n * 2 );
+		Staged x( nullptr, n * 12, stream ), r( nullptr, n * 4, stream ), d( nullptr, n * 4, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
+		if( n ) enclosedNearest( n, (uint32_t*)x.p, (uint32_t*)r.p, (uint32_t*)d.p, (uint32_t*)v.p, (uint32_t*)a.p, nullptr, stream );
+		fetch( xyz, x, stream );
+		fetch( region, r, stream );
+		fetch( dist2, d, stream );
+		fetch( nearest, v, stream );
+		fetch( attribs, a, stream );
+		return nRegions;
+	}
+	// every enclosed cell becomes a voxel with the colour and emission of its nearest voxel, taken on the set before the fill, as editVoxels would set it; returns
+	// the number of cells filled.  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
+	uint64_t fillEnclosedNearest( void* stream = nullptr )
+	{
+		uint64_t nFilled = 0;
+		check( mvrt_svo_fill_enclosed_nearest( m_handle, &nFilled, stream ), "IntersectorOctreeGPU::fillEnclosedNearest" );
+		refresh();
+		return nFilled;
+	}
 
 	// a coarser level of detail from the voxels themselves (mvrt_svo_coarse_voxels / mvrt_svo_coarsen; semantics in mvrt.h): the cells (x >> k, y >> k, z >> k),
 	// k = levelsDown, that hold at least minCount voxels, each with the integer mean attribute.  Device-pointer form: any output may be nullptr, all nullptr = the

@@ -120,6 +120,8 @@ SIGNATURES = {
     "mvrt_svo_surface_merged_masked": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_enclosed_cells": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_fill_enclosed": (_i32, [_vp, _vp, _vp, _vp]),
+    "mvrt_svo_enclosed_nearest": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_fill_enclosed_nearest": (_i32, [_vp, _vp, _vp]),
     "mvrt_svo_coarse_voxels": (_i32, [_vp, _i32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_coarsen": (_i32, [_vp, _vp, _i32, _u64, _i32, _vp]),
     "mvrt_svo_dilation_cells": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),
@@ -212,6 +214,7 @@ SIGNATURES = {
     "mvrt_test_fail_allocation": (_i32, [C.c_int64]),
     "mvrt_test_allocation_state": (_i32, [_vp, _vp, _vp]),
     "mvrt_test_ball_stats": (_i32, [_vp]),
+    "mvrt_test_enclosed_nearest_stats": (_i32, [_vp]),
     "mvrt_test_resample_stats": (_i32, [_vp]),
     "mvrt_test_peak_bytes": (_i32, [_vp, _i32]),
     "mvrt_pt_set_profiling": (_i32, [_vp, _i32]),
@@ -288,6 +291,14 @@ def ball_stats():
     v = (C.c_uint64 * 5)()
     _check(lib().mvrt_test_ball_stats(v))
     return {"records": [int(v[0]), int(v[1]), int(v[2])], "seeds": int(v[3]), "cells": int(v[4])}
+
+
+def enclosed_nearest_stats():
+    """measuring: what the last enclosed_nearest / fill_enclosed_nearest this thread ran did: {cells, gaps: per pass along x, y, z, longest: the longest gap per
+    axis in cells, deepest: the largest d2}; a call that ran no pass leaves all but cells at 0 (mvrt_test_enclosed_nearest_stats)"""
+    v = (C.c_uint64 * 8)()
+    _check(lib().mvrt_test_enclosed_nearest_stats(v))
+    return {"cells": int(v[0]), "gaps": [int(v[1]), int(v[2]), int(v[3])], "longest": [int(v[4]), int(v[5]), int(v[6])], "deepest": int(v[7])}
 
 
 def resample_stats():
@@ -515,6 +526,32 @@ class IntersectorOctreeGPU:
         a = None if attrib is None else np.ascontiguousarray(attrib).view(np.uint8).reshape(8)
         n = C.c_uint64(0)
         _check(lib().mvrt_svo_fill_enclosed(self._h, _hp(a), C.byref(n), stream))
+        return n.value
+
+    def enclosed_nearest_device(self, capacity=0, xyz=None, region=None, dist2=None, nearest=None, attribs=None, stream=None):
+        """mvrt_svo_enclosed_nearest into caller device arrays of `capacity` cells (any may be None; all None = the sizing call, which runs no distance pass);
+        returns (nCells, nRegions).  On MvrtError nothing was written."""
+        nc, nr = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_enclosed_nearest(self._h, int(capacity), _dev_ptr(xyz), _dev_ptr(region), _dev_ptr(dist2), _dev_ptr(nearest), _dev_ptr(attribs), C.byref(nc),
+                                               C.byref(nr), stream))
+        return nc.value, nr.value
+
+    def enclosed_nearest(self, stream=None):
+        """the enclosed cells of enclosed_cells(), in its order, with their nearest voxel: {xyz (n, 3) uint32, region (n,) uint32, dist2 (n,) uint32 = the exact
+        squared distance to the set (no radius; below 2^20), nearest (n,) uint32 = the lowest vIndex among the voxels at that distance, attribs (n, 8) uint8 = that
+        voxel's colour and emission with alpha 255, nRegions}"""
+        n, nr = self.enclosed_nearest_device(stream=stream)
+        xyz, region, d2, near, at = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
+        if n:
+            self.enclosed_nearest_device(n, xyz, region, d2, near, at, stream)
+        return {"xyz": xyz.to_host(), "region": region.to_host(), "dist2": d2.to_host(), "nearest": near.to_host(), "attribs": at.to_host(), "nRegions": nr}
+
+    def fill_enclosed_nearest(self, stream=None):
+        """mvrt_svo_fill_enclosed_nearest: every enclosed cell becomes a voxel with the colour and emission of its nearest voxel (taken on the set before the
+        fill), exactly as edit_voxels would set the cells and attribs of enclosed_nearest(); returns the number of cells filled (0: the handle was not touched).
+        Invalidates device_view() snapshots otherwise."""
+        n = C.c_uint64(0)
+        _check(lib().mvrt_svo_fill_enclosed_nearest(self._h, C.byref(n), stream))
         return n.value
 
     def coarse_voxels_device(self, levels_down, min_count=1, capacity=0, xyz=None, attribs=None, count=None, stream=None):

@@ -138,6 +138,53 @@ MVRT_EXPORT int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribH
 	return 0;
 }
 
+// The same cells with their nearest voxel, and the fill that takes its colours from them (kernels_nearest.hip).  The fill is mvrt_svo_fill_enclosed with one
+// attribute per cell: the same route through the edit, the same refusals in the same order.
+MVRT_EXPORT int mvrt_svo_enclosed_nearest( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev,
+										   uint64_t* nCellsOut, uint64_t* nRegionsOut, void* stream )
+{
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_enclosed_nearest", &s ) ) return 1;
+	return enclosedNearest( s, capacity, xyzDev, regionDev, dist2Dev, nearestDev, attribsDev, nCellsOut, nRegionsOut, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_fill_enclosed_nearest( mvrt_svo* svo, uint64_t* nFilledOut, void* stream )
+{
+	if( nFilledOut ) *nFilledOut = 0;
+	SurfaceSource s;
+	if( surfaceSource( svo, "mvrt_svo_fill_enclosed_nearest", &s ) ) return 1;
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf xyz, attribs;
+	uint64_t nCells = 0;
+	if( enclosedNearestUnordered( s, xyz, attribs, &nCells, st ) ) return 1; // (near is taken on the set as it is now)
+	if( nCells == 0 ) return 0; // nothing to fill: the handle is not touched
+	REQUIRE( (uint64_t)svo->oct.nVoxels + nCells < 0xFFFFFFFFull,
+			 "mvrt_svo_fill_enclosed_nearest: %llu voxels and %llu enclosed cells exceed the 32-bit index range of the builder", (unsigned long long)svo->oct.nVoxels,
+			 (unsigned long long)nCells );
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
+	const mvrt_svo_info& info = svo->oct.info;
+	SvoBuildResult r;
+	int structural = 0;
+	uint32_t he = 0;
+	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nCells, (int)info.gridRes,
+					   svo->oct.buildFlags, st, &r, &structural, &he ) )
+		return 1;
+	REQUIRE( structural, "mvrt_svo_fill_enclosed_nearest: internal error: the enclosed cells hold voxels" ); // (every cell is an insert)
+	xyz.release();
+	attribs.release();
+	if( adoptOnOwnGrid( svo, r, svo->oct.buildFlags ) ) return 1;
+	if( nFilledOut ) *nFilledOut = nCells;
+	return 0;
+}
+MVRT_EXPORT int mvrt_test_enclosed_nearest_stats( uint64_t out[8] )
+{
+	const NearestStats t = nearestLastStats();
+	REQUIRE( out, "mvrt_test_enclosed_nearest_stats: null out" );
+	out[0] = t.cells;
+	for( int k = 0; k < 3; k++ ) out[1 + k] = t.gaps[k], out[4 + k] = t.longest[k];
+	out[7] = t.deepest;
+	return 0;
+}
+
 // A coarser level of detail (kernels_coarsen.hip).  Every refusal is made here, on the host: first what the arguments alone decide, then the handle.  The listing
 // reads the sorted codes and the attributes alone; the build hands the list, which stays on the device, to the levels of the voxel-list build.
 static int coarsenSource( const mvrt_svo* svo, const char* who, int levelsDown, uint64_t minCount )

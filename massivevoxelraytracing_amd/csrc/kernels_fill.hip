@@ -213,12 +213,7 @@ __global__ void __launch_bounds__( FB ) kFillAttribs( uint2 attrib, uint64_t n, 
 	if( i < n ) out[i] = attrib;
 }
 
-// what the classification leaves: the sorted linear keys, the flattened roots (node i + 1 = gap i; root 0 = EXTERIOR) and, for the emit, the n + 1 cell offsets
-struct Classified
-{
-	DevBuf count, lin, root, offs;
-	uint64_t nCells = 0, nRegions = 0;
-};
+typedef EnclosedClassified Classified; // (launch.h)
 // keys, sort, parents, unions, flatten: lin and root.  nRegions is on its way to the host: valid once the stream has been waited for
 int classifyGaps( const SurfaceSource& s, Classified* out, hipStream_t st )
 {
@@ -263,6 +258,20 @@ int launchEmit( const SurfaceSource& s, const Classified& c, uint64_t* codes, ui
 }
 } // namespace
 
+int enclosedClassify( const SurfaceSource& s, EnclosedClassified* out, hipStream_t st ) { return classify( s, out, st ); }
+
+int enclosedRegionRanks( const uint32_t* roots, uint32_t nCells, uint32_t nVoxels, DevBuf& firstCell, DevBuf& rank1, hipStream_t st )
+{
+	const uint64_t nNodes = (uint64_t)nVoxels + 1;
+	if( firstCell.alloc( nNodes * 4 ) ) return 1;
+	MVRT_HIP( hipMemsetAsync( firstCell.p, 0xFF, nNodes * 4, st ) );
+	hipLaunchKernelGGL( kFillFirstCells, dim3( divUp( nCells, FB ) ), dim3( FB ), 0, st, roots, nCells, firstCell.as<uint32_t>() );
+	MVRT_HIP( hipGetLastError() );
+	hipcub::CountingInputIterator<uint32_t> counting( 0u );
+	hipcub::TransformInputIterator<uint32_t, RegionHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, RegionHead{ roots, firstCell.as<uint32_t>() } );
+	return rankHeads( heads, nCells, rank1, nullptr, st );
+}
+
 int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, hipStream_t st )
 {
 	Classified c;
@@ -285,15 +294,8 @@ int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, 
 	c.lin.release();
 	c.offs.release();
 	c.root.release();
-	const uint64_t nNodes = (uint64_t)s.nVoxels + 1;
-	if( firstCell.alloc( nNodes * 4 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( firstCell.p, 0xFF, nNodes * 4, st ) );
+	if( enclosedRegionRanks( roots.as<uint32_t>(), nCells, s.nVoxels, firstCell, rank1, st ) ) return 1;
 	const dim3 grid( divUp( nCells, FB ) ), block( FB );
-	hipLaunchKernelGGL( kFillFirstCells, grid, block, 0, st, roots.as<uint32_t>(), nCells, firstCell.as<uint32_t>() );
-	MVRT_HIP( hipGetLastError() );
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, RegionHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, RegionHead{ roots.as<uint32_t>(), firstCell.as<uint32_t>() } );
-	if( rankHeads( heads, c.nCells, rank1, nullptr, st ) ) return 1;
 	// (the caller's arrays are written by this launch alone, behind every allocation and check)
 	hipLaunchKernelGGL( kFillList, grid, block, 0, st, codes.as<uint64_t>(), roots.as<uint32_t>(), firstCell.as<uint32_t>(), rank1.as<uint32_t>(), nCells, xyzDev, regionDev );
 	MVRT_HIP( hipGetLastError() );

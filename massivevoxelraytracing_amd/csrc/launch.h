@@ -203,6 +203,31 @@ int enclosedCellsUnordered( const SurfaceSource& s, DevBuf& xyz, uint64_t* nCell
 // classification above (linear keys, unions, flatten) and the masks kernel of kernels_surface.hip.  masksDev == nullptr: counts only
 int surfaceExteriorMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* nFacesOut, uint64_t* nHiddenOut, hipStream_t stream );
 int launchFillAttribs( uint2 attrib, uint64_t n, uint2* out, hipStream_t stream ); // n copies of one VoxelAttirb.  Not synchronised.
+// What the classification of kernels_fill.hip leaves: the sorted linear keys ( z << 2L | y << L | x ) of the voxels, the flattened roots (node i + 1 = gap i, the
+// empty run between sorted voxels i and i + 1 of one row; root 0 = EXTERIOR) and the n + 1 exclusive cell offsets of the enclosed gaps.  The counts are valid
+// when enclosedClassify returns
+struct EnclosedClassified
+{
+	DevBuf count, lin, root, offs;
+	uint64_t nCells = 0, nRegions = 0;
+};
+int enclosedClassify( const SurfaceSource& s, EnclosedClassified* out, hipStream_t stream );
+// roots: the root of every cell of a listing in ascending Morton code.  firstCell (nVoxels + 1 entries, allocated here) = per root the position of its first cell,
+// rank1 (allocated here) = the inclusive count of first cells: the region of cell c is rank1[firstCell[roots[c]]] - 1.  Waits for the stream
+int enclosedRegionRanks( const uint32_t* roots, uint32_t nCells, uint32_t nVoxels, DevBuf& firstCell, DevBuf& rank1, hipStream_t stream );
+
+// nearest voxel of the enclosed cells (kernels_nearest.hip; mvrt_svo_enclosed_nearest / mvrt_svo_fill_enclosed_nearest): morton, attrs, nVoxels and levels of the
+// source are read.  The calls block, keep their scratch in DevBufs and write NOTHING to the caller's arrays unless they succeed.
+struct NearestStats // what the last call of this thread did (tools/enclosed_nearest_bench.py through mvrt_test_enclosed_nearest_stats)
+{
+	uint64_t cells = 0, gaps[3] = { 0, 0, 0 }, longest[3] = { 0, 0, 0 }, deepest = 0; // per axis x, y, z; all but cells stay 0 where no pass was run
+};
+int enclosedNearest( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev,
+					 uint64_t* nCellsOut, uint64_t* nRegionsOut, hipStream_t stream );
+// the same cells in no particular order with the attribute of their nearest voxel, for the edit (xyz 3 x u32, attribs 8 bytes per cell, allocated here; left empty
+// when there are no cells or nVoxels + *nCells >= 2^32 - 1: the caller looks at *nCells)
+int enclosedNearestUnordered( const SurfaceSource& s, DevBuf& xyz, DevBuf& attribs, uint64_t* nCells, hipStream_t stream );
+NearestStats nearestLastStats(); // of this thread
 
 // ---- sorted voxel lists (kernels_list.hip) -------------------------------------------------------------------------------------------------------------
 // What every voxel-set operator hands to svoBuildFromSorted: n sorted unique codes with their attributes and the emission flag over them, allocated by the

@@ -13,6 +13,9 @@
 //                   components (kernels_components.hip), the half of an element that sees every adjacent pair once and the search that returns the index.
 //   round offsets   ballReach, ballShiftRange, ballShifted and the packed key ( d2 << 32 | payload ) of kernels_ball.hip: the shifts an entry of a distance pass sends
 //                   records to, clipped to the grid and to the radius.  Host-callable (tests/hip/ball_host.hip).
+//   nearest voxel   nearestAxisKey / nearestAxisCell / nearestGapHead (the cells of a line as consecutive keys), nearestGapKey, nearestEndKey, nearestGoOn and
+//                   nearestScan of kernels_nearest.hip: the minimum of the packed key over a gap of enclosed cells and its two end voxels.  Host-callable
+//                   (tests/hip/nearest_host.hip).
 //   two sets        combineTranslate (a code moved by an integer offset and clipped to a grid) of kernels_combine.hip, and combineWindow / codeIndexInRange: the
 //                   partner search of a group of ascending codes, bounded once per group.  Host-callable (tests/hip/combine_host.hip).
 //   resampling      resamplePoint (the point rule of mvrt_cell_transform), resampleBox / resampleBoxShift / resampleBoxHoldsVoxel (the conservative test of a node
@@ -201,6 +204,72 @@ MVRT_HDI bool ballShifted( uint64_t code, uint32_t levels, uint32_t axis, int32_
 }
 // the key of the record at shift s: the distance field grows by s * s, the payload stays.  Adding the same constant to both keeps the order of two keys
 MVRT_HDI uint64_t ballShiftKey( uint64_t key, int32_t s ) { return key + ( (uint64_t)( (uint32_t)( s * s ) ) << 32 ); }
+
+// ---- nearest voxel of the enclosed cells (kernels_nearest.hip) ------------------------------------------------------------------------------------------------
+// Three passes over the gaps, one per axis: along an axis the enclosed cells of a line fall into gaps, maximal runs of cells with a voxel at
+// either end, and a cell's packed key ( d2 << 32 | vIndex ) is minimised over its own gap and the gap's two end voxels.  d2 of an enclosed cell is below 2^20
+// (mvrt.h), so a shift beyond NEAREST_MAX_SHIFT never wins: the scan does not go further, and the x pass stores the square of NEAREST_MAX_SHIFT + 1 for a voxel
+// further off.  Such an entry loses against the true minimum wherever it is read, and the sum of three such squares fits the distance field.  Host-callable
+// (tests/hip/nearest_host.hip runs the passes with exactly these functions).
+#define NEAREST_MAX_SHIFT 1023u
+// The key of a line of cells along `axis` (0 = x, 1 = y, 2 = z): the coordinate of that axis in the low L bits, so that the cells of one line are consecutive
+// keys.  An enclosed cell has no coordinate 0 or R - 1: key + 1 never carries into another line, and two sorted keys that differ by 1 are face neighbours
+MVRT_HDI uint64_t nearestAxisKey( uint32_t axis, uint32_t x, uint32_t y, uint32_t z, uint32_t L )
+{
+	const uint64_t a = axis == 0u ? x : axis == 1u ? y : z, b = axis == 0u ? y : x, c = axis == 2u ? y : z;
+	return ( (uint64_t)c << ( 2u * L ) ) | ( (uint64_t)b << L ) | a;
+}
+MVRT_HDI void nearestAxisCell( uint32_t axis, uint64_t key, uint32_t L, uint32_t& x, uint32_t& y, uint32_t& z )
+{
+	const uint64_t m = ( 1ull << L ) - 1ull;
+	const uint32_t a = (uint32_t)( key & m ), b = (uint32_t)( ( key >> L ) & m ), c = (uint32_t)( key >> ( 2u * L ) );
+	x = axis == 0u ? a : b;
+	y = axis == 0u ? b : axis == 1u ? a : c;
+	z = axis == 2u ? a : c;
+}
+MVRT_HDI bool nearestGapHead( const uint64_t* __restrict__ keys, uint64_t i ) { return i == 0 || keys[i] != keys[i - 1] + 1ull; }
+// the candidate of the voxel at shift s >= 1 with index vIndex; s is clamped as said above
+MVRT_HDI uint64_t nearestEndKey( uint64_t s, uint32_t vIndex )
+{
+	const uint32_t c = s > NEAREST_MAX_SHIFT ? NEAREST_MAX_SHIFT + 1u : (uint32_t)s;
+	return ballKey( c * c, vIndex );
+}
+// pass x: cell k of a gap of g cells between the voxels vLo (left of cell 0) and vHi (right of cell g - 1)
+MVRT_HDI uint64_t nearestGapKey( uint64_t k, uint64_t g, uint32_t vLo, uint32_t vHi )
+{
+	const uint64_t lo = nearestEndKey( k + 1ull, vLo ), hi = nearestEndKey( g - k, vHi );
+	return lo < hi ? lo : hi;
+}
+// The stop rule: a candidate at shift s has a distance of at least s * s, so a side is left once s * s > the best d2 -- not >=: a tie at equal d2 can still lower
+// the vIndex
+MVRT_HDI bool nearestGoOn( uint32_t s, uint64_t best ) { return s <= NEAREST_MAX_SHIFT && s * s <= ballKeyDist2( best ); }
+// passes y and z: seg = the keys the previous pass left for the g cells of one gap, in the order of the axis; the result for cell k.  Reads seg[k] and, per
+// side, the cells at the shifts the stop rule admits; where a side reaches the end of the gap under that rule, the end voxel is the last candidate
+MVRT_HDI uint64_t nearestScan( const uint64_t* __restrict__ seg, uint32_t g, uint32_t k, uint32_t vLo, uint32_t vHi )
+{
+	uint64_t best = seg[k];
+	for( uint32_t s = 1u; nearestGoOn( s, best ); s++ )
+	{
+		const uint64_t c = s <= k ? ballShiftKey( seg[k - s], (int32_t)s ) : nearestEndKey( s, vLo );
+		best = c < best ? c : best;
+		if( s > k ) break;
+	}
+	const uint32_t above = g - 1u - k; // cells behind k
+	for( uint32_t s = 1u; nearestGoOn( s, best ); s++ )
+	{
+		const uint64_t c = s <= above ? ballShiftKey( seg[k + s], (int32_t)s ) : nearestEndKey( s, vHi );
+		best = c < best ? c : best;
+		if( s > above ) break;
+	}
+	return best;
+}
+// the 8 bytes a cell takes from its nearest voxel: colour RGB and emission RGB, both alpha bytes 255 (the rule of MVRT_VOXEL_SET)
+MVRT_HDI uint2 nearestAttrib( uint2 a )
+{
+	a.x |= 0xFF000000u;
+	a.y |= 0xFF000000u;
+	return a;
+}
 
 // ---- two sets (kernels_combine.hip) -------------------------------------------------------------------------------------------------------------------------
 // The cell `code` names, moved by the offset o (each component in [-2^21, 2^21]) inside a grid of R = 2^levels <= 2^21 cells per axis: false when it leaves the

@@ -1,0 +1,294 @@
+// nearest_host.hip -- the three passes over the gaps run on the host with exactly the functions the lanes of csrc/kernels_nearest.hip run
+// (nearestAxisKey, nearestAxisCell, nearestGapHead, nearestGapKey, nearestEndKey, nearestGoOn, nearestScan of csrc/voxel_passes.h), against brute force: for every
+// enclosed cell the minimum over all voxels of the packed ( squared distance, index in Morton order ).  The shapes: random shells of 8^3 to 16^3 with debris in
+// their cavities, the cage, and a shell at the far corner of the 2^21 grid.  Then the stop rule at its boundary.  A program of its own: it makes no HIP call and
+// needs no GPU.  Exit status 0 = every check held; each failure prints one line.
+#include <stdio.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../massivevoxelraytracing_amd/csrc/voxel_passes.h"
+
+#if defined( __has_feature )
+#if __has_feature( address_sanitizer )
+#include <sanitizer/asan_interface.h>
+#define POISON( p, bytes ) ASAN_POISON_MEMORY_REGION( p, bytes )
+#define UNPOISON( p, bytes ) ASAN_UNPOISON_MEMORY_REGION( p, bytes )
+#endif
+#endif
+#ifndef POISON
+#define POISON( p, bytes ) ( (void)0 )
+#define UNPOISON( p, bytes ) ( (void)0 )
+#endif
+
+static int g_failures = 0;
+#define CHECK( cond, ... )                     \
+	do                                         \
+	{                                          \
+		if( !( cond ) )                        \
+		{                                      \
+			if( g_failures++ < 20 )            \
+			{                                  \
+				printf( "FAILED %s: ", #cond ); \
+				printf( __VA_ARGS__ );         \
+				printf( "\n" );                \
+			}                                  \
+		}                                      \
+	} while( 0 )
+
+static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
+static uint64_t rnd() // xorshift64
+{
+	g_rng ^= g_rng << 13;
+	g_rng ^= g_rng >> 7;
+	g_rng ^= g_rng << 17;
+	return g_rng;
+}
+
+// A box of B^3 cells whose lowest cell is (o, o, o) in a grid of 2^L cells per axis.  The cells of the box's own border are empty, so an empty cell of the box is
+// exterior exactly when a 6-connected path of empty cells of the box joins it to that border
+struct Box
+{
+	uint32_t L, o, B;
+	std::vector<uint8_t> voxel;
+	Box( uint32_t levels, uint32_t origin, uint32_t size ) : L( levels ), o( origin ), B( size ), voxel( (size_t)size * size * size, 0 ) {}
+	size_t at( uint32_t x, uint32_t y, uint32_t z ) const { return ( (size_t)z * B + y ) * B + x; } // local coordinates
+};
+
+static uint64_t g_cellsChecked = 0;
+static uint32_t g_deepest = 0;
+
+static void checkBox( const Box& b, const char* name )
+{
+	const uint32_t B = b.B, L = b.L;
+	const size_t N = (size_t)B * B * B;
+	// enclosed = empty and not reached from the border of the box
+	std::vector<uint8_t> ext( N, 0 );
+	std::vector<uint32_t> stack;
+	for( uint32_t z = 0; z < B; z++ )
+		for( uint32_t y = 0; y < B; y++ )
+			for( uint32_t x = 0; x < B; x++ )
+				if( x == 0 || y == 0 || z == 0 || x == B - 1 || y == B - 1 || z == B - 1 )
+				{
+					CHECK( !b.voxel[b.at( x, y, z )], "%s: a voxel on the border of the box", name );
+					ext[b.at( x, y, z )] = 1;
+					stack.push_back( (uint32_t)b.at( x, y, z ) );
+				}
+	while( !stack.empty() )
+	{
+		const uint32_t i = stack.back();
+		stack.pop_back();
+		const uint32_t x = i % B, y = ( i / B ) % B, z = i / ( B * B );
+		const int d[6][3] = { { -1, 0, 0 }, { 1, 0, 0 }, { 0, -1, 0 }, { 0, 1, 0 }, { 0, 0, -1 }, { 0, 0, 1 } };
+		for( int k = 0; k < 6; k++ )
+		{
+			const uint32_t nx = x + (uint32_t)d[k][0], ny = y + (uint32_t)d[k][1], nz = z + (uint32_t)d[k][2];
+			if( nx >= B || ny >= B || nz >= B ) continue;
+			const size_t j = b.at( nx, ny, nz );
+			if( b.voxel[j] || ext[j] ) continue;
+			ext[j] = 1;
+			stack.push_back( (uint32_t)j );
+		}
+	}
+	// the voxels in Morton order of their grid coordinates: vIndex
+	struct V
+	{
+		uint64_t code;
+		uint32_t x, y, z;
+	};
+	std::vector<V> vox;
+	for( uint32_t z = 0; z < B; z++ )
+		for( uint32_t y = 0; y < B; y++ )
+			for( uint32_t x = 0; x < B; x++ )
+				if( b.voxel[b.at( x, y, z )] ) vox.push_back( V{ mortonEncode( b.o + x, b.o + y, b.o + z ), x, y, z } );
+	std::sort( vox.begin(), vox.end(), []( const V& p, const V& q ) { return p.code < q.code; } );
+	std::vector<uint32_t> vIndex( N, ~0u );
+	for( size_t i = 0; i < vox.size(); i++ ) vIndex[b.at( vox[i].x, vox[i].y, vox[i].z )] = (uint32_t)i;
+
+	// pass x on the rows of the box; a gap is a maximal run of enclosed cells, and the lemma says a voxel stands at either end
+	std::vector<uint64_t> cur( N, ~0ull );
+	uint64_t nCells = 0;
+	for( uint32_t z = 0; z < B; z++ )
+		for( uint32_t y = 0; y < B; y++ )
+			for( uint32_t x = 0; x < B; x++ )
+			{
+				if( b.voxel[b.at( x, y, z )] || ext[b.at( x, y, z )] ) continue;
+				uint32_t x1 = x;
+				while( !b.voxel[b.at( x1 + 1, y, z )] && !ext[b.at( x1 + 1, y, z )] ) x1++;
+				const uint32_t g = x1 - x + 1u, vLo = vIndex[b.at( x - 1, y, z )], vHi = vIndex[b.at( x1 + 1, y, z )];
+				CHECK( vLo != ~0u && vHi != ~0u, "%s: an x gap at (%u, %u, %u) without a voxel at an end", name, x, y, z );
+				for( uint32_t k = 0; k < g; k++ ) cur[b.at( x + k, y, z )] = nearestGapKey( k, g, vLo, vHi );
+				nCells += g;
+				x = x1;
+			}
+	// passes y and z: the cells sorted by the key of the axis, gaps by the head flags, the scan on the segment of a gap
+	for( uint32_t axis = 1; axis <= 2; axis++ )
+	{
+		std::vector<uint64_t> keys;
+		for( uint32_t z = 0; z < B; z++ )
+			for( uint32_t y = 0; y < B; y++ )
+				for( uint32_t x = 0; x < B; x++ )
+					if( !b.voxel[b.at( x, y, z )] && !ext[b.at( x, y, z )] ) keys.push_back( nearestAxisKey( axis, b.o + x, b.o + y, b.o + z, L ) );
+		std::sort( keys.begin(), keys.end() );
+		std::vector<uint64_t> in( keys.size() ), out( keys.size() );
+		for( size_t i = 0; i < keys.size(); i++ )
+		{
+			uint32_t x, y, z;
+			nearestAxisCell( axis, keys[i], L, x, y, z );
+			CHECK( x >= b.o && y >= b.o && z >= b.o && x - b.o < B && y - b.o < B && z - b.o < B && nearestAxisKey( axis, x, y, z, L ) == keys[i], "%s: axis %u key round trip", name, axis );
+			in[i] = cur[b.at( x - b.o, y - b.o, z - b.o )];
+		}
+		for( size_t a = 0; a < keys.size(); )
+		{
+			CHECK( nearestGapHead( keys.data(), a ), "%s: axis %u: no head at the start of a segment", name, axis );
+			size_t e = a + 1;
+			while( e < keys.size() && !nearestGapHead( keys.data(), e ) ) e++;
+			uint32_t x0, y0, z0, x1, y1, z1;
+			nearestAxisCell( axis, keys[a], L, x0, y0, z0 );
+			nearestAxisCell( axis, keys[e - 1], L, x1, y1, z1 );
+			x0 -= b.o, y0 -= b.o, z0 -= b.o, x1 -= b.o, y1 -= b.o, z1 -= b.o;
+			CHECK( x0 == x1 && ( axis == 1 ? z0 == z1 && y1 - y0 == e - a - 1 : y0 == y1 && z1 - z0 == e - a - 1 ), "%s: axis %u: a segment is not one line", name, axis );
+			const uint32_t vLo = axis == 1 ? vIndex[b.at( x0, y0 - 1, z0 )] : vIndex[b.at( x0, y0, z0 - 1 )];
+			const uint32_t vHi = axis == 1 ? vIndex[b.at( x1, y1 + 1, z1 )] : vIndex[b.at( x1, y1, z1 + 1 )];
+			CHECK( vLo != ~0u && vHi != ~0u, "%s: axis %u: a gap at (%u, %u, %u) without a voxel at an end", name, axis, x0, y0, z0 );
+			for( size_t i = a; i < e; i++ ) out[i] = nearestScan( in.data() + a, (uint32_t)( e - a ), (uint32_t)( i - a ), vLo, vHi );
+			a = e;
+		}
+		for( size_t i = 0; i < keys.size(); i++ )
+		{
+			uint32_t x, y, z;
+			nearestAxisCell( axis, keys[i], L, x, y, z );
+			cur[b.at( x - b.o, y - b.o, z - b.o )] = out[i];
+		}
+	}
+	// brute force over all voxels
+	for( uint32_t z = 0; z < B; z++ )
+		for( uint32_t y = 0; y < B; y++ )
+			for( uint32_t x = 0; x < B; x++ )
+			{
+				if( b.voxel[b.at( x, y, z )] || ext[b.at( x, y, z )] ) continue;
+				uint64_t best = ~0ull;
+				for( size_t i = 0; i < vox.size(); i++ )
+				{
+					const int64_t dx = (int64_t)vox[i].x - x, dy = (int64_t)vox[i].y - y, dz = (int64_t)vox[i].z - z;
+					const uint64_t k = ballKey( (uint32_t)( dx * dx + dy * dy + dz * dz ), (uint32_t)i );
+					best = k < best ? k : best;
+				}
+				const uint64_t got = cur[b.at( x, y, z )];
+				CHECK( got == best, "%s: cell (%u, %u, %u): ( %u, %u ), want ( %u, %u )", name, x, y, z, ballKeyDist2( got ), ballKeyPayload( got ), ballKeyDist2( best ),
+					   ballKeyPayload( best ) );
+				g_deepest = std::max( g_deepest, ballKeyDist2( best ) );
+			}
+	g_cellsChecked += nCells;
+}
+
+// the shell of a union of random spheres and boxes inside [2, R - 3]^3, with debris voxels in what it encloses
+static void randomShell( uint32_t levels )
+{
+	const uint32_t R = 1u << levels;
+	Box b( levels, 0u, R );
+	std::vector<uint8_t> solid( b.voxel.size(), 0 );
+	const uint32_t parts = 1u + (uint32_t)( rnd() % 4u );
+	for( uint32_t p = 0; p < parts; p++ )
+	{
+		const bool sphere = rnd() & 1u;
+		const int span = (int)R - 4, r = 2 + (int)( rnd() % (uint64_t)( span / 2 - 1 ) );
+		const int cx = 2 + r + (int)( rnd() % (uint64_t)( span - 2 * r + 1 ) ), cy = 2 + r + (int)( rnd() % (uint64_t)( span - 2 * r + 1 ) ),
+				  cz = 2 + r + (int)( rnd() % (uint64_t)( span - 2 * r + 1 ) );
+		for( int z = cz - r; z <= cz + r; z++ )
+			for( int y = cy - r; y <= cy + r; y++ )
+				for( int x = cx - r; x <= cx + r; x++ )
+				{
+					const int dx = x - cx, dy = y - cy, dz = z - cz;
+					if( !sphere || dx * dx + dy * dy + dz * dz <= r * r ) solid[b.at( (uint32_t)x, (uint32_t)y, (uint32_t)z )] = 1;
+				}
+	}
+	const uint32_t debris = (uint32_t)( rnd() % 8u ); // percent of the inside cells
+	for( uint32_t z = 1; z < R - 1; z++ )
+		for( uint32_t y = 1; y < R - 1; y++ )
+			for( uint32_t x = 1; x < R - 1; x++ )
+			{
+				if( !solid[b.at( x, y, z )] ) continue;
+				bool inner = true;
+				for( int dz = -1; dz <= 1; dz++ )
+					for( int dy = -1; dy <= 1; dy++ )
+						for( int dx = -1; dx <= 1; dx++ ) inner = inner && solid[b.at( x + (uint32_t)dx, y + (uint32_t)dy, z + (uint32_t)dz )];
+				if( !inner || rnd() % 100u < debris ) b.voxel[b.at( x, y, z )] = 1;
+			}
+	checkBox( b, "random shell" );
+}
+
+// a shell of 5^3 voxels around a cavity of 3^3 cells, its lowest voxel at (at, at, at) of the box
+static void cage( Box& b, uint32_t at )
+{
+	for( uint32_t z = 0; z < 5; z++ )
+		for( uint32_t y = 0; y < 5; y++ )
+			for( uint32_t x = 0; x < 5; x++ )
+				if( x == 0 || y == 0 || z == 0 || x == 4 || y == 4 || z == 4 ) b.voxel[b.at( at + x, at + y, at + z )] = 1;
+}
+
+static void checkStopRule()
+{
+	CHECK( nearestGoOn( 2u, ballKey( 4u, 9u ) ), "s * s == d2 goes on" );
+	CHECK( !nearestGoOn( 2u, ballKey( 3u, 9u ) ), "s * s == d2 + 1 stops" );
+	CHECK( nearestGoOn( NEAREST_MAX_SHIFT, ballKey( 1u << 20, 0u ) ) && !nearestGoOn( NEAREST_MAX_SHIFT + 1u, ballKey( 0x7FFFFFFFu, 0u ) ), "the largest shift" );
+	CHECK( nearestEndKey( 1ull << 21, 5u ) == ballKey( 1u << 20, 5u ) && nearestEndKey( 1023u, 5u ) == ballKey( 1023u * 1023u, 5u ), "a far end voxel is clamped above every legal d2" );
+	CHECK( nearestGapKey( 0u, 1u << 21, 3u, 4u ) == ballKey( 1u, 3u ) && nearestGapKey( ( 1u << 21 ) - 1u, 1u << 21, 3u, 4u ) == ballKey( 1u, 4u ), "the ends of the longest gap" );
+	CHECK( nearestGapKey( 2u, 5u, 9u, 4u ) == ballKey( 9u, 4u ) && nearestGapKey( 2u, 5u, 4u, 9u ) == ballKey( 9u, 4u ), "the middle of a gap: the lower index" );
+	// a gap of 9 cells, the lane of cell 4 with d2 = 4 so far.  Shift 2 has s * s == d2: it is read, and its lower index wins.  Shift 3 is not read on either side:
+	// under the address sanitizer those cells are poisoned, a read ends the program
+	std::vector<uint64_t> seg( 9, ballKey( 1000u, 77u ) );
+	seg[4] = ballKey( 4u, 50u );
+	seg[2] = ballKey( 0u, 10u ); // -> ( 4, 10 )
+	seg[6] = ballKey( 0u, 30u ); // -> ( 4, 30 )
+	POISON( seg.data(), 2 * 8 );
+	POISON( seg.data() + 7, 2 * 8 );
+	const uint64_t tie = nearestScan( seg.data(), 9u, 4u, 1u, 2u );
+	UNPOISON( seg.data(), 9 * 8 );
+	CHECK( tie == ballKey( 4u, 10u ), "a tie at s * s == d2 with a lower index: ( %u, %u )", ballKeyDist2( tie ), ballKeyPayload( tie ) );
+	// d2 = 3 so far: shift 1 is read, shift 2 ( s * s == d2 + 1 ) is not
+	seg.assign( 9, ballKey( 1000u, 77u ) );
+	seg[4] = ballKey( 3u, 50u );
+	POISON( seg.data(), 3 * 8 );
+	POISON( seg.data() + 6, 3 * 8 );
+	const uint64_t stop = nearestScan( seg.data(), 9u, 4u, 1u, 2u );
+	UNPOISON( seg.data(), 9 * 8 );
+	CHECK( stop == ballKey( 3u, 50u ), "nothing nearer: ( %u, %u )", ballKeyDist2( stop ), ballKeyPayload( stop ) );
+	// the end voxels: cell 1 of a gap of 3 cells with d2 = 4 so far meets both ends at shift 2, the tie goes to the lower index; with d2 = 3 neither is taken
+	std::vector<uint64_t> g3( 3, ballKey( 1000u, 77u ) );
+	g3[1] = ballKey( 4u, 50u );
+	CHECK( nearestScan( g3.data(), 3u, 1u, 60u, 20u ) == ballKey( 4u, 20u ), "an end voxel at s * s == d2 with a lower index" );
+	g3[1] = ballKey( 3u, 50u );
+	CHECK( nearestScan( g3.data(), 3u, 1u, 6u, 2u ) == ballKey( 3u, 50u ), "an end voxel at s * s == d2 + 1" );
+	std::vector<uint64_t> g1( 1, ballKey( 9u, 5u ) );
+	CHECK( nearestScan( g1.data(), 1u, 0u, 8u, 3u ) == ballKey( 1u, 3u ), "a gap of one cell" );
+}
+
+int main()
+{
+	checkStopRule();
+	for( int t = 0; t < 60; t++ ) randomShell( 3 );
+	for( int t = 0; t < 120; t++ ) randomShell( 4 );
+	{
+		Box b( 3, 0u, 8u );
+		cage( b, 1u );
+		checkBox( b, "cage" );
+	}
+	{
+		Box b( 21, ( 1u << 21 ) - 8u, 8u ); // its last cell is the last cell of the grid
+		cage( b, 2u );						 // voxels up to R - 2
+		b.voxel[b.at( 4, 4, 4 )] = 1;		 // and one voxel floating in the cavity
+		checkBox( b, "far corner" );
+	}
+	{
+		Box b( 21, 0u, 8u ); // the first cells of the grid
+		cage( b, 1u );
+		checkBox( b, "near corner" );
+	}
+	CHECK( g_cellsChecked >= 20000, "only %llu cells checked", (unsigned long long)g_cellsChecked );
+	printf( "%llu enclosed cells checked, deepest d2 %u\n", (unsigned long long)g_cellsChecked, g_deepest );
+	if( g_failures ) printf( "%d check(s) failed\n", g_failures );
+	else printf( "nearest host checks ok\n" );
+	return g_failures ? 1 : 0;
+}
