@@ -6,6 +6,7 @@
 //              [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]
 //              [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]
 //              [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]
+//              [--recolour-from other.obj [--recolour-max D] | --distance-to other.obj]
 //              [--ao [samples] [--ao-radius voxels]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
@@ -46,6 +47,12 @@
 // scaled by s > 0, both about the centre of the grid, before it is combined: resampled into a scratch octree on the same lattice (mvrt_svo_resample with the
 // transform mvrt_cell_transform_from_world makes of the world matrix), no triangle is voxelised again.  A line reports the second set's voxels before and after;
 // --offset still applies, to the resampled set.
+// --recolour-from other.obj: the second model is voxelised on the joint grid exactly as for --union (--offset, --rotate-b and --scale-b apply as there) and
+// every voxel of the scene takes the colour and emission of the nearest voxel of the second set (mvrt_svo_transfer_attributes): clean geometry coloured from a
+// scan.  --recolour-max D limits the reach to D cells (maxDist2 = D * D); voxels further off keep their bytes.  A line reports the voxels changed and beyond.
+// --distance-to other.obj: a line reports, for both directions, the largest distance from a voxel of the one set to the other set (the one-sided Hausdorff
+// distance, mvrt_svo_nearest_between) as the root of the integer d2, the farthest voxel, the voxels at distance 0 and the voxel counts; the mesh is then written as
+// without the flag.  Only one of these two and --union / --intersect / --subtract / --xor; they run at the place of the combine, before --lod and what follows.
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <algorithm>
 #include <cmath>
@@ -74,6 +81,8 @@ int main( int argc, char** argv )
 	bool keep = false, keepOk = true;
 	const char *combineName = nullptr, *otherObj = nullptr; // "union", "intersect", "subtract" or "xor"
 	int combineOps = 0, combineOp = 0, offset[3] = { 0, 0, 0 };
+	bool recolour = false, distanceTo = false; // --recolour-from / --distance-to: at the place of the combine, with its second model
+	long long recolourMax = -1;					// cells; -1 = no limit
 	bool attribB = false, resampleB = false, resampleOk = true;
 	double rotateB[4] = { 0.0, 0.0, 1.0, 0.0 }, scaleB = 1.0; // axis and degrees
 	std::vector<const char*> pos;
@@ -120,6 +129,14 @@ int main( int argc, char** argv )
 			otherObj = argv[++i];
 			combineOps++;
 		}
+		else if( ( !std::strcmp( argv[i], "--recolour-from" ) || !std::strcmp( argv[i], "--distance-to" ) ) && i + 1 < argc )
+		{
+			combineName = argv[i] + 2;
+			( !std::strcmp( combineName, "recolour-from" ) ? recolour : distanceTo ) = true;
+			otherObj = argv[++i];
+			combineOps++;
+		}
+		else if( !std::strcmp( argv[i], "--recolour-max" ) && i + 1 < argc ) recolourMax = std::atoll( argv[++i] );
 		else if( !std::strcmp( argv[i], "--offset" ) && i + 3 < argc )
 		{
 			for( int k = 0; k < 3; k++ ) offset[k] = std::atoi( argv[++i] );
@@ -166,11 +183,15 @@ int main( int argc, char** argv )
 					 "                  [--dilate K | --erode K | --close K | --open K] [--element faces|cube] [--components] [--keep-largest K] [--min-component N]\n"
 					 "                  [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]\n"
 					 "                  [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]\n"
+					 "                  [--recolour-from other.obj [--recolour-max D] | --distance-to other.obj]\n"
 					 "                  [--ao [samples] [--ao-radius voxels]]\n"
 					 "  --union O, --intersect O, --subtract O, --xor O  combine the voxel set with that of a second model O.obj first, both voxelised on one grid\n"
 					 "               over their joint bounding box; --offset x y z moves the second set by whole cells, --attrib-b colours shared cells from it\n"
 					 "  --rotate-b ax ay az deg, --scale-b s  turn the second voxel set by deg degrees about the axis and scale it by s > 0, about the grid centre,\n"
 					 "               before it is combined (resampled on the GPU; only with one of the four options above)\n"
+					 "  --recolour-from O  every voxel takes colour and emission of the nearest voxel of a second model O.obj, voxelised as for --union (--offset,\n"
+					 "               --rotate-b, --scale-b apply); --recolour-max D: only within D cells.  --distance-to O  report the largest distance between the two\n"
+					 "               voxel sets in both directions; the mesh is written as without it.  One of these and --union / --intersect / --subtract / --xor\n"
 					 "  --lod K      coarsen the octree by K levels first (gridRes >> K); --lod-min-count C keeps a coarse cell only when it holds C fine voxels\n"
 					 "  --dilate K   grow the voxel set by K layers; --erode K peels K layers; --close K = dilate K, erode K (plugs holes); --open K = erode K,\n"
 					 "               dilate K (removes specks).  One of them, after --lod and before --fill / --exterior; --element faces|cube (default cube)\n"
@@ -193,12 +214,17 @@ int main( int argc, char** argv )
 	}
 	if( combineOps > 1 )
 	{
-		std::fprintf( stderr, "voxel_mesh: only one of --union / --intersect / --subtract / --xor\n" );
+		std::fprintf( stderr, "voxel_mesh: only one of --union / --intersect / --subtract / --xor / --recolour-from / --distance-to\n" );
+		return 2;
+	}
+	if( recolourMax != -1 && ( !recolour || recolourMax < 0 || recolourMax > 8000000 ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: --recolour-max D (D in [0, 8000000] cells) needs --recolour-from\n" );
 		return 2;
 	}
 	if( resampleB && ( combineOps != 1 || !resampleOk ) )
 	{
-		std::fprintf( stderr, "voxel_mesh: --rotate-b ax ay az deg (an axis that is not zero) and --scale-b s (s > 0) need one of --union / --intersect / --subtract / --xor\n" );
+		std::fprintf( stderr, "voxel_mesh: --rotate-b ax ay az deg (an axis that is not zero) and --scale-b s (s > 0) need one of --union / --intersect / --subtract / --xor / --recolour-from / --distance-to\n" );
 		return 2;
 	}
 	if( fill && exterior )
@@ -295,13 +321,42 @@ int main( int argc, char** argv )
 						 rotateB[3], scaleB );
 			second = &turned;
 		}
-		const uint32_t before = svo.m_numberOfVoxels, flags = attribB ? mvrt::IntersectorOctreeGPU::COMBINE_ATTRIB_B : 0u;
-		uint64_t overlap = 0, clipped = 0, removed = 0;
-		svo.combineVoxels( *second, combineOp, offset, flags, 0, nullptr, nullptr, nullptr, &overlap, &clipped, stream );
-		const uint64_t added = svo.combine( *second, combineOp, offset, flags, &removed, nullptr, stream );
-		std::printf( "%s: voxels %u -> %u, other %u, offset %d %d %d, overlap %llu, clipped %llu, added %llu, removed %llu\n", combineName, before, svo.m_numberOfVoxels,
-					 second->m_numberOfVoxels, offset[0], offset[1], offset[2], (unsigned long long)overlap, (unsigned long long)clipped, (unsigned long long)added,
-					 (unsigned long long)removed );
+		if( recolour ) // colour and emission of the nearest voxel of the second set
+		{
+			const uint64_t limit = recolourMax < 0 ? mvrt::IntersectorOctreeGPU::NO_LIMIT : (uint64_t)recolourMax * (uint64_t)recolourMax;
+			uint64_t beyond = 0;
+			const uint64_t changed = svo.transferAttributes( *second, offset, limit, mvrt::IntersectorOctreeGPU::TRANSFER_COLOUR | mvrt::IntersectorOctreeGPU::TRANSFER_EMISSION, &beyond,
+															  stream );
+			std::printf( "recolour-from: voxels %u, other %u, offset %d %d %d, max %lld, changed %llu, beyond %llu\n", svo.m_numberOfVoxels, second->m_numberOfVoxels, offset[0],
+						 offset[1], offset[2], recolourMax, (unsigned long long)changed, (unsigned long long)beyond );
+		}
+		else if( distanceTo ) // both directions; nothing changes
+		{
+			const int32_t back[3] = { -offset[0], -offset[1], -offset[2] };
+			const mvrt::IntersectorOctreeGPU* sets[2] = { &svo, second };
+			std::printf( "distance-to: offset %d %d %d", offset[0], offset[1], offset[2] );
+			for( int d = 0; d < 2; d++ ) // a -> b + o, then b + o -> a
+			{
+				const mvrt::IntersectorOctreeGPU::Between r =
+					sets[d]->nearestBetween( *sets[1 - d], d == 0 ? offset : back, mvrt::IntersectorOctreeGPU::NO_LIMIT, 0, nullptr, nullptr, stream );
+				std::vector<uint32_t> xyz, attribs;
+				sets[d]->readVoxels( xyz, attribs, stream ); // (for the cell of the farthest voxel)
+				std::printf( "; %s: max %.6f (d2 %llu) at voxel %u (%u %u %u), zero %llu of %llu", d == 0 ? "a -> b" : "b -> a", std::sqrt( (double)r.maxDist2 ),
+							 (unsigned long long)r.maxDist2, r.farthest, xyz[3 * (size_t)r.farthest], xyz[3 * (size_t)r.farthest + 1], xyz[3 * (size_t)r.farthest + 2],
+							 (unsigned long long)r.nZero, (unsigned long long)r.n );
+			}
+			std::printf( "\n" );
+		}
+		else
+		{
+			const uint32_t before = svo.m_numberOfVoxels, flags = attribB ? mvrt::IntersectorOctreeGPU::COMBINE_ATTRIB_B : 0u;
+			uint64_t overlap = 0, clipped = 0, removed = 0;
+			svo.combineVoxels( *second, combineOp, offset, flags, 0, nullptr, nullptr, nullptr, &overlap, &clipped, stream );
+			const uint64_t added = svo.combine( *second, combineOp, offset, flags, &removed, nullptr, stream );
+			std::printf( "%s: voxels %u -> %u, other %u, offset %d %d %d, overlap %llu, clipped %llu, added %llu, removed %llu\n", combineName, before, svo.m_numberOfVoxels,
+						 second->m_numberOfVoxels, offset[0], offset[1], offset[2], (unsigned long long)overlap, (unsigned long long)clipped, (unsigned long long)added,
+						 (unsigned long long)removed );
+		}
 	}
 	if( lod > 0 ) // before anything else is done with the octree
 	{

@@ -486,6 +486,50 @@ int mvrt_svo_resample( const mvrt_svo* src, mvrt_svo* dst, const mvrt_cell_trans
  * non-finite input, det W == 0 or a non-finite inverse ("singular"), a dps that is not finite and positive, and any entry outside the limits above. */
 int mvrt_cell_transform_from_world( const double world[12], const float srcLower[3], float srcDps, const float dstLower[3], float dstDps, mvrt_cell_transform* out );
 
+/* The nearest voxel of arbitrary lattice points, the distance from one voxel set to another, and the recolouring of one set from another (new; the reference has
+ * none).  Definitions:
+ *   - Set and queries: B = the voxel set of a handle.  A voxel is named by its vIndex, its Morton rank, the order of mvrt_svo_read_voxels.  A query is a point q
+ *     of the integer cell lattice, three int32, each in [-2^22, 2^22]; it need not lie in the grid.
+ *   - Distance and nearest voxel: d2(q) = min over v in B of |q - v|^2; near(q) = the lowest vIndex among the voxels that attain d2(q).  This is the rule of
+ *     mvrt_svo_distance_cells and mvrt_svo_enclosed_nearest, without a radius and for any point.
+ *   - Field widths: d2 is below 2^47 and is a uint64 everywhere in this interface; the packed 64-bit key of the distance band does not fit, ( d2, vIndex ) is
+ *     compared as a pair.
+ *   - Limit: maxDist2 is a uint64; UINT64_MAX means no limit, 0 is legal and is the membership test.  A query with d2(q) > maxDist2 reports dist2 = UINT64_MAX,
+ *     nearest = 0xFFFFFFFF and all-zero attribute bytes.  Otherwise the answer is exact: the limit never changes an answer that lies within it.
+ *   - Attributes: attribs(q) = colour RGB and emission RGB of voxel near(q) with both alpha bytes 255, the rule of MVRT_VOXEL_SET.
+ *   - Determinism: everything is integers and a property of the set and the query alone, independent of any schedule.  A tie at equal d2 goes to the lower vIndex:
+ *     a part of the set is passed over only when it lies STRICTLY further than the best distance so far.
+ * The three calls follow mvrt_svo_combine_voxels word for word on refusals and on what a failure leaves: every octree this library built or edited is accepted, in
+ * every flavour, the tree flavour included (only the codes and the attributes are read); an upload is refused ("keeps no Morton codes": it works after one
+ * mvrt_svo_rebuild), an empty handle too ("no octree"), and a bad coordinate, offset or flags bit; all refusals happen on the host before any GPU work.  The calls
+ * block.  A failed allocation of scratch returns an error, leaks nothing and has written nothing: nothing is written to a caller's array before the last
+ * allocation and the capacity check have passed.
+ * mvrt_svo_nearest_voxels: queryDev holds n x 3 int32 on the device, dist2Dev n uint64, nearestDev n uint32, attribsDev 8 bytes per query; any output may be NULL.
+ * n == 0 is a success without a launch, n >= 2^32 is refused.  Answers come in the caller's order.  The handle is never modified.  The coordinates are on the
+ * device and are not checked: one outside [-2^22, 2^22] gives an unspecified answer for that query alone (the arithmetic is 64-bit and cannot fault). */
+int mvrt_svo_nearest_voxels( const mvrt_svo* svo, uint64_t n, const int32_t* queryDev /* 3 per query */, uint64_t maxDist2, uint64_t* dist2Dev, uint32_t* nearestDev,
+							 uint32_t* attribsDev /* 8 bytes per query */, void* stream );
+/* For every voxel v of a, in a's vIndex order, the query q = v - o in b's cell space; o is three int32 in [-2^21, 2^21], NULL = 0, as for mvrt_svo_combine_voxels.
+ * Nothing is clipped: distances need no grid, and the gridRes of a and b need not be equal.  *nOut = a's voxel count; *maxDist2Out = the largest d2 within the
+ * limit, the squared one-sided Hausdorff distance from A to B + o; *farthestOut = the lowest vIndex of a that attains it; *nZeroOut = the voxels of a with
+ * d2 == 0, which equals nOverlap of mvrt_svo_combine_voxels on equal grids; *nBeyondOut = the voxels beyond the limit (with all of them beyond, *maxDist2Out is 0
+ * and *farthestOut 0xFFFFFFFF).  Each may be NULL.  dist2Dev and nearestDev hold `capacity` entries; both NULL is the summary call (capacity is then ignored); a
+ * capacity below the count with an array given is an error: *nOut is still returned and NOTHING is written.  a == b is allowed: with o = 0 every d2 is 0 and
+ * nearest[i] = i.  The queries are made on the device from a's codes; nothing travels to the host but the five numbers.  Neither handle is modified. */
+int mvrt_svo_nearest_between( const mvrt_svo* a, const mvrt_svo* b, const int32_t offset[3], uint64_t maxDist2, uint64_t capacity, uint64_t* dist2Dev, uint32_t* nearestDev,
+							  uint64_t* nOut, uint64_t* maxDist2Out, uint32_t* farthestOut, uint64_t* nZeroOut, uint64_t* nBeyondOut, void* stream );
+/* In place: dst becomes exactly what mvrt_svo_edit_voxels leaves when given every voxel v of dst that has a nearest voxel of src within the limit, as
+ * MVRT_VOXEL_SET, with the word or words `flags` names (MVRT_TRANSFER_COLOUR = the colour word, MVRT_TRANSFER_EMISSION = the emission word; at least one, any
+ * other bit is refused) of attribs( v - o ) taken in src, and the other word the voxel's own.  This is the attribute-only edit: nodes and numbering are kept, the
+ * attributes are written in place, hasEmission is recomputed, totalDumpedVoxels ends 0, and through mvrt_pt_intersector( pt ) the steps issued before finish
+ * first.  Voxels beyond the limit keep all 8 bytes verbatim.  near is taken in src BEFORE anything is written: dst == src is allowed, and with o = 0 it only
+ * normalises the alpha bytes.  *nChangedOut = the voxels whose 8 bytes differ afterwards, *nBeyondOut = the voxels beyond the limit; either may be NULL.  A call
+ * that changes no byte succeeds and leaves the handle untouched, its device views valid.  Failures are the edit's: a failed allocation leaves dst as it was. */
+#define MVRT_TRANSFER_COLOUR 1u
+#define MVRT_TRANSFER_EMISSION 2u
+int mvrt_svo_transfer_attributes( mvrt_svo* dst, const mvrt_svo* src, const int32_t offset[3], uint64_t maxDist2, uint32_t flags, uint64_t* nChangedOut, uint64_t* nBeyondOut,
+								  void* stream );
+
 /* Exterior-only surface extraction without touching the octree, and the three extraction calls on face masks the caller supplies (new; the reference has
  * none).  Definitions:
  *   - Exterior mask of a voxel: one byte, directions d = 0..5 as in mvrt_svo_surface_masks (0 = -Y, 1 = +Y, 2 = -Z, 3 = +X, 4 = +Z, 5 = -X).  Bit d is set when the
@@ -970,6 +1014,10 @@ int mvrt_test_resample_stats( uint64_t out[24] );
  * cells, out[1..3] = the gaps of the passes along x, y and z, out[4..6] = the longest gap per axis in cells, out[7] = the deepest d2.  A call that ran no pass
  * (the sizing call, a refusal, zero cells) leaves all but out[0] at 0. */
 int mvrt_test_enclosed_nearest_stats( uint64_t out[8] );
+/* Measuring (tools/nearest_query_bench.py): what the last mvrt_svo_nearest_voxels, mvrt_svo_nearest_between or mvrt_svo_transfer_attributes of this thread did:
+ * out[0] = its queries, out[1] = the node visits in total (non-empty children whose box was tested), out[2] = the most visits of one query, out[3] = the voxels
+ * whose distance was taken, the seed's included.  A call that ran no walk (n == 0) leaves all at 0; a refusal made on the host leaves the figures of the call before. */
+int mvrt_test_nearest_query_stats( uint64_t out[4] );
 int mvrt_pt_set_profiling( mvrt_pt* pt, int enabled ); /* HIP events on `stream` around each kernel of step(); read by get_stats */
 int mvrt_pt_reset_stats( mvrt_pt* pt );
 int mvrt_pt_get_stats( mvrt_pt* pt, void* stream, mvrt_pt_stats* out ); /* synchronises the stream */

@@ -475,6 +475,74 @@ struct IntersectorOctreeGPU
 		return n;
 	}
 
+	// the nearest voxel of arbitrary lattice points, the distance to a second voxel set and the recolouring from it (mvrt_svo_nearest_voxels / _nearest_between /
+	// _transfer_attributes; semantics in mvrt.h).  maxDist2 = NO_LIMIT: no limit; a query beyond the limit reports dist2 NO_LIMIT, nearest 0xFFFFFFFF, attribs 0.
+	// Device-pointer form: n queries of 3 int32 each, any output may be nullptr
+	static constexpr uint64_t NO_LIMIT = ~0ull;
+	enum
+	{
+		TRANSFER_COLOUR = MVRT_TRANSFER_COLOUR,
+		TRANSFER_EMISSION = MVRT_TRANSFER_EMISSION
+	};
+	void nearestVoxels( uint64_t n, const int32_t* queryDev, uint64_t maxDist2, uint64_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, void* stream ) const
+	{
+		check( mvrt_svo_nearest_voxels( m_handle, n, queryDev, maxDist2, dist2Dev, nearestDev, attribsDev, stream ), "IntersectorOctreeGPU::nearestVoxels" );
+	}
+	// host-vector form: query = 3 entries per point; dist2 and nearest = 1 entry per point in the caller's order, attribs = 2
+	void nearestVoxels( const std::vector<int32_t>& query, uint64_t maxDist2, std::vector<uint64_t>& dist2, std::vector<uint32_t>& nearest, std::vector<uint32_t>& attribs,
+						void* stream ) const
+	{
+		const uint64_t n = query.size() / 3;
+		nearestVoxels( 0, nullptr, maxDist2, nullptr, nullptr, nullptr, stream ); // (what the handle decides is refused before anything is allocated)
+		dist2.resize( n );
+		nearest.resize( n );
+		attribs.resize( n * 2 );
+		Staged q( query.data(), n * 12, stream ), d( nullptr, n * 8, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
+		if( n ) nearestVoxels( n, (const int32_t*)q.p, maxDist2, (uint64_t*)d.p, (uint32_t*)v.p, (uint32_t*)a.p, stream );
+		fetch( dist2, d, stream );
+		fetch( nearest, v, stream );
+		fetch( attribs, a, stream );
+	}
+	// every voxel v of this set, in vIndex order, asked as v - offset (3 ints or nullptr = zero) in b; b may be this object
+	struct Between
+	{
+		uint64_t n = 0, maxDist2 = 0, nZero = 0, nBeyond = 0; // this set's voxels, the largest dist2 within the limit, the voxels at distance 0, those beyond the limit
+		uint32_t farthest = 0;								  // the lowest vIndex of this set that attains maxDist2
+	};
+	// device-pointer form: either array may be nullptr, both nullptr = the summary call
+	Between nearestBetween( const IntersectorOctreeGPU& b, const int32_t* offset, uint64_t maxDist2, uint64_t capacity, uint64_t* dist2Dev, uint32_t* nearestDev, void* stream ) const
+	{
+		Between r;
+		check( mvrt_svo_nearest_between( m_handle, b.m_handle, offset, maxDist2, capacity, dist2Dev, nearestDev, &r.n, &r.maxDist2, &r.farthest, &r.nZero, &r.nBeyond, stream ),
+			   "IntersectorOctreeGPU::nearestBetween" );
+		return r;
+	}
+	Between nearestBetween( const IntersectorOctreeGPU& b, const int32_t* offset, uint64_t maxDist2, std::vector<uint64_t>& dist2, std::vector<uint32_t>& nearest, void* stream ) const
+	{
+		mvrt_svo_info i;
+		check( mvrt_svo_get_info( m_handle, &i ), "IntersectorOctreeGPU::nearestBetween" );
+		const uint64_t n = i.numberOfVoxels;
+		if( !n ) return nearestBetween( b, offset, maxDist2, 0, nullptr, nullptr, stream ); // (an empty handle: the call refuses it)
+		dist2.resize( n );
+		nearest.resize( n );
+		Staged d( nullptr, n * 8, stream ), v( nullptr, n * 4, stream );
+		const Between r = nearestBetween( b, offset, maxDist2, n, (uint64_t*)d.p, (uint32_t*)v.p, stream );
+		fetch( dist2, d, stream );
+		fetch( nearest, v, stream );
+		return r;
+	}
+	// in place: every voxel with a voxel of src within maxDist2 takes the words `flags` names (TRANSFER_COLOUR | TRANSFER_EMISSION) of the nearest one, exactly as the
+	// edit with MVRT_VOXEL_SET stores them; src may be this object.  Returns the voxels whose bytes changed; *beyond may be nullptr.  A call that changes no byte
+	// does not touch the octree; otherwise the attributes are written in place, the nodes stay, and hasEmission is recomputed (a deviceView() snapshot keeps the old flag)
+	uint64_t transferAttributes( const IntersectorOctreeGPU& src, const int32_t* offset = nullptr, uint64_t maxDist2 = NO_LIMIT, uint32_t flags = TRANSFER_COLOUR | TRANSFER_EMISSION,
+								 uint64_t* beyond = nullptr, void* stream = nullptr )
+	{
+		uint64_t n = 0;
+		check( mvrt_svo_transfer_attributes( m_handle, src.m_handle, offset, maxDist2, flags, &n, beyond, stream ), "IntersectorOctreeGPU::transferAttributes" );
+		refresh();
+		return n;
+	}
+
 	// the voxel set resampled onto a grid of dstGridRes cells per axis under an affine map (mvrt_svo_resample_voxels / mvrt_svo_resample; semantics in mvrt.h): xf is
 	// the INVERSE map, destination cells to source cells, in fixed point; cellTransformFromWorld makes it from a world matrix and two lattices.  Device-pointer form
 	// of the listing: any output may be nullptr, all nullptr = the sizing call.  Returns the number of voxels.

@@ -81,6 +81,8 @@ MORPH_FACES = 0  # structuring elements of dilate / erode / close / open (includ
 MORPH_CUBE = 1
 COMBINE_UNION, COMBINE_INTERSECTION, COMBINE_DIFFERENCE, COMBINE_XOR = 0, 1, 2, 3  # mvrt_svo_combine_voxels / mvrt_svo_combine ops (include/mvrt.h)
 COMBINE_ATTRIB_B = 1  # flags: the surviving overlap takes b's attributes
+TRANSFER_COLOUR, TRANSFER_EMISSION = 1, 2  # mvrt_svo_transfer_attributes flags (include/mvrt.h)
+NO_LIMIT = (1 << 64) - 1  # maxDist2 of the nearest-voxel calls: UINT64_MAX = no limit; also the dist2 of a query beyond the limit
 
 
 # every symbol include/mvrt.h declares: name -> (restype, argtypes)
@@ -133,6 +135,9 @@ SIGNATURES = {
     "mvrt_svo_resample_voxels": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_resample": (_i32, [_vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp]),
     "mvrt_cell_transform_from_world": (_i32, [_vp, _vp, _f32, _vp, _f32, _vp]),
+    "mvrt_svo_nearest_voxels": (_i32, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_nearest_between": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_transfer_attributes": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp]),
     "mvrt_svo_dilate": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_erode": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "mvrt_svo_close": (_i32, [_vp, _i32, _i32, _vp, _vp]),
@@ -215,6 +220,7 @@ SIGNATURES = {
     "mvrt_test_allocation_state": (_i32, [_vp, _vp, _vp]),
     "mvrt_test_ball_stats": (_i32, [_vp]),
     "mvrt_test_enclosed_nearest_stats": (_i32, [_vp]),
+    "mvrt_test_nearest_query_stats": (_i32, [_vp]),
     "mvrt_test_resample_stats": (_i32, [_vp]),
     "mvrt_test_peak_bytes": (_i32, [_vp, _i32]),
     "mvrt_pt_set_profiling": (_i32, [_vp, _i32]),
@@ -299,6 +305,14 @@ def enclosed_nearest_stats():
     v = (C.c_uint64 * 8)()
     _check(lib().mvrt_test_enclosed_nearest_stats(v))
     return {"cells": int(v[0]), "gaps": [int(v[1]), int(v[2]), int(v[3])], "longest": [int(v[4]), int(v[5]), int(v[6])], "deepest": int(v[7])}
+
+
+def nearest_query_stats():
+    """measuring: what the last nearest_voxels / nearest_between / transfer_attributes this thread ran did: {queries, visits: the node visits in total, most: the
+    most visits of one query, compared: the voxels whose distance was taken} (mvrt_test_nearest_query_stats)"""
+    v = (C.c_uint64 * 4)()
+    _check(lib().mvrt_test_nearest_query_stats(v))
+    return {"queries": int(v[0]), "visits": int(v[1]), "most": int(v[2]), "compared": int(v[3])}
 
 
 def resample_stats():
@@ -741,6 +755,55 @@ class IntersectorOctreeGPU:
         ad, rm, cl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().mvrt_svo_combine(self._h, b._h, int(op), _hp(self._offset(offset)), int(flags), C.byref(ad), C.byref(rm), C.byref(cl), stream))
         return ad.value, rm.value, cl.value
+
+    def nearest_voxels_device(self, n, query, max_dist2=NO_LIMIT, dist2=None, nearest=None, attribs=None, stream=None):
+        """mvrt_svo_nearest_voxels: n queries (n x 3 int32 on the device) into caller device arrays (dist2 uint64, nearest uint32, attribs 8 bytes per query; any
+        may be None).  On MvrtError nothing was written."""
+        _check(lib().mvrt_svo_nearest_voxels(self._h, int(n), _dev_ptr(query), int(max_dist2), _dev_ptr(dist2), _dev_ptr(nearest), _dev_ptr(attribs), stream))
+
+    def nearest_voxels(self, query, max_dist2=NO_LIMIT, stream=None):
+        """the nearest voxel of every point of `query` ((n, 3) int32 lattice points, each coordinate in [-2^22, 2^22], inside the grid or not), in its order:
+        {dist2 (n,) uint64 = the exact squared distance to the set, nearest (n,) uint32 = the lowest vIndex among the voxels at that distance, attribs (n, 8) uint8
+        = that voxel's colour and emission with alpha 255}.  A query further than max_dist2 (NO_LIMIT = none, 0 = the membership test) reports NO_LIMIT,
+        0xFFFFFFFF and zero bytes.  The octree is not modified."""
+        q = np.ascontiguousarray(query, np.int32).reshape(-1, 3)
+        if len(q) and (q.min() < -(1 << 22) or q.max() > (1 << 22)):
+            raise ValueError("a query coordinate is outside [-2^22, 2^22]")
+        n = len(q)
+        self.nearest_voxels_device(0, None, max_dist2, stream=stream)  # (what the handle decides is refused before anything is allocated)
+        qd = DeviceArray.from_host(q)
+        d2, near, at = DeviceArray(n, np.uint64), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
+        self.nearest_voxels_device(n, qd, max_dist2, d2, near, at, stream)
+        return {"dist2": d2.to_host(), "nearest": near.to_host(), "attribs": at.to_host()}
+
+    def nearest_between_device(self, b, offset=None, max_dist2=NO_LIMIT, capacity=0, dist2=None, nearest=None, stream=None):
+        """mvrt_svo_nearest_between into caller device arrays of `capacity` entries (either may be None; both None = the summary call); returns {n, maxDist2,
+        farthest, zero, beyond}.  On MvrtError nothing was written."""
+        n, md, nz, nb, far = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        _check(lib().mvrt_svo_nearest_between(self._h, b._h, _hp(self._offset(offset)), int(max_dist2), int(capacity), _dev_ptr(dist2), _dev_ptr(nearest), C.byref(n), C.byref(md),
+                                              C.byref(far), C.byref(nz), C.byref(nb), stream))
+        return {"n": n.value, "maxDist2": md.value, "farthest": far.value, "zero": nz.value, "beyond": nb.value}
+
+    def nearest_between(self, b, offset=None, max_dist2=NO_LIMIT, stream=None):
+        """for every voxel v of this set, in vIndex order, the nearest voxel of `b` to v - offset (3 ints, None = 0) in b's cell space: {dist2 (n,) uint64,
+        nearest (n,) uint32 = a vIndex of b, n, maxDist2 = the largest dist2 within the limit (the squared one-sided Hausdorff distance from this set to b +
+        offset), farthest = the lowest vIndex of this set that attains it, zero = the voxels at distance 0, beyond = the voxels beyond max_dist2}.  Neither octree
+        is modified; b may be this object."""
+        n = self.info().numberOfVoxels
+        if n == 0:
+            return self.nearest_between_device(b, offset, max_dist2, stream=stream)  # (an empty handle: the call refuses it)
+        d2, near = DeviceArray(n, np.uint64), DeviceArray(n, np.uint32)
+        r = self.nearest_between_device(b, offset, max_dist2, n, d2, near, stream)
+        r["dist2"], r["nearest"] = d2.to_host(), near.to_host()
+        return r
+
+    def transfer_attributes(self, src, offset=None, max_dist2=NO_LIMIT, flags=TRANSFER_COLOUR | TRANSFER_EMISSION, stream=None):
+        """mvrt_svo_transfer_attributes: every voxel v of this octree with a voxel of `src` within max_dist2 of v - offset takes the colour (TRANSFER_COLOUR)
+        and / or the emission (TRANSFER_EMISSION) of the nearest one, exactly as edit_voxels with VOXEL_SET would store them; the others keep their 8 bytes.
+        near is taken before anything is written: src may be this object.  Returns (changed, beyond); a call that changes no byte leaves the handle untouched."""
+        ch, nb = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mvrt_svo_transfer_attributes(self._h, src._h, _hp(self._offset(offset)), int(max_dist2), int(flags), C.byref(ch), C.byref(nb), stream))
+        return ch.value, nb.value
 
     def resample_voxels_device(self, xf, gridRes=None, capacity=0, xyz=None, attribs=None, source=None, stream=None):
         """mvrt_svo_resample_voxels into caller device arrays of `capacity` voxels (any may be None; all None = the sizing call); returns the count.  gridRes: the

@@ -437,6 +437,88 @@ MVRT_EXPORT int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const 
 	return 0;
 }
 
+// The nearest voxel of arbitrary lattice points (kernels_query.hip).  Every refusal the arguments and the handles decide is made here, on the host.  The listings
+// never touch a handle; the transfer hands its list, which stays on the device, to the edit's own attribute-only path, as the fills do.
+static_assert( MVRT_TRANSFER_COLOUR == 1u && MVRT_TRANSFER_EMISSION == 2u, "mvrt.h and nearestTransferAttrib number the words alike" );
+static int querySources( const mvrt_svo* a, const mvrt_svo* b, const char* who, const int32_t offset[3], SurfaceSource* sa, SurfaceSource* sb, int32_t o[3] )
+{
+	if( surfaceSource( a, who, sa ) ) return 1;
+	REQUIRE( b, "%s: null second handle", who );
+	REQUIRE( !b->empty(), "%s: the second handle holds no octree (build first)", who );
+	REQUIRE( b->oct.morton.p, "%s: the second handle is an uploaded octree, which keeps no Morton codes", who );
+	if( surfaceSource( b, who, sb ) ) return 1;
+	for( int k = 0; k < 3; k++ )
+	{
+		o[k] = offset ? offset[k] : 0;
+		REQUIRE( o[k] >= -( 1 << 21 ) && o[k] <= ( 1 << 21 ), "%s: offset[%d] = %d is outside [-2^21, 2^21]", who, k, o[k] );
+	}
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_nearest_voxels( const mvrt_svo* svo, uint64_t n, const int32_t* queryDev, uint64_t maxDist2, uint64_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev,
+										 void* stream )
+{
+	const char* who = "mvrt_svo_nearest_voxels";
+	SurfaceSource s;
+	if( surfaceSource( svo, who, &s ) ) return 1;
+	REQUIRE( n < ( 1ull << 32 ), "%s: %llu queries are 2^32 or more", who, (unsigned long long)n );
+	REQUIRE( n == 0 || queryDev, "%s: null queries", who );
+	return nearestVoxels( s, n, queryDev, maxDist2, dist2Dev, nearestDev, attribsDev, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_nearest_between( const mvrt_svo* a, const mvrt_svo* b, const int32_t offset[3], uint64_t maxDist2, uint64_t capacity, uint64_t* dist2Dev, uint32_t* nearestDev,
+										  uint64_t* nOut, uint64_t* maxDist2Out, uint32_t* farthestOut, uint64_t* nZeroOut, uint64_t* nBeyondOut, void* stream )
+{
+	if( nOut ) *nOut = 0;
+	SurfaceSource sa, sb;
+	int32_t o[3];
+	if( querySources( a, b, "mvrt_svo_nearest_between", offset, &sa, &sb, o ) ) return 1;
+	NearestBetweenCounts c;
+	const int rc = nearestBetween( sa, sb, o, maxDist2, capacity, dist2Dev, nearestDev, &c, (hipStream_t)stream );
+	if( nOut ) *nOut = c.n; // (still returned where the capacity is refused)
+	if( rc ) return 1;
+	if( maxDist2Out ) *maxDist2Out = c.maxDist2;
+	if( farthestOut ) *farthestOut = c.farthest;
+	if( nZeroOut ) *nZeroOut = c.nZero;
+	if( nBeyondOut ) *nBeyondOut = c.nBeyond;
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_transfer_attributes( mvrt_svo* dst, const mvrt_svo* src, const int32_t offset[3], uint64_t maxDist2, uint32_t flags, uint64_t* nChangedOut,
+											  uint64_t* nBeyondOut, void* stream )
+{
+	const char* who = "mvrt_svo_transfer_attributes";
+	if( nChangedOut ) *nChangedOut = 0;
+	if( nBeyondOut ) *nBeyondOut = 0;
+	SurfaceSource sd, ss;
+	int32_t o[3];
+	if( querySources( dst, src, who, offset, &sd, &ss, o ) ) return 1;
+	REQUIRE( flags != 0u && ( flags & ~( MVRT_TRANSFER_COLOUR | MVRT_TRANSFER_EMISSION ) ) == 0u, "%s: flags 0x%x are not MVRT_TRANSFER_COLOUR (1) | MVRT_TRANSFER_EMISSION (2)",
+			 who, flags );
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf xyz, attribs;
+	uint64_t nTaken = 0, nChanged = 0, nBeyond = 0;
+	if( nearestTransferList( sd, ss, o, maxDist2, flags, xyz, attribs, &nTaken, &nChanged, &nBeyond, st ) ) return 1; // (near is taken in src as it is now)
+	if( nBeyondOut ) *nBeyondOut = nBeyond;
+	if( nChanged == 0 ) return 0; // no byte changes: the handle is not touched
+	if( ownerDrain( dst ) ) return 1; // steps already issued render the old scene; the edit writes in place
+	SvoBuildResult r;
+	int structural = 0;
+	uint32_t he = 0;
+	if( svoEditVoxels( dst->oct.morton.as<uint64_t>(), dst->oct.attrs.as<uint2>(), dst->oct.nVoxels, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nTaken,
+					   (int)dst->oct.info.gridRes, dst->oct.buildFlags, st, &r, &structural, &he ) )
+		return 1;
+	REQUIRE( !structural, "%s: internal error: the voxels of the handle are not its voxels", who ); // (every entry is a voxel of dst)
+	dst->oct.totalDumped = 0;
+	dst->oct.hasEmission = he;
+	if( nChangedOut ) *nChangedOut = nChanged;
+	return 0;
+}
+MVRT_EXPORT int mvrt_test_nearest_query_stats( uint64_t out[4] )
+{
+	const NearestQueryStats t = nearestQueryLastStats();
+	REQUIRE( out, "mvrt_test_nearest_query_stats: null out" );
+	out[0] = t.queries, out[1] = t.visits, out[2] = t.mostVisits, out[3] = t.compared;
+	return 0;
+}
+
 // Affine resampling (kernels_resample.hip).  Every refusal the arguments and the handles decide is made here, on the host: first what the arguments alone decide
 // (a null handle, the transform, the grid), then the handle, as the coarsening does.  The listing reads the sorted codes and the attributes alone; the build hands the list, which stays on the device, to the
 // levels of the voxel-list build, as the coarsening does.

@@ -229,6 +229,28 @@ int enclosedNearest( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev
 int enclosedNearestUnordered( const SurfaceSource& s, DevBuf& xyz, DevBuf& attribs, uint64_t* nCells, hipStream_t stream );
 NearestStats nearestLastStats(); // of this thread
 
+// nearest voxel of arbitrary lattice points (kernels_query.hip; mvrt_svo_nearest_voxels / mvrt_svo_nearest_between / mvrt_svo_transfer_attributes): morton, attrs,
+// nVoxels and levels of the sources are read; the query range, the offset, the flags and n < 2^32 are checked by the caller.  The calls block, keep their scratch in
+// DevBufs and write NOTHING to the caller's arrays before their last allocation and check have passed.
+struct NearestQueryStats // what the last call of this thread did (tools/nearest_query_bench.py through mvrt_test_nearest_query_stats)
+{
+	uint64_t queries = 0, visits = 0, mostVisits = 0, compared = 0;
+};
+struct NearestBetweenCounts
+{
+	uint64_t n = 0, maxDist2 = 0, nZero = 0, nBeyond = 0;
+	uint32_t farthest = 0;
+};
+int nearestVoxels( const SurfaceSource& s, uint64_t n, const int32_t* queryDev, uint64_t maxDist2, uint64_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, hipStream_t stream );
+// every voxel of a, moved by -o, queried in b
+int nearestBetween( const SurfaceSource& a, const SurfaceSource& b, const int32_t o[3], uint64_t maxDist2, uint64_t capacity, uint64_t* dist2Dev, uint32_t* nearestDev,
+					NearestBetweenCounts* counts, hipStream_t stream );
+// the list the attribute-only edit takes: the voxels of dst with a nearest voxel of src within the limit (*nTaken of them, xyz 3 x u32 and attribs 8 bytes, allocated
+// here) with the bytes they end with.  *nChanged == 0: no byte would change and no list is made
+int nearestTransferList( const SurfaceSource& dst, const SurfaceSource& src, const int32_t o[3], uint64_t maxDist2, uint32_t flags, DevBuf& xyz, DevBuf& attribs, uint64_t* nTaken,
+						 uint64_t* nChanged, uint64_t* nBeyond, hipStream_t stream );
+NearestQueryStats nearestQueryLastStats(); // of this thread
+
 // ---- sorted voxel lists (kernels_list.hip) -------------------------------------------------------------------------------------------------------------
 // What every voxel-set operator hands to svoBuildFromSorted: n sorted unique codes with their attributes and the emission flag over them, allocated by the
 // operator.  The one convention of "nothing changed": the arrays are left empty and n is the voxel count of the set the operator started from.

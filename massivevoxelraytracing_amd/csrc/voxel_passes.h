@@ -16,6 +16,8 @@
 //   nearest voxel   nearestAxisKey / nearestAxisCell / nearestGapHead (the cells of a line as consecutive keys), nearestGapKey, nearestEndKey, nearestGoOn and
 //                   nearestScan of kernels_nearest.hip: the minimum of the packed key over a gap of enclosed cells and its two end voxels.  Host-callable
 //                   (tests/hip/nearest_host.hip).
+//   nearest query   nearestBoxDist2, nearestChildRange, nearestChildOrder, nearestSeed, nearestPairBelow and the whole walk nearestQueryWalk of kernels_query.hip: the
+//                   nearest voxel of an arbitrary lattice point by branch and bound on the sorted codes.  Host-callable (tests/hip/query_host.hip).
 //   two sets        combineTranslate (a code moved by an integer offset and clipped to a grid) of kernels_combine.hip, and combineWindow / codeIndexInRange: the
 //                   partner search of a group of ascending codes, bounded once per group.  Host-callable (tests/hip/combine_host.hip).
 //   resampling      resamplePoint (the point rule of mvrt_cell_transform), resampleBox / resampleBoxShift / resampleBoxHoldsVoxel (the conservative test of a node
@@ -269,6 +271,157 @@ MVRT_HDI uint2 nearestAttrib( uint2 a )
 	a.x |= 0xFF000000u;
 	a.y |= 0xFF000000u;
 	return a;
+}
+
+// ---- nearest voxel of arbitrary lattice points (kernels_query.hip) ----------------------------------------------------------------------------------------------
+// An exact branch-and-bound descent on the n sorted codes.  A node is a code prefix at a depth d in [0, L] with its range [lo, hi) of the code
+// array: depth 0 is the grid with [0, n), depth L a voxel, whose place in the array is its vIndex.  A query q is three int32, each in [-2^22, 2^22]; a
+// coordinate difference is below 2^23 in magnitude, a square below 2^46 and a sum of three below 2^48: everything is taken in int64 / uint64 and nothing can
+// wrap (d2 itself stays below 2^47).  Host-callable (tests/hip/query_host.hip runs the whole walk against brute force).
+#define NEAREST_QUERY_NONE_D2 0xFFFFFFFFFFFFFFFFull // no voxel within the limit: dist2 = UINT64_MAX, nearest = 0xFFFFFFFF, attribs 0
+#define NEAREST_QUERY_NONE 0xFFFFFFFFu
+#define NEAREST_QUERY_COORD_MAX ( 1 << 22 )
+#define NEAREST_QUERY_RUN 8u // a child of at most this many voxels is compared voxel by voxel: cheaper than three more levels of searches
+// the squared distance from q to the cells [c, c + 2^s - 1] per axis: 0 inside, else to the nearest face, edge or corner cell
+MVRT_HDI uint64_t nearestBoxDist2( int32_t qx, int32_t qy, int32_t qz, uint32_t cx, uint32_t cy, uint32_t cz, uint32_t s )
+{
+	const int64_t span = ( (int64_t)1 << s ) - 1;
+	const int64_t q[3] = { qx, qy, qz }, c[3] = { (int64_t)cx, (int64_t)cy, (int64_t)cz };
+	uint64_t d2 = 0;
+	for( int k = 0; k < 3; k++ )
+	{
+		const int64_t d = q[k] < c[k] ? c[k] - q[k] : q[k] > c[k] + span ? q[k] - c[k] - span : 0;
+		d2 += (uint64_t)d * (uint64_t)d;
+	}
+	return d2;
+}
+MVRT_HDI uint64_t nearestPointDist2( int32_t qx, int32_t qy, int32_t qz, uint64_t code )
+{
+	uint32_t x, y, z;
+	mortonDecode( code, x, y, z );
+	return nearestBoxDist2( qx, qy, qz, x, y, z, 0u );
+}
+// ( d2, vIndex ) compared as a pair: the candidate replaces the best when it is nearer, or as near with a lower index
+MVRT_HDI bool nearestPairBelow( uint64_t d2, uint32_t v, uint64_t bestD2, uint32_t bestV ) { return d2 < bestD2 || ( d2 == bestD2 && v < bestV ); }
+// The pruning rule, which is the correctness of the walk: a box is skipped only when its distance EXCEEDS the best d2 so far or the limit -- not >=: a voxel
+// at exactly the best d2 can still lower the vIndex (the stop rule of nearestGoOn)
+MVRT_HDI bool nearestBoxSkipped( uint64_t boxD2, uint64_t bestD2, uint64_t maxDist2 ) { return boxD2 > bestD2 || boxD2 > maxDist2; }
+// the k-th child to visit, k in [0, 8), for a query in octant `oct` of the node (bit a = q is at or beyond the node's centre on axis a): the octant itself, its
+// three face neighbours, its three edge neighbours, the opposite one.  The order only decides how soon the bound tightens, never the answer
+MVRT_HDI uint32_t nearestChildOrder( uint32_t oct, uint32_t k ) { return oct ^ ( ( 0x76534210u >> ( 4u * k ) ) & 7u ); }
+MVRT_HDI uint32_t nearestOctant( int32_t qx, int32_t qy, int32_t qz, uint32_t cx, uint32_t cy, uint32_t cz, uint32_t s ) // s = log2 of the CHILD size
+{
+	const int64_t h = (int64_t)1 << s;
+	return ( qx >= (int64_t)cx + h ? 1u : 0u ) | ( qy >= (int64_t)cy + h ? 2u : 0u ) | ( qz >= (int64_t)cz + h ? 4u : 0u );
+}
+// the range of child c (its size 2^s per axis) of the node with code prefix `prefix` (the code of its lowest cell) inside the node's range [lo, hi): two
+// searches in the range, none where the child is the first or the last of its node.  ( prefix + ( c + 1 ) << 3s ) <= 2^63
+MVRT_HDI void nearestChildRange( const uint64_t* __restrict__ codes, uint64_t lo, uint64_t hi, uint64_t prefix, uint32_t c, uint32_t s, uint64_t* cLo, uint64_t* cHi )
+{
+	const uint64_t first = prefix | (uint64_t)c << ( 3u * s );
+	*cLo = c == 0u ? lo : lowerBound( codes, lo, hi, first );
+	*cHi = c == 7u ? hi : lowerBound( codes, *cLo, hi, first + ( 1ull << ( 3u * s ) ) );
+}
+// the bound before the descent, from real voxels: the one or two codes next to where the code of q, clamped into the grid, would stand.  Every candidate is the
+// true distance to a real voxel, so nothing can fall below the minimum
+MVRT_HDI uint32_t nearestSeed( const uint64_t* __restrict__ codes, uint64_t n, uint32_t L, int32_t qx, int32_t qy, int32_t qz, uint64_t* bestD2, uint32_t* bestV )
+{
+	uint32_t taken = 0u;
+	const int32_t last = (int32_t)( ( 1u << L ) - 1u );
+	const uint32_t x = (uint32_t)( qx < 0 ? 0 : qx > last ? last : qx ), y = (uint32_t)( qy < 0 ? 0 : qy > last ? last : qy ), z = (uint32_t)( qz < 0 ? 0 : qz > last ? last : qz );
+	const uint64_t j = lowerBound( codes, 0, n, mortonEncode( x, y, z ) );
+	for( uint64_t i = j > 0 ? j - 1 : 0; i < n && i <= j; i++ )
+	{
+		const uint64_t d2 = nearestPointDist2( qx, qy, qz, codes[i] );
+		if( nearestPairBelow( d2, (uint32_t)i, *bestD2, *bestV ) ) *bestD2 = d2, *bestV = (uint32_t)i;
+		taken++;
+	}
+	return taken; // the voxels compared
+}
+// The backtracking state of one walk: per depth d in [0, L) the range of the node there, kept by the caller (the kernel: LDS, one column per lane; a host
+// program: an array), and the number of children already tried, 4 bits per depth in two words that stay in registers
+struct NearestQueryHostStack
+{
+	uint32_t lo[21], hi[21];
+	MVRT_HDI void put( uint32_t d, uint32_t l, uint32_t h ) { lo[d] = l, hi[d] = h; }
+	MVRT_HDI void get( uint32_t d, uint32_t& l, uint32_t& h ) const { l = lo[d], h = hi[d]; }
+};
+MVRT_HDI uint32_t nearestTriedGet( uint64_t w0, uint64_t w1, uint32_t d ) { return (uint32_t)( ( d < 16u ? w0 >> ( 4u * d ) : w1 >> ( 4u * ( d - 16u ) ) ) & 15ull ); }
+MVRT_HDI void nearestTriedSet( uint64_t& w0, uint64_t& w1, uint32_t d, uint32_t k )
+{
+	if( d < 16u ) w0 = ( w0 & ~( 15ull << ( 4u * d ) ) ) | (uint64_t)k << ( 4u * d );
+	else w1 = ( w1 & ~( 15ull << ( 4u * ( d - 16u ) ) ) ) | (uint64_t)k << ( 4u * ( d - 16u ) );
+}
+struct NearestQueryAnswer
+{
+	uint64_t d2;	  // NEAREST_QUERY_NONE_D2: no voxel within maxDist2
+	uint32_t near;	  // the lowest vIndex among the voxels at d2
+	uint32_t visits;  // non-empty children whose box was tested
+	uint32_t compared; // voxels whose distance was taken, the seed's included
+};
+// The whole query: n >= 1 sorted unique codes of a grid of L in [1, 21] levels, q within +-NEAREST_QUERY_COORD_MAX, n < 2^32.  Every loop is bounded: a
+// (node, child) pair is taken once, a node has 8 children and a path L nodes; a run by NEAREST_QUERY_RUN.  seed == 0 starts without a bound (measuring only)
+template <class Stack>
+MVRT_HDI NearestQueryAnswer nearestQueryWalk( const uint64_t* __restrict__ codes, uint64_t n, uint32_t L, int32_t qx, int32_t qy, int32_t qz, uint64_t maxDist2, int seed, Stack& stack )
+{
+	NearestQueryAnswer r = { NEAREST_QUERY_NONE_D2, NEAREST_QUERY_NONE, 0u, 0u };
+	if( seed ) r.compared = nearestSeed( codes, n, L, qx, qy, qz, &r.d2, &r.near );
+	if( r.d2 == 0ull ) return r; // the query is a voxel: the voxels are distinct, nothing else is as near, and 0 is within every limit
+	uint64_t tried0 = 0, tried1 = 0, prefix = 0;
+	uint32_t d = 0, lo = 0, hi = (uint32_t)n, cx = 0, cy = 0, cz = 0, k = 0;
+	for( ;; )
+	{
+		if( k == 8u ) // this node is done: back to its parent
+		{
+			if( d == 0u ) break;
+			d--;
+			stack.get( d, lo, hi );
+			k = nearestTriedGet( tried0, tried1, d );
+			const uint32_t keep = ~( ( 1u << ( L - d ) ) - 1u ); // (L - d <= 21)
+			cx &= keep, cy &= keep, cz &= keep;
+			prefix &= ~( ( 1ull << ( 3u * ( L - d ) ) ) - 1ull );
+			continue;
+		}
+		const uint32_t s = L - d - 1u; // log2 of the child size
+		const uint32_t c = nearestChildOrder( nearestOctant( qx, qy, qz, cx, cy, cz, s ), k++ );
+		uint64_t cLo, cHi;
+		nearestChildRange( codes, lo, hi, prefix, c, s, &cLo, &cHi );
+		if( cLo == cHi ) continue; // no voxel below this child
+		const uint32_t kx = cx | ( c & 1u ) << s, ky = cy | ( ( c >> 1 ) & 1u ) << s, kz = cz | ( c >> 2 ) << s;
+		r.visits++;
+		if( nearestBoxSkipped( nearestBoxDist2( qx, qy, qz, kx, ky, kz, s ), r.d2, maxDist2 ) ) continue;
+		if( s == 0u || cHi - cLo <= NEAREST_QUERY_RUN ) // a voxel, or a short run of them
+		{
+			for( uint64_t i = cLo; i < cHi; i++ )
+			{
+				const uint64_t d2 = nearestPointDist2( qx, qy, qz, codes[i] );
+				if( nearestPairBelow( d2, (uint32_t)i, r.d2, r.near ) ) r.d2 = d2, r.near = (uint32_t)i;
+			}
+			r.compared += (uint32_t)( cHi - cLo );
+			continue;
+		}
+		stack.put( d, lo, hi );
+		nearestTriedSet( tried0, tried1, d, k );
+		d++;
+		lo = (uint32_t)cLo, hi = (uint32_t)cHi;
+		cx = kx, cy = ky, cz = kz;
+		prefix |= (uint64_t)c << ( 3u * s );
+		k = 0u;
+	}
+	if( r.d2 > maxDist2 ) r.d2 = NEAREST_QUERY_NONE_D2, r.near = NEAREST_QUERY_NONE; // (a seed beyond the limit, or nothing in reach)
+	return r;
+}
+// the query of voxel `code` of another set moved by -o into this one's cell space: q = v - o, |q| <= 2^21 + 2^21
+MVRT_HDI void nearestQueryOfVoxel( uint64_t code, const int32_t o[3], int32_t* qx, int32_t* qy, int32_t* qz )
+{
+	uint32_t x, y, z;
+	mortonDecode( code, x, y, z );
+	*qx = (int32_t)x - o[0], *qy = (int32_t)y - o[1], *qz = (int32_t)z - o[2];
+}
+// the 8 bytes a voxel with the attribute `own` ends with when it takes the words `flags` names (1 = colour, 2 = emission) from `from`, as MVRT_VOXEL_SET stores them
+MVRT_HDI uint2 nearestTransferAttrib( uint2 own, uint2 from, uint32_t flags )
+{
+	return nearestAttrib( make_uint2( ( flags & 1u ) ? from.x : own.x, ( flags & 2u ) ? from.y : own.y ) );
 }
 
 // ---- two sets (kernels_combine.hip) -------------------------------------------------------------------------------------------------------------------------
