@@ -1,6 +1,7 @@
 // api.hip -- the C-ABI of libmvrt_hip.so (include/mvrt.h), first half: the runtime pass-throughs, the octree handle (the reference's host struct
 // IntersectorOctreeGPU, IntersectorOctreeGPU.hpp:21-275, behind an opaque handle), the batch traces and the camera.  The path tracer is api_pt.hip, the
-// voxel-set operators are api_voxels.hip; the one way a handle takes a new octree (adoptBuild, adoptSorted) is here.
+// voxel-set operators are api_voxels.hip; the ways a handle takes a new octree (adoptBuild, adoptSortedOnGrid, adoptSorted) and the one way it is edited from a
+// device list (editHandle) are here.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -340,11 +341,45 @@ int adoptSorted( mvrt_svo* svo, SortedVoxels& v, hipStream_t st )
 {
 	if( v.unchanged( svo->oct.nVoxels ) ) return 0; // nothing changes: the handle is not touched
 	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
+	const mvrt_svo_info info = svo->oct.info; // (read before the old octree goes)
+	return adoptSortedOnGrid( svo, v, 0 /* as an edit leaves it */, info.lower, info.dps, (int)info.gridRes, svo->oct.buildFlags, nullptr, st );
+}
+// A new octree from a sorted list on a given grid (the coarsening, the resampling, adoptSorted): the levels are built next to whatever the handle holds, which may
+// be the source of the list, with the list's emission flag and the caller's totalDumped, and adoptBuild swaps.  *nOut (may be null) = the voxels of the list, written
+// once the levels stand.  The caller has drained the owner
+int adoptSortedOnGrid( mvrt_svo* svo, SortedVoxels& v, uint64_t totalDumped, const float origin[3], float dps, int gridRes, int flags, uint64_t* nOut, hipStream_t st )
+{
 	SvoBuildResult r;
-	if( svoBuildFromSorted( v.codes, v.attrs, v.n, (int)svo->oct.info.gridRes, svo->oct.buildFlags, st, &r ) ) return 1;
+	if( svoBuildFromSorted( v.codes, v.attrs, v.n, gridRes, flags, st, &r ) ) return 1;
 	r.hasEmission = v.hasEmission;
-	r.totalDumped = 0; // (as an edit leaves it)
-	return adoptOnOwnGrid( svo, r, svo->oct.buildFlags );
+	r.totalDumped = totalDumped;
+	if( nOut ) *nOut = v.n;
+	return adoptBuild( svo, r, origin, dps, gridRes, flags );
+}
+// The one route of an edit from a device list of n entries (mvrt_svo_edit_voxels, the fills, the attribute transfer): the owner is drained, the edit runs on the
+// handle's own list, grid and flags, and the handle ends as the edit's outcome says -- a structural edit is adopted on the handle's grid, an attribute-only one has
+// written in place.  accepts: the outcomes the caller's list can have (EDIT_STRUCTURAL | EDIT_ATTRIBUTES); the other one is an internal error, worded for the one
+// caller that can meet it.  ownXyz / ownAttribs (may be null): the caller's scratch behind xyz / attribs, released before the levels are adopted
+int editHandle( mvrt_svo* svo, const char* who, int accepts, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, DevBuf* ownXyz, DevBuf* ownAttribs,
+				hipStream_t st )
+{
+	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene; an attribute-only edit writes in place
+	Octree& o = svo->oct;
+	SvoBuildResult r;
+	int structural = 0;
+	uint32_t he = 0;
+	if( svoEditVoxels( o.morton.as<uint64_t>(), o.attrs.as<uint2>(), o.nVoxels, xyz, attribs, ops, n, (int)o.info.gridRes, o.buildFlags, st, &r, &structural, &he ) ) return 1;
+	REQUIRE( structural || ( accepts & EDIT_ATTRIBUTES ), "%s: internal error: the enclosed cells hold voxels", who ); // (a fill: every cell is an insert)
+	REQUIRE( !structural || ( accepts & EDIT_STRUCTURAL ), "%s: internal error: the voxels of the handle are not its voxels", who ); // (a transfer: every entry is a voxel)
+	if( !structural )
+	{
+		o.totalDumped = 0;
+		o.hasEmission = he;
+		return 0;
+	}
+	if( ownXyz ) ownXyz->release();
+	if( ownAttribs ) ownAttribs->release();
+	return adoptOnOwnGrid( svo, r, o.buildFlags );
 }
 MVRT_EXPORT int mvrt_svo_build_ex( mvrt_svo* svo, const float* verticesHost, const float* vcolorsHost, const float* vemissionsHost, uint64_t nVertices, void* stream,
 								   const float origin[3], float dps, int gridRes, int flags )
@@ -383,8 +418,7 @@ MVRT_EXPORT int mvrt_svo_build_voxels( mvrt_svo* svo, const uint32_t* xyzDev, co
 	REQUIRE( xyzDev && origin, "mvrt_svo_build_voxels: null coordinates or origin" );
 	REQUIRE( n >= 1 && n < 0xFFFFFFFFull, "mvrt_svo_build_voxels: voxel count %llu is not in [1, 2^32-2]", (unsigned long long)n );
 	REQUIRE( levelsOf( gridRes ) > 0 && gridRes <= ( 1 << 21 ), "mvrt_svo_build_voxels: gridRes %d is not a power of two in [2, 2^21]", gridRes );
-	REQUIRE( ( flags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0,
-			 "mvrt_svo_build_voxels: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", flags );
+	REQUIRE_BUILD_FLAGS( "mvrt_svo_build_voxels", flags );
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
 	SvoBuildResult r;
@@ -398,22 +432,7 @@ MVRT_EXPORT int mvrt_svo_edit_voxels( mvrt_svo* svo, const uint32_t* xyzDev, con
 	REQUIRE( svo->oct.morton.p, "mvrt_svo_edit_voxels: an uploaded octree keeps no Morton codes; only octrees built by this library can be edited" );
 	REQUIRE( xyzDev, "mvrt_svo_edit_voxels: null coordinates" );
 	REQUIRE( n >= 1 && n < 0xFFFFFFFFull, "mvrt_svo_edit_voxels: entry count %llu is not in [1, 2^32-2]", (unsigned long long)n );
-	hipStream_t st = (hipStream_t)stream;
-	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene; an attribute-only edit writes in place
-	const mvrt_svo_info& info = svo->oct.info;
-	SvoBuildResult r;
-	int structural = 0;
-	uint32_t he = 0;
-	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyzDev, attribsDev, opsDev, n, (int)info.gridRes, svo->oct.buildFlags, st, &r,
-					   &structural, &he ) )
-		return 1;
-	if( !structural )
-	{
-		svo->oct.totalDumped = 0;
-		svo->oct.hasEmission = he;
-		return 0;
-	}
-	return adoptOnOwnGrid( svo, r, svo->oct.buildFlags );
+	return editHandle( svo, "mvrt_svo_edit_voxels", EDIT_STRUCTURAL | EDIT_ATTRIBUTES, xyzDev, attribsDev, opsDev, n, nullptr, nullptr, (hipStream_t)stream );
 }
 MVRT_EXPORT int mvrt_svo_read_voxels( const mvrt_svo* svo, uint32_t* xyzDev, uint32_t* attribsDev, void* stream )
 {
@@ -463,8 +482,7 @@ MVRT_EXPORT int mvrt_svo_rebuild( mvrt_svo* svo, int flags, void* stream )
 {
 	REQUIRE( svo, "mvrt_svo_rebuild: null handle" );
 	REQUIRE( !svo->empty(), "mvrt_svo_rebuild: no octree (build or upload first)" );
-	REQUIRE( ( flags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0, "mvrt_svo_rebuild: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)",
-			 flags );
+	REQUIRE_BUILD_FLAGS( "mvrt_svo_rebuild", flags );
 	hipStream_t st = (hipStream_t)stream;
 	if( ownerDrain( svo ) ) return 1; // steps already issued keep the octree they were issued with
 	const Octree& o = svo->oct;

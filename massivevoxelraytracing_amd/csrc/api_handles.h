@@ -20,6 +20,10 @@
 		}                             \
 	} while( 0 )
 
+// the refusal of build flags other than the two a voxel-list build knows, in the name of the call `who`
+#define REQUIRE_BUILD_FLAGS( who, flags ) \
+	REQUIRE( ( ( flags ) & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0, "%s: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", who, flags )
+
 // scratch of the persistent traversal kernels with its owner: one per octree handle and one per pipeline slot of a path tracer
 struct Workspace
 {
@@ -120,11 +124,19 @@ static inline CameraPinhole cameraFrom15( const float c[15] ) // the 15 floats o
 int ptFlush( mvrt_pt* pt ); // (api_pt.hip)
 int ptDrain( mvrt_pt* pt );
 
-// What api.hip and api_voxels.hip share.  ownerDrain finishes the steps of the path tracer that owns the handle; adoptBuild, adoptOnOwnGrid and adoptSorted are
-// the only ways a handle takes a new octree (api.hip, where each says what a failure leaves); surfaceSource refuses a handle without sorted codes, in the name
-// of the call `who`, and fills what the passes read (api_voxels.hip)
+// What api.hip and api_voxels.hip share.  ownerDrain finishes the steps of the path tracer that owns the handle; adoptBuild, adoptOnOwnGrid, adoptSortedOnGrid and
+// adoptSorted are the only ways a handle takes a new octree and editHandle is the only way it is edited from a device list (api.hip, where each says what a failure
+// leaves); surfaceSource refuses a handle without sorted codes, in the name of the call `who`, and fills what the passes read (api_voxels.hip)
 int ownerDrain( const mvrt_svo* svo );
 int adoptBuild( mvrt_svo* svo, SvoBuildResult& r, const float origin[3], float dps, int gridRes, int flags );
 int adoptOnOwnGrid( mvrt_svo* svo, SvoBuildResult& r, int flags );
+int adoptSortedOnGrid( mvrt_svo* svo, SortedVoxels& v, uint64_t totalDumped, const float origin[3], float dps, int gridRes, int flags, uint64_t* nOut, hipStream_t stream );
 int adoptSorted( mvrt_svo* svo, SortedVoxels& v, hipStream_t stream );
+enum // the outcomes of an edit that a caller of editHandle accepts
+{
+	EDIT_STRUCTURAL = 1,
+	EDIT_ATTRIBUTES = 2
+};
+int editHandle( mvrt_svo* svo, const char* who, int accepts, const uint32_t* xyz, const uint32_t* attribs, const uint8_t* ops, uint64_t n, DevBuf* ownXyz, DevBuf* ownAttribs,
+				hipStream_t stream );
 int surfaceSource( const mvrt_svo* svo, const char* who, SurfaceSource* s );

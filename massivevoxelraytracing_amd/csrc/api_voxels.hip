@@ -1,6 +1,6 @@
 // api_voxels.hip -- the C-ABI of libmvrt_hip.so (include/mvrt.h), the voxel-set operators on a built octree: surface extraction, enclosed cells and the fill,
 // coarsening, morphology with the step elements and with the ball, connected components, the two-set operators and the affine resampling.  Every refusal the arguments and the handles
-// decide is made here, on the host; the listings never touch the handle, the in-place calls end in adoptSorted (api.hip).
+// decide is made here, on the host; the listings never touch the handle, the in-place calls end in adoptSorted, adoptSortedOnGrid or editHandle (api.hip).
 #include "api_handles.h"
 
 // Surface extraction (kernels_surface.hip).  Only the sorted codes and, where there is one, the cell index are read: every flavour is accepted and the
@@ -97,24 +97,25 @@ MVRT_EXPORT int mvrt_svo_surface_merged_masked( const mvrt_svo* svo, const uint8
 }
 
 // Enclosed empty cells and the fill (kernels_fill.hip).  The listing reads the sorted codes alone, like the surface calls.  The fill hands the cells, which stay on
-// the device, to the edit's own path: what it leaves is what mvrt_svo_edit_voxels leaves, by construction.
+// the device, to the edit's own route (editHandle, api.hip): what it leaves is what mvrt_svo_edit_voxels leaves, by construction.
 MVRT_EXPORT int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, void* stream )
 {
 	SurfaceSource s;
 	if( surfaceSource( svo, "mvrt_svo_enclosed_cells", &s ) ) return 1;
 	return enclosedCells( s, capacity, xyzDev, regionDev, nCellsOut, nRegionsOut, (hipStream_t)stream );
 }
-MVRT_EXPORT int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8], uint64_t* nFilledOut, void* stream )
+// both fills: they differ in the step that makes the cells, which for the nearest-voxel fill brings one attribute per cell along (fillAttribHost is null then)
+static int fillEnclosed( mvrt_svo* svo, const char* who, bool nearest, const uint8_t* fillAttribHost, uint64_t* nFilledOut, void* stream )
 {
 	if( nFilledOut ) *nFilledOut = 0;
 	SurfaceSource s;
-	if( surfaceSource( svo, "mvrt_svo_fill_enclosed", &s ) ) return 1;
+	if( surfaceSource( svo, who, &s ) ) return 1;
 	hipStream_t st = (hipStream_t)stream;
 	DevBuf xyz, attribs;
 	uint64_t nCells = 0;
-	if( enclosedCellsUnordered( s, xyz, &nCells, st ) ) return 1;
+	if( nearest ? enclosedNearestUnordered( s, xyz, attribs, &nCells, st ) : enclosedCellsUnordered( s, xyz, &nCells, st ) ) return 1; // (near is taken on the set as it is now)
 	if( nCells == 0 ) return 0; // nothing to fill: the handle is not touched
-	REQUIRE( (uint64_t)svo->oct.nVoxels + nCells < 0xFFFFFFFFull, "mvrt_svo_fill_enclosed: %llu voxels and %llu enclosed cells exceed the 32-bit index range of the builder",
+	REQUIRE( (uint64_t)svo->oct.nVoxels + nCells < 0xFFFFFFFFull, "%s: %llu voxels and %llu enclosed cells exceed the 32-bit index range of the builder", who,
 			 (unsigned long long)svo->oct.nVoxels, (unsigned long long)nCells );
 	if( fillAttribHost )
 	{
@@ -122,24 +123,17 @@ MVRT_EXPORT int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribH
 		memcpy( &a, fillAttribHost, 8 );
 		if( attribs.alloc( nCells * 8 ) || launchFillAttribs( a, nCells, attribs.as<uint2>(), st ) ) return 1;
 	}
-	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
-	const mvrt_svo_info& info = svo->oct.info;
-	SvoBuildResult r;
-	int structural = 0;
-	uint32_t he = 0;
-	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nCells, (int)info.gridRes,
-					   svo->oct.buildFlags, st, &r, &structural, &he ) )
-		return 1;
-	REQUIRE( structural, "mvrt_svo_fill_enclosed: internal error: the enclosed cells hold voxels" ); // (every cell is an insert)
-	xyz.release();
-	attribs.release();
-	if( adoptOnOwnGrid( svo, r, svo->oct.buildFlags ) ) return 1;
+	if( editHandle( svo, who, EDIT_STRUCTURAL, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nCells, &xyz, &attribs, st ) ) return 1;
 	if( nFilledOut ) *nFilledOut = nCells;
 	return 0;
 }
+MVRT_EXPORT int mvrt_svo_fill_enclosed( mvrt_svo* svo, const uint8_t fillAttribHost[8], uint64_t* nFilledOut, void* stream )
+{
+	return fillEnclosed( svo, "mvrt_svo_fill_enclosed", false, fillAttribHost, nFilledOut, stream );
+}
 
 // The same cells with their nearest voxel, and the fill that takes its colours from them (kernels_nearest.hip).  The fill is mvrt_svo_fill_enclosed with one
-// attribute per cell: the same route through the edit, the same refusals in the same order.
+// attribute per cell: the same function (fillEnclosed above), so the same route through the edit and the same refusals in the same order.
 MVRT_EXPORT int mvrt_svo_enclosed_nearest( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev,
 										   uint64_t* nCellsOut, uint64_t* nRegionsOut, void* stream )
 {
@@ -149,31 +143,7 @@ MVRT_EXPORT int mvrt_svo_enclosed_nearest( const mvrt_svo* svo, uint64_t capacit
 }
 MVRT_EXPORT int mvrt_svo_fill_enclosed_nearest( mvrt_svo* svo, uint64_t* nFilledOut, void* stream )
 {
-	if( nFilledOut ) *nFilledOut = 0;
-	SurfaceSource s;
-	if( surfaceSource( svo, "mvrt_svo_fill_enclosed_nearest", &s ) ) return 1;
-	hipStream_t st = (hipStream_t)stream;
-	DevBuf xyz, attribs;
-	uint64_t nCells = 0;
-	if( enclosedNearestUnordered( s, xyz, attribs, &nCells, st ) ) return 1; // (near is taken on the set as it is now)
-	if( nCells == 0 ) return 0; // nothing to fill: the handle is not touched
-	REQUIRE( (uint64_t)svo->oct.nVoxels + nCells < 0xFFFFFFFFull,
-			 "mvrt_svo_fill_enclosed_nearest: %llu voxels and %llu enclosed cells exceed the 32-bit index range of the builder", (unsigned long long)svo->oct.nVoxels,
-			 (unsigned long long)nCells );
-	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene
-	const mvrt_svo_info& info = svo->oct.info;
-	SvoBuildResult r;
-	int structural = 0;
-	uint32_t he = 0;
-	if( svoEditVoxels( svo->oct.morton.as<uint64_t>(), svo->oct.attrs.as<uint2>(), svo->oct.nVoxels, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nCells, (int)info.gridRes,
-					   svo->oct.buildFlags, st, &r, &structural, &he ) )
-		return 1;
-	REQUIRE( structural, "mvrt_svo_fill_enclosed_nearest: internal error: the enclosed cells hold voxels" ); // (every cell is an insert)
-	xyz.release();
-	attribs.release();
-	if( adoptOnOwnGrid( svo, r, svo->oct.buildFlags ) ) return 1;
-	if( nFilledOut ) *nFilledOut = nCells;
-	return 0;
+	return fillEnclosed( svo, "mvrt_svo_fill_enclosed_nearest", true, nullptr, nFilledOut, stream );
 }
 MVRT_EXPORT int mvrt_test_enclosed_nearest_stats( uint64_t out[8] )
 {
@@ -209,8 +179,7 @@ MVRT_EXPORT int mvrt_svo_coarse_voxels( const mvrt_svo* svo, int levelsDown, uin
 MVRT_EXPORT int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levelsDown, uint64_t minCount, int buildFlags, void* stream )
 {
 	REQUIRE( src && dst, "mvrt_svo_coarsen: null handle" );
-	REQUIRE( ( buildFlags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0,
-			 "mvrt_svo_coarsen: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", buildFlags );
+	REQUIRE_BUILD_FLAGS( "mvrt_svo_coarsen", buildFlags );
 	if( coarsenSource( src, "mvrt_svo_coarsen", levelsDown, minCount ) ) return 1;
 	const mvrt_svo_info info = src->oct.info; // (a copy: dst may be src)
 	const float dps = info.dps * (float)( 1u << levelsDown ); // exact: a power of two
@@ -222,12 +191,7 @@ MVRT_EXPORT int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levels
 	SortedVoxels v;
 	if( coarseList( src->oct.morton.as<uint64_t>(), src->oct.attrs.as<uint2>(), nFine, levelsDown, minCount, v, st ) ) return 1;
 	REQUIRE( v.n >= 1, "mvrt_svo_coarsen: minCount %llu would leave no voxel (no coarse cell holds that many of the %u voxels)", (unsigned long long)minCount, nFine );
-	SvoBuildResult r;
-	if( svoBuildFromSorted( v.codes, v.attrs, v.n, gridRes, buildFlags, st, &r ) ) return 1;
-	r.hasEmission = v.hasEmission;
-	r.totalDumped = nFine;
-	const float origin[3] = { info.lower[0], info.lower[1], info.lower[2] };
-	return adoptBuild( dst, r, origin, dps, gridRes, buildFlags ); // (the source is read before the old octree of dst goes)
+	return adoptSortedOnGrid( dst, v, nFine, info.lower, dps, gridRes, buildFlags, nullptr, st ); // (the source is read before the old octree of dst goes)
 }
 
 // Dilation, erosion, closing and opening (kernels_morph.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listings read the
@@ -383,21 +347,30 @@ MVRT_EXPORT int mvrt_svo_keep_components( mvrt_svo* svo, int element, uint64_t m
 static_assert( MVRT_COMBINE_UNION == MVRT_COMBINE_OP_UNION && MVRT_COMBINE_INTERSECTION == MVRT_COMBINE_OP_INTERSECTION && MVRT_COMBINE_DIFFERENCE == MVRT_COMBINE_OP_DIFFERENCE &&
 				   MVRT_COMBINE_XOR == MVRT_COMBINE_OP_XOR && (int)MVRT_COMBINE_ATTRIB_B == MVRT_COMBINE_FLAG_ATTRIB_B,
 			   "mvrt.h and launch.h number the operators alike" );
-static int combineSources( const mvrt_svo* a, const mvrt_svo* b, const char* who, int op, const int32_t offset[3], uint32_t flags, SurfaceSource* sa, SurfaceSource* sb, int32_t o[3] )
+// The second handle of a two-set call, in the words of the call (`missing`: how it names one that is not there, `name`: how it names the handle), and its cell offset: the
+// checks of the two-set operators here and of the nearest-voxel calls below
+static int secondSource( const mvrt_svo* b, const char* who, const char* missing, const char* name, SurfaceSource* sb )
 {
-	if( surfaceSource( a, who, sa ) ) return 1;
-	REQUIRE( b, "%s: null handle b", who );
-	REQUIRE( !b->empty(), "%s: b holds no octree (build first)", who );
-	REQUIRE( b->oct.morton.p, "%s: b is an uploaded octree, which keeps no Morton codes", who );
-	if( surfaceSource( b, who, sb ) ) return 1;
-	REQUIRE( op >= MVRT_COMBINE_UNION && op <= MVRT_COMBINE_XOR, "%s: unknown op %d (MVRT_COMBINE_UNION = 0, _INTERSECTION = 1, _DIFFERENCE = 2, _XOR = 3)", who, op );
-	REQUIRE( ( flags & ~(uint32_t)MVRT_COMBINE_ATTRIB_B ) == 0, "%s: unknown flags 0x%x (MVRT_COMBINE_ATTRIB_B only)", who, flags );
+	REQUIRE( b, "%s: null %s", who, missing );
+	REQUIRE( !b->empty(), "%s: %s holds no octree (build first)", who, name );
+	REQUIRE( b->oct.morton.p, "%s: %s is an uploaded octree, which keeps no Morton codes", who, name );
+	return surfaceSource( b, who, sb );
+}
+static int cellOffset( const char* who, const int32_t offset[3], int32_t o[3] )
+{
 	for( int k = 0; k < 3; k++ )
 	{
 		o[k] = offset ? offset[k] : 0;
 		REQUIRE( o[k] >= -( 1 << 21 ) && o[k] <= ( 1 << 21 ), "%s: offset[%d] = %d is outside [-2^21, 2^21]", who, k, o[k] );
 	}
 	return 0;
+}
+static int combineSources( const mvrt_svo* a, const mvrt_svo* b, const char* who, int op, const int32_t offset[3], uint32_t flags, SurfaceSource* sa, SurfaceSource* sb, int32_t o[3] )
+{
+	if( surfaceSource( a, who, sa ) || secondSource( b, who, "handle b", "b", sb ) ) return 1;
+	REQUIRE( op >= MVRT_COMBINE_UNION && op <= MVRT_COMBINE_XOR, "%s: unknown op %d (MVRT_COMBINE_UNION = 0, _INTERSECTION = 1, _DIFFERENCE = 2, _XOR = 3)", who, op );
+	REQUIRE( ( flags & ~(uint32_t)MVRT_COMBINE_ATTRIB_B ) == 0, "%s: unknown flags 0x%x (MVRT_COMBINE_ATTRIB_B only)", who, flags );
+	return cellOffset( who, offset, o );
 }
 MVRT_EXPORT int mvrt_svo_combine_voxels( const mvrt_svo* a, const mvrt_svo* b, int op, const int32_t offset[3], uint32_t flags, uint64_t capacity, uint32_t* xyzDev,
 										 uint32_t* attribsDev, uint8_t* sourceDev, uint64_t* nOut, uint64_t* nOverlapOut, uint64_t* nClippedOut, void* stream )
@@ -442,17 +415,7 @@ MVRT_EXPORT int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const 
 static_assert( MVRT_TRANSFER_COLOUR == 1u && MVRT_TRANSFER_EMISSION == 2u, "mvrt.h and nearestTransferAttrib number the words alike" );
 static int querySources( const mvrt_svo* a, const mvrt_svo* b, const char* who, const int32_t offset[3], SurfaceSource* sa, SurfaceSource* sb, int32_t o[3] )
 {
-	if( surfaceSource( a, who, sa ) ) return 1;
-	REQUIRE( b, "%s: null second handle", who );
-	REQUIRE( !b->empty(), "%s: the second handle holds no octree (build first)", who );
-	REQUIRE( b->oct.morton.p, "%s: the second handle is an uploaded octree, which keeps no Morton codes", who );
-	if( surfaceSource( b, who, sb ) ) return 1;
-	for( int k = 0; k < 3; k++ )
-	{
-		o[k] = offset ? offset[k] : 0;
-		REQUIRE( o[k] >= -( 1 << 21 ) && o[k] <= ( 1 << 21 ), "%s: offset[%d] = %d is outside [-2^21, 2^21]", who, k, o[k] );
-	}
-	return 0;
+	return surfaceSource( a, who, sa ) || secondSource( b, who, "second handle", "the second handle", sb ) || cellOffset( who, offset, o );
 }
 MVRT_EXPORT int mvrt_svo_nearest_voxels( const mvrt_svo* svo, uint64_t n, const int32_t* queryDev, uint64_t maxDist2, uint64_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev,
 										 void* stream )
@@ -498,16 +461,7 @@ MVRT_EXPORT int mvrt_svo_transfer_attributes( mvrt_svo* dst, const mvrt_svo* src
 	if( nearestTransferList( sd, ss, o, maxDist2, flags, xyz, attribs, &nTaken, &nChanged, &nBeyond, st ) ) return 1; // (near is taken in src as it is now)
 	if( nBeyondOut ) *nBeyondOut = nBeyond;
 	if( nChanged == 0 ) return 0; // no byte changes: the handle is not touched
-	if( ownerDrain( dst ) ) return 1; // steps already issued render the old scene; the edit writes in place
-	SvoBuildResult r;
-	int structural = 0;
-	uint32_t he = 0;
-	if( svoEditVoxels( dst->oct.morton.as<uint64_t>(), dst->oct.attrs.as<uint2>(), dst->oct.nVoxels, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nTaken,
-					   (int)dst->oct.info.gridRes, dst->oct.buildFlags, st, &r, &structural, &he ) )
-		return 1;
-	REQUIRE( !structural, "%s: internal error: the voxels of the handle are not its voxels", who ); // (every entry is a voxel of dst)
-	dst->oct.totalDumped = 0;
-	dst->oct.hasEmission = he;
+	if( editHandle( dst, who, EDIT_ATTRIBUTES, xyz.as<uint32_t>(), attribs.as<uint32_t>(), nullptr, nTaken, nullptr, nullptr, st ) ) return 1; // (every entry is a voxel of dst)
 	if( nChangedOut ) *nChangedOut = nChanged;
 	return 0;
 }
@@ -547,8 +501,7 @@ MVRT_EXPORT int mvrt_svo_resample( const mvrt_svo* src, mvrt_svo* dst, const mvr
 	const char* who = "mvrt_svo_resample";
 	if( nOut ) *nOut = 0;
 	REQUIRE( src && dst, "%s: null handle", who );
-	REQUIRE( ( buildFlags & ~( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK ) ) == 0, "%s: unsupported flags 0x%x (MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK only)", who,
-			 buildFlags );
+	REQUIRE_BUILD_FLAGS( who, buildFlags );
 	SurfaceSource s;
 	if( resampleSource( src, who, xf, dstGridRes, &s ) ) return 1;
 	REQUIRE( dstOriginHost, "%s: null origin", who );
@@ -559,12 +512,7 @@ MVRT_EXPORT int mvrt_svo_resample( const mvrt_svo* src, mvrt_svo* dst, const mvr
 	SortedVoxels v;
 	if( resampleList( who, s, xf->m, xf->t, (uint32_t)levelsOf( dstGridRes ), v, st ) ) return 1;
 	REQUIRE( v.n >= 1, "%s: the transform would leave no voxel (no destination cell centre maps into one of the %u voxels)", who, nSrc );
-	SvoBuildResult r;
-	if( svoBuildFromSorted( v.codes, v.attrs, v.n, dstGridRes, buildFlags, st, &r ) ) return 1;
-	r.hasEmission = v.hasEmission;
-	r.totalDumped = nSrc;
-	if( nOut ) *nOut = v.n;
-	return adoptBuild( dst, r, origin, dstDps, dstGridRes, buildFlags ); // (the source is read before the old octree of dst goes)
+	return adoptSortedOnGrid( dst, v, nSrc, origin, dstDps, dstGridRes, buildFlags, nOut, st ); // (the source is read before the old octree of dst goes)
 }
 // host only, no GPU call: the transform of two lattices in world space
 MVRT_EXPORT int mvrt_cell_transform_from_world( const double world[12], const float srcLower[3], float srcDps, const float dstLower[3], float dstDps, mvrt_cell_transform* out )

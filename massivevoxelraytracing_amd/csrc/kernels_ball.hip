@@ -32,17 +32,7 @@ struct BandLength // scan input: the records of entry i in the pass along `axis`
 		return i < n ? (uint64_t)ballShiftRange( ballAxisCoord( codes[i], axis ), levels, ballKeyDist2( keys[i] ), rho, &first ) : 0ull;
 	}
 };
-struct BandHead // scan input: 1 where sorted record i starts a new cell
-{
-	const uint64_t* codes;
-	__host__ __device__ uint32_t operator()( uint32_t i ) const { return i == 0u || codes[i] != codes[i - 1u] ? 1u : 0u; }
-};
-struct NonZero // scan input: 1 where flag[i] is set (item n: 0)
-{
-	const uint32_t* flag;
-	uint32_t n;
-	__host__ __device__ uint32_t operator()( uint32_t i ) const { return i < n && flag[i] != 0u ? 1u : 0u; }
-};
+// (the head of a run of sorted records: KeyHead, voxel_passes.h; the scans of the flags: maskOffsets with removed = 1, kernels_list.hip)
 
 // offs: the n + 1 exclusive sums of BandLength.  gridDim.x = ceil( n / BB ).  recKeys != null: the record's key goes there and the sort carries its index;
 // null: the sort carries d2
@@ -171,15 +161,12 @@ int distanceBand( const char* who, DevBuf& seedCodes, DevBuf& seedKeys, uint32_t
 	b->n = nSeeds;
 	g_ballStats = BallStats();
 	g_ballStats.seeds = nSeeds;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
 	for( uint32_t axis = 0; axis < 3; axis++ )
 	{
 		DevBuf offs, recCodes, recKeys, recVals, sortedCodes, sortedVals, rank1, outCodes, outKeys;
 		const uint32_t n = b->n;
-		hipcub::TransformInputIterator<uint64_t, BandLength, hipcub::CountingInputIterator<uint32_t>> lengths(
-			counting, BandLength{ b->codes.as<uint64_t>(), b->keys.as<uint64_t>(), n, levels, axis, rho } );
 		uint64_t total = 0;
-		if( exclusiveOffsets<uint64_t>( lengths, (uint64_t)n + 1, offs, &total, st ) ) return 1;
+		if( exclusiveOffsetsOf<uint64_t>( BandLength{ b->codes.as<uint64_t>(), b->keys.as<uint64_t>(), n, levels, axis, rho }, (uint64_t)n + 1, offs, &total, st ) ) return 1;
 		g_ballStats.records[axis] = total;
 		if( total >= 0xFFFFFFFFull )
 		{
@@ -192,9 +179,8 @@ int distanceBand( const char* who, DevBuf& seedCodes, DevBuf& seedKeys, uint32_t
 		MVRT_HIP( hipGetLastError() );
 		if( sortPairsInto( recCodes, recVals, total, (int)( 3u * levels ), sortedCodes, sortedVals, st ) ) return 1;
 		offs.release();
-		hipcub::TransformInputIterator<uint32_t, BandHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, BandHead{ sortedCodes.as<uint64_t>() } );
 		uint32_t nCells = 0;
-		if( rankHeads( heads, total, rank1, &nCells, st ) ) return 1;
+		if( rankHeadsOf( KeyHead{ sortedCodes.as<uint64_t>() }, total, rank1, &nCells, st ) ) return 1;
 		if( outCodes.alloc( (uint64_t)nCells * 8 ) || outKeys.alloc( (uint64_t)nCells * 8 ) ) return 1;
 		hipLaunchKernelGGL( kBandHeads, dim3( divUp( total, BB ) ), dim3( BB ), 0, st, sortedCodes.as<uint64_t>(), sortedVals.as<uint32_t>(), recKeys.as<uint64_t>(), rank1.as<uint32_t>(),
 							(uint32_t)total, outCodes.as<uint64_t>(), outKeys.as<uint64_t>() );
@@ -222,10 +208,8 @@ int dilationBand( const char* who, const uint64_t* codes, uint32_t n, uint32_t l
 	if( seedFlag.alloc( (uint64_t)n * 4 ) ) return 1;
 	hipLaunchKernelGGL( kBallSeedFlags, dim3( divUp( n, BB ) ), dim3( BB ), 0, st, codes, n, levels, seedFlag.as<uint32_t>() );
 	MVRT_HIP( hipGetLastError() );
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, NonZero, hipcub::CountingInputIterator<uint32_t>> isSeed( counting, NonZero{ seedFlag.as<uint32_t>(), n } );
 	uint32_t nSeeds = 0;
-	if( exclusiveOffsets<uint32_t>( isSeed, (uint64_t)n + 1, seedOffs, &nSeeds, st ) ) return 1;
+	if( maskOffsets( seedFlag.as<uint32_t>(), n, 1u, seedOffs, &nSeeds, st ) ) return 1;
 	if( nSeeds == 0 ) return 0; // a full grid
 	if( seedCodes.alloc( (uint64_t)nSeeds * 8 ) || seedKeys.alloc( (uint64_t)nSeeds * 8 ) ) return 1;
 	hipLaunchKernelGGL( kBallSeeds, dim3( divUp( n, BB ) ), dim3( BB ), 0, st, codes, seedFlag.as<uint32_t>(), seedOffs.as<uint32_t>(), n, seedCodes.as<uint64_t>(),
@@ -239,8 +223,7 @@ int dilationBand( const char* who, const uint64_t* codes, uint32_t n, uint32_t l
 	if( c->flag.alloc( (uint64_t)nBand * 4 ) ) return 1;
 	hipLaunchKernelGGL( kBallOutside, dim3( divUp( nBand, BB ) ), dim3( BB ), 0, st, c->band.codes.as<uint64_t>(), nBand, codes, n, c->flag.as<uint32_t>() );
 	MVRT_HIP( hipGetLastError() );
-	hipcub::TransformInputIterator<uint32_t, NonZero, hipcub::CountingInputIterator<uint32_t>> outside( counting, NonZero{ c->flag.as<uint32_t>(), nBand } );
-	return exclusiveOffsets<uint32_t>( outside, (uint64_t)nBand + 1, c->offs, &c->nNew, st );
+	return maskOffsets( c->flag.as<uint32_t>(), nBand, 1u, c->offs, &c->nNew, st );
 }
 int launchNewCells( const NewCells& c, const uint2* attrs, uint64_t* codes, uint32_t* xyz, uint32_t* dist2, uint32_t* nearest, uint32_t* attribs, hipStream_t st )
 {
@@ -266,9 +249,7 @@ int depthBand( const char* who, const uint64_t* codes, const uint2* attrs, uint3
 	if( depth.alloc( (uint64_t)n * 4 ) ) return 1;
 	hipLaunchKernelGGL( kBallDepth, dim3( divUp( n, BB ) ), dim3( BB ), 0, st, codes, n, band.codes.as<uint64_t>(), band.keys.as<uint64_t>(), band.n, depth.as<uint32_t>() );
 	MVRT_HIP( hipGetLastError() );
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, NonZero, hipcub::CountingInputIterator<uint32_t>> shallow( counting, NonZero{ depth.as<uint32_t>(), n } );
-	return exclusiveOffsets<uint32_t>( shallow, (uint64_t)n + 1, offs, nShallow, st ); // (has waited: the band is released on return)
+	return maskOffsets( depth.as<uint32_t>(), n, 1u, offs, nShallow, st ); // (has waited: the band is released on return)
 }
 
 int dilateHalf( const char* who, VoxelList& l, uint32_t levels, uint32_t rho, hipStream_t st )

@@ -231,9 +231,7 @@ int reduceCells( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_
 {
 	const uint32_t shift = 3u * levelsDown;
 	DevBuf rank1;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, CoarseHeadFlag, hipcub::CountingInputIterator<uint32_t>> heads( counting, CoarseHeadFlag{ morton, shift } );
-	if( rankHeads( heads, n, rank1, &out->nSeg, st ) ) return 1;
+	if( rankHeadsOf( CoarseHeadFlag{ morton, shift }, n, rank1, &out->nSeg, st ) ) return 1;
 	const uint32_t nSeg = out->nSeg;
 	out->nKept = nSeg;
 	if( minCount == 1 && countOnly ) return 0;
@@ -249,8 +247,7 @@ int reduceCells( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_
 		MVRT_HIP( hipStreamSynchronize( st ) ); // (rank1 is released on return)
 		return 0;
 	}
-	hipcub::TransformInputIterator<uint32_t, CoarseKeptFlag, hipcub::CountingInputIterator<uint32_t>> kept( counting, CoarseKeptFlag{ out->counts.as<uint32_t>(), minCount, nSeg } );
-	return exclusiveOffsets<uint32_t>( kept, (uint64_t)nSeg + 1, out->offs, &out->nKept, st );
+	return exclusiveOffsetsOf<uint32_t>( CoarseKeptFlag{ out->counts.as<uint32_t>(), minCount, nSeg }, (uint64_t)nSeg + 1, out->offs, &out->nKept, st );
 }
 int launchEmit( const Reduced& r, uint64_t minCount, uint64_t* codes, uint32_t* attribs, uint32_t* count, uint32_t* xyz, uint32_t* hasEmission, hipStream_t st )
 {

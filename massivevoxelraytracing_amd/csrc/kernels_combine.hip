@@ -151,9 +151,7 @@ int classify( const uint64_t* mine, uint32_t nMine, const uint64_t* other, uint3
 							out->partner.as<uint32_t>(), out->state.as<uint8_t>() );
 		MVRT_HIP( hipGetLastError() );
 	}
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, Lives, hipcub::CountingInputIterator<uint32_t>> lives( counting, Lives{ out->state.as<uint8_t>(), nMine } );
-	return exclusiveOffsets<uint32_t>( lives, (uint64_t)nMine + 1, out->offs, &out->nLives, st );
+	return exclusiveOffsetsOf<uint32_t>( Lives{ out->state.as<uint8_t>(), nMine }, (uint64_t)nMine + 1, out->offs, &out->nLives, st );
 }
 
 // both operands classified under an operator: what the listing and the in-place call emit from
@@ -184,10 +182,8 @@ int translate( const SurfaceSource& a, const SurfaceSource& b, const int32_t o[3
 	const dim3 grid( divUp( b.nVoxels, KB ) ), block( KB );
 	hipLaunchKernelGGL( kCombineTranslate, grid, block, 0, st, b.morton, b.nVoxels, off, a.levels, keys.as<uint64_t>() );
 	MVRT_HIP( hipGetLastError() );
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, InGrid, hipcub::CountingInputIterator<uint32_t>> inGrid( counting, InGrid{ keys.as<uint64_t>(), b.nVoxels } );
 	uint32_t nIn = 0;
-	if( exclusiveOffsets<uint32_t>( inGrid, (uint64_t)b.nVoxels + 1, offs, &nIn, st ) ) return 1;
+	if( exclusiveOffsetsOf<uint32_t>( InGrid{ keys.as<uint64_t>(), b.nVoxels }, (uint64_t)b.nVoxels + 1, offs, &nIn, st ) ) return 1;
 	p->nClipped = b.nVoxels - nIn;
 	p->b.n = nIn;
 	p->b.codes = nullptr;

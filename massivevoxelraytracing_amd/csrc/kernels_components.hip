@@ -177,9 +177,7 @@ int labelComponents( const SurfaceSource& s, int element, Labelled* out, hipStre
 	hipLaunchKernelGGL( kCompUnite, grid, block, 0, st, s.morton, n, s.levels, element, parent );
 	hipLaunchKernelGGL( kCompFlatten, grid, block, 0, st, parent, n );
 	MVRT_HIP( hipGetLastError() );
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, RootFlag, hipcub::CountingInputIterator<uint32_t>> heads( counting, RootFlag{ parent } );
-	return rankHeads( heads, n, out->rank1, &out->nComponents, st );
+	return rankHeadsOf( RootFlag{ parent }, n, out->rank1, &out->nComponents, st );
 }
 // size (allocated here, and box where wanted) of every component.  Not synchronised
 int reduceComponents( const SurfaceSource& s, const Labelled& l, DevBuf& size, DevBuf* box, hipStream_t st )

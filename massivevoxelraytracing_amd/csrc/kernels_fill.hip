@@ -132,8 +132,7 @@ __global__ void __launch_bounds__( FB ) kFillExteriorMasks( const uint64_t* __re
 		cleared = __popc( m ^ out );
 		if( cleared ) masks[i] = (uint8_t)out;
 	}
-	for( int o = WAVE / 2; o > 0; o >>= 1 ) cleared += __shfl_down( cleared, o, WAVE );
-	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && cleared ) atomicAdd( nHidden, (unsigned long long)cleared );
+	waveAddInto( nHidden, cleared );
 }
 
 struct EnclosedLength // scan input: the cells of gap i where its root is not EXTERIOR (item n - 1 and beyond: 0)
@@ -244,10 +243,8 @@ int classifyGaps( const SurfaceSource& s, Classified* out, hipStream_t st )
 int classify( const SurfaceSource& s, Classified* out, hipStream_t st )
 {
 	if( classifyGaps( s, out, st ) ) return 1;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint64_t, EnclosedLength, hipcub::CountingInputIterator<uint32_t>> lengths(
-		counting, EnclosedLength{ out->lin.as<uint64_t>(), out->root.as<uint32_t>(), s.nVoxels, s.levels } );
-	return exclusiveOffsets<uint64_t>( lengths, (uint64_t)s.nVoxels + 1, out->offs, &out->nCells, st );
+	return exclusiveOffsetsOf<uint64_t>( EnclosedLength{ out->lin.as<uint64_t>(), out->root.as<uint32_t>(), s.nVoxels, s.levels }, (uint64_t)s.nVoxels + 1, out->offs, &out->nCells,
+										 st );
 }
 int launchEmit( const SurfaceSource& s, const Classified& c, uint64_t* codes, uint32_t* roots, uint32_t* xyz, hipStream_t st )
 {
@@ -267,9 +264,7 @@ int enclosedRegionRanks( const uint32_t* roots, uint32_t nCells, uint32_t nVoxel
 	MVRT_HIP( hipMemsetAsync( firstCell.p, 0xFF, nNodes * 4, st ) );
 	hipLaunchKernelGGL( kFillFirstCells, dim3( divUp( nCells, FB ) ), dim3( FB ), 0, st, roots, nCells, firstCell.as<uint32_t>() );
 	MVRT_HIP( hipGetLastError() );
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, RegionHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, RegionHead{ roots, firstCell.as<uint32_t>() } );
-	return rankHeads( heads, nCells, rank1, nullptr, st );
+	return rankHeadsOf( RegionHead{ roots, firstCell.as<uint32_t>() }, nCells, rank1, nullptr, st );
 }
 
 int enclosedCells( const SurfaceSource& s, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, hipStream_t st )
@@ -320,8 +315,9 @@ int surfaceExteriorMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* n
 	Classified c;
 	if( classifyGaps( s, &c, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (nRegions)
-	DevBuf cnt, own;
-	if( cnt.alloc( 16 ) ) return 1;
+	Counters cnt; // [0] plain faces [1] hidden faces
+	DevBuf own;
+	if( cnt.init( 2, st ) ) return 1;
 	uint8_t* masks = masksDev;
 	if( !masks && c.nRegions ) // counts only: the second kernel still reads the plain masks
 	{
@@ -329,18 +325,15 @@ int surfaceExteriorMasks( const SurfaceSource& s, uint8_t* masksDev, uint64_t* n
 		masks = own.as<uint8_t>();
 	}
 	// (the caller's array is written from here on, behind every allocation)
-	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 16, st ) );
-	unsigned long long* counts = cnt.as<unsigned long long>(); // [0] plain faces [1] hidden faces
-	if( launchSurfaceMasks( s, masks, counts, st ) ) return 1;
+	if( launchSurfaceMasks( s, masks, cnt.dev(), st ) ) return 1;
 	if( c.nRegions ) // without an enclosed region the exterior masks are the plain masks
 	{
 		hipLaunchKernelGGL( kFillExteriorMasks, dim3( divUp( s.nVoxels, FB ) ), dim3( FB ), 0, st, s.morton, c.lin.as<uint64_t>(), c.root.as<uint32_t>(), s.nVoxels, s.levels, masks,
-							counts + 1 );
+							cnt.dev() + 1 );
 		MVRT_HIP( hipGetLastError() );
 	}
 	unsigned long long h[2] = { 0, 0 };
-	MVRT_HIP( hipMemcpyAsync( h, cnt.p, 16, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
+	if( cnt.read( h, 2, st ) ) return 1; // (waits: the scratch is released on return)
 	if( nFacesOut ) *nFacesOut = h[0] - h[1];
 	if( nHiddenOut ) *nHiddenOut = h[1];
 	return 0;

@@ -102,9 +102,7 @@ int anyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStrea
 
 int maskOffsets( const uint32_t* mask, uint32_t n, uint32_t removed, DevBuf& offs, uint32_t* count, hipStream_t st )
 {
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, MaskFlag, hipcub::CountingInputIterator<uint32_t>> flagged( counting, MaskFlag{ mask, n, removed } );
-	return exclusiveOffsets<uint32_t>( flagged, (uint64_t)n + 1, offs, count, st );
+	return exclusiveOffsetsOf<uint32_t>( MaskFlag{ mask, n, removed }, (uint64_t)n + 1, offs, count, st );
 }
 int launchCompactMasked( const uint64_t* codes, const uint2* attrs, const uint32_t* mask, const uint32_t* offs, uint32_t n, uint32_t removed, uint64_t* codesOut, uint2* attrsOut,
 						 uint32_t* vIndexOut, hipStream_t st )

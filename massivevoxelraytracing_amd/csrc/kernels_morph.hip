@@ -28,11 +28,7 @@ struct MaskLength // scan input: the records of voxel i (item n: 0)
 	uint32_t n;
 	__host__ __device__ uint64_t operator()( uint32_t i ) const { return i < n ? (uint64_t)__builtin_popcount( mask[i] ) : 0ull; }
 };
-struct RecordHead // scan input: 1 where sorted record i starts a new cell
-{
-	const uint64_t* keys;
-	__host__ __device__ uint32_t operator()( uint32_t i ) const { return i == 0u || keys[i] != keys[i - 1u] ? 1u : 0u; }
-};
+// (the head of a run of sorted records, 1 where record i starts a new cell: KeyHead, voxel_passes.h)
 
 // offs: the n + 1 exclusive sums of the popcounts.  gridDim.x = ceil( n / MB ); a workgroup without records writes nothing
 __global__ void __launch_bounds__( MB ) kMorphEmit( const uint64_t* __restrict__ codes, const uint32_t* __restrict__ mask, const uint64_t* __restrict__ offs, uint32_t n,
@@ -112,10 +108,8 @@ int dilationRecords( const char* who, const uint64_t* codes, uint32_t n, uint32_
 {
 	DevBuf mask, offs, keysA, srcA;
 	if( launchMasks( codes, n, levels, element, mask, st ) ) return 1;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint64_t, MaskLength, hipcub::CountingInputIterator<uint32_t>> lengths( counting, MaskLength{ mask.as<uint32_t>(), n } );
 	uint64_t total = 0;
-	if( exclusiveOffsets<uint64_t>( lengths, (uint64_t)n + 1, offs, &total, st ) ) return 1;
+	if( exclusiveOffsetsOf<uint64_t>( MaskLength{ mask.as<uint32_t>(), n }, (uint64_t)n + 1, offs, &total, st ) ) return 1;
 	if( total == 0 ) return 0; // a full grid
 	if( total >= 0xFFFFFFFFull )
 	{
@@ -129,9 +123,8 @@ int dilationRecords( const char* who, const uint64_t* codes, uint32_t n, uint32_
 	if( sortPairsInto( keysA, srcA, total, (int)( 3u * levels ), r->keys, r->src, st ) ) return 1;
 	mask.release();
 	offs.release();
-	hipcub::TransformInputIterator<uint32_t, RecordHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, RecordHead{ r->keys.as<uint64_t>() } );
 	r->nRecords = (uint32_t)total;
-	return rankHeads( heads, total, r->rank1, &r->nCells, st );
+	return rankHeadsOf( KeyHead{ r->keys.as<uint64_t>() }, total, r->rank1, &r->nCells, st );
 }
 int launchCells( const Records& r, const uint2* attrs, uint64_t* codes, uint32_t* attribs, uint32_t* count, uint32_t* xyz, hipStream_t st )
 {

@@ -34,16 +34,7 @@ enum // the slots of the device counters
 	NS_SLOTS = 6
 };
 
-// all lanes of the wave call this
-MVRT_DI void waveMaxInto( unsigned long long* dst, uint32_t v )
-{
-	for( int o = WAVE / 2; o > 0; o >>= 1 )
-	{
-		const uint32_t w = __shfl_down( v, o, WAVE );
-		v = w > v ? w : v;
-	}
-	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && v ) atomicMax( dst, (unsigned long long)v );
-}
+// (waveMaxInto, the maximum of a wave into a counter: voxel_passes.h)
 
 // the vIndex of the voxel (x, y, z); a voxel that is not there is counted and gives 0
 MVRT_DI uint32_t voxelIndex( const uint64_t* __restrict__ morton, uint32_t n, uint32_t x, uint32_t y, uint32_t z, unsigned long long* stats )
@@ -208,7 +199,8 @@ __global__ void __launch_bounds__( NB ) kNearestCells( const uint64_t* __restric
 // what the three passes leave: the keys of pass z in its order, and for the listing the pair of the Morton sort, the places in the order of pass x and the roots there
 struct Passes
 {
-	DevBuf stats, keysZ, val, comp, rootsX, codesA, placeA;
+	Counters stats;
+	DevBuf keysZ, val, comp, rootsX, codesA, placeA;
 };
 // c: the classification, with 0 < nCells < 2^32; its arrays are released on the way
 int runPasses( const SurfaceSource& s, EnclosedClassified& c, bool listing, Passes& p, hipStream_t st )
@@ -216,9 +208,8 @@ int runPasses( const SurfaceSource& s, EnclosedClassified& c, bool listing, Pass
 	const uint32_t n = s.nVoxels, L = s.levels, nCells = (uint32_t)c.nCells;
 	const int endBit = (int)( 3u * L );
 	const dim3 cellGrid( divUp( nCells, NB ) ), block( NB );
-	if( p.stats.alloc( NS_SLOTS * 8 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( p.stats.p, 0, NS_SLOTS * 8, st ) );
-	unsigned long long* stats = p.stats.as<unsigned long long>();
+	if( p.stats.init( NS_SLOTS, st ) ) return 1;
+	unsigned long long* stats = p.stats.dev();
 	DevBuf cur, keyA, placeA, keyS, place;
 	if( cur.alloc( c.nCells * 8 ) || keyA.alloc( c.nCells * 8 ) || placeA.alloc( c.nCells * 4 ) || ( listing && p.rootsX.alloc( c.nCells * 4 ) ) ) return 1;
 	hipLaunchKernelGGL( kNearestEmitX, dim3( divUp( n, NB ) ), block, 0, st, c.lin.as<uint64_t>(), c.root.as<uint32_t>(), c.offs.as<uint64_t>(), s.morton, n, L, cur.as<uint64_t>(),
@@ -235,10 +226,8 @@ int runPasses( const SurfaceSource& s, EnclosedClassified& c, bool listing, Pass
 		if( in.alloc( c.nCells * 8 ) || ( compose && comp.alloc( c.nCells * 4 ) ) ) return 1;
 		hipLaunchKernelGGL( kNearestGather, cellGrid, block, 0, st, cur.as<uint64_t>(), place.as<uint32_t>(), p.comp.as<uint32_t>(), nCells, in.as<uint64_t>(), comp.as<uint32_t>() );
 		MVRT_HIP( hipGetLastError() );
-		hipcub::CountingInputIterator<uint32_t> counting( 0u );
-		hipcub::TransformInputIterator<uint32_t, GapHead, hipcub::CountingInputIterator<uint32_t>> heads( counting, GapHead{ keyS.as<uint64_t>() } );
 		uint32_t nGaps = 0;
-		if( rankHeads( heads, c.nCells, rank1, &nGaps, st ) ) return 1; // (waits: the gather is done)
+		if( rankHeadsOf( GapHead{ keyS.as<uint64_t>() }, c.nCells, rank1, &nGaps, st ) ) return 1; // (waits: the gather is done)
 		cur.release();
 		if( listing && axis == 1u ) p.comp = std::move( place ); // the order of pass y against the order of pass x
 		else place.release();
@@ -265,8 +254,7 @@ int runPasses( const SurfaceSource& s, EnclosedClassified& c, bool listing, Pass
 int finishStats( const char* who, Passes& p, hipStream_t st )
 {
 	unsigned long long h[NS_SLOTS];
-	MVRT_HIP( hipMemcpyAsync( h, p.stats.p, sizeof( h ), hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( p.stats.read( h, NS_SLOTS, st ) ) return 1;
 	g_nearestStats.gaps[0] = h[NS_GAPS_X];
 	for( int a = 0; a < 3; a++ ) g_nearestStats.longest[a] = h[NS_LONGEST + a];
 	g_nearestStats.deepest = h[NS_DEEPEST];

@@ -13,7 +13,6 @@
 #include "launch.h"
 #include "voxel_passes.h"
 
-#define WAVE 64
 #define QB 64 // threads per workgroup of the walk: one wave, so that the LDS a group asks for is ( levels - 1 ) * 512 bytes
 #define NB 256
 
@@ -46,30 +45,8 @@ struct LaneStack
 	}
 };
 
-// all lanes of the wave call these
-MVRT_DI unsigned long long waveSum( unsigned long long v )
-{
-	for( int o = WAVE / 2; o > 0; o >>= 1 ) v += __shfl_down( v, o, WAVE );
-	return v;
-}
-MVRT_DI unsigned long long waveMax( unsigned long long v )
-{
-	for( int o = WAVE / 2; o > 0; o >>= 1 )
-	{
-		const unsigned long long w = __shfl_down( v, o, WAVE );
-		v = w > v ? w : v;
-	}
-	return v;
-}
-MVRT_DI unsigned long long waveMin( unsigned long long v )
-{
-	for( int o = WAVE / 2; o > 0; o >>= 1 )
-	{
-		const unsigned long long w = __shfl_down( v, o, WAVE );
-		v = w < v ? w : v;
-	}
-	return v;
-}
+// (waveSum, waveMax, waveMin and the Into forms, on unsigned long long here: voxel_passes.h)
+typedef unsigned long long Count;
 
 struct QueryOffset
 {
@@ -99,8 +76,8 @@ __global__ void __launch_bounds__( QB ) kNearestQuery( const uint64_t* __restric
 		if( nearest ) nearest[i] = r.near;
 		if( attribs ) attribs[i] = found ? nearestAttrib( attrs[r.near] ) : make_uint2( 0u, 0u );
 	}
-	const uint64_t visits = waveSum( r.visits ), most = waveMax( r.visits ), compared = waveSum( r.compared );
-	const bool lane0 = ( threadIdx.x & ( WAVE - 1 ) ) == 0;
+	const uint64_t visits = waveSum<Count>( r.visits ), most = waveMax<Count>( r.visits ), compared = waveSum<Count>( r.compared );
+	const bool lane0 = waveLane0();
 	if( lane0 )
 	{
 		atomicAdd( stats + QS_VISITS, (unsigned long long)visits );
@@ -109,7 +86,8 @@ __global__ void __launch_bounds__( QB ) kNearestQuery( const uint64_t* __restric
 	}
 	if( !summary ) return;
 	const bool within = live && r.d2 != NEAREST_QUERY_NONE_D2;
-	const uint64_t zero = waveSum( within && r.d2 == 0ull ? 1ull : 0ull ), beyond = waveSum( live && !within ? 1ull : 0ull ), far = waveMax( within ? r.d2 : 0ull );
+	// (three reductions, then the atomics: with waveAddInto the atomics stand between the reductions and the kernel's instructions change)
+	const uint64_t zero = waveSum<Count>( within && r.d2 == 0ull ? 1ull : 0ull ), beyond = waveSum<Count>( live && !within ? 1ull : 0ull ), far = waveMax<Count>( within ? r.d2 : 0ull );
 	if( lane0 )
 	{
 		if( zero ) atomicAdd( stats + QS_ZERO, (unsigned long long)zero );
@@ -123,8 +101,8 @@ __global__ void __launch_bounds__( NB ) kQueryFarthest( const uint64_t* __restri
 {
 	const uint64_t i = (uint64_t)blockIdx.x * NB + threadIdx.x;
 	const uint64_t want = stats[QS_MAXD2];
-	const uint64_t mine = waveMin( i < n && dist2[i] == want ? i : ~0ull );
-	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && mine != ~0ull ) atomicMin( stats + QS_FARTHEST, (unsigned long long)mine );
+	const uint64_t mine = waveMin<Count>( i < n && dist2[i] == want ? i : ~0ull );
+	if( waveLane0() && mine != ~0ull ) atomicMin( stats + QS_FARTHEST, (unsigned long long)mine );
 }
 
 // transfer: fresh[i] = the 8 bytes voxel i ends with, take[i] = 1 where it has a nearest voxel within the limit (it goes to the edit); the changed are counted
@@ -142,8 +120,7 @@ __global__ void __launch_bounds__( NB ) kTransferCompose( const uint2* __restric
 		take[i] = within ? 1u : 0u;
 		changed = a.x != b.x || a.y != b.y ? 1ull : 0ull;
 	}
-	changed = waveSum( changed );
-	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && changed ) atomicAdd( stats + QS_CHANGED, (unsigned long long)changed );
+	waveAddInto<Count>( stats + QS_CHANGED, changed );
 }
 // the taken voxels in order: their cells and their bytes, the list of the edit.  offs = the n + 1 exclusive sums of take
 __global__ void __launch_bounds__( NB ) kTransferList( const uint64_t* __restrict__ codes, const uint2* __restrict__ fresh, const uint32_t* __restrict__ take,
@@ -156,7 +133,9 @@ __global__ void __launch_bounds__( NB ) kTransferList( const uint64_t* __restric
 	attribs[j] = fresh[i];
 }
 
-struct TakeFlag // scan input
+// scan input.  (Not maskOffsets( take, n, 1u, ... ) of kernels_list.hip, which gives the same sums: without a scan instantiated in this file the compiler inlines
+// __shfl_down into the three kernels above in another form, and their instructions are pinned by profiles/voxel_ops_refactor2_ab.txt)
+struct TakeFlag
 {
 	const uint32_t* take;
 	uint32_t n;
@@ -165,14 +144,7 @@ struct TakeFlag // scan input
 
 int seedKnob() { return mvrtKnob( "MVRT_NEAREST_QUERY_SEED", 1 ) ? 1 : 0; } // (an experiment build can walk without the seed: tools/nearest_query_bench.py)
 
-// the counters of one call, zeroed; QS_FARTHEST starts at ~0
-int initStats( DevBuf& stats, hipStream_t st )
-{
-	if( stats.alloc( QS_SLOTS * 8 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( stats.p, 0, QS_SLOTS * 8, st ) );
-	MVRT_HIP( hipMemsetAsync( stats.as<unsigned long long>() + QS_FARTHEST, 0xFF, 8, st ) );
-	return 0;
-}
+// (the counters of one call: Counters, voxel_passes.h, zeroed with QS_FARTHEST preset to ~0)
 int launchWalk( const SurfaceSource& s, const int32_t* query, const uint64_t* from, const int32_t o[3], uint32_t n, uint64_t maxDist2, int summary, uint64_t* dist2, uint32_t* nearest,
 				uint2* attribs, unsigned long long* stats, hipStream_t st )
 {
@@ -184,10 +156,9 @@ int launchWalk( const SurfaceSource& s, const int32_t* query, const uint64_t* fr
 	return 0;
 }
 // behind the last launch; waits for the stream
-int readStats( DevBuf& stats, uint32_t n, unsigned long long h[QS_SLOTS], hipStream_t st )
+int readStats( const Counters& stats, uint32_t n, unsigned long long h[QS_SLOTS], hipStream_t st )
 {
-	MVRT_HIP( hipMemcpyAsync( h, stats.p, QS_SLOTS * 8, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( stats.read( h, QS_SLOTS, st ) ) return 1;
 	g_queryStats.queries = n;
 	g_queryStats.visits = h[QS_VISITS];
 	g_queryStats.mostVisits = h[QS_MOST];
@@ -202,10 +173,10 @@ int nearestVoxels( const SurfaceSource& s, uint64_t n, const int32_t* queryDev, 
 {
 	g_queryStats = NearestQueryStats();
 	if( n == 0 ) return 0; // no launch
-	DevBuf stats;
-	if( initStats( stats, st ) ) return 1;
+	Counters stats;
+	if( stats.init( QS_SLOTS, st, QS_FARTHEST ) ) return 1;
 	// (the caller's arrays are written by this launch alone, behind the only allocation)
-	if( launchWalk( s, queryDev, nullptr, nullptr, (uint32_t)n, maxDist2, 0, dist2Dev, nearestDev, (uint2*)attribsDev, stats.as<unsigned long long>(), st ) ) return 1;
+	if( launchWalk( s, queryDev, nullptr, nullptr, (uint32_t)n, maxDist2, 0, dist2Dev, nearestDev, (uint2*)attribsDev, stats.dev(), st ) ) return 1;
 	unsigned long long h[QS_SLOTS];
 	return readStats( stats, (uint32_t)n, h, st );
 }
@@ -223,11 +194,12 @@ int nearestBetween( const SurfaceSource& a, const SurfaceSource& b, const int32_
 		listingRefusal( who, "capacity", "voxels of a", capacity, n );
 		return 1;
 	}
-	DevBuf stats, own;
-	if( initStats( stats, st ) || ( !dist2Dev && own.alloc( (uint64_t)n * 8 ) ) ) return 1;
+	Counters stats;
+	DevBuf own;
+	if( stats.init( QS_SLOTS, st, QS_FARTHEST ) || ( !dist2Dev && own.alloc( (uint64_t)n * 8 ) ) ) return 1;
 	uint64_t* d2 = dist2Dev ? dist2Dev : own.as<uint64_t>(); // (the second pass reads the distances: the summary call keeps them in scratch)
-	if( launchWalk( b, nullptr, a.morton, o, n, maxDist2, 1, d2, nearestDev, nullptr, stats.as<unsigned long long>(), st ) ) return 1;
-	hipLaunchKernelGGL( kQueryFarthest, dim3( divUp( n, NB ) ), dim3( NB ), 0, st, d2, n, stats.as<unsigned long long>() );
+	if( launchWalk( b, nullptr, a.morton, o, n, maxDist2, 1, d2, nearestDev, nullptr, stats.dev(), st ) ) return 1;
+	hipLaunchKernelGGL( kQueryFarthest, dim3( divUp( n, NB ) ), dim3( NB ), 0, st, d2, n, stats.dev() );
 	MVRT_HIP( hipGetLastError() );
 	unsigned long long h[QS_SLOTS];
 	if( readStats( stats, n, h, st ) ) return 1;
@@ -244,11 +216,12 @@ int nearestTransferList( const SurfaceSource& dst, const SurfaceSource& src, con
 	g_queryStats = NearestQueryStats();
 	const uint32_t n = dst.nVoxels;
 	const dim3 grid( divUp( n, NB ) ), block( NB );
-	DevBuf stats, near, from, fresh, take, offs;
-	if( initStats( stats, st ) || near.alloc( (uint64_t)n * 4 ) || from.alloc( (uint64_t)n * 8 ) || fresh.alloc( (uint64_t)n * 8 ) || take.alloc( (uint64_t)n * 4 ) ) return 1;
-	if( launchWalk( src, nullptr, dst.morton, o, n, maxDist2, 1, nullptr, near.as<uint32_t>(), from.as<uint2>(), stats.as<unsigned long long>(), st ) ) return 1;
+	Counters stats;
+	DevBuf near, from, fresh, take, offs;
+	if( stats.init( QS_SLOTS, st, QS_FARTHEST ) || near.alloc( (uint64_t)n * 4 ) || from.alloc( (uint64_t)n * 8 ) || fresh.alloc( (uint64_t)n * 8 ) || take.alloc( (uint64_t)n * 4 ) ) return 1;
+	if( launchWalk( src, nullptr, dst.morton, o, n, maxDist2, 1, nullptr, near.as<uint32_t>(), from.as<uint2>(), stats.dev(), st ) ) return 1;
 	hipLaunchKernelGGL( kTransferCompose, grid, block, 0, st, dst.attrs, from.as<uint2>(), near.as<uint32_t>(), n, flags, fresh.as<uint2>(), take.as<uint32_t>(),
-						stats.as<unsigned long long>() );
+						stats.dev() );
 	MVRT_HIP( hipGetLastError() );
 	unsigned long long h[QS_SLOTS];
 	if( readStats( stats, n, h, st ) ) return 1;
@@ -258,9 +231,7 @@ int nearestTransferList( const SurfaceSource& dst, const SurfaceSource& src, con
 	*nBeyond = h[QS_BEYOND];
 	*nTaken = n - h[QS_BEYOND];
 	if( *nChanged == 0 ) return 0; // no byte changes: no list
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, TakeFlag, hipcub::CountingInputIterator<uint32_t>> flagsIn( counting, TakeFlag{ take.as<uint32_t>(), n } );
-	if( exclusiveOffsets<uint32_t>( flagsIn, (uint64_t)n + 1, offs, (uint32_t*)nullptr, st ) ) return 1;
+	if( exclusiveOffsetsOf<uint32_t>( TakeFlag{ take.as<uint32_t>(), n }, (uint64_t)n + 1, offs, nullptr, st ) ) return 1;
 	if( xyz.alloc( *nTaken * 12 ) || attribs.alloc( *nTaken * 8 ) ) return 1;
 	hipLaunchKernelGGL( kTransferList, grid, block, 0, st, dst.morton, fresh.as<uint2>(), take.as<uint32_t>(), offs.as<uint32_t>(), n, xyz.as<uint32_t>(), attribs.as<uint2>() );
 	MVRT_HIP( hipGetLastError() );

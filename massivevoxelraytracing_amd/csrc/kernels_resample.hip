@@ -135,7 +135,7 @@ int refine( const char* who, const SurfaceSource& s, const ResampleXf& xf, uint3
 	if( r->frontier.alloc( 8 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( r->frontier.p, 0, 8, st ) ); // level 0: the grid, code 0
 	r->nNodes = 1;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
+	hipcub::CountingInputIterator<uint32_t> counting( 0u ); // (the one scan that keeps its hand-built iterator pair: profiles/voxel_ops_refactor2_ab.txt, section 5)
 	for( uint32_t l = 1; l <= dstLevels; l++ ) // the level of the children
 	{
 		const uint32_t nNodes = r->nNodes;

@@ -17,7 +17,6 @@
 #include "launch.h"
 #include "voxel_passes.h"
 
-#define WAVE 64
 #define SB 256 // threads per workgroup, and voxels per workgroup of the emit kernel
 
 namespace
@@ -90,8 +89,7 @@ template <bool CELLS> __global__ void __launch_bounds__( SB ) kSurfaceMasks( Sur
 			if( two ) masks[i + 1] = (uint8_t)m1;
 		}
 	}
-	for( int o = WAVE / 2; o > 0; o >>= 1 ) cnt += __shfl_down( cnt, o, WAVE );
-	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && cnt ) atomicAdd( nFaces, (unsigned long long)cnt );
+	waveAddInto( nFaces, cnt );
 }
 
 // the caller's masks of the _masked calls into the scratch: bits 6 and 7 dropped, the set bits counted the same way
@@ -105,8 +103,7 @@ __global__ void __launch_bounds__( SB ) kSurfaceGivenMasks( const uint8_t* __res
 		masks[i] = (uint8_t)m;
 		cnt = __popc( m );
 	}
-	for( int o = WAVE / 2; o > 0; o >>= 1 ) cnt += __shfl_down( cnt, o, WAVE );
-	if( ( threadIdx.x & ( WAVE - 1 ) ) == 0 && cnt ) atomicAdd( nFaces, (unsigned long long)cnt );
+	waveAddInto( nFaces, cnt );
 }
 
 struct PopcountOf // scan input: faces of voxel i
@@ -196,11 +193,7 @@ __global__ void __launch_bounds__( SB ) kSurfaceEmit( const uint64_t* __restrict
 	}
 }
 
-struct HeadOf // scan input: 1 where a sorted corner key differs from the one before it
-{
-	const uint64_t* keys;
-	__host__ __device__ uint32_t operator()( uint32_t i ) const { return ( i == 0u || keys[i] != keys[i - 1u] ) ? 1u : 0u; }
-};
+// (the head of a run of sorted corner keys, 1 where a key differs from the one before it: KeyHead, voxel_passes.h)
 // sorted corners -> indices[face * 4 + k] = rank of the key, vertices[rank] = the key's position (written by the first corner of each run)
 __global__ void __launch_bounds__( SB ) kSurfaceWeld( const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ rank1, uint32_t nCorners,
 													  f3 lower, float dps, uint32_t gridRes, uint32_t* __restrict__ indices, float* __restrict__ vertices )
@@ -237,18 +230,16 @@ int launchEmit( const SurfaceSource& s, const uint8_t* masks, const uint64_t* of
 // the masks kernel into `masks` (null = count only), or a caller's `given` masks copied there, and the sum of the popcounts, on the host when this returns
 int masksAndCount( const SurfaceSource& s, const uint8_t* given, uint8_t* masks, uint64_t* nFaces, hipStream_t st )
 {
-	DevBuf cnt;
-	if( cnt.alloc( 8 ) ) return 1;
-	MVRT_HIP( hipMemsetAsync( cnt.p, 0, 8, st ) );
+	Counters cnt;
+	if( cnt.init( 1, st ) ) return 1;
 	if( given )
 	{
-		hipLaunchKernelGGL( kSurfaceGivenMasks, dim3( divUp( s.nVoxels, SB ) ), dim3( SB ), 0, st, given, s.nVoxels, masks, cnt.as<unsigned long long>() );
+		hipLaunchKernelGGL( kSurfaceGivenMasks, dim3( divUp( s.nVoxels, SB ) ), dim3( SB ), 0, st, given, s.nVoxels, masks, cnt.dev() );
 		MVRT_HIP( hipGetLastError() );
 	}
-	else if( launchSurfaceMasks( s, masks, cnt.as<unsigned long long>(), st ) ) return 1;
+	else if( launchSurfaceMasks( s, masks, cnt.dev(), st ) ) return 1;
 	unsigned long long h = 0;
-	MVRT_HIP( hipMemcpyAsync( &h, cnt.p, 8, hipMemcpyDeviceToHost, st ) );
-	MVRT_HIP( hipStreamSynchronize( st ) );
+	if( cnt.read( &h, 1, st ) ) return 1;
 	*nFaces = h;
 	return 0;
 }
@@ -278,9 +269,7 @@ int buildWeld( const SurfaceSource& s, DevBuf& keysA, DevBuf& valsA, uint32_t nC
 	int endBit = 3 * ( (int)s.levels + 1 ); // a key is below ( gridRes + 1 )^3 <= 2^( 3 * ( levels + 1 ) )
 	if( endBit > 64 ) endBit = 64;
 	if( sortPairsInto( keysA, valsA, nCorners, endBit, w->keys, w->vals, st ) ) return 1;
-	hipcub::CountingInputIterator<uint32_t> counting( 0u );
-	hipcub::TransformInputIterator<uint32_t, HeadOf, hipcub::CountingInputIterator<uint32_t>> heads( counting, HeadOf{ w->keys.as<uint64_t>() } );
-	if( rankHeads( heads, nCorners, w->rank1, &w->nVertices, st ) ) return 1;
+	if( rankHeadsOf( KeyHead{ w->keys.as<uint64_t>() }, nCorners, w->rank1, &w->nVertices, st ) ) return 1;
 	w->nCorners = nCorners;
 	return 0;
 }

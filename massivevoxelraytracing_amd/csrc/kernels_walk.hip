@@ -156,10 +156,7 @@ int walkPaths( const WalkSource& s, bool fill, uint64_t fillLimit, WalkResult* o
 		DevBuf& off = offs[d & 1u];
 		const bool last = d + 1u == s.levels;
 		uint64_t total = 0;
-		hipcub::CountingInputIterator<uint64_t> counting( 0ull );
-		hipcub::TransformInputIterator<uint64_t, ChildCount, hipcub::CountingInputIterator<uint64_t>> in(
-			counting, ChildCount{ par.word.as<uint32_t>(), s.embedded ? nullptr : s.masks, s.nNodes, n } );
-		if( exclusiveOffsets<uint64_t>( in, n + 1, off, &total, st ) ) return 1;
+		if( exclusiveOffsetsOf<uint64_t, uint64_t>( ChildCount{ par.word.as<uint32_t>(), s.embedded ? nullptr : s.masks, s.nNodes, n }, n + 1, off, &total, st ) ) return 1;
 		if( last ) out->n = total;
 		if( total == 0 ) return 0; // every path ended in a node of mask 0 (the empty octree: the root)
 		if( last && ( !fill || total > fillLimit ) ) return 0;

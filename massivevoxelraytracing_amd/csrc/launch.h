@@ -283,7 +283,8 @@ int mergeLists( const uint64_t* aCodes, const uint2* aAttrs, uint32_t nA, const 
 int gatherAttrs( const uint64_t* codes, uint32_t n, const uint64_t* srcCodes, const uint2* srcAttrs, uint32_t nSrc, DevBuf& attribs, hipStream_t stream );
 int anyEmission( const uint2* attrs, uint32_t n, uint32_t* hasEmission, hipStream_t stream );
 // offs = the n + 1 exclusive sums of the flags ( mask[i] != 0 ) == ( removed != 0 ), *count = their number; then the flagged entries in order: code and attribute
-// (a step) or index (a listing), any output may be null.  The launch is not synchronised
+// (a step) or index (a listing), any output may be null.  The launch is not synchronised.  maskOffsets with removed = 1 is the scan of every compaction by a
+// 32-bit flag array: the erosion listing, the seeds, the cells outside the set and the shallow voxels of the round offsets (kernels_ball.hip)
 int maskOffsets( const uint32_t* mask, uint32_t n, uint32_t removed, DevBuf& offs, uint32_t* count, hipStream_t stream );
 int launchCompactMasked( const uint64_t* codes, const uint2* attrs, const uint32_t* mask, const uint32_t* offs, uint32_t n, uint32_t removed, uint64_t* codesOut, uint2* attrsOut,
 						 uint32_t* vIndexOut, hipStream_t stream );

@@ -24,9 +24,15 @@
 //                   of the destination grid) and resampleTransformOk of kernels_resample.hip.  Host-callable (tests/hip/resample_host.hip).
 //   union-find      ufLoad / ufStore / ufFind / ufUnite / ufRoot: the lock-free union-find over node ids that kernels_fill.hip runs on the gaps and
 //                   kernels_components.hip on the voxels.  Device only.
+//   wave sums       waveSum / waveMax / waveMin over the 64 lanes, templates on the type the shuffles move, and waveAddInto / waveMaxInto, which end in one atomic
+//                   of lane 0 into a 64-bit counter: the counts of kernels_surface.hip, kernels_fill.hip, kernels_nearest.hip and kernels_query.hip.  Device only.
 //   host steps      exclusiveOffsets (the offsets above), sortPairsInto (a radix sort out of place that gives the input back) and rankHeads (head flags of sorted
 //                   entries -> rank + 1 of every entry and the number of runs).  Each allocates its output itself, runs hipcub through withCubTemp and has waited
-//                   for the stream when it returns.
+//                   for the stream when it returns.  exclusiveOffsetsOf / rankHeadsOf take the scan's input as a functor of the item's number and build the
+//                   counting and transform iterators themselves: the scans over a functor of eleven kernels_*.hip go through them (the three scans of kernels_surface.hip
+//                   over a byte array keep their transform iterator over the pointer, the per-level scan of kernels_resample.hip its hand-built pair).  KeyHead is the one head functor "sorted key differs from
+//                   its predecessor" (kernels_morph.hip, kernels_ball.hip, kernels_surface.hip).  Counters is the block of 64-bit counters of one call: allocated
+//                   and zeroed on the stream, read back with a wait (kernels_surface.hip, kernels_fill.hip, kernels_nearest.hip, kernels_query.hip).
 //   list steps      not here: the steps on whole sorted voxel lists that the operators share (merge, gather of attributes, emission scan, compaction by a mask, the
 //                   driver of a dilate / erode / close / open, the tail of a listing) are declared in launch.h under "sorted voxel lists" and live in kernels_list.hip.
 #pragma once
@@ -584,6 +590,44 @@ MVRT_DI uint32_t ufRoot( uint32_t* parent, uint32_t v )
 	}
 }
 
+// ---- wave reductions --------------------------------------------------------------------------------------------------------------------------------------
+// All 64 lanes of the wave call these; lane 0 ends with the sum, the maximum or the minimum of the wave's values.  The Into forms are the usual end of a counting
+// kernel: lane 0 adds (or maximises) a result that is not 0 into a 64-bit counter, one atomic per wave.  T is the type the shuffles move.  Device only.
+template <class T> MVRT_DI T waveSum( T v )
+{
+	for( int o = 32; o > 0; o >>= 1 ) v += __shfl_down( v, o, 64 );
+	return v;
+}
+template <class T> MVRT_DI T waveMax( T v )
+{
+	for( int o = 32; o > 0; o >>= 1 )
+	{
+		const T w = __shfl_down( v, o, 64 );
+		v = w > v ? w : v;
+	}
+	return v;
+}
+template <class T> MVRT_DI T waveMin( T v )
+{
+	for( int o = 32; o > 0; o >>= 1 )
+	{
+		const T w = __shfl_down( v, o, 64 );
+		v = w < v ? w : v;
+	}
+	return v;
+}
+MVRT_DI bool waveLane0() { return ( threadIdx.x & 63u ) == 0; }
+template <class T> MVRT_DI void waveAddInto( unsigned long long* dst, T v )
+{
+	v = waveSum( v );
+	if( waveLane0() && v ) atomicAdd( dst, (unsigned long long)v );
+}
+template <class T> MVRT_DI void waveMaxInto( unsigned long long* dst, T v )
+{
+	v = waveMax( v );
+	if( waveLane0() && v ) atomicMax( dst, (unsigned long long)v );
+}
+
 // ---- host steps -------------------------------------------------------------------------------------------------------------------------------------------
 // offs (allocated here) = the exclusive sums of `items` values of `in`, as T.  lastOnHost: where offs[items - 1] goes, valid when this returns (null = not wanted)
 template <class T, class In> int exclusiveOffsets( In in, uint64_t items, DevBuf& offs, T* lastOnHost, hipStream_t st )
@@ -594,6 +638,12 @@ template <class T, class In> int exclusiveOffsets( In in, uint64_t items, DevBuf
 		if( e != hipSuccess || !tmp || !lastOnHost ) return e;
 		return hipMemcpyAsync( lastOnHost, offs.as<T>() + ( items - 1 ), sizeof( T ), hipMemcpyDeviceToHost, st ); // (withCubTemp waits)
 	} );
+}
+// the same over a functor of the item's number: in = f( 0 ), f( 1 ), ..., the counting and the transform iterator built here (Index: the argument type of f)
+template <class T, class Index = uint32_t, class F> int exclusiveOffsetsOf( F f, uint64_t items, DevBuf& offs, T* lastOnHost, hipStream_t st )
+{
+	typedef hipcub::CountingInputIterator<Index> Counting;
+	return exclusiveOffsets<T>( hipcub::TransformInputIterator<T, F, Counting>( Counting( (Index)0 ), f ), items, offs, lastOnHost, st );
 }
 // n (key, value) pairs sorted by bits [0, endBit) of the key from A into B (allocated here); A is released
 inline int sortPairsInto( DevBuf& keysA, DevBuf& valsA, uint64_t n, int endBit, DevBuf& keysB, DevBuf& valsB, hipStream_t st )
@@ -618,3 +668,37 @@ template <class In> int rankHeads( In heads, uint64_t n, DevBuf& rank1, uint32_t
 		return hipMemcpyAsync( count, rank1.as<uint32_t>() + ( n - 1 ), 4, hipMemcpyDeviceToHost, st ); // (withCubTemp waits)
 	} );
 }
+// the same over a functor of the entry's number, as exclusiveOffsetsOf
+template <class F> int rankHeadsOf( F f, uint64_t n, DevBuf& rank1, uint32_t* count, hipStream_t st )
+{
+	typedef hipcub::CountingInputIterator<uint32_t> Counting;
+	return rankHeads( hipcub::TransformInputIterator<uint32_t, F, Counting>( Counting( 0u ), f ), n, rank1, count, st );
+}
+// the head flag of sorted keys, for rankHeadsOf: 1 where key i differs from its predecessor (the sorted records of a morphology step and of a band pass, the
+// sorted corner keys of the weld)
+struct KeyHead
+{
+	const uint64_t* keys;
+	__host__ __device__ uint32_t operator()( uint32_t i ) const { return i == 0u || keys[i] != keys[i - 1u] ? 1u : 0u; }
+};
+
+// The 64-bit counters of one call, which its kernels add into: allocated and zeroed on the stream by init (slot `ones`, where given, preset to ~0 for a minimum);
+// read copies them to the host behind the launches issued so far and waits for the stream
+struct Counters
+{
+	DevBuf buf;
+	unsigned long long* dev() const { return buf.as<unsigned long long>(); }
+	int init( uint32_t slots, hipStream_t st, int ones = -1 )
+	{
+		if( buf.alloc( slots * 8 ) ) return 1;
+		MVRT_HIP( hipMemsetAsync( buf.p, 0, slots * 8, st ) );
+		if( ones >= 0 ) MVRT_HIP( hipMemsetAsync( dev() + ones, 0xFF, 8, st ) );
+		return 0;
+	}
+	int read( unsigned long long* host, uint32_t slots, hipStream_t st ) const
+	{
+		MVRT_HIP( hipMemcpyAsync( host, buf.p, slots * 8, hipMemcpyDeviceToHost, st ) );
+		MVRT_HIP( hipStreamSynchronize( st ) );
+		return 0;
+	}
+};
