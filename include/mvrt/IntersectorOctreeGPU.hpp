@@ -117,34 +117,24 @@ struct IntersectorOctreeGPU
 	{
 		mvrt_svo_info i;
 		check( mvrt_svo_get_info( m_handle, &i ), "mvrt_svo_get_info" );
-		xyz.resize( (size_t)i.numberOfVoxels * 3 );
-		attribs.resize( (size_t)i.numberOfVoxels * 2 );
-		Staged x( nullptr, xyz.size() * 4, stream ), a( nullptr, attribs.size() * 4, stream );
-		readVoxels( (uint32_t*)x.p, (uint32_t*)a.p, stream );
-		check( mvrt_memcpy_d2h( xyz.data(), x.p, xyz.size() * 4, stream ), "mvrt_memcpy_d2h" );
-		check( mvrt_memcpy_d2h( attribs.data(), a.p, attribs.size() * 4, stream ), "mvrt_memcpy_d2h" );
+		Out<uint32_t> x( xyz, (uint64_t)i.numberOfVoxels * 3, stream ), a( attribs, (uint64_t)i.numberOfVoxels * 2, stream );
+		readVoxels( x, a, stream );
+		x.fetch( stream, true ), a.fetch( stream, true ); // (true: the one listing that asks for the copy of an empty vector too)
 	}
 
 	// the voxels of whatever octree this holds, uploaded or built, one per root-to-voxel path in ascending Morton order (mvrt_svo_walk_voxels; semantics in mvrt.h).
 	// Device-pointer form: any output may be nullptr, all nullptr = the sizing call; returns the count.  A capacity below the count aborts like any failure.
 	uint64_t walkVoxels( uint64_t capacity, uint32_t* xyzDev, uint32_t* vIndexDev, uint32_t* attribsDev, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_walk_voxels( m_handle, capacity, xyzDev, vIndexDev, attribsDev, &n, stream ), "IntersectorOctreeGPU::walkVoxels" );
-		return n;
+		return counted( "IntersectorOctreeGPU::walkVoxels", [&]( uint64_t* n ) { return mvrt_svo_walk_voxels( m_handle, capacity, xyzDev, vIndexDev, attribsDev, n, stream ); } );
 	}
 	// host-vector form: xyz = 3 entries per voxel, vIndex = 1, attribs = 2
 	void walkVoxels( std::vector<uint32_t>& xyz, std::vector<uint32_t>& vIndex, std::vector<uint32_t>& attribs, void* stream ) const
 	{
 		const uint64_t n = walkVoxels( 0, nullptr, nullptr, nullptr, stream );
-		xyz.resize( n * 3 );
-		vIndex.resize( n );
-		attribs.resize( n * 2 );
-		Staged x( nullptr, n * 12, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
-		if( n ) walkVoxels( n, (uint32_t*)x.p, (uint32_t*)v.p, (uint32_t*)a.p, stream );
-		fetch( xyz, x, stream );
-		fetch( vIndex, v, stream );
-		fetch( attribs, a, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), v( vIndex, n, stream ), a( attribs, n * 2, stream );
+		if( n ) walkVoxels( n, x, v, a, stream );
+		fetch( stream, x, v, a );
 	}
 	// an uploaded octree becomes one this library built (mvrt_svo_rebuild): readVoxels / editVoxels / surface* work afterwards.  Invalidates deviceView() snapshots.
 	void rebuild( int flags = 0, void* stream = nullptr )
@@ -157,40 +147,32 @@ struct IntersectorOctreeGPU
 	// mvrt_svo_fill_enclosed; semantics in mvrt.h).  Device-pointer form: either output may be nullptr, both nullptr = the sizing call; returns the cell count.
 	uint64_t enclosedCells( uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nRegions, void* stream ) const
 	{
-		uint64_t nCells = 0;
-		check( mvrt_svo_enclosed_cells( m_handle, capacity, xyzDev, regionDev, &nCells, nRegions, stream ), "IntersectorOctreeGPU::enclosedCells" );
-		return nCells;
+		return counted( "IntersectorOctreeGPU::enclosedCells", [&]( uint64_t* nCells ) { return mvrt_svo_enclosed_cells( m_handle, capacity, xyzDev, regionDev, nCells, nRegions, stream ); } );
 	}
 	// host-vector form: xyz = 3 entries per cell in ascending Morton order, region = 1 per cell, numbered by first appearance; returns the number of regions
 	uint64_t enclosedCells( std::vector<uint32_t>& xyz, std::vector<uint32_t>& region, void* stream ) const
 	{
 		uint64_t nRegions = 0;
 		const uint64_t n = enclosedCells( 0, nullptr, nullptr, &nRegions, stream );
-		xyz.resize( n * 3 );
-		region.resize( n );
-		Staged x( nullptr, n * 12, stream ), r( nullptr, n * 4, stream );
-		if( n ) enclosedCells( n, (uint32_t*)x.p, (uint32_t*)r.p, nullptr, stream );
-		fetch( xyz, x, stream );
-		fetch( region, r, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), r( region, n, stream );
+		if( n ) enclosedCells( n, x, r, nullptr, stream );
+		fetch( stream, x, r );
 		return nRegions;
 	}
 	// every enclosed cell becomes a voxel with fillAttrib (8 bytes VoxelAttirb, nullptr = white, no emission), as editVoxels would set it; returns the number of
 	// cells filled.  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
 	uint64_t fillEnclosed( const uint8_t* fillAttrib = nullptr, void* stream = nullptr )
 	{
-		uint64_t nFilled = 0;
-		check( mvrt_svo_fill_enclosed( m_handle, fillAttrib, &nFilled, stream ), "IntersectorOctreeGPU::fillEnclosed" );
-		refresh();
-		return nFilled;
+		return edited( "IntersectorOctreeGPU::fillEnclosed", [&]( uint64_t* nFilled ) { return mvrt_svo_fill_enclosed( m_handle, fillAttrib, nFilled, stream ); } );
 	}
 	// the same cells with their nearest voxel, without a radius (mvrt_svo_enclosed_nearest / mvrt_svo_fill_enclosed_nearest; semantics in mvrt.h).  Device-pointer
 	// form: any output may be nullptr, all nullptr = the sizing call, which computes no distance; returns the cell count.
 	uint64_t enclosedNearest( uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, uint64_t* nRegions,
 							  void* stream ) const
 	{
-		uint64_t nCells = 0;
-		check( mvrt_svo_enclosed_nearest( m_handle, capacity, xyzDev, regionDev, dist2Dev, nearestDev, attribsDev, &nCells, nRegions, stream ), "IntersectorOctreeGPU::enclosedNearest" );
-		return nCells;
+		return counted( "IntersectorOctreeGPU::enclosedNearest", [&]( uint64_t* nCells ) {
+			return mvrt_svo_enclosed_nearest( m_handle, capacity, xyzDev, regionDev, dist2Dev, nearestDev, attribsDev, nCells, nRegions, stream );
+		} );
 	}
 	// host-vector form: xyz and region as enclosedCells gives them, dist2 = 1 entry per cell (the exact squared distance to the set, below 2^20), nearest = 1 (the
 	// vIndex of the nearest voxel, the lowest on a tie), attribs = 2 (that voxel's colour and emission, alpha 255); returns the number of regions
@@ -199,28 +181,16 @@ struct IntersectorOctreeGPU
 	{
 		uint64_t nRegions = 0;
 		const uint64_t n = enclosedNearest( 0, nullptr, nullptr, nullptr, nullptr, nullptr, &nRegions, stream );
-		xyz.resize( n * 3 );
-		region.resize( n );
-		dist2.resize( n );
-		nearest.resize( n );
-		attribs.resize( n * 2 );
-		Staged x( nullptr, n * 12, stream ), r( nullptr, n * 4, stream ), d( nullptr, n * 4, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
-		if( n ) enclosedNearest( n, (uint32_t*)x.p, (uint32_t*)r.p, (uint32_t*)d.p, (uint32_t*)v.p, (uint32_t*)a.p, nullptr, stream );
-		fetch( xyz, x, stream );
-		fetch( region, r, stream );
-		fetch( dist2, d, stream );
-		fetch( nearest, v, stream );
-		fetch( attribs, a, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), r( region, n, stream ), d( dist2, n, stream ), v( nearest, n, stream ), a( attribs, n * 2, stream );
+		if( n ) enclosedNearest( n, x, r, d, v, a, nullptr, stream );
+		fetch( stream, x, r, d, v, a );
 		return nRegions;
 	}
 	// every enclosed cell becomes a voxel with the colour and emission of its nearest voxel, taken on the set before the fill, as editVoxels would set it; returns
 	// the number of cells filled.  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
 	uint64_t fillEnclosedNearest( void* stream = nullptr )
 	{
-		uint64_t nFilled = 0;
-		check( mvrt_svo_fill_enclosed_nearest( m_handle, &nFilled, stream ), "IntersectorOctreeGPU::fillEnclosedNearest" );
-		refresh();
-		return nFilled;
+		return edited( "IntersectorOctreeGPU::fillEnclosedNearest", [&]( uint64_t* nFilled ) { return mvrt_svo_fill_enclosed_nearest( m_handle, nFilled, stream ); } );
 	}
 
 	// a coarser level of detail from the voxels themselves (mvrt_svo_coarse_voxels / mvrt_svo_coarsen; semantics in mvrt.h): the cells (x >> k, y >> k, z >> k),
@@ -228,22 +198,16 @@ struct IntersectorOctreeGPU
 	// sizing call; returns the number of kept cells.
 	uint64_t coarseVoxels( int levelsDown, uint64_t minCount, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_coarse_voxels( m_handle, levelsDown, minCount, capacity, xyzDev, attribsDev, countDev, &n, stream ), "IntersectorOctreeGPU::coarseVoxels" );
-		return n;
+		return counted( "IntersectorOctreeGPU::coarseVoxels",
+						[&]( uint64_t* n ) { return mvrt_svo_coarse_voxels( m_handle, levelsDown, minCount, capacity, xyzDev, attribsDev, countDev, n, stream ); } );
 	}
 	// host-vector form: xyz = 3 entries per cell in ascending Morton order, attribs = 2, count = 1 (the fine voxels of the cell)
 	void coarseVoxels( int levelsDown, uint64_t minCount, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs, std::vector<uint32_t>& count, void* stream ) const
 	{
 		const uint64_t n = coarseVoxels( levelsDown, minCount, 0, nullptr, nullptr, nullptr, stream );
-		xyz.resize( n * 3 );
-		attribs.resize( n * 2 );
-		count.resize( n );
-		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), c( nullptr, n * 4, stream );
-		if( n ) coarseVoxels( levelsDown, minCount, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint32_t*)c.p, stream );
-		fetch( xyz, x, stream );
-		fetch( attribs, a, stream );
-		fetch( count, c, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), a( attribs, n * 2, stream ), c( count, n, stream );
+		if( n ) coarseVoxels( levelsDown, minCount, n, x, a, c, stream );
+		fetch( stream, x, a, c );
 	}
 	// dst (nullptr = this object: the in-place LOD) becomes the octree buildFromVoxels would build from that list at gridRes >> levelsDown with buildFlags, inside
 	// the same bounds.  Invalidates deviceView() snapshots of dst.
@@ -259,139 +223,92 @@ struct IntersectorOctreeGPU
 	// return the count.
 	uint64_t dilationCells( int element, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* countDev, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_dilation_cells( m_handle, element, capacity, xyzDev, attribsDev, countDev, &n, stream ), "IntersectorOctreeGPU::dilationCells" );
-		return n;
+		return counted( "IntersectorOctreeGPU::dilationCells", [&]( uint64_t* n ) { return mvrt_svo_dilation_cells( m_handle, element, capacity, xyzDev, attribsDev, countDev, n, stream ); } );
 	}
 	// host-vector form: xyz = 3 entries per cell in ascending Morton order, attribs = 2, count = 1 (the occupied neighbours of the cell)
 	void dilationCells( int element, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs, std::vector<uint32_t>& count, void* stream ) const
 	{
 		const uint64_t n = dilationCells( element, 0, nullptr, nullptr, nullptr, stream );
-		xyz.resize( n * 3 );
-		attribs.resize( n * 2 );
-		count.resize( n );
-		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), c( nullptr, n * 4, stream );
-		if( n ) dilationCells( element, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint32_t*)c.p, stream );
-		fetch( xyz, x, stream );
-		fetch( attribs, a, stream );
-		fetch( count, c, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), a( attribs, n * 2, stream ), c( count, n, stream );
+		if( n ) dilationCells( element, n, x, a, c, stream );
+		fetch( stream, x, a, c );
 	}
 	uint64_t erosionVoxels( int element, uint64_t capacity, uint32_t* vIndexDev, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_erosion_voxels( m_handle, element, capacity, vIndexDev, &n, stream ), "IntersectorOctreeGPU::erosionVoxels" );
-		return n;
+		return counted( "IntersectorOctreeGPU::erosionVoxels", [&]( uint64_t* n ) { return mvrt_svo_erosion_voxels( m_handle, element, capacity, vIndexDev, n, stream ); } );
 	}
 	// host-vector form: the vIndex, ascending, of the voxels one erosion step removes
 	void erosionVoxels( int element, std::vector<uint32_t>& vIndex, void* stream ) const
 	{
 		const uint64_t n = erosionVoxels( element, 0, nullptr, stream );
-		vIndex.resize( n );
-		Staged v( nullptr, n * 4, stream );
-		if( n ) erosionVoxels( element, n, (uint32_t*)v.p, stream );
-		fetch( vIndex, v, stream );
+		Out<uint32_t> v( vIndex, n, stream );
+		if( n ) erosionVoxels( element, n, v, stream );
+		fetch( stream, v );
 	}
 	// in place, the levels built once per call.  They return the cells added (dilate), the voxels removed (erode), the net cells added (close) and the net voxels
 	// removed (open).  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
 	uint64_t dilate( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_dilate( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::dilate" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::dilate", [&]( uint64_t* n ) { return mvrt_svo_dilate( m_handle, element, steps, n, stream ); } );
 	}
 	uint64_t erode( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_erode( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::erode" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::erode", [&]( uint64_t* n ) { return mvrt_svo_erode( m_handle, element, steps, n, stream ); } );
 	}
 	uint64_t close( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_close( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::close" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::close", [&]( uint64_t* n ) { return mvrt_svo_close( m_handle, element, steps, n, stream ); } );
 	}
 	uint64_t open( int element = MVRT_MORPH_CUBE, int steps = 1, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_open( m_handle, element, steps, &n, stream ), "IntersectorOctreeGPU::open" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::open", [&]( uint64_t* n ) { return mvrt_svo_open( m_handle, element, steps, n, stream ); } );
 	}
 
 	// round offsets (mvrt_svo_distance_cells / _depth_voxels / _dilate_ball / _erode_ball / _close_ball / _open_ball; semantics in mvrt.h), radius2 = the squared
 	// radius of the ball, 1..1024.  Device-pointer forms of the listings: any output may be nullptr, all nullptr = the sizing call; they return the count.
 	uint64_t distanceCells( uint32_t radius2, uint64_t capacity, uint32_t* xyzDev, uint32_t* dist2Dev, uint32_t* nearestDev, uint32_t* attribsDev, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_distance_cells( m_handle, radius2, capacity, xyzDev, dist2Dev, nearestDev, attribsDev, &n, stream ), "IntersectorOctreeGPU::distanceCells" );
-		return n;
+		return counted( "IntersectorOctreeGPU::distanceCells",
+						[&]( uint64_t* n ) { return mvrt_svo_distance_cells( m_handle, radius2, capacity, xyzDev, dist2Dev, nearestDev, attribsDev, n, stream ); } );
 	}
 	// host-vector form: xyz = 3 entries per cell in ascending Morton order, dist2 = 1 (the exact squared distance to the set), nearest = 1 (the vIndex of the
 	// nearest voxel, the lowest on a tie), attribs = 2 (that voxel's colour and emission, alpha 255)
 	void distanceCells( uint32_t radius2, std::vector<uint32_t>& xyz, std::vector<uint32_t>& dist2, std::vector<uint32_t>& nearest, std::vector<uint32_t>& attribs, void* stream ) const
 	{
 		const uint64_t n = distanceCells( radius2, 0, nullptr, nullptr, nullptr, nullptr, stream );
-		xyz.resize( n * 3 );
-		dist2.resize( n );
-		nearest.resize( n );
-		attribs.resize( n * 2 );
-		Staged x( nullptr, n * 12, stream ), d( nullptr, n * 4, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
-		if( n ) distanceCells( radius2, n, (uint32_t*)x.p, (uint32_t*)d.p, (uint32_t*)v.p, (uint32_t*)a.p, stream );
-		fetch( xyz, x, stream );
-		fetch( dist2, d, stream );
-		fetch( nearest, v, stream );
-		fetch( attribs, a, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), d( dist2, n, stream ), v( nearest, n, stream ), a( attribs, n * 2, stream );
+		if( n ) distanceCells( radius2, n, x, d, v, a, stream );
+		fetch( stream, x, d, v, a );
 	}
 	uint64_t depthVoxels( uint32_t radius2, uint64_t capacity, uint32_t* vIndexDev, uint32_t* depth2Dev, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_depth_voxels( m_handle, radius2, capacity, vIndexDev, depth2Dev, &n, stream ), "IntersectorOctreeGPU::depthVoxels" );
-		return n;
+		return counted( "IntersectorOctreeGPU::depthVoxels", [&]( uint64_t* n ) { return mvrt_svo_depth_voxels( m_handle, radius2, capacity, vIndexDev, depth2Dev, n, stream ); } );
 	}
 	// host-vector form: the vIndex, ascending, of the voxels whose squared depth is at most radius2, and that depth
 	void depthVoxels( uint32_t radius2, std::vector<uint32_t>& vIndex, std::vector<uint32_t>& depth2, void* stream ) const
 	{
 		const uint64_t n = depthVoxels( radius2, 0, nullptr, nullptr, stream );
-		vIndex.resize( n );
-		depth2.resize( n );
-		Staged v( nullptr, n * 4, stream ), d( nullptr, n * 4, stream );
-		if( n ) depthVoxels( radius2, n, (uint32_t*)v.p, (uint32_t*)d.p, stream );
-		fetch( vIndex, v, stream );
-		fetch( depth2, d, stream );
+		Out<uint32_t> v( vIndex, n, stream ), d( depth2, n, stream );
+		if( n ) depthVoxels( radius2, n, v, d, stream );
+		fetch( stream, v, d );
 	}
 	// in place, one ball per call, the levels built once.  They return the cells added (dilateBall), the voxels removed (erodeBall), the net cells added (closeBall)
 	// and the net voxels removed (openBall).  0: the octree was not touched; otherwise deviceView() snapshots are invalidated.
 	uint64_t dilateBall( uint32_t radius2, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_dilate_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::dilateBall" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::dilateBall", [&]( uint64_t* n ) { return mvrt_svo_dilate_ball( m_handle, radius2, n, stream ); } );
 	}
 	uint64_t erodeBall( uint32_t radius2, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_erode_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::erodeBall" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::erodeBall", [&]( uint64_t* n ) { return mvrt_svo_erode_ball( m_handle, radius2, n, stream ); } );
 	}
 	uint64_t closeBall( uint32_t radius2, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_close_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::closeBall" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::closeBall", [&]( uint64_t* n ) { return mvrt_svo_close_ball( m_handle, radius2, n, stream ); } );
 	}
 	uint64_t openBall( uint32_t radius2, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_open_ball( m_handle, radius2, &n, stream ), "IntersectorOctreeGPU::openBall" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::openBall", [&]( uint64_t* n ) { return mvrt_svo_open_ball( m_handle, radius2, n, stream ); } );
 	}
 
 	// connected components of the voxel set (mvrt_svo_components / mvrt_svo_keep_components; semantics in mvrt.h), element = MVRT_MORPH_FACES (6-connected) or
@@ -399,35 +316,25 @@ struct IntersectorOctreeGPU
 	// output may be nullptr, all nullptr = the sizing call.  Returns the number of components; *largest (may be nullptr) = the size of the largest.
 	uint64_t components( int element, uint32_t* labelDev, uint64_t componentCapacity, uint32_t* sizeDev, uint32_t* firstDev, uint32_t* boxDev, uint64_t* largest, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_components( m_handle, element, labelDev, componentCapacity, sizeDev, firstDev, boxDev, &n, largest, stream ), "IntersectorOctreeGPU::components" );
-		return n;
+		return counted( "IntersectorOctreeGPU::components",
+						[&]( uint64_t* n ) { return mvrt_svo_components( m_handle, element, labelDev, componentCapacity, sizeDev, firstDev, boxDev, n, largest, stream ); } );
 	}
 	// host-vector form: label = one entry per voxel in vIndex order, numbered by first appearance; per component size = 1 entry, first = 1 (its lowest vIndex),
 	// box = 6 (min x, y, z, max x, y, z)
 	void components( int element, std::vector<uint32_t>& label, std::vector<uint32_t>& size, std::vector<uint32_t>& first, std::vector<uint32_t>& box, void* stream ) const
 	{
 		const uint64_t n = components( element, nullptr, 0, nullptr, nullptr, nullptr, nullptr, stream );
-		label.resize( m_numberOfVoxels );
-		size.resize( n );
-		first.resize( n );
-		box.resize( n * 6 );
-		Staged l( nullptr, (uint64_t)m_numberOfVoxels * 4, stream ), s( nullptr, n * 4, stream ), f( nullptr, n * 4, stream ), b( nullptr, n * 24, stream );
-		components( element, (uint32_t*)l.p, n, (uint32_t*)s.p, (uint32_t*)f.p, (uint32_t*)b.p, nullptr, stream );
-		fetch( label, l, stream );
-		fetch( size, s, stream );
-		fetch( first, f, stream );
-		fetch( box, b, stream );
+		Out<uint32_t> l( label, m_numberOfVoxels, stream ), s( size, n, stream ), f( first, n, stream ), b( box, n * 6, stream );
+		components( element, l, n, s, f, b, nullptr, stream ); // (made at n == 0 too, unlike the listings above)
+		fetch( stream, l, s, f, b );
 	}
 	// in place: keeps the components of at least minVoxels voxels and, where keepLargest != 0, only the keepLargest largest of them (a tie goes to the component
 	// that appears first).  Returns the voxels removed; *keptComponents (may be nullptr) = the components kept.  0: the octree was not touched; otherwise
 	// deviceView() snapshots are invalidated.
 	uint64_t keepComponents( int element = MVRT_MORPH_CUBE, uint64_t minVoxels = 1, uint32_t keepLargest = 0, uint64_t* keptComponents = nullptr, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_keep_components( m_handle, element, minVoxels, keepLargest, &n, keptComponents, stream ), "IntersectorOctreeGPU::keepComponents" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::keepComponents",
+					   [&]( uint64_t* n ) { return mvrt_svo_keep_components( m_handle, element, minVoxels, keepLargest, n, keptComponents, stream ); } );
 	}
 
 	// boolean operations with a second voxel set moved by an integer cell offset (mvrt_svo_combine_voxels / mvrt_svo_combine; semantics in mvrt.h): op = COMBINE_*,
@@ -444,24 +351,19 @@ struct IntersectorOctreeGPU
 	uint64_t combineVoxels( const IntersectorOctreeGPU& b, int op, const int32_t* offset, uint32_t flags, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev,
 							uint8_t* sourceDev, uint64_t* overlap, uint64_t* clipped, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_combine_voxels( m_handle, b.m_handle, op, offset, flags, capacity, xyzDev, attribsDev, sourceDev, &n, overlap, clipped, stream ),
-			   "IntersectorOctreeGPU::combineVoxels" );
-		return n;
+		return counted( "IntersectorOctreeGPU::combineVoxels", [&]( uint64_t* n ) {
+			return mvrt_svo_combine_voxels( m_handle, b.m_handle, op, offset, flags, capacity, xyzDev, attribsDev, sourceDev, n, overlap, clipped, stream );
+		} );
 	}
 	// host-vector form: xyz = 3 entries per voxel in ascending Morton order, attribs = 2, source = 1 byte (1 = this set only, 2 = b only, 3 = both)
 	void combineVoxels( const IntersectorOctreeGPU& b, int op, const int32_t* offset, uint32_t flags, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs,
 						std::vector<uint8_t>& source, uint64_t* overlap, uint64_t* clipped, void* stream ) const
 	{
 		const uint64_t n = combineVoxels( b, op, offset, flags, 0, nullptr, nullptr, nullptr, overlap, clipped, stream );
-		xyz.resize( n * 3 );
-		attribs.resize( n * 2 );
-		source.resize( n );
-		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), s( nullptr, n, stream );
-		if( n ) combineVoxels( b, op, offset, flags, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint8_t*)s.p, nullptr, nullptr, stream );
-		fetch( xyz, x, stream );
-		fetch( attribs, a, stream );
-		fetch( source, s, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), a( attribs, n * 2, stream );
+		Out<uint8_t> s( source, n, stream );
+		if( n ) combineVoxels( b, op, offset, flags, n, x, a, s, nullptr, nullptr, stream );
+		fetch( stream, x, a, s );
 	}
 	// in place: this octree becomes the result, exactly as the edit with the added voxels as MVRT_VOXEL_SET and the dropped ones as MVRT_VOXEL_REMOVE leaves it; b
 	// may be this object.  Returns the voxels added; *removed and *clipped may be nullptr.  A call that changes nothing does not touch the octree; otherwise
@@ -469,10 +371,7 @@ struct IntersectorOctreeGPU
 	uint64_t combine( const IntersectorOctreeGPU& b, int op, const int32_t* offset = nullptr, uint32_t flags = 0, uint64_t* removed = nullptr, uint64_t* clipped = nullptr,
 					  void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_combine( m_handle, b.m_handle, op, offset, flags, &n, removed, clipped, stream ), "IntersectorOctreeGPU::combine" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::combine", [&]( uint64_t* n ) { return mvrt_svo_combine( m_handle, b.m_handle, op, offset, flags, n, removed, clipped, stream ); } );
 	}
 
 	// the nearest voxel of arbitrary lattice points, the distance to a second voxel set and the recolouring from it (mvrt_svo_nearest_voxels / _nearest_between /
@@ -494,14 +393,11 @@ struct IntersectorOctreeGPU
 	{
 		const uint64_t n = query.size() / 3;
 		nearestVoxels( 0, nullptr, maxDist2, nullptr, nullptr, nullptr, stream ); // (what the handle decides is refused before anything is allocated)
-		dist2.resize( n );
-		nearest.resize( n );
-		attribs.resize( n * 2 );
-		Staged q( query.data(), n * 12, stream ), d( nullptr, n * 8, stream ), v( nullptr, n * 4, stream ), a( nullptr, n * 8, stream );
-		if( n ) nearestVoxels( n, (const int32_t*)q.p, maxDist2, (uint64_t*)d.p, (uint32_t*)v.p, (uint32_t*)a.p, stream );
-		fetch( dist2, d, stream );
-		fetch( nearest, v, stream );
-		fetch( attribs, a, stream );
+		Staged q( query.data(), n * 12, stream );
+		Out<uint64_t> d( dist2, n, stream );
+		Out<uint32_t> v( nearest, n, stream ), a( attribs, n * 2, stream );
+		if( n ) nearestVoxels( n, (const int32_t*)q.p, maxDist2, d, v, a, stream );
+		fetch( stream, d, v, a );
 	}
 	// every voxel v of this set, in vIndex order, asked as v - offset (3 ints or nullptr = zero) in b; b may be this object
 	struct Between
@@ -523,12 +419,10 @@ struct IntersectorOctreeGPU
 		check( mvrt_svo_get_info( m_handle, &i ), "IntersectorOctreeGPU::nearestBetween" );
 		const uint64_t n = i.numberOfVoxels;
 		if( !n ) return nearestBetween( b, offset, maxDist2, 0, nullptr, nullptr, stream ); // (an empty handle: the call refuses it)
-		dist2.resize( n );
-		nearest.resize( n );
-		Staged d( nullptr, n * 8, stream ), v( nullptr, n * 4, stream );
-		const Between r = nearestBetween( b, offset, maxDist2, n, (uint64_t*)d.p, (uint32_t*)v.p, stream );
-		fetch( dist2, d, stream );
-		fetch( nearest, v, stream );
+		Out<uint64_t> d( dist2, n, stream );
+		Out<uint32_t> v( nearest, n, stream );
+		const Between r = nearestBetween( b, offset, maxDist2, n, d, v, stream );
+		fetch( stream, d, v );
 		return r;
 	}
 	// in place: every voxel with a voxel of src within maxDist2 takes the words `flags` names (TRANSFER_COLOUR | TRANSFER_EMISSION) of the nearest one, exactly as the
@@ -537,10 +431,8 @@ struct IntersectorOctreeGPU
 	uint64_t transferAttributes( const IntersectorOctreeGPU& src, const int32_t* offset = nullptr, uint64_t maxDist2 = NO_LIMIT, uint32_t flags = TRANSFER_COLOUR | TRANSFER_EMISSION,
 								 uint64_t* beyond = nullptr, void* stream = nullptr )
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_transfer_attributes( m_handle, src.m_handle, offset, maxDist2, flags, &n, beyond, stream ), "IntersectorOctreeGPU::transferAttributes" );
-		refresh();
-		return n;
+		return edited( "IntersectorOctreeGPU::transferAttributes",
+					   [&]( uint64_t* n ) { return mvrt_svo_transfer_attributes( m_handle, src.m_handle, offset, maxDist2, flags, n, beyond, stream ); } );
 	}
 
 	// the voxel set resampled onto a grid of dstGridRes cells per axis under an affine map (mvrt_svo_resample_voxels / mvrt_svo_resample; semantics in mvrt.h): xf is
@@ -555,22 +447,16 @@ struct IntersectorOctreeGPU
 	}
 	uint64_t resampleVoxels( const mvrt_cell_transform& xf, int dstGridRes, uint64_t capacity, uint32_t* xyzDev, uint32_t* attribsDev, uint32_t* sourceDev, void* stream ) const
 	{
-		uint64_t n = 0;
-		check( mvrt_svo_resample_voxels( m_handle, &xf, dstGridRes, capacity, xyzDev, attribsDev, sourceDev, &n, stream ), "IntersectorOctreeGPU::resampleVoxels" );
-		return n;
+		return counted( "IntersectorOctreeGPU::resampleVoxels",
+						[&]( uint64_t* n ) { return mvrt_svo_resample_voxels( m_handle, &xf, dstGridRes, capacity, xyzDev, attribsDev, sourceDev, n, stream ); } );
 	}
 	// host-vector form: xyz = 3 entries per voxel in ascending Morton order of the destination grid, attribs = 2, source = 1 (the vIndex the voxel comes from)
 	void resampleVoxels( const mvrt_cell_transform& xf, int dstGridRes, std::vector<uint32_t>& xyz, std::vector<uint32_t>& attribs, std::vector<uint32_t>& source, void* stream ) const
 	{
 		const uint64_t n = resampleVoxels( xf, dstGridRes, 0, nullptr, nullptr, nullptr, stream );
-		xyz.resize( n * 3 );
-		attribs.resize( n * 2 );
-		source.resize( n );
-		Staged x( nullptr, n * 12, stream ), a( nullptr, n * 8, stream ), s( nullptr, n * 4, stream );
-		if( n ) resampleVoxels( xf, dstGridRes, n, (uint32_t*)x.p, (uint32_t*)a.p, (uint32_t*)s.p, stream );
-		fetch( xyz, x, stream );
-		fetch( attribs, a, stream );
-		fetch( source, s, stream );
+		Out<uint32_t> x( xyz, n * 3, stream ), a( attribs, n * 2, stream ), s( source, n, stream );
+		if( n ) resampleVoxels( xf, dstGridRes, n, x, a, s, stream );
+		fetch( stream, x, a, s );
 	}
 	// dst (nullptr = this object) becomes the octree buildFromVoxels would build from that list with dstOrigin, dstDps, dstGridRes and buildFlags.  Returns the voxels
 	// of the result; an empty result aborts like any failure.  Invalidates deviceView() snapshots of dst.
@@ -578,25 +464,20 @@ struct IntersectorOctreeGPU
 	{
 		IntersectorOctreeGPU* d = dst ? dst : this;
 		const float o[3] = { dstOrigin.x, dstOrigin.y, dstOrigin.z };
-		uint64_t n = 0;
-		check( mvrt_svo_resample( m_handle, d->m_handle, &xf, o, dstDps, dstGridRes, buildFlags, &n, stream ), "IntersectorOctreeGPU::resample" );
-		d->refresh();
-		return n;
+		return d->edited( "IntersectorOctreeGPU::resample", // (d->: it is dst that is refreshed)
+						  [&]( uint64_t* n ) { return mvrt_svo_resample( m_handle, d->m_handle, &xf, o, dstDps, dstGridRes, buildFlags, n, stream ); } );
 	}
 
 	// the exposed faces of the voxel set as quads (mvrt_svo_surface_masks / _quads / _mesh; semantics in mvrt.h; the reference's Save As Mesh, voxMesh.cpp:111-219).
 	// Device-pointer forms: any output may be nullptr, all nullptr = the sizing call; they return the counts.  A capacity below the count aborts like any failure.
 	uint64_t surfaceMasks( uint8_t* masksDev, void* stream ) const
 	{
-		uint64_t nFaces = 0;
-		check( mvrt_svo_surface_masks( m_handle, masksDev, &nFaces, stream ), "IntersectorOctreeGPU::surfaceMasks" );
-		return nFaces;
+		return counted( "IntersectorOctreeGPU::surfaceMasks", [&]( uint64_t* nFaces ) { return mvrt_svo_surface_masks( m_handle, masksDev, nFaces, stream ); } );
 	}
 	uint64_t surfaceQuads( uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, void* stream ) const
 	{
-		uint64_t nFaces = 0;
-		check( mvrt_svo_surface_quads( m_handle, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, &nFaces, stream ), "IntersectorOctreeGPU::surfaceQuads" );
-		return nFaces;
+		return counted( "IntersectorOctreeGPU::surfaceQuads",
+						[&]( uint64_t* nFaces ) { return mvrt_svo_surface_quads( m_handle, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFaces, stream ); } );
 	}
 	void surfaceMesh( uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFaces,
 					  uint64_t* nVertices, void* stream ) const
@@ -607,39 +488,21 @@ struct IntersectorOctreeGPU
 	// host-vector forms: sized here (the sizing call, then the real one), staged through mvrt_malloc / mvrt_memcpy_d2h
 	uint64_t surfaceMasks( std::vector<uint8_t>& masks, void* stream ) const
 	{
-		masks.resize( m_numberOfVoxels );
-		Staged m( nullptr, masks.size(), stream );
-		const uint64_t nFaces = surfaceMasks( (uint8_t*)m.p, stream );
-		fetch( masks, m, stream );
+		Out<uint8_t> m( masks, m_numberOfVoxels, stream );
+		const uint64_t nFaces = surfaceMasks( m, stream );
+		fetch( stream, m );
 		return nFaces;
 	}
+	// (the host-vector forms of quads, mesh, merged and ao and their *Masked twins are one private template each, below: quadsToHost, meshToHost, mergedToHost,
+	// aoToHost; `a...` = the capacities, outputs and counters as the template passes them to the device-pointer form)
 	void surfaceQuads( std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<float>& positions /* 12 per face */, void* stream ) const
 	{
-		const uint64_t n = surfaceQuads( 0, nullptr, nullptr, nullptr, stream );
-		faceVoxel.resize( n );
-		faceDir.resize( n );
-		positions.resize( n * 12 );
-		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), p( nullptr, n * 48, stream );
-		surfaceQuads( n, (uint32_t*)v.p, (uint8_t*)d.p, (float*)p.p, stream );
-		fetch( faceVoxel, v, stream );
-		fetch( faceDir, d, stream );
-		fetch( positions, p, stream );
+		quadsToHost( [&]( const auto&... a ) { return surfaceQuads( a..., stream ); }, faceVoxel, faceDir, positions, stream );
 	}
 	void surfaceMesh( std::vector<float>& vertices /* 3 per vertex */, std::vector<uint32_t>& indices /* 4 per face */, std::vector<uint32_t>& faceVoxel,
 					  std::vector<uint8_t>& faceDir, void* stream ) const
 	{
-		uint64_t nf = 0, nv = 0;
-		surfaceMesh( 0, 0, nullptr, nullptr, nullptr, nullptr, &nf, &nv, stream );
-		vertices.resize( nv * 3 );
-		indices.resize( nf * 4 );
-		faceVoxel.resize( nf );
-		faceDir.resize( nf );
-		Staged x( nullptr, nv * 12, stream ), i( nullptr, nf * 16, stream ), v( nullptr, nf * 4, stream ), d( nullptr, nf, stream );
-		surfaceMesh( nf, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)i.p, (float*)x.p, &nf, &nv, stream );
-		fetch( vertices, x, stream );
-		fetch( indices, i, stream );
-		fetch( faceVoxel, v, stream );
-		fetch( faceDir, d, stream );
+		meshToHost( [&]( const auto&... a ) { surfaceMesh( a..., stream ); }, vertices, indices, faceVoxel, faceDir, stream );
 	}
 
 	// the same surface with coplanar faces merged into rectangles (mvrt_svo_surface_merged; the rule is in mvrt.h).  flags: MVRT_SURFACE_MERGE_ANY_ATTRIBUTE |
@@ -656,24 +519,7 @@ struct IntersectorOctreeGPU
 	uint64_t surfaceMerged( uint32_t flags, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& rectVoxel, std::vector<uint8_t>& rectDir,
 							std::vector<uint32_t>& rectSize /* 2 per rectangle */, void* stream ) const
 	{
-		const bool weld = ( flags & MVRT_SURFACE_MERGE_WELD ) != 0;
-		uint64_t nf = 0, nr = 0, nv = 0;
-		surfaceMerged( flags, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nf, &nr, &nv, stream );
-		const uint64_t points = weld ? nv : nr * 4;
-		vertices.resize( points * 3 );
-		indices.resize( weld ? nr * 4 : 0 );
-		rectVoxel.resize( nr );
-		rectDir.resize( nr );
-		rectSize.resize( nr * 2 );
-		Staged x( nullptr, points * 12, stream ), i( nullptr, indices.size() * 4, stream ), v( nullptr, nr * 4, stream ), d( nullptr, nr, stream ), s( nullptr, nr * 8, stream );
-		surfaceMerged( flags, nr, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)s.p, weld ? nullptr : (float*)x.p, weld ? (uint32_t*)i.p : nullptr, weld ? (float*)x.p : nullptr, &nf,
-					   &nr, &nv, stream );
-		fetch( vertices, x, stream );
-		fetch( indices, i, stream );
-		fetch( rectVoxel, v, stream );
-		fetch( rectDir, d, stream );
-		fetch( rectSize, s, stream );
-		return nf;
+		return mergedToHost( [&]( const auto&... a ) { surfaceMerged( flags, a..., stream ); }, flags, vertices, indices, rectVoxel, rectDir, rectSize, stream );
 	}
 
 	// exterior-only masks and the three extraction calls on face masks the caller supplies (mvrt_svo_surface_exterior_masks / mvrt_svo_surface_*_masked; semantics in
@@ -682,15 +528,14 @@ struct IntersectorOctreeGPU
 	// (counts only); returns the exterior faces, *nHidden = the faces of surfaceMasks minus those
 	uint64_t surfaceExteriorMasks( uint8_t* masksDev, uint64_t* nHidden, void* stream ) const
 	{
-		uint64_t nFaces = 0;
-		check( mvrt_svo_surface_exterior_masks( m_handle, masksDev, &nFaces, nHidden, stream ), "IntersectorOctreeGPU::surfaceExteriorMasks" );
-		return nFaces;
+		return counted( "IntersectorOctreeGPU::surfaceExteriorMasks",
+						[&]( uint64_t* nFaces ) { return mvrt_svo_surface_exterior_masks( m_handle, masksDev, nFaces, nHidden, stream ); } );
 	}
 	uint64_t surfaceQuadsMasked( const uint8_t* masksDev, uint64_t faceCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, float* positionsDev, void* stream ) const
 	{
-		uint64_t nFaces = 0;
-		check( mvrt_svo_surface_quads_masked( m_handle, masksDev, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, &nFaces, stream ), "IntersectorOctreeGPU::surfaceQuadsMasked" );
-		return nFaces;
+		return counted( "IntersectorOctreeGPU::surfaceQuadsMasked", [&]( uint64_t* nFaces ) {
+			return mvrt_svo_surface_quads_masked( m_handle, masksDev, faceCapacity, faceVoxelDev, faceDirDev, positionsDev, nFaces, stream );
+		} );
 	}
 	void surfaceMeshMasked( const uint8_t* masksDev, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev,
 							float* verticesDev, uint64_t* nFaces, uint64_t* nVertices, void* stream ) const
@@ -709,81 +554,36 @@ struct IntersectorOctreeGPU
 	// host-vector forms, like their namesakes; `masks` holds numberOfVoxels bytes
 	uint64_t surfaceExteriorMasks( std::vector<uint8_t>& masks, uint64_t* nHidden, void* stream ) const
 	{
-		masks.resize( m_numberOfVoxels );
-		Staged m( nullptr, masks.size(), stream );
-		const uint64_t nFaces = surfaceExteriorMasks( (uint8_t*)m.p, nHidden, stream );
-		fetch( masks, m, stream );
+		Out<uint8_t> m( masks, m_numberOfVoxels, stream );
+		const uint64_t nFaces = surfaceExteriorMasks( m, nHidden, stream );
+		fetch( stream, m );
 		return nFaces;
 	}
 	void surfaceQuadsMasked( const std::vector<uint8_t>& masks, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<float>& positions /* 12 per face */,
 							 void* stream ) const
 	{
 		Staged m( masks.data(), masks.size(), stream );
-		const uint64_t n = surfaceQuadsMasked( (const uint8_t*)m.p, 0, nullptr, nullptr, nullptr, stream );
-		faceVoxel.resize( n );
-		faceDir.resize( n );
-		positions.resize( n * 12 );
-		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), p( nullptr, n * 48, stream );
-		surfaceQuadsMasked( (const uint8_t*)m.p, n, (uint32_t*)v.p, (uint8_t*)d.p, (float*)p.p, stream );
-		fetch( faceVoxel, v, stream );
-		fetch( faceDir, d, stream );
-		fetch( positions, p, stream );
+		quadsToHost( [&]( const auto&... a ) { return surfaceQuadsMasked( (const uint8_t*)m.p, a..., stream ); }, faceVoxel, faceDir, positions, stream );
 	}
 	void surfaceMeshMasked( const std::vector<uint8_t>& masks, std::vector<float>& vertices /* 3 per vertex */, std::vector<uint32_t>& indices /* 4 per face */,
 							std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, void* stream ) const
 	{
 		Staged m( masks.data(), masks.size(), stream );
-		uint64_t nf = 0, nv = 0;
-		surfaceMeshMasked( (const uint8_t*)m.p, 0, 0, nullptr, nullptr, nullptr, nullptr, &nf, &nv, stream );
-		vertices.resize( nv * 3 );
-		indices.resize( nf * 4 );
-		faceVoxel.resize( nf );
-		faceDir.resize( nf );
-		Staged x( nullptr, nv * 12, stream ), i( nullptr, nf * 16, stream ), v( nullptr, nf * 4, stream ), d( nullptr, nf, stream );
-		surfaceMeshMasked( (const uint8_t*)m.p, nf, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)i.p, (float*)x.p, &nf, &nv, stream );
-		fetch( vertices, x, stream );
-		fetch( indices, i, stream );
-		fetch( faceVoxel, v, stream );
-		fetch( faceDir, d, stream );
+		meshToHost( [&]( const auto&... a ) { surfaceMeshMasked( (const uint8_t*)m.p, a..., stream ); }, vertices, indices, faceVoxel, faceDir, stream );
 	}
 	uint64_t surfaceMergedMasked( const std::vector<uint8_t>& masks, uint32_t flags, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& rectVoxel,
 								  std::vector<uint8_t>& rectDir, std::vector<uint32_t>& rectSize /* 2 per rectangle */, void* stream ) const
 	{
 		Staged m( masks.data(), masks.size(), stream );
-		const bool weld = ( flags & MVRT_SURFACE_MERGE_WELD ) != 0;
-		uint64_t nf = 0, nr = 0, nv = 0;
-		surfaceMergedMasked( (const uint8_t*)m.p, flags, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nf, &nr, &nv, stream );
-		const uint64_t points = weld ? nv : nr * 4;
-		vertices.resize( points * 3 );
-		indices.resize( weld ? nr * 4 : 0 );
-		rectVoxel.resize( nr );
-		rectDir.resize( nr );
-		rectSize.resize( nr * 2 );
-		Staged x( nullptr, points * 12, stream ), i( nullptr, indices.size() * 4, stream ), v( nullptr, nr * 4, stream ), d( nullptr, nr, stream ), s( nullptr, nr * 8, stream );
-		surfaceMergedMasked( (const uint8_t*)m.p, flags, nr, nv, (uint32_t*)v.p, (uint8_t*)d.p, (uint32_t*)s.p, weld ? nullptr : (float*)x.p, weld ? (uint32_t*)i.p : nullptr,
-							 weld ? (float*)x.p : nullptr, &nf, &nr, &nv, stream );
-		fetch( vertices, x, stream );
-		fetch( indices, i, stream );
-		fetch( rectVoxel, v, stream );
-		fetch( rectDir, d, stream );
-		fetch( rectSize, s, stream );
-		return nf;
+		return mergedToHost( [&]( const auto&... a ) { surfaceMergedMasked( (const uint8_t*)m.p, flags, a..., stream ); }, flags, vertices, indices, rectVoxel, rectDir, rectSize,
+							 stream );
 	}
 	// the faces of surfaceQuadsMasked with their occlusion (surfaceAo below takes any face list)
 	void surfaceAoMasked( const std::vector<uint8_t>& masks, int samples, float radius, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<uint16_t>& open,
 						  void* stream ) const
 	{
 		Staged m( masks.data(), masks.size(), stream );
-		const uint64_t n = surfaceQuadsMasked( (const uint8_t*)m.p, 0, nullptr, nullptr, nullptr, stream );
-		faceVoxel.resize( n );
-		faceDir.resize( n );
-		open.resize( n );
-		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), o( nullptr, n * 2, stream );
-		surfaceQuadsMasked( (const uint8_t*)m.p, n, (uint32_t*)v.p, (uint8_t*)d.p, nullptr, stream );
-		surfaceAo( n, (const uint32_t*)v.p, (const uint8_t*)d.p, samples, radius, (uint16_t*)o.p, stream );
-		fetch( faceVoxel, v, stream );
-		fetch( faceDir, d, stream );
-		fetch( open, o, stream );
+		aoToHost( [&]( const auto&... a ) { return surfaceQuadsMasked( (const uint8_t*)m.p, a..., stream ); }, samples, radius, faceVoxel, faceDir, open, stream );
 	}
 
 	// batch form of the device method intersect() (:243-251): SoA device arrays
@@ -806,16 +606,7 @@ struct IntersectorOctreeGPU
 	// host-vector form: the faces of surfaceQuads with their occlusion
 	void surfaceAo( int samples, float radius, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<uint16_t>& open, void* stream ) const
 	{
-		const uint64_t n = surfaceQuads( 0, nullptr, nullptr, nullptr, stream );
-		faceVoxel.resize( n );
-		faceDir.resize( n );
-		open.resize( n );
-		Staged v( nullptr, n * 4, stream ), d( nullptr, n, stream ), o( nullptr, n * 2, stream );
-		surfaceQuads( n, (uint32_t*)v.p, (uint8_t*)d.p, nullptr, stream );
-		surfaceAo( n, (const uint32_t*)v.p, (const uint8_t*)d.p, samples, radius, (uint16_t*)o.p, stream );
-		fetch( faceVoxel, v, stream );
-		fetch( faceDir, d, stream );
-		fetch( open, o, stream );
+		aoToHost( [&]( const auto&... a ) { return surfaceQuads( a..., stream ); }, samples, radius, faceVoxel, faceDir, open, stream );
 	}
 	// the table of occlusion ray directions (mvrt_ao_directions): 6 * samples * 3 floats, host only
 	static std::vector<float> aoDirections( int samples )
@@ -887,9 +678,81 @@ private:
 		Staged( const Staged& ) = delete;
 		void operator=( const Staged& ) = delete;
 	};
-	template <class T> static void fetch( std::vector<T>& host, const Staged& dev, void* stream ) // device -> host vector of the same size (nothing for an empty one)
+	// one output of a host-vector form: the caller's vector, resized to `count` entries, tied to its uninitialised staging block on the device (none for count 0).
+	// It converts to the T* the device-pointer forms take.  A listing declares its outputs once, in allocation order, and copies them back with fetch(): not in
+	// a destructor, since check() aborts and an abort while unwinding would hide the first error.
+	template <class T> struct Out
 	{
-		if( !host.empty() ) check( mvrt_memcpy_d2h( host.data(), dev.p, host.size() * sizeof( T ), stream ), "mvrt_memcpy_d2h" );
+		std::vector<T>& host;
+		Staged dev;
+		Out( std::vector<T>& h, uint64_t count, void* stream ) : host( ( h.resize( count ), h ) ), dev( nullptr, count * sizeof( T ), stream ) {}
+		operator T*() const { return (T*)dev.p; }
+		void fetch( void* stream, bool copyEmpty = false ) const // device -> host vector of the same size (nothing for an empty one)
+		{
+			if( copyEmpty || !host.empty() ) check( mvrt_memcpy_d2h( host.data(), dev.p, host.size() * sizeof( T ), stream ), "mvrt_memcpy_d2h" );
+		}
+	};
+	template <class... O> static void fetch( void* stream, const O&... outs ) { ( outs.fetch( stream ), ... ); } // in the order given
+	// a call that reports its first count through the pointer it is handed: checked under `label`; edited(): an in-place operation, the members refreshed after it
+	template <class Call> static uint64_t counted( const char* label, Call call )
+	{
+		uint64_t n = 0;
+		check( call( &n ), label );
+		return n;
+	}
+	template <class Call> uint64_t edited( const char* label, Call call )
+	{
+		const uint64_t n = counted( label, call );
+		refresh();
+		return n;
+	}
+	// the host-vector forms of the surface listings, `quads` / `mesh` / `merged` = the device-pointer form without its stream (surfaceQuads or surfaceQuadsMasked
+	// on staged masks, ...).  Unlike the voxel listings they make the filling call at a count of 0 too.
+	template <class Quads> void quadsToHost( Quads quads, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<float>& positions, void* stream ) const
+	{
+		const uint64_t n = quads( 0, nullptr, nullptr, nullptr );
+		Out<uint32_t> v( faceVoxel, n, stream );
+		Out<uint8_t> d( faceDir, n, stream );
+		Out<float> p( positions, n * 12, stream );
+		quads( n, v, d, p );
+		fetch( stream, v, d, p );
+	}
+	template <class Mesh>
+	void meshToHost( Mesh mesh, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, void* stream ) const
+	{
+		uint64_t nf = 0, nv = 0;
+		mesh( 0, 0, nullptr, nullptr, nullptr, nullptr, &nf, &nv );
+		Out<float> x( vertices, nv * 3, stream );
+		Out<uint32_t> i( indices, nf * 4, stream ), v( faceVoxel, nf, stream );
+		Out<uint8_t> d( faceDir, nf, stream );
+		mesh( nf, nv, v, d, i, x, &nf, &nv );
+		fetch( stream, x, i, v, d );
+	}
+	template <class Merged>
+	uint64_t mergedToHost( Merged merged, uint32_t flags, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& rectVoxel, std::vector<uint8_t>& rectDir,
+						   std::vector<uint32_t>& rectSize, void* stream ) const
+	{
+		const bool weld = ( flags & MVRT_SURFACE_MERGE_WELD ) != 0;
+		uint64_t nf = 0, nr = 0, nv = 0;
+		merged( 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nf, &nr, &nv );
+		Out<float> x( vertices, ( weld ? nv : nr * 4 ) * 3, stream ); // welded: the shared vertices; else the positions, 4 corners per rectangle
+		Out<uint32_t> i( indices, weld ? nr * 4 : 0, stream ), v( rectVoxel, nr, stream );
+		Out<uint8_t> d( rectDir, nr, stream );
+		Out<uint32_t> s( rectSize, nr * 2, stream );
+		merged( nr, nv, v, d, s, weld ? nullptr : (float*)x, weld ? (uint32_t*)i : nullptr, weld ? (float*)x : nullptr, &nf, &nr, &nv );
+		fetch( stream, x, i, v, d, s );
+		return nf;
+	}
+	template <class Quads>
+	void aoToHost( Quads quads, int samples, float radius, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, std::vector<uint16_t>& open, void* stream ) const
+	{
+		const uint64_t n = quads( 0, nullptr, nullptr, nullptr );
+		Out<uint32_t> v( faceVoxel, n, stream );
+		Out<uint8_t> d( faceDir, n, stream );
+		Out<uint16_t> o( open, n, stream );
+		quads( n, v, d, nullptr );
+		surfaceAo( n, v, d, samples, radius, o, stream );
+		fetch( stream, v, d, o );
 	}
 	mvrt_svo* m_handle = nullptr;
 	bool m_owned = true;

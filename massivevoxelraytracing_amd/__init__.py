@@ -477,6 +477,28 @@ class IntersectorOctreeGPU:
                 raise ValueError("%s has %d entries, xyz %d" % (what, m, n))
         return n, keep, px, pa, po
 
+    def _counts(self, fn, args, n, stream):
+        """the call every wrapper that returns counts makes: fn(handle, *args, n uint64 out-counters, stream), checked; -> the count (n == 1) or the n of them"""
+        out = [C.c_uint64(0) for _ in range(n)]
+        _check(fn(self._h, *args, *[C.byref(c) for c in out], stream))
+        return out[0].value if n == 1 else tuple(c.value for c in out)
+
+    @staticmethod
+    def _listing(device, lead, outs, stream, scalars=()):
+        """a listing in host form.  device = the bound *_device method, device(*lead, capacity, *arrays, stream) -> the count or (count, further counts...);
+        outs = ((key, trailing shape, dtype), ...) in the order of its arrays.  The sizing call, one device array of `count` entries per output, the filling call
+        unless the count is 0, the copies back; -> {key: host array, ..., then the further counts of the sizing call under the names `scalars`}"""
+        r = device(*lead, stream=stream)
+        n, more = (r[0], r[1:]) if isinstance(r, tuple) else (r, ())
+        arrays = [DeviceArray((n,) + shape, dtype) for _, shape, dtype in outs]
+        if n:
+            device(*lead, n, *arrays, stream)
+        out = {key: a.to_host() for (key, _, _), a in zip(outs, arrays)}
+        out.update(zip(scalars, more))
+        return out
+
+    _XYZ, _ATTRIBS = ("xyz", (3,), np.uint32), ("attribs", (8,), np.uint8)  # the two outputs most listings share
+
     def build_voxels(self, xyz, attribs=None, origin=(0.0, 0.0, 0.0), dps=None, gridRes=None, flags=0, stream=None):
         """mvrt_svo_build_voxels: xyz (n, 3) uint32 in [0, gridRes), attribs (n, 8) uint8 VoxelAttirb {color, emission} or None (white, no emission).
         Duplicates merge like the reference's unique (integer mean).  flags: BUILD_NO_DAG | BUILD_NO_EMBEDDED_MASK."""
@@ -500,18 +522,12 @@ class IntersectorOctreeGPU:
     def walk_voxels_device(self, capacity=0, xyz=None, vIndex=None, attribs=None, stream=None):
         """mvrt_svo_walk_voxels into caller device arrays of `capacity` entries (any may be None; all None = the sizing call); returns the path count.
         On MvrtError nothing was written."""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_walk_voxels(self._h, int(capacity), _dev_ptr(xyz), _dev_ptr(vIndex), _dev_ptr(attribs), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_walk_voxels, (int(capacity), _dev_ptr(xyz), _dev_ptr(vIndex), _dev_ptr(attribs)), 1, stream)
 
     def walk_voxels(self, stream=None):
         """the voxels of whatever octree the handle holds, uploaded or built, one per root-to-voxel path in ascending path (Morton) order:
         {xyz (n, 3) uint32, vIndex (n,) uint32 = what a trace reports for the voxel, attribs (n, 8) uint8 = the attribute of that vIndex}"""
-        n = self.walk_voxels_device(stream=stream)
-        xyz, vi, at = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
-        if n:
-            self.walk_voxels_device(n, xyz, vi, at, stream)
-        return {"xyz": xyz.to_host(), "vIndex": vi.to_host(), "attribs": at.to_host()}
+        return self._listing(self.walk_voxels_device, (), (self._XYZ, ("vIndex", (), np.uint32), self._ATTRIBS), stream)
 
     def rebuild(self, flags=0, stream=None):
         """mvrt_svo_rebuild: the octree becomes the one build_voxels would build from its walked voxels (attribute bytes and hasEmission kept), after which
@@ -521,68 +537,46 @@ class IntersectorOctreeGPU:
     def enclosed_cells_device(self, capacity=0, xyz=None, region=None, stream=None):
         """mvrt_svo_enclosed_cells into caller device arrays of `capacity` cells (either may be None; both None = the sizing call); returns (nCells, nRegions).
         On MvrtError nothing was written."""
-        nc, nr = C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_enclosed_cells(self._h, int(capacity), _dev_ptr(xyz), _dev_ptr(region), C.byref(nc), C.byref(nr), stream))
-        return nc.value, nr.value
+        return self._counts(lib().mvrt_svo_enclosed_cells, (int(capacity), _dev_ptr(xyz), _dev_ptr(region)), 2, stream)
 
     def enclosed_cells(self, stream=None):
         """the empty cells no 6-connected path of empty cells joins to the grid border: {xyz (n, 3) uint32 in ascending Morton order, region (n,) uint32 numbered
         by first appearance in that order, nRegions}"""
-        n, nr = self.enclosed_cells_device(stream=stream)
-        xyz, region = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32)
-        if n:
-            self.enclosed_cells_device(n, xyz, region, stream)
-        return {"xyz": xyz.to_host(), "region": region.to_host(), "nRegions": nr}
+        return self._listing(self.enclosed_cells_device, (), (self._XYZ, ("region", (), np.uint32)), stream, ("nRegions",))
 
     def fill_enclosed(self, attrib=None, stream=None):
         """mvrt_svo_fill_enclosed: every enclosed cell becomes a voxel with `attrib` (8 bytes VoxelAttirb {color, emission}; None = white, no emission), exactly
         as edit_voxels would set them; returns the number of cells filled (0: the handle was not touched).  Invalidates device_view() snapshots otherwise."""
         a = None if attrib is None else np.ascontiguousarray(attrib).view(np.uint8).reshape(8)
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_fill_enclosed(self._h, _hp(a), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_fill_enclosed, (_hp(a),), 1, stream)
 
     def enclosed_nearest_device(self, capacity=0, xyz=None, region=None, dist2=None, nearest=None, attribs=None, stream=None):
         """mvrt_svo_enclosed_nearest into caller device arrays of `capacity` cells (any may be None; all None = the sizing call, which runs no distance pass);
         returns (nCells, nRegions).  On MvrtError nothing was written."""
-        nc, nr = C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_enclosed_nearest(self._h, int(capacity), _dev_ptr(xyz), _dev_ptr(region), _dev_ptr(dist2), _dev_ptr(nearest), _dev_ptr(attribs), C.byref(nc),
-                                               C.byref(nr), stream))
-        return nc.value, nr.value
+        return self._counts(lib().mvrt_svo_enclosed_nearest, (int(capacity), _dev_ptr(xyz), _dev_ptr(region), _dev_ptr(dist2), _dev_ptr(nearest), _dev_ptr(attribs)), 2, stream)
 
     def enclosed_nearest(self, stream=None):
         """the enclosed cells of enclosed_cells(), in its order, with their nearest voxel: {xyz (n, 3) uint32, region (n,) uint32, dist2 (n,) uint32 = the exact
         squared distance to the set (no radius; below 2^20), nearest (n,) uint32 = the lowest vIndex among the voxels at that distance, attribs (n, 8) uint8 = that
         voxel's colour and emission with alpha 255, nRegions}"""
-        n, nr = self.enclosed_nearest_device(stream=stream)
-        xyz, region, d2, near, at = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
-        if n:
-            self.enclosed_nearest_device(n, xyz, region, d2, near, at, stream)
-        return {"xyz": xyz.to_host(), "region": region.to_host(), "dist2": d2.to_host(), "nearest": near.to_host(), "attribs": at.to_host(), "nRegions": nr}
+        outs = (self._XYZ, ("region", (), np.uint32), ("dist2", (), np.uint32), ("nearest", (), np.uint32), self._ATTRIBS)
+        return self._listing(self.enclosed_nearest_device, (), outs, stream, ("nRegions",))
 
     def fill_enclosed_nearest(self, stream=None):
         """mvrt_svo_fill_enclosed_nearest: every enclosed cell becomes a voxel with the colour and emission of its nearest voxel (taken on the set before the
         fill), exactly as edit_voxels would set the cells and attribs of enclosed_nearest(); returns the number of cells filled (0: the handle was not touched).
         Invalidates device_view() snapshots otherwise."""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_fill_enclosed_nearest(self._h, C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_fill_enclosed_nearest, (), 1, stream)
 
     def coarse_voxels_device(self, levels_down, min_count=1, capacity=0, xyz=None, attribs=None, count=None, stream=None):
         """mvrt_svo_coarse_voxels into caller device arrays of `capacity` cells (any may be None; all None = the sizing call); returns the number of kept cells.
         On MvrtError nothing was written."""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_coarse_voxels(self._h, int(levels_down), int(min_count), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(count), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_coarse_voxels, (int(levels_down), int(min_count), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(count)), 1, stream)
 
     def coarse_voxels(self, levels_down, min_count=1, stream=None):
         """the voxel set `levels_down` levels coarser: the cells (x >> k, y >> k, z >> k) that hold at least min_count voxels, in ascending Morton order:
         {xyz (n, 3) uint32 coarse coordinates, attribs (n, 8) uint8 = the integer mean per channel with alpha 255, count (n,) uint32 fine voxels per cell}"""
-        n = self.coarse_voxels_device(levels_down, min_count, stream=stream)
-        xyz, at, cnt = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint32)
-        if n:
-            self.coarse_voxels_device(levels_down, min_count, n, xyz, at, cnt, stream)
-        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "count": cnt.to_host()}
+        return self._listing(self.coarse_voxels_device, (levels_down, min_count), (self._XYZ, self._ATTRIBS, ("count", (), np.uint32)), stream)
 
     def coarsen(self, levels_down, min_count=1, flags=0, dst=None, stream=None):
         """mvrt_svo_coarsen: dst (None = this object, the in-place LOD) becomes the octree build_voxels would build from coarse_voxels() at gridRes >> levels_down
@@ -595,135 +589,97 @@ class IntersectorOctreeGPU:
     def dilation_cells_device(self, element=MORPH_CUBE, capacity=0, xyz=None, attribs=None, count=None, stream=None):
         """mvrt_svo_dilation_cells into caller device arrays of `capacity` cells (any may be None; all None = the sizing call); returns the number of cells.
         On MvrtError nothing was written."""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_dilation_cells(self._h, int(element), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(count), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_dilation_cells, (int(element), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(count)), 1, stream)
 
     def dilation_cells(self, element=MORPH_CUBE, stream=None):
         """the cells one dilation step with `element` (MORPH_FACES / MORPH_CUBE) adds, in ascending Morton order: {xyz (n, 3) uint32, attribs (n, 8) uint8 = the
         integer mean per channel over the occupied in-grid neighbours with alpha 255, count (n,) uint32 = their number}"""
-        n = self.dilation_cells_device(element, stream=stream)
-        xyz, at, cnt = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint32)
-        if n:
-            self.dilation_cells_device(element, n, xyz, at, cnt, stream)
-        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "count": cnt.to_host()}
+        return self._listing(self.dilation_cells_device, (element,), (self._XYZ, self._ATTRIBS, ("count", (), np.uint32)), stream)
 
     def erosion_voxels_device(self, element=MORPH_CUBE, capacity=0, vIndex=None, stream=None):
         """mvrt_svo_erosion_voxels into a caller device array of `capacity` entries (None = the sizing call); returns the number of voxels a step removes."""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_erosion_voxels(self._h, int(element), int(capacity), _dev_ptr(vIndex), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_erosion_voxels, (int(element), int(capacity), _dev_ptr(vIndex)), 1, stream)
 
     def erosion_voxels(self, element=MORPH_CUBE, stream=None):
         """the vIndex, ascending, of the voxels one erosion step removes: those with an empty e-neighbour inside the grid (outside counts as occupied)"""
-        n = self.erosion_voxels_device(element, stream=stream)
-        vi = DeviceArray(n, np.uint32)
-        if n:
-            self.erosion_voxels_device(element, n, vi, stream)
-        return vi.to_host()
-
-    def _morph(self, fn, element, steps, stream):
-        n = C.c_uint64(0)
-        _check(fn(self._h, int(element), int(steps), C.byref(n), stream))
-        return n.value
+        return self._listing(self.erosion_voxels_device, (element,), (("vIndex", (), np.uint32),), stream)["vIndex"]
 
     def dilate(self, element=MORPH_CUBE, steps=1, stream=None):
         """mvrt_svo_dilate: `steps` dilation steps in place, the levels built once; returns the cells added (0: the handle was not touched).  Invalidates
         device_view() snapshots otherwise, like edit_voxels."""
-        return self._morph(lib().mvrt_svo_dilate, element, steps, stream)
+        return self._counts(lib().mvrt_svo_dilate, (int(element), int(steps)), 1, stream)
 
     def erode(self, element=MORPH_CUBE, steps=1, stream=None):
         """mvrt_svo_erode: `steps` erosion steps in place (outside the grid counts as occupied); returns the voxels removed.  Refused when none would be left."""
-        return self._morph(lib().mvrt_svo_erode, element, steps, stream)
+        return self._counts(lib().mvrt_svo_erode, (int(element), int(steps)), 1, stream)
 
     def close(self, element=MORPH_CUBE, steps=1, stream=None):
         """mvrt_svo_close: `steps` dilation steps, then `steps` erosion steps, in place; returns the net cells added.  close(MORPH_CUBE, 1) before fill_enclosed
         repairs a shell with one-voxel holes."""
-        return self._morph(lib().mvrt_svo_close, element, steps, stream)
+        return self._counts(lib().mvrt_svo_close, (int(element), int(steps)), 1, stream)
 
     def open(self, element=MORPH_CUBE, steps=1, stream=None):
         """mvrt_svo_open: `steps` erosion steps, then `steps` dilation steps, in place; a pure removal (the voxels left keep their bytes); returns the net voxels
         removed.  Refused when none would be left."""
-        return self._morph(lib().mvrt_svo_open, element, steps, stream)
+        return self._counts(lib().mvrt_svo_open, (int(element), int(steps)), 1, stream)
 
     def distance_cells_device(self, radius2=1, capacity=0, xyz=None, dist2=None, nearest=None, attribs=None, stream=None):
         """mvrt_svo_distance_cells into caller device arrays of `capacity` cells (any may be None; all None = the sizing call); returns the number of cells.
         On MvrtError nothing was written."""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_distance_cells(self._h, int(radius2), int(capacity), _dev_ptr(xyz), _dev_ptr(dist2), _dev_ptr(nearest), _dev_ptr(attribs), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_distance_cells, (int(radius2), int(capacity), _dev_ptr(xyz), _dev_ptr(dist2), _dev_ptr(nearest), _dev_ptr(attribs)), 1, stream)
 
     def distance_cells(self, radius2=1, stream=None):
         """the empty in-grid cells within squared distance `radius2` (1..1024) of the set, in ascending Morton order: {xyz (n, 3) uint32, dist2 (n,) uint32 = the
         exact squared distance to the set, nearest (n,) uint32 = the lowest vIndex among the voxels at that distance, attribs (n, 8) uint8 = that voxel's colour and
         emission with alpha 255}"""
-        n = self.distance_cells_device(radius2, stream=stream)
-        xyz, d2, near, at = DeviceArray((n, 3), np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
-        if n:
-            self.distance_cells_device(radius2, n, xyz, d2, near, at, stream)
-        return {"xyz": xyz.to_host(), "dist2": d2.to_host(), "nearest": near.to_host(), "attribs": at.to_host()}
+        return self._listing(self.distance_cells_device, (radius2,), (self._XYZ, ("dist2", (), np.uint32), ("nearest", (), np.uint32), self._ATTRIBS), stream)
 
     def depth_voxels_device(self, radius2=1, capacity=0, vIndex=None, depth2=None, stream=None):
         """mvrt_svo_depth_voxels into caller device arrays of `capacity` entries (any may be None; both None = the sizing call); returns the number of voxels."""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_depth_voxels(self._h, int(radius2), int(capacity), _dev_ptr(vIndex), _dev_ptr(depth2), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_depth_voxels, (int(radius2), int(capacity), _dev_ptr(vIndex), _dev_ptr(depth2)), 1, stream)
 
     def depth_voxels(self, radius2=1, stream=None):
         """the voxels whose squared distance to the nearest empty in-grid cell is at most `radius2` (outside the grid counts as occupied), the ones erode_ball
         removes: {vIndex (n,) uint32 ascending, depth2 (n,) uint32}"""
-        n = self.depth_voxels_device(radius2, stream=stream)
-        vi, d2 = DeviceArray(n, np.uint32), DeviceArray(n, np.uint32)
-        if n:
-            self.depth_voxels_device(radius2, n, vi, d2, stream)
-        return {"vIndex": vi.to_host(), "depth2": d2.to_host()}
-
-    def _ball(self, fn, radius2, stream):
-        n = C.c_uint64(0)
-        _check(fn(self._h, int(radius2), C.byref(n), stream))
-        return n.value
+        return self._listing(self.depth_voxels_device, (radius2,), (("vIndex", (), np.uint32), ("depth2", (), np.uint32)), stream)
 
     def dilate_ball(self, radius2=1, stream=None):
         """mvrt_svo_dilate_ball: the set grown by the ball of squared radius `radius2` in place, one operation, the levels built once; a new cell takes the
         attribute of its nearest voxel.  Returns the cells added (0: the handle was not touched).  Invalidates device_view() snapshots otherwise."""
-        return self._ball(lib().mvrt_svo_dilate_ball, radius2, stream)
+        return self._counts(lib().mvrt_svo_dilate_ball, (int(radius2),), 1, stream)
 
     def erode_ball(self, radius2=1, stream=None):
         """mvrt_svo_erode_ball: the voxels deeper than `radius2` stay (outside the grid counts as occupied); returns the voxels removed.  Refused when none would
         be left."""
-        return self._ball(lib().mvrt_svo_erode_ball, radius2, stream)
+        return self._counts(lib().mvrt_svo_erode_ball, (int(radius2),), 1, stream)
 
     def close_ball(self, radius2=1, stream=None):
         """mvrt_svo_close_ball: dilate_ball, then erode_ball, in one call; returns the net cells added."""
-        return self._ball(lib().mvrt_svo_close_ball, radius2, stream)
+        return self._counts(lib().mvrt_svo_close_ball, (int(radius2),), 1, stream)
 
     def open_ball(self, radius2=1, stream=None):
         """mvrt_svo_open_ball: erode_ball, then dilate_ball, in one call; a pure removal (the voxels left keep their bytes); returns the net voxels removed.
         Refused when none would be left."""
-        return self._ball(lib().mvrt_svo_open_ball, radius2, stream)
+        return self._counts(lib().mvrt_svo_open_ball, (int(radius2),), 1, stream)
 
     def components_device(self, element=MORPH_CUBE, label=None, capacity=0, size=None, first=None, box=None, stream=None):
         """mvrt_svo_components into caller device arrays: label of numberOfVoxels uint32, size / first of `capacity` uint32, box of capacity x 6 uint32 (any may be
         None; all None = the sizing call); returns (nComponents, largest).  On MvrtError nothing was written."""
-        n, big = C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_components(self._h, int(element), _dev_ptr(label), int(capacity), _dev_ptr(size), _dev_ptr(first), _dev_ptr(box), C.byref(n), C.byref(big), stream))
-        return n.value, big.value
+        return self._counts(lib().mvrt_svo_components, (int(element), _dev_ptr(label), int(capacity), _dev_ptr(size), _dev_ptr(first), _dev_ptr(box)), 2, stream)
 
     def components(self, element=MORPH_CUBE, stream=None):
         """the connected components under `element` (MORPH_FACES = 6-connected, MORPH_CUBE = 26-connected), numbered in order of first appearance in vIndex
         order: {label (numberOfVoxels,) uint32, size (n,) uint32, first (n,) uint32 = the lowest vIndex, box (n, 6) uint32 = min x, y, z, max x, y, z}"""
         n, _ = self.components_device(element, stream=stream)
         label, size, first, box = DeviceArray(self.info().numberOfVoxels, np.uint32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32), DeviceArray((n, 6), np.uint32)
-        self.components_device(element, label, n, size, first, box, stream)
+        self.components_device(element, label, n, size, first, box, stream)  # (made at n == 0 too, and label is sized by the voxels: not a _listing)
         return {"label": label.to_host(), "size": size.to_host(), "first": first.to_host(), "box": box.to_host()}
 
     def keep_components(self, element=MORPH_CUBE, min_voxels=1, keep_largest=0, stream=None):
         """mvrt_svo_keep_components: keeps, in place, the components of at least `min_voxels` voxels and, where keep_largest != 0, only the keep_largest largest
         of them (a tie goes to the component that appears first); exactly edit_voxels with VOXEL_REMOVE on the rest.  Returns (voxels removed, components
         kept); 0 removed: the handle was not touched.  Refused when no voxel would be left."""
-        removed, kept = C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_keep_components(self._h, int(element), int(min_voxels), int(keep_largest), C.byref(removed), C.byref(kept), stream))
-        return removed.value, kept.value
+        return self._counts(lib().mvrt_svo_keep_components, (int(element), int(min_voxels), int(keep_largest)), 2, stream)
 
     @staticmethod
     def _offset(offset):
@@ -732,29 +688,21 @@ class IntersectorOctreeGPU:
     def combine_voxels_device(self, b, op, offset=None, flags=0, capacity=0, xyz=None, attribs=None, source=None, stream=None):
         """mvrt_svo_combine_voxels into caller device arrays of `capacity` voxels (any may be None; all None = the sizing call); returns (n, overlap, clipped).
         On MvrtError nothing was written."""
-        n, ov, cl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_combine_voxels(self._h, b._h, int(op), _hp(self._offset(offset)), int(flags), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(source),
-                                             C.byref(n), C.byref(ov), C.byref(cl), stream))
-        return n.value, ov.value, cl.value
+        return self._counts(lib().mvrt_svo_combine_voxels, (b._h, int(op), _hp(self._offset(offset)), int(flags), int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(source)),
+                            3, stream)
 
     def combine_voxels(self, b, op, offset=None, flags=0, stream=None):
         """this set `op` (COMBINE_UNION / _INTERSECTION / _DIFFERENCE / _XOR) the set of `b` moved by `offset` (3 ints, None = 0) and clipped to this grid, in
         ascending Morton order: {xyz (n, 3) uint32, attribs (n, 8) uint8, source (n,) uint8 = 1 this only, 2 b only, 3 both, overlap = the voxels in both,
         clipped = the voxels of b the offset moves out of the grid}.  A voxel of this set keeps its bytes (COMBINE_ATTRIB_B: the overlap takes b's), one of b
         alone takes b's colour and emission with alpha 255.  Neither octree is modified."""
-        n, ov, cl = self.combine_voxels_device(b, op, offset, flags, stream=stream)
-        xyz, at, src = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint8)
-        if n:
-            self.combine_voxels_device(b, op, offset, flags, n, xyz, at, src, stream)
-        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "source": src.to_host(), "overlap": ov, "clipped": cl}
+        return self._listing(self.combine_voxels_device, (b, op, offset, flags), (self._XYZ, self._ATTRIBS, ("source", (), np.uint8)), stream, ("overlap", "clipped"))
 
     def combine(self, b, op, offset=None, flags=0, stream=None):
         """mvrt_svo_combine: this octree becomes combine_voxels(b, op, offset, flags), exactly as edit_voxels with the added voxels (and, under COMBINE_ATTRIB_B,
         the overlap) as VOXEL_SET and the dropped ones as VOXEL_REMOVE would leave it; b may be this object.  Returns (added, removed, clipped); a call that
         changes nothing leaves the handle untouched.  Refused when no voxel would be left.  Invalidates device_view() snapshots otherwise."""
-        ad, rm, cl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_combine(self._h, b._h, int(op), _hp(self._offset(offset)), int(flags), C.byref(ad), C.byref(rm), C.byref(cl), stream))
-        return ad.value, rm.value, cl.value
+        return self._counts(lib().mvrt_svo_combine, (b._h, int(op), _hp(self._offset(offset)), int(flags)), 3, stream)
 
     def nearest_voxels_device(self, n, query, max_dist2=NO_LIMIT, dist2=None, nearest=None, attribs=None, stream=None):
         """mvrt_svo_nearest_voxels: n queries (n x 3 int32 on the device) into caller device arrays (dist2 uint64, nearest uint32, attribs 8 bytes per query; any
@@ -773,7 +721,7 @@ class IntersectorOctreeGPU:
         self.nearest_voxels_device(0, None, max_dist2, stream=stream)  # (what the handle decides is refused before anything is allocated)
         qd = DeviceArray.from_host(q)
         d2, near, at = DeviceArray(n, np.uint64), DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)
-        self.nearest_voxels_device(n, qd, max_dist2, d2, near, at, stream)
+        self.nearest_voxels_device(n, qd, max_dist2, d2, near, at, stream)  # (made for n == 0 too; the C++ mirror skips it there)
         return {"dist2": d2.to_host(), "nearest": near.to_host(), "attribs": at.to_host()}
 
     def nearest_between_device(self, b, offset=None, max_dist2=NO_LIMIT, capacity=0, dist2=None, nearest=None, stream=None):
@@ -801,27 +749,19 @@ class IntersectorOctreeGPU:
         """mvrt_svo_transfer_attributes: every voxel v of this octree with a voxel of `src` within max_dist2 of v - offset takes the colour (TRANSFER_COLOUR)
         and / or the emission (TRANSFER_EMISSION) of the nearest one, exactly as edit_voxels with VOXEL_SET would store them; the others keep their 8 bytes.
         near is taken before anything is written: src may be this object.  Returns (changed, beyond); a call that changes no byte leaves the handle untouched."""
-        ch, nb = C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_transfer_attributes(self._h, src._h, _hp(self._offset(offset)), int(max_dist2), int(flags), C.byref(ch), C.byref(nb), stream))
-        return ch.value, nb.value
+        return self._counts(lib().mvrt_svo_transfer_attributes, (src._h, _hp(self._offset(offset)), int(max_dist2), int(flags)), 2, stream)
 
     def resample_voxels_device(self, xf, gridRes=None, capacity=0, xyz=None, attribs=None, source=None, stream=None):
         """mvrt_svo_resample_voxels into caller device arrays of `capacity` voxels (any may be None; all None = the sizing call); returns the count.  gridRes: the
         destination grid (None = this octree's).  On MvrtError nothing was written."""
-        n = C.c_uint64(0)
         res = int((self.info().gridRes or 2) if gridRes is None else gridRes)  # (an empty handle has no grid: the call itself refuses it, "no octree")
-        _check(lib().mvrt_svo_resample_voxels(self._h, C.byref(xf), res, int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(source), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_resample_voxels, (C.byref(xf), res, int(capacity), _dev_ptr(xyz), _dev_ptr(attribs), _dev_ptr(source)), 1, stream)
 
     def resample_voxels(self, xf, gridRes=None, stream=None):
         """this set resampled onto a grid of gridRes cells per axis (None = its own) under the CellTransform xf, the INVERSE map from destination cells to source
         cells: the destination cells whose centre maps into a voxel, in ascending Morton order: {xyz (n, 3) uint32, attribs (n, 8) uint8 = that voxel's colour and
         emission with alpha 255, source (n,) uint32 = its vIndex}.  The octree is not modified."""
-        n = self.resample_voxels_device(xf, gridRes, stream=stream)
-        xyz, at, src = DeviceArray((n, 3), np.uint32), DeviceArray((n, 8), np.uint8), DeviceArray(n, np.uint32)
-        if n:
-            self.resample_voxels_device(xf, gridRes, n, xyz, at, src, stream)
-        return {"xyz": xyz.to_host(), "attribs": at.to_host(), "source": src.to_host()}
+        return self._listing(self.resample_voxels_device, (xf, gridRes), (self._XYZ, self._ATTRIBS, ("source", (), np.uint32)), stream)
 
     def resample(self, xf, dst=None, origin=None, dps=None, gridRes=None, flags=0, stream=None):
         """mvrt_svo_resample: dst (None = this object) becomes the octree build_voxels would build from resample_voxels(xf, gridRes) with origin, dps, gridRes (None
@@ -832,15 +772,12 @@ class IntersectorOctreeGPU:
         o = np.ascontiguousarray(i.lower[:] if origin is None else origin, np.float32).reshape(3)
         dps = np.float32(i.dps if dps is None else dps)
         res = int((i.gridRes or 2) if gridRes is None else gridRes)
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_resample(self._h, dst._h, C.byref(xf), _hp(o), float(dps), res, int(flags), C.byref(n), stream))
+        self._counts(lib().mvrt_svo_resample, (dst._h, C.byref(xf), _hp(o), float(dps), res, int(flags)), 1, stream)
         return dst
 
     def surface_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_masks into a caller's device array of numberOfVoxels bytes (None = count only); returns nFaces"""
-        n = C.c_uint64(0)
-        _check(lib().mvrt_svo_surface_masks(self._h, _dev_ptr(masks_dev), C.byref(n), stream))
-        return n.value
+        return self._counts(lib().mvrt_svo_surface_masks, (_dev_ptr(masks_dev),), 1, stream)
 
     def surface_masks(self, stream=None):
         """mvrt_svo_surface_masks -> (masks (numberOfVoxels,) uint8 in vIndex order, nFaces): bit d of a mask = the neighbour in direction d is empty,
@@ -852,9 +789,7 @@ class IntersectorOctreeGPU:
     def surface_exterior_masks_device(self, masks_dev=None, stream=None):
         """mvrt_svo_surface_exterior_masks into a caller's device array of numberOfVoxels bytes (None = counts only); returns (nFaces, nHidden): the exterior
         faces and the faces of surface_masks that look into an enclosed cell.  The octree is not modified."""
-        nf, nh = C.c_uint64(0), C.c_uint64(0)
-        _check(lib().mvrt_svo_surface_exterior_masks(self._h, _dev_ptr(masks_dev), C.byref(nf), C.byref(nh), stream))
-        return nf.value, nh.value
+        return self._counts(lib().mvrt_svo_surface_exterior_masks, (_dev_ptr(masks_dev),), 2, stream)
 
     def surface_exterior_masks(self, stream=None):
         """mvrt_svo_surface_exterior_masks -> (masks (numberOfVoxels,) uint8 in vIndex order, nFaces, nHidden): the masks of surface_masks without the bits that
@@ -871,13 +806,11 @@ class IntersectorOctreeGPU:
     def surface_quads_device(self, face_capacity=0, faceVoxel=None, faceDir=None, positions=None, stream=None, *, masks=None):
         """mvrt_svo_surface_quads into caller device arrays (any may be None; all None = the sizing call); returns nFaces.  On MvrtError nothing was written.
         masks (numberOfVoxels uint8, numpy or device): mvrt_svo_surface_quads_masked, the faces are the set bits 0..5 of the masks as given."""
-        n = C.c_uint64(0)
+        args = (int(face_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(positions))
         if masks is None:
-            _check(lib().mvrt_svo_surface_quads(self._h, int(face_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(positions), C.byref(n), stream))
-        else:
-            m = self._given_masks(masks)
-            _check(lib().mvrt_svo_surface_quads_masked(self._h, _dev_ptr(m), int(face_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(positions), C.byref(n), stream))
-        return n.value
+            return self._counts(lib().mvrt_svo_surface_quads, args, 1, stream)
+        m = self._given_masks(masks)
+        return self._counts(lib().mvrt_svo_surface_quads_masked, (_dev_ptr(m),) + args, 1, stream)
 
     def surface_quads(self, stream=None, *, masks=None):
         """the exposed faces as unwelded quads: {faceVoxel (n,) uint32 vIndex, faceDir (n,) uint8, positions (n, 4, 3) float32}, faces by vIndex then direction;
@@ -885,21 +818,17 @@ class IntersectorOctreeGPU:
         masks = None if masks is None else self._given_masks(masks)
         n = self.surface_quads_device(stream=stream, masks=masks)
         fv, fd, pos = DeviceArray(n, np.uint32), DeviceArray(n, np.uint8), DeviceArray((n, 4, 3), np.float32)
-        self.surface_quads_device(n, fv, fd, pos, stream, masks=masks)
+        self.surface_quads_device(n, fv, fd, pos, stream, masks=masks)  # (the surface listings make the filling call at a count of 0 too)
         return {"faceVoxel": fv.to_host(), "faceDir": fd.to_host(), "positions": pos.to_host()}
 
     def surface_mesh_device(self, face_capacity=0, vertex_capacity=0, faceVoxel=None, faceDir=None, indices=None, vertices=None, stream=None, *, masks=None):
         """mvrt_svo_surface_mesh into caller device arrays (any may be None; all None = the sizing call); returns (nFaces, nVertices).
         masks: mvrt_svo_surface_mesh_masked (surface_quads_device)"""
-        nf, nv = C.c_uint64(0), C.c_uint64(0)
+        args = (int(face_capacity), int(vertex_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(indices), _dev_ptr(vertices))
         if masks is None:
-            _check(lib().mvrt_svo_surface_mesh(self._h, int(face_capacity), int(vertex_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(indices), _dev_ptr(vertices),
-                                               C.byref(nf), C.byref(nv), stream))
-        else:
-            m = self._given_masks(masks)
-            _check(lib().mvrt_svo_surface_mesh_masked(self._h, _dev_ptr(m), int(face_capacity), int(vertex_capacity), _dev_ptr(faceVoxel), _dev_ptr(faceDir), _dev_ptr(indices),
-                                                      _dev_ptr(vertices), C.byref(nf), C.byref(nv), stream))
-        return nf.value, nv.value
+            return self._counts(lib().mvrt_svo_surface_mesh, args, 2, stream)
+        m = self._given_masks(masks)
+        return self._counts(lib().mvrt_svo_surface_mesh_masked, (_dev_ptr(m),) + args, 2, stream)
 
     def surface_mesh(self, stream=None, *, masks=None):
         """the exposed faces over shared vertices: {vertices (m, 3) float32 in corner-key order, indices (n, 4) uint32, faceVoxel (n,), faceDir (n,)};
@@ -915,15 +844,11 @@ class IntersectorOctreeGPU:
         """mvrt_svo_surface_merged into caller device arrays (any may be None; all None = the sizing call); returns (nFaces, nRects, nVertices).
         flags: SURFACE_MERGE_ANY_ATTRIBUTE | SURFACE_MERGE_WELD; indices / vertices need the weld flag.  On MvrtError nothing was written.
         masks: mvrt_svo_surface_merged_masked (surface_quads_device)"""
-        nf, nr, nv = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        out = [_dev_ptr(a) for a in (rectVoxel, rectDir, rectSize, positions, indices, vertices)]
+        args = (int(flags), int(rect_capacity), int(vertex_capacity)) + tuple(_dev_ptr(a) for a in (rectVoxel, rectDir, rectSize, positions, indices, vertices))
         if masks is None:
-            _check(lib().mvrt_svo_surface_merged(self._h, int(flags), int(rect_capacity), int(vertex_capacity), *out, C.byref(nf), C.byref(nr), C.byref(nv), stream))
-        else:
-            m = self._given_masks(masks)
-            _check(lib().mvrt_svo_surface_merged_masked(self._h, _dev_ptr(m), int(flags), int(rect_capacity), int(vertex_capacity), *out, C.byref(nf), C.byref(nr), C.byref(nv),
-                                                        stream))
-        return nf.value, nr.value, nv.value
+            return self._counts(lib().mvrt_svo_surface_merged, args, 3, stream)
+        m = self._given_masks(masks)
+        return self._counts(lib().mvrt_svo_surface_merged_masked, (_dev_ptr(m),) + args, 3, stream)
 
     def surface_merged(self, flags=0, stream=None, *, masks=None):
         """the exposed faces merged into rectangles, ascending (direction, plane, u0, v0): {nFaces, rectVoxel (n,) uint32 the anchor's vIndex, rectDir (n,) uint8,

@@ -10,6 +10,27 @@ GOLDEN = os.path.join(HERE, "golden")
 f32 = np.float32
 
 
+def compile_usage(tmp_path, name, missing="skip"):
+    """tests/cpp/<name>.cpp built with g++ against the header-only mirrors in include/ and linked with the library, as an application would be -> (exe, libdir).
+    missing: without a g++ "skip" the test or "fail" it; None = do not look, run "g++" as it is."""
+    import shutil
+    import subprocess
+
+    import pytest
+
+    import massivevoxelraytracing_amd as mv
+    gxx = shutil.which("g++") if missing else "g++"
+    if gxx is None and missing == "skip":
+        pytest.skip("no g++")
+    assert gxx, "no g++"
+    root = os.path.dirname(HERE)
+    exe = tmp_path / name
+    libdir = os.path.dirname(mv.LIB_PATH)
+    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", name + ".cpp"), "-o", str(exe),
+                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    return exe, libdir
+
+
 def golden():
     with open(os.path.join(GOLDEN, "survey_appendix_a.json")) as f:
         return json.load(f)

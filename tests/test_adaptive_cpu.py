@@ -4,12 +4,12 @@ points exist in every layer."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import adaptive_expected as X
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
 
@@ -126,11 +126,6 @@ def test_entry_points_exist_in_every_layer(tmp_path):
     assert "se > threshold * max( m1, lumFloor )" in text  # the formula is written out in the header
     for m in ("set_sample_mask", "active_pixels", "error_mask"):
         assert callable(getattr(mv.PathTracer, m))
-    gxx = shutil.which("g++")
-    assert gxx, "no g++"
-    exe = tmp_path / "adaptive_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "adaptive_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "adaptive_usage", missing="fail")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"refused 1 1 active 0" in out

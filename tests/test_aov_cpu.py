@@ -3,12 +3,12 @@ three entry points exist in the header, the library, the Python mirror and the C
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import aov_expected as A
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
 
@@ -63,13 +63,7 @@ def test_feature_buffer_entry_points_exist_in_every_layer(tmp_path):
     assert l.mvrt_pt_set_aovs(None, 1) != 0
     assert l.mvrt_pt_aov_dev(None, 0) is None and b"null" in l.mvrt_last_error()
     assert l.mvrt_pt_read_aov(None, None, 0, None) != 0
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "aov_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "aov_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "aov_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"MVRT_AOV_ALBEDO 0 MVRT_AOV_NORMAL_DEPTH 1" in out
 

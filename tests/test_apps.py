@@ -8,6 +8,7 @@ import zlib
 import numpy as np
 import pytest
 
+import common
 from common import GOLDEN, bunny_tris
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -211,13 +212,7 @@ def test_cpp_mirror_frame_buffer_members(tmp_path):
     after resolve(); m_steps counts step() calls.  tests/cpp/mirror_usage.cpp does exactly that on the header-only mirror."""
     import shutil as sh
     import massivevoxelraytracing_amd as mv
-    gxx = sh.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "mirror_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "mirror_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "mirror_usage")
     sh.copy(os.path.join(GOLDEN, "monks_forest_s.hdr"), tmp_path / "monks_forest_s.hdr")
     out = subprocess.check_output([str(exe), "run"], cwd=tmp_path, timeout=300).decode()
     assert "steps 1 " in out

@@ -1,11 +1,11 @@
 """The component interface without a GPU: the header, the Python table and the C++ mirror declare the two calls, and tests/cpp/components_usage.cpp, which pins
 their C signatures, compiles and links against the library (it is run on a GPU by tests/test_gpu_components_app.py)."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
+import common
 import massivevoxelraytracing_amd as mv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,14 +13,7 @@ CALLS = ("mvrt_svo_components", "mvrt_svo_keep_components")
 
 
 def compile_usage(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "components_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "components_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
-    return exe, libdir
+    return common.compile_usage(tmp_path, "components_usage")
 
 
 def test_header_python_and_mirror_declare_the_interface():

@@ -3,12 +3,12 @@ quality of the filter the contract defines (on oracle renders alone), and the ho
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import aov_expected as A
 import denoise_expected as D
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
@@ -225,11 +225,6 @@ def test_entry_points_exist_in_every_layer(tmp_path):
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     assert re.search(r"#define\s+MVRT_DENOISE_NO_DEMODULATION\s+1u?\b", code)
     assert "mvrt_exp( -e )" in text and "Iteration i = 0 .. iterations - 1" in text  # the filter is written out in the header
-    gxx = shutil.which("g++")
-    assert gxx, "no g++"
-    exe = tmp_path / "denoise_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "denoise_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "denoise_usage", missing="fail")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"iterations 5 structBytes 40 scratch %d" % mv.denoise_scratch_bytes(64, 36) in out

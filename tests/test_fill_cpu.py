@@ -3,12 +3,12 @@ answer is known by hand, against scipy's labelling where scipy is installed, the
 the two calls, and the C++ mirror's new methods."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import fill_expected as F
 import massivevoxelraytracing_amd as mv
 import surface_expected as S
@@ -106,13 +106,6 @@ def test_header_python_and_mirror_declare_the_interface():
 
 
 def test_cpp_mirror_fill_methods_compile_and_link(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "fill_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    cmd = [gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "fill_usage.cpp"), "-o", str(exe),
-           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"]
-    subprocess.check_call(cmd)
+    exe, libdir = common.compile_usage(tmp_path, "fill_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out

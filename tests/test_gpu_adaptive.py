@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import common
 import adaptive_expected as X
 import denoise_expected as D
 from common import GOLDEN, bunny_tris, hdr_bytes, position_colors, probe_camera
@@ -365,12 +366,7 @@ def test_denoise_after_masked_steps(mv, O, scene, hdr):
 def test_cpp_mirror_adaptive_members(tmp_path):
     """tests/cpp/adaptive_usage.cpp on the header-only mirror: errorMask, setSampleMask, activePixels"""
     import massivevoxelraytracing_amd as mv
-    gxx = shutil.which("g++")
-    assert gxx, "no g++"
-    exe = tmp_path / "adaptive_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "adaptive_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "adaptive_usage", missing="fail")
     shutil.copy(os.path.join(GOLDEN, "monks_forest_s.hdr"), tmp_path / "monks_forest_s.hdr")
     out = subprocess.check_output([str(exe), "run"], cwd=tmp_path, timeout=300).decode()
     print(out)

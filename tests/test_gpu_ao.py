@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import common
 import surface_expected as S
 from common import bunny_tris, position_colors
 
@@ -200,10 +201,7 @@ def test_uploaded_and_empty_handles_are_refused(mv, O):
 
 
 def test_cpp_mirror_range_methods_run(tmp_path, mv):
-    libdir = os.path.dirname(mv.LIB_PATH)
-    exe = tmp_path / "range_usage"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "range_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "range_usage", missing=None)
     r = subprocess.run(["timeout", "-k", "10", "120", str(exe), "run"], capture_output=True, text=True)
     assert r.returncode == 0 and "faces 12 nearAll 12 farLess 2 t 3 3.40282347e+38" in r.stdout, (r.returncode, r.stdout, r.stderr)
 

@@ -6,6 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import common
 import aov_expected as A
 from common import GOLDEN, bunny_tris, hdr_bytes, position_colors, probe_camera
 
@@ -389,14 +390,8 @@ def test_cpp_mirror_feature_buffer_members(tmp_path):
     join == mvrt_pt_read_aov, views gone after setAOVs( false ) and after setTile"""
     import shutil
     import massivevoxelraytracing_amd as mv
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "aov_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "aov_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "aov_usage")
     shutil.copy(os.path.join(GOLDEN, "monks_forest_s.hdr"), tmp_path / "monks_forest_s.hdr")
     out = subprocess.check_output([str(exe), "run"], cwd=tmp_path, timeout=300).decode()
     print(out)

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import common
 import aov_expected as A
 import denoise_expected as D
 from common import GOLDEN, bunny_tris, hdr_bytes, position_colors, probe_camera
@@ -370,12 +371,7 @@ def test_a_failed_allocation_of_denoise_leaves_the_frame_and_no_denoised_buffer(
 def test_cpp_mirror_denoise_members(tmp_path):
     """tests/cpp/denoise_usage.cpp on the header-only mirror: setMoments, denoise, m_momentsF32 / m_denoisedF32 re-pointed by everything that reallocates"""
     import massivevoxelraytracing_amd as mv
-    gxx = shutil.which("g++")
-    assert gxx, "no g++"
-    exe = tmp_path / "denoise_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "denoise_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "denoise_usage", missing="fail")
     shutil.copy(os.path.join(GOLDEN, "monks_forest_s.hdr"), tmp_path / "monks_forest_s.hdr")
     out = subprocess.check_output([str(exe), "run"], cwd=tmp_path, timeout=300).decode()
     print(out)

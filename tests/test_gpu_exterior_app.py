@@ -2,12 +2,12 @@
 a filled voxel owns no face, so the faces, their order, the welded vertices and the colours are the same; the report line names the faces before and after.
 And the C++ mirror's exterior and masked methods, compiled and run (tests/cpp/exterior_usage.cpp)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import surface_expected as S
 from common import bunny_tris
 
@@ -63,13 +63,7 @@ def test_exterior_with_fill_is_refused(tmp_path, bunny_obj):
 
 def test_cpp_mirror_runs(tmp_path):
     import massivevoxelraytracing_amd as mv
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "exterior_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "exterior_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "exterior_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     assert "plain 120 exterior 96 hidden 24 counts 96 24 quads 96 mesh 96 vertices 98 covered 96 rects 6 corners 8 same 1" in out

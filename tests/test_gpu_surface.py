@@ -5,13 +5,13 @@ the calls (capacities, NULL outputs, refusals).  The weld limit (4 * nFaces >= 2
 covered by reading: reaching it takes a surface of 2^30 faces."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import common
 import surface_expected as S
 from common import bunny_tris
 
@@ -318,13 +318,7 @@ def test_the_handle_is_not_modified(mv, small):
 
 # ---- upper layers ---------------------------------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror_runs(tmp_path, mv):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "surface_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "surface_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "surface_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     assert "voxels 8 masks 8 first 37 faces 24 counted 24 quads 24 vertices 26 indices 96 same 1" in out
 

@@ -5,12 +5,12 @@ the contract of the call (capacities, NULL outputs, refusals).  The model's attr
 (4 * nRects >= 2^32) is a host comparison in surfaceMerged (csrc/kernels_surface.hip) and is covered by reading: reaching it takes 2^30 rectangles."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import merge_expected as M
 import surface_expected as S
 from common import bunny_tris
@@ -365,13 +365,7 @@ def test_the_handle_is_not_modified(mv, small):
 
 # ---- upper layers ---------------------------------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror_runs(tmp_path, mv):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "surface_merge_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "surface_merge_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "surface_merge_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     assert "faces 24 rects 6 vertices 8 sized 24 6 8 same 1 two 1" in out
 

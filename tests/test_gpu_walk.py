@@ -4,12 +4,12 @@ frontier level), one-voxel chains, the empty octree, several thousand parents wi
 prefix at 21 levels; every legal upload shape of tests/upload_shapes.py, both flavours; hand-made trees whose last frontier is 255, 256 and 257 parents, and
 one with a whole group of 256 childless parents between two groups with children."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import deep_scenes as D
 import surface_expected as S
 import upload_shapes as U
@@ -332,12 +332,6 @@ def test_frontiers_at_the_group_seams(mv, O, name, emb):
 
 # ---- upper layers -----------------------------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror_runs(tmp_path, mv):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "walk_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "walk_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    exe, libdir = common.compile_usage(tmp_path, "walk_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     assert "paths 4 counted 4 walked 1 voxels 4 emission 1 same 1 faces 24" in out

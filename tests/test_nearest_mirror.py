@@ -2,12 +2,12 @@
 their C signatures, compiles and links against the library -- without a GPU, where it also checks the refusals the host makes before any GPU work.  On a GPU the
 program is run, and every line it prints is compared with what the Python wrapper and the model of tests/nearest_expected.py give for the same set."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import massivevoxelraytracing_amd as mv
 import nearest_expected as N
 
@@ -16,14 +16,7 @@ CALLS = ("mvrt_svo_enclosed_nearest", "mvrt_svo_fill_enclosed_nearest", "mvrt_te
 
 
 def compile_usage(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "nearest_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "nearest_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
-    return exe, libdir
+    return common.compile_usage(tmp_path, "nearest_usage")
 
 
 def test_header_python_and_mirror_declare_the_interface():

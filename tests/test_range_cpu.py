@@ -2,12 +2,12 @@
 on the Hammersley points, the refusals that happen on the host before any GPU call, and the three layers of the interface (header, binding, C++ mirror)."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import massivevoxelraytracing_amd as mv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -82,14 +82,7 @@ def test_interface_is_declared_in_every_layer():
 
 
 def test_cpp_mirror_range_methods_compile_and_link(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "range_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    cmd = [gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "range_usage.cpp"), "-o", str(exe),
-           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"]
-    subprocess.check_call(cmd)
+    exe, libdir = common.compile_usage(tmp_path, "range_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out and b"directions 24" in out
     first = np.array(out.split(b"first ")[1].split(b")")[0].split(), np.float32)

@@ -3,12 +3,12 @@ the layout of mvrt_cell_transform, compiles and links against the library -- wit
 On a GPU the program is run, and every line it prints is compared with what the Python wrapper and the model of tests/resample_expected.py give for the same set."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import massivevoxelraytracing_amd as mv
 import resample_expected as E
 
@@ -17,14 +17,7 @@ CALLS = ("mvrt_svo_resample_voxels", "mvrt_svo_resample", "mvrt_cell_transform_f
 
 
 def compile_usage(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "resample_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "resample_usage.cpp"), "-o", str(exe),
-                           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
-    return exe, libdir
+    return common.compile_usage(tmp_path, "resample_usage")
 
 
 def test_header_python_and_mirror_declare_the_interface():

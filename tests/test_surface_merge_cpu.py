@@ -1,12 +1,12 @@
 """The numpy model of the merged surface (tests/merge_expected.py) against an independent brute force and hand-checked cases, the two invariants of the rule
 (include/mvrt.h, mvrt_svo_surface_merged) on every case, and the layers of the interface (header, binding, C++ mirror) -- all without a GPU."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import massivevoxelraytracing_amd as mv
 import merge_expected as M
 import surface_expected as S
@@ -195,13 +195,6 @@ def test_refusals_need_no_gpu():
 
 
 def test_cpp_mirror_merge_methods_compile_and_link(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "surface_merge_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    cmd = [gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "surface_merge_usage.cpp"), "-o", str(exe),
-           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"]
-    subprocess.check_call(cmd)
+    exe, libdir = common.compile_usage(tmp_path, "surface_merge_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out

@@ -2,12 +2,12 @@
 checks fail with the intended messages before any HIP call, and the C++ mirror's new methods compile and link."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import massivevoxelraytracing_amd as mv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,13 +72,6 @@ def test_header_declares_the_voxel_list_interface():
 
 
 def test_cpp_mirror_voxel_methods_compile_and_link(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "voxel_edit_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    cmd = [gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "voxel_edit_usage.cpp"), "-o", str(exe),
-           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"]
-    subprocess.check_call(cmd)
+    exe, libdir = common.compile_usage(tmp_path, "voxel_edit_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out

@@ -2,12 +2,12 @@
 upload-shape generators (tests/upload_shapes.py) whose effect on paths and sums is known, and the oracle's traversal, whose hit vIndex is the sum the
 walk must report.  Also compiles the C++ mirror's usage program (run on a GPU by tests/test_gpu_walk.py)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import common
 import deep_scenes as D
 import upload_shapes as U
 import walk_expected as W
@@ -97,13 +97,6 @@ def test_vindex_is_what_the_oracle_reports_for_a_hit(O, random7, shape, emb):
 
 
 def test_cpp_mirror_walk_methods_compile_and_link(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "walk_usage"
-    libdir = os.path.dirname(mv.LIB_PATH)
-    cmd = [gxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "walk_usage.cpp"), "-o", str(exe),
-           "-L", libdir, "-l:libmvrt_hip.so", "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"]
-    subprocess.check_call(cmd)
+    exe, libdir = common.compile_usage(tmp_path, "walk_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out
