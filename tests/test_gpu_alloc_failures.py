@@ -7,6 +7,7 @@ import gc
 import numpy as np
 import pytest
 
+from alloc_sweep import mv  # noqa: F401 (the fixture)
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
 
 pytestmark = pytest.mark.gpu
@@ -19,13 +20,6 @@ INFO_FIELDS = ("numberOfNodes", "numberOfVoxels", "dps", "emissionScale", "hasEm
 def O():
     from oracle import oracle
     return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")

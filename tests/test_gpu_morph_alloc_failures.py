@@ -6,17 +6,11 @@ import numpy as np
 import pytest
 
 import morph_expected as M
+from alloc_sweep import filled, mv, same, sweep_edit, sweep_reader  # noqa: F401 (mv: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -33,15 +27,6 @@ def build(svo, voxels):
     svo.build_voxels(voxels[0], voxels[1], origin=LOWER, dps=DPS, gridRes=RES)
 
 
-def filled(mv, shape, dtype):
-    host = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(host), host
-
-
-def same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
 def test_each_allocation_of_the_listings_fails_in_turn(mv, voxels):
     svo = mv.IntersectorOctreeGPU()
     build(svo, voxels)
@@ -51,26 +36,12 @@ def test_each_allocation_of_the_listings_fails_in_turn(mv, voxels):
     n, m = len(want["xyz"]), len(gone)
     assert n > 100 and m > 100
     (dx, hx), (da, ha), (dc, hc), (dv, hv) = filled(mv, (n, 3), np.uint32), filled(mv, (n, 8), np.uint8), filled(mv, n, np.uint32), filled(mv, m, np.uint32)
-    octree, info = svo.download(want_morton=True), bytes(svo.info())
     calls = ((lambda: svo.dilation_cells_device(M.CUBE, n, dx, da, dc), n, 9, ((dx, hx), (da, ha), (dc, hc))),  # masks, offsets, scan storage, pairs twice, sort storage, ranks, ...
              (lambda: svo.erosion_voxels_device(M.CUBE, m, dv), m, 3, ((dv, hv),)))  # masks, offsets, scan storage
     for call, count, least, arrays in calls:
-        state = mv.allocation_state()
-        assert call() == count
-        total = mv.allocation_state()[2] - state[2]
-        assert total >= least and mv.allocation_state()[:2] == state[:2]
-        for d, h in arrays:  # back to the canary for the sweep
-            mv.lib().mvrt_memcpy_h2d(d.ptr, h.ctypes.data, d.nbytes, None)
-        for k in range(1, total + 1):
-            mv.set_test_fail_allocation(k)
-            with pytest.raises(mv.MvrtError, match="mvrt_test_fail_allocation"):
-                call()
-            assert mv.lib().mvrt_test_fail_allocation(0) == 0
-            assert mv.allocation_state()[:2] == state[:2], k  # nothing leaked
-            assert bytes(svo.info()) == info and same(svo.download(want_morton=True), octree), k
-            assert all(np.array_equal(d.to_host(), h) for d, h in arrays), k  # the caller's arrays are written last, behind every allocation
+        total, result = sweep_reader(mv, call, [svo], arrays, least)
         print("listing: allocations failed in turn:", total)
-        assert call() == count
+        assert result == count
     assert np.array_equal(dx.to_host(), want["xyz"]) and np.array_equal(da.to_host(), want["attribs"]) and np.array_equal(dc.to_host(), want["count"])
     assert np.array_equal(dv.to_host(), gone)
 
@@ -80,35 +51,12 @@ def test_each_allocation_of_an_in_place_call_fails_in_turn(mv, voxels, op, eleme
     base = mv.allocation_state()[:2]
     svo = mv.IntersectorOctreeGPU()
     build(svo, voxels)
-    held = tuple(a - b for a, b in zip(mv.allocation_state()[:2], base))
-    octree, info = svo.download(want_morton=True), bytes(svo.info())
     x0, a0 = svo.read_voxels()
     wx, wa = M.morph(op, x0, a0, RES, element, steps)
-    before = mv.allocation_state()[2]
-    assert getattr(svo, op)(element, steps) == abs(len(wx) - len(x0)) > 0
-    total = mv.allocation_state()[2] - before
-    expected = svo.download(want_morton=True)
-    assert total >= 10 and same(svo.read_voxels(), (wx, wa))
-    ends = []
-    for k in range(1, total + 1):
-        build(svo, voxels)
-        assert bytes(svo.info()) == info and tuple(a - b for a, b in zip(mv.allocation_state()[:2], base)) == held
-        mv.set_test_fail_allocation(k)
-        with pytest.raises(mv.MvrtError, match="mvrt_test_fail_allocation"):
-            getattr(svo, op)(element, steps)
-        assert mv.lib().mvrt_test_fail_allocation(0) == 0
-        live = tuple(a - b for a, b in zip(mv.allocation_state()[:2], base))
-        if svo.info().numberOfNodes == 0:  # behind the adoption: an empty handle that every reader refuses
-            ends.append("empty")
-            assert live == (0, 0), k
-            with pytest.raises(mv.MvrtError, match="no octree"):
-                svo.dilation_cells_device()
-        else:
-            ends.append("old")
-            assert live == held, k
-            assert bytes(svo.info()) == info and same(svo.download(want_morton=True), octree), k
-    print(op, "allocations failed in turn:", total, "-- old octree kept by the first", ends.count("old"))
-    assert ends == sorted(ends, reverse=True) and ends[0] == "old" and ends[-1] == "empty"  # the old octree up to one point of the call, none from there on
-    build(svo, voxels)
-    getattr(svo, op)(element, steps)
-    assert same(svo.download(want_morton=True), expected)
+
+    def call():
+        assert getattr(svo, op)(element, steps) == abs(len(wx) - len(x0)) > 0
+
+    total, kept = sweep_edit(mv, call, svo, lambda: build(svo, voxels), base, svo.dilation_cells_device, 10)
+    print(op, "allocations failed in turn:", total, "-- old octree kept by the first", kept)
+    assert same(svo.read_voxels(), (wx, wa))

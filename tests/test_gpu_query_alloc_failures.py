@@ -6,17 +6,11 @@ import numpy as np
 import pytest
 
 import query_expected as Q
+from alloc_sweep import filled, mv, same, sweep_reader  # noqa: F401 (mv: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -27,35 +21,10 @@ def sets():
     return a, rng.integers(0, 256, (len(a), 8), dtype=np.uint8), b, rng.integers(0, 256, (len(b), 8), dtype=np.uint8)
 
 
-def build(mv, xyz, at):
-    svo = mv.IntersectorOctreeGPU()
+def build(mv, xyz, at, svo=None):
+    svo = mv.IntersectorOctreeGPU() if svo is None else svo
     svo.build_voxels(xyz, at, origin=LOWER, dps=DPS, gridRes=RES)
     return svo
-
-
-def filled(mv, shape, dtype):
-    host = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(host), host
-
-
-def sweep(mv, call, handles, arrays, least):
-    """call() once for the count of its allocations, then with each of them failing in turn"""
-    octrees, infos, state = [h.download(want_morton=True) for h in handles], [bytes(h.info()) for h in handles], mv.allocation_state()
-    call()
-    total = mv.allocation_state()[2] - state[2]
-    assert total >= least and mv.allocation_state()[:2] == state[:2]
-    for d, h in arrays:  # back to the canary for the sweep
-        mv.lib().mvrt_memcpy_h2d(d.ptr, h.ctypes.data, d.nbytes, None)
-    for k in range(1, total + 1):
-        mv.set_test_fail_allocation(k)
-        with pytest.raises(mv.MvrtError, match="mvrt_test_fail_allocation"):
-            call()
-        assert mv.lib().mvrt_test_fail_allocation(0) == 0
-        assert mv.allocation_state()[:2] == state[:2], k  # nothing leaked
-        for h, o, i in zip(handles, octrees, infos):
-            assert bytes(h.info()) == i and all(np.array_equal(x, y) for x, y in zip(h.download(want_morton=True), o)), k
-        assert all(np.array_equal(d.to_host(), h) for d, h in arrays), k  # the caller's arrays are written last, behind every allocation
-    return total
 
 
 def test_each_allocation_of_the_queries_fails_in_turn(mv, sets):
@@ -64,9 +33,8 @@ def test_each_allocation_of_the_queries_fails_in_turn(mv, sets):
     q = np.random.default_rng(2).integers(-5, RES + 5, (1000, 3)).astype(np.int32)
     qd = mv.DeviceArray.from_host(q)
     d2, near, at = filled(mv, len(q), np.uint64), filled(mv, len(q), np.uint32), filled(mv, (len(q), 8), np.uint8)
-    total = sweep(mv, lambda: svo.nearest_voxels_device(len(q), qd, dist2=d2[0], nearest=near[0], attribs=at[0]), [svo], [d2, near, at], 1)
+    total, _ = sweep_reader(mv, lambda: svo.nearest_voxels_device(len(q), qd, dist2=d2[0], nearest=near[0], attribs=at[0]), [svo], [d2, near, at], 1)
     print("nearest_voxels: allocations failed in turn:", total)
-    svo.nearest_voxels_device(len(q), qd, dist2=d2[0], nearest=near[0], attribs=at[0])
     want = Q.nearest_voxels(xa, aa, q)
     assert np.array_equal(d2[0].to_host(), want["dist2"]) and np.array_equal(near[0].to_host(), want["nearest"]) and np.array_equal(at[0].to_host(), want["attribs"])
 
@@ -76,8 +44,8 @@ def test_each_allocation_of_the_two_set_call_fails_in_turn(mv, sets):
     a, b = build(mv, xa, aa), build(mv, xb, ab)
     n = a.info().numberOfVoxels
     d2, near = filled(mv, n, np.uint64), filled(mv, n, np.uint32)
-    total = sweep(mv, lambda: a.nearest_between_device(b, (1, 2, -1), capacity=n, dist2=d2[0], nearest=near[0]), [a, b], [d2, near], 1)
-    summary = sweep(mv, lambda: a.nearest_between_device(b, (1, 2, -1)), [a, b], [d2, near], 2)  # the summary call keeps the distances in scratch
+    total, _ = sweep_reader(mv, lambda: a.nearest_between_device(b, (1, 2, -1), capacity=n, dist2=d2[0], nearest=near[0]), [a, b], [d2, near], 1)
+    summary, _ = sweep_reader(mv, lambda: a.nearest_between_device(b, (1, 2, -1)), [a, b], [d2, near], 2)  # the summary call keeps the distances in scratch
     print("nearest_between: allocations failed in turn:", total, "summary call:", summary)
     got = a.nearest_between_device(b, (1, 2, -1), capacity=n, dist2=d2[0], nearest=near[0])
     want = Q.nearest_between(xa, xb, (1, 2, -1))
@@ -93,20 +61,8 @@ def test_each_allocation_of_the_transfer_fails_in_turn(mv, sets):
     twin = build(mv, xa, aa)
     twin.edit_voxels(x[taken].astype(np.uint32), new[taken])
     expected = twin.download(want_morton=True)
-    probe = build(mv, xa, aa)
-    before = mv.allocation_state()[2]
-    assert probe.transfer_attributes(src, (0, 1, 0), 3) == (changed, int((~taken).sum()))
-    total = mv.allocation_state()[2] - before
-    assert total >= 15 and all(np.array_equal(p, e) for p, e in zip(probe.download(want_morton=True), expected))  # the walk's 5, the list's 4, the edit's own
     dst = build(mv, xa, aa)
-    octree, info, state = dst.download(want_morton=True), bytes(dst.info()), mv.allocation_state()[:2]
-    for k in range(1, total + 1):
-        mv.set_test_fail_allocation(k)
-        with pytest.raises(mv.MvrtError, match="mvrt_test_fail_allocation"):
-            dst.transfer_attributes(src, (0, 1, 0), 3)
-        assert mv.lib().mvrt_test_fail_allocation(0) == 0
-        assert mv.allocation_state()[:2] == state, k  # nothing leaked
-        assert bytes(dst.info()) == info and all(np.array_equal(x_, y) for x_, y in zip(dst.download(want_morton=True), octree)), k  # nothing was written
+    # the walk's 5, the list's 4, the edit's own
+    total, result = sweep_reader(mv, lambda: dst.transfer_attributes(src, (0, 1, 0), 3), [dst, src], [], 15, reset=lambda: build(mv, xa, aa, dst))
     print("transfer_attributes: allocations failed in turn:", total)
-    assert dst.transfer_attributes(src, (0, 1, 0), 3) == (changed, int((~taken).sum()))
-    assert all(np.array_equal(p, e) for p, e in zip(dst.download(want_morton=True), expected))
+    assert result == (changed, int((~taken).sum())) and same(dst.download(want_morton=True), expected)

@@ -5,16 +5,11 @@ the hook then gives the result of an undisturbed one.  mvrt_trace_batch_range al
 import numpy as np
 import pytest
 
+from alloc_sweep import filled, mv  # noqa: F401 (mv: the fixture)
+
 pytestmark = pytest.mark.gpu
 
 LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def test_each_allocation_fails_in_turn(mv):
@@ -24,8 +19,7 @@ def test_each_allocation_fails_in_turn(mv):
     q = svo.surface_quads()
     n = len(q["faceVoxel"])
     fv, fd = mv.DeviceArray.from_host(q["faceVoxel"]), mv.DeviceArray.from_host(q["faceDir"])
-    canary = np.full(n, 0x5A5A, np.uint16)
-    out = mv.DeviceArray.from_host(canary)
+    out, canary = filled(mv, n, np.uint16)
     radius = np.float32(4) * DPS
     call = lambda: svo.surface_ao_device(n, fv, fd, 64, radius, out)
     ro = (LOWER + rng.random((2000, 3)) * DPS * RES).astype(np.float32)

@@ -7,17 +7,11 @@ import pytest
 
 import merge_expected as M
 import surface_expected as S
+from alloc_sweep import bits, filled, mv, sweep_reader  # noqa: F401 (mv: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -32,15 +26,6 @@ def scene(mv):
     return svo, xyz, attrs
 
 
-def filled(mv, shape, dtype):
-    host = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(host), host
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
 @pytest.mark.parametrize("flags", [0, M.WELD])
 def test_each_allocation_fails_in_turn(mv, scene, flags):
     svo, xyz, attrs = scene
@@ -51,30 +36,9 @@ def test_each_allocation_fails_in_turn(mv, scene, flags):
         shapes.update(indices=((n, 4), np.uint32), vertices=((m, 3), np.float32))
     outs = {k: filled(mv, s, t) for k, (s, t) in shapes.items()}
     d = {k: v[0] for k, v in outs.items()}
-
-    def call():
-        return svo.surface_merged_device(flags, n, m, **d)
-
-    octree = svo.download(want_morton=True)
-    info = bytes(svo.info())
-    state = mv.allocation_state()
-    assert call() == (want["nFaces"], n, m)
-    total = mv.allocation_state()[2] - state[2]
     # the counter and the masks; per direction offsets, two sorts, two head scans and the rectangles, each with library storage; + keys, values (twice), ranks
-    assert total >= 2 + 6 * 16 + (7 if flags else 0)
-    assert mv.allocation_state()[:2] == state[:2]
-    for k in d:  # back to the canary for the sweep
-        mv.lib().mvrt_memcpy_h2d(d[k].ptr, outs[k][1].ctypes.data, d[k].nbytes, None)
-    for k in range(1, total + 1):
-        mv.set_test_fail_allocation(k)
-        with pytest.raises(mv.MvrtError, match="mvrt_test_fail_allocation"):
-            call()
-        assert mv.lib().mvrt_test_fail_allocation(0) == 0
-        assert mv.allocation_state()[:2] == state[:2], k  # nothing leaked
-        assert bytes(svo.info()) == info and all(np.array_equal(a, b) for a, b in zip(svo.download(want_morton=True), octree)), k
-        for name in d:  # the caller's arrays are written last, behind every allocation
-            assert np.array_equal(bits(d[name].to_host()), bits(outs[name][1])), (k, name)
+    total, result = sweep_reader(mv, lambda: svo.surface_merged_device(flags, n, m, **d), [svo], list(outs.values()), 2 + 6 * 16 + (7 if flags else 0))
     print("flags", flags, "allocations failed in turn:", total)
-    call()
+    assert result == (want["nFaces"], n, m)
     for name in d:
         assert np.array_equal(bits(d[name].to_host()), bits(want[name])), name

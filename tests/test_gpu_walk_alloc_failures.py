@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import walk_expected as W
+from alloc_sweep import bits, filled, mv, sweep_reader  # noqa: F401 (mv: the fixture)
 from test_gpu_parity import random_rays
 from test_gpu_upload_shapes import oracle_scene, shapes, upload, voxel_set
 from test_gpu_voxel_edit import assert_svo
@@ -21,24 +22,8 @@ def O():
 
 
 @pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
 def base():
     return voxel_set("random7", 7, 20_000, 2_000, 7)
-
-
-def filled(mv, shape, dtype):
-    host = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(host), host
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
 
 
 @pytest.mark.parametrize("emb", [True, False])
@@ -51,31 +36,15 @@ def test_each_allocation_of_a_walk_fails_in_turn(mv, O, base, emb):
     want = {"xyz": xyz, "vIndex": vi, "attribs": sc.attrs[vi]}
     outs = {"xyz": filled(mv, (n, 3), np.uint32), "vIndex": filled(mv, n, np.uint32), "attribs": filled(mv, (n, 8), np.uint8)}
     d = {k: v[0] for k, v in outs.items()}
-    call = lambda: svo.walk_voxels_device(n, d["xyz"], d["vIndex"], d["attribs"])
     ro, rd = random_rays(sc, 6000, 3)
     traced = svo.intersect(ro, rd, want_descents=True)
-    octree = svo.download()
-    info = bytes(svo.info())
-    state = mv.allocation_state()
-    assert call() == n
-    total = mv.allocation_state()[2] - state[2]
-    assert total >= 3 + 2 * 7 + 6 * 3 + 2  # the root entry; offsets and scan storage per level; a frontier per inner level; codes and sums
-    assert mv.allocation_state()[:2] == state[:2]
-    for k in d:  # back to the canary for the sweep
-        mv.lib().mvrt_memcpy_h2d(d[k].ptr, outs[k][1].ctypes.data, d[k].nbytes, None)
-    for k in range(1, total + 1):
-        mv.set_test_fail_allocation(k)
-        with pytest.raises(mv.MvrtError, match="mvrt_test_fail_allocation"):
-            call()
-        assert mv.lib().mvrt_test_fail_allocation(0) == 0
-        assert mv.allocation_state()[:2] == state[:2], k  # nothing leaked
-        assert bytes(svo.info()) == info and all(np.array_equal(a, b) for a, b in zip(svo.download()[:2], octree[:2])), k
-        for name in d:  # the caller's arrays are written last, behind every allocation
-            assert np.array_equal(bits(d[name].to_host()), bits(outs[name][1])), (k, name)
+    # the root entry; offsets and scan storage per level; a frontier per inner level; codes and sums
+    total, result = sweep_reader(mv, lambda: svo.walk_voxels_device(n, d["xyz"], d["vIndex"], d["attribs"]), [svo], list(outs.values()), 3 + 2 * 7 + 6 * 3 + 2,
+                                 download=lambda h: h.download()[:2])
     print("walk: allocations failed in turn:", total)
     got = svo.intersect(ro, rd, want_descents=True)
     assert all(np.array_equal(got[k], traced[k]) for k in traced)
-    assert call() == n
+    assert result == n
     for name in d:
         assert np.array_equal(bits(d[name].to_host()), bits(want[name])), name
 
