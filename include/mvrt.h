@@ -904,8 +904,12 @@ int mvrt_denoise_default_params( mvrt_denoise_params* p );
 /* new; the reference has none.  Bytes of scratch mvrt_denoise_buffers needs for a frame (0 and mvrt_last_error for a bad size); no GPU call */
 uint64_t mvrt_denoise_scratch_bytes( int width, int height );
 /* new; the reference has none.  The filter on full-frame device buffers, asynchronous on `stream`; params NULL = the defaults.  outDev: width * height float4; it and
- * scratchDev must not overlap the inputs.  Every rejected argument (structBytes, iterations outside 1..8, a sigma or the floor not greater than 0, width or
- * height not greater than 0, scratch too small, a null pointer) fails on the host before any GPU call. */
+ * scratchDev must not overlap the inputs.  Every rejected argument (structBytes, iterations outside 1..8, a sigma or the floor not greater than 0, a sigma or
+ * the floor that is not finite, a sigmaNormal whose square underflows to 0, width or height not greater than 0, scratch too small, a null pointer) fails on the
+ * host before any GPU call.
+ * Non-finite INPUT is not refused: the filter applies the arithmetic above to it.  What is promised then: a pixel farther than 2 * ( 2^iterations - 1 ) from every
+ * non-finite pixel in both x and y (the reach of the taps) gets the value it would get without it, bit for bit; which of the pixels within the reach come out
+ * non-finite follows from the arithmetic above (IEEE rules for inf and NaN, a comparison with NaN is false), but payload and sign of a NaN are not part of the contract. */
 int mvrt_denoise_buffers( const float* colorDev, const float* albedoDev, const float* normalDepthDev, const float* momentsDev, int width, int height,
 						  const mvrt_denoise_params* params, float* outDev, void* scratchDev, uint64_t scratchBytes, void* stream );
 /* new; the reference has none.  The same on a handle with tileCount == 1, feature buffers and moments on and at least one step: like resolve it launches the pending steps
@@ -964,7 +968,10 @@ int mvrt_pt_set_tile( mvrt_pt* pt, int tileIndex, int tileCount );
 uint64_t mvrt_pt_owned_pixels( const mvrt_pt* pt ); /* padded to whole 256-pixel blocks */
 /* scatter gathered per-rank buffers (rank-major, each rankStridePixels float4) back to a width*height frame */
 int mvrt_pt_assemble_tiles( const float* gatheredDev, int tileCount, uint64_t rankStridePixels, int width, int height, float* frameDev, void* stream );
-/* renderResolve (voxKernel.cu:779-795) on an arbitrary float4 buffer */
+/* renderResolve (voxKernel.cu:779-795) on an arbitrary float4 buffer: per channel mean = x / w, v = 255 * mvrt_pow( mean, 1.0f / 2.2f ) + 0.5f, byte = v
+ * truncated, at most 255; alpha = 255.  Outside the ordinary range (deviation: the reference converts v to int before it clamps, which is undefined there):
+ *   a mean that is NaN, negative or zero -- 0 / 0 among them, so a pixel without samples is black -- gives 0 (mvrt_pow is 0 for them);
+ *   every mean with v >= 255 gives 255, +inf and x / 0 with x > 0 included: the clamp is taken in float, no out-of-range value is ever converted. */
 int mvrt_resolve_buffer( const float* rgbaF32Dev, uint64_t nPixels, uint8_t* rgbaU8Dev, void* stream );
 
 /* Per-sample radiance of the LAST step (debug / parity): ownedPixels*16*3 floats on the device */

@@ -950,6 +950,13 @@ static int denoiseParams( const mvrt_denoise_params* in, mvrt_denoise_params* ou
 	REQUIRE( in->sigmaCoverage > 0.0f, "%s: sigmaCoverage %g is not greater than 0", who, (double)in->sigmaCoverage );
 	REQUIRE( in->sigmaLuminance > 0.0f, "%s: sigmaLuminance %g is not greater than 0", who, (double)in->sigmaLuminance );
 	REQUIRE( in->albedoFloor > 0.0f, "%s: albedoFloor %g is not greater than 0", who, (double)in->albedoFloor );
+	// +inf passes the rules above, and sigmaLuminance * sqrt( 0 ) = inf * 0 = NaN turns the whole frame NaN by the contract's own arithmetic
+	REQUIRE( in->sigmaNormal - in->sigmaNormal == 0.0f, "%s: sigmaNormal %g is not finite", who, (double)in->sigmaNormal );
+	REQUIRE( in->sigmaDepth - in->sigmaDepth == 0.0f, "%s: sigmaDepth %g is not finite", who, (double)in->sigmaDepth );
+	REQUIRE( in->sigmaCoverage - in->sigmaCoverage == 0.0f, "%s: sigmaCoverage %g is not finite", who, (double)in->sigmaCoverage );
+	REQUIRE( in->sigmaLuminance - in->sigmaLuminance == 0.0f, "%s: sigmaLuminance %g is not finite", who, (double)in->sigmaLuminance );
+	REQUIRE( in->albedoFloor - in->albedoFloor == 0.0f, "%s: albedoFloor %g is not finite", who, (double)in->albedoFloor );
+	REQUIRE( in->sigmaNormal * in->sigmaNormal > 0.0f, "%s: sigmaNormal %g is too small, its square is not greater than 0 (the centre tap would be 0 / 0)", who, (double)in->sigmaNormal );
 	REQUIRE( ( in->flags & ~(uint32_t)MVRT_DENOISE_NO_DEMODULATION ) == 0, "%s: unknown flags 0x%x", who, in->flags );
 	*out = *in;
 	return 0;

@@ -95,9 +95,10 @@ int launchErrorMask( const float4* frameBuffer, const float4* moments, uint64_t 
 // ---- denoiser ---------------------------------------------------------------------------------------------------------------------------------------
 // What a tap reads of a pixel: two 16-byte records and one float.
 //   uv  { u.xyz, v }   demodulated mean radiance and the variance of its luminance; ping-ponged across the iterations
-//   geo { N.xyz, Z }   mean first-hit normal and mean hit t.  Z = DN_NO_TAP (negative; a real Z is a mean of positive t) marks a pixel that is never
-//                      filtered and never a tap -- sky (h == 0) or without samples (n == 0) -- so a tap is rejected on the record it loads anyway
-//   cov f = h / n      hit share
+//   geo { N.xyz, Z }   mean first-hit normal and mean hit t: a caller's values, of any sign
+//   cov f = h / n      hit share.  f = DN_NO_TAP marks a pixel that is never filtered and never a tap -- sky (h == 0) or without samples (n == 0).  The
+//                      marker is negative and h / n of a filtered pixel (n > 0 and h > 0) never is, whatever the other buffers hold, so validity is what the
+//                      contract says and nothing else; a tap is rejected on the float it loads anyway
 #define DN_NO_TAP -1.0f
 #define DN_TILE_X 32
 #define DN_TILE_Y 8
@@ -121,8 +122,8 @@ __global__ void __launch_bounds__( 256 ) kDenoisePrepare( const float4* __restri
 	if( n == 0.0f )
 	{
 		uv[p] = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
-		geo[p] = make_float4( 0.0f, 0.0f, 0.0f, DN_NO_TAP );
-		cov[p] = 0.0f;
+		geo[p] = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
+		cov[p] = DN_NO_TAP;
 		out[p] = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
 		return;
 	}
@@ -130,8 +131,8 @@ __global__ void __launch_bounds__( 256 ) kDenoisePrepare( const float4* __restri
 	if( h == 0.0f ) // sky: passed through exactly
 	{
 		uv[p] = make_float4( c.x, c.y, c.z, 0.0f );
-		geo[p] = make_float4( 0.0f, 0.0f, 0.0f, DN_NO_TAP );
-		cov[p] = 0.0f;
+		geo[p] = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
+		cov[p] = DN_NO_TAP;
 		out[p] = make_float4( c.x, c.y, c.z, 1.0f );
 		return;
 	}
@@ -204,10 +205,10 @@ __global__ void __launch_bounds__( 256 ) kDenoiseAtrous( const float4* __restric
 	if( x >= W || y >= H ) return;
 	const uint32_t p = (uint32_t)y * (uint32_t)W + (uint32_t)x;
 	DnCentre c;
-	c.g = geo[p];
-	if( c.g.w < 0.0f ) return; // sky or empty: prepare wrote the output, and no tap ever reads this pixel's record
-	const float4 up = uvIn[p];
 	c.f = cov[p];
+	if( c.f < 0.0f ) return; // sky or empty: prepare wrote the output, and no tap ever reads this pixel's record
+	c.g = geo[p];
+	const float4 up = uvIn[p];
 	c.l = lum3( up.x, up.y, up.z );
 	c.sv = sg.l * sqrtf( up.w ) + 1e-6f;
 	DnSums a = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
@@ -221,9 +222,9 @@ __global__ void __launch_bounds__( 256 ) kDenoiseAtrous( const float4* __restric
 			const int qx = x + dx * s;
 			if( qx < 0 || qx >= W || qy < 0 || qy >= H ) continue;
 			const uint32_t q = (uint32_t)qy * (uint32_t)W + (uint32_t)qx;
-			const float4 gq = geo[q];
-			if( gq.w < 0.0f ) continue;
-			dnTap( c, sg, dnKernel( dy ) * dnKernel( dx ), gq, uvIn[q], cov[q], a );
+			const float fq = cov[q];
+			if( fq < 0.0f ) continue;
+			dnTap( c, sg, dnKernel( dy ) * dnKernel( dx ), geo[q], uvIn[q], fq, a );
 		}
 	}
 	dnStore<LAST>( a, p, uvOut, color, albedo, floorA, flags, out );

@@ -354,15 +354,19 @@ int launchHdriSat( const float4* pixels, int w, int h, double* satF64, uint32_t*
 }
 
 // ---- renderResolve, voxKernel.cu:779-795 ------------------------------------------------------------------
+// Deviation: the clamp to 255 is taken in float, before the conversion -- the reference converts first, and a mean that scales past INT_MAX (1e16, +inf, x / 0)
+// makes that conversion undefined.  mvrt_pow is 0 for NaN and for means <= 0, so v is never NaN and never below 0.5 (include/mvrt.h, mvrt_resolve_buffer).
+static MVRT_DI uint8_t resolveChannel( float mean )
+{
+	const float v = 255 * mvrt_pow( mean, 1.0f / 2.2f ) + 0.5f;
+	return (uint8_t)( v >= 255.0f ? 255 : (int)v );
+}
 __global__ void __launch_bounds__( 256 ) kResolve( const float4* __restrict__ fb, uint64_t n, uchar4* __restrict__ out )
 {
 	for( uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256 )
 	{
 		float4 v = fb[i];
-		int r = (int)( 255 * mvrt_pow( v.x / v.w, 1.0f / 2.2f ) + 0.5f );
-		int g = (int)( 255 * mvrt_pow( v.y / v.w, 1.0f / 2.2f ) + 0.5f );
-		int b = (int)( 255 * mvrt_pow( v.z / v.w, 1.0f / 2.2f ) + 0.5f );
-		out[i] = make_uchar4( (uint8_t)( r < 255 ? r : 255 ), (uint8_t)( g < 255 ? g : 255 ), (uint8_t)( b < 255 ? b : 255 ), 255 );
+		out[i] = make_uchar4( resolveChannel( v.x / v.w ), resolveChannel( v.y / v.w ), resolveChannel( v.z / v.w ), 255 );
 	}
 }
 int launchResolve( const float4* fb, uint64_t n, uchar4* out, hipStream_t stream )

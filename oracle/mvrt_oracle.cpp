@@ -1801,18 +1801,22 @@ ORC_API void orc_render_pt( void* sp, void* hp, const float* pmjTable, const flo
 }
 
 // renderResolve, voxKernel.cu:779-795
+// The clamp is taken in float, before the conversion: a mean of 1e16 or +inf scales past INT_MAX, and converting that to int is undefined (x86 gives INT_MIN,
+// i.e. black; the GPU saturates).  mvrt_pow is 0 for NaN and for means <= 0, so v >= 0.5 there; libm's pow (mathMode 0) is NaN for a negative mean: 0 as well.
+static inline uint8_t resolveChannel( const Math& M, float mean )
+{
+	const float v = 255 * M.pow_( mean, 1.0f / 2.2f ) + 0.5f;
+	return (uint8_t)( v >= 255.0f ? 255 : v >= 0.0f ? (int)v : 0 );
+}
 ORC_API void orc_resolve( const float* fb, int64_t n, int mathMode, uint8_t* rgbaOut )
 {
 	Math M = { mathMode };
 	for( int64_t i = 0; i < n; i++ )
 	{
 		const float* v = fb + i * 4;
-		int r = (int)( 255 * M.pow_( v[0] / v[3], 1.0f / 2.2f ) + 0.5f );
-		int g = (int)( 255 * M.pow_( v[1] / v[3], 1.0f / 2.2f ) + 0.5f );
-		int b = (int)( 255 * M.pow_( v[2] / v[3], 1.0f / 2.2f ) + 0.5f );
-		rgbaOut[i * 4 + 0] = (uint8_t)std::min( r, 255 );
-		rgbaOut[i * 4 + 1] = (uint8_t)std::min( g, 255 );
-		rgbaOut[i * 4 + 2] = (uint8_t)std::min( b, 255 );
+		rgbaOut[i * 4 + 0] = resolveChannel( M, v[0] / v[3] );
+		rgbaOut[i * 4 + 1] = resolveChannel( M, v[1] / v[3] );
+		rgbaOut[i * 4 + 2] = resolveChannel( M, v[2] / v[3] );
 		rgbaOut[i * 4 + 3] = 255;
 	}
 }

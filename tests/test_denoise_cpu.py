@@ -10,6 +10,7 @@ import pytest
 
 import common
 import aov_expected as A
+import denoise_cases as K
 import denoise_expected as D
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
 
@@ -112,6 +113,61 @@ def test_filter_helper_on_hand_made_frames(O):
     assert abs(out[c + 1, 0] - k[2] * k[1] / (1 - k[4])) < 1e-6
 
 
+def test_fp32_recipe_against_float64_on_the_hand_made_frames(O):
+    """every random case of tests/denoise_cases.py in both precisions: the float32 restatement (the contract) against the same formula evaluated in float64 with
+    exp( clamp( x, -87, 88 ) ), on max |a - b| / max( |b|, 1e-3 ) over the rgb components.  Measured maximum 6.2e-6 (37 x 19, the other sigmas; median 6.5e-7); the
+    bound is four times that, a margin for another seed of the generator.  This pins the fp32 contract to the mathematics rather than to itself, and tells "another
+    summation order" from "another formula" when a bitwise comparison fails.  The frames with v == 0 (var_zero, var_clamped) stay out: there
+    e = |dl| / 1e-6 amplifies the last bit of a luminance into the weight, so the contract is not continuous in its inputs."""
+    worst = (0.0, "")
+    for W, H, params in K.random_cases():
+        bufs = K.frame(W, H)
+        a = K.expected(O, bufs, W, H, params, "random")
+        b = K.expected(O, bufs, W, H, params, "random", np.float64)
+        assert a.dtype == f32 and b.dtype == np.float64 and np.isfinite(a).all() and np.isfinite(b).all()
+        assert np.array_equal(a[:, 3], b[:, 3])
+        worst = max(worst, (K.rel_error(a, b), K.case_id((W, H, params))))
+    print("float32 against float64: max %.3g at %s; asserted %.3g" % (worst + (K.F32_AGAINST_F64_BOUND,)))
+    assert worst[0] <= K.F32_AGAINST_F64_BOUND, worst
+    assert worst[0] >= K.F32_AGAINST_F64 / 4, worst  # (the two evaluations do differ: the check is not comparing a thing with itself)
+
+
+def test_hand_made_frames_are_what_they_say(O):
+    """the generator obeys the buffers' invariants and visits what it claims; the helper stays finite on every frame with finite inputs except the one where the
+    contract itself overflows (albedoFloor 1e-30: v = var / 0)"""
+    for W, H in K.SIZES:
+        c, a, nd, m = K.frame(W, H)
+        n, h = c[:, 3], a[:, 3]
+        assert np.isin(n, [0, 16, 32, 64]).all() and (h >= 0).all() and (h <= n).all() and (a[:, 0:3] <= h[:, None]).all() and (np.abs(nd[:, 0:3]).sum(1) == h).all()
+        assert (c[:, 0:3] >= 0).all() and (c[:, 0:3] <= 4 * n[:, None]).all() and (m[:, 1] * np.maximum(n, 1) >= m[:, 0] ** 2 * (1 - 1e-6)).all() and not m[:, 2:4].any()
+        for b in (a, nd, m):
+            assert not b[n == 0].any()
+    c, a, nd, m = K.frame(65, 17)
+    pr = D.prepare(c, a, nd, m, 0.01, 0)
+    assert pr["empty"].sum() > 20 and pr["sky"].sum() > 50 and ((a[:, 3] > 0) & (a[:, 3] < c[:, 3])).sum() > 200 and (pr["v"][pr["valid"]] > 0).all()
+    W, H = K.SPECIAL_SIZE
+    for name in K.SPECIAL_NAMES:
+        bufs, params, info = K.special_frame(name)
+        pr = D.prepare(*bufs, params.get("albedoFloor", 0.01), 0)
+        out = K.expected(O, bufs, W, H, dict(params, iterations=5), name)
+        if info["finite"]:
+            assert all(np.isfinite(b).all() for b in bufs) and np.isfinite(out).all(), name
+        what = {"all_empty": pr["empty"].all(), "all_sky": pr["sky"].all(), "one_hit_in_sky": pr["valid"].sum() == 1 and pr["sky"].sum() == W * H - 1,
+                "checkerboard": pr["valid"].sum() == (W * H + 1) // 2 and pr["sky"].sum() == W * H // 2, "var_zero": not pr["v"].any(), "var_clamped": not pr["v"].any(),
+                "n_one": (bufs[0][:, 3][~pr["empty"]] == 1).all(), "black_albedo": (pr["A"][pr["valid"]] == f32(0.01)).all(),
+                "tiny_floor": np.isinf(pr["v"][pr["valid"]]).all() and np.isfinite(pr["u"]).all(), "z_zero": not pr["Z"].any(),
+                "z_tiny": (pr["Z"][pr["valid"]] > 0).all() and (pr["Z"] < 1e-20).all(), "z_huge": (pr["Z"][pr["valid"]] > 5e29).all(),
+                "negative_t": (pr["Z"][pr["valid"]] < 0).sum() > W * H // 5 and (pr["Z"][pr["valid"]] > 0).sum() > W * H // 5,
+                "inf_radiance": np.isinf(bufs[0]).sum() == 1 and pr["valid"][info["bad"][1] * W + info["bad"][0]]}[name]
+        assert what, name
+        assert pr["valid"].sum() > W * H // 2 or name in ("all_empty", "all_sky", "one_hit_in_sky", "checkerboard"), name
+    # the clamp frame is really below: m2 - m1 * m1 < 0 on most pixels
+    c, a, nd, m = K.special_frame("var_clamped")[0]
+    k = c[:, 3] > 0
+    m1, m2 = (m[k, 0] / c[k, 3]).astype(f32), (m[k, 1] / c[k, 3]).astype(f32)
+    assert ((m2 - (m1 * m1).astype(f32)).astype(f32) < 0).mean() > 0.9
+
+
 def test_quality_on_oracle_frames(O, scene, hdri):
     """bunny 256^3, 128 x 72, three cameras, inputs of 1 and 4 steps (16 and 64 spp), truth = the 48-step oracle frame, default parameters:
     relMSE( denoised ) < relMSE( noisy ) over the whole frame and over the pixels with h > 0, in all six cases; sky pixels come out as c bit for bit.
@@ -180,6 +236,16 @@ def test_host_side_refusals_without_a_gpu():
             p = mv.denoise_params(**fields)
             assert buffers(params=p) != 0 and word in _err(lib), fields
             assert lib.mvrt_pt_denoise(h, None, C.byref(p)) != 0 and word in _err(lib), fields
+        # a sigma or the floor that is not finite: +inf passes "greater than 0", and sigmaLuminance = inf makes sv = inf * 0 = NaN wherever v == 0
+        inf = float("inf")
+        for field in ("sigmaNormal", "sigmaDepth", "sigmaCoverage", "sigmaLuminance", "albedoFloor"):
+            p = mv.denoise_params(**{field: inf})
+            assert buffers(params=p) != 0 and field in _err(lib) and "is not finite" in _err(lib), field
+            assert lib.mvrt_pt_denoise(h, None, C.byref(p)) != 0 and field in _err(lib) and "is not finite" in _err(lib), field
+            p = mv.denoise_params(**{field: -inf})
+            assert buffers(params=p) != 0 and field in _err(lib) and "not greater than 0" in _err(lib), field
+        p = mv.denoise_params(sigmaNormal=1e-30)  # its square is 0: the centre tap's normal term would be 0 / 0
+        assert buffers(params=p) != 0 and "sigmaNormal" in _err(lib) and "square" in _err(lib)
         assert lib.mvrt_pt_denoise(None, None, None) != 0 and "null" in _err(lib)
         # a handle: feature buffers off, then moments off, then no steps; a tile share is pointed to mvrt_denoise_buffers
         assert lib.mvrt_pt_denoise(h, None, None) != 0 and "mvrt_pt_set_aovs" in _err(lib)

@@ -36,6 +36,27 @@ def test_pow_gamma_accuracy():
     assert O.detmath("pow", np.zeros(1, np.float32), y[:1])[0] == 0.0
 
 
+def test_resolve_outside_the_ordinary_range():
+    """the oracle's resolve on the rows of tests/denoise_cases.py: NaN, negative means and 0 / 0 give 0, every mean whose scaled value is at least 255 gives 255
+    (include/mvrt.h, mvrt_resolve_buffer).  With the conversion to int taken before the clamp, x86 turned 1e16, 1e20, 3e38, +inf and x / 0 into 0: the second, fourth and
+    fifth row came out as (0,0,0), (0,255,0) and (0,0,0).  The ordinary range around the clamp is pinned byte by byte against float64."""
+    from denoise_cases import RESOLVE_BYTES, RESOLVE_ROWS
+    assert np.array_equal(O.resolve(RESOLVE_ROWS, math_mode=1), RESOLVE_BYTES)
+    assert np.array_equal(O.resolve(RESOLVE_ROWS, math_mode=0), RESOLVE_BYTES)  # libm's pow is NaN for the negative mean: 0 as well
+    # ordinary means, dense around the point where the clamp sets in (mean = 1: 255.5) and up to where the old conversion still worked
+    m = np.concatenate([np.linspace(0.0, 1.2, 20001), np.exp(np.linspace(np.log(1.2), np.log(1e15), 2001))]).astype(np.float32)
+    fb = np.stack([m, m * 2, m * 0.5, np.ones_like(m)], 1).astype(np.float32)
+    fb[:, 0:3] *= 32
+    fb[:, 3] = 32
+    got = O.resolve(fb, math_mode=1)
+    mean = fb[:, 0:3].astype(np.float64) / 32
+    v = 255 * mean ** (1 / 2.2) + 0.5
+    want = np.minimum(np.floor(v), 255)
+    near = np.abs(v - np.round(v)) < 1e-3  # (within pow's 2e-6 relative error of a byte boundary: either neighbour)
+    assert (np.abs(got[:, 0:3] - want) <= near).all() and (got[:, 3] == 255).all()
+    assert near.mean() < 0.01 and (want == 255).mean() > 0.3 and len(np.unique(got[:, 0:3])) >= 250  # (the gamma curve is steep at 0: the grid steps over byte 1)
+
+
 def test_libm_vs_detmath_image_tolerance():
     """The oracle in the reference's HOST math (libm) vs the deterministic math the GPU path uses: mean
     radiance within 1e-3 relative on a 128x72x16spp frame; most pixels are bit-identical, the rest are

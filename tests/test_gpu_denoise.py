@@ -70,9 +70,7 @@ def buffers(pt, n):
     return pt.read_framebuffer()[:n], pt.read_aov(pt.AOV_ALBEDO)[:n], pt.read_aov(pt.AOV_NORMAL_DEPTH)[:n], pt.read_moments()[:n]
 
 
-def assert_same(got, want, what):
-    bad = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(1))[0]
-    assert len(bad) == 0, "%s: %d of %d pixels differ, first %s: %s vs %s" % (what, len(bad), len(got), bad[:4], got[bad[:2]], want[bad[:2]])
+assert_same = D.assert_same
 
 
 # ---- 5. moments -------------------------------------------------------------------------------------------------------------------------------------
