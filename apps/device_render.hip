@@ -2,15 +2,18 @@
 // device API (include/mvrt/device.hpp) and nothing else: one primary ray through each pixel centre, normal colour or vertex colour,
 // plus an optional shadow ray per hit towards a directional sun (a second intersect() in the same thread).
 //
-//   device_render scene.obj out.ppm [--size W H] [--res N] [--vertex-color] [--camera c0 ... c14] [--sun x y z] [--dump prefix] [--bench N]
+//   device_render scene.obj out.ppm [--size W H] [--res N] [--vertex-color] [--camera c0 ... c14] [--sun x y z] [--lod SCALE] [--dump prefix] [--bench N]
 //
 // The octree is built from the OBJ with mvrt_svo_build (grid = bounding cube of the mesh, apps/scene_io.hpp).  Without --camera the view
 // frames the grid from (+0.6, +0.4, +0.6) grid extents off its centre.
 // --sun x y z: for each hit, a shadow ray (isShadowRay = true) with origin o = ro + rd * t and direction (x, y, z), both computed per component
 //   in fp32 without contraction (o.x = ro.x + rd.x * t); the pixel is halved if that ray hits anything.
+// --lod SCALE: the image comes from a second application kernel, renderLod, on intersectCone and mvrt::DeviceLod: every pixel's ray stops at the octree level
+//   whose cells are SCALE pixels wide where it enters them (coneA = 0, coneB = SCALE * 2 tanHthetaY / H, as mvrt_render_primary_lod), and a stopped ray takes
+//   the mean colour of its cell from the attribute pyramid (mvrt_svo_lod_prepare).  It casts no shadow ray: --lod is refused together with --sun.
 // --dump prefix: prefix.camera.txt (the 15 camera floats, %a), prefix.t.f32, prefix.nmajor.i32 (per pixel) and, with --sun, prefix.shadow.u8.
 // --bench N: N interleaved rounds of this kernel and of mvrt_render_primary (the library's persistent traversal) on the same octree and
-//   camera, timed with HIP events; prints one JSON line with the median and minimum ms per frame of each.
+//   camera, timed with HIP events; prints one JSON line with the median and minimum ms per frame of each, and with --lod of renderLod as well.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -70,6 +73,42 @@ __global__ void __launch_bounds__( RENDER_THREADS ) render( mvrt_device_octree v
 	if( shadowOut ) shadowOut[pixelIdx] = shadowed;
 }
 
+// the same pixel through a cone: the walk stops at the pixel's own level of detail and the colour is the cell's, by its code
+__global__ void __launch_bounds__( RENDER_THREADS ) renderLod( mvrt_device_octree view, mvrt_device_lod lodView, mvrt::CameraPinhole pinhole, int W, int H, int showVertexColor,
+																float coneB, uchar4* frameBuffer, float* tOut, int* nMajorOut )
+{
+	MVRT_DEVICE_FP_STRICT
+	const mvrt::DeviceOctree intersector( view );
+	const mvrt::DeviceLod lod( lodView );
+	const uint32_t pixelIdx = blockIdx.x * RENDER_THREADS + threadIdx.x;
+	if( pixelIdx >= (uint32_t)( W * H ) ) return;
+	const int x = (int)( pixelIdx % W ), y = (int)( pixelIdx / W );
+	float3 ro, rd;
+	pinhole.shoot( &ro, &rd, x, y, 0.5f, 0.5f, W, H );
+	float t;
+	int nMajor;
+	uint32_t level, index;
+	uint64_t cellCode;
+	intersector.intersectCone( ro, rd, 0.0f, coneB, &t, &nMajor, &level, &cellCode );
+	uchar4 colorOut = make_uchar4( 0, 0, 0, 255 );
+	if( t != MVRT_MAX_FLOAT )
+	{
+		if( showVertexColor )
+		{
+			if( lod.lookup( level, cellCode, &index ) ) colorOut = lod.color( level, index );
+		}
+		else
+		{
+			const float3 hitN = mvrt::getHitN( nMajor, rd );
+			const float cx = ( hitN.x + 1.0f ) * 0.5f, cy = ( hitN.y + 1.0f ) * 0.5f, cz = ( hitN.z + 1.0f ) * 0.5f;
+			colorOut = make_uchar4( (uint8_t)( 255 * cx + 0.5f ), (uint8_t)( 255 * cy + 0.5f ), (uint8_t)( 255 * cz + 0.5f ), 255 );
+		}
+	}
+	frameBuffer[pixelIdx] = colorOut;
+	if( tOut ) tOut[pixelIdx] = t;
+	if( nMajorOut ) nMajorOut[pixelIdx] = nMajor;
+}
+
 #define HIP_CHECK( e )                                                                           \
 	do                                                                                           \
 	{                                                                                            \
@@ -109,10 +148,11 @@ int main( int argc, char** argv )
 {
 	if( argc < 3 )
 	{
-		std::fprintf( stderr, "usage: %s scene.obj out.ppm [--size W H] [--res N] [--vertex-color] [--camera c0 ... c14] [--sun x y z] [--dump prefix] [--bench N]\n", argv[0] );
+		std::fprintf( stderr, "usage: %s scene.obj out.ppm [--size W H] [--res N] [--vertex-color] [--camera c0 ... c14] [--sun x y z] [--lod SCALE] [--dump prefix] [--bench N]\n", argv[0] );
 		return 2;
 	}
-	int W = 1920, H = 1080, res = 256, vertexColor = 0, useSun = 0, bench = 0, haveCamera = 0;
+	int W = 1920, H = 1080, res = 256, vertexColor = 0, useSun = 0, bench = 0, haveCamera = 0, useLod = 0;
+	float lodScale = 0.0f;
 	float cam[15] = {};
 	float sun[3] = { 0, 0, 0 };
 	std::string dump;
@@ -131,11 +171,13 @@ int main( int argc, char** argv )
 		else if( a == "--vertex-color" ) vertexColor = 1;
 		else if( a == "--camera" ) { need( 15 ); for( int k = 0; k < 15; k++ ) cam[k] = std::strtof( argv[++i], nullptr ); haveCamera = 1; }
 		else if( a == "--sun" ) { need( 3 ); for( int k = 0; k < 3; k++ ) sun[k] = std::strtof( argv[++i], nullptr ); useSun = 1; }
+		else if( a == "--lod" ) { need( 1 ); lodScale = std::strtof( argv[++i], nullptr ); useLod = 1; }
 		else if( a == "--dump" ) { need( 1 ); dump = argv[++i]; }
 		else if( a == "--bench" ) { need( 1 ); bench = std::atoi( argv[++i] ); }
 		else { std::fprintf( stderr, "unknown option %s\n", a.c_str() ); return 2; }
 	}
 	if( W <= 0 || H <= 0 || (long long)W * H > ( 1ll << 30 ) ) { std::fprintf( stderr, "bad --size\n" ); return 2; }
+	if( useLod && useSun ) { std::fprintf( stderr, "--lod and --sun do not go together: the cone kernel casts no shadow ray\n" ); return 2; }
 
 	std::vector<mvrt_io::V3> verts, cols, emis;
 	if( !mvrt_io::readObj( argv[1], &verts, &cols, &emis ) ) { std::fprintf( stderr, "cannot read %s\n", argv[1] ); return 1; }
@@ -148,6 +190,13 @@ int main( int argc, char** argv )
 	MVRT_CHECK( mvrt_svo_build( svo, &verts[0].x, &cols[0].x, &emis[0].x, verts.size(), nullptr, o, dps, res ) );
 	mvrt_device_octree view;
 	MVRT_CHECK( mvrt_svo_device_view( svo, &view ) );
+	mvrt_device_lod lodView;
+	std::memset( &lodView, 0, sizeof( lodView ) );
+	if( useLod )
+	{
+		MVRT_CHECK( mvrt_svo_lod_prepare( svo, nullptr ) );
+		MVRT_CHECK( mvrt_svo_lod_view( svo, &lodView ) );
+	}
 
 	if( !haveCamera ) // look at the grid's centre from (+0.6, +0.4, +0.6) extents away, fovy 45 degrees
 	{
@@ -178,7 +227,9 @@ int main( int argc, char** argv )
 	HIP_CHECK( hipMalloc( &nmDev, n * sizeof( int ) ) );
 	HIP_CHECK( hipMalloc( &shDev, n ) );
 	const dim3 grid( (unsigned)( ( n + RENDER_THREADS - 1 ) / RENDER_THREADS ) );
-	hipLaunchKernelGGL( render, grid, dim3( RENDER_THREADS ), 0, 0, view, pinhole, W, H, vertexColor, useSun, sunDir, rgba, tDev, nmDev, useSun ? shDev : nullptr );
+	const float coneB = lodScale * ( ( 2.0f * cam[12] ) / (float)H );
+	if( useLod ) hipLaunchKernelGGL( renderLod, grid, dim3( RENDER_THREADS ), 0, 0, view, lodView, pinhole, W, H, vertexColor, coneB, rgba, tDev, nmDev );
+	else hipLaunchKernelGGL( render, grid, dim3( RENDER_THREADS ), 0, 0, view, pinhole, W, H, vertexColor, useSun, sunDir, rgba, tDev, nmDev, useSun ? shDev : nullptr );
 	HIP_CHECK( hipGetLastError() );
 	HIP_CHECK( hipDeviceSynchronize() );
 
@@ -209,11 +260,12 @@ int main( int argc, char** argv )
 	{
 		uint8_t* rgbaLib = nullptr;
 		HIP_CHECK( hipMalloc( &rgbaLib, n * 4 ) );
-		hipEvent_t e0, e1, e2;
+		hipEvent_t e0, e1, e2, e3;
 		HIP_CHECK( hipEventCreate( &e0 ) );
 		HIP_CHECK( hipEventCreate( &e1 ) );
 		HIP_CHECK( hipEventCreate( &e2 ) );
-		std::vector<float> own, lib;
+		HIP_CHECK( hipEventCreate( &e3 ) );
+		std::vector<float> own, lib, cone;
 		for( int r = -2; r < bench; r++ ) // two warm-up rounds of each, then N timed rounds, interleaved
 		{
 			HIP_CHECK( hipEventRecord( e0, 0 ) );
@@ -221,19 +273,31 @@ int main( int argc, char** argv )
 			HIP_CHECK( hipEventRecord( e1, 0 ) );
 			MVRT_CHECK( mvrt_render_primary( svo, cam, W, H, vertexColor, rgbaLib, nullptr, nullptr, nullptr, nullptr, nullptr ) );
 			HIP_CHECK( hipEventRecord( e2, 0 ) );
-			HIP_CHECK( hipEventSynchronize( e2 ) );
-			float a = 0, b = 0;
+			if( useLod )
+			{
+				hipLaunchKernelGGL( renderLod, grid, dim3( RENDER_THREADS ), 0, 0, view, lodView, pinhole, W, H, vertexColor, coneB, rgba, (float*)nullptr, (int*)nullptr );
+				HIP_CHECK( hipEventRecord( e3, 0 ) );
+			}
+			HIP_CHECK( hipEventSynchronize( useLod ? e3 : e2 ) );
+			float a = 0, b = 0, c = 0;
 			HIP_CHECK( hipEventElapsedTime( &a, e0, e1 ) );
 			HIP_CHECK( hipEventElapsedTime( &b, e1, e2 ) );
+			if( useLod ) HIP_CHECK( hipEventElapsedTime( &c, e2, e3 ) );
 			if( r >= 0 )
 			{
 				own.push_back( a );
 				lib.push_back( b );
+				if( useLod ) cone.push_back( c );
 			}
 		}
+		char lodPart[160] = "";
+		if( useLod )
+			std::snprintf( lodPart, sizeof( lodPart ), ", \"lod_scale\": %g, \"lod_kernel_ms\": {\"median\": %.4f, \"min\": %.4f}", (double)lodScale, median( cone ),
+						   *std::min_element( cone.begin(), cone.end() ) );
 		std::printf( "{\"size\": [%d, %d], \"res\": %d, \"sun\": %s, \"rounds\": %d, \"device_kernel_ms\": {\"median\": %.4f, \"min\": %.4f}, "
-					 "\"render_primary_ms\": {\"median\": %.4f, \"min\": %.4f}}\n",
-					 W, H, res, useSun ? "true" : "false", bench, median( own ), *std::min_element( own.begin(), own.end() ), median( lib ), *std::min_element( lib.begin(), lib.end() ) );
+					 "\"render_primary_ms\": {\"median\": %.4f, \"min\": %.4f}%s}\n",
+					 W, H, res, useSun ? "true" : "false", bench, median( own ), *std::min_element( own.begin(), own.end() ), median( lib ), *std::min_element( lib.begin(), lib.end() ),
+					 lodPart );
 		HIP_CHECK( hipFree( rgbaLib ) );
 	}
 	HIP_CHECK( hipFree( rgba ) );

@@ -740,9 +740,66 @@ MVRT_STATIC_ASSERT_( __builtin_offsetof( mvrt_device_octree, nodes ) == 8 && __b
 						 __builtin_offsetof( mvrt_device_octree, lower ) == 64 && __builtin_offsetof( mvrt_device_octree, emissionScale ) == 92 &&
 						 __builtin_offsetof( mvrt_device_octree, levels ) == 100 && __builtin_offsetof( mvrt_device_octree, cellBits ) == 124,
 					 "mvrt_device_octree field offsets" );
-#undef MVRT_STATIC_ASSERT_
 /* Fill *out with the device view of svo (no GPU call).  Fails without an octree, on a tree-flavour octree and above MVRT_DEVICE_MAX_LEVELS. */
 int mvrt_svo_device_view( const mvrt_svo* svo, mvrt_device_octree* out );
+
+/* ---- Level of detail per ray inside ONE octree (new; the reference has none) ----------------------------------------------------------
+ * The attribute pyramid.  mvrt_svo_lod_prepare attaches to the handle, for every level L in [1, levels - 1], the occupied cells of that level as ascending codes
+ * (uint64, the Morton code of any voxel below the cell >> 3 * ( levels - L )), their 8-byte attributes and their voxel counts (uint32): exactly what
+ * mvrt_svo_coarse_voxels( levelsDown = levels - L, minCount = 1 ) lists, in its order, from the same exact integer sums over the voxels (never means of means).
+ * The pyramid is keyed by the cell's code, not by the node: the octree is a DAG, subtrees of equal shape share nodes whatever their colours.
+ *   - Handles as for mvrt_svo_coarse_voxels (an upload is refused: "keeps no Morton codes"; an empty handle: "no octree"), except the tree flavour, which is
+ *     refused by name, and octrees above MVRT_DEVICE_MAX_LEVELS levels.  A one-level octree has an empty pyramid and succeeds.
+ *   - The call blocks.  It is built on the GPU from the sorted voxel list; nothing travels to the host.  A failed allocation leaves the octree whole, no
+ *     half-built pyramid and no leak.  A second call replaces the pyramid.
+ *   - Every build, edit (attribute-only ones included, and an edit the device checks refuse as well: it is dropped before the edit runs), rebuild, upload, coarsen
+ *     in place, every other in-place voxel-set call that changes the handle, cleanUp and destroy drops the pyramid: it never outlives the voxels it describes.
+ *     mvrt_svo_lod_release drops it by hand; mvrt_svo_lod_bytes = its size (0 without one).
+ * mvrt_device_lod is the by-value view for application kernels (mvrt::DeviceLod, include/mvrt/device.hpp): entry L of each array describes level L; entry
+ * `levels` is the voxel list itself (its codes, the octree's attributes, numberOfVoxels; no counts), entry 0 and the entries above `levels` are 0.  Like
+ * mvrt_device_octree it is a snapshot: whatever drops the pyramid invalidates it. */
+typedef struct mvrt_device_lod
+{
+	uint32_t structBytes; /* sizeof( mvrt_device_lod ) of the library that filled it */
+	uint32_t levels;	  /* of the octree */
+	uint64_t codes[MVRT_DEVICE_MAX_LEVELS + 1];		 /* per level: ascending cell codes (uint64) */
+	uint64_t attrs[MVRT_DEVICE_MAX_LEVELS + 1];		 /* per level: {uchar4 color, uchar4 emission} per cell */
+	uint64_t cellVoxels[MVRT_DEVICE_MAX_LEVELS + 1]; /* per level: voxels per cell (uint32); 0 at level `levels` */
+	uint32_t count[MVRT_DEVICE_MAX_LEVELS + 1];		 /* per level: the number of cells */
+	uint32_t reserved;
+} mvrt_device_lod;
+MVRT_STATIC_ASSERT_( sizeof( mvrt_device_lod ) == 488, "mvrt_device_lod is 488 bytes" );
+MVRT_STATIC_ASSERT_( __builtin_offsetof( mvrt_device_lod, codes ) == 8 && __builtin_offsetof( mvrt_device_lod, attrs ) == 144 &&
+						 __builtin_offsetof( mvrt_device_lod, cellVoxels ) == 280 && __builtin_offsetof( mvrt_device_lod, count ) == 416,
+					 "mvrt_device_lod field offsets" );
+#undef MVRT_STATIC_ASSERT_
+int mvrt_svo_lod_prepare( mvrt_svo* svo, void* stream );
+int mvrt_svo_lod_release( mvrt_svo* svo );
+uint64_t mvrt_svo_lod_bytes( const mvrt_svo* svo );
+/* Fill *out with the view of the pyramid (no GPU call).  Fails without a prepared pyramid. */
+int mvrt_svo_lod_view( const mvrt_svo* svo, mvrt_device_lod* out );
+/* CONE-LIMITED rays: ray i stops the octree walk at its own level of detail.  coneADev, coneBDev: n floats each, required; the ray's footprint at time S is
+ * f = coneA + coneB * S (one fp32 product, one fp32 sum, each rounded).  On the first visit of an inner node at level in [1, levels - 1], entered at time S, the
+ * node is terminal iff 0 < S and dps * 2^( levels - level ) <= f, and reports the hit a voxel in its place would: t = S, nMajor by the voxel's rule,
+ * levelDev[i] = the node's level, cellCodeDev[i] = the cell's code (as in the pyramid above).  A voxel hit reports level = levels and the voxel's Morton code, a miss
+ * MVRT_MAX_FLOAT, -1, 0, 0.  The root is never terminal.  Bit for bit: t and nMajor of a walk stopped at level D are those of mvrt_trace_batch against the octree
+ * mvrt_svo_coarsen makes with levelsDown = levels - D; a zero, negative or NaN footprint gives mvrt_trace_batch's t, nMajor and descents; descents never exceed the
+ * unlimited ray's; where the unlimited ray hits the cone ray hits too, and it may hit where that one misses (a coarse cell is solid to it).
+ *   - indexDev (uint32: the cell's rank in its level; at a voxel the vIndex) and attribDev (8 bytes per ray: the pyramid's attribute of the cell, at a voxel the
+ *     voxel's; zeros on a miss) need a prepared pyramid (mvrt_svo_lod_prepare): without one they are refused by name when non-NULL.  Without them any octree
+ *     mvrt_svo_device_view accepts is legal, uploads included.  nMajorDev, levelDev, cellCodeDev, indexDev, attribDev, descentsDev may be NULL.
+ *   - Asynchrony as for mvrt_trace_batch_range; the tree flavour is refused by name.  n = 0 succeeds without a launch.  A NULL coneADev, coneBDev, tDev or ray array
+ *     is refused on the host before the handle is looked at. */
+int mvrt_trace_batch_cone( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
+						   const float* rdzDev, const float* coneADev, const float* coneBDev, float* tDev, int32_t* nMajorDev, uint32_t* levelDev, uint64_t* cellCodeDev,
+						   uint32_t* indexDev, uint32_t* attribDev /* 2 per ray */, uint32_t* descentsDev, void* stream );
+/* mvrt_render_primary with one cone per pixel: the rays of mvrt_render_primary (CameraPinhole::shoot through pixel centres), coneA = 0 and
+ * coneB = lodScale * ( ( 2.0f * tanHthetaY ) / (float)height ), computed once on the host in that order: lodScale pixels' width at rd . front = 1.  Colour = the
+ * terminal cell's pyramid colour, or the voxel's at a voxel, converted as mvrt_render_primary converts a voxel colour (showVertexColor: needs a prepared pyramid), or
+ * the hit normal.  levelDev: the level each pixel stopped at (0 on a miss).  lodScale = 0 equals mvrt_render_primary in rgba, t, nMajor and descents.  The kernel
+ * is the per-thread walk: octrees as for mvrt_trace_batch_cone.  rgbaDev, tDev, nMajorDev, levelDev, descentsDev may be NULL. */
+int mvrt_render_primary_lod( const mvrt_svo* svo, const float camera[15], int width, int height, float lodScale, int showVertexColor, uint8_t* rgbaDev, float* tDev,
+							 int32_t* nMajorDev, uint32_t* levelDev, uint32_t* descentsDev, void* stream );
 
 /* CameraPinhole::initFromPerspective (renderCommon.hpp:21-35) */
 int mvrt_camera_from_matrices( const float view[16], const float proj[16], float focus, float lensR, float cameraOut[15] );

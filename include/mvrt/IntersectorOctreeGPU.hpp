@@ -627,6 +627,31 @@ struct IntersectorOctreeGPU
 		return v;
 	}
 
+	// level of detail per ray (mvrt_svo_lod_prepare / _release / _bytes / _view, mvrt_trace_batch_cone, mvrt_render_primary_lod; semantics in mvrt.h).  The pyramid
+	// is dropped by whatever changes the voxels; lodView() is a snapshot like deviceView()
+	void lodPrepare( void* stream = nullptr ) { check( mvrt_svo_lod_prepare( m_handle, stream ), "IntersectorOctreeGPU::lodPrepare" ); }
+	void lodRelease() { check( mvrt_svo_lod_release( m_handle ), "IntersectorOctreeGPU::lodRelease" ); }
+	uint64_t lodBytes() const { return mvrt_svo_lod_bytes( m_handle ); }
+	mvrt_device_lod lodView() const
+	{
+		mvrt_device_lod v;
+		check( mvrt_svo_lod_view( m_handle, &v ), "IntersectorOctreeGPU::lodView" );
+		return v;
+	}
+	// cone-limited rays on device arrays: every output but t may be nullptr; index and attrib (2 words per ray) need lodPrepare()
+	void intersectCone( uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz, const float* coneA, const float* coneB,
+						float* t, int32_t* nMajor, uint32_t* level, uint64_t* cellCode, uint32_t* index, uint32_t* attrib, uint32_t* descents, void* stream ) const
+	{
+		check( mvrt_trace_batch_cone( m_handle, n, rox, roy, roz, rdx, rdy, rdz, coneA, coneB, t, nMajor, level, cellCode, index, attrib, descents, stream ),
+			   "IntersectorOctreeGPU::intersectCone" );
+	}
+	void renderLod( const float camera[15], int width, int height, float lodScale, bool showVertexColor, uint8_t* rgbaDev, float* tDev, int32_t* nMajorDev, uint32_t* levelDev,
+					uint32_t* descentsDev, void* stream ) const
+	{
+		check( mvrt_render_primary_lod( m_handle, camera, width, height, lodScale, showVertexColor ? 1 : 0, rgbaDev, tDev, nMajorDev, levelDev, descentsDev, stream ),
+			   "IntersectorOctreeGPU::renderLod" );
+	}
+
 	mvrt_svo* handle() const { return m_handle; }
 
 	// re-bind to a handle owned by someone else (PathTracer::m_intersectorOctreeGPU is a VALUE member in the reference, PathTracer.hpp:18)

@@ -11,6 +11,8 @@
 //     intersectRange( [stack,] ro, rd, tMax, &t, &nMajor, &vIndex, isShadowRay )   the same ray, limited to t <= tMax (see below)
 //     intersectRangeEx( ..., &descents )
 //     occluded( [stack,] ro, rd, tMax )                                 shadow ray with the limit: true when something is hit within tMax
+//     intersectCone( [stack,] ro, rd, coneA, coneB, &t, &nMajor, &level, &cellCode )   the same ray, stopped at its own level of detail (see below)
+//     intersectConeEx( ..., &descents )
 //     getVoxelColor( vIndex ), getVoxelEmission( vIndex, withScale ), hasEmission()
 //
 // Results equal mvrt_trace_batch's bit for bit (t, nMajor, vIndex, descents; MVRT_MAX_FLOAT / -1 / 0 on a miss, vIndex 0 for
@@ -27,6 +29,18 @@
 // stops early once the candidate child's entry time exceeds tMax by a margin that covers the fp32 rounding of the entry times along the walk
 // (DESIGN.md 5.12 derives it); rays whose slab deltas are not all finite are never cut, only filtered.  descents of a limited ray = the child
 // fetches it made: at most the unlimited ray's, equal to them on an accepted hit.
+//
+// Cone limit: the ray's footprint at time S is f = coneA + coneB * S (one product, one sum, each rounded).  On the FIRST visit of an inner node
+// at level in [1, levels - 1], with S = the node's entry time of that iteration, the node is terminal iff 0 < S and size <= f, size = dps * 2^levels * 2^-level
+// (exact).  A terminal node reports the hit a voxel in its place would: t = S, nMajor by the voxel's rule, level = the node's level, cellCode = the path to it (3
+// bits per level = the Morton code of any voxel below it >> 3 * ( levels - level )).  A voxel hit reports level = levels and the voxel's Morton code; a miss
+// MVRT_MAX_FLOAT, -1, 0, 0.  The root is never terminal, a node with S <= 0 is descended into as always, and a node is not tested again after a pop.  Every slab
+// time derives from the root's times and the level alone, so a walk stopped at depth D reports bit for bit the t and nMajor of the same ray against the octree
+// coarsened to D levels (mvrt_svo_coarsen keeps lower and upper bit-identical).  What follows from the rule:
+//   * coneA = coneB = 0, any negative footprint and NaN give the unlimited ray's t, nMajor and descents, bit for bit (the compare is false for them);
+//   * the cone ray's descents never exceed the unlimited ray's: it is the same walk up to the first terminal node;
+//   * where the unlimited ray hits, the cone ray hits too (at that voxel or at a node on the walk before it);
+//   * a cone ray may hit where the unlimited ray misses: a coarse cell is solid to it.
 //
 // Floating point: bit-exactness needs every product and sum rounded on its own.  Every function here that does fp32 arithmetic
 // opens with `#pragma clang fp contract(off)`, which clang honours under hipcc's default and under -ffp-contract=on.
@@ -217,9 +231,42 @@ struct DeviceOctree
 		return t != detail::kMaxFloat;
 	}
 
+	// The cone-limited ray (see the head of this file): level = the depth the walk stopped at (view.levels at a voxel), cellCode = the 3-bits-per-level path to
+	// that cell = the Morton code of any voxel below it >> 3 * ( levels - level ).  A miss reports MVRT_MAX_FLOAT, -1, 0, 0
+	__device__ void intersectCone( float3 ro, float3 rd, float coneA, float coneB, float* t, int* nMajor, uint32_t* level, uint64_t* cellCode ) const
+	{
+		StackEntry stack[MVRT_DEVICE_MAX_LEVELS];
+		uint32_t descents;
+		intersectConeEx( stack, ro, rd, coneA, coneB, t, nMajor, level, cellCode, &descents );
+	}
+	__device__ void intersectCone( StackEntry* stack, float3 ro, float3 rd, float coneA, float coneB, float* t, int* nMajor, uint32_t* level, uint64_t* cellCode ) const
+	{
+		uint32_t descents;
+		intersectConeEx( stack, ro, rd, coneA, coneB, t, nMajor, level, cellCode, &descents );
+	}
+	__device__ void intersectConeEx( float3 ro, float3 rd, float coneA, float coneB, float* t, int* nMajor, uint32_t* level, uint64_t* cellCode, uint32_t* descents ) const
+	{
+		StackEntry stack[MVRT_DEVICE_MAX_LEVELS];
+		intersectConeEx( stack, ro, rd, coneA, coneB, t, nMajor, level, cellCode, descents );
+	}
+	__device__ void intersectConeEx( StackEntry* stack, float3 ro, float3 rd, float coneA, float coneB, float* t, int* nMajor, uint32_t* level, uint64_t* cellCode,
+									 uint32_t* descents ) const
+	{
+		uint32_t vIndex;
+		walk<false, true>( stack, ro, rd, 0.0f, t, nMajor, &vIndex, false, descents, coneA, coneB, level, cellCode );
+	}
+
 	// the walk of every method above.  RANGE = false is the unlimited ray: tMax is not read and no compare is added to the loop
 	template <bool RANGE>
 	__device__ void walk( StackEntry* stack, float3 ro, float3 rd, float tMax, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay, uint32_t* descentsOut ) const
+	{
+		walk<RANGE, false>( stack, ro, rd, tMax, t, nMajor, vIndex, isShadowRay, descentsOut, 0.0f, 0.0f, nullptr, nullptr );
+	}
+	// ... with its second flag: CONE = true is the cone-limited ray (intersectCone).  coneA, coneB, levelOut and codeOut are read and written by it alone, and
+	// its vIndex stays 0 (DeviceLod::lookup gives the index); CONE = false adds nothing to the loop
+	template <bool RANGE, bool CONE>
+	__device__ void walk( StackEntry* stack, float3 ro, float3 rd, float tMax, float* t, int* nMajor, uint32_t* vIndex, bool isShadowRay, uint32_t* descentsOut, float coneA,
+						  float coneB, uint32_t* levelOut, uint64_t* codeOut ) const
 	{
 		MVRT_DEVICE_FP_STRICT
 		using namespace detail;
@@ -230,6 +277,11 @@ struct DeviceOctree
 		*nMajor = -1;
 		*vIndex = 0;
 		*descentsOut = 0;
+		if( CONE )
+		{
+			*levelOut = 0;
+			*codeOut = 0;
+		}
 		if( RANGE && !( 0.0f < tMax ) ) return; // a hit has 0 < t: nothing lies within such a limit (NaN included)
 		// ray setup, voxCommon.hpp:240-278
 		float ix = 1.0f / rd.x, iy = 1.0f / rd.y, iz = 1.0f / rd.z;
@@ -284,6 +336,7 @@ struct DeviceOctree
 		uint32_t level = 0, childMask = 8u /* first visit */, pending = 0, descents = 0;
 		uint64_t resume = 0; // 3 bits per pending level: the candidate a popped node resumes with
 		uint64_t path = 0;	 // child indices root -> current node, 3 bits per level
+		const float rootEdge = CONE ? view.dps * __uint_as_float( ( 127u + view.levels ) << 23 ) : 0.0f; // dps * 2^levels
 		for( ;; )
 		{
 			const float scale = __uint_as_float( ( 127u - level ) << 23 ); // 2^-level
@@ -300,13 +353,34 @@ struct DeviceOctree
 					if( RANGE && !( S <= tMax ) ) return; // the unlimited ray's hit lies beyond the limit: a miss
 					*t = S;
 					*nMajor = ( S == tx0 ) ? 1 : ( ( S == ty0 ) ? 2 : 0 );
-					if( !isShadowRay ) *vIndex = voxelIndexFromPath( path );
+					if( CONE )
+					{
+						*levelOut = level;
+						*codeOut = path;
+					}
+					else if( !isShadowRay )
+						*vIndex = voxelIndexFromPath( path );
 					return;
 				}
 				pop = true;
 			}
 			else
 			{
+				// CONE: an inner node below the root, entered in front of the origin and no larger than the ray's footprint there, is solid: it reports
+				// the hit a voxel in its place would.  Tested on the first visit only, never after a pop
+				if( CONE && ( childMask & 8u ) && level != 0u && level < view.levels )
+				{
+					const float f = coneA + coneB * S;
+					if( 0.0f < S && rootEdge * scale <= f ) // (false for a NaN or negative f)
+					{
+						*descentsOut = descents;
+						*t = S;
+						*nMajor = ( S == tx0 ) ? 1 : ( ( S == ty0 ) ? 2 : 0 );
+						*levelOut = level;
+						*codeOut = path;
+						return;
+					}
+				}
 				const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
 				const float tyM = 0.5f * ( ty0 + ty1 );
 				const float tzM = 0.5f * ( tz0 + tz1 );
@@ -407,5 +481,40 @@ struct DeviceOctree
 
 private:
 	__device__ const uint2* attrs() const { return (const uint2*)(uintptr_t)view.attrs; }
+};
+
+// The attribute pyramid of an octree (mvrt_svo_lod_prepare, mvrt_svo_lod_view): per level the occupied cells as ascending codes, with their mean attributes.
+// The octree is a DAG -- subtrees of equal shape share their nodes whatever their colours --, so attributes are keyed by the cell's code, not by the node
+struct DeviceLod
+{
+	mvrt_device_lod view;
+
+	DeviceLod() = default;
+	__host__ __device__ explicit DeviceLod( const mvrt_device_lod& v ) : view( v ) {}
+
+	// the rank of cellCode among the cells of `level` in [1, view.levels] (binary search); false when the level holds no such cell.  At level == view.levels the
+	// rank is the voxel's vIndex
+	__host__ __device__ bool lookup( uint32_t level, uint64_t cellCode, uint32_t* index ) const
+	{
+		if( level == 0u || level > view.levels ) return false;
+		const uint64_t* const codes = (const uint64_t*)(uintptr_t)view.codes[level];
+		uint32_t lo = 0, hi = view.count[level];
+		while( lo < hi )
+		{
+			const uint32_t mid = lo + ( hi - lo ) / 2u;
+			if( codes[mid] < cellCode ) lo = mid + 1u;
+			else hi = mid;
+		}
+		if( lo == view.count[level] || codes[lo] != cellCode ) return false;
+		*index = lo;
+		return true;
+	}
+	// the 8-byte attribute {colour, emission} of cell `index` of `level`
+	__host__ __device__ uint2 attrib( uint32_t level, uint32_t index ) const { return ( (const uint2*)(uintptr_t)view.attrs[level] )[index]; }
+	__host__ __device__ uchar4 color( uint32_t level, uint32_t index ) const
+	{
+		const uint32_t c = attrib( level, index ).x;
+		return make_uchar4( c & 0xFF, ( c >> 8 ) & 0xFF, ( c >> 16 ) & 0xFF, ( c >> 24 ) & 0xFF );
+	}
 };
 } // namespace mvrt

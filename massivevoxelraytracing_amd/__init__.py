@@ -38,6 +38,11 @@ class DeviceOctree(C.Structure):
                 ("treeRoot", _u32), ("cellBits", _u32)]
 
 
+class DeviceLod(C.Structure):
+    """mvrt_device_lod (include/mvrt.h): the view of the attribute pyramid a user kernel takes by value (mvrt::DeviceLod, include/mvrt/device.hpp)"""
+    _fields_ = [("structBytes", _u32), ("levels", _u32), ("codes", _u64 * 17), ("attrs", _u64 * 17), ("cellVoxels", _u64 * 17), ("count", _u32 * 17), ("reserved", _u32)]
+
+
 class PtStats(C.Structure):
     _fields_ = [("samples", _u64), ("rays", _u64), ("shadowRays", _u64), ("descents", _u64), ("shadowDescents", _u64), ("hits", _u64), ("traceLaunches", _u64),
                 ("traceKernelMs", C.c_double), ("shadeKernelMs", C.c_double), ("totalKernelMs", C.c_double)]
@@ -160,6 +165,12 @@ SIGNATURES = {
     "mvrt_trace_batch_hinted": (_i32, [_vp, _u64] + [_vp] * 12 + [_vp]),
     "mvrt_trace_batch_host": (_i32, [_vp, _u64] + [_vp] * 7),
     "mvrt_trace_batch_range": (_i32, [_vp, _u64] + [_vp] * 12 + [_vp]),
+    "mvrt_trace_batch_cone": (_i32, [_vp, _u64] + [_vp] * 15 + [_vp]),
+    "mvrt_render_primary_lod": (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_svo_lod_prepare": (_i32, [_vp, _vp]),
+    "mvrt_svo_lod_release": (_i32, [_vp]),
+    "mvrt_svo_lod_bytes": (_u64, [_vp]),
+    "mvrt_svo_lod_view": (_i32, [_vp, _vp]),
     "mvrt_ao_directions": (_i32, [_i32, _vp]),
     "mvrt_svo_surface_ao": (_i32, [_vp, _u64, _vp, _vp, _i32, _f32, _vp, _vp]),
     "mvrt_render_primary": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -962,6 +973,70 @@ class IntersectorOctreeGPU:
 
     def intersect_range_device(self, n, rox, roy, roz, rdx, rdy, rdz, isShadow, tMax, t, nMajor=None, vIndex=None, descents=None, stream=None):
         _check(lib().mvrt_trace_batch_range(self._h, n, *[_dev_ptr(a) for a in (rox, roy, roz, rdx, rdy, rdz, isShadow, tMax, t, nMajor, vIndex, descents)], stream))
+
+    def lod_prepare(self, stream=None):
+        """mvrt_svo_lod_prepare: attach the attribute pyramid of the cone-limited rays (per level the cells of coarse_voxels(levels - L, 1)); returns its size in
+        bytes.  Every build, edit, rebuild, upload, coarsen in place and cleanUp drops it."""
+        _check(lib().mvrt_svo_lod_prepare(self._h, stream))
+        return self.lod_bytes()
+
+    def lod_release(self):
+        _check(lib().mvrt_svo_lod_release(self._h))
+
+    def lod_bytes(self):
+        """mvrt_svo_lod_bytes: the size of the pyramid, 0 without one"""
+        return int(lib().mvrt_svo_lod_bytes(self._h))
+
+    def lod_view(self):
+        """mvrt_svo_lod_view: the ctypes DeviceLod a HIP kernel built on include/mvrt/device.hpp takes by value.  A snapshot, like device_view()."""
+        v = DeviceLod()
+        _check(lib().mvrt_svo_lod_view(self._h, C.byref(v)))
+        return v
+
+    def lod_level(self, level):
+        """level `level` in [1, levels - 1] of the prepared pyramid on the host: {code (n,) uint64, attribs (n, 8) uint8, count (n,) uint32}"""
+        v = self.lod_view()
+        if not 1 <= level < v.levels:
+            raise ValueError("level %d is outside [1, %d]" % (level, v.levels - 1))
+        n = v.count[level]
+        out = {"code": np.empty(n, np.uint64), "attribs": np.empty((n, 8), np.uint8), "count": np.empty(n, np.uint32)}
+        for key, ptr in (("code", v.codes[level]), ("attribs", v.attrs[level]), ("count", v.cellVoxels[level])):
+            if n:
+                _check(lib().mvrt_memcpy_d2h(_hp(out[key]), ptr, out[key].nbytes, None))
+        return out
+
+    def intersect_cone(self, ro, rd, coneA, coneB, want_attribs=False):
+        """mvrt_trace_batch_cone on packed host arrays (n,3) and one cone per ray (scalars = the same for all): {t, nMajor, level, cellCode, descents} and, with
+        want_attribs (needs lod_prepare), index and attribs (n, 8)"""
+        ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
+        rd = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
+        n = len(ro)
+        dev = [DeviceArray.from_host(np.ascontiguousarray(a)) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
+        dev += [DeviceArray.from_host(np.ascontiguousarray(np.broadcast_to(np.asarray(c, np.float32), (n,)))) for c in (coneA, coneB)]
+        t, nm, lv, code, de = DeviceArray(n, np.float32), DeviceArray(n, np.int32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint64), DeviceArray(n, np.uint32)
+        idx, at = (DeviceArray(n, np.uint32), DeviceArray((n, 8), np.uint8)) if want_attribs else (None, None)
+        self.intersect_cone_device(n, *dev, t, nm, lv, code, idx, at, de)
+        synchronize()
+        out = {"t": t.to_host(), "nMajor": nm.to_host(), "level": lv.to_host(), "cellCode": code.to_host(), "descents": de.to_host()}
+        if want_attribs:
+            out.update(index=idx.to_host(), attribs=at.to_host())
+        return out
+
+    def intersect_cone_device(self, n, rox, roy, roz, rdx, rdy, rdz, coneA, coneB, t, nMajor=None, level=None, cellCode=None, index=None, attrib=None, descents=None,
+                              stream=None):
+        _check(lib().mvrt_trace_batch_cone(self._h, n, *[_dev_ptr(a) for a in (rox, roy, roz, rdx, rdy, rdz, coneA, coneB, t, nMajor, level, cellCode, index, attrib,
+                                                                                 descents)], stream))
+
+    def render_lod(self, camera, width, height, lodScale, showVertexColor=False, stream=None):
+        """mvrt_render_primary_lod: render() with one cone per pixel, lodScale pixels wide; returns host arrays {rgba, t, nMajor, level, descents}.
+        showVertexColor needs lod_prepare."""
+        cam = np.ascontiguousarray(camera, np.float32)
+        n = width * height
+        rgba, t, nm, lv, de = DeviceArray((n, 4), np.uint8), DeviceArray(n, np.float32), DeviceArray(n, np.int32), DeviceArray(n, np.uint32), DeviceArray(n, np.uint32)
+        _check(lib().mvrt_render_primary_lod(self._h, _hp(cam), width, height, float(np.float32(lodScale)), int(showVertexColor), rgba.ptr, t.ptr, nm.ptr, lv.ptr, de.ptr,
+                                             stream))
+        _check(lib().mvrt_stream_synchronize(stream))
+        return {"rgba": rgba.to_host(), "t": t.to_host(), "nMajor": nm.to_host(), "level": lv.to_host(), "descents": de.to_host()}
 
     def surface_ao_device(self, nFaces, faceVoxel, faceDir, samples, radius, open, stream=None):
         """mvrt_svo_surface_ao into a caller device array of nFaces uint16: per face the number of `samples` occlusion rays that are open within `radius`.

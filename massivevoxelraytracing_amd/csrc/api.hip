@@ -365,6 +365,7 @@ int editHandle( mvrt_svo* svo, const char* who, int accepts, const uint32_t* xyz
 {
 	if( ownerDrain( svo ) ) return 1; // steps already issued render the old scene; an attribute-only edit writes in place
 	Octree& o = svo->oct;
+	o.lod = LodPyramid(); // the edit may write attributes in place: the pyramid does not outlive the voxels it describes
 	SvoBuildResult r;
 	int structural = 0;
 	uint32_t he = 0;
@@ -669,6 +670,40 @@ MVRT_EXPORT int mvrt_svo_surface_ao( const mvrt_svo* svo, uint64_t nFaces, const
 	mvrt_device_octree view;
 	if( rangeView( svo, "mvrt_svo_surface_ao", &view ) ) return 1;
 	return surfaceAo( view, s.morton, nFaces, faceVoxelDev, faceDirDev, samples, radius, openDev, (hipStream_t)stream );
+}
+
+// Cone-limited rays (kernels_lod.hip): the same per-lane walk, so the octrees of rangeView; the pyramid is asked for only where an output needs it
+MVRT_EXPORT int mvrt_trace_batch_cone( const mvrt_svo* svo, uint64_t n, const float* roxDev, const float* royDev, const float* rozDev, const float* rdxDev, const float* rdyDev,
+									   const float* rdzDev, const float* coneADev, const float* coneBDev, float* tDev, int32_t* nMajorDev, uint32_t* levelDev, uint64_t* cellCodeDev,
+									   uint32_t* indexDev, uint32_t* attribDev, uint32_t* descentsDev, void* stream )
+{
+	REQUIRE( coneADev && coneBDev, "mvrt_trace_batch_cone: coneADev and coneBDev are required (one cone per ray)" );
+	REQUIRE( tDev, "mvrt_trace_batch_cone: t output is required" );
+	REQUIRE( n == 0 || ( roxDev && royDev && rozDev && rdxDev && rdyDev && rdzDev ), "mvrt_trace_batch_cone: null ray array" );
+	REQUIRE( svo && !svo->empty(), "mvrt_trace_batch_cone: no octree (build or upload first)" );
+	mvrt_device_octree view;
+	if( rangeView( svo, "mvrt_trace_batch_cone", &view ) ) return 1;
+	mvrt_device_lod lod;
+	const bool needLod = indexDev || attribDev;
+	REQUIRE( !needLod || svo->oct.lod.ready, "mvrt_trace_batch_cone: %s needs the attribute pyramid (mvrt_svo_lod_prepare first)", indexDev ? "indexDev" : "attribDev" );
+	if( needLod && mvrt_svo_lod_view( svo, &lod ) ) return 1;
+	return launchTraceCone( view, needLod ? &lod : nullptr, n, roxDev, royDev, rozDev, rdxDev, rdyDev, rdzDev, coneADev, coneBDev, tDev, nMajorDev, levelDev, cellCodeDev, indexDev,
+							attribDev, descentsDev, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_render_primary_lod( const mvrt_svo* svo, const float camera[15], int width, int height, float lodScale, int showVertexColor, uint8_t* rgbaDev, float* tDev,
+										 int32_t* nMajorDev, uint32_t* levelDev, uint32_t* descentsDev, void* stream )
+{
+	REQUIRE( camera, "mvrt_render_primary_lod: null camera" );
+	REQUIRE( width > 0 && height > 0, "mvrt_render_primary_lod: bad resolution %dx%d", width, height );
+	REQUIRE( svo && !svo->empty(), "mvrt_render_primary_lod: no octree (build or upload first)" );
+	mvrt_device_octree view;
+	if( rangeView( svo, "mvrt_render_primary_lod", &view ) ) return 1;
+	mvrt_device_lod lod;
+	const bool needLod = showVertexColor && rgbaDev;
+	REQUIRE( !needLod || svo->oct.lod.ready, "mvrt_render_primary_lod: showVertexColor needs the attribute pyramid (mvrt_svo_lod_prepare first)" );
+	if( needLod && mvrt_svo_lod_view( svo, &lod ) ) return 1;
+	const float coneB = lodScale * ( ( 2.0f * camera[12] ) / (float)height ); // lodScale pixels' width at rd . front = 1
+	return launchRenderLod( view, needLod ? &lod : nullptr, camera, width, height, coneB, (uchar4*)rgbaDev, tDev, nMajorDev, levelDev, descentsDev, (hipStream_t)stream );
 }
 
 MVRT_EXPORT int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const float* roHost, const float* rdHost, const uint8_t* isShadowHost, float* tHost,

@@ -70,6 +70,9 @@ struct Octree : SvoBuildResult
 	uint8_t rootMask = 0;
 	uint32_t leafPsumIsPopcount = 1; // (uploads: checked, see launchCheckLeafPsum)
 	int buildFlags = 0;				 // MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK of the build, kept by edits
+	// the attribute pyramid (mvrt_svo_lod_prepare): part of the octree record, so whatever replaces or clears the octree drops it; an edit that rewrites
+	// the attributes in place drops it by hand (editHandle)
+	LodPyramid lod;
 };
 struct mvrt_svo
 {

@@ -194,6 +194,50 @@ MVRT_EXPORT int mvrt_svo_coarsen( const mvrt_svo* src, mvrt_svo* dst, int levels
 	return adoptSortedOnGrid( dst, v, nFine, info.lower, dps, gridRes, buildFlags, nullptr, st ); // (the source is read before the old octree of dst goes)
 }
 
+// The attribute pyramid of the cone-limited rays (kernels_lod.hip): the listing above once per level, kept with the handle.  The refusals are the listing's, with its
+// words, then the two of the device view the pyramid is read through.  The old pyramid goes first; the new one is moved in whole or not at all
+MVRT_EXPORT int mvrt_svo_lod_prepare( mvrt_svo* svo, void* stream )
+{
+	REQUIRE( svo, "mvrt_svo_lod_prepare: null handle" );
+	REQUIRE( !svo->empty(), "mvrt_svo_lod_prepare: no octree (build first)" );
+	REQUIRE( svo->oct.morton.p, "mvrt_svo_lod_prepare: an uploaded octree keeps no Morton codes" );
+	REQUIRE( !svo->oct.tree, "mvrt_svo_lod_prepare: tree-flavour octrees (MVRT_FLAVOUR_TREE) are not supported" );
+	REQUIRE( svo->oct.info.levels <= MVRT_DEVICE_MAX_LEVELS, "mvrt_svo_lod_prepare: %u levels, the device API supports at most %d", svo->oct.info.levels, MVRT_DEVICE_MAX_LEVELS );
+	Octree& o = svo->oct;
+	o.lod = LodPyramid();
+	return lodBuild( o.morton.as<uint64_t>(), o.attrs.as<uint2>(), o.nVoxels, o.info.levels, &o.lod, (hipStream_t)stream );
+}
+MVRT_EXPORT int mvrt_svo_lod_release( mvrt_svo* svo )
+{
+	REQUIRE( svo, "mvrt_svo_lod_release: null handle" );
+	svo->oct.lod = LodPyramid();
+	return 0;
+}
+MVRT_EXPORT uint64_t mvrt_svo_lod_bytes( const mvrt_svo* svo ) { return svo && svo->oct.lod.ready ? svo->oct.lod.bytes() : 0; }
+MVRT_EXPORT int mvrt_svo_lod_view( const mvrt_svo* svo, mvrt_device_lod* out )
+{
+	REQUIRE( svo && out, "mvrt_svo_lod_view: null argument" );
+	REQUIRE( !svo->empty(), "mvrt_svo_lod_view: no octree (build first)" );
+	const Octree& o = svo->oct;
+	REQUIRE( o.lod.ready, "mvrt_svo_lod_view: no attribute pyramid (mvrt_svo_lod_prepare first)" );
+	mvrt_device_lod v;
+	memset( &v, 0, sizeof( v ) );
+	v.structBytes = sizeof( mvrt_device_lod );
+	v.levels = o.info.levels;
+	for( uint32_t L = 1; L < o.info.levels; L++ )
+	{
+		v.codes[L] = (uint64_t)(uintptr_t)o.lod.codes[L].p;
+		v.attrs[L] = (uint64_t)(uintptr_t)o.lod.attrs[L].p;
+		v.cellVoxels[L] = (uint64_t)(uintptr_t)o.lod.counts[L].p;
+		v.count[L] = o.lod.n[L];
+	}
+	v.codes[o.info.levels] = (uint64_t)(uintptr_t)o.morton.p; // the last level is the voxel list itself: the rank is the vIndex
+	v.attrs[o.info.levels] = (uint64_t)(uintptr_t)o.attrs.p;
+	v.count[o.info.levels] = o.nVoxels;
+	*out = v;
+	return 0;
+}
+
 // Dilation, erosion, closing and opening (kernels_morph.hip).  Every refusal the arguments and the handle decide is made here, on the host.  The listings read the
 // sorted codes and the attributes alone; the in-place calls run their steps on sorted lists next to the old octree and build the levels once, from the last list.
 static int morphSource( const mvrt_svo* svo, const char* who, int element, SurfaceSource* s )
@@ -398,6 +442,7 @@ MVRT_EXPORT int mvrt_svo_combine( mvrt_svo* a, const mvrt_svo* b, int op, const 
 	{
 		if( !c.recolours ) return 0; // nothing changes: the handle is not touched
 		if( ownerDrain( a ) ) return 1; // steps already issued render the old scene; a recolouring writes in place
+		a->oct.lod = LodPyramid();		// (as editHandle: the pyramid's means are of the colours about to go)
 		MVRT_HIP( hipMemcpyAsync( a->oct.attrs.p, c.list.attrs.p, (uint64_t)c.list.n * 8, hipMemcpyDeviceToDevice, st ) );
 		MVRT_HIP( hipStreamSynchronize( st ) );
 		a->oct.totalDumped = 0;

@@ -275,6 +275,21 @@ int coarseVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, int le
 	return 0;
 }
 
+int coarseCells( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, DevBuf& codes, DevBuf& attribs, DevBuf& counts, uint32_t* nCells, hipStream_t st )
+{
+	Reduced r;
+	if( reduceCells( morton, attrs, n, (uint32_t)levelsDown, 1, false, &r, st ) ) return 1;
+	DevBuf a;
+	if( a.alloc( (uint64_t)r.nSeg * 8 ) ) return 1;
+	if( launchEmit( r, 1, nullptr, a.as<uint32_t>(), nullptr, nullptr, nullptr, st ) ) return 1;
+	MVRT_HIP( hipStreamSynchronize( st ) ); // (the sums are released on return)
+	codes = std::move( r.segCode ); // every cell is kept: the reduce's own arrays are the listing's, in its order
+	counts = std::move( r.counts );
+	attribs = std::move( a );
+	*nCells = r.nSeg;
+	return 0;
+}
+
 int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, SortedVoxels& out, hipStream_t st )
 {
 	Reduced r;

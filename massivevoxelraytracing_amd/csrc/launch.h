@@ -338,6 +338,9 @@ int coarseVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, int le
 				  uint32_t* countDev, uint64_t* nOut, hipStream_t stream );
 // the same list as sorted codes and attributes for svoBuildFromSorted (left empty when no cell is kept: the caller looks at out.n)
 int coarseList( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, uint64_t minCount, SortedVoxels& out, hipStream_t stream );
+// every cell of the listing with minCount = 1 as device arrays allocated here, in its order: ascending codes, attributes and voxel counts (*nCells >= 1 of each).
+// On failure the three arrays are left as they were
+int coarseCells( const uint64_t* morton, const uint2* attrs, uint32_t n, int levelsDown, DevBuf& codes, DevBuf& attribs, DevBuf& counts, uint32_t* nCells, hipStream_t stream );
 
 // dilation, erosion, closing and opening (kernels_morph.hip; mvrt_svo_dilation_cells / _erosion_voxels / _dilate / _erode / _close / _open): morton, attrs, nVoxels
 // and levels of the source are read, element is MVRT_MORPH_FACES or MVRT_MORPH_CUBE, checked by the caller.  The calls block, keep their scratch in DevBufs and
@@ -426,6 +429,32 @@ int svoReadVoxels( const uint64_t* morton, const uint2* attrs, uint32_t n, uint3
 struct mvrt_device_octree;
 int launchTraceRange( const mvrt_device_octree& view, uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz,
 					  const uint8_t* isShadow, const float* tMax, float* t, int32_t* nMajor, uint32_t* vIndex, uint32_t* descents, hipStream_t stream );
+// level of detail per ray (kernels_lod.hip; mvrt_svo_lod_prepare / mvrt_trace_batch_cone / mvrt_render_primary_lod): the attribute pyramid of a built octree and
+// the cone walk of include/mvrt/device.hpp (DeviceOctree::intersectConeEx, DeviceLod) on the views mvrt_svo_device_view and mvrt_svo_lod_view fill.
+// Entry L of the pyramid = level L in [1, levels - 1]: what coarseCells lists with levelsDown = levels - L.  It owns its arrays; an octree handle keeps one
+// (api_handles.h, Octree) so that whatever replaces or clears the octree drops it
+struct LodPyramid
+{
+	DevBuf codes[16], attrs[16], counts[16];
+	uint32_t n[16] = { 0 };
+	uint32_t ready = 0;
+	uint64_t bytes() const
+	{
+		uint64_t b = 0;
+		for( int l = 0; l < 16; l++ ) b += codes[l].bytes + attrs[l].bytes + counts[l].bytes;
+		return b;
+	}
+};
+// builds every level from the n sorted codes and attributes of a build with levels in [1, 16]; blocks.  On failure *out is left empty
+int lodBuild( const uint64_t* morton, const uint2* attrs, uint32_t n, uint32_t levels, LodPyramid* out, hipStream_t stream );
+struct mvrt_device_lod;
+// lod == nullptr: index and attrib are null too.  Asynchronous
+int launchTraceCone( const mvrt_device_octree& view, const mvrt_device_lod* lod, uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy,
+					 const float* rdz, const float* coneA, const float* coneB, float* t, int32_t* nMajor, uint32_t* level, uint64_t* cellCode, uint32_t* index, uint32_t* attrib,
+					 uint32_t* descents, hipStream_t stream );
+// lod == nullptr: the hit normal is the colour.  Asynchronous
+int launchRenderLod( const mvrt_device_octree& view, const mvrt_device_lod* lod, const float camera[15], int W, int H, float coneB, uchar4* rgba, float* t, int32_t* nMajor,
+					 uint32_t* level, uint32_t* descents, hipStream_t stream );
 bool aoSamplesOk( int samples );				// a power of two in [1, 256]
 void aoDirections( int samples, float* dirs ); // host only: 6 * samples * 3 floats
 int surfaceAo( const mvrt_device_octree& view, const uint64_t* morton, uint64_t nFaces, const uint32_t* faceVoxel, const uint8_t* faceDir, int samples, float radius,
