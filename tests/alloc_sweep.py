@@ -7,18 +7,8 @@ fake library and sees each of their assertions fire."""
 import numpy as np
 import pytest
 
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def filled(mv, shape, dtype):
-    """(device array, host copy) of the canary byte 0x5A"""
-    host = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(host), host
+from fixtures import mv  # noqa: F401 (the fixture, for the sweep files)
+from voxel_sets import filled, same  # noqa: F401 (filled: for the sweep files)
 
 
 def bits(a):
@@ -27,10 +17,6 @@ def bits(a):
 
 def with_morton(handle):
     return handle.download(want_morton=True)
-
-
-def same(a, b):
-    return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
 
 
 def snapshot(handle, download=with_morton):

@@ -31,6 +31,24 @@ def compile_usage(tmp_path, name, missing="skip"):
     return exe, libdir
 
 
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def run_host_probe(tmp_path, name, ok_line, sanitize=False, timeout=120):
+    """tests/hip/<name>.hip, a program of its own that makes no HIP call (the host pass is all of it), compiled for the host with hipcc and run directly; it has
+    to end with status 0 and print ok_line.  sanitize: built with the address and undefined-behaviour sanitizers, whose reports fail the run."""
+    import subprocess
+    exe = str(tmp_path / name)
+    extra = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", "-Xarch_host", "-fno-omit-frame-pointer"] if sanitize else []
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O1" if sanitize else "-O2", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function",
+                        "-Wno-unused-result"] + extra + [os.path.join(HERE, "hip", name + ".hip"), "-o", exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=timeout)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert ok_line in r.stdout and "runtime error" not in r.stderr, r.stdout + r.stderr
+
+
 def golden():
     with open(os.path.join(GOLDEN, "survey_appendix_a.json")) as f:
         return json.load(f)

@@ -154,7 +154,7 @@ class DeepScene:
         return ro, rd
 
     def tie_rays(self, n, seed):
-        """like tests/test_gpu_device_api.py's tie_rays at the deep levels: diagonals through lattice points (cell corners of the last 6 levels)
+        """like tests/rays.py's tie_rays at the deep levels: diagonals through lattice points (cell corners of the last 6 levels)
         next to the clusters from dyadic distances outside the grid, and from ON those lattice points"""
         rng = np.random.default_rng(seed)
         pts = np.concatenate(list(self.clusters.values()))

@@ -10,38 +10,7 @@
 #include <vector>
 
 #include "../../massivevoxelraytracing_amd/csrc/voxel_passes.h"
-
-static int g_failures = 0;
-#define CHECK( cond, ... )                     \
-	do                                         \
-	{                                          \
-		if( !( cond ) )                        \
-		{                                      \
-			if( g_failures++ < 20 )            \
-			{                                  \
-				printf( "FAILED %s: ", #cond ); \
-				printf( __VA_ARGS__ );         \
-				printf( "\n" );                \
-			}                                  \
-		}                                      \
-	} while( 0 )
-
-static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() // xorshift64
-{
-	g_rng ^= g_rng << 13;
-	g_rng ^= g_rng >> 7;
-	g_rng ^= g_rng << 17;
-	return g_rng;
-}
-
-// brute force: the code of (x, y, z) bit by bit
-static uint64_t encodeSlow( uint32_t x, uint32_t y, uint32_t z )
-{
-	uint64_t c = 0;
-	for( int b = 0; b < 21; b++ ) c |= (uint64_t)( ( x >> b ) & 1u ) << ( 3 * b ) | (uint64_t)( ( y >> b ) & 1u ) << ( 3 * b + 1 ) | (uint64_t)( ( z >> b ) & 1u ) << ( 3 * b + 2 );
-	return c;
-}
+#include "host_check.h"
 
 static void checkReachAndKeys()
 {

@@ -8,37 +8,7 @@
 #include <vector>
 
 #include "../../massivevoxelraytracing_amd/csrc/voxel_passes.h"
-
-static int g_failures = 0;
-#define CHECK( cond, ... )                     \
-	do                                         \
-	{                                          \
-		if( !( cond ) )                        \
-		{                                      \
-			if( g_failures++ < 20 )            \
-			{                                  \
-				printf( "FAILED %s: ", #cond ); \
-				printf( __VA_ARGS__ );         \
-				printf( "\n" );                \
-			}                                  \
-		}                                      \
-	} while( 0 )
-
-static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() // xorshift64
-{
-	g_rng ^= g_rng << 13;
-	g_rng ^= g_rng >> 7;
-	g_rng ^= g_rng << 17;
-	return g_rng;
-}
-// brute force: the code of (x, y, z) bit by bit
-static uint64_t encodeSlow( uint64_t x, uint64_t y, uint64_t z )
-{
-	uint64_t c = 0;
-	for( int b = 0; b < 21; b++ ) c |= ( ( x >> b ) & 1ull ) << ( 3 * b ) | ( ( y >> b ) & 1ull ) << ( 3 * b + 1 ) | ( ( z >> b ) & 1ull ) << ( 3 * b + 2 );
-	return c;
-}
+#include "host_check.h"
 
 // one cell, one offset: inside exactly when every moved coordinate lies in [0, R), and then the code of the moved cell
 static void checkOne( long long x, long long y, long long z, const int32_t o[3], uint32_t levels )

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../massivevoxelraytracing_amd/csrc/voxel_passes.h"
+#include "host_check.h"
 
 #if defined( __has_feature )
 #if __has_feature( address_sanitizer )
@@ -21,30 +22,6 @@
 #define POISON( p, bytes ) ( (void)0 )
 #define UNPOISON( p, bytes ) ( (void)0 )
 #endif
-
-static int g_failures = 0;
-#define CHECK( cond, ... )                     \
-	do                                         \
-	{                                          \
-		if( !( cond ) )                        \
-		{                                      \
-			if( g_failures++ < 20 )            \
-			{                                  \
-				printf( "FAILED %s: ", #cond ); \
-				printf( __VA_ARGS__ );         \
-				printf( "\n" );                \
-			}                                  \
-		}                                      \
-	} while( 0 )
-
-static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() // xorshift64
-{
-	g_rng ^= g_rng << 13;
-	g_rng ^= g_rng >> 7;
-	g_rng ^= g_rng << 17;
-	return g_rng;
-}
 
 // A box of B^3 cells whose lowest cell is (o, o, o) in a grid of 2^L cells per axis.  The cells of the box's own border are empty, so an empty cell of the box is
 // exterior exactly when a 6-connected path of empty cells of the box joins it to that border

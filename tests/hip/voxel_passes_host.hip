@@ -5,30 +5,7 @@
 #include <vector>
 
 #include "../../massivevoxelraytracing_amd/csrc/voxel_passes.h"
-
-static int g_failures = 0;
-#define CHECK( cond, ... )                     \
-	do                                         \
-	{                                          \
-		if( !( cond ) )                        \
-		{                                      \
-			if( g_failures++ < 20 )            \
-			{                                  \
-				printf( "FAILED %s: ", #cond ); \
-				printf( __VA_ARGS__ );         \
-				printf( "\n" );                \
-			}                                  \
-		}                                      \
-	} while( 0 )
-
-static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() // xorshift64
-{
-	g_rng ^= g_rng << 13;
-	g_rng ^= g_rng >> 7;
-	g_rng ^= g_rng << 17;
-	return g_rng;
-}
+#include "host_check.h"
 
 // ---- codec ------------------------------------------------------------------------------------------------------------------------------------------------
 static uint64_t splitSlow( uint32_t a )

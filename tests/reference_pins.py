@@ -217,7 +217,7 @@ def reference_build(walk, tris, origin, dps, res, flags):
 
 # ---- voxel sets of the builder pins ---------------------------------------------------------------------------------------------------------------
 def voxel_set(levels, n_cluster, n_scattered, seed):
-    """the random voxel sets of tests/test_gpu_upload_shapes.py (random7 = (7, 20000, 2000, 7), random9 = (9, 30000, 3000, 9)): sorted unique codes"""
+    """the random voxel sets of tests/upload_shapes.py (random7 = (7, 20000, 2000, 7), random9 = (9, 30000, 3000, 9)): sorted unique codes"""
     rng = np.random.default_rng(seed)
     res = 1 << levels
     box = max(2, res // 3)
@@ -240,7 +240,7 @@ def builder_scenes(O):
 
 # ---- rays -----------------------------------------------------------------------------------------------------------------------------------------
 def random_rays(lo, hi, n, seed):
-    """tests/test_gpu_parity.py::random_rays on explicit bounds: a tenth each with a zero x / y / z component, 50 straight down, a tenth from inside"""
+    """tests/rays.py::random_rays on explicit bounds: a tenth each with a zero x / y / z component, 50 straight down, a tenth from inside"""
     rng = np.random.default_rng(seed)
     c = (lo + hi) / 2
     ext = (hi - lo).max()

@@ -1,52 +1,16 @@
 """Host applications on top of the boundary (apps/): file formats on CPU, the RTCamp-style batch driver on the GPU."""
 import os
 import shutil
-import struct
 import subprocess
-import zlib
 
 import numpy as np
 import pytest
 
 import common
 from common import GOLDEN, bunny_tris
+from voxel_mesh_app import read_png_rgba, write_reader_obj
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def write_obj(path, tris, with_colors=False):
-    v = tris.reshape(-1, 3)
-    with open(path, "w") as f:
-        f.write("# test mesh\n")
-        for i, p in enumerate(v):
-            if with_colors:
-                f.write("v %.9g %.9g %.9g %.3f %.3f %.3f\n" % (p[0], p[1], p[2], (i % 7) / 7.0, (i % 5) / 5.0, (i % 3) / 3.0))
-            else:
-                f.write("v %.9g %.9g %.9g\n" % tuple(p))
-        for t in range(len(v) // 3):
-            if t % 2:
-                f.write("f %d//%d %d//%d %d//%d\n" % (3 * t + 1, 1, 3 * t + 2, 1, 3 * t + 3, 1))
-            else:
-                f.write("f %d %d %d\n" % (3 * t + 1 - len(v) - 1, 3 * t + 2 - len(v) - 1, 3 * t + 3 - len(v) - 1))  # relative indices
-
-
-def read_png_rgba(path):
-    d = open(path, "rb").read()
-    assert d[:8] == b"\x89PNG\r\n\x1a\n"
-    pos, idat, w, h = 8, b"", 0, 0
-    while pos < len(d):
-        n, typ = struct.unpack(">I4s", d[pos:pos + 8])
-        body = d[pos + 8:pos + 8 + n]
-        assert struct.unpack(">I", d[pos + 8 + n:pos + 12 + n])[0] == zlib.crc32(typ + body) & 0xFFFFFFFF
-        if typ == b"IHDR":
-            w, h, depth, ctype = struct.unpack(">IIBB", body[:10])
-            assert (depth, ctype) == (8, 6)
-        elif typ == b"IDAT":
-            idat += body
-        pos += 12 + n
-    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, w * 4 + 1)
-    assert (raw[:, 0] == 0).all()
-    return raw[:, 1:].reshape(h, w, 4)
 
 
 def test_scene_io_formats(tmp_path):
@@ -57,7 +21,7 @@ def test_scene_io_formats(tmp_path):
     subprocess.check_call([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "apps"), os.path.join(ROOT, "tests", "cpp", "io_check.cpp"), "-o", str(exe)])
     tris = bunny_tris()[:500]
     obj = tmp_path / "m.obj"
-    write_obj(obj, tris, with_colors=True)
+    write_reader_obj(obj, tris, with_colors=True)
     out = subprocess.check_output([str(exe), str(obj), str(tmp_path / "a.png"), str(tmp_path / "a.ppm")]).split()
     v = np.loadtxt(obj, comments=["#", "f"], usecols=(1, 2, 3, 4, 5, 6), dtype=np.float64, converters={0: lambda s: 0.0}) if False else None
     pts = tris.reshape(-1, 3).astype(np.float64)
@@ -92,7 +56,7 @@ def test_batch_driver_frames_match_the_oracle(tmp_path):
     exe = b.build_apps(verbose=False)
     tris = bunny_tris()
     obj = tmp_path / "bunny.obj"
-    write_obj(obj, tris)
+    write_reader_obj(obj, tris)
     hdr = os.path.join(GOLDEN, "monks_forest_s.hdr")
     W, H, steps = 160, 90, 3
     subprocess.check_call([exe, str(obj), hdr, str(tmp_path), "--frames", "8", "--frame-range", "4", "7", "--size", str(W), str(H), "--res", "64", "1024", "--steps", str(steps),
@@ -139,7 +103,7 @@ def test_tile_render_single_process_rccl_matches_the_oracle(tmp_path):
     exe = os.path.join(ROOT, "apps", "tile_render")
     tris = bunny_tris()
     obj = tmp_path / "bunny.obj"
-    write_obj(obj, tris)
+    write_reader_obj(obj, tris)
     hdr = os.path.join(GOLDEN, "monks_forest_s.hdr")
     W, H, steps, res = 200, 113, 2, 128
     out = subprocess.check_output([exe, str(obj), hdr, str(tmp_path / "f.ppm"), "--gpus", "8", "--size", str(W), str(H), "--res", str(res), "--steps", str(steps),

@@ -12,10 +12,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("mvrt_svo_distance_cells", "mvrt_svo_depth_voxels", "mvrt_svo_dilate_ball", "mvrt_svo_erode_ball", "mvrt_svo_close_ball", "mvrt_svo_open_ball")
 
 
-def compile_usage(tmp_path):
-    return common.compile_usage(tmp_path, "ball_usage")
-
-
 def test_header_python_and_mirror_declare_the_interface():
     src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
     for name in CALLS:
@@ -39,6 +35,6 @@ def test_refusals_that_need_no_gpu():
 
 
 def test_cpp_mirror_ball_methods_compile_and_link(tmp_path):
-    exe, libdir = compile_usage(tmp_path)
+    exe, libdir = common.compile_usage(tmp_path, "ball_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out

@@ -13,12 +13,9 @@ import coarsen_expected as X
 import massivevoxelraytracing_amd as mv
 import surface_expected as S
 from common import bunny_tris
+from voxel_sets import full
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
 
 
 def test_by_hand():

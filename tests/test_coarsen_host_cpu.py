@@ -3,23 +3,12 @@ coarseMaxCount) of csrc/voxel_passes.h, which the kernels of csrc/kernels_coarse
 8^20, shifts of 3, 33 and 60 bits.  tests/hip/coarsen_host.hip is a program of its own that makes no HIP call; it is compiled for the host with hipcc and run
 here."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-PROBE = os.path.join(ROOT, "tests", "hip", "coarsen_host.hip")
+import common
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.skipif(not os.path.exists(common.HIPCC), reason="no hipcc")
 def test_coarsen_helpers_against_brute_force(tmp_path):
-    exe = str(tmp_path / "coarsen_host")
-    # (the program has no kernel: the host pass is all of it)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unused-result", PROBE, "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "coarsen host checks ok" in r.stdout
+    common.run_host_probe(tmp_path, "coarsen_host", "coarsen host checks ok", timeout=120)

@@ -15,10 +15,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("mvrt_svo_combine_voxels", "mvrt_svo_combine")
 
 
-def compile_usage(tmp_path):
-    return common.compile_usage(tmp_path, "combine_usage")
-
-
 def test_header_python_and_mirror_declare_the_interface():
     src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
     for name in CALLS:
@@ -48,7 +44,7 @@ def test_refusals_that_need_no_gpu():
 
 
 def test_cpp_mirror_combine_methods_compile_and_link(tmp_path):
-    exe, libdir = compile_usage(tmp_path)
+    exe, libdir = common.compile_usage(tmp_path, "combine_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out
 
@@ -64,7 +60,7 @@ def checksum(r):
 
 @pytest.mark.gpu
 def test_cpp_mirror_agrees_with_the_python_wrapper(tmp_path):
-    exe, _ = compile_usage(tmp_path)
+    exe, _ = common.compile_usage(tmp_path, "combine_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     g = np.zeros((16, 16, 16), bool)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import deep_scenes as D
+from fixtures import O  # noqa: F401 (fixtures)
 
 MAXF = np.float32(3.402823466e38)
 N_RAYS = 9000
@@ -18,12 +19,6 @@ DDA_STEPS = 64  # short rays start at most ~9 voxels from their target: it lies 
 
 # unambiguous share of the short rays with general directions that hit, per depth: measured (seeded) -> asserted floor
 UNAMBIGUOUS_GENERAL = {14: (0.991, 0.95), 15: (0.984, 0.93), 16: (0.965, 0.90), 17: (0.940, 0.85), 20: (0.524, 0.40), 21: (0.259, 0.15)}
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
 
 
 def ulp32(x):

@@ -13,15 +13,10 @@ import aov_expected as A
 import denoise_cases as K
 import denoise_expected as D
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+from fixtures import O  # noqa: F401 (fixtures)
 
 OFFSETS = [(6, 4, 6), (-6, -4, -6), (-2.5, 1.5, -2.0)]  # the three cameras of tests/test_gpu_aov.py
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
 
 
 @pytest.fixture(scope="module")

@@ -11,7 +11,7 @@ import exterior_expected as E
 import massivevoxelraytracing_amd as mv
 import surface_expected as S
 from common import bunny_tris
-from test_gpu_fill import CAGE, shell, tube
+from voxel_sets import CAGE, shell, tube
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

@@ -13,9 +13,9 @@ import fill_expected as F
 import massivevoxelraytracing_amd as mv
 import surface_expected as S
 from common import bunny_tris
+from voxel_sets import CAGE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CAGE = [(0, 1, 1), (2, 1, 1), (1, 0, 1), (1, 2, 1), (1, 1, 0), (1, 1, 2)]  # the six face neighbours of (1, 1, 1)
 
 
 def test_cage_of_six_voxels():

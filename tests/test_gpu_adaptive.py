@@ -11,7 +11,8 @@ import pytest
 import common
 import adaptive_expected as X
 import denoise_expected as D
-from common import GOLDEN, bunny_tris, hdr_bytes, position_colors, probe_camera
+from common import GOLDEN, bunny_tris, position_colors, probe_camera
+from fixtures import hdr, mv, O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,31 +26,12 @@ OFFSET = {(128, 72): (6, 4, 6), (100, 37): (-2.5, 1.5, -2.0)}
 
 
 @pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-@pytest.fixture(scope="module")
 def scene(O):
     tris = bunny_tris()
     cols, emis = position_colors(tris)
     sc = O.build_scene_from_triangles(tris, 256, cols, emis)
     assert sc.has_emission == 1
     return sc
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(hdr_bytes())
 
 
 @pytest.fixture(scope="module")

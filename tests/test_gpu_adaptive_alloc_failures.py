@@ -9,17 +9,12 @@ import pytest
 import adaptive_expected as X
 from alloc_sweep import mv  # noqa: F401 (the fixture)
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+from fixtures import O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 W, H = 64, 36
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
 
 
 @pytest.fixture(autouse=True)

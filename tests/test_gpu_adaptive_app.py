@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from common import GOLDEN, bunny_tris
+from voxel_mesh_app import write_reader_obj
 
 pytestmark = pytest.mark.gpu
 
@@ -16,11 +17,10 @@ pytestmark = pytest.mark.gpu
 def test_batch_driver_adaptive(tmp_path):
     import massivevoxelraytracing_amd as mv
     from massivevoxelraytracing_amd import build as b
-    from test_apps import write_obj
     exe = b.build_apps(verbose=False)
     tris = bunny_tris()
     obj = tmp_path / "bunny.obj"
-    write_obj(obj, tris)
+    write_reader_obj(obj, tris)
     hdr_file = os.path.join(GOLDEN, "monks_forest_s.hdr")
     W, H, steps, threshold, every = 96, 54, 8, 0.1, 2
     out = tmp_path / "out"

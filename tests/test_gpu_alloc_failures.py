@@ -9,17 +9,13 @@ import pytest
 
 from alloc_sweep import mv  # noqa: F401 (the fixture)
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+from fixtures import O  # noqa: F401 (fixtures)
+from rays import splitmix64
 
 pytestmark = pytest.mark.gpu
 
 RES, W, H, NRAYS = 256, 64, 36, 20_000
 INFO_FIELDS = ("numberOfNodes", "numberOfVoxels", "dps", "emissionScale", "hasEmission", "embeddedMask", "gridRes", "levels", "totalDumpedVoxels", "flavour")
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +45,7 @@ def info_of(svo):
 
 
 def mixed_rays(sc, n, seed):
-    """from outside and inside the volume, axis-parallel and zero-component directions among them (tests/test_gpu_parity.py), a third of them shadow rays"""
+    """from outside and inside the volume, axis-parallel and zero-component directions among them (tests/rays.py), a third of them shadow rays"""
     rng = np.random.default_rng(seed)
     lo, hi = sc.bounds()
     ro = ((lo + hi) / 2 + (rng.random((n, 3)) - 0.5) * (hi - lo).max() * 2.5).astype(np.float32)
@@ -172,13 +168,6 @@ def test_build_ex(mv, O, bunny, flags):
     sc = bunny if flags == 0 else O.Scene(O.build_octree(bunny.morton, RES, dag=False, embed=False), bunny.attrs, bunny.origin, bunny.dps, RES, bunny.has_emission, embedded=False)
     v, c, e = tris.reshape(-1, 3), cols.reshape(-1, 3), emis.reshape(-1, 3)
     sweep_always_empty(mv, O, lambda svo: svo.build(v, c, e, None, sc.origin, sc.dps, RES, flags=flags), sc)
-
-
-def splitmix64(x):
-    x = (x + np.uint64(0x9E3779B97F4A7C15)).astype(np.uint64)
-    x = ((x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)).astype(np.uint64)
-    x = ((x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)).astype(np.uint64)
-    return x ^ (x >> np.uint64(31))
 
 
 def synthetic_voxels(O, res, n, seed):

@@ -10,51 +10,13 @@ import pytest
 import common
 import surface_expected as S
 from common import bunny_tris, position_colors
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from rays import AXIS, PLUS, expected_open, oracle_t
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAXF = np.float32(3.402823466e38)
-AXIS = np.array([1, 1, 2, 0, 2, 0])  # direction -> normal axis, in the order of mvrt.h: -Y +Y -Z +X +Z -X
-PLUS = np.array([0, 1, 0, 1, 1, 0])
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-def face_origins(xyz, face_voxel, face_dir, lower, dps):
-    """ro[a] = lower[a] + (float)c2 * (0.5f * dps), c2 in half voxels: the voxel's middle in the plane, the face on the normal axis"""
-    f32 = np.float32
-    c2 = 2 * xyz[face_voxel].astype(np.int64) + 1
-    c2[np.arange(len(c2)), AXIS[face_dir]] += np.where(PLUS[face_dir] == 1, 1, -1)
-    h = f32(f32(0.5) * f32(dps))
-    return (np.asarray(lower, f32)[None, :] + (c2.astype(f32) * h).astype(f32)).astype(f32)
-
-
-def oracle_t(mv, sc, xyz, face_voxel, face_dir, K):
-    """the oracle's unlimited t of the K occlusion rays of every face: (nFaces, K)"""
-    lo, _ = sc.bounds()
-    ro = face_origins(xyz, face_voxel, face_dir, lo, np.float32(sc.dps))
-    dirs = mv.ao_directions(K)
-    rd = dirs[face_dir]  # (n, K, 3)
-    ro = np.ascontiguousarray(np.broadcast_to(ro[:, None, :], rd.shape)).reshape(-1, 3)
-    t = sc.trace(ro, rd.reshape(-1, 3), np.ones(len(ro), np.uint8), threads=8)["t"]
-    return t.reshape(len(face_voxel), K)
-
-
-def expected_open(t, radius):
-    return (~((t != MAXF) & (t <= np.float32(radius)))).sum(1).astype(np.uint16)
 
 
 def voxel_scene(O, xyz, res, origin, dps):

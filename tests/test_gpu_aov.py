@@ -8,25 +8,13 @@ import pytest
 
 import common
 import aov_expected as A
-from common import GOLDEN, bunny_tris, hdr_bytes, position_colors, probe_camera
+from common import GOLDEN, bunny_tris, position_colors, probe_camera
+from fixtures import hdr, mv, O  # noqa: F401 (fixtures)
+from voxel_mesh_app import read_png_rgba, write_reader_obj
 
 pytestmark = pytest.mark.gpu
 
 OFFSETS = [(6, 4, 6), (-6, -4, -6), (-2.5, 1.5, -2.0)]
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -36,11 +24,6 @@ def scene(O):
     sc = O.build_scene_from_triangles(tris, 256, cols, emis)
     assert sc.has_emission == 1
     return sc
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(hdr_bytes())
 
 
 def make_pt(mv, sc, w, h, hdr, tile=(0, 1), aovs=True, upload=True, embedded=True, has_emission=None, attrs=None):
@@ -347,11 +330,10 @@ def test_profiling_counts_the_feature_kernels_as_other(mv, O, scene, hdr):
 def test_batch_driver_writes_the_feature_images(tmp_path, O):
     """rtcamp_batch --aov: <frame>_albedo and <frame>_normal beside each frame == the bytes computed from the expected buffers with the documented encoding; PPM and PNG"""
     from massivevoxelraytracing_amd import build as b
-    from test_apps import read_png_rgba, write_obj
     exe = b.build_apps(verbose=False)
     tris = bunny_tris()
     obj = tmp_path / "bunny.obj"
-    write_obj(obj, tris)
+    write_reader_obj(obj, tris)
     hdr_file = os.path.join(GOLDEN, "monks_forest_s.hdr")
     W, H, steps = 96, 54, 2
     v = tris.reshape(-1, 3)

@@ -16,52 +16,12 @@ import ball_expected as B
 import morph_expected as M
 import surface_expected as S
 from common import GOLDEN, bunny_tris, probe_camera
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, assert_same_octree, build, colours, filled, full, holed_shell, octree, same, specks_and_block
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 OPS = ("dilate", "erode", "close", "open")
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def colours(n, seed=1, emission=True):
-    at = np.random.default_rng(seed).integers(0, 256, size=(n, 8), dtype=np.uint8)
-    if not emission:
-        at[:, 4:7] = 0
-    return at
-
-
-def build(mv, xyz, res, flags=0, attribs=None):
-    xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build_voxels(xyz, colours(len(xyz)) if attribs is None else attribs, origin=LOWER, dps=DPS, gridRes=res, flags=flags)
-    return svo
-
-
-def octree(svo):
-    return svo.download(want_morton=True)
-
-
-def same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def assert_same_octree(a, b):
-    ia, ib = a.info(), b.info()
-    for f in ("numberOfNodes", "numberOfVoxels", "hasEmission", "embeddedMask", "gridRes", "levels", "flavour", "dps", "totalDumpedVoxels"):
-        assert getattr(ia, f) == getattr(ib, f), f
-    assert ia.lower[:] == ib.lower[:] and ia.upper[:] == ib.upper[:] and ia.emissionScale == ib.emissionScale
-    assert same(octree(a), octree(b)) and same(a.read_voxels(), b.read_voxels())
-    if ia.flavour != 2:  # (the tree flavour has no device view)
-        va, vb = a.device_view(), b.device_view()
-        assert (va.cellBlocks != 0, va.cellBits, va.rootIndex, va.rootMask) == (vb.cellBlocks != 0, vb.cellBits, vb.rootIndex, vb.rootMask)
-    assert a.traversal_bytes() == b.traversal_bytes()  # the resident derived tables
 
 
 def assert_listings(svo, res, rho, sparse=False):
@@ -110,18 +70,6 @@ def assert_all(mv, xyz, res, rhos, flags=0, attribs=None, sparse=False):
         assert_listings(svo, res, rho, sparse)
         for op in OPS:
             assert_op(mv, xyz, res, op, rho, flags, attribs, sparse)
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
-
-
-def holed_shell():
-    g = np.zeros((16, 16, 16), bool)
-    g[4:11, 4:11, 4:11] = True
-    g[5:10, 5:10, 5:10] = False
-    g[7, 7, 10] = False
-    return np.argwhere(g)
 
 
 # ---- the smallest grids ----------------------------------------------------------------------------------------------------------------------------------------
@@ -243,10 +191,7 @@ def test_the_full_reach_on_one_voxel(mv):
 # ---- closing and opening -----------------------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def mixed():
-    rng = np.random.default_rng(77)
-    solid = np.ones((12, 12, 12), bool)  # a block with three one-voxel holes among specks that an opening removes
-    solid[1, 1, 1] = solid[10, 10, 1] = solid[1, 10, 10] = False
-    return S.sorted_voxels(np.concatenate([np.argwhere(rng.random((32, 32, 32)) < 0.02), np.argwhere(solid) + 9]))
+    return S.sorted_voxels(specks_and_block([(1, 1, 1), (10, 10, 1), (1, 10, 10)]))  # a block with three one-voxel holes among specks that an opening removes
 
 
 @pytest.mark.parametrize("rho", [1, 2, 5, 9])
@@ -410,11 +355,6 @@ def small(mv, mixed):
     return build(mv, mixed, 32)
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_null_outputs_and_capacity(mv, small):
     svo = small
     x0, a0 = svo.read_voxels()
@@ -430,11 +370,11 @@ def test_null_outputs_and_capacity(mv, small):
     assert lib.mvrt_svo_depth_voxels(svo._h, 5, 0, None, None, None, None) == 0
     one = build(mv, [(1, 1, 1)], 4)
     assert lib.mvrt_svo_dilate_ball(one._h, 3, None, None) == 0 and one.info().numberOfVoxels == 27
-    big, host = canary(mv, (n + 5, 3), np.uint32)  # a larger capacity writes the count's worth
+    big, host = filled(mv, (n + 5, 3), np.uint32)  # a larger capacity writes the count's worth
     assert svo.distance_cells_device(5, n + 5, big) == n
     assert np.array_equal(big.to_host()[:n], want["xyz"]) and np.array_equal(big.to_host()[n:], host[n:])
     # one short: the count is still returned and nothing is written
-    (xyz, xyz_host), (near, near_host) = canary(mv, (n, 3), np.uint32), canary(mv, n, np.uint32)
+    (xyz, xyz_host), (near, near_host) = filled(mv, (n, 3), np.uint32), filled(mv, n, np.uint32)
     nc = C.c_uint64(0)
     assert lib.mvrt_svo_distance_cells(svo._h, 5, n - 1, xyz.ptr, None, near.ptr, None, C.byref(nc), None) != 0
     assert nc.value == n and b"capacity %d" % (n - 1) in lib.mvrt_last_error() and b"%d cells" % n in lib.mvrt_last_error()
@@ -444,7 +384,7 @@ def test_null_outputs_and_capacity(mv, small):
     vi, dp = mv.DeviceArray(m, np.uint32), mv.DeviceArray(m, np.uint32)
     assert svo.depth_voxels_device(5, m, vi, None) == m and np.array_equal(vi.to_host(), gone["vIndex"])
     assert svo.depth_voxels_device(5, m, None, dp) == m and np.array_equal(dp.to_host(), gone["depth2"])
-    (vi, vi_host), (dp, dp_host) = canary(mv, m, np.uint32), canary(mv, m, np.uint32)
+    (vi, vi_host), (dp, dp_host) = filled(mv, m, np.uint32), filled(mv, m, np.uint32)
     nc.value = 0
     assert lib.mvrt_svo_depth_voxels(svo._h, 5, m - 1, vi.ptr, dp.ptr, C.byref(nc), None) != 0
     assert nc.value == m and b"capacity" in lib.mvrt_last_error() and np.array_equal(vi.to_host(), vi_host) and np.array_equal(dp.to_host(), dp_host)

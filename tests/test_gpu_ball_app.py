@@ -9,14 +9,12 @@ import numpy as np
 import pytest
 
 import ball_expected as B
+import common
 import surface_expected as S
-from test_ball_mirror import compile_usage
-from test_gpu_morph_app import holed_box
+from voxel_mesh_app import APP, holed_box, write_obj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-APP = os.path.join(ROOT, "apps", "voxel_mesh")
 RES = 16
 
 
@@ -26,9 +24,7 @@ def box_obj(tmp_path_factory):
     b.build_apps(verbose=False)
     tris = holed_box()
     path = tmp_path_factory.mktemp("ball_app") / "box.obj"
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % tuple(p) for p in tris.reshape(-1, 3)) + "".join("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3) for t in range(len(tris))))
-    return str(path), tris
+    return write_obj(path, tris), tris
 
 
 def built(mv, tris):
@@ -77,7 +73,7 @@ def test_the_other_operators_and_the_refused_combinations(tmp_path, box_obj):
 
 
 def test_cpp_mirror_runs(tmp_path):
-    exe, _ = compile_usage(tmp_path)
+    exe, _ = common.compile_usage(tmp_path, "ball_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     assert "shell 217 cells 485 farthest 3 thin 217 deepest 1 plugged 1 enclosed 125 grown 392 opened 0 eroded 348 left 262" in out

@@ -14,30 +14,12 @@ import os
 import numpy as np
 import pytest
 
-from common import GOLDEN
-from test_gpu_parity import assert_hits_equal, random_rays
+from fixtures import hdr, mv, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, random_rays
 
 pytestmark = pytest.mark.gpu
 W, H = 1920, 1080
 THREADS = min(16, len(os.sched_getaffinity(0)))
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(open(os.path.join(GOLDEN, "monks_forest_s.hdr"), "rb").read())
 
 
 def scene_and_oracle(O, name, res):

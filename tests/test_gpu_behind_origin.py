@@ -12,26 +12,13 @@ import pytest
 
 import deep_scenes as D
 from common import hdr_bytes
-from test_gpu_parity import assert_hits_equal
-from test_gpu_resume_point import voxel_scene
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, voxel_scene
 
 pytestmark = pytest.mark.gpu
 
 MAXF = np.float32(3.402823466e38)
 FLAGS = [0, 2, 3]  # embedded masks / plain indices / tree (bricks): flavours 0, 1, 2
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def build(mv, s, flags):

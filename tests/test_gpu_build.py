@@ -6,22 +6,10 @@ import numpy as np
 import pytest
 
 from common import bunny_tris, golden, hdr_bytes, position_colors, probe_camera
+from fixtures import mv, O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 G = golden()
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def gpu_build(mv, tris, res, cols=None, emis=None):

@@ -12,18 +12,12 @@ import pytest
 import coarsen_expected as X
 import surface_expected as S
 from common import GOLDEN, bunny_tris, probe_camera
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, assert_same_octree, filled, full, shell
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 B = 1024  # entries per workgroup of the reduce kernel (CB, csrc/kernels_coarsen.hip): 256 threads, four consecutive entries each; a wave covers 256 entries
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def build(mv, xyz, res, flags=0, attribs=None, origin=LOWER, dps=DPS):
@@ -45,12 +39,6 @@ def info_of(svo):
     return out
 
 
-def assert_same_octree(got, twin):
-    assert info_of(got) == info_of(twin)
-    a, b = got.download(want_morton=True), twin.download(want_morton=True)
-    assert all(x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
-
-
 def assert_listing(svo, want, k, min_count=1):
     got = svo.coarse_voxels(k, min_count)
     n = len(want["xyz"])
@@ -69,7 +57,7 @@ def assert_coarsened(mv, src, want, n_fine, res, k, min_count=1, flags=0, dst=No
     twin = build(mv, want["xyz"], res >> k, flags, want["attribs"], origin=np.frombuffer(before["lower"], np.float32),
                  dps=np.float32(np.frombuffer(before["dps"], np.float32)[0] * np.float32(2 ** k)))
     twin.set_emission_scale(scale)
-    assert_same_octree(dst, twin)
+    assert_same_octree(dst, twin, skip=("totalDumpedVoxels",))  # the coarsening hands adoptSortedOnGrid the source's voxel count (csrc/api.hip), asserted below
     assert dst.info().totalDumpedVoxels == n_fine and info_of(dst)["upper"] == before["upper"]  # the same box, bit for bit
     return dst
 
@@ -85,10 +73,6 @@ def check(mv, xyz, attribs, res, k, min_count=1, flags=0, src_flags=0):
         assert_coarsened(mv, src, want, len(xyz), res, k, min_count, flags)
     assert all(np.array_equal(a, b) for a, b in zip(src.download(want_morton=True), held))  # the source is only read
     return src, want
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
 
 
 def random_attribs(rng, n):
@@ -231,11 +215,6 @@ def test_sums_beyond_32_bits(mv, white_box):
 
 
 # ---- sources of every flavour, edits, fills, uploads ---------------------------------------------------------------------------------------------------------------
-def shell(lo, hi):
-    p = np.stack(np.meshgrid(*[np.arange(lo, hi)] * 3, indexing="ij"), -1).reshape(-1, 3)
-    return p[((p == lo) | (p == hi - 1)).any(1)]
-
-
 @pytest.fixture(scope="module")
 def mixed():
     rng = np.random.default_rng(40)
@@ -360,11 +339,6 @@ def small(mv, mixed):
     return build(mv, xyz, 32, 0, attribs), X.coarse(xyz, attribs, 1, 2)
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_null_outputs(mv, small):
     svo, want = small
     n = len(want["xyz"])
@@ -374,7 +348,7 @@ def test_null_outputs(mv, small):
     assert svo.coarse_voxels_device(1, 2, n, None, attribs, None) == n and np.array_equal(attribs.to_host(), want["attribs"])
     assert svo.coarse_voxels_device(1, 2, n, None, None, count) == n and np.array_equal(count.to_host(), want["count"])
     assert mv.lib().mvrt_svo_coarse_voxels(svo._h, 1, 2, 0, None, None, None, None, None) == 0  # even the count may be NULL
-    big, host = canary(mv, (n + 5, 3), np.uint32)  # a larger capacity than the count is fine and writes the count's worth
+    big, host = filled(mv, (n + 5, 3), np.uint32)  # a larger capacity than the count is fine and writes the count's worth
     assert svo.coarse_voxels_device(1, 2, n + 5, big, None, None) == n
     assert np.array_equal(big.to_host()[:n], want["xyz"]) and np.array_equal(big.to_host()[n:], host[n:])
 
@@ -383,7 +357,7 @@ def test_null_outputs(mv, small):
 def test_capacity_one_short(mv, small, mixed, min_count):
     svo = small[0]
     n = len(X.coarse(mixed[0], mixed[1], 1, min_count)["xyz"])
-    (xyz, xyz_host), (attribs, attribs_host), (count, count_host) = canary(mv, (n, 3), np.uint32), canary(mv, (n, 8), np.uint8), canary(mv, n, np.uint32)
+    (xyz, xyz_host), (attribs, attribs_host), (count, count_host) = filled(mv, (n, 3), np.uint32), filled(mv, (n, 8), np.uint8), filled(mv, n, np.uint32)
     lib = mv.lib()
     got = C.c_uint64(0)
     assert lib.mvrt_svo_coarse_voxels(svo._h, 1, min_count, n - 1, xyz.ptr, attribs.ptr, count.ptr, C.byref(got), None) != 0

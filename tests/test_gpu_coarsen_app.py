@@ -10,6 +10,7 @@ import pytest
 import coarsen_expected as X
 import surface_expected as S
 from common import GOLDEN, bunny_tris
+from voxel_mesh_app import write_reader_obj
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +21,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_voxel_mesh_lod(tmp_path, extra, min_count):
     import massivevoxelraytracing_amd as mv
     from massivevoxelraytracing_amd import build as b
-    from test_apps import write_obj
     b.build_apps(verbose=False)
     tris = bunny_tris()
-    write_obj(tmp_path / "bunny.obj", tris)
+    write_reader_obj(tmp_path / "bunny.obj", tris)
     out = subprocess.check_output([os.path.join(ROOT, "apps", "voxel_mesh"), str(tmp_path / "bunny.obj"), "64", str(tmp_path / "bunny.ply"), "--lod", "1"] + extra, timeout=120).decode()
     print(out)
     v = tris.reshape(-1, 3)
@@ -48,10 +48,9 @@ def test_voxel_mesh_lod(tmp_path, extra, min_count):
 
 def test_batch_driver_lod(tmp_path):
     from massivevoxelraytracing_amd import build as b
-    from test_apps import write_obj
     exe = b.build_apps(verbose=False)
     obj = tmp_path / "bunny.obj"
-    write_obj(obj, bunny_tris())
+    write_reader_obj(obj, bunny_tris())
     out = tmp_path / "out"
     os.mkdir(out)
     W, H = 96, 54

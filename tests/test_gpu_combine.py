@@ -13,53 +13,19 @@ import pytest
 import combine_expected as E
 import surface_expected as S
 from common import GOLDEN, bunny_tris, probe_camera
+from fixtures import load
+from voxel_sets import DPS, LOWER, assert_same_octree, build, colours, filled, full, octree, same, specks_and_block
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 REMOVE = 0  # IntersectorOctreeGPU.VOXEL_REMOVE
 
 
 @pytest.fixture(scope="module")
 def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
+    m = load()
     assert (m.COMBINE_UNION, m.COMBINE_INTERSECTION, m.COMBINE_DIFFERENCE, m.COMBINE_XOR, m.COMBINE_ATTRIB_B) == (E.UNION, E.INTERSECTION, E.DIFFERENCE, E.XOR, E.ATTRIB_B)
     return m
-
-
-def colours(n, seed=1, emission=True):
-    at = np.random.default_rng(seed).integers(0, 256, size=(n, 8), dtype=np.uint8)
-    if not emission:
-        at[:, 4:7] = 0
-    return at
-
-
-def build(mv, xyz, res, flags=0, attribs=None, seed=1):
-    xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build_voxels(xyz, colours(len(xyz), seed) if attribs is None else attribs, origin=LOWER, dps=DPS, gridRes=res, flags=flags)
-    return svo
-
-
-def octree(svo):
-    return svo.download(want_morton=True)
-
-
-def same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def assert_same_octree(a, b):
-    ia, ib = a.info(), b.info()
-    for f in ("numberOfNodes", "numberOfVoxels", "hasEmission", "embeddedMask", "gridRes", "levels", "flavour", "dps", "totalDumpedVoxels"):
-        assert getattr(ia, f) == getattr(ib, f), f
-    assert ia.lower[:] == ib.lower[:] and ia.upper[:] == ib.upper[:] and ia.emissionScale == ib.emissionScale
-    assert same(octree(a), octree(b)) and same(a.read_voxels(), b.read_voxels())
-    if ia.flavour != 2 and ia.levels <= 16:  # (the tree flavour has no device view, nor have more than 16 levels)
-        va, vb = a.device_view(), b.device_view()
-        assert (va.cellBlocks != 0, va.cellBits, va.rootIndex, va.rootMask) == (vb.cellBlocks != 0, vb.cellBits, vb.rootIndex, vb.rootMask)
-    assert a.traversal_bytes() == b.traversal_bytes()  # the resident derived tables
 
 
 def assert_listing(a, b, op, offset=None, flags=0):
@@ -127,10 +93,6 @@ def assert_all(mv, xa, xb, res, offset=None, res_b=None, flags=(0, E.ATTRIB_B), 
             out[op, f] = assert_listing(reader, b, op, offset, f)
             assert_in_place(mv, build(mv, xa, res, build_flags), b, op, offset, f, build_flags)
     return out
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
 
 
 def first_codes(n, res, start=0):
@@ -374,10 +336,7 @@ def test_alpha_bytes_of_b_arrive_as_255(mv):
 # ---- every flavour, every way a handle comes to its codes ----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def mixed():
-    rng = np.random.default_rng(77)
-    solid = np.ones((12, 12, 12), bool)
-    solid[1, 1, 1] = solid[10, 10, 1] = False
-    return S.sorted_voxels(np.concatenate([np.argwhere(rng.random((32, 32, 32)) < 0.02), np.argwhere(solid) + 9]))
+    return S.sorted_voxels(specks_and_block([(1, 1, 1), (10, 10, 1)]))
 
 
 @pytest.mark.parametrize("flags_a", [0, 1, 2, 3])
@@ -495,11 +454,6 @@ def pair(mv, mixed):
     return build(mv, mixed, 32), build(mv, np.argwhere(np.random.default_rng(91).random((32, 32, 32)) < 0.05), 32, seed=4)
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_null_outputs_and_capacity(mv, pair):
     a, b = pair
     off = (1, 2, 3)
@@ -519,11 +473,11 @@ def test_null_outputs_and_capacity(mv, pair):
     o1 = np.array((1, 1, 1), np.int32)
     assert lib.mvrt_svo_combine(one._h, one._h, E.UNION, o1.ctypes.data, 0, None, None, None, None) == 0 and one.info().numberOfVoxels == 3  # (3, 3, 3) + 1 is clipped
     assert lib.mvrt_svo_combine(one._h, one._h, E.UNION, None, 0, None, None, None, None) == 0 and one.info().numberOfVoxels == 3  # a NULL offset is zero
-    wide, host = canary(mv, (n + 5, 3), np.uint32)  # a larger capacity writes the count's worth
+    wide, host = filled(mv, (n + 5, 3), np.uint32)  # a larger capacity writes the count's worth
     assert a.combine_voxels_device(b, E.UNION, off, 0, n + 5, wide) == counts
     assert np.array_equal(wide.to_host()[:n], want["xyz"]) and np.array_equal(wide.to_host()[n:], host[n:])
     # one short: the counts are still returned and nothing is written
-    (xyz, xyz_host), (at, at_host), (src, src_host) = canary(mv, (n, 3), np.uint32), canary(mv, (n, 8), np.uint8), canary(mv, n, np.uint8)
+    (xyz, xyz_host), (at, at_host), (src, src_host) = filled(mv, (n, 3), np.uint32), filled(mv, (n, 8), np.uint8), filled(mv, n, np.uint8)
     nn, nov, ncl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     assert lib.mvrt_svo_combine_voxels(a._h, b._h, E.UNION, o.ctypes.data, 0, n - 1, xyz.ptr, at.ptr, src.ptr, C.byref(nn), C.byref(nov), C.byref(ncl), None) != 0
     assert (nn.value, nov.value, ncl.value) == counts and b"capacity %d" % (n - 1) in lib.mvrt_last_error() and b"%d voxels" % n in lib.mvrt_last_error()

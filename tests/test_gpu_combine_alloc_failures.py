@@ -7,20 +7,12 @@ import pytest
 
 import combine_expected as E
 from alloc_sweep import filled, mv, same, sweep_edit, sweep_reader  # noqa: F401 (mv: the fixture)
+from voxel_sets import DPS, LOWER, block_and_noise
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
+RES = 32
 OFFSETS = [None, (3, -2, 1)]
-
-
-def voxels(seed):
-    rng = np.random.default_rng(seed)
-    solid = np.zeros((RES, RES, RES), bool)
-    solid[8:20, 8:20, 8:20] = True
-    solid |= rng.random((RES, RES, RES)) < 0.03
-    xyz = np.argwhere(solid).astype(np.uint32)
-    return xyz, rng.integers(0, 256, (len(xyz), 8), dtype=np.uint8)
 
 
 def build(svo, v):
@@ -30,8 +22,8 @@ def build(svo, v):
 @pytest.mark.parametrize("offset", OFFSETS)
 def test_each_allocation_of_the_listing_fails_in_turn(mv, offset):
     a, b = mv.IntersectorOctreeGPU(), mv.IntersectorOctreeGPU()
-    build(a, voxels(31))
-    build(b, voxels(32))
+    build(a, block_and_noise(31, RES))
+    build(b, block_and_noise(32, RES))
     (xa, aa), (xb, ab) = a.read_voxels(), b.read_voxels()
     want = E.combine(xa, aa, xb, ab, RES, E.XOR, offset, E.ATTRIB_B)
     n, counts = len(want["xyz"]), (len(want["xyz"]), want["overlap"], want["clipped"])
@@ -49,10 +41,10 @@ def test_each_allocation_of_the_listing_fails_in_turn(mv, offset):
 @pytest.mark.parametrize("op,flags", [(E.UNION, E.ATTRIB_B), (E.DIFFERENCE, 0)])
 def test_each_allocation_of_the_in_place_call_fails_in_turn(mv, offset, op, flags):
     b = mv.IntersectorOctreeGPU()
-    build(b, voxels(32))
+    build(b, block_and_noise(32, RES))
     base = mv.allocation_state()[:2]
     a = mv.IntersectorOctreeGPU()
-    va = voxels(31)
+    va = block_and_noise(31, RES)
     build(a, va)
     (xa, aa), (xb, ab) = a.read_voxels(), b.read_voxels()
     want = E.combine(xa, aa, xb, ab, RES, op, offset, flags)
@@ -68,7 +60,7 @@ def test_each_allocation_of_the_in_place_call_fails_in_turn(mv, offset, op, flag
 
 def test_each_allocation_of_a_recolouring_fails_in_turn(mv):
     """the attribute-only call writes in place, behind its last allocation: every failure leaves the old bytes"""
-    va = voxels(31)
+    va = block_and_noise(31, RES)
     a, b = mv.IntersectorOctreeGPU(), mv.IntersectorOctreeGPU()
     build(a, va)
     build(b, (va[0], np.random.default_rng(33).integers(0, 256, (len(va[0]), 8), dtype=np.uint8)))  # the same cells in other colours

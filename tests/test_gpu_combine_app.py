@@ -10,35 +10,12 @@ import pytest
 
 import combine_expected as E
 import surface_expected as S
+from voxel_mesh_app import APP, block, run, write_obj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-APP = os.path.join(ROOT, "apps", "voxel_mesh")
 RES = 32
 OPTIONS = {"--union": E.UNION, "--intersect": E.INTERSECTION, "--subtract": E.DIFFERENCE, "--xor": E.XOR}
-
-
-def quad(a, b, c, d):
-    return [a, b, c, a, c, d]
-
-
-def slab(x0, x1, y0, y1, z):
-    return quad((x0, y0, z), (x1, y0, z), (x1, y1, z), (x0, y1, z))
-
-
-def block(lo, hi):
-    """horizontal slabs through the middle of the layers z = lo .. hi - 1: a solid block of (hi - lo)^3 voxels at [lo, hi)^3, in voxel units"""
-    v = []
-    for k in range(lo, hi):
-        v += slab(lo + 0.25, hi - 0.25, lo + 0.25, hi - 0.25, k + 0.5)
-    return v
-
-
-def write_obj(path, tris):
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % tuple(p) for p in tris.reshape(-1, 3)) + "".join("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3) for t in range(len(tris))))
-    return str(path)
 
 
 @pytest.fixture(scope="module")
@@ -62,12 +39,6 @@ def scene(tmp_path_factory):
         sets.append(svo.read_voxels())
     assert len(sets[1][0]) == 512 and len(sets[0][0]) >= 512
     return write_obj(d / "first.obj", first), write_obj(d / "other.obj", other), sets
-
-
-def run(*args):
-    out = subprocess.check_output([APP] + [str(a) for a in args], timeout=120).decode()
-    print(out)
-    return out
 
 
 @pytest.mark.parametrize("option", sorted(OPTIONS))

@@ -13,53 +13,13 @@ import pytest
 import components_expected as K
 import surface_expected as S
 from common import GOLDEN, bunny_tris, probe_camera
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, assert_same_octree, build, colours, filled, full, octree, same, specks_and_block
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 ELEMENTS = (K.FACES, K.CUBE)
 REMOVE = 0  # IntersectorOctreeGPU.VOXEL_REMOVE
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def colours(n, seed=1, emission=True):
-    at = np.random.default_rng(seed).integers(0, 256, size=(n, 8), dtype=np.uint8)
-    if not emission:
-        at[:, 4:7] = 0
-    return at
-
-
-def build(mv, xyz, res, flags=0, attribs=None):
-    xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build_voxels(xyz, colours(len(xyz)) if attribs is None else attribs, origin=LOWER, dps=DPS, gridRes=res, flags=flags)
-    return svo
-
-
-def octree(svo):
-    return svo.download(want_morton=True)
-
-
-def same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def assert_same_octree(a, b):
-    ia, ib = a.info(), b.info()
-    for f in ("numberOfNodes", "numberOfVoxels", "hasEmission", "embeddedMask", "gridRes", "levels", "flavour", "dps", "totalDumpedVoxels"):
-        assert getattr(ia, f) == getattr(ib, f), f
-    assert ia.lower[:] == ib.lower[:] and ia.upper[:] == ib.upper[:] and ia.emissionScale == ib.emissionScale
-    assert same(octree(a), octree(b)) and same(a.read_voxels(), b.read_voxels())
-    if ia.flavour != 2 and ia.levels <= 16:  # (the tree flavour has no device view, nor have more than 16 levels)
-        va, vb = a.device_view(), b.device_view()
-        assert (va.cellBlocks != 0, va.cellBits, va.rootIndex, va.rootMask) == (vb.cellBlocks != 0, vb.cellBits, vb.rootIndex, vb.rootMask)
-    assert a.traversal_bytes() == b.traversal_bytes()  # the resident derived tables
 
 
 def assert_listing(svo, res, sparse=False, elements=ELEMENTS):
@@ -109,10 +69,6 @@ def assert_keep(mv, xyz, res, e, min_voxels=1, keep_largest=0, flags=0, attribs=
         twin.edit_voxels(gone.astype(np.uint32), None, np.full(len(gone), REMOVE, np.uint8))
         assert_same_octree(svo, twin)
     return svo
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
 
 
 def checkerboard(res):
@@ -280,10 +236,7 @@ def test_nothing_dropped_leaves_the_handle_and_its_views(mv):
 # ---- every flavour, every way a handle comes to its codes ----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def mixed():
-    rng = np.random.default_rng(77)
-    solid = np.ones((12, 12, 12), bool)
-    solid[1, 1, 1] = solid[10, 10, 1] = False
-    return S.sorted_voxels(np.concatenate([np.argwhere(rng.random((32, 32, 32)) < 0.02), np.argwhere(solid) + 9]))
+    return S.sorted_voxels(specks_and_block([(1, 1, 1), (10, 10, 1)]))
 
 
 @pytest.mark.parametrize("flags", [0, 1, 2, 3])
@@ -401,11 +354,6 @@ def small(mv, mixed):
     return build(mv, mixed, 32)
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_null_outputs_and_capacity(mv, small):
     svo = small
     x0, _ = svo.read_voxels()
@@ -422,12 +370,12 @@ def test_null_outputs_and_capacity(mv, small):
     assert lib.mvrt_svo_components(svo._h, K.CUBE, None, 0, None, None, None, None, None, None) == 0  # even the counts may be NULL
     one = build(mv, [(1, 1, 1), (3, 3, 3)], 4)
     assert lib.mvrt_svo_keep_components(one._h, K.CUBE, 1, 1, None, None, None) == 0 and one.info().numberOfVoxels == 1
-    wide, host = canary(mv, (n + 5, 6), np.uint32)  # a larger capacity writes the count's worth
+    wide, host = filled(mv, (n + 5, 6), np.uint32)  # a larger capacity writes the count's worth
     assert svo.components_device(K.CUBE, None, n + 5, None, None, wide) == (n, big)
     assert np.array_equal(wide.to_host()[:n], want["box"]) and np.array_equal(wide.to_host()[n:], host[n:])
     # one short: the counts are still returned and nothing is written, the labels included
-    (label, label_host), (size, size_host), (first, first_host), (box, box_host) = (canary(mv, nv, np.uint32), canary(mv, n, np.uint32), canary(mv, n, np.uint32),
-                                                                                   canary(mv, (n, 6), np.uint32))
+    (label, label_host), (size, size_host), (first, first_host), (box, box_host) = (filled(mv, nv, np.uint32), filled(mv, n, np.uint32), filled(mv, n, np.uint32),
+                                                                                   filled(mv, (n, 6), np.uint32))
     nc, nl = C.c_uint64(0), C.c_uint64(0)
     assert lib.mvrt_svo_components(svo._h, K.CUBE, label.ptr, n - 1, size.ptr, first.ptr, box.ptr, C.byref(nc), C.byref(nl), None) != 0
     assert (nc.value, nl.value) == (n, big) and b"componentCapacity %d" % (n - 1) in lib.mvrt_last_error() and b"%d components" % n in lib.mvrt_last_error()

@@ -7,20 +7,16 @@ import pytest
 
 import components_expected as K
 from alloc_sweep import filled, mv, same, sweep_edit, sweep_reader  # noqa: F401 (mv: the fixture)
+from voxel_sets import DPS, LOWER, block_and_noise
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
+RES = 32
 
 
 @pytest.fixture(scope="module")
 def voxels():
-    rng = np.random.default_rng(31)
-    solid = np.zeros((RES, RES, RES), bool)
-    solid[8:20, 8:20, 8:20] = True
-    solid |= rng.random((RES, RES, RES)) < 0.03
-    xyz = np.argwhere(solid).astype(np.uint32)
-    return xyz, rng.integers(0, 256, (len(xyz), 8), dtype=np.uint8)
+    return block_and_noise(31, RES)
 
 
 def build(svo, voxels):

@@ -7,27 +7,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import common
 import components_expected as K
-from test_components_mirror import compile_usage
+from voxel_mesh_app import APP, corners, quad, run, slab, write_obj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-APP = os.path.join(ROOT, "apps", "voxel_mesh")
 RES = 32
-
-
-def quad(a, b, c, d):
-    return [a, b, c, a, c, d]
-
-
-def slab(x0, x1, y0, y1, z):
-    return quad((x0, y0, z), (x1, y0, z), (x1, y1, z), (x0, y1, z))
-
-
-def corners(lo, hi, d):
-    """two small triangles that stretch the bounding grid to [lo, hi]^3"""
-    return [(lo, lo, lo), (lo + d, lo, lo), (lo, lo + d, lo), (hi, hi, hi), (hi - d, hi, hi), (hi, hi - d, hi)]
 
 
 def dumbbell():
@@ -53,12 +39,6 @@ def box_with_debris():
     return np.array(v, np.float32).reshape(-1, 3, 3)
 
 
-def write_obj(path, tris):
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % tuple(p) for p in tris.reshape(-1, 3)) + "".join("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3) for t in range(len(tris))))
-    return str(path)
-
-
 @pytest.fixture(scope="module")
 def objs(tmp_path_factory):
     from massivevoxelraytracing_amd import build as b
@@ -73,12 +53,6 @@ def built(mv, tris, res):
     svo = mv.IntersectorOctreeGPU()
     svo.build(v, None, None, None, lo, np.float32((v.max(0) - lo).max() / np.float32(res)), res)
     return svo
-
-
-def run(*args):
-    out = subprocess.check_output([APP] + [str(a) for a in args], timeout=120).decode()
-    print(out)
-    return out
 
 
 def test_components_flag_against_the_model(tmp_path, objs):
@@ -139,7 +113,7 @@ def test_min_component_then_fill(tmp_path, objs):
 
 
 def test_cpp_mirror_runs(tmp_path):
-    exe, _ = compile_usage(tmp_path)
+    exe, _ = common.compile_usage(tmp_path, "components_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     assert "voxels 221 faces 4 largest 218 cube 3 listed 1 specks 1 kept 2 debris 2 none 0 left 218" in out

@@ -17,26 +17,14 @@ import pytest
 import lod_expected as L
 import surface_expected as S
 from common import probe_camera
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from voxel_mesh_app import read_ppm, run_app, write_obj
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -331,7 +319,6 @@ def test_device_render_lod_equals_render_lod(mv, tmp_path):
     """apps/device_render --lod: an application kernel on intersectCone and DeviceLod paints the image of mvrt_render_primary_lod"""
     from common import bunny_tris, position_colors
     from massivevoxelraytracing_amd import build as b, scenes
-    from test_gpu_device_api import read_ppm, run_app, write_obj
     b.build_apps(verbose=False)
     exe = os.path.join(ROOT, "apps", "device_render")
     tris = bunny_tris()

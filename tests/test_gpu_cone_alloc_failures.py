@@ -7,10 +7,11 @@ import pytest
 import coarsen_expected as X
 import surface_expected as S
 from alloc_sweep import fail_kth, mv, sweep_reader, with_morton  # noqa: F401 (mv: the fixture)
+from voxel_sets import DPS, LOWER
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS, RES, LEVELS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32, 5
+RES, LEVELS = 32, 5
 
 
 @pytest.fixture(scope="module")

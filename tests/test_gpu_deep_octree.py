@@ -9,35 +9,15 @@ import numpy as np
 import pytest
 
 import deep_scenes as D
-from common import hdr_bytes
-from test_gpu_device_api import compile_probe, probe_trace
-from test_gpu_large_octree import synthetic_reference
-from test_gpu_parity import assert_hits_equal, secondary_like_rays
-from test_gpu_voxel_edit import SET, Model, assert_svo, has_emission
+from edit_model import SET, Model, assert_svo, has_emission
+from fixtures import hdr, mv, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, compile_probe, probe_trace, secondary_like_rays, synthetic_reference
 
 pytestmark = pytest.mark.gpu
 
 THREADS = min(16, len(os.sched_getaffinity(0)))
 MAXF = np.float32(3.402823466e38)
 NO_HINT = np.uint64(0xFFFFFFFFFFFFFFFF)
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(hdr_bytes())
 
 
 def build(mv, s, flags=0, svo=None):

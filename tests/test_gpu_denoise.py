@@ -11,7 +11,9 @@ import pytest
 import common
 import aov_expected as A
 import denoise_expected as D
-from common import GOLDEN, bunny_tris, hdr_bytes, position_colors, probe_camera
+from common import GOLDEN, bunny_tris, position_colors, probe_camera
+from fixtures import hdr, mv, O  # noqa: F401 (fixtures)
+from voxel_mesh_app import write_reader_obj
 
 pytestmark = pytest.mark.gpu
 
@@ -21,29 +23,10 @@ f32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-@pytest.fixture(scope="module")
 def scene(O):
     tris = bunny_tris()
     cols, emis = position_colors(tris)
     return O.build_scene_from_triangles(tris, 256, cols, emis)
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(hdr_bytes())
 
 
 def make_pt(mv, sc, w, h, hdr, tile=(0, 1), aovs=True, moments=True):
@@ -383,11 +366,10 @@ def test_batch_driver_writes_the_denoised_frame(tmp_path, O):
     the Python binding from the dumped camera); the frame itself is unchanged by the option"""
     import massivevoxelraytracing_amd as mv
     from massivevoxelraytracing_amd import build as b
-    from test_apps import write_obj
     exe = b.build_apps(verbose=False)
     tris = bunny_tris()
     obj = tmp_path / "bunny.obj"
-    write_obj(obj, tris)
+    write_reader_obj(obj, tris)
     hdr_file = os.path.join(GOLDEN, "monks_forest_s.hdr")
     W, H, steps = 96, 54, 2
     outs = {}

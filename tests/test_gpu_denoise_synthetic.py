@@ -6,23 +6,10 @@ import pytest
 
 import denoise_cases as K
 import denoise_expected as D
+from fixtures import mv, O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 def run(mv, bufs, W, H, **params):

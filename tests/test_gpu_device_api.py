@@ -3,116 +3,24 @@ with hipcc and loaded through ctypes) gives what mvrt_trace_batch and the CPU or
 descents -- in both stack modes, on every octree flavour the view accepts; apps/device_render reproduces mvrt_render_primary."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from common import bunny_tris, position_colors, probe_camera
+from fixtures import bunny256, mv, O  # noqa: F401 (fixtures)
+from rays import compile_probe, probe_trace, ray_set, upload
+from voxel_mesh_app import read_ppm, run_app, write_obj
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAXF = np.float32(3.402823466e38)
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-def compile_probe(out_dir, flags):
-    so = os.path.join(str(out_dir), "device_api_probe%s.so" % "".join(flags).replace("=", "_"))
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror"] + flags +
-                          ["-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "hip", "device_api_probe.hip"), "-o", so], timeout=300)
-    lib = C.CDLL(so)
-    lib.probe_trace.restype = C.c_int
-    lib.probe_trace.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11 + [C.c_int]
-    lib.probe_attrs.restype = C.c_int
-    lib.probe_attrs.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
-    lib.probe_camera.restype = C.c_int
-    lib.probe_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    return lib
 
 
 @pytest.fixture(scope="module")
 def probe(mv, tmp_path_factory):
     return compile_probe(tmp_path_factory.mktemp("probe"), [])
-
-
-def probe_trace(mv, probe, view, ro, rd, sh=None, mode=0):
-    ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
-    rd = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
-    n = len(ro)
-    if n == 0:
-        assert probe.probe_trace(C.byref(view), 0, *([None] * 11), mode) == 0
-        return {k: np.zeros(0, d) for k, d in (("t", np.float32), ("nMajor", np.int32), ("vIndex", np.uint32), ("descents", np.uint32))}
-    dev = [mv.DeviceArray.from_host(np.ascontiguousarray(a)) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
-    dsh = None if sh is None else mv.DeviceArray.from_host(np.ascontiguousarray(sh, np.uint8))
-    out = [mv.DeviceArray(n, d) for d in (np.float32, np.int32, np.uint32, np.uint32)]
-    rc = probe.probe_trace(C.byref(view), n, *[a.ptr for a in dev], None if dsh is None else dsh.ptr, *[a.ptr for a in out], mode)
-    assert rc == 0, rc
-    return dict(zip(("t", "nMajor", "vIndex", "descents"), (a.to_host() for a in out)))
-
-
-def random_rays(sc, n, seed):
-    """(tests/test_gpu_parity.py) rays from around the grid onto random points of it, with axis-parallel / zero-component directions and rays from inside"""
-    rng = np.random.default_rng(seed)
-    lo, hi = sc.bounds()
-    c = (lo + hi) / 2
-    ext = (hi - lo).max()
-    ro = (c + (rng.random((n, 3)) - 0.5) * ext * 2.5).astype(np.float32)
-    tgt = (lo + rng.random((n, 3)) * (hi - lo)).astype(np.float32)
-    rd = (tgt - ro).astype(np.float32)
-    k = n // 10
-    rd[:k, 0] = 0.0
-    rd[k:2 * k, 1] = 0.0
-    rd[2 * k:3 * k, 2] = 0.0
-    rd[3 * k:3 * k + 50] = np.array([0, 0, -1], np.float32)
-    ro[4 * k:5 * k] = (lo + rng.random((k, 3)) * (hi - lo)).astype(np.float32)
-    return ro, rd
-
-
-def tie_rays(sc, n_out=3000, n_in=1500, seed=3):
-    """(tests/test_gpu_parity.py) diagonals through lattice points of the octree from dyadic distances, and from ON the lattice planes"""
-    lo, _ = sc.bounds()
-    ext = np.float32(sc.dps * sc.grid_res)
-    levels = int(np.log2(sc.grid_res))
-    rng = np.random.default_rng(seed)
-    dirs = [(1, 1, 1), (1, 1, -1), (1, -1, 1), (-1, 1, 1), (1, 1, 0.5), (1, 0.5, 1), (0.5, 1, 1), (1, 0.5, 0.25), (2, 1, 1), (1, 2, -1), (-1, -1, -1), (1, -1, -0.5)]
-    ros, rds = [], []
-    for k in range(n_out):
-        lvl = int(rng.integers(1, levels + 1))
-        cell = ext / np.float32(2 ** lvl)
-        p = lo + cell * rng.integers(0, 2 ** lvl + 1, size=3).astype(np.float32)
-        d = np.array(dirs[k % len(dirs)], np.float32)
-        s = np.float32(2 ** int(rng.integers(0, 3)))
-        ros.append((p - d * ext * s).astype(np.float32))
-        rds.append(d if k % 3 else d * np.float32(0.5))
-    for k in range(n_in):
-        lvl = int(rng.integers(1, levels + 1))
-        cell = ext / np.float32(2 ** lvl)
-        ros.append((lo + cell * rng.integers(0, 2 ** lvl + 1, size=3).astype(np.float32)).astype(np.float32))
-        rds.append(np.array(dirs[k % len(dirs)], np.float32))
-    return np.array(ros, np.float32), np.array(rds, np.float32)
-
-
-def ray_set(sc, n, seed):
-    ro, rd = random_rays(sc, n, seed)
-    tr, td = tie_rays(sc)
-    ro, rd = np.concatenate([ro, tr]), np.concatenate([rd, td])
-    sh = (np.random.default_rng(seed + 1).random(len(ro)) < 0.3).astype(np.uint8)
-    return ro, rd, sh
 
 
 def assert_same(a, b):
@@ -136,17 +44,6 @@ def check_octree(mv, O, probe, svo, sc, n, seed, min_hits=1000):
         assert_same(got, lib)
     assert (lib["vIndex"][sh == 1] == 0).all()
     return ro, rd, sh, lib
-
-
-@pytest.fixture(scope="module")
-def bunny256(O):
-    return O.build_scene_from_triangles(bunny_tris(), 256)
-
-
-def upload(mv, sc, embedded=True):
-    svo = mv.IntersectorOctreeGPU()
-    svo.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission, embeddedMask=embedded)
-    return svo
 
 
 @pytest.mark.parametrize("embedded", [True, False])
@@ -247,14 +144,6 @@ def test_voxel_colour_and_emission_of_every_voxel(mv, O, probe):
 
 
 # ---- apps/device_render ------------------------------------------------------------------------------------------------------------------------
-def write_obj(path, v, cols):
-    with open(path, "w") as f:
-        for p, c in zip(v, cols):
-            f.write("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
-        for t in range(len(v) // 3):
-            f.write("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3))
-
-
 @pytest.fixture(scope="module")
 def render_setup(mv, tmp_path_factory):
     from massivevoxelraytracing_amd import build as b, scenes
@@ -272,19 +161,6 @@ def render_setup(mv, tmp_path_factory):
     svo.build(v, cols, np.zeros_like(v), None, origin, dps, 256)
     cam = probe_camera(origin, dps, 256)
     return exe, d, obj, svo, cam
-
-
-def run_app(exe, args):
-    r = subprocess.run(["timeout", "-k", "10", "120", exe] + args, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout
-
-
-def read_ppm(path, W, H):
-    data = open(path, "rb").read()
-    head = b"P6\n%d %d\n255\n" % (W, H)
-    assert data.startswith(head)
-    return np.frombuffer(data[len(head):], np.uint8).reshape(W * H, 3)
 
 
 @pytest.mark.parametrize("vertex_color", [False, True])

@@ -14,25 +14,12 @@ import ball_expected as B
 import nearest_expected as N
 import surface_expected as S
 from common import GOLDEN, bunny_tris, probe_camera
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, assert_same_octree, colours, filled, full, octree, same, serpentine, shell
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 KEYS = ("xyz", "region", "dist2", "nearest", "attribs")
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def colours(n, seed=1, emission=True):
-    at = np.random.default_rng(seed).integers(0, 256, size=(n, 8), dtype=np.uint8)
-    if not emission:
-        at[:, 4:7] = 0
-    return at
 
 
 def build(mv, xyz, res, flags=0, attribs=None, emission=True):
@@ -40,26 +27,6 @@ def build(mv, xyz, res, flags=0, attribs=None, emission=True):
     svo = mv.IntersectorOctreeGPU()
     svo.build_voxels(xyz, colours(len(xyz), emission=emission) if attribs is None else attribs, origin=LOWER, dps=DPS, gridRes=res, flags=flags)
     return svo
-
-
-def octree(svo):
-    return svo.download(want_morton=True)
-
-
-def same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def assert_same_octree(a, b):  # (as in tests/test_gpu_ball.py)
-    ia, ib = a.info(), b.info()
-    for f in ("numberOfNodes", "numberOfVoxels", "hasEmission", "embeddedMask", "gridRes", "levels", "flavour", "dps", "totalDumpedVoxels"):
-        assert getattr(ia, f) == getattr(ib, f), f
-    assert ia.lower[:] == ib.lower[:] and ia.upper[:] == ib.upper[:] and ia.emissionScale == ib.emissionScale
-    assert same(octree(a), octree(b)) and same(a.read_voxels(), b.read_voxels())
-    if ia.flavour != 2:  # (the tree flavour has no device view)
-        va, vb = a.device_view(), b.device_view()
-        assert (va.cellBlocks != 0, va.cellBits, va.rootIndex, va.rootMask) == (vb.cellBlocks != 0, vb.cellBits, vb.rootIndex, vb.rootMask)
-    assert a.traversal_bytes() == b.traversal_bytes()
 
 
 def assert_listing(svo, res, want=None):
@@ -80,17 +47,6 @@ def assert_listing(svo, res, want=None):
 def check(mv, xyz, res, flags=0, attribs=None):
     svo = build(mv, xyz, res, flags, attribs)
     return svo, assert_listing(svo, res)
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
-
-
-def shell(lo, hi):
-    """the voxels of the hollow cube [lo, hi)^3 (or of the box given by two triples), one voxel thick"""
-    lo, hi = np.broadcast_to(lo, 3), np.broadcast_to(hi, 3)
-    p = np.stack(np.meshgrid(*[np.arange(a, b) for a, b in zip(lo, hi)], indexing="ij"), -1).reshape(-1, 3)
-    return p[((p == lo) | (p == hi - 1)).any(1)]
 
 
 def open_cage():
@@ -180,25 +136,6 @@ def test_far_corner_of_the_largest_grid(mv):
     assert svo.fill_enclosed_nearest() == 63 and svo.enclosed_nearest_device() == (0, 0)
 
 
-def serpentine(res=32):  # (the corridor of tests/test_gpu_fill.py)
-    solid = np.ones((res,) * 3, bool)
-    path, right = [], True
-    ys = list(range(1, res - 1, 2))
-    for z in range(1, res - 1, 2):
-        for y in ys:
-            xs = range(1, res - 1) if right else range(res - 2, 0, -1)
-            path += [(x, y, z) for x in xs]
-            right = not right
-            if y != ys[-1]:
-                path.append((path[-1][0], y + (1 if ys[0] < ys[-1] else -1), z))
-        if z + 2 < res - 1:
-            path.append((path[-1][0], path[-1][1], z + 1))
-        ys.reverse()
-    p = np.array(path)
-    solid[p[:, 0], p[:, 1], p[:, 2]] = False
-    return solid, p
-
-
 def test_serpentine_corridor(mv):
     solid, path = serpentine()
     _, want = check(mv, np.argwhere(solid), 32)
@@ -208,7 +145,7 @@ def test_serpentine_corridor(mv):
 def test_grids_without_an_enclosed_cell(mv):
     for xyz, res in ((full(4), 4), ([(1, 0, 1)], 2), (open_cage(), 8)):
         svo = build(mv, xyz, res)
-        xyz_d, hx = canary(mv, (4, 3), np.uint32)
+        xyz_d, hx = filled(mv, (4, 3), np.uint32)
         assert svo.enclosed_nearest_device(4, xyz_d) == (0, 0) and np.array_equal(xyz_d.to_host(), hx)
         got = svo.enclosed_nearest()
         assert all(len(got[k]) == 0 for k in KEYS) and got["nRegions"] == 0
@@ -344,11 +281,6 @@ def test_through_the_path_tracers_intersector_with_steps_in_flight(mv):
 
 
 # ---- the contract ------------------------------------------------------------------------------------------------------------------------------------------------
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_null_outputs_and_capacity(mv):
     svo = build(mv, debris_cavity(16, 8, 6, 2), 16)
     before, info, held = octree(svo), bytes(svo.info()), mv.allocation_state()[:2]
@@ -365,7 +297,7 @@ def test_null_outputs_and_capacity(mv):
     lib = mv.lib()
     assert lib.mvrt_svo_enclosed_nearest(svo._h, 0, None, None, None, None, None, None, None, None) == 0  # even the counts may be NULL
     # one short: the counts are still returned and nothing is written
-    arrays = {k: canary(mv, *shapes[k]) for k in KEYS}
+    arrays = {k: filled(mv, *shapes[k]) for k in KEYS}
     nc, nr = C.c_uint64(0), C.c_uint64(0)
     assert lib.mvrt_svo_enclosed_nearest(svo._h, n - 1, *[arrays[k][0].ptr for k in KEYS], C.byref(nc), C.byref(nr), None) != 0
     assert (nc.value, nr.value) == (n, want["nRegions"]) and b"capacity %d" % (n - 1) in lib.mvrt_last_error()

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import adaptive_expected as X
+from fixtures import mv  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -30,14 +31,6 @@ RECIPES = [(1, 1.0, 3.0),                      # n == minSamples - 1: 1;  under 
            (16, 16 * 0.2, 16 * (0.04 + 40.0))]
 NON_FINITE = [(32, np.inf, 1.0), (32, 1.0, np.inf), (32, np.nan, 1.0), (32, 1.0, np.nan), (32, np.inf, np.inf), (32, -np.inf, 1.0), (np.inf, 1.0, 1.0), (np.nan, 1.0, 1.0),
               (32, 3e38, 3e38), (32, 1.0, 2.0)]
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 def handle(mv, w, h):

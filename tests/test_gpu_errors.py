@@ -4,21 +4,9 @@ import numpy as np
 import pytest
 
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+from fixtures import mv, O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def test_calls_out_of_order_report_and_recover(mv, O):

@@ -14,18 +14,12 @@ import fill_expected as F
 import merge_expected as M
 import surface_expected as S
 from common import bunny_tris
-from test_gpu_fill import CAGE, DPS, LOWER, canary, filler, full, serpentine, shell, tube
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import CAGE, DPS, LOWER, filled, filler, full, serpentine, shell, tube
 
 pytestmark = pytest.mark.gpu
 
 ALL_FLAGS = (0, M.ANY_ATTRIBUTE, M.WELD, M.ANY_ATTRIBUTE | M.WELD)
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def bits(a):
@@ -310,7 +304,7 @@ def test_masks_are_taken_as_given(mv):
 def test_all_zero_masks_succeed_and_write_nothing(mv):
     svo = build(mv, full(2), 2)
     zero = mv.DeviceArray.from_host(np.zeros(8, np.uint8))
-    (fv, fv_host), (fd, fd_host), (pos, pos_host) = canary(mv, 4, np.uint32), canary(mv, 4, np.uint8), canary(mv, (4, 4, 3), np.float32)
+    (fv, fv_host), (fd, fd_host), (pos, pos_host) = filled(mv, 4, np.uint32), filled(mv, 4, np.uint8), filled(mv, (4, 4, 3), np.float32)
     assert svo.surface_quads_device(4, fv, fd, pos, masks=zero) == 0
     assert svo.surface_mesh_device(4, 4, fv, fd, fv, pos, masks=zero) == (0, 0)
     assert svo.surface_merged_device(M.WELD, 4, 4, fv, fd, None, pos, fv, None, masks=zero) == (0, 0, 0)
@@ -322,7 +316,7 @@ def test_capacity_one_short(mv, mixed):
     svo = build(mv, xyz, 32)
     ext = mv.DeviceArray.from_host(want["masks"])
     n = want["nFaces"]
-    (fv, fv_host), (fd, fd_host), (pos, pos_host) = canary(mv, n, np.uint32), canary(mv, n, np.uint8), canary(mv, (n, 4, 3), np.float32)
+    (fv, fv_host), (fd, fd_host), (pos, pos_host) = filled(mv, n, np.uint32), filled(mv, n, np.uint8), filled(mv, (n, 4, 3), np.float32)
     lib = mv.lib()
     nf = C.c_uint64(0)
     assert lib.mvrt_svo_surface_quads_masked(svo._h, ext.ptr, n - 1, fv.ptr, fd.ptr, pos.ptr, C.byref(nf), None) != 0

@@ -10,11 +10,9 @@ import pytest
 import common
 import surface_expected as S
 from common import bunny_tris
+from voxel_mesh_app import APP, write_obj
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-APP = os.path.join(ROOT, "apps", "voxel_mesh")
 
 
 @pytest.fixture(scope="module")
@@ -22,11 +20,7 @@ def bunny_obj(tmp_path_factory):
     from massivevoxelraytracing_amd import build as b
     b.build_apps(verbose=False)
     tris = bunny_tris()
-    v = tris.reshape(-1, 3)
-    path = tmp_path_factory.mktemp("exterior_app") / "bunny.obj"
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % tuple(p) for p in v) + "".join("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3) for t in range(len(tris))))
-    return str(path)
+    return write_obj(tmp_path_factory.mktemp("exterior_app") / "bunny.obj", tris)
 
 
 def run(obj, ply, *flags):

@@ -13,18 +13,10 @@ import pytest
 import fill_expected as F
 import surface_expected as S
 from common import GOLDEN, bunny_tris, probe_camera
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import CAGE, DPS, LOWER, assert_same_octree, filled, filler, full, serpentine, shell, tube
 
 pytestmark = pytest.mark.gpu
-
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
-CAGE = [(0, 1, 1), (2, 1, 1), (1, 0, 1), (1, 2, 1), (1, 1, 0), (1, 1, 2)]
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def build(mv, xyz, res, flags=0, attribs=None):
@@ -47,17 +39,6 @@ def check(mv, xyz, res, flags=0):
     svo = build(mv, xyz, res, flags)
     assert_cells(svo, want)
     return svo, want
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
-
-
-def shell(lo, hi):
-    """the voxels of the hollow cube [lo, hi)^3 (or of the box given by two triples), one voxel thick"""
-    lo, hi = np.broadcast_to(lo, 3), np.broadcast_to(hi, 3)
-    p = np.stack(np.meshgrid(*[np.arange(a, b) for a, b in zip(lo, hi)], indexing="ij"), -1).reshape(-1, 3)
-    return p[((p == lo) | (p == hi - 1)).any(1)]
 
 
 # ---- tiny grids, the cage, diagonal contact, the border --------------------------------------------------------------------------------------------------------
@@ -90,11 +71,6 @@ def test_shell_on_the_grid_border(mv):
 
 
 # ---- one long gap: the neighbour walk; many chained gaps: the union-find -----------------------------------------------------------------------------------------
-def tube():
-    """a hollow 3 x 3 tube along x, 300 long, closed at both ends, in gridRes 512: one gap of 298 cells whose four neighbour rows hold 298 voxels each"""
-    return shell((100, 10, 20), (400, 13, 23))
-
-
 def test_one_long_gap(mv):
     t = tube()
     _, want = check(mv, t, 512)
@@ -103,28 +79,6 @@ def test_one_long_gap(mv):
     assert cap.sum() == 1
     _, w = check(mv, t[~cap], 512)
     assert len(w["xyz"]) == 0
-
-
-def serpentine(res=32):
-    """a one-cell corridor through a solid res^3 block filling the grid: rows along x at odd y of the odd z layers, joined at alternating ends, the layers joined
-    behind the last row of each.  -> (solid (res, res, res) bool, the corridor's cells in walking order)"""
-    solid = np.ones((res,) * 3, bool)
-    path, right = [], True
-    ys = list(range(1, res - 1, 2))
-    for z in range(1, res - 1, 2):
-        for y in ys:
-            xs = range(1, res - 1) if right else range(res - 2, 0, -1)
-            path += [(x, y, z) for x in xs]
-            right = not right
-            if y != ys[-1]:
-                path.append((path[-1][0], y + (1 if ys[0] < ys[-1] else -1), z))
-        if z + 2 < res - 1:
-            path.append((path[-1][0], path[-1][1], z + 1))
-        ys.reverse()
-    p = np.array(path)
-    assert len({tuple(c) for c in path}) == len(path) and (np.abs(np.diff(p, axis=0)).sum(1) == 1).all()
-    solid[p[:, 0], p[:, 1], p[:, 2]] = False
-    return solid, p
 
 
 def test_many_chained_gaps(mv):
@@ -187,15 +141,6 @@ def emitted_per_gap(xyz, res, want):
     out = np.append(np.where(inside, length, 0), 0)
     assert out.sum() == len(w)
     return out
-
-
-def filler(count, z, res=32):
-    """`count` voxels of layer z without an enclosed gap: full rows along x, then a partial row whose last voxel stands at the far border (one exterior gap)"""
-    i = np.arange(count)
-    p = np.stack([i % res, i // res, np.full(count, z)], 1)
-    if 1 < count % res < res - 1:
-        p[-1, 0] = res - 1
-    return p
 
 
 def seam_scene(n):
@@ -332,11 +277,6 @@ def small(mv, mixed):
     return build(mv, xyz, 32), want
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_null_outputs(mv, small):
     svo, want = small
     n, nr = len(want["xyz"]), want["nRegions"]
@@ -351,7 +291,7 @@ def test_null_outputs(mv, small):
     nc.value = 0
     assert lib.mvrt_svo_enclosed_cells(svo._h, 0, None, None, None, C.byref(nc), None) == 0 and nc.value == nr
     # a larger capacity than the count is fine and writes the count's worth
-    big, host = canary(mv, (n + 5, 3), np.uint32)
+    big, host = filled(mv, (n + 5, 3), np.uint32)
     assert svo.enclosed_cells_device(n + 5, big, None) == (n, nr)
     assert np.array_equal(big.to_host()[:n], want["xyz"]) and np.array_equal(big.to_host()[n:], host[n:])
 
@@ -359,7 +299,7 @@ def test_null_outputs(mv, small):
 def test_capacity_one_short(mv, small):
     svo, want = small
     n, nr = len(want["xyz"]), want["nRegions"]
-    (xyz, xyz_host), (region, region_host) = canary(mv, (n, 3), np.uint32), canary(mv, n, np.uint32)
+    (xyz, xyz_host), (region, region_host) = filled(mv, (n, 3), np.uint32), filled(mv, n, np.uint32)
     lib = mv.lib()
     nc, nreg = C.c_uint64(0), C.c_uint64(0)
     assert lib.mvrt_svo_enclosed_cells(svo._h, n - 1, xyz.ptr, region.ptr, C.byref(nc), C.byref(nreg), None) != 0
@@ -396,19 +336,6 @@ def test_the_handle_is_not_modified(mv, small):
 
 
 # ---- the fill ----------------------------------------------------------------------------------------------------------------------------------------------------------
-def assert_same_octree(a, b):
-    ia, ib = a.info(), b.info()
-    for f in ("numberOfNodes", "numberOfVoxels", "hasEmission", "embeddedMask", "gridRes", "levels", "flavour", "dps"):
-        assert getattr(ia, f) == getattr(ib, f), f
-    assert ia.lower[:] == ib.lower[:] and ia.upper[:] == ib.upper[:] and ia.emissionScale == ib.emissionScale
-    assert all(np.array_equal(x, y) for x, y in zip(a.download(want_morton=True), b.download(want_morton=True)))
-    assert all(np.array_equal(x, y) for x, y in zip(a.read_voxels(), b.read_voxels()))
-    if ia.flavour != 2:  # (the tree flavour has no device view)
-        va, vb = a.device_view(), b.device_view()
-        assert (va.cellBlocks != 0, va.cellBits, va.rootIndex, va.rootMask) == (vb.cellBlocks != 0, vb.cellBits, vb.rootIndex, vb.rootMask)
-    assert a.traversal_bytes() == b.traversal_bytes()  # the resident derived tables
-
-
 RED_GLOW = np.array([200, 10, 20, 7, 90, 0, 0, 9], np.uint8)  # emissive; both alpha bytes are stored as 255
 
 

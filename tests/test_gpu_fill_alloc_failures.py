@@ -7,10 +7,11 @@ import pytest
 
 import fill_expected as F
 from alloc_sweep import filled, mv, same, sweep_edit, sweep_reader  # noqa: F401 (mv: the fixture)
+from voxel_sets import DPS, LOWER
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
+RES = 32
 
 
 @pytest.fixture(scope="module")

@@ -8,24 +8,11 @@ import pytest
 
 import hdri_maps as M
 from common import bunny_tris, position_colors, probe_camera
+from fixtures import mv, O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 RES, W, H = 64, 64, 40
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 @pytest.fixture(scope="module")

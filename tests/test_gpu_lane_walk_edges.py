@@ -12,9 +12,8 @@ import pytest
 
 import deep_scenes as D
 import lane_walk_expected as E
-import test_gpu_ao as A
-import test_gpu_device_api as P
-import test_gpu_range as G
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from rays import compile_probe, compile_range_probe, expected_open, oracle_t, probe_range, probe_trace
 
 pytestmark = pytest.mark.gpu
 
@@ -23,23 +22,9 @@ N_RAGGED = 20_000
 
 
 @pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-@pytest.fixture(scope="module")
 def probes(mv, tmp_path_factory):
     d = tmp_path_factory.mktemp("lane_walk_probes")
-    return P.compile_probe(d, []), G.compile_probe(d, [])
+    return compile_probe(d, []), compile_range_probe(d, [])
 
 
 def in_parts(exp, call):
@@ -77,12 +62,12 @@ def test_every_walk_equals_the_oracle(mv, O, probes, scene, how, embedded):
     # unlimited: the stream kernel, then the device API in both stack modes
     exp.check_unlimited(in_parts(exp, lambda c: svo.intersect(exp.ro[c], exp.rd[c], exp.sh[c], want_descents=True)), "mvrt_trace_batch")
     for mode in (0, 1):
-        exp.check_unlimited(in_parts(exp, lambda c: P.probe_trace(mv, trace_probe, view, exp.ro[c], exp.rd[c], exp.sh[c], mode)), "intersectEx, stack mode %d" % mode)
+        exp.check_unlimited(in_parts(exp, lambda c: probe_trace(mv, trace_probe, view, exp.ro[c], exp.rd[c], exp.sh[c], mode)), "intersectEx, stack mode %d" % mode)
     # limited: kTraceRange, then the device API in both stack modes with occluded()
     got = [in_parts(exp, lambda c: svo.intersect_range(exp.ro[c], exp.rd[c], exp.tmax[c], exp.sh[c], want_descents=True))]
     exp.check_limited(got[0], "mvrt_trace_batch_range", occluded=False)
     for mode in (0, 1):
-        got.append(in_parts(exp, lambda c: G.probe_range(mv, range_probe, view, exp.ro[c], exp.rd[c], exp.sh[c], exp.tmax[c], mode)))
+        got.append(in_parts(exp, lambda c: probe_range(mv, range_probe, view, exp.ro[c], exp.rd[c], exp.sh[c], exp.tmax[c], mode)))
         exp.check_limited(got[-1], "intersectRangeEx, stack mode %d" % mode)
     assert np.array_equal(got[0]["descents"], got[1]["descents"]) and np.array_equal(got[1]["descents"], got[2]["descents"])
 
@@ -118,12 +103,12 @@ def test_occlusion_bake_at_16_levels(mv, O):
     fv, fd = np.ascontiguousarray(mesh["faceVoxel"][pick]), np.ascontiguousarray(mesh["faceDir"][pick])
     assert len(np.unique(pick)) == 2048 and set(fd.tolist()) == set(range(6))
     xyz, _ = svo.read_voxels()
-    t = A.oracle_t(mv, exp.sc, xyz, fv, fd, 16)
+    t = oracle_t(mv, exp.sc, xyz, fv, fd, 16)
     t.setflags(write=False)
     dfv, dfd = mv.DeviceArray.from_host(fv), mv.DeviceArray.from_host(fd)
     for radius in (np.float32(4) * dps, np.float32(np.inf)):
         out = mv.DeviceArray(2048, np.uint16)
         svo.surface_ao_device(2048, dfv, dfd, 16, radius, out)
-        want = A.expected_open(t, radius)
+        want = expected_open(t, radius)
         assert np.array_equal(out.to_host(), want), radius
         assert (want < 16).sum() >= 200 and (want == 16).sum() >= 200  # occluded and open faces both

@@ -5,49 +5,10 @@ import numpy as np
 import pytest
 
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
-from test_gpu_parity import assert_hits_equal, random_rays
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, random_rays, synthetic_reference
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def splitmix64(x):
-    x = (x + np.uint64(0x9E3779B97F4A7C15)).astype(np.uint64)
-    x = ((x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)).astype(np.uint64)
-    x = ((x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)).astype(np.uint64)
-    return x ^ (x >> np.uint64(31))
-
-
-def synthetic_reference(O, res, n, seed):
-    """numpy restatement of the documented generator (include/mvrt.h) + the oracle's merge and non-DAG build"""
-    with np.errstate(over="ignore"):
-        i = np.arange(n, dtype=np.uint64)
-        h = splitmix64(np.uint64(seed) + i)
-        c = splitmix64(h)
-    m = np.uint64(res - 1)
-    xyz = np.stack([h & m, (h >> np.uint64(21)) & m, (h >> np.uint64(42)) & m], -1).astype(np.uint32)
-    morton = O.morton_encode_batch(xyz)
-    rgb = (c & np.uint64(0xFFFFFF)) | np.uint64(0x404040)
-    em = np.where((c >> np.uint64(56)) == 0, rgb, np.uint64(0))
-    attrs = np.zeros((n, 8), np.uint8)
-    for k in range(3):
-        attrs[:, k] = ((rgb >> np.uint64(8 * k)) & np.uint64(255)).astype(np.uint8)
-        attrs[:, 4 + k] = ((em >> np.uint64(8 * k)) & np.uint64(255)).astype(np.uint8)
-    attrs[:, 3] = 255
-    attrs[:, 7] = 255
-    return O.merge_voxels(morton, attrs)
 
 
 def test_non_dag_non_embedded_build_and_traversal(mv, O):

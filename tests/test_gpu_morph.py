@@ -15,53 +15,13 @@ import pytest
 import morph_expected as M
 import surface_expected as S
 from common import GOLDEN, bunny_tris, probe_camera
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, assert_same_octree, build, colours, filled, full, holed_shell, octree, same, specks_and_block
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 ELEMENTS = (M.FACES, M.CUBE)
 OPS = ("dilate", "erode", "close", "open")
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def colours(n, seed=1, emission=True):
-    at = np.random.default_rng(seed).integers(0, 256, size=(n, 8), dtype=np.uint8)
-    if not emission:
-        at[:, 4:7] = 0
-    return at
-
-
-def build(mv, xyz, res, flags=0, attribs=None):
-    xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build_voxels(xyz, colours(len(xyz)) if attribs is None else attribs, origin=LOWER, dps=DPS, gridRes=res, flags=flags)
-    return svo
-
-
-def octree(svo):
-    return svo.download(want_morton=True)
-
-
-def same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def assert_same_octree(a, b):
-    ia, ib = a.info(), b.info()
-    for f in ("numberOfNodes", "numberOfVoxels", "hasEmission", "embeddedMask", "gridRes", "levels", "flavour", "dps", "totalDumpedVoxels"):
-        assert getattr(ia, f) == getattr(ib, f), f
-    assert ia.lower[:] == ib.lower[:] and ia.upper[:] == ib.upper[:] and ia.emissionScale == ib.emissionScale
-    assert same(octree(a), octree(b)) and same(a.read_voxels(), b.read_voxels())
-    if ia.flavour != 2:  # (the tree flavour has no device view)
-        va, vb = a.device_view(), b.device_view()
-        assert (va.cellBlocks != 0, va.cellBits, va.rootIndex, va.rootMask) == (vb.cellBlocks != 0, vb.cellBits, vb.rootIndex, vb.rootMask)
-    assert a.traversal_bytes() == b.traversal_bytes()  # the resident derived tables
 
 
 def assert_listings(svo, res, sparse=False):
@@ -105,18 +65,6 @@ def assert_all(mv, xyz, res, flags=0, attribs=None, sparse=False, steps=(1,)):
     assert_listings(build(mv, xyz, res, flags, attribs), res, sparse)
     for op, e, k in itertools.product(OPS, ELEMENTS, steps):
         assert_op(mv, xyz, res, op, e, k, flags, attribs, sparse)
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
-
-
-def holed_shell():
-    g = np.zeros((16, 16, 16), bool)
-    g[4:11, 4:11, 4:11] = True
-    g[5:10, 5:10, 5:10] = False
-    g[7, 7, 10] = False
-    return np.argwhere(g)
 
 
 # ---- the smallest grids ----------------------------------------------------------------------------------------------------------------------------------------
@@ -230,10 +178,8 @@ def test_borders_and_corners_of_the_largest_grid(mv):
 # ---- several steps, closing and opening ------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def mixed():
-    rng = np.random.default_rng(77)
-    solid = np.ones((12, 12, 12), bool)  # a block with three one-voxel holes, so that three erosion steps leave something, among specks that an opening removes
-    solid[1, 1, 1] = solid[10, 10, 1] = solid[1, 10, 10] = False
-    return np.concatenate([np.argwhere(rng.random((32, 32, 32)) < 0.02), np.argwhere(solid) + 9])
+    # a block with three one-voxel holes, so that three erosion steps leave something, among specks that an opening removes
+    return specks_and_block([(1, 1, 1), (10, 10, 1), (1, 10, 10)])
 
 
 def unique(xyz):
@@ -421,11 +367,6 @@ def small(mv, mixed):
     return build(mv, unique(mixed), 32)
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_null_outputs_and_capacity(mv, small):
     svo = small
     x0, a0 = svo.read_voxels()
@@ -440,17 +381,17 @@ def test_null_outputs_and_capacity(mv, small):
     assert lib.mvrt_svo_erosion_voxels(svo._h, M.CUBE, 0, None, None, None) == 0
     one = build(mv, [(1, 1, 1)], 4)
     assert lib.mvrt_svo_dilate(one._h, M.CUBE, 1, None, None) == 0 and one.info().numberOfVoxels == 27
-    big, host = canary(mv, (n + 5, 3), np.uint32)  # a larger capacity writes the count's worth
+    big, host = filled(mv, (n + 5, 3), np.uint32)  # a larger capacity writes the count's worth
     assert svo.dilation_cells_device(M.CUBE, n + 5, big, None, None) == n
     assert np.array_equal(big.to_host()[:n], want["xyz"]) and np.array_equal(big.to_host()[n:], host[n:])
     # one short: the count is still returned and nothing is written
-    (xyz, xyz_host), (cnt, cnt_host) = canary(mv, (n, 3), np.uint32), canary(mv, n, np.uint32)
+    (xyz, xyz_host), (cnt, cnt_host) = filled(mv, (n, 3), np.uint32), filled(mv, n, np.uint32)
     nc = C.c_uint64(0)
     assert lib.mvrt_svo_dilation_cells(svo._h, M.CUBE, n - 1, xyz.ptr, None, cnt.ptr, C.byref(nc), None) != 0
     assert nc.value == n and b"capacity %d" % (n - 1) in lib.mvrt_last_error() and b"%d cells" % n in lib.mvrt_last_error()
     assert np.array_equal(xyz.to_host(), xyz_host) and np.array_equal(cnt.to_host(), cnt_host)
     gone = M.erosion_voxels(x0, 32, M.FACES)
-    vi, vi_host = canary(mv, len(gone), np.uint32)
+    vi, vi_host = filled(mv, len(gone), np.uint32)
     nc.value = 0
     assert lib.mvrt_svo_erosion_voxels(svo._h, M.FACES, len(gone) - 1, vi.ptr, C.byref(nc), None) != 0
     assert nc.value == len(gone) and b"capacity" in lib.mvrt_last_error() and np.array_equal(vi.to_host(), vi_host)

@@ -8,36 +8,14 @@ import subprocess
 import numpy as np
 import pytest
 
+import common
 import morph_expected as M
 import surface_expected as S
-from test_morph_mirror import compile_usage
+from voxel_mesh_app import APP, holed_box, write_obj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-APP = os.path.join(ROOT, "apps", "voxel_mesh")
 RES = 16
-
-
-def quad(a, b, c, d):
-    return [a, b, c, a, c, d]
-
-
-def holed_box():
-    """the unit cube as triangles; its floor z = 0 is four rectangles around the hole [0.43, 0.51]^2.  Two small triangles off two opposite corners stretch the
-    bounding grid to [-0.03, 1.03]^3, so that no face lies on a cell boundary: the floor voxel x = y = 7 of the 16^3 grid spans [0.43375, 0.5], inside the hole,
-    and its neighbours 6 and 8 reach under the rectangles"""
-    v = [(-0.03, -0.03, -0.03), (-0.02, -0.03, -0.03), (-0.03, -0.02, -0.03), (1.03, 1.03, 1.03), (1.02, 1.03, 1.03), (1.03, 1.02, 1.03)]
-    for axis in range(3):
-        for side in (0.0, 1.0):
-            if axis == 2 and side == 0.0:
-                continue
-            p = [[0.0, 0.0], [1.0, 0.0], [1.0, 1.0], [0.0, 1.0]]
-            v += quad(*[tuple(np.insert(np.array(q), axis, side)) for q in p])
-    h0, h1 = 0.43, 0.51
-    for (x0, x1, y0, y1) in ((0.0, 1.0, 0.0, h0), (0.0, 1.0, h1, 1.0), (0.0, h0, h0, h1), (h1, 1.0, h0, h1)):
-        v += quad((x0, y0, 0.0), (x1, y0, 0.0), (x1, y1, 0.0), (x0, y1, 0.0))
-    return np.array(v, np.float32).reshape(-1, 3, 3)
 
 
 @pytest.fixture(scope="module")
@@ -46,9 +24,7 @@ def box_obj(tmp_path_factory):
     b.build_apps(verbose=False)
     tris = holed_box()
     path = tmp_path_factory.mktemp("morph_app") / "box.obj"
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % tuple(p) for p in tris.reshape(-1, 3)) + "".join("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3) for t in range(len(tris))))
-    return str(path), tris
+    return write_obj(path, tris), tris
 
 
 def test_close_then_fill_repairs_the_leaky_box(tmp_path, box_obj):
@@ -102,7 +78,7 @@ def test_the_other_operators_and_the_element_flag(tmp_path, box_obj):
 
 
 def test_cpp_mirror_runs(tmp_path):
-    exe, _ = compile_usage(tmp_path)
+    exe, _ = common.compile_usage(tmp_path, "morph_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     assert "shell 217 leaky 0 cells 485 peeled 217 plugged 1 enclosed 125 grown 392 opened 0 eroded 348 left 262" in out

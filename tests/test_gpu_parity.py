@@ -5,7 +5,9 @@ mathMode 1 = the shared deterministic transcendental set, see include/mvrt_detma
 import numpy as np
 import pytest
 
-from common import bunny_tris, golden, hdr_bytes, position_colors, probe_camera
+from common import bunny_tris, golden, position_colors, probe_camera
+from fixtures import bunny256, hdr, load, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, make_pt, random_rays, secondary_like_rays, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -13,23 +15,11 @@ G = golden()
 
 
 @pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
 def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
+    m = load()
     assert m.device_count() >= 1
     print("device:", m.device_name())
     return m
-
-
-@pytest.fixture(scope="module")
-def bunny256(O):
-    return O.build_scene_from_triangles(bunny_tris(), 256)
 
 
 @pytest.fixture(scope="module")
@@ -41,41 +31,6 @@ def bunny256_color(O):
     return sc
 
 
-def upload(mv, sc, embedded=True):
-    svo = mv.IntersectorOctreeGPU()
-    svo.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission, embeddedMask=embedded)
-    return svo
-
-
-def random_rays(sc, n, seed):
-    rng = np.random.default_rng(seed)
-    lo, hi = sc.bounds()
-    c = (lo + hi) / 2
-    ext = (hi - lo).max()
-    ro = (c + (rng.random((n, 3)) - 0.5) * ext * 2.5).astype(np.float32)
-    tgt = (lo + rng.random((n, 3)) * (hi - lo)).astype(np.float32)
-    rd = (tgt - ro).astype(np.float32)
-    # a share of axis-parallel and zero-component directions (the 1/0 clamp path, voxCommon.hpp:265-269)
-    k = n // 10
-    rd[:k, 0] = 0.0
-    rd[k:2 * k, 1] = 0.0
-    rd[2 * k:3 * k, 2] = 0.0
-    rd[3 * k:3 * k + 50] = np.array([0, 0, -1], np.float32)
-    # rays starting inside the volume
-    ro[4 * k:5 * k] = (lo + rng.random((k, 3)) * (hi - lo)).astype(np.float32)
-    return ro, rd
-
-
-def assert_hits_equal(a, b):
-    assert np.array_equal(a["t"], b["t"])
-    hit = a["t"] != np.float32(3.402823466e38)
-    assert np.array_equal(a["nMajor"][hit], b["nMajor"][hit])
-    assert np.array_equal(a["vIndex"][hit], b["vIndex"][hit])
-    assert (b["nMajor"][~hit] == -1).all()
-    if "descents" in a and "descents" in b:
-        assert np.array_equal(a["descents"], b["descents"])
-
-
 def test_trace_batch_bit_exact(mv, O, bunny256):
     svo = upload(mv, bunny256)
     ro, rd = random_rays(bunny256, 200_000, 7)
@@ -85,18 +40,6 @@ def test_trace_batch_bit_exact(mv, O, bunny256):
     assert_hits_equal(want, got)
     assert (got["vIndex"][sh == 1] == 0).all()  # shadow rays never accumulate vIndex
     assert (want["t"] != O.MAX_FLOAT).sum() > 10000
-
-
-def secondary_like_rays(sc, prim_ro, prim_rd, hits, seed):
-    """rays that start ON the voxels other rays hit (what the path tracer's shadow / bounce rays are): origin = ro + rd * t as the shade kernel
-    computes it, direction random; the hint = Morton code of the hit voxel"""
-    rng = np.random.default_rng(seed)
-    hit = hits["t"] != np.float32(3.402823466e38)
-    t = hits["t"][hit].astype(np.float32)
-    ro = (prim_ro[hit] + prim_rd[hit] * t[:, None]).astype(np.float32)
-    rd = rng.normal(size=ro.shape).astype(np.float32)
-    hint = sc.morton[hits["vIndex"][hit]].astype(np.uint64)
-    return ro, rd, hint
 
 
 @pytest.mark.parametrize("res", [256, 1024])
@@ -208,23 +151,6 @@ def test_compaction_indices_bit_exact(mv, O, n):
         dst, kept = mv.compact_indices(keep)
         assert kept == len(src_want)
         assert np.array_equal(dst, dst_want)
-
-
-def make_pt(mv, O, sc, w, h, rgba, hw, hh, tile=(0, 1), hdri_scale=None):
-    pt = mv.PathTracer()
-    pt.setup(None)
-    pt.set_tile(*tile)
-    pt.resizeFrameBufferIfNeeded(None, w, h)
-    pt.loadHDRIPixels(None, rgba, hw, hh, rgba, hw, hh)
-    if hdri_scale is not None:
-        pt.set_hdri_scale(hdri_scale)
-    pt.m_intersectorOctreeGPU.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission)
-    return pt
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(hdr_bytes())
 
 
 def test_hdri_tables_bit_exact(mv, O, bunny256, hdr):

@@ -10,26 +10,13 @@ import pytest
 import query_expected as Q
 import surface_expected as S
 from common import bunny_tris
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, colours, filled, full, octree, same, shell
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 KEYS = ("dist2", "nearest", "attribs")
 NO_LIMIT, NONE = Q.NO_LIMIT, Q.NONE
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def colours(n, seed=1, emission=True):
-    at = np.random.default_rng(seed).integers(0, 256, size=(n, 8), dtype=np.uint8)
-    if not emission:
-        at[:, 4:7] = 0
-    return at
 
 
 def build(mv, xyz, res, flags=0, attribs=None, emission=True, seed=1):
@@ -37,23 +24,6 @@ def build(mv, xyz, res, flags=0, attribs=None, emission=True, seed=1):
     svo = mv.IntersectorOctreeGPU()
     svo.build_voxels(xyz, colours(len(xyz), seed, emission) if attribs is None else attribs, origin=LOWER, dps=DPS, gridRes=res, flags=flags)
     return svo
-
-
-def octree(svo):
-    return svo.download(want_morton=True)
-
-
-def same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
-
-
-def shell(lo, hi):
-    p = full(hi - lo) + lo
-    return p[((p == lo) | (p == hi - 1)).any(1)]
 
 
 def ask(svo, queries, max_dist2=NO_LIMIT):
@@ -64,11 +34,6 @@ def ask(svo, queries, max_dist2=NO_LIMIT):
     for k in KEYS:
         assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and np.array_equal(got[k], want[k]), k
     return want
-
-
-def canary(mv, shape, dtype):
-    host = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(host), host
 
 
 # ---- the walk -------------------------------------------------------------------------------------------------------------------------------------------------
@@ -293,8 +258,8 @@ def test_a_set_against_itself(mv, bunny_case):
 def test_capacity_too_small_writes_nothing(mv, cube_case):
     a = cube_case[0]
     n = a.info().numberOfVoxels
-    d2, hd = canary(mv, n, np.uint64)
-    near, hn = canary(mv, n, np.uint32)
+    d2, hd = filled(mv, n, np.uint64)
+    near, hn = filled(mv, n, np.uint32)
     for arrays in ({"dist2": d2, "nearest": near}, {"dist2": d2}, {"nearest": near}):
         with pytest.raises(mv.MvrtError, match="capacity %d is smaller than the %d" % (n - 1, n)):
             a.nearest_between_device(a, capacity=n - 1, **arrays)

@@ -10,18 +10,11 @@ import pytest
 
 import surface_expected as S
 from common import bunny_tris, position_colors
+from voxel_mesh_app import APP, run, write_obj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-APP = os.path.join(ROOT, "apps", "voxel_mesh")
 RES = 64
-
-
-def write_obj(path, v, c):
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (tuple(p) + tuple(q)) for p, q in zip(v, c)) + "".join("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3) for t in range(len(v) // 3)))
-    return str(path)
 
 
 @pytest.fixture(scope="module")
@@ -38,12 +31,6 @@ def scene(tmp_path_factory):
     w = (w + (hi - lo) * np.array([0.1, 0.05, -0.05], np.float32)).astype(np.float32)  # and shifted
     c2 = np.ascontiguousarray(c[:, ::-1])  # other colours
     return write_obj(d / "bunny.obj", v, c), write_obj(d / "other.obj", w, c2), (v, w, c, c2)
-
-
-def run(*args):
-    out = subprocess.check_output([APP] + [str(a) for a in args], timeout=120).decode()
-    print(out)
-    return out
 
 
 def both(mv, scene):

@@ -1,62 +1,24 @@
 """Distance-limited rays on the MI355X: mvrt_trace_batch_range and a user kernel on the limited methods of include/mvrt/device.hpp (tests/hip/range_probe.hip,
-both stack modes) report, bit for bit, the CPU oracle's unlimited hit where its t <= tMax and a miss otherwise -- on the ray set of test_gpu_device_api.py (random,
+both stack modes) report, bit for bit, the CPU oracle's unlimited hit where its t <= tMax and a miss otherwise -- on the ray set of tests/rays.py (random,
 zero-component, from-inside and dyadic tie rays, 30 % shadow) with a per-ray limit that cycles over t, its two neighbours, 0.25 t, 4 t, MAX_FLOAT, +inf, 0, -1, NaN."""
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from common import bunny_tris
+from fixtures import mv, O  # noqa: F401 (fixtures)
 from lane_walk_expected import CASES, expected, limits  # shared with tests/test_lane_walk_cpu.py and tests/test_gpu_lane_walk_edges.py
-from test_gpu_device_api import ray_set, upload
+from rays import compile_range_probe, probe_range, ray_set, upload
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAXF = np.float32(3.402823466e38)
 OUTPUTS = ("t", "nMajor", "vIndex", "descents")
 
 
 @pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-def compile_probe(out_dir, flags):
-    so = os.path.join(str(out_dir), "range_probe%s.so" % "".join(flags).replace("=", "_"))
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror"] + flags +
-                          ["-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "hip", "range_probe.hip"), "-o", so], timeout=300)
-    lib = C.CDLL(so)
-    lib.probe_range.restype = C.c_int
-    lib.probe_range.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 13 + [C.c_int]
-    return lib
-
-
-@pytest.fixture(scope="module")
 def probe(mv, tmp_path_factory):
-    return compile_probe(tmp_path_factory.mktemp("range_probe"), [])
-
-
-def probe_range(mv, probe, view, ro, rd, sh, tmax, mode):
-    n = len(ro)
-    dev = [mv.DeviceArray.from_host(np.ascontiguousarray(a)) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
-    dsh, dlim = mv.DeviceArray.from_host(np.ascontiguousarray(sh, np.uint8)), mv.DeviceArray.from_host(np.ascontiguousarray(tmax, np.float32))
-    out = [mv.DeviceArray(n, d) for d in (np.float32, np.int32, np.uint32, np.uint32, np.uint8)]
-    rc = probe.probe_range(C.byref(view), n, *[a.ptr for a in dev], dsh.ptr, dlim.ptr, *[a.ptr for a in out], mode)
-    assert rc == 0, rc
-    return dict(zip(OUTPUTS + ("occluded",), (a.to_host() for a in out)))
+    return compile_range_probe(tmp_path_factory.mktemp("range_probe"), [])
 
 
 class Reference:
@@ -176,7 +138,7 @@ def test_tree_flavour_is_refused_by_name(mv):
 
 
 def test_contract_on_build_gives_identical_output(mv, probe, bunny256, ref256, tmp_path):
-    on = compile_probe(tmp_path, ["-ffp-contract=on"])
+    on = compile_range_probe(tmp_path, ["-ffp-contract=on"])
     ref = ref256[True]
     svo = upload(mv, bunny256[True])  # (kept alive: the view is a snapshot of its buffers)
     view = svo.device_view()

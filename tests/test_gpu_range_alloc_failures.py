@@ -6,10 +6,11 @@ import numpy as np
 import pytest
 
 from alloc_sweep import filled, mv  # noqa: F401 (mv: the fixture)
+from voxel_sets import DPS, LOWER
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
+RES = 32
 
 
 def test_each_allocation_fails_in_turn(mv):

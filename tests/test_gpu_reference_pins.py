@@ -15,22 +15,10 @@ import pytest
 
 import reference_pins as R
 from common import hdr_bytes
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from rays import compile_probe
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -135,7 +123,6 @@ def test_pmj_table_on_the_device(mv, render):
 def test_device_camera(mv, render, tmp_path_factory):
     """mvrt::CameraPinhole::shoot / shootThinLens of include/mvrt/device.hpp, run on the device by tests/hip/device_api_probe.hip: corner pixels, offsets and
     lens samples at 0 and at the float below 1, odd and non-square sizes, an orthonormal and a skewed basis -- 2736 rays per camera and entry point"""
-    from test_gpu_device_api import compile_probe
     probe = compile_probe(tmp_path_factory.mktemp("camera_probe"), [])
     px, fl = R.camera_rays()
     dpx, dfl = mv.DeviceArray.from_host(px), mv.DeviceArray.from_host(fl)

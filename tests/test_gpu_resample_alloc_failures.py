@@ -8,20 +8,12 @@ import pytest
 
 import resample_expected as E
 from alloc_sweep import filled, mv, same, sweep_edit, sweep_reader  # noqa: F401 (mv: the fixture)
+from voxel_sets import DPS, LOWER, block_and_noise
 
 pytestmark = pytest.mark.gpu
 
-LOWER, DPS, RES = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013), 32
+RES = 32
 TURN = E.rotation((1, 2, 3), 30.0)
-
-
-def voxels(seed):
-    rng = np.random.default_rng(seed)
-    solid = np.zeros((RES, RES, RES), bool)
-    solid[8:20, 8:20, 8:20] = True
-    solid |= rng.random((RES, RES, RES)) < 0.03
-    xyz = np.argwhere(solid).astype(np.uint32)
-    return xyz, rng.integers(0, 256, (len(xyz), 8), dtype=np.uint8)
 
 
 def build(svo, v, res=RES):
@@ -31,7 +23,7 @@ def build(svo, v, res=RES):
 @pytest.mark.parametrize("rd", [32, 64])
 def test_each_allocation_of_the_listing_fails_in_turn(mv, rd):
     src = mv.IntersectorOctreeGPU()
-    build(src, voxels(31))
+    build(src, block_and_noise(31, RES))
     mt = E.about_centre(TURN * (RES / rd), RES, rd)
     xf = mv.CellTransform.make(*mt)
     want = E.dense(*src.read_voxels(), RES, mt[0], mt[1], rd)
@@ -53,7 +45,7 @@ def test_each_allocation_of_the_build_fails_in_turn(mv, in_place):
     xf = mv.CellTransform.make(*mt)
     base = mv.allocation_state()[:2]
     src, dst = mv.IntersectorOctreeGPU(), mv.IntersectorOctreeGPU()
-    v_src, v_dst = voxels(31), voxels(35)
+    v_src, v_dst = block_and_noise(31, RES), block_and_noise(35, RES)
     build(src, v_src)
     held_src = tuple(x - y for x, y in zip(mv.allocation_state()[:2], base))
     if in_place:

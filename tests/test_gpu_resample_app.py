@@ -13,19 +13,11 @@ import combine_expected as CE
 import resample_expected as E
 import surface_expected as S
 from common import bunny_tris
+from voxel_mesh_app import APP, run, write_obj
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-APP = os.path.join(ROOT, "apps", "voxel_mesh")
 RES = 64
-
-
-def write_obj(path, tris):
-    tris = tris.reshape(-1, 3, 3)
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % tuple(p) for p in tris.reshape(-1, 3)) + "".join("f %d %d %d\n" % (3 * t + 1, 3 * t + 2, 3 * t + 3) for t in range(len(tris))))
-    return str(path)
 
 
 @pytest.fixture(scope="module")
@@ -57,12 +49,6 @@ def world_about_centre(origin, dps, axis, degrees, scale):
     centre = origin.astype(np.float64) + half
     W = scale * E.rotation(axis, degrees)
     return np.concatenate([W, (centre - W @ centre).reshape(3, 1)], 1)
-
-
-def run(*args):
-    out = subprocess.check_output([APP] + [str(a) for a in args], timeout=120).decode()
-    print(out)
-    return out
 
 
 @pytest.mark.parametrize("axis,degrees,scale,offset", [((0, 0, 1), 90.0, None, None), ((1, 2, 3), 30.0, 0.75, (2, 0, -1))])

@@ -6,39 +6,19 @@ for the path tracer):
   * ancestors stacked by the hint replay (their resume point comes from the hint's prefix),
   * more pending ancestors than the LDS ring has slots (evicted entries come back from the HBM spill rows in the same format),
   * tied mid-plane times (candidates of the chain coincide: the filter must not admit the child already taken again)."""
-import types
 
 import numpy as np
 import pytest
 
 import deep_scenes as D
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
-from test_gpu_parity import assert_hits_equal
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, voxel_scene
 
 pytestmark = pytest.mark.gpu
 
 MAXF = np.float32(3.402823466e38)
 FLAGS = [0, 2, 3]  # embedded masks / plain indices / tree (bricks): flavours 0, 1, 2
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
-
-
-def voxel_scene(xyz, res):
-    xyz = np.ascontiguousarray(xyz, np.uint32)
-    attrs = np.full((len(xyz), 8), 255, np.uint8)
-    attrs[:, 4:7] = 0
-    return types.SimpleNamespace(xyz=xyz, attrs=attrs, res=res, origin=np.zeros(3, np.float32), dps=np.float32(1.0 / res))
 
 
 def build(mv, s, flags):

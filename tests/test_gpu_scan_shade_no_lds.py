@@ -7,26 +7,13 @@ import numpy as np
 import pytest
 
 import adaptive_expected as X
-from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+from common import bunny_tris, position_colors, probe_camera
+from fixtures import hdr, mv, O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 BLOCK, T, C = 256, 256, 256
 COUNTERS = ("samples", "rays", "shadowRays", "descents", "shadowDescents", "hits")
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -36,11 +23,6 @@ def scene(O):
     sc = O.build_scene_from_triangles(tris, 256, cols, emis)
     assert sc.has_emission == 1
     return sc
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(hdr_bytes())
 
 
 @pytest.fixture(scope="module")

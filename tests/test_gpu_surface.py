@@ -14,18 +14,12 @@ import pytest
 import common
 import surface_expected as S
 from common import bunny_tris
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, filled, full
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # no power of two: products and sums really round
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def bits(a):
@@ -57,10 +51,6 @@ def check(mv, xyz, res, flags=0):
     assert svo.info().numberOfVoxels == len(want["xyz"])
     assert_surface(svo, want)
     return svo, want
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
 
 
 # ---- tiny grids ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -237,15 +227,10 @@ def small(mv):
     return build(mv, xyz, 16), S.surface(xyz, 16, LOWER, DPS)
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_capacity_one_short(mv, small):
     svo, want = small
     n, m = want["nFaces"], len(want["vertices"])
-    outs = {k: canary(mv, s, t) for k, s, t in (("fv", n, np.uint32), ("fd", n, np.uint8), ("pos", (n, 12), np.float32), ("idx", (n, 4), np.uint32), ("vtx", (m, 3), np.float32))}
+    outs = {k: filled(mv, s, t) for k, s, t in (("fv", n, np.uint32), ("fd", n, np.uint8), ("pos", (n, 12), np.float32), ("idx", (n, 4), np.uint32), ("vtx", (m, 3), np.float32))}
     nf, nv = C.c_uint64(0), C.c_uint64(0)
     lib = mv.lib()
     assert lib.mvrt_svo_surface_quads(svo._h, n - 1, outs["fv"][0].ptr, outs["fd"][0].ptr, outs["pos"][0].ptr, C.byref(nf), None) != 0

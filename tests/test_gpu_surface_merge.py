@@ -14,20 +14,14 @@ import common
 import merge_expected as M
 import surface_expected as S
 from common import bunny_tris
+from fixtures import mv  # noqa: F401 (fixtures)
+from voxel_sets import DPS, LOWER, filled, full
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)  # as in test_gpu_surface.py
 ALL_FLAGS = (0, M.ANY_ATTRIBUTE, M.WELD, M.ANY_ATTRIBUTE | M.WELD)
 RED, BLUE = (200, 10, 10, 255, 0, 0, 0, 255), (10, 10, 200, 255, 0, 0, 0, 255)
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def bits(a):
@@ -73,10 +67,6 @@ def assert_merged(svo, res, flags_list=ALL_FLAGS, lower=LOWER, dps=DPS):
 def check(mv, xyz, res, attrs=None, flags_list=ALL_FLAGS, build_flags=0):
     svo = build(mv, xyz, res, attrs, build_flags)
     return svo, assert_merged(svo, res, flags_list)
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
 
 
 def two_colours(rng, n):
@@ -275,15 +265,10 @@ def small(mv):
     return svo, M.merged(xyz, attrs, 16, LOWER, DPS, M.WELD)
 
 
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
-
-
 def test_capacity_one_short(mv, small):
     svo, want = small
     f, n, m = want["nFaces"], len(want["rectVoxel"]), len(want["vertices"])
-    outs = {k: canary(mv, s, t) for k, s, t in (("rv", n, np.uint32), ("rd", n, np.uint8), ("rs", (n, 2), np.uint32), ("pos", (n, 12), np.float32), ("idx", (n, 4), np.uint32),
+    outs = {k: filled(mv, s, t) for k, s, t in (("rv", n, np.uint32), ("rd", n, np.uint8), ("rs", (n, 2), np.uint32), ("pos", (n, 12), np.float32), ("idx", (n, 4), np.uint32),
                                                 ("vtx", (m, 3), np.float32))}
     p = {k: v[0].ptr for k, v in outs.items()}
     lib = mv.lib()
@@ -334,7 +319,7 @@ def test_refusals_without_gpu_work(mv, small):
     i = svo.info()
     up = mv.IntersectorOctreeGPU()
     up.upload(nodes, attrs, LOWER, DPS, 16, i.hasEmission, embeddedMask=bool(i.embeddedMask))
-    idx, vtx = canary(mv, (n, 4), np.uint32), canary(mv, (len(want["vertices"]), 3), np.float32)
+    idx, vtx = filled(mv, (n, 4), np.uint32), filled(mv, (len(want["vertices"]), 3), np.float32)
     before = mv.allocation_state()[2]
     for h, text in ((empty, "no octree"), (up, "keeps no Morton codes")):
         for flags in ALL_FLAGS:

@@ -10,32 +10,14 @@ import numpy as np
 import pytest
 
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
-from test_gpu_parity import assert_hits_equal, make_pt, random_rays, secondary_like_rays, upload
+from fixtures import bunny256, mv, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, make_pt, random_rays, secondary_like_rays, upload
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 36, 37, 65, 4097, 150_001)
 N_MAX = max(SIZES)
 NO_HINT = np.uint64(0xFFFFFFFFFFFFFFFF)
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-@pytest.fixture(scope="module")
-def bunny256(O):
-    return O.build_scene_from_triangles(bunny_tris(), 256)
 
 
 @pytest.fixture(scope="module")

@@ -10,10 +10,10 @@ import pytest
 
 import deep_scenes as D
 import upload_shapes as U
-from common import bunny_tris, hdr_bytes, position_colors, probe_camera
-from massivevoxelraytracing_amd import IntersectorOctreeGPU
-from test_gpu_device_api import compile_probe, probe_trace
-from test_gpu_parity import assert_hits_equal, random_rays
+from common import probe_camera
+from fixtures import hdr, mv, O  # noqa: F401 (fixtures)
+from rays import assert_hits_equal, compile_probe, probe_trace, random_rays
+from upload_shapes import Base, bases, oracle_scene, shapes, upload, voxel_set  # noqa: F401 (bases is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,99 +23,8 @@ NO_HINT = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 @pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
-
-
-@pytest.fixture(scope="module")
-def hdr(O):
-    return O.decode_rgbe(hdr_bytes())
-
-
-@pytest.fixture(scope="module")
 def probe(mv, tmp_path_factory):
     return compile_probe(tmp_path_factory.mktemp("probe_shapes"), [])
-
-
-class Base:
-    """a voxel set: sorted Morton codes, merged attributes, grid"""
-
-    def __init__(self, name, morton, attrs, res, origin=(0.0, 0.0, 0.0), dps=None, he=None):
-        self.name, self.morton, self.attrs, self.res = name, np.asarray(morton, np.uint64), np.asarray(attrs, np.uint8).reshape(-1, 8), res
-        self.origin = np.asarray(origin, np.float32)
-        self.dps = np.float32(1.0 / res) if dps is None else np.float32(dps)
-        self.he = int((self.attrs[:, 4:7] != 0).any()) if he is None else he
-
-
-def voxel_set(name, levels, n_cluster, n_scattered, seed):
-    rng = np.random.default_rng(seed)
-    res = 1 << levels
-    box = max(2, res // 3)
-    pts = np.concatenate([rng.integers(0, box, (n_cluster, 3)) + res // 4, rng.integers(0, res, (n_scattered, 3))])
-    m = np.unique(D.morton(pts))
-    attrs = rng.integers(0, 256, (len(m), 8), dtype=np.uint8)
-    attrs[rng.random(len(m)) >= 0.1, 4:7] = 0
-    attrs[:, 3] = 255
-    return Base(name, m, attrs, res)
-
-
-@pytest.fixture(scope="module")
-def bases(O):
-    tris = bunny_tris()
-    cols, emis = position_colors(tris)
-    b = O.build_scene_from_triangles(tris, 256, cols, emis)
-    out = {"bunny256": Base("bunny256", b.morton, b.attrs, 256, b.origin, b.dps, b.has_emission),
-           "random7": voxel_set("random7", 7, 20_000, 2_000, 7),
-           "random9": voxel_set("random9", 9, 30_000, 3_000, 9)}
-    for L in (1, 2, 3):
-        rng = np.random.default_rng(100 + L)
-        out["single%d" % L] = Base("single%d" % L, [int(rng.integers(0, 8 ** L))], [[200, 100, 50, 255, 0, 0, 0, 0]], 1 << L)
-    s = D.DeepScene(14)
-    sc = D.oracle_scene(O, s)
-    out["deep14"] = Base("deep14", sc.morton, sc.attrs, s.res, s.origin, s.dps, sc.has_emission)
-    return out
-
-
-def shapes(O, base, emb, seed):
-    """{shape: (nodes, keeps_builder_answers)}: every legal generator on the builder's octree of `base` (the empty octree: itself only)"""
-    if base is None:
-        empty = np.zeros(1, O.NODE_DTYPE)
-        empty["children"] = U.LEAF
-        return {"empty": (empty, True)}
-    rng = np.random.default_rng(seed)
-    nodes = O.build_octree(base.morton, base.res, dag=True, embed=emb)
-    nv, res = len(base.morton), base.res
-    out = {"builder": (nodes, True), "permute": (U.permute(nodes, emb, rng), True), "unreachable": (U.add_unreachable(nodes, emb, rng, 50, 50), True),
-           "unshare": (U.unshare(nodes, emb), True), "empty_inner": (U.add_empty_inner(nodes, res, emb, rng, 64), False),
-           "psum_zero": (U.psum_zero(nodes), False), "psum_random": (U.psum_random(U.permute(nodes, emb, rng), nv, res, rng), False)}
-    if nv >= 2:
-        out["psum_one_off"] = (U.psum_one_off(nodes, emb)[0], False)
-    out["all"] = (U.permute(U.add_unreachable(U.add_empty_inner(U.unshare(nodes, emb), res, emb, rng), emb, rng), emb, rng), False)
-    for k, (n, _) in out.items():
-        U.set_masks_zero_padding(n)
-        assert IntersectorOctreeGPU.check_upload(n, nv, res, emb) is None, k
-    return out
-
-
-def oracle_scene(O, base, nodes, emb):
-    if base is None:
-        return O.Scene(nodes, np.zeros((0, 8), np.uint8), (0.0, 0.0, 0.0), 0.25, 4, 0, embedded=emb)
-    return O.Scene(nodes, base.attrs, base.origin, base.dps, base.res, base.he, embedded=emb)
-
-
-def upload(mv, sc, emb, svo=None):
-    svo = mv.IntersectorOctreeGPU() if svo is None else svo
-    svo.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission, embeddedMask=emb)
-    return svo
 
 
 def rays_in_voxels(base, paths, n, seed):

@@ -4,23 +4,10 @@ import numpy as np
 import pytest
 
 from common import bunny_tris, hdr_bytes, position_colors, probe_camera
+from edit_model import REMOVE, SET, Model, assert_svo, has_emission, normalised
+from fixtures import mv, O  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-SET, REMOVE = 1, 0
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    return m
 
 
 def decode(m):
@@ -33,38 +20,6 @@ def decode(m):
             v |= ((m >> np.uint64(3 * b + axis)) & np.uint64(1)) << np.uint64(b)
         out[:, axis] = v.astype(np.uint32)
     return out
-
-
-def normalised(attrs):
-    a = np.array(attrs, np.uint8).reshape(-1, 8)
-    a[:, 3] = 255
-    a[:, 7] = 255
-    return a
-
-
-def has_emission(attrs):
-    return int(np.any(attrs[:, 4:7] != 0))
-
-
-def oracle_octree(O, morton, grid_res, flags):
-    return O.build_octree(morton, grid_res, dag=not (flags & 1), embed=not (flags & 2))
-
-
-def assert_svo(O, svo, morton, attrs, he, grid_res, flags, dumped, nodes=None):
-    """the handle holds exactly the octree the oracle builds over (morton, attrs)"""
-    info = svo.info()
-    if nodes is None:
-        nodes = oracle_octree(O, morton, grid_res, flags)
-    assert info.totalDumpedVoxels == dumped
-    assert info.numberOfVoxels == len(morton)
-    assert info.numberOfNodes == len(nodes)
-    assert info.hasEmission == he
-    gn, ga, gm = svo.download(want_morton=True)
-    assert np.array_equal(gm, morton)
-    assert np.array_equal(ga, attrs)
-    got = gn.view(O.NODE_DTYPE)
-    for f in ("mask", "children", "psum"):
-        assert np.array_equal(got[f], nodes[f]), f
 
 
 def assert_same_handles(a, b):
@@ -81,28 +36,6 @@ def random_list(rng, n, res, emissive=0.1):
     attrs = rng.integers(0, 256, size=(n, 8), dtype=np.uint8)  # garbage alpha bytes included
     attrs[rng.random(n) >= emissive, 4:7] = 0
     return xyz, attrs
-
-
-class Model:
-    """the voxel set as a dict Morton -> attribute row, with the last-wins batch semantics"""
-
-    def __init__(self, O, xyz, attrs):
-        m, a, _ = O.merge_voxels(O.morton_encode_batch(xyz), attrs)
-        self.d = {int(k): a[i] for i, k in enumerate(m)}
-
-    def apply(self, O, xyz, attrs, ops):
-        keys = O.morton_encode_batch(xyz)
-        attrs = normalised(attrs)
-        for i, k in enumerate(keys):
-            if ops[i] == SET:
-                self.d[int(k)] = attrs[i]
-            else:
-                self.d.pop(int(k), None)
-
-    def arrays(self):
-        ks = np.array(sorted(self.d), np.uint64)
-        at = np.array([self.d[int(k)] for k in ks], np.uint8).reshape(-1, 8)
-        return ks, at
 
 
 def edit_batch(rng, model, n, res, emissive=0.1):

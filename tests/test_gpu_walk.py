@@ -15,29 +15,17 @@ import surface_expected as S
 import upload_shapes as U
 import walk_expected as W
 from common import hdr_bytes, probe_camera
-from test_gpu_parity import random_rays
-from test_gpu_upload_shapes import Base, bases, oracle_scene, shapes, upload  # noqa: F401 (bases is a fixture)
-from test_gpu_voxel_edit import assert_svo, has_emission, normalised, oracle_octree
+from edit_model import assert_svo, has_emission, normalised, oracle_octree
+from fixtures import mv, O  # noqa: F401 (fixtures)
+from rays import random_rays
+from upload_shapes import Base, bases, oracle_scene, shapes, upload  # noqa: F401 (bases is a fixture)
+from voxel_sets import filled
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAXF = np.float32(3.402823466e38)
 SCENES = ["single1", "single2", "single3", "empty", "random7", "random9", "bunny256", "deep14", "deep21"]
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def mv():
-    import massivevoxelraytracing_amd as m
-    m.lib()
-    assert m.device_count() >= 1
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -61,11 +49,6 @@ def shapes_of(O, scenes, scene, emb):
         res = 4 if base is None else base.res
         _shapes[key] = (base, nodes, {k: W.walk(n, res, emb) for k, n in nodes.items()})
     return _shapes[key]
-
-
-def canary(mv, shape, dtype):
-    a = np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype).reshape(shape)
-    return mv.DeviceArray.from_host(a), a
 
 
 def assert_walk(got, want_xyz, want_vi, want_attrs):
@@ -97,7 +80,7 @@ def test_walk_of_every_legal_shape(mv, O, scenes, scene, emb):
     assert svo.walk_voxels_device(n, dx, None, None) == n and np.array_equal(dx.to_host(), xyz)  # each output alone
     assert svo.walk_voxels_device(n, None, dv, None) == n and np.array_equal(dv.to_host(), vi)
     assert svo.walk_voxels_device(n + 5, None, None, da) == n and np.array_equal(da.to_host(), sc.attrs[vi])  # a larger capacity writes the count's worth
-    outs = [canary(mv, (n, 3), np.uint32), canary(mv, n, np.uint32), canary(mv, (n, 8), np.uint8)]
+    outs = [filled(mv, (n, 3), np.uint32), filled(mv, n, np.uint32), filled(mv, (n, 8), np.uint8)]
     import ctypes as C
     cnt = C.c_uint64(0)
     lib = mv.lib()

@@ -8,17 +8,12 @@ import pytest
 
 import walk_expected as W
 from alloc_sweep import bits, filled, mv, sweep_reader  # noqa: F401 (mv: the fixture)
-from test_gpu_parity import random_rays
-from test_gpu_upload_shapes import oracle_scene, shapes, upload, voxel_set
-from test_gpu_voxel_edit import assert_svo
+from edit_model import assert_svo
+from fixtures import O  # noqa: F401 (fixtures)
+from rays import random_rays
+from upload_shapes import oracle_scene, shapes, upload, voxel_set
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
 
 
 @pytest.fixture(scope="module")

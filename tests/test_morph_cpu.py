@@ -9,6 +9,7 @@ import pytest
 import fill_expected as F
 import morph_expected as M
 from surface_expected import morton
+from voxel_sets import holed_shell
 
 
 def random_set(rng, res, density):
@@ -100,16 +101,8 @@ def test_duality_extensivity_and_idempotence(res, element):
                     assert c not in index or np.array_equal(b, at[index[c]])
 
 
-def holed_shell():
-    g = np.zeros((16, 16, 16), bool)
-    g[4:11, 4:11, 4:11] = True
-    g[5:10, 5:10, 5:10] = False
-    g[7, 7, 10] = False
-    return np.argwhere(g).astype(np.uint32)
-
-
 def test_holed_shell_needs_the_cube_closing():
-    xyz = holed_shell()
+    xyz = holed_shell().astype(np.uint32)
     at = np.tile(np.array([200, 100, 50, 255, 0, 0, 0, 255], np.uint8), (len(xyz), 1))
     assert len(F.enclosed(xyz, 16)["xyz"]) == 0  # one missing voxel makes the whole interior exterior
     cube = M.morph("close", xyz, at, 16, M.CUBE, 1)[0]

@@ -12,10 +12,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("mvrt_svo_dilation_cells", "mvrt_svo_erosion_voxels", "mvrt_svo_dilate", "mvrt_svo_erode", "mvrt_svo_close", "mvrt_svo_open")
 
 
-def compile_usage(tmp_path):
-    return common.compile_usage(tmp_path, "morph_usage")
-
-
 def test_header_python_and_mirror_declare_the_interface():
     src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
     for name in CALLS:
@@ -40,6 +36,6 @@ def test_refusals_that_need_no_gpu():
 
 
 def test_cpp_mirror_morph_methods_compile_and_link(tmp_path):
-    exe, libdir = compile_usage(tmp_path)
+    exe, libdir = common.compile_usage(tmp_path, "morph_usage")
     out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")))
     assert b"usage" in out

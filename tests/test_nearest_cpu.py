@@ -8,23 +8,7 @@ import fill_expected as F
 import nearest_expected as N
 import surface_expected as S
 from common import bunny_tris
-
-
-def shell(lo, hi):
-    p = np.stack(np.meshgrid(*[np.arange(lo, hi)] * 3, indexing="ij"), -1).reshape(-1, 3)
-    return p[((p == lo) | (p == hi - 1)).any(1)]
-
-
-def colours(n, seed=1):
-    return np.random.default_rng(seed).integers(0, 256, size=(n, 8), dtype=np.uint8)
-
-
-def shapes():
-    # (gridRes 8: the band model walks the 137 000 offsets of the largest ball over the whole grid)
-    rng = np.random.default_rng(11)
-    inner = np.stack(np.meshgrid(*[np.arange(1, 7)] * 3, indexing="ij"), -1).reshape(-1, 3)
-    yield np.concatenate([shell(0, 8), inner[rng.random(len(inner)) < 0.04]]), 8  # debris in a cavity, the shell on the grid border
-    yield np.concatenate([shell(0, 8), shell(2, 6)]), 8  # nested
+from voxel_sets import cavities, colours, shell
 
 
 def assert_face_neighbours_are_at_distance_one(xyz, want, res):
@@ -35,7 +19,7 @@ def assert_face_neighbours_are_at_distance_one(xyz, want, res):
 
 
 def test_model_against_the_band_model_and_distance_one():
-    for xyz, res in shapes():
+    for xyz, res in cavities():
         at = colours(len(xyz))
         want = N.enclosed_nearest(xyz, at, res)
         band = B.distance_cells(xyz, at, res, 1024)
@@ -64,7 +48,7 @@ def test_ties_go_to_the_lowest_vindex():
 
 
 def test_the_fill_keeps_the_voxels_and_adds_the_cells_with_their_attributes():
-    xyz, res = next(shapes())
+    xyz, res = next(cavities())
     at = colours(len(xyz), 3)
     want = N.enclosed_nearest(xyz, at, res)
     fx, fa = N.filled(xyz, at, res)

@@ -15,10 +15,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("mvrt_svo_enclosed_nearest", "mvrt_svo_fill_enclosed_nearest", "mvrt_test_enclosed_nearest_stats")
 
 
-def compile_usage(tmp_path):
-    return common.compile_usage(tmp_path, "nearest_usage")
-
-
 def test_header_python_and_mirror_declare_the_interface():
     src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
     for name in CALLS:
@@ -44,7 +40,7 @@ def test_refusals_that_need_no_gpu():
 
 
 def test_cpp_mirror_nearest_methods_compile_link_and_refuse(tmp_path):
-    exe, libdir = compile_usage(tmp_path)
+    exe, libdir = common.compile_usage(tmp_path, "nearest_usage")
     r = subprocess.run([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")), capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0 and "usage" in r.stdout and "(0 host checks failed)" in r.stdout
@@ -61,7 +57,7 @@ def checksum(r):
 
 @pytest.mark.gpu
 def test_cpp_mirror_agrees_with_the_python_wrapper_and_the_model(tmp_path):
-    exe, _ = compile_usage(tmp_path)
+    exe, _ = common.compile_usage(tmp_path, "nearest_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     cube = np.array([(x, y, z) for z in range(7) for y in range(7) for x in range(7) if x % 6 == 0 or y % 6 == 0 or z % 6 == 0 or (x, y, z) == (2, 4, 3)], np.uint32)

@@ -6,11 +6,11 @@ import numpy as np
 import ball_expected as B
 import nearest_expected as N
 import query_expected as Q
-from test_nearest_cpu import colours, shapes, shell
+from voxel_sets import cavities, colours, shell
 
 
 def test_model_against_the_enclosed_cells_and_the_band():
-    for xyz, res in shapes():
+    for xyz, res in cavities():
         at = colours(len(xyz))
         for listing in (N.enclosed_nearest(xyz, at, res), B.distance_cells(xyz, at, res, 1024)):
             assert len(listing["xyz"]) > 100

@@ -16,10 +16,6 @@ CALLS = ("mvrt_svo_nearest_voxels", "mvrt_svo_nearest_between", "mvrt_svo_transf
 M64 = (1 << 64) - 1
 
 
-def compile_usage(tmp_path):
-    return common.compile_usage(tmp_path, "query_usage")
-
-
 def test_header_python_and_mirror_declare_the_interface():
     src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
     for name in CALLS:
@@ -51,7 +47,7 @@ def test_refusals_that_need_no_gpu():
 
 
 def test_cpp_mirror_query_methods_compile_link_and_refuse(tmp_path):
-    exe, libdir = compile_usage(tmp_path)
+    exe, libdir = common.compile_usage(tmp_path, "query_usage")
     r = subprocess.run([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")), capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0 and "usage" in r.stdout and "(0 host checks failed)" in r.stdout
@@ -77,7 +73,7 @@ def checksum(dist2, nearest, attribs=None):
 
 @pytest.mark.gpu
 def test_cpp_mirror_agrees_with_the_python_wrapper_and_the_model(tmp_path):
-    exe, _ = compile_usage(tmp_path)
+    exe, _ = common.compile_usage(tmp_path, "query_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     (xa, ca), (xb, cb) = shell(4, 0), shell(6, 0x010101)

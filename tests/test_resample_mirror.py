@@ -16,10 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("mvrt_svo_resample_voxels", "mvrt_svo_resample", "mvrt_cell_transform_from_world", "mvrt_test_resample_stats")
 
 
-def compile_usage(tmp_path):
-    return common.compile_usage(tmp_path, "resample_usage")
-
-
 def test_header_python_and_mirror_declare_the_interface():
     src = open(os.path.join(ROOT, "include", "mvrt.h")).read()
     for name in CALLS:
@@ -85,7 +81,7 @@ def test_the_python_record_carries_what_the_c_side_reads():
 
 
 def test_cpp_mirror_resample_methods_compile_link_and_refuse(tmp_path):
-    exe, libdir = compile_usage(tmp_path)
+    exe, libdir = common.compile_usage(tmp_path, "resample_usage")
     r = subprocess.run([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", "")), capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0 and "usage" in r.stdout and "(0 host checks failed)" in r.stdout
@@ -102,7 +98,7 @@ def checksum(r):
 
 @pytest.mark.gpu
 def test_cpp_mirror_agrees_with_the_python_wrapper(tmp_path):
-    exe, _ = compile_usage(tmp_path)
+    exe, _ = common.compile_usage(tmp_path, "resample_usage")
     out = subprocess.check_output([str(exe), "run"], timeout=120).decode()
     print(out)
     ell = np.array([(x, y, z) for z in range(2, 5) for y in range(1, 12) for x in range(1, 14) if y < 4 or x < 3], np.uint32)

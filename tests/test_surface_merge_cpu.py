@@ -10,9 +10,9 @@ import common
 import massivevoxelraytracing_amd as mv
 import merge_expected as M
 import surface_expected as S
+from voxel_sets import DPS, LOWER, full
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOWER, DPS = np.array([-0.3, 0.7, 1.1], np.float32), np.float32(0.013)
 
 
 def brute_force(xyz, attrs, res, any_attribute):
@@ -78,10 +78,6 @@ def as_tuples(xyz, m):
 
 
 L_SHAPE = [(0, 0, 0), (1, 0, 0), (2, 0, 0), (0, 0, 1), (1, 0, 1)]
-
-
-def full(res):
-    return np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing="ij"), -1).reshape(-1, 3)
 
 
 @pytest.mark.parametrize("any_attribute", [False, True])

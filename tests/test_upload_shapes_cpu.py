@@ -12,22 +12,12 @@ import pytest
 import deep_scenes as D
 import upload_shapes as U
 from common import bunny_tris, position_colors
-from test_gpu_parity import random_rays
+from fixtures import bunny256, O  # noqa: F401 (fixtures)
+from rays import random_rays
 
 import massivevoxelraytracing_amd as mv
 
 check = mv.IntersectorOctreeGPU.check_upload
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
-
-
-@pytest.fixture(scope="module")
-def bunny256(O):
-    return O.build_scene_from_triangles(bunny_tris(), 256)
 
 
 def verdict(msg):

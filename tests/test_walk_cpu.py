@@ -11,18 +11,13 @@ import common
 import deep_scenes as D
 import upload_shapes as U
 import walk_expected as W
-from test_gpu_upload_shapes import oracle_scene, shapes, voxel_set
+from fixtures import O  # noqa: F401 (fixtures)
+from upload_shapes import oracle_scene, shapes, voxel_set
 
 import massivevoxelraytracing_amd as mv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAXF = np.float32(3.402823466e38)
-
-
-@pytest.fixture(scope="module")
-def O():
-    from oracle import oracle
-    return oracle
 
 
 @pytest.fixture(scope="module")

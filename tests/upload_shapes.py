@@ -7,8 +7,16 @@ Everything works on oracle.NODE_DTYPE arrays (the reference's 68-byte nodes, roo
 - `voxel_paths`: the root->voxel path (= Morton code) of every voxel, the hints of the GPU tests;
 - `MUTATIONS`: single changes that break one rule each.
 
-An octree here is the tuple (nodes, numberOfVoxels, gridRes, embedded)."""
+An octree here is the tuple (nodes, numberOfVoxels, gridRes, embedded).
+
+The last section is what the tests of uploaded octrees build on: the voxel sets (`Base`, `voxel_set`, the `bases` fixture), every legal shape of one of them
+(`shapes`), its oracle scene and its upload."""
 import numpy as np
+import pytest
+
+import deep_scenes as D
+from common import bunny_tris, position_colors
+from massivevoxelraytracing_amd import IntersectorOctreeGPU
 
 LEAF = 0xFFFFFFFF
 IDX = 0xFFFFFF
@@ -504,3 +512,76 @@ def small_octree(O, rng, levels, dag, embedded, n_voxels=None):
         codes = np.unique(rng.integers(0, cells, n, dtype=np.uint64))
     nodes = O.build_octree(codes, res, dag=dag, embed=embedded)
     return nodes, len(codes), res, embedded
+
+
+# ---- voxel sets, their shapes, scenes and uploads ------------------------------------------------------------------------------------------------------------------
+class Base:
+    """a voxel set: sorted Morton codes, merged attributes, grid"""
+
+    def __init__(self, name, morton, attrs, res, origin=(0.0, 0.0, 0.0), dps=None, he=None):
+        self.name, self.morton, self.attrs, self.res = name, np.asarray(morton, np.uint64), np.asarray(attrs, np.uint8).reshape(-1, 8), res
+        self.origin = np.asarray(origin, np.float32)
+        self.dps = np.float32(1.0 / res) if dps is None else np.float32(dps)
+        self.he = int((self.attrs[:, 4:7] != 0).any()) if he is None else he
+
+
+def voxel_set(name, levels, n_cluster, n_scattered, seed):
+    rng = np.random.default_rng(seed)
+    res = 1 << levels
+    box = max(2, res // 3)
+    pts = np.concatenate([rng.integers(0, box, (n_cluster, 3)) + res // 4, rng.integers(0, res, (n_scattered, 3))])
+    m = np.unique(D.morton(pts))
+    attrs = rng.integers(0, 256, (len(m), 8), dtype=np.uint8)
+    attrs[rng.random(len(m)) >= 0.1, 4:7] = 0
+    attrs[:, 3] = 255
+    return Base(name, m, attrs, res)
+
+
+@pytest.fixture(scope="module")
+def bases(O):
+    tris = bunny_tris()
+    cols, emis = position_colors(tris)
+    b = O.build_scene_from_triangles(tris, 256, cols, emis)
+    out = {"bunny256": Base("bunny256", b.morton, b.attrs, 256, b.origin, b.dps, b.has_emission),
+           "random7": voxel_set("random7", 7, 20_000, 2_000, 7),
+           "random9": voxel_set("random9", 9, 30_000, 3_000, 9)}
+    for L in (1, 2, 3):
+        rng = np.random.default_rng(100 + L)
+        out["single%d" % L] = Base("single%d" % L, [int(rng.integers(0, 8 ** L))], [[200, 100, 50, 255, 0, 0, 0, 0]], 1 << L)
+    s = D.DeepScene(14)
+    sc = D.oracle_scene(O, s)
+    out["deep14"] = Base("deep14", sc.morton, sc.attrs, s.res, s.origin, s.dps, sc.has_emission)
+    return out
+
+
+def shapes(O, base, emb, seed):
+    """{shape: (nodes, keeps_builder_answers)}: every legal generator on the builder's octree of `base` (the empty octree: itself only)"""
+    if base is None:
+        empty = np.zeros(1, O.NODE_DTYPE)
+        empty["children"] = LEAF
+        return {"empty": (empty, True)}
+    rng = np.random.default_rng(seed)
+    nodes = O.build_octree(base.morton, base.res, dag=True, embed=emb)
+    nv, res = len(base.morton), base.res
+    out = {"builder": (nodes, True), "permute": (permute(nodes, emb, rng), True), "unreachable": (add_unreachable(nodes, emb, rng, 50, 50), True),
+           "unshare": (unshare(nodes, emb), True), "empty_inner": (add_empty_inner(nodes, res, emb, rng, 64), False),
+           "psum_zero": (psum_zero(nodes), False), "psum_random": (psum_random(permute(nodes, emb, rng), nv, res, rng), False)}
+    if nv >= 2:
+        out["psum_one_off"] = (psum_one_off(nodes, emb)[0], False)
+    out["all"] = (permute(add_unreachable(add_empty_inner(unshare(nodes, emb), res, emb, rng), emb, rng), emb, rng), False)
+    for k, (n, _) in out.items():
+        set_masks_zero_padding(n)
+        assert IntersectorOctreeGPU.check_upload(n, nv, res, emb) is None, k
+    return out
+
+
+def oracle_scene(O, base, nodes, emb):
+    if base is None:
+        return O.Scene(nodes, np.zeros((0, 8), np.uint8), (0.0, 0.0, 0.0), 0.25, 4, 0, embedded=emb)
+    return O.Scene(nodes, base.attrs, base.origin, base.dps, base.res, base.he, embedded=emb)
+
+
+def upload(mv, sc, emb, svo=None):
+    svo = mv.IntersectorOctreeGPU() if svo is None else svo
+    svo.upload(sc.nodes, sc.attrs, sc.origin, sc.dps, sc.grid_res, sc.has_emission, embeddedMask=emb)
+    return svo
