@@ -532,9 +532,14 @@ struct PtIO
 		const int kind = kindOf( r, &i );
 		*ro = mk3( in.rox[i], in.roy[i], in.roz[i] );
 		if( useHint ) *hint = in.org[i]; // every ray of a path starts on the voxel the path hit last
-		if( kind == 0 ) *rd = mk3( in.rdx[i], in.rdy[i], in.rdz[i] );
-		else if( kind == 1 ) *rd = mk3( buf.sx[i], buf.sy[i], buf.sz[i] );
-		else *rd = mk3( buf.ex[i], buf.ey[i], buf.ez[i] );
+		// the direction arrays of the three kinds: all nine pointers are fetched (one batch of scalar loads from the table) and the lane picks its three with
+		// selects.  As an if / else chain over the kinds every arm fetched its own pointers behind a divergent branch and waited for them there, and the third
+		// pointer came through a per-lane vector load that the direction load then had to wait for -- a second memory round trip in every refill
+		const float *x0 = in.rdx, *y0 = in.rdy, *z0 = in.rdz, *x1 = buf.sx, *y1 = buf.sy, *z1 = buf.sz, *x2 = buf.ex, *y2 = buf.ey, *z2 = buf.ez;
+		const float* const px = kind == 0 ? x0 : ( kind == 1 ? x1 : x2 );
+		const float* const py = kind == 0 ? y0 : ( kind == 1 ? y1 : y2 );
+		const float* const pz = kind == 0 ? z0 : ( kind == 1 ? z1 : z2 );
+		*rd = mk3( px[i], py[i], pz[i] );
 		return kind == 1;
 	}
 	MVRT_DI void store( uint32_t r, const StreamHit& h, bool )

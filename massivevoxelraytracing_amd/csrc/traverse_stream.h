@@ -96,6 +96,8 @@
 #ifndef MVRT_HINT_MAX
 #define MVRT_HINT_MAX 7u // levels a hint carries = deepest prefix table (8^7 entries of 4 bytes); at most the ring's 8 slots
 #endif
+// replayHint unrolls MVRT_HINT_MAX levels into ring slots 0 .. MVRT_HINT_MAX - 1 without an eviction test, and aligns a hint in 3 * MVRT_HINT_MAX <= 21 bits
+static_assert( MVRT_HINT_MAX <= MVRT_RING_EMBED && MVRT_HINT_MAX <= 7u, "a hint's levels must fit the embedded flavour's ring and 21 bits" );
 MVRT_HDI uint32_t hintLevelsOf( uint32_t levels ) { return levels == 0u ? 0u : ( levels - 1u < MVRT_HINT_MAX ? levels - 1u : MVRT_HINT_MAX ); }
 MVRT_HDI uint32_t hintTabLevelsOf( uint32_t levels ) { return hintLevelsOf( levels ); }
 MVRT_HDI uint32_t prefixTabOffset( uint32_t l ) { return 0x49249249u & ( ( 1u << ( 3u * l ) ) - 1u ); } // (8^l - 1) / 7: entries of the tables of fewer levels
@@ -479,9 +481,13 @@ MVRT_DI uint32_t setupRay( const TraceCore& s, f3 ro, f3 rd, float* t0x, float* 
 		iz = -iz;
 		ro.z = s.loz + s.hiz - ro.z;
 	}
-	ix = smin( ix, MVRT_MAXF / smax( smax( sabs( s.lox - ro.x ), sabs( s.hix - ro.x ) ), 1.0f ) );
-	iy = smin( iy, MVRT_MAXF / smax( smax( sabs( s.loy - ro.y ), sabs( s.hiy - ro.y ) ), 1.0f ) );
-	iz = smin( iz, MVRT_MAXF / smax( smax( sabs( s.loz - ro.z ), sabs( s.hiz - ro.z ) ), 1.0f ) );
+	// |x| through the sign bit (a source modifier, no instruction) for the reference's compare-select sabs( x ) = x >= 0 ? x : -x.  The two differ for x = -0
+	// (sabs keeps -0) and for a NaN (sabs flips its sign, the bit clears it).  Here that shows nowhere: every smax below picks by a compare, which takes -0 for
+	// +0 and is false for a NaN of either sign, so the same operand is picked; a zero of either sign then loses to 1.0f, and a NaN that survives makes
+	// MAX_FLOAT / NaN = NaN, which smin drops (NaN < ix is false) -- the clamped reciprocal has the same bits
+	ix = smin( ix, MVRT_MAXF / smax( smax( __builtin_fabsf( s.lox - ro.x ), __builtin_fabsf( s.hix - ro.x ) ), 1.0f ) );
+	iy = smin( iy, MVRT_MAXF / smax( smax( __builtin_fabsf( s.loy - ro.y ), __builtin_fabsf( s.hiy - ro.y ) ), 1.0f ) );
+	iz = smin( iz, MVRT_MAXF / smax( smax( __builtin_fabsf( s.loz - ro.z ), __builtin_fabsf( s.hiz - ro.z ) ), 1.0f ) );
 	*t0x = ( s.lox - ro.x ) * ix, *t0y = ( s.loy - ro.y ) * iy, *t0z = ( s.loz - ro.z ) * iz;
 	*tx1 = ( s.hix - ro.x ) * ix;
 	*ty1 = ( s.hiy - ro.y ) * iy;
@@ -646,7 +652,8 @@ MVRT_DI VisitStep visitCandidates( uint32_t level, float tx1, float ty1, float t
 // Straight-line code: the level counter is a compile-time constant (the loop is unrolled, at most MVRT_HINT_MAX = 7
 // levels = ring slots: a refilled lane's ring is empty, so nothing is ever evicted here), the node references of the
 // hint's ancestors are ONE batch of independent table gathers issued up front (no pointer chase), lanes that have left
-// the hint's path just stop changing their state.
+// the hint's path just stop changing their state.  No divergent region inside the walk: the lanes on the path are one
+// lane mask, and a level is selects on it (profiles/r15_refill_diet.txt).
 struct HintStart // where the fast loop starts: exit times, node, the stacked ancestors, the levels skipped and the path down to there
 {
 	float tx1, ty1, tz1;
@@ -655,67 +662,82 @@ struct HintStart // where the fast loop starts: exit times, node, the stacked an
 };
 MVRT_DI HintStart replayHint( const TraceCore& s, LdsU4* myRing, uint32_t hint, uint32_t node, uint32_t vMask, float dtx, float dty, float dtz, float tx1, float ty1, float tz1 )
 {
-	uint32_t pending = 0;
 	const uint32_t P = hintLevelsOf( s.levelsM1 + 1u );
 	const char* const tab = (const char*)s.kids + ( ( s.rootIndex + 1u ) << 5 ); // the prefix tables lie behind the children array (32 B per node; root = last node)
+	// the hint aligned to MVRT_HINT_MAX levels (a hint is < 8^P): level L's child sits at the compile-time bit 3 * ( MVRT_HINT_MAX - 1 - L ) and the prefix of L
+	// levels is a shift by a constant, whatever P is -- no per-level shift count has to live in a scalar register across the walk
+	const uint32_t ha = hint << ( 3u * ( MVRT_HINT_MAX - P ) );
+	const uint32_t hm = ha ^ __umul24( vMask, 0x249249u ); // the same children in the mirrored space, where the octant bits are computed
+	// (the tables of more than P levels do not exist: their gathers are clamped onto the last entry that does -- one v_min per level instead of a wave-uniform
+	// branch around each load; the levels that would use them are never replayed)
+	const uint32_t lastEntry = prefixTabOffset( P + 1u ) - 1u;
 	uint32_t anc[MVRT_HINT_MAX + 1];
 #pragma unroll
 	for( uint32_t L = 1; L <= MVRT_HINT_MAX; L++ )
-		anc[L] = L <= P ? *(const uint32_t*)( tab + ( ( prefixTabOffset( L ) + ( hint >> ( 3u * ( P - L ) ) ) ) << 2 ) ) : 0u;
-	uint32_t k = 0u;
-	bool on = true;
+	{
+		const uint32_t at = prefixTabOffset( L ) + ( ha >> ( 3u * ( MVRT_HINT_MAX - L ) ) );
+		anc[L] = *(const uint32_t*)( tab + ( ( at < lastEntry ? at : lastEntry ) << 2 ) );
+	}
 	anc[0] = node;
+	// The lanes still on the hint's path only shrink, level after level: they are ONE lane mask (onM), and every state change of a level is a select on it
+	// (or on a mask derived from it on the scalar unit) -- no divergent region per level, no exec juggling, one wave-uniform branch per level (L < P).
+	// The levels a lane stayed on the path and the levels it stacked are shifted in from the right, one add-with-carry each (level L at bit P - 1 - L).
+	// The ring entry of level L is written by EVERY lane that replays, stacked or not, on the path or off it:
+	// a ring slot whose `pending` bit is clear is never read (the pop reads the slot of the highest pending bit, an eviction the slots of inLds, and
+	// inLds = pending after the replay), and a refilled lane's ring is empty, so the write overwrites nothing that is alive.
+	lmask onM = ~0ull;
+	uint32_t onBits = 0u, stacked = 0u;
 #pragma unroll
 	for( uint32_t L = 0; L < MVRT_HINT_MAX; L++ )
 	{
-		if( L < P && on ) // (L < P is wave-uniform; lanes that have left the hint's path drop out of the rest of the nest)
-		{
-			const float scale = mvrt_u2f( ( 127u - L ) << 23 );
-			const v2f t1yz = { ty1, tz1 };
-			const v2f dtyz = { dty, dtz };
-			const float tx0 = tx1 - dtx * scale; // :317-320, the step's own operations
-			const v2f t0yz = t1yz - dtyz * scale;
-			const float S0 = fmaxf( fmaxf( fmaxf( tx0, t0yz.x ), t0yz.y ), 0.0f );
-			const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
-			const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
-			const bool bx = txM < S0, by = tMyz.x < S0, bz = tMyz.y < S0;
-			const uint32_t b = ( bx ? 1u : 0u ) | ( by ? 2u : 0u ) | ( bz ? 4u : 0u );
-			on = ( b ^ vMask ) == ( ( hint >> ( 3u * ( P - 1u - L ) ) ) & 7u ); // the origin's octant is the hint's child: it exists, the step enters it
-			if( on )
-			{
-				const bool later = ( (int)!bx & (int)( txM <= minF( ty1, tz1 ) ) ) | ( (int)!by & (int)( tMyz.x < tx1 ) & (int)( tMyz.x <= tz1 ) ) | ( (int)!bz & (int)( tMyz.y < minF( tx1, ty1 ) ) );
-				if( later ) // stack the ancestor (:377-380); the octant it is left through is the hint's child at this level, which `path` holds as for any entry
-				{
-					// (the node reference -- word 0 -- is filled in after the walk, when the table gathers have landed: their
-					// latency hides behind this arithmetic instead of stalling the wave at the first level)
-					LdsU32* const w = (LdsU32*)( myRing + L * 64 );
-					w[1] = mvrt_f2u( tx1 );
-					w[2] = mvrt_f2u( ty1 );
-					w[3] = mvrt_f2u( tz1 );
-					pending |= 1u << L;
-				}
-				tx1 = bx ? tx1 : txM; // :382-386
-				ty1 = by ? ty1 : tMyz.x;
-				tz1 = bz ? tz1 : tMyz.y;
-				k = L + 1u;
-			}
-		}
+		if( L >= P ) break; // (wave-uniform)
+		const float scale = mvrt_u2f( ( 127u - L ) << 23 );
+		const v2f t1yz = { ty1, tz1 };
+		const v2f dtyz = { dty, dtz };
+		const float tx0 = tx1 - dtx * scale; // :317-320, the step's own operations
+		const v2f t0yz = t1yz - dtyz * scale;
+		const float S0 = fmaxf( fmaxf( fmaxf( tx0, t0yz.x ), t0yz.y ), 0.0f );
+		const float txM = 0.5f * ( tx0 + tx1 ); // :338-340
+		const v2f tMyz = ( t0yz + t1yz ) * 0.5f;
+		const float tyM = tMyz.x, tzM = tMyz.y;
+		const lmask X = __ballot( txM < S0 ), Y = __ballot( tyM < S0 ), Z = __ballot( tzM < S0 );
+		float mXY, mYZ; // (one asm statement, as in the step: no wait state between the two)
+		asm( "v_min_f32 %0, %2, %3\n\tv_min_f32 %1, %3, %4" : "=&v"( mXY ), "=&v"( mYZ ) : "v"( tx1 ), "v"( ty1 ), "v"( tz1 ) );
+		const lmask fX = ~X & __ballot( txM <= mYZ );
+		const lmask fY = ~Y & __ballot( tyM < tx1 ) & __ballot( tyM <= tz1 );
+		const lmask fZ = ~Z & __ballot( tzM < mXY );
+		const uint32_t b = MVRT_SHIFT_IN( MVRT_SHIFT_IN( MVRT_SELKK( Z, 1, 0 ), Y ), X ); // the origin's octant, mirrored space (the step's i0)
+		onM &= __ballot( b == ( ( hm >> ( 3u * ( MVRT_HINT_MAX - 1u - L ) ) ) & 7u ) ); // it is the hint's child: it exists, the step enters it
+		// stack the ancestor (:377-380) where a later candidate exists; the octant it is left through is the hint's child at this level, which `path` holds as for any entry.
+		// The three exit times go into the slot here, without a test, the `stacked` bit alone says whether they count.  (Dword stores, volatile: merged into one
+		// 16-byte store the entry wants four consecutive registers, and the visit loop then pays register moves around its own push and pop)
+		volatile LdsU32* const w = (LdsU32*)( myRing + L * 64 );
+		w[1] = mvrt_f2u( tx1 ), w[2] = mvrt_f2u( ty1 ), w[3] = mvrt_f2u( tz1 );
+		const lmask laterM = onM & ( fX | fY | fZ );
+		stacked = MVRT_SHIFT_IN( stacked, laterM );
+		const lmask keepX = X | ~onM, keepY = Y | ~onM, keepZ = Z | ~onM; // :382-386 for the lanes on the path; the others keep their state
+		tx1 = LANE( keepX ) ? tx1 : txM;
+		ty1 = LANE( keepY ) ? ty1 : tyM;
+		tz1 = LANE( keepZ ) ? tz1 : tzM;
+		onBits = MVRT_SHIFT_IN( onBits, onM );
 	}
+	// The node words last, when the table gathers have landed: their latency hides behind the walk's arithmetic instead of stalling the wave at its first
+	// level.  Straight-line for all MVRT_HINT_MAX levels: beyond P the on-bit is clear, the gather was clamped, and the ring slot is as dead as any other
+	const uint32_t onA = onBits << ( MVRT_HINT_MAX - P ); // level L at bit MVRT_HINT_MAX - 1 - L
 #pragma unroll
 	for( uint32_t L = 0; L < MVRT_HINT_MAX; L++ )
 	{
-		if( L < P )
-		{
-			if( pending & ( 1u << L ) ) *(LdsU32*)( myRing + L * 64 ) = anc[L];
-			node = k == L + 1u ? anc[L + 1] : node;
-		}
+		*(volatile LdsU32*)( myRing + L * 64 ) = anc[L];
+		uint32_t m; // (0 / -1 from the level's on-bit, then a bit select: one asm statement, as in halveBox)
+		asm( "v_bfe_i32 %1, %2, %4, 1\n\tv_bfi_b32 %0, %1, %3, %0" : "+v"( node ), "=&v"( m ) : "v"( onA ), "v"( anc[L + 1] ), "n"( MVRT_HINT_MAX - 1u - L ) );
 	}
+	const uint32_t k = (uint32_t)__popc( onBits );
 	HintStart hs;
 	hs.tx1 = tx1, hs.ty1 = ty1, hs.tz1 = tz1;
 	hs.node = node;
-	hs.pending = pending;
+	hs.pending = __brev( stacked ) >> ( ( 32u - P ) & 31u ); // P levels were shifted in (none for P = 0: stacked is 0)
 	hs.levels = k;
-	hs.path = k ? (uint64_t)( hint >> ( 3u * ( P - k ) ) ) : 0ull;
+	hs.path = (uint64_t)( ha >> ( 3u * ( MVRT_HINT_MAX - k ) ) ); // the first k children; nothing for k = 0 (a hint is < 8^MVRT_HINT_MAX)
 	return hs;
 }
 
@@ -979,8 +1001,10 @@ MVRT_DI void traceStream( const TraceCore& s, IO& io, uint64_t total64, unsigned
 						}
 						else if( ( ( mvrt_f2u( tx1 - t0x ) & 0x7F800000u ) == 0x7F800000u ) || ( ( mvrt_f2u( ty1 - t0y ) & 0x7F800000u ) == 0x7F800000u ) ||
 								 ( ( mvrt_f2u( tz1 - t0z ) & 0x7F800000u ) == 0x7F800000u ) ||
-								 !( smax( max3f( sabs( tx1 ), sabs( ty1 ), sabs( tz1 ) ), max3f( sabs( t0x ), sabs( t0y ), sabs( t0z ) ) ) < 1.7014118346046923e38f ) )
+								 !( smax( max3f( __builtin_fabsf( tx1 ), __builtin_fabsf( ty1 ), __builtin_fabsf( tz1 ) ), max3f( __builtin_fabsf( t0x ), __builtin_fabsf( t0y ), __builtin_fabsf( t0z ) ) ) < 1.7014118346046923e38f ) )
 						{
+							// (|x| through the sign bit instead of sabs, as in setupRay: the compare-selects pick the same operands, the maximum differs at most in the sign of a
+							// zero or of a NaN, and "< 2^127" reads neither)
 							// irregular ray (inf / NaN slab delta): exact reference emulation, see traceIrregular.  Also a ray with a slab time of 2^127 or more (every
 							// direction component zero or denormal: 1 / rd clamped to MAX_FLOAT / extent): its deltas are finite, but the reference's mid-plane
 							// 0.5f * ( t0 + t1 ) overflows to +inf, the walk then goes down the first children and reports a HIT at t = +inf (voxCommon.hpp:338-340,
