@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/combine_bench.py [--scenes dragon,tunnel] [--ops listing,inplace] [--reps 5] [--warmup 1] [--host-reps 2] [--shift 8] [--step-timeout 420]
+"""usage: tools/combine_bench.py [--scenes dragon[:grid],tunnel[:grid]] [--ops listing,inplace] [--reps 5] [--warmup 1] [--host-reps 2] [--shift 8] [--step-timeout 420]
                                  [--out profiles/combine_bench.json]
 
 Cost of the two-set calls on the procedural stand-ins (dragon 2048^3, tunnel 4096^3), b being a second build of the same model, per scene:
@@ -13,39 +13,18 @@ Cost of the two-set calls on the procedural stand-ins (dragon 2048^3, tunnel 409
 The octree is rebuilt from its voxel list before every timed in-place call, outside the clock.  Median of --reps calls after --warmup calls (host_route:
 --host-reps calls, no warm-up: seconds each); host clock around each call (every call blocks).  A call the library refuses is reported with its message, never
 guessed.  MVRT_LIB in the environment selects another build of the library (an A/B of two kernels); a kernel trace of one step is taken by running
-`--step scene:op` under the profiler, in a run of its own.
+`--step scene:grid:op` under the profiler, in a run of its own.
 Every step runs in a child process of its own under --step-timeout seconds; a step that fails, is killed or runs out of time ends the run: nothing more is
 started on the GPU behind it."""
 import argparse
-import json
 import os
-import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchkit as bk
 
-GRID = {"dragon": 2048, "tunnel": 4096}
 OPS = {"union": 0, "intersection": 1, "difference": 2, "xor": 3}
-
-
-def built(mv, name, res):
-    from massivevoxelraytracing_amd import scenes
-    verts, cols, emis = scenes.SCENES[name](1.0)
-    origin, dps = scenes.bounding_grid(verts, res)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build(verts, cols, emis, None, origin, dps, res)
-    return svo, origin, dps
-
-
-def snapshot(mv, svo):
-    n = svo.info().numberOfVoxels
-    xyz, attrs = mv.DeviceArray((n, 3), np.uint32), mv.DeviceArray((n, 8), np.uint8)
-    mv._check(mv.lib().mvrt_svo_read_voxels(svo._h, xyz.ptr, attrs.ptr, None))
-    return xyz, attrs
 
 
 def keys_of(xyz, res):
@@ -75,94 +54,55 @@ def step(args):
     """one child process: prints one JSON row per measurement"""
     import massivevoxelraytracing_amd as mv
     mv.set_device(0)
-    name, what = args.step.split(":")
-    res = GRID[name]
-    svo, origin, dps = built(mv, name, res)
-    b, _, _ = built(mv, name, res)
+    name, res, what = args.step.split(":")
+    res = int(res)
+    svo, origin, dps = bk.built(mv, name, res)
+    b, _, _ = bk.built(mv, name, res)
     base = dict(scene=name, grid=res, voxels=svo.info().numberOfVoxels, lib=os.path.basename(mv.LIB_PATH))
 
-    def emit(**kw):
-        print(json.dumps(dict(base, **kw)), flush=True)
-
-    def timed(label, fn, before=None, reps=args.reps, warmup=args.warmup, **kw):
-        ts, result = [], None
-        for i in range(warmup + reps):
-            if before:
-                before()
-            mv.synchronize()
-            t0 = time.perf_counter()
-            try:
-                result = fn()
-            except mv.MvrtError as err:
-                emit(op=label, refused=str(err), **kw)
-                return None
-            if i >= warmup:
-                ts.append((time.perf_counter() - t0) * 1e3)
-        emit(op=label, ms=float(np.median(ts)), all_ms=ts, result=result, **kw)
-        return result
+    def measure(label, fn, before=None, reps=args.reps, warmup=args.warmup, **kw):
+        return bk.timed_or_refused(mv, base, label, fn, reps, warmup, before, **kw)
 
     shifted = (args.shift, 0, 0)
     if what == "listing":
         for oname, op in OPS.items():
             for offset in ((0, 0, 0), shifted):
-                got = timed("combine_count", lambda: list(svo.combine_voxels_device(b, op, offset)), set_op=oname, offset=list(offset))
+                got = measure("combine_count", lambda: list(svo.combine_voxels_device(b, op, offset)), set_op=oname, offset=list(offset))
                 if got and got[0]:
                     n = got[0]
                     xyz, at, src = mv.DeviceArray((n, 3), np.uint32), mv.DeviceArray((n, 8), np.uint8), mv.DeviceArray(n, np.uint8)
-                    timed("combine_list", lambda: list(svo.combine_voxels_device(b, op, offset, 0, n, xyz, at, src)), set_op=oname, offset=list(offset))
+                    measure("combine_list", lambda: list(svo.combine_voxels_device(b, op, offset, 0, n, xyz, at, src)), set_op=oname, offset=list(offset))
                     del xyz, at, src
     elif what == "inplace":
-        original = snapshot(mv, svo)
+        original = bk.snapshot(mv, svo)
 
         def restore():
             svo.build_voxels(original[0], original[1], origin=origin, dps=dps, gridRes=res)
 
         for oname, op in OPS.items():
-            timed("combine", lambda: list(svo.combine(b, op, shifted)), before=restore, set_op=oname, offset=list(shifted))
-            timed("host_route", lambda: host_route(svo, b, op, shifted, res), before=restore, reps=args.host_reps, warmup=0, set_op=oname, offset=list(shifted))
+            measure("combine", lambda: list(svo.combine(b, op, shifted)), before=restore, set_op=oname, offset=list(shifted))
+            measure("host_route", lambda: host_route(svo, b, op, shifted, res), before=restore, reps=args.host_reps, warmup=0, set_op=oname, offset=list(shifted))
+
+
+def line(r):
+    what = "%9.2f ms" % r["ms"] if "ms" in r else r.get("refused") or r.get("failed")
+    return "%-7s %5s %-12s %-14s %-10s %10s voxels  %s  -> %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("set_op", ""), r.get("op", ""),
+                                                                 r.get("offset", ""), r.get("voxels", ""), what, r.get("result", ""))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="dragon,tunnel")
+    ap.add_argument("--scenes", type=bk.parse_scenes, default="dragon,tunnel")
     ap.add_argument("--ops", default="listing,inplace")
     ap.add_argument("--shift", type=int, default=8)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-reps", type=int, default=2)
-    ap.add_argument("--step-timeout", type=int, default=420)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
+    bk.add_step_args(ap, reps=5, warmup=1, step_timeout=420)
     args = ap.parse_args()
     if args.step:
         return step(args)
-    steps = [":".join((s, op)) for s in args.scenes.split(",") for op in args.ops.split(",")]
-    rows, rc = [], 0
-    for s in steps:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", s, "--reps", str(args.reps), "--warmup", str(args.warmup), "--host-reps", str(args.host_reps), "--shift",
-               str(args.shift)]
-        print("step", s, flush=True)
-        try:
-            out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=args.step_timeout)
-        except subprocess.TimeoutExpired:
-            rows.append(dict(step=s, failed="no result within %d s" % args.step_timeout))
-            rc = 1
-            break
-        for line in out.stdout.decode().splitlines():
-            if line.startswith("{"):
-                rows.append(json.loads(line))
-                print(line, flush=True)
-        if out.returncode != 0:
-            rows.append(dict(step=s, failed="exit status %d" % out.returncode))
-            rc = 1
-            break  # nothing more is started on the GPU behind a step that failed
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(rows, f, indent=1)
-    for r in rows:
-        what = "%9.2f ms" % r["ms"] if "ms" in r else r.get("refused") or r.get("failed")
-        print("%-7s %5s %-12s %-14s %-10s %10s voxels  %s  -> %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("set_op", ""), r.get("op", ""),
-                                                                   r.get("offset", ""), r.get("voxels", ""), what, r.get("result", "")), file=sys.stderr)
+    steps = ["%s:%d:%s" % (name, res, op) for name, res in args.scenes for op in args.ops.split(",")]
+    rows, rc = bk.run_steps(__file__, steps, lambda s: bk.flags(args, "reps", "warmup", "host_reps", "shift"), args.step_timeout, args.out)
+    bk.print_table(rows, line)
     return rc
 
 

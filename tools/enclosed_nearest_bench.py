@@ -14,46 +14,11 @@ longest gap per axis, deepest d2.  A call the library refuses, or whose scratch 
 Every step runs in a child process of its own under `timeout -k 10 --step-timeout`; a step that fails, is killed or runs out of time ends the run: nothing more
 is started on the GPU behind it.  A child sizes no thread pool of its own."""
 import argparse
-import json
-import os
-import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def timed(mv, fn, reps, warmup, before=None):
-    ts = []
-    for i in range(warmup + reps):
-        if before:
-            before()
-        mv.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts)), ts
-
-
-def built(mv, name, res):
-    from massivevoxelraytracing_amd import scenes
-    verts, cols, emis = scenes.SCENES[name](1.0)
-    origin, dps = scenes.bounding_grid(verts, res)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build(verts, cols, emis, None, origin, dps, res)
-    return svo, origin, dps
-
-
-def peak_of(mv, fn):
-    """the most bytes the library held during fn beyond what it held before"""
-    held = mv.allocation_state()[1]
-    mv.peak_bytes(reset=True)
-    fn()
-    return mv.peak_bytes() - held
+import benchkit as bk
 
 
 def step(args):
@@ -62,89 +27,66 @@ def step(args):
     mv.set_device(0)
     name, res, op = args.step.split(":")
     res = int(res)
-    svo, origin, dps = built(mv, name, res)
+    svo, origin, dps = bk.built(mv, name, res)
     n_vox = svo.info().numberOfVoxels
     n_cells, n_regions = svo.enclosed_cells_device()
     base = dict(scene=name, grid=res, voxels=n_vox, nCells=n_cells, nRegions=n_regions)
 
-    def emit(**kw):
-        print(json.dumps(dict(kw, **base)), flush=True)
-
     def measure(label, fn, before=None, stats=False):
         try:
-            peak = peak_of(mv, (lambda: (before(), fn())) if before else fn)  # (with `before` the peak covers the rebuild too: reported as such)
-            ms, ts = timed(mv, fn, args.reps, args.warmup, before)
+            peak = bk.peak_of(mv, (lambda: (before(), fn())) if before else fn)  # (with `before` the peak covers the rebuild too: reported as such)
+            ms, ts = bk.timed(mv, fn, args.reps, args.warmup, before=before)
         except mv.MvrtError as e:
-            emit(op=label, refused=str(e), peak_bytes=mv.peak_bytes() - mv.allocation_state()[1])
+            bk.emit(base, op=label, refused=str(e), peak_bytes=mv.peak_bytes() - mv.allocation_state()[1])
             return None
-        emit(op=label, ms=ms, all_ms=ts, peak_bytes=peak, peak_includes_rebuild=bool(before), **(mv.enclosed_nearest_stats() if stats else {}))
+        bk.emit(base, op=label, ms=ms, all_ms=ts, peak_bytes=peak, peak_includes_rebuild=bool(before), **(mv.enclosed_nearest_stats() if stats else {}))
         return ms
 
     if op == "size":
         a = measure("nearest_size", svo.enclosed_nearest_device)
         b = measure("cells_size", svo.enclosed_cells_device)
-        emit(op="size_ratio", ratio=a / b)
+        bk.emit(base, op="size_ratio", ratio=a / b)
     elif op == "list":
         if n_cells == 0 or n_cells >= 1 << 32:
-            emit(op="nearest_list", skipped="%d cells" % n_cells)
+            bk.emit(base, op="nearest_list", skipped="%d cells" % n_cells)
             return
         xyz, region = mv.DeviceArray((n_cells, 3), np.uint32), mv.DeviceArray(n_cells, np.uint32)
         d2, near, at = mv.DeviceArray(n_cells, np.uint32), mv.DeviceArray(n_cells, np.uint32), mv.DeviceArray((n_cells, 8), np.uint8)
         a = measure("nearest_list", lambda: svo.enclosed_nearest_device(n_cells, xyz, region, d2, near, at), stats=True)
         b = measure("cells_list", lambda: svo.enclosed_cells_device(n_cells, xyz, region))
         if a and b:
-            emit(op="list_ratio", ratio=a / b, cells_per_s=n_cells / (a * 1e-3))
+            bk.emit(base, op="list_ratio", ratio=a / b, cells_per_s=n_cells / (a * 1e-3))
     elif op == "fill":
         if n_cells == 0 or n_cells + n_vox >= (1 << 32) - 1:
-            emit(op="nearest_fill", skipped="%d cells" % n_cells)
+            bk.emit(base, op="nearest_fill", skipped="%d cells" % n_cells)
             return
-        xyz, attrs = mv.DeviceArray((n_vox, 3), np.uint32), mv.DeviceArray((n_vox, 8), np.uint8)
-        mv._check(mv.lib().mvrt_svo_read_voxels(svo._h, xyz.ptr, attrs.ptr, None))
+        xyz, attrs = bk.snapshot(mv, svo)
         rebuild = lambda: svo.build_voxels(xyz, attrs, origin=origin, dps=dps, gridRes=res)
         filled = []
         a = measure("nearest_fill", lambda: filled.append(svo.fill_enclosed_nearest()), before=rebuild, stats=True)
         b = measure("plain_fill", lambda: filled.append(svo.fill_enclosed()), before=rebuild)
         assert set(filled) <= {n_cells}, (set(filled), n_cells)
         if a and b:
-            emit(op="fill_ratio", ratio=a / b, voxels_after=svo.info().numberOfVoxels, cells_left=svo.enclosed_cells_device()[0])
+            bk.emit(base, op="fill_ratio", ratio=a / b, voxels_after=svo.info().numberOfVoxels, cells_left=svo.enclosed_cells_device()[0])
+
+
+def line(r):
+    what = "%9.2f ms" % r["ms"] if "ms" in r else "x %.2f" % r["ratio"] if "ratio" in r else r.get("refused") or r.get("skipped") or r.get("failed")
+    return "%-7s %5s %-13s %10s voxels %11s cells %5s regions  %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("op", ""), r.get("voxels", ""), r.get("nCells", ""),
+                                                                      r.get("nRegions", ""), what)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="dragon:2048,tunnel:4096,dragon:1024")
+    ap.add_argument("--scenes", type=bk.parse_scenes, default="dragon:2048,tunnel:4096,dragon:1024")
     ap.add_argument("--ops", default="size,list,fill")
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--step-timeout", type=int, default=420)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
+    bk.add_step_args(ap, reps=5, warmup=1, step_timeout=420)
     args = ap.parse_args()
     if args.step:
         return step(args)
-    steps = [s + ":" + op for s in args.scenes.split(",") for op in args.ops.split(",")]
-    rows, rc = [], 0
-    for s in steps:
-        cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--step", s, "--reps", str(args.reps), "--warmup", str(args.warmup)]
-        print("step", s, flush=True)
-        out = subprocess.run(cmd, stdout=subprocess.PIPE)
-        for line in out.stdout.decode().splitlines():
-            if line.startswith("{"):
-                rows.append(json.loads(line))
-                print(line, flush=True)
-        if out.returncode != 0:
-            rows.append(dict(step=s, failed="no result within %d s" % args.step_timeout if out.returncode in (124, 137) else "exit status %d" % out.returncode))
-            rc = 1
-            break  # nothing more is started on the GPU behind a step that failed
-        if args.out:  # (kept up to date step by step)
-            with open(args.out, "w") as f:
-                json.dump(rows, f, indent=1)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(rows, f, indent=1)
-    for r in rows:
-        what = "%9.2f ms" % r["ms"] if "ms" in r else "x %.2f" % r["ratio"] if "ratio" in r else r.get("refused") or r.get("skipped") or r.get("failed")
-        print("%-7s %5s %-13s %10s voxels %11s cells %5s regions  %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("op", ""), r.get("voxels", ""), r.get("nCells", ""),
-                                                                        r.get("nRegions", ""), what), file=sys.stderr)
+    steps = ["%s:%d:%s" % (name, res, op) for name, res in args.scenes for op in args.ops.split(",")]
+    rows, rc = bk.run_steps(__file__, steps, lambda s: bk.flags(args, "reps", "warmup"), args.step_timeout, args.out)
+    bk.print_table(rows, line)
     return rc
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/fill_bench.py [--scenes dragon,tunnel] [--reps 10] [--warmup 2] [--step-timeout 360] [--out profiles/fill_bench.json] [--no-host-method]
+"""usage: tools/fill_bench.py [--scenes dragon[:grid],tunnel[:grid]] [--reps 10] [--warmup 2] [--step-timeout 360] [--out profiles/fill_bench.json] [--no-host-method]
 
 Cost of classifying and filling the enclosed empty cells on the procedural stand-ins (dragon 2048^3, tunnel 4096^3):
   count   mvrt_svo_enclosed_cells, the sizing call: linear keys + radix sort + unions + flatten + scan, counts back on the host
@@ -14,40 +14,13 @@ Once, on the dragon at --host-grid (default 1024, the largest power of two whose
 only route without this feature -- mvrt_svo_read_voxels + a dense host flood fill (scipy.ndimage.label where scipy is installed, else the numpy propagation
 of tests/fill_expected.py), next to the GPU's time for the same grid."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-GRID = {"dragon": 2048, "tunnel": 4096}
-
-
-def timed(mv, fn, reps, warmup, before=None):
-    ts = []
-    for i in range(warmup + reps):
-        if before:
-            before()
-        mv.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts)), ts
-
-
-def built(mv, name, res):
-    from massivevoxelraytracing_amd import scenes
-    verts, cols, emis = scenes.SCENES[name](1.0)
-    origin, dps = scenes.bounding_grid(verts, res)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build(verts, cols, emis, None, origin, dps, res)
-    return svo, origin, dps
+import benchkit as bk
 
 
 def host_flood_fill(xyz, res):
@@ -57,7 +30,7 @@ def host_flood_fill(xyz, res):
     try:
         from scipy import ndimage
     except ImportError:
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        sys.path.insert(0, os.path.join(bk.ROOT, "tests"))
         import fill_expected as F
         want = F.enclosed(xyz, res)
         return len(want["xyz"]), want["nRegions"], "numpy propagation"
@@ -77,101 +50,75 @@ def step(args):
     """one child process: prints one JSON row per measurement"""
     import massivevoxelraytracing_amd as mv
     mv.set_device(0)
-    name, op = args.step.split(":")
-    res = args.host_grid if op == "host" else GRID[name]
-    svo, origin, dps = built(mv, name, res)
+    name, res, op = args.step.split(":")
+    res = int(res)
+    svo, origin, dps = bk.built(mv, name, res)
     n_vox = svo.info().numberOfVoxels
     n_cells, n_regions = svo.enclosed_cells_device()
     base = dict(scene=name, grid=res, voxels=n_vox, nCells=n_cells, nRegions=n_regions)
 
-    def emit(**kw):
-        print(json.dumps(dict(kw, **base)), flush=True)
-
     if op == "cells":
-        ms, ts = timed(mv, svo.enclosed_cells_device, args.reps, args.warmup)
-        emit(op="count", ms=ms, all_ms=ts)
+        ms, ts = bk.timed(mv, svo.enclosed_cells_device, args.reps, args.warmup)
+        bk.emit(base, op="count", ms=ms, all_ms=ts)
         if n_cells == 0 or n_cells > args.max_cells:
             if n_cells >= 1 << 32:
                 try:
                     svo.enclosed_cells_device(n_cells, mv.DeviceArray(3, np.uint32), None)  # refused on the host, before anything is written
                 except mv.MvrtError as e:
-                    emit(op="list", refused=str(e))
+                    bk.emit(base, op="list", refused=str(e))
                     return
-            emit(op="list", skipped="no cells" if n_cells == 0 else "%d cells exceed --max-cells %d" % (n_cells, args.max_cells))
+            bk.emit(base, op="list", skipped="no cells" if n_cells == 0 else "%d cells exceed --max-cells %d" % (n_cells, args.max_cells))
             return
         xyz, region = mv.DeviceArray((n_cells, 3), np.uint32), mv.DeviceArray(n_cells, np.uint32)
-        ms, ts = timed(mv, lambda: svo.enclosed_cells_device(n_cells, xyz, region), args.reps, args.warmup)
-        emit(op="list", ms=ms, all_ms=ts, cells_per_s=n_cells / (ms * 1e-3))
+        ms, ts = bk.timed(mv, lambda: svo.enclosed_cells_device(n_cells, xyz, region), args.reps, args.warmup)
+        bk.emit(base, op="list", ms=ms, all_ms=ts, cells_per_s=n_cells / (ms * 1e-3))
     elif op == "fill":
         if n_cells == 0 or n_cells > args.max_cells:
             if n_cells + n_vox >= (1 << 32) - 1:
                 try:
                     svo.fill_enclosed()
                 except mv.MvrtError as e:
-                    emit(op="fill", refused=str(e))
+                    bk.emit(base, op="fill", refused=str(e))
                     return
-            emit(op="fill", skipped="no cells" if n_cells == 0 else "%d cells exceed --max-cells %d" % (n_cells, args.max_cells))
+            bk.emit(base, op="fill", skipped="no cells" if n_cells == 0 else "%d cells exceed --max-cells %d" % (n_cells, args.max_cells))
             return
-        xyz, attrs = mv.DeviceArray((n_vox, 3), np.uint32), mv.DeviceArray((n_vox, 8), np.uint8)
-        mv._check(mv.lib().mvrt_svo_read_voxels(svo._h, xyz.ptr, attrs.ptr, None))
+        xyz, attrs = bk.snapshot(mv, svo)
         filled = []
-        ms, ts = timed(mv, lambda: filled.append(svo.fill_enclosed()), args.reps, args.warmup,
+        ms, ts = bk.timed(mv, lambda: filled.append(svo.fill_enclosed()), args.reps, args.warmup,
                        before=lambda: svo.build_voxels(xyz, attrs, origin=origin, dps=dps, gridRes=res))
         assert set(filled) == {n_cells}, (set(filled), n_cells)
-        emit(op="fill", ms=ms, all_ms=ts, voxels_after=svo.info().numberOfVoxels, cells_left=svo.enclosed_cells_device()[0])
+        bk.emit(base, op="fill", ms=ms, all_ms=ts, voxels_after=svo.info().numberOfVoxels, cells_left=svo.enclosed_cells_device()[0])
     elif op == "host":
-        ms, ts = timed(mv, svo.enclosed_cells_device, args.reps, args.warmup)
-        emit(op="count", ms=ms, all_ms=ts)
+        ms, ts = bk.timed(mv, svo.enclosed_cells_device, args.reps, args.warmup)
+        bk.emit(base, op="count", ms=ms, all_ms=ts)
         t0 = time.perf_counter()
         xyz, _ = svo.read_voxels()
         cells, regions, method = host_flood_fill(xyz, res)
-        emit(op="host_flood_fill", ms=(time.perf_counter() - t0) * 1e3, method=method, host_cells=cells, host_regions=regions,
+        bk.emit(base, op="host_flood_fill", ms=(time.perf_counter() - t0) * 1e3, method=method, host_cells=cells, host_regions=regions,
              equal_to_gpu=bool((cells, regions) == (n_cells, n_regions)))
+
+
+def line(r):
+    what = "%9.2f ms" % r["ms"] if "ms" in r else r.get("refused") or r.get("skipped") or r.get("failed")
+    return "%-7s %5s %-16s %10s voxels %11s cells %7s regions  %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("op", ""), r.get("voxels", ""), r.get("nCells", ""),
+                                                                      r.get("nRegions", ""), what)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="dragon,tunnel")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--step-timeout", type=int, default=360)
+    ap.add_argument("--scenes", type=bk.parse_scenes, default="dragon,tunnel")
     ap.add_argument("--max-cells", type=int, default=1 << 30)
     ap.add_argument("--host-grid", type=int, default=1024)
-    ap.add_argument("--out", default=None)
     ap.add_argument("--no-host-method", action="store_true")
-    ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
+    bk.add_step_args(ap, reps=10, warmup=2, step_timeout=360)
     args = ap.parse_args()
     if args.step:
         return step(args)
-    steps = [s + ":" + op for s in args.scenes.split(",") for op in ("cells", "fill")]
-    if "dragon" in args.scenes.split(",") and not args.no_host_method:
-        steps.append("dragon:host")
-    rows, rc = [], 0
-    for s in steps:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", s, "--reps", str(args.reps), "--warmup", str(args.warmup), "--max-cells", str(args.max_cells),
-               "--host-grid", str(args.host_grid)]
-        print("step", s, flush=True)
-        try:
-            out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=args.step_timeout)
-        except subprocess.TimeoutExpired:
-            rows.append(dict(step=s, failed="no result within %d s" % args.step_timeout))
-            rc = 1
-            break
-        for line in out.stdout.decode().splitlines():
-            if line.startswith("{"):
-                rows.append(json.loads(line))
-                print(line, flush=True)
-        if out.returncode != 0:
-            rows.append(dict(step=s, failed="exit status %d" % out.returncode))
-            rc = 1
-            break  # nothing more is started on the GPU behind a step that failed
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(rows, f, indent=1)
-    for r in rows:
-        what = "%9.2f ms" % r["ms"] if "ms" in r else r.get("refused") or r.get("skipped") or r.get("failed")
-        print("%-7s %5s %-16s %10s voxels %11s cells %7s regions  %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("op", ""), r.get("voxels", ""), r.get("nCells", ""),
-                                                                        r.get("nRegions", ""), what), file=sys.stderr)
+    steps = ["%s:%d:%s" % (name, res, op) for name, res in args.scenes for op in ("cells", "fill")]
+    if "dragon" in [name for name, _ in args.scenes] and not args.no_host_method:
+        steps.append("dragon:%d:host" % args.host_grid)
+    rows, rc = bk.run_steps(__file__, steps, lambda s: bk.flags(args, "reps", "warmup", "max_cells"), args.step_timeout, args.out)
+    bk.print_table(rows, line)
     return rc
 
 

@@ -12,35 +12,19 @@ started on the GPU) and what was measured up to there is still written.  Per gri
   render         mvrt_render_primary (the streaming kernel) and mvrt_render_primary_lod at the same scales, voxel colours
 Median of --reps calls after --warmup calls (mvrt_svo_lod_prepare included), host clock between device synchronisations."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchkit as bk
 
 W, H = 1920, 1080
 SCALES = (0.0, 0.5, 1.0, 2.0)
 STEPS = ("pyramid", "yardstick", "cone", "render")
 MAXF = np.float32(3.402823466e38)
 f32 = np.float32
-
-
-def timed(mv, fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        mv.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        mv.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts)), ts
 
 
 def pixel_rays(cam):
@@ -74,7 +58,7 @@ def build_dragon(mv, res):
 
 def step_pyramid(mv, args, res):
     svo, _, base, build_ms = build_dragon(mv, res)
-    ms, ts = timed(mv, lambda: svo.lod_prepare(), args.reps, args.warmup)
+    ms, ts = bk.timed_async(mv, lambda: svo.lod_prepare(), args.reps, args.warmup)
     return [dict(op="lod_prepare", ms=ms, all_ms=ts, lod_bytes=svo.lod_bytes(), traversal_bytes=int(svo.traversal_bytes()), voxel_list_bytes=base["voxels"] * 16,
                  build_ms=build_ms, **base)]
 
@@ -88,7 +72,7 @@ def step_rays(mv, args, res, which):
     inf = mv.DeviceArray.from_host(np.full(n, np.inf, np.float32))
     yardstick = lambda: svo.intersect_range_device(n, *dev, None, inf, t, nm, None, de)
     if which == "yardstick":
-        ms, ts = timed(mv, yardstick, args.reps, args.warmup)
+        ms, ts = bk.timed_async(mv, yardstick, args.reps, args.warmup)
         return [dict(op="trace_batch_range", tMax="+inf", ms=ms, all_ms=ts, descents_per_ray=float(de.to_host().mean()), hits=int((t.to_host() != MAXF).sum()), **base)]
     yardstick()
     mv.synchronize()
@@ -98,7 +82,7 @@ def step_rays(mv, args, res, which):
     for scale in SCALES:
         cone_b = f32(scale) * ((f32(2.0) * f32(cam[12])) / f32(H))
         db = mv.DeviceArray.from_host(np.full(n, cone_b, np.float32))
-        ms, ts = timed(mv, lambda: svo.intersect_cone_device(n, *dev, zero, db, t, nm, lv, None, None, None, de), args.reps, args.warmup)
+        ms, ts = bk.timed_async(mv, lambda: svo.intersect_cone_device(n, *dev, zero, db, t, nm, lv, None, None, None, de), args.reps, args.warmup)
         got_t, got_de, got_lv = t.to_host(), de.to_host(), lv.to_host()
         rows.append(dict(op="trace_batch_cone", lodScale=scale, ms=ms, all_ms=ts, descents_per_ray=float(got_de.mean()), descents_per_ray_unlimited=float(yard_de.mean()),
                          hits=int((got_t != MAXF).sum()), level_histogram=np.bincount(got_lv, minlength=base["levels"] + 1).tolist(),
@@ -111,7 +95,7 @@ def step_render(mv, args, res):
     svo, cam, base, _ = build_dragon(mv, res)
     svo.lod_prepare()
     rgba = mv.DeviceArray((W * H, 4), np.uint8)
-    ms, ts = timed(mv, lambda: svo.render_device(cam, W, H, True, rgba), args.reps, args.warmup)
+    ms, ts = bk.timed_async(mv, lambda: svo.render_device(cam, W, H, True, rgba), args.reps, args.warmup)
     rows = [dict(op="render_primary", ms=ms, all_ms=ts, **base)]
     lib = mv.lib()
     cam32 = np.ascontiguousarray(cam, np.float32)
@@ -119,46 +103,29 @@ def step_render(mv, args, res):
         def render():
             if lib.mvrt_render_primary_lod(svo._h, cam32.ctypes.data, W, H, float(scale), 1, rgba.ptr, None, None, None, None, None) != 0:
                 raise RuntimeError(lib.mvrt_last_error().decode())
-        ms, ts = timed(mv, render, args.reps, args.warmup)
+        ms, ts = bk.timed_async(mv, render, args.reps, args.warmup)
         rows.append(dict(op="render_primary_lod", lodScale=scale, ms=ms, all_ms=ts, **base))
     return rows
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lod_cone_bench.json"))
     ap.add_argument("--grids", default="2048,8192")
     ap.add_argument("--steps", default=",".join(STEPS))
-    ap.add_argument("--step-timeout", type=int, default=240)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    bk.add_step_args(ap, reps=5, warmup=1, step_timeout=240, out=os.path.join(bk.ROOT, "profiles", "lod_cone_bench.json"))
     args = ap.parse_args()
-    if args.child:
+    if args.step:
         import massivevoxelraytracing_amd as mv
         mv.set_device(0)
-        step, res = args.child.split(":")
-        rows = step_pyramid(mv, args, int(res)) if step == "pyramid" else step_render(mv, args, int(res)) if step == "render" else step_rays(mv, args, int(res), step)
-        print("ROWS " + json.dumps(rows), flush=True)
+        step, res = args.step.split(":")
+        for row in step_pyramid(mv, args, int(res)) if step == "pyramid" else step_render(mv, args, int(res)) if step == "render" else step_rays(mv, args, int(res), step):
+            bk.emit(row)
         return 0
-    rows, status = [], 0
-    for grid, step in [(g, s) for g in args.grids.split(",") for s in args.steps.split(",")]:
+    for step in args.steps.split(","):
         if step not in STEPS:
             ap.error("unknown step " + step)
-        cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--child", step + ":" + grid, "--reps", str(args.reps),
-               "--warmup", str(args.warmup)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        got = [json.loads(line[5:]) for line in r.stdout.splitlines() if line.startswith("ROWS ")]
-        if r.returncode != 0 or not got:
-            print("step %s of grid %s failed with status %d; stopping here\n%s" % (step, grid, r.returncode, r.stderr[-2000:]), file=sys.stderr)
-            status = 1
-            break
-        for row in got[0]:
-            rows.append(row)
-            print(json.dumps({k: v for k, v in row.items() if k != "all_ms"}), flush=True)
-    with open(args.out, "w") as f:
-        json.dump(rows, f, indent=1)
-    return status
+    steps = [s + ":" + g for g in args.grids.split(",") for s in args.steps.split(",")]
+    return bk.run_steps(__file__, steps, lambda s: bk.flags(args, "reps", "warmup"), args.step_timeout, args.out, echo=bk.brief)[1]
 
 
 if __name__ == "__main__":

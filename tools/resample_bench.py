@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/resample_bench.py [--scenes dragon,tunnel] [--cases identity,turn90,turn30,magnify2] [--reps 5] [--warmup 1] [--host-reps 1] [--step-timeout 420]
+"""usage: tools/resample_bench.py [--scenes dragon[:grid],tunnel[:grid]] [--cases identity,turn90,turn30,magnify2] [--reps 5] [--warmup 1] [--host-reps 1] [--step-timeout 420]
                                   [--out profiles/resample_bench.json]
 
 Cost of the resampling calls on the procedural stand-ins (dragon 2048^3, tunnel 4096^3), per scene and case:
@@ -20,29 +20,15 @@ Every step runs in a child process of its own under --step-timeout seconds; a st
 started on the GPU behind it."""
 import argparse
 import itertools
-import json
 import os
-import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchkit as bk
 
-GRID = {"dragon": 2048, "tunnel": 4096}
 CASES = ("identity", "turn90", "turn30", "magnify2")
 F = 24
-
-
-def built(mv, name, res):
-    from massivevoxelraytracing_amd import scenes
-    verts, cols, emis = scenes.SCENES[name](1.0)
-    origin, dps = scenes.bounding_grid(verts, res)
-    svo = mv.IntersectorOctreeGPU()
-    svo.build(verts, cols, emis, None, origin, dps, res)
-    return svo, origin, dps
 
 
 def rotation(axis, degrees):
@@ -94,38 +80,23 @@ def step(args):
     """one child process: prints one JSON row per measurement"""
     import massivevoxelraytracing_amd as mv
     mv.set_device(0)
-    name, case = args.step.split(":")
-    rd = GRID[name]
+    name, rd, case = args.step.split(":")
+    rd = int(rd)
     rs = rd // 2 if case == "magnify2" else rd
-    src, origin, dps = built(mv, name, rs)
+    src, origin, dps = bk.built(mv, name, rs)
     dps = np.float32(dps * np.float32(rs / rd))  # the same box on the destination grid (exact: a power of two)
     m, t = transform(case, rs, rd)
     xf = mv.CellTransform.make(m, t)
     dst = mv.IntersectorOctreeGPU()
     base = dict(scene=name, case=case, src_grid=rs, grid=rd, voxels=src.info().numberOfVoxels, lib=os.path.basename(mv.LIB_PATH))
 
-    def emit(**kw):
-        print(json.dumps(dict(base, **kw)), flush=True)
+    def measure(label, fn, reps=args.reps, warmup=args.warmup):
+        return bk.timed_or_refused(mv, base, label, fn, reps, warmup)
 
-    def timed(label, fn, reps=args.reps, warmup=args.warmup, **kw):
-        ts, result = [], None
-        for i in range(warmup + reps):
-            mv.synchronize()
-            t0 = time.perf_counter()
-            try:
-                result = fn()
-            except mv.MvrtError as err:
-                emit(op=label, refused=str(err), **kw)
-                return None
-            if i >= warmup:
-                ts.append((time.perf_counter() - t0) * 1e3)
-        emit(op=label, ms=float(np.median(ts)), all_ms=ts, result=result, **kw)
-        return result
-
-    n = timed("resample_count", lambda: src.resample_voxels_device(xf, rd))
+    n = measure("resample_count", lambda: src.resample_voxels_device(xf, rd))
     if n:
         xyz, at, so = mv.DeviceArray((n, 3), np.uint32), mv.DeviceArray((n, 8), np.uint8), mv.DeviceArray(n, np.uint32)
-        timed("resample_list", lambda: src.resample_voxels_device(xf, rd, n, xyz, at, so))
+        measure("resample_list", lambda: src.resample_voxels_device(xf, rd, n, xyz, at, so))
         del xyz, at, so
     peaks = []
 
@@ -136,54 +107,33 @@ def step(args):
         peaks.append(mv.peak_bytes() - held)
         return int(dst.info().numberOfVoxels)
 
-    got = timed("resample", call)
+    got = measure("resample", call)
     if got is not None:
-        emit(op="resample_stats", frontier=mv.resample_stats()["frontier"], peak_bytes=int(max(peaks)), result=got)
+        bk.emit(base, op="resample_stats", frontier=mv.resample_stats()["frontier"], peak_bytes=int(max(peaks)), result=got)
     twin = mv.IntersectorOctreeGPU()
-    host = timed("host_route", lambda: host_route(src, twin, m, t, rd, origin, dps), reps=args.host_reps, warmup=0)
+    host = measure("host_route", lambda: host_route(src, twin, m, t, rd, origin, dps), reps=args.host_reps, warmup=0)
     if host is not None and got is not None:
-        emit(op="host_route_check", agrees=bool(host == got), result=host)
+        bk.emit(base, op="host_route_check", agrees=bool(host == got), result=host)
+
+
+def line(r):
+    what = "%9.2f ms" % r["ms"] if "ms" in r else r.get("refused") or r.get("failed") or ""
+    return "%-7s %5s %-9s %-16s %10s voxels  %s  -> %s %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("case", ""), r.get("op", ""), r.get("voxels", ""), what,
+                                                              r.get("result", ""), r.get("frontier", ""))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="dragon,tunnel")
+    ap.add_argument("--scenes", type=bk.parse_scenes, default="dragon,tunnel")
     ap.add_argument("--cases", default=",".join(CASES))
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-reps", type=int, default=1)
-    ap.add_argument("--step-timeout", type=int, default=420)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
+    bk.add_step_args(ap, reps=5, warmup=1, step_timeout=420)
     args = ap.parse_args()
     if args.step:
         return step(args)
-    steps = [":".join((s, c)) for s in args.scenes.split(",") for c in args.cases.split(",")]
-    rows, rc = [], 0
-    for s in steps:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", s, "--reps", str(args.reps), "--warmup", str(args.warmup), "--host-reps", str(args.host_reps)]
-        print("step", s, flush=True)
-        try:
-            out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=args.step_timeout)
-        except subprocess.TimeoutExpired:
-            rows.append(dict(step=s, failed="no result within %d s" % args.step_timeout))
-            rc = 1
-            break
-        for line in out.stdout.decode().splitlines():
-            if line.startswith("{"):
-                rows.append(json.loads(line))
-                print(line, flush=True)
-        if out.returncode != 0:
-            rows.append(dict(step=s, failed="exit status %d" % out.returncode))
-            rc = 1
-            break  # nothing more is started on the GPU behind a step that failed
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(rows, f, indent=1)
-    for r in rows:
-        what = "%9.2f ms" % r["ms"] if "ms" in r else r.get("refused") or r.get("failed") or ""
-        print("%-7s %5s %-9s %-16s %10s voxels  %s  -> %s %s" % (r.get("scene", r.get("step")), r.get("grid", ""), r.get("case", ""), r.get("op", ""), r.get("voxels", ""), what,
-                                                                r.get("result", ""), r.get("frontier", "")), file=sys.stderr)
+    steps = ["%s:%d:%s" % (name, res, c) for name, res in args.scenes for c in args.cases.split(",")]
+    rows, rc = bk.run_steps(__file__, steps, lambda s: bk.flags(args, "reps", "warmup", "host_reps"), args.step_timeout, args.out)
+    bk.print_table(rows, line)
     return rc
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/surface_bench.py [--scenes dragon,tunnel] [--reps 10] [--warmup 2] [--out profiles/surface_bench.json] [--no-host-method]
+"""usage: tools/surface_bench.py [--scenes dragon[:grid],tunnel[:grid]] [--reps 10] [--warmup 2] [--out profiles/surface_bench.json] [--no-host-method]
 
 Cost of extracting the voxel surface on the procedural stand-ins (dragon 2048^3, tunnel 4096^3):
   masks   mvrt_svo_surface_masks into a device array (16 B read + 1 B written per voxel)
@@ -14,32 +14,16 @@ Once, on the dragon: the only route without this feature -- mvrt_svo_read_voxels
 voxel in the sorted codes), here with numpy searchsorted on all cores numpy uses, masks only."""
 import argparse
 import json
-import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import massivevoxelraytracing_amd as mv  # noqa: E402
-from massivevoxelraytracing_amd import scenes  # noqa: E402
+import benchkit as bk
+import massivevoxelraytracing_amd as mv
 
-GRID = {"dragon": 2048, "tunnel": 4096}
 HBM_PEAK = 8.0e12
 DIRS = ((1, -1), (1, +1), (2, -1), (0, +1), (2, +1), (0, -1))
-
-
-def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        mv.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts)), ts
 
 
 def morton(xyz):
@@ -70,7 +54,7 @@ def host_method(svo, res):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="dragon,tunnel")
+    ap.add_argument("--scenes", type=bk.parse_scenes, default="dragon,tunnel")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
@@ -83,27 +67,26 @@ def main():
         rows.append(kw)
         print(json.dumps(kw), flush=True)
 
-    for name in args.scenes.split(","):
-        res = GRID[name]
-        verts, cols, emis = scenes.SCENES[name](1.0)
-        origin, dps = scenes.bounding_grid(verts, res)
-        svo = mv.IntersectorOctreeGPU()
-        svo.build(verts, cols, emis, None, origin, dps, res)
+    def clock(fn):  # warm-ups first, then synchronize() and the clock around each blocking call
+        return bk.timed(mv, fn, args.reps, args.warmup, warmup_first=True)
+
+    for name, res in args.scenes:
+        svo, _, _ = bk.built(mv, name, res)
         n_vox = svo.info().numberOfVoxels
         n_faces, n_vertices = svo.surface_mesh_device()
         base = dict(scene=name, grid=res, voxels=n_vox, nFaces=n_faces, nVertices=n_vertices)
         masks = mv.DeviceArray(n_vox, np.uint8)
-        ms, ts = timed(lambda: svo.surface_masks_device(masks), args.reps, args.warmup)
+        ms, ts = clock(lambda: svo.surface_masks_device(masks))
         rate = n_vox * 17 / (ms * 1e-3)
         emit(op="masks", ms=ms, all_ms=ts, bytes=n_vox * 17, bytes_per_s=rate, of_hbm_peak=rate / HBM_PEAK, **base)
         fv, fd = mv.DeviceArray(n_faces, np.uint32), mv.DeviceArray(n_faces, np.uint8)
         pos = mv.DeviceArray((n_faces, 12), np.float32)
-        ms, ts = timed(lambda: svo.surface_quads_device(n_faces, fv, fd, pos), args.reps, args.warmup)
+        ms, ts = clock(lambda: svo.surface_quads_device(n_faces, fv, fd, pos))
         rate = n_faces * 53 / (ms * 1e-3)
         emit(op="quads", ms=ms, all_ms=ts, bytes=n_faces * 53, bytes_per_s=rate, of_hbm_peak=rate / HBM_PEAK, **base)
         del pos
         idx, vtx = mv.DeviceArray((n_faces, 4), np.uint32), mv.DeviceArray((n_vertices, 3), np.float32)
-        ms, ts = timed(lambda: svo.surface_mesh_device(n_faces, n_vertices, fv, fd, idx, vtx), args.reps, args.warmup)
+        ms, ts = clock(lambda: svo.surface_mesh_device(n_faces, n_vertices, fv, fd, idx, vtx))
         emit(op="mesh", ms=ms, all_ms=ts, **base)
         del idx, vtx, fv, fd
         for flags in (0, mv.SURFACE_MERGE_ANY_ATTRIBUTE, mv.SURFACE_MERGE_WELD, mv.SURFACE_MERGE_ANY_ATTRIBUTE | mv.SURFACE_MERGE_WELD):
@@ -112,7 +95,7 @@ def main():
             rv, rd, rs = mv.DeviceArray(n_rects, np.uint32), mv.DeviceArray(n_rects, np.uint8), mv.DeviceArray((n_rects, 2), np.uint32)
             pos = None if weld else mv.DeviceArray((n_rects, 12), np.float32)
             idx, vtx = (mv.DeviceArray((n_rects, 4), np.uint32), mv.DeviceArray((n_welded, 3), np.float32)) if weld else (None, None)
-            ms, ts = timed(lambda: svo.surface_merged_device(flags, n_rects, n_welded, rv, rd, rs, pos, idx, vtx), args.reps, args.warmup)
+            ms, ts = clock(lambda: svo.surface_merged_device(flags, n_rects, n_welded, rv, rd, rs, pos, idx, vtx))
             emit(op="merged", flags=flags, any_attribute=bool(flags & mv.SURFACE_MERGE_ANY_ATTRIBUTE), weld=weld, nRects=n_rects, nMergedVertices=n_welded,
                  rects_per_face=n_rects / max(n_faces, 1), ms=ms, all_ms=ts, **base)
             del rv, rd, rs, pos, idx, vtx

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/upload_walk_bench.py [--scenes dragon,rtcamp] [--reps 10] [--warmup 2] [--no-pt] [--kernel-stats DIR] [--out profiles/upload_walk_bench.json]
+"""usage: tools/upload_walk_bench.py [--scenes dragon[:grid],rtcamp[:grid]] [--reps 10] [--warmup 2] [--no-pt] [--kernel-stats DIR] [--out profiles/upload_walk_bench.json]
 
 Cost of walking an uploaded octree (mvrt_svo_walk_voxels, mvrt_svo_rebuild) on the two uploads DESIGN.md 5.6 measures: the dragon stand-in's 2048^3 DAG and
 the rtcamp stand-in's 4096^3 DAG, each built on the GPU, downloaded and uploaded again (an upload keeps no Morton codes, so it is walked from the root).
@@ -25,26 +25,12 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import massivevoxelraytracing_amd as mv  # noqa: E402
-from massivevoxelraytracing_amd import scenes  # noqa: E402
+import benchkit as bk
+import massivevoxelraytracing_amd as mv
+from massivevoxelraytracing_amd import scenes
 
-GRID = {"dragon": 2048, "rtcamp": 4096}
+UPLOADS = dict(dragon=2048, rtcamp=4096)
 HBM_PEAK = 8.0e12
-
-
-def timed(fn, reps, warmup, before=None):
-    ts = []
-    for i in range(warmup + reps):
-        if before:
-            before()
-        mv.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts)), ts
 
 
 def last_emit_stats(directory):
@@ -62,7 +48,7 @@ def pt_before_after(nodes, attrs, info, reps, frames=4, frame_steps=4):
     pt = mv.PathTracer()
     pt.setup(None)
     pt.resizeFrameBufferIfNeeded(None, W, H)
-    hdr = os.path.join(ROOT, "tests", "golden", "monks_forest_s.hdr")
+    hdr = os.path.join(bk.ROOT, "tests", "golden", "monks_forest_s.hdr")
     pt.loadHDRI(None, hdr, hdr)
     svo = pt.m_intersectorOctreeGPU
     lo, hi = np.array(info.lower[:]), np.array(info.upper[:])
@@ -96,7 +82,7 @@ def pt_before_after(nodes, attrs, info, reps, frames=4, frame_steps=4):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="dragon,rtcamp")
+    ap.add_argument("--scenes", type=lambda text: bk.parse_scenes(text, UPLOADS), default="dragon,rtcamp")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pt-reps", type=int, default=3)
@@ -111,12 +97,8 @@ def main():
         rows.append(kw)
         print(json.dumps(kw), flush=True)
 
-    for name in args.scenes.split(","):
-        res = GRID[name]
-        verts, cols, emis = scenes.SCENES[name](1.0)
-        origin, dps = scenes.bounding_grid(verts, res)
-        built = mv.IntersectorOctreeGPU()
-        built.build(verts, cols, emis, None, origin, dps, res)
+    for name, res in args.scenes:
+        built, origin, dps = bk.built(mv, name, res)
         info = built.info()
         nodes, attrs, morton = built.download(want_morton=True)
         n_parents = int(np.unique(morton >> np.uint64(3)).size)
@@ -131,9 +113,9 @@ def main():
         def walk():
             up.walk_voxels_device(up.walk_voxels_device(), xyz, vi, at)
 
-        ms, ts = timed(walk, args.reps, args.warmup)
+        ms, ts = bk.timed(mv, walk, args.reps, args.warmup)
         emit(op="walk_voxels", ms=ms, all_ms=ts, **base)
-        ms, ts = timed(lambda: up.walk_voxels_device(), args.reps, args.warmup)
+        ms, ts = bk.timed(mv, lambda: up.walk_voxels_device(), args.reps, args.warmup)
         emit(op="walk_voxels_sizing_call", ms=ms, all_ms=ts, **base)
         b = n_parents * (16 + 8 + 64) + n * 12
         b_once = n_parents * (16 + 8) + min(n_parents, info.numberOfNodes) * 64 + n * 12
@@ -146,9 +128,9 @@ def main():
                            each_line_once_bytes_per_s=b_once / (ks["avg_us"] * 1e-6), each_line_once_of_hbm_peak=b_once / (ks["avg_us"] * 1e-6) / HBM_PEAK)
         emit(**row)
         target = mv.IntersectorOctreeGPU()
-        ms, ts = timed(lambda: target.rebuild(0), args.reps, args.warmup, before=lambda: target.upload(*args_up, embeddedMask=bool(info.embeddedMask)))
+        ms, ts = bk.timed(mv, lambda: target.rebuild(0), args.reps, args.warmup, before=lambda: target.upload(*args_up, embeddedMask=bool(info.embeddedMask)))
         emit(op="rebuild", ms=ms, all_ms=ts, **base)
-        ms, ts = timed(lambda: target.build_voxels(xyz, at, origin=origin, dps=dps, gridRes=res, flags=0), args.reps, args.warmup)
+        ms, ts = bk.timed(mv, lambda: target.build_voxels(xyz, at, origin=origin, dps=dps, gridRes=res, flags=0), args.reps, args.warmup)
         emit(op="build_voxels_of_the_walked_list", ms=ms, all_ms=ts, **base)
         del target, up, xyz, vi, at
         if name == "dragon" and not args.no_pt:

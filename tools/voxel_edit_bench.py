@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/voxel_edit_bench.py [--scenes dragon,tunnel] [--reps 10] [--warmup 2] [--out FILE]
+"""usage: tools/voxel_edit_bench.py [--scenes dragon[:grid],tunnel[:grid]] [--reps 10] [--warmup 2] [--out FILE]
 
 Cost of getting voxels into an octree and of changing them, on the procedural stand-ins (dragon 2048^3, tunnel 4096^3):
   rebuild      mvrt_svo_build from the triangles (voxelize + sort + unique + levels)
@@ -10,32 +10,15 @@ Median of --reps calls after --warmup calls; host clock around each call (every 
 device before the clock starts.  One JSON line per measurement, and a summary table on stderr."""
 import argparse
 import json
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import massivevoxelraytracing_amd as mv  # noqa: E402
-from massivevoxelraytracing_amd import scenes  # noqa: E402
+import benchkit as bk
+import massivevoxelraytracing_amd as mv
+from massivevoxelraytracing_amd import scenes
 
-GRID = {"dragon": 2048, "tunnel": 4096}
 SIZES = [1, 1000, 64000, 1000000]
-
-
-def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        mv.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        mv.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts)), ts
 
 
 def decode(m):
@@ -50,7 +33,7 @@ def decode(m):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default="dragon,tunnel")
+    ap.add_argument("--scenes", type=bk.parse_scenes, default="dragon,tunnel")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
@@ -62,19 +45,18 @@ def main():
         rows.append(kw)
         print(json.dumps(kw), flush=True)
 
-    for name in args.scenes.split(","):
-        res = GRID[name]
+    for name, res in args.scenes:
         verts, cols, emis = scenes.SCENES[name](1.0)
         origin, dps = scenes.bounding_grid(verts, res)
         svo = mv.IntersectorOctreeGPU()
-        ms, ts = timed(lambda: svo.build(verts, cols, emis, None, origin, dps, res), args.reps, args.warmup)
+        ms, ts = bk.timed_async(mv, lambda: svo.build(verts, cols, emis, None, origin, dps, res), args.reps, args.warmup)
         info = svo.info()
         n_vox = info.numberOfVoxels
         emit(scene=name, grid=res, op="rebuild", entries=int(info.totalDumpedVoxels), voxels=n_vox, nodes=info.numberOfNodes, ms=ms, all_ms=ts)
         xyz, attrs = svo.read_voxels()
         d_xyz, d_at = mv.DeviceArray.from_host(xyz), mv.DeviceArray.from_host(attrs)
         other = mv.IntersectorOctreeGPU()
-        ms, ts = timed(lambda: other.build_voxels(d_xyz, d_at, origin=origin, dps=dps, gridRes=res), args.reps, args.warmup)
+        ms, ts = bk.timed_async(mv, lambda: other.build_voxels(d_xyz, d_at, origin=origin, dps=dps, gridRes=res), args.reps, args.warmup)
         emit(scene=name, grid=res, op="build_voxels", entries=n_vox, voxels=other.info().numberOfVoxels, nodes=other.info().numberOfNodes, ms=ms, all_ms=ts)
         del other
         rng = np.random.default_rng(res)
@@ -100,7 +82,7 @@ def main():
                     svo.edit_voxels(b[0], b[1], b[2])
 
                 buf0 = svo.m_nodeBuffer
-                ms, ts = timed(call, args.reps, args.warmup)
+                ms, ts = bk.timed_async(mv, call, args.reps, args.warmup)
                 kept = svo.m_nodeBuffer == buf0
                 emit(scene=name, grid=res, op="edit_" + kind, entries=n, voxels=svo.info().numberOfVoxels, nodes=svo.info().numberOfNodes, nodes_kept=bool(kept), ms=ms,
                      all_ms=ts)
