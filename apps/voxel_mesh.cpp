@@ -7,7 +7,7 @@
 //              [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]
 //              [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]
 //              [--recolour-from other.obj [--recolour-max D] | --distance-to other.obj]
-//              [--ao [samples] [--ao-radius voxels]]
+//              [--ao [samples] [--ao-radius voxels]] [--smooth K [--smooth-limit L] [--smooth-taubin]]
 //
 // Default: shared vertices (mvrt_svo_surface_mesh).  --no-weld: four vertices of its own per face, like the reference's file (mvrt_svo_surface_quads);
 // the positions are the same bit patterns either way.  --merge: coplanar faces of equal attribute become rectangles (mvrt_svo_surface_merged); --merge-any:
@@ -53,6 +53,11 @@
 // --distance-to other.obj: a line reports, for both directions, the largest distance from a voxel of the one set to the other set (the one-sided Hausdorff
 // distance, mvrt_svo_nearest_between) as the root of the integer d2, the farthest voxel, the voxels at distance 0 and the voxel counts; the mesh is then written as
 // without the flag.  Only one of these two and --union / --intersect / --subtract / --xor; they run at the place of the combine, before --lod and what follows.
+// --smooth K: the welded mesh smoothed by K iterations of constrained surface nets (mvrt_svo_surface_smooth): the faces, indices and colours of the default
+// mesh, every vertex relaxed towards the mean of its edge neighbours inside a box of --smooth-limit L / 256 cell (L in [0, 128], default 127: no two vertices
+// can meet) around its lattice corner.  --smooth-taubin: the weights 128 / -136 of Taubin's non-shrinking pair instead of the plain 256 / 256.  The line of
+// counts also reports the clamped count.  With every flag --exterior and --fill combine with (--exterior through the masks argument) and with --ao, whose bake
+// stays per voxel face; not with --merge / --merge-any (merged rectangles have T-junctions) nor with --no-weld (unshared corners have no neighbours).
 // Grid placement: bounding box of the mesh, dps = longest side / gridRes (voxPTGPU.cpp:159-163).
 #include <algorithm>
 #include <cmath>
@@ -68,6 +73,8 @@ int main( int argc, char** argv )
 {
 	bool weld = true, conservative = false, merge = false, mergeAny = false, ao = false, fill = false, exterior = false, fillNearest = false, solid = false;
 	int aoSamples = 64;
+	bool smooth = false, smoothTaubin = false, smoothLimitGiven = false;
+	int smoothIterations = 0, smoothLimit = 127;
 	float aoRadiusVoxels = 8.0f;
 	int lod = 0;
 	unsigned long long lodMinCount = 1;
@@ -102,6 +109,17 @@ int main( int argc, char** argv )
 			if( i + 1 < argc && argv[i + 1][0] && std::strspn( argv[i + 1], "0123456789" ) == std::strlen( argv[i + 1] ) ) aoSamples = std::atoi( argv[++i] );
 		}
 		else if( !std::strcmp( argv[i], "--ao-radius" ) && i + 1 < argc ) aoRadiusVoxels = (float)std::atof( argv[++i] );
+		else if( !std::strcmp( argv[i], "--smooth" ) && i + 1 < argc )
+		{
+			smooth = true;
+			smoothIterations = std::atoi( argv[++i] );
+		}
+		else if( !std::strcmp( argv[i], "--smooth-limit" ) && i + 1 < argc )
+		{
+			smoothLimitGiven = true;
+			smoothLimit = std::atoi( argv[++i] );
+		}
+		else if( !std::strcmp( argv[i], "--smooth-taubin" ) ) smoothTaubin = true;
 		else if( !std::strcmp( argv[i], "--lod" ) && i + 1 < argc ) lod = std::atoi( argv[++i] );
 		else if( !std::strcmp( argv[i], "--lod-min-count" ) && i + 1 < argc ) lodMinCount = std::strtoull( argv[++i], nullptr, 10 );
 		else if( ( !std::strcmp( argv[i], "--dilate" ) || !std::strcmp( argv[i], "--erode" ) || !std::strcmp( argv[i], "--close" ) || !std::strcmp( argv[i], "--open" ) ) && i + 1 < argc )
@@ -184,7 +202,7 @@ int main( int argc, char** argv )
 					 "                  [--round-dilate RHO | --round-erode RHO | --round-close RHO | --round-open RHO]\n"
 					 "                  [--union | --intersect | --subtract | --xor other.obj [--rotate-b ax ay az deg] [--scale-b s] [--offset x y z] [--attrib-b]]\n"
 					 "                  [--recolour-from other.obj [--recolour-max D] | --distance-to other.obj]\n"
-					 "                  [--ao [samples] [--ao-radius voxels]]\n"
+					 "                  [--ao [samples] [--ao-radius voxels]] [--smooth K [--smooth-limit L] [--smooth-taubin]]\n"
 					 "  --union O, --intersect O, --subtract O, --xor O  combine the voxel set with that of a second model O.obj first, both voxelised on one grid\n"
 					 "               over their joint bounding box; --offset x y z moves the second set by whole cells, --attrib-b colours shared cells from it\n"
 					 "  --rotate-b ax ay az deg, --scale-b s  turn the second voxel set by deg degrees about the axis and scale it by s > 0, about the grid centre,\n"
@@ -207,6 +225,9 @@ int main( int argc, char** argv )
 					 "  --exterior   drop the faces that look into an enclosed cell instead; the octree stays as built.  Not with --fill\n"
 					 "  --ao         bake ambient occlusion into the face colours: samples rays per face (power of two <= 256, default 64) within\n"
 					 "               --ao-radius voxels (default 8); not with --merge / --merge-any\n"
+					 "  --smooth K   smooth the welded mesh by K iterations (0..256) of constrained surface nets: same faces and indices, every vertex kept within\n"
+					 "               --smooth-limit L / 256 cell (0..128, default 127) of its lattice corner; --smooth-taubin: the non-shrinking weights 128 / -136.\n"
+					 "               With --exterior, --fill and --ao; not with --merge / --merge-any or --no-weld\n"
 					 "  --no-weld    four vertices of its own per face instead of shared ones\n"
 					 "  --merge      merge coplanar faces of equal colour and emission into rectangles\n"
 					 "  --merge-any  merge whatever the attributes; a rectangle takes the colour of its anchor voxel\n" );
@@ -261,6 +282,17 @@ int main( int argc, char** argv )
 	if( ao && ( aoSamples < 1 || aoSamples > 256 || ( aoSamples & ( aoSamples - 1 ) ) != 0 || !( aoRadiusVoxels > 0.0f ) ) )
 	{
 		std::fprintf( stderr, "voxel_mesh: --ao needs a power of two in [1, 256] and --ao-radius a value above 0\n" );
+		return 2;
+	}
+	if( smooth && ( merge || !weld ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: --smooth cannot be combined with --merge / --merge-any (merged rectangles have T-junctions) or with --no-weld (unshared corners "
+							  "have no neighbours)\n" );
+		return 2;
+	}
+	if( ( ( smoothTaubin || smoothLimitGiven ) && !smooth ) || ( smooth && ( smoothIterations < 0 || smoothIterations > 256 || smoothLimit < 0 || smoothLimit > 128 ) ) )
+	{
+		std::fprintf( stderr, "voxel_mesh: --smooth K with K in [0, 256]; --smooth-limit L (L in [0, 128]) and --smooth-taubin need it\n" );
 		return 2;
 	}
 	const int gridRes = std::atoi( pos[1] );
@@ -421,7 +453,7 @@ int main( int argc, char** argv )
 	std::vector<float> points;
 	std::vector<uint32_t> indices, faceVoxel;
 	std::vector<uint8_t> faceDir;
-	uint64_t nFaces = 0;
+	uint64_t nFaces = 0, smoothClamped = 0;
 	std::vector<uint8_t> masks; // --exterior: the face set of every call below
 	if( exterior )
 	{
@@ -436,6 +468,14 @@ int main( int argc, char** argv )
 		std::vector<uint32_t> rectSize;
 		nFaces = exterior ? svo.surfaceMergedMasked( masks, mergeFlags, points, indices, faceVoxel, faceDir, rectSize, stream )
 						  : svo.surfaceMerged( mergeFlags, points, indices, faceVoxel, faceDir, rectSize, stream );
+	}
+	else if( smooth )
+	{
+		mvrt_smooth_params sp = mvrt::IntersectorOctreeGPU::smoothDefaultParams();
+		sp.iterations = smoothIterations;
+		sp.limit = smoothLimit;
+		if( smoothTaubin ) sp.weightEven = 128, sp.weightOdd = -136;
+		smoothClamped = exterior ? svo.surfaceSmooth( masks, sp, points, indices, faceVoxel, faceDir, stream ) : svo.surfaceSmooth( sp, points, indices, faceVoxel, faceDir, stream );
 	}
 	else if( weld )
 	{
@@ -483,6 +523,9 @@ int main( int argc, char** argv )
 	}
 	if( merge )
 		std::printf( "voxels %u faces %llu rects %zu vertices %zu -> %s\n", svo.m_numberOfVoxels, (unsigned long long)nFaces, faceVoxel.size(), points.size() / 3, pos[2] );
+	else if( smooth )
+		std::printf( "voxels %u faces %zu vertices %zu smooth %d weights %d %d limit %d clamped %llu -> %s\n", svo.m_numberOfVoxels, faceVoxel.size(), points.size() / 3,
+					 smoothIterations, smoothTaubin ? 128 : 256, smoothTaubin ? -136 : 256, smoothLimit, (unsigned long long)smoothClamped, pos[2] );
 	else
 		std::printf( "voxels %u faces %zu vertices %zu -> %s\n", svo.m_numberOfVoxels, faceVoxel.size(), points.size() / 3, pos[2] );
 	return 0;

@@ -567,6 +567,51 @@ int mvrt_svo_surface_merged_masked( const mvrt_svo* svo, const uint8_t* masksDev
 									uint8_t* rectDirDev, uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut,
 									uint64_t* nRectsOut, uint64_t* nVerticesOut, void* stream );
 
+/* The welded mesh smoothed by constrained surface nets (Gibson; new, the reference has none): the dual mesh of a binary voxel set has exactly the vertices and
+ * quads of mvrt_svo_surface_mesh, only the vertex positions change.  Each vertex relaxes towards the mean of its edge neighbours and never leaves a box around
+ * the lattice corner it came from.  Defined in integers, so the result is unique and independent of any schedule; one conversion to float at the end.
+ *   - Mesh: the faces, their order, faceVoxel, faceDir, the welded vertices, their order (ascending corner key) and indices are exactly those of
+ *     mvrt_svo_surface_mesh; with masksDev != NULL those of mvrt_svo_surface_mesh_masked for the same masks.  Only vertex positions differ.
+ *   - Corner: vertex i has the integer lattice corner c_i in [0, gridRes]^3, decoded from its key.
+ *   - Neighbours: N(i) = the vertices joined to i by an edge of at least one listed face: corners k and (k +- 1) mod 4 of the same quad.  Two such corners
+ *     differ by +-1 on exactly one axis, so N(i) has at most 6 members, one per slot; the slots are the bits of the per-vertex neighbour mask: bit 0 = -x,
+ *     1 = +x, 2 = -y, 3 = +y, 4 = -z, 5 = +z; bits 6-7 are 0.  n_i = |N(i)| >= 2.  u_ij = c_j - c_i, a signed unit vector.  The definition goes through the
+ *     face list, not through occupancy: it holds for caller-supplied and exterior masks as well; a face listed from both sides adds nothing new.
+ *   - Displacement: d_i = 3 x int32 in steps of 1 / MVRT_SMOOTH_STEPS_PER_CELL cell, 0 at the start.
+ *   - Iteration k = 0, 1, ..., a Jacobi step (every vertex reads the d of iteration k - 1), per axis in exact integers:
+ *       T_i = sum over j in N(i) of ( 256 u_ij + d_j ) - n_i d_i
+ *       delta_i = rdiv( w_k T_i, 256 n_i ),  rdiv( a, b ) = sign( a ) * floor( ( 2|a| + b ) / ( 2 b ) ) for b > 0: nearest, ties away from zero, so that
+ *       mirrored sets give mirrored meshes;  w_k = weightEven for even k, weightOdd for odd k
+ *       d_i <- clamp( d_i + delta_i, -limit, +limit )
+ *     Every axis of every vertex whose d_i + delta_i lay outside [-limit, limit] adds 1 to the call's clamped count, summed over all iterations.
+ *     |w T| stays below 2^20.
+ *   - Parameters: iterations 0..256 (default 4); weightEven, weightOdd -256..256 (256, 256: the plain Laplacian step; 128, -136 is Taubin's non-shrinking
+ *     pair); limit 0..128 (127; 128 is half a cell); the reserved words must be 0.  A value outside its range and a non-zero reserved word are refused on
+ *     the host, the message naming the field.  With limit <= 127 all vertices have distinct positions in fixed point: no two vertices meet, no quad
+ *     collapses (at 128 the eight vertices of a lone voxel meet in its centre).
+ *   - Position, per axis: q = 256 c + d (int32, at most 2^29 + 128); t = (float)q * 0.00390625f (the conversion rounds once, the scaling is exact);
+ *     p = lower + t * dps, multiply and add each rounded to fp32, no FMA.  For d = 0, t == (float)c: iterations = 0 returns the bits of mvrt_svo_surface_mesh.
+ * The rules of mvrt_svo_surface_mesh hold word for word: every octree this library built or edited is accepted, in every flavour; an upload ("keeps no Morton
+ * codes") and an empty handle ("no octree") are refused before any GPU work; the handle is never modified; the call blocks; any output pointer may be NULL; all
+ * arrays NULL is the sizing call, which runs no iteration (*clampedOut = 0); a capacity below the count is an error, the counts are still returned and NOTHING
+ * is written; 4 * nFaces >= 2^32 is refused, naming the count; gridRes up to 2^21; a failed scratch allocation returns an error, leaves the octree whole and
+ * leaks nothing.  displacementsDev and neighboursDev follow vertexCapacity. */
+#define MVRT_SMOOTH_STEPS_PER_CELL 256
+typedef struct mvrt_smooth_params
+{
+	int32_t iterations;	  /* 0..256, default 4 */
+	int32_t weightEven;	  /* -256..256, default 256 */
+	int32_t weightOdd;	  /* -256..256, default 256 */
+	int32_t limit;		  /* 0..128, default 127 */
+	uint32_t reserved[4]; /* 0 */
+} mvrt_smooth_params;
+/* Fills *p with the defaults above */
+int mvrt_smooth_default_params( mvrt_smooth_params* p );
+int mvrt_svo_surface_smooth( const mvrt_svo* svo, const uint8_t* masksDev /* NULL: the masks of mvrt_svo_surface_masks */,
+							 const mvrt_smooth_params* params /* NULL: the defaults */, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev,
+							 uint32_t* indicesDev /* 4 per face */, float* verticesDev /* 3 per vertex */, int32_t* displacementsDev /* 3 per vertex */,
+							 uint8_t* neighboursDev /* 1 per vertex */, uint64_t* nFacesOut, uint64_t* nVerticesOut, uint64_t* clampedOut, void* stream );
+
 /* Adopt an SVO built elsewhere (e.g. IntersectorOctree::buildDAGReference on the CPU, IntersectorOctree.hpp:
  * 224-231): nodes in the reference's 68-byte layout, root last.  embeddedMask = 0 selects the variant where
  * the mask is fetched from the node (voxCommon.hpp:353-356; required above 0xFFFFFF nodes). */

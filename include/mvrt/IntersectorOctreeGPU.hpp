@@ -586,6 +586,37 @@ struct IntersectorOctreeGPU
 		aoToHost( [&]( const auto&... a ) { return surfaceQuadsMasked( (const uint8_t*)m.p, a..., stream ); }, samples, radius, faceVoxel, faceDir, open, stream );
 	}
 
+	// the welded mesh smoothed by constrained surface nets (mvrt_svo_surface_smooth; the rule is in mvrt.h): the faces, indices and vertex order of surfaceMesh (of
+	// surfaceMeshMasked for masksDev != nullptr), the vertices relaxed inside a box around their lattice corners.  params nullptr = smoothDefaultParams().
+	// Device-pointer form: any output may be nullptr, all nullptr = the sizing call, which runs no iteration; displacementsDev (3 int32 per vertex, steps of
+	// 1 / 256 cell) and neighboursDev (1 byte per vertex) follow vertexCapacity.  *clamped: the axes an iteration held at the limit, over all iterations
+	static mvrt_smooth_params smoothDefaultParams()
+	{
+		mvrt_smooth_params p;
+		check( mvrt_smooth_default_params( &p ), "IntersectorOctreeGPU::smoothDefaultParams" );
+		return p;
+	}
+	void surfaceSmooth( const uint8_t* masksDev, const mvrt_smooth_params* params, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev,
+						uint32_t* indicesDev, float* verticesDev, int32_t* displacementsDev, uint8_t* neighboursDev, uint64_t* nFaces, uint64_t* nVertices, uint64_t* clamped,
+						void* stream ) const
+	{
+		check( mvrt_svo_surface_smooth( m_handle, masksDev, params, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, displacementsDev, neighboursDev,
+										nFaces, nVertices, clamped, stream ),
+			   "IntersectorOctreeGPU::surfaceSmooth" );
+	}
+	// host-vector forms, like surfaceMesh; returns the clamped count.  `masks`: numberOfVoxels bytes, the faces to smooth (surfaceMeshMasked)
+	uint64_t surfaceSmooth( const mvrt_smooth_params& params, std::vector<float>& vertices /* 3 per vertex */, std::vector<uint32_t>& indices /* 4 per face */,
+							std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, void* stream ) const
+	{
+		return smoothToHost( nullptr, params, vertices, indices, faceVoxel, faceDir, stream );
+	}
+	uint64_t surfaceSmooth( const std::vector<uint8_t>& masks, const mvrt_smooth_params& params, std::vector<float>& vertices /* 3 per vertex */,
+							std::vector<uint32_t>& indices /* 4 per face */, std::vector<uint32_t>& faceVoxel, std::vector<uint8_t>& faceDir, void* stream ) const
+	{
+		Staged m( masks.data(), masks.size(), stream );
+		return smoothToHost( (const uint8_t*)m.p, params, vertices, indices, faceVoxel, faceDir, stream );
+	}
+
 	// batch form of the device method intersect() (:243-251): SoA device arrays
 	void intersect( uint64_t n, const float* rox, const float* roy, const float* roz, const float* rdx, const float* rdy, const float* rdz, const uint8_t* isShadowRay, float* t,
 					int32_t* nMajor, uint32_t* vIndex, void* stream ) const
@@ -752,6 +783,15 @@ private:
 		Out<uint8_t> d( faceDir, nf, stream );
 		mesh( nf, nv, v, d, i, x, &nf, &nv );
 		fetch( stream, x, i, v, d );
+	}
+	uint64_t smoothToHost( const uint8_t* masksDev, const mvrt_smooth_params& params, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& faceVoxel,
+						   std::vector<uint8_t>& faceDir, void* stream ) const
+	{
+		uint64_t clamped = 0;
+		meshToHost( [&]( uint64_t fc, uint64_t vc, uint32_t* v, uint8_t* d, uint32_t* i, float* x, uint64_t* nf, uint64_t* nv ) {
+			surfaceSmooth( masksDev, &params, fc, vc, v, d, i, x, nullptr, nullptr, nf, nv, &clamped, stream );
+		}, vertices, indices, faceVoxel, faceDir, stream );
+		return clamped;
 	}
 	template <class Merged>
 	uint64_t mergedToHost( Merged merged, uint32_t flags, std::vector<float>& vertices, std::vector<uint32_t>& indices, std::vector<uint32_t>& rectVoxel, std::vector<uint8_t>& rectDir,

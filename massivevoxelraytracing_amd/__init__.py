@@ -54,6 +54,11 @@ class DenoiseParams(C.Structure):
                 ("albedoFloor", _f32), ("flags", _u32), ("reserved", _u32 * 2)]
 
 
+class SmoothParams(C.Structure):
+    """mvrt_smooth_params (include/mvrt.h)"""
+    _fields_ = [("iterations", C.c_int32), ("weightEven", C.c_int32), ("weightOdd", C.c_int32), ("limit", C.c_int32), ("reserved", _u32 * 4)]
+
+
 class CellTransform(C.Structure):
     """mvrt_cell_transform (include/mvrt.h): the inverse map, destination cell space to source cell space, m row-major in Q24 and t in Q25.
     CellTransform.make(m, t) takes 9 and 3 Python ints as they are; from_cells(A, b) rounds a real 3x3 matrix and translation in cell units."""
@@ -125,6 +130,8 @@ SIGNATURES = {
     "mvrt_svo_surface_quads_masked": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_mesh_masked": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_surface_merged_masked": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvrt_smooth_default_params": (_i32, [_vp]),
+    "mvrt_svo_surface_smooth": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_enclosed_cells": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "mvrt_svo_fill_enclosed": (_i32, [_vp, _vp, _vp, _vp]),
     "mvrt_svo_enclosed_nearest": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -875,6 +882,31 @@ class IntersectorOctreeGPU:
         if weld:
             out.update(vertices=vtx.to_host(), indices=idx.to_host())
         return out
+
+    def surface_smooth_device(self, params=None, face_capacity=0, vertex_capacity=0, faceVoxel=None, faceDir=None, indices=None, vertices=None, displacements=None,
+                              neighbours=None, stream=None, *, masks=None):
+        """mvrt_svo_surface_smooth into caller device arrays (any may be None; all None = the sizing call, which runs no iteration); returns
+        (nFaces, nVertices, clamped).  params: a SmoothParams (None = the defaults); masks: the faces of the given masks (surface_quads_device).
+        On MvrtError nothing was written."""
+        m = None if masks is None else self._given_masks(masks)
+        args = (_dev_ptr(m), None if params is None else C.byref(params), int(face_capacity), int(vertex_capacity)) + tuple(
+            _dev_ptr(a) for a in (faceVoxel, faceDir, indices, vertices, displacements, neighbours))
+        return self._counts(lib().mvrt_svo_surface_smooth, args, 3, stream)
+
+    def surface_smooth(self, iterations=4, weights=(256, 256), limit=127, stream=None, *, masks=None):
+        """the mesh of surface_mesh smoothed by constrained surface nets: {vertices (m, 3) float32, indices (n, 4) uint32, faceVoxel (n,), faceDir (n,),
+        displacements (m, 3) int32 in steps of 1/256 cell, neighbours (m,) uint8 (bit 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z), clamped}.  weights: (even, odd)
+        iterations, 256 = the plain Laplacian step, (128, -136) Taubin's pair; limit <= 127 keeps all vertices apart.  masks: as surface_mesh"""
+        p = SmoothParams()
+        _check(lib().mvrt_smooth_default_params(C.byref(p)))
+        p.iterations, p.weightEven, p.weightOdd, p.limit = int(iterations), int(weights[0]), int(weights[1]), int(limit)
+        masks = None if masks is None else self._given_masks(masks)
+        nf, nv, _ = self.surface_smooth_device(p, stream=stream, masks=masks)
+        fv, fd, idx, vtx = DeviceArray(nf, np.uint32), DeviceArray(nf, np.uint8), DeviceArray((nf, 4), np.uint32), DeviceArray((nv, 3), np.float32)
+        disp, nbr = DeviceArray((nv, 3), np.int32), DeviceArray(nv, np.uint8)
+        _, _, clamped = self.surface_smooth_device(p, nf, nv, fv, fd, idx, vtx, disp, nbr, stream, masks=masks)
+        return {"vertices": vtx.to_host(), "indices": idx.to_host(), "faceVoxel": fv.to_host(), "faceDir": fd.to_host(), "displacements": disp.to_host(),
+                "neighbours": nbr.to_host(), "clamped": clamped}
 
     def upload(self, nodes68, attribs, origin, dps, gridRes, hasEmission=0, embeddedMask=True, stream=None):
         nodes68 = np.ascontiguousarray(nodes68)

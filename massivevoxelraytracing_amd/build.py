@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("MVRT_LIB_OUT", os.path.join(HERE, "libmvrt_hip.so"))
-SOURCES = ["api.hip", "api_voxels.hip", "api_pt.hip", "kernels_list.hip", "kernels_rt.hip", "kernels_setup.hip", "svo_build.hip", "kernels_denoise.hip", "kernels_surface.hip", "kernels_walk.hip", "kernels_range.hip", "kernels_lod.hip", "kernels_fill.hip", "kernels_coarsen.hip", "kernels_morph.hip", "kernels_components.hip", "kernels_combine.hip", "kernels_ball.hip", "kernels_resample.hip", "kernels_nearest.hip", "kernels_query.hip"]
+SOURCES = ["api.hip", "api_voxels.hip", "api_pt.hip", "kernels_list.hip", "kernels_rt.hip", "kernels_setup.hip", "svo_build.hip", "kernels_denoise.hip", "kernels_surface.hip", "kernels_smooth.hip", "kernels_walk.hip", "kernels_range.hip", "kernels_lod.hip", "kernels_fill.hip", "kernels_coarsen.hip", "kernels_morph.hip", "kernels_components.hip", "kernels_combine.hip", "kernels_ball.hip", "kernels_resample.hip", "kernels_nearest.hip", "kernels_query.hip"]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
     "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden",

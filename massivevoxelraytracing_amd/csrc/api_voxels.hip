@@ -96,6 +96,37 @@ MVRT_EXPORT int mvrt_svo_surface_merged_masked( const mvrt_svo* svo, const uint8
 						  nVerticesOut, (hipStream_t)stream );
 }
 
+// Constrained surface nets (kernels_smooth.hip).  The parameters are looked at before the handle: a bad field is named whatever the handle holds.
+MVRT_EXPORT int mvrt_smooth_default_params( mvrt_smooth_params* p )
+{
+	REQUIRE( p, "mvrt_smooth_default_params: null argument" );
+	memset( p, 0, sizeof( *p ) );
+	p->iterations = 4;
+	p->weightEven = p->weightOdd = 256;
+	p->limit = 127;
+	return 0;
+}
+MVRT_EXPORT int mvrt_svo_surface_smooth( const mvrt_svo* svo, const uint8_t* masksDev, const mvrt_smooth_params* params, uint64_t faceCapacity, uint64_t vertexCapacity,
+										 uint32_t* faceVoxelDev, uint8_t* faceDirDev, uint32_t* indicesDev, float* verticesDev, int32_t* displacementsDev, uint8_t* neighboursDev,
+										 uint64_t* nFacesOut, uint64_t* nVerticesOut, uint64_t* clampedOut, void* stream )
+{
+	const char* who = "mvrt_svo_surface_smooth";
+	mvrt_smooth_params p;
+	mvrt_smooth_default_params( &p );
+	if( params ) p = *params;
+	REQUIRE( svo, "%s: null handle", who );
+	REQUIRE( p.iterations >= 0 && p.iterations <= 256, "%s: iterations %d outside 0..256", who, p.iterations );
+	REQUIRE( p.weightEven >= -256 && p.weightEven <= 256, "%s: weightEven %d outside -256..256", who, p.weightEven );
+	REQUIRE( p.weightOdd >= -256 && p.weightOdd <= 256, "%s: weightOdd %d outside -256..256", who, p.weightOdd );
+	REQUIRE( p.limit >= 0 && p.limit <= 128, "%s: limit %d outside 0..128", who, p.limit );
+	for( int k = 0; k < 4; k++ ) REQUIRE( p.reserved[k] == 0, "%s: reserved[%d] is 0x%x, not 0", who, k, p.reserved[k] );
+	SurfaceSource s;
+	if( surfaceSource( svo, who, &s ) ) return 1;
+	const SmoothRule rule = { p.iterations, p.weightEven, p.weightOdd, p.limit };
+	return surfaceSmooth( s, masksDev, rule, faceCapacity, vertexCapacity, faceVoxelDev, faceDirDev, indicesDev, verticesDev, displacementsDev, neighboursDev, nFacesOut, nVerticesOut,
+						  clampedOut, (hipStream_t)stream );
+}
+
 // Enclosed empty cells and the fill (kernels_fill.hip).  The listing reads the sorted codes alone, like the surface calls.  The fill hands the cells, which stay on
 // the device, to the edit's own route (editHandle, api.hip): what it leaves is what mvrt_svo_edit_voxels leaves, by construction.
 MVRT_EXPORT int mvrt_svo_enclosed_cells( const mvrt_svo* svo, uint64_t capacity, uint32_t* xyzDev, uint32_t* regionDev, uint64_t* nCellsOut, uint64_t* nRegionsOut, void* stream )

@@ -7,7 +7,7 @@
 //           the masks alone, never occupancy.
 //   faces   exclusive scan of the popcounts (64-bit offsets), then the run expansion of voxel_passes.h: one workgroup per 256 voxels emits that group's faces,
 //           one thread per face, so a wave writes 64 consecutive records.
-//   weld    corner keys, then the Weld record: radix sort of (key, face * 4 + k), head flags, inclusive scan = rank + 1; scatter of the ranks and decode of the heads.
+//   weld    corner keys, then the SurfaceWeld record: radix sort of (key, face * 4 + k), head flags, inclusive scan = rank + 1; scatter of the ranks and decode of the heads.
 //
 // The codec, the searches and the host steps (exclusiveOffsets, sortPairsInto, rankHeads) are those of mvrt_common.h and voxel_passes.h; the four
 // corners of a quad are emitQuadCorners here, for the unit faces and for the merged rectangles.
@@ -15,6 +15,7 @@
 // Directions, corners and windings are the reference's (voxMesh.cpp:172-200); positions are lower + (float)c * dps, one multiply and one add, each rounded
 // (this file is compiled without contraction like every other).
 #include "launch.h"
+#include "surface_weld.h"
 #include "voxel_passes.h"
 
 #define SB 256 // threads per workgroup, and voxels per workgroup of the emit kernel
@@ -111,18 +112,7 @@ struct PopcountOf // scan input: faces of voxel i
 	__host__ __device__ uint64_t operator()( uint8_t m ) const { return popcount8( m ); }
 };
 
-// corner number -> offset (the reference's numbering): 0 (0,0,0) 1 (1,0,0) 2 (1,0,1) 3 (0,0,1) 4 (0,1,0) 5 (1,1,0) 6 (1,1,1) 7 (0,1,1)
-MVRT_DI uint32_t cornerX( uint32_t c ) { return ( 0x66u >> c ) & 1u; }
-MVRT_DI uint32_t cornerY( uint32_t c ) { return ( 0xF0u >> c ) & 1u; }
-MVRT_DI uint32_t cornerZ( uint32_t c ) { return ( 0xCCu >> c ) & 1u; }
-// face d, corner k -> corner number: -Y 3,2,1,0  +Y 4,5,6,7  -Z 0,1,5,4  +X 1,2,6,5  +Z 2,3,7,6  -X 3,0,4,7 (three bits each, corner 0 lowest)
-MVRT_DI uint32_t faceCorner( uint32_t d, uint32_t k )
-{
-	const uint64_t lo = 03u | 02u << 3 | 01u << 6 | 00u << 9 | ( 04ull | 05u << 3 | 06u << 6 | 07u << 9 ) << 12 | ( 00ull | 01u << 3 | 05u << 6 | 04u << 9 ) << 24;
-	const uint64_t hi = 01u | 02u << 3 | 06u << 6 | 05u << 9 | ( 02ull | 03u << 3 | 07u << 6 | 06u << 9 ) << 12 | ( 03ull | 00u << 3 | 04u << 6 | 07u << 9 ) << 24;
-	return (uint32_t)( ( d < 3u ? lo >> ( 12u * d ) : hi >> ( 12u * ( d - 3u ) ) ) >> ( 3u * k ) ) & 7u;
-}
-
+// (the corner tables cornerX / cornerY / cornerZ / faceCorner: surface_weld.h)
 // The four corners of quad f: direction d at voxel (x, y, z), a corner offset counting sx / sy / sz voxels on its axis (1, 1, 1: a unit face).  positions (12 floats
 // per quad) and keys / vals (the weld's corner keys and f * 4 + k) may each be null.
 template <bool V4>
@@ -213,8 +203,10 @@ __global__ void __launch_bounds__( SB ) kSurfaceWeld( const uint64_t* __restrict
 		vertices[(uint64_t)r * 3 + 2] = lower.z + (float)cz * dps;
 	}
 }
+} // namespace
 
-int launchEmit( const SurfaceSource& s, const uint8_t* masks, const uint64_t* offs, uint32_t* faceVoxel, uint8_t* faceDir, float* positions, uint64_t* keys, uint32_t* vals,
+// ---- the host steps that kernels_smooth.hip shares (surface_weld.h) -------------------------------------------------------------------------------------------
+int surfaceLaunchEmit( const SurfaceSource& s, const uint8_t* masks, const uint64_t* offs, uint32_t* faceVoxel, uint8_t* faceDir, float* positions, uint64_t* keys, uint32_t* vals,
 				hipStream_t st )
 {
 	const dim3 grid( divUp( s.nVoxels, SB ) );
@@ -228,7 +220,7 @@ int launchEmit( const SurfaceSource& s, const uint8_t* masks, const uint64_t* of
 }
 
 // the masks kernel into `masks` (null = count only), or a caller's `given` masks copied there, and the sum of the popcounts, on the host when this returns
-int masksAndCount( const SurfaceSource& s, const uint8_t* given, uint8_t* masks, uint64_t* nFaces, hipStream_t st )
+static int masksAndCount( const SurfaceSource& s, const uint8_t* given, uint8_t* masks, uint64_t* nFaces, hipStream_t st )
 {
 	Counters cnt;
 	if( cnt.init( 1, st ) ) return 1;
@@ -244,27 +236,21 @@ int masksAndCount( const SurfaceSource& s, const uint8_t* given, uint8_t* masks,
 	return 0;
 }
 // the same into scratch of n + 1 bytes, the last one 0 so that the scan below yields offs[n]
-int scratchMasksAndCount( const SurfaceSource& s, const uint8_t* given, DevBuf& masks, uint64_t* nFaces, hipStream_t st )
+int surfaceScratchMasks( const SurfaceSource& s, const uint8_t* given, DevBuf& masks, uint64_t* nFaces, hipStream_t st )
 {
 	if( masks.alloc( (uint64_t)s.nVoxels + 1 ) ) return 1;
 	MVRT_HIP( hipMemsetAsync( masks.as<uint8_t>() + s.nVoxels, 0, 1, st ) );
 	return masksAndCount( s, given, masks.as<uint8_t>(), nFaces, st );
 }
-int scanOffsets( const SurfaceSource& s, const DevBuf& masks, DevBuf& offs, hipStream_t st )
+int surfaceScanOffsets( const SurfaceSource& s, const DevBuf& masks, DevBuf& offs, hipStream_t st )
 {
 	hipcub::TransformInputIterator<uint64_t, PopcountOf, const uint8_t*> in( masks.as<uint8_t>(), PopcountOf() );
 	return exclusiveOffsets<uint64_t>( in, (uint64_t)s.nVoxels + 1, offs, nullptr, st );
 }
 
-// The weld of a list of quads (unit faces or merged rectangles): the corners sorted by key with their numbers (quad * 4 + k), rank + 1 of every sorted corner among
-// the distinct keys, and the two counts.  Left empty where there is no corner.
-struct Weld
-{
-	DevBuf keys, vals, rank1;
-	uint32_t nCorners = 0, nVertices = 0;
-};
+// (the weld of a list of quads, unit faces or merged rectangles: struct SurfaceWeld, surface_weld.h)
 // from the keys and numbers of nCorners >= 1 corners (keysA / valsA are released): radix sort, head flags, inclusive scan.  The counts are on the host when this returns
-int buildWeld( const SurfaceSource& s, DevBuf& keysA, DevBuf& valsA, uint32_t nCorners, Weld* w, hipStream_t st )
+int surfaceBuildWeld( const SurfaceSource& s, DevBuf& keysA, DevBuf& valsA, uint32_t nCorners, SurfaceWeld* w, hipStream_t st )
 {
 	int endBit = 3 * ( (int)s.levels + 1 ); // a key is below ( gridRes + 1 )^3 <= 2^( 3 * ( levels + 1 ) )
 	if( endBit > 64 ) endBit = 64;
@@ -274,7 +260,7 @@ int buildWeld( const SurfaceSource& s, DevBuf& keysA, DevBuf& valsA, uint32_t nC
 	return 0;
 }
 // indices[quad * 4 + k] and the vertices of a weld with corners; either may be null.  Not synchronised.
-int writeWeld( const SurfaceSource& s, const Weld& w, uint32_t* indicesDev, float* verticesDev, hipStream_t st )
+int surfaceWriteWeld( const SurfaceSource& s, const SurfaceWeld& w, uint32_t* indicesDev, float* verticesDev, hipStream_t st )
 {
 	if( !indicesDev && !verticesDev ) return 0;
 	hipLaunchKernelGGL( kSurfaceWeld, dim3( divUp( w.nCorners, SB ) ), dim3( SB ), 0, st, w.keys.as<uint64_t>(), w.vals.as<uint32_t>(), w.rank1.as<uint32_t>(), w.nCorners, s.lower,
@@ -282,7 +268,6 @@ int writeWeld( const SurfaceSource& s, const Weld& w, uint32_t* indicesDev, floa
 	MVRT_HIP( hipGetLastError() );
 	return 0;
 }
-} // namespace
 
 int launchSurfaceMasks( const SurfaceSource& s, uint8_t* masks, unsigned long long* nFacesDev, hipStream_t st )
 {
@@ -306,7 +291,7 @@ int surfaceQuads( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fa
 	const char* who = givenMasks ? "mvrt_svo_surface_quads_masked" : "mvrt_svo_surface_quads";
 	DevBuf masks, offs;
 	uint64_t nFaces = 0;
-	if( scratchMasksAndCount( s, givenMasks, masks, &nFaces, st ) ) return 1;
+	if( surfaceScratchMasks( s, givenMasks, masks, &nFaces, st ) ) return 1;
 	if( nFacesOut ) *nFacesOut = nFaces;
 	if( !faceVoxelDev && !faceDirDev && !positionsDev ) return 0; // the sizing call
 	if( faceCapacity < nFaces )
@@ -314,8 +299,8 @@ int surfaceQuads( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fa
 		listingRefusal( who, "faceCapacity", "faces of the surface", faceCapacity, nFaces );
 		return 1;
 	}
-	if( scanOffsets( s, masks, offs, st ) ) return 1;
-	if( launchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), faceVoxelDev, faceDirDev, positionsDev, nullptr, nullptr, st ) ) return 1;
+	if( surfaceScanOffsets( s, masks, offs, st ) ) return 1;
+	if( surfaceLaunchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), faceVoxelDev, faceDirDev, positionsDev, nullptr, nullptr, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }
@@ -326,7 +311,7 @@ int surfaceMesh( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fac
 	const char* who = givenMasks ? "mvrt_svo_surface_mesh_masked" : "mvrt_svo_surface_mesh";
 	DevBuf masks, offs;
 	uint64_t nFaces = 0;
-	if( scratchMasksAndCount( s, givenMasks, masks, &nFaces, st ) ) return 1;
+	if( surfaceScratchMasks( s, givenMasks, masks, &nFaces, st ) ) return 1;
 	if( nFacesOut ) *nFacesOut = nFaces;
 	if( nVerticesOut ) *nVerticesOut = 0;
 	if( 4ull * nFaces >= ( 1ull << 32 ) )
@@ -336,14 +321,14 @@ int surfaceMesh( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fac
 		return 1;
 	}
 	const uint32_t nCorners = (uint32_t)( 4ull * nFaces );
-	Weld weld;
+	SurfaceWeld weld;
 	if( nCorners )
 	{
-		if( scanOffsets( s, masks, offs, st ) ) return 1;
+		if( surfaceScanOffsets( s, masks, offs, st ) ) return 1;
 		DevBuf keysA, valsA;
 		if( keysA.alloc( (uint64_t)nCorners * 8 ) || valsA.alloc( (uint64_t)nCorners * 4 ) ) return 1;
-		if( launchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), nullptr, nullptr, nullptr, keysA.as<uint64_t>(), valsA.as<uint32_t>(), st ) ) return 1;
-		if( buildWeld( s, keysA, valsA, nCorners, &weld, st ) ) return 1;
+		if( surfaceLaunchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), nullptr, nullptr, nullptr, keysA.as<uint64_t>(), valsA.as<uint32_t>(), st ) ) return 1;
+		if( surfaceBuildWeld( s, keysA, valsA, nCorners, &weld, st ) ) return 1;
 	}
 	const uint32_t nVertices = weld.nVertices;
 	if( nVerticesOut ) *nVerticesOut = nVertices;
@@ -360,8 +345,8 @@ int surfaceMesh( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fac
 		return 1;
 	}
 	if( nCorners == 0 ) return 0;
-	if( ( faceVoxelDev || faceDirDev ) && launchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), faceVoxelDev, faceDirDev, nullptr, nullptr, nullptr, st ) ) return 1;
-	if( writeWeld( s, weld, indicesDev, verticesDev, st ) ) return 1;
+	if( ( faceVoxelDev || faceDirDev ) && surfaceLaunchEmit( s, masks.as<uint8_t>(), offs.as<uint64_t>(), faceVoxelDev, faceDirDev, nullptr, nullptr, nullptr, st ) ) return 1;
+	if( surfaceWriteWeld( s, weld, indicesDev, verticesDev, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }
@@ -602,7 +587,7 @@ int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t f
 	uint64_t nFaces = 0, nRects = 0;
 	{
 		DevBuf masks;
-		if( scratchMasksAndCount( s, givenMasks, masks, &nFaces, st ) ) return 1;
+		if( surfaceScratchMasks( s, givenMasks, masks, &nFaces, st ) ) return 1;
 		if( nFacesOut ) *nFacesOut = nFaces;
 		if( nRectsOut ) *nRectsOut = 0;
 		if( nVerticesOut ) *nVerticesOut = 0;
@@ -613,7 +598,7 @@ int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t f
 		}
 	}
 	if( nRectsOut ) *nRectsOut = nRects;
-	Weld weld;
+	SurfaceWeld weld;
 	if( welded )
 	{
 		if( 4ull * nRects >= ( 1ull << 32 ) )
@@ -629,7 +614,7 @@ int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t f
 			DevBuf keysA, valsA;
 			if( keysA.alloc( (uint64_t)nCorners * 8 ) || valsA.alloc( (uint64_t)nCorners * 4 ) ) return 1;
 			if( launchMergeEmit( s, rects, counts, nullptr, nullptr, nullptr, nullptr, keysA.as<uint64_t>(), valsA.as<uint32_t>(), st ) ) return 1;
-			if( buildWeld( s, keysA, valsA, nCorners, &weld, st ) ) return 1;
+			if( surfaceBuildWeld( s, keysA, valsA, nCorners, &weld, st ) ) return 1;
 		}
 		if( nVerticesOut ) *nVerticesOut = weld.nVertices;
 	}
@@ -648,7 +633,7 @@ int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t f
 	if( nRects == 0 ) return 0;
 	if( ( rectVoxelDev || rectDirDev || rectSizeDev || positionsDev ) && launchMergeEmit( s, rects, counts, rectVoxelDev, rectDirDev, rectSizeDev, positionsDev, nullptr, nullptr, st ) )
 		return 1;
-	if( writeWeld( s, weld, indicesDev, verticesDev, st ) ) return 1;
+	if( surfaceWriteWeld( s, weld, indicesDev, verticesDev, st ) ) return 1;
 	MVRT_HIP( hipStreamSynchronize( st ) ); // (the scratch is released on return)
 	return 0;
 }

@@ -193,6 +193,15 @@ int surfaceMesh( const SurfaceSource& s, const uint8_t* givenMasks, uint64_t fac
 int surfaceMerged( const SurfaceSource& s, const uint8_t* givenMasks, uint32_t flags, uint64_t rectCapacity, uint64_t vertexCapacity, uint32_t* rectVoxelDev, uint8_t* rectDirDev,
 				   uint32_t* rectSizeDev, float* positionsDev, uint32_t* indicesDev, float* verticesDev, uint64_t* nFacesOut, uint64_t* nRectsOut, uint64_t* nVerticesOut,
 				   hipStream_t stream );
+// constrained surface nets on the welded mesh (kernels_smooth.hip; mvrt_svo_surface_smooth): the mesh of surfaceMesh with relaxed vertex positions.  The rule's
+// ranges are checked by the caller; the sizing call runs no iteration
+struct SmoothRule
+{
+	int32_t iterations, weightEven, weightOdd, limit;
+};
+int surfaceSmooth( const SurfaceSource& s, const uint8_t* givenMasks, const SmoothRule& rule, uint64_t faceCapacity, uint64_t vertexCapacity, uint32_t* faceVoxelDev, uint8_t* faceDirDev,
+				   uint32_t* indicesDev, float* verticesDev, int32_t* displacementsDev, uint8_t* neighboursDev, uint64_t* nFacesOut, uint64_t* nVerticesOut, uint64_t* clampedOut,
+				   hipStream_t stream );
 
 // enclosed empty cells (kernels_fill.hip; mvrt_svo_enclosed_cells / mvrt_svo_fill_enclosed): only morton, nVoxels and levels of the source are read.  The calls
 // block, keep their scratch in DevBufs and write NOTHING to the caller's arrays unless they succeed.
