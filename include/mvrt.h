@@ -12,7 +12,8 @@
  *     IntersectorOctreeGPU.hpp:48-51.  The header-only C++ mirrors in include/mvrt/ (IntersectorOctreeGPU.hpp, PathTracer.hpp) keep the
  *     void signatures and abort() on a non-zero status.)
  *   - `stream` is a hipStream_t passed as void* (0 = default stream); calls are asynchronous on
- *     it unless stated otherwise, exactly like the reference (PathTracer.hpp:150-169).
+ *     it unless stated otherwise, exactly like the reference (PathTracer.hpp:150-169).  Streams created with hipStreamNonBlocking are supported: a
+ *     call returns only after its own scratch is no longer in use, and its outputs are ordered on `stream` (tests/test_gpu_stream_order.py).
  *   - "host" / "dev" in a parameter name says where the pointer must live.
  *   - vectors are 3 packed floats; matrices are 16 floats, column-major (glm).
  *   - camera = the 15 floats of CameraPinhole {m_o, m_front, m_up, m_right, m_tanHthetaY,

@@ -321,10 +321,11 @@ int adoptBuild( mvrt_svo* svo, SvoBuildResult& r, const float origin[3], float d
 	o.buildFlags = flags & ( MVRT_BUILD_NO_DAG | MVRT_BUILD_NO_EMBEDDED_MASK );
 	setBounds( o.info, origin, dps, gridRes );
 	svo->cleanUp();
+	// default stream from here on: every builder that hands over an SvoBuildResult has ended in hipStreamSynchronize( st ) (svo_build.hip), so the arrays are complete
 	MVRT_HIP( hipMemcpy( &o.rootMask, o.masks.as<uint8_t>() + ( o.nNodes - 1 ), 1, hipMemcpyDeviceToHost ) );
 	if( buildTopTable( o, nullptr ) ) return 1;
 	if( buildCellIndex( o, nullptr ) ) return 1;
-	MVRT_HIP( hipDeviceSynchronize() );
+	MVRT_HIP( hipDeviceSynchronize() ); // the derived tables stand before the call returns, whatever stream the caller traces on
 	svo->oct = std::move( o );
 	return 0;
 }
@@ -720,11 +721,11 @@ MVRT_EXPORT int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const fl
 		}
 	DevBuf in, sh, t, nm, vi, de;
 	if( in.alloc( n * 24 ) || t.alloc( n * 4 ) || nm.alloc( n * 4 ) || vi.alloc( n * 4 ) || de.alloc( n * 4 ) ) return 1;
-	MVRT_HIP( hipMemcpy( in.p, soa.data(), n * 24, hipMemcpyHostToDevice ) );
+	MVRT_HIP( hipMemcpy( in.p, soa.data(), n * 24, hipMemcpyHostToDevice ) ); // (no stream argument: default stream throughout, ended by the hipDeviceSynchronize below)
 	if( isShadowHost )
 	{
 		if( sh.alloc( n ) ) return 1;
-		MVRT_HIP( hipMemcpy( sh.p, isShadowHost, n, hipMemcpyHostToDevice ) );
+		MVRT_HIP( hipMemcpy( sh.p, isShadowHost, n, hipMemcpyHostToDevice ) ); // (default stream, as above)
 	}
 	const float* b = in.as<float>();
 	if( svo->ensureWorkspace( n ) ) return 1;
@@ -732,6 +733,7 @@ MVRT_EXPORT int mvrt_trace_batch_host( const mvrt_svo* svo, uint64_t n, const fl
 						  vi.as<uint32_t>(), de.as<uint32_t>(), 0 ) )
 		return 1;
 	MVRT_HIP( hipDeviceSynchronize() );
+	// default stream, the four downloads: behind the hipDeviceSynchronize above
 	MVRT_HIP( hipMemcpy( tHost, t.p, n * 4, hipMemcpyDeviceToHost ) );
 	if( nMajorHost ) MVRT_HIP( hipMemcpy( nMajorHost, nm.p, n * 4, hipMemcpyDeviceToHost ) );
 	if( vIndexHost ) MVRT_HIP( hipMemcpy( vIndexHost, vi.p, n * 4, hipMemcpyDeviceToHost ) );

@@ -467,7 +467,7 @@ MVRT_EXPORT int mvrt_pt_setup( mvrt_pt* pt, void* stream )
 MVRT_EXPORT int mvrt_pt_download_pmj( mvrt_pt* pt, float* tableHost )
 {
 	REQUIRE( pt && pt->pmj.p && tableHost, "mvrt_pt_download_pmj: call mvrt_pt_setup first" );
-	MVRT_HIP( hipMemcpy( tableHost, pt->pmj.p, pt->pmj.bytes, hipMemcpyDeviceToHost ) );
+	MVRT_HIP( hipMemcpy( tableHost, pt->pmj.p, pt->pmj.bytes, hipMemcpyDeviceToHost ) ); // (default stream: mvrt_pt_setup waited for its upload)
 	return 0;
 }
 
@@ -525,6 +525,7 @@ int mvrt_pt::allocWorkSlot( Slot& sl )
 	REQUIRE( carveWork( (uintptr_t)sl.work.p, cap, nBlocks, b ) == bytes, "internal: the work block was measured as %llu bytes and carved differently", (unsigned long long)bytes );
 	b.stats = statsBuf.as<unsigned long long>(); // shared by all slots (atomic tallies)
 	b.cap = cap;
+	// default stream: allocSlots drained every slot stream first, and the synchronous copy behind the memset on the same stream returns only after both
 	MVRT_HIP( hipMemset( b.liveCount, 0, 64 * 4 ) );
 	MVRT_HIP( hipMemcpy( (void*)b.selfDev, &b, sizeof( PtBuffers ), hipMemcpyHostToDevice ) );
 	if( aovs && sl.aovPart.alloc( cap / MVRT_SPP_PER_STEP * 2 * sizeof( float4 ) ) ) return 1; // a block of its own: the sizes above are those of a library without feature buffers
@@ -536,7 +537,7 @@ int mvrt_pt::allocSlots()
 	if( !statsBuf.p )
 	{
 		if( statsBuf.alloc( 64 * 8 ) ) return 1;
-		MVRT_HIP( hipMemset( statsBuf.p, 0, 64 * 8 ) );
+		MVRT_HIP( hipMemset( statsBuf.p, 0, 64 * 8 ) ); // (default stream: completed by the synchronous copy of the first allocWorkSlot below, before any slot stream runs)
 	}
 	if( !forkEv ) MVRT_HIP( hipEventCreateWithFlags( &forkEv, hipEventDisableTiming ) );
 	for( Slot& sl : slots ) sl.release(); // what is allocated now is about to be replaced: released first, allocated second
@@ -656,7 +657,7 @@ MVRT_EXPORT int mvrt_pt_load_hdri( mvrt_pt* pt, void* stream, const float* rgbaH
 	}
 	MVRT_HIP( hipStreamSynchronize( st ) ); // :313 (and satF64 is released on return)
 	double totals[7];
-	MVRT_HIP( hipMemcpy( totals, satF64.as<double>() + n, sizeof( totals ), hipMemcpyDeviceToHost ) );
+	MVRT_HIP( hipMemcpy( totals, satF64.as<double>() + n, sizeof( totals ), hipMemcpyDeviceToHost ) ); // (default stream: behind the hipStreamSynchronize( st ) above)
 	for( int i = 0; i < 7; i++ ) // a table without a total > 0 is all zeros and selects nothing (mvrt.h): the shade kernel tests this bit, not memory
 		if( !( totals[i] > 0.0 ) ) h.dev.zeroTables |= 1u << i;
 	h.dev.scale = pt->hdri.dev.scale;
@@ -685,7 +686,7 @@ MVRT_EXPORT int mvrt_rgbe_read_file( const char* file, float* rgbaHost, uint64_t
 MVRT_EXPORT int mvrt_pt_download_hdri_sat( mvrt_pt* pt, int which, uint32_t* satHost )
 {
 	REQUIRE( pt && which >= 0 && which < 7 && pt->hdri.sat[which].p, "no such HDRI table" );
-	MVRT_HIP( hipMemcpy( satHost, pt->hdri.sat[which].p, pt->hdri.sat[which].bytes, hipMemcpyDeviceToHost ) );
+	MVRT_HIP( hipMemcpy( satHost, pt->hdri.sat[which].p, pt->hdri.sat[which].bytes, hipMemcpyDeviceToHost ) ); // (default stream: mvrt_pt_load_hdri waited for its tables)
 	return 0;
 }
 MVRT_EXPORT int mvrt_pt_set_hdri_scale( mvrt_pt* pt, float scale )
@@ -848,7 +849,7 @@ static int allocCleared( std::initializer_list<DevBuf*> bufs, uint64_t bytes, co
 		if( b->alloc( bytes ) ) return 1;
 	hipError_t e = hipSuccess;
 	for( DevBuf* b : bufs )
-		if( e == hipSuccess ) e = hipMemset( b->p, 0, bytes );
+		if( e == hipSuccess ) e = hipMemset( b->p, 0, bytes ); // (default stream: setOption drained the slot streams; waited for by the hipStreamSynchronize( nullptr ) below)
 	if( e == hipSuccess ) e = hipStreamSynchronize( nullptr );
 	if( e == hipSuccess ) return 0;
 	mvrtSetError( "%s: clearing the %s failed: %s", who, what, hipGetErrorString( e ) );
@@ -1092,7 +1093,7 @@ MVRT_EXPORT int mvrt_pt_read_sample_radiance( mvrt_pt* pt, float* xyzHost, uint6
 	if( pt->drain() ) return 1;
 	const PtBuffers& b = pt->slots[pt->lastSlot].buf;
 	REQUIRE( b.Lsx && nSamples <= b.cap, "no such samples" );
-	MVRT_HIP( hipMemcpy( xyzHost, b.Lsx, nSamples * 4, hipMemcpyDeviceToHost ) );
+	MVRT_HIP( hipMemcpy( xyzHost, b.Lsx, nSamples * 4, hipMemcpyDeviceToHost ) ); // (default stream, the three copies: behind the drain above)
 	MVRT_HIP( hipMemcpy( xyzHost + nSamples, b.Lsy, nSamples * 4, hipMemcpyDeviceToHost ) );
 	MVRT_HIP( hipMemcpy( xyzHost + 2 * nSamples, b.Lsz, nSamples * 4, hipMemcpyDeviceToHost ) );
 	return 0;
@@ -1158,7 +1159,7 @@ MVRT_EXPORT int mvrt_pt_read_debug_stage( mvrt_pt* pt, int stage, uint32_t* task
 	if( pt->drain() ) return 1;
 	const mvrt_pt::Slot& sl = pt->slots[pt->lastSlot];
 	REQUIRE( sl.buf.dbgTasks, "debug capture was not enabled for the last pass" );
-	MVRT_HIP( hipMemcpy( survivorsOut, sl.buf.liveCount + stage + 1, 4, hipMemcpyDeviceToHost ) );
+	MVRT_HIP( hipMemcpy( survivorsOut, sl.buf.liveCount + stage + 1, 4, hipMemcpyDeviceToHost ) ); // (default stream, both copies: behind the drain above)
 	REQUIRE( *survivorsOut <= capacity && *survivorsOut <= sl.buf.cap, "tasksHost holds %llu entries, stage %d kept %u", (unsigned long long)capacity, stage, *survivorsOut );
 	if( tasksHost && *survivorsOut ) MVRT_HIP( hipMemcpy( tasksHost, sl.buf.dbgTasks + (uint64_t)stage * sl.buf.cap, (uint64_t)*survivorsOut * 4, hipMemcpyDeviceToHost ) );
 	return 0;
@@ -1180,6 +1181,7 @@ MVRT_EXPORT int mvrt_pt_set_profiling( mvrt_pt* pt, int enabled )
 // a diagnostic build's tallies behind the six of mvrt_pt_stats (tools/build_variant.sh util -DMVRT_UTIL_STATS), printed when MVRT_PRINT_UTIL is set
 static int printUtilStats( const unsigned long long* stats, unsigned long long rays )
 {
+	// default stream, the three copies: mvrt_pt_get_stats, the only caller, has drained the slot streams and waited for its `stream`
 	unsigned long long u[4];
 	MVRT_HIP( hipMemcpy( u, stats + 8, sizeof( u ), hipMemcpyDeviceToHost ) );
 	// u[0], u[1]: refill events and the lanes active right after them; u[2], u[3]: wave-iterations of the node-visit loop and
@@ -1200,7 +1202,12 @@ MVRT_EXPORT int mvrt_pt_reset_stats( mvrt_pt* pt )
 {
 	REQUIRE( pt, "null argument" );
 	if( pt->drain() ) return 1;
-	if( pt->statsBuf.p ) MVRT_HIP( hipMemset( pt->statsBuf.p, 0, 64 * 8 ) );
+	if( pt->statsBuf.p )
+	{
+		// default stream, behind the drain above; waited for, since the next step tallies on a non-blocking slot stream that does not wait for the default stream
+		MVRT_HIP( hipMemset( pt->statsBuf.p, 0, 64 * 8 ) );
+		MVRT_HIP( hipStreamSynchronize( nullptr ) );
+	}
 	pt->prof.collect();
 	pt->prof.ms[0] = pt->prof.ms[1] = pt->prof.ms[2] = 0.0;
 	pt->prof.traceLaunches = 0;
@@ -1215,7 +1222,7 @@ MVRT_EXPORT int mvrt_pt_get_stats( mvrt_pt* pt, void* stream, mvrt_pt_stats* out
 	if( pt->statsBuf.p )
 	{
 		unsigned long long s[6];
-		MVRT_HIP( hipMemcpy( s, pt->statsBuf.p, sizeof( s ), hipMemcpyDeviceToHost ) );
+		MVRT_HIP( hipMemcpy( s, pt->statsBuf.p, sizeof( s ), hipMemcpyDeviceToHost ) ); // (default stream: behind the drain and the wait for `stream` above)
 		out->rays = s[0];
 		out->shadowRays = s[1];
 		out->descents = s[2];

@@ -187,7 +187,7 @@ int surfaceAo( const mvrt_device_octree& view, const uint64_t* morton, uint64_t 
 	{
 		uint32_t v = 0;
 		uint8_t d = 0;
-		MVRT_HIP( hipMemcpy( &v, faceVoxel + bad, sizeof( v ), hipMemcpyDeviceToHost ) );
+		MVRT_HIP( hipMemcpy( &v, faceVoxel + bad, sizeof( v ), hipMemcpyDeviceToHost ) ); // (default stream, both: the caller's arrays, behind the hipStreamSynchronize( stream ) above)
 		MVRT_HIP( hipMemcpy( &d, faceDir + bad, sizeof( d ), hipMemcpyDeviceToHost ) );
 		mvrtSetError( "mvrt_svo_surface_ao: entry %llu is out of range (faceVoxel %u of %u voxels, faceDir %u of 6); nothing was written", bad, v, view.numberOfVoxels,
 					  (unsigned)d );

@@ -1435,14 +1435,14 @@ static int encodeVoxels( const char* who, const uint32_t* xyz, const uint32_t* a
 	if( bad[0] != ~0ull )
 	{
 		uint32_t c[3] = { 0, 0, 0 };
-		MVRT_HIP( hipMemcpy( c, xyz + bad[0] * 3, 12, hipMemcpyDeviceToHost ) );
+		MVRT_HIP( hipMemcpy( c, xyz + bad[0] * 3, 12, hipMemcpyDeviceToHost ) ); // (default stream: the caller's array, behind the hipStreamSynchronize( st ) above)
 		mvrtSetError( "%s: entry %llu (%u, %u, %u) lies outside the %d^3 grid", who, bad[0], c[0], c[1], c[2], gridRes );
 		return 1;
 	}
 	if( bad[1] != ~0ull )
 	{
 		uint8_t op = 0;
-		MVRT_HIP( hipMemcpy( &op, ops + bad[1], 1, hipMemcpyDeviceToHost ) );
+		MVRT_HIP( hipMemcpy( &op, ops + bad[1], 1, hipMemcpyDeviceToHost ) ); // (default stream: the caller's array, behind the hipStreamSynchronize( st ) above)
 		mvrtSetError( "%s: entry %llu has the unknown op %u (MVRT_VOXEL_REMOVE = 0, MVRT_VOXEL_SET = 1)", who, bad[1], (unsigned)op );
 		return 1;
 	}
